@@ -7,6 +7,12 @@ BASELINE config (default: config 3, the one the metric is quoted on): activation
 parameter groups (gaussian_pointcloud.py:331-378).  Inputs are resident in HBM before the timed region.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--cfg 3] [--P 500000] [--path fused|dropin] [--scaling strong|weak]
+                  [--dump-outputs DIR] [--full]
+
+A plain run is the headline figure alone: set-up, warm-up, the K timed steps, the outputs of the last step if --dump-outputs is given,
+the JSON line.  --full adds everything measured or checked beside it: the self checks, the other path and the op alone, per-kernel
+times and the roofline (with their rocprofv3 child passes), the CPU baseline, the knn / quadric timings, the all-in-view variant, the
+sustained and window figures, and at N > 1 the all-reduce cost and the replicas reference.
 
 N > 1: one rank per GPU over RCCL.  Under a launcher (torch.distributed.run sets WORLD_SIZE, which must equal --gpus) the process
 is one rank; started plainly as `python bench.py --gpus N`, the script launches its N ranks itself as a child job BEFORE anything
@@ -14,9 +20,9 @@ touches the GPU (launch_ranks) and exits with the child's code.  Default `--scal
 built, sharded by object id (dqo_harness.sharding.shard_scene), every rank owns its objects' Gaussians + Adam state and renders
 only the tiles its objects' masks touch; one iteration of the job = every shard stepped once, so value = steps / time whatever N
 is.  The job is defined per object (object gate + per-object masked loss), so N shards compute exactly what N = 1
-computes — asserted on every N > 1 run (config.n1_equivalence).  The only exchange is one packed all-reduce per iteration of the
-shards' loss sums (started asynchronously, off the compute stream's critical path).  `--scaling weak` keeps round 1's mode (an independent map of P Gaussians per rank).  After the timed
-loop every rank checks its result against the same shard run alone and the job exits non-zero on a mismatch.
+computes — asserted on every N > 1 run with --full (config.n1_equivalence).  The only exchange is one packed all-reduce per iteration of the
+shards' loss sums (started asynchronously, off the compute stream's critical path).  `--scaling weak` keeps round 1's mode (an independent map of P Gaussians per rank).  With --full,
+after the timed loop every rank checks its result against the same shard run alone and the job exits non-zero on a mismatch.
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -108,6 +114,13 @@ def parse():
                          "asynchronously beside it; the first execution of RCCL's init / all-reduce / stream semantics on a one-GPU box")
     ap.add_argument("--as-shard", default=None, metavar="R/N",
                     help="analysis on one GPU: run shard R of an N-rank strong-scaling job alone (no collective partner; not a scaling measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (see the module docstring); off: the --no-* switches "
+                         "above are all on and --sustained / --window are 0")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step handed its caller to DIR/<name>.npy (float32 / float64): the "
+                         "rasteriser's nine outputs, the loss and the parameters after that step's Adam update; per-Gaussian arrays as a "
+                         "fixed seeded sample of rows (rank 0's shard at N > 1)")
     return ap.parse_args()
 
 
@@ -281,6 +294,7 @@ def make_dropin_step(prob, device, loss_buf, optin=False, dqo_adam=False):
         loss_buf.reduce()  # the path's only exchange: ONE packed fp32 all-reduce
         return out
 
+    step.params = params  # (--dump-outputs: the parameters after the last step)
     return step
 
 
@@ -1234,8 +1248,42 @@ def pmc_valu(args, kernel_name, avg_launch_us):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ------------------------------------------------------------------------------------------------------------------
+OUTPUT_NAMES = ("render", "depth", "color_index_map", "depth_index_map", "color_hit_weight", "depth_hit_weight", "T_map", "n_touched", "radii")
+DUMP_ROWS = 65536  # per-Gaussian arrays: this many rows, drawn from a fixed seed (at 1200x680: 16 MB of the 50 MB written)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, out, params, loss):
+    """What the timed path handed its caller in its last step, as DIR/<name>.npy: the op's nine outputs (the reference's dict keys), the
+    loss [total, colour, depth] and the raw parameters after that step's Adam update.  Floats stay float32; integer outputs (ids, radii,
+    counts) are written as float64, which holds them exactly.  Per-Gaussian arrays are cut to the rows in `gaussian_rows.npy`."""
+    if isinstance(out, dict):
+        out = [out[k] for k in OUTPUT_NAMES]
+    images = dict(zip(OUTPUT_NAMES[:7], out[:7]))
+    per_gaussian = dict(zip(OUTPUT_NAMES[7:], out[7:]), **{k: v.reshape(v.shape[0], -1) for k, v in params.items()})
+    P = int(out[8].shape[0])
+    rows = np.sort(np.random.default_rng(0).choice(P, size=min(P, DUMP_ROWS), replace=False))
+    rows_dev = torch.tensor(rows, device=out[8].device)
+    arrays = {"gaussian_rows": rows.astype(np.float64), "loss": np.asarray(loss, np.float64)}
+    for name, t in list(images.items()) + [(k, v[rows_dev]) for k, v in per_gaussian.items()]:
+        a = t.detach().cpu().numpy()
+        arrays[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs, more than the {DUMP_LIMIT_BYTES} allowed")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+# ------------------------------------------------------------------------------------------------------------------
 def main():
     args = parse()
+    if not args.full:  # the headline figure alone (module docstring)
+        args.no_cpu_baseline = args.no_roofline = args.no_pmc = args.no_aux = args.no_selfcheck = True
+        args.sustained = args.window = 0
     rw = resolve_world(args)  # before any GPU call: with --gpus N > 1 and no launcher the ranks run as a child job
     if rw is None:
         sys.exit(args._rc)
@@ -1312,6 +1360,15 @@ def main():
             g0 = None if prob.get("gate") is None else (torch.tensor(np.asarray(prob["full"]["obj_id"], np.int32), device=device), prob["pix_obj"])
             render0 = mapping.render(prob["settings"], mapping.GaussianParams(prob["full"], device).activated(), object_gate=g0)["render"].cpu().numpy()
     loss_buf = PackedAllReduce(LOSS_SPEC, device, force=coll)
+    # the interpreter's cyclic collector off the timed region: a full collection over the set-up's objects (the synthetic maps, the
+    # oracle's arrays) is a 40-80 ms pause, and the growth steps' temporaries trigger one now and then (nothing here builds cycles).
+    # BEFORE the capture and the warm-up, not between them and the timed region: a GPU left idle for 50 ms clocks down and needs ~10 ms
+    # of load to come back (tools/replay_times.py: the first five graph launches after such a pause run 3-6 % slower) — a 20-step timed
+    # region behind a collector pause measured the ramp, not the iteration.
+    import gc
+    gc.collect()
+    gc.freeze()
+    gc.disable()
     runner = step_dropin = None
     if args.path == "fused":
         runner = FusedRunner(prob, device, loss_buf, world, collective=coll, use_graph=not args.no_graph, growth_every=args.growth_every, growth_seed=rank,
@@ -1329,15 +1386,6 @@ def main():
 
     if runner is not None:
         runner.prepare_growth(args.warmup + args.steps)
-    # the interpreter's cyclic collector off the timed region: a full collection over the set-up's objects (the synthetic maps, the
-    # oracle's arrays) is a 40-80 ms pause, and the growth steps' temporaries trigger one now and then (nothing here builds cycles).
-    # BEFORE the warm-up, not between it and the timed region: a GPU left idle for 50 ms clocks down and needs ~10 ms of load to come
-    # back (tools/replay_times.py: the first five graph launches after such a pause run 3-6 % slower) — a 20-step timed region behind a
-    # collector pause measured the ramp, not the iteration.
-    import gc
-    gc.collect()
-    gc.freeze()
-    gc.disable()
     twin_loss = None
     if runner is not None and not args.no_selfcheck and not runner.growth_every:
         twin_loss = run_twin(prob, runner, device, args.warmup + args.steps)  # (self-check (2)'s reference, see run_twin)
@@ -1366,6 +1414,16 @@ def main():
     gc.enable()
     loss_now = reduced_losses(loss_buf.buf, world, per_object)
     dbg("timed loop done: dt", dt, "rank loss", runner.fm.loss[:3].tolist() if runner else None, "reduced", loss_now)
+    if args.dump_outputs and rank == 0 and not args.inner:
+        if runner is not None:
+            m = runner.fm
+            params = dict(xyz=m.xyz, shs=m.shs, opacity_raw=m.opacity_raw, scaling_raw=m.scaling_raw, rotation_raw=m.rotation_raw)
+        else:
+            m = step_dropin.params
+            params = dict(xyz=m._xyz, shs=torch.cat([m._features_dc, m._features_rest], 1), opacity_raw=m._opacity,
+                          scaling_raw=m._scaling, rotation_raw=m._rotation)
+        dump_outputs(args.dump_outputs, out, params, loss_now)
+        del m, params
     if args.inner:
         print(json.dumps({"inner": True, "ms_per_step": dt / args.steps * 1e3}))
         return
@@ -1381,7 +1439,7 @@ def main():
     # the same staging path — issued back to back with nothing else in flight, max over the ranks.  In the timed loop it runs
     # asynchronously beside the next iteration's graph, so this is what it would add if it were on the critical path, not what it adds.
     allreduce = None
-    if coll:
+    if coll and args.full:
         n_ops = 50
         torch.distributed.barrier()
         torch.cuda.synchronize()
@@ -1417,7 +1475,7 @@ def main():
 
     # ---- the other path, timed the same way (single GPU only), so both numbers come from one run ----
     alt = alt_optin = None
-    if world == 1:
+    if world == 1 and args.full:
         def time_path(step_other):
             # (host-bound loops: the allocator's block cache, the op's capacity hint and header ring, torch's kernel modules all settle
             # over the first iterations — at least ten of them, whatever --warmup says; a driver-style `--warmup 5` run used to time

@@ -84,3 +84,34 @@ def test_list_split_choices_are_host_logic():
             pair(bad, None, st)
     assert FusedMapper.pick_list_split("auto", tiles(300), st, 1500) == 256 and FusedMapper.pick_list_split("auto", None, st, 7000) == 0
     assert bench.parse_list_split("auto") == "auto" and bench.parse_list_split("512") == 512 and bench.parse_list_split("2048,0") == (2048, 0)
+
+
+def test_dump_outputs_is_a_fixed_sample_in_float32_or_float64(tmp_path, monkeypatch):
+    """bench.dump_outputs: the op's tuple and the reference's dict give the same files; integer outputs become exact float64; the
+    per-Gaussian rows are drawn from a fixed seed; a dump over the limit (64 MB; 1 MB here) is refused."""
+    import numpy as np
+    import torch
+    import bench
+    P, H, W = 70_000, 24, 40
+    g = torch.Generator().manual_seed(1)
+    f = lambda *s: torch.rand(*s, generator=g)
+    i = lambda *s: torch.randint(-1, P, s, generator=g, dtype=torch.int32)
+    out = (f(3, H, W), f(1, H, W), i(1, H, W), i(1, H, W), f(1, H, W), f(1, H, W), f(1, H, W), i(P), i(P))
+    params = dict(xyz=f(P, 3), shs=f(P, 16, 3), opacity_raw=f(P, 1))
+    bench.dump_outputs(str(tmp_path / "a"), out, params, [0.5, 0.25, 0.125])
+    bench.dump_outputs(str(tmp_path / "b"), dict(zip(bench.OUTPUT_NAMES, out)), params, [0.5, 0.25, 0.125])
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    a = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(np.array_equal(a[n[:-4]], np.load(tmp_path / "b" / n)) for n in names)
+    rows = a["gaussian_rows"].astype(np.int64)
+    assert rows.size == bench.DUMP_ROWS and np.all(np.diff(rows) > 0)
+    assert a["render"].dtype == np.float32 and np.array_equal(a["render"], out[0].numpy())
+    assert a["depth_index_map"].dtype == np.float64 and np.array_equal(a["depth_index_map"], out[3].numpy())
+    assert np.array_equal(a["radii"], out[8].numpy()[rows]) and np.array_equal(a["shs"], params["shs"].numpy().reshape(P, -1)[rows])
+    assert a["loss"].tolist() == [0.5, 0.25, 0.125]
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 20)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "c"), out, params, [0.0, 0.0, 0.0])
+    assert not (tmp_path / "c").exists()

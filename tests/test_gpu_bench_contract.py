@@ -12,8 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-pmc",
-                        "--no-aux"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
+                        "--no-pmc", "--no-aux"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines  # ONE JSON line, nothing else on stdout
@@ -41,7 +41,7 @@ def test_two_rank_rehearsal_on_one_gpu():
     env = dict(os.environ, DQO_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "4", "--warmup", "2"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -56,3 +56,27 @@ def test_two_rank_rehearsal_on_one_gpu():
     assert "cpu_baseline" not in d  # rank 0 at N = 1 only
     rep = d["config"]["replicas_reference"]  # every rank stepping the whole unsharded map: the aggregate of two replicas
     assert rep["unit"] == "iter/s" and rep["value"] > 0 and rep["ms_per_step"] > 0
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full: the timed steps and the result line, nothing measured or checked beside them; --dump-outputs writes the last
+    step's outputs (float32 / float64, 64 MB at most) and the loss the line reports."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"] == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
+    assert d["steps"] == 6 and d["warmup"] == 2 and d["unit"] == "iter/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 0.01 * d["value"]
+    assert not {"roofline", "cpu_baseline", "other_path", "other_path_optin", "other_workload"} & set(d)
+    assert not {"kernel_us", "sustained", "window", "aux"} & set(d["config"]) and d["config"]["selfcheck"] == "skipped"
+    a = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+    assert set(a) == {"render", "depth", "color_index_map", "depth_index_map", "color_hit_weight", "depth_hit_weight", "T_map", "n_touched",
+                      "radii", "xyz", "shs", "opacity_raw", "scaling_raw", "rotation_raw", "loss", "gaussian_rows"}
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["render"].shape == (3, 680, 1200) and a["shs"].shape == (a["gaussian_rows"].size, 48)
+    assert np.allclose(a["loss"], d["loss"], rtol=1e-5) and (a["depth_index_map"] >= 0).any()

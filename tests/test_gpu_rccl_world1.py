@@ -23,8 +23,8 @@ def test_rccl_one_rank_group_beside_graph_replays(ipc_legacy):
         env.pop(k, None)
     if ipc_legacy != "unset":
         env["HSA_ENABLE_IPC_MODE_LEGACY"] = ipc_legacy
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-collective", "--steps", "1000", "--warmup", "20",
-                        "--no-cpu-baseline", "--no-pmc", "--no-aux"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-collective", "--full", "--steps", "1000", "--warmup",
+                        "20", "--no-cpu-baseline", "--no-pmc", "--no-aux"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

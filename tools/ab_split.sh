@@ -7,7 +7,7 @@ for item in $1; do
   for runs in $values; do
     extra=""; tag=full
     if [ "$sh" != "-" ]; then extra="--as-shard $sh"; tag=${sh/\//of}; fi
-    timeout -k 10 300 python bench.py --cfg $cfg --growth-every 0 $extra --steps 60 --warmup 10 --no-cpu-baseline --no-pmc --no-aux --list-split $runs \
+    timeout -k 10 300 python bench.py --full --cfg $cfg --growth-every 0 $extra --steps 60 --warmup 10 --no-cpu-baseline --no-pmc --no-aux --list-split $runs \
       > gpurun_out/split/c${cfg}_${tag}_${runs}.json 2> gpurun_out/split/c${cfg}_${tag}_${runs}.err || exit 1
   done
 done
