@@ -42,8 +42,8 @@ def _full_size_case(oracle, cfg, name, fp64=True, P=None, gated=False):
     equal results: tests/test_oracle_rast.py::test_openmp_build_equals_serial): forward within 1e-4, flipped pixels within the 0.1 %
     budget and masked out of the incoming gradient on BOTH sides, gradients within 1e-3 of the fp32 oracle — north_star's numbers,
     no slack term.  The fp64 oracle runs beside EVERY configuration (seconds on the GPU box's host cores): a gradient row beyond 1e-3
-    must be explained by the fp32 oracle's own distance from fp64 on that row (util_rast.compare_grads); unexplained rows are capped
-    at max(1, 1e-5 x rows) and named.  gated: the blend kernels' GATE instantiation (rasterize_gaussians_gated) with bench.py's own
+    must be explained by the fp32 oracle's own distance from fp64 on that row (util_rast.compare_grads); unexplained rows are not
+    allowed (unexplained_cap = 0) and are named.  gated: the blend kernels' GATE instantiation (rasterize_gaussians_gated) with bench.py's own
     gate, against the gated oracle."""
     cam, sc = scenes.make_config(cfg, P=P)
     rng = np.random.default_rng(11)
