@@ -60,27 +60,10 @@ template <typename T>
 __device__ __forceinline__ void stnt(T v, T* p) {
     __builtin_nontemporal_store(v, p);
 }
-// The moments of the SMALL groups ([P,3] xyz / scaling, [P] opacity): plain accesses.  A non-temporal access to part of a line is
+// The moments of the SMALL groups ([P,3] xyz / scaling, [P] opacity) are plain accesses: a non-temporal access to part of a line is
 // served memory-side without the neighbours' help; through L2 the rows of adjacent Gaussians share their lines (measured, round 4:
-// fused tail 129 -> 121 us on cfg 3, 508 -> 467 us on cfg 5; without any of this traffic: 111 / 368 — `-DDQO_SMALL_MV_NT` restores the
-// non-temporal form).  The SH moments (whole 192-byte rows, 0.7 GB touched once per iteration) stay non-temporal: plain accesses there
-// measured +0 / +20 us.
-template <typename T>
-__device__ __forceinline__ T ldsm(const T* p) {
-#ifdef DQO_SMALL_MV_NT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-template <typename T>
-__device__ __forceinline__ void stsm(T v, T* p) {
-#ifdef DQO_SMALL_MV_NT
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
+// fused tail 129 -> 121 us on cfg 3, 508 -> 467 us on cfg 5; without any of this traffic: 111 / 368).  The SH moments (whole
+// 192-byte rows, 0.7 GB touched once per iteration) stay non-temporal: plain accesses there measured +0 / +20 us.
 
 __device__ __forceinline__ float adam_wave_red(float v) {
 #pragma unroll
@@ -106,11 +89,11 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, con
 struct AdamGradGlobal {
     const AdamArgs& a;
     // (the small rows through plain loads, like their moments: ldsm)
-    __device__ __forceinline__ float xyz(int, uint32_t, size_t i, bool has_g) const { return ldsm(&a.g_xyz[has_g ? i : 0]); }
-    __device__ __forceinline__ float scales(int, uint32_t, size_t i, bool has_g) const { return ldsm(&a.g_scales[has_g ? i : 0]); }
+    __device__ __forceinline__ float xyz(int, uint32_t, size_t i, bool has_g) const { return a.g_xyz[has_g ? i : 0]; }
+    __device__ __forceinline__ float scales(int, uint32_t, size_t i, bool has_g) const { return a.g_scales[has_g ? i : 0]; }
     // SH element j of the row; ei = its element index, e0 = a valid element index of the same trip
     __device__ __forceinline__ float sh(int, uint32_t, uint32_t ei, uint32_t e0, bool has_g) const { return ldnt(&a.g_shs[has_g ? ei : e0]); }
-    __device__ __forceinline__ float opacity(int, uint32_t i, bool has_g) const { return ldsm(&a.g_opacity[has_g ? i : 0u]); }
+    __device__ __forceinline__ float opacity(int, uint32_t i, bool has_g) const { return a.g_opacity[has_g ? i : 0u]; }
     __device__ __forceinline__ float4 rot(int, uint32_t i, bool has_g) const { return reinterpret_cast<const float4*>(a.g_rot)[has_g ? i : 0u]; }
     // does the row's f_dc gradient (SH coefficient 0) have a non-zero element?  (mapper.py:908-909; three loads at a clamped address)
     __device__ __forceinline__ bool dc_nonzero(int, uint32_t i, bool has_g) const {
@@ -175,9 +158,9 @@ __device__ __forceinline__ void adam_xyz_update(const AdamArgs& a, const uint32_
         att_sum += 0.5f * a.attach_g3 * (dx * dx + ds * ds);
     }
     adam1(p, gx, m, v, a, a.step_xyz);
-    a.xyz[i] = p, stsm(m, &a.m_xyz[i]), stsm(v, &a.v_xyz[i]);
+    a.xyz[i] = p, a.m_xyz[i] = m, a.v_xyz[i] = v;
     adam1(ps, gs, ms, vs, a, a.step_scaling);
-    a.scaling_raw[i] = ps, stsm(ms, &a.m_scaling[i]), stsm(vs, &a.v_scaling[i]);
+    a.scaling_raw[i] = ps, a.m_scaling[i] = ms, a.v_scaling[i] = vs;
     if (a.act_scales) a.act_scales[i] = expf(ps);  // = activate_kernel on the updated value
 }
 
@@ -196,7 +179,7 @@ __device__ __forceinline__ void adam_row_update(const AdamArgs& a, const uint32_
     float4 q = x.q, mq = x.mq, vq = x.vq;
     const float sg = 1.0f / (1.0f + expf(-p));
     adam1(p, (has_g ? x.go_ld : 0.f) * (sg * (1.f - sg)), m, v, a, a.step_opacity);
-    a.opacity_raw[i] = p, stsm(m, &a.m_opacity[i]), stsm(v, &a.v_opacity[i]);
+    a.opacity_raw[i] = p, a.m_opacity[i] = m, a.v_opacity[i] = v;
     if (a.act_opacity) a.act_opacity[i] = 1.0f / (1.0f + expf(-p));
 
     const float4 g = has_g ? x.gr_ld : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -243,8 +226,8 @@ __device__ __forceinline__ float adam_passes(const AdamArgs& a, const uint32_t* 
         const size_t i = (size_t)(r & 0x3fffffffu) * 3 + j;
         // all loads of the element in one round (a row outside the attach set reads element 0 and discards it)
         AdamXyzVals x;
-        x.p = a.xyz[i], x.m = ldsm(&a.m_xyz[i]), x.v = ldsm(&a.v_xyz[i]);
-        x.ps = a.scaling_raw[i], x.ms = ldsm(&a.m_scaling[i]), x.vs = ldsm(&a.v_scaling[i]);
+        x.p = a.xyz[i], x.m = a.m_xyz[i], x.v = a.v_xyz[i];
+        x.ps = a.scaling_raw[i], x.ms = a.m_scaling[i], x.vs = a.v_scaling[i];
         x.gx_ld = gsrc.xyz((int)k, j, i, has_g), x.gs_ld = gsrc.scales((int)k, j, i, has_g);
         x.p0 = x.ps0 = 0.f;
         if (ATTACH) {
@@ -307,7 +290,7 @@ __device__ __forceinline__ float adam_passes(const AdamArgs& a, const uint32_t* 
         const bool has_g = (r >> 31) != 0u;
         // all loads of the row in one round
         AdamRowVals x;
-        x.p = a.opacity_raw[i], x.m = ldsm(&a.m_opacity[i]), x.v = ldsm(&a.v_opacity[i]);
+        x.p = a.opacity_raw[i], x.m = a.m_opacity[i], x.v = a.v_opacity[i];
         x.q = reinterpret_cast<float4*>(a.rotation_raw)[i];
         x.mq = reinterpret_cast<float4*>(a.m_rotation)[i], x.vq = reinterpret_cast<float4*>(a.v_rotation)[i];
         x.go_ld = gsrc.opacity(tid, i, has_g);
@@ -345,10 +328,7 @@ __device__ __forceinline__ float adam_passes_tail(const AdamArgs& a, const uint3
     // ~50 rows — ran on wave 0 alone behind the SH pass, 6 us during which wave 1 waited at the block's last barrier): wave 1 takes the
     // row pass (rows 0..63; wave 0 the rows beyond, if any) and in exchange at most ONE trip of the SH pass, wave 0 the rest of it.
     // Element for element the statements are unchanged: same bits (the attach loss is grouped differently: a reported scalar).
-#ifndef DQO_TAIL_ROLE_SPLIT
-#define DQO_TAIL_ROLE_SPLIT 1
-#endif
-    constexpr bool SPLIT = DQO_TAIL_ROLE_SPLIT && THREADS == 128;
+    constexpr bool SPLIT = THREADS == 128;
     const int wave = tid >> 6, lane = tid & 63;
     const int my_row = SPLIT ? (wave == 1 ? lane : 64 + lane) : tid;
     auto rows_pass = [&]() {
@@ -357,7 +337,7 @@ __device__ __forceinline__ float adam_passes_tail(const AdamArgs& a, const uint3
             const uint32_t r = s_rows[my_row], i = r & 0x3fffffffu;
             const bool has_g = (r >> 31) != 0u;
             AdamRowVals x;
-            x.p = a.opacity_raw[i], x.m = ldsm(&a.m_opacity[i]), x.v = ldsm(&a.v_opacity[i]);
+            x.p = a.opacity_raw[i], x.m = a.m_opacity[i], x.v = a.v_opacity[i];
             x.q = reinterpret_cast<float4*>(a.rotation_raw)[i];
             x.mq = reinterpret_cast<float4*>(a.m_rotation)[i], x.vq = reinterpret_cast<float4*>(a.v_rotation)[i];
             x.go_ld = gsrc.opacity(my_row, i, has_g);
@@ -375,8 +355,8 @@ __device__ __forceinline__ float adam_passes_tail(const AdamArgs& a, const uint3
         const bool has_g = (r >> 31) != 0u;
         const size_t i = (size_t)(r & 0x3fffffffu) * 3 + j;
         AdamXyzVals x;
-        x.p = a.xyz[i], x.m = ldsm(&a.m_xyz[i]), x.v = ldsm(&a.v_xyz[i]);
-        x.ps = a.scaling_raw[i], x.ms = ldsm(&a.m_scaling[i]), x.vs = ldsm(&a.v_scaling[i]);
+        x.p = a.xyz[i], x.m = a.m_xyz[i], x.v = a.v_xyz[i];
+        x.ps = a.scaling_raw[i], x.ms = a.m_scaling[i], x.vs = a.v_scaling[i];
         x.gx_ld = gsrc.xyz((int)k, j, i, has_g), x.gs_ld = gsrc.scales((int)k, j, i, has_g);
         x.p0 = x.ps0 = 0.f;
         if (ATTACH) {

@@ -83,7 +83,8 @@ struct DqoGeomLayout {
     uint32_t* tiles_touched; // [P]
     uint32_t* slot_base;     // [P] first gaussian-major instance slot of this Gaussian
     uint8_t* clamped;        // [P] bit0..2 = SH colour channel clamped at 0 (forward.cu:151-153)
-    float4* grad_sum;        // [P][4] backward only: summed gradient record (DqoGradRec) of each Gaussian with instances
+    float4* grad_sum;        // [P][4] unused, kept for the layout: its size is part of dqo_rast_geom_bytes, and where buffers
+                             //        land moves kernel times (FusedMapper.capture_placed)
     size_t total;
 };
 
@@ -323,18 +324,18 @@ static inline DqoBinLayout dqo_bin_layout(void* base, int64_t cap, int64_t list_
 }
 
 // Per-instance gradient record written by the backward blend kernel (one per (tile, Gaussian) instance), summed per
-// Gaussian in a fixed order by the per-Gaussian backward kernel: bitwise reproducible, no float atomics.
+// Gaussian in a fixed order by the per-Gaussian kernel (map_fused_tail.hip): bitwise reproducible, no float atomics.
 struct __attribute__((aligned(16))) DqoGradRec {
     float dcolor[3];   // dL/d rgb
     // pixel moments of q = G * dL/dalpha over the pixels that blended the instance; the opacity / conic / viewport factors that
     // turn them into dL/d(2D mean), dL/d(conic), dL/d(opacity) (backward.cu:964-994) are per-Gaussian constants and are
-    // applied by gaussian_backward_kernel
+    // applied by the per-Gaussian chain (dqo_gauss_chain.h)
     float m1[2];       // sum q dx, sum q dy
     float m2[3];       // sum q dx^2, sum q dx dy, sum q dy^2
     float m0;          // sum q
     // depth-hit sums over the pixels whose depth this instance fixed (backward.cu:997-1065); the per-Gaussian factors of
     // that gradient that are LINEAR (normal, view matrix, quaternion Jacobian) are applied once per Gaussian by
-    // gaussian_backward_kernel:  hit[0] = sum dL/ddepth over pixels in the centre-depth branch,  hit[1] = sum of
+    // the per-Gaussian chain:  hit[0] = sum dL/ddepth over pixels in the centre-depth branch,  hit[1] = sum of
     // dL/ddepth * ray.z / (n.ray) over pixels in the ray/plane branch,  hit[2..4] = sum of dL/ddepth * d(depth)/d(n_c) =
     // dL/ddepth * ray.z (nr p_c - np ray) / nr^2, evaluated per pixel with the reference's statements (backward.cu:1018-1041)
     float hit[5];
@@ -348,10 +349,10 @@ static inline size_t dqo_bwd_recs_bytes(int64_t cap) { return dqo_align_up(sizeo
 static inline size_t dqo_bwd_ws_bytes(int64_t cap) { return dqo_bwd_recs_bytes(cap) + 256; }
 
 // Block -> Gaussian assignment of the two kernels whose cost depends on WHICH Gaussians share a block (bin_count_kernel: same-
-// tile atomics; record_sum_kernel: slots per block).  A block of 256 threads owns 16 groups of 16 consecutive Gaussians taken
+// tile atomics; the per-Gaussian kernels of map_fused_tail.hip: slots per block).  A block of 256 threads owns 16 groups of 16 consecutive Gaussians taken
 // from 16 distant parts of the index range (a 16 x G/16 transpose of the group index), so a spatially coherent storage order
 // (an incrementally built map) is spread over the blocks the way a random order is, while every load still covers 16
-// consecutive records.  Both kernels use the same mapping: a block's Gaussians get one contiguous run of instance slots.
+// consecutive records.  All of them use the same mapping: a block's Gaussians get one contiguous run of instance slots.
 // Returns >= P for the padding positions.
 __host__ __device__ static inline int dqo_spread_index(int logical, int P) {
     const int G = (P + 15) >> 4;            // groups of 16
@@ -465,7 +466,7 @@ __device__ __forceinline__ void dqo_header_from_spread(const DqoGeomLayout& g, i
 }
 
 // The long-list sort launch is dropped when no list can outgrow the per-tile sort (buckets of at most DQO_SORTW_CAP entries, tile order kept,
-// the late part of the per-Gaussian forward not riding that launch, no list splitting); DQO_SKIP_LONG_SORT=0 keeps it.
+// the late part of the per-Gaussian forward not riding that launch, no list splitting).
 bool dqo_skip_long_sort(const DqoRastParams* p, const DqoRastCtx* ctx);
 
 // Zero fill of caller memory on the launch stream.  The library never uses hipMemsetAsync for this: as a memset NODE of a captured

@@ -1,4 +1,4 @@
-// Per-Gaussian backward chain (K8 + K9) as one device function, shared by gaussian_backward_kernel (rast_backward.hip: the drop-in
+// Per-Gaussian backward chain (K8 + K9) as one device function, shared by gaussian_rows_kernel (map_fused_tail.hip: the drop-in
 // backward, gradient rows to HBM) and gaussian_tail_kernel (map_fused_tail.hip: the fused mapping iteration, gradient rows stay in
 // LDS and feed Adam) — ONE statement sequence, so both produce the same bits.
 //

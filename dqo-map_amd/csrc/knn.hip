@@ -12,7 +12,7 @@
 // sort), four 8-bit passes of histogram -> scan -> scatter; the rank of a key among the equal digits of its block comes from wave
 // ballots (eight ballots match the lanes with the same digit) + per-wave counts in LDS.  12 launches for any size; the first
 // version — a 64-bit bitonic network, 4096-key runs in LDS, merge steps >= 4096 in global memory — needed 55 launches and 0.73 ms
-// for 2 M keys (`make EXTRA=-DKNN_BITONIC_SORT` keeps it for comparison).
+// for 2 M keys.
 #include <float.h>
 #include <limits.h>
 
@@ -25,7 +25,6 @@ namespace {
 constexpr int KNN_BOX = 1024;  // simple_knn.cu:16 BOX_SIZE (part of the pruning structure only)
 constexpr int KNN_SUB = 64;    // second pruning level of the query search: one wave-load of sorted points
 constexpr int SORT_RUN = 4096;
-constexpr int SORT_T = 256;
 constexpr int RDX_T = 256, RDX_KPT = 8, RDX_BLK = RDX_T * RDX_KPT;  // radix sort: keys per block
 
 struct KnnWs {
@@ -179,45 +178,6 @@ __global__ void morton_fine_kernel(int P, int P2, const float* __restrict__ xyz,
     const uint64_t cy = prep_morton64(min(f2u(((y - mny) / (mxy - mny)) * top), (uint32_t)top));
     const uint64_t cz = prep_morton64(min(f2u(((z - mnz) / (mxz - mnz)) * top), (uint32_t)top));
     keys[i] = ((cx | (cy << 1) | (cz << 2)) << FINE_IDX_BITS) | (uint64_t)i;
-}
-
-// classic bitonic network on a power-of-two array: LDS kernel handles every step with j < SORT_RUN of one k-level
-// (or all levels k <= SORT_RUN when `first`), the global kernel one step with j >= SORT_RUN.
-__global__ __launch_bounds__(SORT_T) void bitonic_lds_kernel(uint64_t* __restrict__ keys, int k_level, int first) {
-    __shared__ uint64_t s[SORT_RUN];
-    const int base = blockIdx.x * SORT_RUN;
-    for (int i = threadIdx.x; i < SORT_RUN; i += SORT_T) s[i] = keys[base + i];
-    __syncthreads();
-    const int k_lo = first ? 2 : k_level, k_hi = first ? SORT_RUN : k_level;
-    for (int k = k_lo; k <= k_hi; k <<= 1) {
-        for (int j = min(k >> 1, SORT_RUN >> 1); j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < SORT_RUN / 2; t += SORT_T) {
-                const int i = 2 * j * (t / j) + (t % j);
-                const int p = i + j;
-                const bool up = (((base + i) & k) == 0);
-                const uint64_t a = s[i], b = s[p];
-                if ((a > b) == up) {
-                    s[i] = b;
-                    s[p] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = threadIdx.x; i < SORT_RUN; i += SORT_T) keys[base + i] = s[i];
-}
-
-__global__ void bitonic_global_kernel(uint64_t* __restrict__ keys, int n_half, int k, int j) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_half) return;
-    const int i = 2 * j * (t / j) + (t % j);
-    const int p = i + j;
-    const bool up = ((i & k) == 0);
-    const uint64_t a = keys[i], b = keys[p];
-    if ((a > b) == up) {
-        keys[i] = b;
-        keys[p] = a;
-    }
 }
 
 // ---- stable LSD radix sort, one 8-bit pass = three kernels ----
@@ -676,16 +636,6 @@ static int knn_build(int P, const float* xyz, const KnnWs& w, bool with_boxes, h
     }
     if (fine) DQO_LAUNCH("morton_kernel", morton_fine_kernel, dim3((P2 + 255) / 256), dim3(256), s, P, P2, xyz, w.bbox, w.keys, group);
     else DQO_LAUNCH("morton_kernel", morton_kernel, dim3((P2 + 255) / 256), dim3(256), s, P, P2, xyz, w.bbox, w.keys);
-#ifdef KNN_BITONIC_SORT
-    const int runs = P2 / SORT_RUN;
-    DQO_LAUNCH("bitonic_lds_kernel", bitonic_lds_kernel, dim3(runs), dim3(SORT_T), s, w.keys, SORT_RUN, 1);
-    for (int k = SORT_RUN * 2; k <= P2; k <<= 1) {
-        for (int j = k >> 1; j >= SORT_RUN; j >>= 1) {
-            DQO_LAUNCH("bitonic_global_kernel", bitonic_global_kernel, dim3((P2 / 2 + 255) / 256), dim3(256), s, w.keys, P2 / 2, k, j);
-        }
-        DQO_LAUNCH("bitonic_lds_kernel", bitonic_lds_kernel, dim3(runs), dim3(SORT_T), s, w.keys, k, 0);
-    }
-#else
     {   // the Morton code sits in bits 32..61 of the key: four stable 8-bit passes; the second key buffer is `sorted` (16 B per point,
         // written by the gather only after the sort); an even number of passes leaves the result in w.keys
         const int nblk = (P + RDX_BLK - 1) / RDX_BLK;
@@ -703,7 +653,6 @@ static int knn_build(int P, const float* xyz, const KnnWs& w, bool with_boxes, h
             std::swap(a, b);
         }
     }
-#endif
     DQO_LAUNCH("gather_sorted_kernel", gather_sorted_kernel, dim3((P + 255) / 256), dim3(256), s, P, xyz, w.keys, w.sorted,
                fine ? ((1ull << FINE_IDX_BITS) - 1ull) : 0xffffffffull, group);
     if (with_boxes) {

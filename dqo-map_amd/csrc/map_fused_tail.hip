@@ -1,19 +1,18 @@
 // Fused per-Gaussian tail of one mapping iteration for gfx950: record sum -> per-Gaussian backward chain -> Adam in ONE pass over
 // the Gaussians (dqo_rast_backward_adam, include/dqo_raster.h).
 //
-// Replaces, for the fused mapping iteration only (the drop-in backward keeps its kernels: its gradient rows are outputs),
-//   record_sum_kernel + gaussian_backward_kernel (rast_backward.hip)  <- cuda_rasterizer/backward.cu:273-548 (K8, K9)
-//   adam_kernel (map_fused.hip)                                       <- SLAM/gaussian_pointcloud.py:331-378, mapper.py:548, 812-829
-// As three kernels the 59-float gradient row of every visible Gaussian made a round trip through HBM between two kernels that
-// visit the same Gaussians (284 B written + 236 B re-read), and so did its 64-byte summed record.  Here a workgroup owns 128
-// Gaussians (the thread -> Gaussian assignment of bin_count_kernel / record_sum_kernel, so their instance slots are one contiguous
-// range):
+// Replaces, for the fused mapping iteration only (the drop-in backward keeps its kernel: its gradient rows are outputs),
+//   gaussian_rows_kernel (below)  <- cuda_rasterizer/backward.cu:273-548 (K8, K9)
+//   adam_kernel (map_fused.hip)   <- SLAM/gaussian_pointcloud.py:331-378, mapper.py:548, 812-829
+// As separate kernels the 59-float gradient row of every visible Gaussian makes a round trip through HBM between two kernels that
+// visit the same Gaussians (284 B written + 236 B re-read).  Here a workgroup owns 128 Gaussians (the thread -> Gaussian assignment
+// of bin_count_kernel, so their instance slots are one contiguous range):
 //   A  lists the rows Adam has to touch (LDS: visible Gaussians and, in the exact sparse mode, those with non-zero moments),
-//   B  sums its Gaussians' partial gradient records in the fixed (slot, quadrant) order of record_sum_kernel,
-//   C  runs the per-Gaussian chain (dqo_gauss_chain.h: the same statements as gaussian_backward_kernel) and leaves each gradient row
+//   B  sums its Gaussians' partial gradient records in a fixed (slot, quadrant) order,
+//   C  runs the per-Gaussian chain (dqo_gauss_chain.h: the same statements as gaussian_rows_kernel) and leaves each gradient row
 //      in LDS — factored: dL/dsh[k][c] = w[k] * dRGB[c], so a row is 30 floats instead of 59 (15.5 KB per workgroup),
 //   D  runs Adam's passes over the list with the gradient read from LDS (dqo_adam.h: the same statements as adam_kernel).
-// Every float that reaches a parameter or a moment is produced by the same operations on the same operands as in the three-kernel
+// Every float that reaches a parameter or a moment is produced by the same operations on the same operands as in the two-kernel
 // path: bit-identical results (tests/test_gpu_fused_mapping.py::test_fused_tail_is_bitwise_the_three_kernels).
 //
 // What bounds it (round 3 measurements, cfg 3): the latency of a workgroup's dependent memory rounds — SQ counters: 60 % of
@@ -37,7 +36,7 @@ constexpr int TAIL_THREADS = DQO_TAIL_THREADS;  // Gaussians (= threads) per wor
 constexpr int ROW_MEAN = 0, ROW_W = 3, ROW_RGB = 19, ROW_OP = 22, ROW_SC = 23, ROW_ROT = 26, ROW_STRIDE = 31;
 
 // Gradient source of Adam's passes: the rows phase C left in LDS (k = list row).  The SH gradient is formed here from its two factors
-// — one IEEE multiply, the reference's per-coefficient statement (backward.cu:152-268) and what gaussian_backward_kernel stores.
+// — one IEEE multiply, the reference's per-coefficient statement (backward.cu:152-268) and what gaussian_rows_kernel stores.
 struct AdamGradLds {
     const float* s_g;
     int used3;  // 3 x (coefficients of the active SH degree): elements beyond it have a zero gradient (rasterize_points.cu:204)
@@ -182,8 +181,8 @@ __global__ __launch_bounds__(TAIL_THREADS, DQO_TAIL_WAVES) void gaussian_tail_ke
     if (act) s_rows[my_row] = (uint32_t)idx | (visible ? 0x80000000u : 0u) | (att ? 0x40000000u : 0u);
     const uint32_t hi = (uint32_t)min((int64_t)hi_all, capacity);  // (an overflowed forward never gets here; belt and braces)
 
-    // ---- second round of loads: everything the chain needs of this lane's Gaussian, issued as a whole before the record gather (the
-    //      same round structure as gaussian_backward_kernel; in flight while phase B runs).  (Compacting the visible Gaussians of a
+    // ---- second round of loads: everything the chain needs of this lane's Gaussian, issued as a whole before the record gather (in
+    //      flight while phase B runs).  (Compacting the visible Gaussians of a
     //      256-thread block into as few waves as they fill — cfg 3: 39 % are visible — was built and measured: no gain; the chain is a
     //      long dependent instruction sequence whose duration does not depend on how many lanes run it.) ----
     DqoChainIn ci;
@@ -208,7 +207,7 @@ __global__ __launch_bounds__(TAIL_THREADS, DQO_TAIL_WAVES) void gaussian_tail_ke
         ci.dd[6] = d2.x, ci.dd[7] = d2.y, ci.dd[8] = d2.z;
     }
 
-    // ---- B: fixed-order sum of this lane's Gaussian's partial gradient records (record_sum_kernel's statements; one slot per thread and trip) ----
+    // ---- B: fixed-order sum of this lane's Gaussian's partial gradient records (one slot per thread and trip) ----
     float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
     if (lo < hi) {  // (wave-uniform)
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -266,7 +265,7 @@ __global__ __launch_bounds__(TAIL_THREADS, DQO_TAIL_WAVES) void gaussian_tail_ke
         ci.a[4] = a1.x, ci.a[5] = a1.y, ci.a[6] = a1.z, ci.a[7] = a1.w;
         ci.a[8] = a2.x, ci.a[9] = a2.y, ci.a[10] = a2.z, ci.a[11] = a2.w;
         ci.a[12] = a3.x, ci.a[13] = a3.y, ci.a[14] = a3.z, ci.a[15] = a3.w;
-        if (cnt == 0u) ci.cop = make_float4(0.f, 0.f, 0.f, 0.f);  // (a Gaussian without instances: gaussian_backward_kernel's rule)
+        if (cnt == 0u) ci.cop = make_float4(0.f, 0.f, 0.f, 0.f);  // (a Gaussian without instances: no pixel blended it)
         DqoChainOut co;
         dqo_gauss_chain(v, view, proj, ci, true, co);
         float* row = s_g + my_row * ROW_STRIDE;
@@ -308,10 +307,9 @@ __global__ __launch_bounds__(TAIL_THREADS, DQO_TAIL_WAVES) void gaussian_tail_ke
 
 // ------------------------------------------------------------------------------------------------------------------
 // The drop-in backward's per-Gaussian half as ONE kernel: record sum -> per-Gaussian chain -> gradient ROWS, written to the caller's
-// tensors in coalesced pieces.  Replaces record_sum_kernel + gaussian_backward_kernel (rast_backward.hip; kept behind
-// DQO_ROWS_KERNEL=0 for A/B): those two sent every Gaussian's 64-byte summed record through HBM, and gaussian_backward_kernel wrote a
-// Gaussian's 59 + 12 gradient floats from ONE thread — 71 store instructions per wave, each touching 64 different cache lines, for
-// visible and culled rows alike (the culled rows, 61 % of cfg 3, are plain zeros the reference's API contract still wants written).
+// tensors in coalesced pieces.  A Gaussian's 59 + 12 gradient floats stored from ONE thread would be 71 store instructions per wave,
+// each touching 64 different cache lines, for visible and culled rows alike (the culled rows, 61 % of cfg 3, are plain zeros the
+// reference's API contract still wants written).
 // Here phases A - C are gaussian_tail_kernel's (same block -> Gaussian mapping, same fixed-order sums, same chain: same bits), the
 // gradient row of every Gaussian of the block waits in LDS (41 floats, factored SH), and phase D streams the block's rows out tensor
 // by tensor: consecutive threads write consecutive floats, 16 consecutive Gaussians of a spread group at a time.
@@ -443,7 +441,7 @@ __global__ __launch_bounds__(TAIL_THREADS, DQO_TAIL_WAVES) void gaussian_rows_ke
         ci.a[4] = a1.x, ci.a[5] = a1.y, ci.a[6] = a1.z, ci.a[7] = a1.w;
         ci.a[8] = a2.x, ci.a[9] = a2.y, ci.a[10] = a2.z, ci.a[11] = a2.w;
         ci.a[12] = a3.x, ci.a[13] = a3.y, ci.a[14] = a3.z, ci.a[15] = a3.w;
-        if (cnt == 0u) ci.cop = make_float4(0.f, 0.f, 0.f, 0.f);  // (a Gaussian without instances: gaussian_backward_kernel's rule)
+        if (cnt == 0u) ci.cop = make_float4(0.f, 0.f, 0.f, 0.f);  // (a Gaussian without instances: no pixel blended it)
         DqoChainOut co;
         dqo_gauss_chain(v, view, proj, ci, with_sh, co);
         float* row = s_g + tid * RROW_STRIDE;

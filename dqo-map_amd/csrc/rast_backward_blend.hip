@@ -6,17 +6,18 @@
 //   * Depth-hit sums first, once per pixel: every pixel has at most one entry that fixed its depth; the pixels of the quadrant
 //     that share it are added up by their lowest lane through wave-private LDS and written as floats 9..13 of that
 //     (quadrant, instance) record.
-//   * The wave then walks its tile's list back to front in chunks of 64 positions, but only over the entries the forward marked
-//     live for this quadrant: the live ones of a chunk are compacted with one ballot and their 16-byte records gathered into
-//     wave-private LDS; the next chunk's live bytes are loaded while the current chunk is processed.
-//   * Per live entry every lane evaluates its pixel with predicated (branch-free) arithmetic and produces nine sums-to-be (three
-//     colour terms, six moments of q = G dL/dalpha).  Seven entries at a time, their 63 values go through ONE 64-value
-//     reduce-scatter butterfly (v_permlane32/16_swap, bank-masked v_add_f32_dpp, quad_perm), after which lane 9 b + f holds float
-//     f of entry b: those lanes store the 64-byte partial records at recs[slot * 4 + quadrant] and lanes 0..6 mark them valid
-//     (1 = colour-path floats, 3 = depth-hit floats as well).
-// record_sum_kernel adds a Gaussian's valid partial records in a fixed order: bitwise reproducible.  Instruction costs behind the
-// choices (swap = 8 cycles, DPP = 4-5, plain = 3-4): tools/ubench_valu.hip, profiles/r01_ubench_valu.txt.
-#include <cstdlib>
+//   * The wave then walks its tile's list back to front, but only over the entries the forward marked live for this quadrant, each
+//     16-lane row of the wave over its own sub-list (the row walk, blend_quadrant_bwd).  Per live entry every lane evaluates its
+//     pixel with predicated (branch-free) arithmetic and produces nine sums-to-be (three colour terms, six moments of
+//     q = G dL/dalpha); seven entries at a time go through a row-local reduce-scatter, and every (quadrant, instance) pair gets ONE
+//     64-byte partial record at recs[slot * 4 + quadrant], marked valid (1 = colour-path floats, 3 = depth-hit floats as well).
+//   * The long lists of DqoRastCtx.list_split are walked by eight waves per quadrant over the union of the live entries: chunks of
+//     64 positions, the live ones compacted with one ballot and their 16-byte records gathered into wave-private LDS; seven entries
+//     at a time, their 63 values go through ONE 64-value reduce-scatter butterfly (v_permlane32/16_swap, bank-masked
+//     v_add_f32_dpp, quad_perm), after which lane 9 b + f holds float f of entry b and stores it.
+// gaussian_rows_kernel / gaussian_tail_kernel (map_fused_tail.hip) add a Gaussian's valid partial records in a fixed order: bitwise
+// reproducible.  Instruction costs behind the choices (swap = 8 cycles, DPP = 4-5, plain = 3-4): tools/ubench_valu.hip,
+// profiles/r01_ubench_valu.txt.
 #include <type_traits>
 
 #include "dqo_common.h"
@@ -148,22 +149,6 @@ __device__ __forceinline__ float wave_reduce64(const float (&v)[64], int lane) {
     return wave_reduce_tail16(b, lane);
 }
 
-// The same butterfly for THIRTY-TWO values: lane l (and lane l ^ 32) ends up with the 64-lane total of v[l & 31].  The lane ^ 32
-// exchange comes last, on the one value that is left (a swap of a register with its own copy + one add), instead of first on 32
-// pairs: 73 VALU for 32 sums — more per sum than the 64-value form, but half the registers, which is what decides how many waves
-// share a SIMD (the kernel is bound by per-wave instruction latency, not by VALU throughput: tools/ubench_valu.hip).
-__device__ __forceinline__ float wave_reduce32(const float (&v)[32], int lane) {
-    float b[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        const dqo_uint2v r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i + 16]), false, false);
-        b[i] = __uint_as_float(r.x) + __uint_as_float(r.y);
-    }
-    const float y = wave_reduce_tail16(b, lane);
-    const dqo_uint2v r32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(y), __float_as_uint(y), false, false);
-    return __uint_as_float(r32.x) + __uint_as_float(r32.y);
-}
-
 // ---- per-row (16-lane) reduce-scatter for the row walk ------------------------------------------------------------------
 // SIXTY-FOUR values per lane, reduced over the 16 lanes of each DPP row separately: afterwards lane s of a row holds the row's totals of
 // v[4 s .. 4 s + 3].  Four halving stages (lane ^ 8, ^ 4: two bank-masked v_add_f32_dpp per output; lane ^ 2, ^ 1: quad_perm with
@@ -192,39 +177,6 @@ __device__ __forceinline__ void row_stage4(const float (&lo)[8], const float (&h
                    [l7] "v"(lo[7]), [h0] "v"(hi[0]), [h1] "v"(hi[1]), [h2] "v"(hi[2]), [h3] "v"(hi[3]), [h4] "v"(hi[4]), [h5] "v"(hi[5]),
                    [h6] "v"(hi[6]), [h7] "v"(hi[7]));
 #undef DQO_R4
-}
-// ... and for THIRTY-TWO values (three entries per batch): lane s of a row ends up with the row's totals of v[2 s], v[2 s + 1]; 66 VALU
-// for 27 sums — more per sum than the 64-value form, but half the registers (what decides how many waves share a SIMD)
-__device__ __forceinline__ void row_reduce32(const float (&v)[32], float (&out)[2], int lane) {
-    float c[16];
-#pragma unroll
-    for (int q = 0; q < 2; q++) {  // c[i] = v[i] (+) v[i + 16]
-        float lo[8], hi[8], r[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) lo[i] = v[8 * q + i], hi[i] = v[16 + 8 * q + i];
-        row_stage8(lo, hi, r);
-#pragma unroll
-        for (int i = 0; i < 8; i++) c[8 * q + i] = r[i];
-    }
-    float d[8];
-    {
-        float lo[8], hi[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) lo[i] = c[i], hi[i] = c[8 + i];
-        row_stage4(lo, hi, d);
-    }
-    const bool b1 = (lane & 2) != 0, b0 = (lane & 1) != 0;
-    float e[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const float keep = b1 ? d[i + 4] : d[i], send = b1 ? d[i] : d[i + 4];
-        e[i] = keep + dpp_mov<0x4E>(send);  // partner lane ^ 2
-    }
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-        const float keep = b0 ? e[i + 2] : e[i], send = b0 ? e[i] : e[i + 2];
-        out[i] = keep + dpp_mov<0xB1>(send);  // partner lane ^ 1
-    }
 }
 __device__ __forceinline__ void row_reduce64(const float (&v)[64], float (&out)[4], int lane) {
     float c[32];
@@ -296,10 +248,6 @@ constexpr int BWD_THREADS = 64;
 // LDS of one wave: the gathered records of its chunk's live entries (three float4 tables, three word tables) and the depth-hit sums
 constexpr int BWD_BLK = 3 * BWD_THREADS * 4 + 3 * BWD_THREADS + 5 * BWD_THREADS;  // words: 1280 = 5120 B
 constexpr int BWD_XCH = 5 * BWD_THREADS;                                            // words of one wave's pass-1 result (SEGS > 1)
-__device__ __forceinline__ void row_reduce(const float (&v)[64], float (&out)[4], int lane) { row_reduce64(v, out, lane); }
-__device__ __forceinline__ void row_reduce(const float (&v)[32], float (&out)[2], int lane) { row_reduce32(v, out, lane); }
-__device__ __forceinline__ void row_store(float* p, const float (&o)[4]) { *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]); }
-__device__ __forceinline__ void row_store(float* p, const float (&o)[2]) { *reinterpret_cast<float2*>(p) = make_float2(o[0], o[1]); }
 
 // ---- the row walk (ROWS): every 16-lane DPP row (4x4 pixel block, dqo_lane_x / _y) of the quadrant wave walks ITS OWN sub-list ----
 // The forward's live byte of a (quadrant, list position) is a 4-bit row code: which rows have a pixel with work for the entry.  The
@@ -317,13 +265,9 @@ __device__ __forceinline__ void row_store(float* p, const float (&o)[2]) { *rein
                        // wave = four waves per SIMD (56: 11.7 KB, 3.5 waves, and 159 instead of 145 us on cfg 3 although it saves 3.6 % more steps)
 #endif
 constexpr int RG = DQO_BWD_RG;
-#ifndef DQO_BWD_ROW_NB
-#define DQO_BWD_ROW_NB 7  // steps per batch: 7 (63 of 64 values through row_reduce64) or 3 (27 of 32 through row_reduce32: fewer registers)
-#endif
-constexpr int RNB = DQO_BWD_ROW_NB;
-constexpr int RNV = RNB == 7 ? 64 : 32;     // values per lane and batch
-constexpr int RLS = RNB == 7 ? 8 : 4;       // list slots per batch (the last one is padding)
-static_assert(RNB == 7 || RNB == 3, "batches of 7 or 3 steps");
+constexpr int RNB = 7;   // steps per batch: 7 x 9 = 63 of 64 values through row_reduce64
+constexpr int RNV = 64;  // values per lane and batch
+constexpr int RLS = 8;   // list slots per batch (the last one is padding)
 static_assert(RG % RNB == 0 && RG >= RNB && (RG / RNB) * RLS <= 64 && (RG / RNB) * RLS - 2 < 63, "RG: whole batches, 64 list slots per row, slot 63 free");
 constexpr int R_ENT_W = 12;                          // words of an entry record: conic + opacity | x, y, object id, position | r, g, b, slot
 constexpr int R_ENT = 0;                             // [RG + 1] records (the last one: the dummy a finished row keeps stepping on)
@@ -364,25 +308,26 @@ __device__ __forceinline__ BwdTap tap_frame_scales(const DqoGeomLayout& g, const
     }
     return t;
 }
-// live entries per reduction batch: BWD_NB x 9 values go through one butterfly — 7 x 9 = 63 of 64 values (wave_reduce64), or
-// 3 x 9 = 27 of 32 (wave_reduce32: fewer registers -> more waves per SIMD)
+// live entries per reduction batch of the union walk: 7 x 9 = 63 of 64 values go through one butterfly (wave_reduce64)
+constexpr int BWD_NB = 7;
 // GATE: DqoObjectGate (an entry acts on a pixel only if the Gaussian's object id equals the pixel's owner id) — a template parameter,
 // so that the ungated kernel keeps its instruction stream.
-// SEGS: waves per quadrant.  1 = the wave described at the top of the file.  8 = DqoRastCtx.list_split, the counterpart of the
-// forward's split (rast_forward_blend.hip): the walk goes in rounds of SEGS chunks, chunk r * SEGS + w of round r by wave w.  Walking
+// SEGS: waves per quadrant.  1 = the single wave described at the top of the file, which does the row walk.  8 = the long lists of
+// DqoRastCtx.list_split, the counterpart of the forward's split (rast_forward_blend.hip): the union walk goes in rounds of SEGS
+// chunks, chunk r * SEGS + w of round r by wave w.  Walking
 // an entry maps the pixel's state (T, S) to (T / (1 - alpha), S + alpha (c - S)) — T is scaled, S goes through an affine map — so
 //   pass 1  every wave composes its chunk's maps per pixel: Q = prod 1 / (1 - alpha), and (A, B) with S_out = A + B S_in;
 //   scan    the state its chunk starts from = the round's start state sent through the chunks before it (one block barrier per round);
 //   pass 2  the walk itself on the chunk from that state: the gradient sums and records exactly as the single wave forms them.
 // The backward has no early exit, so unlike the forward nothing is evaluated that the single wave would have skipped; pass 1 costs
 // a quarter of pass 2.  T and S are grouped by chunk instead of strictly back to front: last-bit differences, like the forward's.
-template <int BWD_NB, bool GATE, int SEGS, bool ROWS = false>
+template <bool GATE, int SEGS>
 __device__ __forceinline__ void blend_quadrant_bwd(const DqoView& v, const DqoGeomLayout& g, const DqoImageLayout& img, const DqoBinLayout& bin,
                                                    const float* __restrict__ dL_dpixels, const float* __restrict__ dL_ddepths,
                                                    float* __restrict__ recs, uint8_t* __restrict__ valid, const int64_t capacity,
                                                    const DqoTapDev& tap, const DqoGateDev& gate, const int tile, const int quad, const int wave, const int lane, uint32_t* const lds, const int skip_over,
                                                    const uint2 range) {
-    static_assert(!ROWS || (SEGS == 1 && BWD_NB == 7), "the row walk is the single-wave walk");
+    constexpr bool ROWS = SEGS == 1;
     uint32_t* const blk = lds + wave * (ROWS ? ROWS_BLK : BWD_BLK);
     float4* const s_co = reinterpret_cast<float4*>(blk);
     float4* const s_xy = s_co + BWD_THREADS;
@@ -528,7 +473,7 @@ __device__ __forceinline__ void blend_quadrant_bwd(const DqoView& v, const DqoGe
     // No incoming gradient on any pixel of the quadrant (outside the loss mask): every term of every record would be an exact
     // zero, so nothing is written and the records stay invalid (= zero for the per-Gaussian sum).
     // An earlier backward over the same forward context (retain_graph=True, one autograd.grad call per loss term) may have
-    // written this quadrant's records and marked them valid: the marks are taken back, so that record_sum_kernel never adds a
+    // written this quadrant's records and marked them valid: the marks are taken back, so that the per-Gaussian sum never adds a
     // previous call's records (the workspace is the caller's and changes between calls) — the backward is a function of its
     // arguments only, like the reference's.
     if (__builtin_amdgcn_ballot_w64(dp0 != 0.f || dp1 != 0.f || dp2 != 0.f || ddep != 0.f) == 0ull) {
@@ -670,7 +615,7 @@ __device__ __forceinline__ void blend_quadrant_bwd(const DqoView& v, const DqoGe
                 const bool in = ((code >> r) & 1u) != 0u;
                 const unsigned long long m = __builtin_amdgcn_ballot_w64(in);
                 const int rk = below(m);
-                const int sidx = RNB == 7 ? rk + ((rk * 37) >> 8) : rk + ((rk * 43) >> 7);  // rk + rk / RNB for rk < 64: batch * RLS + step
+                const int sidx = rk + ((rk * 37) >> 8);  // rk + rk / 7 for rk < 64: batch * RLS + step
                 if (in) s_list[r * 64 + sidx] = (uint16_t)(lane * (R_ENT_W * 4));
                 where = in ? ((where & ~(0xffu << (8 * r))) | ((uint32_t)sidx << (8 * r))) : where;
                 nsteps = max(nsteps, (int)__popcll(m));
@@ -682,14 +627,8 @@ __device__ __forceinline__ void blend_quadrant_bwd(const DqoView& v, const DqoGe
             // ---- walk: seven steps per batch ----
             auto batch = [&](const int t, auto full_tag) {
                 constexpr bool FULL = decltype(full_tag)::value;
-                uint32_t lw[4];
-                if constexpr (RNB == 7) {
-                    const uint4 li = *reinterpret_cast<const uint4*>(list_row + t * 16);
-                    lw[0] = li.x, lw[1] = li.y, lw[2] = li.z, lw[3] = li.w;
-                } else {
-                    const uint2 li = *reinterpret_cast<const uint2*>(list_row + t * 8);
-                    lw[0] = li.x, lw[1] = li.y, lw[2] = lw[3] = 0u;
-                }
+                const uint4 li = *reinterpret_cast<const uint4*>(list_row + t * 16);
+                const uint32_t lw[4] = {li.x, li.y, li.z, li.w};
                 float v64[RNV];
 #pragma unroll
                 for (int i = 9 * RNB; i < RNV; i++) v64[i] = 0.f;
@@ -733,9 +672,9 @@ __device__ __forceinline__ void blend_quadrant_bwd(const DqoView& v, const DqoGe
                     v64[9 * b + 5] = r_ka, v64[9 * b + 6] = r_kb, v64[9 * b + 7] = r_kc, v64[9 * b + 8] = r_op;
                 }
                 // the row's sums of the batch's entries, as they are: part[row][batch][9 b + f] (every (row, entry) pair exists once)
-                float out[RNV / 16];
-                row_reduce(v64, out, lane);
-                row_store(part_lane + t * RNV, out);
+                float out[4];
+                row_reduce64(v64, out, lane);
+                *reinterpret_cast<float4*>(part_lane + t * RNV) = make_float4(out[0], out[1], out[2], out[3]);
             };
             {
                 int t = 0;
@@ -780,10 +719,9 @@ __device__ __forceinline__ void blend_quadrant_bwd(const DqoView& v, const DqoGe
     // of its dependency chains, not by the number of instructions: with a branch per entry the chain was one whole entry long.
     auto batch = [&](const int k0, auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
-        constexpr int NV = BWD_NB == 7 ? 64 : 32;
-        float v64[NV];
+        float v64[64];
 #pragma unroll
-        for (int i = 9 * BWD_NB; i < NV; i++) v64[i] = 0.f;
+        for (int i = 9 * BWD_NB; i < 64; i++) v64[i] = 0.f;
         uint32_t hitmask = 0u;  // entries of this batch that also carry depth-hit sums (wave-uniform)
 #pragma unroll
         for (int b = 0; b < BWD_NB; b++) {
@@ -813,7 +751,7 @@ __device__ __forceinline__ void blend_quadrant_bwd(const DqoView& v, const DqoGe
                 S2 += alpha * e2;
                 // Everything downstream of dL/dalpha * G is linear in per-Gaussian constants (opacity, conic, W/2, H/2):
                 // the wave only sums the pixel moments of q = G * dL/dalpha — q, q dx, q dy, q dx^2, q dx dy, q dy^2 — and
-                // gaussian_backward_kernel applies those constants once per Gaussian (backward.cu:964-994 does it per pair).
+                // the per-Gaussian chain (dqo_gauss_chain.h) applies those constants once per Gaussian (backward.cu:964-994 does it per pair).
                 const float q = G * dL_dalpha;
                 const float qx = q * dx, qy = q * dy;
                 r_c0 = dchannel_dcolor * dp0;
@@ -831,9 +769,7 @@ __device__ __forceinline__ void blend_quadrant_bwd(const DqoView& v, const DqoGe
             v64[9 * b + 0] = r_c0, v64[9 * b + 1] = r_c1, v64[9 * b + 2] = r_c2, v64[9 * b + 3] = r_mx, v64[9 * b + 4] = r_my;
             v64[9 * b + 5] = r_ka, v64[9 * b + 6] = r_kb, v64[9 * b + 7] = r_kc, v64[9 * b + 8] = r_op;
         }
-        float tot;
-        if constexpr (BWD_NB == 7) tot = wave_reduce64(v64, lane);
-        else tot = wave_reduce32(v64, lane);
+        const float tot = wave_reduce64(v64, lane);
         // lane 9 b + f stores float f (0..8) of entry b's 64-byte partial record; lanes 0..BWD_NB-1 mark the records valid
         // (1 = colour-path floats, 3 = depth-hit floats 9..13 present as well)
         const int kb = k0 + lane_b;
@@ -868,67 +804,51 @@ __device__ __forceinline__ void blend_quadrant_bwd(const DqoView& v, const DqoGe
         for (; k0 + BWD_NB <= cnt; k0 += BWD_NB) batch(k0, std::true_type{});
         if (k0 < cnt) batch(k0, std::false_type{});
     };
-    if (SEGS == 1) {
-        // chunk c covers list positions L-1-c*64 ... descending; lane l looks at position L-1-(c*64+l): lane order == walk order
-        lv_nx = (L - 1 - lane >= 0) ? live[L - 1 - lane] : (uint8_t)0;
-        for (int c = 0; c < chunks; c++) {
-            const int pos = L - 1 - (c * BWD_THREADS + lane);
-            const bool is_live = lv_nx != 0;
-            {
-                const int pn = pos - BWD_THREADS;
-                lv_nx = pn >= 0 ? live[pn] : (uint8_t)0;  // next chunk's live bytes, in flight while this chunk is processed
-            }
-            if (__builtin_amdgcn_ballot_w64(is_live) == 0ull) continue;
-            gather(pos, is_live);
-            walk_chunk();
+    // ---- rounds of SEGS chunks, chunk r * SEGS + w (in walk order) to wave w ----
+    float* const s_x = reinterpret_cast<float*>(lds + SEGS * BWD_BLK);  // [round parity][wave][Q, B, A0, A1, A2][lane]
+    float T_round = T_final, R0 = 0.f, R1 = 0.f, R2 = 0.f;              // the state at the start of the round (same bits in every wave)
+    int p_nx = L - 1 - (wave * BWD_THREADS + lane);
+    lv_nx = p_nx >= 0 ? live[p_nx] : (uint8_t)0;
+    for (int r = 0; r * SEGS < chunks; r++) {
+        const int pos = L - 1 - ((r * SEGS + wave) * BWD_THREADS + lane);
+        const bool is_live = lv_nx != 0;
+        {
+            const int pn = pos - SEGS * BWD_THREADS;
+            lv_nx = pn >= 0 ? live[pn] : (uint8_t)0;
         }
-    } else {
-        // ---- rounds of SEGS chunks, chunk r * SEGS + w (in walk order) to wave w ----
-        float* const s_x = reinterpret_cast<float*>(lds + SEGS * BWD_BLK);  // [round parity][wave][Q, B, A0, A1, A2][lane]
-        float T_round = T_final, R0 = 0.f, R1 = 0.f, R2 = 0.f;              // the state at the start of the round (same bits in every wave)
-        int p_nx = L - 1 - (wave * BWD_THREADS + lane);
-        lv_nx = p_nx >= 0 ? live[p_nx] : (uint8_t)0;
-        for (int r = 0; r * SEGS < chunks; r++) {
-            const int pos = L - 1 - ((r * SEGS + wave) * BWD_THREADS + lane);
-            const bool is_live = lv_nx != 0;
-            {
-                const int pn = pos - SEGS * BWD_THREADS;
-                lv_nx = pn >= 0 ? live[pn] : (uint8_t)0;
-            }
-            gather(pos, is_live);  // (no live entry, or a chunk past the front of the list: cnt = 0, the identity map)
-            // pass 1: the chunk's map of the pixel's state
-            float Q = 1.f, B = 1.f, A0 = 0.f, A1 = 0.f, A2 = 0.f;
+        gather(pos, is_live);  // (no live entry, or a chunk past the front of the list: cnt = 0, the identity map)
+        // pass 1: the chunk's map of the pixel's state
+        float Q = 1.f, B = 1.f, A0 = 0.f, A1 = 0.f, A2 = 0.f;
 #pragma unroll 2
-            for (int k = 0; k < cnt; k++) {
-                const float4 co = s_co[k], xy = s_xy[k], cs = s_rgb[k];
-                const int c0 = s_pos[k];
-                const float dx = xy.x - pixfx, dy = xy.y - pixfy;
-                const float power = dqo_power_pre(co.x, co.y, co.z, dx, dy);
-                const float alpha_x = fminf(0.99f, co.w * dqo_gauss(power));
-                const bool did_color = c0 < last_contrib && power <= 0.0f && alpha_x >= 1.0f / 255.0f && (!GATE || __float_as_int(xy.w) == owner);
-                const float alpha = did_color ? alpha_x : 0.f;
-                Q *= dqo_rcp(1.f - alpha);
-                A0 += alpha * (cs.x - A0), A1 += alpha * (cs.y - A1), A2 += alpha * (cs.z - A2);
-                B *= 1.f - alpha;
-            }
-            float* const xw = s_x + ((r & 1) * SEGS + wave) * BWD_XCH + lane;
-            xw[0 * BWD_THREADS] = Q, xw[1 * BWD_THREADS] = B, xw[2 * BWD_THREADS] = A0, xw[3 * BWD_THREADS] = A1, xw[4 * BWD_THREADS] = A2;
-            // (one barrier per round: the round after next writes this parity again, and the next round's barrier lies between)
-            __syncthreads();
-            // scan: the state this chunk starts from, and the state the next round starts from
-            float Tn = T_round, N0 = R0, N1 = R1, N2 = R2;
-#pragma unroll
-            for (int j = 0; j < SEGS; j++) {
-                if (j == wave) T = Tn, S0 = N0, S1 = N1, S2 = N2;
-                const float* xj = s_x + ((r & 1) * SEGS + j) * BWD_XCH + lane;
-                const float Bj = xj[1 * BWD_THREADS];
-                Tn *= xj[0 * BWD_THREADS];
-                N0 = xj[2 * BWD_THREADS] + Bj * N0, N1 = xj[3 * BWD_THREADS] + Bj * N1, N2 = xj[4 * BWD_THREADS] + Bj * N2;
-            }
-            T_round = Tn, R0 = N0, R1 = N1, R2 = N2;
-            // pass 2: the walk of the chunk from that state
-            walk_chunk();
+        for (int k = 0; k < cnt; k++) {
+            const float4 co = s_co[k], xy = s_xy[k], cs = s_rgb[k];
+            const int c0 = s_pos[k];
+            const float dx = xy.x - pixfx, dy = xy.y - pixfy;
+            const float power = dqo_power_pre(co.x, co.y, co.z, dx, dy);
+            const float alpha_x = fminf(0.99f, co.w * dqo_gauss(power));
+            const bool did_color = c0 < last_contrib && power <= 0.0f && alpha_x >= 1.0f / 255.0f && (!GATE || __float_as_int(xy.w) == owner);
+            const float alpha = did_color ? alpha_x : 0.f;
+            Q *= dqo_rcp(1.f - alpha);
+            A0 += alpha * (cs.x - A0), A1 += alpha * (cs.y - A1), A2 += alpha * (cs.z - A2);
+            B *= 1.f - alpha;
         }
+        float* const xw = s_x + ((r & 1) * SEGS + wave) * BWD_XCH + lane;
+        xw[0 * BWD_THREADS] = Q, xw[1 * BWD_THREADS] = B, xw[2 * BWD_THREADS] = A0, xw[3 * BWD_THREADS] = A1, xw[4 * BWD_THREADS] = A2;
+        // (one barrier per round: the round after next writes this parity again, and the next round's barrier lies between)
+        __syncthreads();
+        // scan: the state this chunk starts from, and the state the next round starts from
+        float Tn = T_round, N0 = R0, N1 = R1, N2 = R2;
+#pragma unroll
+        for (int j = 0; j < SEGS; j++) {
+            if (j == wave) T = Tn, S0 = N0, S1 = N1, S2 = N2;
+            const float* xj = s_x + ((r & 1) * SEGS + j) * BWD_XCH + lane;
+            const float Bj = xj[1 * BWD_THREADS];
+            Tn *= xj[0 * BWD_THREADS];
+            N0 = xj[2 * BWD_THREADS] + Bj * N0, N1 = xj[3 * BWD_THREADS] + Bj * N1, N2 = xj[4 * BWD_THREADS] + Bj * N2;
+        }
+        T_round = Tn, R0 = N0, R1 = N1, R2 = N2;
+        // pass 2: the walk of the chunk from that state
+        walk_chunk();
     }
 }
 
@@ -939,13 +859,13 @@ __device__ __forceinline__ void blend_quadrant_bwd(const DqoView& v, const DqoGe
 #ifndef DQO_BWD_ROWS_WAVES
 #define DQO_BWD_ROWS_WAVES 4  // the row walk's LDS (ROWS_BLK words per wave) leaves room for 4 waves per SIMD at RG = 42
 #endif
-template <int BWD_NB, bool GATE, bool ROWS = false>
-__global__ __launch_bounds__(BWD_THREADS * BWD_WPB, ROWS ? DQO_BWD_ROWS_WAVES : (BWD_NB == 7 ? 5 : 8)) void blend_backward_kernel(const DqoView v, DqoGeomLayout g, DqoImageLayout img,
+template <bool GATE>
+__global__ __launch_bounds__(BWD_THREADS * BWD_WPB, DQO_BWD_ROWS_WAVES) void blend_backward_kernel(const DqoView v, DqoGeomLayout g, DqoImageLayout img,
                                                                      DqoBinLayout bin, const float* __restrict__ dL_dpixels,
                                                                      const float* __restrict__ dL_ddepths,
                                                                      float* __restrict__ recs, uint8_t* __restrict__ valid,
                                                                      int64_t capacity, const DqoTapDev tap, const DqoGateDev gate) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[(ROWS ? ROWS_BLK : BWD_BLK) * BWD_WPB];
+    __shared__ __attribute__((aligned(16))) uint32_t lds[ROWS_BLK * BWD_WPB];
     const int wave = BWD_WPB > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
     const int lane = (int)(threadIdx.x & 63);
     // DqoLossTap: the first block also reports the loss (before the early exits below: block 0 may have no list)
@@ -958,8 +878,8 @@ __global__ __launch_bounds__(BWD_THREADS * BWD_WPB, ROWS ? DQO_BWD_ROWS_WAVES : 
     const uint4 si = img.slot_info[xg * T8 + (jg >> 2)];  // (tile, list start, list end) of the slot: one round
     const uint32_t tile_u = si.x;
     if (tile_u == 0xffffffffu) return;  // unused slot
-    blend_quadrant_bwd<BWD_NB, GATE, 1, ROWS>(v, g, img, bin, dL_dpixels, dL_ddepths, recs, valid, capacity, tap, gate, (int)tile_u, jg & 3, wave,
-                                               lane, lds, 0x7fffffff, make_uint2(si.y, si.z));
+    blend_quadrant_bwd<GATE, 1>(v, g, img, bin, dL_dpixels, dL_ddepths, recs, valid, capacity, tap, gate, (int)tile_u, jg & 3, wave, lane, lds,
+                                0x7fffffff, make_uint2(si.y, si.z));
 }
 
 // DqoRastCtx.list_split, the backward's half (the layout of blend_forward_split_kernel): blocks of eight waves; the first BSPLIT_GRID and
@@ -967,20 +887,19 @@ __global__ __launch_bounds__(BWD_THREADS * BWD_WPB, ROWS ? DQO_BWD_ROWS_WAVES : 
 // round; the blocks in between are eight independent single-wave walks, two tiles of one XCD band, skipping the long lists.
 constexpr int BSPLIT_RUNS = 8;
 constexpr int BSPLIT_GRID = 256;
-// LDS of a block: the eight waves' blocks + the pass-1 results of two round parities (long lists), or — ROWS: the short-list blocks walk
-// their lists like blend_backward_kernel<7, GATE, true>, the row walk — eight row-walk blocks: 72.7 KB, more than a kernel may declare
-// statically, so the array is the launch's dynamic LDS (two blocks per CU either way)
+// LDS of a block: the eight waves' blocks + the pass-1 results of two round parities (long lists), or eight row-walk blocks (short
+// lists, walked like blend_backward_kernel does): 72.7 KB, more than a kernel may declare statically, so the array is the launch's
+// dynamic LDS (two blocks per CU either way)
 constexpr int BSPLIT_LDS_SPLIT = BSPLIT_RUNS * BWD_BLK + 2 * BSPLIT_RUNS * BWD_XCH;
 constexpr int BSPLIT_LDS_ROWS = BSPLIT_RUNS * ROWS_BLK;
-template <bool ROWS>
-constexpr int bsplit_lds_words() { return (ROWS && BSPLIT_LDS_ROWS > BSPLIT_LDS_SPLIT) ? BSPLIT_LDS_ROWS : BSPLIT_LDS_SPLIT; }
-template <bool GATE, bool ROWS>
+constexpr int BSPLIT_LDS_WORDS = BSPLIT_LDS_ROWS > BSPLIT_LDS_SPLIT ? BSPLIT_LDS_ROWS : BSPLIT_LDS_SPLIT;
+template <bool GATE>
 __global__ __launch_bounds__(BWD_THREADS * BSPLIT_RUNS, 4) void blend_backward_split_kernel(const DqoView v, DqoGeomLayout g, DqoImageLayout img,
                                                                      DqoBinLayout bin, const float* __restrict__ dL_dpixels,
                                                                      const float* __restrict__ dL_ddepths,
                                                                      float* __restrict__ recs, uint8_t* __restrict__ valid,
                                                                      int64_t capacity, const DqoTapDev tap, const DqoGateDev gate) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];  // bsplit_lds_words<ROWS>() words
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];  // BSPLIT_LDS_WORDS words
     __shared__ uint32_t s_item;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
     if (tap.scale != nullptr && blockIdx.x == 0 && wave == 0) {
@@ -1002,8 +921,8 @@ __global__ __launch_bounds__(BWD_THREADS * BSPLIT_RUNS, 4) void blend_backward_s
                 return;
             }
             const int tile_s = (int)img.split_tiles[it >> 2];
-            blend_quadrant_bwd<7, GATE, BSPLIT_RUNS>(v, g, img, bin, dL_dpixels, dL_ddepths, recs, valid, capacity, tap, gate, tile_s,
-                                                     (int)(it & 3u), wave, lane, lds, 0x7fffffff, img.ranges[tile_s]);
+            blend_quadrant_bwd<GATE, BSPLIT_RUNS>(v, g, img, bin, dL_dpixels, dL_ddepths, recs, valid, capacity, tap, gate, tile_s,
+                                                  (int)(it & 3u), wave, lane, lds, 0x7fffffff, img.ranges[tile_s]);
             __syncthreads();  // (everyone has read this trip's ticket and the last round's pass-1 results)
         }
     }
@@ -1014,8 +933,8 @@ __global__ __launch_bounds__(BWD_THREADS * BSPLIT_RUNS, 4) void blend_backward_s
     if (slot >= T8) return;
     const uint32_t tile_u = img.tile_order[(b & 7) * T8 + slot];
     if (tile_u == 0xffffffffu) return;
-    blend_quadrant_bwd<7, GATE, 1, ROWS>(v, g, img, bin, dL_dpixels, dL_ddepths, recs, valid, capacity, tap, gate, (int)tile_u, wave & 3, wave, lane,
-                                         lds, fwd_split > 0 ? fwd_split : 0x7fffffff, img.ranges[tile_u]);
+    blend_quadrant_bwd<GATE, 1>(v, g, img, bin, dL_dpixels, dL_ddepths, recs, valid, capacity, tap, gate, (int)tile_u, wave & 3, wave, lane, lds,
+                                fwd_split > 0 ? fwd_split : 0x7fffffff, img.ranges[tile_u]);
 }
 
 }  // namespace
@@ -1048,61 +967,37 @@ int dqo_launch_tap_report(const DqoGeomLayout& g, const DqoTapDev& tap, hipStrea
 int dqo_launch_blend_backward(const DqoView& v, const DqoGeomLayout& g, const DqoImageLayout& img, const DqoBinLayout& bin, int T,
                               const float* dL_dcolor, const float* dL_ddepth, DqoGradRec* recs, uint8_t* valid, int64_t capacity,
                               const DqoTapDev& tap, const DqoGateDev& gate, int list_split, hipStream_t s) {
-    // DQO_BWD_NB=3 (measurement only) selects the 32-value butterfly: 55 instead of 81 VGPRs, 5.4 instead of 3.7 waves resident
-    // per SIMD — and 5 % SLOWER (round 2, profiles/README.md): the kernel is bound by VALU execution, not by latency
-    static const int nb = [] {
-        const char* e = getenv("DQO_BWD_NB");
-        return e ? atoi(e) : 7;
-    }();
     float* r = reinterpret_cast<float*>(recs);
-    // DQO_BWD_ROWS=0 (measurement / A-B only): the union walk (every entry on all 64 pixels of the quadrant) instead of the row walk
-    static const bool rows = [] {
-        const char* e = getenv("DQO_BWD_ROWS");
-        return e ? atoi(e) != 0 : true;
-    }();
     if (list_split > 0) {
         const dim3 grid(2 * BSPLIT_GRID + 8 * (((T + 7) / 8 + 1) / 2)), block(BWD_THREADS * BSPLIT_RUNS);
-        // (the row-walk variant's dynamic LDS is above the 64 KB a launch gets without asking: raised once per process and kernel)
-        static const int raised = [] {
-            const int bytes = bsplit_lds_words<true>() * 4;
-            hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&blend_backward_split_kernel<true, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&blend_backward_split_kernel<false, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            return (e1 == hipSuccess && e2 == hipSuccess) ? 1 : 0;
+        // (the dynamic LDS is above the 64 KB a launch gets without asking: raised once per process and kernel)
+        static const hipError_t raised = [] {
+            const int bytes = BSPLIT_LDS_WORDS * 4;
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&blend_backward_split_kernel<true>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&blend_backward_split_kernel<false>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+            return e;
         }();
-        const bool use_rows = rows && nb == 7 && raised != 0;
-#define DQO_BSPLIT(GT, RW)                                                                                                                 \
-    DQO_LAUNCH_SMEM("blend_backward_kernel", (blend_backward_split_kernel<GT, RW>), grid, block, (size_t)bsplit_lds_words<RW>() * 4, s, v, g, img, \
-                    bin, dL_dcolor, dL_ddepth, r, valid, capacity, tap, gate)
-        if (gate.gobj != nullptr) {
-            if (use_rows) DQO_BSPLIT(true, true);
-            else DQO_BSPLIT(true, false);
-        } else {
-            if (use_rows) DQO_BSPLIT(false, true);
-            else DQO_BSPLIT(false, false);
+        if (raised != hipSuccess) {
+            dqo_set_error("hipFuncSetAttribute(blend_backward_split_kernel, MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(raised));
+            return DQO_ERR_LAUNCH;
         }
-#undef DQO_BSPLIT
+        if (gate.gobj != nullptr)
+            DQO_LAUNCH_SMEM("blend_backward_kernel", blend_backward_split_kernel<true>, grid, block, (size_t)BSPLIT_LDS_WORDS * 4, s, v, g, img, bin,
+                            dL_dcolor, dL_ddepth, r, valid, capacity, tap, gate);
+        else
+            DQO_LAUNCH_SMEM("blend_backward_kernel", blend_backward_split_kernel<false>, grid, block, (size_t)BSPLIT_LDS_WORDS * 4, s, v, g, img, bin,
+                            dL_dcolor, dL_ddepth, r, valid, capacity, tap, gate);
         return DQO_OK;
     }
     const dim3 grid(8 * ((T + 7) / 8) * 4 / BWD_WPB);
-    if (rows && nb == 7) {
-        if (gate.gobj != nullptr)
-            DQO_LAUNCH("blend_backward_kernel", (blend_backward_kernel<7, true, true>), grid, dim3(BWD_THREADS * BWD_WPB), s, v, g, img, bin, dL_dcolor,
-                       dL_ddepth, r, valid, capacity, tap, gate);
-        else
-            DQO_LAUNCH("blend_backward_kernel", (blend_backward_kernel<7, false, true>), grid, dim3(BWD_THREADS * BWD_WPB), s, v, g, img, bin, dL_dcolor,
-                       dL_ddepth, r, valid, capacity, tap, gate);
-        return DQO_OK;
-    }
     if (gate.gobj != nullptr)
-        DQO_LAUNCH("blend_backward_kernel", (blend_backward_kernel<7, true>), grid, dim3(BWD_THREADS * BWD_WPB), s, v, g, img, bin, dL_dcolor, dL_ddepth, r,
-                   valid, capacity, tap, gate);
-    else if (nb == 7)
-        DQO_LAUNCH("blend_backward_kernel", (blend_backward_kernel<7, false>), grid, dim3(BWD_THREADS * BWD_WPB), s, v, g, img, bin, dL_dcolor, dL_ddepth, r,
+        DQO_LAUNCH("blend_backward_kernel", blend_backward_kernel<true>, grid, dim3(BWD_THREADS * BWD_WPB), s, v, g, img, bin, dL_dcolor, dL_ddepth, r,
                    valid, capacity, tap, gate);
     else
-        DQO_LAUNCH("blend_backward_kernel", (blend_backward_kernel<3, false>), grid, dim3(BWD_THREADS * BWD_WPB), s, v, g, img, bin, dL_dcolor, dL_ddepth, r,
+        DQO_LAUNCH("blend_backward_kernel", blend_backward_kernel<false>, grid, dim3(BWD_THREADS * BWD_WPB), s, v, g, img, bin, dL_dcolor, dL_ddepth, r,
                    valid, capacity, tap, gate);
     return DQO_OK;
 }

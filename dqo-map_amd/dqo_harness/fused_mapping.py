@@ -758,7 +758,7 @@ class FusedMapper:
         forward's blend kernel and its gradient is formed inside the backward's (DqoRastCtx.loss_tap: no loss kernels; self.loss is
         written by the backward).  fused_tail: the per-Gaussian half of the backward and the Adam step run as ONE kernel
         (dqo_rast_backward_adam: record sum -> per-Gaussian chain -> Adam per block of 256 Gaussians, gradient rows in LDS) instead of
-        three (gradient rows and summed records through HBM).  All three leave every parameter and moment bit for bit as it is without
+        two (gradient rows through HBM).  All three leave every parameter and moment bit for bit as it is without
         them.  reuse_probe: size the capacities from
         the previous capture's counts (scaled by the map's growth) instead of a probing forward — for a re-capture right after a small
         change of the map; falls back to probing if the eager iteration overflows.  unroll: iterations per graph — replay() then runs

@@ -209,8 +209,7 @@ def test_fused_mapper_with_split_lists_and_a_partial_render_mask(env):
 
 def test_the_split_kernels_walk_short_lists_exactly_like_the_unsplit_ones(env):
     """With a threshold that no list reaches the split launch has no long list: its short-list blocks — the serial forward wave, and in
-    the backward the ROW walk of blend_backward_kernel<7, GATE, true> since round 6 (the union walk until then: last-bit differences
-    in the record sums) — must give the outputs and the gradients of list_split = 0 bit for bit."""
+    the backward the row walk of blend_backward_kernel<GATE> — must give the outputs and the gradients of list_split = 0 bit for bit."""
     dgr = env
     cam, sc = scenes.make_config(3, P=30000)
     dL = _dL(cam, 9)
