@@ -371,6 +371,15 @@ def _inputs(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
                            campos=N.ptr(rs.campos), tile_mask=N.ptr(tile_mask), row_flags=N.ptr(row_flags))
 
 
+def _new_outputs(P, H, W, device):
+    """The op's nine outputs (colour, depth, hit ids, hit weights, T, n_touched, radii) and the DqoRastOutputs that points at them."""
+    f32, i32 = dict(dtype=torch.float32, device=device), dict(dtype=torch.int32, device=device)
+    out = (torch.empty((3, H, W), **f32), torch.empty((1, H, W), **f32), torch.empty((1, H, W), **i32), torch.empty((1, H, W), **i32),
+           torch.empty((1, H, W), **f32), torch.empty((1, H, W), **f32), torch.empty((1, H, W), **f32), torch.empty((P,), **i32),
+           torch.empty((P,), **i32))
+    return out, N.DqoRastOutputs(*(N.ptr(t) for t in out))
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask, raster_settings,
@@ -417,28 +426,15 @@ class _RasterizeGaussians(torch.autograd.Function):
                 gate.tile_objects = N.ptr(tile_objects)
         elif tile_objects is not None:
             raise RuntimeError("object gate: tile_objects without gaussian_object / pixel_object")
-        i32 = dict(dtype=torch.int32, device=dev)
-        f32 = dict(dtype=torch.float32, device=dev)
         u8 = dict(dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             stream = N.current_stream()
-            color = torch.empty((3, H, W), **f32)
-            depth = torch.empty((1, H, W), **f32)
-            hit_color = torch.empty((1, H, W), **i32)
-            hit_depth = torch.empty((1, H, W), **i32)
-            hit_color_weight = torch.empty((1, H, W), **f32)
-            hit_depth_weight = torch.empty((1, H, W), **f32)
-            T_map = torch.empty((1, H, W), **f32)
-            n_touched = torch.empty((P,), **i32)
-            radii = torch.empty((P,), **i32)
+            out, outputs = _new_outputs(P, H, W, dev)
+            _, _, hit_color, hit_depth, _, _, _, n_touched, radii = out
             geomBuffer = torch.empty((lib.dqo_rast_geom_bytes(P, W, H),), **u8)
             imgBuffer = torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8)
             params = _params(rs, P, M)
             inputs = _inputs(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask)
-            outputs = N.DqoRastOutputs(out_color=color.data_ptr(), out_depth=depth.data_ptr(), out_hit_color=hit_color.data_ptr(),
-                                       out_hit_depth=hit_depth.data_ptr(), out_hit_color_weight=hit_color_weight.data_ptr(),
-                                       out_hit_depth_weight=hit_depth_weight.data_ptr(), out_T=T_map.data_ptr(),
-                                       n_touched=N.ptr(n_touched), radii=N.ptr(radii))
             cctx = N.DqoRastCtx(geom=geomBuffer.data_ptr(), geom_bytes=geomBuffer.numel(), binning=None, binning_bytes=0,
                                 image=imgBuffer.data_ptr(), image_bytes=imgBuffer.numel(), inst_capacity=0, list_split=_list_split)
             if gate is not None:
@@ -561,7 +557,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.save_for_backward(colors_precomp, hit_depth, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
                               binningBuffer, imgBuffer, opacities, tile_mask if tile_mask is not None else torch.empty(0))
         ctx.mark_non_differentiable(hit_color, hit_depth, n_touched, radii)
-        return (color, depth, hit_color, hit_depth, hit_color_weight, hit_depth_weight, T_map, n_touched, radii)
+        return out
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_out_depth, grad_hit_color, grad_hit_depth, grad_hit_color_weight,

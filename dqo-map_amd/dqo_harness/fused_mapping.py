@@ -90,6 +90,37 @@ class _Ctx:
         pass
 
 
+class _FrameGraph:
+    """One captured mapping iteration of a FusedMapper (capture()): the frame's inputs, the options it was captured with, and the
+    capacities, buffers and C structs the capture fixed (the graph holds their addresses)."""
+
+    def __init__(self, frame, settings, pixel_object, tile_objects, gt_color, gt_depth, mask, tile_mask, options):
+        self.frame = frame  # slot of the window (None: the single-frame mapper's graph; (k, m): a mixed graph of _graph_of)
+        # the frame's inputs, read in place at every replay and rewritten in place by set_frame: the graph's own copies of the camera
+        # tensors, the gate's owner map and its tile sets (None: no gate), the target images, the uint8 render mask (None: unmasked)
+        self.settings, self.pixel_object, self.tile_objects = settings, pixel_object, tile_objects
+        self.gt_color, self.gt_depth, self.mask, self.tile_mask = gt_color, gt_depth, mask, tile_mask
+        # capture()'s options as passed (tile_buckets, keep_tile_order, loss_tap, fused_tail, list_split, unroll, run_unroll,
+        # short_bucket_margin): _recapture passes them again
+        self.options = options
+        self.stale = False  # the attach set / object gate changed since the capture: its kernel arguments point at freed buffers
+        self.cap = 0  # instance capacity
+        self.bucket = 0  # DqoRastCtx.tile_bucket_capacity (0: packed lists)
+        self.out = None  # the op's 9 outputs (dgr._new_outputs) of the last iteration
+        self.geom = self.img = self.binning = self.ws = None  # context buffers and the backward's workspace
+        self.grads = None  # gradient rows of the unfused tail (dict: means3D, sh, opacity, scales, rot)
+        self.grad_scale = None  # DqoLossTap.grad_scale
+        # the step state is the mapper's, shared by all its graphs (DqoAdamStep.step_dev: the Adam launch advances it itself through
+        # block_ticket; bias_table: the bias corrections, computed once per step)
+        self.step_dev = self.ticket = self.bias = None
+        self.params = self.inputs = self.outputs = self.cctx = self.cgrads = self.adam = None
+        self.tap = self.gate = None  # DqoLossTap (None: loss kernels), DqoObjectGate (None: no gate)
+        self.ls_fwd = self.ls_bwd = 0  # DqoRastCtx.list_split of the forward and of the backward call
+        self.fused_tail = False  # the per-Gaussian backward and Adam as one kernel (dqo_rast_backward_adam)
+        self.unroll, self.graph = 1, None  # iterations per replay(), the graph
+        self.run_unroll, self.run_graph = 1, None  # iterations per launch of replay_run's graph (None: run_unroll is 1)
+
+
 class FusedMapper:
     def __init__(self, scene, settings, device, lrs=None, betas=(0.9, 0.999), eps=1e-15, color_weight=mapping.COLOR_WEIGHT,
                  depth_weight=mapping.DEPTH_WEIGHT, add_depth_thres=0.1, sparse_moments=True, attach=True, attach_count_reducer=None):
@@ -119,8 +150,12 @@ class FusedMapper:
         self._expected_step, self._unsettled = 1, False
         # DqoAdamStep.block_ticket: the Adam launch advances the device step count itself (False: a one-thread launch behind it does)
         self.use_block_ticket = True
-        self._frames = []  # the captured graphs of a window (capture_window); self._g = the one replayed last / by default
+        self._g = None     # the graph replayed last / by default (a _FrameGraph)
+        self._frames = []  # the captured graphs of a window (capture_window)
         self._mixed = {}   # (k, m) -> graph of frame k's camera and target under frame m's masks (global_optimization's quirk)
+        self._window_kw, self._window_frames = {}, []  # capture_window's arguments: _graph_of captures mixed graphs from them
+        self._last_probe = None  # (candidates, longest list, P) the last capture was sized on: capture(reuse_probe=True)
+        self._side_stream = None  # grow()'s stream for the attach step (made once: creating a stream costs a growth step ~1 ms)
         # The reference keeps TWO clouds and trains one of them per mapping call while it renders one or both (mapper.py:533, 578,
         # 1119, 1199-1204).  One map here: DqoAdamStep.row_flags / DqoRastInputs.row_flags (bit 0 = not trained, bit 1 = not rendered),
         # rewritten in place by set_training_rows — a captured graph follows.
@@ -149,6 +184,7 @@ class FusedMapper:
         # DqoAdamStep.attach_gains: the attach term's two factors in device memory, rewritten in place by begin_mapping_call — a captured
         # graph survives a new mapping call
         self.attach_gains = torch.zeros((2,), dtype=torch.float32, device=device)
+        self.init_xyz = None  # init_stat: begin_mapping_call takes it
         self.begin_mapping_call(reset_optimizer=False)
         P = self.P
         f = dict(dtype=torch.float32, device=device)
@@ -192,10 +228,9 @@ class FusedMapper:
 
     # ------------------------------------------------------------------ the two clouds, per-call learning rates ---------
     def _graphs(self):
-        gs = [g for g in getattr(self, "_frames", []) if g is not None] + list(getattr(self, "_mixed", {}).values())
-        g = getattr(self, "_g", None)
-        if g is not None and all(g is not f for f in gs):
-            gs.append(g)
+        gs = [g for g in self._frames if g is not None] + list(self._mixed.values())
+        if self._g is not None and all(self._g is not f for f in gs):
+            gs.append(self._g)
         return gs
 
     _LR_ORDER = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")
@@ -277,14 +312,14 @@ class FusedMapper:
         mask = (torch.sigmoid(self.opacity_raw) < 0.9).reshape(-1)
         if self.alive is not None:
             mask &= self.alive.bool()  # (a spare row is no Gaussian of the map)
-        if getattr(self, "row_flags", None) is not None and self.row_flags.shape[0] == P:
+        if self.row_flags.shape[0] == P:
             mask &= (self.row_flags & N.ROW_FROZEN) == 0  # init_stat is the TRAINED cloud's (mapper.py:533-545, 1132-1137)
         if history:  # history_stat's members that only history_merge reads (mapper.py:535-540)
             if self.init_shs is not None and self.init_shs.shape[0] == P:
                 self.init_shs.copy_(self.shs), self.init_confidence.copy_(self.confidence)
             else:
                 self.init_shs, self.init_confidence = self.shs.clone(), self.confidence.clone()
-        same = getattr(self, "init_xyz", None) is not None and self.init_xyz.shape[0] == P and self.attach_mask.shape[0] == P
+        same = self.init_xyz is not None and self.init_xyz.shape[0] == P and self.attach_mask.shape[0] == P
         if same:
             self.init_xyz.copy_(self.xyz), self.init_scaling.copy_(self.scaling_raw), self.init_rotation.copy_(self.rotation_raw)
             self.attach_mask.copy_(mask)
@@ -302,12 +337,11 @@ class FusedMapper:
             if self.moment_live is not None:
                 self.moment_live.zero_()
             self.step_count = 0
-            if getattr(self, "_step_dev", None) is not None:
-                self._step_dev.fill_(1)
-                self._expected_step, self._unsettled = 1, False
-        for g in self._graphs():
-            if not (same and getattr(g, "attach_in_place", False)):
-                g.stale = True  # the captured kernel arguments (attach set buffers) were fixed at capture time
+            self._step_dev.fill_(1)
+            self._expected_step, self._unsettled = 1, False
+        if not same:  # the captured kernel arguments (attach set buffers) were fixed at capture time
+            for g in self._graphs():
+                g.stale = True
 
     def _count_attach_set(self):
         self.attach_count = int(self.attach_mask.sum().item()) if self.use_attach else 0
@@ -460,12 +494,9 @@ class FusedMapper:
             # answer afterwards) — on a stream and a host thread of its own (both sides wait on the host for small results in between
             # their kernels).  Round 4 started it behind the filter: the step's critical path was filter + attach.
             import threading
-            if not self._act_valid:
-                N.check(N.lib().dqo_map_activate(self.P, N.ptr(self.opacity_raw), N.ptr(self.scaling_raw), N.ptr(self.rotation_raw),
-                                                 N.ptr(self.opacity), N.ptr(self.scales), N.ptr(self.rotations), N.current_stream()))
-                self._act_valid = True
-            if getattr(self, "_side_stream", None) is None:
-                self._side_stream = torch.cuda.Stream(device=dev)  # (made once: creating a stream costs a growth step ~1 ms)
+            self.activate()
+            if self._side_stream is None:
+                self._side_stream = torch.cuda.Stream(device=dev)
             side, box = self._side_stream, {}
             side.wait_stream(torch.cuda.current_stream())
 
@@ -571,9 +602,8 @@ class FusedMapper:
                         # place, so the next step's filter / stable-only render see the row as unstable
                         stable_mask.index_fill_(0, rows, False)
                 # (a captured iteration starts from the activations its previous Adam launch left: bring them up to date for the new rows)
-                N.check(N.lib().dqo_map_activate(self.P, N.ptr(self.opacity_raw), N.ptr(self.scaling_raw), N.ptr(self.rotation_raw),
-                                                 N.ptr(self.opacity), N.ptr(self.scales), N.ptr(self.rotations), N.current_stream()))
-                self._act_valid = True
+                self._act_valid = False
+                self.activate()
                 self.begin_mapping_call(reset_optimizer=True)  # in place too: fresh moments, fresh init_stat, the new attach set
                 stats["in_place"] = True
                 return stats
@@ -649,10 +679,7 @@ class FusedMapper:
         sm = stable_mask.to(dev).bool().reshape(-1)
         if self.alive is not None:
             sm = sm & self.alive.bool()
-        if not self._act_valid:
-            N.check(N.lib().dqo_map_activate(self.P, N.ptr(self.opacity_raw), N.ptr(self.scaling_raw), N.ptr(self.rotation_raw),
-                                             N.ptr(self.opacity), N.ptr(self.scales), N.ptr(self.rotations), N.current_stream()))
-            self._act_valid = True
+        self.activate()
         # the stable cloud alone = the map with every other Gaussian parked behind the camera (culled before the binning, so the tile
         # lists are the stable cloud's), indices in map rows.  One quirk to carry over: a tile that renders nothing keeps the op's
         # zero fill, which the reference's `>= 0` test reads as a hit on Gaussian 0 OF THE STABLE CLOUD (F3 / rasterize_points.cu:79-89)
@@ -744,7 +771,7 @@ class FusedMapper:
         settings / pixel_object / frame (round 6, the frame set of a mapping call — capture_window drives them): the camera of THIS
         graph (default: the mapper's), its pixel -> owner map when the object gate is on (default: set_object_gate's), and the slot of
         the window it fills (None = a single-frame mapper: the graph replaces whatever was captured before).  Every graph has its own
-        context buffers, capacities and outputs; parameters, moments, activations, the device-side step count, the row flags, the
+        camera tensors (copies: set_frame rewrites them), context buffers, capacities and outputs; parameters, moments, activations, the device-side step count, the row flags, the
         confidence counter and the learning-rate table are the mapper's and shared.
 
         The capture fixes two capacities from the state it is taken on: the instance capacity (candidates x capacity_margin)
@@ -764,27 +791,28 @@ class FusedMapper:
         change of the map; falls back to probing if the eager iteration overflows.  unroll: iterations per graph — replay() then runs
         `unroll` iterations with one launch call (back-to-back graph launches leave the GPU idle for ~9 us each on MI355X; the
         iterations inside one graph follow each other without a gap); self._g.out / self.loss then show the last of them."""
-        lib = N.lib()
-        dev, P, M = self.device, self.P, self.M
+        dev = self.device
         st = self.settings if settings is None else _normalised_settings(settings, dev)
-        if settings is not None:  # (the graph's own copies: set_frame rewrites them in place)
-            st = st._replace(bg=st.bg.clone(), viewmatrix=st.viewmatrix.clone(), projmatrix=st.projmatrix.clone(), campos=st.campos.clone())
+        # (the graph's own copies: set_frame rewrites them in place)
+        st = st._replace(bg=st.bg.clone(), viewmatrix=st.viewmatrix.clone(), projmatrix=st.projmatrix.clone(), campos=st.campos.clone())
         H, W = int(st.image_height), int(st.image_width)
         if (H, W) != (int(self.settings.image_height), int(self.settings.image_width)):
             raise RuntimeError("FusedMapper.capture: every frame of a mapper has the mapper's image size")
-        f = dict(dtype=torch.float32, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        u8 = dict(dtype=torch.uint8, device=dev)
         tile_mask = self.tile_mask if tile_mask is None else _checked_tile_mask(tile_mask, dev, H, W)
-        call_kw = dict(tile_mask=tile_mask, capacity_margin=capacity_margin, tile_buckets=tile_buckets, keep_tile_order=keep_tile_order,
-                       loss_tap=loss_tap, fused_tail=fused_tail, list_split=list_split, unroll=unroll, run_unroll=run_unroll, settings=settings,
-                       pixel_object=pixel_object, frame=frame, short_bucket_margin=short_bucket_margin)
         pix_obj, tile_obj = self.pixel_object, self.tile_objects
         if pixel_object is not None:
             if self.gaussian_object is None:
                 raise RuntimeError("FusedMapper.capture: a per-frame pixel_object needs set_object_gate first")
             pix_obj = torch.as_tensor(pixel_object).to(dev, torch.int32).contiguous().reshape(H, W)
             tile_obj = tile_object_sets(pix_obj)
+        for name, t_, shape in (("gt_color", gt_color, (3, H, W)), ("gt_depth", gt_depth, (1, H, W))):
+            if t_.dtype != torch.float32 or not t_.is_cuda or not t_.is_contiguous() or tuple(t_.shape) != shape:
+                raise RuntimeError(f"FusedMapper.capture: {name} must be a contiguous float32 GPU tensor of shape {shape} "
+                                   "(the graph reads it in place at every replay)")
+        mask = None if render_mask is None else render_mask.to(torch.uint8).contiguous()
+        g = _FrameGraph(frame, st, pix_obj, tile_obj, gt_color, gt_depth, mask, tile_mask,
+                        dict(tile_buckets=tile_buckets, keep_tile_order=keep_tile_order, loss_tap=loss_tap, fused_tail=fused_tail,
+                             list_split=list_split, unroll=unroll, run_unroll=run_unroll, short_bucket_margin=short_bucket_margin))
         with torch.cuda.device(dev):
             # re-capture (e.g. after an overflow): replays of invalid frames did not advance the device-side step count
             # (DqoAdamStep.frame_header), the host count assumed they did — _settle_replays takes exactly those back; eager step()
@@ -792,163 +820,172 @@ class FusedMapper:
             self._settle_replays()
             if frame is None:
                 self._g, self._frames, self._mixed = None, [], {}
-            if not self._act_valid:
-                N.check(lib.dqo_map_activate(P, N.ptr(self.opacity_raw), N.ptr(self.scaling_raw), N.ptr(self.rotation_raw),
-                                             N.ptr(self.opacity), N.ptr(self.scales), N.ptr(self.rotations), N.current_stream()))
-                self._act_valid = True
-            # capacity: the reference's num_rendered of the current state (an upper bound of the instances kept) plus a margin
-            # for the Gaussians that move while the graph is being replayed; the device header flags an overflow.  The probe runs
-            # through the C ABI on buffers of its own (two header reads), so the operator's global state is not touched.
-            # (reuse_probe: the counts of the previous capture, scaled by the growth of the map since — for a re-capture right after a
-            # growth step, which changes the map by a fraction of a percent; if the eager iteration below overflows, the capture
-            # is redone with a real probe)
-            last = getattr(self, "_last_probe", None)
-            if reuse_probe and last is not None and last[2] > 0:
-                grown = max(1.0, P / last[2])
-                cand, longest = int(last[0] * grown) + 1, int(last[1] * grown) + 1
-            else:
-                reuse_probe = False
-                cand, longest = self._probe(tile_mask, st, pix_obj, tile_obj)
-            self._last_probe = (cand, longest, P)
-            cap = int(cand * capacity_margin) + 4096
-            g = self._g = type("G", (), {})()
-            g.cap = cap
-            g.settings, g.pixel_object, g.tile_objects = st, pix_obj, tile_obj
-            g.frame = frame
+            self.activate()
+            reuse_probe, longest = self._size_graph(g, capacity_margin, reuse_probe)
+            self._g = g
             if isinstance(frame, tuple):  # (camera / target of frame k, masks of frame m): global_optimization's second half
                 self._mixed[frame] = g
             elif frame is not None:
                 while len(self._frames) <= frame:
                     self._frames.append(None)
                 self._frames[frame] = g
-            # fixed per-tile list buckets (DqoRastCtx.tile_bucket_capacity): at least twice the longest list of the current state,
-            # a power of two; a tile that outgrows it raises the same overflow flag as running out of instance capacity
-            g.bucket = 0
-            if tile_buckets:
-                g.bucket = 256
-                while g.bucket < 2 * longest:
-                    g.bucket *= 2
-                # 1024 entries are what the per-tile sort launch reaches: while no list can be longer, the long-list sort launch is
-                # dropped (6 us of launch on a map whose lists are all short) — worth a smaller margin (short_bucket_margin, default
-                # 1.3 x the longest list; pass 2.0 to never trade margin for that launch) to stay there.  A tile that outgrows its
-                # bucket flags the frame (graph_overflowed(); run() / run_window() re-capture; the replays in between train nothing).
-                if g.bucket == 2048 and float(short_bucket_margin) * longest <= 1024:
-                    g.bucket = 1024
-            for name, t_, shape in (("gt_color", gt_color, (3, H, W)), ("gt_depth", gt_depth, (1, H, W))):
-                if t_.dtype != torch.float32 or not t_.is_cuda or not t_.is_contiguous() or tuple(t_.shape) != shape:
-                    raise RuntimeError(f"FusedMapper.capture: {name} must be a contiguous float32 GPU tensor of shape {shape} "
-                                       "(the graph reads it in place at every replay)")
-            g.gt_color, g.gt_depth = gt_color, gt_depth
-            g.mask = None if render_mask is None else render_mask.to(torch.uint8).contiguous()
-            g.tile_mask = tile_mask
-            g.stale = False
-            g.attach_in_place = True  # attach set, init_stat and its size are read from device memory at every replay
-            g.fused_tail = bool(fused_tail) and M <= 16
-            g.out = (torch.empty((3, H, W), **f), torch.empty((1, H, W), **f), torch.empty((1, H, W), **i32), torch.empty((1, H, W), **i32),
-                     torch.empty((1, H, W), **f), torch.empty((1, H, W), **f), torch.empty((1, H, W), **f), torch.empty((P,), **i32),
-                     torch.empty((P,), **i32))
-            g.geom = torch.empty((lib.dqo_rast_geom_bytes(P, W, H),), **u8)
-            g.img = torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8)
-            g.binning = torch.empty((lib.dqo_rast_binning_bytes_bucketed(cap, W, H, g.bucket),), **u8)
-            g.ws = torch.empty((lib.dqo_rast_backward_workspace_bytes(cap),), **u8)
-            # dL_dcolors / dL_dcov3D / dL_dmeans2D have no consumer in the mapping step: NULL = the backward does not store them
-            g.grads = dict(means3D=torch.empty((P, 3), **f), sh=torch.empty((P, M, 3), **f),
-                           opacity=torch.empty((P, 1), **f), scales=torch.empty((P, 3), **f), rot=torch.empty((P, 4), **f))
-            # the step state is the mapper's, shared by all its graphs (DqoAdamStep.step_dev: the Adam launch advances it itself through
-            # block_ticket; bias_table: the bias corrections, computed once per step)
-            g.step_dev, g.ticket, g.bias = self._step_dev, self._ticket, self._bias
-            self._step_dev.fill_(self.step_count + 1)
-            self._expected_step = self.step_count + 1
-            g.params = dgr._params(st, P, M)
-            g.inputs = dgr._inputs(st, self.xyz, self.shs, self._empty, self.opacity, self.scales, self.rotations, self._empty, g.tile_mask,
-                                   row_flags=self.row_flags)
-            o = g.out
-            g.outputs = N.DqoRastOutputs(out_color=o[0].data_ptr(), out_depth=o[1].data_ptr(), out_hit_color=o[2].data_ptr(),
-                                         out_hit_depth=o[3].data_ptr(), out_hit_color_weight=o[4].data_ptr(),
-                                         out_hit_depth_weight=o[5].data_ptr(), out_T=o[6].data_ptr(), n_touched=o[7].data_ptr(),
-                                         radii=o[8].data_ptr())
-            g.cctx = N.DqoRastCtx(geom=g.geom.data_ptr(), geom_bytes=g.geom.numel(), binning=g.binning.data_ptr(),
-                                  binning_bytes=g.binning.numel(), image=g.img.data_ptr(), image_bytes=g.img.numel(), inst_capacity=cap,
-                                  tile_bucket_capacity=g.bucket)
-            # (DqoRastCtx.list_split is read by the forward and by the backward call: _static_iteration sets it before each)
-            g.ls_fwd, g.ls_bwd = self.pick_list_split_pair(list_split, g.tile_mask, st, longest)
-            g.cctx.list_split = g.ls_fwd
-            g.list_split = list_split
-            # DqoLossTap: the masked loss is summed by the forward's blend kernel and its gradient images are formed inside the
-            # backward's (bit for bit what dqo_map_loss_fwd_bwd computes): no loss kernels, no passes over the full image
-            g.tap = None
-            if g.mask is None and self.ssim_weight != 0:
-                # the SSIM term's gradient is an image (an 11 x 11 window around every pixel): the tap, which forms sign(error) x weight
-                # inside the backward's blend kernel, cannot carry it -> loss kernels + gradient images (three more launches + the SSIM's three)
-                loss_tap = False
-            if loss_tap:
-                g.grad_scale = torch.zeros((2,), **f)
-                g.tap = N.DqoLossTap(gt_color=N.ptr(gt_color), gt_depth=N.ptr(gt_depth), render_mask=N.ptr(g.mask), out_color=o[0].data_ptr(),
-                                     out_depth=o[1].data_ptr(), color_weight=self.color_weight, depth_weight=self.depth_weight,
-                                     add_depth_thres=self.add_depth_thres, loss_out=N.ptr(self.loss), grad_scale=g.grad_scale.data_ptr(),
-                                     per_object=1 if (self.per_object_loss and self.gaussian_object is not None) else 0)
-                g.cctx.loss_tap = ctypes.addressof(g.tap)
-            g.gate = None
-            if self.gaussian_object is not None:
-                g.gate = N.DqoObjectGate(gaussian_object=N.ptr(self.gaussian_object), pixel_object=N.ptr(pix_obj), tile_objects=N.ptr(tile_obj))
-                g.cctx.object_gate = ctypes.addressof(g.gate)
-                if self.per_object_loss and not loss_tap:
-                    raise RuntimeError("FusedMapper.capture: the per-object loss is computed by the loss tap (loss_tap=True)")
-            gr = g.grads
-            g.cgrads = N.DqoRastGrads(dL_dmeans3D=gr["means3D"].data_ptr(), dL_dsh=gr["sh"].data_ptr(), dL_dcolors=None,
-                                      dL_dopacity=gr["opacity"].data_ptr(), dL_dscales=gr["scales"].data_ptr(),
-                                      dL_drotations=gr["rot"].data_ptr(), dL_dcov3D=None, dL_dmeans2D=None, skip_culled_rows=1)
-            stt = self.state
-            g.adam = N.DqoAdamStep(P=P, M=M, step=0, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, lr_xyz=self.lrs["xyz"],
-                                   lr_f_dc=self.lrs["f_dc"], lr_f_rest=self.lrs["f_rest"], lr_opacity=self.lrs["opacity"],
-                                   lr_scaling=self.lrs["scaling"], lr_rotation=self.lrs["rotation"], xyz=N.ptr(self.xyz), shs=N.ptr(self.shs),
-                                   opacity_raw=N.ptr(self.opacity_raw), scaling_raw=N.ptr(self.scaling_raw),
-                                   rotation_raw=N.ptr(self.rotation_raw), g_means3D=gr["means3D"].data_ptr(), g_sh=gr["sh"].data_ptr(),
-                                   g_opacity=gr["opacity"].data_ptr(), g_scales=gr["scales"].data_ptr(), g_rotations=gr["rot"].data_ptr(),
-                                   m_xyz=N.ptr(stt["xyz"][0]), m_shs=N.ptr(stt["shs"][0]), m_opacity=N.ptr(stt["opacity"][0]),
-                                   m_scaling=N.ptr(stt["scaling"][0]), m_rotation=N.ptr(stt["rotation"][0]), v_xyz=N.ptr(stt["xyz"][1]),
-                                   v_shs=N.ptr(stt["shs"][1]), v_opacity=N.ptr(stt["opacity"][1]), v_scaling=N.ptr(stt["scaling"][1]),
-                                   v_rotation=N.ptr(stt["rotation"][1]), act_opacity=N.ptr(self.opacity), act_scales=N.ptr(self.scales),
-                                   act_rotations=N.ptr(self.rotations), radii=o[8].data_ptr(), step_dev=g.step_dev.data_ptr(),
-                                   moment_live=N.ptr(self.moment_live), frame_header=g.geom.data_ptr(),
-                                   block_ticket=g.ticket.data_ptr() if self.use_block_ticket else None,
-                                   bias_table=g.bias.data_ptr() if self.use_block_ticket else None, row_flags=N.ptr(self.row_flags),
-                                   confidence=N.ptr(self.confidence) if self.count_confidence else None, lr_table=N.ptr(self.lr_table),
-                                   **self._attach_fields())
-            # one eager iteration on a side stream (warms every kernel up), then the capture
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._static_iteration()
-            torch.cuda.current_stream().wait_stream(side)
-            if self.graph_overflowed() and reuse_probe:  # the reused counts were too small after all: measure and start over
+            self._allocate_graph(g)
+            self._build_graph_structs(g, longest)
+            if not self._warm_up_and_record(g, reuse_probe):  # the reused counts were too small after all: measure and start over
                 self._last_probe = None
-                return self.capture(gt_color, gt_depth, render_mask, reuse_probe=False, **call_kw)
-            if not self.graph_overflowed():  # (an invalid frame is a no-op for the optimiser and its step count)
-                self.step_count += 1
-            # the eager iteration left its tile launch order in g.img; the replays keep it (DqoRastCtx.keep_tile_order: the order is
-            # a scheduling hint, and the lists of one camera change little between the iterations of a mapping call)
-            g.cctx.keep_tile_order = 1 if (g.bucket > 0 and keep_tile_order) else 0
-            # ... and start from the counters the previous iteration's per-Gaussian kernel cleared (DqoRastCtx.frame_prezeroed: no
-            # zero-fill launch in a replay; only dqo_rast_backward_adam clears them, so only with the fused tail)
-            g.cctx.frame_prezeroed = 1 if g.fused_tail else 0
-            g.graph = torch.cuda.CUDAGraph()
-            # thread_local: other threads of the process (e.g. a collective library's watchdog) may keep issuing runtime calls
-            g.unroll = max(1, int(unroll))
-            with torch.cuda.graph(g.graph, capture_error_mode="thread_local"):
-                for _ in range(g.unroll):
-                    self._static_iteration()
-            # run_unroll (capture_window): a SECOND graph over the same context buffers with that many iterations, for the stretches of a
-            # schedule that stay on one frame — the second half of local_optimize renders the newest frame only (mapper.py:574-576) —
-            # where one launch per iteration leaves the GPU idle for ~9 us between graphs (replay_run)
-            g.run_graph, g.run_unroll = None, max(1, int(run_unroll))
-            if g.run_unroll > 1:
-                g.run_graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g.run_graph, capture_error_mode="thread_local"):
-                    for _ in range(g.run_unroll):
-                        self._static_iteration()
-            self._expected_step = self.step_count + 1
+                return self._recapture(g, capacity_margin)
         return self
+
+    def _recapture(self, g, capacity_margin):
+        """capture() again for graph g on the current state, with a new capacity margin: its live inputs (set_frame may have rewritten
+        them), its camera, its window slot and the options it was captured with."""
+        own_pixel_object = self.gaussian_object is not None and g.pixel_object is not self.pixel_object
+        return self.capture(g.gt_color, g.gt_depth, g.mask, tile_mask=g.tile_mask, capacity_margin=capacity_margin, settings=g.settings,
+                            pixel_object=g.pixel_object if own_pixel_object else None, frame=g.frame, **g.options)
+
+    def _size_graph(self, g, capacity_margin, reuse_probe):
+        """The capacities of a new graph (g.cap, g.bucket).  Returns (whether the previous capture's counts were reused, the longest
+        tile list they assume)."""
+        # capacity: the reference's num_rendered of the current state (an upper bound of the instances kept) plus a margin
+        # for the Gaussians that move while the graph is being replayed; the device header flags an overflow.  The probe runs
+        # through the C ABI on buffers of its own (two header reads), so the operator's global state is not touched.
+        # (reuse_probe: the counts of the previous capture, scaled by the growth of the map since — for a re-capture right after a
+        # growth step, which changes the map by a fraction of a percent; if the eager iteration overflows, the capture
+        # is redone with a real probe)
+        P, last = self.P, self._last_probe
+        if reuse_probe and last is not None and last[2] > 0:
+            grown = max(1.0, P / last[2])
+            cand, longest = int(last[0] * grown) + 1, int(last[1] * grown) + 1
+        else:
+            reuse_probe = False
+            cand, longest = self._probe(g.tile_mask, g.settings, g.pixel_object, g.tile_objects)
+        self._last_probe = (cand, longest, P)
+        g.cap = int(cand * capacity_margin) + 4096
+        # fixed per-tile list buckets (DqoRastCtx.tile_bucket_capacity): at least twice the longest list of the current state,
+        # a power of two; a tile that outgrows it raises the same overflow flag as running out of instance capacity
+        if g.options["tile_buckets"]:
+            g.bucket = 256
+            while g.bucket < 2 * longest:
+                g.bucket *= 2
+            # 1024 entries are what the per-tile sort launch reaches: while no list can be longer, the long-list sort launch is
+            # dropped (6 us of launch on a map whose lists are all short) — worth a smaller margin (short_bucket_margin, default
+            # 1.3 x the longest list; pass 2.0 to never trade margin for that launch) to stay there.  A tile that outgrows its
+            # bucket flags the frame (graph_overflowed(); run() / run_window() re-capture; the replays in between train nothing).
+            if g.bucket == 2048 and float(g.options["short_bucket_margin"]) * longest <= 1024:
+                g.bucket = 1024
+        return reuse_probe, longest
+
+    def _allocate_graph(self, g):
+        """The persistent buffers of a new graph: outputs, context buffers, the backward's workspace and gradient rows."""
+        lib, dev, P, M = N.lib(), self.device, self.P, self.M
+        H, W = int(g.settings.image_height), int(g.settings.image_width)
+        f, u8 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.uint8, device=dev)
+        g.out, g.outputs = dgr._new_outputs(P, H, W, dev)
+        g.geom = torch.empty((lib.dqo_rast_geom_bytes(P, W, H),), **u8)
+        g.img = torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8)
+        g.binning = torch.empty((lib.dqo_rast_binning_bytes_bucketed(g.cap, W, H, g.bucket),), **u8)
+        g.ws = torch.empty((lib.dqo_rast_backward_workspace_bytes(g.cap),), **u8)
+        # dL_dcolors / dL_dcov3D / dL_dmeans2D have no consumer in the mapping step: NULL = the backward does not store them
+        g.grads = dict(means3D=torch.empty((P, 3), **f), sh=torch.empty((P, M, 3), **f),
+                       opacity=torch.empty((P, 1), **f), scales=torch.empty((P, 3), **f), rot=torch.empty((P, 4), **f))
+        g.step_dev, g.ticket, g.bias = self._step_dev, self._ticket, self._bias
+
+    def _build_graph_structs(self, g, longest):
+        """The C structs of a new graph's iteration over its buffers (their addresses are kernel arguments of the graph)."""
+        st, opt = g.settings, g.options
+        g.fused_tail = bool(opt["fused_tail"]) and self.M <= 16
+        g.params = dgr._params(st, self.P, self.M)
+        g.inputs = dgr._inputs(st, self.xyz, self.shs, self._empty, self.opacity, self.scales, self.rotations, self._empty, g.tile_mask,
+                               row_flags=self.row_flags)
+        g.cctx = N.DqoRastCtx(geom=g.geom.data_ptr(), geom_bytes=g.geom.numel(), binning=g.binning.data_ptr(),
+                              binning_bytes=g.binning.numel(), image=g.img.data_ptr(), image_bytes=g.img.numel(), inst_capacity=g.cap,
+                              tile_bucket_capacity=g.bucket)
+        # (DqoRastCtx.list_split is read by the forward and by the backward call: _static_iteration sets it before each)
+        g.ls_fwd, g.ls_bwd = self.pick_list_split_pair(opt["list_split"], g.tile_mask, st, longest)
+        g.cctx.list_split = g.ls_fwd
+        # DqoLossTap: the masked loss is summed by the forward's blend kernel and its gradient images are formed inside the
+        # backward's (bit for bit what dqo_map_loss_fwd_bwd computes): no loss kernels, no passes over the full image.
+        # The SSIM term's gradient (no render mask) is an image (an 11 x 11 window around every pixel): the tap, which forms
+        # sign(error) x weight inside the backward's blend kernel, cannot carry it -> loss kernels + gradient images (three more
+        # launches + the SSIM's three)
+        loss_tap = opt["loss_tap"] and not (g.mask is None and self.ssim_weight != 0)
+        if loss_tap:
+            g.grad_scale = torch.zeros((2,), dtype=torch.float32, device=self.device)
+            g.tap = N.DqoLossTap(gt_color=N.ptr(g.gt_color), gt_depth=N.ptr(g.gt_depth), render_mask=N.ptr(g.mask),
+                                 out_color=g.out[0].data_ptr(), out_depth=g.out[1].data_ptr(), color_weight=self.color_weight,
+                                 depth_weight=self.depth_weight, add_depth_thres=self.add_depth_thres, loss_out=N.ptr(self.loss),
+                                 grad_scale=g.grad_scale.data_ptr(),
+                                 per_object=1 if (self.per_object_loss and self.gaussian_object is not None) else 0)
+            g.cctx.loss_tap = ctypes.addressof(g.tap)
+        if self.gaussian_object is not None:
+            g.gate = N.DqoObjectGate(gaussian_object=N.ptr(self.gaussian_object), pixel_object=N.ptr(g.pixel_object),
+                                     tile_objects=N.ptr(g.tile_objects))
+            g.cctx.object_gate = ctypes.addressof(g.gate)
+            if self.per_object_loss and not loss_tap:
+                raise RuntimeError("FusedMapper.capture: the per-object loss is computed by the loss tap (loss_tap=True)")
+        gr = [g.grads[k].data_ptr() for k in ("means3D", "sh", "opacity", "scales", "rot")]
+        g.cgrads = N.DqoRastGrads(dL_dmeans3D=gr[0], dL_dsh=gr[1], dL_dcolors=None, dL_dopacity=gr[2], dL_dscales=gr[3],
+                                  dL_drotations=gr[4], dL_dcov3D=None, dL_dmeans2D=None, skip_culled_rows=1)
+        g.adam = self._adam_step_args(gr, radii=g.out[8].data_ptr(), frame_header=g.geom.data_ptr(), step_dev=g.step_dev)
+
+    def _warm_up_and_record(self, g, reuse_probe):
+        """One eager iteration of graph g (warms every kernel up), then the capture of its graphs.  Returns False, recording nothing, if
+        the iteration overflowed capacities sized on reused counts."""
+        self._step_dev.fill_(self.step_count + 1)
+        self._expected_step = self.step_count + 1
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._static_iteration()
+        torch.cuda.current_stream().wait_stream(side)
+        if not self.graph_overflowed():  # (an invalid frame is a no-op for the optimiser and its step count)
+            self.step_count += 1
+        elif reuse_probe:
+            return False
+        # the eager iteration left its tile launch order in g.img; the replays keep it (DqoRastCtx.keep_tile_order: the order is
+        # a scheduling hint, and the lists of one camera change little between the iterations of a mapping call)
+        g.cctx.keep_tile_order = 1 if (g.bucket > 0 and g.options["keep_tile_order"]) else 0
+        # ... and start from the counters the previous iteration's per-Gaussian kernel cleared (DqoRastCtx.frame_prezeroed: no
+        # zero-fill launch in a replay; only dqo_rast_backward_adam clears them, so only with the fused tail)
+        g.cctx.frame_prezeroed = 1 if g.fused_tail else 0
+        g.graph = torch.cuda.CUDAGraph()
+        # thread_local: other threads of the process (e.g. a collective library's watchdog) may keep issuing runtime calls
+        g.unroll = max(1, int(g.options["unroll"]))
+        with torch.cuda.graph(g.graph, capture_error_mode="thread_local"):
+            for _ in range(g.unroll):
+                self._static_iteration()
+        # run_unroll (capture_window): a SECOND graph over the same context buffers with that many iterations, for the stretches of a
+        # schedule that stay on one frame — the second half of local_optimize renders the newest frame only (mapper.py:574-576) —
+        # where one launch per iteration leaves the GPU idle for ~9 us between graphs (replay_run)
+        g.run_unroll = max(1, int(g.options["run_unroll"]))
+        if g.run_unroll > 1:
+            g.run_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g.run_graph, capture_error_mode="thread_local"):
+                for _ in range(g.run_unroll):
+                    self._static_iteration()
+        self._expected_step = self.step_count + 1
+        return True
+
+    def _adam_step_args(self, grads, radii, frame_header, step=0, step_dev=None):
+        """The DqoAdamStep of one iteration over this mapper's parameters, moments and activations.  grads: the five gradient-row
+        pointers (means3D, sh, opacity, scales, rotations).  step_dev (the captured path): the device-side step count, with the
+        block ticket and bias table when use_block_ticket is on and the learning rates from lr_table; without it (eager step()) the
+        launch takes `step` and the learning rates as arguments."""
+        stt, ticket = self.state, step_dev is not None and self.use_block_ticket
+        return N.DqoAdamStep(P=self.P, M=self.M, step=step, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, lr_xyz=self.lrs["xyz"],
+                             lr_f_dc=self.lrs["f_dc"], lr_f_rest=self.lrs["f_rest"], lr_opacity=self.lrs["opacity"],
+                             lr_scaling=self.lrs["scaling"], lr_rotation=self.lrs["rotation"], xyz=N.ptr(self.xyz), shs=N.ptr(self.shs),
+                             opacity_raw=N.ptr(self.opacity_raw), scaling_raw=N.ptr(self.scaling_raw),
+                             rotation_raw=N.ptr(self.rotation_raw), g_means3D=grads[0], g_sh=grads[1], g_opacity=grads[2],
+                             g_scales=grads[3], g_rotations=grads[4], m_xyz=N.ptr(stt["xyz"][0]), m_shs=N.ptr(stt["shs"][0]),
+                             m_opacity=N.ptr(stt["opacity"][0]), m_scaling=N.ptr(stt["scaling"][0]), m_rotation=N.ptr(stt["rotation"][0]),
+                             v_xyz=N.ptr(stt["xyz"][1]), v_shs=N.ptr(stt["shs"][1]), v_opacity=N.ptr(stt["opacity"][1]),
+                             v_scaling=N.ptr(stt["scaling"][1]), v_rotation=N.ptr(stt["rotation"][1]), act_opacity=N.ptr(self.opacity),
+                             act_scales=N.ptr(self.scales), act_rotations=N.ptr(self.rotations), radii=radii, step_dev=N.ptr(step_dev),
+                             moment_live=N.ptr(self.moment_live), frame_header=frame_header,
+                             block_ticket=N.ptr(self._ticket) if ticket else None, bias_table=N.ptr(self._bias) if ticket else None,
+                             row_flags=N.ptr(self.row_flags), confidence=N.ptr(self.confidence) if self.count_confidence else None,
+                             lr_table=N.ptr(self.lr_table) if step_dev is not None else None, **self._attach_fields())
 
     # ------------------------------------------------------------------ the frame set of a mapping call -----------------
     def _snapshot_state(self):
@@ -1049,11 +1086,7 @@ class FusedMapper:
                 for k in bad:
                     g = self._graph_of(k)
                     snap = self._snapshot_state()
-                    self.capture(g.gt_color, g.gt_depth, g.mask, tile_mask=g.tile_mask, capacity_margin=capacity_margin,
-                                 tile_buckets=g.bucket > 0, keep_tile_order=bool(g.cctx.keep_tile_order) or g.bucket > 0,
-                                 loss_tap=g.tap is not None, fused_tail=g.fused_tail, list_split=g.list_split, unroll=g.unroll,
-                                 run_unroll=getattr(g, "run_unroll", 1),
-                                 settings=g.settings, pixel_object=g.pixel_object if self.gaussian_object is not None else None, frame=k)
+                    self._recapture(g, capacity_margin)
                     self._restore_state(snap)
                     recaptures += 1
                 for j in range(lost):
@@ -1167,19 +1200,13 @@ class FusedMapper:
         if pixel_object is None:
             pixel_object, tile_objects = self.pixel_object, self.tile_objects
         H, W = int(st.image_height), int(st.image_width)
-        f, i32, u8 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev), dict(dtype=torch.uint8, device=dev)
-        out = [torch.empty((3, H, W), **f), torch.empty((1, H, W), **f), torch.empty((1, H, W), **i32), torch.empty((1, H, W), **i32),
-               torch.empty((1, H, W), **f), torch.empty((1, H, W), **f), torch.empty((1, H, W), **f), torch.empty((P,), **i32),
-               torch.empty((P,), **i32)]
+        u8 = dict(dtype=torch.uint8, device=dev)
+        out, outputs = dgr._new_outputs(P, H, W, dev)
         geom = torch.empty((lib.dqo_rast_geom_bytes(P, W, H),), **u8)
         img = torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8)
         params = dgr._params(st, P, M)
         inputs = dgr._inputs(st, self.xyz, self.shs, self._empty, self.opacity, self.scales, self.rotations, self._empty, tile_mask,
                              row_flags=self.row_flags)
-        outputs = N.DqoRastOutputs(out_color=out[0].data_ptr(), out_depth=out[1].data_ptr(), out_hit_color=out[2].data_ptr(),
-                                   out_hit_depth=out[3].data_ptr(), out_hit_color_weight=out[4].data_ptr(),
-                                   out_hit_depth_weight=out[5].data_ptr(), out_T=out[6].data_ptr(), n_touched=out[7].data_ptr(),
-                                   radii=out[8].data_ptr())
         cctx = N.DqoRastCtx(geom=geom.data_ptr(), geom_bytes=geom.numel(), binning=None, binning_bytes=0, image=img.data_ptr(),
                             image_bytes=img.numel(), inst_capacity=0)
         if self.gaussian_object is not None:
@@ -1240,37 +1267,18 @@ class FusedMapper:
         (None: the one replayed last / the single-frame mapper's); outputs are the persistent tensors in self._g.out."""
         if frame is not None:
             self._g = self._graph_of(frame)
-        g = self._g
-        if g.stale:
-            raise RuntimeError("FusedMapper: the attach set / object gate changed since capture(); capture again")
-        if self._expected_step != self.step_count + 1:  # eager step() calls in between: resynchronise the device-side step count
-            self._resync_step_count()
-        g.graph.replay()
-        self._unsettled = True
-        self._attach_n = ((self.P + 255) // 256) * (4 if g.fused_tail else 1)  # (a new mapping call in between had reset it)
-        self.step_count += g.unroll  # (assumes valid frames; _settle_replays re-reads the device-side count)
-        self._expected_step = self.step_count + 1
-        return g.out
+        return self._launch(self._g, self._g.graph, self._g.unroll)
 
     def replay_run(self, frame, n):
         """n consecutive iterations on ONE frame of the window: launches of the frame's run graph (capture_window(run_unroll=k): k
         iterations each) while at least k remain, single launches for the rest — the same kernels in the same order as n replay(frame)
         calls, bit for bit.  Returns the outputs like replay()."""
         g = self._graph_of(frame)
-        k = getattr(g, "run_unroll", 1)
+        k = g.run_unroll
         out = None
         while n >= k and k > 1:
             self._g = g
-            if g.stale:
-                raise RuntimeError("FusedMapper: the attach set / object gate changed since capture(); capture again")
-            if self._expected_step != self.step_count + 1:
-                self._resync_step_count()
-            g.run_graph.replay()
-            self._unsettled = True
-            self._attach_n = ((self.P + 255) // 256) * (4 if g.fused_tail else 1)
-            self.step_count += k
-            self._expected_step = self.step_count + 1
-            out = g.out
+            out = self._launch(g, g.run_graph, k)
             n -= k
         for _ in range(n):
             out = self.replay(frame=frame)
@@ -1292,7 +1300,7 @@ class FusedMapper:
         expected after the last replay is the number of invalid replays — taken back here, BEFORE anything else (an eager step(), a
         re-capture, a resynchronisation) builds on the host count or overwrites the device count.  One 4-byte read, and only when
         replays happened since the last time."""
-        if not getattr(self, "_unsettled", False):
+        if not self._unsettled:
             return
         dev_step = int(self._step_dev.item())
         invalid = int(self._expected_step) - dev_step
@@ -1313,8 +1321,7 @@ class FusedMapper:
         optimiser (DqoAdamStep.frame_header: parameters, moments and the device step count are untouched), so the graph is captured
         again on the current state with `capacity_margin` and the missing iterations are replayed.  Returns the number of
         re-captures.  The inputs of the last capture() (ground-truth images, masks) are reused."""
-        g = self._g
-        if g.unroll != 1:
+        if self._g.unroll != 1:
             raise RuntimeError("FusedMapper.run counts single iterations: capture with unroll=1")
         target = self.step_count + n_iters
         recaptures = 0
@@ -1327,27 +1334,30 @@ class FusedMapper:
             if int(self._step_dev.item()) - 1 != self.step_count or self.graph_overflowed():
                 if recaptures > 8:
                     raise RuntimeError("FusedMapper.run: the map keeps outgrowing the captured capacities")
-                g = self._g
                 # (capture() re-reads the device-side step count: the valid replays of this batch stay counted, the others do not)
-                self.capture(g.gt_color, g.gt_depth, g.mask, tile_mask=g.tile_mask, capacity_margin=capacity_margin,
-                             tile_buckets=g.bucket > 0, keep_tile_order=bool(g.cctx.keep_tile_order) or g.bucket > 0, loss_tap=g.tap is not None,
-                             fused_tail=g.fused_tail, list_split=g.list_split, run_unroll=getattr(g, "run_unroll", 1),
-                             settings=g.settings if g.settings is not self.settings else None,
-                             pixel_object=g.pixel_object if (self.gaussian_object is not None and g.pixel_object is not self.pixel_object) else None,
-                             frame=g.frame)
+                self._recapture(self._g, capacity_margin)
                 recaptures += 1
         return recaptures
 
     def step_static(self):
         """One iteration over the persistent buffers issued eagerly — exactly the calls the captured graph holds (for per-kernel
         profiling: events cannot be recorded inside a replay)."""
-        g = self._g
-        if self._expected_step != self.step_count + 1:
+        return self._launch(self._g, None, 1)
+
+    def _launch(self, g, graph, n):
+        """n iterations of graph g: a launch of `graph` (one of g's captured graphs), or None = g's calls issued eagerly (n = 1)."""
+        if g.stale:
+            raise RuntimeError("FusedMapper: the attach set / object gate changed since capture(); capture again")
+        if self._expected_step != self.step_count + 1:  # eager step() calls in between: resynchronise the device-side step count
             self._resync_step_count()
-        with torch.cuda.device(self.device):
-            self._static_iteration()
+        if graph is None:
+            with torch.cuda.device(self.device):
+                self._static_iteration()
+        else:
+            graph.replay()
         self._unsettled = True
-        self.step_count += 1
+        self._attach_n = ((self.P + 255) // 256) * (4 if g.fused_tail else 1)  # (a new mapping call in between had reset it)
+        self.step_count += n  # (assumes valid frames; _settle_replays re-reads the device-side count)
         self._expected_step = self.step_count + 1
         return g.out
 
@@ -1368,13 +1378,10 @@ class FusedMapper:
     def step(self, gt_color, gt_depth, render_mask, tile_mask=None):
         """One mapping iteration; returns the op's 9-tuple (views of this iteration's outputs) — losses are in self.loss."""
         lib = N.lib()
-        P, M = self.P, self.M
         self._settle_replays()  # (replays of invalid frames since the last check do not count: this step's bias corrections depend on it)
         with torch.cuda.device(self.device):
             stream = N.current_stream()
-            if not self._act_valid:  # later iterations get the activations from the previous Adam step
-                N.check(lib.dqo_map_activate(P, N.ptr(self.opacity_raw), N.ptr(self.scaling_raw), N.ptr(self.rotation_raw),
-                                             N.ptr(self.opacity), N.ptr(self.scales), N.ptr(self.rotations), stream))
+            self.activate()  # (later iterations get the activations from the previous Adam step)
             ctx = _Ctx()
             out = dgr._RasterizeGaussians.forward(ctx, self.xyz, self.shs, self._empty, self.opacity, self.scales, self.rotations,
                                                   self._empty, self.tile_mask if tile_mask is None else tile_mask, self.settings,
@@ -1404,24 +1411,9 @@ class FusedMapper:
                     self._ssim_term(N.ptr(color), gt_color, stream)
             ctx.sparse_grad_rows = True  # gradient rows of culled Gaussians stay unwritten; the Adam kernel gets radii instead
             grads = dgr._RasterizeGaussians.backward(ctx, self.dL_dcolor, self.dL_ddepth, None, None, None, None, None, None, None)
-            g_means3D, g_sh, _, g_opacity, g_scales, g_rot = grads[0], grads[1], grads[2], grads[3], grads[4], grads[5]
             self.step_count += 1
-            st = N.DqoAdamStep(P=P, M=M, step=self.step_count, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
-                               lr_xyz=self.lrs["xyz"], lr_f_dc=self.lrs["f_dc"], lr_f_rest=self.lrs["f_rest"],
-                               lr_opacity=self.lrs["opacity"], lr_scaling=self.lrs["scaling"], lr_rotation=self.lrs["rotation"],
-                               xyz=N.ptr(self.xyz), shs=N.ptr(self.shs), opacity_raw=N.ptr(self.opacity_raw),
-                               scaling_raw=N.ptr(self.scaling_raw), rotation_raw=N.ptr(self.rotation_raw), g_means3D=N.ptr(g_means3D),
-                               g_sh=N.ptr(g_sh), g_opacity=N.ptr(g_opacity), g_scales=N.ptr(g_scales), g_rotations=N.ptr(g_rot),
-                               m_xyz=N.ptr(self.state["xyz"][0]), m_shs=N.ptr(self.state["shs"][0]),
-                               m_opacity=N.ptr(self.state["opacity"][0]), m_scaling=N.ptr(self.state["scaling"][0]),
-                               m_rotation=N.ptr(self.state["rotation"][0]), v_xyz=N.ptr(self.state["xyz"][1]),
-                               v_shs=N.ptr(self.state["shs"][1]), v_opacity=N.ptr(self.state["opacity"][1]),
-                               v_scaling=N.ptr(self.state["scaling"][1]), v_rotation=N.ptr(self.state["rotation"][1]),
-                               act_opacity=N.ptr(self.opacity), act_scales=N.ptr(self.scales), act_rotations=N.ptr(self.rotations),
-                               radii=N.ptr(out[8]), moment_live=N.ptr(self.moment_live), frame_header=N.ptr(ctx.saved_tensors[8]),
-                               row_flags=N.ptr(self.row_flags), confidence=N.ptr(self.confidence) if self.count_confidence else None,
-                               **self._attach_fields())
+            st = self._adam_step_args([N.ptr(grads[i]) for i in (0, 1, 3, 4, 5)], radii=N.ptr(out[8]),
+                                      frame_header=N.ptr(ctx.saved_tensors[8]), step=self.step_count)
             N.check(lib.dqo_map_adam_step(ctypes.byref(st), stream))
-            self._attach_n = (P + 255) // 256
-            self._act_valid = True
+            self._attach_n = (self.P + 255) // 256
         return out

@@ -319,6 +319,25 @@ def test_fused_tail_is_a_noop_on_an_overflowed_frame(env):
     assert torch.equal(fm.moment_live, live_before)
 
 
+def test_step_static_refuses_a_stale_graph(env):
+    """A graph whose object gate changed since its capture points at buffers the change dropped: step_static() raises like replay()
+    instead of issuing the captured calls, and counts no iteration."""
+    torch = env
+    from dqo_harness.fused_mapping import FusedMapper
+    cam, scene, settings, gt_color, gt_depth, mask, dev = _problem(torch)
+    fm = FusedMapper(scene, settings, dev)
+    fm.capture(gt_color, gt_depth, mask)
+    fm.step_static()
+    assert fm.step_count == 2
+    fm.set_object_gate(None, None)
+    assert fm._g.stale
+    with pytest.raises(RuntimeError, match="capture again"):
+        fm.step_static()
+    with pytest.raises(RuntimeError, match="capture again"):
+        fm.replay()
+    assert fm.step_count == 2
+
+
 def test_loss_tap_equals_the_loss_kernels(env):
     """DqoRastCtx.loss_tap: the masked loss summed inside the forward's blend kernel and its gradient formed inside the backward's
     must train exactly like the two loss kernels between them — same counts, same gradient scale, hence bit-identical parameters and
@@ -368,19 +387,15 @@ def test_loss_tap_on_an_empty_map(env):
     cam, scene, settings, gt_color, gt_depth, mask, dev = _problem(torch)
     lib = N.lib()
     H, W = cam.H, cam.W
-    f, i32, u8 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev), dict(dtype=torch.uint8, device=dev)
+    f, u8 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.uint8, device=dev)
     st = settings._replace(bg=torch.tensor([0.2, 0.4, 0.6], **f))
-    out = [torch.empty((3, H, W), **f), torch.empty((1, H, W), **f), torch.empty((1, H, W), **i32), torch.empty((1, H, W), **i32),
-           torch.empty((1, H, W), **f), torch.empty((1, H, W), **f), torch.empty((1, H, W), **f), torch.empty((0,), **i32), torch.empty((0,), **i32)]
+    out, outputs = dgr._new_outputs(0, H, W, dev)
     geom = torch.empty((lib.dqo_rast_geom_bytes(0, W, H),), **u8)
     img = torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8)
     binning = torch.empty((lib.dqo_rast_binning_bytes(1),), **u8)
     e = torch.empty((0,), **f)
     params = dgr._params(st, 0, 16)
     inputs = dgr._inputs(st, e, e, e, e, e, e, e, None)
-    outputs = N.DqoRastOutputs(out_color=out[0].data_ptr(), out_depth=out[1].data_ptr(), out_hit_color=out[2].data_ptr(),
-                               out_hit_depth=out[3].data_ptr(), out_hit_color_weight=out[4].data_ptr(), out_hit_depth_weight=out[5].data_ptr(),
-                               out_T=out[6].data_ptr(), n_touched=None, radii=None)
     loss, scale = torch.full((8,), -1.0, **f), torch.full((2,), -1.0, **f)
     m8 = mask.to(torch.uint8).contiguous()
     tap = N.DqoLossTap(gt_color=N.ptr(gt_color), gt_depth=N.ptr(gt_depth), render_mask=N.ptr(m8), out_color=out[0].data_ptr(),

@@ -356,6 +356,34 @@ def test_set_frame_rewrites_a_captured_frame_in_place(env):
         assert torch.equal(x, y)
 
 
+def test_set_frame_moves_only_its_own_camera(env):
+    """Frames captured with the mapper's camera (no settings= of their own) each keep a copy of it: a new camera for one of them
+    (set_frame(k, settings=...)) leaves the other frames' cameras, the mapper's camera and the next eager step() as they were."""
+    torch, _ = env
+    from dqo_harness.fused_mapping import FusedMapper
+    P = 12000
+    sc, cams, frames, dev = _window_problem(torch, P, 2, seed=2)
+    cam_names = ("bg", "viewmatrix", "projmatrix", "campos")
+    st0 = frames[0]["settings"]
+    cam0 = {n: getattr(st0, n).clone() for n in cam_names}
+    fm = FusedMapper(sc, st0, dev)
+    twin = FusedMapper(sc, st0._replace(**cam0), dev)
+    fm.capture_window([{k: v for k, v in fr.items() if k != "settings"} for fr in frames], loss_tap=True, fused_tail=True)
+    fm.set_frame(0, settings=frames[1]["settings"])
+    for n in cam_names:
+        assert torch.equal(getattr(fm._frames[0].settings, n), getattr(frames[1]["settings"], n)), n
+        assert torch.equal(getattr(fm._frames[1].settings, n), cam0[n]), n
+        assert torch.equal(getattr(fm.settings, n), cam0[n]), n
+    f0 = frames[0]
+    outs = [m.step(f0["gt_color"], f0["gt_depth"], f0["render_mask"]) for m in (fm, twin)]
+    torch.cuda.synchronize()
+    for x, y in zip(*outs):
+        assert torch.equal(x, y)
+    assert torch.equal(fm.loss, twin.loss)
+    for k in fm._params():
+        assert torch.equal(fm._params()[k], twin._params()[k]), k
+
+
 def test_run_window_recaptures_a_frame_that_outgrew_its_capacities(env):
     """run_window(): one frame of the window is captured with room for 5 % of its candidate pairs — its replays are invalid frames, no-ops
     for the optimiser (parameters, moments, confidence, step count untouched); run_window notices from the device step count, captures
