@@ -50,6 +50,16 @@ class DqoRastGrads(ctypes.Structure):
                                     "dL_dmeans2D")] + [("skip_culled_rows", c_i32)]
 
 
+class DqoRastParamInputs(ctypes.Structure):
+    """The parameter form's raw inputs (dqo_rast_*_params, ABI 5 symbols-only addition)."""
+    _fields_ = [("features_dc", c_vp), ("features_rest", c_vp), ("rest", c_i32), ("opacity_raw", c_vp), ("scaling_raw", c_vp),
+                ("rotation_raw", c_vp)]
+
+
+class DqoRastParamGrads(ctypes.Structure):
+    _fields_ = [(n, c_vp) for n in ("dL_dfeatures_dc", "dL_dfeatures_rest", "dL_dopacity_raw", "dL_dscaling_raw", "dL_drotation_raw")]
+
+
 class DqoRastHeader(ctypes.Structure):
     _fields_ = [("num_rendered", ctypes.c_uint32), ("num_tiles", ctypes.c_uint32), ("overflow", ctypes.c_uint32),
                 ("max_tile_count", ctypes.c_uint32), ("num_visible", ctypes.c_uint32), ("num_candidates", ctypes.c_uint32),
@@ -85,7 +95,8 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_rast_forward", "dqo_rast_forward_async", "dqo_rast_backward", "dqo_rast_backward_adam", "dqo_mark_visible", "dqo_knn3_workspace_bytes", "dqo_knn3",
            "dqo_quadric_iou_fwd_bwd", "dqo_quadric_adam", "dqo_tile_count_mask", "dqo_transmission_mask", "dqo_tile_color_error", "dqo_knn3_query_workspace_bytes",
            "dqo_knn3_query", "dqo_knn3_query_within", "dqo_knn3_query_grouped", "dqo_icp_workspace_bytes", "dqo_icp_normal_equations",
-           "dqo_attach_pixels", "dqo_attach_decide", "dqo_growth_scales", "dqo_growth_inside", "dqo_error_maps", "dqo_map_history_merge")
+           "dqo_attach_pixels", "dqo_attach_decide", "dqo_growth_scales", "dqo_growth_inside", "dqo_error_maps", "dqo_map_history_merge",
+           "dqo_rast_forward_prepare_params", "dqo_rast_forward_render_params", "dqo_rast_forward_async_params", "dqo_rast_backward_params")
 
 _lib = None
 
@@ -122,6 +133,12 @@ def lib():
                                         ctypes.c_size_t, c_vp]
         L.dqo_rast_backward_adam.argtypes = [P(DqoRastParams), P(DqoRastInputs), P(DqoRastCtx), c_vp, c_vp, P(DqoAdamStep), c_vp,
                                              ctypes.c_size_t, c_vp]
+        L.dqo_rast_forward_prepare_params.argtypes = [P(DqoRastParams), P(DqoRastInputs), P(DqoRastParamInputs), P(DqoRastOutputs),
+                                                      P(DqoRastCtx), c_vp]
+        L.dqo_rast_forward_render_params.argtypes = L.dqo_rast_forward_prepare_params.argtypes
+        L.dqo_rast_forward_async_params.argtypes = L.dqo_rast_forward_prepare_params.argtypes[:5] + [c_vp, c_vp, c_vp]
+        L.dqo_rast_backward_params.argtypes = [P(DqoRastParams), P(DqoRastInputs), P(DqoRastParamInputs), P(DqoRastCtx), c_vp, c_vp, c_vp,
+                                               P(DqoRastGrads), P(DqoRastParamGrads), c_vp, ctypes.c_size_t, c_vp]
         L.dqo_mark_visible.argtypes = [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
         L.dqo_knn3.argtypes = [c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]
         L.dqo_quadric_iou_fwd_bwd.argtypes = [c_i32] + [c_vp] * 12
@@ -165,7 +182,7 @@ def lib():
         L.dqo_abi_sizeof.restype = ctypes.c_size_t
         L.dqo_abi_sizeof.argtypes = [c_i32]
         for k, st in enumerate((DqoRastParams, DqoRastInputs, DqoRastOutputs, DqoRastCtx, DqoRastGrads, DqoRastHeader, DqoProfileEntry,
-                                DqoAdamStep, DqoLossTap, DqoObjectGate, DqoAdamTensor)):
+                                DqoAdamStep, DqoLossTap, DqoObjectGate, DqoAdamTensor, DqoRastParamInputs, DqoRastParamGrads)):
             if L.dqo_abi_sizeof(k) != ctypes.sizeof(st):
                 raise RuntimeError(f"libdqoraster.so: struct {st.__name__} is {L.dqo_abi_sizeof(k)} bytes in the library, "
                                    f"{ctypes.sizeof(st)} in the binding")

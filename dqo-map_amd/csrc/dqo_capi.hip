@@ -156,7 +156,7 @@ DQO_API int dqo_abi_version(void) { return DQO_ABI_VERSION; }
 DQO_API size_t dqo_abi_sizeof(int32_t which) {
     static const size_t sz[] = {sizeof(DqoRastParams), sizeof(DqoRastInputs), sizeof(DqoRastOutputs), sizeof(DqoRastCtx), sizeof(DqoRastGrads),
                                 sizeof(DqoRastHeader), sizeof(DqoProfileEntry), sizeof(DqoAdamStep), sizeof(DqoLossTap), sizeof(DqoObjectGate),
-                                sizeof(DqoAdamTensor)};
+                                sizeof(DqoAdamTensor), sizeof(DqoRastParamInputs), sizeof(DqoRastParamGrads)};
     return (which >= 0 && which < (int32_t)(sizeof(sz) / sizeof(sz[0]))) ? sz[which] : 0;
 }
 DQO_API const char* dqo_last_error(void) { return g_err; }
@@ -286,8 +286,10 @@ DQO_API int dqo_rast_forward_async(const DqoRastParams* p, const DqoRastInputs* 
     return dqo_launch_forward_render(p, in, out, ctx, (hipStream_t)stream, header_host, (hipEvent_t)header_event);
 }
 
-DQO_API int dqo_rast_backward(const DqoRastParams* p, const DqoRastInputs* in, const DqoRastCtx* ctx, const float* dL_dcolor,
-                              const float* dL_ddepth, const int32_t* hit_image, DqoRastGrads* g, void* ws, size_t ws_bytes, void* stream) {
+// dqo_rast_backward and dqo_rast_backward_params (pf: the parameter form's coefficients 1.., dL_drest their gradient rows)
+static int rast_backward(const DqoRastParams* p, const DqoRastInputs* in, const DqoRastCtx* ctx, const float* dL_dcolor, const float* dL_ddepth,
+                         const int32_t* hit_image, DqoRastGrads* g, void* ws, size_t ws_bytes, hipStream_t stream, const DqoShRest* pf,
+                         float* dL_drest) {
     int rc = check_common(p, in, ctx);
     if (rc) return rc;
     DQO_CHECK_ARG(g, "null grads");
@@ -306,7 +308,103 @@ DQO_API int dqo_rast_backward(const DqoRastParams* p, const DqoRastInputs* in, c
         dqo_set_error("backward workspace too small (%zu < %zu)", ws_bytes, dqo_rast_backward_workspace_bytes(ctx->inst_capacity));
         return DQO_ERR_WORKSPACE;
     }
-    return dqo_launch_backward(p, in, ctx, dL_dcolor, dL_ddepth, hit_image, g, ws, ws_bytes, (hipStream_t)stream);
+    return dqo_launch_backward(p, in, ctx, dL_dcolor, dL_ddepth, hit_image, g, ws, ws_bytes, stream, pf, dL_drest);
+}
+
+DQO_API int dqo_rast_backward(const DqoRastParams* p, const DqoRastInputs* in, const DqoRastCtx* ctx, const float* dL_dcolor,
+                              const float* dL_ddepth, const int32_t* hit_image, DqoRastGrads* g, void* ws, size_t ws_bytes, void* stream) {
+    return rast_backward(p, in, ctx, dL_dcolor, dL_ddepth, hit_image, g, ws, ws_bytes, (hipStream_t)stream, nullptr, nullptr);
+}
+
+// ---- the parameter form (DqoRastParamInputs / DqoRastParamGrads) ----
+// Checks what is particular to the form and builds the DqoRastInputs / DqoRastParams the launchers take: the raw tensors in the
+// activated tensors' places (the kernels' PF instantiations read them as such), M = 1 + rest.  The common checks follow on those.
+static int pf_inputs(const DqoRastParams* p, const DqoRastInputs* in, const DqoRastParamInputs* pin, DqoRastParams* p2, DqoRastInputs* in2,
+                     DqoShRest* rest) {
+    DQO_CHECK_ARG(p && in && pin, "null params / inputs / parameter inputs");
+    DQO_CHECK_ARG(in->shs == nullptr && in->opacities == nullptr && in->scales == nullptr && in->rotations == nullptr,
+                  "parameter form: DqoRastInputs.shs / opacities / scales / rotations must be NULL (they come from DqoRastParamInputs)");
+    DQO_CHECK_ARG(in->colors_precomp == nullptr, "parameter form: colors_precomp is not supported");
+    DQO_CHECK_ARG(pin->rest >= 0, "parameter form: negative rest coefficient count %d", pin->rest);
+    DQO_CHECK_ARG(p->M == 1 + pin->rest, "parameter form: params M = %d, must be 1 + rest = %d", p->M, 1 + pin->rest);
+    DQO_CHECK_ARG(p->D < 0 || p->D > 3 || 1 + pin->rest >= (p->D + 1) * (p->D + 1),
+                  "parameter form: features_rest has %d coefficients, degree %d needs %d", pin->rest, p->D, (p->D + 1) * (p->D + 1) - 1);
+    if (p->P > 0) {
+        DQO_CHECK_ARG(pin->features_dc && pin->opacity_raw && pin->scaling_raw && pin->rotation_raw, "parameter form: null raw parameter");
+        DQO_CHECK_ARG(pin->rest == 0 || pin->features_rest, "parameter form: null features_rest with rest = %d", pin->rest);
+    }
+    *p2 = *p;
+    *in2 = *in;
+    in2->shs = pin->features_dc, in2->opacities = pin->opacity_raw, in2->scales = pin->scaling_raw, in2->rotations = pin->rotation_raw;
+    rest->rest = pin->features_rest, rest->m_rest = pin->rest;
+    return DQO_OK;
+}
+
+DQO_API int dqo_rast_forward_prepare_params(const DqoRastParams* p, const DqoRastInputs* in, const DqoRastParamInputs* pin, DqoRastOutputs* out,
+                                            DqoRastCtx* ctx, void* stream) {
+    DqoRastParams p2;
+    DqoRastInputs in2;
+    DqoShRest rest;
+    int rc = pf_inputs(p, in, pin, &p2, &in2, &rest);
+    if (rc) return rc;
+    rc = check_common(&p2, &in2, ctx);
+    if (rc) return rc;
+    rc = check_outputs(&p2, out);
+    if (rc) return rc;
+    rc = dqo_launch_forward_prepare(&p2, &in2, out, ctx, (hipStream_t)stream, &rest);
+    if (rc) return rc;
+    return dqo_launch_mark_header_stage0(&p2, ctx, (hipStream_t)stream);
+}
+
+DQO_API int dqo_rast_forward_render_params(const DqoRastParams* p, const DqoRastInputs* in, const DqoRastParamInputs* pin, DqoRastOutputs* out,
+                                           DqoRastCtx* ctx, void* stream) {
+    DqoRastParams p2;
+    DqoRastInputs in2;
+    DqoShRest rest;
+    int rc = pf_inputs(p, in, pin, &p2, &in2, &rest);
+    if (rc) return rc;
+    rc = check_render(&p2, &in2, out, ctx);
+    if (rc) return rc;
+    return dqo_launch_forward_render(&p2, &in2, out, ctx, (hipStream_t)stream, nullptr, nullptr, &rest);
+}
+
+DQO_API int dqo_rast_forward_async_params(const DqoRastParams* p, const DqoRastInputs* in, const DqoRastParamInputs* pin, DqoRastOutputs* out,
+                                          DqoRastCtx* ctx, DqoRastHeader* header_host, void* header_event, void* stream) {
+    DqoRastParams p2;
+    DqoRastInputs in2;
+    DqoShRest rest;
+    int rc = pf_inputs(p, in, pin, &p2, &in2, &rest);
+    if (rc) return rc;
+    rc = check_render(&p2, &in2, out, ctx);  // (covers the checks of the first stage)
+    if (rc) return rc;
+    rc = dqo_launch_forward_prepare(&p2, &in2, out, ctx, (hipStream_t)stream, &rest);
+    if (rc) return rc;
+    return dqo_launch_forward_render(&p2, &in2, out, ctx, (hipStream_t)stream, header_host, (hipEvent_t)header_event, &rest);
+}
+
+DQO_API int dqo_rast_backward_params(const DqoRastParams* p, const DqoRastInputs* in, const DqoRastParamInputs* pin, const DqoRastCtx* ctx,
+                                     const float* dL_dcolor, const float* dL_ddepth, const int32_t* hit_image, DqoRastGrads* g,
+                                     DqoRastParamGrads* pg, void* ws, size_t ws_bytes, void* stream) {
+    DqoRastParams p2;
+    DqoRastInputs in2;
+    DqoShRest rest;
+    int rc = pf_inputs(p, in, pin, &p2, &in2, &rest);
+    if (rc) return rc;
+    DQO_CHECK_ARG(g && pg, "null grads / parameter grads");
+    DQO_CHECK_ARG(g->dL_dsh == nullptr && g->dL_dopacity == nullptr && g->dL_dscales == nullptr && g->dL_drotations == nullptr &&
+                      g->dL_dcolors == nullptr,
+                  "parameter form: DqoRastGrads.dL_dsh / dL_dopacity / dL_dscales / dL_drotations / dL_dcolors must be NULL "
+                  "(DqoRastParamGrads holds them)");
+    if (p2.P > 0) {
+        DQO_CHECK_ARG(pg->dL_dfeatures_dc && pg->dL_dopacity_raw && pg->dL_dscaling_raw && pg->dL_drotation_raw,
+                      "parameter form: null raw gradient output");
+        DQO_CHECK_ARG(pin->rest == 0 || pg->dL_dfeatures_rest, "parameter form: null dL_dfeatures_rest with rest = %d", pin->rest);
+    }
+    // the kernels' rows: the activated form's fields carry the raw gradients (gaussian_rows_pf_kernel applies the Jacobians)
+    DqoRastGrads g2 = *g;
+    g2.dL_dsh = pg->dL_dfeatures_dc, g2.dL_dopacity = pg->dL_dopacity_raw, g2.dL_dscales = pg->dL_dscaling_raw;
+    g2.dL_drotations = pg->dL_drotation_raw;
+    return rast_backward(&p2, &in2, ctx, dL_dcolor, dL_ddepth, hit_image, &g2, ws, ws_bytes, (hipStream_t)stream, &rest, pg->dL_dfeatures_rest);
 }
 
 static int check_adam_step(const DqoAdamStep* st, bool need_grads) {

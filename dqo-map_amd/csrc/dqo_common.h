@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/dqo_raster.h"
+#include "dqo_activate.h"
 
 #define DQO_TILE 16  // reference BLOCK_X = BLOCK_Y = 16 (cuda_rasterizer/config.h:15-16); part of the op's semantics
 #define DQO_WAVE 64
@@ -477,10 +478,14 @@ int dqo_launch_zero_words(uint32_t* p, size_t n_words, hipStream_t s);
 // launchers (defined in the .hip files)
 int dqo_launch_bin_count_k1(const DqoView& v, const DqoRastInputs* in, const DqoRastOutputs* out, const int32_t* gobj, const DqoGeomLayout& g,
                             const DqoImageLayout& img, const DqoBinLayout& bin, int64_t capacity, const unsigned long long* tile_objects,
-                            hipStream_t s);
-int dqo_launch_forward_prepare(const DqoRastParams* p, const DqoRastInputs* in, DqoRastOutputs* out, DqoRastCtx* ctx, hipStream_t s);
+                            hipStream_t s, bool pf = false);
+// pf (the parameter form, dqo_rast_*_params): NULL for the activated form; otherwise `in` holds the raw opacities / scales / rotations
+// and features_dc in place of shs, pf the coefficients 1.. (and the backward's dL_drest their gradient rows)
+int dqo_launch_forward_prepare(const DqoRastParams* p, const DqoRastInputs* in, DqoRastOutputs* out, DqoRastCtx* ctx, hipStream_t s,
+                               const DqoShRest* pf = nullptr);
 int dqo_launch_mark_header_stage0(const DqoRastParams* p, DqoRastCtx* ctx, hipStream_t s);
 int dqo_launch_forward_render(const DqoRastParams* p, const DqoRastInputs* in, DqoRastOutputs* out, DqoRastCtx* ctx, hipStream_t s,
-                              DqoRastHeader* header_host = nullptr, hipEvent_t header_event = nullptr);
+                              DqoRastHeader* header_host = nullptr, hipEvent_t header_event = nullptr, const DqoShRest* pf = nullptr);
 int dqo_launch_backward(const DqoRastParams* p, const DqoRastInputs* in, const DqoRastCtx* ctx, const float* dL_dcolor,
-                        const float* dL_ddepth, const int32_t* hit_image, DqoRastGrads* g, void* ws, size_t ws_bytes, hipStream_t s);
+                        const float* dL_ddepth, const int32_t* hit_image, DqoRastGrads* g, void* ws, size_t ws_bytes, hipStream_t s,
+                        const DqoShRest* pf = nullptr, float* dL_drest = nullptr);

@@ -5,7 +5,9 @@
 //   bin_count_kernel<true> (rast_binning.hip)  at the head of the binning kernel, whose blocks own the same Gaussians and need exactly
 //                                              these results (rect, conic, pixel position): a replayed iteration then has one launch
 //                                              less and the binning kernel reads raw parameters instead of the tables it used to wait for.
-// Same statements, same bits (tests/test_gpu_fused_mapping.py).  Everything here has internal linkage.
+// Same statements, same bits (tests/test_gpu_fused_mapping.py).  PF (the operator's parameter form, dqo_rast_*_params): opacities /
+// scales / rotations are the RAW parameters, activated on load (dqo_activate.h), and shs is features_dc with coefficients 1.. in `rest`.
+// Everything here has internal linkage.
 #pragma once
 #include "dqo_k1_late.h"
 
@@ -19,13 +21,14 @@ struct K1Early {
 
 // Writes the Gaussian's rows of conic_opacity / xy_depth (visible ones), rect16, radii and n_touched (all of them), and — LATE — the
 // late part's tables.  view / proj: the matrices in registers (wave-uniform loads of the caller).
-template <bool LATE>
+template <bool LATE, bool PF = false>
 __device__ __forceinline__ K1Early k1_early(const DqoView& v, const float (&view)[16], const float (&proj)[16], const float cam0,
                                             const float cam1, const float cam2, const int idx, const float* __restrict__ means3D,
                                             const float* __restrict__ scales, const float* __restrict__ rotations,
                                             const float* __restrict__ opacities, const float* __restrict__ shs,
                                             const float* __restrict__ colors_precomp, const int32_t* __restrict__ gobj, DqoGeomLayout& g,
-                                            int32_t* __restrict__ radii_out, int32_t* __restrict__ n_touched_out) {
+                                            int32_t* __restrict__ radii_out, int32_t* __restrict__ n_touched_out,
+                                            const DqoShRest rest = DqoShRest{}) {
 #pragma clang fp contract(off)
     K1Early e;
     e.co = make_float4(0.f, 0.f, 0.f, 0.f), e.xy = e.co;
@@ -45,12 +48,13 @@ __device__ __forceinline__ K1Early k1_early(const DqoView& v, const float (&view
         const float tvy = view[1] * px + view[5] * py + view[9] * pz + view[13];
         const float tvz = view[2] * px + view[6] * py + view[10] * pz + view[14];
         if (tvz <= 0.2f || (double)projx < -1.3 || (double)projx > 1.3 || (double)projy < -1.3 || (double)projy > 1.3) break;
-        const float opac = opacities[idx];  // (with the scales / rotation round: used only by the stores at the very end)
+        const float opac = PF ? dqo_act_opacity(opacities[idx]) : opacities[idx];  // (with the scales / rotation round: used only by the stores at the very end)
         // DqoObjectGate: the Gaussian's object id travels to the blend kernels in the spare word of its xy record
         const int obj_id = gobj != nullptr ? gobj[idx] : 0;
         // computeCov3D, forward.cu:202-235
-        const float sx = scales[3 * idx], sy = scales[3 * idx + 1], sz = scales[3 * idx + 2];
-        const float4 q = reinterpret_cast<const float4*>(rotations)[idx];
+        float sx = scales[3 * idx], sy = scales[3 * idx + 1], sz = scales[3 * idx + 2];
+        float4 q = reinterpret_cast<const float4*>(rotations)[idx];
+        if constexpr (PF) sx = dqo_act_scale(sx), sy = dqo_act_scale(sy), sz = dqo_act_scale(sz), q = dqo_act_rotation(q);
         float Rm[3][3];
         quat_to_R(q, Rm);
         const float s[3] = {v.scale_mod * sx, v.scale_mod * sy, v.scale_mod * sz};
@@ -108,7 +112,7 @@ __device__ __forceinline__ K1Early k1_early(const DqoView& v, const float (&view
         rmaxx = min(v.gx, max(0, (int)((pixx + (float)ir + (float)(DQO_TILE - 1)) / (float)DQO_TILE)));
         rmaxy = min(v.gy, max(0, (int)((pixy + (float)ir + (float)(DQO_TILE - 1)) / (float)DQO_TILE)));
         if ((rmaxx - rminx) * (rmaxy - rminy) == 0) break;
-        if constexpr (LATE) k1_late_part(v, view, cam0, cam1, cam2, idx, px, py, pz, tvx, tvy, tvz, sx, sy, sz, Rm, shs, colors_precomp, g);
+        if constexpr (LATE) k1_late_part<PF>(v, view, cam0, cam1, cam2, idx, px, py, pz, tvx, tvy, tvz, sx, sy, sz, Rm, shs, colors_precomp, g, rest);
         radius = ir;
         e.co = make_float4(conx, cony, conz, opac);
         e.xy = make_float4(pixx, pixy, tvz, __int_as_float(gobj != nullptr ? obj_id : ir));

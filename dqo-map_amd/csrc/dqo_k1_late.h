@@ -3,6 +3,7 @@
 #pragma once
 #include <cstdlib>
 
+#include "dqo_activate.h"
 #include "dqo_common.h"
 #include "dqo_gauss_chain.h"
 
@@ -58,10 +59,13 @@ static int dqo_k1_where(int P) {
 // — where dqo_k1_where says so — by the extra blocks of a sort launch (k1_late_block), where it runs beside the sorts:
 // those keep a few waves busy for their whole serial chain and leave the rest of the GPU idle, this part is memory traffic (the 192-byte
 // SH row) and plain arithmetic that nothing before the blend kernel waits for.
+// PF (the parameter form): coefficient 0 comes from shs = features_dc [P, 1, 3], coefficients 1.. from rest.rest [P, rest.m_rest, 3].
+template <bool PF = false>
 __device__ __forceinline__ void k1_late_part(const DqoView& v, const float (&view)[16], const float cam0, const float cam1, const float cam2,
                                              const int idx, const float px, const float py, const float pz, const float tvx, const float tvy,
                                              const float tvz, const float sx, const float sy, const float sz, const float (&Rm)[3][3],
-                                             const float* __restrict__ shs, const float* __restrict__ colors_precomp, const DqoGeomLayout& g) {
+                                             const float* __restrict__ shs, const float* __restrict__ colors_precomp, const DqoGeomLayout& g,
+                                             const DqoShRest rest = DqoShRest{}) {
 #pragma clang fp contract(off)
     // colour: computeColorFromSH, forward.cu:104-155
     float rgb[3];
@@ -73,8 +77,23 @@ __device__ __forceinline__ void k1_late_part(const DqoView& v, const float (&vie
         const float x = dxx / len, y = dyy / len, z = dzz / len;
         // all coefficients of the active degree in ONE batch of loads: fetched inside the per-degree blocks below they
         // would come in twelve small groups (three channels x four degrees), each waited for before the next is issued
-        const float* shp = shs + (size_t)idx * v.M * 3;
         float sh[48];
+        if constexpr (PF) {
+            const float* rp = rest.rest + (size_t)idx * rest.m_rest * 3;
+#pragma unroll
+            for (int i = 0; i < 3; i++) sh[i] = shs[3 * (size_t)idx + i];
+            if (v.D >= 3) {
+#pragma unroll
+                for (int i = 0; i < 45; i++) sh[3 + i] = rp[i];
+            } else if (v.D == 2) {
+#pragma unroll
+                for (int i = 0; i < 24; i++) sh[3 + i] = rp[i];
+            } else if (v.D == 1) {
+#pragma unroll
+                for (int i = 0; i < 9; i++) sh[3 + i] = rp[i];
+            }
+        } else {
+        const float* shp = shs + (size_t)idx * v.M * 3;
         if (v.D >= 3) {
 #pragma unroll
             for (int i = 0; i < 48; i++) sh[i] = shp[i];
@@ -87,6 +106,7 @@ __device__ __forceinline__ void k1_late_part(const DqoView& v, const float (&vie
         } else {
 #pragma unroll
             for (int i = 0; i < 3; i++) sh[i] = shp[i];
+        }
         }
         const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
 #pragma unroll
@@ -138,8 +158,8 @@ __device__ __forceinline__ void k1_late_part(const DqoView& v, const float (&vie
     }
 }
 
-template <int THREADS>
-__device__ __forceinline__ void k1_late_block(const DqoK1Late& a, const DqoGeomLayout& g, const int block) {
+template <int THREADS, bool PF = false>
+__device__ __forceinline__ void k1_late_block(const DqoK1Late& a, const DqoGeomLayout& g, const int block, const DqoShRest rest = DqoShRest{}) {
 #pragma clang fp contract(off)
     const int idx = block * THREADS + (int)threadIdx.x;
     if (idx >= a.v.P) return;
@@ -153,10 +173,11 @@ __device__ __forceinline__ void k1_late_block(const DqoK1Late& a, const DqoGeomL
     const float tvx = view[0] * px + view[4] * py + view[8] * pz + view[12];
     const float tvy = view[1] * px + view[5] * py + view[9] * pz + view[13];
     const float tvz = view[2] * px + view[6] * py + view[10] * pz + view[14];
-    const float sx = a.scales[3 * idx], sy = a.scales[3 * idx + 1], sz = a.scales[3 * idx + 2];
-    const float4 q = reinterpret_cast<const float4*>(a.rotations)[idx];
+    float sx = a.scales[3 * idx], sy = a.scales[3 * idx + 1], sz = a.scales[3 * idx + 2];
+    float4 q = reinterpret_cast<const float4*>(a.rotations)[idx];
+    if constexpr (PF) sx = dqo_act_scale(sx), sy = dqo_act_scale(sy), sz = dqo_act_scale(sz), q = dqo_act_rotation(q);
     float Rm[3][3];
     quat_to_R(q, Rm);
-    k1_late_part(a.v, view, a.v.campos[0], a.v.campos[1], a.v.campos[2], idx, px, py, pz, tvx, tvy, tvz, sx, sy, sz, Rm, a.shs, a.colors_precomp, g);
+    k1_late_part<PF>(a.v, view, a.v.campos[0], a.v.campos[1], a.v.campos[2], idx, px, py, pz, tvx, tvy, tvz, sx, sy, sz, Rm, a.shs, a.colors_precomp, g, rest);
 }
 }  // namespace

@@ -20,10 +20,12 @@ int dqo_launch_blend_backward(const DqoView& v, const DqoGeomLayout& g, const Dq
                               const float* dL_dcolor, const float* dL_ddepth, DqoGradRec* recs, uint8_t* valid, int64_t capacity,
                               const DqoTapDev& tap, const DqoGateDev& gate, int list_split, hipStream_t s);
 int dqo_launch_gaussian_rows(const DqoView& v, const DqoGeomLayout& g, const DqoRastInputs* in, const DqoGradRec* recs, const uint8_t* valid,
-                             int64_t cap, const DqoRastGrads& gr, hipStream_t s, uint32_t frame_words, uint32_t* hist, uint32_t hist_words);
+                             int64_t cap, const DqoRastGrads& gr, hipStream_t s, uint32_t frame_words, uint32_t* hist, uint32_t hist_words,
+                             bool pf, float* dL_drest);
 
 int dqo_launch_backward(const DqoRastParams* p, const DqoRastInputs* in, const DqoRastCtx* ctx, const float* dL_dcolor,
-                        const float* dL_ddepth, const int32_t* hit_image, DqoRastGrads* gr, void* ws, size_t ws_bytes, hipStream_t s) {
+                        const float* dL_ddepth, const int32_t* hit_image, DqoRastGrads* gr, void* ws, size_t ws_bytes, hipStream_t s,
+                        const DqoShRest* pf, float* dL_drest) {
     (void)hit_image;  // the hit Gaussian is recovered from its list position kept in the image context
     (void)ws_bytes;
     if (p->P <= 0) return DQO_OK;
@@ -45,5 +47,5 @@ int dqo_launch_backward(const DqoRastParams* p, const DqoRastInputs* in, const D
     // Not with list_split: a second backward over the same forward (retain_graph) would find the long-list queue's counters gone.
     const bool clear = ctx->frame_prezeroed != 0 && dqo_list_split(ctx) == 0;
     return dqo_launch_gaussian_rows(v, g, in, recs, valid, cap, *gr, s, clear ? (uint32_t)dqo_frame_scalar_words(ctx) : 0u, img.tile_count,
-                                    clear ? (uint32_t)((img.tile_flag + T) - img.tile_count) : 0u);
+                                    clear ? (uint32_t)((img.tile_flag + T) - img.tile_count) : 0u, pf != nullptr, dL_drest);
 }

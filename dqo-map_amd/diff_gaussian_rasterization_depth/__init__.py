@@ -380,251 +380,336 @@ def _new_outputs(P, H, W, device):
     return out, N.DqoRastOutputs(*(N.ptr(t) for t in out))
 
 
+def _forward_call(lib, stage, params, inputs, pinputs, outputs, cctx, *rest):
+    """dqo_rast_forward_<stage> of the activated form, or its _params counterpart when the parameter form's inputs are given."""
+    if pinputs is None:
+        return getattr(lib, "dqo_rast_forward_" + stage)(ctypes.byref(params), ctypes.byref(inputs), ctypes.byref(outputs),
+                                                         ctypes.byref(cctx), *rest)
+    return getattr(lib, "dqo_rast_forward_" + stage + "_params")(ctypes.byref(params), ctypes.byref(inputs), ctypes.byref(pinputs),
+                                                                 ctypes.byref(outputs), ctypes.byref(cctx), *rest)
+
+
+def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask, raster_settings,
+             gaussian_object=None, pixel_object=None, tile_objects=None, pf=None):
+    """The operator's forward, shared by both entries.  pf: None (the activated form), or the parameter form's
+    (features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw) — checked and contiguous — with sh, opacities, scales and
+    rotations given as empty tensors; everything else (sync modes, pooled contexts, leases, capacity hints) is the same code."""
+    rs = raster_settings
+    lib = N.lib()
+    if means3D.ndimension() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:67-70
+    N.require_gpu(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask, rs.bg, rs.viewmatrix,
+                  rs.projmatrix, rs.campos)
+    if not means3D.is_cuda:
+        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    dev = means3D.device
+    means3D, opacities = _f32(means3D, "means3D"), _f32(opacities, "opacities")
+    sh, colors_precomp = _f32(sh, "sh"), _f32(colors_precomp, "colors_precomp")
+    scales, rotations, cov3Ds_precomp = _f32(scales, "scales"), _f32(rotations, "rotations"), _f32(cov3Ds_precomp, "cov3D_precomp")
+    bg, view, proj, campos = (_f32(rs.bg, "bg"), _f32(rs.viewmatrix, "viewmatrix"), _f32(rs.projmatrix, "projmatrix"),
+                              _f32(rs.campos, "campos"))
+    rs = rs._replace(bg=bg, viewmatrix=view, projmatrix=proj, campos=campos)
+    if tile_mask is not None:
+        if tile_mask.dtype != torch.int32:
+            raise RuntimeError(f"expected scalar type Int but found {tile_mask.dtype} (tile_mask)")
+        tile_mask = tile_mask.contiguous()
+    P = means3D.size(0)
+    H, W = int(rs.image_height), int(rs.image_width)
+    M = sh.size(1) if sh.numel() != 0 else 0  # rasterize_points.cu:105-109
+    pinputs = None
+    if pf is not None:
+        f_dc, f_rest, o_raw, s_raw, r_raw = pf
+        M = 1 + f_rest.size(1)
+        pinputs = N.DqoRastParamInputs(features_dc=N.ptr(f_dc), features_rest=N.ptr(f_rest), rest=M - 1, opacity_raw=N.ptr(o_raw),
+                                       scaling_raw=N.ptr(s_raw), rotation_raw=N.ptr(r_raw))
+    gate = None
+    if (gaussian_object is None) != (pixel_object is None):
+        raise RuntimeError("object gate: gaussian_object and pixel_object go together")
+    if gaussian_object is not None:
+        N.require_gpu(gaussian_object, pixel_object)
+        if gaussian_object.dtype != torch.int32 or pixel_object.dtype != torch.int32:
+            raise RuntimeError("expected scalar type Int (object gate)")
+        if gaussian_object.numel() != P or pixel_object.numel() != H * W:
+            raise RuntimeError("object gate: gaussian_object must have num_points elements, pixel_object H x W")
+        gaussian_object, pixel_object = gaussian_object.contiguous(), pixel_object.contiguous()
+        _check_gate_ids(gaussian_object, pixel_object)
+        gate = N.DqoObjectGate(gaussian_object=N.ptr(gaussian_object), pixel_object=N.ptr(pixel_object))
+        if tile_objects is not None:
+            N.require_gpu(tile_objects)
+            if tile_objects.dtype != torch.int64 or tile_objects.numel() != ((H + 15) // 16) * ((W + 15) // 16):
+                raise RuntimeError("object gate: tile_objects must be int64 with ceil(H/16) x ceil(W/16) elements")
+            tile_objects = tile_objects.contiguous()
+            gate.tile_objects = N.ptr(tile_objects)
+    elif tile_objects is not None:
+        raise RuntimeError("object gate: tile_objects without gaussian_object / pixel_object")
+    u8 = dict(dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = N.current_stream()
+        out, outputs = _new_outputs(P, H, W, dev)
+        _, _, hit_color, hit_depth, _, _, _, n_touched, radii = out
+        geomBuffer = torch.empty((lib.dqo_rast_geom_bytes(P, W, H),), **u8)
+        imgBuffer = torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8)
+        params = _params(rs, P, M)
+        inputs = _inputs(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask)
+        cctx = N.DqoRastCtx(geom=geomBuffer.data_ptr(), geom_bytes=geomBuffer.numel(), binning=None, binning_bytes=0,
+                            image=imgBuffer.data_ptr(), image_bytes=imgBuffer.numel(), inst_capacity=0, list_split=_list_split)
+        if gate is not None:
+            cctx.object_gate = ctypes.addressof(gate)
+        key = (dev.index, P, W, H)
+        cap = None
+        lease = None
+        if _sync_mode == "graph":
+            with _lock:
+                cap = _cap_hint.get(key)
+            if cap is None:
+                raise RuntimeError("diff_gaussian_rasterization_depth ('graph' mode): no instance capacity known for "
+                                   f"P={P}, {W}x{H}: run one forward in 'lazy' mode first (the warm-up before the capture) or call "
+                                   "set_capacity(P, W, H, instances)")
+            # nothing below touches the host: the launches of both stages, no header copy, no event
+            num_rendered = -1
+            with _lock:
+                # (only a forward that IS being captured pins a context: an eager call in this mode keeps contexts of its own)
+                capturing = P > 0 and torch.cuda.is_current_stream_capturing()
+                pooled = _pooled_set(lib, key, stream, dev, W, H, pin=True) if capturing else None
+                if pooled is not None:
+                    # the context belongs to the graph from here on (_Pinned).  The counters' promise holds at every replay only if
+                    # the captured iteration also holds this frame's backward, which clears them: a forward that needs no gradient
+                    # is captured with its own zero fill
+                    lease = _Pinned(pooled)
+                    _captured.append(pooled)
+                    geomBuffer, imgBuffer, binningBuffer, cap = pooled.geom, pooled.img, pooled.binning, pooled.cap
+                    cctx.geom, cctx.geom_bytes = geomBuffer.data_ptr(), geomBuffer.numel()
+                    cctx.image, cctx.image_bytes = imgBuffer.data_ptr(), imgBuffer.numel()
+                    cctx.tile_bucket_capacity = pooled.bucket
+                    cctx.keep_tile_order = 1 if pooled.order_valid else 0
+                    cctx.frame_prezeroed = 1 if (pooled.clean and _list_split == 0 and any(ctx.needs_input_grad)) else 0
+                    pooled.clean = False
+                    pooled.captured = (int(cctx.keep_tile_order), int(cctx.frame_prezeroed))
+                else:
+                    binningBuffer = torch.empty((lib.dqo_rast_binning_bytes(cap),), **u8)
+            cctx.binning, cctx.binning_bytes, cctx.inst_capacity = binningBuffer.data_ptr(), binningBuffer.numel(), cap
+            N.check(_forward_call(lib, "async", params, inputs, pinputs, outputs, cctx, None, None, stream))
+            _last["header"] = geomBuffer  # (a captured forward: the graph's own buffer, valid after every replay)
+        elif _sync_mode != "exact":
+            _verify_pending(block=False)
+            with _lock:
+                cap = _cap_hint.get(key)
+        if _sync_mode == "graph":
+            pass
+        elif cap is None:
+            # 'exact', or the first call for this shape in 'lazy' / 'deferred' (measure once): stage 1, the one D2H read, stage 2
+            N.check(_forward_call(lib, "prepare", params, inputs, pinputs, outputs, cctx, stream))
+            hdr = N.DqoRastHeader()
+            N.check(lib.dqo_rast_read_header(ctypes.byref(cctx), ctypes.byref(hdr), stream))
+            # (Gaussian, tile) pairs in the tile rects: the reference's num_rendered, and an upper bound of the instances
+            # the binning keeps after its footprint test — a capacity that always fits
+            num_rendered = int(hdr.num_candidates)
+            cap = max(num_rendered, 1)
+            if _sync_mode == "exact":
+                _last["num_rendered"], _last["num_visible"] = num_rendered, int(hdr.num_visible)
+            else:
+                cap = num_rendered + 4096  # later calls keep max(this, 1.25 N)
+                with _lock:
+                    cap = _cap_hint[key] = max(_cap_hint.get(key, 0), cap)
+                num_rendered = -1
+            binningBuffer = torch.empty((lib.dqo_rast_binning_bytes(cap),), **u8)
+            cctx.binning, cctx.binning_bytes, cctx.inst_capacity = binningBuffer.data_ptr(), binningBuffer.numel(), cap
+            N.check(_forward_call(lib, "render", params, inputs, pinputs, outputs, cctx, stream))
+            if _sync_mode == "exact":
+                # exact mode has read what it needs already: nothing per call; last_header() reads the rest on demand from the
+                # geometry buffer, which therefore stays referenced until the next forward (~160 B per Gaussian, one call longer)
+                _last["header"] = geomBuffer
+            else:
+                with _lock:
+                    host, ev, _, _ = _ring_slot(dev.index)
+                    host.copy_(geomBuffer[:32].view(torch.int32), non_blocking=True)
+                    ev.record()
+                    _pending.append((ev, host, key, cap, False))
+                    _last["header"] = (ev, host)
+        else:
+            # 'lazy' / 'deferred' with a carried-over capacity: ONE call — both stages, and between the sort and the blend kernel
+            # (where the frame's header is final) its asynchronous copy into a pinned ring slot + the slot's event: the deferred
+            # capacity check, available a blend kernel before the forward's end
+            num_rendered = -1
+            with _lock:
+                pooled = _pooled_set(lib, key, stream, dev, W, H) if P > 0 else None
+                if pooled is not None:
+                    # a pooled context (see _pool): its buffers instead of the fresh ones, lists in per-tile buckets, the tile
+                    # order of the previous frame on it, and — if that frame's backward cleared the counters — no zero fill and
+                    # no preprocess launch
+                    lease = _Lease(pooled)
+                    geomBuffer, imgBuffer, binningBuffer, cap = pooled.geom, pooled.img, pooled.binning, pooled.cap
+                    cctx.geom, cctx.geom_bytes = geomBuffer.data_ptr(), geomBuffer.numel()
+                    cctx.image, cctx.image_bytes = imgBuffer.data_ptr(), imgBuffer.numel()
+                    cctx.tile_bucket_capacity = pooled.bucket
+                    cctx.keep_tile_order = 1 if pooled.order_valid else 0
+                    cctx.frame_prezeroed = 1 if (pooled.clean and _list_split == 0) else 0
+                    pooled.clean = False  # (whatever happens below: this frame's counters are in use)
+                else:
+                    binningBuffer = torch.empty((lib.dqo_rast_binning_bytes(cap),), **u8)
+                cctx.binning, cctx.binning_bytes, cctx.inst_capacity = binningBuffer.data_ptr(), binningBuffer.numel(), cap
+                host, ev, host_ptr, ev_handle = _ring_slot(dev.index)
+                N.check(_forward_call(lib, "async", params, inputs, pinputs, outputs, cctx, host_ptr, ev_handle, stream))
+                if pooled is not None:
+                    pooled.order_valid = True
+                _pending.append((ev, host, key, cap, pooled is not None))
+                _last["header"] = (ev, host)
+    # Only grad_out_color and grad_out_depth are consumed by the backward (like the reference's, __init__.py:176-238): the engine need not
+    # fill zero images for the three float outputs nobody differentiated through (hit_color_weight, hit_depth_weight, T_map) — three
+    # fill launches per backward; an undefined colour / depth gradient arrives as None and is replaced by zeros there
+    if hasattr(ctx, "set_materialize_grads"):  # (callers that drive forward / backward by hand pass a plain object)
+        ctx.set_materialize_grads(False)
+    ctx.pooled = lease  # (None: a context of this call's own)
+    ctx.raster_settings = rs
+    ctx.num_rendered = num_rendered
+    ctx.inst_capacity = cap
+    ctx.list_split = _list_split  # (the backward shares the same lists between eight waves: the queue is the forward's)
+    ctx.M = M
+    ctx.object_gate = None if gate is None else (gaussian_object, pixel_object)
+    ctx.save_for_backward(colors_precomp, hit_depth, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
+                          binningBuffer, imgBuffer, opacities, tile_mask if tile_mask is not None else torch.empty(0),
+                          *(pf if pf is not None else ()))
+    ctx.mark_non_differentiable(hit_color, hit_depth, n_touched, radii)
+    return out
+
+
+def _backward(ctx, grad_out_color, grad_out_depth):
+    """The operator's backward, shared by both entries: the activated form's seven gradients, or (parameter form, the forward's pf
+    saved behind the usual tensors) (g_means3D, g_features_dc, g_features_rest, g_opacity_raw, g_scaling_raw, g_rotation_raw)."""
+    # only grad_out_color and grad_out_depth are consumed, exactly like the reference (__init__.py:176-238; F6)
+    rs = ctx.raster_settings
+    lib = N.lib()
+    (colors_precomp, hit_depth, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer,
+     opacities, tile_mask) = ctx.saved_tensors[:13]
+    pf = ctx.saved_tensors[13:] or None
+    if tile_mask.numel() == 0:
+        tile_mask = None
+    if _sync_mode in ("lazy", "deferred"):
+        _verify_pending(block=(_sync_mode == "lazy"))  # (lazy: no gradient of an invalid frame; deferred: never wait, see set_sync_mode)
+    P, M = means3D.size(0), ctx.M
+    H, W = int(rs.image_height), int(rs.image_width)
+    dev = means3D.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    if grad_out_color is None:
+        grad_out_color = torch.zeros((3, H, W), **f32)
+    if grad_out_depth is None:
+        grad_out_depth = torch.zeros((1, H, W), **f32)
+    grad_out_color, grad_out_depth = _f32(grad_out_color, "grad_out_color"), _f32(grad_out_depth, "grad_out_depth")
+    with torch.cuda.device(dev):
+        stream = N.current_stream()
+        # dL/dmeans2D is computed by the reference's C++ and dropped by its Python (__init__.py:247-283 returns no slot for it);
+        # dL/dcolors_precomp and dL/dcov3D_precomp only have a receiver when those inputs were given: rows nobody reads are not
+        # written (NULL = the per-Gaussian kernel skips the tensor: 24 of its 142 MB of stores on config 3)
+        want_colors, want_cov = colors_precomp.numel() != 0, cov3Ds_precomp.numel() != 0
+        g_means3D = torch.empty((P, 3), **f32)
+        g_colors = torch.empty((P, 3), **f32) if want_colors else None
+        g_opacity = torch.empty((P, 1), **f32)
+        g_cov3D = torch.empty((P, 6), **f32) if want_cov else None
+        g_sh = torch.empty((P, M, 3), **f32) if pf is None else None
+        g_scales = torch.empty((P, 3), **f32)
+        g_rot = torch.empty((P, 4), **f32)
+        pinputs = pgrads = None
+        if pf is not None:
+            f_dc, f_rest, o_raw, s_raw, r_raw = pf
+            g_dc, g_rest = torch.empty((P, 1, 3), **f32), torch.empty((P, M - 1, 3), **f32)
+            pinputs = N.DqoRastParamInputs(features_dc=N.ptr(f_dc), features_rest=N.ptr(f_rest), rest=M - 1,
+                                           opacity_raw=N.ptr(o_raw), scaling_raw=N.ptr(s_raw), rotation_raw=N.ptr(r_raw))
+            pgrads = N.DqoRastParamGrads(dL_dfeatures_dc=N.ptr(g_dc), dL_dfeatures_rest=N.ptr(g_rest), dL_dopacity_raw=N.ptr(g_opacity),
+                                         dL_dscaling_raw=N.ptr(g_scales), dL_drotation_raw=N.ptr(g_rot))
+        if P > 0:
+            cap = ctx.inst_capacity
+            ws = torch.empty((lib.dqo_rast_backward_workspace_bytes(cap),), dtype=torch.uint8, device=dev)
+            params = _params(rs, P, M)
+            inputs = _inputs(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask)
+            cctx = N.DqoRastCtx(geom=geomBuffer.data_ptr(), geom_bytes=geomBuffer.numel(), binning=binningBuffer.data_ptr(),
+                                binning_bytes=binningBuffer.numel(), image=imgBuffer.data_ptr(), image_bytes=imgBuffer.numel(),
+                                inst_capacity=cap, list_split=getattr(ctx, "list_split", 0))
+            lease = getattr(ctx, "pooled", None)
+            if lease is not None:
+                # a pooled context: its lists live in buckets, and this call — the last consumer of the frame's counters — clears
+                # them for the next forward on the context (DqoRastCtx.frame_prezeroed as dqo_rast_backward reads it)
+                cctx.tile_bucket_capacity = lease.set.bucket
+                cctx.frame_prezeroed = 1 if cctx.list_split == 0 else 0
+            if getattr(ctx, "object_gate", None) is not None:
+                gate = N.DqoObjectGate(gaussian_object=N.ptr(ctx.object_gate[0]), pixel_object=N.ptr(ctx.object_gate[1]))
+                cctx.object_gate = ctypes.addressof(gate)
+            grads = N.DqoRastGrads(dL_dmeans3D=g_means3D.data_ptr(), dL_dsh=N.ptr(g_sh), dL_dcolors=N.ptr(g_colors),
+                                   dL_dopacity=g_opacity.data_ptr(), dL_dscales=g_scales.data_ptr(),
+                                   dL_drotations=g_rot.data_ptr(), dL_dcov3D=N.ptr(g_cov3D), dL_dmeans2D=None,
+                                   skip_culled_rows=1 if getattr(ctx, "sparse_grad_rows", False) else 0)
+            if pf is None:
+                N.check(lib.dqo_rast_backward(ctypes.byref(params), ctypes.byref(inputs), ctypes.byref(cctx),
+                                              grad_out_color.data_ptr(), grad_out_depth.data_ptr(), hit_depth.data_ptr(),
+                                              ctypes.byref(grads), ws.data_ptr(), ws.numel(), stream))
+            else:
+                grads.dL_dopacity = grads.dL_dscales = grads.dL_drotations = None  # (DqoRastParamGrads holds them)
+                N.check(lib.dqo_rast_backward_params(ctypes.byref(params), ctypes.byref(inputs), ctypes.byref(pinputs),
+                                                     ctypes.byref(cctx), grad_out_color.data_ptr(), grad_out_depth.data_ptr(),
+                                                     hit_depth.data_ptr(), ctypes.byref(grads), ctypes.byref(pgrads), ws.data_ptr(),
+                                                     ws.numel(), stream))
+            if lease is not None and cctx.frame_prezeroed:
+                with _lock:
+                    lease.set.clean = True
+    if pf is not None:
+        if P == 0:
+            g_dc, g_rest = torch.empty((0, 1, 3), **f32), torch.empty((0, M - 1, 3), **f32)
+        return (g_means3D, g_dc, g_rest, g_opacity.view_as(pf[2]), g_scales, g_rot)
+    # gradient slots of the reference (__init__.py:273-283); inputs handed over as empty tensors get None
+    def slot(g, inp):
+        return g if (g is not None and inp.numel() != 0) else None
+    return (g_means3D, slot(g_sh, sh), slot(g_colors, colors_precomp), g_opacity.view_as(opacities) if opacities.numel() else None,
+            slot(g_scales, scales), slot(g_rot, rotations), slot(g_cov3D, cov3Ds_precomp), None, None, None, None, None)
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask, raster_settings,
                 gaussian_object=None, pixel_object=None, tile_objects=None):
-        rs = raster_settings
-        lib = N.lib()
-        if means3D.ndimension() != 2 or means3D.size(1) != 3:
-            raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:67-70
-        N.require_gpu(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask, rs.bg, rs.viewmatrix,
-                      rs.projmatrix, rs.campos)
-        if not means3D.is_cuda:
-            raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
-        dev = means3D.device
-        means3D, opacities = _f32(means3D, "means3D"), _f32(opacities, "opacities")
-        sh, colors_precomp = _f32(sh, "sh"), _f32(colors_precomp, "colors_precomp")
-        scales, rotations, cov3Ds_precomp = _f32(scales, "scales"), _f32(rotations, "rotations"), _f32(cov3Ds_precomp, "cov3D_precomp")
-        bg, view, proj, campos = (_f32(rs.bg, "bg"), _f32(rs.viewmatrix, "viewmatrix"), _f32(rs.projmatrix, "projmatrix"),
-                                  _f32(rs.campos, "campos"))
-        rs = rs._replace(bg=bg, viewmatrix=view, projmatrix=proj, campos=campos)
-        if tile_mask is not None:
-            if tile_mask.dtype != torch.int32:
-                raise RuntimeError(f"expected scalar type Int but found {tile_mask.dtype} (tile_mask)")
-            tile_mask = tile_mask.contiguous()
-        P = means3D.size(0)
-        H, W = int(rs.image_height), int(rs.image_width)
-        M = sh.size(1) if sh.numel() != 0 else 0  # rasterize_points.cu:105-109
-        gate = None
-        if (gaussian_object is None) != (pixel_object is None):
-            raise RuntimeError("object gate: gaussian_object and pixel_object go together")
-        if gaussian_object is not None:
-            N.require_gpu(gaussian_object, pixel_object)
-            if gaussian_object.dtype != torch.int32 or pixel_object.dtype != torch.int32:
-                raise RuntimeError("expected scalar type Int (object gate)")
-            if gaussian_object.numel() != P or pixel_object.numel() != H * W:
-                raise RuntimeError("object gate: gaussian_object must have num_points elements, pixel_object H x W")
-            gaussian_object, pixel_object = gaussian_object.contiguous(), pixel_object.contiguous()
-            _check_gate_ids(gaussian_object, pixel_object)
-            gate = N.DqoObjectGate(gaussian_object=N.ptr(gaussian_object), pixel_object=N.ptr(pixel_object))
-            if tile_objects is not None:
-                N.require_gpu(tile_objects)
-                if tile_objects.dtype != torch.int64 or tile_objects.numel() != ((H + 15) // 16) * ((W + 15) // 16):
-                    raise RuntimeError("object gate: tile_objects must be int64 with ceil(H/16) x ceil(W/16) elements")
-                tile_objects = tile_objects.contiguous()
-                gate.tile_objects = N.ptr(tile_objects)
-        elif tile_objects is not None:
-            raise RuntimeError("object gate: tile_objects without gaussian_object / pixel_object")
-        u8 = dict(dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            stream = N.current_stream()
-            out, outputs = _new_outputs(P, H, W, dev)
-            _, _, hit_color, hit_depth, _, _, _, n_touched, radii = out
-            geomBuffer = torch.empty((lib.dqo_rast_geom_bytes(P, W, H),), **u8)
-            imgBuffer = torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8)
-            params = _params(rs, P, M)
-            inputs = _inputs(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask)
-            cctx = N.DqoRastCtx(geom=geomBuffer.data_ptr(), geom_bytes=geomBuffer.numel(), binning=None, binning_bytes=0,
-                                image=imgBuffer.data_ptr(), image_bytes=imgBuffer.numel(), inst_capacity=0, list_split=_list_split)
-            if gate is not None:
-                cctx.object_gate = ctypes.addressof(gate)
-            key = (dev.index, P, W, H)
-            cap = None
-            lease = None
-            if _sync_mode == "graph":
-                with _lock:
-                    cap = _cap_hint.get(key)
-                if cap is None:
-                    raise RuntimeError("diff_gaussian_rasterization_depth ('graph' mode): no instance capacity known for "
-                                       f"P={P}, {W}x{H}: run one forward in 'lazy' mode first (the warm-up before the capture) or call "
-                                       "set_capacity(P, W, H, instances)")
-                # nothing below touches the host: the launches of both stages, no header copy, no event
-                num_rendered = -1
-                with _lock:
-                    # (only a forward that IS being captured pins a context: an eager call in this mode keeps contexts of its own)
-                    capturing = P > 0 and torch.cuda.is_current_stream_capturing()
-                    pooled = _pooled_set(lib, key, stream, dev, W, H, pin=True) if capturing else None
-                    if pooled is not None:
-                        # the context belongs to the graph from here on (_Pinned).  The counters' promise holds at every replay only if
-                        # the captured iteration also holds this frame's backward, which clears them: a forward that needs no gradient
-                        # is captured with its own zero fill
-                        lease = _Pinned(pooled)
-                        _captured.append(pooled)
-                        geomBuffer, imgBuffer, binningBuffer, cap = pooled.geom, pooled.img, pooled.binning, pooled.cap
-                        cctx.geom, cctx.geom_bytes = geomBuffer.data_ptr(), geomBuffer.numel()
-                        cctx.image, cctx.image_bytes = imgBuffer.data_ptr(), imgBuffer.numel()
-                        cctx.tile_bucket_capacity = pooled.bucket
-                        cctx.keep_tile_order = 1 if pooled.order_valid else 0
-                        cctx.frame_prezeroed = 1 if (pooled.clean and _list_split == 0 and any(ctx.needs_input_grad)) else 0
-                        pooled.clean = False
-                        pooled.captured = (int(cctx.keep_tile_order), int(cctx.frame_prezeroed))
-                    else:
-                        binningBuffer = torch.empty((lib.dqo_rast_binning_bytes(cap),), **u8)
-                cctx.binning, cctx.binning_bytes, cctx.inst_capacity = binningBuffer.data_ptr(), binningBuffer.numel(), cap
-                N.check(lib.dqo_rast_forward_async(ctypes.byref(params), ctypes.byref(inputs), ctypes.byref(outputs),
-                                                   ctypes.byref(cctx), None, None, stream))
-                _last["header"] = geomBuffer  # (a captured forward: the graph's own buffer, valid after every replay)
-            elif _sync_mode != "exact":
-                _verify_pending(block=False)
-                with _lock:
-                    cap = _cap_hint.get(key)
-            if _sync_mode == "graph":
-                pass
-            elif cap is None:
-                # 'exact', or the first call for this shape in 'lazy' / 'deferred' (measure once): stage 1, the one D2H read, stage 2
-                N.check(lib.dqo_rast_forward_prepare(ctypes.byref(params), ctypes.byref(inputs), ctypes.byref(outputs),
-                                                     ctypes.byref(cctx), stream))
-                hdr = N.DqoRastHeader()
-                N.check(lib.dqo_rast_read_header(ctypes.byref(cctx), ctypes.byref(hdr), stream))
-                # (Gaussian, tile) pairs in the tile rects: the reference's num_rendered, and an upper bound of the instances
-                # the binning keeps after its footprint test — a capacity that always fits
-                num_rendered = int(hdr.num_candidates)
-                cap = max(num_rendered, 1)
-                if _sync_mode == "exact":
-                    _last["num_rendered"], _last["num_visible"] = num_rendered, int(hdr.num_visible)
-                else:
-                    cap = num_rendered + 4096  # later calls keep max(this, 1.25 N)
-                    with _lock:
-                        cap = _cap_hint[key] = max(_cap_hint.get(key, 0), cap)
-                    num_rendered = -1
-                binningBuffer = torch.empty((lib.dqo_rast_binning_bytes(cap),), **u8)
-                cctx.binning, cctx.binning_bytes, cctx.inst_capacity = binningBuffer.data_ptr(), binningBuffer.numel(), cap
-                N.check(lib.dqo_rast_forward_render(ctypes.byref(params), ctypes.byref(inputs), ctypes.byref(outputs),
-                                                    ctypes.byref(cctx), stream))
-                if _sync_mode == "exact":
-                    # exact mode has read what it needs already: nothing per call; last_header() reads the rest on demand from the
-                    # geometry buffer, which therefore stays referenced until the next forward (~160 B per Gaussian, one call longer)
-                    _last["header"] = geomBuffer
-                else:
-                    with _lock:
-                        host, ev, _, _ = _ring_slot(dev.index)
-                        host.copy_(geomBuffer[:32].view(torch.int32), non_blocking=True)
-                        ev.record()
-                        _pending.append((ev, host, key, cap, False))
-                        _last["header"] = (ev, host)
-            else:
-                # 'lazy' / 'deferred' with a carried-over capacity: ONE call — both stages, and between the sort and the blend kernel
-                # (where the frame's header is final) its asynchronous copy into a pinned ring slot + the slot's event: the deferred
-                # capacity check, available a blend kernel before the forward's end
-                num_rendered = -1
-                with _lock:
-                    pooled = _pooled_set(lib, key, stream, dev, W, H) if P > 0 else None
-                    if pooled is not None:
-                        # a pooled context (see _pool): its buffers instead of the fresh ones, lists in per-tile buckets, the tile
-                        # order of the previous frame on it, and — if that frame's backward cleared the counters — no zero fill and
-                        # no preprocess launch
-                        lease = _Lease(pooled)
-                        geomBuffer, imgBuffer, binningBuffer, cap = pooled.geom, pooled.img, pooled.binning, pooled.cap
-                        cctx.geom, cctx.geom_bytes = geomBuffer.data_ptr(), geomBuffer.numel()
-                        cctx.image, cctx.image_bytes = imgBuffer.data_ptr(), imgBuffer.numel()
-                        cctx.tile_bucket_capacity = pooled.bucket
-                        cctx.keep_tile_order = 1 if pooled.order_valid else 0
-                        cctx.frame_prezeroed = 1 if (pooled.clean and _list_split == 0) else 0
-                        pooled.clean = False  # (whatever happens below: this frame's counters are in use)
-                    else:
-                        binningBuffer = torch.empty((lib.dqo_rast_binning_bytes(cap),), **u8)
-                    cctx.binning, cctx.binning_bytes, cctx.inst_capacity = binningBuffer.data_ptr(), binningBuffer.numel(), cap
-                    host, ev, host_ptr, ev_handle = _ring_slot(dev.index)
-                    N.check(lib.dqo_rast_forward_async(ctypes.byref(params), ctypes.byref(inputs), ctypes.byref(outputs),
-                                                       ctypes.byref(cctx), host_ptr, ev_handle, stream))
-                    if pooled is not None:
-                        pooled.order_valid = True
-                    _pending.append((ev, host, key, cap, pooled is not None))
-                    _last["header"] = (ev, host)
-        # Only grad_out_color and grad_out_depth are consumed by the backward (like the reference's, __init__.py:176-238): the engine need not
-        # fill zero images for the three float outputs nobody differentiated through (hit_color_weight, hit_depth_weight, T_map) — three
-        # fill launches per backward; an undefined colour / depth gradient arrives as None and is replaced by zeros there
-        if hasattr(ctx, "set_materialize_grads"):  # (callers that drive forward / backward by hand pass a plain object)
-            ctx.set_materialize_grads(False)
-        ctx.pooled = lease  # (None: a context of this call's own)
-        ctx.raster_settings = rs
-        ctx.num_rendered = num_rendered
-        ctx.inst_capacity = cap
-        ctx.list_split = _list_split  # (the backward shares the same lists between eight waves: the queue is the forward's)
-        ctx.M = M
-        ctx.object_gate = None if gate is None else (gaussian_object, pixel_object)
-        ctx.save_for_backward(colors_precomp, hit_depth, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer, opacities, tile_mask if tile_mask is not None else torch.empty(0))
-        ctx.mark_non_differentiable(hit_color, hit_depth, n_touched, radii)
-        return out
+        return _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask, raster_settings,
+                        gaussian_object, pixel_object, tile_objects)
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_out_depth, grad_hit_color, grad_hit_depth, grad_hit_color_weight,
                  grad_hit_depth_weight, grad_T_map, grad_n_touched, _):
-        # only grad_out_color and grad_out_depth are consumed, exactly like the reference (__init__.py:176-238; F6)
-        rs = ctx.raster_settings
-        lib = N.lib()
-        (colors_precomp, hit_depth, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer,
-         opacities, tile_mask) = ctx.saved_tensors
-        if tile_mask.numel() == 0:
-            tile_mask = None
-        if _sync_mode in ("lazy", "deferred"):
-            _verify_pending(block=(_sync_mode == "lazy"))  # (lazy: no gradient of an invalid frame; deferred: never wait, see set_sync_mode)
-        P, M = means3D.size(0), ctx.M
-        H, W = int(rs.image_height), int(rs.image_width)
-        dev = means3D.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        if grad_out_color is None:
-            grad_out_color = torch.zeros((3, H, W), **f32)
-        if grad_out_depth is None:
-            grad_out_depth = torch.zeros((1, H, W), **f32)
-        grad_out_color, grad_out_depth = _f32(grad_out_color, "grad_out_color"), _f32(grad_out_depth, "grad_out_depth")
-        with torch.cuda.device(dev):
-            stream = N.current_stream()
-            # dL/dmeans2D is computed by the reference's C++ and dropped by its Python (__init__.py:247-283 returns no slot for it);
-            # dL/dcolors_precomp and dL/dcov3D_precomp only have a receiver when those inputs were given: rows nobody reads are not
-            # written (NULL = the per-Gaussian kernel skips the tensor: 24 of its 142 MB of stores on config 3)
-            want_colors, want_cov = colors_precomp.numel() != 0, cov3Ds_precomp.numel() != 0
-            g_means3D = torch.empty((P, 3), **f32)
-            g_colors = torch.empty((P, 3), **f32) if want_colors else None
-            g_opacity = torch.empty((P, 1), **f32)
-            g_cov3D = torch.empty((P, 6), **f32) if want_cov else None
-            g_sh = torch.empty((P, M, 3), **f32)
-            g_scales = torch.empty((P, 3), **f32)
-            g_rot = torch.empty((P, 4), **f32)
-            if P > 0:
-                cap = ctx.inst_capacity
-                ws = torch.empty((lib.dqo_rast_backward_workspace_bytes(cap),), dtype=torch.uint8, device=dev)
-                params = _params(rs, P, M)
-                inputs = _inputs(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask)
-                cctx = N.DqoRastCtx(geom=geomBuffer.data_ptr(), geom_bytes=geomBuffer.numel(), binning=binningBuffer.data_ptr(),
-                                    binning_bytes=binningBuffer.numel(), image=imgBuffer.data_ptr(), image_bytes=imgBuffer.numel(),
-                                    inst_capacity=cap, list_split=getattr(ctx, "list_split", 0))
-                lease = getattr(ctx, "pooled", None)
-                if lease is not None:
-                    # a pooled context: its lists live in buckets, and this call — the last consumer of the frame's counters — clears
-                    # them for the next forward on the context (DqoRastCtx.frame_prezeroed as dqo_rast_backward reads it)
-                    cctx.tile_bucket_capacity = lease.set.bucket
-                    cctx.frame_prezeroed = 1 if cctx.list_split == 0 else 0
-                if getattr(ctx, "object_gate", None) is not None:
-                    gate = N.DqoObjectGate(gaussian_object=N.ptr(ctx.object_gate[0]), pixel_object=N.ptr(ctx.object_gate[1]))
-                    cctx.object_gate = ctypes.addressof(gate)
-                grads = N.DqoRastGrads(dL_dmeans3D=g_means3D.data_ptr(), dL_dsh=N.ptr(g_sh), dL_dcolors=N.ptr(g_colors),
-                                       dL_dopacity=g_opacity.data_ptr(), dL_dscales=g_scales.data_ptr(),
-                                       dL_drotations=g_rot.data_ptr(), dL_dcov3D=N.ptr(g_cov3D), dL_dmeans2D=None,
-                                       skip_culled_rows=1 if getattr(ctx, "sparse_grad_rows", False) else 0)
-                N.check(lib.dqo_rast_backward(ctypes.byref(params), ctypes.byref(inputs), ctypes.byref(cctx),
-                                              grad_out_color.data_ptr(), grad_out_depth.data_ptr(), hit_depth.data_ptr(),
-                                              ctypes.byref(grads), ws.data_ptr(), ws.numel(), stream))
-                if lease is not None and cctx.frame_prezeroed:
-                    with _lock:
-                        lease.set.clean = True
-        # gradient slots of the reference (__init__.py:273-283); inputs handed over as empty tensors get None
-        def slot(g, inp):
-            return g if (g is not None and inp.numel() != 0) else None
-        return (g_means3D, slot(g_sh, sh), slot(g_colors, colors_precomp), g_opacity.view_as(opacities) if opacities.numel() else None,
-                slot(g_scales, scales), slot(g_rot, rotations), slot(g_cov3D, cov3Ds_precomp), None, None, None, None, None)
+        return _backward(ctx, grad_out_color, grad_out_depth)
+
+
+def rasterize_gaussian_params(means3D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, tile_mask, raster_settings):
+    """NOT part of the reference's surface: the operator fed with the map's RAW parameters as DQO-MAP stores them
+    (SLAM/gaussian_pointcloud.py: _xyz, _features_dc [P, 1, 3], _features_rest [P, R, 3], _opacity (logit) [P, 1], _scaling (log) [P, 3],
+    _rotation (not normalised) [P, 4]).  The activations (sigmoid, exp, F.normalize) and the SH concatenation happen inside the
+    per-Gaussian kernels (dqo_rast_*_params, include/dqo_raster.h): no activated copies, no extra launch, and the same 9-tuple, bit for
+    bit, as rasterize_gaussians fed with those copies.  Gradients go straight to the six tensors.  tile_mask=None means all tiles.
+    Every sync mode, the pooled contexts, set_list_split and verify_pending apply as to the activated entry."""
+    return _RasterizeGaussianParams.apply(means3D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, tile_mask,
+                                          raster_settings)
+
+
+class _RasterizeGaussianParams(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means3D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, tile_mask, raster_settings):
+        if means3D.ndimension() != 2 or means3D.size(1) != 3:
+            raise RuntimeError("means3D must have dimensions (num_points, 3)")
+        N.require_gpu(features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw)
+        pf = (_f32(features_dc, "features_dc"), _f32(features_rest, "features_rest"), _f32(opacity_raw, "opacity_raw"),
+              _f32(scaling_raw, "scaling_raw"), _f32(rotation_raw, "rotation_raw"))
+        P = means3D.size(0)
+        for t, name, shape in zip(pf, ("features_dc", "features_rest", "opacity_raw", "scaling_raw", "rotation_raw"),
+                                  ((P, 1, 3), None, (P, 1), (P, 3), (P, 4))):
+            if shape is not None and (t.numel() != P * shape[1] * (shape[2] if len(shape) > 2 else 1) or t.size(0) != P):
+                raise RuntimeError(f"{name} must have shape {list(shape)} (num_points = {P})")
+        if pf[1].ndimension() != 3 or pf[1].size(0) != P or pf[1].size(2) != 3:
+            raise RuntimeError(f"features_rest must have shape [{P}, R, 3]")
+        if 1 + pf[1].size(1) < (int(raster_settings.sh_degree) + 1) ** 2:
+            raise RuntimeError(f"features_rest has {pf[1].size(1)} coefficients, sh_degree {int(raster_settings.sh_degree)} needs "
+                               f"{(int(raster_settings.sh_degree) + 1) ** 2 - 1}")
+        empty = torch.empty(0, device=means3D.device)
+        return _forward(ctx, means3D, empty, empty, empty, empty, empty, empty, tile_mask, raster_settings, pf=pf)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, grad_out_depth, grad_hit_color, grad_hit_depth, grad_hit_color_weight,
+                 grad_hit_depth_weight, grad_T_map, grad_n_touched, _):
+        return _backward(ctx, grad_out_color, grad_out_depth) + (None, None)
 
 
 class GaussianRasterizationSettings(NamedTuple):

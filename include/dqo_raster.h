@@ -236,7 +236,7 @@ int dqo_abi_version(void);
 const char* dqo_last_error(void);
 /* sizeof() of the ABI structs as this library was compiled (a binding checks its own struct definitions against it):
  * 0 DqoRastParams, 1 DqoRastInputs, 2 DqoRastOutputs, 3 DqoRastCtx, 4 DqoRastGrads, 5 DqoRastHeader, 6 DqoProfileEntry,
- * 7 DqoAdamStep, 8 DqoLossTap, 9 DqoObjectGate, 10 DqoAdamTensor; 0 for any other index. */
+ * 7 DqoAdamStep, 8 DqoLossTap, 9 DqoObjectGate, 10 DqoAdamTensor, 11 DqoRastParamInputs, 12 DqoRastParamGrads; 0 for any other index. */
 size_t dqo_abi_sizeof(int32_t which);
 
 /* Optional per-kernel timing (measurement only; the reference has nothing comparable — it times whole frames with
@@ -293,6 +293,40 @@ int dqo_rast_backward(const DqoRastParams*, const DqoRastInputs*, const DqoRastC
 
 int dqo_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
                      void* hipStream);
+
+/* The parameter form (symbols-only addition to ABI 5): the same operator fed with the map's RAW parameters, as DQO-MAP stores them
+ * (SLAM/gaussian_pointcloud.py: _features_dc, _features_rest, _opacity, _scaling, _rotation), with the activations of
+ * :732-733, 746-747, 815-822 (sigmoid, exp, F.normalize) and the SH concatenation done inside the per-Gaussian kernels — no extra
+ * launch, the same bits as dqo_map_activate followed by the activated form.  The DqoRastInputs given with it must have shs, opacities,
+ * scales and rotations NULL (they come from here) and colors_precomp NULL (not supported in this form); params->M must be 1 + rest. */
+typedef struct DqoRastParamInputs {
+    const float* features_dc;   /* [P,1,3]  SH coefficient 0 */
+    const float* features_rest; /* [P,rest,3] coefficients 1 .. rest (NULL when rest == 0) */
+    int32_t rest;               /* coefficients in features_rest: 1 + rest >= (D+1)^2 */
+    const float* opacity_raw;   /* [P,1] logit:         opacity = sigmoid(x) */
+    const float* scaling_raw;   /* [P,3] log scale:     scale = exp(x) */
+    const float* rotation_raw;  /* [P,4] (r,x,y,z), not normalised: rotation = x / max(|x|, 1e-12) */
+} DqoRastParamInputs;
+
+/* Gradients w.r.t. the raw parameters (the activation Jacobians applied in registers).  Given with a DqoRastGrads whose dL_dsh,
+ * dL_dopacity, dL_dscales and dL_drotations are NULL (dL_dmeans3D stays there, dL_dcolors must be NULL). */
+typedef struct DqoRastParamGrads {
+    float* dL_dfeatures_dc;   /* [P,1,3] */
+    float* dL_dfeatures_rest; /* [P,rest,3] (NULL when rest == 0); coefficients above the active degree get zeros */
+    float* dL_dopacity_raw;   /* [P,1] */
+    float* dL_dscaling_raw;   /* [P,3] */
+    float* dL_drotation_raw;  /* [P,4] */
+} DqoRastParamGrads;
+
+int dqo_rast_forward_prepare_params(const DqoRastParams*, const DqoRastInputs*, const DqoRastParamInputs*, DqoRastOutputs*, DqoRastCtx*,
+                                    void* hipStream);
+int dqo_rast_forward_render_params(const DqoRastParams*, const DqoRastInputs*, const DqoRastParamInputs*, DqoRastOutputs*, DqoRastCtx*,
+                                   void* hipStream);
+int dqo_rast_forward_async_params(const DqoRastParams*, const DqoRastInputs*, const DqoRastParamInputs*, DqoRastOutputs*, DqoRastCtx*,
+                                  DqoRastHeader* header_host, void* header_event, void* hipStream);
+int dqo_rast_backward_params(const DqoRastParams*, const DqoRastInputs*, const DqoRastParamInputs*, const DqoRastCtx*,
+                             const float* dL_dout_color, const float* dL_dout_depth, const int32_t* hit_image, DqoRastGrads*,
+                             DqoRastParamGrads*, void* workspace, size_t workspace_bytes, void* hipStream);
 
 /* Exact 3-NN: mean of the 3 smallest squared distances and the 3 neighbour indices (ascending distance, ties by
  * Morton order, INT_MAX / FLT_MAX when fewer than 3 other points exist). */
