@@ -393,7 +393,9 @@ def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov
              gaussian_object=None, pixel_object=None, tile_objects=None, pf=None):
     """The operator's forward, shared by both entries.  pf: None (the activated form), or the parameter form's
     (features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw) — checked and contiguous — with sh, opacities, scales and
-    rotations given as empty tensors; everything else (sync modes, pooled contexts, leases, capacity hints) is the same code."""
+    rotations given as empty tensors; everything else (sync modes, pooled contexts, leases, capacity hints) is the same code.
+    ctx.row_flags (optional, set by a caller that drives forward / backward by hand — FusedMapper.step): DqoRastInputs.row_flags, uint8 [P]
+    in device memory; hidden rows are not rendered, in this forward and in its backward.  Absent or None (the drop-in operator): every row."""
     rs = raster_settings
     lib = N.lib()
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
@@ -442,6 +444,11 @@ def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov
             gate.tile_objects = N.ptr(tile_objects)
     elif tile_objects is not None:
         raise RuntimeError("object gate: tile_objects without gaussian_object / pixel_object")
+    row_flags = getattr(ctx, "row_flags", None)
+    if row_flags is not None:
+        N.require_gpu(row_flags)
+        if row_flags.dtype != torch.uint8 or row_flags.numel() != P or not row_flags.is_contiguous():
+            raise RuntimeError("row_flags must be a contiguous uint8 tensor with num_points elements")  # (read in place: no copy)
     u8 = dict(dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         stream = N.current_stream()
@@ -450,7 +457,7 @@ def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov
         geomBuffer = torch.empty((lib.dqo_rast_geom_bytes(P, W, H),), **u8)
         imgBuffer = torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8)
         params = _params(rs, P, M)
-        inputs = _inputs(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask)
+        inputs = _inputs(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask, row_flags=row_flags)
         cctx = N.DqoRastCtx(geom=geomBuffer.data_ptr(), geom_bytes=geomBuffer.numel(), binning=None, binning_bytes=0,
                             image=imgBuffer.data_ptr(), image_bytes=imgBuffer.numel(), inst_capacity=0, list_split=_list_split)
         if gate is not None:
@@ -620,7 +627,9 @@ def _backward(ctx, grad_out_color, grad_out_depth):
             cap = ctx.inst_capacity
             ws = torch.empty((lib.dqo_rast_backward_workspace_bytes(cap),), dtype=torch.uint8, device=dev)
             params = _params(rs, P, M)
-            inputs = _inputs(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask)
+            # (the forward's row flags: the per-Gaussian chain sees the rows the forward culled as culled)
+            inputs = _inputs(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask,
+                             row_flags=getattr(ctx, "row_flags", None))
             cctx = N.DqoRastCtx(geom=geomBuffer.data_ptr(), geom_bytes=geomBuffer.numel(), binning=binningBuffer.data_ptr(),
                                 binning_bytes=binningBuffer.numel(), image=imgBuffer.data_ptr(), image_bytes=imgBuffer.numel(),
                                 inst_capacity=cap, list_split=getattr(ctx, "list_split", 0))

@@ -1383,6 +1383,7 @@ class FusedMapper:
             stream = N.current_stream()
             self.activate()  # (later iterations get the activations from the previous Adam step)
             ctx = _Ctx()
+            ctx.row_flags = self.row_flags  # (hidden rows are not rendered, as in the captured iteration; the backward reads it too)
             out = dgr._RasterizeGaussians.forward(ctx, self.xyz, self.shs, self._empty, self.opacity, self.scales, self.rotations,
                                                   self._empty, self.tile_mask if tile_mask is None else tile_mask, self.settings,
                                                   self.gaussian_object, self.pixel_object)

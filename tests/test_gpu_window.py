@@ -56,9 +56,10 @@ def _state(fm):
 GROUPS = (("xyz", "xyz"), ("shs", "shs"), ("opacity", "opacity"), ("scaling", "scaling"), ("rotation", "rotation"))
 
 
-def _oracle_iteration(torch, ol, fm, cam, sc_rows, rows, s0, mask, gtc, gtd, init, lrs):
+def _oracle_iteration(torch, ol, fm, cam, sc_rows, rows, s0, mask, gtc, gtd, init, lrs, gate=None):
     """One CPU iteration on the rows `rows` (the rendered ones) from the GPU's state s0: returns (loss triple, raw-parameter gradients of
-    the fp32 and the fp64 oracle as dicts over the Adam groups, [len(rows), ...]); the rasteriser sees the GPU's own activations."""
+    the fp32 and the fp64 oracle as dicts over the Adam groups, [len(rows), ...]); the rasteriser sees the GPU's own activations.
+    gate: None, or the object gate (gaussian_object [len(rows)], pixel_object [H, W]) of the rendered rows."""
     from oracle import map_oracle as mo
     act = [a.detach().cpu().numpy() for a in fm.activate()]
     sca = dict(xyz=s0["xyz"][rows], shs=s0["shs"][rows], opacity=act[0][rows], scales=act[1][rows], rotations=act[2][rows])
@@ -67,17 +68,22 @@ def _oracle_iteration(torch, ol, fm, cam, sc_rows, rows, s0, mask, gtc, gtd, ini
     for name, dt in (("f32", np.float32), ("f64", np.float64)):
         o = ol.OracleRasterizer(dt, omp=True)
         r = o.forward(st, sca["xyz"], sca["opacity"], cam.world_view_transform, cam.full_proj_transform, cam.camera_center, shs=sca["shs"],
-                      scales=sca["scales"], rotations=sca["rotations"])
+                      scales=sca["scales"], rotations=sca["rotations"],
+                      **({} if gate is None else dict(gaussian_object=gate[0], pixel_object=gate[1])))
         out[name] = (o, r)
     return sca, out
 
 
-def _finish_oracle(ol, out, s0, rows, mask, gtc, gtd, init, attach_rows):
+def _finish_oracle(ol, out, s0, rows, mask, gtc, gtd, init, attach_rows, pixel_object=None):
+    """pixel_object: None (the masked loss), or the gate's owner map (the per-object loss of the gated job)."""
     from oracle import map_oracle as mo
     grads, loss = {}, None
     for name in ("f32", "f64"):
         o, r = out[name]
-        tot, col, dep, dC, dD = mo.masked_loss(r.color, r.depth, r.hit_depth, gtc, gtd, mask)
+        if pixel_object is None:
+            tot, col, dep, dC, dD = mo.masked_loss(r.color, r.depth, r.hit_depth, gtc, gtd, mask)
+        else:
+            tot, col, dep, dC, dD = mo.per_object_masked_loss(r.color, r.depth, r.hit_depth, gtc, gtd, pixel_object, mask)
         if name == "f32":
             loss, dL = (tot, col, dep), (dC.astype(np.float32), dD.astype(np.float32))
         g = o.backward(*dL)
