@@ -96,7 +96,10 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_quadric_iou_fwd_bwd", "dqo_quadric_adam", "dqo_tile_count_mask", "dqo_transmission_mask", "dqo_tile_color_error", "dqo_knn3_query_workspace_bytes",
            "dqo_knn3_query", "dqo_knn3_query_within", "dqo_knn3_query_grouped", "dqo_icp_workspace_bytes", "dqo_icp_normal_equations",
            "dqo_attach_pixels", "dqo_attach_decide", "dqo_growth_scales", "dqo_growth_inside", "dqo_error_maps", "dqo_map_history_merge",
-           "dqo_rast_forward_prepare_params", "dqo_rast_forward_render_params", "dqo_rast_forward_async_params", "dqo_rast_backward_params")
+           "dqo_rast_forward_prepare_params", "dqo_rast_forward_render_params", "dqo_rast_forward_async_params", "dqo_rast_backward_params",
+           "dqo_icp_gauss_newton", "dqo_track_preprocess_workspace_bytes", "dqo_track_preprocess", "dqo_track_pyramid_pixels",
+           "dqo_track_pyramid_workspace_bytes", "dqo_track_pyramid", "dqo_track_fill_model_depth", "dqo_track_p2p_workspace_bytes",
+           "dqo_track_p2p_loss")
 
 _lib = None
 
@@ -171,6 +174,19 @@ def lib():
         L.dqo_icp_workspace_bytes.restype = ctypes.c_size_t
         L.dqo_icp_workspace_bytes.argtypes = []
         L.dqo_icp_normal_equations.argtypes = [c_i32, c_i32] + [c_vp] * 5 + [c_f] * 6 + [c_vp] * 4 + [ctypes.c_size_t, c_vp]
+        L.dqo_icp_gauss_newton.argtypes = [c_i32, c_i32] + [c_vp] * 6 + [c_f] * 4 + [c_vp] * 2 + [ctypes.c_size_t, c_vp]
+        L.dqo_track_preprocess_workspace_bytes.restype = ctypes.c_size_t
+        L.dqo_track_preprocess_workspace_bytes.argtypes = [c_i32, c_i32]
+        L.dqo_track_preprocess.argtypes = [c_i32, c_i32, c_vp, c_vp] + [c_f] * 3 + [c_i32] + [c_vp] * 6 + [ctypes.c_size_t, c_vp]
+        L.dqo_track_pyramid_pixels.restype = ctypes.c_int64
+        L.dqo_track_pyramid_pixels.argtypes = [c_i32, c_i32, c_i32]
+        L.dqo_track_pyramid_workspace_bytes.restype = ctypes.c_size_t
+        L.dqo_track_pyramid_workspace_bytes.argtypes = []
+        L.dqo_track_pyramid.argtypes = [c_i32, c_i32, c_i32] + [c_vp] * 5 + [ctypes.c_size_t, c_vp]
+        L.dqo_track_fill_model_depth.argtypes = [c_i32, c_i32] + [c_vp] * 4 + [c_f, c_f, c_vp]
+        L.dqo_track_p2p_workspace_bytes.restype = ctypes.c_size_t
+        L.dqo_track_p2p_workspace_bytes.argtypes = []
+        L.dqo_track_p2p_loss.argtypes = [c_i32, c_i32] + [c_vp] * 4 + [c_f] + [c_vp] * 5 + [ctypes.c_size_t, c_vp]
         L.dqo_tile_count_mask.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp]
         L.dqo_transmission_mask.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
         L.dqo_tile_color_error.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]

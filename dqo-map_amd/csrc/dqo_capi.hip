@@ -52,6 +52,22 @@ size_t dqo_icp_ws_bytes(void);
 int dqo_launch_icp(int H, int W, const float* vertex0, const float* vertex1, const float* normal0, const float* normal1, const float* pose10,
                    float fx, float fy, float cx, float cy, float dist_thr, float normal_thr, float* JtJ, float* JtR, int32_t* valid_count,
                    void* ws, hipStream_t s);
+int dqo_launch_icp_gauss_newton(int H, int W, const float* vertex0, const float* vertex1, const float* normal0, const float* normal1, float* pose10,
+                                const float* K, float k_scale, float dist_thr, float normal_thr, float damping, int32_t* valid_count, void* ws,
+                                hipStream_t s);
+size_t dqo_track_preprocess_ws_bytes(int H, int W);
+int dqo_launch_track_preprocess(int H, int W, const float* depth, const float* K, float min_depth, float max_depth,
+                                float conf_thr, int filter, float* depth_out, float* vertex_out, float* normal_out, float* conf_out,
+                                uint8_t* invalid_out, void* ws, hipStream_t s);
+size_t dqo_track_pyramid_ws_bytes(void);
+int64_t dqo_track_pyramid_pixel_count(int H, int W, int levels);
+int dqo_launch_track_pyramid(int H, int W, int levels, const float* depth, const float* K, float* vertex, float* normal,
+                             void* ws, hipStream_t s);
+int dqo_launch_track_fill(int H, int W, float* render_depth, const float* frame_depth, const float* render_normal, const float* frame_normal,
+                          float dist_thr, float normal_thr, hipStream_t s);
+size_t dqo_track_p2p_ws_bytes(void);
+int dqo_launch_track_p2p(int H, int W, const float* vertex0, const float* vertex1, const float* normal0, const float* pose10, float fail_thr,
+                         const int32_t* valid_count, float* loss, int32_t* success, float* valid_ratio, void* ws, hipStream_t s);
 int dqo_launch_tile_count(int W, int H, int mode, const uint8_t* mask_in, const float* T_map, uint8_t* mask_out, int32_t* tile_count,
                           int32_t* total, hipStream_t s);
 int dqo_launch_tile_color_error(int W, int H, const float* render, const float* gt, float* err_px, float* tile_sum, hipStream_t s);
@@ -701,6 +717,80 @@ DQO_API int dqo_icp_normal_equations(int32_t H, int32_t W, const float* vertex0,
     }
     return dqo_launch_icp(H, W, vertex0, vertex1, normal0, normal1, pose10, fx, fy, cx, cy, dist_thr, normal_thr, JtJ, JtR, valid_count, ws,
                           (hipStream_t)stream);
+}
+
+// image sizes of the tracker entry points: positive, and H * W * 4 floats still indexable with int
+static bool track_size_ok(int32_t H, int32_t W) { return H > 0 && W > 0 && (int64_t)H * W < (int64_t)0x7fffffff / 4; }
+
+DQO_API int dqo_icp_gauss_newton(int32_t H, int32_t W, const float* vertex0, const float* vertex1, const float* normal0, const float* normal1,
+                                 float* pose10, const float* K, float k_scale, float dist_thr, float normal_thr, float damping,
+                                 int32_t* valid_count, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(H > 1 && W > 1 && (int64_t)H * W < (int64_t)0x7fffffff / 3, "bad image size");
+    DQO_CHECK_ARG(vertex0 && vertex1 && normal0 && normal1 && pose10 && K && valid_count, "null pointer");
+    if (ws == nullptr || ws_bytes < dqo_icp_ws_bytes()) {
+        dqo_set_error("icp workspace too small (%zu < %zu)", ws_bytes, dqo_icp_ws_bytes());
+        return DQO_ERR_WORKSPACE;
+    }
+    return dqo_launch_icp_gauss_newton(H, W, vertex0, vertex1, normal0, normal1, pose10, K, k_scale, dist_thr, normal_thr, damping, valid_count,
+                                       ws, (hipStream_t)stream);
+}
+
+DQO_API size_t dqo_track_preprocess_workspace_bytes(int32_t H, int32_t W) {
+    return track_size_ok(H, W) ? dqo_track_preprocess_ws_bytes(H, W) : 0;
+}
+
+DQO_API int dqo_track_preprocess(int32_t H, int32_t W, const float* depth, const float* K, float min_depth, float max_depth, float conf_thr,
+                                 int32_t depth_filter, float* depth_out, float* vertex_out, float* normal_out, float* conf_out, uint8_t* invalid_out, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(track_size_ok(H, W), "bad image size");
+    DQO_CHECK_ARG(depth && K && depth_out && vertex_out && normal_out && conf_out && invalid_out, "null pointer");
+    if (ws == nullptr || ws_bytes < dqo_track_preprocess_ws_bytes(H, W)) {
+        dqo_set_error("track preprocess workspace too small (%zu < %zu)", ws_bytes, dqo_track_preprocess_ws_bytes(H, W));
+        return DQO_ERR_WORKSPACE;
+    }
+    return dqo_launch_track_preprocess(H, W, depth, K, min_depth, max_depth, conf_thr, depth_filter ? 1 : 0, depth_out, vertex_out,
+                                       normal_out, conf_out, invalid_out, ws, (hipStream_t)stream);
+}
+
+DQO_API int64_t dqo_track_pyramid_pixels(int32_t H, int32_t W, int32_t levels) {
+    if (!track_size_ok(H, W) || levels < 1 || levels > 4) return -1;
+    return dqo_track_pyramid_pixel_count(H, W, levels);
+}
+
+DQO_API size_t dqo_track_pyramid_workspace_bytes(void) { return dqo_track_pyramid_ws_bytes(); }
+
+DQO_API int dqo_track_pyramid(int32_t H, int32_t W, int32_t levels, const float* depth, const float* K, float* vertex, float* normal, void* ws,
+                              size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(levels >= 1 && levels <= 4, "levels must be in [1, 4]");
+    DQO_CHECK_ARG(track_size_ok(H, W) && (H >> (levels - 1)) > 0 && (W >> (levels - 1)) > 0, "bad image size for %d levels", levels);
+    DQO_CHECK_ARG(depth && K && vertex && normal, "null pointer");
+    if (ws == nullptr || ws_bytes < dqo_track_pyramid_ws_bytes()) {
+        dqo_set_error("track pyramid workspace too small (%zu < %zu)", ws_bytes, dqo_track_pyramid_ws_bytes());
+        return DQO_ERR_WORKSPACE;
+    }
+    return dqo_launch_track_pyramid(H, W, levels, depth, K, vertex, normal, ws, (hipStream_t)stream);
+}
+
+DQO_API int dqo_track_fill_model_depth(int32_t H, int32_t W, float* render_depth, const float* frame_depth, const float* render_normal,
+                                       const float* frame_normal, float dist_thr, float normal_thr, void* stream) {
+    DQO_CHECK_ARG(track_size_ok(H, W), "bad image size");
+    DQO_CHECK_ARG(render_depth && frame_depth && render_normal && frame_normal, "null pointer");
+    return dqo_launch_track_fill(H, W, render_depth, frame_depth, render_normal, frame_normal, dist_thr, normal_thr, (hipStream_t)stream);
+}
+
+DQO_API size_t dqo_track_p2p_workspace_bytes(void) { return dqo_track_p2p_ws_bytes(); }
+
+DQO_API int dqo_track_p2p_loss(int32_t H, int32_t W, const float* vertex0, const float* vertex1, const float* normal0, const float* pose10,
+                               float fail_thr, const int32_t* valid_count, float* loss, int32_t* success, float* valid_ratio, void* ws,
+                               size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(track_size_ok(H, W), "bad image size");
+    DQO_CHECK_ARG(vertex0 && vertex1 && normal0 && pose10 && loss && success, "null pointer");
+    DQO_CHECK_ARG((valid_count == nullptr) == (valid_ratio == nullptr), "valid_count and valid_ratio go together");
+    if (ws == nullptr || ws_bytes < dqo_track_p2p_ws_bytes()) {
+        dqo_set_error("track p2p workspace too small (%zu < %zu)", ws_bytes, dqo_track_p2p_ws_bytes());
+        return DQO_ERR_WORKSPACE;
+    }
+    return dqo_launch_track_p2p(H, W, vertex0, vertex1, normal0, pose10, fail_thr, valid_count, loss, success, valid_ratio, ws,
+                                (hipStream_t)stream);
 }
 
 DQO_API int dqo_map_adam_step(const DqoAdamStep* st, void* stream) {

@@ -38,6 +38,14 @@ void dqo_set_error(const char* fmt, ...);
 
 static inline size_t dqo_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Intrinsics from a row-major 3x3 fp32 matrix in device memory, scaled as the reference's `K * downscale` (fp32; K[2,2] unused)
+struct DqoIntrinsics {
+    float fx, fy, cx, cy;
+};
+__device__ __forceinline__ DqoIntrinsics dqo_load_intrinsics(const float* __restrict__ K, float s) {
+    return DqoIntrinsics{K[0] * s, K[4] * s, K[2] * s, K[5] * s};
+}
+
 // ---- optional per-kernel timing (dqo_profile_enable): HIP events recorded on the launch stream around every kernel ----
 extern int g_dqo_profile_on;
 void dqo_profile_before(const char* name, hipStream_t s);

@@ -5,6 +5,11 @@ value).  Per Gauss-Newton iteration the reference builds residuals, Jacobians an
 kernels; here that is one call of libdqoraster.so's dqo_icp_normal_equations (csrc/icp.hip).  The damped 6x6 solve and the
 se(3) exponential (icp.py:248-337) are restated in double precision on the host, where the reference also runs them
 (its invH moves the matrix to the CPU).  GPU only: there is no CPU path.
+
+The rest of the tracker's per-frame work runs on the device as well (csrc/track.hip, the Gauss-Newton kernel of csrc/icp.hip):
+`preprocess_frame` is the geometry half of Tracker.map_preprocess (SLAM/multiprocess/tracker.py:118-165), and `IcpTracker` mirrors
+SLAM/icp.py:361-458 (pyramids, model-depth fill, the coarse-to-fine loop, the failure test) as stream-ordered launches whose only
+host synchronisation is predict_pose's read of the result.
 """
 import ctypes
 import math
@@ -88,3 +93,240 @@ class ICP:
         return pose10, cnt / H / W
 
     __call__ = icp
+
+
+_K_UPLOADS = {}  # (device, the nine fp32 values) -> the device copy of a host intrinsic matrix
+
+
+def _k_device(K, dev):
+    """K as a row-major 3x3 fp32 tensor on `dev` for the kernels, which read the intrinsics from device memory: no host read.
+    A GPU tensor is used where it is (converted on the device when it is not fp32 / contiguous), so a caller that builds a fresh GPU
+    intrinsic every frame pays nothing.  A host matrix (CPU tensor, numpy array, nested list) is uploaded once per distinct value and
+    device and the upload reused, which keeps repeated calls (a graph capture among them) free of copies; its values are read on
+    every call, so changing them in place takes effect."""
+    if torch.is_tensor(K) and K.is_cuda:
+        if K.device != dev:
+            raise ValueError(f"intrinsics on {K.device}, maps on {dev}")
+        return K.detach().to(torch.float32).reshape(3, 3).contiguous()
+    vals = np.asarray(K.detach() if torch.is_tensor(K) else K, dtype=np.float32).reshape(3, 3)
+    key = (str(dev), vals.tobytes())
+    if key not in _K_UPLOADS:
+        if len(_K_UPLOADS) >= 64:
+            _K_UPLOADS.clear()
+        _K_UPLOADS[key] = torch.tensor(vals, device=dev)
+    return _K_UPLOADS[key]
+
+
+def _depth2d(depth):
+    if not (torch.is_tensor(depth) and depth.is_cuda):
+        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    if depth.dim() == 3 and depth.shape[-1] == 1:
+        depth = depth[..., 0]
+    if depth.dim() != 2:
+        raise ValueError(f"depth must be [H, W] or [H, W, 1], got {tuple(depth.shape)}")
+    return depth.detach().float().contiguous()
+
+
+def preprocess_frame(depth, K, min_depth, max_depth, invalid_confidence_thresh, depth_filter=False):
+    """The geometry half of Tracker.map_preprocess (SLAM/multiprocess/tracker.py:135-156) for a metric depth map [H, W] or [H, W, 1]:
+    optional bilateral filter (radius 5, sigma 2 / 2), range mask, vertex / normal / confidence maps and the invalid-confidence mask,
+    with depth, vertex, normal and confidence zeroed where that mask is set.  Two launches (csrc/track.hip).
+
+    Returns {"depth_map": like `depth`, "vertex_map_c": [H, W, 3], "normal_map_c": [H, W, 3], "confidence_map": [H, W, 1],
+    "invalid_confidence_mask": [H, W] bool}, all new tensors; `depth` is not modified.  The reference differs there: with the
+    filter off its depth_map_filter IS depth_map, so the range mask and the zeroing also write into the frame's depth map (and
+    frame.original_depth is reassigned from it); a caller that relies on that assigns "depth_map" back itself."""
+    d = _depth2d(depth)
+    H, W = d.shape
+    lib = N.lib()
+    dev = d.device
+    Kd = _k_device(K, dev)
+    out_depth = torch.empty((H, W), dtype=torch.float32, device=dev)
+    vertex = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    normal = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    conf = torch.empty((H, W, 1), dtype=torch.float32, device=dev)
+    invalid = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    ws = torch.empty((max(1, lib.dqo_track_preprocess_workspace_bytes(H, W)),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        N.check(lib.dqo_track_preprocess(H, W, N.ptr(d), N.ptr(Kd), float(min_depth), float(max_depth), float(invalid_confidence_thresh),
+                                         1 if depth_filter else 0, N.ptr(out_depth), N.ptr(vertex), N.ptr(normal), N.ptr(conf),
+                                         N.ptr(invalid), N.ptr(ws), ws.numel(), N.current_stream()))
+    return {"depth_map": out_depth.view(depth.shape), "vertex_map_c": vertex, "normal_map_c": normal, "confidence_map": conf,
+            "invalid_confidence_mask": invalid.view(torch.bool)}
+
+
+class _TrackBuffers:
+    """Device state of an IcpTracker for one image size: three packed pyramid sets (two for the frames, one for the model depth),
+    the pose and the scalars of predict_pose_async, and the workspaces.  Allocated once per size."""
+
+    def __init__(self, H, W, levels, dev):
+        lib = N.lib()
+        self.H, self.W, self.L = H, W, levels
+        n = lib.dqo_track_pyramid_pixels(H, W, levels)
+        if n <= 0:
+            raise ValueError(f"a {H}x{W} depth map has no {levels}-level pyramid")
+        self.sizes = [(H >> (levels - 1 - i), W >> (levels - 1 - i)) for i in range(levels)]
+        self.offsets = np.concatenate([[0], np.cumsum([h * w for h, w in self.sizes])]).tolist()
+        f = dict(dtype=torch.float32, device=dev)
+        self.sets = [(torch.empty((n, 3), **f), torch.empty((n, 3), **f)) for _ in range(3)]
+        u8 = dict(dtype=torch.uint8, device=dev)
+        self.pyr_ws = torch.empty((lib.dqo_track_pyramid_workspace_bytes(),), **u8)
+        self.icp_ws = torch.empty((lib.dqo_icp_workspace_bytes(),), **u8)
+        self.p2p_ws = torch.empty((lib.dqo_track_p2p_workspace_bytes(),), **u8)
+        self.eye = torch.eye(4, **f)
+        self.pose = torch.eye(4, **f)
+        self.count = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.success = torch.ones((1,), dtype=torch.int32, device=dev)
+        self.loss = torch.zeros((1,), **f)
+        self.ratio = torch.zeros((1,), **f)
+        self.K_pyr = [None] * 3  # the device intrinsics each pyramid set was built with, and the ICP's (kept alive for the kernels)
+        self.K_icp = None
+
+    def level(self, s, i, which):
+        h, w = self.sizes[i]
+        return self.sets[s][which][self.offsets[i]:self.offsets[i + 1]].view(h, w, 3)
+
+    def pyramid(self, s, which):
+        return [self.level(s, i, which) for i in range(self.L)]
+
+
+class IcpTracker:
+    """IcpTracker of SLAM/icp.py:361-458 on the device.  Same constructor argument (an object with the reference's attribute names)
+    and methods; every method only issues stream-ordered launches, except predict_pose, whose read of the result is the tracker's only
+    host synchronisation.  After the first call for an image size, predict_pose_async allocates nothing and does not synchronise, so it
+    can be captured in a torch.cuda.graph (the graph holds the buffers of the tracker state it was captured in).  The intrinsics never
+    go to the host: the kernels read K from device memory.  A GPU K (DQO-MAP's `frame.get_intrinsic`, a fresh tensor every frame) is
+    used where it is; a host K is uploaded once per distinct value and reused (`_k_device`).  A captured graph reads the K tensor it
+    was captured with.  A fp32 GPU K that is not contiguous, or not fp32, is converted on the device, which allocates.
+
+    Differences from the reference: on the first frame (no last-frame pyramids) predict_pose returns (identity, True) — the reference
+    returns its identity too but then raises a TypeError indexing the missing pyramids for its loss (icp.py:450); the 6x6 solve is in
+    double with a Cholesky-or-Jacobi pseudo-inverse; the loss and the valid ratio are printed only when
+    `verbose`."""
+
+    def __init__(self, args):
+        self.icp_downscales = list(args.icp_downscales)
+        self.icp_warmup_frames = args.icp_warmup_frames
+        self.icp_use_model_depth = args.icp_use_model_depth
+        self.icp_trackers = [ICP(iters, distance_threshold=args.icp_distance_threshold, normal_threshold=args.icp_normal_threshold,
+                                 damping=args.icp_damping, verbose=args.verbose) for iters in args.icp_downscale_iters]
+        if not 1 <= len(self.icp_downscales) <= 4 or len(self.icp_trackers) != len(self.icp_downscales):
+            raise ValueError("icp_downscales: 1 to 4 levels, one entry of icp_downscale_iters per level")
+        self.icp_sample_distance_threshold = args.icp_sample_distance_threshold
+        self.icp_sample_normal_threshold = args.icp_sample_normal_threshold
+        self.icp_fail_threshold = args.icp_fail_threshold
+        self.verbose = args.verbose
+        self.K = None
+        self._bufs = {}
+        self._t0 = self._t1 = None  # (buffers, pyramid set) of the last / current frame
+        self.depth_t1 = self.last_model_depth = None
+
+    # -- pyramids in the reference's attribute names (views of the device buffers) -------------------------------------------------
+    def _pyr(self, ref, which):
+        return None if ref is None else ref[0].pyramid(ref[1], which)
+
+    vertex_pyramid_t0 = property(lambda self: self._pyr(self._t0, 0))
+    normal_pyramid_t0 = property(lambda self: self._pyr(self._t0, 1))
+    vertex_pyramid_t1 = property(lambda self: self._pyr(self._t1, 0))
+    normal_pyramid_t1 = property(lambda self: self._pyr(self._t1, 1))
+
+    def _buffers(self, d):
+        key = (d.shape[0], d.shape[1], d.device)
+        if key not in self._bufs:
+            self._bufs[key] = _TrackBuffers(d.shape[0], d.shape[1], len(self.icp_downscales), d.device)
+        return self._bufs[key]
+
+    def _build(self, b, s, depth):
+        d = _depth2d(depth)
+        if d.shape != (b.H, b.W):
+            raise ValueError(f"depth map {tuple(d.shape)} does not match the tracker's {b.H}x{b.W} frames")
+        v, n = b.sets[s]
+        b.K_pyr[s] = _k_device(self.K, d.device)  # the tracker's K (the first one given), as build_vertex_pyramid uses it
+        lib = N.lib()
+        with torch.cuda.device(d.device):
+            N.check(lib.dqo_track_pyramid(b.H, b.W, b.L, N.ptr(d), N.ptr(b.K_pyr[s]), N.ptr(v), N.ptr(n), N.ptr(b.pyr_ws),
+                                          b.pyr_ws.numel(), N.current_stream()))
+
+    def update_curr_status(self, depth_t1, K):
+        """icp.py:391-396: vertex / normal pyramids of the current frame's depth with the tracker's K (the first one it was given)."""
+        if self.K is None:
+            self.K = K
+        self.depth_t1 = depth_t1
+        b = self._buffers(_depth2d(depth_t1))
+        s = 0 if self._t0 != (b, 0) else 1  # never the set the last frame's pyramids live in
+        self._t1 = (b, s)
+        self._build(b, s, depth_t1)
+
+    def move_last_status(self):
+        """icp.py:398-401: the current frame becomes the last one (its pyramids are shared until the next update_curr_status)."""
+        self._t0 = self._t1
+        self.last_model_depth = self.depth_t1
+
+    def update_last_status(self, frame, render_depth, frame_depth, render_normal, frame_normal):
+        """icp.py:403-421: render_depth ([H, W] or [H, W, 1], contiguous fp32 on the GPU) takes frame_depth IN PLACE where the two
+        disagree (depth difference, empty render, normal angle) and the frame has depth; it becomes the model depth."""
+        for t in (render_depth, frame_depth, render_normal, frame_normal):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise RuntimeError("update_last_status: contiguous fp32 GPU tensors expected (render_depth is updated in place)")
+        H, W = render_depth.shape[:2]
+        if frame_depth.numel() != H * W or render_normal.numel() != 3 * H * W or frame_normal.numel() != 3 * H * W:
+            raise ValueError("update_last_status: maps of different sizes")
+        lib = N.lib()
+        with torch.cuda.device(render_depth.device):
+            N.check(lib.dqo_track_fill_model_depth(H, W, N.ptr(render_depth), N.ptr(frame_depth), N.ptr(render_normal), N.ptr(frame_normal),
+                                                   float(self.icp_sample_distance_threshold), float(self.icp_sample_normal_threshold),
+                                                   N.current_stream()))
+        self.last_model_depth = render_depth
+
+    def predict_pose_async(self, frame):
+        """predict_pose on the device: (pose_t1_t0 [4, 4] fp32, success [1] int32, p2p loss [1] fp32, valid ratio [1] fp32), tensors
+        owned by the tracker (overwritten by the next call for the same image size).  The first frame gives the identity, success 1,
+        loss 0 and ratio 0."""
+        K, frame_id = frame["K"], frame["frame_id"]
+        if self._t1 is None:
+            raise RuntimeError("predict_pose before update_curr_status")
+        b = self._t1[0]
+        if self._t0 is None:
+            self.K = K
+            b.pose.copy_(b.eye)
+            b.success.fill_(1)
+            b.loss.zero_()
+            b.ratio.zero_()
+            return b.pose, b.success, b.loss, b.ratio
+        if self._t0[0] is not b:
+            raise ValueError("the last and the current frame differ in size")
+        if self.icp_use_model_depth and frame_id >= self.icp_warmup_frames:
+            self._build(b, 2, self.last_model_depth)
+            self._t0 = (b, 2)
+        b.K_icp = _k_device(K, b.pose.device)  # held: the launches (or a captured graph) read it
+        s0, s1 = self._t0[1], self._t1[1]
+        lib = N.lib()
+        with torch.cuda.device(b.pose.device):
+            stream = N.current_stream()
+            b.pose.copy_(b.eye)
+            for level, ds in enumerate(self.icp_downscales):
+                h, w = b.sizes[level]
+                icp = self.icp_trackers[level]
+                # icp.py:445-448: the current frame's maps are ICP's frame 0, the last frame's its frame 1
+                v0, n0 = b.level(s1, level, 0), b.level(s1, level, 1)
+                v1, n1 = b.level(s0, level, 0), b.level(s0, level, 1)
+                for _ in range(icp.max_iterations):
+                    N.check(lib.dqo_icp_gauss_newton(h, w, N.ptr(v0), N.ptr(v1), N.ptr(n0), N.ptr(n1), N.ptr(b.pose), N.ptr(b.K_icp),
+                                                     float(ds), float(icp.distance_threshold), float(icp.normal_threshold), float(icp.damping),
+                                                     N.ptr(b.count), N.ptr(b.icp_ws), b.icp_ws.numel(), stream))
+            h, w = b.sizes[-1]
+            N.check(lib.dqo_track_p2p_loss(h, w, N.ptr(b.level(s0, b.L - 1, 0)), N.ptr(b.level(s1, b.L - 1, 0)), N.ptr(b.level(s0, b.L - 1, 1)),
+                                           N.ptr(b.pose), float(self.icp_fail_threshold), N.ptr(b.count), N.ptr(b.loss), N.ptr(b.success),
+                                           N.ptr(b.ratio), N.ptr(b.p2p_ws), b.p2p_ws.numel(), stream))
+        return b.pose, b.success, b.loss, b.ratio
+
+    def predict_pose(self, frame):
+        """icp.py:423-458: (pose_t1_t0 as a float32 numpy [4, 4], tracking_success).  The one host synchronisation of the tracker."""
+        if self._t0 is None:
+            self.K = frame["K"]
+            return np.eye(4, dtype=np.float32), True
+        pose, success, loss, ratio = self.predict_pose_async(frame)
+        host = torch.cat([pose.reshape(-1), loss, ratio, success.float()]).cpu().numpy()
+        if self.verbose:
+            print(host[16], host[17])
+        return host[:16].reshape(4, 4).copy(), bool(host[18] != 0)

@@ -517,6 +517,52 @@ int dqo_icp_normal_equations(int32_t H, int32_t W, const float* vertex0, const f
                              float normal_threshold, float* JtJ, float* JtR, int32_t* valid_count, void* workspace,
                              size_t workspace_bytes, void* hipStream);
 
+/* Row f4 — one Gauss-Newton iteration of ICP.icp on the device (SLAM/icp.py:33-47, 248-337): dqo_icp_normal_equations' pass, then
+ * one block that folds its partials in the same order, forms lev_mar_H = JtJ + damping * trace(JtJ) * I in fp32, solves
+ * xi = -H^-1 JtR in double (Cholesky; a cyclic-Jacobi pseudo-inverse with numpy.linalg.pinv's cutoff when H is not positive
+ * definite, so H == 0 gives xi = 0) and updates pose10 <- exp_se3(xi) @ pose10 IN PLACE (exp in double, the product in fp32).
+ * valid_count [1] gets the iteration's valid pixel count.  Two launches, no host copy: an ICP level of n iterations is n calls.
+ * K: the intrinsics as a row-major 3x3 fp32 matrix in DEVICE memory, used as K * k_scale (fp32, icp.py:437-439), so a per-frame
+ * GPU intrinsic needs no host read.  workspace: dqo_icp_workspace_bytes(). */
+int dqo_icp_gauss_newton(int32_t H, int32_t W, const float* vertex0, const float* vertex1, const float* normal0, const float* normal1,
+                         float* pose10, const float* K, float k_scale, float distance_threshold, float normal_threshold, float damping,
+                         int32_t* valid_count, void* workspace, size_t workspace_bytes, void* hipStream);
+
+/* Tracker frame geometry (Tracker.map_preprocess, SLAM/multiprocess/tracker.py:135-156) of a metric depth map [H, W]:
+ * optional bilateralFilter_torch(depth, 5, 2, 2) (depth_filter != 0), range mask min_depth < d < max_depth, compute_vertex_map,
+ * compute_normal_map (Sobel, cross(dy, dx), zero where z <= min z or z >= max z over the whole map), compute_confidence_map,
+ * invalid = (normal == 0).all() | confidence < invalid_confidence_thresh, and depth / vertex / normal / confidence zeroed there.
+ * Out: depth_out [H, W], vertex_out / normal_out [H, W, 3], confidence_out [H, W], invalid_out [H, W] (0 / 1).  depth_out may
+ * be `depth` itself (in place).  K: row-major 3x3 fp32 intrinsics in device memory, as for dqo_icp_gauss_newton.  Two launches. */
+size_t dqo_track_preprocess_workspace_bytes(int32_t H, int32_t W);
+int dqo_track_preprocess(int32_t H, int32_t W, const float* depth, const float* K, float min_depth, float max_depth,
+                         float invalid_confidence_thresh, int32_t depth_filter, float* depth_out, float* vertex_out, float* normal_out,
+                         float* confidence_out, uint8_t* invalid_out, void* workspace, size_t workspace_bytes, void* hipStream);
+
+/* Vertex / normal pyramids of a depth map [H, W] (ImagePyramids("max") + build_vertex_pyramid + build_normal_pyramid, SLAM/icp.py:340-358,
+ * SLAM/utils.py:542-558).  `levels` in [1, 4]; level i (coarsest first) max-pools by 2^(levels-1-i) with floor sizes
+ * (H >> (levels-1-i), W >> ...), takes K * 2^-(levels-1-i) (K[2,2] = 1) for its vertex map and the normal rule of
+ * dqo_track_preprocess per level.  vertex / normal hold the levels packed in that order: dqo_track_pyramid_pixels(H, W, levels)
+ * rows of 3 floats each.  K: device intrinsics as for dqo_icp_gauss_newton.  Two launches. */
+int64_t dqo_track_pyramid_pixels(int32_t H, int32_t W, int32_t levels);
+size_t dqo_track_pyramid_workspace_bytes(void);
+int dqo_track_pyramid(int32_t H, int32_t W, int32_t levels, const float* depth, const float* K, float* vertex, float* normal,
+                      void* workspace, size_t workspace_bytes, void* hipStream);
+
+/* IcpTracker.update_last_status (SLAM/icp.py:403-421), in place on render_depth [H, W]: where frame_depth > 0 and
+ * (|render - frame| > sample_distance_threshold or render == 0 or 1 - cos(render_normal, frame_normal) > sample_normal_threshold),
+ * render_depth takes frame_depth.  Normals [H, W, 3].  One launch. */
+int dqo_track_fill_model_depth(int32_t H, int32_t W, float* render_depth, const float* frame_depth, const float* render_normal,
+                               const float* frame_normal, float sample_distance_threshold, float sample_normal_threshold, void* hipStream);
+
+/* predict_pose's failure test (SLAM/icp.py:7-14, 450-457): loss [1] = mean over all H * W pixels of ((R v1 + t - v0) . n0)^2 with
+ * pose10's R, t — pixel-aligned, no data association; success [1] = !(loss > fail_threshold).  valid_count non-NULL: valid_ratio [1]
+ * = valid_count / H / W in fp32 (the last ICP level's ratio when that level is this H x W).  Two launches. */
+size_t dqo_track_p2p_workspace_bytes(void);
+int dqo_track_p2p_loss(int32_t H, int32_t W, const float* vertex0, const float* vertex1, const float* normal0, const float* pose10,
+                       float fail_threshold, const int32_t* valid_count, float* loss, int32_t* success, float* valid_ratio, void* workspace,
+                       size_t workspace_bytes, void* hipStream);
+
 #define DQO_TICKET_WORDS (16 + 16 * 64) /* int32 words behind DqoAdamStep.block_ticket */
 typedef struct DqoAdamStep {
     int32_t P, M;      /* Gaussians, SH coefficients per Gaussian (f_dc = coefficient 0, f_rest = the others) */
