@@ -25,8 +25,10 @@ With a render mask (every live call site of the reference) the loss is the maske
 one the SSIM term of mapper.py:839-845 is added by dqo_map_ssim_fwd_bwd (three launches; the loss tap is off then — the SSIM gradient
 is an image).  GPU only.
 """
+import collections
 import ctypes
 import os
+import threading
 
 import numpy as np
 import torch
@@ -90,6 +92,61 @@ class _Ctx:
         pass
 
 
+class _SideJob:
+    """`work` on the stream `side`, beside the caller's own kernels: start() runs it on a host thread of its own (threaded=False: in
+    line, the A/B of the overlap); result() joins both and returns what it returned or raises what it raised."""
+
+    def __init__(self, work, side, threaded):
+        self.work, self.side, self.value, self.error = work, side, None, None
+        self.thread = threading.Thread(target=self._run) if threaded else None
+
+    def _run(self):
+        try:
+            self.value = self.work()
+        except BaseException as e:  # (re-raised by result(), in the caller's thread)
+            self.error = e
+
+    def start(self):
+        self.thread.start() if self.thread is not None else self._run()
+        return self
+
+    def result(self):
+        if self.thread is not None:
+            self.thread.join()
+        torch.cuda.current_stream().wait_stream(self.side)
+        if self.error is not None:
+            raise self.error
+        return self.value
+
+
+# Every tensor of a FusedMapper with one row per Gaussian, declared once.  reserve(), grow(), begin_mapping_call() and the state snapshots
+# iterate this table (FusedMapper._rows) instead of naming the buffers: a new per-Gaussian buffer is one line here plus the code that
+# uses it.  A buffer is the mapper's attribute `name` (`of` = (k, i): the Adam moment state[k][i]), None while it does not exist.
+#   group  "param" the raw parameters Adam trains | "moment" Adam's moments and the sparse Adam's flag | "snapshot" init_stat of the
+#          mapping call (src: the parameter begin_mapping_call copies; attach_mask is computed) | "meta" what a row is | "sized" sized
+#          by P (shape: P -> shape), made anew when P changes (spare None: uninitialised, else the fill) | "dropped" dropped when P changes
+#   spare  the value of a spare row (reserve): "park" = _park_position(), "unit_q" = the unit quaternion
+#   freed  an in-place growth step writes `spare` into the rows it frees: what makes the row a spare row for the kernels
+#   live   the value of a row a Gaussian moves into, where the growth step computes none
+_RowBuffer = collections.namedtuple("_RowBuffer", "name group spare freed live src of shape", defaults=(None, False, 0, None, None, None))
+_ROW_BUFFERS = (
+    _RowBuffer("xyz", "param", "park", freed=True), _RowBuffer("shs", "param", 0.0), _RowBuffer("opacity_raw", "param", -10.0, freed=True),
+    _RowBuffer("scaling_raw", "param", -10.0, freed=True), _RowBuffer("rotation_raw", "param", "unit_q"),
+    *(_RowBuffer(f"state[{k}][{i}]", "moment", 0.0, of=(k, i)) for k in ("xyz", "shs", "opacity", "scaling", "rotation") for i in (0, 1)),
+    _RowBuffer("moment_live", "moment", 0),
+    _RowBuffer("init_xyz", "snapshot", "park", src="xyz"), _RowBuffer("init_scaling", "snapshot", -10.0, src="scaling_raw"),
+    _RowBuffer("init_rotation", "snapshot", "unit_q", src="rotation_raw"), _RowBuffer("attach_mask", "snapshot", 0),
+    _RowBuffer("alive", "meta", 0, freed=True, live=1),
+    _RowBuffer("row_flags", "meta", N.ROW_HIDDEN | N.ROW_FROZEN, freed=True),  # (a spare row: not rendered, not trained)
+    _RowBuffer("confidence", "meta", 0.0, freed=True), _RowBuffer("gaussian_object", "meta", 0),
+    _RowBuffer("opacity", "sized", shape=lambda P: (P, 1)), _RowBuffer("scales", "sized", shape=lambda P: (P, 3)),
+    _RowBuffer("rotations", "sized", shape=lambda P: (P, 4)),
+    # (one partial sum per block of 256 Gaussians from dqo_map_adam_step, per wave of 64 from dqo_rast_backward_adam)
+    _RowBuffer("attach_partial", "sized", 0.0, shape=lambda P: (4 * ((P + 255) // 256),)),
+    _RowBuffer("init_shs", "dropped"), _RowBuffer("init_confidence", "dropped"),
+)
+
+
 class _FrameGraph:
     """One captured mapping iteration of a FusedMapper (capture()): the frame's inputs, the options it was captured with, and the
     capacities, buffers and C structs the capture fixed (the graph holds their addresses)."""
@@ -150,9 +207,9 @@ class FusedMapper:
         self._expected_step, self._unsettled = 1, False
         # DqoAdamStep.block_ticket: the Adam launch advances the device step count itself (False: a one-thread launch behind it does)
         self.use_block_ticket = True
-        self._g = None     # the graph replayed last / by default (a _FrameGraph)
-        self._frames = []  # the captured graphs of a window (capture_window)
-        self._mixed = {}   # (k, m) -> graph of frame k's camera and target under frame m's masks (global_optimization's quirk)
+        # _g: the graph replayed last / by default (a _FrameGraph); _frames: the captured graphs of a window (capture_window);
+        # _mixed: (k, m) -> graph of frame k's camera and target under frame m's masks (global_optimization's quirk)
+        self._drop_graphs()
         self._window_kw, self._window_frames = {}, []  # capture_window's arguments: _graph_of captures mixed graphs from them
         self._last_probe = None  # (candidates, longest list, P) the last capture was sized on: capture(reuse_probe=True)
         self._side_stream = None  # grow()'s stream for the attach step (made once: creating a stream costs a growth step ~1 ms)
@@ -180,17 +237,14 @@ class FusedMapper:
         self.object_cell = None  # per-object growth decisions: cell size of dqo_mapgrowth.object_offsets (None = its 16 m default)
         self.per_object_loss = False
         self.alive = None  # reserve(): uint8 [P], 0 = a spare row (parked behind the camera, no Gaussian of the map)
-        self._n_spare = 0
+        self._n_spare = self._spare_rows = 0  # spare rows now (host copy of the count: grow() keeps it up to date) / as reserve()d
         # DqoAdamStep.attach_gains: the attach term's two factors in device memory, rewritten in place by begin_mapping_call — a captured
         # graph survives a new mapping call
         self.attach_gains = torch.zeros((2,), dtype=torch.float32, device=device)
-        self.init_xyz = None  # init_stat: begin_mapping_call takes it
+        self.init_xyz = self.init_scaling = self.init_rotation = self.attach_mask = None  # init_stat: begin_mapping_call takes it
+        self._row_count_changed()  # (makes the activations and attach_partial)
         self.begin_mapping_call(reset_optimizer=False)
-        P = self.P
         f = dict(dtype=torch.float32, device=device)
-        self.opacity = torch.empty((P, 1), **f)
-        self.scales = torch.empty((P, 3), **f)
-        self.rotations = torch.empty((P, 4), **f)
         H, W = settings.image_height, settings.image_width
         self.dL_dcolor = torch.empty((3, H, W), **f)
         self.dL_ddepth = torch.empty((1, H, W), **f)
@@ -319,23 +373,20 @@ class FusedMapper:
                 self.init_shs.copy_(self.shs), self.init_confidence.copy_(self.confidence)
             else:
                 self.init_shs, self.init_confidence = self.shs.clone(), self.confidence.clone()
-        same = self.init_xyz is not None and self.init_xyz.shape[0] == P and self.attach_mask.shape[0] == P
-        if same:
-            self.init_xyz.copy_(self.xyz), self.init_scaling.copy_(self.scaling_raw), self.init_rotation.copy_(self.rotation_raw)
-            self.attach_mask.copy_(mask)
-            self.attach_partial.zero_()
-        else:
-            self.init_xyz, self.init_scaling, self.init_rotation = self.xyz.clone(), self.scaling_raw.clone(), self.rotation_raw.clone()
-            self.attach_mask = mask.to(torch.uint8).contiguous()
-            # (one partial sum per block of 256 Gaussians from dqo_map_adam_step, per wave of 64 from dqo_rast_backward_adam)
-            self.attach_partial = torch.zeros((4 * ((P + 255) // 256),), dtype=torch.float32, device=self.device)
+        snapshot = [b for b in _ROW_BUFFERS if b.group == "snapshot"]
+        same = all(getattr(self, b.name) is not None and getattr(self, b.name).shape[0] == P for b in snapshot)
+        for b in snapshot:
+            src = mask if b.src is None else getattr(self, b.src)  # (attach_mask: the set found above)
+            if same:
+                getattr(self, b.name).copy_(src)
+            else:
+                setattr(self, b.name, src.to(torch.uint8) if b.src is None else src.clone())
+        self.attach_partial.zero_()
         self._count_attach_set()
         self._attach_n = 0
         if reset_optimizer:
-            for m, v in self.state.values():
-                m.zero_(), v.zero_()
-            if self.moment_live is not None:
-                self.moment_live.zero_()
+            for _, a in self._rows("moment"):
+                a.zero_()
             self.step_count = 0
             self._step_dev.fill_(1)
             self._expected_step, self._unsettled = 1, False
@@ -391,6 +442,84 @@ class FusedMapper:
         V = self.settings.viewmatrix  # world_view_transform as the reference passes it: p_view = p @ V[:3, :3] + V[3, :3]
         return (self.settings.campos.reshape(3) - 1.0e4 * V[:3, 2]).to(torch.float32)
 
+    # ------------------------------------------------------------------ the per-Gaussian buffers (_ROW_BUFFERS) ----------
+    def _rows(self, *groups):
+        """(declaration, tensor) of every per-Gaussian buffer of the given groups (none given: all of them) that exists now."""
+        for b in _ROW_BUFFERS:
+            if not groups or b.group in groups:
+                a = self.state[b.of[0]][b.of[1]] if b.of else getattr(self, b.name)
+                if a is not None:
+                    yield b, a
+
+    def _set_rows(self, b, a):
+        if b.of:
+            pair = list(self.state[b.of[0]])
+            pair[b.of[1]] = a
+            self.state[b.of[0]] = tuple(pair)
+        else:
+            setattr(self, b.name, a)
+
+    def _spare_value(self, b):
+        if b.spare == "park":
+            return self._park_position()
+        if b.spare == "unit_q":
+            import dqo_mapgrowth as mg
+            return mg.const_tensor([1.0, 0.0, 0.0, 0.0], self.device)
+        return b.spare
+
+    @staticmethod
+    def _write_rows(a, rows, value):
+        """a[rows] = value.  (index_fill_ carries a scalar as a kernel argument; `a[rows] = scalar` stages it through a host tensor: a
+        blocking copy.)"""
+        if torch.is_tensor(value):
+            a[rows] = value
+        else:
+            a.index_fill_(0, rows, value)
+
+    def _free_rows(self, rows):
+        """In place: the Gaussians of `rows` leave the map.  Only what makes a row a spare row for the kernels is written (`freed` in
+        _ROW_BUFFERS); the other buffers keep their bits until a Gaussian moves in or the next mapping call rewrites them."""
+        for b, a in self._rows("param", "meta"):
+            if b.freed:
+                self._write_rows(a, rows, self._spare_value(b))
+
+    def _fill_rows(self, rows, new):
+        """In place: the Gaussians of `new` (buffer name -> their rows' values) move into `rows`.  What growth adds is rendered and trained by
+        the next call (the unstable cloud, mapper.py:1438-1466) with confidence 0; moments and init_stat are the next mapping call's."""
+        for b, a in self._rows("param", "meta"):
+            self._write_rows(a, rows, new.get(b.name, b.live))
+
+    def _compact_and_append(self, keep_old, new, carry_call):
+        """Into new buffers: the old rows `keep_old` (indices; None = all) in order, then the Gaussians of `new`.  A new row holds what
+        `new` gives for the buffer, or for the parameter the buffer is a snapshot of, and zeros elsewhere.  carry_call: the mapping call
+        goes on, so moments and init_stat come along; else the moments are made empty and init_stat is left to begin_mapping_call, which
+        would overwrite both (a third of the step's copies)."""
+        n = new["xyz"].shape[0]
+        for b, a in self._rows("param", "meta", *(("moment", "snapshot") if carry_call else ())):
+            add = new.get(b.name, new.get(b.src))
+            if add is None:
+                add = torch.zeros((n,) + tuple(a.shape[1:]), dtype=a.dtype, device=self.device)
+            self._set_rows(b, torch.cat([a if keep_old is None else a[keep_old], add]).contiguous())
+        self.P = self.xyz.shape[0]
+        if not carry_call:
+            for b, a in self._rows("moment", "snapshot"):
+                self._set_rows(b, None if b.group == "snapshot" else torch.zeros((self.P,) + tuple(a.shape[1:]), dtype=a.dtype, device=self.device))
+
+    def _drop_graphs(self):
+        self._g, self._frames, self._mixed = None, [], {}
+
+    def _row_count_changed(self):
+        """After P changed: what is sized by P is made anew (the one place the activations and attach_partial are allocated), what holds
+        for one P only and every captured graph (whose kernel arguments are the old buffers and their length) is dropped."""
+        for b in _ROW_BUFFERS:
+            if b.group == "dropped":
+                setattr(self, b.name, None)
+            elif b.group == "sized":
+                make = torch.empty if b.spare is None else torch.zeros
+                setattr(self, b.name, make(b.shape(self.P), dtype=torch.float32, device=self.device))
+        self._attach_n, self._act_valid = 0, False
+        self._drop_graphs()
+
     @torch.no_grad()
     def reserve(self, spare_rows):
         """Room for `spare_rows` more Gaussians in every per-Gaussian buffer, so that a growth step writes the new Gaussians into spare
@@ -402,38 +531,17 @@ class FusedMapper:
         n = int(spare_rows)
         if n <= 0:
             return self
-        dev, P0 = self.device, self.xyz.shape[0]
-
-        def pad(a, fill):
-            tail = torch.empty((n,) + tuple(a.shape[1:]), dtype=a.dtype, device=dev)
-            tail[:] = fill if not torch.is_tensor(fill) else fill.to(a.dtype)
-            return torch.cat([a, tail]).contiguous()
-
-        park = self._park_position()
-        import dqo_mapgrowth as mg
-        unit_q = mg.const_tensor([1.0, 0.0, 0.0, 0.0], dev)
-        self.alive = pad(self.alive if self.alive is not None else torch.ones((P0,), dtype=torch.uint8, device=dev), 0)
-        self.init_xyz, self.init_scaling, self.init_rotation = pad(self.init_xyz, park), pad(self.init_scaling, -10.0), pad(self.init_rotation, unit_q)
-        self.xyz, self.shs = pad(self.xyz, park), pad(self.shs, 0.0)
-        self.opacity_raw, self.scaling_raw, self.rotation_raw = pad(self.opacity_raw, -10.0), pad(self.scaling_raw, -10.0), pad(self.rotation_raw, unit_q)
-        self.state = {k: (pad(m, 0.0), pad(v, 0.0)) for k, (m, v) in self.state.items()}
-        if self.moment_live is not None:
-            self.moment_live = pad(self.moment_live, 0)
-        if self.gaussian_object is not None:
-            self.gaussian_object = pad(self.gaussian_object, 0)
-        self.attach_mask = pad(self.attach_mask, 0)
-        self.row_flags = pad(self.row_flags, N.ROW_HIDDEN | N.ROW_FROZEN)  # (a spare row: not rendered, not trained)
-        self.confidence = pad(self.confidence, 0.0)
-        self.init_shs = self.init_confidence = None
+        if self.alive is None:
+            self.alive = torch.ones((self.P,), dtype=torch.uint8, device=self.device)
+        for b, a in self._rows("param", "moment", "snapshot", "meta"):
+            fill = self._spare_value(b)
+            tail = torch.empty((n,) + tuple(a.shape[1:]), dtype=a.dtype, device=self.device)
+            tail[:] = fill.to(a.dtype) if torch.is_tensor(fill) else fill
+            self._set_rows(b, torch.cat([a, tail]).contiguous())
         self._spare_rows = n
         self._n_spare = int(self.alive.numel() - int(self.alive.sum().item()))  # (host copy of the spare-row count: grow() keeps it up to date)
-        self.P = P = P0 + n
-        f = dict(dtype=torch.float32, device=dev)
-        self.opacity, self.scales, self.rotations = torch.empty((P, 1), **f), torch.empty((P, 3), **f), torch.empty((P, 4), **f)
-        self.attach_partial = torch.zeros((4 * ((P + 255) // 256),), **f)
-        self._attach_n = 0
-        self._act_valid = False
-        self._g, self._frames, self._mixed = None, [], {}
+        self.P += n
+        self._row_count_changed()
         return self
 
     @property
@@ -444,7 +552,8 @@ class FusedMapper:
     def grow(self, new, delete_mask=None, min_radius=0.001, max_radius=0.05, xyz_factor=(1.0, 1.0, 0.1), scale_factor=1.0,
              new_mapping_call=False, stable_mask=None, unstable_opacity_low=0.1, attach_async=True):
         """The map-growth step between two mapping calls — Mapping.gaussians_add (SLAM/multiprocess/mapper.py:249-254) and the
-        deletion half of error_gaussians_remove (:1086-1096) — on this mapper's map:
+        deletion half of error_gaussians_remove (:1086-1096) — on this mapper's map.  `new`: dict(xyz [Q,3], scales [Q,3],
+        rotations [Q,4], opacity [Q,1], shs [Q,M,3]; with an object gate also obj_id [Q]) of numpy arrays or GPU tensors.
           1. temp_points_filter (:1351-1380): new points that fall inside an existing Gaussian (one of their 3 nearest existing
              centres closer than 0.6 x its radius; dqo_knn3_query) are dropped;
           2. temp_to_optimize -> GaussianPointCloud.update_geometry (:1438-1442, gaussian_pointcloud.py:519-570): the survivors'
@@ -453,217 +562,188 @@ class FusedMapper:
           3. delete_mask [P] bool (optional): existing Gaussians to delete (the reference derives it from
              accumulate_gaussian_error's per-Gaussian depth error, cuda_utils._C);
           4. cat (:1466): the rest joins the map with zero Adam moments.
-        stable_mask [P] bool GPU tensor (optional) is the reference's split into its two clouds — 1 = a Gaussian of `stable_pointcloud`, 0 =
-        of the unstable `pointcloud`; an in-place step clears it IN PLACE on the rows the new Gaussians take — and switches on the two
-        steps that need it:
+        stable_mask [P] bool GPU tensor (optional) is the reference's split into its two clouds — 1 = a Gaussian of `stable_pointcloud`,
+        0 = of the unstable `pointcloud` — and switches on the two steps that need it:
           1'. the filter of step 1 looks at the UNSTABLE Gaussians only (:1356-1357, unstable_params);
           1b. temp_points_attach (:1384-1436): the survivors of step 1 that project onto a pixel whose strongest contributor in a render
              of the STABLE Gaussians alone exists and whose plane they lie within 0.5 x add_depth_thres of get opacity
              `unstable_opacity_low` — which makes them members of the next mapping call's attach set (opacity < 0.9).  The stable-only
              render is this mapper's map with the other Gaussians parked behind the camera (the index map is the stable cloud's, in
              map rows).
-        With reserve()d spare rows and new_mapping_call=True the step is IN PLACE: deleted Gaussians become spare rows, new ones take
-        spare rows (row order then differs from the reference's cat; nothing depends on it), no buffer moves and a captured graph
-        stays valid; it falls back to re-allocation (with the same number of spare rows again) when the spare rows run out.  `new`: dict(xyz [Q,3], scales [Q,3], rotations [Q,4], opacity [Q,1], shs [Q,M,3]) of numpy arrays or GPU
-        tensors.  Per-Gaussian buffers are re-allocated: a captured graph is dropped (capture() again), and the next mapping
-        call starts with begin_mapping_call() — new_mapping_call=True does that here (fresh Adam, fresh init_stat, as the reference
-        does after every growth step, mapper.py:533-548) and then neither gathers nor concatenates the old moments and snapshots,
-        which the new call would overwrite (a third of the step's copies).  Returns the counts of each stage."""
-        import dqo_mapgrowth as mg
-        dev = self.device
-        t = lambda a: a.to(dev).float().contiguous() if torch.is_tensor(a) else torch.tensor(np.ascontiguousarray(a, np.float32), device=dev)
-        nx, nsc, nrot, nop, nsh = t(new["xyz"]), t(new["scales"]), t(new["rotations"]), t(new["opacity"]).reshape(-1, 1), t(new["shs"])
-        Q = nx.shape[0]
-        nobj = None
-        if self.gaussian_object is not None:  # the object gate needs every new Gaussian's object id (`_obj_id`, gaussian_pointcloud.py:497)
-            if new.get("obj_id") is None:
-                raise RuntimeError("FusedMapper.grow: with an object gate the new points need 'obj_id'")
-            nobj = torch.as_tensor(new["obj_id"]).to(dev, torch.int32).reshape(-1)
+        With an object gate every decision judges a candidate against the Gaussians of its OWN object only (dqo_mapgrowth.*_per_object),
+        so a shard — which holds whole objects — takes exactly the decisions the unsharded map takes for its objects.
+        The result is stored in one of two ways (_store_in_place / _store_reallocating say what each means for captured graphs): in
+        place when the map has reserve()d spare rows, new_mapping_call is set and the spare and deleted rows hold the new Gaussians;
+        into re-allocated buffers otherwise.  new_mapping_call=True also starts the next mapping call (begin_mapping_call: fresh Adam,
+        fresh init_stat, as the reference does after every growth step, mapper.py:533-548).  Returns the counts of each stage."""
+        c = self._grow_candidates(new)
+        Q = c["xyz"].shape[0]
         stats = dict(candidates=int(Q), inside_existing=0, invalid_scale=0, added=0, deleted=0)
-        exist_xyz, exist_radius = self.xyz, self.radius()  # (spare rows sit 10^4 units away: outside every search box)
-        keep = torch.ones((Q,), dtype=torch.bool, device=dev)
-        # The per-object job (set_object_gate): every decision of the step judges a candidate against the Gaussians of its OWN object
-        # only (dqo_mapgrowth.*_per_object), so a shard — which holds whole objects — takes exactly the decisions the unsharded map
-        # takes for its objects: the N-rank map grows like the N = 1 map.  Without a gate: the reference's decisions.
-        per_obj = nobj is not None
+        exist = (self.xyz, self.radius())  # (spare rows sit 10^4 units away: outside every search box)
+        keep = torch.ones((Q,), dtype=torch.bool, device=self.device)
         live_rows = None if self.alive is None else self.alive.bool()
-        attach_job = None
-        if stable_mask is not None and Q > 0:
-            # temp_points_attach only changes opacities and judges every candidate by itself; the filter and update_geometry only read
-            # positions and radii: the attach runs beside BOTH, on ALL candidates (the ones the filter drops are dropped from its
-            # answer afterwards) — on a stream and a host thread of its own (both sides wait on the host for small results in between
-            # their kernels).  Round 4 started it behind the filter: the step's critical path was filter + attach.
-            import threading
-            self.activate()
-            if self._side_stream is None:
-                self._side_stream = torch.cuda.Stream(device=dev)
-            side, box = self._side_stream, {}
-            side.wait_stream(torch.cuda.current_stream())
-
-            def attach_work(tx=nx, to=nop, tobj=nobj):
-                try:
-                    with torch.cuda.device(dev), torch.cuda.stream(side), torch.no_grad():
-                        box["att"] = self._temp_points_attach(tx, to, stable_mask, unstable_opacity_low, temp_obj=tobj)
-                except BaseException as e:  # (re-raised by the caller's thread)
-                    box["err"] = e
-
-            if attach_async:
-                attach_job = threading.Thread(target=attach_work)
-                attach_job.start()
-            else:  # (A/B of the overlap: the same work in line)
-                attach_work()
-                attach_job = threading.Thread(target=lambda: None)
-                attach_job.start()
+        attach = self._start_attach(c, stable_mask, unstable_opacity_low, attach_async) if stable_mask is not None and Q > 0 else None
         if Q > 0:
-            if stable_mask is None and not per_obj:
-                inside = mg.temp_points_filter_mask(nx, exist_xyz, exist_radius)
-            else:  # the reference filters against its unstable cloud
-                un = torch.ones((self.P,), dtype=torch.bool, device=dev) if stable_mask is None else ~stable_mask.to(dev).bool().reshape(-1)
-                if live_rows is not None:
-                    un = un & live_rows  # (spare rows are no Gaussians of the map)
-                un = un.nonzero().reshape(-1)  # (the unstable cloud is small: a few thousand rows of a 2 M map)
-                if per_obj:
-                    inside = mg.temp_points_filter_mask_per_object(nx, nobj, exist_xyz[un], exist_radius[un], self.gaussian_object[un],
-                                                                   cell=self.object_cell)
-                else:
-                    inside = mg.temp_points_filter_mask(nx, exist_xyz[un], exist_radius[un])
+            inside = self._inside_existing(c, exist, stable_mask, live_rows)
             if inside is not None:
                 keep &= ~inside
                 stats["inside_existing"] = int(inside.sum().item())
         idx = keep.nonzero().reshape(-1)
-        nx, nsc, nrot, nop, nsh = nx[idx], nsc[idx], nrot[idx], nop[idx], nsh[idx]
-        nobj = None if nobj is None else nobj[idx]
-        log_scales = None
-        if nx.shape[0] > 0:
-            nrad = (nsc.sum(dim=1) - nsc.min(dim=1).values) / 2
-            if per_obj:
-                gobj_live = self.gaussian_object if live_rows is None else torch.where(live_rows, self.gaussian_object, -1)
-                scales, invalid = mg.update_geometry_scales_per_object(nx, nobj, nrad, exist_xyz, exist_radius, gobj_live, min_radius, max_radius,
-                                                                       cell=self.object_cell)
-            else:
-                scales, invalid = mg.update_geometry_scales(nx, nrad, exist_xyz, exist_radius, min_radius, max_radius)
-        if attach_job is not None:
-            attach_job.join()
-            torch.cuda.current_stream().wait_stream(side)
-            if "err" in box:
-                raise box["err"]
-            # (the attach judged all Q candidates: keep its answer for the ones the filter kept, as positions among them)
-            att_all = torch.zeros((Q,), dtype=torch.bool, device=dev)
-            att_all.index_fill_(0, box["att"], True)  # (x[rows] = scalar stages the scalar through a host tensor: a blocking copy)
-            att = att_all[idx].nonzero().reshape(-1)
-            stats["attached"] = int(att.numel())
-            nop = nop.clone()
-            nop.index_fill_(0, att, unstable_opacity_low)
-        if nx.shape[0] > 0:
-            stats["invalid_scale"] = int(invalid.sum().item())
-            ok = (~invalid).nonzero().reshape(-1)
-            if ok.numel() > 0:  # gaussian_pointcloud.py:558-568
-                fac = scale_factor * scales[:, None].repeat(1, 3) * mg.const_tensor(xyz_factor, dev)
-                log_scales = torch.log(fac)[ok]
-            nx, nrot, nop, nsh = nx[ok], nrot[ok], nop[ok], nsh[ok]
-            nobj = None if nobj is None else nobj[ok]
-        if log_scales is None:
-            nx, nrot, nop, nsh = nx[:0], nrot[:0], nop[:0], nsh[:0]
-            nobj = None if nobj is None else nobj[:0]
-            log_scales = torch.empty((0, 3), dtype=torch.float32, device=dev)
-        stats["added"] = n_add = int(nx.shape[0])
-        opc = nop.clamp(1e-4, 1 - 1e-4)
-        spare = 0 if self.alive is None else self._n_spare
+        c = {k: None if v is None else v[idx] for k, v in c.items()}
+        scales = invalid = None
+        if idx.numel() > 0:
+            scales, invalid = self._init_scales(c, exist, live_rows, min_radius, max_radius)
+        if attach is not None:  # (the join sits between the scale search and the reading of its result: the attach overlaps both searches)
+            stats["attached"] = self._lower_attached(c, idx, attach.result(), Q, unstable_opacity_low)
+        rows = self._new_rows(c, scales, invalid, scale_factor, xyz_factor, stats)
+        stats["added"] = n_add = int(rows["xyz"].shape[0])
         if self.alive is not None:
             # (the deleted rows as indices, found once: four boolean-mask writes were four passes over the map + four host round trips)
             if delete_mask is None:
-                del_rows = torch.empty((0,), dtype=torch.long, device=dev)
+                del_rows = torch.empty((0,), dtype=torch.long, device=self.device)
             else:
-                del_rows = (delete_mask.to(dev).bool().reshape(-1) & live_rows).nonzero().reshape(-1)
-            stats["deleted"] = n_del = int(del_rows.numel())
-            if new_mapping_call and n_add <= spare + n_del:
-                # ---- in place: deleted Gaussians become spare rows, the new ones take spare rows ----
-                if n_del:
-                    self.alive.index_fill_(0, del_rows, 0)
-                    self.xyz[del_rows] = self._park_position()
-                    self.opacity_raw.index_fill_(0, del_rows, -10.0), self.scaling_raw.index_fill_(0, del_rows, -10.0)
-                    self.row_flags.index_fill_(0, del_rows, N.ROW_HIDDEN | N.ROW_FROZEN)  # a spare row again
-                    self.confidence.index_fill_(0, del_rows, 0.0)
-                self._n_spare += n_del - n_add
-                if n_add:
-                    rows = (self.alive == 0).nonzero().reshape(-1)[:n_add]
-                    self.xyz[rows], self.shs[rows], self.rotation_raw[rows] = nx, nsh, nrot
-                    self.opacity_raw[rows], self.scaling_raw[rows] = torch.log(opc / (1 - opc)), log_scales
-                    if self.gaussian_object is not None:
-                        self.gaussian_object[rows] = nobj
-                    self.alive.index_fill_(0, rows, 1)
-                    # what growth adds is rendered and trained by the next call (the unstable cloud, mapper.py:1438-1466), confidence 0
-                    self.row_flags.index_fill_(0, rows, 0)
-                    self.confidence.index_fill_(0, rows, 0.0)
-                    stats["rows"] = rows
-                    if stable_mask is not None:
-                        # what growth adds belongs to the UNSTABLE cloud (mapper.py:1438-1466) — also when it lands in a row a deleted
-                        # stable Gaussian just freed (spare rows are handed out lowest index first): the caller's mask is updated in
-                        # place, so the next step's filter / stable-only render see the row as unstable
-                        stable_mask.index_fill_(0, rows, False)
-                # (a captured iteration starts from the activations its previous Adam launch left: bring them up to date for the new rows)
-                self._act_valid = False
-                self.activate()
-                self.begin_mapping_call(reset_optimizer=True)  # in place too: fresh moments, fresh init_stat, the new attach set
-                stats["in_place"] = True
-                return stats
+                del_rows = (delete_mask.to(self.device).bool().reshape(-1) & live_rows).nonzero().reshape(-1)
+            stats["deleted"] = int(del_rows.numel())
+            if new_mapping_call and n_add <= self._n_spare + stats["deleted"]:
+                return self._store_in_place(rows, del_rows, stable_mask, stats)
             # spare rows exhausted (or the mapping call goes on): compact — spare rows go with the deleted ones — and reserve again
             delete_mask = ~live_rows
             delete_mask.index_fill_(0, del_rows, True)
-            self.alive = None
-            self._n_spare = 0
+            self.alive, self._n_spare = None, 0
             stats["in_place"] = False
+        return self._store_reallocating(rows, delete_mask, new_mapping_call, stats)
+
+    def _grow_candidates(self, new):
+        """grow()'s `new` as GPU tensors; obj: the object ids the gate needs (`_obj_id`, gaussian_pointcloud.py:497; None without a gate)."""
+        dev = self.device
+        t = lambda a: a.to(dev).float().contiguous() if torch.is_tensor(a) else torch.tensor(np.ascontiguousarray(a, np.float32), device=dev)
+        c = dict(xyz=t(new["xyz"]), scales=t(new["scales"]), rotations=t(new["rotations"]), opacity=t(new["opacity"]).reshape(-1, 1),
+                 shs=t(new["shs"]), obj=None)
+        if self.gaussian_object is not None:
+            if new.get("obj_id") is None:
+                raise RuntimeError("FusedMapper.grow: with an object gate the new points need 'obj_id'")
+            c["obj"] = torch.as_tensor(new["obj_id"]).to(dev, torch.int32).reshape(-1)
+        return c
+
+    def _start_attach(self, c, stable_mask, unstable_opacity_low, attach_async):
+        """temp_points_attach only changes opacities and judges every candidate by itself; the filter and update_geometry only read
+        positions and radii: the attach runs beside BOTH, on ALL candidates (the ones the filter drops are dropped from its answer
+        afterwards) — on a stream and a host thread of its own (both sides wait on the host for small results in between their
+        kernels).  Started behind the filter, the step's critical path was filter + attach."""
+        dev = self.device
+        self.activate()
+        if self._side_stream is None:
+            self._side_stream = torch.cuda.Stream(device=dev)
+        side = self._side_stream
+        side.wait_stream(torch.cuda.current_stream())
+
+        def work(tx=c["xyz"], to=c["opacity"], tobj=c["obj"]):
+            with torch.cuda.device(dev), torch.cuda.stream(side), torch.no_grad():
+                return self._temp_points_attach(tx, to, stable_mask, unstable_opacity_low, temp_obj=tobj)
+
+        return _SideJob(work, side, threaded=attach_async).start()
+
+    def _inside_existing(self, c, exist, stable_mask, live_rows):
+        """Step 1 / 1': bool [Q], the candidates inside an existing Gaussian — of the unstable cloud when the clouds are told apart, of
+        their own object with an object gate."""
+        import dqo_mapgrowth as mg
+        exist_xyz, exist_radius = exist
+        if stable_mask is None and c["obj"] is None:
+            return mg.temp_points_filter_mask(c["xyz"], exist_xyz, exist_radius)
+        if stable_mask is None:
+            un = torch.ones((self.P,), dtype=torch.bool, device=self.device)
+        else:  # the reference filters against its unstable cloud
+            un = ~stable_mask.to(self.device).bool().reshape(-1)
+        if live_rows is not None:
+            un = un & live_rows  # (spare rows are no Gaussians of the map)
+        un = un.nonzero().reshape(-1)  # (the unstable cloud is small: a few thousand rows of a 2 M map)
+        if c["obj"] is not None:
+            return mg.temp_points_filter_mask_per_object(c["xyz"], c["obj"], exist_xyz[un], exist_radius[un], self.gaussian_object[un],
+                                                         cell=self.object_cell)
+        return mg.temp_points_filter_mask(c["xyz"], exist_xyz[un], exist_radius[un])
+
+    def _init_scales(self, c, exist, live_rows, min_radius, max_radius):
+        """Step 2: (scales [n], invalid [n] bool) of the filter's survivors, both still on the device."""
+        import dqo_mapgrowth as mg
+        nsc = c["scales"]
+        nrad = (nsc.sum(dim=1) - nsc.min(dim=1).values) / 2
+        if c["obj"] is None:
+            return mg.update_geometry_scales(c["xyz"], nrad, exist[0], exist[1], min_radius, max_radius)
+        gobj_live = self.gaussian_object if live_rows is None else torch.where(live_rows, self.gaussian_object, -1)
+        return mg.update_geometry_scales_per_object(c["xyz"], c["obj"], nrad, exist[0], exist[1], gobj_live, min_radius, max_radius,
+                                                    cell=self.object_cell)
+
+    def _lower_attached(self, c, idx, attached, Q, unstable_opacity_low):
+        """Step 1b's answer (indices among all Q candidates) on the filter's survivors `idx`: their opacity is lowered; returns their number."""
+        att_all = torch.zeros((Q,), dtype=torch.bool, device=self.device)
+        att_all.index_fill_(0, attached, True)
+        att = att_all[idx].nonzero().reshape(-1)
+        c["opacity"] = c["opacity"].clone()
+        c["opacity"].index_fill_(0, att, unstable_opacity_low)
+        return int(att.numel())
+
+    def _new_rows(self, c, scales, invalid, scale_factor, xyz_factor, stats):
+        """The survivors with a valid scale as rows of the map: per-Gaussian buffer name -> values (gaussian_pointcloud.py:558-568 for
+        the scales), plus `activated_opacity`, from which a mapping call that goes on takes their attach membership."""
+        import dqo_mapgrowth as mg
+        dev = self.device
+        ok = torch.empty((0,), dtype=torch.long, device=dev)
+        log_scales = torch.empty((0, 3), dtype=torch.float32, device=dev)
+        if invalid is not None:
+            stats["invalid_scale"] = int(invalid.sum().item())
+            ok = (~invalid).nonzero().reshape(-1)
+            if ok.numel() > 0:
+                fac = scale_factor * scales[:, None].repeat(1, 3) * mg.const_tensor(xyz_factor, dev)
+                log_scales = torch.log(fac)[ok]
+        opacity = c["opacity"][ok]
+        opc = opacity.clamp(1e-4, 1 - 1e-4)
+        return dict(xyz=c["xyz"][ok], shs=c["shs"][ok], opacity_raw=torch.log(opc / (1 - opc)), scaling_raw=log_scales,
+                    rotation_raw=c["rotations"][ok], gaussian_object=None if c["obj"] is None else c["obj"][ok], activated_opacity=opacity)
+
+    def _store_in_place(self, new, del_rows, stable_mask, stats):
+        """Deleted Gaussians become spare rows, the new ones take spare rows, lowest index first (row order then differs from the
+        reference's cat; nothing depends on it), and the next mapping call starts — all rewritten in place: no buffer moves, P stays,
+        and a captured graph stays valid.  stable_mask is cleared IN PLACE on the rows the new Gaussians take."""
+        n_del, n_add = int(del_rows.numel()), int(new["xyz"].shape[0])
+        if n_del:
+            self._free_rows(del_rows)
+        self._n_spare += n_del - n_add
+        if n_add:
+            rows = (self.alive == 0).nonzero().reshape(-1)[:n_add]
+            self._fill_rows(rows, new)
+            stats["rows"] = rows
+            if stable_mask is not None:
+                # what growth adds belongs to the UNSTABLE cloud (mapper.py:1438-1466) — also when it lands in a row a deleted stable
+                # Gaussian just freed: the caller's mask is updated in place, so the next step's filter / stable-only render see the
+                # row as unstable
+                stable_mask.index_fill_(0, rows, False)
+        # (a captured iteration starts from the activations its previous Adam launch left: bring them up to date for the new rows)
+        self._act_valid = False
+        self.activate()
+        self.begin_mapping_call(reset_optimizer=True)  # in place too: fresh moments, fresh init_stat, the new attach set
+        stats["in_place"] = True
+        return stats
+
+    def _store_reallocating(self, new, delete_mask, new_mapping_call, stats):
+        """Every per-Gaussian buffer is re-allocated as cat(kept old rows, new rows) — the reference's row order — and P changes: every
+        captured graph is dropped (capture() again).  The mapping call goes on with its moments, init_stat and attach set carried for the
+        kept rows (the new ones start at their own values: they have not moved), or — new_mapping_call — the next one starts.  A map
+        that had spare rows and ran out of them (stats["in_place"] is False) gets the same number again."""
         keep_old = None
         if delete_mask is not None:
-            keep_old = (~delete_mask.to(dev).bool().reshape(-1)).nonzero().reshape(-1)
-            if "deleted" not in stats or stats.get("in_place") is None:
+            keep_old = (~delete_mask.to(self.device).bool().reshape(-1)).nonzero().reshape(-1)
+            if "in_place" not in stats:  # (with spare rows "deleted" counts Gaussians, and the spare rows leave with them)
                 stats["deleted"] = int(self.P - keep_old.numel())
-        sel = (lambda a: a) if keep_old is None else (lambda a: a[keep_old])
         stats["kept_rows"] = keep_old  # (None = all of them, in place) the old rows that now lead the map, for per-row data of the caller's
-        self.xyz = torch.cat([sel(self.xyz), nx]).contiguous()
-        self.shs = torch.cat([sel(self.shs), nsh]).contiguous()
-        self.opacity_raw = torch.cat([sel(self.opacity_raw), torch.log(opc / (1 - opc))]).contiguous()
-        self.scaling_raw = torch.cat([sel(self.scaling_raw), log_scales]).contiguous()
-        self.rotation_raw = torch.cat([sel(self.rotation_raw), nrot]).contiguous()
-        if self.gaussian_object is not None:
-            self.gaussian_object = torch.cat([sel(self.gaussian_object), nobj]).contiguous()
-        self.row_flags = torch.cat([sel(self.row_flags), torch.zeros((nx.shape[0],), dtype=torch.uint8, device=dev)]).contiguous()
-        self.confidence = torch.cat([sel(self.confidence), torch.zeros((nx.shape[0],), dtype=torch.float32, device=dev)]).contiguous()
-        self.init_shs = self.init_confidence = None
-        params = self._params()
-        n_new = nx.shape[0]
+        if not new_mapping_call:
+            new["attach_mask"] = (new["activated_opacity"].reshape(-1) < 0.9).to(torch.uint8)
+        self._compact_and_append(keep_old, new, carry_call=not new_mapping_call)
+        self._row_count_changed()
         if new_mapping_call:
-            self.state = {k: (torch.zeros_like(pv), torch.zeros_like(pv)) for k, pv in params.items()}
-            if self.moment_live is not None:
-                self.moment_live = torch.zeros((self.xyz.shape[0],), dtype=torch.uint8, device=dev)
-        else:
-            self.state = {k: (torch.cat([sel(m), torch.zeros_like(params[k][m.shape[0] if keep_old is None else keep_old.numel():])]),
-                              torch.cat([sel(v), torch.zeros_like(params[k][v.shape[0] if keep_old is None else keep_old.numel():])]))
-                          for k, (m, v) in self.state.items()}
-            if self.moment_live is not None:
-                self.moment_live = torch.cat([sel(self.moment_live), torch.zeros((n_new,), dtype=torch.uint8, device=dev)])
-        self.P = P = self.xyz.shape[0]
-        f = dict(dtype=torch.float32, device=dev)
-        self.opacity, self.scales, self.rotations = torch.empty((P, 1), **f), torch.empty((P, 3), **f), torch.empty((P, 4), **f)
-        self._act_valid = False
-        self._g, self._frames, self._mixed = None, [], {}
-        refill = stats.get("in_place") is False  # the map had spare rows and ran out of them: the same number again
-        if new_mapping_call:
-            self.init_xyz = None  # (sizes changed: begin_mapping_call takes fresh snapshots)
             self.begin_mapping_call(reset_optimizer=True)
-            if refill:
-                self.reserve(self._spare_rows)
-            return stats
-        # init_stat / attach set: kept for the old Gaussians, the new ones start at their own values (they have not moved);
-        # a new mapping call re-snapshots everything (begin_mapping_call)
-        self.init_xyz = torch.cat([sel(self.init_xyz), nx])
-        self.init_scaling = torch.cat([sel(self.init_scaling), log_scales])
-        self.init_rotation = torch.cat([sel(self.init_rotation), nrot])
-        self.attach_mask = torch.cat([sel(self.attach_mask), (nop.reshape(-1) < 0.9).to(torch.uint8)]).contiguous()
-        self._count_attach_set()
-        self.attach_partial = torch.zeros((4 * ((P + 255) // 256),), **f)
-        self._attach_n = 0
-        if refill:
+        else:
+            self._count_attach_set()
+        if stats.get("in_place") is False:
             self.reserve(self._spare_rows)
         return stats
 
@@ -674,7 +754,6 @@ class FusedMapper:
         its own object; the zero fill of never-rendered tiles counts as no hit (the reference's alias of such a pixel to "Gaussian 0"
         would name a different Gaussian on every shard layout)."""
         import dqo_mapgrowth as mg
-        from . import mapping
         st, dev = self.settings, self.device
         sm = stable_mask.to(dev).bool().reshape(-1)
         if self.alive is not None:
@@ -700,7 +779,6 @@ class FusedMapper:
             # the binning, a quadrant without a candidate ends at once; the owned pixels blend exactly what the full-frame gated
             # render blends for them (pixels are independent).  Two launches around the render (csrc/map_attach.hip) instead of the
             # reference's chain of boolean-index ops: the growth step is bound by the host's op issue rate.
-            import diff_gaussian_rasterization_depth as dgr
             lin, sparse, tile_sets = mg.attach_pixels(temp_xyz, st.viewmatrix, W / (2.0 * st.tanfovx), H / (2.0 * st.tanfovy), st.cx, st.cy,
                                                       W, H, self.pixel_object)
             dgr.gate_ids_checked(sparse)  # (values of pixel_object, which has been checked, or -1)
@@ -819,7 +897,7 @@ class FusedMapper:
             # calls since then advanced the host count alone (they never touch the device count) and stay counted
             self._settle_replays()
             if frame is None:
-                self._g, self._frames, self._mixed = None, [], {}
+                self._drop_graphs()
             self.activate()
             reuse_probe, longest = self._size_graph(g, capacity_margin, reuse_probe)
             self._g = g
@@ -988,21 +1066,16 @@ class FusedMapper:
                              lr_table=N.ptr(self.lr_table) if step_dev is not None else None, **self._attach_fields())
 
     # ------------------------------------------------------------------ the frame set of a mapping call -----------------
+    def _trained_state(self):
+        return [a for _, a in self._rows("param", "moment")] + [self.confidence]
+
     def _snapshot_state(self):
-        return dict(params={k: v.clone() for k, v in self._params().items()},
-                    state={k: (m.clone(), v.clone()) for k, (m, v) in self.state.items()},
-                    live=None if self.moment_live is None else self.moment_live.clone(), step=self.step_count,
-                    conf=self.confidence.clone())
+        return dict(rows=[a.clone() for a in self._trained_state()], step=self.step_count)
 
     def _restore_state(self, snap):
         self._settle_replays()
-        for k, v in self._params().items():
-            v.copy_(snap["params"][k])
-        for k, (m, v) in self.state.items():
-            m.copy_(snap["state"][k][0]), v.copy_(snap["state"][k][1])
-        if self.moment_live is not None:
-            self.moment_live.copy_(snap["live"])
-        self.confidence.copy_(snap["conf"])
+        for a, old in zip(self._trained_state(), snap["rows"]):
+            a.copy_(old)
         self.step_count = snap["step"]
         self._step_dev.fill_(self.step_count + 1)
         self._expected_step, self._unsettled = self.step_count + 1, False
@@ -1020,7 +1093,7 @@ class FusedMapper:
         count are put back): the mapping call starts from the state it was given."""
         snap = self._snapshot_state()
         self._settle_replays()
-        self._g, self._frames, self._mixed = None, [], {}
+        self._drop_graphs()
         self._window_kw, self._window_frames = dict(kw), list(frames)
         for k, fr in enumerate(frames):
             if k:
