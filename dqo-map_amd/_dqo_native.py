@@ -78,7 +78,7 @@ class DqoAdamStep(ctypes.Structure):
                                      "v_shs", "v_opacity", "v_scaling", "v_rotation", "act_opacity", "act_scales", "act_rotations", "radii", "step_dev", "moment_live",
                                      "attach_mask", "init_xyz", "init_scaling_raw", "init_rotation_raw")] +
                 [("attach_count", c_i32), ("attach_partial", c_vp), ("frame_header", c_vp), ("block_ticket", c_vp), ("bias_table", c_vp), ("attach_gains", c_vp),
-                 ("row_flags", c_vp), ("confidence", c_vp), ("lr_table", c_vp)])
+                 ("row_flags", c_vp), ("confidence", c_vp), ("lr_table", c_vp), ("record_ctx", c_vp), ("record_W", c_i32), ("record_H", c_i32)])
 
 ROW_FROZEN, ROW_HIDDEN = 1, 2  # DQO_ROW_FROZEN / DQO_ROW_HIDDEN (include/dqo_raster.h)
 

@@ -39,6 +39,11 @@ struct AdamArgs {
     const uint8_t* row_flags;                                                     // optional: DqoAdamStep.row_flags (DQO_ROW_FROZEN rows are skipped)
     float* confidence;                                                            // optional: DqoAdamStep.confidence
     const float* lr_table;                                                        // optional (with step_dev): DqoAdamStep.lr_table
+    // optional (DqoAdamStep.record_ctx; adam_kernel's exact sparse mode): the backward's record tables of the frame — instance count and
+    // first slot per Gaussian, validity word per slot — from which adam_has_record derives the fused tail's "has a gradient"
+    const uint32_t *rec_count, *rec_base, *rec_valid;
+    int64_t rec_capacity;
+    uint8_t* moment_live;                                                         // optional: DqoAdamStep.moment_live (NULL = dense)
 };
 
 // a float beta as the double it was most likely written as: rounded to seven decimals (0.999f = 0.99900001287... -> 0.999)
@@ -81,6 +86,19 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, con
     v = v * a.beta2 + a.omb2 * g * g;
     const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
     p = p - step_size * (m / denom);
+}
+
+// Did the backward mark ANY partial gradient record of the Gaussian valid?  The rule the fused tail (map_fused_tail.hip) lists a row by,
+// from the same facts: the instance slots [base, base + cnt) of the frame and their validity words.  Without one every record sum is an
+// exact zero and so is the gradient row.  (Deliberately not a test of the row for zeros: sums that cancel to zero still have records.)
+// A serial per-thread walk over the Gaussian's slots with uncoalesced word loads: fine for adam_kernel, the three-kernel A/B form that
+// no timed path runs; the fused tail gets the same words for free from its record gather.
+__device__ __forceinline__ bool adam_has_record(const AdamArgs& a, const int idx) {
+    const uint32_t base = a.rec_base[idx];
+    const uint32_t end = (uint32_t)min((int64_t)base + (int64_t)a.rec_count[idx], a.rec_capacity);
+    uint32_t any = 0u;
+    for (uint32_t s = base; s < end; s++) any |= a.rec_valid[s];
+    return any != 0u;
 }
 
 // Gradient source of adam_kernel: the rows dqo_rast_backward wrote to HBM (a row without a gradient may be unwritten memory: it is read
@@ -206,6 +224,8 @@ __device__ __forceinline__ void adam_row_update(const AdamArgs& a, const uint32_
     }
     reinterpret_cast<float4*>(a.m_rotation)[i] = mq;
     reinterpret_cast<float4*>(a.v_rotation)[i] = vq;
+    // exact sparse mode: the row's moments are (possibly) non-zero from here on — the byte is set where, and only where, a row is updated
+    if (a.moment_live != nullptr) a.moment_live[i] = 1;  // (kernel-uniform branch; only the row's own thread ever looks at this byte)
     // mapper.py:908-910: `_confidence[(f_dc.grad.abs() != 0).any(-1)] += 1` for the rows this launch trains
     if (a.confidence != nullptr && x.dc_nz) a.confidence[i] = x.conf + 1.0f;
 }

@@ -307,23 +307,24 @@ __global__ void adam_advance_kernel(int32_t* step_dev, const DqoRastHeader* fram
 }
 
 // One block per 256 consecutive Gaussians.  The block first lists the Gaussians it has to touch (LDS): all of them in dense mode;
-// in the exact sparse mode (DqoAdamStep.moment_live) those with a gradient row (radii > 0) or non-zero moments — the others are
-// fixed points of the update and their rows are neither read nor written.  It then runs one pass per parameter group over the
+// in the exact sparse mode (DqoAdamStep.moment_live) those with a gradient (radii > 0 and, given DqoAdamStep.record_ctx, at least one
+// valid partial record: the fused tail's rule), those with non-zero moments and the in-view members of the attach set — the others
+// are fixed points of the update and their rows are neither read nor written.  It then runs one pass per parameter group over the
 // list (adam_passes).
 template <bool SPARSE, bool ATTACH>
-__device__ __forceinline__ void adam_block(AdamArgs a, uint8_t* __restrict__ moment_live);
+__device__ __forceinline__ void adam_block(AdamArgs a);
 
 template <bool SPARSE, bool ATTACH>
-__global__ __launch_bounds__(ADAM_THREADS) void adam_kernel(const AdamArgs a, uint8_t* __restrict__ moment_live) {
+__global__ __launch_bounds__(ADAM_THREADS) void adam_kernel(const AdamArgs a) {
     // A frame flagged invalid by the forward (instance capacity / tile bucket exceeded: lists emptied, every gradient zero) must
     // not train: nothing is read or written, the caller re-captures and continues from the state it had.
     if (a.frame_header != nullptr && a.frame_header->overflow != 0u) return;
-    adam_block<SPARSE, ATTACH>(a, moment_live);
+    adam_block<SPARSE, ATTACH>(a);
     adam_take_ticket(a);
 }
 
 template <bool SPARSE, bool ATTACH>
-__device__ __forceinline__ void adam_block(AdamArgs a, uint8_t* __restrict__ moment_live) {
+__device__ __forceinline__ void adam_block(AdamArgs a) {
     __shared__ uint32_t s_rows[ADAM_THREADS];  // Gaussian index | has-gradient << 31 | attach-loss member << 30
     __shared__ float s_att[ADAM_THREADS / 64];
     __shared__ int s_wave_n[ADAM_THREADS / 64];
@@ -333,10 +334,12 @@ __device__ __forceinline__ void adam_block(AdamArgs a, uint8_t* __restrict__ mom
     const int idx = blockIdx.x * ADAM_THREADS + tid;
     bool hg = false, act = false, att = false;
     if (idx < a.P && !(a.row_flags != nullptr && (a.row_flags[idx] & DQO_ROW_FROZEN) != 0u)) {  // (a frozen row: DqoAdamStep.row_flags)
-        hg = a.radii == nullptr || a.radii[idx] > 0;
-        act = !SPARSE || hg || moment_live[idx] != 0;
-        if (SPARSE && hg) moment_live[idx] = 1;  // only this thread ever looks at this byte
+        const bool visible = a.radii == nullptr || a.radii[idx] > 0;
         if (ATTACH) att = a.attach_mask[idx] != 0;
+        hg = visible;
+        if (SPARSE && visible && a.rec_valid != nullptr) hg = adam_has_record(a, idx);
+        const bool live_m = SPARSE && a.moment_live[idx] != 0;
+        act = !SPARSE || hg || live_m || (visible && att);  // (moment_live of a listed row is set where the row is updated: adam_row_update)
     }
     const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
     if (lane == 0) s_wave_n[wave] = (int)__popcll(am);
@@ -433,6 +436,17 @@ int dqo_adam_args(const DqoAdamStep* st, int blocks, AdamArgs* out, bool* attach
     const bool attach = st->attach_mask != nullptr && (st->attach_count > 0 || st->attach_gains != nullptr);
     a.attach_gains = attach ? st->attach_gains : nullptr;
     a.row_flags = st->row_flags, a.confidence = st->confidence, a.lr_table = st->lr_table;
+    a.rec_count = a.rec_base = a.rec_valid = nullptr, a.rec_capacity = 0;
+    a.moment_live = st->moment_live;
+    if (st->record_ctx != nullptr && st->moment_live != nullptr) {
+        const DqoRastCtx* c = st->record_ctx;
+        DQO_CHECK_ARG(c->geom != nullptr && c->binning != nullptr && st->record_W > 0 && st->record_H > 0, "record_ctx needs its buffers and record_W / record_H");
+        const DqoGeomLayout g = dqo_geom_layout(c->geom, st->P);
+        const DqoBinLayout bin = dqo_bin_layout(c->binning, c->inst_capacity,
+                                                dqo_list_cap(c->inst_capacity, st->record_W, st->record_H, c->tile_bucket_capacity),
+                                                c->tile_bucket_capacity);
+        a.rec_count = g.tiles_touched, a.rec_base = g.slot_base, a.rec_valid = bin.rec_valid, a.rec_capacity = (int64_t)c->inst_capacity;
+    }
     DQO_CHECK_ARG(st->lr_table == nullptr || st->step_dev != nullptr, "lr_table is read on the device: it needs step_dev");
     DQO_CHECK_ARG(!attach || (st->init_xyz && st->init_scaling_raw && st->init_rotation_raw), "attach_mask needs the three init_* tensors");
     DQO_CHECK_ARG(st->P < (1 << 30), "P must stay below 2^30");
@@ -457,11 +471,11 @@ int dqo_launch_map_adam(const DqoAdamStep* st, hipStream_t s) {
     const bool advance_inside = a.step_advance != nullptr;
     if (blocks > 0) {  // (an empty map still advances the step count)
         if (st->moment_live != nullptr) {
-            if (attach) DQO_LAUNCH("adam_kernel", (adam_kernel<true, true>), dim3(blocks), dim3(ADAM_THREADS), s, a, st->moment_live);
-            else DQO_LAUNCH("adam_kernel", (adam_kernel<true, false>), dim3(blocks), dim3(ADAM_THREADS), s, a, st->moment_live);
+            if (attach) DQO_LAUNCH("adam_kernel", (adam_kernel<true, true>), dim3(blocks), dim3(ADAM_THREADS), s, a);
+            else DQO_LAUNCH("adam_kernel", (adam_kernel<true, false>), dim3(blocks), dim3(ADAM_THREADS), s, a);
         } else {
-            if (attach) DQO_LAUNCH("adam_kernel", (adam_kernel<false, true>), dim3(blocks), dim3(ADAM_THREADS), s, a, st->moment_live);
-            else DQO_LAUNCH("adam_kernel", (adam_kernel<false, false>), dim3(blocks), dim3(ADAM_THREADS), s, a, st->moment_live);
+            if (attach) DQO_LAUNCH("adam_kernel", (adam_kernel<false, true>), dim3(blocks), dim3(ADAM_THREADS), s, a);
+            else DQO_LAUNCH("adam_kernel", (adam_kernel<false, false>), dim3(blocks), dim3(ADAM_THREADS), s, a);
         }
     }
     if (st->step_dev != nullptr && !advance_inside)

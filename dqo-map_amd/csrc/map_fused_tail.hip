@@ -7,8 +7,14 @@
 // As separate kernels the 59-float gradient row of every visible Gaussian makes a round trip through HBM between two kernels that
 // visit the same Gaussians (284 B written + 236 B re-read).  Here a workgroup owns 128 Gaussians (the thread -> Gaussian assignment
 // of bin_count_kernel, so their instance slots are one contiguous range):
-//   A  lists the rows Adam has to touch (LDS: visible Gaussians and, in the exact sparse mode, those with non-zero moments),
-//   B  sums its Gaussians' partial gradient records in a fixed (slot, quadrant) order,
+//   A  loads what decides a Gaussian's part (tile rect, instance slots, moment_live, attach set, row flags),
+//   B  sums its Gaussians' partial gradient records in a fixed (slot, quadrant) order and notes whether ANY of them was marked valid,
+//      then lists the rows Adam has to touch (LDS).  Dense mode: every trained row.  Exact sparse mode: the rows WITH A GRADIENT — in
+//      view and at least one valid record —, those with non-zero moments and the in-view members of the attach set.  An in-view
+//      Gaussian without a valid record (no list entry left by the culling / tile mask / object gate; every entry behind an early
+//      exit, in another object's pixels or below 1/255; no incoming gradient on its quadrants) has record sums of exact zeros, hence
+//      a zero gradient row: with zero moments it is a fixed point of Adam like a Gaussian out of view, and neither its chain runs
+//      nor its 1.4 KB of parameter / moment rows move (cfg 3: 27 % of the in-view rows, tests/diag_zero_grad_share.py),
 //   C  runs the per-Gaussian chain (dqo_gauss_chain.h: the same statements as gaussian_rows_kernel) and leaves each gradient row
 //      in LDS — factored: dL/dsh[k][c] = w[k] * dRGB[c], so a row is 30 floats instead of 59 (15.5 KB per workgroup),
 //   D  runs Adam's passes over the list with the gradient read from LDS (dqo_adam.h: the same statements as adam_kernel).
@@ -75,7 +81,7 @@ __global__ __launch_bounds__(TAIL_THREADS, DQO_TAIL_WAVES) void gaussian_tail_ke
                                                                         const float* scales, const float* rotations, const float* shs,
                                                                         const float4* __restrict__ partial,
                                                                         const uint32_t* __restrict__ valid, int64_t capacity, AdamArgs a,
-                                                                        uint8_t* __restrict__ moment_live, const uint32_t frame_words,
+                                                                        const uint32_t frame_words,
                                                                         uint32_t* __restrict__ hist, const uint32_t hist_words) {
 #pragma clang fp contract(off)
     // This kernel is the last consumer of the frame's counters (its blocks only read header.overflow): each block clears a slice of
@@ -122,7 +128,7 @@ __global__ __launch_bounds__(TAIL_THREADS, DQO_TAIL_WAVES) void gaussian_tail_ke
     const int idx = dqo_spread_index(blockIdx.x * TAIL_THREADS + tid, v.P);  // bin_count_kernel's thread -> Gaussian assignment
     const bool in_range = idx < v.P;
 
-    // ---- A: first round of loads (rect, instance count, slot base, list flags); Adam's row list ----
+    // ---- A: first round of loads (rect, instance count, slot base, list flags) ----
     uint2 rc = make_uint2(0u, 0u);
     uint32_t base = 0, cnt = 0;
     bool live_m = false, att = false, trained = in_range;
@@ -130,7 +136,7 @@ __global__ __launch_bounds__(TAIL_THREADS, DQO_TAIL_WAVES) void gaussian_tail_ke
         rc = g.rect16[idx];
         cnt = g.tiles_touched[idx];
         base = g.slot_base[idx];
-        if (SPARSE) live_m = moment_live[idx] != 0;
+        if (SPARSE) live_m = a.moment_live[idx] != 0;
         if (ATTACH) att = a.attach_mask[idx] != 0;
         // DqoAdamStep.row_flags: a frozen row is rendered and back-propagated THROUGH (its entries shape the pixels' T), but it is no
         // parameter of this mapping call: no record sum, no chain, no Adam, no confidence (kernel-uniform branch, one byte per row)
@@ -158,27 +164,42 @@ __global__ __launch_bounds__(TAIL_THREADS, DQO_TAIL_WAVES) void gaussian_tail_ke
     if (!trained) cnt = 0u, live_m = false, att = false;
     // radii > 0 (backward.cu:285, 513; DqoAdamStep.radii)  <=>  the forward kept a non-empty tile rect for this Gaussian
     const bool visible = trained && ((rc.x >> 16) > (rc.x & 0xffffu)) && ((rc.y >> 16) > (rc.y & 0xffffu));
-    const bool act = trained && (!SPARSE || visible || live_m);
-    if (SPARSE && visible) moment_live[idx] = 1;  // only this thread ever looks at this byte
-    const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
     // the workgroup's slot range (its Gaussians' slots are one contiguous range, rast_binning.hip): per wave the minimum of the bases and
-    // the maximum of the ends through the crossbar-free butterflies of dqo_common.h, handed over with the row counts in ONE barrier —
-    // 128 LDS atomics on two words and a second barrier until round 6 (2 us of the block's head)
+    // the maximum of the ends through the crossbar-free butterflies of dqo_common.h, handed over in ONE barrier — 128 LDS atomics on two
+    // words and a second barrier until round 6 (2 us of the block's head)
     const uint32_t w_lo = ~dqo_wave_max_u32(cnt ? ~base : 0u, lane), w_hi = dqo_wave_max_u32(cnt ? base + cnt : 0u, lane);
-    if (lane == 0) s_wave_n[wave] = (int)__popcll(am), s_lohi[2 * wave] = w_lo, s_lohi[2 * wave + 1] = w_hi;
-    __syncthreads();  // (a one-wave workgroup's __syncthreads is a wave-level fence, not an s_barrier)
-    int before = 0, n_rows = 0;
+    if (lane == 0) s_lohi[2 * wave] = w_lo, s_lohi[2 * wave + 1] = w_hi;
+    // Adam's row list (s_rows): ballot, row counts per wave through ONE barrier, a row per listed Gaussian.  Dense mode: every trained
+    // row, listed here — the barrier is the one that hands the slot range over, as it always was.  Exact sparse mode: behind phase B.
+    int my_row = 0, n_rows = 0;
+    auto list_rows = [&](const bool act, const uint32_t word) {
+        const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
+        if (lane == 0) s_wave_n[wave] = (int)__popcll(am);
+        __syncthreads();  // (a one-wave workgroup's __syncthreads is a wave-level fence, not an s_barrier)
+        int before = 0;
+#pragma unroll
+        for (int w = 0; w < TAIL_THREADS / 64; w++) {
+            const int c = s_wave_n[w];
+            before += w < wave ? c : 0;
+            n_rows += c;
+        }
+        my_row = before + (int)__popcll(am & ((1ull << lane) - 1ull));  // this Gaussian's list row (if act)
+        // (s_rows is first read in phase D, behind the barrier that closes phase C: no barrier of its own)
+        if (act) s_rows[my_row] = word;
+    };
+    // What the sparse row list needs behind phase B rides in the top bits of `cnt` (an instance count is at most the number of tiles, checked
+    // below 2^29 by the launcher): at 128 registers phase B — sixteen float4 loads in flight beside the chain's inputs — has none to
+    // spare, and one more register sends a loaded chain input to scratch, where the store waits for the load.
+    constexpr uint32_t CNT_ATT = 0x20000000u, CNT_LIVE = 0x40000000u, REC_ANY = 0x80000000u, CNT_MASK = 0x1fffffffu;
+    if (SPARSE) {
+        cnt |= (att ? CNT_ATT : 0u) | (live_m ? CNT_LIVE : 0u);
+        __syncthreads();
+    } else {
+        list_rows(trained, (uint32_t)idx | (visible ? 0x80000000u : 0u) | (att ? 0x40000000u : 0u));
+    }
     uint32_t lo = 0xffffffffu, hi_all = 0u;
 #pragma unroll
-    for (int w = 0; w < TAIL_THREADS / 64; w++) {
-        const int c = s_wave_n[w];
-        before += w < wave ? c : 0;
-        n_rows += c;
-        lo = min(lo, s_lohi[2 * w]), hi_all = max(hi_all, s_lohi[2 * w + 1]);
-    }
-    const int my_row = before + (int)__popcll(am & ((1ull << lane) - 1ull));  // this Gaussian's list row (if act)
-    // (s_rows is first read in phase D, behind the barrier that closes phase C: no barrier of its own)
-    if (act) s_rows[my_row] = (uint32_t)idx | (visible ? 0x80000000u : 0u) | (att ? 0x40000000u : 0u);
+    for (int w = 0; w < TAIL_THREADS / 64; w++) lo = min(lo, s_lohi[2 * w]), hi_all = max(hi_all, s_lohi[2 * w + 1]);
     const uint32_t hi = (uint32_t)min((int64_t)hi_all, capacity);  // (an overflowed forward never gets here; belt and braces)
 
     // ---- second round of loads: everything the chain needs of this lane's Gaussian, issued as a whole before the record gather (in
@@ -193,7 +214,8 @@ __global__ __launch_bounds__(TAIL_THREADS, DQO_TAIL_WAVES) void gaussian_tail_ke
     ci.qt = make_float4(1.f, 0.f, 0.f, 0.f);
     ci.n_np = ci.pc = make_float4(0.f, 0.f, 0.f, 0.f);
     ci.cl = 0;
-    if (visible) {
+    // (exact sparse mode: a Gaussian without instances gets no gradient and is not listed for one — nothing of it is needed)
+    if (visible && (!SPARSE || (cnt & CNT_MASK) != 0u)) {
         ci.cop = g.conic_opacity[idx];
         ci.mx = means3D[3 * idx], ci.my = means3D[3 * idx + 1], ci.mz = means3D[3 * idx + 2];
         ci.sx = scales[3 * idx], ci.sy = scales[3 * idx + 1], ci.sz = scales[3 * idx + 2];
@@ -207,11 +229,15 @@ __global__ __launch_bounds__(TAIL_THREADS, DQO_TAIL_WAVES) void gaussian_tail_ke
         ci.dd[6] = d2.x, ci.dd[7] = d2.y, ci.dd[8] = d2.z;
     }
 
-    // ---- B: fixed-order sum of this lane's Gaussian's partial gradient records (one slot per thread and trip) ----
+    // ---- B: fixed-order sum of this lane's Gaussian's partial gradient records (one slot per thread and trip).  A slot's validity
+    //      word travels through the staging area beside its sums (element 3 of the fourth float4, which no record float uses): OR-ed
+    //      over the Gaussian's slots it says whether the backward wrote ANY record for it. ----
     float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
-    if (lo < hi) {  // (wave-uniform)
+    // (the OR goes to REC_ANY, the top bit of `cnt`)
+    if (lo < hi) {  // (block-uniform)
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
         for (uint32_t c0 = lo; c0 < hi; c0 += TAIL_THREADS) {
+            if (c0 != lo) __syncthreads();  // (the staging area is overwritten by this trip)
             const uint32_t slot = c0 + tid;
             if (slot < hi) {
                 const uint32_t vw = valid[slot];
@@ -239,33 +265,46 @@ __global__ __launch_bounds__(TAIL_THREADS, DQO_TAIL_WAVES) void gaussian_tail_ke
                         }
                     }
                 }
+                m3.w = __uint_as_float(vw);  // (a bit pattern, never an operand)
                 s_rec[tid * 4] = m0, s_rec[tid * 4 + 1] = m1, s_rec[tid * 4 + 2] = m2, s_rec[tid * 4 + 3] = m3;
             }
             __syncthreads();
-            const uint32_t k0 = max(base, c0), k1 = min(base + cnt, min(c0 + (uint32_t)TAIL_THREADS, hi));
+            const uint32_t k0 = max(base, c0), k1 = min(base + (cnt & CNT_MASK), min(c0 + (uint32_t)TAIL_THREADS, hi));
             for (uint32_t k = k0; k < k1; k++) {
                 const float4 r0 = s_rec[(k - c0) * 4], r1 = s_rec[(k - c0) * 4 + 1], r2 = s_rec[(k - c0) * 4 + 2], r3 = s_rec[(k - c0) * 4 + 3];
                 a0.x += r0.x, a0.y += r0.y, a0.z += r0.z, a0.w += r0.w;
                 a1.x += r1.x, a1.y += r1.y, a1.z += r1.z, a1.w += r1.w;
                 a2.x += r2.x, a2.y += r2.y, a2.z += r2.z, a2.w += r2.w;
-                a3.x += r3.x, a3.y += r3.y, a3.z += r3.z, a3.w += r3.w;
+                a3.x += r3.x, a3.y += r3.y;  // (a record has 14 floats: a3.z, a3.w stay zero)
+                cnt |= __float_as_uint(r3.w) != 0u ? REC_ANY : 0u;
             }
-            __syncthreads();  // (the staging area is overwritten — by the next trip or by phase C's rows)
         }
     }
-    if (n_rows == 0) {  // (wave-uniform) nothing to update: no visible Gaussian, no live moment
+    // ---- exact sparse mode: Adam's row list (see the head of the file).  has_grad: the row's gradient is formed by phase C and read by
+    //      phase D.  The list's barrier also frees the staging area for phase C's rows. ----
+    const bool has_grad = visible && (!SPARSE || (cnt & REC_ANY) != 0u);
+    if (SPARSE) {
+        // (a frozen row is neither visible nor live nor an attach member here; moment_live of a listed row is set where the row is
+        // updated, adam_row_update; the Gaussian index is formed again rather than kept across phase B)
+        const bool act = has_grad || (cnt & CNT_LIVE) != 0u || (visible && (cnt & CNT_ATT) != 0u);
+        list_rows(act, (uint32_t)dqo_spread_index(blockIdx.x * TAIL_THREADS + tid, v.P) | (has_grad ? 0x80000000u : 0u) |
+                           ((cnt & CNT_ATT) ? 0x40000000u : 0u));
+    } else if (lo < hi) {
+        __syncthreads();  // (the staging area is overwritten by phase C's rows)
+    }
+    if (n_rows == 0) {  // (block-uniform) nothing to update: no Gaussian with a gradient, no live moment
         if (ATTACH && a.attach_partial != nullptr && tid == 0) a.attach_partial[blockIdx.x] = 0.f;
         adam_take_ticket(a);
         return;
     }
 
     // ---- C: the per-Gaussian chain; the gradient row goes to LDS at the Gaussian's list row ----
-    if (visible) {
+    if (has_grad) {
         ci.a[0] = a0.x, ci.a[1] = a0.y, ci.a[2] = a0.z, ci.a[3] = a0.w;
         ci.a[4] = a1.x, ci.a[5] = a1.y, ci.a[6] = a1.z, ci.a[7] = a1.w;
         ci.a[8] = a2.x, ci.a[9] = a2.y, ci.a[10] = a2.z, ci.a[11] = a2.w;
         ci.a[12] = a3.x, ci.a[13] = a3.y, ci.a[14] = a3.z, ci.a[15] = a3.w;
-        if (cnt == 0u) ci.cop = make_float4(0.f, 0.f, 0.f, 0.f);  // (a Gaussian without instances: no pixel blended it)
+        if ((cnt & CNT_MASK) == 0u) ci.cop = make_float4(0.f, 0.f, 0.f, 0.f);  // (a Gaussian without instances: no pixel blended it)
         DqoChainOut co;
         dqo_gauss_chain(v, view, proj, ci, true, co);
         float* row = s_g + my_row * ROW_STRIDE;
@@ -378,6 +417,7 @@ int dqo_launch_backward_adam(const DqoRastParams* p, const DqoRastInputs* in, co
     DqoBinLayout bin = dqo_bin_layout(ctx->binning, ctx->inst_capacity,
                                       dqo_list_cap(ctx->inst_capacity, p->W, p->H, ctx->tile_bucket_capacity), ctx->tile_bucket_capacity);
     const int T = v.gx * v.gy;
+    DQO_CHECK_ARG(T < (1 << 29), "more than 2^29 tiles");  // (gaussian_tail_kernel keeps three flags above a Gaussian's instance count)
     const int64_t cap = (int64_t)ctx->inst_capacity;
     DqoGradRec* recs = (DqoGradRec*)ws;
     uint8_t* valid = reinterpret_cast<uint8_t*>(bin.rec_valid);  // zeroed by the forward
@@ -386,6 +426,7 @@ int dqo_launch_backward_adam(const DqoRastParams* p, const DqoRastInputs* in, co
     bool attach = false;
     int rc = dqo_adam_args(st, blocks, &a, &attach);
     if (rc) return rc;
+    a.rec_count = a.rec_base = a.rec_valid = nullptr;  // (DqoAdamStep.record_ctx is adam_kernel's: this kernel reads its own ctx)
     a.frame_header = g.header;  // the frame whose gradients this step consumes is this context's
     rc = dqo_launch_blend_backward(v, g, img, bin, T, dL_dcolor, dL_ddepth, recs, valid, cap, dqo_tap_dev(ctx->loss_tap),
                                    dqo_gate_dev(ctx->object_gate), dqo_list_split(ctx), s);
@@ -396,7 +437,7 @@ int dqo_launch_backward_adam(const DqoRastParams* p, const DqoRastInputs* in, co
     const uint32_t hist_words = (uint32_t)((img.tile_flag + T) - img.tile_count);  // tile histogram (padded) + flags, likewise
 #define DQO_TAIL(SP, AT)                                                                                                              \
     DQO_LAUNCH("gaussian_tail_kernel", (gaussian_tail_kernel<SP, AT>), dim3(blocks), dim3(TAIL_THREADS), s, v, g, in->means3D, in->scales, \
-               in->rotations, in->shs, partial, vw, cap, a, st->moment_live, frame_words, img.tile_count, hist_words)
+               in->rotations, in->shs, partial, vw, cap, a, frame_words, img.tile_count, hist_words)
     if (st->moment_live != nullptr) {
         if (attach) DQO_TAIL(true, true);
         else DQO_TAIL(true, false);

@@ -1005,6 +1005,9 @@ class FusedMapper:
         g.cgrads = N.DqoRastGrads(dL_dmeans3D=gr[0], dL_dsh=gr[1], dL_dcolors=None, dL_dopacity=gr[2], dL_dscales=gr[3],
                                   dL_drotations=gr[4], dL_dcov3D=None, dL_dmeans2D=None, skip_culled_rows=1)
         g.adam = self._adam_step_args(gr, radii=g.out[8].data_ptr(), frame_header=g.geom.data_ptr(), step_dev=g.step_dev)
+        # the three-kernel form (fused_tail=False) lists Adam's rows by the backward's record marks, like the fused tail (DqoAdamStep.record_ctx)
+        g.adam.record_ctx = ctypes.addressof(g.cctx)
+        g.adam.record_W, g.adam.record_H = int(st.image_width), int(st.image_height)
 
     def _warm_up_and_record(self, g, reuse_probe):
         """One eager iteration of graph g (warms every kernel up), then the capture of its graphs.  Returns False, recording nothing, if
@@ -1486,6 +1489,9 @@ class FusedMapper:
             ctx.sparse_grad_rows = True  # gradient rows of culled Gaussians stay unwritten; the Adam kernel gets radii instead
             grads = dgr._RasterizeGaussians.backward(ctx, self.dL_dcolor, self.dL_ddepth, None, None, None, None, None, None, None)
             self.step_count += 1
+            # (no DqoAdamStep.record_ctx here: the drop-in op owns this frame's context, so the eager step deliberately keeps the radii
+            # rule — it updates every in-view row and sets its moment_live byte.  Same bits as the captured iteration's rule, which skips
+            # the in-view rows without a gradient record; more rows touched, and those rows stay listed until the next mapping call.)
             st = self._adam_step_args([N.ptr(grads[i]) for i in (0, 1, 3, 4, 5)], radii=N.ptr(out[8]),
                                       frame_header=N.ptr(ctx.saved_tensors[8]), step=self.step_count)
             N.check(lib.dqo_map_adam_step(ctypes.byref(st), stream))

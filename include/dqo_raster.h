@@ -590,7 +590,11 @@ typedef struct DqoAdamStep {
     /* Optional (NULL = dense): one byte per Gaussian, 0 = both moment rows of the Gaussian are identically zero (the state of a
      * freshly built optimiser, which the reference builds per mapping call, mapper.py:548).  Such a Gaussian with no gradient
      * (radii == 0) is a fixed point of Adam — m, v stay 0 and p - step * 0 / (0 + eps) = p bit for bit — so its rows are neither
-     * read nor written; the first gradient sets its byte to 1.  Needs `radii`.  Results are identical to the dense update. */
+     * read nor written; the first update of the row sets its byte to 1.  Needs `radii`.  Results are identical to the dense update.
+     * "No gradient" is radii == 0 and, where the backward's records are at hand (dqo_rast_backward_adam always; dqo_map_adam_step given
+     * record_ctx below), also an in-view Gaussian for which the backward marked no partial record valid: the culling, the tile mask or
+     * the object gate left it no list entry, or every entry sits behind an early exit, in another object's pixels or below 1/255, or
+     * its pixels carry no incoming gradient — its record sums are exact zeros.  In-view members of the attach set are always updated. */
     uint8_t* moment_live;
     /* Optional (NULL = no such term): the attach loss of Mapping.loss_update (SLAM/multiprocess/mapper.py:812-829),
      *   1000 * (mse(_scaling[a], scaling0[a]) + mse(_xyz[a], xyz0[a]) + mse(_rotation[a], rotation0[a])),
@@ -640,6 +644,12 @@ typedef struct DqoAdamStep {
      * launch runs — global_optimization rescales the groups' learning rates per call (mapper.py:1120-1131: xyz 0, the others x 0.1 or
      * x their *_lr_coef); a caller that rewrites the table (and zeroes bias_table) between two mapping calls keeps its captured graph. */
     const float* lr_table;
+    /* Optional, with moment_live (NULL = radii alone decides): the context of the forward / dqo_rast_backward call whose gradient rows
+     * this step consumes, with that call's image size — read on the host when the launch is issued; its buffers must still hold the
+     * frame.  dqo_map_adam_step then lists a row exactly as dqo_rast_backward_adam does (see moment_live): same rows touched, same
+     * moment_live bytes.  Ignored by dqo_rast_backward_adam (it has its own ctx). */
+    const DqoRastCtx* record_ctx;
+    int32_t record_W, record_H;
 } DqoAdamStep;
 int dqo_map_adam_step(const DqoAdamStep*, void* hipStream);
 
