@@ -87,6 +87,15 @@ class DqoAdamTensor(ctypes.Structure):
     _fields_ = [("p", c_vp), ("g", c_vp), ("m", c_vp), ("v", c_vp), ("n", ctypes.c_int64), ("lr", ctypes.c_double)]
 
 
+class DqoLifecycle(ctypes.Structure):
+    """dqo_map_lifecycle_vote / dqo_map_lifecycle_rows (ABI 5 symbols-only addition)."""
+    _fields_ = ([(n, c_i32) for n in ("P", "W", "H", "tick", "unstable_time_window", "delete_thresh", "stable_oversized", "use_votes")] +
+                [(n, c_f) for n in ("stable_confidence_thres", "add_color_thres", "add_depth_thres")] +
+                [(n, c_vp) for n in ("xyz", "opacity_raw", "scaling_raw", "confidence", "alive", "row_flags", "stable", "add_tick",
+                                     "depth_error_counter", "color_error_counter", "park", "vote", "workspace")] +
+                [("workspace_bytes", ctypes.c_size_t), ("stats", c_vp), ("render_header", c_vp)])
+
+
 EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_enable", "dqo_profile_collect", "dqo_map_activate",
            "dqo_map_loss_workspace_bytes", "dqo_map_loss_fwd_bwd", "dqo_map_ssim_workspace_bytes", "dqo_map_ssim_fwd_bwd", "dqo_map_adam_step", "dqo_adam_multi_dev", "dqo_map_attach_workspace_bytes",
            "dqo_map_attach_loss_fwd_bwd", "dqo_adam_multi", "dqo_accumulate_gaussian_error", "dqo_accumulate_gaussian_confidence", "dqo_rast_geom_bytes", "dqo_rast_image_bytes",
@@ -99,7 +108,7 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_rast_forward_prepare_params", "dqo_rast_forward_render_params", "dqo_rast_forward_async_params", "dqo_rast_backward_params",
            "dqo_icp_gauss_newton", "dqo_track_preprocess_workspace_bytes", "dqo_track_preprocess", "dqo_track_pyramid_pixels",
            "dqo_track_pyramid_workspace_bytes", "dqo_track_pyramid", "dqo_track_fill_model_depth", "dqo_track_p2p_workspace_bytes",
-           "dqo_track_p2p_loss")
+           "dqo_track_p2p_loss", "dqo_map_lifecycle_workspace_bytes", "dqo_map_lifecycle_vote", "dqo_map_lifecycle_rows")
 
 _lib = None
 
@@ -191,6 +200,10 @@ def lib():
         L.dqo_transmission_mask.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
         L.dqo_tile_color_error.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
         L.dqo_map_history_merge.argtypes = [c_i32, c_i32, c_f, c_i32] + [c_vp] * 12
+        L.dqo_map_lifecycle_workspace_bytes.restype = ctypes.c_size_t
+        L.dqo_map_lifecycle_workspace_bytes.argtypes = [c_i32]
+        L.dqo_map_lifecycle_vote.argtypes = [P(DqoLifecycle)] + [c_vp] * 7
+        L.dqo_map_lifecycle_rows.argtypes = [P(DqoLifecycle), c_vp]
         L.dqo_profile_enable.argtypes = [ctypes.c_int]
         L.dqo_profile_collect.argtypes = [P(DqoProfileEntry), ctypes.c_int, ctypes.c_int]
         if L.dqo_abi_version() != 5:
@@ -198,8 +211,9 @@ def lib():
         L.dqo_abi_sizeof.restype = ctypes.c_size_t
         L.dqo_abi_sizeof.argtypes = [c_i32]
         for k, st in enumerate((DqoRastParams, DqoRastInputs, DqoRastOutputs, DqoRastCtx, DqoRastGrads, DqoRastHeader, DqoProfileEntry,
-                                DqoAdamStep, DqoLossTap, DqoObjectGate, DqoAdamTensor, DqoRastParamInputs, DqoRastParamGrads)):
-            if L.dqo_abi_sizeof(k) != ctypes.sizeof(st):
+                                DqoAdamStep, DqoLossTap, DqoObjectGate, DqoAdamTensor, DqoRastParamInputs, DqoRastParamGrads, None,
+                                DqoLifecycle)):  # (None: index 13 is unused)
+            if st is not None and L.dqo_abi_sizeof(k) != ctypes.sizeof(st):
                 raise RuntimeError(f"libdqoraster.so: struct {st.__name__} is {L.dqo_abi_sizeof(k)} bytes in the library, "
                                    f"{ctypes.sizeof(st)} in the binding")
         _lib = L

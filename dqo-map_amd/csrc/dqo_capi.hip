@@ -77,6 +77,10 @@ int dqo_launch_growth_scales(int n, const float* xyz, const int32_t* obj, const 
 int dqo_launch_growth_inside(int n, const float* d2, const int32_t* idx, const float* radius, uint8_t* inside, hipStream_t s);
 int dqo_launch_error_maps(int64_t HW, const float* gt_color, const float* gt_depth, const float* render, const float* depth,
                           const int32_t* depth_index, const uint8_t* mask, float* color_err, float* depth_err, hipStream_t s);
+size_t dqo_lifecycle_ws_bytes(int64_t P);
+int dqo_launch_lifecycle_vote(const DqoLifecycle* a, const float* gt_color, const float* gt_depth, const float* render, const float* depth,
+                              const int32_t* depth_index, const int32_t* color_index, hipStream_t s);
+int dqo_launch_lifecycle_rows(const DqoLifecycle* a, hipStream_t s);
 int dqo_launch_attach_pixels(int n, const float* xyz, const float* V, float fx, float fy, float cx, float cy, int W, int H,
                              const int32_t* pixel_object, int32_t* lin, int32_t* sparse, unsigned long long* tile_objects, hipStream_t s);
 int dqo_launch_attach_decide(int n, const float* xyz, const float* opacity, const int32_t* obj, const int32_t* lin, const int32_t* hit_index,
@@ -172,7 +176,8 @@ DQO_API int dqo_abi_version(void) { return DQO_ABI_VERSION; }
 DQO_API size_t dqo_abi_sizeof(int32_t which) {
     static const size_t sz[] = {sizeof(DqoRastParams), sizeof(DqoRastInputs), sizeof(DqoRastOutputs), sizeof(DqoRastCtx), sizeof(DqoRastGrads),
                                 sizeof(DqoRastHeader), sizeof(DqoProfileEntry), sizeof(DqoAdamStep), sizeof(DqoLossTap), sizeof(DqoObjectGate),
-                                sizeof(DqoAdamTensor), sizeof(DqoRastParamInputs), sizeof(DqoRastParamGrads)};
+                                sizeof(DqoAdamTensor), sizeof(DqoRastParamInputs), sizeof(DqoRastParamGrads), 0 /* 13: unused */,
+                                sizeof(DqoLifecycle)};
     return (which >= 0 && which < (int32_t)(sizeof(sz) / sizeof(sz[0]))) ? sz[which] : 0;
 }
 DQO_API const char* dqo_last_error(void) { return g_err; }
@@ -701,6 +706,39 @@ DQO_API int dqo_error_maps(int32_t H, int32_t W, const float* gt_color, const fl
                            const int32_t* depth_index, const uint8_t* mask, float* color_err, float* depth_err, void* stream) {
     DQO_CHECK_ARG(W > 0 && H > 0 && gt_color && gt_depth && render && depth && depth_index && color_err && depth_err, "bad size / null pointer");
     return dqo_launch_error_maps((int64_t)W * H, gt_color, gt_depth, render, depth, depth_index, mask, color_err, depth_err, (hipStream_t)stream);
+}
+
+DQO_API size_t dqo_map_lifecycle_workspace_bytes(int32_t P) { return dqo_lifecycle_ws_bytes(P < 0 ? 0 : P); }
+
+static int check_lifecycle(const DqoLifecycle* a) {
+    DQO_CHECK_ARG(a != nullptr, "null DqoLifecycle");
+    DQO_CHECK_ARG(a->P >= 0 && a->delete_thresh >= 1, "bad P / delete_thresh");
+    if (a->P == 0) return DQO_OK;
+    DQO_CHECK_ARG(a->xyz && a->opacity_raw && a->scaling_raw && a->confidence && a->alive && a->row_flags && a->stable && a->add_tick &&
+                      a->depth_error_counter && a->color_error_counter && a->park && a->vote, "null per-Gaussian buffer / park / vote");
+    if (a->workspace == nullptr || a->workspace_bytes < dqo_lifecycle_ws_bytes(a->P)) {
+        dqo_set_error("lifecycle workspace too small (%zu < %zu)", a->workspace_bytes, dqo_lifecycle_ws_bytes(a->P));
+        return DQO_ERR_WORKSPACE;
+    }
+    return DQO_OK;
+}
+
+DQO_API int dqo_map_lifecycle_vote(const DqoLifecycle* step, const float* gt_color, const float* gt_depth, const float* render_color,
+                                   const float* render_depth, const int32_t* depth_index, const int32_t* color_index, void* stream) {
+    const int rc = check_lifecycle(step);
+    if (rc) return rc;
+    DQO_CHECK_ARG(step->W > 0 && step->H > 0 && (int64_t)step->W * step->H < (1ll << 31), "bad image size");
+    DQO_CHECK_ARG(gt_color && gt_depth && render_color && render_depth && depth_index && color_index, "null image");
+    if (step->P == 0) return DQO_OK;
+    return dqo_launch_lifecycle_vote(step, gt_color, gt_depth, render_color, render_depth, depth_index, color_index, (hipStream_t)stream);
+}
+
+DQO_API int dqo_map_lifecycle_rows(const DqoLifecycle* step, void* stream) {
+    const int rc = check_lifecycle(step);
+    if (rc) return rc;
+    DQO_CHECK_ARG(step->stats != nullptr, "null stats");
+    if (step->P == 0) return dqo_launch_zero_words(reinterpret_cast<uint32_t*>(step->stats), 8, (hipStream_t)stream);
+    return dqo_launch_lifecycle_rows(step, (hipStream_t)stream);
 }
 
 DQO_API size_t dqo_icp_workspace_bytes(void) { return dqo_icp_ws_bytes(); }

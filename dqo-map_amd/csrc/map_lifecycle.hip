@@ -1,0 +1,273 @@
+// Map maintenance for gfx950: the three statements that close every frame of the reference mapper, on ONE map with a `stable` flag per row
+// instead of the reference's two clouds (SLAM/multiprocess/mapper.py:217-219, and :214 on optimise frames):
+//
+//     gaussians_fix()            :657-676    unstable -> stable once confidence > stable_confidence_thres (confidence clipped to it)
+//     error_gaussians_remove()   :989-1102   per-Gaussian error of a render of the whole map, strike counters, delete / release (:679-689)
+//     gaussians_delete()         :692-730    oversized or too-long-unstable Gaussians leave the map
+//
+// Everything is rewritten in place (a deleted row becomes a spare row: exactly what FusedMapper._free_rows writes), nothing is read back
+// by the host, every output is an integer, a flag or a copied value.
+//
+// The reference scatters a per-Gaussian MAXIMUM of the pixel errors and then tests `max > 2 * thres` (:1029-1068): true exactly when some
+// pixel of the Gaussian exceeds the threshold.  So the pixel pass keeps no error image and no float accumulator — a pixel over the
+// threshold sets a bit of its Gaussian's vote word with an integer atomicOr (order-independent; most pixels issue nothing), and the row
+// pass that consumes a vote word clears it: no zero fill per frame.
+//
+// The two `10 x mean radius` limits are whole-cloud reductions over the membership the earlier statements left.  No float atomics: every
+// block writes a double partial sum and a count, the block that takes the last integer ticket (the pattern of dqo_adam.h) adds the partials
+// in index order, rounds the mean to float once and multiplies by 10 in float — bitwise the same from run to run.
+#include "dqo_common.h"
+
+namespace {
+
+// words of the workspace's head (int32; zero when the workspace is made, handed back at zero by every launch that uses them).
+// Same-address atomics are served one at a time memory-side (dqo_adam.h on its block ticket, profiles/r06_tail_ticket.txt): with ONE
+// word per count the last row kernel — whose two what-is-left counts take an atomic from every wave of the map — ran 272 us on a 550 k
+// map (profiles/lifecycle_single_counter_kernel_stats.csv; the spread version below has not been timed yet).  So the block tickets have two levels
+// (a block takes a ticket on line blockIdx % lines, the last block of a line one of word 0's) and the counts are spread over LC_LINES
+// lines of 256 bytes that the last block of the last row kernel adds up.
+enum {
+    LC_LINES = 64,
+    LC_TICKET = 0,         // the row kernels' block tickets (they run one after the other): word 0, and word 16 + 16 * line
+    LC_COUNT = 4,          // [2] rows of the stable / unstable cloud the limits below were formed over
+    LC_LIMIT = 6,          // [2] float bits: 10 x mean radius of the stable / unstable cloud
+    LC_ACC = 1088,         // [LC_LINES][64] word k of a line: count k of the frame while the row kernels run (DqoLifecycle.stats gets the sums)
+    LC_HEAD_WORDS = LC_ACC + LC_LINES * 64,
+};
+static_assert(LC_ACC >= 16 + 16 * LC_LINES && LC_HEAD_WORDS * 4 % 256 == 0, "workspace head layout");
+
+struct LcWorkspace {
+    int32_t* head;
+    double* partial_sum;   // [blocks]
+    int32_t* partial_rows; // [blocks]
+};
+
+__host__ __device__ inline size_t lc_blocks(int64_t P) { return (size_t)((P + 255) / 256); }
+
+inline size_t lc_partial_sum_bytes(int64_t P) { return dqo_align_up(lc_blocks(P) * sizeof(double), 256); }
+
+inline LcWorkspace lc_workspace(void* base, int64_t P) {
+    LcWorkspace w;
+    char* p = (char*)base;
+    w.head = (int32_t*)p;
+    w.partial_sum = (double*)(p + LC_HEAD_WORDS * 4);
+    w.partial_rows = (int32_t*)(p + LC_HEAD_WORDS * 4 + lc_partial_sum_bytes(P));
+    return w;
+}
+
+// GaussianPointCloud.get_radius (gaussian_pointcloud.py:739-743): the mean of the two larger scales
+__device__ __forceinline__ float lc_radius(const float* __restrict__ scaling_raw, size_t i) {
+    const float a = expf(scaling_raw[3 * i]), b = expf(scaling_raw[3 * i + 1]), c = expf(scaling_raw[3 * i + 2]);
+    return (((a + b) + c) - fminf(fminf(a, b), c)) / 2.f;
+}
+
+// FusedMapper._free_rows: the `freed` values of _ROW_BUFFERS, and nothing else
+__device__ __forceinline__ void lc_free_row(const DqoLifecycle& a, size_t i) {
+    a.xyz[3 * i] = a.park[0], a.xyz[3 * i + 1] = a.park[1], a.xyz[3 * i + 2] = a.park[2];
+    a.opacity_raw[i] = -10.f;
+    a.scaling_raw[3 * i] = -10.f, a.scaling_raw[3 * i + 1] = -10.f, a.scaling_raw[3 * i + 2] = -10.f;
+    a.alive[i] = 0;
+    a.row_flags[i] = DQO_ROW_HIDDEN | DQO_ROW_FROZEN;
+    a.confidence[i] = 0.f;
+    a.stable[i] = 0;
+    a.add_tick[i] = 0, a.depth_error_counter[i] = 0, a.color_error_counter[i] = 0;
+}
+
+// one integer atomic per wave and count: ballot + popcount, onto the block's line
+__device__ __forceinline__ void lc_count(int32_t* head, int k, bool pred, int lane) {
+    const int n = __popcll(__ballot(pred));
+    if (lane == 0 && n > 0) atomicAdd(&head[LC_ACC + (blockIdx.x % LC_LINES) * 64 + k], n);
+}
+
+// Takes the block's ticket; true (for every thread of the block) in the block that took the last one, which then sees what every other
+// block wrote before its ticket.
+__device__ __forceinline__ bool lc_last_block(int32_t* ticket, int* s_last) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        const int grid = (int)gridDim.x;
+        const int lines = min((int)LC_LINES, max(1, grid / 16));
+        const int l = (int)blockIdx.x % lines;
+        const int on_line = (grid - l + lines - 1) / lines;  // blocks b < grid with b % lines == l
+        int32_t* const line = ticket + 16 + 16 * l;
+        bool last = atomicAdd(line, 1) == on_line - 1;
+        if (last) {
+            *line = 0;
+            __threadfence();  // (acquire what the line's other blocks released, release it to the block that takes word 0's last ticket)
+            last = atomicAdd(ticket, 1) == lines - 1;
+            if (last) *ticket = 0;
+        }
+        *s_last = last;
+    }
+    __syncthreads();
+    if (!*s_last) return false;
+    __threadfence();
+    return true;
+}
+
+// 10 x the mean radius of the rows with `member` set, over the whole launch: head[LC_LIMIT + which] (float bits) and the row count in
+// head[LC_COUNT + which], written by the last block.  Every thread of every block calls it.
+__device__ __forceinline__ void lc_cloud_limit(const LcWorkspace& w, int which, float radius, bool member) {
+    __shared__ double s_sum[256];
+    __shared__ int s_rows[256];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double x = member ? (double)radius : 0.0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);  // (a fixed butterfly: the same bits every run)
+    const int n = __popcll(__ballot(member));
+    if (lane == 0) s_sum[wave] = x, s_rows[wave] = n;
+    __syncthreads();
+    if (tid == 0) {
+        const int waves = (int)blockDim.x >> 6;
+        double t = 0.0;
+        int c = 0;
+        for (int k = 0; k < waves; k++) t += s_sum[k], c += s_rows[k];
+        __hip_atomic_store(&w.partial_sum[blockIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&w.partial_rows[blockIdx.x], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (!lc_last_block(&w.head[LC_TICKET], &s_last)) return;
+    // the partials in index order: staged through LDS 256 at a time (coalesced loads), added by one thread
+    const int blocks = (int)gridDim.x;
+    double total = 0.0;
+    long long rows = 0;
+    for (int base = 0; base < blocks; base += 256) {
+        const int j = base + tid;
+        s_sum[tid] = j < blocks ? __hip_atomic_load(&w.partial_sum[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+        s_rows[tid] = j < blocks ? __hip_atomic_load(&w.partial_rows[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+        __syncthreads();
+        if (tid == 0) {
+            const int m = min(256, blocks - base);
+            for (int k = 0; k < m; k++) total += s_sum[k], rows += s_rows[k];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float mean = rows > 0 ? (float)(total / (double)rows) : 0.f;  // rounded to float once
+        w.head[LC_LIMIT + which] = __float_as_int(mean * 10.f);
+        w.head[LC_COUNT + which] = (int32_t)rows;
+    }
+}
+
+// ---- the pixel pass (mapper.py:1015-1026, 1064-1068) ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void lifecycle_vote_kernel(int64_t HW, int P, const float* __restrict__ gt_color,
+                                                             const float* __restrict__ gt_depth, const float* __restrict__ render,
+                                                             const float* __restrict__ depth, const int32_t* __restrict__ depth_index,
+                                                             const int32_t* __restrict__ color_index, float color_thr, float depth_thr,
+                                                             uint32_t* __restrict__ vote, const DqoRastHeader* __restrict__ header) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= HW) return;
+    if (header != nullptr && header->overflow != 0u) return;  // the render outgrew its context: its images are invalid
+    const float gd = gt_depth[i];
+    if (gd == 0.f) return;  // both errors are zero there (:1021, 1025)
+    const int di = depth_index[i], ci = color_index[i];
+    const float diff = gd - depth[i];
+    const float de = (diff < 0.f || di == -1) ? 0.f : fabsf(diff);  // (:1015-1016, 1021-1024)
+    // (a Gaussian covers many pixels: the plain read spares most of them the atomic; a stale 0 only costs a redundant one)
+    if (de > depth_thr && di >= 0 && di < P && !(vote[di] & 1u)) atomicOr(&vote[di], 1u);
+    const float ce = (fabsf(gt_color[i] - render[i]) + fabsf(gt_color[HW + i] - render[HW + i])) + fabsf(gt_color[2 * HW + i] - render[2 * HW + i]);
+    if (ce > color_thr && ci >= 0 && ci < P && !(vote[ci] & 2u)) atomicOr(&vote[ci], 2u);
+}
+
+// ---- the row kernels --------------------------------------------------------------------------------------------------------------------
+// (optional) the limit of the STABLE cloud as the frame finds it: gaussians_delete(unstable=False), mapper.py:214
+__global__ __launch_bounds__(256) void lifecycle_stable_limit_kernel(DqoLifecycle a, LcWorkspace w) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool member = i < (size_t)a.P && a.alive[i] != 0 && a.stable[i] != 0;
+    lc_cloud_limit(w, 0, member ? lc_radius(a.scaling_raw, i) : 0.f, member);
+}
+
+// statements 0 (optional), 1 and 2, and the limit of the unstable cloud they leave
+__global__ __launch_bounds__(256) void lifecycle_fix_kernel(DqoLifecycle a, LcWorkspace w) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool in = i < (size_t)a.P;
+    bool alive = in && a.alive[i] != 0;
+    bool stable = alive && a.stable[i] != 0;
+    const float radius = alive ? lc_radius(a.scaling_raw, i) : 0.f;
+    // 0. gaussians_delete(unstable=False): oversized rows of the stable cloud (a cloud with a member has a limit)
+    const bool big_stable = a.stable_oversized != 0 && stable && radius > __int_as_float(w.head[LC_LIMIT + 0]);
+    if (big_stable) lc_free_row(a, i), alive = stable = false;
+    // 1. gaussians_fix
+    const bool promoted = alive && !stable && a.confidence[i] > a.stable_confidence_thres;
+    if (promoted) {
+        a.stable[i] = 1, stable = true;
+        a.confidence[i] = a.stable_confidence_thres;  // torch.clip(confidence, max=thres) of a value above it
+    }
+    // 2. error_gaussians_remove: strikes count on rows that are stable now; delete wins over release; a released row keeps its counters
+    bool by_depth = false, released = false;
+    if (a.use_votes != 0 && in) {
+        const uint32_t v = a.vote[i];
+        if (v != 0u) a.vote[i] = 0u;
+        if (stable) {
+            const int dc = a.depth_error_counter[i] + (int)(v & 1u), cc = a.color_error_counter[i] + (int)((v >> 1) & 1u);
+            by_depth = dc >= a.delete_thresh;
+            released = !by_depth && cc >= a.delete_thresh;
+            if (by_depth) {
+                lc_free_row(a, i), alive = stable = false;
+            } else {
+                if (v & 1u) a.depth_error_counter[i] = dc;
+                if (v & 2u) a.color_error_counter[i] = cc;
+                if (released) {  // gaussians_release, :679-689
+                    a.stable[i] = 0, stable = false;
+                    a.confidence[i] = 0.f;
+                    a.add_tick[i] = a.tick;
+                }
+            }
+        }
+    }
+    lc_count(w.head, 0, promoted, lane);
+    lc_count(w.head, 1, released, lane);
+    lc_count(w.head, 2, by_depth, lane);
+    lc_count(w.head, 5, big_stable, lane);
+    lc_cloud_limit(w, 1, radius, alive && !stable);
+}
+
+// statement 3: gaussians_delete(unstable=True), the counts of what is left, and the frame's counts handed over
+__global__ __launch_bounds__(256) void lifecycle_delete_kernel(DqoLifecycle a, LcWorkspace w) {
+    __shared__ int s_last;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool alive = i < (size_t)a.P && a.alive[i] != 0;
+    const bool stable = alive && a.stable[i] != 0, unstable = alive && !stable;
+    const bool big = unstable && lc_radius(a.scaling_raw, i) > __int_as_float(w.head[LC_LIMIT + 1]);
+    const bool old = unstable && !big && a.tick - a.add_tick[i] > a.unstable_time_window;  // (a row that is both counts as oversized)
+    if (big || old) lc_free_row(a, i);
+    lc_count(w.head, 3, big, lane);
+    lc_count(w.head, 4, old, lane);
+    lc_count(w.head, 6, unstable && !big && !old, lane);
+    lc_count(w.head, 7, stable, lane);
+    if (!lc_last_block(&w.head[LC_TICKET], &s_last)) return;
+    // the eight counts: wave w adds up counts 2w and 2w + 1 over the lines (lane = line) and leaves the lines at zero
+    const int wave = threadIdx.x >> 6;
+    static_assert(LC_LINES == 64, "one lane per line");
+    for (int k = 2 * wave; k < 2 * wave + 2; k++) {
+        const uint32_t n = dqo_wave_sum_u32((uint32_t)atomicExch(&w.head[LC_ACC + lane * 64 + k], 0), lane);
+        if (lane == 0) a.stats[k] = (int32_t)n;
+    }
+}
+
+}  // namespace
+
+size_t dqo_lifecycle_ws_bytes(int64_t P) {
+    return LC_HEAD_WORDS * 4 + lc_partial_sum_bytes(P) + dqo_align_up(lc_blocks(P) * sizeof(int32_t), 256);
+}
+
+int dqo_launch_lifecycle_vote(const DqoLifecycle* a, const float* gt_color, const float* gt_depth, const float* render, const float* depth,
+                              const int32_t* depth_index, const int32_t* color_index, hipStream_t s) {
+    const int64_t HW = (int64_t)a->W * a->H;
+    DQO_LAUNCH("lifecycle_vote_kernel", lifecycle_vote_kernel, dim3((unsigned)((HW + 255) / 256)), dim3(256), s, HW, a->P, gt_color, gt_depth,
+               render, depth, depth_index, color_index, 2.f * a->add_color_thres, 2.f * a->add_depth_thres, a->vote, a->render_header);
+    return DQO_OK;
+}
+
+int dqo_launch_lifecycle_rows(const DqoLifecycle* a, hipStream_t s) {
+    const LcWorkspace w = lc_workspace(a->workspace, a->P);
+    const dim3 grid((unsigned)lc_blocks(a->P)), block(256);
+    if (a->stable_oversized) {
+        DQO_LAUNCH("lifecycle_stable_limit_kernel", lifecycle_stable_limit_kernel, grid, block, s, *a, w);
+    }
+    DQO_LAUNCH("lifecycle_fix_kernel", lifecycle_fix_kernel, grid, block, s, *a, w);
+    DQO_LAUNCH("lifecycle_delete_kernel", lifecycle_delete_kernel, grid, block, s, *a, w);
+    return DQO_OK;
+}

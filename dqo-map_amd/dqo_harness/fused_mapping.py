@@ -129,6 +129,7 @@ class _SideJob:
 #   freed  an in-place growth step writes `spare` into the rows it frees: what makes the row a spare row for the kernels
 #   live   the value of a row a Gaussian moves into, where the growth step computes none
 _RowBuffer = collections.namedtuple("_RowBuffer", "name group spare freed live src of shape", defaults=(None, False, 0, None, None, None))
+_LIFECYCLE_ROWS = ("stable", "add_tick", "depth_error_counter", "color_error_counter")
 _ROW_BUFFERS = (
     _RowBuffer("xyz", "param", "park", freed=True), _RowBuffer("shs", "param", 0.0), _RowBuffer("opacity_raw", "param", -10.0, freed=True),
     _RowBuffer("scaling_raw", "param", -10.0, freed=True), _RowBuffer("rotation_raw", "param", "unit_q"),
@@ -139,6 +140,10 @@ _ROW_BUFFERS = (
     _RowBuffer("alive", "meta", 0, freed=True, live=1),
     _RowBuffer("row_flags", "meta", N.ROW_HIDDEN | N.ROW_FROZEN, freed=True),  # (a spare row: not rendered, not trained)
     _RowBuffer("confidence", "meta", 0.0, freed=True), _RowBuffer("gaussian_object", "meta", 0),
+    # track_lifecycle(): which of the reference's two clouds a row belongs to (1 = stable_pointcloud) and what maintain() keeps per row
+    # (SLAM/gaussian_pointcloud.py:43-46)
+    _RowBuffer("stable", "meta", 0, freed=True), _RowBuffer("add_tick", "meta", 0, freed=True),
+    _RowBuffer("depth_error_counter", "meta", 0, freed=True), _RowBuffer("color_error_counter", "meta", 0, freed=True),
     _RowBuffer("opacity", "sized", shape=lambda P: (P, 1)), _RowBuffer("scales", "sized", shape=lambda P: (P, 3)),
     _RowBuffer("rotations", "sized", shape=lambda P: (P, 4)),
     # (one partial sum per block of 256 Gaussians from dqo_map_adam_step, per wave of 64 from dqo_rast_backward_adam)
@@ -237,6 +242,10 @@ class FusedMapper:
         self.object_cell = None  # per-object growth decisions: cell size of dqo_mapgrowth.object_offsets (None = its 16 m default)
         self.per_object_loss = False
         self.alive = None  # reserve(): uint8 [P], 0 = a spare row (parked behind the camera, no Gaussian of the map)
+        self.stable = self.add_tick = self.depth_error_counter = self.color_error_counter = None  # track_lifecycle()
+        self._n_spare_stale = False  # maintain() freed rows on the device since _n_spare was read
+        self._lifecycle = {}  # maintain(): lifecycle_step's vote words and workspace ("_lifecycle"), made anew when P changes
+        self._maintain_ctx = None  # maintain(): the persistent buffers of its render (_maintain_render)
         self._n_spare = self._spare_rows = 0  # spare rows now (host copy of the count: grow() keeps it up to date) / as reserve()d
         # DqoAdamStep.attach_gains: the attach term's two factors in device memory, rewritten in place by begin_mapping_call — a captured
         # graph survives a new mapping call
@@ -518,6 +527,7 @@ class FusedMapper:
                 make = torch.empty if b.spare is None else torch.zeros
                 setattr(self, b.name, make(b.shape(self.P), dtype=torch.float32, device=self.device))
         self._attach_n, self._act_valid = 0, False
+        self._lifecycle, self._maintain_ctx = {}, None
         self._drop_graphs()
 
     @torch.no_grad()
@@ -548,9 +558,139 @@ class FusedMapper:
     def n_alive(self):
         return self.P if self.alive is None else int(self.alive.sum().item())
 
+    def _refresh_spare_count(self):
+        """maintain() frees rows on the device and reads nothing back: the host's spare-row count is re-read from `alive` by the next
+        grow(), which synchronises anyway."""
+        if self._n_spare_stale:
+            self._n_spare, self._n_spare_stale = int(self.alive.numel() - int(self.alive.sum().item())), False
+
+    # ------------------------------------------------------------------ map maintenance (csrc/map_lifecycle.hip) ----------
+    @torch.no_grad()
+    def track_lifecycle(self, stable_mask=None, tick=0):
+        """Start keeping what the reference keeps per Gaussian for its map maintenance: which cloud the row belongs to (`stable` uint8,
+        1 = stable_pointcloud; stable_mask bool [P] or None = the whole map is unstable), `add_tick` (int32, `tick` for every Gaussian
+        of the map now) and the two strike counters of error_gaussians_remove (int32, zero).  Spare rows hold 0 in all four.  From here on
+        reserve() and grow() carry them, maintain() rewrites them.  A mapper that never calls this behaves as before."""
+        dev, P = self.device, self.P
+        live = torch.ones((P,), dtype=torch.bool, device=dev) if self.alive is None else self.alive.bool()
+        stable = torch.zeros((P,), dtype=torch.bool, device=dev) if stable_mask is None else stable_mask.to(dev).bool().reshape(-1)
+        if stable.numel() != P:
+            raise RuntimeError("FusedMapper.track_lifecycle: stable_mask must have one entry per row")
+        self.stable = (stable & live).to(torch.uint8)
+        self.add_tick = live.to(torch.int32) * int(tick)
+        self.depth_error_counter = torch.zeros((P,), dtype=torch.int32, device=dev)
+        self.color_error_counter = torch.zeros((P,), dtype=torch.int32, device=dev)
+        self._lifecycle = {}
+        return self
+
+    def _require_lifecycle(self, who):
+        if self.stable is None:
+            raise RuntimeError(f"FusedMapper.{who}: this mapper does not track its Gaussians' lifecycle; call track_lifecycle() first")
+
+    def stable_rows(self):
+        """bool [P]: the rows of the reference's stable_pointcloud (alive & stable) — what set_training_rows and grow(stable_mask=...) take."""
+        self._require_lifecycle("stable_rows")
+        return (self.stable != 0) if self.alive is None else (self.stable != 0) & (self.alive != 0)
+
+    # configs/base.yaml:51-52, 59-60 and the `delete_thresh = 10` of mapper.py:1092
+    MAINTAIN_DEFAULTS = dict(stable_confidence_thres=500.0, unstable_time_window=200, add_color_thres=0.1, add_depth_thres=None, delete_thresh=10)
+
+    def _maintain_render(self, st):
+        """The whole map (both clouds: no row flags, no object gate; spare rows are parked and transparent) rendered at camera `st` through
+        the C ABI into persistent buffers: the op's nine outputs c["out"] (0 colour, 1 depth, 2 colour hit index, 3 depth hit index).
+        The first call measures the frame (prepare, one header read, render) and sizes the instance capacity at 1.5 x its candidate
+        pairs + 4096; later calls are ONE dqo_rast_forward call on those buffers — no header copy, no event, no allocation."""
+        lib, dev, P, M = N.lib(), self.device, self.P, self.M
+        H, W = int(st.image_height), int(st.image_width)
+        if (H, W) != (int(self.settings.image_height), int(self.settings.image_width)):
+            raise RuntimeError("FusedMapper.maintain: every frame of a mapper has the mapper's image size")
+        stream = N.current_stream()
+        b = ctypes.byref
+        c = self._maintain_ctx
+        first = c is None or c["key"] != (P, H, W)
+        if first:
+            u8 = dict(dtype=torch.uint8, device=dev)
+            out, outputs = dgr._new_outputs(P, H, W, dev)
+            c = dict(key=(P, H, W), out=out, outputs=outputs, geom=torch.empty((lib.dqo_rast_geom_bytes(P, W, H),), **u8),
+                     img=torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8))
+        params = dgr._params(st, P, M)
+        inputs = dgr._inputs(st, self.xyz, self.shs, self._empty, self.opacity, self.scales, self.rotations, self._empty, self.tile_mask)
+        cctx = N.DqoRastCtx(geom=c["geom"].data_ptr(), geom_bytes=c["geom"].numel(), binning=None, binning_bytes=0,
+                            image=c["img"].data_ptr(), image_bytes=c["img"].numel(), inst_capacity=0)
+        if first:
+            hdr = N.DqoRastHeader()
+            N.check(lib.dqo_rast_forward_prepare(b(params), b(inputs), b(c["outputs"]), b(cctx), stream))
+            N.check(lib.dqo_rast_read_header(b(cctx), b(hdr), stream))
+            c["cap"] = int(1.5 * int(hdr.num_candidates)) + 4096
+            c["binning"] = torch.empty((lib.dqo_rast_binning_bytes(c["cap"]),), dtype=torch.uint8, device=dev)
+        cctx.binning, cctx.binning_bytes, cctx.inst_capacity = c["binning"].data_ptr(), c["binning"].numel(), c["cap"]
+        if first:
+            N.check(lib.dqo_rast_forward_render(b(params), b(inputs), b(c["outputs"]), b(cctx), stream))
+            self._maintain_ctx = c
+        else:
+            N.check(lib.dqo_rast_forward(b(params), b(inputs), b(c["outputs"]), b(cctx), stream))
+        return c
+
+    def maintain_overflowed(self):
+        """Whether the most recent maintain()'s render outgrew its context (one small device-to-host read: call it where a
+        synchronisation is affordable, like graph_overflowed()).  If so that frame cast no votes, and the next maintain() sizes a new
+        context."""
+        c = self._maintain_ctx
+        if c is None:
+            return False
+        over = int(c["geom"][:32].view(torch.int32)[2].item()) != 0
+        if over:
+            self._maintain_ctx = None
+        return over
+
+    @torch.no_grad()
+    def maintain(self, tick, gt_color, gt_depth, settings=None, stable_oversized=False, **thresholds):
+        """The statements that close every frame of the reference mapper (SLAM/multiprocess/mapper.py:217-219) on this mapper's map:
+            gaussians_fix()            :657-676    unstable rows with confidence > stable_confidence_thres become stable
+            error_gaussians_remove()   :989-1102   the whole map is rendered at the frame's camera; a stable row some pixel charges with a
+                                                   depth / colour error above 2 x add_depth_thres / add_color_thres gets a strike;
+                                                   delete_thresh depth strikes delete it, else delete_thresh colour strikes release it
+            gaussians_delete()         :692-730    oversized or too-long-unstable rows of the unstable cloud are deleted
+        and, stable_oversized (optimise frames, :214), gaussians_delete(unstable=False) in front.  tick: the mapper's `time`; gt_color
+        [3,H,W], gt_depth [1,H,W]: the frame (processed_map[-1]); settings: its camera (default: the mapper's).  thresholds:
+        MAINTAIN_DEFAULTS (add_depth_thres None = the mapper's).  One render (_maintain_render), dqo_mapgrowth.lifecycle_step and one
+        activation pass: everything is rewritten in place — deleted rows become spare rows, P stays, captured graphs stay valid.  The
+        FIRST call (and the first after P changed or after maintain_overflowed() reported an overflow) sizes the render's context from
+        one 32-byte header read, as capture() does; every later call reads nothing back and does not synchronise.  A later frame that
+        outgrows that context renders nothing valid: it casts no vote (statements 0, 1 and 3 still run) and maintain_overflowed() tells.
+        The spare-row count is read again by the next grow().  Row flags of surviving rows are the caller's:
+        set_training_rows(trainable=~fm.stable_rows()) names the next call's clouds.  Returns the int32 [8] device tensor of counts
+        (dqo_mapgrowth.LIFECYCLE_STATS)."""
+        import dqo_mapgrowth as mg
+        self._require_lifecycle("maintain")
+        if self.attach_count_reducer is not None:
+            raise NotImplementedError("FusedMapper.maintain: a sharded mapper would need the whole map's mean radii (DESIGN.md §6)")
+        unknown = set(thresholds) - set(self.MAINTAIN_DEFAULTS)
+        if unknown:
+            raise TypeError(f"FusedMapper.maintain: unknown thresholds {sorted(unknown)}")
+        th = dict(self.MAINTAIN_DEFAULTS, **thresholds)
+        if th["add_depth_thres"] is None:
+            th["add_depth_thres"] = self.add_depth_thres
+        dev = self.device
+        st = self.settings if settings is None else _normalised_settings(settings, dev)
+        if self.alive is None:
+            self.alive = torch.ones((self.P,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            self.activate()
+            c = self._maintain_render(st)
+            # (the buffers as they are bound NOW; only the vote words and the workspace are kept from call to call)
+            state = dict({b.name: a for b, a in self._rows("param", "meta")}, **self._lifecycle)
+            stats = mg.lifecycle_step(state, tick, gt_color, gt_depth, c["out"][0], c["out"][1], c["out"][3], c["out"][2],
+                                      stable_oversized=stable_oversized, park=self._park_position(), render_header=c["geom"], **th)
+            self._lifecycle = {"_lifecycle": state["_lifecycle"]}
+        self._n_spare_stale = True  # (_refresh_spare_count)
+        self._act_valid = False  # deleted rows' raw parameters changed
+        self.activate()  # (a captured iteration starts from the activations of the current parameters)
+        return stats
+
     @torch.no_grad()
     def grow(self, new, delete_mask=None, min_radius=0.001, max_radius=0.05, xyz_factor=(1.0, 1.0, 0.1), scale_factor=1.0,
-             new_mapping_call=False, stable_mask=None, unstable_opacity_low=0.1, attach_async=True):
+             new_mapping_call=False, stable_mask=None, unstable_opacity_low=0.1, attach_async=True, tick=None):
         """The map-growth step between two mapping calls — Mapping.gaussians_add (SLAM/multiprocess/mapper.py:249-254) and the
         deletion half of error_gaussians_remove (:1086-1096) — on this mapper's map.  `new`: dict(xyz [Q,3], scales [Q,3],
         rotations [Q,4], opacity [Q,1], shs [Q,M,3]; with an object gate also obj_id [Q]) of numpy arrays or GPU tensors.
@@ -575,7 +715,10 @@ class FusedMapper:
         The result is stored in one of two ways (_store_in_place / _store_reallocating say what each means for captured graphs): in
         place when the map has reserve()d spare rows, new_mapping_call is set and the spare and deleted rows hold the new Gaussians;
         into re-allocated buffers otherwise.  new_mapping_call=True also starts the next mapping call (begin_mapping_call: fresh Adam,
-        fresh init_stat, as the reference does after every growth step, mapper.py:533-548).  Returns the counts of each stage."""
+        fresh init_stat, as the reference does after every growth step, mapper.py:533-548).  tick (a mapper that track_lifecycle()s): the
+        new rows' add_tick — they join the unstable cloud with zero strike counters (temp_to_optimize, mapper.py:1438-1466).  Returns the
+        counts of each stage."""
+        self._refresh_spare_count()
         c = self._grow_candidates(new)
         Q = c["xyz"].shape[0]
         stats = dict(candidates=int(Q), inside_existing=0, invalid_scale=0, added=0, deleted=0)
@@ -597,6 +740,8 @@ class FusedMapper:
             stats["attached"] = self._lower_attached(c, idx, attach.result(), Q, unstable_opacity_low)
         rows = self._new_rows(c, scales, invalid, scale_factor, xyz_factor, stats)
         stats["added"] = n_add = int(rows["xyz"].shape[0])
+        if tick is not None and self.add_tick is not None:
+            rows["add_tick"] = torch.full((n_add,), int(tick), dtype=torch.int32, device=self.device)
         if self.alive is not None:
             # (the deleted rows as indices, found once: four boolean-mask writes were four passes over the map + four host round trips)
             if delete_mask is None:
@@ -1070,7 +1215,7 @@ class FusedMapper:
 
     # ------------------------------------------------------------------ the frame set of a mapping call -----------------
     def _trained_state(self):
-        return [a for _, a in self._rows("param", "moment")] + [self.confidence]
+        return [a for _, a in self._rows("param", "moment")] + [self.confidence] + [a for b, a in self._rows("meta") if b.name in _LIFECYCLE_ROWS]
 
     def _snapshot_state(self):
         return dict(rows=[a.clone() for a in self._trained_state()], step=self.step_count)

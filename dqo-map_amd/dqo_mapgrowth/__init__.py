@@ -18,6 +18,8 @@
 The nearest-neighbour search is libdqoraster.so's dqo_knn3_query (Morton-sorted, box-pruned, wave-uniform candidate loads —
 csrc/knn.hip); everything else is a handful of element-wise torch ops exactly as in the reference.  GPU only.
 """
+import ctypes
+
 import torch
 
 import _dqo_native as N
@@ -407,3 +409,73 @@ def temp_points_attach_indices(temp_xyz, temp_opacity, w2c, intrinsic, image_wid
         on_plane &= stable_obj[sidx] == temp_obj[keep][idx]
     idx = idx[on_plane]
     return origin[keep][idx]
+
+
+# ---- map maintenance: promote, release and delete Gaussians (csrc/map_lifecycle.hip) -----------------------------------------------------
+LIFECYCLE_STATE = (("xyz", torch.float32, 3), ("opacity_raw", torch.float32, 1), ("scaling_raw", torch.float32, 3), ("confidence", torch.float32, 1),
+                   ("alive", torch.uint8, 1), ("row_flags", torch.uint8, 1), ("stable", torch.uint8, 1), ("add_tick", torch.int32, 1),
+                   ("depth_error_counter", torch.int32, 1), ("color_error_counter", torch.int32, 1))
+LIFECYCLE_STATS = ("promoted", "released", "deleted_depth", "deleted_oversized_unstable", "deleted_time", "deleted_oversized_stable",
+                   "unstable_left", "stable_left")
+
+
+def lifecycle_step(state, tick, gt_color, gt_depth, render_color, render_depth, depth_index, color_index, *, stable_confidence_thres,
+                   unstable_time_window, add_color_thres, add_depth_thres, delete_thresh=10, stable_oversized=False, park, stats=None, render_header=None):
+    """The three statements that close every frame of the reference mapper — gaussians_fix (SLAM/multiprocess/mapper.py:657-676),
+    error_gaussians_remove (:989-1102) and gaussians_delete (:692-730); with stable_oversized also gaussians_delete(unstable=False) (:214)
+    in front — on ONE map whose rows carry a `stable` flag (include/dqo_raster.h, DqoLifecycle, says what each statement does).
+
+    state: dict of the GPU tensors the kernels rewrite IN PLACE, one row per Gaussian (LIFECYCLE_STATE: xyz [P,3], opacity_raw [P,1],
+    scaling_raw [P,3], confidence [P] float32; alive, row_flags, stable [P] uint8; add_tick, depth_error_counter, color_error_counter [P]
+    int32).  The vote words and the workspace are made on the first call and kept in state["_lifecycle"]; later calls allocate nothing.
+    gt_color [3,H,W], gt_depth [1,H,W]: the frame; render_color, render_depth, depth_index, color_index: a render of the whole map at the
+    frame's camera (index maps int32, in map rows) — all four None: statement 2 is skipped (the reference's early return), counters and
+    votes do not move.  park: [3] GPU tensor, where deleted rows go.  Returns the int32 [8] device tensor of the frame's counts
+    (LIFECYCLE_STATS; `stats` if given).  render_header (optional): the geometry buffer of the forward that rendered the images (its
+    device header leads it) — a frame that overflowed its capacity then casts no vote.  At most four launches, no host synchronisation."""
+    dev = state["xyz"].device
+    P = int(state["xyz"].shape[0])
+    for name, dtype, width in LIFECYCLE_STATE:
+        a = state[name]
+        N.require_gpu(a)
+        if a.dtype != dtype or a.numel() != P * width or not a.is_contiguous() or a.device != dev:
+            raise RuntimeError(f"lifecycle_step: state['{name}'] must be a contiguous {dtype} tensor of {P} x {width} on {dev} (it is rewritten in place)")
+    renders = (render_color, render_depth, depth_index, color_index)
+    use_votes = all(r is not None for r in renders)
+    if not use_votes and any(r is not None for r in renders):
+        raise RuntimeError("lifecycle_step: the render arguments are given together or not at all")
+    park = park.contiguous() if torch.is_tensor(park) else const_tensor(list(park), dev)
+    N.require_gpu(park)
+    if park.dtype != torch.float32 or park.numel() != 3:
+        raise RuntimeError("lifecycle_step: park is a float32 tensor of 3")
+    lib = N.lib()
+    ws = state.get("_lifecycle")
+    if ws is None or ws[0] != P:
+        ws = state["_lifecycle"] = (P, torch.zeros((max(P, 1),), dtype=torch.int32, device=dev),
+                                    torch.zeros((lib.dqo_map_lifecycle_workspace_bytes(P),), dtype=torch.uint8, device=dev),
+                                    torch.zeros((8,), dtype=torch.int32, device=dev))
+    _, vote, work, own_stats = ws
+    stats = own_stats if stats is None else stats
+    N.require_gpu(stats)
+    if stats.dtype != torch.int32 or stats.numel() != 8 or not stats.is_contiguous():
+        raise RuntimeError("lifecycle_step: stats is a contiguous int32 tensor of 8")
+    H = W = 0
+    if use_votes:
+        H, W = int(gt_depth.shape[-2]), int(gt_depth.shape[-1])
+        images = ((gt_color, torch.float32, 3), (gt_depth, torch.float32, 1), (render_color, torch.float32, 3), (render_depth, torch.float32, 1),
+                  (depth_index, torch.int32, 1), (color_index, torch.int32, 1))
+        for a, dtype, planes in images:
+            N.require_gpu(a)
+            if a.dtype != dtype or a.numel() != planes * H * W:
+                raise RuntimeError(f"lifecycle_step: images are float32 [3 | 1, {H}, {W}], index maps int32 [1, {H}, {W}]")
+    step = N.DqoLifecycle(P=P, W=W, H=H, tick=int(tick), unstable_time_window=int(unstable_time_window), delete_thresh=int(delete_thresh),
+                          stable_oversized=int(bool(stable_oversized)), use_votes=int(use_votes),
+                          stable_confidence_thres=float(stable_confidence_thres), add_color_thres=float(add_color_thres),
+                          add_depth_thres=float(add_depth_thres), park=N.ptr(park), vote=N.ptr(vote), workspace=N.ptr(work),
+                          workspace_bytes=work.numel(), stats=N.ptr(stats), render_header=N.ptr(render_header), **{name: N.ptr(state[name]) for name, _, _ in LIFECYCLE_STATE})
+    with torch.cuda.device(dev):
+        if use_votes:
+            c = [a.contiguous() for a, _, _ in images]
+            N.check(lib.dqo_map_lifecycle_vote(ctypes.byref(step), *[N.ptr(a) for a in c], N.current_stream()))
+        N.check(lib.dqo_map_lifecycle_rows(ctypes.byref(step), N.current_stream()))
+    return stats

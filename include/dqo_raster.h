@@ -236,7 +236,8 @@ int dqo_abi_version(void);
 const char* dqo_last_error(void);
 /* sizeof() of the ABI structs as this library was compiled (a binding checks its own struct definitions against it):
  * 0 DqoRastParams, 1 DqoRastInputs, 2 DqoRastOutputs, 3 DqoRastCtx, 4 DqoRastGrads, 5 DqoRastHeader, 6 DqoProfileEntry,
- * 7 DqoAdamStep, 8 DqoLossTap, 9 DqoObjectGate, 10 DqoAdamTensor, 11 DqoRastParamInputs, 12 DqoRastParamGrads; 0 for any other index. */
+ * 7 DqoAdamStep, 8 DqoLossTap, 9 DqoObjectGate, 10 DqoAdamTensor, 11 DqoRastParamInputs, 12 DqoRastParamGrads, 14 DqoLifecycle; 0 for
+ * any other index (13 stays unused: bindings probe it for the end of the parameter-form structs). */
 size_t dqo_abi_sizeof(int32_t which);
 
 /* Optional per-kernel timing (measurement only; the reference has nothing comparable — it times whole frames with
@@ -392,6 +393,67 @@ int dqo_growth_scales(int32_t n, const float* xyz, const int32_t* object, const 
 int dqo_growth_inside(int32_t n, const float* d2, const int32_t* idx, const float* radius, uint8_t* inside, void* hipStream);
 int dqo_error_maps(int32_t H, int32_t W, const float* gt_color, const float* gt_depth, const float* render, const float* depth,
                    const int32_t* depth_index, const uint8_t* mask, float* color_err, float* depth_err, void* hipStream);
+
+/* Map maintenance: the three statements that close every frame of the reference mapper (SLAM/multiprocess/mapper.py:217-219, and :214 on
+ * optimise frames) on ONE map whose rows carry a `stable` flag instead of living in two clouds, rewritten in place, nothing read back:
+ *     gaussians_fix()            :657-676    unstable -> stable once confidence > stable_confidence_thres (strict; confidence clipped to it)
+ *     error_gaussians_remove()   :989-1102   per-Gaussian error of a render of the whole map -> strike counters -> delete / release (:679-689)
+ *     gaussians_delete()         :692-730    oversized (radius > 10 x the cloud's mean radius) or too-long-unstable rows leave the map
+ *
+ * dqo_map_lifecycle_vote (one launch, one thread per pixel; images are [C, H*W] planes, index maps the op's hit_color / hit_depth):
+ *   de = gt_depth - depth where that is > 0, else 0, and 0 where gt_depth == 0 or depth_index == -1; ce = (|dr| + |dg|) + |db|, 0 where
+ *   gt_depth == 0 (:1015-1026).  The reference scatters a per-Gaussian maximum and tests `max > 2 x thres` (:1029-1068), which holds exactly
+ *   when some pixel exceeds it: a pixel with de > 2 x add_depth_thres sets bit 0 of vote[depth_index], one with ce > 2 x add_color_thres
+ *   bit 1 of vote[color_index] (integer atomic OR; indices outside [0, P) are ignored).  No error image, no float accumulator.  The
+ *   normal error is identically zero in the reference (:1020) and is not formed.
+ * dqo_map_lifecycle_rows (two launches, three with stable_oversized; one thread per row; rows with alive == 0 take part in nothing):
+ *   0. stable_oversized (gaussians_delete(unstable=False), :214): stable rows with radius > 10 x the stable cloud's mean radius are deleted;
+ *   1. gaussians_fix: an unstable row with confidence > stable_confidence_thres becomes stable, its confidence the threshold;
+ *   2. use_votes (error_gaussians_remove): on the rows that are stable now, vote bit 0 / 1 adds one to depth_error_counter /
+ *      color_error_counter; depth_error_counter >= delete_thresh deletes the row, otherwise color_error_counter >= delete_thresh releases
+ *      it (stable = 0, confidence = 0, add_tick = tick).  A released row keeps both counters, as the reference's remove() / cat() carry
+ *      them (gaussian_pointcloud.py:235-293, 415-432).  Every vote word is cleared as it is read;
+ *   3. gaussians_delete(unstable=True): unstable rows (released ones included) with radius > 10 x the unstable cloud's mean radius or
+ *      tick - add_tick > unstable_time_window are deleted.
+ *   radius = (sum exp(scaling_raw) - min exp(scaling_raw)) / 2 (get_radius, gaussian_pointcloud.py:739-743).  Each mean is over the
+ *   membership the earlier statements left (an empty cloud deletes nothing, :697): per block a double partial sum and a count, added in
+ *   index order by the block that takes the last integer ticket, rounded to float once, x 10 in float — no float atomics, the same bits on
+ *   every run.  Deleting a row writes what a spare row holds and nothing else: xyz = park, opacity_raw = scaling_raw = -10, alive = 0,
+ *   row_flags = DQO_ROW_HIDDEN | DQO_ROW_FROZEN, confidence = 0, and 0 into stable / add_tick / both counters.
+ *   stats[8] (the frame's counts, overwritten): promoted, released, deleted by depth, deleted oversized-unstable, deleted by time (and
+ *   not oversized), deleted oversized-stable, unstable rows left, stable rows left.
+ * workspace: dqo_map_lifecycle_workspace_bytes(P) bytes, ZERO when first used and then left to these calls (they hand it back ready for
+ * the next frame); vote [P] likewise. */
+typedef struct DqoLifecycle {
+    int32_t P, W, H;
+    int32_t tick;                  /* the mapper's `time` */
+    int32_t unstable_time_window, delete_thresh;
+    int32_t stable_oversized;      /* non-zero: statement 0 */
+    int32_t use_votes;             /* non-zero: statement 2 (0: the reference's early return, no stable Gaussian / no processed frame) */
+    float stable_confidence_thres, add_color_thres, add_depth_thres;
+    float* xyz;                    /* [P,3] */
+    float* opacity_raw;            /* [P] */
+    float* scaling_raw;            /* [P,3] */
+    float* confidence;             /* [P] */
+    uint8_t* alive;                /* [P] */
+    uint8_t* row_flags;            /* [P] */
+    uint8_t* stable;               /* [P] */
+    int32_t* add_tick;             /* [P] */
+    int32_t* depth_error_counter;  /* [P] */
+    int32_t* color_error_counter;  /* [P] */
+    const float* park;             /* [3] where deleted rows are parked (device memory) */
+    uint32_t* vote;                /* [P] */
+    void* workspace;
+    size_t workspace_bytes;
+    int32_t* stats;                /* [8] */
+    const DqoRastHeader* render_header; /* dqo_map_lifecycle_vote: the device header of the forward that rendered the images (the start of its
+                                      geometry buffer), or NULL.  A frame that overflowed its capacity (header.overflow != 0: invalid
+                                      outputs) casts no vote. */
+} DqoLifecycle;
+size_t dqo_map_lifecycle_workspace_bytes(int32_t P);
+int dqo_map_lifecycle_vote(const DqoLifecycle* step, const float* gt_color, const float* gt_depth, const float* render_color,
+                           const float* render_depth, const int32_t* depth_index, const int32_t* color_index, void* hipStream);
+int dqo_map_lifecycle_rows(const DqoLifecycle* step, void* hipStream);
 
 /* Batched dual-quadric residual over B independent (object, view) pairs: loss = 1 - IoU(obs, bbox(ellipsoid, P34)),
  * with gradients.  valid[b] = 0 when loss == 1 (the reference skips that Adam step). */
