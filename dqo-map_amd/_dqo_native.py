@@ -96,6 +96,17 @@ class DqoLifecycle(ctypes.Structure):
                 [("workspace_bytes", ctypes.c_size_t), ("stats", c_vp), ("render_header", c_vp)])
 
 
+class DqoGrowthSample(ctypes.Structure):
+    """dqo_growth_sample (ABI 5 symbols-only addition)."""
+    _fields_ = ([(n, c_i32) for n in ("W", "H", "first_frame", "uniform_sample_num", "capacity", "key_bits", "M", "identity_rotation")] +
+                [("seed", ctypes.c_uint64)] +
+                [(n, c_f) for n in ("add_transmission_thres", "add_depth_thres", "add_color_thres", "transmission_sample_ratio",
+                                    "error_sample_ratio", "init_opacity")] +
+                [(n, c_vp) for n in ("vertex", "normal", "color", "depth", "instance", "T", "render_depth", "render_color", "depth_index",
+                                     "xyz", "scales", "rotations", "opacity", "shs", "obj_id", "out_normal", "pixel", "header", "workspace")] +
+                [("workspace_bytes", ctypes.c_size_t)])
+
+
 EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_enable", "dqo_profile_collect", "dqo_map_activate",
            "dqo_map_loss_workspace_bytes", "dqo_map_loss_fwd_bwd", "dqo_map_ssim_workspace_bytes", "dqo_map_ssim_fwd_bwd", "dqo_map_adam_step", "dqo_adam_multi_dev", "dqo_map_attach_workspace_bytes",
            "dqo_map_attach_loss_fwd_bwd", "dqo_adam_multi", "dqo_accumulate_gaussian_error", "dqo_accumulate_gaussian_confidence", "dqo_rast_geom_bytes", "dqo_rast_image_bytes",
@@ -108,7 +119,8 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_rast_forward_prepare_params", "dqo_rast_forward_render_params", "dqo_rast_forward_async_params", "dqo_rast_backward_params",
            "dqo_icp_gauss_newton", "dqo_track_preprocess_workspace_bytes", "dqo_track_preprocess", "dqo_track_pyramid_pixels",
            "dqo_track_pyramid_workspace_bytes", "dqo_track_pyramid", "dqo_track_fill_model_depth", "dqo_track_p2p_workspace_bytes",
-           "dqo_track_p2p_loss", "dqo_map_lifecycle_workspace_bytes", "dqo_map_lifecycle_vote", "dqo_map_lifecycle_rows")
+           "dqo_track_p2p_loss", "dqo_map_lifecycle_workspace_bytes", "dqo_map_lifecycle_vote", "dqo_map_lifecycle_rows",
+           "dqo_growth_sample_workspace_bytes", "dqo_growth_sample")
 
 _lib = None
 
@@ -204,6 +216,9 @@ def lib():
         L.dqo_map_lifecycle_workspace_bytes.argtypes = [c_i32]
         L.dqo_map_lifecycle_vote.argtypes = [P(DqoLifecycle)] + [c_vp] * 7
         L.dqo_map_lifecycle_rows.argtypes = [P(DqoLifecycle), c_vp]
+        L.dqo_growth_sample_workspace_bytes.restype = ctypes.c_size_t
+        L.dqo_growth_sample_workspace_bytes.argtypes = [c_i32, c_i32]
+        L.dqo_growth_sample.argtypes = [P(DqoGrowthSample), c_vp]
         L.dqo_profile_enable.argtypes = [ctypes.c_int]
         L.dqo_profile_collect.argtypes = [P(DqoProfileEntry), ctypes.c_int, ctypes.c_int]
         if L.dqo_abi_version() != 5:
@@ -212,7 +227,7 @@ def lib():
         L.dqo_abi_sizeof.argtypes = [c_i32]
         for k, st in enumerate((DqoRastParams, DqoRastInputs, DqoRastOutputs, DqoRastCtx, DqoRastGrads, DqoRastHeader, DqoProfileEntry,
                                 DqoAdamStep, DqoLossTap, DqoObjectGate, DqoAdamTensor, DqoRastParamInputs, DqoRastParamGrads, None,
-                                DqoLifecycle)):  # (None: index 13 is unused)
+                                DqoLifecycle, DqoGrowthSample)):  # (None: index 13 is unused)
             if st is not None and L.dqo_abi_sizeof(k) != ctypes.sizeof(st):
                 raise RuntimeError(f"libdqoraster.so: struct {st.__name__} is {L.dqo_abi_sizeof(k)} bytes in the library, "
                                    f"{ctypes.sizeof(st)} in the binding")

@@ -81,6 +81,8 @@ size_t dqo_lifecycle_ws_bytes(int64_t P);
 int dqo_launch_lifecycle_vote(const DqoLifecycle* a, const float* gt_color, const float* gt_depth, const float* render, const float* depth,
                               const int32_t* depth_index, const int32_t* color_index, hipStream_t s);
 int dqo_launch_lifecycle_rows(const DqoLifecycle* a, hipStream_t s);
+size_t dqo_sample_ws_bytes(int64_t HW);
+int dqo_launch_growth_sample(const DqoGrowthSample* a, hipStream_t s);
 int dqo_launch_attach_pixels(int n, const float* xyz, const float* V, float fx, float fy, float cx, float cy, int W, int H,
                              const int32_t* pixel_object, int32_t* lin, int32_t* sparse, unsigned long long* tile_objects, hipStream_t s);
 int dqo_launch_attach_decide(int n, const float* xyz, const float* opacity, const int32_t* obj, const int32_t* lin, const int32_t* hit_index,
@@ -177,7 +179,7 @@ DQO_API size_t dqo_abi_sizeof(int32_t which) {
     static const size_t sz[] = {sizeof(DqoRastParams), sizeof(DqoRastInputs), sizeof(DqoRastOutputs), sizeof(DqoRastCtx), sizeof(DqoRastGrads),
                                 sizeof(DqoRastHeader), sizeof(DqoProfileEntry), sizeof(DqoAdamStep), sizeof(DqoLossTap), sizeof(DqoObjectGate),
                                 sizeof(DqoAdamTensor), sizeof(DqoRastParamInputs), sizeof(DqoRastParamGrads), 0 /* 13: unused */,
-                                sizeof(DqoLifecycle)};
+                                sizeof(DqoLifecycle), sizeof(DqoGrowthSample)};
     return (which >= 0 && which < (int32_t)(sizeof(sz) / sizeof(sz[0]))) ? sz[which] : 0;
 }
 DQO_API const char* dqo_last_error(void) { return g_err; }
@@ -739,6 +741,29 @@ DQO_API int dqo_map_lifecycle_rows(const DqoLifecycle* step, void* stream) {
     DQO_CHECK_ARG(step->stats != nullptr, "null stats");
     if (step->P == 0) return dqo_launch_zero_words(reinterpret_cast<uint32_t*>(step->stats), 8, (hipStream_t)stream);
     return dqo_launch_lifecycle_rows(step, (hipStream_t)stream);
+}
+
+// Mapping.temp_points_init (SLAM/multiprocess/mapper.py:1231-1347), sample_pixels (SLAM/utils.py:145-212) and
+// GaussianPointCloud.add_empty_points (SLAM/gaussian_pointcloud.py:445-517)
+DQO_API size_t dqo_growth_sample_workspace_bytes(int32_t W, int32_t H) {
+    return (W > 0 && H > 0 && (int64_t)W * H < (1ll << 31) / 3) ? dqo_sample_ws_bytes((int64_t)W * H) : 0;
+}
+
+DQO_API int dqo_growth_sample(const DqoGrowthSample* a, void* stream) {
+    DQO_CHECK_ARG(a != nullptr, "null DqoGrowthSample");
+    DQO_CHECK_ARG(a->W > 0 && a->H > 0 && (int64_t)a->W * a->H < (1ll << 31) / 3, "bad image size");
+    DQO_CHECK_ARG(a->uniform_sample_num >= 0 && a->capacity >= 0 && a->M >= 1, "bad uniform_sample_num / capacity / M");
+    DQO_CHECK_ARG(a->key_bits >= 1 && a->key_bits <= 32, "key_bits must be in [1, 32]");
+    DQO_CHECK_ARG(a->transmission_sample_ratio >= 0.f && a->error_sample_ratio >= 0.f, "negative sample ratio");
+    DQO_CHECK_ARG(a->vertex && a->normal && a->color && a->depth && a->header, "null frame image / header");
+    DQO_CHECK_ARG(a->first_frame || (a->T && a->render_depth && a->render_color && a->depth_index), "null render image");
+    DQO_CHECK_ARG(a->capacity == 0 || (a->xyz && a->scales && a->rotations && a->opacity && a->shs && a->out_normal && a->pixel),
+                  "null row buffer");
+    if (a->workspace == nullptr || a->workspace_bytes < dqo_sample_ws_bytes((int64_t)a->W * a->H)) {
+        dqo_set_error("growth sample workspace too small (%zu < %zu)", a->workspace_bytes, dqo_sample_ws_bytes((int64_t)a->W * a->H));
+        return DQO_ERR_WORKSPACE;
+    }
+    return dqo_launch_growth_sample(a, (hipStream_t)stream);
 }
 
 DQO_API size_t dqo_icp_workspace_bytes(void) { return dqo_icp_ws_bytes(); }

@@ -246,6 +246,7 @@ class FusedMapper:
         self._n_spare_stale = False  # maintain() freed rows on the device since _n_spare was read
         self._lifecycle = {}  # maintain(): lifecycle_step's vote words and workspace ("_lifecycle"), made anew when P changes
         self._maintain_ctx = None  # maintain(): the persistent buffers of its render (_maintain_render)
+        self._sample_ctx, self.sample_header = None, None  # sample_new(): the sampler's row buffers and workspace; its last header
         self._n_spare = self._spare_rows = 0  # spare rows now (host copy of the count: grow() keeps it up to date) / as reserve()d
         # DqoAdamStep.attach_gains: the attach term's two factors in device memory, rewritten in place by begin_mapping_call — a captured
         # graph survives a new mapping call
@@ -687,6 +688,61 @@ class FusedMapper:
         self._act_valid = False  # deleted rows' raw parameters changed
         self.activate()  # (a captured iteration starts from the activations of the current parameters)
         return stats
+
+    # configs/base.yaml:32-33, 47-52
+    SAMPLE_DEFAULTS = dict(uniform_sample_num=50000, add_transmission_thres=0.5, add_depth_thres=None, add_color_thres=0.1,
+                           transmission_sample_ratio=1.0, error_sample_ratio=0.05, init_opacity=0.99, xyz_factor=(1.0, 1.0, 0.1),
+                           capacity=None, key_bits=32)
+
+    @torch.no_grad()
+    def sample_new(self, frame_map, settings=None, *, seed, tick, first_frame=False, model_map=None, **thresholds):
+        """The first statement of a mapping frame — Mapping.temp_points_init (SLAM/multiprocess/mapper.py:1231-1347): get_render_output
+        (:1673-1688; the whole map rendered at the frame's camera on the persistent context maintain() keeps: colour, depth, T_map, depth
+        hit index) followed by dqo_mapgrowth.temp_points_init on the frame.  frame_map: the reference's dict (depth_map [H,W,1],
+        vertex_map_w, normal_map_w, color_map [H,W,3], optional instance_img [H,W,3]); settings: the frame's camera (default: the
+        mapper's); first_frame: the form without a render (:1234-1247).  thresholds: SAMPLE_DEFAULTS (add_depth_thres None = the
+        mapper's).  Returns what grow() takes, so a frame runs as grow(sample_new(...), ...) -> window -> maintain(...); the counts of the
+        call are left in self.sample_header.  With an object gate the mapper keeps the rows of the objects it holds: a shard's rows are
+        the unsharded mapper's rows with its objects' ids, in the same order — given the same render: both k are whole-frame counts, so a
+        shard passes the WHOLE map's render as model_map (dqo_mapgrowth.temp_points_init's dict; its own render shows its objects only).
+        The sampler's buffers are made once per capacity."""
+        import dqo_mapgrowth as mg
+        unknown = set(thresholds) - set(self.SAMPLE_DEFAULTS)
+        if unknown:
+            raise TypeError(f"FusedMapper.sample_new: unknown thresholds {sorted(unknown)}")
+        th = dict(self.SAMPLE_DEFAULTS, **thresholds)
+        if th["add_depth_thres"] is None:
+            th["add_depth_thres"] = self.add_depth_thres
+        dev = self.device
+        H, W = int(self.settings.image_height), int(self.settings.image_width)
+        if th["capacity"] is None:
+            th["capacity"] = mg.sample_capacity(H, W, first_frame, th["uniform_sample_num"], th["transmission_sample_ratio"], th["error_sample_ratio"])
+        with torch.cuda.device(dev):
+            if first_frame:
+                model_map = None
+            elif model_map is None:
+                st = self.settings if settings is None else _normalised_settings(settings, dev)
+                self.activate()
+                c = self._maintain_render(st)
+                if self.maintain_overflowed():  # (the frame outgrew the context an earlier frame sized: size a new one)
+                    c = self._maintain_render(st)
+                out = c["out"]
+                model_map = dict(render_color=out[0].permute(1, 2, 0), render_depth=out[1].permute(1, 2, 0),
+                                 render_depth_index=out[3].permute(1, 2, 0), render_transmission=out[6].permute(1, 2, 0))
+            s = self._sample_ctx
+            if s is None or s["key"] != (th["capacity"], self.M):
+                s = self._sample_ctx = dict(key=(th["capacity"], self.M), buffers=mg.sample_buffers(th["capacity"], self.M, dev),
+                                            workspace=torch.empty((N.lib().dqo_growth_sample_workspace_bytes(W, H),), dtype=torch.uint8, device=dev))
+            new, self.sample_header = mg.temp_points_init(frame_map, model_map, seed=seed, tick=tick, sh_coeffs=self.M, buffers=s["buffers"],
+                                                          workspace=s["workspace"], **th)
+            if self.gaussian_object is not None:
+                if "obj_id" not in new:
+                    raise RuntimeError("FusedMapper.sample_new: with an object gate the frame needs 'instance_img'")
+                held = torch.zeros((64,), dtype=torch.bool, device=dev)
+                held[(self.gaussian_object if self.alive is None else self.gaussian_object[self.alive.bool()]).long()] = True
+                keep = held[new["obj_id"].clamp(0, 63).long()] & (new["obj_id"] >= 0) & (new["obj_id"] < 64)
+                new = {k: v[keep] for k, v in new.items()}
+        return new
 
     @torch.no_grad()
     def grow(self, new, delete_mask=None, min_radius=0.001, max_radius=0.05, xyz_factor=(1.0, 1.0, 0.1), scale_factor=1.0,

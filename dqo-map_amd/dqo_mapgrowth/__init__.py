@@ -479,3 +479,100 @@ def lifecycle_step(state, tick, gt_color, gt_depth, render_color, render_depth, 
             N.check(lib.dqo_map_lifecycle_vote(ctypes.byref(step), *[N.ptr(a) for a in c], N.current_stream()))
         N.check(lib.dqo_map_lifecycle_rows(ctypes.byref(step), N.current_stream()))
     return stats
+
+
+# ---- map growth, the first statement: a frame's new Gaussians (csrc/map_sample.hip) --------------------------------------------------------
+SAMPLE_HEADER = ("mask_a", "mask_a_stripped", "mask_b", "mask_b_stripped", "k_a", "k_b", "rows", "overflow")
+_SAMPLE_ROWS = (("xyz", torch.float32, (3,)), ("scales", torch.float32, (3,)), ("rotations", torch.float32, (4,)), ("opacity", torch.float32, (1,)),
+                ("shs", torch.float32, None), ("obj_id", torch.int32, ()), ("normal", torch.float32, (3,)), ("pixel", torch.int32, ()))
+
+
+def sample_capacity(H, W, first_frame, uniform_sample_num, transmission_sample_ratio, error_sample_ratio):
+    """The most rows the statements of temp_points_init can give: uniform_sample_num on the first frame, otherwise
+    ceil(transmission_sample_ratio x uniform_sample_num) + ceil(error_sample_ratio x H x W)."""
+    import math
+    if first_frame:
+        return int(uniform_sample_num)
+    return int(math.ceil(transmission_sample_ratio * uniform_sample_num)) + int(math.ceil(error_sample_ratio * H * W))
+
+
+def sample_buffers(capacity, sh_coeffs, device):
+    """The caller-owned, fixed-capacity row buffers of dqo_growth_sample (+ its header), in the layout FusedMapper.grow(new=...) takes."""
+    buf = {name: torch.empty((capacity,) + ((sh_coeffs, 3) if shape is None else shape), dtype=dtype, device=device)
+           for name, dtype, shape in _SAMPLE_ROWS}
+    buf["header"] = torch.zeros((8,), dtype=torch.int32, device=device)
+    return buf
+
+
+def temp_points_init(frame_map, model_map=None, *, seed, tick, uniform_sample_num, add_transmission_thres, add_depth_thres, add_color_thres,
+                     transmission_sample_ratio, error_sample_ratio, init_opacity, xyz_factor, capacity=None, key_bits=32, sh_coeffs=16,
+                     buffers=None, workspace=None):
+    """Mapping.temp_points_init (SLAM/multiprocess/mapper.py:1231-1347) with sample_pixels (SLAM/utils.py:145-212) and
+    GaussianPointCloud.add_empty_points (SLAM/gaussian_pointcloud.py:445-517): one RGB-D frame (and a render of the map) -> the candidate
+    rows FusedMapper.grow(new=...) takes.  include/dqo_raster.h (DqoGrowthSample) restates every statement; the CPU torch.randperm of
+    utils.py:185 is replaced by the k smallest (hash32(seed, draw, pixel), pixel) pairs (csrc/dqo_sample_hash.h) — the same distribution,
+    a pure function of the arguments, rows in ascending pixel index, the transmission draw's before the error draw's.
+
+    frame_map: the reference's dict of GPU tensors — depth_map [H,W,1], vertex_map_w, normal_map_w, color_map [H,W,3], instance_img
+    [H,W,3] or None / absent.  model_map: render_transmission, render_depth [H,W,1], render_color [H,W,3] (a permuted view of the renderer's
+    [3,H,W] is taken as it is), render_depth_index int32 [H,W,1]; None = the first-frame form (mapper.py:1234-1247).
+    capacity: rows the buffers hold (default: sample_capacity(), the bound the statements give).  buffers / workspace: sample_buffers() /
+    a uint8 tensor of dqo_growth_sample_workspace_bytes(W, H) to reuse from call to call (any contents).
+    Returns (new, header): `new` = dict(xyz, scales, rotations, opacity, shs, normal, pixel; obj_id with an instance image) of views of
+    length header["rows"], header = dict over SAMPLE_HEADER plus tick.  One small device-to-host read (the header); raises on overflow."""
+    depth = frame_map["depth_map"]
+    dev = depth.device
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    first = model_map is None
+    f32 = lambda a, n: _sample_image(a, torch.float32, n, H, W)
+    inst = frame_map.get("instance_img")
+    images = dict(vertex=f32(frame_map["vertex_map_w"], 3), normal=f32(frame_map["normal_map_w"], 3), color=f32(frame_map["color_map"], 3),
+                  depth=f32(depth, 1), instance=None if inst is None else f32(inst, 3))
+    if not first:
+        rc = model_map["render_color"]
+        if tuple(rc.shape) != (H, W, 3):
+            raise RuntimeError(f"temp_points_init: render_color must be [{H}, {W}, 3]")
+        images.update(T=f32(model_map["render_transmission"], 1), render_depth=f32(model_map["render_depth"], 1),
+                      render_color=_sample_image(rc.permute(2, 0, 1), torch.float32, H * W, 3, 1),
+                      depth_index=_sample_image(model_map["render_depth_index"], torch.int32, 1, H, W))
+    if capacity is None:
+        capacity = sample_capacity(H, W, first, uniform_sample_num, transmission_sample_ratio, error_sample_ratio)
+    capacity = int(capacity)
+    lib = N.lib()
+    if buffers is None:
+        buffers = sample_buffers(capacity, sh_coeffs, dev)
+    for name, dtype, shape in _SAMPLE_ROWS:
+        b = buffers[name]
+        N.require_gpu(b)
+        if b.dtype != dtype or b.shape[0] < capacity or not b.is_contiguous() or (shape is None and tuple(b.shape[1:]) != (sh_coeffs, 3)):
+            raise RuntimeError(f"temp_points_init: buffers['{name}'] must be a contiguous {dtype} tensor of at least {capacity} rows")
+    need = lib.dqo_growth_sample_workspace_bytes(W, H)
+    if need == 0:
+        raise RuntimeError("temp_points_init: bad image size")
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    N.require_gpu(workspace)
+    identity = tuple(float(x) for x in xyz_factor) == (1.0, 1.0, 1.0)  # gaussian_pointcloud.py:470-474
+    args = N.DqoGrowthSample(W=W, H=H, first_frame=int(first), uniform_sample_num=int(uniform_sample_num), capacity=capacity,
+                             key_bits=int(key_bits), M=int(sh_coeffs), identity_rotation=int(identity), seed=int(seed) & (2 ** 64 - 1),
+                             add_transmission_thres=float(add_transmission_thres), add_depth_thres=float(add_depth_thres),
+                             add_color_thres=float(add_color_thres), transmission_sample_ratio=float(transmission_sample_ratio),
+                             error_sample_ratio=float(error_sample_ratio), init_opacity=float(init_opacity),
+                             out_normal=N.ptr(buffers["normal"]), header=N.ptr(buffers["header"]), workspace=N.ptr(workspace),
+                             workspace_bytes=workspace.numel(), **{k: N.ptr(v) for k, v in images.items()},
+                             **{k: N.ptr(buffers[k]) for k in ("xyz", "scales", "rotations", "opacity", "shs", "obj_id", "pixel")})
+    with torch.cuda.device(dev):
+        N.check(lib.dqo_growth_sample(ctypes.byref(args), N.current_stream()))
+        header = dict(zip(SAMPLE_HEADER, buffers["header"].tolist()), tick=int(tick))  # (the one device-to-host read)
+    if header["overflow"]:
+        raise RuntimeError(f"temp_points_init: the frame gives more than the {capacity} rows the buffers hold")
+    rows = header["rows"]
+    new = {name: buffers[name][:rows] for name, _, _ in _SAMPLE_ROWS if name != "obj_id" or inst is not None}
+    return new, header
+
+
+def _sample_image(a, dtype, channels, H, W):
+    N.require_gpu(a)
+    if a.dtype != dtype or a.numel() != channels * H * W:
+        raise RuntimeError(f"temp_points_init: images are {dtype} with {channels} x {H} x {W} elements, got {a.dtype} {tuple(a.shape)}")
+    return a.contiguous()

@@ -236,7 +236,7 @@ int dqo_abi_version(void);
 const char* dqo_last_error(void);
 /* sizeof() of the ABI structs as this library was compiled (a binding checks its own struct definitions against it):
  * 0 DqoRastParams, 1 DqoRastInputs, 2 DqoRastOutputs, 3 DqoRastCtx, 4 DqoRastGrads, 5 DqoRastHeader, 6 DqoProfileEntry,
- * 7 DqoAdamStep, 8 DqoLossTap, 9 DqoObjectGate, 10 DqoAdamTensor, 11 DqoRastParamInputs, 12 DqoRastParamGrads, 14 DqoLifecycle; 0 for
+ * 7 DqoAdamStep, 8 DqoLossTap, 9 DqoObjectGate, 10 DqoAdamTensor, 11 DqoRastParamInputs, 12 DqoRastParamGrads, 14 DqoLifecycle, 15 DqoGrowthSample; 0 for
  * any other index (13 stays unused: bindings probe it for the end of the parameter-form structs). */
 size_t dqo_abi_sizeof(int32_t which);
 
@@ -454,6 +454,67 @@ size_t dqo_map_lifecycle_workspace_bytes(int32_t P);
 int dqo_map_lifecycle_vote(const DqoLifecycle* step, const float* gt_color, const float* gt_depth, const float* render_color,
                            const float* render_depth, const int32_t* depth_index, const int32_t* color_index, void* hipStream);
 int dqo_map_lifecycle_rows(const DqoLifecycle* step, void* hipStream);
+
+/* Map growth, the first statement: Mapping.temp_points_init (SLAM/multiprocess/mapper.py:1231-1347) with sample_pixels (SLAM/utils.py:145-212)
+ * and GaussianPointCloud.add_empty_points (SLAM/gaussian_pointcloud.py:445-517) — from one RGB-D frame (and a render of the map) to the
+ * candidate rows FusedMapper.grow(new=...) takes.  Seven small launches, nothing read back, every k formed on the device.
+ *
+ * Masks (one thread per pixel; strip(p) = the normal's components sum to non-zero, and with an instance image its components too —
+ * what sample_pixels writes INTO its select_mask argument, utils.py:169-174):
+ *   first_frame:  draw 0 over depth > 0 (mapper.py:1235), k = uniform_sample_num.
+ *   otherwise:    draw 1 over trans = (T > add_transmission_thres) & (depth > 0) (:1251-1253),
+ *                   k = trunc((transmission_sample_ratio * (float(sum trans) / float(H * W))) * float(uniform_sample_num)), float32, the sum
+ *                   taken BEFORE the strip (:1254-1262);
+ *                 draw 2 over ((|depth - render_depth| > add_depth_thres & depth > 0 & depth_index > -1) | (mean3 |color - render_color| >
+ *                   add_color_thres & depth > 0 & T < add_transmission_thres)) & ~trans (:1292-1326), with trans AFTER the strip the
+ *                   redundant first sample_pixels call (:1269) left in it — unless draw 1's k is 0, when that call returns before it
+ *                   touches the mask (utils.py:155-156); k = trunc(float(sum mask) * error_sample_ratio) before the strip (:1327).
+ *   mean3 = ((a + b) + c) / 3; every k is clamped to its mask's count after the strip (utils.py:176-177).
+ * Selection (replaces the CPU torch.randperm of utils.py:185, same distribution): every pixel of a draw's stripped mask gets
+ *   key = hash32(seed, draw, pixel) & (2^key_bits - 1) (csrc/dqo_sample_hash.h); chosen are the k smallest (key, pixel) pairs; rows come out
+ *   in ascending pixel index, draw 1's before draw 2's (:1288, 1345).  A radix select over three digits of the key — never a sort.
+ * Rows (add_empty_points): normal / (|normal| + 1e-8) with |n| = sqrt(fma(z, z, fma(y, y, x * x))); a row whose normalised components sum
+ *   ((x + y) + z) to exactly 0 is dropped (:457); shs[row][0] = (color - 0.5) / C0, the other M - 1 coefficients 0; scales 1e-6; opacity
+ *   init_opacity; rotation (1, 0, 0, 0) with identity_rotation, else compute_rot((0, 0, 1), normal) (utils.py:246-251,
+ *   utils/general_utils.py:185-191, both + 1e-8 normalisations); obj_id = int(instance[0] * 255) (:497); pixel = y * W + x.
+ * Images are the reference's [H, W, C] layouts except render_color, which is the renderer's [3, H * W] planes.
+ * header (8 x int32, overwritten): 0 / 2 pixels of draw A / B's mask before the strip, 1 / 3 after it, 4 / 5 the clamped k of A / B,
+ *   6 rows written, 7 overflow (non-zero: more than `capacity` rows — rows beyond the capacity are not written).  A = draw 0 or 1, B = draw 2.
+ * workspace: dqo_growth_sample_workspace_bytes(W, H) bytes, any contents. */
+typedef struct DqoGrowthSample {
+    int32_t W, H;
+    int32_t first_frame;
+    int32_t uniform_sample_num;
+    int32_t capacity;            /* rows the output buffers hold */
+    int32_t key_bits;            /* 1..32 */
+    int32_t M;                   /* SH coefficients per row of shs */
+    int32_t identity_rotation;   /* non-zero: xyz_factor == (1, 1, 1) */
+    uint64_t seed;
+    float add_transmission_thres, add_depth_thres, add_color_thres;
+    float transmission_sample_ratio, error_sample_ratio, init_opacity;
+    const float* vertex;         /* [H*W,3] frame_map["vertex_map_w"] */
+    const float* normal;         /* [H*W,3] frame_map["normal_map_w"] */
+    const float* color;          /* [H*W,3] frame_map["color_map"] */
+    const float* depth;          /* [H*W]   frame_map["depth_map"] */
+    const float* instance;       /* [H*W,3] frame_map["instance_img"], or NULL */
+    const float* T;              /* [H*W]   model_map["render_transmission"]      (the four below: unused with first_frame) */
+    const float* render_depth;   /* [H*W] */
+    const float* render_color;   /* [3,H*W] */
+    const int32_t* depth_index;  /* [H*W] */
+    float* xyz;                  /* [capacity,3] */
+    float* scales;               /* [capacity,3] */
+    float* rotations;            /* [capacity,4] */
+    float* opacity;              /* [capacity] */
+    float* shs;                  /* [capacity,M,3] */
+    int32_t* obj_id;             /* [capacity], or NULL (written only with an instance image) */
+    float* out_normal;           /* [capacity,3] */
+    int32_t* pixel;              /* [capacity] */
+    int32_t* header;             /* [8] */
+    void* workspace;
+    size_t workspace_bytes;
+} DqoGrowthSample;
+size_t dqo_growth_sample_workspace_bytes(int32_t W, int32_t H);
+int dqo_growth_sample(const DqoGrowthSample* args, void* hipStream);
 
 /* Batched dual-quadric residual over B independent (object, view) pairs: loss = 1 - IoU(obs, bbox(ellipsoid, P34)),
  * with gradients.  valid[b] = 0 when loss == 1 (the reference skips that Adam step). */
