@@ -423,7 +423,7 @@ DQO_API int dqo_rast_backward_params(const DqoRastParams* p, const DqoRastInputs
                       "parameter form: null raw gradient output");
         DQO_CHECK_ARG(pin->rest == 0 || pg->dL_dfeatures_rest, "parameter form: null dL_dfeatures_rest with rest = %d", pin->rest);
     }
-    // the kernels' rows: the activated form's fields carry the raw gradients (gaussian_rows_pf_kernel applies the Jacobians)
+    // the kernels' rows: the activated form's fields carry the raw gradients (gaussian_rows_kernel<true> applies the Jacobians)
     DqoRastGrads g2 = *g;
     g2.dL_dsh = pg->dL_dfeatures_dc, g2.dL_dopacity = pg->dL_dopacity_raw, g2.dL_dscales = pg->dL_dscaling_raw;
     g2.dL_drotations = pg->dL_drotation_raw;

@@ -28,7 +28,7 @@ __device__ __forceinline__ K1Early k1_early(const DqoView& v, const float (&view
                                             const float* __restrict__ opacities, const float* __restrict__ shs,
                                             const float* __restrict__ colors_precomp, const int32_t* __restrict__ gobj, DqoGeomLayout& g,
                                             int32_t* __restrict__ radii_out, int32_t* __restrict__ n_touched_out,
-                                            const DqoShRest rest = DqoShRest{}) {
+                                            const DqoShRest rest) {
 #pragma clang fp contract(off)
     K1Early e;
     e.co = make_float4(0.f, 0.f, 0.f, 0.f), e.xy = e.co;

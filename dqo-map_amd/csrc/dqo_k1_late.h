@@ -65,7 +65,7 @@ __device__ __forceinline__ void k1_late_part(const DqoView& v, const float (&vie
                                              const int idx, const float px, const float py, const float pz, const float tvx, const float tvy,
                                              const float tvz, const float sx, const float sy, const float sz, const float (&Rm)[3][3],
                                              const float* __restrict__ shs, const float* __restrict__ colors_precomp, const DqoGeomLayout& g,
-                                             const DqoShRest rest = DqoShRest{}) {
+                                             const DqoShRest rest) {
 #pragma clang fp contract(off)
     // colour: computeColorFromSH, forward.cu:104-155
     float rgb[3];
@@ -159,7 +159,7 @@ __device__ __forceinline__ void k1_late_part(const DqoView& v, const float (&vie
 }
 
 template <int THREADS, bool PF = false>
-__device__ __forceinline__ void k1_late_block(const DqoK1Late& a, const DqoGeomLayout& g, const int block, const DqoShRest rest = DqoShRest{}) {
+__device__ __forceinline__ void k1_late_block(const DqoK1Late& a, const DqoGeomLayout& g, const int block, const DqoShRest rest) {
 #pragma clang fp contract(off)
     const int idx = block * THREADS + (int)threadIdx.x;
     if (idx >= a.v.P) return;

@@ -41,33 +41,73 @@ constexpr int K1_THREADS = 256;
 constexpr int K1_ITEMS = 1;
 
 // LATE: the late part runs here (one kernel); !LATE: it runs in the shadow of the per-tile sorts (tile_sort_wave_kernel<true>)
-template <bool LATE>
+// PF: the parameter form (dqo_rast_*_params, dqo_k1_early.h): scales / rotations / opacities are the raw parameters, shs is features_dc
+// (+ rest), and there is no colors_precomp
+template <bool LATE, bool PF>
 __global__ __launch_bounds__(K1_THREADS, K1_WAVES) void preprocess_kernel(const DqoView v, const float* __restrict__ means3D,
                                                                 const float* __restrict__ scales, const float* __restrict__ rotations,
                                                                 const float* __restrict__ opacities, const float* __restrict__ shs,
-                                                                const float* __restrict__ colors_precomp, const int32_t* __restrict__ tile_mask,
-                                                                DqoGeomLayout g, int32_t* __restrict__ radii_out, int32_t* __restrict__ n_touched_out,
+                                                                const DqoFormArg<!PF, const float* __restrict__> colors_arg,
+                                                                const int32_t* __restrict__ tile_mask, DqoGeomLayout g,
+                                                                int32_t* __restrict__ radii_out, int32_t* __restrict__ n_touched_out,
                                                                 uint32_t* __restrict__ zero_base, size_t zero_words, const int32_t* __restrict__ gobj,
-                                                                const int check_prezeroed) {
+                                                                const int check_prezeroed, const DqoFormArg<PF, DqoShRest> rest_arg) {
 #pragma clang fp contract(off)
-    constexpr bool PF = false;
-    const DqoShRest rest{};
-#include "preprocess_body.inc"
-}
-// the parameter form (dqo_rast_*_params, dqo_k1_early.h): scales / rotations / opacities are the raw parameters, shs is features_dc (+ rest)
-template <bool LATE>
-__global__ __launch_bounds__(K1_THREADS, K1_WAVES) void preprocess_pf_kernel(const DqoView v, const float* __restrict__ means3D,
-                                                                   const float* __restrict__ scales, const float* __restrict__ rotations,
-                                                                   const float* __restrict__ opacities, const float* __restrict__ shs,
-                                                                   const int32_t* __restrict__ tile_mask, DqoGeomLayout g,
-                                                                   int32_t* __restrict__ radii_out, int32_t* __restrict__ n_touched_out,
-                                                                   uint32_t* __restrict__ zero_base, size_t zero_words,
-                                                                   const int32_t* __restrict__ gobj, const int check_prezeroed,
-                                                                   const DqoShRest rest) {
-#pragma clang fp contract(off)
-    constexpr bool PF = true;
-    const float* const colors_precomp = nullptr;
-#include "preprocess_body.inc"
+    const float* colors_precomp = nullptr;
+    if constexpr (!PF) colors_precomp = colors_arg;
+    DqoShRest rest{};
+    if constexpr (PF) rest = rest_arg;
+    __shared__ uint32_t s_visible;
+    const int tid = threadIdx.x;
+    const int P = v.P;
+    float view[16], proj[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) view[i] = v.view[i], proj[i] = v.proj[i];
+    const float cam0 = v.campos[0], cam1 = v.campos[1], cam2 = v.campos[2];
+    __shared__ uint32_t s_cand;
+    if (tid == 0) s_visible = 0, s_cand = 0;
+    // (a frame_prezeroed frame still holds the previous frame's header: mark it "stage 1" until the sort kernels rewrite it)
+    if (blockIdx.x == 0 && tid == 0) g.header->stage = 1u;
+    // DqoRastCtx.frame_prezeroed is a promise of the caller (the previous frame on this ctx ended in dqo_rast_backward_adam, whose tail
+    // clears the per-frame scalars).  A broken promise — a forward-only render, dqo_rast_backward, an error return in between — would
+    // give wrong slot bases and doubled statistics without a sign: the first block looks at the words no kernel of THIS frame has
+    // touched yet (slot allocators, queue counters, loss-tap sums; not words 0, 1 of the lines, which this launch is adding to) and
+    // raises counters[8], which both header writers fold into header.overflow.
+    if (check_prezeroed && blockIdx.x == 0 && tid < DQO_SPREAD) {
+        const uint32_t* line = g.spread + (size_t)tid * 64;
+        uint32_t bad = line[2] | line[3] | line[4] | line[5];
+#pragma unroll
+        for (int i = 8; i < 16; i++) bad |= line[i];
+        if (tid < 8) bad |= g.counters[tid];
+        if (bad != 0u) atomicOr(&g.counters[8], 1u);
+    }
+    // this launch also zeroes the tile histogram + tile flags for bin_count_kernel (one contiguous range, a slice per block)
+    {
+        const size_t per = (zero_words + gridDim.x - 1) / gridDim.x;
+        const size_t z0 = (size_t)blockIdx.x * per, z1 = min(zero_words, z0 + per);
+        for (size_t i = z0 + tid; i < z1; i += K1_THREADS) zero_base[i] = 0u;
+    }
+    __syncthreads();
+
+    uint32_t nvis = 0, ncand = 0;
+#pragma unroll 1
+    for (int it = 0; it < K1_ITEMS; it++) {
+        const int idx = blockIdx.x * (K1_THREADS * K1_ITEMS) + it * K1_THREADS + tid;
+        if (idx >= P) continue;
+        const K1Early e = k1_early<LATE, PF>(v, view, proj, cam0, cam1, cam2, idx, means3D, scales, rotations, opacities, shs, colors_precomp, gobj,
+                                             g, radii_out, n_touched_out, rest);
+        const int radius = e.radius, rminx = e.rminx, rminy = e.rminy, rmaxx = e.rmaxx, rmaxy = e.rmaxy;
+        nvis += radius > 0 ? 1u : 0u;
+        ncand += (uint32_t)((rmaxx - rminx) * (rmaxy - rminy));
+    }
+    // visible count (statistics) and the number of (Gaussian, tile) pairs in the tile rects — the reference's num_rendered
+    // (rasterizer_impl.cu:303-309) and an upper bound of the instances the binning keeps
+    if (nvis) atomicAdd(&s_visible, nvis);
+    if (ncand) atomicAdd(&s_cand, ncand);
+    __syncthreads();
+    uint32_t* const my_line = g.spread + (size_t)(blockIdx.x % DQO_SPREAD) * 64;
+    if (tid == 0 && s_visible) atomicAdd(&my_line[0], s_visible);
+    if (tid == 0 && s_cand) atomicAdd(&my_line[1], s_cand);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -407,20 +447,71 @@ __device__ __forceinline__ void pair_sort_tile(const DqoBinLayout& bin, uint32_t
 // one block (two waves) per tile slot; the second wave only works on lists longer than 512 entries
 constexpr int SORTW_THREADS = 128;
 
-
-template <bool LATE>
+// LATE: + the late part of the per-Gaussian forward in extra blocks behind the sort blocks; PF (only with LATE): the parameter form
+// (dqo_rast_*_params), whose late part activates the raw parameters on load
+template <bool LATE, bool PF>
 __global__ __launch_bounds__(SORTW_THREADS, LATE ? SORTW_LATE_WAVES : SORTW_WAVES) void tile_sort_wave_kernel(int T, DqoImageLayout img, DqoBinLayout bin, DqoGeomLayout g,
-                                                                       int64_t capacity, int keep_order, int list_split, const DqoK1Late late) {
-    constexpr bool PF = false;
-    const DqoShRest rest{};
-#include "tile_sort_wave_body.inc"
-}
-// the parameter form (dqo_rast_*_params): the late part in the extra blocks activates the raw parameters on load
-__global__ __launch_bounds__(SORTW_THREADS, SORTW_LATE_WAVES) void tile_sort_wave_pf_kernel(int T, DqoImageLayout img, DqoBinLayout bin, DqoGeomLayout g,
-                                                                                           int64_t capacity, int keep_order, int list_split,
-                                                                                           const DqoK1Late late, const DqoShRest rest) {
-    constexpr bool LATE = true, PF = true;
-#include "tile_sort_wave_body.inc"
+                                                                       int64_t capacity, int keep_order, int list_split, const DqoK1Late late,
+                                                                       const DqoFormArg<PF, DqoShRest> rest_arg) {
+    static_assert(LATE || !PF, "the parameter form only differs in the late part");
+    DqoShRest rest{};
+    if constexpr (PF) rest = rest_arg;
+    if constexpr (LATE) {
+        if ((int)blockIdx.x >= late.first_block) {  // (block-uniform; the sort blocks come first: the longest lists start at once)
+            k1_late_block<SORTW_THREADS, PF>(late, g, (int)blockIdx.x - late.first_block, rest);
+            return;
+        }
+    }
+    __shared__ uint64_t s_key[2 * SORTP_RUN];
+    __shared__ uint32_t s_val[2 * SORTP_RUN];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int ti = blockIdx.x;
+    // the threshold the queue is built with, for the backward: its split kernel leaves to the queue exactly the lists that are in it
+    // (whatever the caller's backward context says)
+    if (ti == 0 && threadIdx.x == 0) g.counters[6] = (uint32_t)list_split;
+    const uint32_t tile = img.tile_order[ti];  // [8][T8] slots, unused ones hold ~0
+    if (tile >= (uint32_t)T) {
+        if (threadIdx.x == 0) img.slot_info[ti] = make_uint4(0xffffffffu, 0u, 0u, 0u);
+        return;
+    }
+    uint2 rg;
+    if (keep_order) {
+        const uint32_t c = img.tile_count[(size_t)tile * DQO_TSTRIDE];
+        // the slot tables are incomplete when the instance capacity ran out: every list is emptied, as tile_scan_kernel does; a
+        // list that outgrew its bucket is cut at the bucket (bin_count_kernel dropped the rest); both invalidate the frame
+        const bool lost = g.counters[7] != 0u;  // (bucket mode: a slot region ran out of its share, bin_count_kernel)
+        const uint32_t n_keep = lost ? 0u : min(c, (uint32_t)bin.bucket);
+        const uint32_t first = tile * (uint32_t)bin.bucket;
+        rg = make_uint2(n_keep ? first : 0u, n_keep ? first + n_keep : 0u);
+        if (threadIdx.x == 0) {
+            img.ranges[tile] = rg;
+            if (c) {
+                uint32_t* const line = g.spread + (size_t)(ti % DQO_SPREAD) * 64;
+                atomicMax(&line[2], c);
+                atomicAdd(&line[3], 1u);
+            }
+        }
+    } else {
+        rg = img.ranges[tile];
+    }
+    if (threadIdx.x == 0) img.slot_info[ti] = make_uint4(tile, rg.x, rg.y, 0u);  // (DqoImageLayout.slot_info: the blend kernels' one-round head)
+    const int n = (int)(rg.y - rg.x);
+    if (n <= 0) return;
+    // DqoRastCtx.list_split: the blend kernels' queue of lists shared between eight waves (longest first, like the one below)
+    if (list_split > 0 && n > list_split && threadIdx.x == 0) img.split_tiles[atomicAdd(&g.counters[4], 1u)] = tile;
+    if (n > SORTW_CAP) {  // tile_sort_kernel's: queued (the blocks run longest list first, so the queue is close to that order too)
+        if (threadIdx.x == 0) img.long_tiles[atomicAdd(&g.counters[1], 1u)] = tile;
+        return;
+    }
+    if (n > SORTP_RUN) {
+        pair_sort_tile(bin, rg.x, n, lane, wave, s_key, s_val);
+        return;
+    }
+    if (wave != 0) return;
+    if (n <= 64) wave_sort_tile<1>(bin, rg.x, n, lane);
+    else if (n <= 128) wave_sort_tile<2>(bin, rg.x, n, lane);
+    else if (n <= 256) wave_sort_tile<4>(bin, rg.x, n, lane);
+    else wave_sort_tile<8>(bin, rg.x, n, lane);
 }
 
 // Lists longer than SORTW_CAP: queued by tile_sort_wave_kernel (img.long_tiles, geom counters[1]) and sorted by a persistent grid of
@@ -440,19 +531,131 @@ constexpr int SORTL_RUN = SORTP_RUN;  // 512
 // frame left in the image buffer (any permutation of the tiles gives the same results), a list's range follows from its own
 // counter, and the frame statistics the header needs go to the spread lines (words 2..3), which tile_sort_kernel's first block
 // sums up (header_from_spread).
-
-template <bool LATE>
+// LATE, PF: as for tile_sort_wave_kernel
+template <bool LATE, bool PF>
 __global__ __launch_bounds__(SORT_THREADS, LATE ? 4 : 6) void tile_sort_kernel(int T, DqoImageLayout img, DqoBinLayout bin, DqoGeomLayout g, int64_t capacity,
-                                                                 int keep_order, const DqoK1Late late) {
-    constexpr bool PF = false;
-    const DqoShRest rest{};
-#include "tile_sort_body.inc"
-}
-// the parameter form (dqo_rast_*_params): the late part in the extra blocks activates the raw parameters on load
-__global__ __launch_bounds__(SORT_THREADS, 4) void tile_sort_pf_kernel(int T, DqoImageLayout img, DqoBinLayout bin, DqoGeomLayout g, int64_t capacity,
-                                                                      int keep_order, const DqoK1Late late, const DqoShRest rest) {
-    constexpr bool LATE = true, PF = true;
-#include "tile_sort_body.inc"
+                                                                 int keep_order, const DqoK1Late late, const DqoFormArg<PF, DqoShRest> rest_arg) {
+    static_assert(LATE || !PF, "the parameter form only differs in the late part");
+    DqoShRest rest{};
+    if constexpr (PF) rest = rest_arg;
+    if constexpr (LATE) {  // (the late part of the per-Gaussian forward behind the long-list sort blocks: dqo_k1_where == 2)
+        if ((int)blockIdx.x >= late.first_block) {
+            k1_late_block<SORT_THREADS, PF>(late, g, (int)blockIdx.x - late.first_block, rest);
+            return;
+        }
+    }
+    const uint32_t sort_blocks = LATE ? (uint32_t)late.first_block : gridDim.x;
+    __shared__ uint64_t s_keys[SORTL_SEG];
+    __shared__ uint32_t s_vals[SORTL_SEG];
+    if (keep_order && blockIdx.x == 0 && threadIdx.x < 64) dqo_header_from_spread(g, capacity, bin.bucket, (int)threadIdx.x);
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const uint32_t n_long = min(g.counters[1], (uint32_t)T);  // tiles queued by tile_sort_wave_kernel
+    for (uint32_t q = blockIdx.x; q < n_long; q += sort_blocks) {  // (block-uniform trip count; every helper ends with a barrier)
+    const uint32_t tile = img.long_tiles[q];
+    const uint2 rg = img.ranges[tile];
+    const int n = (int)(rg.y - rg.x);
+    uint4* gr = bin.recs + rg.x;
+    int n2 = 2 * SORTL_RUN;
+    while (n2 < n) n2 <<= 1;
+    const int seg_len = min(n2, SORTL_SEG);
+
+    // one ascending compare-exchange step of the network on the segment in LDS: `flip` pairs i with its mirror inside blocks of k
+    // (first step of a merge of two ascending halves), otherwise i with i + j
+    auto lds_step = [&](int k, int j, bool flip) {
+        for (int t = tid; t < seg_len / 2; t += SORT_THREADS) {
+            int i, p;
+            if (flip) {
+                const int h = k >> 1, blk = t / h, off = t - blk * h;
+                i = blk * k + off, p = blk * k + k - 1 - off;
+            } else {
+                i = 2 * j * (t / j) + (t % j), p = i + j;
+            }
+            const uint64_t a = s_keys[i], b = s_keys[p];
+            if (a > b) {
+                s_keys[i] = b, s_keys[p] = a;
+                const uint32_t va = s_vals[i];
+                s_vals[i] = s_vals[p], s_vals[p] = va;
+            }
+        }
+        __syncthreads();
+    };
+    // every run of the segment through the registers of one wave: full sort (first) or the last nine steps of a merge
+    auto runs_in_registers = [&](bool full_sort) {
+        for (int run = wave; run < seg_len / SORTL_RUN; run += SORT_THREADS / 64) {
+            uint64_t key[SORTP_E];
+            uint32_t val[SORTP_E];
+            const int base = run * SORTL_RUN + lane * SORTP_E;
+#pragma unroll
+            for (int r = 0; r < SORTP_E; r++) key[r] = s_keys[base + r], val[r] = s_vals[base + r];
+            if (full_sort) wave_bitonic<SORTP_E>(key, val, lane);
+            else wave_bitonic_phase<SORTP_E>(key, val, lane, 2 * SORTL_RUN);
+#pragma unroll
+            for (int r = 0; r < SORTP_E; r++) s_keys[base + r] = key[r], s_vals[base + r] = val[r];
+        }
+        __syncthreads();
+    };
+    auto load_segment = [&](int s0) {
+        for (int i = tid; i < seg_len; i += SORT_THREADS) {
+            const bool in = s0 + i < n;
+            const uint4 e = in ? gr[s0 + i] : make_uint4(~0u, ~0u, 0u, 0u);  // padding sorts behind every real key
+            s_keys[i] = ((uint64_t)e.y << 32) | e.x;
+            s_vals[i] = e.z;
+        }
+        __syncthreads();
+    };
+    auto store_segment = [&](int s0, bool final_lists) {
+        for (int i = tid; i < seg_len; i += SORT_THREADS) {
+            if (s0 + i >= n) continue;
+            if (final_lists) {
+                bin.point_list[rg.x + s0 + i] = (uint32_t)(s_keys[i] & 0xffffffffu);
+                bin.slot_list[rg.x + s0 + i] = s_vals[i];
+            } else {
+                gr[s0 + i] = make_uint4((uint32_t)s_keys[i], (uint32_t)(s_keys[i] >> 32), s_vals[i], 0u);
+            }
+        }
+        __syncthreads();
+    };
+    const int nseg = n2 / seg_len;
+    // ---- every segment sorted on its own ----
+    for (int sg = 0; sg < nseg; sg++) {
+        load_segment(sg * seg_len);
+        runs_in_registers(true);
+        for (int k = 2 * SORTL_RUN; k <= seg_len; k <<= 1) {
+            lds_step(k, 0, true);
+            for (int j = k >> 2; j >= SORTL_RUN; j >>= 1) lds_step(k, j, false);
+            runs_in_registers(false);
+        }
+        store_segment(sg * seg_len, nseg == 1);
+    }
+    // ---- merges across segments ----
+    for (int k = 2 * seg_len; k <= n2 && nseg > 1; k <<= 1) {
+        for (int j = k >> 1; j >= seg_len; j >>= 1) {  // global steps: the flip at distance k, then half cleaners down to one segment
+            const bool flip = j == (k >> 1);
+            for (int t = tid; t < n2 / 2; t += SORT_THREADS) {
+                int i, p;
+                if (flip) {
+                    const int blk = t / j, off = t - blk * j;
+                    i = blk * k + off, p = blk * k + k - 1 - off;
+                } else {
+                    i = 2 * j * (t / j) + (t % j), p = i + j;
+                }
+                if (p < n) {  // (a partner past the end is +infinity: nothing to exchange)
+                    const uint4 a = gr[i], b = gr[p];
+                    if ((((uint64_t)a.y << 32) | a.x) > (((uint64_t)b.y << 32) | b.x)) gr[i] = b, gr[p] = a;
+                }
+            }
+            __syncthreads();
+        }
+        const bool last = (k << 1) > n2;
+        for (int sg = 0; sg < nseg; sg++) {
+            if (sg * seg_len >= n) break;  // a segment of padding only
+            load_segment(sg * seg_len);
+            for (int j = seg_len >> 1; j >= SORTL_RUN; j >>= 1) lds_step(2 * j, j, false);
+            runs_in_registers(false);
+            store_segment(sg * seg_len, last);
+        }
+    }
+    }  // queue loop
 }
 
 // Zero fill of the per-frame scalars (header, slot allocator, statistics counters).  A kernel, not hipMemsetAsync: as a memset NODE
@@ -517,23 +720,20 @@ int dqo_launch_forward_prepare(const DqoRastParams* p, const DqoRastInputs* in, 
         const int grid = (p->P + per_block - 1) / per_block;
         const int32_t* gobj = ctx->object_gate ? ctx->object_gate->gaussian_object : nullptr;
         const int prez = ctx->frame_prezeroed != 0 ? 1 : 0;
-        if (pf != nullptr) {  // (the parameter form: no colors_precomp)
-            if (dqo_k1_where(p->P) != 0) {
-                DQO_LAUNCH("preprocess_pf_kernel", preprocess_pf_kernel<false>, dim3(grid), dim3(K1_THREADS), s, v, in->means3D, in->scales,
-                           in->rotations, in->opacities, in->shs, in->tile_mask, g, out->radii, out->n_touched, img.tile_count, zero_words, gobj,
-                           prez, *pf);
-            } else {
-                DQO_LAUNCH("preprocess_pf_kernel", preprocess_pf_kernel<true>, dim3(grid), dim3(K1_THREADS), s, v, in->means3D, in->scales,
-                           in->rotations, in->opacities, in->shs, in->tile_mask, g, out->radii, out->n_touched, img.tile_count, zero_words, gobj,
-                           prez, *pf);
-            }
-        } else if (dqo_k1_where(p->P) != 0) {
-            DQO_LAUNCH("preprocess_kernel", preprocess_kernel<false>, dim3(grid), dim3(K1_THREADS), s, v, in->means3D, in->scales, in->rotations,
-                       in->opacities, in->shs, in->colors_precomp, in->tile_mask, g, out->radii, out->n_touched, img.tile_count, zero_words, gobj, prez);
+        const DqoShRest rest = pf != nullptr ? *pf : DqoShRest{};
+#define DQO_K1(LATE, PF)                                                                                                                \
+    DQO_LAUNCH(PF ? "preprocess_pf_kernel" : "preprocess_kernel", (preprocess_kernel<LATE, PF>), dim3(grid), dim3(K1_THREADS), s, v,     \
+               in->means3D, in->scales, in->rotations, in->opacities, in->shs, dqo_form_arg<!PF>(in->colors_precomp), in->tile_mask, g, \
+               out->radii, out->n_touched, img.tile_count, zero_words, gobj, prez, dqo_form_arg<PF>(rest))
+        const bool late_here = dqo_k1_where(p->P) == 0;
+        if (pf != nullptr) {
+            if (late_here) DQO_K1(true, true);
+            else DQO_K1(false, true);
         } else {
-            DQO_LAUNCH("preprocess_kernel", preprocess_kernel<true>, dim3(grid), dim3(K1_THREADS), s, v, in->means3D, in->scales, in->rotations,
-                       in->opacities, in->shs, in->colors_precomp, in->tile_mask, g, out->radii, out->n_touched, img.tile_count, zero_words, gobj, prez);
+            if (late_here) DQO_K1(true, false);
+            else DQO_K1(false, false);
         }
+#undef DQO_K1
     }
     return DQO_OK;
 }
@@ -572,29 +772,30 @@ int dqo_launch_forward_render(const DqoRastParams* p, const DqoRastInputs* in, D
         DqoK1Late late;
         late.v = v, late.means3D = in->means3D, late.scales = in->scales, late.rotations = in->rotations, late.shs = in->shs;
         late.colors_precomp = in->colors_precomp, late.first_block = slots;
-        if (dqo_k1_where(p->P) == 1 && pf != nullptr) {
-            DQO_LAUNCH("tile_sort_wave_pf_kernel", tile_sort_wave_pf_kernel, dim3(slots + (p->P + SORTW_THREADS - 1) / SORTW_THREADS),
-                       dim3(SORTW_THREADS), s, T, img, bin, g, cap, keep_order, dqo_list_split(ctx), late, *pf);
-        } else if (dqo_k1_where(p->P) == 1) {
-            DQO_LAUNCH("tile_sort_wave_kernel", tile_sort_wave_kernel<true>, dim3(slots + (p->P + SORTW_THREADS - 1) / SORTW_THREADS),
-                       dim3(SORTW_THREADS), s, T, img, bin, g, cap, keep_order, dqo_list_split(ctx), late);
-        } else {
-            DQO_LAUNCH("tile_sort_wave_kernel", tile_sort_wave_kernel<false>, dim3(slots), dim3(SORTW_THREADS), s, T, img, bin, g, cap, keep_order,
-                       dqo_list_split(ctx), late);
-        }
+        // (only with the late part in its extra blocks does a sort kernel touch a parameter: only then is there a parameter-form one)
+        const DqoShRest rest = pf != nullptr ? *pf : DqoShRest{};
+        const int where = dqo_k1_where(p->P);
+        const int late_w = where == 1 ? (p->P + SORTW_THREADS - 1) / SORTW_THREADS : 0;  // extra blocks: the late part
+#define DQO_SORTW(LATE, PF)                                                                                                          \
+    DQO_LAUNCH(PF ? "tile_sort_wave_pf_kernel" : "tile_sort_wave_kernel", (tile_sort_wave_kernel<LATE, PF>), dim3(slots + late_w), \
+               dim3(SORTW_THREADS), s, T, img, bin, g, cap, keep_order, dqo_list_split(ctx), late, dqo_form_arg<PF>(rest))
+        if (where == 1 && pf != nullptr) DQO_SORTW(true, true);
+        else if (where == 1) DQO_SORTW(true, false);
+        else DQO_SORTW(false, false);
+#undef DQO_SORTW
         if (dqo_skip_long_sort(p, ctx)) {
             // no list can be longer than the per-tile sort reaches (a tile that outgrows its bucket is flagged): no long-list launch;
             // the frame's header — that launch's first block forms it in keep_order frames — comes from an extra block of the blend launch
-        } else if (dqo_k1_where(p->P) == 2 && pf != nullptr) {
-            late.first_block = SORT_GRID;
-            DQO_LAUNCH("tile_sort_pf_kernel", tile_sort_pf_kernel, dim3(SORT_GRID + (p->P + SORT_THREADS - 1) / SORT_THREADS), dim3(SORT_THREADS), s,
-                       T, img, bin, g, cap, keep_order, late, *pf);
-        } else if (dqo_k1_where(p->P) == 2) {
-            late.first_block = SORT_GRID;
-            DQO_LAUNCH("tile_sort_kernel", tile_sort_kernel<true>, dim3(SORT_GRID + (p->P + SORT_THREADS - 1) / SORT_THREADS), dim3(SORT_THREADS), s, T,
-                       img, bin, g, cap, keep_order, late);
         } else {
-            DQO_LAUNCH("tile_sort_kernel", tile_sort_kernel<false>, dim3(SORT_GRID), dim3(SORT_THREADS), s, T, img, bin, g, cap, keep_order, late);
+            if (where == 2) late.first_block = SORT_GRID;
+            const int late_l = where == 2 ? (p->P + SORT_THREADS - 1) / SORT_THREADS : 0;
+#define DQO_SORTL(LATE, PF)                                                                                                 \
+    DQO_LAUNCH(PF ? "tile_sort_pf_kernel" : "tile_sort_kernel", (tile_sort_kernel<LATE, PF>), dim3(SORT_GRID + late_l), \
+               dim3(SORT_THREADS), s, T, img, bin, g, cap, keep_order, late, dqo_form_arg<PF>(rest))
+            if (where == 2 && pf != nullptr) DQO_SORTL(true, true);
+            else if (where == 2) DQO_SORTL(true, false);
+            else DQO_SORTL(false, false);
+#undef DQO_SORTL
         }
     }
     // In a frame without the long-list sort launch the header is formed by an extra block of the BLEND launch: the copy and the event

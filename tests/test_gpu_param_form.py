@@ -286,9 +286,9 @@ def test_launches_per_pair_are_the_activated_entrys_pf_counterparts(torch_cuda):
 
 
 def test_every_placement_of_the_late_part_gives_the_same_bits(torch_cuda):
-    """DQO_K1_WHERE 0 / 1 / 2 (csrc/dqo_k1_late.h: preprocess_pf_kernel<true>, tile_sort_wave_pf_kernel, tile_sort_pf_kernel; 2 is the
+    """DQO_K1_WHERE 0 / 1 / 2 (csrc/dqo_k1_late.h: preprocess_kernel<true, true>, tile_sort_wave_kernel<true, true>, tile_sort_kernel<true, true>; 2 is the
     default above 786432 Gaussians): read once per process, so each placement runs in a child process and reports a digest of the
-    outputs and gradients of an exact-mode call and of three deferred calls (pooled: bin_count_pf_kernel)."""
+    outputs and gradients of an exact-mode call and of three deferred calls (pooled: bin_count_kernel<true, true>)."""
     import os, subprocess, sys
     code = r'''
 import hashlib, os, sys
