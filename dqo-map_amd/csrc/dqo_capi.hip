@@ -83,6 +83,10 @@ int dqo_launch_lifecycle_vote(const DqoLifecycle* a, const float* gt_color, cons
 int dqo_launch_lifecycle_rows(const DqoLifecycle* a, hipStream_t s);
 size_t dqo_sample_ws_bytes(int64_t HW);
 int dqo_launch_growth_sample(const DqoGrowthSample* a, hipStream_t s);
+size_t dqo_eval_ws_bytes(int64_t HW);
+int dqo_launch_eval_picture(int W, int H, const float* render, const float* gt_color, const float* depth, const float* gt_depth,
+                            const int32_t* depth_index, float min_depth, float max_depth, const DqoRastHeader* header, float* out_row,
+                            void* ws, hipStream_t s);
 int dqo_launch_attach_pixels(int n, const float* xyz, const float* V, float fx, float fy, float cx, float cy, int W, int H,
                              const int32_t* pixel_object, int32_t* lin, int32_t* sparse, unsigned long long* tile_objects, hipStream_t s);
 int dqo_launch_attach_decide(int n, const float* xyz, const float* opacity, const int32_t* obj, const int32_t* lin, const int32_t* hit_index,
@@ -764,6 +768,25 @@ DQO_API int dqo_growth_sample(const DqoGrowthSample* a, void* stream) {
         return DQO_ERR_WORKSPACE;
     }
     return dqo_launch_growth_sample(a, (hipStream_t)stream);
+}
+
+// eval_picture (SLAM/eval.py:38-188): psnr (:63), l1_loss (:70), the depth statements (:115-126)
+DQO_API size_t dqo_eval_picture_workspace_bytes(int32_t W, int32_t H) {
+    return (W > 0 && H > 0 && (int64_t)W * H < (1ll << 31) / 3) ? dqo_eval_ws_bytes((int64_t)W * H) : 0;
+}
+
+DQO_API int dqo_eval_picture(int32_t W, int32_t H, const float* render, const float* gt_color, const float* depth, const float* gt_depth,
+                             const int32_t* depth_index, float min_depth, float max_depth, const DqoRastHeader* render_header, float* out,
+                             int32_t row, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(W > 0 && H > 0 && (int64_t)W * H < (1ll << 31) / 3, "bad image size");
+    DQO_CHECK_ARG(render && gt_color && depth && gt_depth && depth_index && out, "null pointer");
+    DQO_CHECK_ARG(row >= 0, "bad row %d", row);
+    if (ws == nullptr || ws_bytes < dqo_eval_ws_bytes((int64_t)W * H)) {
+        dqo_set_error("eval_picture workspace too small (%zu < %zu)", ws_bytes, dqo_eval_ws_bytes((int64_t)W * H));
+        return DQO_ERR_WORKSPACE;
+    }
+    return dqo_launch_eval_picture(W, H, render, gt_color, depth, gt_depth, depth_index, min_depth, max_depth, render_header,
+                                   out + (size_t)8 * row, ws, (hipStream_t)stream);
 }
 
 DQO_API size_t dqo_icp_workspace_bytes(void) { return dqo_icp_ws_bytes(); }

@@ -1,0 +1,163 @@
+// Keyframe evaluation for gfx950: the numbers eval_picture reports for a rendered frame (SLAM/eval.py:38-188, called from slam.py:155,
+// 184 and metric.py), in ONE pass over the frame and ONE launch, nothing read back:
+//
+//     psnr_value = psnr(gt_image, image).mean()                          :63      utils/loss_utils.py:23-25, per channel, then the mean
+//     color_loss = l1_loss(gt_image, image)                              :70      utils/loss_utils.py:27-29
+//     valid_range_mask = (gt_depth > min_depth) & (gt_depth < max_depth) :116-117 gt_depth = 0 outside the range
+//     invalid_depth_mask = (index == -1) | (gt_depth == 0)               :120-123
+//     valid_pixel_ratio = valid_depth_mask.sum() / pixel_num             :124-125
+//     depth_loss = l1_loss(depth[valid], gt_depth[valid])                :126     NaN when nothing is valid (the mean of an empty selection)
+//
+// The reference forms every difference and every mean in float32 with torch's summation tree.  Here the differences of the float inputs
+// are formed in double (exact: a float difference, its square and its magnitude all fit) and summed in double, so what remains is the order
+// of the additions — at most H W 2^-53 relative — and one rounding to float32 per output.
+//
+// No float or double atomic anywhere: a thread adds its EV_PIX pixels in order, a wave its lanes by the xor butterfly (dqo_lane_xor on
+// the two halves of a double), a block its waves in order, and the block that takes the launch's last integer ticket (two levels, the
+// pattern of map_lifecycle.hip) adds the blocks' partials IN BLOCK-INDEX ORDER and writes the row: the same bits from run to run, whatever
+// order the blocks ran in.  The ticket words are handed back at zero, so the entry has no zero fill and is capturable in a hipGraph.
+#include "dqo_common.h"
+
+namespace {
+
+enum {
+    EV_LINES = 64,                           // ticket lines: word 0, and word 16 + 16 * line
+    EV_HEAD_WORDS = 16 + 16 * EV_LINES + 48,  // padded to a multiple of 256 bytes
+    EV_PIX = 4,                              // pixels per thread: a 1200 x 680 frame is 797 blocks — every CU busy, and a short last sum
+    EV_SUMS = 6,                             // squared colour error r, g, b | absolute colour error | absolute depth error | valid pixels
+    EV_STRIDE = 8,                           // doubles per block partial: one 64-byte line
+};
+static_assert(EV_HEAD_WORDS * 4 % 256 == 0, "workspace head layout");
+
+struct EvWorkspace {
+    int32_t* ticket;
+    double* partial;  // [blocks][EV_STRIDE]
+};
+
+inline size_t ev_blocks(int64_t HW) { return (size_t)((HW + 256 * EV_PIX - 1) / (256 * EV_PIX)); }
+
+template <int D>
+__device__ __forceinline__ double ev_lane_xor(double x, int lane) {
+    return __hiloint2double((int)dqo_lane_xor<D>((uint32_t)__double2hiint(x), lane), (int)dqo_lane_xor<D>((uint32_t)__double2loint(x), lane));
+}
+// wave64 double sum in the order of the xor butterfly 32, 16, 8, 4, 2, 1: every lane ends with the same total
+__device__ __forceinline__ double ev_wave_sum(double x, int lane) {
+    x += ev_lane_xor<32>(x, lane), x += ev_lane_xor<16>(x, lane), x += ev_lane_xor<8>(x, lane);
+    x += ev_lane_xor<4>(x, lane), x += ev_lane_xor<2>(x, lane), x += ev_lane_xor<1>(x, lane);
+    return x;
+}
+
+// Takes the block's ticket; true (for every thread of the block) in the block that took the last one, which then sees what every other
+// block wrote before its ticket.  The words it used are zero again.
+__device__ __forceinline__ bool ev_last_block(int32_t* ticket, int* s_last) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        const int grid = (int)gridDim.x;
+        const int lines = min((int)EV_LINES, max(1, grid / 16));
+        const int l = (int)blockIdx.x % lines;
+        const int on_line = (grid - l + lines - 1) / lines;  // blocks b < grid with b % lines == l
+        int32_t* const line = ticket + 16 + 16 * l;
+        bool last = atomicAdd(line, 1) == on_line - 1;
+        if (last) {
+            *line = 0;
+            __threadfence();  // (acquire what the line's other blocks released, release it to the block that takes word 0's last ticket)
+            last = atomicAdd(ticket, 1) == lines - 1;
+            if (last) *ticket = 0;
+        }
+        *s_last = last;
+    }
+    __syncthreads();
+    if (!*s_last) return false;
+    __threadfence();
+    return true;
+}
+
+__global__ __launch_bounds__(256) void eval_picture_kernel(int64_t HW, const float* __restrict__ render, const float* __restrict__ gt_color,
+                                                           const float* __restrict__ depth, const float* __restrict__ gt_depth,
+                                                           const int32_t* __restrict__ depth_index, float min_depth, float max_depth,
+                                                           const DqoRastHeader* __restrict__ header, EvWorkspace w, float* __restrict__ out) {
+    __shared__ double s_stage[256 * EV_STRIDE];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double a[EV_SUMS];
+#pragma unroll
+    for (int q = 0; q < EV_SUMS; q++) a[q] = 0.0;
+#pragma unroll
+    for (int k = 0; k < EV_PIX; k++) {
+        const int64_t i = ((int64_t)blockIdx.x * EV_PIX + k) * 256 + tid;
+        if (i < HW) {
+            const double dr = (double)gt_color[i] - (double)render[i];
+            const double dg = (double)gt_color[HW + i] - (double)render[HW + i];
+            const double db = (double)gt_color[2 * HW + i] - (double)render[2 * HW + i];
+            a[0] += dr * dr, a[1] += dg * dg, a[2] += db * db;
+            a[3] += (fabs(dr) + fabs(dg)) + fabs(db);
+            const float gd = gt_depth[i];
+            if (depth_index[i] != -1 && gd > min_depth && gd < max_depth) {  // (a NaN target is outside the range, as in the reference)
+                a[4] += fabs((double)depth[i] - (double)gd);
+                a[5] += 1.0;
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < EV_SUMS; q++) a[q] = ev_wave_sum(a[q], lane);
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < EV_SUMS; q++) s_stage[wave * EV_STRIDE + q] = a[q];
+    }
+    __syncthreads();
+    if (tid < EV_SUMS) {
+        double t = 0.0;
+        for (int v = 0; v < 4; v++) t += s_stage[v * EV_STRIDE + tid];
+        __hip_atomic_store(&w.partial[(size_t)blockIdx.x * EV_STRIDE + tid], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (!ev_last_block(w.ticket, &s_last)) return;
+    // the partials in block-index order: staged through LDS 256 blocks at a time (coalesced loads), sum q added by thread q
+    const int blocks = (int)gridDim.x;
+    double total = 0.0;
+    for (int base = 0; base < blocks; base += 256) {
+        const int m = min(256, blocks - base);
+        for (int j = tid; j < m * EV_STRIDE; j += 256)
+            s_stage[j] = __hip_atomic_load(&w.partial[(size_t)base * EV_STRIDE + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (tid < EV_SUMS)
+            for (int k = 0; k < m; k++) total += s_stage[k * EV_STRIDE + tid];
+        __syncthreads();
+    }
+    if (tid < EV_SUMS) s_stage[tid] = total;
+    __syncthreads();
+    if (tid != 0) return;
+    if (header != nullptr && header->overflow != 0u) {  // the render outgrew its context: its images are invalid, and so is the row
+#pragma unroll
+        for (int q = 0; q < 8; q++) out[q] = __int_as_float(0x7fc00000);
+        return;
+    }
+    const double n = (double)HW;
+    double psnr = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const double mse = s_stage[c] / n;
+        out[5 + c] = (float)mse;
+        psnr += 20.0 * log10(1.0 / sqrt(mse));  // (mse = 0: 1 / 0 = inf, log10(inf) = inf — the reference's value)
+    }
+    out[0] = (float)(psnr / 3.0);
+    out[1] = (float)(s_stage[3] / (3.0 * n));
+    out[2] = (float)(s_stage[4] / s_stage[5]);  // (nothing valid: 0 / 0 = NaN — torch's mean of an empty selection)
+    out[3] = (float)s_stage[5] / (float)n;      // valid_depth_mask.sum() / pixel_num: torch divides the two integers as float32
+}
+
+}  // namespace
+
+size_t dqo_eval_ws_bytes(int64_t HW) { return EV_HEAD_WORDS * 4 + dqo_align_up(ev_blocks(HW) * EV_STRIDE * sizeof(double), 256); }
+
+int dqo_launch_eval_picture(int W, int H, const float* render, const float* gt_color, const float* depth, const float* gt_depth,
+                            const int32_t* depth_index, float min_depth, float max_depth, const DqoRastHeader* header, float* out_row,
+                            void* ws, hipStream_t s) {
+    const int64_t HW = (int64_t)W * H;
+    EvWorkspace w;
+    w.ticket = (int32_t*)ws;
+    w.partial = (double*)((char*)ws + EV_HEAD_WORDS * 4);
+    DQO_LAUNCH("eval_picture_kernel", eval_picture_kernel, dim3((unsigned)ev_blocks(HW)), dim3(256), s, HW, render, gt_color, depth, gt_depth,
+               depth_index, min_depth, max_depth, header, w, out_row);
+    return DQO_OK;
+}

@@ -246,6 +246,7 @@ class FusedMapper:
         self._n_spare_stale = False  # maintain() freed rows on the device since _n_spare was read
         self._lifecycle = {}  # maintain(): lifecycle_step's vote words and workspace ("_lifecycle"), made anew when P changes
         self._maintain_ctx = None  # maintain(): the persistent buffers of its render (_maintain_render)
+        self._eval_tables, self._eval_ws = {}, None  # evaluate(): its [K,8] table per K, and dqo_eval's workspace
         self._sample_ctx, self.sample_header = None, None  # sample_new(): the sampler's row buffers and workspace; its last header
         self._n_spare = self._spare_rows = 0  # spare rows now (host copy of the count: grow() keeps it up to date) / as reserve()d
         # DqoAdamStep.attach_gains: the attach term's two factors in device memory, rewritten in place by begin_mapping_call — a captured
@@ -688,6 +689,42 @@ class FusedMapper:
         self._act_valid = False  # deleted rows' raw parameters changed
         self.activate()  # (a captured iteration starts from the activations of the current parameters)
         return stats
+
+    @torch.no_grad()
+    def evaluate(self, frames, min_depth=0.3, max_depth=5.0, out=None):
+        """How good the map is, over a keyframe set: eval_frame / eval_picture of the reference (SLAM/eval.py:38-188, slam.py:155,184,
+        metric.py) for every frame of `frames`, a list of (settings, gt_color [3,H,W], gt_depth [1,H,W] in metres); settings None = the
+        mapper's camera.  min_depth / max_depth: the valid range of the target depth (configs/base.yaml:39-40).  Per frame: the whole map
+        rendered on maintain()'s persistent context (_maintain_render: no row flags, no gate — what eval_frame renders with
+        `global_params`), dqo_eval.eval_picture into row k, the SSIM value into its slot 4.  Returns the float32 [K,8] device table
+        (dqo_eval.ROW: psnr, color_loss, depth_loss, valid_pixel_ratio, ssim, mse r/g/b; `out` or this mapper's own table for K,
+        overwritten by the next call with the same K); dqo_eval.eval_picture_dict(table[k]) reads a row.
+        The FIRST call for a (P, H, W) sizes the render's context from one 32-byte header read, exactly as maintain() does; after that a
+        call reads nothing back, allocates nothing and does not synchronise.  A frame that outgrows that context leaves a row of NaN; the
+        caller checks maintain_overflowed() where it can afford a read (it tells about the LAST frame rendered, and makes the next call
+        size a new context).  "ssim" is the single-scale SSIM of utils/loss_utils.py:60-100; the reference's MS-SSIM and LPIPS are not
+        built (dqo_eval)."""
+        import dqo_eval
+        if self.attach_count_reducer is not None:
+            raise NotImplementedError("FusedMapper.evaluate: a sharded mapper would need the whole map's render, a shard's shows its "
+                                      "objects only (DESIGN.md §6)")
+        dev, K = self.device, len(frames)
+        H, W = int(self.settings.image_height), int(self.settings.image_width)
+        if self._eval_ws is None:
+            self._eval_ws = dqo_eval.workspace(W, H, dev)
+        table = out
+        if table is None:
+            table = self._eval_tables.get(K)
+            if table is None:
+                table = self._eval_tables[K] = torch.empty((K, 8), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            self.activate()
+            for k, (settings, gt_color, gt_depth) in enumerate(frames):
+                c = self._maintain_render(self.settings if settings is None else _normalised_settings(settings, dev))
+                o = c["out"]
+                dqo_eval.eval_picture(dict(render=o[0], depth=o[1], depth_index_map=o[3]), gt_color, gt_depth, min_depth, max_depth, out=table,
+                                      row=k, workspace_buffer=self._eval_ws, render_header=c["geom"])
+        return table
 
     # configs/base.yaml:32-33, 47-52
     SAMPLE_DEFAULTS = dict(uniform_sample_num=50000, add_transmission_thres=0.5, add_depth_thres=None, add_color_thres=0.1,

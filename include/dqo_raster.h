@@ -516,6 +516,29 @@ typedef struct DqoGrowthSample {
 size_t dqo_growth_sample_workspace_bytes(int32_t W, int32_t H);
 int dqo_growth_sample(const DqoGrowthSample* args, void* hipStream);
 
+/* Keyframe evaluation: the metrics eval_picture reports for one rendered frame (SLAM/eval.py:38-188; called per frame from slam.py:155,
+ * 184 and from metric.py) in one launch, nothing read back.  Replaces, statement by statement:
+ *     psnr(gt_image, image).mean()                 eval.py:63   (utils/loss_utils.py:23-25: 20 log10(1 / sqrt(mse_c)) per channel)
+ *     l1_loss(gt_image, image)                     eval.py:70   (utils/loss_utils.py:27-29)
+ *     valid_range_mask, gt_depth[~mask] = 0        eval.py:116-117
+ *     invalid_depth_mask, valid_depth_mask         eval.py:120-123   valid = depth_index != -1 && min_depth < gt_depth < max_depth
+ *     valid_pixel_ratio                            eval.py:124-125   float32(valid count) / float32(H * W)
+ *     l1_loss(depth[valid], gt_depth[valid])       eval.py:126       NaN when no pixel is valid
+ * render, gt_color: [3, H*W] planes; depth, gt_depth (metres), depth_index: [H*W].  Every difference is formed in double from the float
+ * inputs and every sum is a double: lanes by a fixed butterfly, one partial per block, the partials added in block-index order by the block
+ * that takes the launch's last integer ticket.  No float atomic: the row is bitwise reproducible and independent of block scheduling.
+ * out + 8 * row receives eight floats: 0 psnr (+inf for identical images), 1 color_loss, 2 depth_loss, 3 valid_pixel_ratio,
+ *   4 NOT WRITTEN (the caller's SSIM: dqo_map_ssim_fwd_bwd in value-only mode), 5..7 the mean squared error of r, g, b.
+ * render_header (may be NULL): the device header of the forward that rendered the images (the start of its geometry buffer).  A frame
+ *   that overflowed its capacity (header.overflow != 0: invalid images) gets NaN in all eight slots, slot 4 included.
+ * workspace: dqo_eval_picture_workspace_bytes(W, H) bytes (0 for a bad size), ZERO when first used and then left to this call, which hands it
+ *   back ready for the next one — no zero fill per call, so the entry can be captured in a hipGraph.  Calls that share a workspace must be
+ *   ordered (one stream). */
+size_t dqo_eval_picture_workspace_bytes(int32_t W, int32_t H);
+int dqo_eval_picture(int32_t W, int32_t H, const float* render, const float* gt_color, const float* depth, const float* gt_depth,
+                     const int32_t* depth_index, float min_depth, float max_depth, const DqoRastHeader* render_header, float* out, int32_t row,
+                     void* workspace, size_t workspace_bytes, void* hipStream);
+
 /* Batched dual-quadric residual over B independent (object, view) pairs: loss = 1 - IoU(obs, bbox(ellipsoid, P34)),
  * with gradients.  valid[b] = 0 when loss == 1 (the reference skips that Adam step). */
 int dqo_quadric_iou_fwd_bwd(int32_t B, const float* axes, const float* R, const float* center, const float* P34,
