@@ -83,6 +83,12 @@ int dqo_launch_lifecycle_vote(const DqoLifecycle* a, const float* gt_color, cons
 int dqo_launch_lifecycle_rows(const DqoLifecycle* a, hipStream_t s);
 size_t dqo_sample_ws_bytes(int64_t HW);
 int dqo_launch_growth_sample(const DqoGrowthSample* a, hipStream_t s);
+size_t dqo_nn1_ws_bytes(int Q, int R);
+int dqo_launch_nn1(int Q, const float* q_xyz, const uint8_t* q_keep, int R, const float* r_xyz, const uint8_t* r_keep, const float* q_xform,
+                   const float* r_xform, float* dist2, int32_t* idx, void* ws, hipStream_t s);
+size_t dqo_eval_pcd_ws_bytes(int n_gt, int n_rec);
+int dqo_launch_eval_pcd(int n_gt, const float* gt_xyz, const uint8_t* gt_keep, int n_rec, const float* rec_xyz, const uint8_t* rec_keep,
+                        const float* rec_xform, int n_thres, const float* thres, float* out_row, void* ws, hipStream_t s);
 size_t dqo_eval_ws_bytes(int64_t HW);
 int dqo_launch_eval_picture(int W, int H, const float* render, const float* gt_color, const float* depth, const float* gt_depth,
                             const int32_t* depth_index, float min_depth, float max_depth, const DqoRastHeader* header, float* out_row,
@@ -787,6 +793,44 @@ DQO_API int dqo_eval_picture(int32_t W, int32_t H, const float* render, const fl
     }
     return dqo_launch_eval_picture(W, H, render, gt_color, depth, gt_depth, depth_index, min_depth, max_depth, render_header,
                                    out + (size_t)8 * row, ws, (hipStream_t)stream);
+}
+
+// the index word of a sorted point carries 25 index bits (knn.hip: FINE_IDX_BITS)
+static bool nn1_size_ok(int32_t n) { return n >= 0 && n < (1 << 25); }
+
+DQO_API size_t dqo_nn1_workspace_bytes(int32_t Q, int32_t R) { return nn1_size_ok(Q) && nn1_size_ok(R) ? dqo_nn1_ws_bytes(Q, R) : 0; }
+
+DQO_API int dqo_nn1(int32_t Q, const float* q_xyz, const uint8_t* q_keep, int32_t R, const float* r_xyz, const uint8_t* r_keep,
+                    const float* q_xform, const float* r_xform, float* dist2, int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(nn1_size_ok(Q) && nn1_size_ok(R), "bad size: at most 2^25 - 1 rows per set");
+    if (Q == 0) return DQO_OK;
+    DQO_CHECK_ARG(q_xyz && dist2, "null query / output");
+    DQO_CHECK_ARG(R == 0 || r_xyz, "null reference set");
+    if (ws == nullptr || ws_bytes < dqo_nn1_ws_bytes(Q, R)) {
+        dqo_set_error("nn1 workspace too small (%zu < %zu)", ws_bytes, dqo_nn1_ws_bytes(Q, R));
+        return DQO_ERR_WORKSPACE;
+    }
+    return dqo_launch_nn1(Q, q_xyz, q_keep, R, r_xyz, r_keep, q_xform, r_xform, dist2, idx, ws, (hipStream_t)stream);
+}
+
+// eval_pcd (SLAM/eval.py:190-282): accuracy, completion, chamfer distance, precision / recall / F1 per threshold
+DQO_API size_t dqo_eval_pcd_workspace_bytes(int32_t n_gt, int32_t n_rec) {
+    return nn1_size_ok(n_gt) && nn1_size_ok(n_rec) ? dqo_eval_pcd_ws_bytes(n_gt, n_rec) : 0;
+}
+
+DQO_API int dqo_eval_pcd(int32_t n_gt, const float* gt_xyz, const uint8_t* gt_keep, int32_t n_rec, const float* rec_xyz, const uint8_t* rec_keep,
+                         const float* rec_xform, int32_t n_thres, const float* thres_host, float* out_table, int32_t row, void* ws,
+                         size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(nn1_size_ok(n_gt) && nn1_size_ok(n_rec), "bad size: at most 2^25 - 1 rows per set");
+    DQO_CHECK_ARG((n_gt == 0 || gt_xyz) && (n_rec == 0 || rec_xyz) && out_table, "null pointer");
+    DQO_CHECK_ARG(n_thres >= 0 && n_thres <= 8 && (n_thres == 0 || thres_host), "at most 8 thresholds (got %d)", n_thres);
+    DQO_CHECK_ARG(row >= 0, "bad row %d", row);
+    if (ws == nullptr || ws_bytes < dqo_eval_pcd_ws_bytes(n_gt, n_rec)) {
+        dqo_set_error("eval_pcd workspace too small (%zu < %zu)", ws_bytes, dqo_eval_pcd_ws_bytes(n_gt, n_rec));
+        return DQO_ERR_WORKSPACE;
+    }
+    return dqo_launch_eval_pcd(n_gt, gt_xyz, gt_keep, n_rec, rec_xyz, rec_keep, rec_xform, n_thres, thres_host, out_table + (size_t)32 * row, ws,
+                               (hipStream_t)stream);
 }
 
 DQO_API size_t dqo_icp_workspace_bytes(void) { return dqo_icp_ws_bytes(); }

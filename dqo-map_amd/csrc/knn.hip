@@ -158,6 +158,16 @@ __device__ __forceinline__ uint64_t prep_morton64(uint64_t x) {  // bit i -> bit
     x = (x | (x << 2)) & 0x1249249249249249ull;
     return x;
 }
+// the 39-bit code of a position on the grid laid over `bbox`; a position outside the box takes the code of the nearest cell
+__device__ __forceinline__ uint64_t morton_fine_code(float x, float y, float z, const float* __restrict__ bbox) {
+#pragma clang fp contract(off)
+    const float mnx = bbox[0], mny = bbox[1], mnz = bbox[2], mxx = bbox[3], mxy = bbox[4], mxz = bbox[5];
+    const float top = (float)((1 << FINE_BITS) - 1);
+    const uint64_t cx = prep_morton64(min(f2u(((x - mnx) / (mxx - mnx)) * top), (uint32_t)top));
+    const uint64_t cy = prep_morton64(min(f2u(((y - mny) / (mxy - mny)) * top), (uint32_t)top));
+    const uint64_t cz = prep_morton64(min(f2u(((z - mnz) / (mxz - mnz)) * top), (uint32_t)top));
+    return cx | (cy << 1) | (cz << 2);
+}
 __global__ void morton_fine_kernel(int P, int P2, const float* __restrict__ xyz, const float* __restrict__ bbox, uint64_t* __restrict__ keys,
                                    const int32_t* __restrict__ group) {
 #pragma clang fp contract(off)
@@ -171,13 +181,7 @@ __global__ void morton_fine_kernel(int P, int P2, const float* __restrict__ xyz,
         keys[i] = (((1ull << (3 * FINE_BITS)) - 1ull) << FINE_IDX_BITS) | (uint64_t)i;
         return;
     }
-    const float mnx = bbox[0], mny = bbox[1], mnz = bbox[2], mxx = bbox[3], mxy = bbox[4], mxz = bbox[5];
-    const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-    const float top = (float)((1 << FINE_BITS) - 1);
-    const uint64_t cx = prep_morton64(min(f2u(((x - mnx) / (mxx - mnx)) * top), (uint32_t)top));
-    const uint64_t cy = prep_morton64(min(f2u(((y - mny) / (mxy - mny)) * top), (uint32_t)top));
-    const uint64_t cz = prep_morton64(min(f2u(((z - mnz) / (mxz - mnz)) * top), (uint32_t)top));
-    keys[i] = ((cx | (cy << 1) | (cz << 2)) << FINE_IDX_BITS) | (uint64_t)i;
+    keys[i] = (morton_fine_code(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], bbox) << FINE_IDX_BITS) | (uint64_t)i;
 }
 
 // ---- stable LSD radix sort, one 8-bit pass = three kernels ----
@@ -619,9 +623,188 @@ __global__ __launch_bounds__(256) void knn_query_wave_kernel(int Q, const float*
     }
 }
 
+
+// ---- dqo_nn1: the exact nearest REFERENCE of every QUERY when both sets are large and lie among each other ----------------------------
+// (eval_pcd, SLAM/eval.py:190-226: scipy's KDTree(a).query(b), one million points against one million.)  knn_query_wave_kernel puts a
+// wave on every query: right for few scattered queries, but a million queries among a million references repeat the same walk over the
+// level-1 boxes a million times.  Here the QUERIES are sorted too — by their Morton code on the REFERENCE's grid, so that a wave's 64
+// lanes hold 64 neighbouring queries — and the search is knn_scan_kernel's: one lane per query, a record (group of 64 boxes, box, run of
+// 64 points) is opened by the whole wave when any lane cannot exclude it, its candidates arrive by wave-uniform loads.  K = 1, so a lane
+// keeps one distance; it starts from the references either side of its own rank among the reference keys, and the box that rank falls
+// into is scanned first.  Every candidate a lane sees is a kept reference, every record it skips has dist_box_point > its best: the
+// result is the minimum of kbest's float expression over ALL kept references, bit for bit, whatever the order.
+// A dropped row (keep byte 0) of the reference set takes knn_build's group path (no group: outside the bounding box, sorted last, a far
+// sentinel, its records' group words 0), a kept one is group 0: bit 25 of its index word.  The same bit marks a kept query.
+constexpr uint32_t NN1_IDX_MASK = (1u << FINE_IDX_BITS) - 1u;
+
+// the point as it is searched: row i under the row-major 3x4 transform m (NULL: as stored) — open3d's rec_pc.transform(transform)
+__device__ __forceinline__ float4 nn1_point(const float* __restrict__ xyz, const float* __restrict__ m, int i) {
+#pragma clang fp contract(off)
+    const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+    if (m == nullptr) return make_float4(x, y, z, 0.f);
+    return make_float4((m[0] * x + m[1] * y) + m[2] * z + m[3], (m[4] * x + m[5] * y) + m[6] * z + m[7],
+                       (m[8] * x + m[9] * y) + m[10] * z + m[11], 0.f);
+}
+
+// reference side, only with a mask or a transform: the transformed rows and / or the group ids knn_build reads
+__global__ void nn1_prepare_ref_kernel(int R, const float* __restrict__ xyz, const uint8_t* __restrict__ keep, const float* __restrict__ xform,
+                                       float* __restrict__ txyz, int32_t* __restrict__ grp) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= R) return;
+    if (txyz != nullptr) {
+        const float4 p = nn1_point(xyz, xform, i);
+        txyz[3 * (size_t)i] = p.x, txyz[3 * (size_t)i + 1] = p.y, txyz[3 * (size_t)i + 2] = p.z;
+    }
+    if (grp != nullptr) grp[i] = keep[i] != 0 ? 0 : -1;
+}
+
+// query keys on the reference's grid; a dropped query sorts behind every kept one
+__global__ void nn1_query_keys_kernel(int Q, const float* __restrict__ xyz, const uint8_t* __restrict__ keep, const float* __restrict__ xform,
+                                      const float* __restrict__ ref_bbox, uint64_t* __restrict__ keys) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Q) return;
+    uint64_t code = (1ull << (3 * FINE_BITS)) - 1ull;
+    if (keep == nullptr || keep[i] != 0) {
+        const float4 p = nn1_point(xyz, xform, i);
+        code = morton_fine_code(p.x, p.y, p.z, ref_bbox);
+    }
+    keys[i] = (code << FINE_IDX_BITS) | (uint64_t)i;
+}
+
+__global__ void nn1_gather_query_kernel(int Q, const float* __restrict__ xyz, const uint8_t* __restrict__ keep, const float* __restrict__ xform,
+                                        const uint64_t* __restrict__ keys, float4* __restrict__ sorted_q) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Q) return;
+    const uint32_t src = (uint32_t)keys[i] & NN1_IDX_MASK;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    uint32_t w = src;
+    if (keep == nullptr || keep[src] != 0) p = nn1_point(xyz, xform, (int)src), w |= 1u << FINE_IDX_BITS;
+    p.w = __uint_as_float(w);
+    sorted_q[i] = p;
+}
+
+// kbest with K = 1; with a mask only a reference that carries a group counts (the sentinel rows do not)
+__device__ __forceinline__ void nn1_take(const float4 me, const float4 cand, bool masked, float& best, int& bidx) {
+#pragma clang fp contract(off)
+    const float dx = cand.x - me.x, dy = cand.y - me.y, dz = cand.z - me.z;
+    const float dist = dx * dx + dy * dy + dz * dz;
+    const uint32_t w = __float_as_uint(cand.w);
+    if ((!masked || (w >> FINE_IDX_BITS) != 0u) && dist < best) best = dist, bidx = (int)(w & NN1_IDX_MASK);
+}
+
+__global__ __launch_bounds__(256) void nn1_scan_kernel(int Q, const float4* __restrict__ sorted_q, const uint64_t* __restrict__ keys_q, int R,
+                                                       const float4* __restrict__ sorted_r, const uint64_t* __restrict__ keys_r,
+                                                       const float* __restrict__ boxes, const float* __restrict__ sub,
+                                                       const float* __restrict__ groups, int masked_i, float* __restrict__ dist2,
+                                                       int32_t* __restrict__ idx) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool masked = masked_i != 0;
+    const float4 me = q < Q ? sorted_q[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint32_t my_w = __float_as_uint(me.w);
+    const bool live = q < Q && (my_w >> FINE_IDX_BITS) != 0u;
+    float best = FLT_MAX;
+    int bidx = -1, rank = 0;
+    if (live) {  // the first reference key not below the query's code, and the two references either side of it
+        const uint64_t key = (keys_q[q] >> FINE_IDX_BITS) << FINE_IDX_BITS;
+        int lo = 0, hi = R;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (keys_r[mid] < key) lo = mid + 1;
+            else hi = mid;
+        }
+        rank = lo;
+        for (int i = max(0, rank - 2); i <= min(R - 1, rank + 1); i++) nn1_take(me, sorted_r[i], masked, best, bidx);
+    }
+    const int nb = (R + KNN_BOX - 1) / KNN_BOX, ng = (nb + 63) / 64;
+    auto scan_box = [&](int b) {  // (b wave-uniform: the records and the candidates come by wave-uniform loads)
+        const float* bx = boxes + 8 * (size_t)b;
+        if (masked && knn_record_groups(bx) == 0ull) return;  // nothing kept in it
+        const float d = dist_box_point(bx, me);
+        if (__ballot(live && !(d > best)) == 0) return;
+        const int lo = b * KNN_BOX, hi = min(R, lo + KNN_BOX);
+        for (int r0 = lo; r0 < hi; r0 += KNN_SUB) {
+            const float* sx = sub + 8 * (size_t)(r0 / KNN_SUB);
+            if (masked && knn_record_groups(sx) == 0ull) continue;
+            const float ds = dist_box_point(sx, me);
+            if (__ballot(live && !(ds > best)) == 0) continue;
+            // every lane takes every candidate, asked for the run or not (a candidate like any other; a lane without a query is not
+            // written).  A full run has a constant trip count: its wave-uniform loads are issued several at a time
+            if (r0 + KNN_SUB <= hi) {
+#pragma unroll 8
+                for (int i = 0; i < KNN_SUB; i++) nn1_take(me, sorted_r[r0 + i], masked, best, bidx);
+            } else {
+                for (int i = r0; i < hi; i++) nn1_take(me, sorted_r[i], masked, best, bidx);
+            }
+        }
+    };
+    if (__ballot(live) != 0) {
+        // dropped queries sort last, so lane 0 of a wave with a live lane is live: the box its rank falls into first
+        const int home = min(nb - 1, __builtin_amdgcn_readfirstlane(rank) / KNN_BOX);
+        scan_box(home);
+        for (int g = 0; g < ng; g++) {
+            const float* gx = groups + 8 * (size_t)g;
+            if (masked && knn_record_groups(gx) == 0ull) continue;
+            const float dg = dist_box_point(gx, me);
+            if (__ballot(live && !(dg > best)) == 0) continue;
+            const int b1 = min(nb, (g + 1) * 64);
+            for (int b = g * 64; b < b1; b++)
+                if (b != home) scan_box(b);
+        }
+    }
+    if (q < Q) {
+        const uint32_t dst = my_w & NN1_IDX_MASK;
+        dist2[dst] = live && bidx >= 0 ? best : FLT_MAX;
+        if (idx != nullptr) idx[dst] = live ? bidx : -1;
+    }
+}
+
+__global__ void nn1_fill_kernel(int Q, float* __restrict__ dist2, int32_t* __restrict__ idx) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Q) return;
+    dist2[i] = FLT_MAX;
+    if (idx != nullptr) idx[i] = -1;
+}
+
+struct Nn1Ws {
+    KnnWs r, q;
+    float* txyz;    // [R][3] the reference rows under ref_xform
+    int32_t* grp;   // [R] 0 = kept, -1 = dropped
+    size_t total;
+};
+inline Nn1Ws nn1_ws(void* base, int Q, int R) {
+    Nn1Ws w;
+    char* p = (char*)base;
+    w.r = knn_ws(p, R), p += w.r.total;
+    w.q = knn_ws(p, Q), p += w.q.total;
+    w.txyz = (float*)p, p += dqo_align_up(12 * (size_t)R, 256);
+    w.grp = (int32_t*)p, p += dqo_align_up(4 * (size_t)R, 256);
+    w.total = (size_t)(p - (char*)base);
+    return w;
+}
+
 }  // namespace
 
 size_t dqo_knn3_ws_bytes(int P) { return knn_ws(nullptr, P).total; }
+
+// Stable sort of w.keys[0, P) by the Morton code.  The code sits in bits 32..61 of the key: four stable 8-bit passes; the second key buffer
+// is `sorted` (16 B per point, written by the gather only after the sort); an even number of passes leaves the result in w.keys.
+// (fine codes: 39 bits above the 25-bit index — five passes; an even pass count leaves the result in w.keys, so a sixth pass
+// sorts by the top byte once more: a stable sort of sorted keys by a prefix of the key moves nothing but the buffer)
+static int knn_radix_sort(int P, const KnnWs& w, bool fine, hipStream_t s) {
+    const int nblk = (P + RDX_BLK - 1) / RDX_BLK;
+    uint64_t* a = w.keys;
+    uint64_t* b = reinterpret_cast<uint64_t*>(w.sorted);
+    const int n_pass = fine ? 6 : 4, shift0 = fine ? FINE_IDX_BITS : 32;
+    for (int pass = 0; pass < n_pass; pass++) {
+        const int shift = pass < 5 ? shift0 + 8 * pass : 56;
+        DQO_LAUNCH("radix_hist_kernel", radix_hist_kernel, dim3(nblk), dim3(RDX_T), s, P, a, shift, w.hist, nblk);
+        DQO_LAUNCH("radix_scan_kernel", radix_scan_kernel, dim3(256), dim3(256), s, w.hist, nblk, w.hist + (size_t)256 * nblk);
+        DQO_LAUNCH("radix_scatter_kernel", radix_scatter_kernel, dim3(nblk), dim3(RDX_T), s, P, a, b, shift, w.hist, nblk,
+                   w.hist + (size_t)256 * nblk);
+        std::swap(a, b);
+    }
+    return DQO_OK;
+}
 
 // bounding box -> Morton keys -> sort -> gather into Morton order (-> boxes)
 // fine: morton_fine_kernel's 39-bit codes (the query search's reference set) instead of the reference's 30-bit ones
@@ -636,23 +819,8 @@ static int knn_build(int P, const float* xyz, const KnnWs& w, bool with_boxes, h
     }
     if (fine) DQO_LAUNCH("morton_kernel", morton_fine_kernel, dim3((P2 + 255) / 256), dim3(256), s, P, P2, xyz, w.bbox, w.keys, group);
     else DQO_LAUNCH("morton_kernel", morton_kernel, dim3((P2 + 255) / 256), dim3(256), s, P, P2, xyz, w.bbox, w.keys);
-    {   // the Morton code sits in bits 32..61 of the key: four stable 8-bit passes; the second key buffer is `sorted` (16 B per point,
-        // written by the gather only after the sort); an even number of passes leaves the result in w.keys
-        const int nblk = (P + RDX_BLK - 1) / RDX_BLK;
-        uint64_t* a = w.keys;
-        uint64_t* b = reinterpret_cast<uint64_t*>(w.sorted);
-        // (fine codes: 39 bits above the 25-bit index — five passes; an even pass count leaves the result in w.keys, so a sixth pass
-        // sorts by the top byte once more: a stable sort of sorted keys by a prefix of the key moves nothing but the buffer)
-        const int n_pass = fine ? 6 : 4, shift0 = fine ? FINE_IDX_BITS : 32;
-        for (int pass = 0; pass < n_pass; pass++) {
-            const int shift = pass < 5 ? shift0 + 8 * pass : 56;
-            DQO_LAUNCH("radix_hist_kernel", radix_hist_kernel, dim3(nblk), dim3(RDX_T), s, P, a, shift, w.hist, nblk);
-            DQO_LAUNCH("radix_scan_kernel", radix_scan_kernel, dim3(256), dim3(256), s, w.hist, nblk, w.hist + (size_t)256 * nblk);
-            DQO_LAUNCH("radix_scatter_kernel", radix_scatter_kernel, dim3(nblk), dim3(RDX_T), s, P, a, b, shift, w.hist, nblk,
-                       w.hist + (size_t)256 * nblk);
-            std::swap(a, b);
-        }
-    }
+    const int rc = knn_radix_sort(P, w, fine, s);
+    if (rc) return rc;
     DQO_LAUNCH("gather_sorted_kernel", gather_sorted_kernel, dim3((P + 255) / 256), dim3(256), s, P, xyz, w.keys, w.sorted,
                fine ? ((1ull << FINE_IDX_BITS) - 1ull) : 0xffffffffull, group);
     if (with_boxes) {
@@ -691,5 +859,39 @@ int dqo_launch_knn3_query(int Q, const float* q_xyz, int R, const float* r_xyz, 
     else
         DQO_LAUNCH("knn_query_wave_kernel", knn_query_wave_kernel<false>, dim3(((size_t)Q * 64 + 255) / 256), dim3(256), s, Q, q_xyz, R, wr.sorted,
                    wr.boxes, wr.sub, wr.groups, dist2, idx3, bound2, q_group, group_box);
+    return DQO_OK;
+}
+
+size_t dqo_nn1_ws_bytes(int Q, int R) { return nn1_ws(nullptr, Q < 1 ? 1 : Q, R < 1 ? 1 : R).total; }
+
+int dqo_launch_nn1(int Q, const float* q_xyz, const uint8_t* q_keep, int R, const float* r_xyz, const uint8_t* r_keep, const float* q_xform,
+                   const float* r_xform, float* dist2, int32_t* idx, void* ws, hipStream_t s) {
+    if (Q == 0) return DQO_OK;
+    if (R == 0) {
+        DQO_LAUNCH("nn1_fill_kernel", nn1_fill_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, dist2, idx);
+        return DQO_OK;
+    }
+    const Nn1Ws w = nn1_ws(ws, Q, R);
+    const float* ref = r_xyz;
+    const int32_t* grp = nullptr;
+    if (r_keep != nullptr || r_xform != nullptr) {
+        DQO_LAUNCH("nn1_prepare_ref_kernel", nn1_prepare_ref_kernel, dim3((R + 255) / 256), dim3(256), s, R, r_xyz, r_keep, r_xform,
+                   r_xform != nullptr ? w.txyz : nullptr, r_keep != nullptr ? w.grp : nullptr);
+        if (r_xform != nullptr) ref = w.txyz;
+        if (r_keep != nullptr) grp = w.grp;
+    }
+    int rc = knn_build(R, ref, w.r, true, s, true, grp);
+    if (rc) return rc;
+    const int ns = (R + KNN_SUB - 1) / KNN_SUB, nb = (R + KNN_BOX - 1) / KNN_BOX, ng = (nb + 63) / 64;
+    DQO_LAUNCH("sub_minmax_kernel", sub_minmax_kernel, dim3((ns * 64 + 255) / 256), dim3(256), s, R, w.r.sorted, w.r.sub);
+    DQO_LAUNCH("group_minmax_kernel", group_minmax_kernel, dim3((ng * 64 + 255) / 256), dim3(256), s, nb, w.r.boxes, w.r.groups);
+    DQO_LAUNCH("nn1_query_keys_kernel", nn1_query_keys_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, q_xyz, q_keep, q_xform, w.r.bbox,
+               w.q.keys);
+    rc = knn_radix_sort(Q, w.q, true, s);
+    if (rc) return rc;
+    DQO_LAUNCH("nn1_gather_query_kernel", nn1_gather_query_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, q_xyz, q_keep, q_xform, w.q.keys,
+               w.q.sorted);
+    DQO_LAUNCH("nn1_scan_kernel", nn1_scan_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, w.q.sorted, w.q.keys, R, w.r.sorted, w.r.keys,
+               w.r.boxes, w.r.sub, w.r.groups, grp != nullptr ? 1 : 0, dist2, idx);
     return DQO_OK;
 }

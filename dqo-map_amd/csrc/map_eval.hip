@@ -16,7 +16,13 @@
 // the two halves of a double), a block its waves in order, and the block that takes the launch's last integer ticket (two levels, the
 // pattern of map_lifecycle.hip) adds the blocks' partials IN BLOCK-INDEX ORDER and writes the row: the same bits from run to run, whatever
 // order the blocks ran in.  The ticket words are handed back at zero, so the entry has no zero fill and is capturable in a hipGraph.
+#include <algorithm>
+
 #include "dqo_common.h"
+
+size_t dqo_nn1_ws_bytes(int Q, int R);
+int dqo_launch_nn1(int Q, const float* q_xyz, const uint8_t* q_keep, int R, const float* r_xyz, const uint8_t* r_keep, const float* q_xform,
+                   const float* r_xform, float* dist2, int32_t* idx, void* ws, hipStream_t s);
 
 namespace {
 
@@ -146,6 +152,128 @@ __global__ __launch_bounds__(256) void eval_picture_kernel(int64_t HW, const flo
     out[3] = (float)s_stage[5] / (float)n;      // valid_depth_mask.sum() / pixel_num: torch divides the two integers as float32
 }
 
+
+// ---- geometry evaluation: eval_pcd's numbers (SLAM/eval.py:190-282) from the two nearest-neighbour searches ---------------------------
+//     completion_ratio / accuracy_ratio   :190-201   np.mean(distances < dist_th)        -> R / P of :264-268, F1 :269
+//     accuracy / completion               :204-215   np.mean(distances)                  -> cm, :273-274
+//     chamfer_distance                    :218-226   the two means added (metres; the reference prints it, :253-254)
+// The reference builds a KDTree and queries it anew for every one of these statements; here d2_rec (every reconstructed point to its
+// nearest ground-truth point) and d2_gt (the other way round) come from two dqo_nn1 searches, and ONE launch reduces both: per kept row
+// sqrt((double)d2) and, per threshold, (double)d2 < (double)th * (double)th — both sides exact in double, so a count is an exact function
+// of the search's bits (the reference's strict '<' on distances).  Sums as in eval_picture_kernel: a thread's rows in order, lanes by the
+// butterfly, waves in order, one partial per block, the last block (integer ticket) adds the partials in block-index order.
+enum {
+    PC_ROWS = 4,           // rows of a set per thread
+    PC_THRES = 8,          // thresholds at most
+    PC_SUMS = 2 + PC_THRES,  // distance | kept rows | rows under threshold t
+    PC_STRIDE = 16,        // doubles per block partial: two 64-byte lines
+    PC_STAGE = 128,        // partials staged through LDS at a time by the last block
+    PC_SLOTS = 32,         // floats of a table row
+};
+
+struct PcThres {
+    float th[PC_THRES];
+};
+
+inline size_t pc_blocks(int n) { return ((size_t)n + 256 * PC_ROWS - 1) / (256 * PC_ROWS); }
+
+// blocks [0, blocks_rec) reduce d2_rec, the rest d2_gt
+__global__ __launch_bounds__(256) void eval_pcd_kernel(int n_rec, const float* __restrict__ d2_rec, const uint8_t* __restrict__ rec_keep, int n_gt,
+                                                       const float* __restrict__ d2_gt, const uint8_t* __restrict__ gt_keep, int n_thres,
+                                                       PcThres thres, int blocks_rec, EvWorkspace w, float* __restrict__ out) {
+    __shared__ double s_stage[PC_STAGE * PC_STRIDE];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool rec_side = (int)blockIdx.x < blocks_rec;
+    const int n = rec_side ? n_rec : n_gt, block = rec_side ? (int)blockIdx.x : (int)blockIdx.x - blocks_rec;
+    const float* __restrict__ d2 = rec_side ? d2_rec : d2_gt;
+    const uint8_t* __restrict__ keep = rec_side ? rec_keep : gt_keep;
+    double th2[PC_THRES];
+#pragma unroll
+    for (int t = 0; t < PC_THRES; t++) th2[t] = (double)thres.th[t] * (double)thres.th[t];
+    double a[PC_SUMS];
+#pragma unroll
+    for (int q = 0; q < PC_SUMS; q++) a[q] = 0.0;
+#pragma unroll
+    for (int k = 0; k < PC_ROWS; k++) {
+        const int64_t i = ((int64_t)block * PC_ROWS + k) * 256 + tid;
+        if (i < n && (keep == nullptr || keep[i] != 0)) {
+            const double v = (double)d2[i];
+            a[0] += sqrt(v);
+            a[1] += 1.0;
+#pragma unroll
+            for (int t = 0; t < PC_THRES; t++)
+                if (t < n_thres && v < th2[t]) a[2 + t] += 1.0;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < PC_SUMS; q++) a[q] = ev_wave_sum(a[q], lane);
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < PC_SUMS; q++) s_stage[wave * PC_STRIDE + q] = a[q];
+    }
+    __syncthreads();
+    if (tid < PC_SUMS) {
+        double t = 0.0;
+        for (int v = 0; v < 4; v++) t += s_stage[v * PC_STRIDE + tid];
+        __hip_atomic_store(&w.partial[(size_t)blockIdx.x * PC_STRIDE + tid], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (!ev_last_block(w.ticket, &s_last)) return;
+    // the partials of each side in block-index order, sum q added by thread q
+    const int blocks = (int)gridDim.x;
+    double tot_rec = 0.0, tot_gt = 0.0;
+    for (int base = 0; base < blocks; base += PC_STAGE) {
+        const int m = min((int)PC_STAGE, blocks - base);
+        for (int j = tid; j < m * PC_STRIDE; j += 256)
+            s_stage[j] = __hip_atomic_load(&w.partial[(size_t)base * PC_STRIDE + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (tid < PC_SUMS)
+            for (int k = 0; k < m; k++) {
+                if (base + k < blocks_rec) tot_rec += s_stage[k * PC_STRIDE + tid];
+                else tot_gt += s_stage[k * PC_STRIDE + tid];
+            }
+        __syncthreads();
+    }
+    if (tid < PC_SUMS) s_stage[tid] = tot_rec, s_stage[PC_STRIDE + tid] = tot_gt;
+    __syncthreads();
+    if (tid != 0) return;
+    const float nan = __int_as_float(0x7fc00000);
+    const double* rec = s_stage;
+    const double* gt = s_stage + PC_STRIDE;
+#pragma unroll
+    for (int q = 0; q < PC_SLOTS; q++) out[q] = nan;
+    if (rec[1] == 0.0 || gt[1] == 0.0) return;  // an empty set on either side: nothing to report
+    const double acc = rec[0] / rec[1], comp = gt[0] / gt[1];
+    out[0] = (float)(100.0 * acc);   // :273 (cm)
+    out[1] = (float)(100.0 * comp);  // :274
+    out[2] = (float)(acc + comp);    // :225 (metres)
+    out[3] = (float)n_thres;
+    for (int t = 0; t < n_thres; t++) {
+        const double P = 100.0 * (rec[2 + t] / rec[1]), R = 100.0 * (gt[2 + t] / gt[1]);  // :264-268
+        out[4 + 3 * t] = (float)P;
+        out[5 + 3 * t] = (float)R;
+        out[6 + 3 * t] = (float)(2.0 * P * R / (P + R));  // :269 (P + R = 0: 0 / 0 = NaN, numpy's value)
+    }
+}
+
+struct PcWorkspace {
+    EvWorkspace ev;
+    float *d2_rec, *d2_gt;
+    void* nn1;
+    size_t total;
+};
+inline PcWorkspace pc_ws(void* base, int n_gt, int n_rec) {
+    PcWorkspace w;
+    char* p = (char*)base;
+    w.ev.ticket = (int32_t*)p, p += EV_HEAD_WORDS * 4;
+    w.ev.partial = (double*)p, p += dqo_align_up((pc_blocks(n_rec) + pc_blocks(n_gt) + 1) * PC_STRIDE * sizeof(double), 256);
+    w.d2_rec = (float*)p, p += dqo_align_up(4 * (size_t)n_rec, 256);
+    w.d2_gt = (float*)p, p += dqo_align_up(4 * (size_t)n_gt, 256);
+    w.nn1 = p, p += std::max(dqo_nn1_ws_bytes(n_rec, n_gt), dqo_nn1_ws_bytes(n_gt, n_rec));  // the two searches run one after the other
+    w.total = (size_t)(p - (char*)base);
+    return w;
+}
+
 }  // namespace
 
 size_t dqo_eval_ws_bytes(int64_t HW) { return EV_HEAD_WORDS * 4 + dqo_align_up(ev_blocks(HW) * EV_STRIDE * sizeof(double), 256); }
@@ -159,5 +287,23 @@ int dqo_launch_eval_picture(int W, int H, const float* render, const float* gt_c
     w.partial = (double*)((char*)ws + EV_HEAD_WORDS * 4);
     DQO_LAUNCH("eval_picture_kernel", eval_picture_kernel, dim3((unsigned)ev_blocks(HW)), dim3(256), s, HW, render, gt_color, depth, gt_depth,
                depth_index, min_depth, max_depth, header, w, out_row);
+    return DQO_OK;
+}
+
+size_t dqo_eval_pcd_ws_bytes(int n_gt, int n_rec) { return pc_ws(nullptr, n_gt, n_rec).total; }
+
+int dqo_launch_eval_pcd(int n_gt, const float* gt_xyz, const uint8_t* gt_keep, int n_rec, const float* rec_xyz, const uint8_t* rec_keep,
+                        const float* rec_xform, int n_thres, const float* thres, float* out_row, void* ws, hipStream_t s) {
+    const PcWorkspace w = pc_ws(ws, n_gt, n_rec);
+    // accuracy: every reconstructed point to the ground truth (:204-208); completion: the other way round (:211-215)
+    int rc = dqo_launch_nn1(n_rec, rec_xyz, rec_keep, n_gt, gt_xyz, gt_keep, rec_xform, nullptr, w.d2_rec, nullptr, w.nn1, s);
+    if (rc) return rc;
+    rc = dqo_launch_nn1(n_gt, gt_xyz, gt_keep, n_rec, rec_xyz, rec_keep, nullptr, rec_xform, w.d2_gt, nullptr, w.nn1, s);
+    if (rc) return rc;
+    PcThres th;
+    for (int t = 0; t < PC_THRES; t++) th.th[t] = t < n_thres ? thres[t] : 0.f;
+    const int blocks_rec = (int)pc_blocks(n_rec), blocks = std::max(1, blocks_rec + (int)pc_blocks(n_gt));  // (two empty sets: one block writes the NaN row)
+    DQO_LAUNCH("eval_pcd_kernel", eval_pcd_kernel, dim3((unsigned)blocks), dim3(256), s, n_rec, w.d2_rec, rec_keep, n_gt, w.d2_gt, gt_keep, n_thres,
+               th, blocks_rec, w.ev, out_row);
     return DQO_OK;
 }

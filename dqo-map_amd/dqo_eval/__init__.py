@@ -14,13 +14,33 @@ AlexNet, :65-68).  Neither library exists on this platform, so neither value can
 Slot 4 / the "ssim" key here is the SINGLE-SCALE SSIM of utils/loss_utils.py:60-100 (the one the mapping loss uses), and there is no
 "lpips" key.  The picture dumps (`save_picture`) and the semantic / instance branches are not part of this either.
 
+Geometry evaluation — eval_pcd, SLAM/eval.py:190-282: accuracy, completion, chamfer distance and precision / recall / F1 per distance
+threshold of a reconstruction against a ground-truth point set — stays on the device as well:
+
+    eval_pcd(gt_points, rec_points, dist_thres, transform)  ->  float32 [32] on the device (PCD_ROW)
+    eval_pcd_dict(row, dist_thres)                          ->  the reference's `results` dict plus `chamfer` (the ONE host read)
+    nearest(query, ref)                                     ->  (dist2, idx): the exact nearest reference of every query (dqo_nn1)
+
+Two dense exact 1-NN searches (dqo_nn1, csrc/knn.hip) replace the 4 + 2 T scipy KDTree builds and single-threaded queries of the
+reference, one reduction launch (dqo_eval_pcd, csrc/map_eval.hip) forms every number from double sums added in a fixed order.
+
+What is NOT here: the reference's PREPARATION of the two sets — `trimesh.sample.sample_surface` on the ground-truth mesh (eval.py:247)
+and `np.random.choice` above `sample_nums` reconstructed points (:244), which it reads back from a PLY with open3d.  Neither trimesh nor
+open3d exists on this platform, so neither statement can be pinned against its source: the caller passes both sets as points.
+
 GPU only: there is no CPU path.
 """
+import ctypes
+
 import torch
 
 import _dqo_native as N
 
 ROW = ("psnr", "color_loss", "depth_loss", "valid_pixel_ratio", "ssim", "mse_r", "mse_g", "mse_b")
+
+PCD_THRES_MAX = 8
+PCD_ROW = (("accuracy", "completion", "chamfer", "n_thres") + tuple(f"{n}{t}" for t in range(PCD_THRES_MAX) for n in ("P", "R", "F1_"))
+           + ("unused28", "unused29", "unused30", "unused31"))
 
 _workspaces = {}
 
@@ -100,3 +120,133 @@ def eval_picture_dict(row_tensor):
     normal_loss (0, as eval.py:167), psnr, ssim (single-scale, see eval_picture), plus color_loss.  No `lpips` key: not built."""
     v = row_tensor.detach().reshape(-1)[:8].cpu().tolist()
     return {"valid_pixel_ratio": v[3], "depth_loss": v[2], "normal_loss": 0, "psnr": v[0], "ssim": v[4], "color_loss": v[1]}
+
+
+def _points(t, name):
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise RuntimeError(f"dqo_eval: {name} must be [N,3], got {tuple(t.shape)}")
+    return t.to(torch.float32).contiguous()  # (no copy, no launch, when it already is)
+
+
+def _keep(t, n, name):
+    if t is None:
+        return None
+    if t.numel() != n or t.dtype not in (torch.uint8, torch.bool):
+        raise RuntimeError(f"dqo_eval: {name} must be a uint8 / bool mask of {n} rows")
+    return t.reshape(-1).contiguous().view(torch.uint8)
+
+
+def _xform(t, dev, name):
+    """A [3,4] or [4,4] transform (tensor, numpy array or nested list) as 12 floats on the device; None stays None."""
+    if t is None:
+        return None
+    t = torch.as_tensor(t)
+    if tuple(t.shape) not in ((3, 4), (4, 4)):
+        raise RuntimeError(f"dqo_eval: {name} must be [3,4] or [4,4], got {tuple(t.shape)}")
+    if torch.is_tensor(t) and t.is_cuda:
+        return t[:3].to(torch.float32).contiguous()
+    return t[:3].to(torch.float32).contiguous().to(dev)  # (a host transform: one small upload, no read)
+
+
+def _workspace(key, nbytes, dev):
+    ws = _workspaces.get(key)
+    if ws is None:
+        ws = _workspaces[key] = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _dev_index(dev):
+    return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
+def nearest(query, ref, query_keep=None, ref_keep=None, query_transform=None, ref_transform=None, want_idx=True, workspace_buffer=None):
+    """The exact nearest reference of every query, both sets large (dqo_nn1): query [Q,3], ref [R,3] -> (dist2 float32 [Q], idx int32 [Q]
+    or None).  dist2 is the smallest float32 dx*dx + dy*dy + dz*dz over the kept references, idx a reference attaining it (ties:
+    arbitrary).  *_keep: uint8 / bool masks, 0 = the row is neither found nor searched for (a dropped query: FLT_MAX / -1); no kept
+    reference: FLT_MAX / -1 everywhere.  *_transform: [3,4] / [4,4], applied to the rows as they are loaded.  No host read, no
+    synchronisation; workspace_buffer: a uint8 tensor of dqo_nn1_workspace_bytes(Q, R) the caller keeps (default: one per device and
+    size, kept by this module — calls that share it must be on one stream)."""
+    N.require_gpu(query, ref, query_keep, ref_keep)
+    if not (query.is_cuda and ref.is_cuda):
+        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    lib, dev = N.lib(), query.device
+    query, ref = _points(query, "query"), _points(ref, "ref")
+    Q, R = int(query.shape[0]), int(ref.shape[0])
+    qk, rk = _keep(query_keep, Q, "query_keep"), _keep(ref_keep, R, "ref_keep")
+    qx, rx = _xform(query_transform, dev, "query_transform"), _xform(ref_transform, dev, "ref_transform")
+    n = lib.dqo_nn1_workspace_bytes(Q, R)
+    if n == 0:
+        raise RuntimeError(f"dqo_eval.nearest: bad sizes {Q}, {R} (at most 2^25 - 1 rows per set)")
+    ws = workspace_buffer if workspace_buffer is not None else _workspace(("nn1", _dev_index(dev), Q, R), n, dev)
+    dist2 = torch.empty((Q,), dtype=torch.float32, device=dev)
+    idx = torch.empty((Q,), dtype=torch.int32, device=dev) if want_idx else None
+    with torch.cuda.device(dev):
+        N.check(lib.dqo_nn1(Q, N.ptr(query), N.ptr(qk), R, N.ptr(ref), N.ptr(rk), N.ptr(qx), N.ptr(rx), N.ptr(dist2), N.ptr(idx), ws.data_ptr(),
+                            ws.numel(), N.current_stream()))
+    return dist2, idx
+
+
+def pcd_workspace(n_gt, n_rec, device):
+    """dqo_eval_pcd's workspace for these sizes as a uint8 tensor (zero when first used, handed back ready by every call)."""
+    n = N.lib().dqo_eval_pcd_workspace_bytes(int(n_gt), int(n_rec))
+    if n == 0:
+        raise RuntimeError(f"dqo_eval: bad point counts {n_gt}, {n_rec} (at most 2^25 - 1 rows per set)")
+    return torch.zeros((n,), dtype=torch.uint8, device=device)
+
+
+def eval_pcd(gt_points, rec_points, dist_thres=(0.03,), transform=None, gt_keep=None, rec_keep=None, out=None, row=0, workspace_buffer=None):
+    """eval_pcd (SLAM/eval.py:190-282) of a reconstruction against a ground-truth point set, on the device.
+
+    gt_points [G,3]: the ground-truth points (the reference samples them from the mesh with trimesh, :247 — not built here, see the
+    module docstring); rec_points [P,3]: the reconstructed points; transform: [3,4] / [4,4], applied to rec_points
+    (rec_pc.transform(transform), :241); dist_thres: up to 8 distances in metres (:229, :263); gt_keep / rec_keep: uint8 / bool masks,
+    0 = the row takes no part (the mapper's row buffers go in as stored).
+    Returns the float32 [32] device row (names: PCD_ROW)
+        0 accuracy (cm)   1 completion (cm)   2 chamfer (m)   3 n_thres   4+3t P   5+3t R   6+3t F1 of threshold t   (the rest NaN)
+    — a new tensor, or out[row] of a caller-owned float32 [K,32] table, whose other rows are not touched.  Nothing is read back and the
+    call does not synchronise; eval_pcd_dict does the single host read.  An empty (kept) set on either side gives a row of NaN; a
+    threshold no distance is under gives F1 = NaN, as numpy's division in the reference.  A row is bitwise reproducible.
+
+    workspace_buffer: a tensor of pcd_workspace(G, P, device) the caller keeps (default: one per device and sizes, kept by this module —
+    calls that share it must be on one stream).  GPU tensors only: a CPU tensor raises RuntimeError."""
+    N.require_gpu(gt_points, rec_points, gt_keep, rec_keep, out)
+    if not (gt_points.is_cuda and rec_points.is_cuda):
+        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    lib, dev = N.lib(), rec_points.device
+    gt, rec = _points(gt_points, "gt_points"), _points(rec_points, "rec_points")
+    G, P = int(gt.shape[0]), int(rec.shape[0])
+    gk, rk = _keep(gt_keep, G, "gt_keep"), _keep(rec_keep, P, "rec_keep")
+    xf = _xform(transform, dev, "transform")
+    thres = [float(t) for t in dist_thres]
+    if len(thres) > PCD_THRES_MAX:
+        raise RuntimeError(f"dqo_eval.eval_pcd: at most {PCD_THRES_MAX} thresholds, got {len(thres)}")
+    if out is None:
+        out, row = torch.empty((1, 32), dtype=torch.float32, device=dev), 0
+    if out.dim() != 2 or out.shape[1] != 32 or out.dtype != torch.float32 or not out.is_contiguous() or not 0 <= int(row) < out.shape[0]:
+        raise RuntimeError("dqo_eval.eval_pcd: out must be a contiguous float32 [K,32] table and row one of its rows")
+    ws = workspace_buffer
+    if ws is None:
+        key = ("pcd", _dev_index(dev), G, P)
+        ws = _workspaces.get(key)
+        if ws is None:
+            ws = _workspaces[key] = pcd_workspace(G, P, dev)
+    with torch.cuda.device(dev):
+        N.check(lib.dqo_eval_pcd(G, N.ptr(gt), N.ptr(gk), P, N.ptr(rec), N.ptr(rk), N.ptr(xf), len(thres), (ctypes.c_float * len(thres))(*thres),
+                                 out.data_ptr(), int(row), ws.data_ptr(), ws.numel(), N.current_stream()))
+    return out[int(row)]
+
+
+def eval_pcd_dict(row_tensor, dist_thres=(0.03,)):
+    """The reference's `results` dict (eval.py:263-281) from a device row — ONE host read.  Keys: accuracy, completion (cm),
+    "P (< th)", "R (< th)", "F1 (< th)" for every th of dist_thres (the thresholds the row was made with: a row holds their count, not
+    their values), plus chamfer (metres), which the reference only prints (:253-254)."""
+    v = row_tensor.detach().reshape(-1)[:32].cpu().tolist()
+    thres = list(dist_thres)
+    if v[3] == v[3] and int(v[3]) != len(thres):
+        raise RuntimeError(f"dqo_eval.eval_pcd_dict: the row was made with {int(v[3])} thresholds, got {len(thres)}")
+    results = {"accuracy": v[0], "completion": v[1]}
+    for name, off in (("P", 4), ("R", 5), ("F1", 6)):  # (the reference's order: every P, every R, every F1 — :279-281)
+        for t, th in enumerate(thres):
+            results["{} (< {})".format(name, th)] = v[off + 3 * t]
+    results["chamfer"] = v[2]
+    return results

@@ -726,6 +726,17 @@ class FusedMapper:
                                       row=k, workspace_buffer=self._eval_ws, render_header=c["geom"])
         return table
 
+    @torch.no_grad()
+    def evaluate_geometry(self, gt_points, dist_thres=(0.03,), transform=None, out=None, row=0):
+        """How good the map's GEOMETRY is against a ground-truth point set: eval_pcd of the reference (SLAM/eval.py:190-282) — accuracy,
+        completion, chamfer distance, precision / recall / F1 per threshold — through dqo_eval.eval_pcd.  The reconstruction is this
+        mapper's own `xyz` buffer with `alive` as the row mask: the points the reference reads back from the PLY it saved, without the
+        file, a copy or a host read.  gt_points [G,3]: the ground-truth points (sampling them from a mesh is the caller's, dqo_eval);
+        transform: [3,4] / [4,4] applied to the map's points (:241).  Returns the float32 [32] device row (dqo_eval.PCD_ROW; out[row] of
+        a caller-owned [K,32] table if given); dqo_eval.eval_pcd_dict reads it.  The workspace is dqo_eval's, per device and sizes."""
+        import dqo_eval
+        return dqo_eval.eval_pcd(gt_points, self.xyz.detach(), dist_thres, transform, rec_keep=self.alive, out=out, row=row)
+
     # configs/base.yaml:32-33, 47-52
     SAMPLE_DEFAULTS = dict(uniform_sample_num=50000, add_transmission_thres=0.5, add_depth_thres=None, add_color_thres=0.1,
                            transmission_sample_ratio=1.0, error_sample_ratio=0.05, init_opacity=0.99, xyz_factor=(1.0, 1.0, 0.1),

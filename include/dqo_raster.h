@@ -539,6 +539,44 @@ int dqo_eval_picture(int32_t W, int32_t H, const float* render, const float* gt_
                      const int32_t* depth_index, float min_depth, float max_depth, const DqoRastHeader* render_header, float* out, int32_t row,
                      void* workspace, size_t workspace_bytes, void* hipStream);
 
+/* Dense exact 1-NN between two large sets (scipy's KDTree(ref).query(query) of SLAM/eval.py:190-226, one million points against one
+ * million): dist2[i] = the smallest squared distance from query i to any kept reference, idx[i] (may be NULL) a reference attaining it,
+ * in the caller's numbering; which one of several equally distant references is arbitrary.  A pair's distance is dx*dx + dy*dy + dz*dz in
+ * float, left to right, never contracted: dist2 is a pure function of the inputs — bit for bit the minimum of that expression over all
+ * kept references.  dqo_knn3_query gives every query a wave (few scattered queries against a large map); here the queries are sorted
+ * along the reference's Morton grid and a wave's 64 lanes hold 64 neighbouring queries that share every box they open.
+ * query_keep / ref_keep: NULL = every row; else one byte per row, 0 = the row is neither found nor searched for (a dropped query gets
+ *   FLT_MAX / -1) — the mapper's row buffers go in as stored, spare and deleted rows included.  No kept reference (or R = 0): every
+ *   query gets FLT_MAX / -1.
+ * query_xform / ref_xform: NULL = identity; else 12 floats, a row-major 3x4 transform applied to a row as it is loaded, per output row
+ *   ((m0 * x + m1 * y) + m2 * z) + m3 in float, never contracted.
+ * At most 2^25 - 1 rows per set (dqo_nn1_workspace_bytes: 0 beyond).  No allocation, no synchronisation, nothing read back; the
+ * workspace needs no initialisation. */
+size_t dqo_nn1_workspace_bytes(int32_t Q, int32_t R);
+int dqo_nn1(int32_t Q, const float* query_xyz, const uint8_t* query_keep, int32_t R, const float* ref_xyz, const uint8_t* ref_keep,
+            const float* query_xform, const float* ref_xform, float* dist2, int32_t* idx, void* workspace, size_t workspace_bytes,
+            void* hipStream);
+
+/* Geometry evaluation: the metrics eval_pcd reports for a reconstruction against a ground-truth point set (SLAM/eval.py:190-282), nothing
+ * read back.  Two dqo_nn1 searches (rec -> gt under rec_xform, gt -> rec) and one reduction launch replace the 4 + 2 T KDTree builds and
+ * queries of the reference:
+ *     accuracy(), completion()                     eval.py:204-215, 273-274   100 * mean distance, in cm
+ *     chamfer_distance()                           eval.py:218-226            the two means added, in metres
+ *     accuracy_ratio(), completion_ratio(), F1     eval.py:190-201, 264-269   100 * share of rows with distance < th; 2 P R / (P + R)
+ * Per kept row d = sqrt((double)dist2), and the threshold test is (double)dist2 < (double)th * (double)th (exact on both sides: the
+ * reference's strict '<').  Means and shares are formed in double over the KEPT rows (gt_keep / rec_keep as in dqo_nn1) and rounded once to
+ * float; the sums are added in a fixed order (see dqo_eval_picture): a row is bitwise reproducible.
+ * out_table + 32 * row receives 32 floats: 0 accuracy, 1 completion, 2 chamfer, 3 n_thres, then for threshold t: 4 + 3 t precision P,
+ *   5 + 3 t recall R, 6 + 3 t F1 (NaN when P + R = 0, as numpy's division); every other slot NaN.  An empty kept set on either side: 32 NaN.
+ * thres_host: n_thres <= 8 floats in HOST memory, read before the call returns.  The ground-truth sampling and the random subsampling of
+ *   eval.py:236-248 (trimesh, open3d) are the caller's: both sets arrive as points.
+ * workspace: dqo_eval_pcd_workspace_bytes(n_gt, n_rec) bytes (0 for a bad size), ZERO when first used and then left to this call, which
+ *   hands it back ready for the next one (capturable in a hipGraph).  Calls that share a workspace must be ordered (one stream). */
+size_t dqo_eval_pcd_workspace_bytes(int32_t n_gt, int32_t n_rec);
+int dqo_eval_pcd(int32_t n_gt, const float* gt_xyz, const uint8_t* gt_keep, int32_t n_rec, const float* rec_xyz, const uint8_t* rec_keep,
+                 const float* rec_xform, int32_t n_thres, const float* thres_host, float* out_table, int32_t row, void* workspace,
+                 size_t workspace_bytes, void* hipStream);
+
 /* Batched dual-quadric residual over B independent (object, view) pairs: loss = 1 - IoU(obs, bbox(ellipsoid, P34)),
  * with gradients.  valid[b] = 0 when loss == 1 (the reference skips that Adam step). */
 int dqo_quadric_iou_fwd_bwd(int32_t B, const float* axes, const float* R, const float* center, const float* P34,
