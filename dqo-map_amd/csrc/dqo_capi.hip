@@ -71,6 +71,9 @@ int dqo_launch_track_p2p(int H, int W, const float* vertex0, const float* vertex
 int dqo_launch_tile_count(int W, int H, int mode, const uint8_t* mask_in, const float* T_map, uint8_t* mask_out, int32_t* tile_count,
                           int32_t* total, hipStream_t s);
 int dqo_launch_tile_color_error(int W, int H, const float* render, const float* gt, float* err_px, float* tile_sum, hipStream_t s);
+size_t dqo_window_masks_ws_bytes(int W, int H);
+int dqo_launch_window_masks(int W, int H, int mode, const float* T_map, const float* render, const float* gt, float tile_mask_ratio, int k,
+                            uint8_t* render_mask, int32_t* tile_mask, float* ratio_out, const DqoRastHeader* header, void* ws, hipStream_t s);
 int dqo_launch_growth_scales(int n, const float* xyz, const int32_t* obj, const float* radius, const int32_t* i_new, const float* d2_old,
                              const int32_t* i_old, const float* extra_radius, float reach2, float min_radius, float max_radius, float* scales,
                              uint8_t* invalid, hipStream_t s);
@@ -673,6 +676,32 @@ DQO_API int dqo_tile_color_error(int32_t W, int32_t H, const float* render, cons
                                  void* stream) {
     DQO_CHECK_ARG(W > 0 && H > 0 && render && gt && tile_sum, "bad size / null pointer");
     return dqo_launch_tile_color_error(W, H, render, gt, color_error, tile_sum, (hipStream_t)stream);
+}
+
+// Mapping.evaluate_render_range (SLAM/multiprocess/mapper.py:930-988) as called once per frame of the window by local_optimize (:549-555)
+// and global_optimization (:1173-1189): render mask (:945, :970-978), tile mask (transmission2tilemask SLAM/utils.py:752-762 / the top-k of
+// colorerror2tilemask :766-799) and render ratio (:987) of one frame, written where the captured graphs read them
+static bool window_masks_size_ok(int32_t W, int32_t H) { return W > 0 && H > 0 && (int64_t)W * H < (1ll << 31) / 3; }
+
+DQO_API size_t dqo_window_masks_workspace_bytes(int32_t W, int32_t H) { return window_masks_size_ok(W, H) ? dqo_window_masks_ws_bytes(W, H) : 0; }
+
+DQO_API int dqo_window_masks(int32_t W, int32_t H, int32_t mode, const float* T_map, const float* render, const float* gt, float tile_mask_ratio,
+                             int32_t k, uint8_t* render_mask, int32_t* tile_mask, float* ratio_out, const DqoRastHeader* render_header,
+                             void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(window_masks_size_ok(W, H), "bad image size");
+    DQO_CHECK_ARG(mode >= 0 && mode <= 2, "bad mode %d", mode);
+    DQO_CHECK_ARG(render_mask && tile_mask && ratio_out, "null output");
+    const int64_t tiles = (int64_t)((W + 15) / 16) * ((H + 15) / 16);
+    if (mode == 1) {
+        DQO_CHECK_ARG(render && gt, "the error mode needs render and gt");
+        DQO_CHECK_ARG(k >= 0 && k <= tiles, "k = %d outside [0, %lld]", k, (long long)tiles);
+    } else {
+        DQO_CHECK_ARG(T_map != nullptr, "null T_map");
+    }
+    DQO_CHECK_ARG(ws != nullptr && ws_bytes >= dqo_window_masks_ws_bytes(W, H), "window_masks workspace too small (%zu < %zu)", ws_bytes,
+                  dqo_window_masks_ws_bytes(W, H));
+    return dqo_launch_window_masks(W, H, mode, T_map, render, gt, tile_mask_ratio, k, render_mask, tile_mask, ratio_out, render_header, ws,
+                                   (hipStream_t)stream);
 }
 
 DQO_API int dqo_attach_pixels(int32_t n, const float* temp_xyz, const float* viewmatrix, float fx, float fy, float cx, float cy, int32_t W,

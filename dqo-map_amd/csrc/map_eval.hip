@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "dqo_common.h"
+#include "dqo_ticket.h"
 
 size_t dqo_nn1_ws_bytes(int Q, int R);
 int dqo_launch_nn1(int Q, const float* q_xyz, const uint8_t* q_keep, int R, const float* r_xyz, const uint8_t* r_keep, const float* q_xform,
@@ -27,13 +28,10 @@ int dqo_launch_nn1(int Q, const float* q_xyz, const uint8_t* q_keep, int R, cons
 namespace {
 
 enum {
-    EV_LINES = 64,                           // ticket lines: word 0, and word 16 + 16 * line
-    EV_HEAD_WORDS = 16 + 16 * EV_LINES + 48,  // padded to a multiple of 256 bytes
     EV_PIX = 4,                              // pixels per thread: a 1200 x 680 frame is 797 blocks — every CU busy, and a short last sum
     EV_SUMS = 6,                             // squared colour error r, g, b | absolute colour error | absolute depth error | valid pixels
     EV_STRIDE = 8,                           // doubles per block partial: one 64-byte line
 };
-static_assert(EV_HEAD_WORDS * 4 % 256 == 0, "workspace head layout");
 
 struct EvWorkspace {
     int32_t* ticket;
@@ -51,32 +49,6 @@ __device__ __forceinline__ double ev_wave_sum(double x, int lane) {
     x += ev_lane_xor<32>(x, lane), x += ev_lane_xor<16>(x, lane), x += ev_lane_xor<8>(x, lane);
     x += ev_lane_xor<4>(x, lane), x += ev_lane_xor<2>(x, lane), x += ev_lane_xor<1>(x, lane);
     return x;
-}
-
-// Takes the block's ticket; true (for every thread of the block) in the block that took the last one, which then sees what every other
-// block wrote before its ticket.  The words it used are zero again.
-__device__ __forceinline__ bool ev_last_block(int32_t* ticket, int* s_last) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        const int grid = (int)gridDim.x;
-        const int lines = min((int)EV_LINES, max(1, grid / 16));
-        const int l = (int)blockIdx.x % lines;
-        const int on_line = (grid - l + lines - 1) / lines;  // blocks b < grid with b % lines == l
-        int32_t* const line = ticket + 16 + 16 * l;
-        bool last = atomicAdd(line, 1) == on_line - 1;
-        if (last) {
-            *line = 0;
-            __threadfence();  // (acquire what the line's other blocks released, release it to the block that takes word 0's last ticket)
-            last = atomicAdd(ticket, 1) == lines - 1;
-            if (last) *ticket = 0;
-        }
-        *s_last = last;
-    }
-    __syncthreads();
-    if (!*s_last) return false;
-    __threadfence();
-    return true;
 }
 
 __global__ __launch_bounds__(256) void eval_picture_kernel(int64_t HW, const float* __restrict__ render, const float* __restrict__ gt_color,

@@ -247,6 +247,8 @@ class FusedMapper:
         self._lifecycle = {}  # maintain(): lifecycle_step's vote words and workspace ("_lifecycle"), made anew when P changes
         self._maintain_ctx = None  # maintain(): the persistent buffers of its render (_maintain_render)
         self._eval_tables, self._eval_ws = {}, None  # evaluate(): its [K,8] table per K, and dqo_eval's workspace
+        # refresh_window(): its [K] ratio table per K, dqo_window_masks' workspace, the uint8 [P] row flags of its render (per P)
+        self._window_ratios, self._window_ws, self._window_flags = {}, None, None
         self._sample_ctx, self.sample_header = None, None  # sample_new(): the sampler's row buffers and workspace; its last header
         self._n_spare = self._spare_rows = 0  # spare rows now (host copy of the count: grow() keeps it up to date) / as reserve()d
         # DqoAdamStep.attach_gains: the attach term's two factors in device memory, rewritten in place by begin_mapping_call — a captured
@@ -530,6 +532,7 @@ class FusedMapper:
                 setattr(self, b.name, make(b.shape(self.P), dtype=torch.float32, device=self.device))
         self._attach_n, self._act_valid = 0, False
         self._lifecycle, self._maintain_ctx = {}, None
+        self._window_flags = None
         self._drop_graphs()
 
     @torch.no_grad()
@@ -597,9 +600,10 @@ class FusedMapper:
     # configs/base.yaml:51-52, 59-60 and the `delete_thresh = 10` of mapper.py:1092
     MAINTAIN_DEFAULTS = dict(stable_confidence_thres=500.0, unstable_time_window=200, add_color_thres=0.1, add_depth_thres=None, delete_thresh=10)
 
-    def _maintain_render(self, st):
+    def _maintain_render(self, st, row_flags=None):
         """The whole map (both clouds: no row flags, no object gate; spare rows are parked and transparent) rendered at camera `st` through
         the C ABI into persistent buffers: the op's nine outputs c["out"] (0 colour, 1 depth, 2 colour hit index, 3 depth hit index).
+        row_flags (refresh_window): DqoRastInputs.row_flags, uint8 [P] — its DQO_ROW_HIDDEN rows are not rendered; None: every row.
         The first call measures the frame (prepare, one header read, render) and sizes the instance capacity at 1.5 x its candidate
         pairs + 4096; later calls are ONE dqo_rast_forward call on those buffers — no header copy, no event, no allocation."""
         lib, dev, P, M = N.lib(), self.device, self.P, self.M
@@ -616,7 +620,8 @@ class FusedMapper:
             c = dict(key=(P, H, W), out=out, outputs=outputs, geom=torch.empty((lib.dqo_rast_geom_bytes(P, W, H),), **u8),
                      img=torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8))
         params = dgr._params(st, P, M)
-        inputs = dgr._inputs(st, self.xyz, self.shs, self._empty, self.opacity, self.scales, self.rotations, self._empty, self.tile_mask)
+        inputs = dgr._inputs(st, self.xyz, self.shs, self._empty, self.opacity, self.scales, self.rotations, self._empty, self.tile_mask,
+                             row_flags=row_flags)
         cctx = N.DqoRastCtx(geom=c["geom"].data_ptr(), geom_bytes=c["geom"].numel(), binning=None, binning_bytes=0,
                             image=c["img"].data_ptr(), image_bytes=c["img"].numel(), inst_capacity=0)
         if first:
@@ -1390,6 +1395,11 @@ class FusedMapper:
                          pixel_object=fk.get("pixel_object"), frame=frame, **self._window_kw)
             self._restore_state(snap)
             self._g = cur
+            # the window's frames were captured a while ago: set_frame / refresh_window have rewritten frame m's masks in place since
+            g2, gm = self._mixed[frame], self._frames[m]
+            for src, dst in ((gm.mask, g2.mask), (gm.tile_mask, g2.tile_mask)) if gm is not None else ():
+                if src is not None and dst is not None and dst.data_ptr() not in (src.data_ptr(), self.tile_mask.data_ptr()):
+                    dst.copy_(src.view(dst.shape))
         return self._mixed[frame]
 
     def run_window(self, schedule, check_every=64, capacity_margin=1.5):
@@ -1468,6 +1478,87 @@ class FusedMapper:
                     g.pixel_object.copy_(torch.as_tensor(pixel_object).to(self.device, torch.int32).reshape(g.pixel_object.shape))
                     g.tile_objects.copy_(tile_object_sets(g.pixel_object))
         return self
+
+    @torch.no_grad()
+    def refresh_window(self, frames=None, *, global_opt=False, sample_ratio=-1, rows=None, out=None):
+        """The loop that opens every mapping call of the reference — `for frame in self.processed_frames: render_mask, tile_mask, _ =
+        self.evaluate_render_range(frame)` (SLAM/multiprocess/mapper.py:549-555, 1173-1189; the function: :930-988) — for the captured
+        frames of the window (`frames`: the slots, default all of them), on the GPU and in place.  Per frame: the cloud `rows` (bool [P];
+        default trained_rows(), the reference's choice in both callers — `unstable_params` in local_optimize, `stable_params` in
+        global_optimization; every other row and every spare row is hidden through DqoRastInputs.row_flags) rendered at the frame
+        graph's own camera on the persistent context maintain() keeps, then dqo_tilemask.window_masks on its T_map (error mode: also its
+        colour and the graph's target) straight into the graph's render mask and tile mask: the next replay trains under them.  Mixed
+        graphs (k, m) that use frame m's masks get them by device copies, each buffer once, as set_frame does.
+        global_opt / sample_ratio: evaluate_render_range's (the local, error and final branch).  Returns the float32 [K] device tensor of
+        the frames' render ratios (`out`, or this mapper's own table for K, overwritten by the next call with the same K).
+        The FIRST call for a (P, H, W) sizes the render's context from one 32-byte header read, exactly as maintain() does; after that a
+        call reads nothing back, keeps no new allocation and does not synchronise.  A frame that outgrows that context keeps its old
+        masks and gets a NaN ratio; maintain_overflowed() tells (about the LAST frame rendered) where a read is affordable.
+        Refused before anything is launched: a frame captured without a render mask; a frame whose tile mask is this mapper's shared
+        all-ones tile mask (writing it would change every default-mask render of the mapper); a sharded mapper; an image size other than
+        the mapper's."""
+        import dqo_tilemask
+        if self.attach_count_reducer is not None:
+            raise NotImplementedError("FusedMapper.refresh_window: a sharded mapper would need the whole map's render, a shard's shows its "
+                                      "objects only (DESIGN.md §6)")
+        dev = self.device
+        H, W = int(self.settings.image_height), int(self.settings.image_width)
+        gy, gx = (H + 15) // 16, (W + 15) // 16
+        slots = [k for k, g in enumerate(self._frames) if g is not None] if frames is None else [int(k) for k in frames]
+        for k in slots:
+            if not 0 <= k < len(self._frames) or self._frames[k] is None:
+                raise RuntimeError(f"FusedMapper.refresh_window: frame {k} of the window is not captured")
+            g = self._frames[k]
+            if (int(g.settings.image_height), int(g.settings.image_width)) != (H, W):
+                raise RuntimeError("FusedMapper.refresh_window: every frame of a mapper has the mapper's image size")
+            if g.mask is None:
+                raise RuntimeError(f"FusedMapper.refresh_window: frame {k} was captured without a render mask")
+            if g.tile_mask is self.tile_mask or g.tile_mask.data_ptr() == self.tile_mask.data_ptr():
+                raise RuntimeError(f"FusedMapper.refresh_window: frame {k} was captured without a tile mask of its own (it reads the "
+                                   "mapper's shared all-ones tile mask, which every default-mask render reads too)")
+            if g.mask.numel() != H * W or g.tile_mask.numel() != gy * gx:
+                raise RuntimeError("FusedMapper.refresh_window: every frame of a mapper has the mapper's image size")
+        if rows is None:
+            rows = self.trained_rows()
+        elif not torch.is_tensor(rows) or rows.dtype != torch.bool or rows.numel() != self.P or rows.device != self.row_flags.device:
+            raise RuntimeError("FusedMapper.refresh_window: rows must be a bool GPU tensor with one entry per row")
+        K = len(slots)
+        table = out
+        if table is None:
+            table = self._window_ratios.get(K)
+            if table is None:
+                table = self._window_ratios[K] = torch.empty((K,), dtype=torch.float32, device=dev)
+        elif table.dtype != torch.float32 or tuple(table.shape) != (K,) or not table.is_contiguous() or table.device != self.row_flags.device:
+            raise RuntimeError(f"FusedMapper.refresh_window: out must be a contiguous float32 [{K}] tensor on the mapper's device")
+        with torch.cuda.device(dev):
+            if self._window_ws is None:
+                self._window_ws = dqo_tilemask.window_masks_workspace(H, W, dev)
+            if self._window_flags is None:
+                self._window_flags = torch.empty((self.P,), dtype=torch.uint8, device=dev)
+            hidden = ~rows.reshape(-1)
+            if self.alive is not None:  # a spare row is no Gaussian of the map, whichever cloud is asked for
+                hidden |= self.alive == 0
+            self._window_flags.copy_(hidden).mul_(N.ROW_HIDDEN)
+            self.activate()
+            done = set()
+            for i, k in enumerate(slots):
+                g = self._frames[k]
+                c = self._maintain_render(g.settings, row_flags=self._window_flags)
+                o = c["out"]
+                dqo_tilemask.window_masks(o[6], o[0], g.gt_color, global_opt=global_opt, sample_ratio=sample_ratio,
+                                          render_mask=g.mask.view(H, W), tile_mask=g.tile_mask.view(gy, gx), ratio_out=table[i:i + 1],
+                                          render_header=c["geom"], workspace=self._window_ws)
+                done.update((g.mask.data_ptr(), g.tile_mask.data_ptr()))
+            for k in slots:
+                g = self._frames[k]
+                for (_, m), g2 in self._mixed.items():
+                    if m != k:
+                        continue
+                    for src, dst in ((g.mask, g2.mask), (g.tile_mask, g2.tile_mask)):
+                        if dst is not None and dst.data_ptr() not in done and dst.data_ptr() != self.tile_mask.data_ptr():
+                            done.add(dst.data_ptr())
+                            dst.copy_(src.view(dst.shape))
+        return table
 
     def capture_placed(self, *args, trials=4, probe_replays=12, **kw):
         """capture() on the best of `trials` PLACEMENTS of the context buffers.  Where the allocator puts the geometry / binning / image

@@ -691,6 +691,31 @@ int dqo_transmission_mask(int32_t W, int32_t H, const float* T_map, uint8_t* ren
 int dqo_tile_color_error(int32_t W, int32_t H, const float* render, const float* gt, float* color_error, float* tile_sum,
                          void* hipStream);
 
+/* dqo_window_masks (ABI 5, symbols-only addition) — Mapping.evaluate_render_range (SLAM/multiprocess/mapper.py:930-988) for one frame
+ * of a mapping call's window, written in place.  T_map: [H*W]; render, gt: [3, H*W] planes; gy = ceil(H/16), gx = ceil(W/16).
+ *   mode 0 (local, :983-985)  render_mask = T_map != 1;  tile_mask = float(count) / 256.f > tile_mask_ratio, count over the tile's in-image
+ *                             pixels (transmission2tilemask, SLAM/utils.py:752-762)
+ *   mode 1 (error, :947-978)  tile_mask = 1 on the k tiles with the largest colour error sum (dqo_tile_color_error's expression and
+ *                             order; k = int(gy * gx * sample_ratio), SLAM/utils.py:787);  render_mask = the tile mask over its 16 x 16
+ *                             pixels, cropped.  T_map is not read.
+ *   mode 2 (final, :980-982)  render_mask = T_map != 1;  tile_mask = 1 everywhere (the reference's None)
+ * render_mask uint8 [H*W], tile_mask int32 [gy*gx], ratio_out[0] = float32(pixels of render_mask) / float32(H * W) (:987).
+ * Mode 1's selection: the k largest by (sum descending, tile index ascending); a sum is compared by its float32 bit pattern as an unsigned
+ *   integer (the sums are non-negative; a NaN lies above every number).  k = 0: all zero; k = gy * gx: all one.  Any tile count.
+ * One launch (mode 1: two), no float atomic, no zero fill: the same bytes for the same inputs, and capturable in a hipGraph.
+ * render_header (may be NULL): the device header of the forward that rendered the images.  header.overflow != 0 (invalid images):
+ *   render_mask and tile_mask keep their bytes and ratio_out[0] = NaN.
+ * workspace: dqo_window_masks_workspace_bytes(W, H) bytes (0 for a bad size), ZERO when first used and then left to this call, which hands
+ *   it back ready for the next one.  After a mode 1 call its float32 words from byte DQO_WINDOW_MASKS_SUMS_OFFSET on are the gy * gx tile
+ *   sums the selection ran on.  Calls that share a workspace must be ordered (one stream).
+ * DQO_ERR_INVALID_ARG before anything is launched: a NULL output, a bad size or mode, modes 0 / 2 without T_map, mode 1 without render /
+ *   gt or with k outside [0, gy * gx], a workspace that is NULL or too small. */
+#define DQO_WINDOW_MASKS_SUMS_OFFSET 4352
+size_t dqo_window_masks_workspace_bytes(int32_t W, int32_t H);
+int dqo_window_masks(int32_t W, int32_t H, int32_t mode, const float* T_map, const float* render, const float* gt, float tile_mask_ratio,
+                     int32_t k, uint8_t* render_mask, int32_t* tile_mask, float* ratio_out, const DqoRastHeader* render_header,
+                     void* workspace, size_t workspace_bytes, void* hipStream);
+
 /* Row f4 — normal equations of one Gauss-Newton iteration of the point-to-plane ICP tracker (SLAM/icp.py:51-123:
  * compute_residuals_jacobian + compute_jtj + compute_jtr).  vertex / normal maps are [H, W, 3] fp32, pose10 a row-major 4x4
  * (maps frame-0 points into frame 1), normal_threshold the cosine.  Out: JtJ [6,6] (rotation block first), JtR [6],
