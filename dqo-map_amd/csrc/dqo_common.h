@@ -206,6 +206,16 @@ __device__ __forceinline__ uint32_t dqo_wave_sum_u32(uint32_t x, int lane) {
     x += dqo_lane_xor<4>(x, lane), x += dqo_lane_xor<2>(x, lane), x += dqo_lane_xor<1>(x, lane);
     return x;
 }
+// ... and the double sum, in the same order: dqo_lane_xor on the two halves of the double
+template <int D>
+__device__ __forceinline__ double dqo_lane_xor_f64(double x, int lane) {
+    return __hiloint2double((int)dqo_lane_xor<D>((uint32_t)__double2hiint(x), lane), (int)dqo_lane_xor<D>((uint32_t)__double2loint(x), lane));
+}
+__device__ __forceinline__ double dqo_wave_sum_f64(double x, int lane) {
+    x += dqo_lane_xor_f64<32>(x, lane), x += dqo_lane_xor_f64<16>(x, lane), x += dqo_lane_xor_f64<8>(x, lane);
+    x += dqo_lane_xor_f64<4>(x, lane), x += dqo_lane_xor_f64<2>(x, lane), x += dqo_lane_xor_f64<1>(x, lane);
+    return x;
+}
 // The two pixel counts of the frame's loss tap (mask pixels, valid depth pixels: at most W x H < 2^32 each) — all a wave of the
 // backward needs for its gradient scales; the sums of dqo_tap_totals below are for the report
 __device__ __forceinline__ void dqo_tap_counts(const uint32_t* spread, int lane, uint32_t& n_col, uint32_t& n_dep) {

@@ -12,14 +12,13 @@
 // are formed in double (exact: a float difference, its square and its magnitude all fit) and summed in double, so what remains is the order
 // of the additions — at most H W 2^-53 relative — and one rounding to float32 per output.
 //
-// No float or double atomic anywhere: a thread adds its EV_PIX pixels in order, a wave its lanes by the xor butterfly (dqo_lane_xor on
-// the two halves of a double), a block its waves in order, and the block that takes the launch's last integer ticket (two levels, the
-// pattern of map_lifecycle.hip) adds the blocks' partials IN BLOCK-INDEX ORDER and writes the row: the same bits from run to run, whatever
-// order the blocks ran in.  The ticket words are handed back at zero, so the entry has no zero fill and is capturable in a hipGraph.
+// No float or double atomic anywhere: a thread adds its EV_PIX pixels in order, and the rest is dqo_reduce.h — a wave its lanes by the xor
+// butterfly, a block its waves in order, and the block that takes the launch's last integer ticket adds the blocks' partials IN
+// BLOCK-INDEX ORDER and writes the row: the same bits from run to run, and an entry without a zero fill that is capturable in a hipGraph.
 #include <algorithm>
 
 #include "dqo_common.h"
-#include "dqo_ticket.h"
+#include "dqo_reduce.h"
 
 size_t dqo_nn1_ws_bytes(int Q, int R);
 int dqo_launch_nn1(int Q, const float* q_xyz, const uint8_t* q_keep, int R, const float* r_xyz, const uint8_t* r_keep, const float* q_xform,
@@ -31,6 +30,7 @@ enum {
     EV_PIX = 4,                              // pixels per thread: a 1200 x 680 frame is 797 blocks — every CU busy, and a short last sum
     EV_SUMS = 6,                             // squared colour error r, g, b | absolute colour error | absolute depth error | valid pixels
     EV_STRIDE = 8,                           // doubles per block partial: one 64-byte line
+    EV_STAGE = 256,                          // partials staged through LDS at a time by the last block
 };
 
 struct EvWorkspace {
@@ -40,24 +40,13 @@ struct EvWorkspace {
 
 inline size_t ev_blocks(int64_t HW) { return (size_t)((HW + 256 * EV_PIX - 1) / (256 * EV_PIX)); }
 
-template <int D>
-__device__ __forceinline__ double ev_lane_xor(double x, int lane) {
-    return __hiloint2double((int)dqo_lane_xor<D>((uint32_t)__double2hiint(x), lane), (int)dqo_lane_xor<D>((uint32_t)__double2loint(x), lane));
-}
-// wave64 double sum in the order of the xor butterfly 32, 16, 8, 4, 2, 1: every lane ends with the same total
-__device__ __forceinline__ double ev_wave_sum(double x, int lane) {
-    x += ev_lane_xor<32>(x, lane), x += ev_lane_xor<16>(x, lane), x += ev_lane_xor<8>(x, lane);
-    x += ev_lane_xor<4>(x, lane), x += ev_lane_xor<2>(x, lane), x += ev_lane_xor<1>(x, lane);
-    return x;
-}
-
 __global__ __launch_bounds__(256) void eval_picture_kernel(int64_t HW, const float* __restrict__ render, const float* __restrict__ gt_color,
                                                            const float* __restrict__ depth, const float* __restrict__ gt_depth,
                                                            const int32_t* __restrict__ depth_index, float min_depth, float max_depth,
                                                            const DqoRastHeader* __restrict__ header, EvWorkspace w, float* __restrict__ out) {
-    __shared__ double s_stage[256 * EV_STRIDE];
+    __shared__ double s_stage[EV_STAGE * EV_STRIDE];
     __shared__ int s_last;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     double a[EV_SUMS];
 #pragma unroll
     for (int q = 0; q < EV_SUMS; q++) a[q] = 0.0;
@@ -77,31 +66,9 @@ __global__ __launch_bounds__(256) void eval_picture_kernel(int64_t HW, const flo
             }
         }
     }
-#pragma unroll
-    for (int q = 0; q < EV_SUMS; q++) a[q] = ev_wave_sum(a[q], lane);
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < EV_SUMS; q++) s_stage[wave * EV_STRIDE + q] = a[q];
-    }
-    __syncthreads();
-    if (tid < EV_SUMS) {
-        double t = 0.0;
-        for (int v = 0; v < 4; v++) t += s_stage[v * EV_STRIDE + tid];
-        __hip_atomic_store(&w.partial[(size_t)blockIdx.x * EV_STRIDE + tid], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (!ev_last_block(w.ticket, &s_last)) return;
-    // the partials in block-index order: staged through LDS 256 blocks at a time (coalesced loads), sum q added by thread q
-    const int blocks = (int)gridDim.x;
-    double total = 0.0;
-    for (int base = 0; base < blocks; base += 256) {
-        const int m = min(256, blocks - base);
-        for (int j = tid; j < m * EV_STRIDE; j += 256)
-            s_stage[j] = __hip_atomic_load(&w.partial[(size_t)base * EV_STRIDE + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (tid < EV_SUMS)
-            for (int k = 0; k < m; k++) total += s_stage[k * EV_STRIDE + tid];
-        __syncthreads();
-    }
+    dqo_block_partial<EV_SUMS, EV_STRIDE>(a, s_stage, w.partial);
+    if (!dqo_last_block(w.ticket, &s_last)) return;
+    const double total = dqo_fold_partials<EV_SUMS, EV_STRIDE, EV_STAGE>(w.partial, 0, (int)gridDim.x, s_stage);
     if (tid < EV_SUMS) s_stage[tid] = total;
     __syncthreads();
     if (tid != 0) return;
@@ -132,8 +99,8 @@ __global__ __launch_bounds__(256) void eval_picture_kernel(int64_t HW, const flo
 // The reference builds a KDTree and queries it anew for every one of these statements; here d2_rec (every reconstructed point to its
 // nearest ground-truth point) and d2_gt (the other way round) come from two dqo_nn1 searches, and ONE launch reduces both: per kept row
 // sqrt((double)d2) and, per threshold, (double)d2 < (double)th * (double)th — both sides exact in double, so a count is an exact function
-// of the search's bits (the reference's strict '<' on distances).  Sums as in eval_picture_kernel: a thread's rows in order, lanes by the
-// butterfly, waves in order, one partial per block, the last block (integer ticket) adds the partials in block-index order.
+// of the search's bits (the reference's strict '<' on distances).  Sums as in eval_picture_kernel: a thread's rows in order, then
+// dqo_reduce.h, the last block folding the partials of each side on their own.
 enum {
     PC_ROWS = 4,           // rows of a set per thread
     PC_THRES = 8,          // thresholds at most
@@ -155,7 +122,7 @@ __global__ __launch_bounds__(256) void eval_pcd_kernel(int n_rec, const float* _
                                                        PcThres thres, int blocks_rec, EvWorkspace w, float* __restrict__ out) {
     __shared__ double s_stage[PC_STAGE * PC_STRIDE];
     __shared__ int s_last;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const bool rec_side = (int)blockIdx.x < blocks_rec;
     const int n = rec_side ? n_rec : n_gt, block = rec_side ? (int)blockIdx.x : (int)blockIdx.x - blocks_rec;
     const float* __restrict__ d2 = rec_side ? d2_rec : d2_gt;
@@ -178,34 +145,10 @@ __global__ __launch_bounds__(256) void eval_pcd_kernel(int n_rec, const float* _
                 if (t < n_thres && v < th2[t]) a[2 + t] += 1.0;
         }
     }
-#pragma unroll
-    for (int q = 0; q < PC_SUMS; q++) a[q] = ev_wave_sum(a[q], lane);
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < PC_SUMS; q++) s_stage[wave * PC_STRIDE + q] = a[q];
-    }
-    __syncthreads();
-    if (tid < PC_SUMS) {
-        double t = 0.0;
-        for (int v = 0; v < 4; v++) t += s_stage[v * PC_STRIDE + tid];
-        __hip_atomic_store(&w.partial[(size_t)blockIdx.x * PC_STRIDE + tid], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (!ev_last_block(w.ticket, &s_last)) return;
-    // the partials of each side in block-index order, sum q added by thread q
-    const int blocks = (int)gridDim.x;
-    double tot_rec = 0.0, tot_gt = 0.0;
-    for (int base = 0; base < blocks; base += PC_STAGE) {
-        const int m = min((int)PC_STAGE, blocks - base);
-        for (int j = tid; j < m * PC_STRIDE; j += 256)
-            s_stage[j] = __hip_atomic_load(&w.partial[(size_t)base * PC_STRIDE + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (tid < PC_SUMS)
-            for (int k = 0; k < m; k++) {
-                if (base + k < blocks_rec) tot_rec += s_stage[k * PC_STRIDE + tid];
-                else tot_gt += s_stage[k * PC_STRIDE + tid];
-            }
-        __syncthreads();
-    }
+    dqo_block_partial<PC_SUMS, PC_STRIDE>(a, s_stage, w.partial);
+    if (!dqo_last_block(w.ticket, &s_last)) return;
+    const double tot_rec = dqo_fold_partials<PC_SUMS, PC_STRIDE, PC_STAGE>(w.partial, 0, blocks_rec, s_stage);
+    const double tot_gt = dqo_fold_partials<PC_SUMS, PC_STRIDE, PC_STAGE>(w.partial, blocks_rec, (int)gridDim.x, s_stage);
     if (tid < PC_SUMS) s_stage[tid] = tot_rec, s_stage[PC_STRIDE + tid] = tot_gt;
     __syncthreads();
     if (tid != 0) return;
@@ -237,7 +180,7 @@ struct PcWorkspace {
 inline PcWorkspace pc_ws(void* base, int n_gt, int n_rec) {
     PcWorkspace w;
     char* p = (char*)base;
-    w.ev.ticket = (int32_t*)p, p += EV_HEAD_WORDS * 4;
+    w.ev.ticket = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
     w.ev.partial = (double*)p, p += dqo_align_up((pc_blocks(n_rec) + pc_blocks(n_gt) + 1) * PC_STRIDE * sizeof(double), 256);
     w.d2_rec = (float*)p, p += dqo_align_up(4 * (size_t)n_rec, 256);
     w.d2_gt = (float*)p, p += dqo_align_up(4 * (size_t)n_gt, 256);
@@ -248,7 +191,7 @@ inline PcWorkspace pc_ws(void* base, int n_gt, int n_rec) {
 
 }  // namespace
 
-size_t dqo_eval_ws_bytes(int64_t HW) { return EV_HEAD_WORDS * 4 + dqo_align_up(ev_blocks(HW) * EV_STRIDE * sizeof(double), 256); }
+size_t dqo_eval_ws_bytes(int64_t HW) { return DQO_REDUCE_HEAD_WORDS * 4 + dqo_align_up(ev_blocks(HW) * EV_STRIDE * sizeof(double), 256); }
 
 int dqo_launch_eval_picture(int W, int H, const float* render, const float* gt_color, const float* depth, const float* gt_depth,
                             const int32_t* depth_index, float min_depth, float max_depth, const DqoRastHeader* header, float* out_row,
@@ -256,7 +199,7 @@ int dqo_launch_eval_picture(int W, int H, const float* render, const float* gt_c
     const int64_t HW = (int64_t)W * H;
     EvWorkspace w;
     w.ticket = (int32_t*)ws;
-    w.partial = (double*)((char*)ws + EV_HEAD_WORDS * 4);
+    w.partial = (double*)((char*)ws + DQO_REDUCE_HEAD_WORDS * 4);
     DQO_LAUNCH("eval_picture_kernel", eval_picture_kernel, dim3((unsigned)ev_blocks(HW)), dim3(256), s, HW, render, gt_color, depth, gt_depth,
                depth_index, min_depth, max_depth, header, w, out_row);
     return DQO_OK;

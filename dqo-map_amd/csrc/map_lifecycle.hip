@@ -14,44 +14,41 @@
 // pass that consumes a vote word clears it: no zero fill per frame.
 //
 // The two `10 x mean radius` limits are whole-cloud reductions over the membership the earlier statements left.  No float atomics: every
-// block writes a double partial sum and a count, the block that takes the last integer ticket (the pattern of dqo_adam.h) adds the partials
-// in index order, rounds the mean to float once and multiplies by 10 in float — bitwise the same from run to run.
+// block writes a double partial sum and a count, the block that takes the last integer ticket adds the partials in index order
+// (dqo_reduce.h), rounds the mean to float once and multiplies by 10 in float — bitwise the same from run to run.
 #include "dqo_common.h"
+#include "dqo_reduce.h"
 
 namespace {
 
-// words of the workspace's head (int32; zero when the workspace is made, handed back at zero by every launch that uses them).
-// Same-address atomics are served one at a time memory-side (dqo_adam.h on its block ticket, profiles/r06_tail_ticket.txt): with ONE
-// word per count the last row kernel — whose two what-is-left counts take an atomic from every wave of the map — ran 272 us on a 550 k
-// map (profiles/lifecycle_single_counter_kernel_stats.csv; the spread version below has not been timed yet).  So the block tickets have two levels
-// (a block takes a ticket on line blockIdx % lines, the last block of a line one of word 0's) and the counts are spread over LC_LINES
-// lines of 256 bytes that the last block of the last row kernel adds up.
+// words of the workspace's head (int32; zero when the workspace is made, handed back at zero by every launch that uses them): the
+// ticket words of dqo_reduce.h — the row kernels run one after the other and share them —, the results in free words of word 0's line,
+// and the frame's counts.  Same-address atomics are served one at a time memory-side (dqo_reduce.h): with ONE word per count the last row
+// kernel — whose two what-is-left counts take an atomic from every wave of the map — ran 272 us on a 550 k map
+// (profiles/lifecycle_single_counter_kernel_stats.csv), so the counts are spread over LC_LINES lines of 256 bytes that the last block of
+// the last row kernel adds up.
 enum {
     LC_LINES = 64,
-    LC_TICKET = 0,         // the row kernels' block tickets (they run one after the other): word 0, and word 16 + 16 * line
     LC_COUNT = 4,          // [2] rows of the stable / unstable cloud the limits below were formed over
     LC_LIMIT = 6,          // [2] float bits: 10 x mean radius of the stable / unstable cloud
-    LC_ACC = 1088,         // [LC_LINES][64] word k of a line: count k of the frame while the row kernels run (DqoLifecycle.stats gets the sums)
+    LC_ACC = DQO_REDUCE_HEAD_WORDS,  // [LC_LINES][64] word k of a line: count k of the frame while the row kernels run (DqoLifecycle.stats gets the sums)
     LC_HEAD_WORDS = LC_ACC + LC_LINES * 64,
+    LC_SUMS = 2,           // doubles per block partial: radius sum | member rows
+    LC_STAGE = 128,        // partials staged through LDS at a time by the last block
 };
-static_assert(LC_ACC >= 16 + 16 * LC_LINES && LC_HEAD_WORDS * 4 % 256 == 0, "workspace head layout");
+static_assert(LC_LIMIT + 2 <= 16 && LC_HEAD_WORDS * 4 % 256 == 0, "workspace head layout");
 
 struct LcWorkspace {
     int32_t* head;
-    double* partial_sum;   // [blocks]
-    int32_t* partial_rows; // [blocks]
+    double* partial;  // [blocks][LC_SUMS]
 };
 
 __host__ __device__ inline size_t lc_blocks(int64_t P) { return (size_t)((P + 255) / 256); }
 
-inline size_t lc_partial_sum_bytes(int64_t P) { return dqo_align_up(lc_blocks(P) * sizeof(double), 256); }
-
-inline LcWorkspace lc_workspace(void* base, int64_t P) {
+inline LcWorkspace lc_workspace(void* base) {
     LcWorkspace w;
-    char* p = (char*)base;
-    w.head = (int32_t*)p;
-    w.partial_sum = (double*)(p + LC_HEAD_WORDS * 4);
-    w.partial_rows = (int32_t*)(p + LC_HEAD_WORDS * 4 + lc_partial_sum_bytes(P));
+    w.head = (int32_t*)base;
+    w.partial = (double*)((char*)base + LC_HEAD_WORDS * 4);
     return w;
 }
 
@@ -79,71 +76,20 @@ __device__ __forceinline__ void lc_count(int32_t* head, int k, bool pred, int la
     if (lane == 0 && n > 0) atomicAdd(&head[LC_ACC + (blockIdx.x % LC_LINES) * 64 + k], n);
 }
 
-// Takes the block's ticket; true (for every thread of the block) in the block that took the last one, which then sees what every other
-// block wrote before its ticket.
-__device__ __forceinline__ bool lc_last_block(int32_t* ticket, int* s_last) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        const int grid = (int)gridDim.x;
-        const int lines = min((int)LC_LINES, max(1, grid / 16));
-        const int l = (int)blockIdx.x % lines;
-        const int on_line = (grid - l + lines - 1) / lines;  // blocks b < grid with b % lines == l
-        int32_t* const line = ticket + 16 + 16 * l;
-        bool last = atomicAdd(line, 1) == on_line - 1;
-        if (last) {
-            *line = 0;
-            __threadfence();  // (acquire what the line's other blocks released, release it to the block that takes word 0's last ticket)
-            last = atomicAdd(ticket, 1) == lines - 1;
-            if (last) *ticket = 0;
-        }
-        *s_last = last;
-    }
-    __syncthreads();
-    if (!*s_last) return false;
-    __threadfence();
-    return true;
-}
-
 // 10 x the mean radius of the rows with `member` set, over the whole launch: head[LC_LIMIT + which] (float bits) and the row count in
 // head[LC_COUNT + which], written by the last block.  Every thread of every block calls it.
 __device__ __forceinline__ void lc_cloud_limit(const LcWorkspace& w, int which, float radius, bool member) {
-    __shared__ double s_sum[256];
-    __shared__ int s_rows[256];
+    __shared__ double s_stage[LC_STAGE * LC_SUMS];
     __shared__ int s_last;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double x = member ? (double)radius : 0.0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);  // (a fixed butterfly: the same bits every run)
-    const int n = __popcll(__ballot(member));
-    if (lane == 0) s_sum[wave] = x, s_rows[wave] = n;
+    double a[LC_SUMS] = {member ? (double)radius : 0.0, member ? 1.0 : 0.0};  // (the count is exact in a double)
+    dqo_block_partial<LC_SUMS, LC_SUMS>(a, s_stage, w.partial);
+    if (!dqo_last_block(w.head, &s_last)) return;
+    const double total = dqo_fold_partials<LC_SUMS, LC_SUMS, LC_STAGE>(w.partial, 0, (int)gridDim.x, s_stage);
+    if (threadIdx.x < LC_SUMS) s_stage[threadIdx.x] = total;
     __syncthreads();
-    if (tid == 0) {
-        const int waves = (int)blockDim.x >> 6;
-        double t = 0.0;
-        int c = 0;
-        for (int k = 0; k < waves; k++) t += s_sum[k], c += s_rows[k];
-        __hip_atomic_store(&w.partial_sum[blockIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&w.partial_rows[blockIdx.x], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (!lc_last_block(&w.head[LC_TICKET], &s_last)) return;
-    // the partials in index order: staged through LDS 256 at a time (coalesced loads), added by one thread
-    const int blocks = (int)gridDim.x;
-    double total = 0.0;
-    long long rows = 0;
-    for (int base = 0; base < blocks; base += 256) {
-        const int j = base + tid;
-        s_sum[tid] = j < blocks ? __hip_atomic_load(&w.partial_sum[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-        s_rows[tid] = j < blocks ? __hip_atomic_load(&w.partial_rows[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-        __syncthreads();
-        if (tid == 0) {
-            const int m = min(256, blocks - base);
-            for (int k = 0; k < m; k++) total += s_sum[k], rows += s_rows[k];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const float mean = rows > 0 ? (float)(total / (double)rows) : 0.f;  // rounded to float once
+    if (threadIdx.x == 0) {
+        const double sum = s_stage[0], rows = s_stage[1];
+        const float mean = rows > 0.0 ? (float)(sum / rows) : 0.f;  // rounded to float once
         w.head[LC_LIMIT + which] = __float_as_int(mean * 10.f);
         w.head[LC_COUNT + which] = (int32_t)rows;
     }
@@ -237,7 +183,7 @@ __global__ __launch_bounds__(256) void lifecycle_delete_kernel(DqoLifecycle a, L
     lc_count(w.head, 4, old, lane);
     lc_count(w.head, 6, unstable && !big && !old, lane);
     lc_count(w.head, 7, stable, lane);
-    if (!lc_last_block(&w.head[LC_TICKET], &s_last)) return;
+    if (!dqo_last_block(w.head, &s_last)) return;
     // the eight counts: wave w adds up counts 2w and 2w + 1 over the lines (lane = line) and leaves the lines at zero
     const int wave = threadIdx.x >> 6;
     static_assert(LC_LINES == 64, "one lane per line");
@@ -249,9 +195,7 @@ __global__ __launch_bounds__(256) void lifecycle_delete_kernel(DqoLifecycle a, L
 
 }  // namespace
 
-size_t dqo_lifecycle_ws_bytes(int64_t P) {
-    return LC_HEAD_WORDS * 4 + lc_partial_sum_bytes(P) + dqo_align_up(lc_blocks(P) * sizeof(int32_t), 256);
-}
+size_t dqo_lifecycle_ws_bytes(int64_t P) { return LC_HEAD_WORDS * 4 + dqo_align_up(lc_blocks(P) * LC_SUMS * sizeof(double), 256); }
 
 int dqo_launch_lifecycle_vote(const DqoLifecycle* a, const float* gt_color, const float* gt_depth, const float* render, const float* depth,
                               const int32_t* depth_index, const int32_t* color_index, hipStream_t s) {
@@ -262,7 +206,7 @@ int dqo_launch_lifecycle_vote(const DqoLifecycle* a, const float* gt_color, cons
 }
 
 int dqo_launch_lifecycle_rows(const DqoLifecycle* a, hipStream_t s) {
-    const LcWorkspace w = lc_workspace(a->workspace, a->P);
+    const LcWorkspace w = lc_workspace(a->workspace);
     const dim3 grid((unsigned)lc_blocks(a->P)), block(256);
     if (a->stable_oversized) {
         DQO_LAUNCH("lifecycle_stable_limit_kernel", lifecycle_stable_limit_kernel, grid, block, s, *a, w);

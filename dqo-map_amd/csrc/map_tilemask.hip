@@ -11,7 +11,7 @@
 // once, coalesced (64-byte rows), and reduced with a wave ballot / DPP sum + one LDS hop — the reference runs 4-7 eager
 // kernels per mask and materialises the padded copies.
 #include "dqo_common.h"
-#include "dqo_ticket.h"
+#include "dqo_reduce.h"
 
 namespace {
 
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void tile_color_error_kernel(int W, int H, int
 //   mode 2 (final, :980-982)   render_mask = T_map != 1;  tile_mask = 1  (the reference's None)
 //   every mode                 ratio_out[0] = float(count of render_mask) / float(H * W)   (:987)
 // One 256-thread block per tile, as above: the tile's word (mode 1: its error sum, tile_color_error_kernel's expression and order;
-// otherwise its pixel count) goes to the workspace, and the block that takes the launch's last ticket (ev_last_block) finishes the frame.
+// otherwise its pixel count) goes to the workspace, and the block that takes the launch's last ticket (dqo_last_block) finishes the frame.
 // Mode 1's selection is DEFINED here: the k largest by (sum descending, tile index ascending), the sum compared by its bit pattern as
 // an unsigned integer (sums are non-negative; a NaN lies above every number).  The last block finds the k-th key by a radix select —
 // four 8-bit digits from the top, a 256-bin LDS histogram of the keys that share the digits fixed so far — which also tells how many keys
@@ -92,13 +92,12 @@ struct WmWorkspace {
 inline WmWorkspace wm_ws(void* base, size_t T, size_t* total) {
     WmWorkspace w;
     char* p = (char*)base;
-    w.ticket = (int32_t*)p, p += EV_HEAD_WORDS * 4;
+    w.ticket = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;  // = DQO_WINDOW_MASKS_SUMS_OFFSET
     w.sums = (float*)p, p += dqo_align_up(4 * T, 256);
     w.counts = (int32_t*)p, p += dqo_align_up(4 * T, 256);
     if (total) *total = (size_t)(p - (char*)base);
     return w;
 }
-static_assert(EV_HEAD_WORDS * 4 == DQO_WINDOW_MASKS_SUMS_OFFSET, "the tile sums' place in the workspace is part of the header");
 
 // the block's sum of one word per thread (every thread gets it); s_wave is free again after the call
 __device__ __forceinline__ uint32_t wm_block_sum(uint32_t v, uint32_t* s_wave, int tid) {
@@ -151,7 +150,7 @@ __global__ __launch_bounds__(256) void window_masks_kernel(int W, int H, int gx,
             }
         }
     }
-    if (!ev_last_block(w.ticket, &s_last)) return;
+    if (!dqo_last_block(w.ticket, &s_last)) return;
     if (!valid) {
         if (tid == 0) ratio_out[0] = __int_as_float(0x7fc00000);
         return;

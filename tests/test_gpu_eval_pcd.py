@@ -4,8 +4,9 @@
 Bars, and why.  dist2: bit for bit — the kernel and nn1_oracle both return the minimum of one float32 expression over the kept references.
 idx: any reference whose recomputed float32 distance equals dist2.  Counts (P n / 100, R n / 100): exactly — both sides of the kernel's
 threshold test are exact in double, and on "room" no point lies within 1e-4 relative of a threshold (tests/test_pcd_oracle.py asserts that
-premise).  Slots 0-2 and P / R / F1: 3e-7 relative — the float32 distances are within 2e-7 relative of scipy's, plus two roundings to float32
-(6e-8 each) and a double sum in another order."""
+premise); a count is read back from a float32 percentage below 128, whose half ulp of 2^-18 is 3.8e-8 n rows: the product lies within
+max(1e-3, 4e-8 n) of the integer (1e-3 up to 25 000 rows).  Slots 0-2 and P / R / F1: 3e-7 relative — the float32 distances are within
+2e-7 relative of scipy's, plus two roundings to float32 (6e-8 each) and a double sum in another order."""
 import numpy as np
 import pytest
 
@@ -140,7 +141,7 @@ def _assert_row(got, gt_n, rec_n, d_rec64, d_gt64, thres, what):
         pairs += [(f"P (< {th})", 4 + 3 * t), (f"R (< {th})", 5 + 3 * t), (f"F1 (< {th})", 6 + 3 * t)]
         p_count, r_count = got[4 + 3 * t] * rec_n / 100, got[5 + 3 * t] * gt_n / 100
         print(f"{what} th {th}: counts {p_count!r} {r_count!r} want {counts[t]}")
-        assert abs(p_count - round(p_count)) < 1e-3 and abs(r_count - round(r_count)) < 1e-3, what
+        assert abs(p_count - round(p_count)) < max(1e-3, 4e-8 * rec_n) and abs(r_count - round(r_count)) < max(1e-3, 4e-8 * gt_n), what
         assert (round(p_count), round(r_count)) == counts[t], what
     for key, slot in pairs:
         g, w = got[slot], float(want[key])
@@ -197,6 +198,25 @@ def test_eval_pcd_masks_and_nan_rows():
     # no distance under the threshold: P = R = 0 and F1 = 0 / 0
     far = dqo_eval.eval_pcd(_t(gt), _t(rec + np.float32([0, 0, 10.0])), (0.03,)).cpu().numpy()
     assert far[4] == 0 and far[5] == 0 and np.isnan(far[6]) and far[0] > 700 and far[3] == 1
+
+
+def test_eval_pcd_more_blocks_than_one_stage_of_the_last_block():
+    """70 001 + 66 000 points, uniform in the unit cube: 69 + 65 blocks of 1 024 rows — more than the 128 partials the last block stages at
+    a time, with the boundary between the two sides inside the first stage.  The bars of _assert_row; their premise, that no distance lies
+    within 1e-4 relative of the threshold (so the float32 and the float64 decisions agree), is asserted here."""
+    import torch
+    import dqo_eval
+    rng = np.random.default_rng(31)
+    rec, gt = _cloud(rng, 70001, scale=(1.0, 1.0, 1.0)), _cloud(rng, 66000, scale=(1.0, 1.0, 1.0))
+    d_rec64, d_gt64 = po.kdtree_distances(gt, rec)
+    th = (0.03,)
+    for d64 in (d_rec64, d_gt64):
+        assert (np.abs(d64 - th[0]) > 1e-4 * th[0]).all() and 0 < (d64 < th[0]).sum() < d64.size
+    g, r = _t(gt), _t(rec)
+    a, b = dqo_eval.eval_pcd(g, r, th), dqo_eval.eval_pcd(g, r, th)
+    torch.cuda.synchronize()
+    _assert_row(a.cpu().numpy(), gt.shape[0], rec.shape[0], d_rec64, d_gt64, th, "unit cube")
+    assert _bits(a).tobytes() == _bits(b).tobytes()
 
 
 def test_ten_calls_on_one_stream_and_a_captured_graph():

@@ -33,11 +33,14 @@ def _oracle(case, state, tick, frame=True, **extra):
 
 
 @pytest.mark.parametrize("kw", [dict(seed=11), dict(seed=12, stable_outlier=True), dict(seed=13, n_alive=1, n_spare=0),
-                                dict(seed=14, n_alive=0, n_spare=64)], ids=["600+200", "stable_oversized", "one_row", "all_spare"])
+                                dict(seed=14, n_alive=0, n_spare=64), dict(seed=15, n_alive=69000, n_spare=1100, stable_outlier=True)],
+                         ids=["600+200", "stable_oversized", "one_row", "all_spare", "69000+1100"])
 def test_one_step_equals_the_oracle(kw):
     """Three blocks of 256 with a partial last one, a 50 x 36 frame; index maps that name one row from many pixels, row 0, the last live
     row, -1, spare rows and values outside the map; pixels without a target depth and pixels whose render lies behind the target.  With
-    stable_oversized one stable row is 30 x its cloud's mean, which the unstable cloud's mean does not see."""
+    stable_oversized one stable row is 30 x its cloud's mean, which the unstable cloud's mean does not see.  69000+1100 is 274 blocks with
+    a ragged last one: 17 ticket lines that 274 is no multiple of, and more partials than the last block folds in one stage, in all three
+    row kernels.  Every case runs twice: all buffers, the counts and the workspace agree bit for bit."""
     import torch
     import dqo_mapgrowth as mg
     case = lc.make_case(**kw)
@@ -51,6 +54,13 @@ def test_one_step_equals_the_oracle(kw):
     assert not bool(state["_lifecycle"][1].any())  # every vote word was cleared as it was read
     if "stable_outlier" in case["named"]:
         assert FATES[int(want["fate"][case["named"]["stable_outlier"][0]])] == "deleted_oversized_stable" and want["stats"][5] == 1
+    stats = stats.clone()
+    again, frame, th = _gpu(case)
+    stats2 = mg.lifecycle_step(again, case["tick"], *frame, **th, **extra)
+    torch.cuda.synchronize()
+    assert torch.equal(stats, stats2) and torch.equal(state["_lifecycle"][2], again["_lifecycle"][2])
+    for name, _, _ in mg.LIFECYCLE_STATE:
+        assert torch.equal(state[name], again[name]), name
 
 
 def _run_sequence(case):
