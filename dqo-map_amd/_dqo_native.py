@@ -121,6 +121,7 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_track_pyramid_workspace_bytes", "dqo_track_pyramid", "dqo_track_fill_model_depth", "dqo_track_p2p_workspace_bytes",
            "dqo_track_p2p_loss", "dqo_map_lifecycle_workspace_bytes", "dqo_map_lifecycle_vote", "dqo_map_lifecycle_rows",
            "dqo_growth_sample_workspace_bytes", "dqo_growth_sample", "dqo_eval_picture_workspace_bytes", "dqo_eval_picture",
+           "dqo_eval_ms_ssim_workspace_bytes", "dqo_eval_ms_ssim",
            "dqo_nn1_workspace_bytes", "dqo_nn1", "dqo_eval_pcd_workspace_bytes", "dqo_eval_pcd", "dqo_window_masks_workspace_bytes",
            "dqo_window_masks")
 
@@ -227,6 +228,9 @@ def lib():
         L.dqo_eval_picture_workspace_bytes.restype = ctypes.c_size_t
         L.dqo_eval_picture_workspace_bytes.argtypes = [c_i32, c_i32]
         L.dqo_eval_picture.argtypes = [c_i32, c_i32] + [c_vp] * 5 + [c_f, c_f, c_vp, c_vp, c_i32, c_vp, ctypes.c_size_t, c_vp]
+        L.dqo_eval_ms_ssim_workspace_bytes.restype = ctypes.c_size_t
+        L.dqo_eval_ms_ssim_workspace_bytes.argtypes = [c_i32, c_i32]
+        L.dqo_eval_ms_ssim.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, ctypes.c_size_t, c_vp]
         L.dqo_nn1_workspace_bytes.restype = ctypes.c_size_t
         L.dqo_nn1_workspace_bytes.argtypes = [c_i32, c_i32]
         L.dqo_nn1.argtypes = [c_i32, c_vp, c_vp, c_i32] + [c_vp] * 7 + [ctypes.c_size_t, c_vp]

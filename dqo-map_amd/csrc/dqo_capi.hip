@@ -93,6 +93,9 @@ size_t dqo_eval_pcd_ws_bytes(int n_gt, int n_rec);
 int dqo_launch_eval_pcd(int n_gt, const float* gt_xyz, const uint8_t* gt_keep, int n_rec, const float* rec_xyz, const uint8_t* rec_keep,
                         const float* rec_xform, int n_thres, const float* thres, float* out_row, void* ws, hipStream_t s);
 size_t dqo_eval_ws_bytes(int64_t HW);
+size_t dqo_msssim_ws_bytes(int W, int H);
+int dqo_launch_msssim(int W, int H, const float* render, const float* gt_color, const DqoRastHeader* header, float* out_row, void* ws,
+                      hipStream_t s);
 int dqo_launch_eval_picture(int W, int H, const float* render, const float* gt_color, const float* depth, const float* gt_depth,
                             const int32_t* depth_index, float min_depth, float max_depth, const DqoRastHeader* header, float* out_row,
                             void* ws, hipStream_t s);
@@ -822,6 +825,23 @@ DQO_API int dqo_eval_picture(int32_t W, int32_t H, const float* render, const fl
     }
     return dqo_launch_eval_picture(W, H, render, gt_color, depth, gt_depth, depth_index, min_depth, max_depth, render_header,
                                    out + (size_t)8 * row, ws, (hipStream_t)stream);
+}
+
+// eval_picture's "ssim" (SLAM/eval.py:19-25, :64): pytorch_msssim's ms_ssim, which asserts min(H, W) > (11 - 1) * 2^4
+static bool msssim_size_ok(int32_t W, int32_t H) { return W > 160 && H > 160 && (int64_t)W * H < (1ll << 31) / 3; }
+
+DQO_API size_t dqo_eval_ms_ssim_workspace_bytes(int32_t W, int32_t H) { return msssim_size_ok(W, H) ? dqo_msssim_ws_bytes(W, H) : 0; }
+
+DQO_API int dqo_eval_ms_ssim(int32_t W, int32_t H, const float* render, const float* gt_color, const DqoRastHeader* render_header, float* out,
+                             int32_t row, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(msssim_size_ok(W, H), "bad image size %d x %d: MS-SSIM needs both sides > 160 (five levels of an 11-tap window)", W, H);
+    DQO_CHECK_ARG(render && gt_color && out, "null pointer");
+    DQO_CHECK_ARG(row >= 0, "bad row %d", row);
+    if (ws == nullptr || ws_bytes < dqo_msssim_ws_bytes(W, H)) {
+        dqo_set_error("ms_ssim workspace too small (%zu < %zu)", ws_bytes, dqo_msssim_ws_bytes(W, H));
+        return DQO_ERR_WORKSPACE;
+    }
+    return dqo_launch_msssim(W, H, render, gt_color, render_header, out + (size_t)20 * row, ws, (hipStream_t)stream);
 }
 
 // the index word of a sorted point carries 25 index bits (knn.hip: FINE_IDX_BITS)

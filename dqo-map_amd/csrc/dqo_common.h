@@ -38,6 +38,13 @@ void dqo_set_error(const char* fmt, ...);
 
 static inline size_t dqo_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The 11-tap Gaussian window of utils/loss_utils.py:41-58 (sigma 1.5), bit for bit the reference's floats; by value into the SSIM kernels
+// (map_ssim.hip, which defines it, and map_msssim.hip)
+struct DqoSsimWindow {
+    float g[11];
+};
+DqoSsimWindow dqo_ssim_window();
+
 // Intrinsics from a row-major 3x3 fp32 matrix in device memory, scaled as the reference's `K * downscale` (fp32; K[2,2] unused)
 struct DqoIntrinsics {
     float fx, fy, cx, cy;

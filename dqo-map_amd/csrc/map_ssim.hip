@@ -20,9 +20,7 @@ namespace {
 
 constexpr int SS_T = 16, SS_R = 5, SS_W = SS_T + 2 * SS_R;  // tile, window radius, halo tile
 
-struct SsimWin {
-    float g[11];
-};
+using SsimWin = DqoSsimWindow;
 
 __global__ __launch_bounds__(SS_T* SS_T) void ssim_map_kernel(int W, int H, const float* __restrict__ img1, const float* __restrict__ img2,
                                                              SsimWin w, float* __restrict__ maps, float* __restrict__ partial) {
@@ -158,6 +156,22 @@ __global__ __launch_bounds__(SS_T* SS_T) void ssim_grad_kernel(int W, int H, con
 
 }  // namespace
 
+DqoSsimWindow dqo_ssim_window() {
+    // utils/loss_utils.py:41-58: float32(exp(-(x - 5)^2 / (2 sigma^2))) / their float32 sum.  The SSIM value is sensitive to the LAST BIT of
+    // that sum: a window summing to 1 + e shifts sigma^2 = E[x^2] - mu^2 by -e mu^2, amplified by mu^2 / (sigma^2 + C2) ~ 10^2 on smooth
+    // images (a sequential float sum, one ulp below torch's, moved ssim by 5e-6).  torch's float sum of these eleven values is the
+    // correctly rounded one: formed here in double and rounded once -> weights bit-identical to the reference's window.
+    DqoSsimWindow w;
+    double sum = 0.0;
+    for (int i = 0; i < 11; i++) {
+        w.g[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5));
+        sum += (double)w.g[i];
+    }
+    const float sum_f = (float)sum;
+    for (int i = 0; i < 11; i++) w.g[i] /= sum_f;
+    return w;
+}
+
 size_t dqo_map_ssim_ws_bytes(int W, int H) {
     const size_t HW = (size_t)W * H;
     const size_t blocks = (size_t)((W + SS_T - 1) / SS_T) * ((H + SS_T - 1) / SS_T) * 3;
@@ -169,18 +183,7 @@ int dqo_launch_map_ssim(int W, int H, const float* img, const float* gt, float w
     const size_t HW = (size_t)W * H;
     float* maps = reinterpret_cast<float*>(ws);
     float* partial = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + dqo_align_up(sizeof(float) * 9 * HW, 256));
-    // utils/loss_utils.py:41-58: float32(exp(-(x - 5)^2 / (2 sigma^2))) / their float32 sum.  The SSIM value is sensitive to the LAST BIT of
-    // that sum: a window summing to 1 + e shifts sigma^2 = E[x^2] - mu^2 by -e mu^2, amplified by mu^2 / (sigma^2 + C2) ~ 10^2 on smooth
-    // images (a sequential float sum, one ulp below torch's, moved ssim by 5e-6).  torch's float sum of these eleven values is the
-    // correctly rounded one: formed here in double and rounded once -> weights bit-identical to the reference's window.
-    SsimWin w;
-    double sum = 0.0;
-    for (int i = 0; i < 11; i++) {
-        w.g[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5));
-        sum += (double)w.g[i];
-    }
-    const float sum_f = (float)sum;
-    for (int i = 0; i < 11; i++) w.g[i] /= sum_f;
+    const SsimWin w = dqo_ssim_window();
     const dim3 grid((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, 3), block(SS_T * SS_T);
     const int nblocks = (int)(grid.x * grid.y * grid.z);
     DQO_LAUNCH("ssim_map_kernel", ssim_map_kernel, grid, block, s, W, H, img, gt, w, maps, partial);

@@ -2,17 +2,24 @@
 frame from slam.py:155,184 and from metric.py — without a host round trip per number.
 
     eval_picture(render_output, gt_color, gt_depth, min_depth, max_depth)  ->  float32 [8] on the device (ROW)
-    eval_picture_dict(row)                                                 ->  the reference's dict (the ONE host read)
+    ms_ssim(image, gt)                                                     ->  float32 [20] on the device (MS_ROW)
+    eval_picture_dict(row, ms_row=None)                                    ->  the reference's dict (the ONE host read)
 
 One HIP launch (libdqoraster.so: dqo_eval_picture, csrc/map_eval.hip) forms psnr (eval.py:63), the colour L1 (:70) and the depth
 statements (:115-126) from double sums added in a fixed order: a row is bitwise reproducible.  The SSIM slot is filled by
 dqo_map_ssim_fwd_bwd in value-only mode (two more launches).  Nothing is read back, so a keyframe set is evaluated into a [K, 8] table
 (`out=`, `row=`) and read once; the calls can be captured in a graph.
 
-What is NOT here: the reference's "ssim" key is MS-SSIM (pytorch_msssim's `ms_ssim`, eval.py:64) and it also reports LPIPS (`lpips`
-AlexNet, :65-68).  Neither library exists on this platform, so neither value can be pinned against its source, and neither is built.
-Slot 4 / the "ssim" key here is the SINGLE-SCALE SSIM of utils/loss_utils.py:60-100 (the one the mapping loss uses), and there is no
-"lpips" key.  The picture dumps (`save_picture`) and the semantic / instance branches are not part of this either.
+The reference's "ssim" key is MS-SSIM (pytorch_msssim's `ms_ssim`, eval.py:19-25, :64), NOT the single-scale SSIM of slot 4: `ms_ssim`
+(libdqoraster.so: dqo_eval_ms_ssim, csrc/map_msssim.hip — nine launches, nothing read back) forms it with its fifteen per-level factors
+into a row of its own, and eval_picture_dict(row, ms_row) reports it under "ssim".  pytorch_msssim does not exist on this platform: the
+kernels follow the algorithm as its published source states it (tests/msssim_oracle.py restates it), and are held to that restatement,
+not to a value recorded from the library.
+
+What is NOT here: the reference also reports LPIPS (`lpips` AlexNet, :65-68).  Its weights do not exist on this platform, so the value
+cannot be pinned against its source and is not built: there is no "lpips" key.  Slot 4 of ROW stays the SINGLE-SCALE SSIM of
+utils/loss_utils.py:60-100 (the one the mapping loss uses).  The picture dumps (`save_picture`) and the semantic / instance branches are
+not part of this either.
 
 Geometry evaluation — eval_pcd, SLAM/eval.py:190-282: accuracy, completion, chamfer distance and precision / recall / F1 per distance
 threshold of a reconstruction against a ground-truth point set — stays on the device as well:
@@ -37,6 +44,9 @@ import torch
 import _dqo_native as N
 
 ROW = ("psnr", "color_loss", "depth_loss", "valid_pixel_ratio", "ssim", "mse_r", "mse_g", "mse_b")
+
+MS_ROW = (("ms_ssim", "ms_r", "ms_g", "ms_b") + tuple(f"F{l}_{c}" for l in range(5) for c in "rgb") + ("unused19",))
+MS_MIN_SIDE = 161  # pytorch_msssim asserts smaller_side > (11 - 1) * 2 ** 4
 
 PCD_THRES_MAX = 8
 PCD_ROW = (("accuracy", "completion", "chamfer", "n_thres") + tuple(f"{n}{t}" for t in range(PCD_THRES_MAX) for n in ("P", "R", "F1_"))
@@ -76,8 +86,9 @@ def eval_picture(render_output, gt_color, gt_depth, min_depth, max_depth, out=No
     call does not synchronise; eval_picture_dict(row) does the single host read.  Identical images give psnr = +inf, a frame without a
     valid depth pixel depth_loss = NaN: the reference's values.  ssim=False leaves slot 4 alone (NaN in a new row).
 
-    The reference's `ssim` key is MS-SSIM from pytorch_msssim and it also reports LPIPS; neither library exists on this platform, so
-    neither is built: slot 4 is the single-scale SSIM of utils/loss_utils.py:60-100 (dqo_map_ssim_fwd_bwd, value only).
+    Slot 4 is the single-scale SSIM of utils/loss_utils.py:60-100 (dqo_map_ssim_fwd_bwd, value only).  The reference's `ssim` key is
+    MS-SSIM (pytorch_msssim's `ms_ssim`): that is ms_ssim()'s row, which eval_picture_dict takes as `ms_row`.  LPIPS is not built (no
+    AlexNet weights here).
 
     workspace_buffer: a tensor of workspace(W, H, device) the caller keeps (default: one per device and image size, kept by this
     module — calls that share it must be on one stream).  render_header: the geometry buffer of the forward that rendered the frame
@@ -115,11 +126,77 @@ def eval_picture(render_output, gt_color, gt_depth, min_depth, max_depth, out=No
     return out[int(row)]
 
 
-def eval_picture_dict(row_tensor):
+def ms_ssim_workspace(W, H, device):
+    """dqo_eval_ms_ssim's workspace at W x H as a uint8 tensor (zero when first used, handed back ready by every call): the ticket words,
+    the level means and the pooled levels 1..4 of both images."""
+    n = N.lib().dqo_eval_ms_ssim_workspace_bytes(int(W), int(H))
+    if n == 0:
+        raise RuntimeError(f"dqo_eval.ms_ssim: bad image size {W} x {H}: both sides must be at least {MS_MIN_SIDE} (five levels of an "
+                           "11-tap window)")
+    return torch.zeros((n,), dtype=torch.uint8, device=device)
+
+
+def ms_ssim(image, gt, out=None, row=0, *, workspace_buffer=None, render_header=None):
+    """MS-SSIM of a rendered image against its target, on the device: the reference's eval_ssim (SLAM/eval.py:19-25) —
+    pytorch_msssim.ms_ssim(image[None], gt[None], data_range=1.0, size_average=True), the `ssim` of eval_picture (:64).
+
+    image, gt: [3,H,W], used as they are (no clamp); both sides above 160 (the library's assertion), else RuntimeError before any launch.
+    Returns the float32 [20] device row (names: MS_ROW)
+        0 ms_ssim   1..3 the value per channel   4 + 3 l + c the factor of level l, channel c, after the clamp at 0   19 unused (NaN)
+    — a new tensor initialised to NaN, or out[row] of a caller-owned contiguous float32 [K,20] table, whose other rows are not touched.
+    The factors are in the row on purpose: an error at one level shows at that level.  Nothing is read back and the call does not
+    synchronise; a row is bitwise reproducible and the call can be captured in a graph.  The algorithm is pytorch_msssim's as its
+    published source states it; the library does not exist on this platform, so no value here was recorded from it.
+
+    workspace_buffer: a tensor of ms_ssim_workspace(W, H, device) the caller keeps (default: one per device and image size, kept by this
+    module — calls that share it must be on one stream).  render_header: as eval_picture's — a frame that overflowed its context gets
+    a row of NaN.  GPU tensors only: a CPU tensor raises RuntimeError."""
+    N.require_gpu(image, gt, out)
+    if not image.is_cuda:
+        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    lib, dev = N.lib(), image.device
+    H, W = int(image.shape[-2]), int(image.shape[-1])
+    f32 = torch.float32
+    image, gt = _image(image, 3, H, W, f32, "image"), _image(gt, 3, H, W, f32, "gt")
+    if min(H, W) < MS_MIN_SIDE:
+        raise RuntimeError(f"dqo_eval.ms_ssim: image size {W} x {H}: both sides must be at least {MS_MIN_SIDE} (the reference's library "
+                           "asserts smaller_side > 160)")
+    if out is None:
+        out, row = torch.full((1, 20), float("nan"), dtype=f32, device=dev), 0
+    if out.dim() != 2 or out.shape[1] != 20 or out.dtype != f32 or not out.is_contiguous() or not 0 <= int(row) < out.shape[0]:
+        raise RuntimeError("dqo_eval.ms_ssim: out must be a contiguous float32 [K,20] table and row one of its rows")
+    ws = workspace_buffer
+    if ws is None:
+        key = ("ms", _dev_index(dev), W, H)
+        ws = _workspaces.get(key)
+        if ws is None:
+            ws = _workspaces[key] = ms_ssim_workspace(W, H, dev)
+    with torch.cuda.device(dev):
+        N.check(lib.dqo_eval_ms_ssim(W, H, N.ptr(image), N.ptr(gt), N.ptr(render_header), out.data_ptr(), int(row), ws.data_ptr(), ws.numel(),
+                                     N.current_stream()))
+    return out[int(row)]
+
+
+def eval_picture_dict(row_tensor, ms_row=None):
     """The reference's `losses` dict (eval.py:178-185) from a device row — ONE host read.  Keys: valid_pixel_ratio, depth_loss,
-    normal_loss (0, as eval.py:167), psnr, ssim (single-scale, see eval_picture), plus color_loss.  No `lpips` key: not built."""
-    v = row_tensor.detach().reshape(-1)[:8].cpu().tolist()
-    return {"valid_pixel_ratio": v[3], "depth_loss": v[2], "normal_loss": 0, "psnr": v[0], "ssim": v[4], "color_loss": v[1]}
+    normal_loss (0, as eval.py:167), psnr, ssim, plus color_loss.  No `lpips` key: not built.
+    ms_row=None: `ssim` is slot 4, the single-scale SSIM (see eval_picture).  With ms_ssim()'s row of the same frame, `ssim` is that
+    row's slot 0 — the reference's quantity — and the single-scale value moves to `ssim_single_scale`.  Two rows that are views of one
+    tensor (one storage, at most 4 096 floats apart) are read in one transfer of the span that holds both; otherwise there are two reads."""
+    if ms_row is None:
+        v = row_tensor.detach().reshape(-1)[:8].cpu().tolist()
+        return {"valid_pixel_ratio": v[3], "depth_loss": v[2], "normal_loss": 0, "psnr": v[0], "ssim": v[4], "color_loss": v[1]}
+    r, m = row_tensor.detach(), ms_row.detach()
+    a, b = r.storage_offset(), m.storage_offset()
+    lo, hi = min(a, b), max(a + 8, b + 1)
+    if (r.dtype == m.dtype == torch.float32 and r.is_contiguous() and m.is_contiguous() and r.numel() >= 8 and hi - lo <= 4096
+            and r.untyped_storage().data_ptr() == m.untyped_storage().data_ptr()):
+        span = torch.as_strided(r, (hi - lo,), (1,), lo).cpu().tolist()
+        v, ms = span[a - lo:a - lo + 8], span[b - lo]
+    else:
+        v, ms = r.reshape(-1)[:8].cpu().tolist(), m.reshape(-1)[:1].cpu().tolist()[0]
+    return {"valid_pixel_ratio": v[3], "depth_loss": v[2], "normal_loss": 0, "psnr": v[0], "ssim": ms, "color_loss": v[1],
+            "ssim_single_scale": v[4]}
 
 
 def _points(t, name):

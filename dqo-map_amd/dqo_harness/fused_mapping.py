@@ -247,6 +247,7 @@ class FusedMapper:
         self._lifecycle = {}  # maintain(): lifecycle_step's vote words and workspace ("_lifecycle"), made anew when P changes
         self._maintain_ctx = None  # maintain(): the persistent buffers of its render (_maintain_render)
         self._eval_tables, self._eval_ws = {}, None  # evaluate(): its [K,8] table per K, and dqo_eval's workspace
+        self._eval_ms_ws = None  # evaluate_ms_ssim(): dqo_eval.ms_ssim's workspace
         # refresh_window(): its [K] ratio table per K, dqo_window_masks' workspace, the uint8 [P] row flags of its render (per P)
         self._window_ratios, self._window_ws, self._window_flags = {}, None, None
         self._sample_ctx, self.sample_header = None, None  # sample_new(): the sampler's row buffers and workspace; its last header
@@ -707,14 +708,37 @@ class FusedMapper:
         The FIRST call for a (P, H, W) sizes the render's context from one 32-byte header read, exactly as maintain() does; after that a
         call reads nothing back, allocates nothing and does not synchronise.  A frame that outgrows that context leaves a row of NaN; the
         caller checks maintain_overflowed() where it can afford a read (it tells about the LAST frame rendered, and makes the next call
-        size a new context).  "ssim" is the single-scale SSIM of utils/loss_utils.py:60-100; the reference's MS-SSIM and LPIPS are not
-        built (dqo_eval)."""
+        size a new context).  Slot 4, "ssim", is the single-scale SSIM of utils/loss_utils.py:60-100; the reference's own "ssim", MS-SSIM,
+        comes from evaluate_ms_ssim (the same renders, a second table); its LPIPS is not built (dqo_eval)."""
+        return self._evaluate(frames, min_depth, max_depth, out, None)
+
+    @torch.no_grad()
+    def evaluate_ms_ssim(self, frames, ms_ssim, min_depth=0.3, max_depth=5.0, out=None):
+        """evaluate(frames, min_depth, max_depth, out) that ALSO fills `ms_ssim`, a float32 [K,20] device table (dqo_eval.MS_ROW): row k
+        receives the reference's OWN "ssim", MS-SSIM (dqo_eval.ms_ssim, SLAM/eval.py:19-25, :64), of frame k's render — the render
+        eval_picture used, no second one, with the same render header; nine launches more per frame.  Returns the [K,8] table, byte for
+        byte evaluate()'s; dqo_eval.eval_picture_dict(table[k], ms_row=ms_ssim[k]) reports "ssim" (MS-SSIM) and "ssim_single_scale".
+        Both image sides must be above 160 (pytorch_msssim's assertion): RuntimeError before anything is rendered.  The workspace is
+        kept on the mapper; after the first call nothing is allocated or read."""
+        import dqo_eval
+        H, W = int(self.settings.image_height), int(self.settings.image_width)
+        if min(H, W) < dqo_eval.MS_MIN_SIDE:
+            raise RuntimeError(f"FusedMapper.evaluate_ms_ssim: both image sides must be above 160, the mapper's image is {W} x {H}")
+        K = len(frames)
+        if (not torch.is_tensor(ms_ssim) or tuple(ms_ssim.shape) != (K, 20) or ms_ssim.dtype != torch.float32 or not ms_ssim.is_contiguous()
+                or not ms_ssim.is_cuda):
+            raise RuntimeError(f"FusedMapper.evaluate_ms_ssim: ms_ssim must be a contiguous float32 [{K},20] device table")
+        return self._evaluate(frames, min_depth, max_depth, out, ms_ssim)
+
+    def _evaluate(self, frames, min_depth, max_depth, out, ms_ssim):
         import dqo_eval
         if self.attach_count_reducer is not None:
             raise NotImplementedError("FusedMapper.evaluate: a sharded mapper would need the whole map's render, a shard's shows its "
                                       "objects only (DESIGN.md §6)")
         dev, K = self.device, len(frames)
         H, W = int(self.settings.image_height), int(self.settings.image_width)
+        if ms_ssim is not None and self._eval_ms_ws is None:
+            self._eval_ms_ws = dqo_eval.ms_ssim_workspace(W, H, dev)
         if self._eval_ws is None:
             self._eval_ws = dqo_eval.workspace(W, H, dev)
         table = out
@@ -729,6 +753,8 @@ class FusedMapper:
                 o = c["out"]
                 dqo_eval.eval_picture(dict(render=o[0], depth=o[1], depth_index_map=o[3]), gt_color, gt_depth, min_depth, max_depth, out=table,
                                       row=k, workspace_buffer=self._eval_ws, render_header=c["geom"])
+                if ms_ssim is not None:
+                    dqo_eval.ms_ssim(o[0], gt_color, out=ms_ssim, row=k, workspace_buffer=self._eval_ms_ws, render_header=c["geom"])
         return table
 
     @torch.no_grad()

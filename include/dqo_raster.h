@@ -539,6 +539,29 @@ int dqo_eval_picture(int32_t W, int32_t H, const float* render, const float* gt_
                      const int32_t* depth_index, float min_depth, float max_depth, const DqoRastHeader* render_header, float* out, int32_t row,
                      void* workspace, size_t workspace_bytes, void* hipStream);
 
+/* dqo_eval_ms_ssim (ABI 5, symbols-only addition) — the "ssim" number of eval_picture (SLAM/eval.py:19-25, :64):
+ * pytorch_msssim.ms_ssim(image[None], gt[None], data_range=1.0, size_average=True), nothing read back.  render, gt_color: [3, H*W] planes,
+ * used as they are (no clamp).  Five levels; a level filters both images, their squares and their product with the separable 11-tap window
+ * of utils/loss_utils.py:41-58 as a VALID correlation ([h,w] -> [h-10,w-10]) and takes per channel the means of
+ *     cs = (2 s12 + C2) / (s1 + s2 + C2),   ss = ((2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1)) * cs,     C1 = 0.01^2, C2 = 0.03^2;
+ * between levels both images become avg_pool2d(kernel_size = 2, padding = (h % 2, w % 2)) (an odd side shifts the 2 x 2 grid by one and
+ * averages a zero into the first row / column; the divisor is always 4).  Factors: F[l][c] = max(mean cs of channel c at level l, 0) for
+ * l = 0..3, F[4][c] = max(mean ss at level 4, 0); ms_c = prod_l F[l][c] ** w[l], w = float32 (0.0448, 0.2856, 0.3001, 0.2363, 0.1333).
+ * cs and ss are float32 per pixel, as the reference's library; their sums are doubles added in a fixed order (see dqo_eval_picture) and
+ * everything from the means on is double, rounded once per slot: a row is bitwise reproducible.
+ * out + 20 * row receives twenty floats: 0 ms_ssim = (ms_r + ms_g + ms_b) / 3, 1..3 ms_r, ms_g, ms_b, 4 + 3 l + c the factor F[l][c]
+ *   (after the clamp), 19 NaN (unused).
+ * render_header (may be NULL): as dqo_eval_picture's — a frame that overflowed its capacity gets NaN in all twenty slots.
+ * Both sides must be > 160 (the library's assertion: smaller_side > (11 - 1) * 2^4) and W * H within dqo_eval_picture's limit;
+ * dqo_eval_ms_ssim_workspace_bytes returns 0 otherwise, the call DQO_ERR_INVALID_ARG — as for a NULL image or out, or a negative row — and
+ * DQO_ERR_WORKSPACE for a workspace that is too small, all before anything is launched.
+ * workspace: ZERO when first used and then left to this call, which hands it back ready for the next one — no zero fill, no allocation,
+ *   nine launches, capturable in a hipGraph.  It holds the pooled levels 1..4 (about 2 H W floats).  Calls that share a workspace must be
+ *   ordered (one stream). */
+size_t dqo_eval_ms_ssim_workspace_bytes(int32_t W, int32_t H);
+int dqo_eval_ms_ssim(int32_t W, int32_t H, const float* render, const float* gt_color, const DqoRastHeader* render_header, float* out,
+                     int32_t row, void* workspace, size_t workspace_bytes, void* hipStream);
+
 /* Dense exact 1-NN between two large sets (scipy's KDTree(ref).query(query) of SLAM/eval.py:190-226, one million points against one
  * million): dist2[i] = the smallest squared distance from query i to any kept reference, idx[i] (may be NULL) a reference attaining it,
  * in the caller's numbering; which one of several equally distant references is arbitrary.  A pair's distance is dx*dx + dy*dy + dz*dz in
