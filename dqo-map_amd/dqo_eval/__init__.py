@@ -31,9 +31,20 @@ threshold of a reconstruction against a ground-truth point set — stays on the 
 Two dense exact 1-NN searches (dqo_nn1, csrc/knn.hip) replace the 4 + 2 T scipy KDTree builds and single-threaded queries of the
 reference, one reduction launch (dqo_eval_pcd, csrc/map_eval.hip) forms every number from double sums added in a fixed order.
 
-What is NOT here: the reference's PREPARATION of the two sets — `trimesh.sample.sample_surface` on the ground-truth mesh (eval.py:247)
-and `np.random.choice` above `sample_nums` reconstructed points (:244), which it reads back from a PLY with open3d.  Neither trimesh nor
-open3d exists on this platform, so neither statement can be pinned against its source: the caller passes both sets as points.
+The reconstruction the reference evaluates where a config sets `pcd_densify` (replica, aithor, real, Cube_Diorama) is not one point per
+Gaussian but the DENSIFIED stable cloud — GaussianPointCloud.densify(1, 30, 5), SLAM/gaussian_pointcloud.py:67-130, 150 points on five
+ellipses per surfel — of which eval_pcd keeps `sample_nums` by np.random.choice (eval.py:244):
+
+    densify(xyz, scaling_raw, rotation_raw, ...)            ->  dict(points, normals, index, keep, header), all on the device
+
+One call (dqo_surfel_densify, csrc/map_densify.hip) forms the subsample of the densified cloud without ever holding the cloud; `keep`
+goes to eval_pcd as `rec_keep`.  (The Python function uploads the 2 * circle_num floats of its angle table per call: a host-blocking
+copy; the C entry itself does not synchronise.)  The draw is the key rule of csrc/dqo_sample_hash.h, not numpy's stream: the same distribution, a pure
+function of the arguments.
+
+What is NOT here: `trimesh.sample.sample_surface` on the ground-truth mesh (eval.py:247) — trimesh does not exist on this platform, so
+the statement cannot be pinned against its source: the caller passes the ground truth as points.  Writing `pcd_densify.ply` (open3d's
+layout) is not built either.
 
 GPU only: there is no CPU path.
 """
@@ -261,6 +272,79 @@ def nearest(query, ref, query_keep=None, ref_keep=None, query_transform=None, re
         N.check(lib.dqo_nn1(Q, N.ptr(query), N.ptr(qk), R, N.ptr(ref), N.ptr(rk), N.ptr(qx), N.ptr(rx), N.ptr(dist2), N.ptr(idx), ws.data_ptr(),
                             ws.numel(), N.current_stream()))
     return dist2, idx
+
+
+DENSIFY_HEADER = ("kept_rows", "N_lo", "N_hi", "n", "M", "threshold_key", "frame", "zero")
+DENSIFY_FRAMES = {"reference": 0, "surfel": 1}
+
+
+def densify_theta(circle_num, seed=0):
+    """The reference's angles (gaussian_pointcloud.py:79): torch.rand(1, circle_num) * torch.pi * 2 from a CPU generator seeded with
+    `seed`, as a float32 [circle_num] CPU tensor."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(int(seed))
+    return (torch.rand(1, int(circle_num), generator=g) * torch.pi * 2).reshape(-1)
+
+
+def densify(xyz, scaling_raw, rotation_raw, sigma=1, circle_num=30, levels=5, theta=None, keep=None, sample_nums=None, seed=0,
+            frame="reference", want_normals=True, want_index=False, workspace_buffer=None):
+    """GaussianPointCloud.densify(sigma, circle_num, levels) (SLAM/gaussian_pointcloud.py:67-130) of the rows `keep` names, and of its
+    N = M * (kept rows) points (M = circle_num * levels * sigma per row) the n = min(N, sample_nums) that eval_pcd would evaluate
+    (SLAM/eval.py:244) — one device step that never holds the densified cloud (dqo_surfel_densify, include/dqo_raster.h).
+
+    xyz [P,3], scaling_raw [P,3] (log scales), rotation_raw [P,4] (r, x, y, z): contiguous float32 device tensors, the map's raw
+    parameters.  theta: [circle_num] angles (None: densify_theta(circle_num, seed), the reference's torch.rand on the CPU); their float32
+    torch.cos / torch.sin are formed on the CPU and uploaded, so the kernel calls no device cosine.  keep: uint8 / bool [P], 0 = the row
+    gives no point.  sample_nums None: cap = P * M, every point of the kept rows comes out; else cap = min(P * M, sample_nums).
+    frame "reference": the points the reference writes to pcd_densify.ply — its matmul has the plane vectors as ROWS, so a rotated
+    surfel's points do not lie in its plane; "surfel": mean + x p0 + z p1, the evident intent.
+    Returns dict(points [cap,3], normals [cap,3] | None, index int64 [cap] | None (the virtual index v = row * M + column of every
+    point), keep uint8 [cap] (1 for the first n rows, 0 behind: eval_pcd's `rec_keep`), header int32 [8] (DENSIFY_HEADER)).  Rows of
+    points / normals / index at and behind n are not written.  The subsample takes the n smallest keys of csrc/dqo_sample_hash.h (draw
+    3) in ascending v: not numpy's stream, the same distribution.  Nothing is read back.  The C entry does not synchronise; this
+    function forms the cos / sin table on the CPU and uploads it from pageable memory on every call, a small copy the host waits for
+    (it is inside every time measured through this function).
+    GPU tensors only: a CPU tensor raises RuntimeError."""
+    N.require_gpu(xyz, scaling_raw, rotation_raw, keep)
+    if not (xyz.is_cuda and scaling_raw.is_cuda and rotation_raw.is_cuda):
+        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    lib, dev = N.lib(), xyz.device
+    P = int(xyz.shape[0]) if xyz.dim() == 2 else -1
+    for t, w, name in ((xyz, 3, "xyz"), (scaling_raw, 3, "scaling_raw"), (rotation_raw, 4, "rotation_raw")):
+        if t.dim() != 2 or tuple(t.shape) != (P, w) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError(f"dqo_eval.densify: {name} must be a contiguous float32 [{max(P, 0)},{w}] tensor on {dev}, got "
+                               f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    if frame not in DENSIFY_FRAMES:
+        raise RuntimeError(f"dqo_eval.densify: frame must be one of {sorted(DENSIFY_FRAMES)}, got {frame!r}")
+    sigma, circle_num, levels = int(sigma), int(circle_num), int(levels)
+    nbytes = lib.dqo_surfel_densify_workspace_bytes(P, circle_num, levels, sigma)
+    if nbytes == 0:
+        raise RuntimeError(f"dqo_eval.densify: bad sizes P = {P}, (sigma, circle_num, levels) = ({sigma}, {circle_num}, {levels}): each at "
+                           "least 1, circle_num at most 1024, at most 65535 points per row and fewer than 2^32 in all")
+    M = circle_num * levels * sigma
+    if sample_nums is not None and int(sample_nums) < 1:
+        raise RuntimeError(f"dqo_eval.densify: sample_nums must be at least 1, got {sample_nums}")
+    cap = P * M if sample_nums is None else min(P * M, int(sample_nums))
+    rk = _keep(keep, P, "keep")
+    if rk is not None and rk.device != dev:
+        raise RuntimeError(f"dqo_eval.densify: keep must be on {dev}")
+    if theta is None:
+        theta = densify_theta(circle_num, seed)
+    theta = torch.as_tensor(theta).detach().to("cpu", torch.float32).reshape(-1)
+    if theta.numel() != circle_num:
+        raise RuntimeError(f"dqo_eval.densify: theta must have circle_num = {circle_num} entries, got {theta.numel()}")
+    circle_cs = torch.cat([torch.cos(theta), torch.sin(theta)]).contiguous().to(dev)  # (gaussian_pointcloud.py:104-105, on the CPU)
+    ws = workspace_buffer if workspace_buffer is not None else _workspace(("densify", _dev_index(dev), P, M), nbytes, dev)
+    points = torch.empty((cap, 3), dtype=torch.float32, device=dev)
+    normals = torch.empty((cap, 3), dtype=torch.float32, device=dev) if want_normals else None
+    index = torch.empty((cap,), dtype=torch.int64, device=dev) if want_index else None
+    keep_out = torch.empty((cap,), dtype=torch.uint8, device=dev)
+    header = torch.empty((8,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        N.check(lib.dqo_surfel_densify(P, N.ptr(xyz), N.ptr(scaling_raw), N.ptr(rotation_raw), N.ptr(rk), circle_num, levels, sigma,
+                                       N.ptr(circle_cs), DENSIFY_FRAMES[frame], int(seed) & (2 ** 64 - 1), cap, N.ptr(points), N.ptr(normals),
+                                       N.ptr(index), N.ptr(keep_out), N.ptr(header), ws.data_ptr(), ws.numel(), N.current_stream()))
+    return dict(points=points, normals=normals, index=index, keep=keep_out, header=header)
 
 
 def pcd_workspace(n_gt, n_rec, device):

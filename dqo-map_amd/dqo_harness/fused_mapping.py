@@ -758,15 +758,52 @@ class FusedMapper:
         return table
 
     @torch.no_grad()
+    def densify(self, rows="stable", **kw):
+        """The densified cloud the reference evaluates where a config sets pcd_densify: stable_pointcloud.densify(1, 30, 5)
+        (slam.py:202-206, SLAM/gaussian_pointcloud.py:67-130) and eval_pcd's subsample of it (SLAM/eval.py:244), from this mapper's raw
+        parameters through dqo_eval.densify, whose keywords (sigma, circle_num, levels, theta, sample_nums, seed, frame, want_normals,
+        want_index, workspace_buffer) pass through and whose dict comes back.  rows "stable": the rows of the reference's
+        stable_pointcloud, alive & stable (needs track_lifecycle()); "all": every Gaussian of the map (`alive`, or every row of a mapper
+        without spare rows).  Nothing is read back."""
+        import dqo_eval
+        if "keep" in kw:
+            raise RuntimeError("FusedMapper.densify: the row mask is chosen with rows=, not keep=")
+        if rows == "stable":
+            keep = self.stable_rows().to(torch.uint8)
+        elif rows == "all":
+            keep = self.alive
+        else:
+            raise RuntimeError(f"FusedMapper.densify: rows must be 'stable' or 'all', got {rows!r}")
+        return dqo_eval.densify(self.xyz.detach(), self.scaling_raw.detach(), self.rotation_raw.detach(), keep=keep, **kw)
+
+    @torch.no_grad()
     def evaluate_geometry(self, gt_points, dist_thres=(0.03,), transform=None, out=None, row=0):
         """How good the map's GEOMETRY is against a ground-truth point set: eval_pcd of the reference (SLAM/eval.py:190-282) — accuracy,
         completion, chamfer distance, precision / recall / F1 per threshold — through dqo_eval.eval_pcd.  The reconstruction is this
         mapper's own `xyz` buffer with `alive` as the row mask: the points the reference reads back from the PLY it saved, without the
         file, a copy or a host read.  gt_points [G,3]: the ground-truth points (sampling them from a mesh is the caller's, dqo_eval);
         transform: [3,4] / [4,4] applied to the map's points (:241).  Returns the float32 [32] device row (dqo_eval.PCD_ROW; out[row] of
-        a caller-owned [K,32] table if given); dqo_eval.eval_pcd_dict reads it.  The workspace is dqo_eval's, per device and sizes."""
+        a caller-owned [K,32] table if given); dqo_eval.eval_pcd_dict reads it.  The workspace is dqo_eval's, per device and sizes.
+        The configs with pcd_densify evaluate another point set: evaluate_geometry_densified."""
         import dqo_eval
         return dqo_eval.eval_pcd(gt_points, self.xyz.detach(), dist_thres, transform, rec_keep=self.alive, out=out, row=row)
+
+    @torch.no_grad()
+    def evaluate_geometry_densified(self, gt_points, dist_thres=(0.03,), transform=None, out=None, row=0, densify=None):
+        """evaluate_geometry on the point set the reference evaluates for the configs with pcd_densify (replica, aithor, real,
+        Cube_Diorama; metric.py:156-157): the densified cloud of densify()'s rows, subsampled as eval_pcd does (SLAM/eval.py:244).
+        densify: a dict of densify()'s keywords, `rows` included (None or {}: the reference's call, densify(1, 30, 5) of the stable
+        cloud); its `sample_nums` defaults to 1 000 000 as eval_frame's and may be at most 2^25 - 1, dqo_nn1's limit.  densify()'s
+        `keep` goes in as eval_pcd's row mask, so no count is read back.  Everything else as evaluate_geometry."""
+        import dqo_eval
+        kw = dict(densify or {})
+        kw.setdefault("sample_nums", 1000000)
+        if kw["sample_nums"] is None or not 1 <= int(kw["sample_nums"]) < (1 << 25):
+            raise RuntimeError("FusedMapper.evaluate_geometry_densified: densify's sample_nums must be in [1, 2^25 - 1], got "
+                               f"{kw['sample_nums']}")
+        kw.setdefault("want_normals", False)
+        d = self.densify(**kw)
+        return dqo_eval.eval_pcd(gt_points, d["points"], dist_thres, transform, rec_keep=d["keep"], out=out, row=row)
 
     # configs/base.yaml:32-33, 47-52
     SAMPLE_DEFAULTS = dict(uniform_sample_num=50000, add_transmission_thres=0.5, add_depth_thres=None, add_color_thres=0.1,

@@ -600,6 +600,44 @@ int dqo_eval_pcd(int32_t n_gt, const float* gt_xyz, const uint8_t* gt_keep, int3
                  const float* rec_xform, int32_t n_thres, const float* thres_host, float* out_table, int32_t row, void* workspace,
                  size_t workspace_bytes, void* hipStream);
 
+/* dqo_surfel_densify (ABI 5, symbols-only addition) — the point set the reference evaluates its geometry on where a config sets
+ * pcd_densify: GaussianPointCloud.densify(sigma, circle_num, levels) (SLAM/gaussian_pointcloud.py:67-130; slam.py:202-206 calls
+ * densify(1, 30, 5)) followed by eval_pcd's subsample (SLAM/eval.py:244), in one step that never holds the densified cloud.
+ * Row i (xyz [P,3], scaling_raw [P,3] log scales, rotation_raw [P,4] as r, x, y, z) becomes M = circle_num * levels * sigma virtual
+ * points v = i * M + c, c = (b * levels + l) * circle_num + k (block b < sigma, level l < levels, angle k < circle_num):
+ *     order        the three axes in ascending order of the RAW scales (exp is monotone); equal scales: the lower axis index first
+ *                  (torch.argmin / argsort leave ties unspecified)
+ *     n, p0, p1    columns order[0], order[1], order[2] of build_rotation(q / |q|) (utils/general_utils.py:108-131), each divided by
+ *                  (its norm + 1e-8);  axis0 = exp(scaling_raw[order[1]]), axis1 = exp(scaling_raw[order[2]])
+ *     a            (axis0 * sigma) * float((l + 0.5) / levels), plus axis0 * b in blocks b >= 1;  b_ the same with axis1
+ *     x, z         a * cos(theta_k),  b_ * sin(theta_k)          circle_cs: 2 * circle_num floats on the device, the cosines then the sines
+ *     frame 0      DQO_DENSIFY_FRAME_REFERENCE: out = mean + (p0.x x + p0.z z,  n.x x + n.z z,  p1.x x + p1.z z) — what the reference
+ *                  writes to pcd_densify.ply: its matmul has p0, n, p1 as the ROWS of the matrix (:107-121)
+ *     frame 1      DQO_DENSIFY_FRAME_SURFEL: out = mean + x p0 + z p1, points in the surfel's plane (the evident intent)
+ *     normal       n, for every point of the row (:122)
+ * every float statement rounded once, none contracted (csrc/map_densify.hip lists them in order).
+ * row_keep: NULL = every row; else one byte per row, 0 = the row gives no point.  N = M * (kept rows).
+ * Subsample (replaces the host's np.random.choice, same distribution): virtual point v of a kept row gets
+ *   key = hash32(seed, draw 3, v) (csrc/dqo_sample_hash.h, all 32 bits; draws 0-2 are dqo_growth_sample's); the n = min(N, cap) smallest
+ *   keys are chosen — keys of different v never tie — and the chosen points come out in ascending v.  A radix select, never a sort.
+ * points [cap,3], normals [cap,3] (may be NULL), index [cap] int64 (may be NULL): v of each emitted point (its surfel: v / M); rows at
+ *   and behind n are NOT written.  keep [cap] uint8, written for ALL cap rows: 1 for the first n, 0 behind — dqo_nn1 / dqo_eval_pcd take
+ *   it as rec_keep, so no count is ever read back.
+ * header (8 x int32, overwritten): 0 kept rows, 1 / 2 N's low / high word, 3 n, 4 M, 5 the threshold key (the n-th smallest key; -1, all
+ *   bits set, when n == N: nothing was rejected), 6 frame, 7 zero.
+ * DQO_ERR_INVALID_ARG before anything is launched: a NULL required pointer, P < 1, circle_num, levels or sigma < 1, circle_num > 1024,
+ *   M > 65535, P * M >= 2^32, cap < 1, an unknown frame.  DQO_ERR_WORKSPACE: the workspace is too small.
+ * workspace: dqo_surfel_densify_workspace_bytes(P, circle_num, levels, sigma) bytes (0 for a bad size), ANY contents: its head is zeroed
+ *   by the call's first launch (dqo_growth_sample's contract).  No allocation, no synchronisation, nothing read back, integer atomics
+ *   only: the output is a pure function of the arguments.  Calls that share a workspace must be ordered (one stream). */
+#define DQO_DENSIFY_FRAME_REFERENCE 0
+#define DQO_DENSIFY_FRAME_SURFEL 1
+size_t dqo_surfel_densify_workspace_bytes(int32_t P, int32_t circle_num, int32_t levels, int32_t sigma);
+int dqo_surfel_densify(int32_t P, const float* xyz, const float* scaling_raw, const float* rotation_raw, const uint8_t* row_keep,
+                       int32_t circle_num, int32_t levels, int32_t sigma, const float* circle_cs, int32_t frame, uint64_t seed, int64_t cap,
+                       float* points, float* normals, int64_t* index, uint8_t* keep, int32_t* header, void* workspace,
+                       size_t workspace_bytes, void* hipStream);
+
 /* Batched dual-quadric residual over B independent (object, view) pairs: loss = 1 - IoU(obs, bbox(ellipsoid, P34)),
  * with gradients.  valid[b] = 0 when loss == 1 (the reference skips that Adam step). */
 int dqo_quadric_iou_fwd_bwd(int32_t B, const float* axes, const float* R, const float* center, const float* P34,
