@@ -103,6 +103,12 @@ int dqo_launch_msssim(int W, int H, const float* render, const float* gt_color, 
 int dqo_launch_eval_picture(int W, int H, const float* render, const float* gt_color, const float* depth, const float* gt_depth,
                             const int32_t* depth_index, float min_depth, float max_depth, const DqoRastHeader* header, float* out_row,
                             void* ws, hipStream_t s);
+size_t dqo_map_pack_ws_bytes(int64_t P);
+int dqo_launch_map_pack(int P, int M, int with_conf, const float* xyz, const float* shs, const float* opacity_raw, const float* scaling_raw,
+                        const float* rotation_raw, const float* confidence, const uint8_t* alive, const uint8_t* stable, float* table,
+                        int32_t* header, void* ws, hipStream_t s);
+int dqo_launch_map_unpack(int M, int64_t n, int64_t first_row, int has_conf, const float* table, float* xyz, float* shs, float* opacity_raw,
+                          float* scaling_raw, float* rotation_raw, float* confidence, hipStream_t s);
 int dqo_launch_attach_pixels(int n, const float* xyz, const float* V, float fx, float fy, float cx, float cy, int W, int H,
                              const int32_t* pixel_object, int32_t* lin, int32_t* sparse, unsigned long long* tile_objects, hipStream_t s);
 int dqo_launch_attach_decide(int n, const float* xyz, const float* opacity, const int32_t* obj, const int32_t* lin, const int32_t* hit_index,
@@ -921,6 +927,42 @@ DQO_API int dqo_surfel_densify(int32_t P, const float* xyz, const float* scaling
     }
     return dqo_launch_surfel_densify(P, xyz, scaling_raw, rotation_raw, row_keep, circle_num, levels, sigma, circle_cs, frame, seed, cap, points,
                                      normals, index, keep, header, ws, (hipStream_t)stream);
+}
+
+// the vertex table of a map checkpoint: at most 2^31 - 1 floats, SH sizes up to 64 coefficients (a tile of 64 rows stays below 64 KiB of LDS)
+static bool map_table_size_ok(int64_t rows, int32_t M, int32_t with_conf) {
+    return rows >= 1 && M >= 1 && M <= 64 && rows * (int64_t)(6 + 3 * M + 8 + (with_conf ? 1 : 0)) <= (int64_t)0x7fffffff;
+}
+
+DQO_API size_t dqo_map_pack_workspace_bytes(int32_t P) { return P >= 1 ? dqo_map_pack_ws_bytes(P) : 0; }
+
+DQO_API int dqo_map_pack_rows(int32_t P, int32_t M, int32_t include_confidence, const float* xyz, const float* shs, const float* opacity_raw,
+                              const float* scaling_raw, const float* rotation_raw, const float* confidence, const uint8_t* alive,
+                              const uint8_t* stable, float* table, int64_t table_rows, int32_t* header, void* ws, size_t ws_bytes,
+                              void* stream) {
+    DQO_CHECK_ARG(P >= 1, "bad row count %d", P);
+    DQO_CHECK_ARG(M >= 1 && M <= 64, "bad SH size M = %d: 1 to 64 coefficients", M);
+    DQO_CHECK_ARG(map_table_size_ok(P, M, include_confidence), "bad size: a table of %d rows exceeds 2^31 - 1 floats", P);
+    DQO_CHECK_ARG(xyz && shs && opacity_raw && scaling_raw && rotation_raw && table && header, "null pointer");
+    DQO_CHECK_ARG(table_rows >= (int64_t)P, "table capacity %lld rows is below the map's %d rows", (long long)table_rows, P);
+    if (ws == nullptr || ws_bytes < dqo_map_pack_ws_bytes(P)) {
+        dqo_set_error("map pack workspace too small (%zu < %zu)", ws_bytes, dqo_map_pack_ws_bytes(P));
+        return DQO_ERR_WORKSPACE;
+    }
+    return dqo_launch_map_pack(P, M, include_confidence != 0, xyz, shs, opacity_raw, scaling_raw, rotation_raw, confidence, alive, stable, table,
+                               header, ws, (hipStream_t)stream);
+}
+
+DQO_API int dqo_map_unpack_rows(int32_t P, int32_t M, int32_t n, int32_t first_row, int32_t has_confidence, const float* table, float* xyz,
+                                float* shs, float* opacity_raw, float* scaling_raw, float* rotation_raw, float* confidence, void* stream) {
+    DQO_CHECK_ARG(P >= 1 && n >= 0 && first_row >= 0 && (int64_t)first_row + n <= (int64_t)P, "bad size: rows [%d, %d + %d) of a map of %d rows",
+                  first_row, first_row, n, P);
+    DQO_CHECK_ARG(M >= 1 && M <= 64, "bad SH size M = %d: 1 to 64 coefficients", M);
+    DQO_CHECK_ARG(map_table_size_ok(P, M, 1), "bad size: a table of %d rows exceeds 2^31 - 1 floats", P);
+    if (n == 0) return DQO_OK;
+    DQO_CHECK_ARG(table && xyz && shs && opacity_raw && scaling_raw && rotation_raw, "null pointer");
+    return dqo_launch_map_unpack(M, n, first_row, has_confidence != 0, table, xyz, shs, opacity_raw, scaling_raw, rotation_raw, confidence,
+                                 (hipStream_t)stream);
 }
 
 DQO_API size_t dqo_icp_workspace_bytes(void) { return dqo_icp_ws_bytes(); }

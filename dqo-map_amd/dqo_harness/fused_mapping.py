@@ -248,6 +248,7 @@ class FusedMapper:
         self._maintain_ctx = None  # maintain(): the persistent buffers of its render (_maintain_render)
         self._eval_tables, self._eval_ws = {}, None  # evaluate(): its [K,8] table per K, and dqo_eval's workspace
         self._eval_ms_ws = None  # evaluate_ms_ssim(): dqo_eval.ms_ssim's workspace
+        self._checkpoint = {}  # pack_rows() / save_model(): workspace, header, table and pinned staging buffer, made anew when P changes
         # refresh_window(): its [K] ratio table per K, dqo_window_masks' workspace, the uint8 [P] row flags of its render (per P)
         self._window_ratios, self._window_ws, self._window_flags = {}, None, None
         self._sample_ctx, self.sample_header = None, None  # sample_new(): the sampler's row buffers and workspace; its last header
@@ -534,6 +535,7 @@ class FusedMapper:
         self._attach_n, self._act_valid = 0, False
         self._lifecycle, self._maintain_ctx = {}, None
         self._window_flags = None
+        self._checkpoint = {}
         self._drop_graphs()
 
     @torch.no_grad()
@@ -805,8 +807,163 @@ class FusedMapper:
         d = self.densify(**kw)
         return dqo_eval.eval_pcd(gt_points, d["points"], dist_thres, transform, rec_keep=d["keep"], out=out, row=row)
 
+    # ------------------------------------------------------------------ checkpoints (csrc/map_checkpoint.hip) -----------
+    @torch.no_grad()
+    def pack_rows(self, include_confidence=True, out=None):
+        """(table, header), both on the device: the map's live rows as the vertex table of the reference's PLY files
+        (dqo_ply.pack_rows, dqo_map_pack_rows) — the unstable cloud's rows in row order, then the stable cloud's; header int32 [2] =
+        {U, S}.  The first U rows are path.ply's vertex data, the last S path_stable.ply's, all of them path_merge.ply's.  A mapper
+        without track_lifecycle() is all unstable, one without spare rows all alive.  table: `out` (float32 [>= P, C]) or this mapper's
+        own buffer, overwritten by the next call; rows at and behind U + S keep their bytes.  Two launches on the current stream, no
+        allocation after the first call, no synchronisation."""
+        import dqo_ply
+        P, C = self.P, 6 + 3 * self.M + 8 + (1 if include_confidence else 0)
+        k = self._checkpoint
+        if k.get("P") != P:
+            k = self._checkpoint = dict(P=P, ws=dqo_ply.pack_workspace(P, self.device),
+                                        header=torch.empty((2,), dtype=torch.int32, device=self.device))
+        if out is None:
+            if "buf" not in k:  # (one buffer serves both column sets: the wider table's size)
+                k["buf"] = torch.empty((P * (6 + 3 * self.M + 9),), dtype=torch.float32, device=self.device)
+            out = k["buf"][:P * C].view(P, C)
+        return dqo_ply.pack_rows(self.xyz, self.shs, self.opacity_raw, self.scaling_raw, self.rotation_raw, self.confidence, self.alive,
+                                 self.stable, include_confidence, out=out, header=k["header"], workspace_buffer=k["ws"])
+
+    @torch.no_grad()
+    def save_model(self, path, save_data=True, save_sibr=True, save_merge=True):
+        """gaussian_map.save_model (SLAM/multiprocess/mapper.py:1580-1608; slam.py:164, 194) of this mapper's map; `path` is the prefix.
+            save_data   path.ply, path_stable.ply            with the confidence column
+            save_sibr   path_sibr.ply, path_stable_sibr.ply  without it
+            save_merge  path_merge.ply / path_merge_sibr.ply, the unstable rows then the stable rows — only when both clouds have rows
+        A file of an empty cloud is not written (gaussian_pointcloud.py:642-643).  Per column set: ONE pack_rows, ONE device-to-host copy
+        into a pinned staging buffer this mapper keeps, and every file is written from a slice of that buffer (the merged file is the
+        table itself: nothing is re-read).  It runs on the current stream, behind whatever replays are enqueued, and synchronises once
+        per column set; the first set's copy takes all P rows (the counts are not known yet), the second the U + S live rows.
+        Returns {file: rows} of the files written.  Not built: save_model_ply_obj (SAVE_obj_ply is False in the reference); a sharded
+        mapper saves its shard."""
+        import dqo_ply
+        P, M = self.P, self.M
+        written, counts = {}, None
+        for with_conf, tag in ((True, ""), (False, "_sibr")):
+            if not (save_data if with_conf else save_sibr):
+                continue
+            C = 6 + 3 * M + 8 + (1 if with_conf else 0)
+            table, header = self.pack_rows(include_confidence=with_conf)
+            k = self._checkpoint
+            if "host" not in k:
+                k["host"] = torch.empty((P * (6 + 3 * M + 9),), dtype=torch.float32, pin_memory=True)
+                k["host_header"] = torch.empty((2,), dtype=torch.int32, pin_memory=True)
+            n = P if counts is None else counts[0] + counts[1]
+            k["host"][:n * C].copy_(table.view(-1)[:n * C], non_blocking=True)
+            k["host_header"].copy_(header, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+            counts = (int(k["host_header"][0]), int(k["host_header"][1]))
+            U, S = counts
+            rows = k["host"][:(U + S) * C].view(U + S, C)
+            files = [(path + tag + ".ply", rows[:U]), (path + "_stable" + tag + ".ply", rows[U:])]
+            if save_merge and U > 0 and S > 0:
+                files.append((path + "_merge" + tag + ".ply", rows))
+            for name, part in files:
+                if dqo_ply.write_vertex_table(name, part, 3 * (M - 1), with_conf) > 0:
+                    written[name] = int(part.shape[0])
+        return written
+
+    @staticmethod
+    def _read_checkpoint(path, stable_path):
+        """[(table of `path` or None, has_confidence), (table of `stable_path` or None, ...)], and the SH size the files agree on."""
+        import dqo_ply
+        tables, M = [], None
+        for p in (path, stable_path):
+            if p is None:
+                tables.append(None)
+                continue
+            props, table = dqo_ply.read_vertex_table(p)
+            n_rest = sum(1 for q in props if q.startswith("f_rest_"))
+            conf = "confidence" in props
+            if n_rest % 3 != 0 or list(props) != dqo_ply.attribute_names(n_rest, conf):
+                raise RuntimeError(f"{p}: not a map file: its properties are not those of save_model_ply")
+            if M is not None and M != n_rest // 3 + 1:
+                raise RuntimeError(f"{p}: {n_rest} f_rest columns, {path} has {3 * (M - 1)}")
+            M = n_rest // 3 + 1
+            tables.append(np.ascontiguousarray(table, np.float32))
+        if M is None:
+            raise RuntimeError("FusedMapper.load_model: neither file was given")
+        return tables, M
+
+    @torch.no_grad()
+    def load_model(self, path, stable_path=None, tick=0):
+        """gaussian_map.pointcloud.load / stable_pointcloud.load (SLAM/gaussian_pointcloud.py:132-207; metric.py, metric_obj.py,
+        make_mesh.py) into THIS mapper, in place: the rows of `path` become the unstable cloud in rows [0, U), the rows of `stable_path`
+        the stable cloud in rows [U, U + S) (either may be None: an empty cloud has no file).  Values are the files' raw parameters, bit
+        for bit (the constructor's clamp and log are not applied); confidence is the file's column, or zeros without one.  add_tick =
+        tick, both strike counters and every Adam moment zero; every other row becomes a spare row exactly as _free_rows leaves one.
+        P never changes: more rows than P is a RuntimeError that names the reserve() needed.  A stable file on a mapper that does not
+        track lifecycles starts tracking.  One host-to-device copy and one launch (dqo_map_unpack_rows) per file.  Row flags: every live
+        row is trained and rendered (set_training_rows() names the next call's clouds).  Ends with
+        begin_mapping_call(reset_optimizer=True); the captured graphs are marked stale — their capacities were sized on another map."""
+        tables, M = self._read_checkpoint(path, stable_path)
+        self._load_tables(tables, M, tick)
+        return self
+
+    def _load_tables(self, tables, M, tick):
+        import dqo_ply
+        dev, P = self.device, self.P
+        if M != self.M:
+            raise RuntimeError(f"FusedMapper.load_model: the files hold {M} SH coefficients per Gaussian, this mapper {self.M}")
+        if self.gaussian_object is not None:
+            raise RuntimeError("FusedMapper.load_model: the files carry no object ids; switch the gate off (set_object_gate(None, None)) first")
+        U, S = (0 if t is None else int(t.shape[0]) for t in tables)
+        n = U + S
+        if n > P:
+            raise RuntimeError(f"FusedMapper.load_model: the files hold {n} rows, this mapper has {P}: reserve({n - P}) more rows first")
+        if self.stable is None and S > 0:
+            self.track_lifecycle()
+        if self.alive is None and n < P:
+            self.alive = torch.ones((P,), dtype=torch.uint8, device=dev)
+        first = 0
+        for t in tables:
+            if t is not None and t.shape[0] > 0:
+                dqo_ply.unpack_rows(torch.from_numpy(t).to(dev), first, self.xyz, self.shs, self.opacity_raw, self.scaling_raw,
+                                    self.rotation_raw, self.confidence)
+                first += int(t.shape[0])
+        if self.alive is not None:
+            self.alive[:n] = 1
+        if self.stable is not None:
+            self.stable[:U] = 0
+            self.stable[U:n] = 1
+            self.add_tick[:n] = int(tick)
+            self.depth_error_counter.zero_(), self.color_error_counter.zero_()
+        if n < P:
+            self._free_rows(torch.arange(n, P, device=dev))
+        self._n_spare, self._n_spare_stale = P - n, False
+        self._maintain_ctx = self._last_probe = None  # (sized on the map that was here before)
+        self.set_training_rows()
+        self._act_valid = False
+        self.begin_mapping_call(reset_optimizer=True)
+        for g in self._graphs():
+            g.stale = True
+        self.activate()  # (a captured iteration starts from the activations of the current parameters)
+
+    @classmethod
+    def from_model_ply(cls, path, stable_path, settings, device, spare_rows=0, **kw):
+        """A mapper of the files' row count and SH size, started from disk: the constructor on placeholder values, reserve(spare_rows),
+        track_lifecycle() and load_model(path, stable_path) — what metric.py / make_mesh.py do with a saved map.  kw: the constructor's
+        (and `tick` for load_model)."""
+        tick = kw.pop("tick", 0)
+        tables, M = cls._read_checkpoint(path, stable_path)
+        n = sum(int(t.shape[0]) for t in tables if t is not None)
+        if n < 1:
+            raise RuntimeError("FusedMapper.from_model_ply: the files hold no rows")
+        scene = dict(xyz=np.zeros((n, 3), np.float32), shs=np.zeros((n, M, 3), np.float32), opacity=np.full((n, 1), 0.5, np.float32),
+                     scales=np.ones((n, 3), np.float32), rotations=np.tile(np.array([1, 0, 0, 0], np.float32), (n, 1)))
+        fm = cls(scene, settings, device, **kw)
+        fm.reserve(spare_rows)
+        fm.track_lifecycle()
+        fm._load_tables(tables, M, tick)
+        return fm
+
     # configs/base.yaml:32-33, 47-52
-    SAMPLE_DEFAULTS = dict(uniform_sample_num=50000, add_transmission_thres=0.5, add_depth_thres=None, add_color_thres=0.1,
+    SAMPLE_DEFAULTS =dict(uniform_sample_num=50000, add_transmission_thres=0.5, add_depth_thres=None, add_color_thres=0.1,
                            transmission_sample_ratio=1.0, error_sample_ratio=0.05, init_opacity=0.99, xyz_factor=(1.0, 1.0, 0.1),
                            capacity=None, key_bits=32)
 

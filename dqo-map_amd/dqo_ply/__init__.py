@@ -1,4 +1,6 @@
-"""PLY wire format of DQO-MAP's Gaussian maps — host-side interchange, no GPU work.
+"""PLY wire format of DQO-MAP's Gaussian maps: the host-side formatter / parser, and the device-side vertex table
+(pack_rows / unpack_rows: dqo_map_pack_rows / dqo_map_unpack_rows, csrc/map_checkpoint.hip) that FusedMapper.save_model / load_model
+move with one copy per table.
 
 Reads and writes the files of /root/reference/SLAM/gaussian_pointcloud.py:
     construct_list_of_attributes :557-588   x y z nx ny nz f_dc_0..2 f_rest_0..(3(D+1)^2-4) opacity scale_0..2 rot_0..3 [confidence]
@@ -41,6 +43,87 @@ def save_model_ply(path, xyz, shs, opacity_raw, scaling_raw, rotation_raw, confi
     with open(path, "wb") as fh:
         fh.write(header.encode("ascii"))
         fh.write(table.tobytes())
+
+
+def write_vertex_table(path, table, n_rest, include_confidence=True):
+    """The file save_model_ply writes, from its finished vertex table: `table` float32 [rows, C] (array or host tensor, C-contiguous;
+    C = 9 + n_rest + 8 (+ 1), the columns of attribute_names(n_rest, include_confidence)).  The header, then the table's bytes as they
+    are — no value is converted.  Nothing is written for zero rows (gaussian_pointcloud.py:642-643).  Returns the row count."""
+    t = table.numpy() if hasattr(table, "numpy") else np.asarray(table)
+    names = attribute_names(n_rest, include_confidence)
+    if t.ndim != 2 or t.shape[1] != len(names) or t.dtype != np.float32 or not t.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"write_vertex_table: the table must be C-contiguous float32 [rows, {len(names)}], got {t.dtype} {t.shape}")
+    rows = t.shape[0]
+    if rows == 0:
+        return 0
+    header = "ply\nformat binary_little_endian 1.0\n" + f"element vertex {rows}\n" + "".join(f"property float {n}\n" for n in names) + "end_header\n"
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(t.data)  # (native float32 is little-endian here, as in save_model_ply; no copy of the table is made)
+    return rows
+
+
+def read_vertex_table(path):
+    """(property names, float32 [rows, len(names)] table) of a map file, binary or ascii; a binary table keeps every value's bits."""
+    return _read_table(path)
+
+
+def pack_workspace(P, device):
+    """dqo_map_pack_rows' workspace for a map of P rows: zero when first used, then left to pack_rows."""
+    import torch
+    import _dqo_native as N
+    return torch.zeros((N.lib().dqo_map_pack_workspace_bytes(int(P)),), dtype=torch.uint8, device=device)
+
+
+def pack_rows(xyz, shs, opacity_raw, scaling_raw, rotation_raw, confidence=None, alive=None, stable=None, include_confidence=True, out=None,
+              header=None, workspace_buffer=None):
+    """(table, header): the vertex table of the map's live rows, on the device (dqo_map_pack_rows, include/dqo_raster.h).  Buffers are
+    contiguous float32 device tensors of P rows (shs [P,M,3]); alive / stable uint8 [P] or None.  table float32 [P, C] (`out`, or new:
+    rows at and behind U + S keep their bytes), header int32 [2] = {U, S} — the unstable cloud's rows first, then the stable cloud's.
+    Nothing is read back."""
+    import torch
+    import _dqo_native as N
+    N.require_gpu(xyz, shs, opacity_raw, scaling_raw, rotation_raw, confidence, alive, stable, out, header, workspace_buffer)
+    P, M = int(xyz.shape[0]), int(shs.shape[1])
+    C = 6 + 3 * M + 8 + (1 if include_confidence else 0)
+    for t, n, dt in ((xyz, 3 * P, torch.float32), (shs, 3 * M * P, torch.float32), (opacity_raw, P, torch.float32),
+                     (scaling_raw, 3 * P, torch.float32), (rotation_raw, 4 * P, torch.float32), (confidence, P, torch.float32),
+                     (alive, P, torch.uint8), (stable, P, torch.uint8)):
+        if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous()):
+            raise RuntimeError(f"pack_rows: every buffer is contiguous, of the map's {P} rows and of its own type (got {t.dtype} {tuple(t.shape)})")
+    dev = xyz.device
+    if out is None:
+        out = torch.empty((P, C), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[1] != C or not out.is_contiguous():
+        raise RuntimeError(f"pack_rows: out must be a contiguous float32 [rows, {C}] table")
+    if header is None:
+        header = torch.empty((2,), dtype=torch.int32, device=dev)
+    if workspace_buffer is None:
+        workspace_buffer = pack_workspace(P, dev)
+    with torch.cuda.device(dev):
+        N.check(N.lib().dqo_map_pack_rows(P, M, 1 if include_confidence else 0, N.ptr(xyz), N.ptr(shs), N.ptr(opacity_raw), N.ptr(scaling_raw),
+                                          N.ptr(rotation_raw), N.ptr(confidence), N.ptr(alive), N.ptr(stable), N.ptr(out), int(out.shape[0]),
+                                          N.ptr(header), N.ptr(workspace_buffer), workspace_buffer.numel(), N.current_stream()))
+    return out, header
+
+
+def unpack_rows(table, first_row, xyz, shs, opacity_raw, scaling_raw, rotation_raw, confidence=None):
+    """The inverse (dqo_map_unpack_rows): the rows of `table` (float32 [n, C] on the device, with or without the confidence column) into
+    rows [first_row, first_row + n) of the buffers; a table without the column writes zeros into `confidence`."""
+    import torch
+    import _dqo_native as N
+    N.require_gpu(table, xyz, shs, opacity_raw, scaling_raw, rotation_raw, confidence)
+    P, M = int(xyz.shape[0]), int(shs.shape[1])
+    C = 6 + 3 * M + 8
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] not in (C, C + 1) or not table.is_contiguous():
+        raise RuntimeError(f"unpack_rows: the table must be contiguous float32 [n, {C}] or [n, {C + 1}], got {table.dtype} {tuple(table.shape)}")
+    for t, n in ((xyz, 3 * P), (shs, 3 * M * P), (opacity_raw, P), (scaling_raw, 3 * P), (rotation_raw, 4 * P), (confidence, P)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous()):
+            raise RuntimeError(f"unpack_rows: every buffer is contiguous float32 of the map's {P} rows")
+    with torch.cuda.device(xyz.device):
+        N.check(N.lib().dqo_map_unpack_rows(P, M, int(table.shape[0]), int(first_row), 1 if table.shape[1] == C + 1 else 0, N.ptr(table),
+                                            N.ptr(xyz), N.ptr(shs), N.ptr(opacity_raw), N.ptr(scaling_raw), N.ptr(rotation_raw),
+                                            N.ptr(confidence), N.current_stream()))
 
 
 def _read_table(path):

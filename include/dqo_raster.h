@@ -777,6 +777,36 @@ int dqo_window_masks(int32_t W, int32_t H, int32_t mode, const float* T_map, con
                      int32_t k, uint8_t* render_mask, int32_t* tile_mask, float* ratio_out, const DqoRastHeader* render_header,
                      void* workspace, size_t workspace_bytes, void* hipStream);
 
+/* dqo_map_pack_rows / dqo_map_unpack_rows (ABI 5, symbols-only addition) — the vertex table of a map checkpoint, built and taken apart on
+ * the device.  They replace the host work of gaussian_map.save_model (SLAM/multiprocess/mapper.py:1571-1608: save_model_ply,
+ * SLAM/gaussian_pointcloud.py:641-684, for each cloud, and merge_ply, SLAM/utils.py:414-423) and of pointcloud.load
+ * (gaussian_pointcloud.py:132-207): boolean indexing of every buffer, seven device-to-host copies, the SH transpose, np.concatenate.
+ * The map: P rows of xyz [P,3], shs [P,M,3] (coefficient 0 = f_dc), opacity_raw [P], scaling_raw [P,3], rotation_raw [P,4],
+ *   confidence [P] (NULL = zeros), alive uint8 [P] (NULL = every row is a Gaussian), stable uint8 [P] (NULL = every row is unstable).
+ * A table row, all float32, C = 6 + 3 M + 8 + (confidence ? 1 : 0) columns in the order of construct_list_of_attributes (:557-588):
+ *   x y z | three zeros (the normals, :645) | f_dc_0..2 | f_rest channel-major, shs[:, 1:, :] as [3, M - 1] | opacity | scale_0..2 |
+ *   rot_0..3 | confidence.  Values are copied as 32-bit words: NaN payloads, -0 and denormals keep their bits.
+ * dqo_map_pack_rows: the alive rows with stable == 0 in ascending row index, then the alive rows with stable != 0 in ascending row
+ *   index — the row order of the reference's merged file.  header (2 x int32, device, overwritten) = {U, S}: the first U table rows are the
+ *   vertex data of path.ply, the last S those of path_stable.ply, all U + S those of path_merge.ply.  table must hold table_rows >= P rows
+ *   (an overflow is impossible without a host read); rows at and behind U + S are NOT written.  Two launches, nothing read back, no float
+ *   atomics, integer atomics only for the last-block ticket: the table is a pure function of the inputs.
+ *   workspace: dqo_map_pack_workspace_bytes(P) bytes (0 for P < 1), ZERO when first used and then left to this call, which hands it back
+ *   ready for the next one (capturable in a hipGraph).  Calls that share a workspace must be ordered (one stream).
+ * dqo_map_unpack_rows: table rows [0, n) (has_confidence: with the column) into rows [first_row, first_row + n) of a map of P rows;
+ *   a table without the column writes confidence as zero; confidence NULL: not written.  One launch.  n = 0: nothing is done.
+ * Size limit: a table of P rows has at most 2^31 - 1 floats (P * C <= 2^31 - 1; the kernels index with 64 bits all the same), and
+ *   1 <= M <= 64.
+ * DQO_ERR_INVALID_ARG before anything is launched: P < 1, M outside [1, 64], P * C > 2^31 - 1, a NULL required pointer, table_rows < P,
+ *   n < 0, first_row < 0, first_row + n > P.  DQO_ERR_WORKSPACE: the workspace is NULL or too small. */
+size_t dqo_map_pack_workspace_bytes(int32_t P);
+int dqo_map_pack_rows(int32_t P, int32_t M, int32_t include_confidence, const float* xyz, const float* shs, const float* opacity_raw,
+                      const float* scaling_raw, const float* rotation_raw, const float* confidence, const uint8_t* alive,
+                      const uint8_t* stable, float* table, int64_t table_rows, int32_t* header, void* workspace, size_t workspace_bytes,
+                      void* hipStream);
+int dqo_map_unpack_rows(int32_t P, int32_t M, int32_t n, int32_t first_row, int32_t has_confidence, const float* table, float* xyz,
+                        float* shs, float* opacity_raw, float* scaling_raw, float* rotation_raw, float* confidence, void* hipStream);
+
 /* Row f4 — normal equations of one Gauss-Newton iteration of the point-to-plane ICP tracker (SLAM/icp.py:51-123:
  * compute_residuals_jacobian + compute_jtj + compute_jtr).  vertex / normal maps are [H, W, 3] fp32, pose10 a row-major 4x4
  * (maps frame-0 points into frame 1), normal_threshold the cosine.  Out: JtJ [6,6] (rotation block first), JtR [6],
