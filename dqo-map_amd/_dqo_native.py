@@ -124,7 +124,7 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_eval_ms_ssim_workspace_bytes", "dqo_eval_ms_ssim",
            "dqo_nn1_workspace_bytes", "dqo_nn1", "dqo_eval_pcd_workspace_bytes", "dqo_eval_pcd", "dqo_window_masks_workspace_bytes",
            "dqo_window_masks", "dqo_surfel_densify_workspace_bytes", "dqo_surfel_densify", "dqo_map_pack_workspace_bytes",
-           "dqo_map_pack_rows", "dqo_map_unpack_rows")
+           "dqo_map_pack_rows", "dqo_map_unpack_rows", "dqo_mesh_sample_workspace_bytes", "dqo_mesh_sample")
 
 _lib = None
 
@@ -242,6 +242,9 @@ def lib():
         L.dqo_surfel_densify_workspace_bytes.argtypes = [c_i32] * 4
         L.dqo_surfel_densify.argtypes = ([c_i32] + [c_vp] * 4 + [c_i32] * 3 + [c_vp, c_i32, ctypes.c_uint64, ctypes.c_int64] + [c_vp] * 6 +
                                          [ctypes.c_size_t, c_vp])
+        L.dqo_mesh_sample_workspace_bytes.restype = ctypes.c_size_t
+        L.dqo_mesh_sample_workspace_bytes.argtypes = [c_i32, c_i32]
+        L.dqo_mesh_sample.argtypes = [c_i32, c_vp, c_i32, c_vp, c_i32, ctypes.c_uint64] + [c_vp] * 5 + [ctypes.c_size_t, c_vp]
         L.dqo_map_pack_workspace_bytes.restype = ctypes.c_size_t
         L.dqo_map_pack_workspace_bytes.argtypes = [c_i32]
         L.dqo_map_pack_rows.argtypes = [c_i32] * 3 + [c_vp] * 9 + [ctypes.c_int64, c_vp, c_vp, ctypes.c_size_t, c_vp]

@@ -96,6 +96,9 @@ size_t dqo_densify_ws_bytes(uint64_t total);
 int dqo_launch_surfel_densify(int P, const float* xyz, const float* scaling_raw, const float* rotation_raw, const uint8_t* row_keep,
                               int circle_num, int levels, int sigma, const float* circle_cs, int frame, uint64_t seed, int64_t cap,
                               float* points, float* normals, int64_t* index, uint8_t* keep, int32_t* header, void* ws, hipStream_t s);
+size_t dqo_mesh_sample_ws_bytes(int64_t F);
+int dqo_launch_mesh_sample(int V, const float* vertices, int F, const int32_t* faces, int count, uint64_t seed, float* points,
+                           int32_t* face_index, uint8_t* keep, int32_t* header, void* ws, hipStream_t s);
 size_t dqo_eval_ws_bytes(int64_t HW);
 size_t dqo_msssim_ws_bytes(int W, int H);
 int dqo_launch_msssim(int W, int H, const float* render, const float* gt_color, const DqoRastHeader* header, float* out_row, void* ws,
@@ -927,6 +930,26 @@ DQO_API int dqo_surfel_densify(int32_t P, const float* xyz, const float* scaling
     }
     return dqo_launch_surfel_densify(P, xyz, scaling_raw, rotation_raw, row_keep, circle_num, levels, sigma, circle_cs, frame, seed, cap, points,
                                      normals, index, keep, header, ws, (hipStream_t)stream);
+}
+
+// trimesh.sample.sample_surface on the ground-truth mesh (SLAM/eval.py:247).  The face table's and dqo_nn1's row limit
+static bool mesh_size_ok(int32_t n) { return n >= 1 && n < (1 << 25); }
+
+DQO_API size_t dqo_mesh_sample_workspace_bytes(int32_t F, int32_t count) {
+    return mesh_size_ok(F) && mesh_size_ok(count) ? dqo_mesh_sample_ws_bytes(F) : 0;
+}
+
+DQO_API int dqo_mesh_sample(int32_t V, const float* vertices, int32_t F, const int32_t* faces, int32_t count, uint64_t seed, float* points,
+                            int32_t* face_index, uint8_t* keep, int32_t* header, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(V >= 1, "bad vertex count %d", V);
+    DQO_CHECK_ARG(mesh_size_ok(F), "bad face count %d: 1 to 2^25 - 1 faces", F);
+    DQO_CHECK_ARG(mesh_size_ok(count), "bad sample count %d: 1 to 2^25 - 1 samples", count);
+    DQO_CHECK_ARG(vertices && faces && points && keep && header, "null pointer");
+    if (ws == nullptr || ws_bytes < dqo_mesh_sample_ws_bytes(F)) {
+        dqo_set_error("mesh sample workspace too small (%zu < %zu)", ws_bytes, dqo_mesh_sample_ws_bytes(F));
+        return DQO_ERR_WORKSPACE;
+    }
+    return dqo_launch_mesh_sample(V, vertices, F, faces, count, seed, points, face_index, keep, header, ws, (hipStream_t)stream);
 }
 
 // the vertex table of a map checkpoint: at most 2^31 - 1 floats, SH sizes up to 64 coefficients (a tile of 64 rows stays below 64 KiB of LDS)

@@ -3,7 +3,8 @@
 // same bits on every run whatever order the blocks ran in, and the ticket words handed back at zero — no zero fill per call, so the entry
 // can be captured in a hipGraph.  Users: map_eval.hip (eval_picture_kernel, eval_pcd_kernel), map_msssim.hip (msssim_level_kernel), map_lifecycle.hip (the two cloud limits and
 // the frame's counts), map_tilemask.hip (window_masks_kernel: ticket only, its last block selects tiles), map_checkpoint.hip (map_pack_count_kernel: its last block scans
-// the blocks' row counts), dqo_adam.h (ticket only, unfenced).
+// the blocks' row counts), map_meshsample.hip (mesh_area_kernel: max and counts; mesh_quantise_kernel: its last block scans the blocks'
+// quanta), dqo_adam.h (ticket only, unfenced).
 //
 // Deliberately NOT users, and not to be "finished" into this header:
 //   - map_sample.hip's sp_last_block: one uint32 word per kernel, zeroed by the call's first launch, a few hundred blocks — a different

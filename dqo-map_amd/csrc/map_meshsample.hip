@@ -1,0 +1,284 @@
+// Geometry evaluation for gfx950, the ground truth's point set: trimesh.sample.sample_surface(mesh_gt, sample_nums) of eval_pcd
+// (SLAM/eval.py:247) — face areas, their cumulative table, one draw located in the table per sample, two draws folded back into the
+// triangle — on the device, from the mesh's vertex and face tensors.  include/dqo_raster.h (dqo_mesh_sample) states the contract.
+//
+// Two departures from trimesh, both so that the result is a pure function of the arguments: the draws are the seeded key rule of
+// dqo_sample_hash.h (draws 4-7; 0-2 are dqo_growth_sample's, 3 is dqo_surfel_densify's) instead of numpy's stream, and the cumulative
+// table holds INTEGER quanta of area instead of float sums, so it does not depend on the order the areas are added in.
+//
+// This file is compiled with -ffp-contract=off.  The statements, one rounding each, in this order (tests/mesh_oracle.py restates them):
+//   area     a face with an index outside [0, V) has A = 0 and its vertices are never loaded.  Otherwise the nine floats become doubles,
+//            e1 = b - a,  e2 = c - a
+//            cx = e1y * e2z - e1z * e2y,  cy = e1z * e2x - e1x * e2z,  cz = e1x * e2y - e1y * e2x
+//            A  = 0.5 * sqrt((cx * cx + cy * cy) + cz * cz);  a non-finite A becomes 0
+//   quanta   amax = the largest A (a max: order-free);  frexp(amax) = (m, x), x = 0 for amax = 0;  e = 61 - bit_length(F) - x
+//            q_f = (uint64) floor(ldexp(A_f, e)) < 2^(61 - bit_length(F)): the total stays below 2^61
+//   table    cum[f] = q_0 + ... + q_f (uint64),  total = cum[F - 1];  total = 0 (no area): nothing is drawn, keep is all 0
+//   draw     k_d = dqo_sample_key(seed_word, dqo_sample_draw_word(seed_word, 4 + d), i, 0xffffffff), d = 0..3, for sample i
+//            t = floor(total * (k0 * 2^32 + k1) / 2^64) = __umul64hi(total, key64);  the face is the first f with cum[f] > t (a binary
+//            search; a face without quanta is never picked)
+//            u = k2 * 2^-32,  v = k3 * 2^-32 (double, exact);  if (u + v > 1.0)  u = 1.0 - u,  v = 1.0 - v
+//            p = a + ((b - a) * u + (c - a) * v) per component in double, then rounded once to float
+//
+// Four launches of 256-thread blocks, a block owning MS_BLOCK = 1024 consecutive faces, thread t faces 4 t .. 4 t + 3 of them:
+//   area      A_f into the table's slot f (as a double), the block's max and its two counts as partials; the block that takes the launch's
+//             last ticket (dqo_reduce.h) folds the partials, forms e and writes header slots 1-4 and 7
+//   quantise  q_f over A_f in place, the block's sum as a partial; the last block turns the sums, in block-index order, into exclusive
+//             offsets in place (256 per round, a carried total) and writes the total and header slots 0, 5, 6
+//   scan      the block's inclusive prefix of its q on top of its offset: cum, in place
+//   sample    one thread per sample
+// Integer atomics only (the tickets, which come back at zero: no zero fill per call); nothing is allocated, read back or synchronised.
+#include "dqo_common.h"
+#include "dqo_reduce.h"
+#include "dqo_sample_hash.h"
+
+namespace {
+
+enum {
+    MS_THREADS = 256,
+    MS_FPT = 4,                       // faces per thread
+    MS_BLOCK = MS_THREADS * MS_FPT,   // faces per block: DQO_MESH_SCAN_BLOCK
+    MS_STATE_BYTES = 256,             // behind the ticket words: MsState
+};
+static_assert(MS_BLOCK == DQO_MESH_SCAN_BLOCK, "include/dqo_raster.h and the kernels disagree");
+
+typedef unsigned long long u64;
+
+struct MsState {
+    u64 total;   // cum[F - 1]
+    int32_t e;   // the quantum exponent
+};
+
+struct MsArgs {
+    int V, F, count;
+    uint32_t nblocks;
+    uint32_t seed_word, draw_word[4];
+    const float* vertices;
+    const int32_t* faces;
+    float* points;
+    int32_t* face_index;
+    uint8_t* keep;
+    int32_t* header;
+    int32_t* ticket;
+    MsState* state;
+    u64 *bmax, *bcount, *bsum;  // [nblocks] partials: the max area's bits, bad | degenerate << 32, the quanta (then the offsets)
+    u64* cum;                   // [F] A_f as a double, then q_f, then cum[f]
+};
+
+__device__ __forceinline__ u64 ms_ld(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void ms_st(u64* p, u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// The block's sum / max of x over its threads, for every thread.  s_wave: 4 words of LDS, free again after the call's last barrier.
+template <bool MAX>
+__device__ __forceinline__ u64 ms_block_fold(u64 x, u64* s_wave) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const u64 y = __shfl_xor(x, d, 64);
+        x = MAX ? (y > x ? y : x) : x + y;
+    }
+    __syncthreads();  // (s_wave may still be read by the previous call)
+    if (lane == 0) s_wave[wave] = x;
+    __syncthreads();
+    u64 r = s_wave[0];
+#pragma unroll
+    for (int w = 1; w < 4; w++) r = MAX ? (s_wave[w] > r ? s_wave[w] : r) : r + s_wave[w];
+    return r;
+}
+
+__device__ __forceinline__ bool ms_in_range(int32_t i, int V) { return (uint32_t)i < (uint32_t)V; }
+
+__device__ __forceinline__ void ms_vertex(const float* vertices, int32_t i, double out[3]) {
+    const float* p = vertices + 3 * (size_t)i;
+    out[0] = (double)p[0], out[1] = (double)p[1], out[2] = (double)p[2];
+}
+
+// ---- area -------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MS_THREADS) void mesh_area_kernel(MsArgs a) {
+    __shared__ u64 s_wave[4];
+    __shared__ int s_last;
+    const int tid = threadIdx.x;
+    u64 amax = 0ull, bad = 0ull, degenerate = 0ull;
+    const int64_t f0 = (int64_t)blockIdx.x * MS_BLOCK + (int64_t)tid * MS_FPT;
+#pragma unroll
+    for (int j = 0; j < MS_FPT; j++) {
+        const int64_t f = f0 + j;
+        if (f >= (int64_t)a.F) break;
+        const int32_t ia = a.faces[3 * f], ib = a.faces[3 * f + 1], ic = a.faces[3 * f + 2];
+        double A = 0.0;
+        if (!(ms_in_range(ia, a.V) && ms_in_range(ib, a.V) && ms_in_range(ic, a.V))) {
+            bad++;
+        } else {
+            double pa[3], pb[3], pc[3];
+            ms_vertex(a.vertices, ia, pa), ms_vertex(a.vertices, ib, pb), ms_vertex(a.vertices, ic, pc);
+            const double e1x = pb[0] - pa[0], e1y = pb[1] - pa[1], e1z = pb[2] - pa[2];
+            const double e2x = pc[0] - pa[0], e2y = pc[1] - pa[1], e2z = pc[2] - pa[2];
+            const double cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
+            A = 0.5 * sqrt((cx * cx + cy * cy) + cz * cz);
+            if (!(A > 0.0 && A < __builtin_huge_val())) A = 0.0, degenerate++;  // (zero, infinite or NaN)
+        }
+        a.cum[f] = (u64)__double_as_longlong(A);
+        const u64 bits = (u64)__double_as_longlong(A);  // (A >= 0: the bits order as the values do)
+        amax = bits > amax ? bits : amax;
+    }
+    amax = ms_block_fold<true>(amax, s_wave);
+    const u64 counts = ms_block_fold<false>(bad | (degenerate << 32), s_wave);  // (both below 2^25: no carry between the halves)
+    if (tid == 0) ms_st(&a.bmax[blockIdx.x], amax), ms_st(&a.bcount[blockIdx.x], counts);
+    if (!dqo_last_block(a.ticket, &s_last)) return;
+    u64 m = 0ull, c = 0ull;
+    for (uint32_t b = (uint32_t)tid; b < a.nblocks; b += MS_THREADS) {
+        const u64 x = ms_ld(&a.bmax[b]);
+        m = x > m ? x : m, c += ms_ld(&a.bcount[b]);
+    }
+    m = ms_block_fold<true>(m, s_wave), c = ms_block_fold<false>(c, s_wave);
+    if (tid == 0) {
+        int x = 0;
+        const double top = __longlong_as_double((long long)m);
+        if (top > 0.0) (void)frexp(top, &x);
+        const int e = 61 - (32 - __clz(a.F)) - x;
+        a.state->e = e;
+        a.header[1] = a.F, a.header[2] = (int32_t)(uint32_t)c, a.header[3] = (int32_t)(c >> 32), a.header[4] = e, a.header[7] = 0;
+    }
+}
+
+// this thread's four table entries of the block (0 behind F)
+__device__ __forceinline__ void ms_load4(const MsArgs& a, int64_t f0, u64 x[MS_FPT]) {
+#pragma unroll
+    for (int j = 0; j < MS_FPT; j++) x[j] = f0 + j < (int64_t)a.F ? a.cum[f0 + j] : 0ull;
+}
+
+// ---- quantise ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MS_THREADS) void mesh_quantise_kernel(MsArgs a) {
+    __shared__ u64 s_wave[4];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int e = a.state->e;
+    const int64_t f0 = (int64_t)blockIdx.x * MS_BLOCK + (int64_t)tid * MS_FPT;
+    u64 x[MS_FPT], sum = 0ull;
+    ms_load4(a, f0, x);
+#pragma unroll
+    for (int j = 0; j < MS_FPT; j++) {
+        if (f0 + j >= (int64_t)a.F) break;
+        const u64 q = (u64)floor(ldexp(__longlong_as_double((long long)x[j]), e));
+        a.cum[f0 + j] = q, sum += q;
+    }
+    sum = ms_block_fold<false>(sum, s_wave);
+    if (tid == 0) ms_st(&a.bsum[blockIdx.x], sum);
+    if (!dqo_last_block(a.ticket, &s_last)) return;
+    // the last block: the blocks' sums -> exclusive offsets, in block-index order
+    u64 carry = 0ull;
+    for (uint32_t base = 0; base < a.nblocks; base += MS_THREADS) {
+        const uint32_t b = base + (uint32_t)tid;
+        const u64 v = b < a.nblocks ? ms_ld(&a.bsum[b]) : 0ull;
+        u64 incl = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const u64 up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        __syncthreads();  // (s_wave is free: the round before has read it)
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        u64 before = carry;
+        for (int w = 0; w < wave; w++) before += s_wave[w];
+        if (b < a.nblocks) a.bsum[b] = before + (incl - v);
+        carry += ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+    }
+    if (tid == 0) {
+        a.state->total = carry;
+        a.header[0] = carry != 0ull ? a.count : 0;
+        a.header[5] = (int32_t)(uint32_t)carry, a.header[6] = (int32_t)(uint32_t)(carry >> 32);
+    }
+}
+
+// ---- scan -------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MS_THREADS) void mesh_scan_kernel(MsArgs a) {
+    __shared__ u64 s_wave[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t f0 = (int64_t)blockIdx.x * MS_BLOCK + (int64_t)tid * MS_FPT;
+    u64 x[MS_FPT];
+    ms_load4(a, f0, x);
+    const u64 own = ((x[0] + x[1]) + x[2]) + x[3];
+    u64 incl = own;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u64 up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += up;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    u64 run = a.bsum[blockIdx.x] + (incl - own);
+    for (int w = 0; w < wave; w++) run += s_wave[w];
+#pragma unroll
+    for (int j = 0; j < MS_FPT; j++) {
+        if (f0 + j >= (int64_t)a.F) break;
+        run += x[j];
+        a.cum[f0 + j] = run;
+    }
+}
+
+// ---- sample -----------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MS_THREADS) void mesh_sample_kernel(MsArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * MS_THREADS + threadIdx.x;
+    if (i >= (int64_t)a.count) return;
+    const u64 total = a.state->total;
+    if (total == 0ull) {  // no area: no point
+        a.keep[i] = 0;
+        return;
+    }
+    uint32_t k[4];
+#pragma unroll
+    for (int d = 0; d < 4; d++) k[d] = dqo_sample_key(a.seed_word, a.draw_word[d], (uint32_t)i, 0xffffffffu);
+    const u64 t = __umul64hi(total, ((u64)k[0] << 32) | (u64)k[1]);  // < total = cum[F - 1]
+    int lo = 0, hi = a.F - 1;
+    while (lo < hi) {  // the first f with cum[f] > t
+        const int mid = lo + ((hi - lo) >> 1);
+        if (a.cum[mid] > t) hi = mid;
+        else lo = mid + 1;
+    }
+    const int32_t ia = a.faces[3 * (size_t)lo], ib = a.faces[3 * (size_t)lo + 1], ic = a.faces[3 * (size_t)lo + 2];
+    if (!(ms_in_range(ia, a.V) && ms_in_range(ib, a.V) && ms_in_range(ic, a.V))) {  // (cannot happen: the face has quanta, so area)
+        a.keep[i] = 0;
+        return;
+    }
+    double pa[3], pb[3], pc[3];
+    ms_vertex(a.vertices, ia, pa), ms_vertex(a.vertices, ib, pb), ms_vertex(a.vertices, ic, pc);
+    double u = (double)k[2] * 0x1p-32, v = (double)k[3] * 0x1p-32;
+    if (u + v > 1.0) u = 1.0 - u, v = 1.0 - v;
+#pragma unroll
+    for (int d = 0; d < 3; d++) a.points[3 * i + d] = (float)(pa[d] + ((pb[d] - pa[d]) * u + (pc[d] - pa[d]) * v));
+    if (a.face_index != nullptr) a.face_index[i] = lo;
+    a.keep[i] = 1;
+}
+
+inline size_t ms_blocks(int64_t F) { return (size_t)((F + MS_BLOCK - 1) / MS_BLOCK); }
+inline size_t ms_partial_bytes(int64_t F) { return dqo_align_up(ms_blocks(F) * sizeof(u64), 256); }
+
+}  // namespace
+
+// the ticket words | MsState | bmax | bcount | bsum | cum (the last align_up(8 F, 256) bytes: dqo_eval.mesh_cum_view reads them for the tests)
+size_t dqo_mesh_sample_ws_bytes(int64_t F) {
+    return DQO_REDUCE_HEAD_WORDS * 4 + MS_STATE_BYTES + 3 * ms_partial_bytes(F) + dqo_align_up((size_t)F * sizeof(u64), 256);
+}
+
+int dqo_launch_mesh_sample(int V, const float* vertices, int F, const int32_t* faces, int count, uint64_t seed, float* points,
+                           int32_t* face_index, uint8_t* keep, int32_t* header, void* ws, hipStream_t s) {
+    MsArgs a;
+    a.V = V, a.F = F, a.count = count, a.nblocks = (uint32_t)ms_blocks(F);
+    a.seed_word = dqo_sample_seed_word(seed);
+    for (uint32_t d = 0; d < 4; d++) a.draw_word[d] = dqo_sample_draw_word(a.seed_word, 4u + d);
+    a.vertices = vertices, a.faces = faces, a.points = points, a.face_index = face_index, a.keep = keep, a.header = header;
+    char* p = (char*)ws;
+    a.ticket = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
+    a.state = (MsState*)p, p += MS_STATE_BYTES;
+    a.bmax = (u64*)p, p += ms_partial_bytes(F);
+    a.bcount = (u64*)p, p += ms_partial_bytes(F);
+    a.bsum = (u64*)p, p += ms_partial_bytes(F);
+    a.cum = (u64*)p;
+    const dim3 grid(a.nblocks), block(MS_THREADS);
+    DQO_LAUNCH("mesh_area_kernel", mesh_area_kernel, grid, block, s, a);
+    DQO_LAUNCH("mesh_quantise_kernel", mesh_quantise_kernel, grid, block, s, a);
+    DQO_LAUNCH("mesh_scan_kernel", mesh_scan_kernel, grid, block, s, a);
+    DQO_LAUNCH("mesh_sample_kernel", mesh_sample_kernel, dim3((unsigned)(((int64_t)count + MS_THREADS - 1) / MS_THREADS)), block, s, a);
+    return DQO_OK;
+}

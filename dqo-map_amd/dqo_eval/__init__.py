@@ -42,9 +42,19 @@ goes to eval_pcd as `rec_keep`.  (The Python function uploads the 2 * circle_num
 copy; the C entry itself does not synchronise.)  The draw is the key rule of csrc/dqo_sample_hash.h, not numpy's stream: the same distribution, a pure
 function of the arguments.
 
-What is NOT here: `trimesh.sample.sample_surface` on the ground-truth mesh (eval.py:247) — trimesh does not exist on this platform, so
-the statement cannot be pinned against its source: the caller passes the ground truth as points.  Writing `pcd_densify.ply` (open3d's
-layout) is not built either.
+The ground truth the reference evaluates against is `trimesh.sample.sample_surface(mesh_gt, sample_nums)` (eval.py:236, :247): points
+drawn on the mesh's surface, a face picked in proportion to its area and a uniform point inside it:
+
+    sample_surface(vertices, faces, count, seed)            ->  dict(points, face_index, keep, header), all on the device
+
+Four launches (dqo_mesh_sample, csrc/map_meshsample.hip) from the mesh's tensors (dqo_ply.read_mesh_ply reads the file on the host);
+`keep` goes to eval_pcd as `gt_keep`.  trimesh does not exist on this platform: the kernels follow its four public steps (face areas,
+their cumulative sum, one draw located in it, two draws folded back into the triangle where u + v > 1) and are held to a restatement
+(tests/mesh_oracle.py), not to a value recorded from the library.  Two departures, both so that a sample is a pure function of the
+arguments: the draws are the key rule of csrc/dqo_sample_hash.h instead of numpy's stream (the same distribution), and the cumulative
+table counts integer quanta of area instead of float sums (no summation order can reach it).
+
+What is NOT here: writing `pcd_densify.ply` (open3d's layout) is not built; the unused bounding box of eval.py:237-239 is not formed.
 
 GPU only: there is no CPU path.
 """
@@ -347,6 +357,62 @@ def densify(xyz, scaling_raw, rotation_raw, sigma=1, circle_num=30, levels=5, th
     return dict(points=points, normals=normals, index=index, keep=keep_out, header=header)
 
 
+MESH_HEADER = ("n", "F", "bad_index_faces", "zero_area_faces", "quantum_exponent", "total_lo", "total_hi", "zero")
+MESH_SCAN_BLOCK = 1024  # faces per block of the table's scan (include/dqo_raster.h: DQO_MESH_SCAN_BLOCK)
+
+
+def mesh_sample_workspace(F, count, device):
+    """dqo_mesh_sample's workspace for a mesh of F faces and `count` samples as a uint8 tensor (zero when first used, handed back ready
+    by every call)."""
+    n = N.lib().dqo_mesh_sample_workspace_bytes(int(F), int(count))
+    if n == 0:
+        raise RuntimeError(f"dqo_eval.sample_surface: bad sizes F = {F}, count = {count}: each in [1, 2^25 - 1]")
+    return torch.zeros((n,), dtype=torch.uint8, device=device)
+
+
+def mesh_cum_view(workspace_buffer, F):
+    """The cumulative table the last sample_surface call left in its workspace: int64 [F], cum[f] = the quanta of faces 0..f (below
+    2^61).  A view, for tests and inspection: the next call overwrites it."""
+    n = (8 * int(F) + 255) // 256 * 256  # (the workspace's last block)
+    return workspace_buffer[workspace_buffer.numel() - n:].view(torch.int64)[:int(F)]
+
+
+def sample_surface(vertices, faces, count, seed=0, want_face_index=False, workspace_buffer=None):
+    """trimesh.sample.sample_surface(mesh, count) (SLAM/eval.py:247) on the device: `count` points on the surface of a triangle mesh, a
+    face picked in proportion to its area, a uniform point inside it (dqo_mesh_sample, include/dqo_raster.h, states every statement).
+
+    vertices [V,3] float32, faces [F,3] int32 (dqo_ply.read_mesh_ply's arrays as device tensors), contiguous; count and F in
+    [1, 2^25 - 1]; seed: 64 bits — the draws are the key rule of csrc/dqo_sample_hash.h (draws 4-7), not numpy's stream.  A face with
+    an index outside [0, V), or of zero or non-finite area, gets no sample; both are counted in the header.
+    Returns dict(points float32 [count,3], face_index int32 [count] | None, keep uint8 [count] (1 everywhere, or all 0 when the mesh
+    has no area and no point was written: eval_pcd's `gt_keep`), header int32 [8] (MESH_HEADER)).  Nothing is read back, the call does
+    not synchronise and can be captured in a graph; the same arguments give the same bits.
+    workspace_buffer: a tensor of mesh_sample_workspace(F, count, device) the caller keeps (default: one per device and sizes, kept by
+    this module — calls that share it must be on one stream).  GPU tensors only: a CPU tensor raises RuntimeError."""
+    N.require_gpu(vertices, faces, workspace_buffer)
+    if not (vertices.is_cuda and faces.is_cuda):
+        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    lib, dev = N.lib(), vertices.device
+    for t, dt, name in ((vertices, torch.float32, "vertices"), (faces, torch.int32, "faces")):
+        if t.dim() != 2 or t.shape[1] != 3 or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError(f"dqo_eval.sample_surface: {name} must be a contiguous {dt} [n,3] tensor on {dev}, got {t.dtype} "
+                               f"{tuple(t.shape)} on {t.device}")
+    V, F, count = int(vertices.shape[0]), int(faces.shape[0]), int(count)
+    nbytes = lib.dqo_mesh_sample_workspace_bytes(F, count) if V >= 1 else 0
+    if nbytes == 0:
+        raise RuntimeError(f"dqo_eval.sample_surface: bad sizes V = {V}, F = {F}, count = {count}: at least one vertex, F and count in "
+                           "[1, 2^25 - 1]")
+    ws = workspace_buffer if workspace_buffer is not None else _workspace(("mesh", _dev_index(dev), F, count), nbytes, dev)
+    points = torch.empty((count, 3), dtype=torch.float32, device=dev)
+    face_index = torch.empty((count,), dtype=torch.int32, device=dev) if want_face_index else None
+    keep = torch.empty((count,), dtype=torch.uint8, device=dev)
+    header = torch.empty((8,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        N.check(lib.dqo_mesh_sample(V, N.ptr(vertices), F, N.ptr(faces), count, int(seed) & (2 ** 64 - 1), N.ptr(points), N.ptr(face_index),
+                                    N.ptr(keep), N.ptr(header), ws.data_ptr(), ws.numel(), N.current_stream()))
+    return dict(points=points, face_index=face_index, keep=keep, header=header)
+
+
 def pcd_workspace(n_gt, n_rec, device):
     """dqo_eval_pcd's workspace for these sizes as a uint8 tensor (zero when first used, handed back ready by every call)."""
     n = N.lib().dqo_eval_pcd_workspace_bytes(int(n_gt), int(n_rec))
@@ -358,8 +424,8 @@ def pcd_workspace(n_gt, n_rec, device):
 def eval_pcd(gt_points, rec_points, dist_thres=(0.03,), transform=None, gt_keep=None, rec_keep=None, out=None, row=0, workspace_buffer=None):
     """eval_pcd (SLAM/eval.py:190-282) of a reconstruction against a ground-truth point set, on the device.
 
-    gt_points [G,3]: the ground-truth points (the reference samples them from the mesh with trimesh, :247 — not built here, see the
-    module docstring); rec_points [P,3]: the reconstructed points; transform: [3,4] / [4,4], applied to rec_points
+    gt_points [G,3]: the ground-truth points (the reference samples them from the mesh with trimesh, :247: sample_surface, whose
+    `keep` is gt_keep); rec_points [P,3]: the reconstructed points; transform: [3,4] / [4,4], applied to rec_points
     (rec_pc.transform(transform), :241); dist_thres: up to 8 distances in metres (:229, :263); gt_keep / rec_keep: uint8 / bool masks,
     0 = the row takes no part (the mapper's row buffers go in as stored).
     Returns the float32 [32] device row (names: PCD_ROW)

@@ -783,7 +783,7 @@ class FusedMapper:
         """How good the map's GEOMETRY is against a ground-truth point set: eval_pcd of the reference (SLAM/eval.py:190-282) — accuracy,
         completion, chamfer distance, precision / recall / F1 per threshold — through dqo_eval.eval_pcd.  The reconstruction is this
         mapper's own `xyz` buffer with `alive` as the row mask: the points the reference reads back from the PLY it saved, without the
-        file, a copy or a host read.  gt_points [G,3]: the ground-truth points (sampling them from a mesh is the caller's, dqo_eval);
+        file, a copy or a host read.  gt_points [G,3]: the ground-truth points (from a mesh: evaluate_geometry_mesh);
         transform: [3,4] / [4,4] applied to the map's points (:241).  Returns the float32 [32] device row (dqo_eval.PCD_ROW; out[row] of
         a caller-owned [K,32] table if given); dqo_eval.eval_pcd_dict reads it.  The workspace is dqo_eval's, per device and sizes.
         The configs with pcd_densify evaluate another point set: evaluate_geometry_densified."""
@@ -806,6 +806,30 @@ class FusedMapper:
         kw.setdefault("want_normals", False)
         d = self.densify(**kw)
         return dqo_eval.eval_pcd(gt_points, d["points"], dist_thres, transform, rec_keep=d["keep"], out=out, row=row)
+
+    @torch.no_grad()
+    def evaluate_geometry_mesh(self, vertices, faces, sample_nums=1000000, seed=0, dist_thres=(0.03,), transform=None, out=None, row=0,
+                               densify=None):
+        """eval_pcd of the reference from the ground-truth MESH (SLAM/eval.py:228-282; metric.py, metric_obj.py): sample_nums points are
+        drawn on its surface (dqo_eval.sample_surface: trimesh.sample.sample_surface, :247) and the map is evaluated against them.
+        vertices [V,3] float32, faces [F,3] int32: device tensors (dqo_ply.read_mesh_ply reads gt_mesh.ply on the host); sample_nums in
+        [1, 2^25 - 1]; seed: the draw's.  densify None: the reconstruction is the live rows, as evaluate_geometry's; True, or a dict of
+        densify()'s keywords: the densified cloud, as evaluate_geometry_densified's (True: the reference's densify(1, 30, 5) of the
+        stable cloud).  The sampled points and their `keep` go in as gt_points / gt_keep: one chain on the current stream from the mesh
+        tensors to the [32] row, no host read.  A mesh without area gives a row of NaN.  Everything else as evaluate_geometry."""
+        import dqo_eval
+        gt = dqo_eval.sample_surface(vertices, faces, sample_nums, seed=seed)
+        if densify is None or densify is False:
+            rec, rec_keep = self.xyz.detach(), self.alive
+        else:
+            kw = {} if densify is True else dict(densify)
+            kw.setdefault("sample_nums", 1000000)
+            if kw["sample_nums"] is None or not 1 <= int(kw["sample_nums"]) < (1 << 25):
+                raise RuntimeError(f"FusedMapper.evaluate_geometry_mesh: densify's sample_nums must be in [1, 2^25 - 1], got {kw['sample_nums']}")
+            kw.setdefault("want_normals", False)
+            d = self.densify(**kw)
+            rec, rec_keep = d["points"], d["keep"]
+        return dqo_eval.eval_pcd(gt["points"], rec, dist_thres, transform, gt_keep=gt["keep"], rec_keep=rec_keep, out=out, row=row)
 
     # ------------------------------------------------------------------ checkpoints (csrc/map_checkpoint.hip) -----------
     @torch.no_grad()

@@ -11,6 +11,9 @@ The reference goes through the third-party `plyfile` package (not vendored, not 
 `format binary_little_endian 1.0` for native-endian float32 records; this module writes / parses that layout directly with numpy
 (and also reads `format ascii 1.0`).  Values are RAW parameters (logit opacity, log scales, unnormalised quaternions), exactly what
 the reference stores.
+
+read_mesh_ply reads the other PLY of an evaluation: the ground-truth triangle mesh eval_pcd loads with trimesh (SLAM/eval.py:236), as
+the two arrays dqo_eval.sample_surface takes.
 """
 import numpy as np
 
@@ -186,3 +189,131 @@ def load_model_ply(path, max_sh_degree=3):
     conf = get(["confidence"]) if "confidence" in col else np.zeros((P, 1), np.float32)
     return dict(xyz=get(["x", "y", "z"]), shs=np.ascontiguousarray(np.concatenate([f_dc, f_rest], 1)), opacity_raw=get(["opacity"]),
                 scaling_raw=get(scales), rotation_raw=get(rots), confidence=conf)
+
+
+_PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+                "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+_MESH_COUNT_TYPES = ("uchar", "uint8", "int", "int32", "uint", "uint32")
+_MESH_INDEX_TYPES = ("int", "int32", "uint", "uint32")
+
+
+def read_mesh_ply(path):
+    """(vertices float32 [V,3], faces int32 [F,3]) of a triangle mesh file — what trimesh.load(gt_meshfile) gives eval_pcd
+    (SLAM/eval.py:236) of the reference's ground-truth meshes, read with numpy on the host.
+
+    Accepted: `format ascii 1.0` and `format binary_little_endian 1.0`; a `vertex` element whose x, y, z are float / float32, anywhere
+    among other scalar properties (normals, uchar colours), which are skipped; then a `face` element whose only property is
+    `property list <uchar|uint8|int|int32|uint|uint32> <int|int32|uint|uint32> vertex_indices` (or vertex_index).  All faces are
+    triangles, or all are quads: a quad (a, b, c, d) becomes (a, b, c), (a, c, d) in file order, as trimesh's loader splits it.  The
+    face table is read as one structured array, not face by face.  Everything else raises RuntimeError naming the file and the
+    reason.  Index values are NOT checked here (an index of 2^31 or more wraps negative): dqo_mesh_sample counts the faces whose
+    indices are outside [0, V) and gives them no sample."""
+    def bad(why):
+        return RuntimeError(f"{path}: {why}")
+
+    with open(path, "rb") as fh:
+        if fh.readline().strip() != b"ply":
+            raise bad("not a PLY file")
+        fmt, elements = None, []  # elements: [name, count, [(kind, ...)]]
+        while True:
+            line = fh.readline()
+            if not line:
+                raise bad("truncated header")
+            tok = line.decode("ascii", "replace").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1] if len(tok) > 1 else None
+            elif tok[0] == "element" and len(tok) == 3:
+                elements.append([tok[1], int(tok[2]), []])
+            elif tok[0] == "property" and elements:
+                elements[-1][2].append(tuple(tok[1:]))
+            elif tok[0] == "end_header":
+                break
+            else:
+                raise bad(f"unexpected header line {line.decode('ascii', 'replace').strip()!r}")
+        if fmt == "binary_big_endian":
+            raise bad("format binary_big_endian is not supported (ascii and binary_little_endian are)")
+        if fmt not in ("ascii", "binary_little_endian"):
+            raise bad(f"unknown format {fmt}")
+        names = [e[0] for e in elements]
+        for need in ("vertex", "face"):
+            if need not in names:
+                raise bad(f"no {need} element")
+        if names != ["vertex", "face"]:
+            raise bad(f"elements {names}: a mesh file holds 'vertex' then 'face' and nothing else")
+        (_, V, vprops), (_, F, fprops) = elements
+        if V < 0 or F < 0:
+            raise bad("negative element count")
+        fields = []
+        for prop in vprops:
+            if len(prop) != 2 or prop[0] not in _PLY_SCALARS:
+                raise bad(f"vertex property {' '.join(prop)!r}: only scalar properties are supported")
+            if prop[1] in ("x", "y", "z") and prop[0] not in ("float", "float32"):
+                raise bad(f"vertex coordinate {prop[1]} has type {prop[0]}: float / float32 only (double coordinates are not supported)")
+            fields.append((prop[1], "<" + _PLY_SCALARS[prop[0]]))
+        vnames = [n for n, _ in fields]
+        if len(set(vnames)) != len(vnames) or not all(c in vnames for c in "xyz"):
+            raise bad("the vertex element needs one x, one y and one z property")
+        if len(fprops) != 1:
+            raise bad(f"the face element has {len(fprops)} properties: exactly one list of vertex indices is supported")
+        fp = fprops[0]
+        if (len(fp) != 4 or fp[0] != "list" or fp[1] not in _MESH_COUNT_TYPES or fp[2] not in _MESH_INDEX_TYPES
+                or fp[3] not in ("vertex_indices", "vertex_index")):
+            raise bad(f"face property {' '.join(fp)!r}: expected 'list <uchar|uint8|int|int32|uint|uint32> <int|int32|uint|uint32> "
+                      "vertex_indices'")
+        if fmt == "binary_little_endian":
+            vdt = np.dtype(fields)
+            raw = fh.read(vdt.itemsize * V)
+            if len(raw) != vdt.itemsize * V:
+                raise bad("truncated vertex data")
+            vt = np.frombuffer(raw, dtype=vdt)
+            vertices = np.stack([vt["x"], vt["y"], vt["z"]], axis=1).astype(np.float32) if V else np.zeros((0, 3), np.float32)
+            cdt, idt = np.dtype("<" + _PLY_SCALARS[fp[1]]), np.dtype("<" + _PLY_SCALARS[fp[2]])
+            if F == 0:
+                return vertices, np.zeros((0, 3), np.int32)
+            first = fh.read(cdt.itemsize)
+            if len(first) != cdt.itemsize:
+                raise bad("truncated face data")
+            n = int(np.frombuffer(first, dtype=cdt)[0])
+            if n not in (3, 4):
+                raise bad(f"a face of {n} vertices: all faces must be triangles, or all quads")
+            fdt = np.dtype([("n", cdt), ("v", idt, (n,))])
+            raw = first + fh.read(fdt.itemsize * F - cdt.itemsize)
+            if len(raw) != fdt.itemsize * F:
+                raise bad("truncated face data (or faces of mixed sizes)")
+            ft = np.frombuffer(raw, dtype=fdt)
+            if not (ft["n"] == n).all():
+                raise bad("faces of mixed sizes: all faces must be triangles, or all quads")
+            idx = ft["v"]
+        else:
+            import warnings
+            try:
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")  # (loadtxt warns about an empty table: reported below as truncated)
+                    vt = np.loadtxt(fh, dtype=np.float64, max_rows=V, ndmin=2) if V else np.zeros((0, len(fields)))
+            except ValueError as e:
+                raise bad(f"bad ascii vertex table ({e})")
+            if vt.shape != (V, len(fields)):
+                raise bad("truncated vertex data")
+            vertices = np.ascontiguousarray(vt[:, [vnames.index(c) for c in "xyz"]], dtype=np.float32)
+            if F == 0:
+                return vertices, np.zeros((0, 3), np.int32)
+            try:
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    ft = np.loadtxt(fh, dtype=np.int64, max_rows=F, ndmin=2)
+            except ValueError as e:
+                raise bad(f"faces of mixed sizes, or a bad ascii face table: all faces must be triangles, or all quads ({e})")
+            if ft.shape[0] != F or ft.shape[1] < 1:
+                raise bad("truncated face data")
+            n = int(ft[0, 0])
+            if n not in (3, 4):
+                raise bad(f"a face of {n} vertices: all faces must be triangles, or all quads")
+            if not (ft[:, 0] == n).all() or ft.shape[1] != n + 1:
+                raise bad("faces of mixed sizes: all faces must be triangles, or all quads")
+            idx = ft[:, 1:]
+    idx = idx.astype(np.int64).astype(np.int32)  # (an index of 2^31 or more wraps negative: out of range for the device step)
+    if n == 4:
+        idx = idx[:, [0, 1, 2, 0, 2, 3]].reshape(-1, 3)
+    return vertices, np.ascontiguousarray(idx, dtype=np.int32)

@@ -591,8 +591,8 @@ int dqo_nn1(int32_t Q, const float* query_xyz, const uint8_t* query_keep, int32_
  * float; the sums are added in a fixed order (see dqo_eval_picture): a row is bitwise reproducible.
  * out_table + 32 * row receives 32 floats: 0 accuracy, 1 completion, 2 chamfer, 3 n_thres, then for threshold t: 4 + 3 t precision P,
  *   5 + 3 t recall R, 6 + 3 t F1 (NaN when P + R = 0, as numpy's division); every other slot NaN.  An empty kept set on either side: 32 NaN.
- * thres_host: n_thres <= 8 floats in HOST memory, read before the call returns.  The ground-truth sampling and the random subsampling of
- *   eval.py:236-248 (trimesh, open3d) are the caller's: both sets arrive as points.
+ * thres_host: n_thres <= 8 floats in HOST memory, read before the call returns.  Both sets arrive as points: the ground-truth sampling of eval.py:247 is
+ *   dqo_mesh_sample, the random subsampling of :244 is part of dqo_surfel_densify.
  * workspace: dqo_eval_pcd_workspace_bytes(n_gt, n_rec) bytes (0 for a bad size), ZERO when first used and then left to this call, which
  *   hands it back ready for the next one (capturable in a hipGraph).  Calls that share a workspace must be ordered (one stream). */
 size_t dqo_eval_pcd_workspace_bytes(int32_t n_gt, int32_t n_rec);
@@ -637,6 +637,36 @@ int dqo_surfel_densify(int32_t P, const float* xyz, const float* scaling_raw, co
                        int32_t circle_num, int32_t levels, int32_t sigma, const float* circle_cs, int32_t frame, uint64_t seed, int64_t cap,
                        float* points, float* normals, int64_t* index, uint8_t* keep, int32_t* header, void* workspace,
                        size_t workspace_bytes, void* hipStream);
+
+/* dqo_mesh_sample (ABI 5, symbols-only addition) — the ground truth's point set of eval_pcd: trimesh.sample.sample_surface(mesh_gt,
+ * sample_nums) (SLAM/eval.py:247) from the mesh's vertices [V,3] float32 and triangles [F,3] int32, nothing read back.  trimesh's four
+ * steps (face areas, their cumulative sum, one uniform draw located in it, two uniform draws folded back into the triangle), with two
+ * departures that make the result a pure function of the arguments: the draws are the key rule of csrc/dqo_sample_hash.h (draws 4-7)
+ * instead of numpy's stream, and the cumulative table counts integer quanta of area, so no float sum's order can reach it.
+ * One rounding per statement, none contracted (tests/mesh_oracle.py restates them):
+ *     area     a face with an index outside [0, V) has A = 0; its vertices are never loaded.  Otherwise, in double: e1 = b - a, e2 = c - a,
+ *              c = e1 x e2 with each component as p * q - r * s, A = 0.5 * sqrt((cx * cx + cy * cy) + cz * cz); a non-finite A becomes 0
+ *     quanta   amax = max A;  frexp(amax) = (m, x) (x = 0 when amax = 0);  e = 61 - bit_length(F) - x;
+ *              q_f = (uint64) floor(ldexp(A_f, e)) < 2^(61 - bit_length(F)), so the total is below 2^61; the largest face has >= 2^35 quanta
+ *     table    cum[f] = q_0 + ... + q_f in uint64, total = cum[F - 1]
+ *     draw     sample i: k_d = dqo_sample_key(seed_word, dqo_sample_draw_word(seed_word, 4 + d), i, 0xffffffff), d = 0..3;
+ *              t = floor(total * (k0 * 2^32 + k1) / 2^64); the face is the first f with cum[f] > t (a face without quanta is never picked);
+ *              u = k2 * 2^-32, v = k3 * 2^-32 in double; if (u + v > 1.0) u = 1.0 - u, v = 1.0 - v;
+ *              p = a + ((b - a) * u + (c - a) * v) per component in double, rounded once to float
+ * points [count,3]; face_index [count] int32 (may be NULL); keep [count] uint8, written for ALL rows: 1, or all 0 when the mesh has no area
+ *   (then no point is written) — dqo_nn1 / dqo_eval_pcd take it as gt_keep, so no count is ever read back.
+ * header (8 x int32, overwritten): 0 n written (count, or 0 when the mesh has no area), 1 F, 2 faces with an index outside [0, V), 3 faces
+ *   of zero or non-finite area among those whose indices are in range, 4 the quantum exponent e, 5 / 6 the total's low / high word, 7 zero.
+ * DQO_ERR_INVALID_ARG before anything is launched: a NULL required pointer, V < 1, F or count outside [1, 2^25 - 1] (dqo_nn1's row limit).
+ *   DQO_ERR_WORKSPACE: the workspace is NULL or too small.
+ * workspace: dqo_mesh_sample_workspace_bytes(F, count) bytes (0 for a bad size), ZERO when first used and then left to this call, which
+ *   hands it back ready for the next one (capturable in a hipGraph): ticket words, the blocks' partials (a block owns
+ *   DQO_MESH_SCAN_BLOCK faces) and, last, cum.  Four launches; no allocation, no synchronisation, integer atomics only.  Calls that share
+ *   a workspace must be ordered (one stream). */
+#define DQO_MESH_SCAN_BLOCK 1024
+size_t dqo_mesh_sample_workspace_bytes(int32_t F, int32_t count);
+int dqo_mesh_sample(int32_t V, const float* vertices, int32_t F, const int32_t* faces, int32_t count, uint64_t seed, float* points,
+                    int32_t* face_index, uint8_t* keep, int32_t* header, void* workspace, size_t workspace_bytes, void* hipStream);
 
 /* Batched dual-quadric residual over B independent (object, view) pairs: loss = 1 - IoU(obs, bbox(ellipsoid, P34)),
  * with gradients.  valid[b] = 0 when loss == 1 (the reference skips that Adam step). */
