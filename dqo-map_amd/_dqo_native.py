@@ -124,7 +124,8 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_eval_ms_ssim_workspace_bytes", "dqo_eval_ms_ssim",
            "dqo_nn1_workspace_bytes", "dqo_nn1", "dqo_eval_pcd_workspace_bytes", "dqo_eval_pcd", "dqo_window_masks_workspace_bytes",
            "dqo_window_masks", "dqo_surfel_densify_workspace_bytes", "dqo_surfel_densify", "dqo_map_pack_workspace_bytes",
-           "dqo_map_pack_rows", "dqo_map_unpack_rows", "dqo_mesh_sample_workspace_bytes", "dqo_mesh_sample")
+           "dqo_map_pack_rows", "dqo_map_unpack_rows", "dqo_mesh_sample_workspace_bytes", "dqo_mesh_sample",
+           "dqo_objmap_frame", "dqo_objmap_optimize", "dqo_objmap_mean_iou")
 
 _lib = None
 
@@ -249,6 +250,9 @@ def lib():
         L.dqo_map_pack_workspace_bytes.argtypes = [c_i32]
         L.dqo_map_pack_rows.argtypes = [c_i32] * 3 + [c_vp] * 9 + [ctypes.c_int64, c_vp, c_vp, ctypes.c_size_t, c_vp]
         L.dqo_map_unpack_rows.argtypes = [c_i32] * 5 + [c_vp] * 8
+        L.dqo_objmap_frame.argtypes = [c_i32] * 3 + [c_vp] * 9 + [c_i32] + [c_vp] * 7 + [c_i32] * 3 + [ctypes.c_uint64] + [c_vp] * 6
+        L.dqo_objmap_optimize.argtypes = [c_i32] * 2 + [c_vp] * 9 + [c_i32, ctypes.c_uint64, c_vp, c_vp]
+        L.dqo_objmap_mean_iou.argtypes = [c_i32] * 2 + [c_vp] * 9
         L.dqo_profile_enable.argtypes = [ctypes.c_int]
         L.dqo_profile_collect.argtypes = [P(DqoProfileEntry), ctypes.c_int, ctypes.c_int]
         if L.dqo_abi_version() != 5:

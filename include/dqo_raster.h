@@ -681,6 +681,57 @@ int dqo_quadric_adam(int32_t n_obj, int32_t n_iters, const int32_t* view_offset,
                      const float* obs_views, const int32_t* view_schedule, float* axes, float* R, float* center,
                      float* loss_hist, void* hipStream);
 
+/* dqo_objmap_frame / dqo_objmap_optimize / dqo_objmap_mean_iou (ABI 5, symbols-only addition) — the object stage of a mapping frame on a
+ * device-resident object table, nothing read back: what SLAM/multiprocess/mapper.py:147-165 runs for a frame with detections
+ * (detections_filter quadrics.py:336-386, ObjectsInitialization / Object.__init__ :429-538, Occlusions_Check :926-968, the live MatchObject
+ * (Only_IOU) :1013-1217, remove_outlier :2397-2425), Object_Optimize_only as mapper.py:204-205 calls it (quadrics.py:2234-2298) and record_iou
+ * (mapper.py:1512-1531).  The reference does this in numpy on the host, with 30 single-pixel reads of the device depth map per detection.
+ * tests/object_oracle.py restates every statement; arithmetic is double from the float32 table, the depth statistics float32 in sample order.
+ *
+ * The table (caller-owned, zero before the first frame; 1 <= cap_obj <= 1024, cap_views >= 2):
+ *   obj_axes [cap_obj,3], obj_R [cap_obj,9] (row-major), obj_center [cap_obj,3] float32 — the layout dqo_quadric_adam updates in place;
+ *   obj_cat, obj_uid (the reference's Object.id_), obj_nviews [cap_obj] int32;
+ *   view_P34 [cap_obj,cap_views,12], view_bbox [cap_obj,cap_views,4] float32: K @ Rt and the detection bbox of each stored observation, in
+ *   append order;  state [3] int32: the object count, the next uid, whether the first-frame branch (Map_global is None) has been taken.
+ *
+ * dqo_objmap_frame: ONE launch of ONE workgroup on the caller's stream, no allocation.  1 <= M <= cap_det <= 64.
+ *   in   det_bbox [M,4], det_ellipse [M,5] (centre, full axes, angle: the json's order, quadrics.py:262), det_cat [M] int32, det_score [M];
+ *        depth [H,W]; K [9]; Rt [12] (3x4, world to camera); W, H, frame_id, seed.
+ *        The 30 depth samples of a detection come from the key rule of csrc/dqo_sample_hash.h (dqo_object_key, draws 8 and 9) instead of
+ *        random.randint: a pure function of (seed, frame_id, the detection's index in the input, the sample).
+ *   out  det_fate [M] int32: 0 dropped by the filter, 1 invalidated (covered by a stored object of its category), 2 matched, 3 new object,
+ *        4 replaced an object (covering replacement), 5 unmatched and too shallow (no object: the mean depth is not in (0.01, 15); the
+ *        first frame: (0, 15));  det_row [M] int32: the detection's row AFTER remove_outlier's compaction, -1 without one (also when
+ *        its object was removed, or dropped for lack of room);  det_depth [M,2] float32: min(mean, 5) and clamp(max - min, 0.05, 0.2) of
+ *        the positive samples, (0, 0) without one;
+ *        opt_flag [cap_obj] uint8: rows a validated detection of this frame holds and that store at least two observations — the gate of
+ *        quadrics.py:2246-2249;
+ *        frame_header [8] int32: accepted, matched, new, replaced, removed (by remove_outlier), has_new_object, overflow_obj, overflow_views.
+ *   Two departures from the reference: (1) the table has no orphans: after a covering replacement the frame's visible list keeps the
+ *   stale projection and category, as the reference's dictionary does, but a later detection matched through that entry is matched to
+ *   the ROW (its observation goes to the row in the reference too); (2) det_row is the row after compaction, where the reference
+ *   leaves a stale index in det["node_id"].
+ *   Capacity: a full table is never written past — the object (overflow_obj) or observation (overflow_views) is dropped and counted;
+ *   an object that is dropped consumes no uid.
+ * dqo_objmap_optimize: Object_Optimize_only for every row with opt_flag set, one lane per row, reading the row's observation slots in
+ *   place: 20 Adam steps with dqo_quadric_adam's learning rates and constants (bit for bit that launch on the gathered views); the view
+ *   of step `it` is dqo_object_key(draw 10, frame_id, uid * 32 + it) modulo the row's count for it <= 5, the last observation afterwards
+ *   (quadrics.py:2264-2266).  loss_hist [cap_obj,20] may be NULL.
+ * dqo_objmap_mean_iou: mean_iou [cap_obj] float32: each row's mean IoU of its projected bbox with its stored observations over those
+ *   with IoU > 0, 0 with none or past the object count.  One lane per row, in double.
+ * DQO_ERR_INVALID_ARG before anything is launched: a NULL pointer (loss_hist excepted), capacities out of range, M outside
+ *   [1, cap_det], a bad image size. */
+int dqo_objmap_frame(int32_t cap_obj, int32_t cap_views, int32_t cap_det, float* obj_axes, float* obj_R, float* obj_center, int32_t* obj_cat,
+                     int32_t* obj_uid, int32_t* obj_nviews, float* view_P34, float* view_bbox, int32_t* state, int32_t M,
+                     const float* det_bbox, const float* det_ellipse, const int32_t* det_cat, const float* det_score, const float* depth,
+                     const float* K, const float* Rt, int32_t W, int32_t H, int32_t frame_id, uint64_t seed, int32_t* det_fate,
+                     int32_t* det_row, float* det_depth, uint8_t* opt_flag, int32_t* frame_header, void* hipStream);
+int dqo_objmap_optimize(int32_t cap_obj, int32_t cap_views, float* obj_axes, float* obj_R, float* obj_center, int32_t* obj_uid,
+                        int32_t* obj_nviews, float* view_P34, float* view_bbox, int32_t* state, const uint8_t* opt_flag, int32_t frame_id,
+                        uint64_t seed, float* loss_hist, void* hipStream);
+int dqo_objmap_mean_iou(int32_t cap_obj, int32_t cap_views, float* obj_axes, float* obj_R, float* obj_center, int32_t* obj_nviews,
+                        float* view_P34, float* view_bbox, int32_t* state, float* mean_iou, void* hipStream);
+
 /* ---- fused helpers around the rasteriser for one mapping iteration (optional) ------------------
  * They replace eager torch op sequences of the reference's callers, not a CUDA binding:
  *   dqo_map_activate      <- SLAM/gaussian_pointcloud.py:732-733, 746-747 (sigmoid / exp / F.normalize)
