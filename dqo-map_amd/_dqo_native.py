@@ -8,9 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libdqoraster.so")
 
-c_f = ctypes.c_float
-c_i32 = ctypes.c_int32
-c_vp = ctypes.c_void_p
+c_f, c_i32, c_vp = ctypes.c_float, ctypes.c_int32, ctypes.c_void_p
 
 
 class DqoRastParams(ctypes.Structure):
@@ -141,124 +139,115 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} not found: the HIP extension is not built (run __graft_entry__.build()). "
                                "There is no CPU fallback for this operator.")
         L = ctypes.CDLL(LIB_PATH)
+        c_sz, c_i64, c_u64, c_d = ctypes.c_size_t, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double
+        P = ctypes.POINTER
+        # every size query returns size_t (ctypes' default c_int would cut it at 2 GiB): by rule, not per export
+        for n in EXPORTS:
+            if "_bytes" in n or n == "dqo_abi_sizeof":  # (*_bytes and dqo_rast_binning_bytes_bucketed)
+                getattr(L, n).restype = c_sz
         L.dqo_last_error.restype = ctypes.c_char_p
-        for n in ("dqo_rast_geom_bytes", "dqo_rast_image_bytes", "dqo_rast_binning_bytes", "dqo_rast_backward_workspace_bytes",
-                  "dqo_knn3_workspace_bytes"):
-            getattr(L, n).restype = ctypes.c_size_t
+        L.dqo_track_pyramid_pixels.restype = c_i64
+        # argument types, grouped as the entry points are in csrc/ (a new operator adds one block).  dqo_capi.hip, rast_forward.hip:
+        L.dqo_abi_sizeof.argtypes = [c_i32]
+        L.dqo_profile_enable.argtypes = [ctypes.c_int]
+        L.dqo_profile_collect.argtypes = [P(DqoProfileEntry), ctypes.c_int, ctypes.c_int]
         L.dqo_rast_geom_bytes.argtypes = [c_i32, c_i32, c_i32]
         L.dqo_rast_image_bytes.argtypes = [c_i32, c_i32]
-        L.dqo_rast_binning_bytes.argtypes = [ctypes.c_int64]
-        L.dqo_rast_binning_bytes_bucketed.restype = ctypes.c_size_t
-        L.dqo_rast_binning_bytes_bucketed.argtypes = [ctypes.c_int64, c_i32, c_i32, c_i32]
-        L.dqo_rast_backward_workspace_bytes.argtypes = [ctypes.c_int64]
-        L.dqo_knn3_workspace_bytes.argtypes = [c_i32]
-        P = ctypes.POINTER
+        L.dqo_rast_binning_bytes.argtypes = [c_i64]
+        L.dqo_rast_binning_bytes_bucketed.argtypes = [c_i64, c_i32, c_i32, c_i32]
+        L.dqo_rast_backward_workspace_bytes.argtypes = [c_i64]
         L.dqo_rast_forward_prepare.argtypes = [P(DqoRastParams), P(DqoRastInputs), P(DqoRastOutputs), P(DqoRastCtx), c_vp]
         L.dqo_rast_forward_render.argtypes = L.dqo_rast_forward_prepare.argtypes
         L.dqo_rast_forward.argtypes = L.dqo_rast_forward_prepare.argtypes
         L.dqo_rast_forward_async.argtypes = L.dqo_rast_forward_prepare.argtypes[:4] + [c_vp, c_vp, c_vp]
         L.dqo_rast_read_header.argtypes = [P(DqoRastCtx), P(DqoRastHeader), c_vp]
-        L.dqo_rast_backward.argtypes = [P(DqoRastParams), P(DqoRastInputs), P(DqoRastCtx), c_vp, c_vp, c_vp, P(DqoRastGrads), c_vp,
-                                        ctypes.c_size_t, c_vp]
-        L.dqo_rast_backward_adam.argtypes = [P(DqoRastParams), P(DqoRastInputs), P(DqoRastCtx), c_vp, c_vp, P(DqoAdamStep), c_vp,
-                                             ctypes.c_size_t, c_vp]
+        L.dqo_rast_backward.argtypes = [P(DqoRastParams), P(DqoRastInputs), P(DqoRastCtx), c_vp, c_vp, c_vp, P(DqoRastGrads), c_vp, c_sz, c_vp]
+        L.dqo_rast_backward_adam.argtypes = [P(DqoRastParams), P(DqoRastInputs), P(DqoRastCtx), c_vp, c_vp, P(DqoAdamStep), c_vp, c_sz, c_vp]
         L.dqo_rast_forward_prepare_params.argtypes = [P(DqoRastParams), P(DqoRastInputs), P(DqoRastParamInputs), P(DqoRastOutputs),
                                                       P(DqoRastCtx), c_vp]
         L.dqo_rast_forward_render_params.argtypes = L.dqo_rast_forward_prepare_params.argtypes
         L.dqo_rast_forward_async_params.argtypes = L.dqo_rast_forward_prepare_params.argtypes[:5] + [c_vp, c_vp, c_vp]
         L.dqo_rast_backward_params.argtypes = [P(DqoRastParams), P(DqoRastInputs), P(DqoRastParamInputs), P(DqoRastCtx), c_vp, c_vp, c_vp,
-                                               P(DqoRastGrads), P(DqoRastParamGrads), c_vp, ctypes.c_size_t, c_vp]
+                                               P(DqoRastGrads), P(DqoRastParamGrads), c_vp, c_sz, c_vp]
         L.dqo_mark_visible.argtypes = [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
-        L.dqo_knn3.argtypes = [c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]
+        # knn.hip
+        L.dqo_knn3_query_workspace_bytes.argtypes = [c_i32, c_i32]
+        L.dqo_knn3_query.argtypes = [c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]
+        L.dqo_knn3_query_within.argtypes = [c_i32, c_vp, c_i32, c_vp, c_f, c_vp, c_vp, c_vp, c_sz, c_vp]
+        L.dqo_knn3_query_grouped.argtypes = [c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_f, c_vp, c_vp, c_vp, c_sz, c_vp]
+        L.dqo_knn3_workspace_bytes.argtypes = [c_i32]
+        L.dqo_knn3.argtypes = [c_i32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]
+        L.dqo_nn1_workspace_bytes.argtypes = [c_i32, c_i32]
+        L.dqo_nn1.argtypes = [c_i32, c_vp, c_vp, c_i32] + [c_vp] * 7 + [c_sz, c_vp]
+        # quadric.hip
         L.dqo_quadric_iou_fwd_bwd.argtypes = [c_i32] + [c_vp] * 12
         L.dqo_quadric_adam.argtypes = [c_i32, c_i32] + [c_vp] * 9
+        # map_fused.hip
         L.dqo_map_activate.argtypes = [c_i32] + [c_vp] * 7
-        L.dqo_map_loss_workspace_bytes.restype = ctypes.c_size_t
-        L.dqo_map_loss_workspace_bytes.argtypes = []
-        L.dqo_map_ssim_workspace_bytes.restype = ctypes.c_size_t
-        L.dqo_map_ssim_workspace_bytes.argtypes = [c_i32, c_i32]
-        L.dqo_map_ssim_fwd_bwd.argtypes = [c_i32, c_i32, c_vp, c_vp, c_f, c_vp, c_vp, c_i32, c_vp, c_vp, ctypes.c_size_t, c_vp]
-        L.dqo_map_loss_fwd_bwd.argtypes = [c_i32, c_i32] + [c_vp] * 6 + [c_f, c_f, c_f] + [c_vp] * 4 + [ctypes.c_size_t, c_vp]
-        L.dqo_map_adam_step.argtypes = [P(DqoAdamStep), c_vp]
-        L.dqo_map_attach_workspace_bytes.restype = ctypes.c_size_t
+        L.dqo_map_loss_fwd_bwd.argtypes = [c_i32, c_i32] + [c_vp] * 6 + [c_f, c_f, c_f] + [c_vp] * 4 + [c_sz, c_vp]
         L.dqo_map_attach_workspace_bytes.argtypes = [c_i32]
-        L.dqo_adam_multi.argtypes = [c_vp, c_i32, c_i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp]
-        L.dqo_adam_multi_dev.argtypes = [c_vp, c_i32, c_vp, c_i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp]
-        L.dqo_map_attach_loss_fwd_bwd.argtypes = [c_i32] + [c_vp] * 7 + [c_i32] + [c_vp] * 5 + [ctypes.c_size_t, c_vp]
+        L.dqo_map_history_merge.argtypes = [c_i32, c_i32, c_f, c_i32] + [c_vp] * 12
+        L.dqo_map_attach_loss_fwd_bwd.argtypes = [c_i32] + [c_vp] * 7 + [c_i32] + [c_vp] * 5 + [c_sz, c_vp]
+        L.dqo_adam_multi.argtypes = [c_vp, c_i32, c_i32, c_d, c_d, c_d, c_vp]
+        L.dqo_adam_multi_dev.argtypes = [c_vp, c_i32, c_vp, c_i32, c_d, c_d, c_d, c_vp]
+        L.dqo_map_adam_step.argtypes = [P(DqoAdamStep), c_vp]
+        # map_ssim.hip
+        L.dqo_map_ssim_workspace_bytes.argtypes = [c_i32, c_i32]
+        L.dqo_map_ssim_fwd_bwd.argtypes = [c_i32, c_i32, c_vp, c_vp, c_f, c_vp, c_vp, c_i32, c_vp, c_vp, c_sz, c_vp]
+        # map_error.hip
         L.dqo_accumulate_gaussian_error.argtypes = [c_i32] * 3 + [c_vp] * 5 + [c_f] * 3 + [c_i32] + [c_vp] * 6
         L.dqo_accumulate_gaussian_confidence.argtypes = [c_i32] * 3 + [c_vp] * 7
-        L.dqo_knn3_query_workspace_bytes.restype = ctypes.c_size_t
-        L.dqo_knn3_query_workspace_bytes.argtypes = [c_i32, c_i32]
-        L.dqo_knn3_query.argtypes = [c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]
-        L.dqo_knn3_query_within.argtypes = [c_i32, c_vp, c_i32, c_vp, c_f, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]
-        L.dqo_knn3_query_grouped.argtypes = [c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_f, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]
-        L.dqo_attach_pixels.argtypes = [c_i32, c_vp, c_vp, c_f, c_f, c_f, c_f, c_i32, c_i32] + [c_vp] * 5
-        L.dqo_attach_decide.argtypes = [c_i32] + [c_vp] * 10 + [c_f, c_f, c_vp, c_vp]
-        L.dqo_growth_scales.argtypes = [c_i32] + [c_vp] * 7 + [c_f, c_f, c_f, c_vp, c_vp, c_vp]
-        L.dqo_growth_inside.argtypes = [c_i32] + [c_vp] * 5
-        L.dqo_error_maps.argtypes = [c_i32, c_i32] + [c_vp] * 9
-        L.dqo_icp_workspace_bytes.restype = ctypes.c_size_t
-        L.dqo_icp_workspace_bytes.argtypes = []
-        L.dqo_icp_normal_equations.argtypes = [c_i32, c_i32] + [c_vp] * 5 + [c_f] * 6 + [c_vp] * 4 + [ctypes.c_size_t, c_vp]
-        L.dqo_icp_gauss_newton.argtypes = [c_i32, c_i32] + [c_vp] * 6 + [c_f] * 4 + [c_vp] * 2 + [ctypes.c_size_t, c_vp]
-        L.dqo_track_preprocess_workspace_bytes.restype = ctypes.c_size_t
-        L.dqo_track_preprocess_workspace_bytes.argtypes = [c_i32, c_i32]
-        L.dqo_track_preprocess.argtypes = [c_i32, c_i32, c_vp, c_vp] + [c_f] * 3 + [c_i32] + [c_vp] * 6 + [ctypes.c_size_t, c_vp]
-        L.dqo_track_pyramid_pixels.restype = ctypes.c_int64
-        L.dqo_track_pyramid_pixels.argtypes = [c_i32, c_i32, c_i32]
-        L.dqo_track_pyramid_workspace_bytes.restype = ctypes.c_size_t
-        L.dqo_track_pyramid_workspace_bytes.argtypes = []
-        L.dqo_track_pyramid.argtypes = [c_i32, c_i32, c_i32] + [c_vp] * 5 + [ctypes.c_size_t, c_vp]
-        L.dqo_track_fill_model_depth.argtypes = [c_i32, c_i32] + [c_vp] * 4 + [c_f, c_f, c_vp]
-        L.dqo_track_p2p_workspace_bytes.restype = ctypes.c_size_t
-        L.dqo_track_p2p_workspace_bytes.argtypes = []
-        L.dqo_track_p2p_loss.argtypes = [c_i32, c_i32] + [c_vp] * 4 + [c_f] + [c_vp] * 5 + [ctypes.c_size_t, c_vp]
+        # map_tilemask.hip
         L.dqo_tile_count_mask.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp]
         L.dqo_transmission_mask.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
         L.dqo_tile_color_error.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
-        L.dqo_window_masks_workspace_bytes.restype = ctypes.c_size_t
         L.dqo_window_masks_workspace_bytes.argtypes = [c_i32, c_i32]
-        L.dqo_window_masks.argtypes = [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_f, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]
-        L.dqo_map_history_merge.argtypes = [c_i32, c_i32, c_f, c_i32] + [c_vp] * 12
-        L.dqo_map_lifecycle_workspace_bytes.restype = ctypes.c_size_t
+        L.dqo_window_masks.argtypes = [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_f, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]
+        # map_attach.hip
+        L.dqo_attach_pixels.argtypes = [c_i32, c_vp, c_vp, c_f, c_f, c_f, c_f, c_i32, c_i32] + [c_vp] * 5
+        L.dqo_attach_decide.argtypes = [c_i32] + [c_vp] * 10 + [c_f, c_f, c_vp, c_vp]
+        # map_growth.hip
+        L.dqo_growth_scales.argtypes = [c_i32] + [c_vp] * 7 + [c_f, c_f, c_f, c_vp, c_vp, c_vp]
+        L.dqo_growth_inside.argtypes = [c_i32] + [c_vp] * 5
+        L.dqo_error_maps.argtypes = [c_i32, c_i32] + [c_vp] * 9
+        # map_lifecycle.hip
         L.dqo_map_lifecycle_workspace_bytes.argtypes = [c_i32]
         L.dqo_map_lifecycle_vote.argtypes = [P(DqoLifecycle)] + [c_vp] * 7
         L.dqo_map_lifecycle_rows.argtypes = [P(DqoLifecycle), c_vp]
-        L.dqo_growth_sample_workspace_bytes.restype = ctypes.c_size_t
+        # map_sample.hip
         L.dqo_growth_sample_workspace_bytes.argtypes = [c_i32, c_i32]
         L.dqo_growth_sample.argtypes = [P(DqoGrowthSample), c_vp]
-        L.dqo_eval_picture_workspace_bytes.restype = ctypes.c_size_t
-        L.dqo_eval_picture_workspace_bytes.argtypes = [c_i32, c_i32]
-        L.dqo_eval_picture.argtypes = [c_i32, c_i32] + [c_vp] * 5 + [c_f, c_f, c_vp, c_vp, c_i32, c_vp, ctypes.c_size_t, c_vp]
-        L.dqo_eval_ms_ssim_workspace_bytes.restype = ctypes.c_size_t
-        L.dqo_eval_ms_ssim_workspace_bytes.argtypes = [c_i32, c_i32]
-        L.dqo_eval_ms_ssim.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, ctypes.c_size_t, c_vp]
-        L.dqo_nn1_workspace_bytes.restype = ctypes.c_size_t
-        L.dqo_nn1_workspace_bytes.argtypes = [c_i32, c_i32]
-        L.dqo_nn1.argtypes = [c_i32, c_vp, c_vp, c_i32] + [c_vp] * 7 + [ctypes.c_size_t, c_vp]
-        L.dqo_eval_pcd_workspace_bytes.restype = ctypes.c_size_t
-        L.dqo_eval_pcd_workspace_bytes.argtypes = [c_i32, c_i32]
-        L.dqo_eval_pcd.argtypes = [c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, ctypes.POINTER(c_f), c_vp, c_i32, c_vp, ctypes.c_size_t, c_vp]
-        L.dqo_surfel_densify_workspace_bytes.restype = ctypes.c_size_t
+        # map_densify.hip, map_meshsample.hip
         L.dqo_surfel_densify_workspace_bytes.argtypes = [c_i32] * 4
-        L.dqo_surfel_densify.argtypes = ([c_i32] + [c_vp] * 4 + [c_i32] * 3 + [c_vp, c_i32, ctypes.c_uint64, ctypes.c_int64] + [c_vp] * 6 +
-                                         [ctypes.c_size_t, c_vp])
-        L.dqo_mesh_sample_workspace_bytes.restype = ctypes.c_size_t
+        L.dqo_surfel_densify.argtypes = [c_i32] + [c_vp] * 4 + [c_i32] * 3 + [c_vp, c_i32, c_u64, c_i64] + [c_vp] * 6 + [c_sz, c_vp]
         L.dqo_mesh_sample_workspace_bytes.argtypes = [c_i32, c_i32]
-        L.dqo_mesh_sample.argtypes = [c_i32, c_vp, c_i32, c_vp, c_i32, ctypes.c_uint64] + [c_vp] * 5 + [ctypes.c_size_t, c_vp]
-        L.dqo_map_pack_workspace_bytes.restype = ctypes.c_size_t
+        L.dqo_mesh_sample.argtypes = [c_i32, c_vp, c_i32, c_vp, c_i32, c_u64] + [c_vp] * 5 + [c_sz, c_vp]
+        # map_eval.hip, map_msssim.hip
+        L.dqo_eval_picture_workspace_bytes.argtypes = [c_i32, c_i32]
+        L.dqo_eval_picture.argtypes = [c_i32, c_i32] + [c_vp] * 5 + [c_f, c_f, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]
+        L.dqo_eval_pcd_workspace_bytes.argtypes = [c_i32, c_i32]
+        L.dqo_eval_pcd.argtypes = [c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, P(c_f), c_vp, c_i32, c_vp, c_sz, c_vp]
+        L.dqo_eval_ms_ssim_workspace_bytes.argtypes = [c_i32, c_i32]
+        L.dqo_eval_ms_ssim.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]
+        # map_checkpoint.hip
         L.dqo_map_pack_workspace_bytes.argtypes = [c_i32]
-        L.dqo_map_pack_rows.argtypes = [c_i32] * 3 + [c_vp] * 9 + [ctypes.c_int64, c_vp, c_vp, ctypes.c_size_t, c_vp]
+        L.dqo_map_pack_rows.argtypes = [c_i32] * 3 + [c_vp] * 9 + [c_i64, c_vp, c_vp, c_sz, c_vp]
         L.dqo_map_unpack_rows.argtypes = [c_i32] * 5 + [c_vp] * 8
-        L.dqo_objmap_frame.argtypes = [c_i32] * 3 + [c_vp] * 9 + [c_i32] + [c_vp] * 7 + [c_i32] * 3 + [ctypes.c_uint64] + [c_vp] * 6
-        L.dqo_objmap_optimize.argtypes = [c_i32] * 2 + [c_vp] * 9 + [c_i32, ctypes.c_uint64, c_vp, c_vp]
+        # map_objects.hip
+        L.dqo_objmap_frame.argtypes = [c_i32] * 3 + [c_vp] * 9 + [c_i32] + [c_vp] * 7 + [c_i32] * 3 + [c_u64] + [c_vp] * 6
+        L.dqo_objmap_optimize.argtypes = [c_i32] * 2 + [c_vp] * 9 + [c_i32, c_u64, c_vp, c_vp]
         L.dqo_objmap_mean_iou.argtypes = [c_i32] * 2 + [c_vp] * 9
-        L.dqo_profile_enable.argtypes = [ctypes.c_int]
-        L.dqo_profile_collect.argtypes = [P(DqoProfileEntry), ctypes.c_int, ctypes.c_int]
+        # icp.hip, track.hip
+        L.dqo_icp_normal_equations.argtypes = [c_i32, c_i32] + [c_vp] * 5 + [c_f] * 6 + [c_vp] * 4 + [c_sz, c_vp]
+        L.dqo_icp_gauss_newton.argtypes = [c_i32, c_i32] + [c_vp] * 6 + [c_f] * 4 + [c_vp] * 2 + [c_sz, c_vp]
+        L.dqo_track_preprocess_workspace_bytes.argtypes = [c_i32, c_i32]
+        L.dqo_track_preprocess.argtypes = [c_i32, c_i32, c_vp, c_vp] + [c_f] * 3 + [c_i32] + [c_vp] * 6 + [c_sz, c_vp]
+        L.dqo_track_pyramid_pixels.argtypes = [c_i32, c_i32, c_i32]
+        L.dqo_track_pyramid.argtypes = [c_i32, c_i32, c_i32] + [c_vp] * 5 + [c_sz, c_vp]
+        L.dqo_track_fill_model_depth.argtypes = [c_i32, c_i32] + [c_vp] * 4 + [c_f, c_f, c_vp]
+        L.dqo_track_p2p_loss.argtypes = [c_i32, c_i32] + [c_vp] * 4 + [c_f] + [c_vp] * 5 + [c_sz, c_vp]
         if L.dqo_abi_version() != 5:
             raise RuntimeError("libdqoraster.so ABI version mismatch")
-        L.dqo_abi_sizeof.restype = ctypes.c_size_t
-        L.dqo_abi_sizeof.argtypes = [c_i32]
         for k, st in enumerate((DqoRastParams, DqoRastInputs, DqoRastOutputs, DqoRastCtx, DqoRastGrads, DqoRastHeader, DqoProfileEntry,
                                 DqoAdamStep, DqoLossTap, DqoObjectGate, DqoAdamTensor, DqoRastParamInputs, DqoRastParamGrads, None,
                                 DqoLifecycle, DqoGrowthSample)):  # (None: index 13 is unused)
@@ -286,6 +275,15 @@ def require_gpu(*tensors):
         if t is not None and t.numel() > 0 and not t.is_cuda:
             raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path. Got a tensor on "
                                f"{t.device}.")
+
+
+def require_gpu_op(principal, *others):
+    """The device rule of an operator's wrapper.  `principal` (a tensor, or a tuple of tensors) names the device the call runs on: it
+    must be a GPU tensor even when it is empty.  `others` (None allowed) follow require_gpu's rule: an empty one may live anywhere."""
+    principal = principal if isinstance(principal, tuple) else (principal,)
+    require_gpu(*principal, *others)
+    if not all(t.is_cuda for t in principal):
+        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
 
 
 def current_stream():

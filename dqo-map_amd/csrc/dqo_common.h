@@ -17,6 +17,9 @@
 #define DQO_TSTRIDE 64
 #endif
 
+// the extern "C" entry points of include/dqo_raster.h: each sits in the .hip file that owns its launches
+#define DQO_API __attribute__((visibility("default")))
+
 // ---- error plumbing -------------------------------------------------------------------------------------------
 void dqo_set_error(const char* fmt, ...);
 #define DQO_CHECK_ARG(cond, ...)          \
@@ -25,6 +28,15 @@ void dqo_set_error(const char* fmt, ...);
             dqo_set_error(__VA_ARGS__);   \
             return DQO_ERR_INVALID_ARG;   \
         }                                 \
+    } while (0)
+// a workspace the caller sizes with the matching *_workspace_bytes query; `need` is evaluated once
+#define DQO_CHECK_WS(what, ws, ws_bytes, need)                                                       \
+    do {                                                                                             \
+        const size_t need_ = (need);                                                                 \
+        if ((ws) == nullptr || (ws_bytes) < need_) {                                                 \
+            dqo_set_error(what " workspace too small (%zu < %zu)", (size_t)(ws_bytes), need_);       \
+            return DQO_ERR_WORKSPACE;                                                                \
+        }                                                                                            \
     } while (0)
 #define DQO_CHECK_HIP(expr)                                                          \
     do {                                                                             \
@@ -514,3 +526,28 @@ int dqo_launch_forward_render(const DqoRastParams* p, const DqoRastInputs* in, D
 int dqo_launch_backward(const DqoRastParams* p, const DqoRastInputs* in, const DqoRastCtx* ctx, const float* dL_dcolor,
                         const float* dL_ddepth, const int32_t* hit_image, DqoRastGrads* g, void* ws, size_t ws_bytes, hipStream_t s,
                         const DqoShRest* pf = nullptr, float* dL_drest = nullptr);
+// the pieces of the rasteriser's two halves that live in files of their own (rast_binning.hip, rast_forward_blend.hip,
+// rast_backward_blend.hip, map_fused_tail.hip)
+int dqo_launch_bin_count(int P, int gx, const int32_t* tile_mask, const DqoGeomLayout& g, const DqoImageLayout& img, const DqoBinLayout& bin,
+                         int64_t capacity, const unsigned long long* tile_objects, hipStream_t s, const uint8_t* row_flags);
+int dqo_launch_bin_place(const DqoGeomLayout& g, const DqoImageLayout& img, const DqoBinLayout& bin, int64_t capacity, hipStream_t s);
+int dqo_launch_blend_forward(const DqoView& v, const DqoGeomLayout& g, const DqoImageLayout& img, const DqoBinLayout& bin,
+                             const DqoRastOutputs& out, int T, const DqoTapDev& tap, const DqoGateDev& gate, int list_split, hipStream_t s,
+                             int64_t header_capacity);
+int dqo_launch_blend_backward(const DqoView& v, const DqoGeomLayout& g, const DqoImageLayout& img, const DqoBinLayout& bin, int T,
+                              const float* dL_dcolor, const float* dL_ddepth, DqoGradRec* recs, uint8_t* valid, int64_t capacity,
+                              const DqoTapDev& tap, const DqoGateDev& gate, int list_split, hipStream_t s);
+int dqo_launch_gaussian_rows(const DqoView& v, const DqoGeomLayout& g, const DqoRastInputs* in, const DqoGradRec* recs, const uint8_t* valid,
+                             int64_t cap, const DqoRastGrads& gr, hipStream_t s, uint32_t frame_words, uint32_t* hist, uint32_t hist_words,
+                             bool pf, float* dL_drest);
+int dqo_launch_tap_report(const DqoGeomLayout& g, const DqoTapDev& tap, hipStream_t s);
+// dqo_rast_backward_adam (dqo_capi.hip) and dqo_map_adam_step (map_fused.hip): the step's checks, the fused tail, the count's advance
+int dqo_check_adam_step(const DqoAdamStep* st, bool need_grads);
+int dqo_launch_backward_adam(const DqoRastParams* p, const DqoRastInputs* in, const DqoRastCtx* ctx, const float* dL_dcolor,
+                             const float* dL_ddepth, const DqoAdamStep* st, void* ws, hipStream_t s);
+int dqo_launch_adam_advance(int32_t* step_dev, const DqoRastHeader* frame_header, hipStream_t s);
+// the exact 1-NN search (knn.hip), which dqo_eval_pcd (map_eval.hip) runs in both directions; its row limit per set
+bool dqo_nn1_size_ok(int32_t n);
+size_t dqo_nn1_ws_bytes(int Q, int R);
+int dqo_launch_nn1(int Q, const float* q_xyz, const uint8_t* q_keep, int R, const float* r_xyz, const uint8_t* r_keep, const float* q_xform,
+                   const float* r_xform, float* dist2, int32_t* idx, void* ws, hipStream_t s);

@@ -293,11 +293,11 @@ __global__ void icp_gauss_newton_kernel(int nblk, const double* __restrict__ par
 
 }  // namespace
 
-size_t dqo_icp_ws_bytes(void) { return sizeof(double) * ICP_NSUM * 1024; }
+static size_t dqo_icp_ws_bytes(void) { return sizeof(double) * ICP_NSUM * 1024; }
 
-int dqo_launch_icp(int H, int W, const float* vertex0, const float* vertex1, const float* normal0, const float* normal1, const float* pose10,
-                   float fx, float fy, float cx, float cy, float dist_thr, float normal_thr, float* JtJ, float* JtR, int32_t* valid_count,
-                   void* ws, hipStream_t s) {
+static int dqo_launch_icp(int H, int W, const float* vertex0, const float* vertex1, const float* normal0, const float* normal1, const float* pose10,
+                          float fx, float fy, float cx, float cy, float dist_thr, float normal_thr, float* JtJ, float* JtR, int32_t* valid_count,
+                          void* ws, hipStream_t s) {
     const int HW = H * W;
     const int nblk = min(1024, (HW + ICP_THREADS - 1) / ICP_THREADS);
     double* partial = (double*)ws;
@@ -307,9 +307,9 @@ int dqo_launch_icp(int H, int W, const float* vertex0, const float* vertex1, con
     return DQO_OK;
 }
 
-int dqo_launch_icp_gauss_newton(int H, int W, const float* vertex0, const float* vertex1, const float* normal0, const float* normal1, float* pose10,
-                                const float* K, float k_scale, float dist_thr, float normal_thr, float damping, int32_t* valid_count, void* ws,
-                                hipStream_t s) {
+static int dqo_launch_icp_gauss_newton(int H, int W, const float* vertex0, const float* vertex1, const float* normal0, const float* normal1,
+                                       float* pose10, const float* K, float k_scale, float dist_thr, float normal_thr, float damping,
+                                       int32_t* valid_count, void* ws, hipStream_t s) {
     const int HW = H * W;
     const int nblk = min(1024, (HW + ICP_THREADS - 1) / ICP_THREADS);
     double* partial = (double*)ws;
@@ -318,3 +318,31 @@ int dqo_launch_icp_gauss_newton(int H, int W, const float* vertex0, const float*
     DQO_LAUNCH("icp_gauss_newton_kernel", icp_gauss_newton_kernel, dim3(1), dim3(64), s, nblk, partial, damping, pose10, valid_count);
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+DQO_API size_t dqo_icp_workspace_bytes(void) { return dqo_icp_ws_bytes(); }
+
+DQO_API int dqo_icp_normal_equations(int32_t H, int32_t W, const float* vertex0, const float* vertex1, const float* normal0,
+                                     const float* normal1, const float* pose10, float fx, float fy, float cx, float cy, float dist_thr,
+                                     float normal_thr, float* JtJ, float* JtR, int32_t* valid_count, void* ws, size_t ws_bytes,
+                                     void* stream) {
+    DQO_CHECK_ARG(H > 1 && W > 1 && (int64_t)H * W < (int64_t)0x7fffffff / 3, "bad image size");
+    DQO_CHECK_ARG(vertex0 && vertex1 && normal0 && normal1 && pose10 && JtJ && JtR && valid_count, "null pointer");
+    DQO_CHECK_WS("icp", ws, ws_bytes, dqo_icp_ws_bytes());
+    return dqo_launch_icp(H, W, vertex0, vertex1, normal0, normal1, pose10, fx, fy, cx, cy, dist_thr, normal_thr, JtJ, JtR, valid_count, ws,
+                          (hipStream_t)stream);
+}
+
+DQO_API int dqo_icp_gauss_newton(int32_t H, int32_t W, const float* vertex0, const float* vertex1, const float* normal0, const float* normal1,
+                                 float* pose10, const float* K, float k_scale, float dist_thr, float normal_thr, float damping,
+                                 int32_t* valid_count, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(H > 1 && W > 1 && (int64_t)H * W < (int64_t)0x7fffffff / 3, "bad image size");
+    DQO_CHECK_ARG(vertex0 && vertex1 && normal0 && normal1 && pose10 && K && valid_count, "null pointer");
+    DQO_CHECK_WS("icp", ws, ws_bytes, dqo_icp_ws_bytes());
+    return dqo_launch_icp_gauss_newton(H, W, vertex0, vertex1, normal0, normal1, pose10, K, k_scale, dist_thr, normal_thr, damping, valid_count,
+                                       ws, (hipStream_t)stream);
+}
+
+}  // extern "C"

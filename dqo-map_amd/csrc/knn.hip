@@ -784,7 +784,7 @@ inline Nn1Ws nn1_ws(void* base, int Q, int R) {
 
 }  // namespace
 
-size_t dqo_knn3_ws_bytes(int P) { return knn_ws(nullptr, P).total; }
+static size_t dqo_knn3_ws_bytes(int P) { return knn_ws(nullptr, P).total; }
 
 // Stable sort of w.keys[0, P) by the Morton code.  The code sits in bits 32..61 of the key: four stable 8-bit passes; the second key buffer
 // is `sorted` (16 B per point, written by the gather only after the sort); an even number of passes leaves the result in w.keys.
@@ -830,7 +830,7 @@ static int knn_build(int P, const float* xyz, const KnnWs& w, bool with_boxes, h
     return DQO_OK;
 }
 
-int dqo_launch_knn3(int P, const float* xyz, float* mean_d2, int32_t* idx3, void* ws, size_t ws_bytes, hipStream_t s) {
+static int dqo_launch_knn3(int P, const float* xyz, float* mean_d2, int32_t* idx3, void* ws, size_t ws_bytes, hipStream_t s) {
     (void)ws_bytes;
     KnnWs w = knn_ws(ws, P);
     int rc = knn_build(P, xyz, w, true, s);
@@ -841,10 +841,10 @@ int dqo_launch_knn3(int P, const float* xyz, float* mean_d2, int32_t* idx3, void
     return DQO_OK;
 }
 
-size_t dqo_knn3_query_ws_bytes(int Q, int R) { return knn_ws(nullptr, Q).total + knn_ws(nullptr, R).total; }
+static size_t dqo_knn3_query_ws_bytes(int Q, int R) { return knn_ws(nullptr, Q).total + knn_ws(nullptr, R).total; }
 
-int dqo_launch_knn3_query(int Q, const float* q_xyz, int R, const float* r_xyz, float* dist2, int32_t* idx3, void* ws, size_t ws_bytes,
-                          hipStream_t s, float bound2, const int32_t* q_group, const int32_t* r_group, const float* group_box) {
+static int dqo_launch_knn3_query(int Q, const float* q_xyz, int R, const float* r_xyz, float* dist2, int32_t* idx3, void* ws, size_t ws_bytes,
+                                 hipStream_t s, float bound2, const int32_t* q_group, const int32_t* r_group, const float* group_box) {
     (void)ws_bytes;
     KnnWs wr = knn_ws(ws, R);
     int rc = knn_build(R, r_xyz, wr, true, s, true, r_group);
@@ -861,6 +861,9 @@ int dqo_launch_knn3_query(int Q, const float* q_xyz, int R, const float* r_xyz, 
                    wr.boxes, wr.sub, wr.groups, dist2, idx3, bound2, q_group, group_box);
     return DQO_OK;
 }
+
+// the index word of a sorted point carries FINE_IDX_BITS index bits
+bool dqo_nn1_size_ok(int32_t n) { return n >= 0 && n < (1 << FINE_IDX_BITS); }
 
 size_t dqo_nn1_ws_bytes(int Q, int R) { return nn1_ws(nullptr, Q < 1 ? 1 : Q, R < 1 ? 1 : R).total; }
 
@@ -895,3 +898,62 @@ int dqo_launch_nn1(int Q, const float* q_xyz, const uint8_t* q_keep, int R, cons
                w.r.boxes, w.r.sub, w.r.groups, grp != nullptr ? 1 : 0, dist2, idx);
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+DQO_API size_t dqo_knn3_query_workspace_bytes(int32_t Q, int32_t R) { return dqo_knn3_query_ws_bytes(Q < 1 ? 1 : Q, R < 1 ? 1 : R); }
+
+static int knn3_query(int32_t Q, const float* q_xyz, int32_t R, const float* r_xyz, float max_dist, float* dist2, int32_t* idx3, void* ws,
+                      size_t ws_bytes, void* stream, const int32_t* q_group = nullptr, const int32_t* r_group = nullptr,
+                      const float* group_box = nullptr) {
+    DQO_CHECK_ARG(Q >= 0 && R >= 0, "negative size");
+    DQO_CHECK_ARG(max_dist > 0.f, "max_dist must be positive");
+    if (Q == 0) return DQO_OK;
+    DQO_CHECK_ARG(q_xyz && dist2 && idx3, "null query / output");
+    DQO_CHECK_ARG(R > 0 && r_xyz, "empty reference set");
+    DQO_CHECK_WS("knn query", ws, ws_bytes, dqo_knn3_query_ws_bytes(Q, R));
+    const float bound2 = max_dist < 1.8e19f ? max_dist * max_dist : 3.402823466e+38f;
+    return dqo_launch_knn3_query(Q, q_xyz, R, r_xyz, dist2, idx3, ws, ws_bytes, (hipStream_t)stream, bound2, q_group, r_group, group_box);
+}
+
+DQO_API int dqo_knn3_query(int32_t Q, const float* q_xyz, int32_t R, const float* r_xyz, float* dist2, int32_t* idx3, void* ws, size_t ws_bytes,
+                           void* stream) {
+    return knn3_query(Q, q_xyz, R, r_xyz, 3.402823466e+38f, dist2, idx3, ws, ws_bytes, stream);
+}
+
+DQO_API int dqo_knn3_query_within(int32_t Q, const float* q_xyz, int32_t R, const float* r_xyz, float max_dist, float* dist2, int32_t* idx3,
+                                  void* ws, size_t ws_bytes, void* stream) {
+    return knn3_query(Q, q_xyz, R, r_xyz, max_dist, dist2, idx3, ws, ws_bytes, stream);
+}
+
+DQO_API int dqo_knn3_query_grouped(int32_t Q, const float* q_xyz, const int32_t* q_group, int32_t R, const float* r_xyz, const int32_t* r_group,
+                                   const float* group_box, float max_dist, float* dist2, int32_t* idx3, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(Q == 0 || (q_group && r_group), "null group ids");
+    DQO_CHECK_ARG(R < (1 << FINE_IDX_BITS), "the grouped search carries the group id in the index word: at most 2^25 - 1 reference points");
+    return knn3_query(Q, q_xyz, R, r_xyz, max_dist, dist2, idx3, ws, ws_bytes, stream, q_group, r_group, group_box);
+}
+
+DQO_API size_t dqo_knn3_workspace_bytes(int32_t P) { return dqo_knn3_ws_bytes(P < 0 ? 0 : P); }
+
+DQO_API int dqo_knn3(int32_t P, const float* xyz, float* mean_d2, int32_t* idx3, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(P >= 0, "bad P");
+    if (P == 0) return DQO_OK;
+    DQO_CHECK_ARG(xyz && mean_d2 && idx3, "null pointer");
+    DQO_CHECK_WS("knn", ws, ws_bytes, dqo_knn3_ws_bytes(P));
+    return dqo_launch_knn3(P, xyz, mean_d2, idx3, ws, ws_bytes, (hipStream_t)stream);
+}
+
+DQO_API size_t dqo_nn1_workspace_bytes(int32_t Q, int32_t R) { return dqo_nn1_size_ok(Q) && dqo_nn1_size_ok(R) ? dqo_nn1_ws_bytes(Q, R) : 0; }
+
+DQO_API int dqo_nn1(int32_t Q, const float* q_xyz, const uint8_t* q_keep, int32_t R, const float* r_xyz, const uint8_t* r_keep,
+                    const float* q_xform, const float* r_xform, float* dist2, int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(dqo_nn1_size_ok(Q) && dqo_nn1_size_ok(R), "bad size: at most 2^25 - 1 rows per set");
+    if (Q == 0) return DQO_OK;
+    DQO_CHECK_ARG(q_xyz && dist2, "null query / output");
+    DQO_CHECK_ARG(R == 0 || r_xyz, "null reference set");
+    DQO_CHECK_WS("nn1", ws, ws_bytes, dqo_nn1_ws_bytes(Q, R));
+    return dqo_launch_nn1(Q, q_xyz, q_keep, R, r_xyz, r_keep, q_xform, r_xform, dist2, idx, ws, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -87,8 +87,8 @@ __global__ __launch_bounds__(256) void attach_decide_kernel(int n, const float* 
 
 }  // namespace
 
-int dqo_launch_attach_pixels(int n, const float* xyz, const float* V, float fx, float fy, float cx, float cy, int W, int H,
-                             const int32_t* pixel_object, int32_t* lin, int32_t* sparse, unsigned long long* tile_objects, hipStream_t s) {
+static int dqo_launch_attach_pixels(int n, const float* xyz, const float* V, float fx, float fy, float cx, float cy, int W, int H,
+                                    const int32_t* pixel_object, int32_t* lin, int32_t* sparse, unsigned long long* tile_objects, hipStream_t s) {
     const int gx = (W + DQO_TILE - 1) / DQO_TILE, gy = (H + DQO_TILE - 1) / DQO_TILE;
     const int64_t HW = (int64_t)W * H;
     DQO_LAUNCH("attach_clear_kernel", attach_clear_kernel, dim3((unsigned)((HW + 255) / 256)), dim3(256), s, HW, gx * gy, sparse, tile_objects);
@@ -98,11 +98,37 @@ int dqo_launch_attach_pixels(int n, const float* xyz, const float* V, float fx, 
     return DQO_OK;
 }
 
-int dqo_launch_attach_decide(int n, const float* xyz, const float* opacity, const int32_t* obj, const int32_t* lin, const int32_t* hit_index,
-                             const float* hit_weight, const float* sxyz, const float* scaling_raw, const float* rotation_raw,
-                             const int32_t* gobj, float plane_thr, float opacity_low, uint8_t* out, hipStream_t s) {
+static int dqo_launch_attach_decide(int n, const float* xyz, const float* opacity, const int32_t* obj, const int32_t* lin, const int32_t* hit_index,
+                                    const float* hit_weight, const float* sxyz, const float* scaling_raw, const float* rotation_raw,
+                                    const int32_t* gobj, float plane_thr, float opacity_low, uint8_t* out, hipStream_t s) {
     if (n > 0)
         DQO_LAUNCH("attach_decide_kernel", attach_decide_kernel, dim3((n + 255) / 256), dim3(256), s, n, xyz, opacity, obj, lin, hit_index,
                    hit_weight, sxyz, scaling_raw, rotation_raw, gobj, plane_thr, opacity_low, out);
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+DQO_API int dqo_attach_pixels(int32_t n, const float* temp_xyz, const float* viewmatrix, float fx, float fy, float cx, float cy, int32_t W,
+                              int32_t H, const int32_t* pixel_object, int32_t* lin, int32_t* sparse_pixel_object, uint64_t* tile_objects,
+                              void* stream) {
+    DQO_CHECK_ARG(n >= 0 && W > 0 && H > 0 && (int64_t)W * H < (1ll << 31), "bad size");
+    DQO_CHECK_ARG(viewmatrix && pixel_object && sparse_pixel_object && tile_objects && (n == 0 || (temp_xyz && lin)), "null pointer");
+    return dqo_launch_attach_pixels(n, temp_xyz, viewmatrix, fx, fy, cx, cy, W, H, pixel_object, lin, sparse_pixel_object,
+                                    reinterpret_cast<unsigned long long*>(tile_objects), (hipStream_t)stream);
+}
+
+DQO_API int dqo_attach_decide(int32_t n, const float* temp_xyz, const float* temp_opacity, const int32_t* temp_object, const int32_t* lin,
+                              const int32_t* hit_index, const float* hit_weight, const float* xyz, const float* scaling_raw,
+                              const float* rotation_raw, const int32_t* gaussian_object, float plane_thr, float opacity_low, uint8_t* out,
+                              void* stream) {
+    DQO_CHECK_ARG(n >= 0, "bad size");
+    if (n == 0) return DQO_OK;
+    DQO_CHECK_ARG(temp_xyz && temp_opacity && temp_object && lin && hit_index && hit_weight && xyz && scaling_raw && rotation_raw &&
+                      gaussian_object && out, "null pointer");
+    return dqo_launch_attach_decide(n, temp_xyz, temp_opacity, temp_object, lin, hit_index, hit_weight, xyz, scaling_raw, rotation_raw,
+                                    gaussian_object, plane_thr, opacity_low, out, (hipStream_t)stream);
+}
+
+}  // extern "C"

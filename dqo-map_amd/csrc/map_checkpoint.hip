@@ -210,11 +210,11 @@ inline uint32_t* pk_u32(float* p) { return reinterpret_cast<uint32_t*>(p); }
 
 }  // namespace
 
-size_t dqo_map_pack_ws_bytes(int64_t P) { return DQO_REDUCE_HEAD_WORDS * 4 + dqo_align_up(pk_blocks(P) * sizeof(u64), 256); }
+static size_t dqo_map_pack_ws_bytes(int64_t P) { return DQO_REDUCE_HEAD_WORDS * 4 + dqo_align_up(pk_blocks(P) * sizeof(u64), 256); }
 
-int dqo_launch_map_pack(int P, int M, int with_conf, const float* xyz, const float* shs, const float* opacity_raw, const float* scaling_raw,
-                        const float* rotation_raw, const float* confidence, const uint8_t* alive, const uint8_t* stable, float* table,
-                        int32_t* header, void* ws, hipStream_t s) {
+static int dqo_launch_map_pack(int P, int M, int with_conf, const float* xyz, const float* shs, const float* opacity_raw, const float* scaling_raw,
+                               const float* rotation_raw, const float* confidence, const uint8_t* alive, const uint8_t* stable, float* table,
+                               int32_t* header, void* ws, hipStream_t s) {
     PkArgs a;
     a.P = P, a.M = M, a.C = 6 + 3 * M + 8 + (with_conf ? 1 : 0), a.Cp = a.C | 1, a.with_conf = with_conf ? 1 : 0;
     a.xyz = pk_u32(xyz), a.shs = pk_u32(shs), a.opacity = pk_u32(opacity_raw), a.scaling = pk_u32(scaling_raw);
@@ -229,8 +229,8 @@ int dqo_launch_map_pack(int P, int M, int with_conf, const float* xyz, const flo
     return DQO_OK;
 }
 
-int dqo_launch_map_unpack(int M, int64_t n, int64_t first_row, int has_conf, const float* table, float* xyz, float* shs, float* opacity_raw,
-                          float* scaling_raw, float* rotation_raw, float* confidence, hipStream_t s) {
+static int dqo_launch_map_unpack(int M, int64_t n, int64_t first_row, int has_conf, const float* table, float* xyz, float* shs, float* opacity_raw,
+                                 float* scaling_raw, float* rotation_raw, float* confidence, hipStream_t s) {
     UnpkArgs a;
     a.M = M, a.Cin = 6 + 3 * M + 8 + (has_conf ? 1 : 0), a.Cp = a.Cin | 1, a.has_conf = has_conf ? 1 : 0;
     a.n = n, a.first_row = first_row, a.table = pk_u32(table);
@@ -240,3 +240,41 @@ int dqo_launch_map_unpack(int M, int64_t n, int64_t first_row, int has_conf, con
                     (size_t)PK_ROWS * a.Cp * 4, s, a);
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+// the vertex table of a map checkpoint: at most 2^31 - 1 floats, SH sizes up to 64 coefficients (a tile of 64 rows stays below 64 KiB of LDS)
+static bool map_table_size_ok(int64_t rows, int32_t M, int32_t with_conf) {
+    return rows >= 1 && M >= 1 && M <= 64 && rows * (int64_t)(6 + 3 * M + 8 + (with_conf ? 1 : 0)) <= (int64_t)0x7fffffff;
+}
+
+DQO_API size_t dqo_map_pack_workspace_bytes(int32_t P) { return P >= 1 ? dqo_map_pack_ws_bytes(P) : 0; }
+
+DQO_API int dqo_map_pack_rows(int32_t P, int32_t M, int32_t include_confidence, const float* xyz, const float* shs, const float* opacity_raw,
+                              const float* scaling_raw, const float* rotation_raw, const float* confidence, const uint8_t* alive,
+                              const uint8_t* stable, float* table, int64_t table_rows, int32_t* header, void* ws, size_t ws_bytes,
+                              void* stream) {
+    DQO_CHECK_ARG(P >= 1, "bad row count %d", P);
+    DQO_CHECK_ARG(M >= 1 && M <= 64, "bad SH size M = %d: 1 to 64 coefficients", M);
+    DQO_CHECK_ARG(map_table_size_ok(P, M, include_confidence), "bad size: a table of %d rows exceeds 2^31 - 1 floats", P);
+    DQO_CHECK_ARG(xyz && shs && opacity_raw && scaling_raw && rotation_raw && table && header, "null pointer");
+    DQO_CHECK_ARG(table_rows >= (int64_t)P, "table capacity %lld rows is below the map's %d rows", (long long)table_rows, P);
+    DQO_CHECK_WS("map pack", ws, ws_bytes, dqo_map_pack_ws_bytes(P));
+    return dqo_launch_map_pack(P, M, include_confidence != 0, xyz, shs, opacity_raw, scaling_raw, rotation_raw, confidence, alive, stable, table,
+                               header, ws, (hipStream_t)stream);
+}
+
+DQO_API int dqo_map_unpack_rows(int32_t P, int32_t M, int32_t n, int32_t first_row, int32_t has_confidence, const float* table, float* xyz,
+                                float* shs, float* opacity_raw, float* scaling_raw, float* rotation_raw, float* confidence, void* stream) {
+    DQO_CHECK_ARG(P >= 1 && n >= 0 && first_row >= 0 && (int64_t)first_row + n <= (int64_t)P, "bad size: rows [%d, %d + %d) of a map of %d rows",
+                  first_row, first_row, n, P);
+    DQO_CHECK_ARG(M >= 1 && M <= 64, "bad SH size M = %d: 1 to 64 coefficients", M);
+    DQO_CHECK_ARG(map_table_size_ok(P, M, 1), "bad size: a table of %d rows exceeds 2^31 - 1 floats", P);
+    if (n == 0) return DQO_OK;
+    DQO_CHECK_ARG(table && xyz && shs && opacity_raw && scaling_raw && rotation_raw, "null pointer");
+    return dqo_launch_map_unpack(M, n, first_row, has_confidence != 0, table, xyz, shs, opacity_raw, scaling_raw, rotation_raw, confidence,
+                                 (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -345,11 +345,11 @@ inline uint32_t dn_chunks(uint64_t total) { return (uint32_t)((total + DN_CHUNK 
 
 }  // namespace
 
-size_t dqo_densify_ws_bytes(uint64_t total) { return DN_HEAD_WORDS * 4 + dqo_align_up((size_t)dn_chunks(total) * sizeof(uint32_t), 256); }
+static size_t dqo_densify_ws_bytes(uint64_t total) { return DN_HEAD_WORDS * 4 + dqo_align_up((size_t)dn_chunks(total) * sizeof(uint32_t), 256); }
 
-int dqo_launch_surfel_densify(int P, const float* xyz, const float* scaling_raw, const float* rotation_raw, const uint8_t* row_keep,
-                              int circle_num, int levels, int sigma, const float* circle_cs, int frame, uint64_t seed, int64_t cap,
-                              float* points, float* normals, int64_t* index, uint8_t* keep, int32_t* header, void* ws, hipStream_t s) {
+static int dqo_launch_surfel_densify(int P, const float* xyz, const float* scaling_raw, const float* rotation_raw, const uint8_t* row_keep,
+                                     int circle_num, int levels, int sigma, const float* circle_cs, int frame, uint64_t seed, int64_t cap,
+                                     float* points, float* normals, int64_t* index, uint8_t* keep, int32_t* header, void* ws, hipStream_t s) {
     DnArgs a;
     a.M = (uint32_t)circle_num * (uint32_t)levels * (uint32_t)sigma;
     a.total = (uint64_t)P * a.M, a.cap = (uint64_t)cap;
@@ -372,3 +372,42 @@ int dqo_launch_surfel_densify(int P, const float* xyz, const float* scaling_raw,
     DQO_LAUNCH("densify_emit_kernel", densify_emit_kernel, grid, block, s, a);
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+// GaussianPointCloud.densify (SLAM/gaussian_pointcloud.py:67-130) and eval_pcd's subsample (SLAM/eval.py:244).  M, or 0 for a bad size
+static int64_t densify_columns(int32_t P, int32_t circle_num, int32_t levels, int32_t sigma) {
+    if (P < 1 || circle_num < 1 || levels < 1 || sigma < 1 || circle_num > 1024) return 0;
+    const int64_t ring = (int64_t)circle_num * levels;
+    if (ring > 65535) return 0;
+    const int64_t M = ring * sigma;
+    return (M > 65535 || (int64_t)P * M >= (1ll << 32)) ? 0 : M;
+}
+
+DQO_API size_t dqo_surfel_densify_workspace_bytes(int32_t P, int32_t circle_num, int32_t levels, int32_t sigma) {
+    const int64_t M = densify_columns(P, circle_num, levels, sigma);
+    return M > 0 ? dqo_densify_ws_bytes((uint64_t)P * (uint64_t)M) : 0;
+}
+
+DQO_API int dqo_surfel_densify(int32_t P, const float* xyz, const float* scaling_raw, const float* rotation_raw, const uint8_t* row_keep,
+                               int32_t circle_num, int32_t levels, int32_t sigma, const float* circle_cs, int32_t frame, uint64_t seed,
+                               int64_t cap, float* points, float* normals, int64_t* index, uint8_t* keep, int32_t* header, void* ws,
+                               size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(P >= 1, "bad row count %d", P);
+    DQO_CHECK_ARG(circle_num >= 1 && levels >= 1 && sigma >= 1, "circle_num, levels and sigma must be at least 1 (got %d, %d, %d)", circle_num,
+                  levels, sigma);
+    DQO_CHECK_ARG(circle_num <= 1024, "circle_num %d: at most 1024", circle_num);
+    DQO_CHECK_ARG((int64_t)circle_num * levels <= 65535 && (int64_t)circle_num * levels * sigma <= 65535,
+                  "circle_num * levels * sigma: at most 65535 points per row");
+    const int64_t M = densify_columns(P, circle_num, levels, sigma);
+    DQO_CHECK_ARG(M > 0, "P * circle_num * levels * sigma must stay below 2^32");
+    DQO_CHECK_ARG(cap >= 1, "bad capacity %lld", (long long)cap);
+    DQO_CHECK_ARG(frame == DQO_DENSIFY_FRAME_REFERENCE || frame == DQO_DENSIFY_FRAME_SURFEL, "bad frame %d", frame);
+    DQO_CHECK_ARG(xyz && scaling_raw && rotation_raw && circle_cs && points && keep && header, "null pointer");
+    DQO_CHECK_WS("surfel densify", ws, ws_bytes, dqo_densify_ws_bytes((uint64_t)P * (uint64_t)M));
+    return dqo_launch_surfel_densify(P, xyz, scaling_raw, rotation_raw, row_keep, circle_num, levels, sigma, circle_cs, frame, seed, cap, points,
+                                     normals, index, keep, header, ws, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -113,8 +113,8 @@ __global__ void confidence_mean_kernel(int P, const int32_t* __restrict__ counte
 
 }  // namespace
 
-int dqo_launch_accumulate_confidence(int H, int W, int P, const int32_t* index, const float* confidence, float* gmax, float* gmin,
-                                     float* gmean, int32_t* counter, hipStream_t s) {
+static int dqo_launch_accumulate_confidence(int H, int W, int P, const int32_t* index, const float* confidence, float* gmax, float* gmin,
+                                            float* gmean, int32_t* counter, hipStream_t s) {
     const int HW = H * W;
     DQO_LAUNCH("confidence_init_kernel", confidence_init_kernel, dim3((P + 255) / 256), dim3(256), s, P, counter, gmax, gmin, gmean);
     DQO_LAUNCH("accumulate_confidence_kernel", accumulate_confidence_kernel, dim3((HW + 255) / 256), dim3(256), s, HW, P, confidence,
@@ -123,10 +123,10 @@ int dqo_launch_accumulate_confidence(int H, int W, int P, const int32_t* index, 
     return DQO_OK;
 }
 
-int dqo_launch_accumulate_error(int H, int W, int P, const float* color_err, const float* depth_err, const float* normal_err,
-                                const int32_t* color_index, const int32_t* depth_index, float color_thr, float depth_thr,
-                                float normal_thr, int check_max, float* gs_color, float* gs_depth, float* gs_normal, float* rescale,
-                                int32_t* counters, hipStream_t s) {
+static int dqo_launch_accumulate_error(int H, int W, int P, const float* color_err, const float* depth_err, const float* normal_err,
+                                       const int32_t* color_index, const int32_t* depth_index, float color_thr, float depth_thr,
+                                       float normal_thr, int check_max, float* gs_color, float* gs_depth, float* gs_normal, float* rescale,
+                                       int32_t* counters, hipStream_t s) {
     for (float* q : {gs_color, gs_depth, gs_normal, rescale}) {
         int rc = dqo_launch_zero_words(reinterpret_cast<uint32_t*>(q), (size_t)P, s);
         if (rc) return rc;
@@ -144,3 +144,30 @@ int dqo_launch_accumulate_error(int H, int W, int P, const float* color_err, con
     }
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+DQO_API int dqo_accumulate_gaussian_error(int32_t H, int32_t W, int32_t P, const float* ce, const float* de, const float* ne,
+                                          const int32_t* ci, const int32_t* di, float color_thr, float depth_thr, float normal_thr,
+                                          int32_t check_max, float* gs_color, float* gs_depth, float* gs_normal, float* rescale,
+                                          int32_t* counters, void* stream) {
+    DQO_CHECK_ARG(H > 0 && W > 0 && P >= 0, "bad sizes");
+    if (P == 0) return DQO_OK;
+    DQO_CHECK_ARG(ce && de && ne && ci && di && gs_color && gs_depth && gs_normal && rescale, "null pointer");
+    DQO_CHECK_ARG(check_max || counters, "mean mode needs the counters scratch buffer");
+    return dqo_launch_accumulate_error(H, W, P, ce, de, ne, ci, di, color_thr, depth_thr, normal_thr, check_max, gs_color, gs_depth,
+                                       gs_normal, rescale, counters, (hipStream_t)stream);
+}
+
+DQO_API int dqo_accumulate_gaussian_confidence(int32_t H, int32_t W, int32_t P, const int32_t* gaussian_index_map,
+                                               const float* gaussian_confidence_map, float* gs_max, float* gs_min, float* gs_mean,
+                                               int32_t* counter, void* stream) {
+    DQO_CHECK_ARG(H > 0 && W > 0 && P >= 0, "bad sizes");
+    if (P == 0) return DQO_OK;
+    DQO_CHECK_ARG(gaussian_index_map && gaussian_confidence_map && gs_max && gs_min && gs_mean && counter, "null pointer");
+    return dqo_launch_accumulate_confidence(H, W, P, gaussian_index_map, gaussian_confidence_map, gs_max, gs_min, gs_mean, counter,
+                                            (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -20,10 +20,6 @@
 #include "dqo_common.h"
 #include "dqo_reduce.h"
 
-size_t dqo_nn1_ws_bytes(int Q, int R);
-int dqo_launch_nn1(int Q, const float* q_xyz, const uint8_t* q_keep, int R, const float* r_xyz, const uint8_t* r_keep, const float* q_xform,
-                   const float* r_xform, float* dist2, int32_t* idx, void* ws, hipStream_t s);
-
 namespace {
 
 enum {
@@ -191,11 +187,11 @@ inline PcWorkspace pc_ws(void* base, int n_gt, int n_rec) {
 
 }  // namespace
 
-size_t dqo_eval_ws_bytes(int64_t HW) { return DQO_REDUCE_HEAD_WORDS * 4 + dqo_align_up(ev_blocks(HW) * EV_STRIDE * sizeof(double), 256); }
+static size_t dqo_eval_ws_bytes(int64_t HW) { return DQO_REDUCE_HEAD_WORDS * 4 + dqo_align_up(ev_blocks(HW) * EV_STRIDE * sizeof(double), 256); }
 
-int dqo_launch_eval_picture(int W, int H, const float* render, const float* gt_color, const float* depth, const float* gt_depth,
-                            const int32_t* depth_index, float min_depth, float max_depth, const DqoRastHeader* header, float* out_row,
-                            void* ws, hipStream_t s) {
+static int dqo_launch_eval_picture(int W, int H, const float* render, const float* gt_color, const float* depth, const float* gt_depth,
+                                   const int32_t* depth_index, float min_depth, float max_depth, const DqoRastHeader* header, float* out_row,
+                                   void* ws, hipStream_t s) {
     const int64_t HW = (int64_t)W * H;
     EvWorkspace w;
     w.ticket = (int32_t*)ws;
@@ -205,10 +201,10 @@ int dqo_launch_eval_picture(int W, int H, const float* render, const float* gt_c
     return DQO_OK;
 }
 
-size_t dqo_eval_pcd_ws_bytes(int n_gt, int n_rec) { return pc_ws(nullptr, n_gt, n_rec).total; }
+static size_t dqo_eval_pcd_ws_bytes(int n_gt, int n_rec) { return pc_ws(nullptr, n_gt, n_rec).total; }
 
-int dqo_launch_eval_pcd(int n_gt, const float* gt_xyz, const uint8_t* gt_keep, int n_rec, const float* rec_xyz, const uint8_t* rec_keep,
-                        const float* rec_xform, int n_thres, const float* thres, float* out_row, void* ws, hipStream_t s) {
+static int dqo_launch_eval_pcd(int n_gt, const float* gt_xyz, const uint8_t* gt_keep, int n_rec, const float* rec_xyz, const uint8_t* rec_keep,
+                               const float* rec_xform, int n_thres, const float* thres, float* out_row, void* ws, hipStream_t s) {
     const PcWorkspace w = pc_ws(ws, n_gt, n_rec);
     // accuracy: every reconstructed point to the ground truth (:204-208); completion: the other way round (:211-215)
     int rc = dqo_launch_nn1(n_rec, rec_xyz, rec_keep, n_gt, gt_xyz, gt_keep, rec_xform, nullptr, w.d2_rec, nullptr, w.nn1, s);
@@ -222,3 +218,41 @@ int dqo_launch_eval_pcd(int n_gt, const float* gt_xyz, const uint8_t* gt_keep, i
                th, blocks_rec, w.ev, out_row);
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+// eval_picture (SLAM/eval.py:38-188): psnr (:63), l1_loss (:70), the depth statements (:115-126)
+DQO_API size_t dqo_eval_picture_workspace_bytes(int32_t W, int32_t H) {
+    return (W > 0 && H > 0 && (int64_t)W * H < (1ll << 31) / 3) ? dqo_eval_ws_bytes((int64_t)W * H) : 0;
+}
+
+DQO_API int dqo_eval_picture(int32_t W, int32_t H, const float* render, const float* gt_color, const float* depth, const float* gt_depth,
+                             const int32_t* depth_index, float min_depth, float max_depth, const DqoRastHeader* render_header, float* out,
+                             int32_t row, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(W > 0 && H > 0 && (int64_t)W * H < (1ll << 31) / 3, "bad image size");
+    DQO_CHECK_ARG(render && gt_color && depth && gt_depth && depth_index && out, "null pointer");
+    DQO_CHECK_ARG(row >= 0, "bad row %d", row);
+    DQO_CHECK_WS("eval_picture", ws, ws_bytes, dqo_eval_ws_bytes((int64_t)W * H));
+    return dqo_launch_eval_picture(W, H, render, gt_color, depth, gt_depth, depth_index, min_depth, max_depth, render_header,
+                                   out + (size_t)8 * row, ws, (hipStream_t)stream);
+}
+
+// eval_pcd (SLAM/eval.py:190-282): accuracy, completion, chamfer distance, precision / recall / F1 per threshold
+DQO_API size_t dqo_eval_pcd_workspace_bytes(int32_t n_gt, int32_t n_rec) {
+    return dqo_nn1_size_ok(n_gt) && dqo_nn1_size_ok(n_rec) ? dqo_eval_pcd_ws_bytes(n_gt, n_rec) : 0;
+}
+
+DQO_API int dqo_eval_pcd(int32_t n_gt, const float* gt_xyz, const uint8_t* gt_keep, int32_t n_rec, const float* rec_xyz, const uint8_t* rec_keep,
+                         const float* rec_xform, int32_t n_thres, const float* thres_host, float* out_table, int32_t row, void* ws,
+                         size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(dqo_nn1_size_ok(n_gt) && dqo_nn1_size_ok(n_rec), "bad size: at most 2^25 - 1 rows per set");
+    DQO_CHECK_ARG((n_gt == 0 || gt_xyz) && (n_rec == 0 || rec_xyz) && out_table, "null pointer");
+    DQO_CHECK_ARG(n_thres >= 0 && n_thres <= 8 && (n_thres == 0 || thres_host), "at most 8 thresholds (got %d)", n_thres);
+    DQO_CHECK_ARG(row >= 0, "bad row %d", row);
+    DQO_CHECK_WS("eval_pcd", ws, ws_bytes, dqo_eval_pcd_ws_bytes(n_gt, n_rec));
+    return dqo_launch_eval_pcd(n_gt, gt_xyz, gt_keep, n_rec, rec_xyz, rec_keep, rec_xform, n_thres, thres_host, out_table + (size_t)32 * row, ws,
+                               (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -370,18 +370,18 @@ __device__ __forceinline__ void adam_block(AdamArgs a) {
 
 }  // namespace
 
-int dqo_launch_map_activate(int P, const float* opacity_raw, const float* scaling_raw, const float* rotation_raw, float* opacity,
-                            float* scales, float* rotations, hipStream_t s) {
+static int dqo_launch_map_activate(int P, const float* opacity_raw, const float* scaling_raw, const float* rotation_raw, float* opacity,
+                                   float* scales, float* rotations, hipStream_t s) {
     DQO_LAUNCH("activate_kernel", activate_kernel, dim3((P + 255) / 256), dim3(256), s, P, opacity_raw, scaling_raw, rotation_raw, opacity,
                scales, rotations);
     return DQO_OK;
 }
 
-size_t dqo_map_loss_ws_bytes(void) { return 4 * sizeof(double) * 1024; }
+static size_t dqo_map_loss_ws_bytes(void) { return 4 * sizeof(double) * 1024; }
 
-int dqo_launch_map_loss(int W, int H, const float* color, const float* depth, const int32_t* depth_index, const float* gt_color,
-                        const float* gt_depth, const uint8_t* render_mask, float color_weight, float depth_weight, float add_depth_thres,
-                        float* loss_out, float* dL_dcolor, float* dL_ddepth, void* ws, hipStream_t s) {
+static int dqo_launch_map_loss(int W, int H, const float* color, const float* depth, const int32_t* depth_index, const float* gt_color,
+                               const float* gt_depth, const uint8_t* render_mask, float color_weight, float depth_weight, float add_depth_thres,
+                               float* loss_out, float* dL_dcolor, float* dL_ddepth, void* ws, hipStream_t s) {
     const int HW = W * H;
     double* partial = (double*)ws;
     auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15u) == 0u; };
@@ -462,7 +462,7 @@ int dqo_adam_args(const DqoAdamStep* st, int blocks, AdamArgs* out, bool* attach
     return DQO_OK;
 }
 
-int dqo_launch_map_adam(const DqoAdamStep* st, hipStream_t s) {
+static int dqo_launch_map_adam(const DqoAdamStep* st, hipStream_t s) {
     const int blocks = (st->P + ADAM_THREADS - 1) / ADAM_THREADS;
     AdamArgs a;
     bool attach = false;
@@ -541,8 +541,8 @@ __global__ __launch_bounds__(ADAMM_THREADS) void adam_multi_kernel(const AdamMul
 }
 }  // namespace
 
-int dqo_launch_adam_multi(const DqoAdamTensor* ts, int n_tensors, int step, double beta1, double beta2, double eps, hipStream_t s,
-                          int32_t* step_dev, int bump) {
+static int dqo_launch_adam_multi(const DqoAdamTensor* ts, int n_tensors, int step, double beta1, double beta2, double eps, hipStream_t s,
+                                 int32_t* step_dev, int bump) {
     AdamMultiArgs q;
     if (step_dev != nullptr) step = 1;  // (placeholders below; the kernel forms the corrections from the device count)
     const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
@@ -566,11 +566,11 @@ int dqo_launch_adam_multi(const DqoAdamTensor* ts, int n_tensors, int step, doub
     return DQO_OK;
 }
 
-size_t dqo_map_attach_ws_bytes(int P) { return sizeof(double) * (size_t)((P + ATT_THREADS - 1) / ATT_THREADS + 1); }
+static size_t dqo_map_attach_ws_bytes(int P) { return sizeof(double) * (size_t)((P + ATT_THREADS - 1) / ATT_THREADS + 1); }
 
-int dqo_launch_map_attach(int P, const float* scaling, const float* xyz, const float* rotation, const float* scaling0, const float* xyz0,
-                          const float* rotation0, const uint8_t* mask, int attach_count, float* loss, float* g_scaling, float* g_xyz,
-                          float* g_rotation, void* ws, hipStream_t s) {
+static int dqo_launch_map_attach(int P, const float* scaling, const float* xyz, const float* rotation, const float* scaling0, const float* xyz0,
+                                 const float* rotation0, const uint8_t* mask, int attach_count, float* loss, float* g_scaling, float* g_xyz,
+                                 float* g_rotation, void* ws, hipStream_t s) {
     const int blocks = (P + ATT_THREADS - 1) / ATT_THREADS;
     // d/dp of 1000 * mean((p - p0)^2) over |a| rows of 3 (scaling, xyz) / 4 (rotation) elements = 2000 (p - p0) / (len |a|); with an empty
     // set the loss and its gradient are zero (mapper.py:813)
@@ -583,9 +583,9 @@ int dqo_launch_map_attach(int P, const float* scaling, const float* xyz, const f
     return DQO_OK;
 }
 
-int dqo_launch_history_merge(int P, int M, float max_weight, int first_row, const uint8_t* row_flags, const float* conf0, const float* conf,
-                             const float* xyz0, const float* shs0, const float* scaling0, const float* rot0_unit, float* xyz, float* shs,
-                             float* scaling_raw, float* rotation_raw, hipStream_t s) {
+static int dqo_launch_history_merge(int P, int M, float max_weight, int first_row, const uint8_t* row_flags, const float* conf0, const float* conf,
+                                    const float* xyz0, const float* shs0, const float* scaling0, const float* rot0_unit, float* xyz, float* shs,
+                                    float* scaling_raw, float* rotation_raw, hipStream_t s) {
     if (P <= 0 || !(max_weight > 0.f)) return DQO_OK;  // mapper.py:608-609
     DQO_LAUNCH("history_merge_kernel", history_merge_kernel, dim3((P + HM_THREADS - 1) / HM_THREADS), dim3(HM_THREADS), s, P, M, max_weight,
                first_row, row_flags, conf0, conf, xyz0, shs0, scaling0, rot0_unit, xyz, shs, scaling_raw, rotation_raw);
@@ -597,3 +597,104 @@ int dqo_launch_adam_advance(int32_t* step_dev, const DqoRastHeader* frame_header
     DQO_LAUNCH("adam_advance_kernel", adam_advance_kernel, dim3(1), dim3(1), s, step_dev, frame_header);
     return DQO_OK;
 }
+
+int dqo_check_adam_step(const DqoAdamStep* st, bool need_grads) {
+    DQO_CHECK_ARG(st, "null step");
+    DQO_CHECK_ARG(st->P >= 0 && st->M >= 1 && (st->step >= 1 || st->step_dev != nullptr), "bad P / M / step");
+    if (st->P == 0) return DQO_OK;
+    DQO_CHECK_ARG(st->xyz && st->shs && st->opacity_raw && st->scaling_raw && st->rotation_raw, "null parameter");
+    if (need_grads) DQO_CHECK_ARG(st->g_means3D && st->g_sh && st->g_opacity && st->g_scales && st->g_rotations, "null gradient");
+    DQO_CHECK_ARG(st->m_xyz && st->m_shs && st->m_opacity && st->m_scaling && st->m_rotation && st->v_xyz && st->v_shs &&
+                      st->v_opacity && st->v_scaling && st->v_rotation,
+                  "null optimiser state");
+    return DQO_OK;
+}
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+DQO_API int dqo_map_activate(int32_t P, const float* opacity_raw, const float* scaling_raw, const float* rotation_raw, float* opacity,
+                             float* scales, float* rotations, void* stream) {
+    DQO_CHECK_ARG(P >= 0, "bad P");
+    if (P == 0) return DQO_OK;
+    DQO_CHECK_ARG(opacity_raw && scaling_raw && rotation_raw && opacity && scales && rotations, "null pointer");
+    return dqo_launch_map_activate(P, opacity_raw, scaling_raw, rotation_raw, opacity, scales, rotations, (hipStream_t)stream);
+}
+
+DQO_API size_t dqo_map_loss_workspace_bytes(void) { return dqo_map_loss_ws_bytes(); }
+
+DQO_API int dqo_map_loss_fwd_bwd(int32_t W, int32_t H, const float* color, const float* depth, const int32_t* depth_index,
+                                 const float* gt_color, const float* gt_depth, const uint8_t* render_mask, float color_weight,
+                                 float depth_weight, float add_depth_thres, float* loss_out, float* dL_dcolor, float* dL_ddepth, void* ws,
+                                 size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(W > 0 && H > 0, "bad image size");
+    DQO_CHECK_ARG(color && depth && depth_index && gt_color && gt_depth && loss_out && dL_dcolor && dL_ddepth, "null pointer");
+    DQO_CHECK_WS("loss", ws, ws_bytes, dqo_map_loss_ws_bytes());
+    return dqo_launch_map_loss(W, H, color, depth, depth_index, gt_color, gt_depth, render_mask, color_weight, depth_weight,
+                               add_depth_thres, loss_out, dL_dcolor, dL_ddepth, ws, (hipStream_t)stream);
+}
+
+DQO_API size_t dqo_map_attach_workspace_bytes(int32_t P) { return dqo_map_attach_ws_bytes(P < 0 ? 0 : P); }
+
+DQO_API int dqo_map_history_merge(int32_t P, int32_t M, float max_weight, int32_t first_row, const uint8_t* row_flags, const float* conf0,
+                                  const float* conf, const float* xyz0, const float* shs0, const float* scaling0, const float* rot0_unit,
+                                  float* xyz, float* shs, float* scaling_raw, float* rotation_raw, void* stream) {
+    DQO_CHECK_ARG(P >= 0 && M >= 1 && M * 3 < 256, "bad P / M");
+    if (P == 0) return DQO_OK;
+    DQO_CHECK_ARG(first_row >= 0 && first_row < P, "first_row %d outside [0, %d)", first_row, P);
+    DQO_CHECK_ARG(conf0 && conf && xyz0 && shs0 && scaling0 && rot0_unit && xyz && shs && scaling_raw && rotation_raw, "null tensor");
+    return dqo_launch_history_merge(P, M, max_weight, first_row, row_flags, conf0, conf, xyz0, shs0, scaling0, rot0_unit, xyz, shs,
+                                    scaling_raw, rotation_raw, (hipStream_t)stream);
+}
+
+DQO_API int dqo_map_attach_loss_fwd_bwd(int32_t P, const float* scaling_raw, const float* xyz, const float* rotation_raw,
+                                        const float* init_scaling_raw, const float* init_xyz, const float* init_rotation_raw,
+                                        const uint8_t* attach_mask, int32_t attach_count, float* loss, float* g_scaling_raw, float* g_xyz,
+                                        float* g_rotation_raw, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(P >= 0 && attach_count >= 0, "bad P / attach_count");
+    DQO_CHECK_ARG(loss, "null loss");
+    if (P == 0) return dqo_launch_zero_words(reinterpret_cast<uint32_t*>(loss), 1, (hipStream_t)stream);
+    DQO_CHECK_ARG(scaling_raw && xyz && rotation_raw && init_scaling_raw && init_xyz && init_rotation_raw && attach_mask && g_scaling_raw &&
+                      g_xyz && g_rotation_raw, "null pointer");
+    DQO_CHECK_WS("attach-loss", ws, ws_bytes, dqo_map_attach_ws_bytes(P));
+    return dqo_launch_map_attach(P, scaling_raw, xyz, rotation_raw, init_scaling_raw, init_xyz, init_rotation_raw, attach_mask, attach_count,
+                                 loss, g_scaling_raw, g_xyz, g_rotation_raw, ws, (hipStream_t)stream);
+}
+
+static int check_adam_multi(const DqoAdamTensor* ts, int32_t n_tensors, double beta1, double beta2, double eps) {
+    DQO_CHECK_ARG(n_tensors >= 0 && n_tensors <= DQO_ADAM_MULTI_MAX, "n_tensors out of range");
+    DQO_CHECK_ARG(n_tensors == 0 || ts != nullptr, "null tensor list");
+    DQO_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0, "bad betas / eps");
+    int64_t total = 0;
+    for (int t = 0; t < n_tensors; t++) {
+        DQO_CHECK_ARG(ts[t].n >= 0, "negative element count");
+        DQO_CHECK_ARG(ts[t].n == 0 || (ts[t].p && ts[t].g && ts[t].m && ts[t].v), "null pointer in the tensor list");
+        total += ts[t].n;
+    }
+    DQO_CHECK_ARG(total < ((int64_t)1 << 40), "too many elements");
+    return DQO_OK;
+}
+
+DQO_API int dqo_adam_multi(const DqoAdamTensor* ts, int32_t n_tensors, int32_t step, double beta1, double beta2, double eps, void* stream) {
+    DQO_CHECK_ARG(step >= 1, "step is the 1-based count of this update");
+    const int rc = check_adam_multi(ts, n_tensors, beta1, beta2, eps);
+    if (rc) return rc;
+    return dqo_launch_adam_multi(ts, n_tensors, step, beta1, beta2, eps, (hipStream_t)stream, nullptr, 0);
+}
+
+DQO_API int dqo_adam_multi_dev(const DqoAdamTensor* ts, int32_t n_tensors, int32_t* step_dev, int32_t advance, double beta1, double beta2,
+                               double eps, void* stream) {
+    DQO_CHECK_ARG(step_dev != nullptr, "null step counter");
+    const int rc = check_adam_multi(ts, n_tensors, beta1, beta2, eps);
+    if (rc) return rc;
+    return dqo_launch_adam_multi(ts, n_tensors, 1, beta1, beta2, eps, (hipStream_t)stream, step_dev, advance != 0);
+}
+
+DQO_API int dqo_map_adam_step(const DqoAdamStep* st, void* stream) {
+    const int rc = dqo_check_adam_step(st, true);
+    if (rc) return rc;
+    if (st->P == 0) return DQO_OK;
+    return dqo_launch_map_adam(st, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -601,11 +601,6 @@ int dqo_launch_gaussian_rows(const DqoView& v, const DqoGeomLayout& g, const Dqo
     return DQO_OK;
 }
 
-int dqo_launch_blend_backward(const DqoView& v, const DqoGeomLayout& g, const DqoImageLayout& img, const DqoBinLayout& bin, int T,
-                              const float* dL_dcolor, const float* dL_ddepth, DqoGradRec* recs, uint8_t* valid, int64_t capacity,
-                              const DqoTapDev& tap, const DqoGateDev& gate, int list_split, hipStream_t s);
-int dqo_launch_adam_advance(int32_t* step_dev, const DqoRastHeader* frame_header, hipStream_t s);
-
 // blend backward + the fused per-Gaussian tail.  The caller (dqo_rast_backward_adam) has checked the arguments.
 int dqo_launch_backward_adam(const DqoRastParams* p, const DqoRastInputs* in, const DqoRastCtx* ctx, const float* dL_dcolor,
                              const float* dL_ddepth, const DqoAdamStep* st, void* ws, hipStream_t s) {

@@ -104,24 +104,53 @@ __global__ __launch_bounds__(256) void error_maps_kernel(int64_t HW, const float
 
 }  // namespace
 
-int dqo_launch_growth_scales(int n, const float* xyz, const int32_t* obj, const float* radius, const int32_t* i_new, const float* d2_old,
-                             const int32_t* i_old, const float* extra_radius, float reach2, float min_radius, float max_radius, float* scales,
-                             uint8_t* invalid, hipStream_t s) {
+static int dqo_launch_growth_scales(int n, const float* xyz, const int32_t* obj, const float* radius, const int32_t* i_new, const float* d2_old,
+                                    const int32_t* i_old, const float* extra_radius, float reach2, float min_radius, float max_radius, float* scales,
+                                    uint8_t* invalid, hipStream_t s) {
     if (n > 0)
         DQO_LAUNCH("growth_scales_kernel", growth_scales_kernel, dim3((n + 255) / 256), dim3(256), s, n, xyz, obj, radius, i_new, d2_old, i_old,
                    extra_radius, reach2, min_radius, max_radius, scales, invalid);
     return DQO_OK;
 }
 
-int dqo_launch_growth_inside(int n, const float* d2, const int32_t* idx, const float* radius, uint8_t* inside, hipStream_t s) {
+static int dqo_launch_growth_inside(int n, const float* d2, const int32_t* idx, const float* radius, uint8_t* inside, hipStream_t s) {
     if (n > 0) DQO_LAUNCH("growth_inside_kernel", growth_inside_kernel, dim3((n + 255) / 256), dim3(256), s, n, d2, idx, radius, inside);
     return DQO_OK;
 }
 
-int dqo_launch_error_maps(int64_t HW, const float* gt_color, const float* gt_depth, const float* render, const float* depth,
-                          const int32_t* depth_index, const uint8_t* mask, float* color_err, float* depth_err, hipStream_t s) {
+static int dqo_launch_error_maps(int64_t HW, const float* gt_color, const float* gt_depth, const float* render, const float* depth,
+                                 const int32_t* depth_index, const uint8_t* mask, float* color_err, float* depth_err, hipStream_t s) {
     if (HW > 0)
         DQO_LAUNCH("error_maps_kernel", error_maps_kernel, dim3((unsigned)((HW + 255) / 256)), dim3(256), s, HW, gt_color, gt_depth, render, depth,
                    depth_index, mask, color_err, depth_err);
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+DQO_API int dqo_growth_scales(int32_t n, const float* xyz, const int32_t* object, const float* radius, const int32_t* i_new,
+                              const float* d2_old, const int32_t* i_old, const float* extra_radius, float reach2, float min_radius,
+                              float max_radius, float* scales, uint8_t* invalid, void* stream) {
+    DQO_CHECK_ARG(n >= 0, "bad size");
+    if (n == 0) return DQO_OK;
+    DQO_CHECK_ARG(xyz && object && radius && scales && invalid, "null pointer");
+    DQO_CHECK_ARG(i_old == nullptr || (d2_old && extra_radius), "i_old without d2_old / extra_radius");
+    return dqo_launch_growth_scales(n, xyz, object, radius, i_new, d2_old, i_old, extra_radius, reach2, min_radius, max_radius, scales, invalid,
+                                    (hipStream_t)stream);
+}
+
+DQO_API int dqo_growth_inside(int32_t n, const float* d2, const int32_t* idx, const float* radius, uint8_t* inside, void* stream) {
+    DQO_CHECK_ARG(n >= 0, "bad size");
+    if (n == 0) return DQO_OK;
+    DQO_CHECK_ARG(d2 && idx && radius && inside, "null pointer");
+    return dqo_launch_growth_inside(n, d2, idx, radius, inside, (hipStream_t)stream);
+}
+
+DQO_API int dqo_error_maps(int32_t H, int32_t W, const float* gt_color, const float* gt_depth, const float* render, const float* depth,
+                           const int32_t* depth_index, const uint8_t* mask, float* color_err, float* depth_err, void* stream) {
+    DQO_CHECK_ARG(W > 0 && H > 0 && gt_color && gt_depth && render && depth && depth_index && color_err && depth_err, "bad size / null pointer");
+    return dqo_launch_error_maps((int64_t)W * H, gt_color, gt_depth, render, depth, depth_index, mask, color_err, depth_err, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -195,17 +195,17 @@ __global__ __launch_bounds__(256) void lifecycle_delete_kernel(DqoLifecycle a, L
 
 }  // namespace
 
-size_t dqo_lifecycle_ws_bytes(int64_t P) { return LC_HEAD_WORDS * 4 + dqo_align_up(lc_blocks(P) * LC_SUMS * sizeof(double), 256); }
+static size_t dqo_lifecycle_ws_bytes(int64_t P) { return LC_HEAD_WORDS * 4 + dqo_align_up(lc_blocks(P) * LC_SUMS * sizeof(double), 256); }
 
-int dqo_launch_lifecycle_vote(const DqoLifecycle* a, const float* gt_color, const float* gt_depth, const float* render, const float* depth,
-                              const int32_t* depth_index, const int32_t* color_index, hipStream_t s) {
+static int dqo_launch_lifecycle_vote(const DqoLifecycle* a, const float* gt_color, const float* gt_depth, const float* render, const float* depth,
+                                     const int32_t* depth_index, const int32_t* color_index, hipStream_t s) {
     const int64_t HW = (int64_t)a->W * a->H;
     DQO_LAUNCH("lifecycle_vote_kernel", lifecycle_vote_kernel, dim3((unsigned)((HW + 255) / 256)), dim3(256), s, HW, a->P, gt_color, gt_depth,
                render, depth, depth_index, color_index, 2.f * a->add_color_thres, 2.f * a->add_depth_thres, a->vote, a->render_header);
     return DQO_OK;
 }
 
-int dqo_launch_lifecycle_rows(const DqoLifecycle* a, hipStream_t s) {
+static int dqo_launch_lifecycle_rows(const DqoLifecycle* a, hipStream_t s) {
     const LcWorkspace w = lc_workspace(a->workspace);
     const dim3 grid((unsigned)lc_blocks(a->P)), block(256);
     if (a->stable_oversized) {
@@ -215,3 +215,38 @@ int dqo_launch_lifecycle_rows(const DqoLifecycle* a, hipStream_t s) {
     DQO_LAUNCH("lifecycle_delete_kernel", lifecycle_delete_kernel, grid, block, s, *a, w);
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+DQO_API size_t dqo_map_lifecycle_workspace_bytes(int32_t P) { return dqo_lifecycle_ws_bytes(P < 0 ? 0 : P); }
+
+static int check_lifecycle(const DqoLifecycle* a) {
+    DQO_CHECK_ARG(a != nullptr, "null DqoLifecycle");
+    DQO_CHECK_ARG(a->P >= 0 && a->delete_thresh >= 1, "bad P / delete_thresh");
+    if (a->P == 0) return DQO_OK;
+    DQO_CHECK_ARG(a->xyz && a->opacity_raw && a->scaling_raw && a->confidence && a->alive && a->row_flags && a->stable && a->add_tick &&
+                      a->depth_error_counter && a->color_error_counter && a->park && a->vote, "null per-Gaussian buffer / park / vote");
+    DQO_CHECK_WS("lifecycle", a->workspace, a->workspace_bytes, dqo_lifecycle_ws_bytes(a->P));
+    return DQO_OK;
+}
+
+DQO_API int dqo_map_lifecycle_vote(const DqoLifecycle* step, const float* gt_color, const float* gt_depth, const float* render_color,
+                                   const float* render_depth, const int32_t* depth_index, const int32_t* color_index, void* stream) {
+    const int rc = check_lifecycle(step);
+    if (rc) return rc;
+    DQO_CHECK_ARG(step->W > 0 && step->H > 0 && (int64_t)step->W * step->H < (1ll << 31), "bad image size");
+    DQO_CHECK_ARG(gt_color && gt_depth && render_color && render_depth && depth_index && color_index, "null image");
+    if (step->P == 0) return DQO_OK;
+    return dqo_launch_lifecycle_vote(step, gt_color, gt_depth, render_color, render_depth, depth_index, color_index, (hipStream_t)stream);
+}
+
+DQO_API int dqo_map_lifecycle_rows(const DqoLifecycle* step, void* stream) {
+    const int rc = check_lifecycle(step);
+    if (rc) return rc;
+    DQO_CHECK_ARG(step->stats != nullptr, "null stats");
+    if (step->P == 0) return dqo_launch_zero_words(reinterpret_cast<uint32_t*>(step->stats), 8, (hipStream_t)stream);
+    return dqo_launch_lifecycle_rows(step, (hipStream_t)stream);
+}
+
+}  // extern "C"

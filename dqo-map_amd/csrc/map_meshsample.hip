@@ -257,12 +257,12 @@ inline size_t ms_partial_bytes(int64_t F) { return dqo_align_up(ms_blocks(F) * s
 }  // namespace
 
 // the ticket words | MsState | bmax | bcount | bsum | cum (the last align_up(8 F, 256) bytes: dqo_eval.mesh_cum_view reads them for the tests)
-size_t dqo_mesh_sample_ws_bytes(int64_t F) {
+static size_t dqo_mesh_sample_ws_bytes(int64_t F) {
     return DQO_REDUCE_HEAD_WORDS * 4 + MS_STATE_BYTES + 3 * ms_partial_bytes(F) + dqo_align_up((size_t)F * sizeof(u64), 256);
 }
 
-int dqo_launch_mesh_sample(int V, const float* vertices, int F, const int32_t* faces, int count, uint64_t seed, float* points,
-                           int32_t* face_index, uint8_t* keep, int32_t* header, void* ws, hipStream_t s) {
+static int dqo_launch_mesh_sample(int V, const float* vertices, int F, const int32_t* faces, int count, uint64_t seed, float* points,
+                                  int32_t* face_index, uint8_t* keep, int32_t* header, void* ws, hipStream_t s) {
     MsArgs a;
     a.V = V, a.F = F, a.count = count, a.nblocks = (uint32_t)ms_blocks(F);
     a.seed_word = dqo_sample_seed_word(seed);
@@ -282,3 +282,25 @@ int dqo_launch_mesh_sample(int V, const float* vertices, int F, const int32_t* f
     DQO_LAUNCH("mesh_sample_kernel", mesh_sample_kernel, dim3((unsigned)(((int64_t)count + MS_THREADS - 1) / MS_THREADS)), block, s, a);
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+// trimesh.sample.sample_surface on the ground-truth mesh (SLAM/eval.py:247).  The face table's and dqo_nn1's row limit
+static bool mesh_size_ok(int32_t n) { return n >= 1 && n < (1 << 25); }
+
+DQO_API size_t dqo_mesh_sample_workspace_bytes(int32_t F, int32_t count) {
+    return mesh_size_ok(F) && mesh_size_ok(count) ? dqo_mesh_sample_ws_bytes(F) : 0;
+}
+
+DQO_API int dqo_mesh_sample(int32_t V, const float* vertices, int32_t F, const int32_t* faces, int32_t count, uint64_t seed, float* points,
+                            int32_t* face_index, uint8_t* keep, int32_t* header, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(V >= 1, "bad vertex count %d", V);
+    DQO_CHECK_ARG(mesh_size_ok(F), "bad face count %d: 1 to 2^25 - 1 faces", F);
+    DQO_CHECK_ARG(mesh_size_ok(count), "bad sample count %d: 1 to 2^25 - 1 samples", count);
+    DQO_CHECK_ARG(vertices && faces && points && keep && header, "null pointer");
+    DQO_CHECK_WS("mesh sample", ws, ws_bytes, dqo_mesh_sample_ws_bytes(F));
+    return dqo_launch_mesh_sample(V, vertices, F, faces, count, seed, points, face_index, keep, header, ws, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -210,10 +210,10 @@ __global__ __launch_bounds__(256) void msssim_level_kernel(int w, int h, const f
 
 }  // namespace
 
-size_t dqo_msssim_ws_bytes(int W, int H) { return ms_ws(nullptr, W, H).total; }
+static size_t dqo_msssim_ws_bytes(int W, int H) { return ms_ws(nullptr, W, H).total; }
 
-int dqo_launch_msssim(int W, int H, const float* render, const float* gt_color, const DqoRastHeader* header, float* out_row, void* ws,
-                      hipStream_t s) {
+static int dqo_launch_msssim(int W, int H, const float* render, const float* gt_color, const DqoRastHeader* header, float* out_row, void* ws,
+                             hipStream_t s) {
     const MsWorkspace k = ms_ws(ws, W, H);
     const DqoSsimWindow win = dqo_ssim_window();
     const float *x = render, *y = gt_color;
@@ -231,3 +231,22 @@ int dqo_launch_msssim(int W, int H, const float* render, const float* gt_color, 
     }
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+// eval_picture's "ssim" (SLAM/eval.py:19-25, :64): pytorch_msssim's ms_ssim, which asserts min(H, W) > (11 - 1) * 2^4
+static bool msssim_size_ok(int32_t W, int32_t H) { return W > 160 && H > 160 && (int64_t)W * H < (1ll << 31) / 3; }
+
+DQO_API size_t dqo_eval_ms_ssim_workspace_bytes(int32_t W, int32_t H) { return msssim_size_ok(W, H) ? dqo_msssim_ws_bytes(W, H) : 0; }
+
+DQO_API int dqo_eval_ms_ssim(int32_t W, int32_t H, const float* render, const float* gt_color, const DqoRastHeader* render_header, float* out,
+                             int32_t row, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(msssim_size_ok(W, H), "bad image size %d x %d: MS-SSIM needs both sides > 160 (five levels of an 11-tap window)", W, H);
+    DQO_CHECK_ARG(render && gt_color && out, "null pointer");
+    DQO_CHECK_ARG(row >= 0, "bad row %d", row);
+    DQO_CHECK_WS("ms_ssim", ws, ws_bytes, dqo_msssim_ws_bytes(W, H));
+    return dqo_launch_msssim(W, H, render, gt_color, render_header, out + (size_t)20 * row, ws, (hipStream_t)stream);
+}
+
+}  // extern "C"

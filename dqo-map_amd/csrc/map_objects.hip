@@ -554,11 +554,11 @@ ObjTable make_table(int cap_obj, int cap_views, float* axes, float* R, float* ce
 
 }  // namespace
 
-int dqo_launch_objmap_frame(int cap_obj, int cap_views, float* axes, float* R, float* center, int32_t* cat, int32_t* uid, int32_t* nviews,
-                            float* view_P34, float* view_bbox, int32_t* state, int M, const float* det_bbox, const float* det_ellipse,
-                            const int32_t* det_cat, const float* det_score, const float* depth, const float* K, const float* Rt, int W, int H,
-                            int frame_id, uint64_t seed, int32_t* det_fate, int32_t* det_row, float* det_depth, uint8_t* opt_flag,
-                            int32_t* frame_header, hipStream_t s) {
+static int dqo_launch_objmap_frame(int cap_obj, int cap_views, float* axes, float* R, float* center, int32_t* cat, int32_t* uid, int32_t* nviews,
+                                   float* view_P34, float* view_bbox, int32_t* state, int M, const float* det_bbox, const float* det_ellipse,
+                                   const int32_t* det_cat, const float* det_score, const float* depth, const float* K, const float* Rt, int W, int H,
+                                   int frame_id, uint64_t seed, int32_t* det_fate, int32_t* det_row, float* det_depth, uint8_t* opt_flag,
+                                   int32_t* frame_header, hipStream_t s) {
     const ObjTable t = make_table(cap_obj, cap_views, axes, R, center, cat, uid, nviews, view_P34, view_bbox, state);
     ObjFrame f;
     f.M = M, f.W = W, f.H = H, f.frame_id = frame_id, f.seed = seed, f.bbox = det_bbox, f.ellipse = det_ellipse, f.score = det_score;
@@ -568,17 +568,62 @@ int dqo_launch_objmap_frame(int cap_obj, int cap_views, float* axes, float* R, f
     return DQO_OK;
 }
 
-int dqo_launch_objmap_optimize(int cap_obj, int cap_views, float* axes, float* R, float* center, int32_t* uid, int32_t* nviews,
-                               float* view_P34, float* view_bbox, int32_t* state, const uint8_t* opt_flag, int frame_id, uint64_t seed,
-                               float* loss_hist, hipStream_t s) {
+static int dqo_launch_objmap_optimize(int cap_obj, int cap_views, float* axes, float* R, float* center, int32_t* uid, int32_t* nviews,
+                                      float* view_P34, float* view_bbox, int32_t* state, const uint8_t* opt_flag, int frame_id, uint64_t seed,
+                                      float* loss_hist, hipStream_t s) {
     const ObjTable t = make_table(cap_obj, cap_views, axes, R, center, nullptr, uid, nviews, view_P34, view_bbox, state);
     DQO_LAUNCH("objmap_optimize_kernel", objmap_optimize_kernel, dim3((cap_obj + 63) / 64), dim3(64), s, t, opt_flag, frame_id, seed, loss_hist);
     return DQO_OK;
 }
 
-int dqo_launch_objmap_mean_iou(int cap_obj, int cap_views, float* axes, float* R, float* center, int32_t* nviews, float* view_P34,
-                               float* view_bbox, int32_t* state, float* mean_iou, hipStream_t s) {
+static int dqo_launch_objmap_mean_iou(int cap_obj, int cap_views, float* axes, float* R, float* center, int32_t* nviews, float* view_P34,
+                                      float* view_bbox, int32_t* state, float* mean_iou, hipStream_t s) {
     const ObjTable t = make_table(cap_obj, cap_views, axes, R, center, nullptr, nullptr, nviews, view_P34, view_bbox, state);
     DQO_LAUNCH("objmap_mean_iou_kernel", objmap_mean_iou_kernel, dim3((cap_obj + 63) / 64), dim3(64), s, t, mean_iou);
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+// the object table's capacities: a row per lane of the one workgroup, a detection per lane of its first wave, room for a covering
+// replacement's doubled observation; the observation slots stay indexable with int
+static bool objmap_caps_ok(int32_t cap_obj, int32_t cap_views) {
+    return cap_obj >= 1 && cap_obj <= 1024 && cap_views >= 2 && (int64_t)cap_obj * cap_views * 12 <= (int64_t)0x7fffffff;
+}
+
+DQO_API int dqo_objmap_frame(int32_t cap_obj, int32_t cap_views, int32_t cap_det, float* obj_axes, float* obj_R, float* obj_center,
+                             int32_t* obj_cat, int32_t* obj_uid, int32_t* obj_nviews, float* view_P34, float* view_bbox, int32_t* state,
+                             int32_t M, const float* det_bbox, const float* det_ellipse, const int32_t* det_cat, const float* det_score,
+                             const float* depth, const float* K, const float* Rt, int32_t W, int32_t H, int32_t frame_id, uint64_t seed,
+                             int32_t* det_fate, int32_t* det_row, float* det_depth, uint8_t* opt_flag, int32_t* frame_header, void* stream) {
+    DQO_CHECK_ARG(objmap_caps_ok(cap_obj, cap_views), "bad capacities: cap_obj %d (1 to 1024), cap_views %d (2 or more)", cap_obj, cap_views);
+    DQO_CHECK_ARG(cap_det >= 1 && cap_det <= 64, "bad capacity: cap_det %d (1 to 64)", cap_det);
+    DQO_CHECK_ARG(M >= 1 && M <= cap_det, "bad detection count %d: 1 to cap_det = %d", M, cap_det);
+    DQO_CHECK_ARG(W >= 1 && H >= 1 && (int64_t)W * H <= (int64_t)0x7fffffff, "bad image size %d x %d", W, H);
+    DQO_CHECK_ARG(obj_axes && obj_R && obj_center && obj_cat && obj_uid && obj_nviews && view_P34 && view_bbox && state, "null pointer (table)");
+    DQO_CHECK_ARG(det_bbox && det_ellipse && det_cat && det_score && depth && K && Rt, "null pointer (frame)");
+    DQO_CHECK_ARG(det_fate && det_row && det_depth && opt_flag && frame_header, "null pointer (outputs)");
+    return dqo_launch_objmap_frame(cap_obj, cap_views, obj_axes, obj_R, obj_center, obj_cat, obj_uid, obj_nviews, view_P34, view_bbox, state, M,
+                                   det_bbox, det_ellipse, det_cat, det_score, depth, K, Rt, W, H, frame_id, seed, det_fate, det_row, det_depth,
+                                   opt_flag, frame_header, (hipStream_t)stream);
+}
+
+DQO_API int dqo_objmap_optimize(int32_t cap_obj, int32_t cap_views, float* obj_axes, float* obj_R, float* obj_center, int32_t* obj_uid,
+                                int32_t* obj_nviews, float* view_P34, float* view_bbox, int32_t* state, const uint8_t* opt_flag,
+                                int32_t frame_id, uint64_t seed, float* loss_hist, void* stream) {
+    DQO_CHECK_ARG(objmap_caps_ok(cap_obj, cap_views), "bad capacities: cap_obj %d (1 to 1024), cap_views %d (2 or more)", cap_obj, cap_views);
+    DQO_CHECK_ARG(obj_axes && obj_R && obj_center && obj_uid && obj_nviews && view_P34 && view_bbox && state && opt_flag, "null pointer");
+    return dqo_launch_objmap_optimize(cap_obj, cap_views, obj_axes, obj_R, obj_center, obj_uid, obj_nviews, view_P34, view_bbox, state, opt_flag,
+                                      frame_id, seed, loss_hist, (hipStream_t)stream);
+}
+
+DQO_API int dqo_objmap_mean_iou(int32_t cap_obj, int32_t cap_views, float* obj_axes, float* obj_R, float* obj_center, int32_t* obj_nviews,
+                                float* view_P34, float* view_bbox, int32_t* state, float* mean_iou, void* stream) {
+    DQO_CHECK_ARG(objmap_caps_ok(cap_obj, cap_views), "bad capacities: cap_obj %d (1 to 1024), cap_views %d (2 or more)", cap_obj, cap_views);
+    DQO_CHECK_ARG(obj_axes && obj_R && obj_center && obj_nviews && view_P34 && view_bbox && state && mean_iou, "null pointer");
+    return dqo_launch_objmap_mean_iou(cap_obj, cap_views, obj_axes, obj_R, obj_center, obj_nviews, view_P34, view_bbox, state, mean_iou,
+                                      (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -432,11 +432,11 @@ __global__ __launch_bounds__(SP_THREADS) void sample_emit_kernel(DqoGrowthSample
 
 }  // namespace
 
-size_t dqo_sample_ws_bytes(int64_t HW) {
+static size_t dqo_sample_ws_bytes(int64_t HW) {
     return SP_HEAD_WORDS * 4 + 2 * dqo_align_up(sp_blocks(HW) * 2 * sizeof(uint32_t), 256) + dqo_align_up((size_t)HW, 256);
 }
 
-int dqo_launch_growth_sample(const DqoGrowthSample* a, hipStream_t s) {
+static int dqo_launch_growth_sample(const DqoGrowthSample* a, hipStream_t s) {
     const int64_t HW = (int64_t)a->W * a->H;
     const SpWorkspace w = sp_workspace(a->workspace, HW);
     SpKeys keys;
@@ -455,3 +455,28 @@ int dqo_launch_growth_sample(const DqoGrowthSample* a, hipStream_t s) {
     DQO_LAUNCH("sample_emit_kernel", sample_emit_kernel, grid, block, s, *a, w, HW);
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+// Mapping.temp_points_init (SLAM/multiprocess/mapper.py:1231-1347), sample_pixels (SLAM/utils.py:145-212) and
+// GaussianPointCloud.add_empty_points (SLAM/gaussian_pointcloud.py:445-517)
+DQO_API size_t dqo_growth_sample_workspace_bytes(int32_t W, int32_t H) {
+    return (W > 0 && H > 0 && (int64_t)W * H < (1ll << 31) / 3) ? dqo_sample_ws_bytes((int64_t)W * H) : 0;
+}
+
+DQO_API int dqo_growth_sample(const DqoGrowthSample* a, void* stream) {
+    DQO_CHECK_ARG(a != nullptr, "null DqoGrowthSample");
+    DQO_CHECK_ARG(a->W > 0 && a->H > 0 && (int64_t)a->W * a->H < (1ll << 31) / 3, "bad image size");
+    DQO_CHECK_ARG(a->uniform_sample_num >= 0 && a->capacity >= 0 && a->M >= 1, "bad uniform_sample_num / capacity / M");
+    DQO_CHECK_ARG(a->key_bits >= 1 && a->key_bits <= 32, "key_bits must be in [1, 32]");
+    DQO_CHECK_ARG(a->transmission_sample_ratio >= 0.f && a->error_sample_ratio >= 0.f, "negative sample ratio");
+    DQO_CHECK_ARG(a->vertex && a->normal && a->color && a->depth && a->header, "null frame image / header");
+    DQO_CHECK_ARG(a->first_frame || (a->T && a->render_depth && a->render_color && a->depth_index), "null render image");
+    DQO_CHECK_ARG(a->capacity == 0 || (a->xyz && a->scales && a->rotations && a->opacity && a->shs && a->out_normal && a->pixel),
+                  "null row buffer");
+    DQO_CHECK_WS("growth sample", a->workspace, a->workspace_bytes, dqo_sample_ws_bytes((int64_t)a->W * a->H));
+    return dqo_launch_growth_sample(a, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -172,14 +172,14 @@ DqoSsimWindow dqo_ssim_window() {
     return w;
 }
 
-size_t dqo_map_ssim_ws_bytes(int W, int H) {
+static size_t dqo_map_ssim_ws_bytes(int W, int H) {
     const size_t HW = (size_t)W * H;
     const size_t blocks = (size_t)((W + SS_T - 1) / SS_T) * ((H + SS_T - 1) / SS_T) * 3;
     return dqo_align_up(sizeof(float) * 9 * HW, 256) + dqo_align_up(sizeof(float) * blocks, 256);
 }
 
-int dqo_launch_map_ssim(int W, int H, const float* img, const float* gt, float weight, float* ssim_out, float* dL_dimg, int accumulate,
-                        float* loss8, void* ws, hipStream_t s) {
+static int dqo_launch_map_ssim(int W, int H, const float* img, const float* gt, float weight, float* ssim_out, float* dL_dimg, int accumulate,
+                               float* loss8, void* ws, hipStream_t s) {
     const size_t HW = (size_t)W * H;
     float* maps = reinterpret_cast<float*>(ws);
     float* partial = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + dqo_align_up(sizeof(float) * 9 * HW, 256));
@@ -194,3 +194,18 @@ int dqo_launch_map_ssim(int W, int H, const float* img, const float* gt, float w
     }
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+DQO_API size_t dqo_map_ssim_workspace_bytes(int32_t W, int32_t H) { return (W > 0 && H > 0) ? dqo_map_ssim_ws_bytes(W, H) : 0; }
+
+DQO_API int dqo_map_ssim_fwd_bwd(int32_t W, int32_t H, const float* image, const float* gt_image, float weight, float* ssim_out,
+                                 float* dL_dimage, int32_t accumulate, float* loss_out8, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(W > 0 && H > 0, "bad image size");
+    DQO_CHECK_ARG(image && gt_image && ssim_out, "null pointer");
+    DQO_CHECK_WS("ssim", ws, ws_bytes, dqo_map_ssim_ws_bytes(W, H));
+    return dqo_launch_map_ssim(W, H, image, gt_image, weight, ssim_out, dL_dimage, accumulate != 0, loss_out8, ws, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -231,8 +231,8 @@ __global__ __launch_bounds__(256) void window_mask_expand_kernel(int W, int64_t 
 
 }  // namespace
 
-int dqo_launch_tile_count(int W, int H, int mode, const uint8_t* mask_in, const float* T_map, uint8_t* mask_out, int32_t* tile_count,
-                          int32_t* total, hipStream_t s) {
+static int dqo_launch_tile_count(int W, int H, int mode, const uint8_t* mask_in, const float* T_map, uint8_t* mask_out, int32_t* tile_count,
+                                 int32_t* total, hipStream_t s) {
     const int gx = (W + DQO_TILE - 1) / DQO_TILE, gy = (H + DQO_TILE - 1) / DQO_TILE;
     if (total) {
         int rc = dqo_launch_zero_words(reinterpret_cast<uint32_t*>(total), 1, s);
@@ -243,20 +243,20 @@ int dqo_launch_tile_count(int W, int H, int mode, const uint8_t* mask_in, const 
     return DQO_OK;
 }
 
-int dqo_launch_tile_color_error(int W, int H, const float* render, const float* gt, float* err_px, float* tile_sum, hipStream_t s) {
+static int dqo_launch_tile_color_error(int W, int H, const float* render, const float* gt, float* err_px, float* tile_sum, hipStream_t s) {
     const int gx = (W + DQO_TILE - 1) / DQO_TILE, gy = (H + DQO_TILE - 1) / DQO_TILE;
     DQO_LAUNCH("tile_color_error_kernel", tile_color_error_kernel, dim3(gx * gy), dim3(256), s, W, H, gx, render, gt, err_px, tile_sum);
     return DQO_OK;
 }
 
-size_t dqo_window_masks_ws_bytes(int W, int H) {
+static size_t dqo_window_masks_ws_bytes(int W, int H) {
     size_t total = 0;
     wm_ws(nullptr, (size_t)((W + DQO_TILE - 1) / DQO_TILE) * ((H + DQO_TILE - 1) / DQO_TILE), &total);
     return total;
 }
 
-int dqo_launch_window_masks(int W, int H, int mode, const float* T_map, const float* render, const float* gt, float tile_mask_ratio, int k,
-                            uint8_t* render_mask, int32_t* tile_mask, float* ratio_out, const DqoRastHeader* header, void* ws, hipStream_t s) {
+static int dqo_launch_window_masks(int W, int H, int mode, const float* T_map, const float* render, const float* gt, float tile_mask_ratio, int k,
+                                   uint8_t* render_mask, int32_t* tile_mask, float* ratio_out, const DqoRastHeader* header, void* ws, hipStream_t s) {
     const int gx = (W + DQO_TILE - 1) / DQO_TILE, gy = (H + DQO_TILE - 1) / DQO_TILE, T = gx * gy;
     const WmWorkspace w = wm_ws(ws, (size_t)T, nullptr);
     DQO_LAUNCH("window_masks_kernel", window_masks_kernel, dim3(T), dim3(256), s, W, H, gx, T, mode, T_map, render, gt, tile_mask_ratio, k,
@@ -269,3 +269,51 @@ int dqo_launch_window_masks(int W, int H, int mode, const float* T_map, const fl
     }
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+DQO_API int dqo_tile_count_mask(int32_t W, int32_t H, const uint8_t* pixel_mask, int32_t* tile_count, void* stream) {
+    DQO_CHECK_ARG(W > 0 && H > 0 && pixel_mask && tile_count, "bad size / null pointer");
+    return dqo_launch_tile_count(W, H, 0, pixel_mask, nullptr, nullptr, tile_count, nullptr, (hipStream_t)stream);
+}
+
+DQO_API int dqo_transmission_mask(int32_t W, int32_t H, const float* T_map, uint8_t* render_mask, int32_t* tile_count, int32_t* total,
+                                  void* stream) {
+    DQO_CHECK_ARG(W > 0 && H > 0 && T_map && tile_count, "bad size / null pointer");
+    return dqo_launch_tile_count(W, H, 1, nullptr, T_map, render_mask, tile_count, total, (hipStream_t)stream);
+}
+
+DQO_API int dqo_tile_color_error(int32_t W, int32_t H, const float* render, const float* gt, float* color_error, float* tile_sum,
+                                 void* stream) {
+    DQO_CHECK_ARG(W > 0 && H > 0 && render && gt && tile_sum, "bad size / null pointer");
+    return dqo_launch_tile_color_error(W, H, render, gt, color_error, tile_sum, (hipStream_t)stream);
+}
+
+// Mapping.evaluate_render_range (SLAM/multiprocess/mapper.py:930-988) as called once per frame of the window by local_optimize (:549-555)
+// and global_optimization (:1173-1189): render mask (:945, :970-978), tile mask (transmission2tilemask SLAM/utils.py:752-762 / the top-k of
+// colorerror2tilemask :766-799) and render ratio (:987) of one frame, written where the captured graphs read them
+static bool window_masks_size_ok(int32_t W, int32_t H) { return W > 0 && H > 0 && (int64_t)W * H < (1ll << 31) / 3; }
+
+DQO_API size_t dqo_window_masks_workspace_bytes(int32_t W, int32_t H) { return window_masks_size_ok(W, H) ? dqo_window_masks_ws_bytes(W, H) : 0; }
+
+DQO_API int dqo_window_masks(int32_t W, int32_t H, int32_t mode, const float* T_map, const float* render, const float* gt, float tile_mask_ratio,
+                             int32_t k, uint8_t* render_mask, int32_t* tile_mask, float* ratio_out, const DqoRastHeader* render_header,
+                             void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(window_masks_size_ok(W, H), "bad image size");
+    DQO_CHECK_ARG(mode >= 0 && mode <= 2, "bad mode %d", mode);
+    DQO_CHECK_ARG(render_mask && tile_mask && ratio_out, "null output");
+    const int64_t tiles = (int64_t)((W + 15) / 16) * ((H + 15) / 16);
+    if (mode == 1) {
+        DQO_CHECK_ARG(render && gt, "the error mode needs render and gt");
+        DQO_CHECK_ARG(k >= 0 && k <= tiles, "k = %d outside [0, %lld]", k, (long long)tiles);
+    } else {
+        DQO_CHECK_ARG(T_map != nullptr, "null T_map");
+    }
+    DQO_CHECK_ARG(ws != nullptr && ws_bytes >= dqo_window_masks_ws_bytes(W, H), "window_masks workspace too small (%zu < %zu)", ws_bytes,
+                  dqo_window_masks_ws_bytes(W, H));
+    return dqo_launch_window_masks(W, H, mode, T_map, render, gt, tile_mask_ratio, k, render_mask, tile_mask, ratio_out, render_header, ws,
+                                   (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -77,16 +77,38 @@ __global__ void quadric_adam_kernel(int n_obj, int n_iters, const int32_t* __res
 
 }  // namespace
 
-int dqo_launch_quadric_iou(int B, const float* axes, const float* R, const float* center, const float* P34, const float* obs,
-                           float* bbox, float* loss, int32_t* valid, float* g_axes, float* g_R, float* g_center, hipStream_t s) {
+static int dqo_launch_quadric_iou(int B, const float* axes, const float* R, const float* center, const float* P34, const float* obs,
+                                  float* bbox, float* loss, int32_t* valid, float* g_axes, float* g_R, float* g_center, hipStream_t s) {
     DQO_LAUNCH("quadric_iou_kernel", quadric_iou_kernel, dim3((B + 63) / 64), dim3(64), s, B, axes, R, center, P34, obs, bbox, loss, valid, g_axes,
                        g_R, g_center);
     return DQO_OK;
 }
 
-int dqo_launch_quadric_adam(int n_obj, int n_iters, const int32_t* view_offset, const float* P34_views, const float* obs_views,
-                            const int32_t* view_schedule, float* axes, float* R, float* center, float* loss_hist, hipStream_t s) {
+static int dqo_launch_quadric_adam(int n_obj, int n_iters, const int32_t* view_offset, const float* P34_views, const float* obs_views,
+                                   const int32_t* view_schedule, float* axes, float* R, float* center, float* loss_hist, hipStream_t s) {
     DQO_LAUNCH("quadric_adam_kernel", quadric_adam_kernel, dim3((n_obj + 63) / 64), dim3(64), s, n_obj, n_iters, view_offset, P34_views, obs_views,
                        view_schedule, axes, R, center, loss_hist);
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+DQO_API int dqo_quadric_iou_fwd_bwd(int32_t B, const float* axes, const float* R, const float* center, const float* P34, const float* obs,
+                                    float* bbox, float* loss, int32_t* valid, float* g_axes, float* g_R, float* g_center, void* stream) {
+    DQO_CHECK_ARG(B >= 0, "bad B");
+    if (B == 0) return DQO_OK;
+    DQO_CHECK_ARG(axes && R && center && P34 && obs && bbox && loss && valid && g_axes && g_R && g_center, "null pointer");
+    return dqo_launch_quadric_iou(B, axes, R, center, P34, obs, bbox, loss, valid, g_axes, g_R, g_center, (hipStream_t)stream);
+}
+
+DQO_API int dqo_quadric_adam(int32_t n_obj, int32_t n_iters, const int32_t* view_offset, const float* P34_views, const float* obs_views,
+                             const int32_t* view_schedule, float* axes, float* R, float* center, float* loss_hist, void* stream) {
+    DQO_CHECK_ARG(n_obj >= 0 && n_iters >= 0, "bad sizes");
+    if (n_obj == 0 || n_iters == 0) return DQO_OK;
+    DQO_CHECK_ARG(view_offset && P34_views && obs_views && view_schedule && axes && R && center, "null pointer");
+    return dqo_launch_quadric_adam(n_obj, n_iters, view_offset, P34_views, obs_views, view_schedule, axes, R, center, loss_hist,
+                                   (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -16,13 +16,6 @@
 //     rule (cov2D, projection, SH, cov3D, depth-hit Jacobians, dqo_gauss_chain.h) and writes the gradient rows.
 #include "dqo_common.h"
 
-int dqo_launch_blend_backward(const DqoView& v, const DqoGeomLayout& g, const DqoImageLayout& img, const DqoBinLayout& bin, int T,
-                              const float* dL_dcolor, const float* dL_ddepth, DqoGradRec* recs, uint8_t* valid, int64_t capacity,
-                              const DqoTapDev& tap, const DqoGateDev& gate, int list_split, hipStream_t s);
-int dqo_launch_gaussian_rows(const DqoView& v, const DqoGeomLayout& g, const DqoRastInputs* in, const DqoGradRec* recs, const uint8_t* valid,
-                             int64_t cap, const DqoRastGrads& gr, hipStream_t s, uint32_t frame_words, uint32_t* hist, uint32_t hist_words,
-                             bool pf, float* dL_drest);
-
 int dqo_launch_backward(const DqoRastParams* p, const DqoRastInputs* in, const DqoRastCtx* ctx, const float* dL_dcolor,
                         const float* dL_ddepth, const int32_t* hit_image, DqoRastGrads* gr, void* ws, size_t ws_bytes, hipStream_t s,
                         const DqoShRest* pf, float* dL_drest) {

@@ -684,13 +684,6 @@ __global__ void mark_visible_kernel(int P, const float* __restrict__ means3D, co
 
 }  // namespace
 
-int dqo_launch_blend_forward(const DqoView& v, const DqoGeomLayout& g, const DqoImageLayout& img, const DqoBinLayout& bin,
-                             const DqoRastOutputs& out, int T, const DqoTapDev& tap, const DqoGateDev& gate, int list_split, hipStream_t s,
-                             int64_t header_capacity);
-int dqo_launch_bin_count(int P, int gx, const int32_t* tile_mask, const DqoGeomLayout& g, const DqoImageLayout& img, const DqoBinLayout& bin,
-                         int64_t capacity, const unsigned long long* tile_objects, hipStream_t s, const uint8_t* row_flags);
-int dqo_launch_bin_place(const DqoGeomLayout& g, const DqoImageLayout& img, const DqoBinLayout& bin, int64_t capacity, hipStream_t s);
-
 int dqo_launch_zero_words(uint32_t* p, size_t n_words, hipStream_t s) {
     if (n_words == 0) return DQO_OK;
     DQO_LAUNCH("zero_words_kernel", zero_words_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), s, p, n_words);
@@ -838,8 +831,20 @@ bool dqo_fuse_k1(const DqoRastParams* p, const DqoRastCtx* ctx) {
     return on && ctx->frame_prezeroed != 0 && p->P > 0 && ctx->tile_bucket_capacity > 0 && dqo_k1_where(p->P) != 0;
 }
 
-int dqo_launch_mark_visible(int P, const float* means3D, const float* view, const float* proj, uint8_t* present, hipStream_t s) {
+static int dqo_launch_mark_visible(int P, const float* means3D, const float* view, const float* proj, uint8_t* present, hipStream_t s) {
     if (P <= 0) return DQO_OK;
     DQO_LAUNCH("mark_visible_kernel", mark_visible_kernel, dim3((P + 255) / 256), dim3(256), s, P, means3D, view, proj, present);
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+DQO_API int dqo_mark_visible(int32_t P, const float* means3D, const float* view, const float* proj, uint8_t* present, void* stream) {
+    DQO_CHECK_ARG(P >= 0, "bad P");
+    if (P == 0) return DQO_OK;
+    DQO_CHECK_ARG(means3D && view && proj && present, "null pointer");
+    return dqo_launch_mark_visible(P, means3D, view, proj, present, (hipStream_t)stream);
+}
+
+}  // extern "C"

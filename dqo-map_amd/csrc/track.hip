@@ -304,14 +304,14 @@ TrackLevels make_levels(int H, int W, int levels) {
 
 }  // namespace
 
-size_t dqo_track_preprocess_ws_bytes(int H, int W) {
+static size_t dqo_track_preprocess_ws_bytes(int H, int W) {
     const size_t HW = (size_t)H * W;
     return dqo_align_up(HW * 4 * sizeof(float), 256) + 2 * sizeof(float) * TR_MAX_BLOCKS;
 }
 
-int dqo_launch_track_preprocess(int H, int W, const float* depth, const float* K, float min_depth, float max_depth,
-                                float conf_thr, int filter, float* depth_out, float* vertex_out, float* normal_out, float* conf_out,
-                                uint8_t* invalid_out, void* ws, hipStream_t s) {
+static int dqo_launch_track_preprocess(int H, int W, const float* depth, const float* K, float min_depth, float max_depth,
+                                       float conf_thr, int filter, float* depth_out, float* vertex_out, float* normal_out, float* conf_out,
+                                       uint8_t* invalid_out, void* ws, hipStream_t s) {
     const int HW = H * W;
     float* dws = (float*)ws;
     float* vws = dws + HW;
@@ -324,16 +324,16 @@ int dqo_launch_track_preprocess(int H, int W, const float* depth, const float* K
     return DQO_OK;
 }
 
-size_t dqo_track_pyramid_ws_bytes(void) { return 2 * sizeof(float) * TR_PYR_MAX_BLOCKS * TR_MAX_LEVELS; }
+static size_t dqo_track_pyramid_ws_bytes(void) { return 2 * sizeof(float) * TR_PYR_MAX_BLOCKS * TR_MAX_LEVELS; }
 
-int64_t dqo_track_pyramid_pixel_count(int H, int W, int levels) {
+static int64_t dqo_track_pyramid_pixel_count(int H, int W, int levels) {
     int64_t n = 0;
     for (int i = 0; i < levels; i++) n += (int64_t)(H >> (levels - 1 - i)) * (W >> (levels - 1 - i));
     return n;
 }
 
-int dqo_launch_track_pyramid(int H, int W, int levels, const float* depth, const float* K, float* vertex, float* normal,
-                             void* ws, hipStream_t s) {
+static int dqo_launch_track_pyramid(int H, int W, int levels, const float* depth, const float* K, float* vertex, float* normal,
+                                    void* ws, hipStream_t s) {
     const TrackLevels py = make_levels(H, W, levels);
     const int nblk = py.lv[levels - 1].blk0 + py.lv[levels - 1].nblk;
     float* partial = (float*)ws;
@@ -342,18 +342,18 @@ int dqo_launch_track_pyramid(int H, int W, int levels, const float* depth, const
     return DQO_OK;
 }
 
-int dqo_launch_track_fill(int H, int W, float* render_depth, const float* frame_depth, const float* render_normal, const float* frame_normal,
-                          float dist_thr, float normal_thr, hipStream_t s) {
+static int dqo_launch_track_fill(int H, int W, float* render_depth, const float* frame_depth, const float* render_normal, const float* frame_normal,
+                                 float dist_thr, float normal_thr, hipStream_t s) {
     const int HW = H * W;
     DQO_LAUNCH("track_fill_kernel", track_fill_kernel, dim3((HW + TR_THREADS - 1) / TR_THREADS), dim3(TR_THREADS), s, HW, render_depth,
                frame_depth, render_normal, frame_normal, dist_thr, normal_thr);
     return DQO_OK;
 }
 
-size_t dqo_track_p2p_ws_bytes(void) { return sizeof(double) * TR_MAX_BLOCKS; }
+static size_t dqo_track_p2p_ws_bytes(void) { return sizeof(double) * TR_MAX_BLOCKS; }
 
-int dqo_launch_track_p2p(int H, int W, const float* vertex0, const float* vertex1, const float* normal0, const float* pose10, float fail_thr,
-                         const int32_t* valid_count, float* loss, int32_t* success, float* valid_ratio, void* ws, hipStream_t s) {
+static int dqo_launch_track_p2p(int H, int W, const float* vertex0, const float* vertex1, const float* normal0, const float* pose10, float fail_thr,
+                                const int32_t* valid_count, float* loss, int32_t* success, float* valid_ratio, void* ws, hipStream_t s) {
     const int HW = H * W;
     const int nblk = blocks_for(HW, TR_MAX_BLOCKS);
     double* partial = (double*)ws;
@@ -363,3 +363,61 @@ int dqo_launch_track_p2p(int H, int W, const float* vertex0, const float* vertex
                success, valid_ratio);
     return DQO_OK;
 }
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+// image sizes of the tracker entry points: positive, and H * W * 4 floats still indexable with int
+static bool track_size_ok(int32_t H, int32_t W) { return H > 0 && W > 0 && (int64_t)H * W < (int64_t)0x7fffffff / 4; }
+
+DQO_API size_t dqo_track_preprocess_workspace_bytes(int32_t H, int32_t W) {
+    return track_size_ok(H, W) ? dqo_track_preprocess_ws_bytes(H, W) : 0;
+}
+
+DQO_API int dqo_track_preprocess(int32_t H, int32_t W, const float* depth, const float* K, float min_depth, float max_depth, float conf_thr,
+                                 int32_t depth_filter, float* depth_out, float* vertex_out, float* normal_out, float* conf_out,
+                                 uint8_t* invalid_out, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(track_size_ok(H, W), "bad image size");
+    DQO_CHECK_ARG(depth && K && depth_out && vertex_out && normal_out && conf_out && invalid_out, "null pointer");
+    DQO_CHECK_WS("track preprocess", ws, ws_bytes, dqo_track_preprocess_ws_bytes(H, W));
+    return dqo_launch_track_preprocess(H, W, depth, K, min_depth, max_depth, conf_thr, depth_filter ? 1 : 0, depth_out, vertex_out,
+                                       normal_out, conf_out, invalid_out, ws, (hipStream_t)stream);
+}
+
+DQO_API int64_t dqo_track_pyramid_pixels(int32_t H, int32_t W, int32_t levels) {
+    if (!track_size_ok(H, W) || levels < 1 || levels > 4) return -1;
+    return dqo_track_pyramid_pixel_count(H, W, levels);
+}
+
+DQO_API size_t dqo_track_pyramid_workspace_bytes(void) { return dqo_track_pyramid_ws_bytes(); }
+
+DQO_API int dqo_track_pyramid(int32_t H, int32_t W, int32_t levels, const float* depth, const float* K, float* vertex, float* normal, void* ws,
+                              size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(levels >= 1 && levels <= 4, "levels must be in [1, 4]");
+    DQO_CHECK_ARG(track_size_ok(H, W) && (H >> (levels - 1)) > 0 && (W >> (levels - 1)) > 0, "bad image size for %d levels", levels);
+    DQO_CHECK_ARG(depth && K && vertex && normal, "null pointer");
+    DQO_CHECK_WS("track pyramid", ws, ws_bytes, dqo_track_pyramid_ws_bytes());
+    return dqo_launch_track_pyramid(H, W, levels, depth, K, vertex, normal, ws, (hipStream_t)stream);
+}
+
+DQO_API int dqo_track_fill_model_depth(int32_t H, int32_t W, float* render_depth, const float* frame_depth, const float* render_normal,
+                                       const float* frame_normal, float dist_thr, float normal_thr, void* stream) {
+    DQO_CHECK_ARG(track_size_ok(H, W), "bad image size");
+    DQO_CHECK_ARG(render_depth && frame_depth && render_normal && frame_normal, "null pointer");
+    return dqo_launch_track_fill(H, W, render_depth, frame_depth, render_normal, frame_normal, dist_thr, normal_thr, (hipStream_t)stream);
+}
+
+DQO_API size_t dqo_track_p2p_workspace_bytes(void) { return dqo_track_p2p_ws_bytes(); }
+
+DQO_API int dqo_track_p2p_loss(int32_t H, int32_t W, const float* vertex0, const float* vertex1, const float* normal0, const float* pose10,
+                               float fail_thr, const int32_t* valid_count, float* loss, int32_t* success, float* valid_ratio, void* ws,
+                               size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(track_size_ok(H, W), "bad image size");
+    DQO_CHECK_ARG(vertex0 && vertex1 && normal0 && pose10 && loss && success, "null pointer");
+    DQO_CHECK_ARG((valid_count == nullptr) == (valid_ratio == nullptr), "valid_count and valid_ratio go together");
+    DQO_CHECK_WS("track p2p", ws, ws_bytes, dqo_track_p2p_ws_bytes());
+    return dqo_launch_track_p2p(H, W, vertex0, vertex1, normal0, pose10, fail_thr, valid_count, loss, success, valid_ratio, ws,
+                                (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -400,10 +400,8 @@ def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov
     lib = N.lib()
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:67-70
-    N.require_gpu(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask, rs.bg, rs.viewmatrix,
-                  rs.projmatrix, rs.campos)
-    if not means3D.is_cuda:
-        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    N.require_gpu_op(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask, rs.bg, rs.viewmatrix,
+                     rs.projmatrix, rs.campos)
     dev = means3D.device
     means3D, opacities = _f32(means3D, "means3D"), _f32(opacities, "opacities")
     sh, colors_precomp = _f32(sh, "sh"), _f32(colors_precomp, "colors_precomp")
@@ -752,9 +750,7 @@ class GaussianRasterizer(nn.Module):
         # frustum test of rasterizer_impl.cu:54-66 for the camera in raster_settings
         with torch.no_grad():
             rs = self.raster_settings
-            N.require_gpu(positions, rs.viewmatrix, rs.projmatrix)
-            if not positions.is_cuda:
-                raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+            N.require_gpu_op(positions, rs.viewmatrix, rs.projmatrix)
             positions = _f32(positions, "positions")
             P = positions.size(0)
             visible = torch.zeros((P,), dtype=torch.bool, device=positions.device)

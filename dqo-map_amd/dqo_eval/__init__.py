@@ -73,17 +73,32 @@ PCD_THRES_MAX = 8
 PCD_ROW = (("accuracy", "completion", "chamfer", "n_thres") + tuple(f"{n}{t}" for t in range(PCD_THRES_MAX) for n in ("P", "R", "F1_"))
            + ("unused28", "unused29", "unused30", "unused31"))
 
-_workspaces = {}
+_workspaces = {}  # the module's own workspaces, one per (operator, device, sizes)
+
+
+def _workspace(key, nbytes, dev):
+    ws = _workspaces.get(key)
+    if ws is None:
+        ws = _workspaces[key] = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _dev_index(dev):
+    return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
+def _picture_bytes(W, H):
+    lib = N.lib()
+    n = lib.dqo_eval_picture_workspace_bytes(W, H)
+    if n == 0:
+        raise RuntimeError(f"dqo_eval: bad image size {W} x {H}")
+    return n + lib.dqo_map_ssim_workspace_bytes(W, H)
 
 
 def workspace(W, H, device):
     """The two workspaces of one evaluation at W x H as one uint8 tensor: dqo_eval_picture's (zero when first used, handed back ready by
     every call) followed by dqo_map_ssim_fwd_bwd's.  Calls that share one must be ordered on one stream."""
-    lib = N.lib()
-    n = lib.dqo_eval_picture_workspace_bytes(W, H)
-    if n == 0:
-        raise RuntimeError(f"dqo_eval: bad image size {W} x {H}")
-    return torch.zeros((n + lib.dqo_map_ssim_workspace_bytes(W, H),), dtype=torch.uint8, device=device)
+    return torch.zeros((_picture_bytes(W, H),), dtype=torch.uint8, device=device)
 
 
 def _image(t, channels, H, W, dtype, name):
@@ -115,9 +130,7 @@ def eval_picture(render_output, gt_color, gt_depth, min_depth, max_depth, out=No
     module — calls that share it must be on one stream).  render_header: the geometry buffer of the forward that rendered the frame
     (uint8 tensor); a frame that overflowed its context then gets a row of NaN.  GPU tensors only: a CPU tensor raises RuntimeError."""
     render, depth, index = render_output["render"], render_output["depth"], render_output["depth_index_map"]
-    N.require_gpu(render, depth, index, gt_color, gt_depth, out)
-    if not render.is_cuda:
-        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    N.require_gpu_op(render, depth, index, gt_color, gt_depth, out)
     lib, dev = N.lib(), render.device
     H, W = int(render.shape[-2]), int(render.shape[-1])
     f32 = torch.float32
@@ -128,12 +141,7 @@ def eval_picture(render_output, gt_color, gt_depth, min_depth, max_depth, out=No
         out, row = torch.full((1, 8), float("nan"), dtype=f32, device=dev), 0
     if out.dim() != 2 or out.shape[1] != 8 or out.dtype != f32 or not out.is_contiguous() or not 0 <= int(row) < out.shape[0]:
         raise RuntimeError("dqo_eval.eval_picture: out must be a contiguous float32 [K,8] table and row one of its rows")
-    ws = workspace_buffer
-    if ws is None:
-        key = (dev.index if dev.index is not None else torch.cuda.current_device(), W, H)
-        ws = _workspaces.get(key)
-        if ws is None:
-            ws = _workspaces[key] = workspace(W, H, dev)
+    ws = workspace_buffer if workspace_buffer is not None else _workspace((_dev_index(dev), W, H), _picture_bytes(W, H), dev)
     n_eval = lib.dqo_eval_picture_workspace_bytes(W, H)
     with torch.cuda.device(dev):
         stream = N.current_stream()
@@ -147,14 +155,18 @@ def eval_picture(render_output, gt_color, gt_depth, min_depth, max_depth, out=No
     return out[int(row)]
 
 
-def ms_ssim_workspace(W, H, device):
-    """dqo_eval_ms_ssim's workspace at W x H as a uint8 tensor (zero when first used, handed back ready by every call): the ticket words,
-    the level means and the pooled levels 1..4 of both images."""
+def _ms_ssim_bytes(W, H):
     n = N.lib().dqo_eval_ms_ssim_workspace_bytes(int(W), int(H))
     if n == 0:
         raise RuntimeError(f"dqo_eval.ms_ssim: bad image size {W} x {H}: both sides must be at least {MS_MIN_SIDE} (five levels of an "
                            "11-tap window)")
-    return torch.zeros((n,), dtype=torch.uint8, device=device)
+    return n
+
+
+def ms_ssim_workspace(W, H, device):
+    """dqo_eval_ms_ssim's workspace at W x H as a uint8 tensor (zero when first used, handed back ready by every call): the ticket words,
+    the level means and the pooled levels 1..4 of both images."""
+    return torch.zeros((_ms_ssim_bytes(W, H),), dtype=torch.uint8, device=device)
 
 
 def ms_ssim(image, gt, out=None, row=0, *, workspace_buffer=None, render_header=None):
@@ -172,9 +184,7 @@ def ms_ssim(image, gt, out=None, row=0, *, workspace_buffer=None, render_header=
     workspace_buffer: a tensor of ms_ssim_workspace(W, H, device) the caller keeps (default: one per device and image size, kept by this
     module — calls that share it must be on one stream).  render_header: as eval_picture's — a frame that overflowed its context gets
     a row of NaN.  GPU tensors only: a CPU tensor raises RuntimeError."""
-    N.require_gpu(image, gt, out)
-    if not image.is_cuda:
-        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    N.require_gpu_op(image, gt, out)
     lib, dev = N.lib(), image.device
     H, W = int(image.shape[-2]), int(image.shape[-1])
     f32 = torch.float32
@@ -186,12 +196,7 @@ def ms_ssim(image, gt, out=None, row=0, *, workspace_buffer=None, render_header=
         out, row = torch.full((1, 20), float("nan"), dtype=f32, device=dev), 0
     if out.dim() != 2 or out.shape[1] != 20 or out.dtype != f32 or not out.is_contiguous() or not 0 <= int(row) < out.shape[0]:
         raise RuntimeError("dqo_eval.ms_ssim: out must be a contiguous float32 [K,20] table and row one of its rows")
-    ws = workspace_buffer
-    if ws is None:
-        key = ("ms", _dev_index(dev), W, H)
-        ws = _workspaces.get(key)
-        if ws is None:
-            ws = _workspaces[key] = ms_ssim_workspace(W, H, dev)
+    ws = workspace_buffer if workspace_buffer is not None else _workspace(("ms", _dev_index(dev), W, H), _ms_ssim_bytes(W, H), dev)
     with torch.cuda.device(dev):
         N.check(lib.dqo_eval_ms_ssim(W, H, N.ptr(image), N.ptr(gt), N.ptr(render_header), out.data_ptr(), int(row), ws.data_ptr(), ws.numel(),
                                      N.current_stream()))
@@ -246,17 +251,6 @@ def _xform(t, dev, name):
     return t[:3].to(torch.float32).contiguous().to(dev)  # (a host transform: one small upload, no read)
 
 
-def _workspace(key, nbytes, dev):
-    ws = _workspaces.get(key)
-    if ws is None:
-        ws = _workspaces[key] = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
-    return ws
-
-
-def _dev_index(dev):
-    return dev.index if dev.index is not None else torch.cuda.current_device()
-
-
 def nearest(query, ref, query_keep=None, ref_keep=None, query_transform=None, ref_transform=None, want_idx=True, workspace_buffer=None):
     """The exact nearest reference of every query, both sets large (dqo_nn1): query [Q,3], ref [R,3] -> (dist2 float32 [Q], idx int32 [Q]
     or None).  dist2 is the smallest float32 dx*dx + dy*dy + dz*dz over the kept references, idx a reference attaining it (ties:
@@ -264,9 +258,7 @@ def nearest(query, ref, query_keep=None, ref_keep=None, query_transform=None, re
     reference: FLT_MAX / -1 everywhere.  *_transform: [3,4] / [4,4], applied to the rows as they are loaded.  No host read, no
     synchronisation; workspace_buffer: a uint8 tensor of dqo_nn1_workspace_bytes(Q, R) the caller keeps (default: one per device and
     size, kept by this module — calls that share it must be on one stream)."""
-    N.require_gpu(query, ref, query_keep, ref_keep)
-    if not (query.is_cuda and ref.is_cuda):
-        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    N.require_gpu_op((query, ref), query_keep, ref_keep)
     lib, dev = N.lib(), query.device
     query, ref = _points(query, "query"), _points(ref, "ref")
     Q, R = int(query.shape[0]), int(ref.shape[0])
@@ -315,9 +307,7 @@ def densify(xyz, scaling_raw, rotation_raw, sigma=1, circle_num=30, levels=5, th
     function forms the cos / sin table on the CPU and uploads it from pageable memory on every call, a small copy the host waits for
     (it is inside every time measured through this function).
     GPU tensors only: a CPU tensor raises RuntimeError."""
-    N.require_gpu(xyz, scaling_raw, rotation_raw, keep)
-    if not (xyz.is_cuda and scaling_raw.is_cuda and rotation_raw.is_cuda):
-        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    N.require_gpu_op((xyz, scaling_raw, rotation_raw), keep)
     lib, dev = N.lib(), xyz.device
     P = int(xyz.shape[0]) if xyz.dim() == 2 else -1
     for t, w, name in ((xyz, 3, "xyz"), (scaling_raw, 3, "scaling_raw"), (rotation_raw, 4, "rotation_raw")):
@@ -389,9 +379,7 @@ def sample_surface(vertices, faces, count, seed=0, want_face_index=False, worksp
     not synchronise and can be captured in a graph; the same arguments give the same bits.
     workspace_buffer: a tensor of mesh_sample_workspace(F, count, device) the caller keeps (default: one per device and sizes, kept by
     this module — calls that share it must be on one stream).  GPU tensors only: a CPU tensor raises RuntimeError."""
-    N.require_gpu(vertices, faces, workspace_buffer)
-    if not (vertices.is_cuda and faces.is_cuda):
-        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    N.require_gpu_op((vertices, faces), workspace_buffer)
     lib, dev = N.lib(), vertices.device
     for t, dt, name in ((vertices, torch.float32, "vertices"), (faces, torch.int32, "faces")):
         if t.dim() != 2 or t.shape[1] != 3 or t.dtype != dt or not t.is_contiguous() or t.device != dev:
@@ -413,12 +401,16 @@ def sample_surface(vertices, faces, count, seed=0, want_face_index=False, worksp
     return dict(points=points, face_index=face_index, keep=keep, header=header)
 
 
-def pcd_workspace(n_gt, n_rec, device):
-    """dqo_eval_pcd's workspace for these sizes as a uint8 tensor (zero when first used, handed back ready by every call)."""
+def _pcd_bytes(n_gt, n_rec):
     n = N.lib().dqo_eval_pcd_workspace_bytes(int(n_gt), int(n_rec))
     if n == 0:
         raise RuntimeError(f"dqo_eval: bad point counts {n_gt}, {n_rec} (at most 2^25 - 1 rows per set)")
-    return torch.zeros((n,), dtype=torch.uint8, device=device)
+    return n
+
+
+def pcd_workspace(n_gt, n_rec, device):
+    """dqo_eval_pcd's workspace for these sizes as a uint8 tensor (zero when first used, handed back ready by every call)."""
+    return torch.zeros((_pcd_bytes(n_gt, n_rec),), dtype=torch.uint8, device=device)
 
 
 def eval_pcd(gt_points, rec_points, dist_thres=(0.03,), transform=None, gt_keep=None, rec_keep=None, out=None, row=0, workspace_buffer=None):
@@ -436,9 +428,7 @@ def eval_pcd(gt_points, rec_points, dist_thres=(0.03,), transform=None, gt_keep=
 
     workspace_buffer: a tensor of pcd_workspace(G, P, device) the caller keeps (default: one per device and sizes, kept by this module —
     calls that share it must be on one stream).  GPU tensors only: a CPU tensor raises RuntimeError."""
-    N.require_gpu(gt_points, rec_points, gt_keep, rec_keep, out)
-    if not (gt_points.is_cuda and rec_points.is_cuda):
-        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    N.require_gpu_op((gt_points, rec_points), gt_keep, rec_keep, out)
     lib, dev = N.lib(), rec_points.device
     gt, rec = _points(gt_points, "gt_points"), _points(rec_points, "rec_points")
     G, P = int(gt.shape[0]), int(rec.shape[0])
@@ -451,12 +441,7 @@ def eval_pcd(gt_points, rec_points, dist_thres=(0.03,), transform=None, gt_keep=
         out, row = torch.empty((1, 32), dtype=torch.float32, device=dev), 0
     if out.dim() != 2 or out.shape[1] != 32 or out.dtype != torch.float32 or not out.is_contiguous() or not 0 <= int(row) < out.shape[0]:
         raise RuntimeError("dqo_eval.eval_pcd: out must be a contiguous float32 [K,32] table and row one of its rows")
-    ws = workspace_buffer
-    if ws is None:
-        key = ("pcd", _dev_index(dev), G, P)
-        ws = _workspaces.get(key)
-        if ws is None:
-            ws = _workspaces[key] = pcd_workspace(G, P, dev)
+    ws = workspace_buffer if workspace_buffer is not None else _workspace(("pcd", _dev_index(dev), G, P), _pcd_bytes(G, P), dev)
     with torch.cuda.device(dev):
         N.check(lib.dqo_eval_pcd(G, N.ptr(gt), N.ptr(gk), P, N.ptr(rec), N.ptr(rk), N.ptr(xf), len(thres), (ctypes.c_float * len(thres))(*thres),
                                  out.data_ptr(), int(row), ws.data_ptr(), ws.numel(), N.current_stream()))

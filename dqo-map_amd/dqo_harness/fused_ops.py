@@ -28,9 +28,7 @@ class _MaskedMappingLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, render, depth, depth_index, gt_color, gt_depth, render_mask, color_weight, depth_weight, add_depth_thres):
         lib = N.lib()
-        N.require_gpu(render, depth, depth_index, gt_color, gt_depth, render_mask)
-        if not render.is_cuda:
-            raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+        N.require_gpu_op(render, depth, depth_index, gt_color, gt_depth, render_mask)
         f = lambda t: t.detach().float().contiguous()
         render, depth, gt_color, gt_depth = f(render), f(depth), f(gt_color), f(gt_depth)
         depth_index = depth_index.to(torch.int32).contiguous()
@@ -63,9 +61,7 @@ class _Ssim(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img1, img2):
         lib = N.lib()
-        N.require_gpu(img1, img2)
-        if not img1.is_cuda:
-            raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+        N.require_gpu_op(img1, img2)
         a, b = img1.detach().float().contiguous(), img2.detach().float().contiguous()
         if a.dim() != 3 or a.shape[0] != 3 or a.shape != b.shape:
             raise RuntimeError(f"fused_ssim: two [3,H,W] images expected, got {tuple(a.shape)} and {tuple(b.shape)}")
@@ -108,9 +104,7 @@ class _AttachLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scaling, xyz, rotation, scaling0, xyz0, rotation0, attach_mask, attach_count):
         lib = N.lib()
-        N.require_gpu(scaling, xyz, rotation, scaling0, xyz0, rotation0, attach_mask)
-        if not xyz.is_cuda:
-            raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+        N.require_gpu_op(xyz, scaling, rotation, scaling0, xyz0, rotation0, attach_mask)
         f = lambda t: t.detach().float().contiguous()
         s, x, q, s0, x0, q0 = f(scaling), f(xyz), f(rotation), f(scaling0), f(xyz0), f(rotation0)
         P, dev = x.shape[0], x.device

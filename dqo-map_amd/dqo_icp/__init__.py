@@ -22,9 +22,7 @@ import _dqo_native as N
 
 def normal_equations(vertex0, vertex1, normal0, normal1, pose10, K, distance_threshold, normal_threshold):
     """(JtJ [6,6], JtR [6,1], valid_count 0-dim int32) of ICP.compute_residuals_jacobian + compute_jtj + compute_jtr."""
-    N.require_gpu(vertex0, vertex1, normal0, normal1)
-    if not vertex0.is_cuda:
-        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    N.require_gpu_op(vertex0, vertex1, normal0, normal1)
     dev = vertex0.device
     H, W = vertex0.shape[:2]
     v0, v1, n0, n1 = (t.float().contiguous() for t in (vertex0, vertex1, normal0, normal1))

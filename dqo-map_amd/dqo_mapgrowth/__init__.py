@@ -32,9 +32,7 @@ def knn_points_k3(p1, p2, max_dist=None, groups=None, group_box=None, int32_idx=
     groups = (g1 [Q], g2 [R]) int32 ids in [0, 64) (any other value: the point belongs to no group): a reference only counts for a
     query of the same group; group_box [64, 6] (lo xyz, hi xyz): ... and only if it lies strictly inside its group's box
     (dqo_knn3_query_grouped)."""
-    N.require_gpu(p1, p2)
-    if not (p1.is_cuda and p2.is_cuda):
-        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    N.require_gpu_op((p1, p2))
     q = p1.float().contiguous()
     r = p2.float().contiguous()
     Q, R = q.shape[0], r.shape[0]

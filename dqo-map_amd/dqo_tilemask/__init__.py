@@ -25,9 +25,7 @@ def _grid(h, w):
 
 
 def _tile_count(pixelmask):
-    N.require_gpu(pixelmask)
-    if not pixelmask.is_cuda:
-        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    N.require_gpu_op(pixelmask)
     h, w = pixelmask.shape[:2]
     m = pixelmask if pixelmask.dtype == torch.uint8 else (pixelmask != 0).to(torch.uint8)
     m = m.contiguous()
@@ -63,9 +61,7 @@ def meanpool(matrix, stride, padding_value=0):
 def color_error_tiles(render, gt):
     """color_error [H, W] = sum_c |render - gt| with the pixels whose rendered colour sums to 0 zeroed
     (mapper.py:949-956), and its 16x16 mean-pool [gy, gx] (meanpool of SLAM/utils.py:720-729), in one pass."""
-    N.require_gpu(render, gt)
-    if not render.is_cuda:
-        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    N.require_gpu_op(render, gt)
     _, h, w = render.shape
     render, gt = render.float().contiguous(), gt.float().contiguous()
     gy, gx = _grid(h, w)
@@ -96,9 +92,7 @@ def colorerror2tilemask(color_error, stride, top_ratio=0.4, _pooled=None):
 def evaluate_render_range(T_map, render=None, gt=None, global_opt=False, sample_ratio=-1):
     """Mapping.evaluate_render_range (mapper.py:930-988) over the rasteriser's outputs: returns
     (render_mask bool [H, W], tile_mask int32 [gy, gx] or None, render_ratio 0-dim tensor)."""
-    N.require_gpu(T_map)
-    if not T_map.is_cuda:
-        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    N.require_gpu_op(T_map)
     t = T_map.reshape(T_map.shape[-2], T_map.shape[-1]).float().contiguous()
     h, w = t.shape
     if global_opt and sample_ratio > 0:
@@ -170,9 +164,7 @@ def window_masks(T_map, render=None, gt=None, *, global_opt=False, sample_ratio=
     shape, contiguity, device), written in place.  Ties of the selection go to the lower tile index.  render_header: the geometry buffer
     (or header tensor) of the render the images come from; if its overflow word is set the masks keep their bytes and the ratio is NaN.
     workspace: window_masks_workspace(H, W, device), kept by the caller between calls (None: made for this call)."""
-    N.require_gpu(T_map)
-    if not T_map.is_cuda:
-        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    N.require_gpu_op(T_map)
     h, w = int(T_map.shape[-2]), int(T_map.shape[-1])
     dev = T_map.device
     gy, gx = _grid(h, w)

@@ -51,6 +51,61 @@ def test_size_queries_and_errors(native):
     assert lib.dqo_knn3(10, 1, 1, 1, None, 0, None) == -2 and b"workspace" in lib.dqo_last_error()
 
 
+def test_size_queries_return_size_t(native):
+    """By rule, not per export: ctypes' default c_int would cut a size at 2 GiB without a sound."""
+    lib = native.lib()
+    names = [n for n in native.EXPORTS if "_bytes" in n]  # (every *_bytes, and dqo_rast_binning_bytes_bucketed)
+    assert len(names) >= 24 and len([n for n in names if n.endswith("_bytes")]) == len(names) - 1
+    for n in names + ["dqo_abi_sizeof"]:
+        assert getattr(lib, n).restype is ctypes.c_size_t, n
+
+
+def test_every_export_with_arguments_has_argtypes(native):
+    lib = native.lib()
+    no_arguments = {"dqo_abi_version", "dqo_last_error", "dqo_map_loss_workspace_bytes", "dqo_icp_workspace_bytes",
+                    "dqo_track_pyramid_workspace_bytes", "dqo_track_p2p_workspace_bytes"}
+    for n in native.EXPORTS:
+        if n not in no_arguments:
+            assert getattr(lib, n).argtypes, n
+
+
+# The workspace check of every entry point that takes (ws, ws_bytes): (the text in front of " workspace too small", its size query,
+# the entry point, the arguments before and behind the pair).  Small valid sizes, 1 for every required pointer: the check fails before
+# anything is dereferenced or launched.  The texts are the literals of the entry points as they stood in dqo_capi.hip.
+WORKSPACE_CHECKS = [
+    ("knn", "dqo_knn3_workspace_bytes", (10,), "dqo_knn3", (10, 1, 1, 1), (None,)),
+    ("knn query", "dqo_knn3_query_workspace_bytes", (4, 5), "dqo_knn3_query", (4, 1, 5, 1, 1, 1), (None,)),
+    ("loss", "dqo_map_loss_workspace_bytes", (), "dqo_map_loss_fwd_bwd", (8, 8, 1, 1, 1, 1, 1, None, 1.0, 1.0, 0.1, 1, 1, 1), (None,)),
+    ("ssim", "dqo_map_ssim_workspace_bytes", (16, 12), "dqo_map_ssim_fwd_bwd", (16, 12, 1, 1, 0.2, 1, None, 0, None), (None,)),
+    ("attach-loss", "dqo_map_attach_workspace_bytes", (5,), "dqo_map_attach_loss_fwd_bwd", (5, 1, 1, 1, 1, 1, 1, 1, 2, 1, 1, 1, 1), (None,)),
+    ("eval_picture", "dqo_eval_picture_workspace_bytes", (16, 12), "dqo_eval_picture", (16, 12, 1, 1, 1, 1, 1, 0.1, 5.0, None, 1, 0), (None,)),
+    ("ms_ssim", "dqo_eval_ms_ssim_workspace_bytes", (161, 162), "dqo_eval_ms_ssim", (161, 162, 1, 1, None, 1, 0), (None,)),
+    ("nn1", "dqo_nn1_workspace_bytes", (3, 4), "dqo_nn1", (3, 1, None, 4, 1, None, None, None, 1, None), (None,)),
+    ("eval_pcd", "dqo_eval_pcd_workspace_bytes", (3, 4), "dqo_eval_pcd", (3, 1, None, 4, 1, None, None, 0, None, 1, 0), (None,)),
+    ("surfel densify", "dqo_surfel_densify_workspace_bytes", (2, 3, 2, 1), "dqo_surfel_densify",
+     (2, 1, 1, 1, None, 3, 2, 1, 1, 0, 7, 4, 1, None, None, 1, 1), (None,)),
+    ("mesh sample", "dqo_mesh_sample_workspace_bytes", (2, 5), "dqo_mesh_sample", (4, 1, 2, 1, 5, 7, 1, None, 1, 1), (None,)),
+    ("map pack", "dqo_map_pack_workspace_bytes", (4,), "dqo_map_pack_rows", (4, 1, 0, 1, 1, 1, 1, 1, None, None, None, 1, 4, 1), (None,)),
+    ("icp", "dqo_icp_workspace_bytes", (), "dqo_icp_normal_equations", (4, 6, 1, 1, 1, 1, 1, 1.0, 1.0, 2.0, 3.0, 0.1, 0.9, 1, 1, 1), (None,)),
+    ("icp", "dqo_icp_workspace_bytes", (), "dqo_icp_gauss_newton", (4, 6, 1, 1, 1, 1, 1, 1, 1.0, 0.1, 0.9, 1e-6, 1), (None,)),
+    ("track preprocess", "dqo_track_preprocess_workspace_bytes", (4, 6), "dqo_track_preprocess",
+     (4, 6, 1, 1, 0.1, 5.0, 0.5, 1, 1, 1, 1, 1, 1), (None,)),
+    ("track pyramid", "dqo_track_pyramid_workspace_bytes", (), "dqo_track_pyramid", (4, 6, 2, 1, 1, 1, 1), (None,)),
+    ("track p2p", "dqo_track_p2p_workspace_bytes", (), "dqo_track_p2p_loss", (4, 6, 1, 1, 1, 1, 0.5, None, 1, 1, None), (None,)),
+]
+
+
+@pytest.mark.parametrize("what,query,sizes,entry,head,tail", WORKSPACE_CHECKS, ids=[c[3] for c in WORKSPACE_CHECKS])
+def test_workspace_check(native, what, query, sizes, entry, head, tail):
+    lib = native.lib()
+    need = getattr(lib, query)(*sizes)
+    assert need > 0
+    # one byte short, then no workspace at all
+    for ws, ws_bytes in ((1, need - 1), (None, need)):
+        assert getattr(lib, entry)(*head, ws, ws_bytes, *tail) == -2
+        assert lib.dqo_last_error().decode() == f"{what} workspace too small ({ws_bytes} < {need})"
+
+
 def test_python_surface_matches_reference(native):
     import diff_gaussian_rasterization_depth as m
     assert m.GaussianRasterizationSettings._fields == (
