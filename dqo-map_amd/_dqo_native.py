@@ -123,7 +123,8 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_nn1_workspace_bytes", "dqo_nn1", "dqo_eval_pcd_workspace_bytes", "dqo_eval_pcd", "dqo_window_masks_workspace_bytes",
            "dqo_window_masks", "dqo_surfel_densify_workspace_bytes", "dqo_surfel_densify", "dqo_map_pack_workspace_bytes",
            "dqo_map_pack_rows", "dqo_map_unpack_rows", "dqo_mesh_sample_workspace_bytes", "dqo_mesh_sample",
-           "dqo_objmap_frame", "dqo_objmap_optimize", "dqo_objmap_mean_iou")
+           "dqo_objmap_frame", "dqo_objmap_optimize", "dqo_objmap_mean_iou", "dqo_traj_append", "dqo_track_world_maps",
+           "dqo_eval_ate_workspace_bytes", "dqo_eval_ate")
 
 _lib = None
 
@@ -237,6 +238,11 @@ def lib():
         L.dqo_objmap_frame.argtypes = [c_i32] * 3 + [c_vp] * 9 + [c_i32] + [c_vp] * 7 + [c_i32] * 3 + [c_u64] + [c_vp] * 6
         L.dqo_objmap_optimize.argtypes = [c_i32] * 2 + [c_vp] * 9 + [c_i32, c_u64, c_vp, c_vp]
         L.dqo_objmap_mean_iou.argtypes = [c_i32] * 2 + [c_vp] * 9
+        # map_traj.hip
+        L.dqo_traj_append.argtypes = [c_i32] + [c_vp] * 14 + [c_i32, c_d, c_d, c_vp]
+        L.dqo_track_world_maps.argtypes = [c_i32, c_i32] + [c_vp] * 6
+        L.dqo_eval_ate_workspace_bytes.argtypes = [c_i32]
+        L.dqo_eval_ate.argtypes = [c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]
         # icp.hip, track.hip
         L.dqo_icp_normal_equations.argtypes = [c_i32, c_i32] + [c_vp] * 5 + [c_f] * 6 + [c_vp] * 4 + [c_sz, c_vp]
         L.dqo_icp_gauss_newton.argtypes = [c_i32, c_i32] + [c_vp] * 6 + [c_f] * 4 + [c_vp] * 2 + [c_sz, c_vp]

@@ -56,6 +56,16 @@ table counts integer quanta of area instead of float sums (no summation order ca
 
 What is NOT here: writing `pcd_densify.ply` (open3d's layout) is not built; the unused bounding box of eval.py:237-239 is not formed.
 
+Tracking evaluation — Tracker.eval_total_ate, SLAM/multiprocess/tracker.py:341-346, 426-430: the absolute trajectory error after Horn's
+alignment (eval_ate, SLAM/utils.py:486-532) for EVERY prefix of the trajectory, which the reference forms with one numpy alignment per
+prefix and a Python loop over its points:
+
+    eval_ate(pose_es, pose_gt)                              ->  float64 [N] on the device, centimetres
+    eval_ate_dict(curve)                                    ->  {"ate": curve[-1]} (the ONE host read)
+
+One launch (dqo_eval_ate, csrc/map_traj.hip), one block per prefix, sums added in a fixed order.  dqo_icp.Trajectory keeps the two pose
+stacks on the device and calls it (`Trajectory.ate()`).  The ATE figure (matplotlib) and scripts/eval_ate.py are not built.
+
 GPU only: there is no CPU path.
 """
 import ctypes
@@ -462,3 +472,57 @@ def eval_pcd_dict(row_tensor, dist_thres=(0.03,)):
             results["{} (< {})".format(name, th)] = v[off + 3 * t]
     results["chamfer"] = v[2]
     return results
+
+
+def _positions(t, name):
+    """(tensor kept alive, pointer, doubles between points, doubles between components, N) of a float64 [N,3] or [N,4,4] GPU tensor:
+    a view's strides are used as they are — the translation column of a pose stack is read in place."""
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+    if t.dtype != torch.float64:
+        raise RuntimeError(f"dqo_eval.eval_ate: {name} must be float64, got {t.dtype}")
+    if t.dim() == 3 and tuple(t.shape[1:]) == (4, 4):
+        t = t[:, :3, 3]
+    if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+        raise RuntimeError(f"dqo_eval.eval_ate: {name} must be [N,3] positions or [N,4,4] poses, got {tuple(t.shape)}")
+    if t.stride(0) < 0 or t.stride(1) < 0:
+        t = t.contiguous()
+    return t, t.data_ptr(), int(t.stride(0)), int(t.stride(1)), int(t.shape[0])
+
+
+def eval_ate(pose_es, pose_gt, out=None, fit=None, workspace_buffer=None):
+    """The ATE curve of Tracker.eval_total_ate (SLAM/multiprocess/tracker.py:341-346) on the device, in one launch (dqo_eval_ate,
+    csrc/map_traj.hip): returns float64 [N] with out[i-1] = Tracker.eval_ate(pose_es, pose_gt, i) (:426-430) — the RMSE in centimetres
+    after Horn's alignment of the first i ground-truth positions onto the first i estimated ones (eval_ate, SLAM/utils.py:486-532).
+
+    pose_es, pose_gt: float64 GPU tensors, [N,3] positions or [N,4,4] poses (their translation column is read in place).  out: a
+    contiguous float64 [N] tensor to fill; fit: a contiguous float64 [12] tensor that receives rot (row-major) and trans of the full
+    trajectory's alignment.  Nothing is read back and the call does not synchronise; eval_ate_dict does the single host read.  The
+    reference runs one alignment per prefix with a Python loop over its points.  A curve is bitwise reproducible.
+
+    workspace_buffer: a uint8 tensor of at least dqo_eval_ate_workspace_bytes(N) bytes the caller keeps (default: one per device and N,
+    kept by this module — calls that share it must be on one stream); on return it holds every prefix's alignment, [N,12] float64."""
+    es, es_p, es_s, es_c, n = _positions(pose_es, "pose_es")
+    gt, gt_p, gt_s, gt_c, n_gt = _positions(pose_gt, "pose_gt")
+    if n != n_gt or es.device != gt.device:
+        raise RuntimeError(f"dqo_eval.eval_ate: {n} estimated and {n_gt} ground-truth poses (or different devices)")
+    lib, dev = N.lib(), es.device
+    if out is None:
+        out = torch.empty((n,), dtype=torch.float64, device=dev)
+    if out.dtype != torch.float64 or tuple(out.shape) != (n,) or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError("dqo_eval.eval_ate: out must be a contiguous float64 [N] tensor on the poses' device")
+    if fit is not None and (fit.dtype != torch.float64 or fit.numel() != 12 or not fit.is_contiguous() or fit.device != dev):
+        raise RuntimeError("dqo_eval.eval_ate: fit must be a contiguous float64 tensor of 12 elements on the poses' device")
+    need = lib.dqo_eval_ate_workspace_bytes(n)
+    if need == 0:
+        raise RuntimeError(f"dqo_eval.eval_ate: bad point count {n}")
+    ws = workspace_buffer if workspace_buffer is not None else _workspace(("ate", _dev_index(dev), n), need, dev)
+    with torch.cuda.device(dev):
+        # model = ground truth, data = estimate: Tracker.eval_ate calls eval_ate(pose_gt, pose_es) (:429)
+        N.check(lib.dqo_eval_ate(n, gt_p, gt_s, gt_c, es_p, es_s, es_c, out.data_ptr(), N.ptr(fit), ws.data_ptr(), ws.numel(), N.current_stream()))
+    return out
+
+
+def eval_ate_dict(curve):
+    """{"ate": the full trajectory's ATE in cm} — what save_traj prints (tracker.py:406-407) — from a device curve: ONE host read."""
+    return {"ate": float(curve.detach().reshape(-1)[-1].cpu())}

@@ -10,6 +10,10 @@ The rest of the tracker's per-frame work runs on the device as well (csrc/track.
 `preprocess_frame` is the geometry half of Tracker.map_preprocess (SLAM/multiprocess/tracker.py:118-165), and `IcpTracker` mirrors
 SLAM/icp.py:361-458 (pyramids, model-depth fill, the coarse-to-fine loop, the failure test) as stream-ordered launches whose only
 host synchronisation is predict_pose's read of the result.
+
+`Trajectory` takes the pose from there (csrc/map_traj.hip): the world pose, the frame's camera tensors, the world-frame vertex / normal
+maps, the keyframe test and the ATE curve (Tracker.tracking, SLAM/multiprocess/tracker.py:307-339; check_keyframe, mapper.py:734-773;
+eval_total_ate, tracker.py:341-346) from predict_pose_async's device tensors, with no host read per frame.
 """
 import ctypes
 import math
@@ -328,3 +332,155 @@ class IcpTracker:
         if self.verbose:
             print(host[16], host[17])
         return host[:16].reshape(4, 4).copy(), bool(host[18] != 0)
+
+
+def world_maps(vertex_c, normal_c, c2w, out=None):
+    """transform_map of the frame's two maps (SLAM/multiprocess/tracker.py:332-337, SLAM/utils.py:56-63) in one launch
+    (dqo_track_world_maps, csrc/map_traj.hip): (vertex_map_w, normal_map_w) = (R v + t, R n) with the float32 c2w [4,4] on the device.
+    Maps: contiguous float32 [H,W,3] GPU tensors; normal_c may be None (then normal_map_w is None).  out: (vertex_w, normal_w) to write
+    into — an output may be its input; default: new tensors.  A zero vertex maps to t, as the reference's does."""
+    N.require_gpu_op((vertex_c, c2w), normal_c)
+    maps = [vertex_c, normal_c] + list(out if out is not None else ())
+    for t in maps:
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 3 and t.shape == vertex_c.shape and t.shape[-1] == 3):
+            raise RuntimeError("world_maps: contiguous float32 [H,W,3] maps of one size expected")
+    if not (c2w.dtype == torch.float32 and c2w.is_contiguous() and c2w.numel() == 16):
+        raise RuntimeError("world_maps: c2w must be a contiguous float32 [4,4] tensor")
+    vw, nw = out if out is not None else (torch.empty_like(vertex_c), None if normal_c is None else torch.empty_like(normal_c))
+    if (normal_c is None) != (nw is None):
+        raise RuntimeError("world_maps: the normal map and its output come together")
+    H, W = vertex_c.shape[:2]
+    with torch.cuda.device(vertex_c.device):
+        N.check(N.lib().dqo_track_world_maps(H, W, vertex_c.data_ptr(), None if normal_c is None else normal_c.data_ptr(), c2w.data_ptr(),
+                                             vw.data_ptr(), None if nw is None else nw.data_ptr(), N.current_stream()))
+    return vw, nw
+
+
+class Trajectory:
+    """The trajectory on the device: what Tracker.tracking does between the tracker's answer and the mapper's input
+    (SLAM/multiprocess/tracker.py:307-339), the mapper's keyframe test (SLAM/multiprocess/mapper.py:734-773) and the ATE curve
+    (tracker.py:341-346), without a host read on the per-frame path:
+
+        pose, ok, _, _ = tracker.predict_pose_async(frame)
+        traj.append(pose)                                   # pose_es[-1] @ pose_t1_t0, frame.updatePose, check_keyframe: one launch
+        vw, nw = traj.world_maps(frame_map["vertex_map_c"], frame_map["normal_map_c"])
+        mapper.set_frame(k, settings=traj.settings(template))
+
+    It owns `capacity` rows of world poses (float64, c2w), ground-truth poses, keyframe flags and metrics, and the current frame's camera
+    tensors; the row index lives on the device and the launch advances it, so a captured append fills consecutive rows when replayed.
+    Arguments in the reference's spellings: projection — the camera's projection_matrix (float32 [4,4], transposed as the reference
+    keeps it; without one `projmatrix` is not formed); gaussian_update_frame — check_keyframe runs on rows i == 0 and
+    (i + 1) % gaussian_update_frame == 0 (0: never); keyframe_theta_thes (degrees) / keyframe_trans_thes (metres): base.yaml's values.
+    init_pose: row 0 in relative mode (identity by default, tracker.py:318).
+
+    Two departures from the reference: `campos` is the CURRENT pose's translation (Camera.update never refreshes camera_center, so the
+    reference keeps the centre of the pose the camera was constructed with); and the first relative append ignores its argument and
+    stores init_pose, as the reference's first frame stores np.eye(4) without asking the tracker.  `projmatrix` is the double product of
+    the double w2c (transposed) and the projection, rounded once: within half a float32 ulp of the exact product, where the reference's
+    float32 bmm of the rounded world_view_transform (cameras.py:179-183) is up to 1.25 ulp from it.
+
+    Not here: the text trajectory files (poses.txt, TUM lines), the figures, the ORB back end, and the keyframes' images
+    (keyframe_list / keymap_list stay with the caller)."""
+
+    def __init__(self, capacity, device, projection=None, gaussian_update_frame=0, keyframe_theta_thes=30.0, keyframe_trans_thes=0.3,
+                 init_pose=None):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+        if capacity < 1:
+            raise ValueError("Trajectory: capacity must be at least 1")
+        self.capacity, self.device = int(capacity), device
+        self.gaussian_update_frame = int(gaussian_update_frame)
+        self.keyframe_theta_thes, self.keyframe_trans_thes = float(keyframe_theta_thes), float(keyframe_trans_thes)
+        f64, f32 = dict(dtype=torch.float64, device=device), dict(dtype=torch.float32, device=device)
+        self._pose, self._pose_gt = torch.zeros((capacity, 4, 4), **f64), torch.zeros((capacity, 4, 4), **f64)
+        self.flags = torch.zeros((capacity,), dtype=torch.int32, device=device)
+        self.kf_metric = torch.zeros((capacity, 2), **f64)
+        self.header = torch.tensor([0, -1, 0, 0], dtype=torch.int32, device=device)  # count, last keyframe row, overflow, unused
+        self.projection = None if projection is None else projection.detach().to(**f32).reshape(4, 4).contiguous()
+        self.init_pose = None if init_pose is None else torch.as_tensor(init_pose).detach().to(**f64).reshape(4, 4).contiguous()
+        self.c2w, self.viewmatrix, self.projmatrix = torch.eye(4, **f32), torch.eye(4, **f32), torch.zeros((4, 4), **f32)
+        self.campos = torch.zeros((3,), **f32)
+        self._n = 0
+        self._ate_ws = None
+        self._held = ()  # the last append's converted operands, alive while its launch (or a graph that captured it) may read them
+
+    def __len__(self):
+        """The host's mirror of the row count (the device's is header[0]): every append() counts one, up to the capacity.  Replays of a
+        graph that captured an append advance the device count only: tell the mirror with advance() (the captured call itself, which
+        launches nothing, has counted one: the first replay's)."""
+        return self._n
+
+    def advance(self, n=1):
+        self._n = min(self.capacity, self._n + int(n))
+
+    def append(self, pose, relative=True, pose_gt=None):
+        """One frame: pose — the tracker's pose_t1_t0 (float32 [4,4] GPU tensor; relative=True: pose[i] = pose[i-1] @ pose) or a world
+        pose (relative=False: use_gt_pose, an ORB-refined pose); pose_gt — the frame's ground-truth pose, stored beside it.  One launch
+        (dqo_traj_append), nothing read back; a float32 contiguous relative pose and float64 contiguous world poses are used where they
+        are, anything else is converted on the device first.  Appending to a full store sets the overflow word and writes nothing."""
+        N.require_gpu_op(pose, pose_gt)
+        if pose.numel() != 16 or (pose_gt is not None and pose_gt.numel() != 16):
+            raise RuntimeError("Trajectory.append: [4,4] poses expected")
+        p = pose.detach().to(torch.float32 if relative else torch.float64).contiguous()
+        g = None if pose_gt is None else pose_gt.detach().to(torch.float64).contiguous()
+        self._held = (p, g)
+        has_proj = self.projection is not None
+        with torch.cuda.device(self.device):
+            N.check(N.lib().dqo_traj_append(self.capacity, self._pose.data_ptr(), self._pose_gt.data_ptr(), self.flags.data_ptr(),
+                                            self.kf_metric.data_ptr(), self.header.data_ptr(), p.data_ptr() if relative else None,
+                                            None if relative else p.data_ptr(), N.ptr(self.init_pose), N.ptr(g), N.ptr(self.projection),
+                                            self.c2w.data_ptr(), self.viewmatrix.data_ptr(), self.projmatrix.data_ptr() if has_proj else None,
+                                            self.campos.data_ptr(), self.gaussian_update_frame, self.keyframe_theta_thes,
+                                            self.keyframe_trans_thes, N.current_stream()))
+        self.advance()
+        return self
+
+    def poses(self):
+        """[len, 4, 4] float64 view of the world poses (pose_es)."""
+        return self._pose[:self._n]
+
+    def poses_gt(self):
+        return self._pose_gt[:self._n]
+
+    def settings(self, template):
+        """`template` (a GaussianRasterizationSettings) with the current frame's camera tensors: FusedMapper.set_frame(k, settings=...)
+        copies them device to device."""
+        if self.projection is None:
+            raise RuntimeError("Trajectory.settings: the trajectory was made without a projection, so there is no projmatrix")
+        return template._replace(viewmatrix=self.viewmatrix, projmatrix=self.projmatrix, campos=self.campos)
+
+    def world_maps(self, vertex_c, normal_c, out=None):
+        """(vertex_map_w, normal_map_w) of the current frame (tracker.py:332-337): see world_maps()."""
+        return world_maps(vertex_c, normal_c, self.c2w, out)
+
+    def keyframe(self):
+        """The device flag word [1] int32 of the last row: bit 0 tested, bit 1 is a keyframe (check_keyframe's return value), bit 2 in
+        the keyframe list.  Nothing is read."""
+        if self._n < 1:
+            raise RuntimeError("Trajectory.keyframe: no frame yet")
+        return self.flags[self._n - 1:self._n]
+
+    def is_keyframe(self):
+        """check_keyframe's return value for the last row: the one 4-byte read, where the caller has to branch."""
+        return bool(int(self.keyframe().cpu()) & 2)
+
+    def ate(self, out=None):
+        """The ATE curve so far, float64 [len] on the device (dqo_eval.eval_ate of the stored poses against the stored ground truth)."""
+        import dqo_eval
+        if self._ate_ws is None:  # sized for the capacity once: the curve grows with every frame
+            self._ate_ws = torch.empty((N.lib().dqo_eval_ate_workspace_bytes(self.capacity),), dtype=torch.uint8, device=self.device)
+        return dqo_eval.eval_ate(self.poses(), self.poses_gt(), out=out, workspace_buffer=self._ate_ws)
+
+    def overflowed(self):
+        """True when an append found the store full (a host read)."""
+        return bool(int(self.header[2].cpu()))
+
+    def save(self, save_path):
+        """pose_es.npy / pose_gt.npy under save_path/save_traj as Tracker.save_traj writes them (tracker.py:397, 403-409): the only host
+        copy of the trajectory."""
+        import os
+        d = os.path.join(save_path, "save_traj")
+        os.makedirs(d, exist_ok=True)
+        np.save(os.path.join(d, "pose_gt.npy"), self.poses_gt().cpu().numpy())
+        np.save(os.path.join(d, "pose_es.npy"), self.poses().cpu().numpy())

@@ -944,6 +944,67 @@ int dqo_track_p2p_loss(int32_t H, int32_t W, const float* vertex0, const float* 
                        float fail_threshold, const int32_t* valid_count, float* loss, int32_t* success, float* valid_ratio, void* workspace,
                        size_t workspace_bytes, void* hipStream);
 
+/* dqo_traj_append / dqo_track_world_maps / dqo_eval_ate (ABI 5, symbols-only addition) — the trajectory on the device: the stretch of
+ * Tracker.tracking between the tracker's answer and the mapper's input (SLAM/multiprocess/tracker.py:307-339), the mapper's keyframe
+ * test and the tracking metric, nothing read back.  csrc/map_traj.hip lists every statement in order; tests/traj_oracle.py restates them.
+ *
+ * dqo_traj_append — one launch per frame.  The trajectory is caller-owned device memory of capacity cap rows:
+ *     pose [cap,16] double   world poses c2w, row-major          pose_gt [cap,16] double   may be NULL when gt is never given
+ *     flags [cap] int32      DQO_TRAJ_* bits                      kf_metric [cap,2] double  (theta in degrees, l2) of a tested row, else 0
+ *     header [DQO_TRAJ_HEADER_WORDS] int32: the row count, the row of the last keyframe (-1: none yet), the overflow word; the caller
+ *       sets (0, -1, 0, 0) once.  The launch reads the row index i from the header and advances it itself, so a captured graph appends
+ *       correctly.  A full store (i >= cap) writes nothing but overflow = 1.
+ *   World pose (tracker.py:312-327): exactly one of rel (float32 [4,4], the tracker's pose_t1_t0: pose[i] = pose[i-1] @ double(rel) in
+ *     double, :324; row 0 takes init_pose, identity when NULL, :318) and abs_pose (double [4,4]: pose[i] = abs_pose — use_gt_pose :313, an
+ *     ORB-refined pose :322).  gt (double [4,4], may be NULL) is copied to pose_gt[i] (:308).
+ *   The frame's camera — Camera.updatePose / update (scene/cameras.py:165-183) — into float32 device buffers, NULL skips one:
+ *     c2w [16] = pose[i] rounded once; viewmatrix [16] = the double inverse of the affine pose (by the cofactors of its 3x3 block, as
+ *     np.linalg.inv :166, never the transpose) transposed and rounded once (world_view_transform :174-178); projmatrix [16] = the double
+ *     w2c transposed @ double(projection), rounded once (full_proj_transform :179-183, which forms it in float32 from the rounded
+ *     viewmatrix and lands up to 1.25 ulp from this; projection: device float32 [4,4], transposed as the reference keeps it);
+ *     campos [3] = pose[i]'s translation (Camera.update never refreshes camera_center: the reference keeps the constructor's).
+ *   Keyframe test — check_keyframe (SLAM/multiprocess/mapper.py:734-773; rot_compare / trans_compare SLAM/utils.py:42-54) on the rows
+ *     i == 0 || (i + 1) % gaussian_update_frame == 0 (0: never): the first tested row enters the keyframe list and reports "not a
+ *     keyframe" (:736-748); any other is a keyframe iff theta > theta_thres || l2 > trans_thres against the last keyframe row (cos not
+ *     clamped: NaN compares false, as in numpy) and then becomes the last keyframe.
+ * DQO_ERR_INVALID_ARG before the launch: cap < 1, a NULL store, both or neither of rel / abs_pose, gt without pose_gt, projmatrix without
+ *   projection, gaussian_update_frame < 0. */
+enum { DQO_TRAJ_HEADER_COUNT = 0, DQO_TRAJ_HEADER_LAST_KEYFRAME = 1, DQO_TRAJ_HEADER_OVERFLOW = 2, DQO_TRAJ_HEADER_WORDS = 4 };
+enum {
+    DQO_TRAJ_TESTED = 1,   /* check_keyframe ran for the row */
+    DQO_TRAJ_KEYFRAME = 2, /* its return value */
+    DQO_TRAJ_LISTED = 4    /* the row is in the keyframe list (row 0 is, and reports "not a keyframe") */
+};
+int dqo_traj_append(int32_t cap, double* pose, double* pose_gt, int32_t* flags, double* kf_metric, int32_t* header, const float* rel,
+                    const double* abs_pose, const double* init_pose, const double* gt, const float* projection, float* c2w,
+                    float* viewmatrix, float* projmatrix, float* campos, int32_t gaussian_update_frame, double theta_thres,
+                    double trans_thres, void* hipStream);
+
+/* transform_map of the frame's two maps (tracker.py:332-337, SLAM/utils.py:56-63) in one pixel launch: vertex_w = ((r0 x + r1 y) + r2 z) + t
+ * per component with c2w's rows (device float32 [16]), normal_w the same with the rotation only (get_rot, utils.py:30-33); float32, one
+ * rounding per operation.  Maps [H,W,3]; a zero vertex maps to t, as the reference's does.  normal_c / normal_w may both be NULL.  An
+ * output may be its input.  Each map is read and written once, 16 bytes per lane when all four addresses are 16-byte aligned.
+ * DQO_ERR_INVALID_ARG before the launch: H * W < 1 or too large, a NULL vertex map or c2w, one normal pointer without the other. */
+int dqo_track_world_maps(int32_t H, int32_t W, const float* vertex_c, const float* normal_c, const float* c2w, float* vertex_w,
+                         float* normal_w, void* hipStream);
+
+/* The ATE curve of Tracker.eval_total_ate (tracker.py:341-346, 426-430; eval_ate / align SLAM/utils.py:486-532) in one launch:
+ * ate[i-1] = eval_ate over the first i points, in centimetres, for i = 1..N.  Argument order as Tracker.eval_ate calls it (:429):
+ * model = ground truth, data = estimate.  A stream is (pointer, doubles between points, doubles between a point's components):
+ * (p, 3, 1) for a packed [N,3], (poses + 3, 16, 4) for the translation column of a [N,4,4] pose stack.
+ * One block per prefix, three passes in double — the means; the 3x3 sum of outer products of the zero-centred points (:502-507); the sum
+ * of squared lengths of R (m - mean m) - (d - mean d), then sqrt(sum / i) * 100 (:515-531) — with R from Horn's quaternion form (the
+ * eigenvector of the largest eigenvalue of the symmetric 4x4, cyclic Jacobi): always a proper rotation, which is what the SVD with
+ * S[2,2] = -1 of :508-512 yields.  Sums are added in a fixed order: a curve is bitwise reproducible.
+ * fit [12] double, may be NULL: rot (row-major) and trans of the full trajectory's alignment (:512-513).
+ * workspace: dqo_eval_ate_workspace_bytes(N) bytes (0 for a bad N), ANY contents; on return it holds the alignment of every prefix,
+ *   [N,12] double.  DQO_ERR_INVALID_ARG before the launch: N outside [1, DQO_ATE_MAX_POINTS], a NULL stream of positions or ate, a
+ *   negative stride.  DQO_ERR_WORKSPACE: the workspace is NULL or too small. */
+#define DQO_ATE_MAX_POINTS (1 << 24)
+size_t dqo_eval_ate_workspace_bytes(int32_t N);
+int dqo_eval_ate(int32_t N, const double* model, int64_t model_stride, int64_t model_cstride, const double* data, int64_t data_stride,
+                 int64_t data_cstride, double* ate, double* fit, void* workspace, size_t workspace_bytes, void* hipStream);
+
 #define DQO_TICKET_WORDS (16 + 16 * 64) /* int32 words behind DqoAdamStep.block_ticket */
 typedef struct DqoAdamStep {
     int32_t P, M;      /* Gaussians, SH coefficients per Gaussian (f_dc = coefficient 0, f_rest = the others) */
