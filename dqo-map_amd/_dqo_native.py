@@ -124,7 +124,8 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_window_masks", "dqo_surfel_densify_workspace_bytes", "dqo_surfel_densify", "dqo_map_pack_workspace_bytes",
            "dqo_map_pack_rows", "dqo_map_unpack_rows", "dqo_mesh_sample_workspace_bytes", "dqo_mesh_sample",
            "dqo_objmap_frame", "dqo_objmap_optimize", "dqo_objmap_mean_iou", "dqo_traj_append", "dqo_track_world_maps",
-           "dqo_eval_ate_workspace_bytes", "dqo_eval_ate")
+           "dqo_eval_ate_workspace_bytes", "dqo_eval_ate", "dqo_prune_workspace_bytes", "dqo_prune_cameras", "dqo_prune_touch",
+           "dqo_prune_rows")
 
 _lib = None
 
@@ -243,6 +244,11 @@ def lib():
         L.dqo_track_world_maps.argtypes = [c_i32, c_i32] + [c_vp] * 6
         L.dqo_eval_ate_workspace_bytes.argtypes = [c_i32]
         L.dqo_eval_ate.argtypes = [c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]
+        # map_prune.hip
+        L.dqo_prune_workspace_bytes.argtypes = [c_i32]
+        L.dqo_prune_cameras.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_d, c_d, c_vp, c_vp, c_vp, c_vp]
+        L.dqo_prune_touch.argtypes = [c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]
+        L.dqo_prune_rows.argtypes = [c_i32] + [c_vp] * 12 + [c_i32, c_i32, c_vp, c_sz, c_vp, c_vp]
         # icp.hip, track.hip
         L.dqo_icp_normal_equations.argtypes = [c_i32, c_i32] + [c_vp] * 5 + [c_f] * 6 + [c_vp] * 4 + [c_sz, c_vp]
         L.dqo_icp_gauss_newton.argtypes = [c_i32, c_i32] + [c_vp] * 6 + [c_f] * 4 + [c_vp] * 2 + [c_sz, c_vp]

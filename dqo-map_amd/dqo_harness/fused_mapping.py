@@ -129,7 +129,7 @@ class _SideJob:
 #   freed  an in-place growth step writes `spare` into the rows it frees: what makes the row a spare row for the kernels
 #   live   the value of a row a Gaussian moves into, where the growth step computes none
 _RowBuffer = collections.namedtuple("_RowBuffer", "name group spare freed live src of shape", defaults=(None, False, 0, None, None, None))
-_LIFECYCLE_ROWS = ("stable", "add_tick", "depth_error_counter", "color_error_counter")
+_LIFECYCLE_ROWS = ("stable", "add_tick", "depth_error_counter", "color_error_counter", "frame_id")
 _ROW_BUFFERS = (
     _RowBuffer("xyz", "param", "park", freed=True), _RowBuffer("shs", "param", 0.0), _RowBuffer("opacity_raw", "param", -10.0, freed=True),
     _RowBuffer("scaling_raw", "param", -10.0, freed=True), _RowBuffer("rotation_raw", "param", "unit_q"),
@@ -144,6 +144,8 @@ _ROW_BUFFERS = (
     # (SLAM/gaussian_pointcloud.py:43-46)
     _RowBuffer("stable", "meta", 0, freed=True), _RowBuffer("add_tick", "meta", 0, freed=True),
     _RowBuffer("depth_error_counter", "meta", 0, freed=True), _RowBuffer("color_error_counter", "meta", 0, freed=True),
+    # track_lifecycle(): the frame a row was added at (GaussianPointCloud._frame_ids, SLAM/gaussian_pointcloud.py:52): prune_floaters()' window
+    _RowBuffer("frame_id", "meta", 0, freed=True),
     _RowBuffer("opacity", "sized", shape=lambda P: (P, 1)), _RowBuffer("scales", "sized", shape=lambda P: (P, 3)),
     _RowBuffer("rotations", "sized", shape=lambda P: (P, 4)),
     # (one partial sum per block of 256 Gaussians from dqo_map_adam_step, per wave of 64 from dqo_rast_backward_adam)
@@ -242,10 +244,11 @@ class FusedMapper:
         self.object_cell = None  # per-object growth decisions: cell size of dqo_mapgrowth.object_offsets (None = its 16 m default)
         self.per_object_loss = False
         self.alive = None  # reserve(): uint8 [P], 0 = a spare row (parked behind the camera, no Gaussian of the map)
-        self.stable = self.add_tick = self.depth_error_counter = self.color_error_counter = None  # track_lifecycle()
+        self.stable = self.add_tick = self.depth_error_counter = self.color_error_counter = self.frame_id = None  # track_lifecycle()
         self._n_spare_stale = False  # maintain() freed rows on the device since _n_spare was read
         self._lifecycle = {}  # maintain(): lifecycle_step's vote words and workspace ("_lifecycle"), made anew when P changes
         self._maintain_ctx = None  # maintain(): the persistent buffers of its render (_maintain_render)
+        self._prune_ctx = None  # prune_floaters(): its camera tables, workspace and stats, made anew when P changes
         self._eval_tables, self._eval_ws = {}, None  # evaluate(): its [K,8] table per K, and dqo_eval's workspace
         self._eval_ms_ws = None  # evaluate_ms_ssim(): dqo_eval.ms_ssim's workspace
         self._checkpoint = {}  # pack_rows() / save_model(): workspace, header, table and pinned staging buffer, made anew when P changes
@@ -533,7 +536,7 @@ class FusedMapper:
                 make = torch.empty if b.spare is None else torch.zeros
                 setattr(self, b.name, make(b.shape(self.P), dtype=torch.float32, device=self.device))
         self._attach_n, self._act_valid = 0, False
-        self._lifecycle, self._maintain_ctx = {}, None
+        self._lifecycle, self._maintain_ctx, self._prune_ctx = {}, None, None
         self._window_flags = None
         self._checkpoint = {}
         self._drop_graphs()
@@ -574,11 +577,14 @@ class FusedMapper:
 
     # ------------------------------------------------------------------ map maintenance (csrc/map_lifecycle.hip) ----------
     @torch.no_grad()
-    def track_lifecycle(self, stable_mask=None, tick=0):
+    def track_lifecycle(self, stable_mask=None, tick=0, frame_id=None):
         """Start keeping what the reference keeps per Gaussian for its map maintenance: which cloud the row belongs to (`stable` uint8,
         1 = stable_pointcloud; stable_mask bool [P] or None = the whole map is unstable), `add_tick` (int32, `tick` for every Gaussian
-        of the map now) and the two strike counters of error_gaussians_remove (int32, zero).  Spare rows hold 0 in all four.  From here on
-        reserve() and grow() carry them, maintain() rewrites them.  A mapper that never calls this behaves as before."""
+        of the map now) and the two strike counters of error_gaussians_remove (int32, zero), and `frame_id` (int32, the frame a row was added at:
+        GaussianPointCloud._frame_ids, SLAM/gaussian_pointcloud.py:52; `frame_id` for every Gaussian of the map now, None = `tick`).  Spare
+        rows hold 0 in all five.  From here on reserve() and grow() carry them, maintain() rewrites the first four and leaves frame_id to
+        its row (a row it frees keeps a stale one: nothing reads it while alive == 0, and grow() overwrites it), prune_floaters() reads
+        frame_id.  A mapper that never calls this behaves as before."""
         dev, P = self.device, self.P
         live = torch.ones((P,), dtype=torch.bool, device=dev) if self.alive is None else self.alive.bool()
         stable = torch.zeros((P,), dtype=torch.bool, device=dev) if stable_mask is None else stable_mask.to(dev).bool().reshape(-1)
@@ -586,6 +592,7 @@ class FusedMapper:
             raise RuntimeError("FusedMapper.track_lifecycle: stable_mask must have one entry per row")
         self.stable = (stable & live).to(torch.uint8)
         self.add_tick = live.to(torch.int32) * int(tick)
+        self.frame_id = live.to(torch.int32) * int(tick if frame_id is None else frame_id)
         self.depth_error_counter = torch.zeros((P,), dtype=torch.int32, device=dev)
         self.color_error_counter = torch.zeros((P,), dtype=torch.int32, device=dev)
         self._lifecycle = {}
@@ -603,10 +610,11 @@ class FusedMapper:
     # configs/base.yaml:51-52, 59-60 and the `delete_thresh = 10` of mapper.py:1092
     MAINTAIN_DEFAULTS = dict(stable_confidence_thres=500.0, unstable_time_window=200, add_color_thres=0.1, add_depth_thres=None, delete_thresh=10)
 
-    def _maintain_render(self, st, row_flags=None):
+    def _maintain_render(self, st, row_flags=None, tile_mask=None):
         """The whole map (both clouds: no row flags, no object gate; spare rows are parked and transparent) rendered at camera `st` through
         the C ABI into persistent buffers: the op's nine outputs c["out"] (0 colour, 1 depth, 2 colour hit index, 3 depth hit index).
         row_flags (refresh_window): DqoRastInputs.row_flags, uint8 [P] — its DQO_ROW_HIDDEN rows are not rendered; None: every row.
+        tile_mask (prune_floaters): int32 [gy,gx], checked by the caller; None: every tile.
         The first call measures the frame (prepare, one header read, render) and sizes the instance capacity at 1.5 x its candidate
         pairs + 4096; later calls are ONE dqo_rast_forward call on those buffers — no header copy, no event, no allocation."""
         lib, dev, P, M = N.lib(), self.device, self.P, self.M
@@ -623,8 +631,8 @@ class FusedMapper:
             c = dict(key=(P, H, W), out=out, outputs=outputs, geom=torch.empty((lib.dqo_rast_geom_bytes(P, W, H),), **u8),
                      img=torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8))
         params = dgr._params(st, P, M)
-        inputs = dgr._inputs(st, self.xyz, self.shs, self._empty, self.opacity, self.scales, self.rotations, self._empty, self.tile_mask,
-                             row_flags=row_flags)
+        inputs = dgr._inputs(st, self.xyz, self.shs, self._empty, self.opacity, self.scales, self.rotations, self._empty,
+                             self.tile_mask if tile_mask is None else tile_mask, row_flags=row_flags)
         cctx = N.DqoRastCtx(geom=c["geom"].data_ptr(), geom_bytes=c["geom"].numel(), binning=None, binning_bytes=0,
                             image=c["img"].data_ptr(), image_bytes=c["img"].numel(), inst_capacity=0)
         if first:
@@ -697,6 +705,84 @@ class FusedMapper:
         self._act_valid = False  # deleted rows' raw parameters changed
         self.activate()  # (a captured iteration starts from the activations of the current parameters)
         return stats
+
+    # ------------------------------------------------------------------ floater pruning (csrc/map_prune.hip) -------------
+    @torch.no_grad()
+    def prune_floaters(self, depth_map, window, *, projection, settings=None, tile_mask=None, theta_deg=3.0, centre="reference"):
+        """Mapping.to_purne with create_virtual_cameras (SLAM/multiprocess/mapper.py:424-529), the reference's floater elimination, on this
+        mapper's map: the keyframe's camera is turned by +-theta_deg about two axes around the point it looks at (dqo_prune_cameras), the
+        whole map (both clouds, no row flags; spare rows are parked) is rendered from the four virtual cameras, and every Gaussian with
+        lo < frame_id <= hi that none of the four views touched (n_touched == 0) is deleted.  depth_map: the keyframe's depth, float32 GPU
+        tensor of H*W elements (frame_map["depth_map"]); window = (lo, hi): (keyframe_list[-2].uid, keyframe_list[-1].uid], or
+        (uid - 1, uid] with one keyframe (:510-515); projection: the camera's float32 [4,4] GPU tensor, transposed as the reference keeps it
+        (Trajectory's argument); settings: the keyframe's camera (default: the mapper's); tile_mask: int32 [gy,gx] GPU tensor, what
+        evaluate_render_range(frame) returned for the frame (:470), applied to all four views as the reference does (None: all tiles).
+        centre="reference": the centre depth is read at row int(cx), column int(cy) — the reference's transposed `cx, cy = int(frame.cy),
+        int(frame.cx)` then `depth_map[cy, cx]` (:471-473) — and a pixel outside the image is a ValueError before any launch (the reference
+        raises IndexError there); centre="principal": row int(cy), column int(cx), the intent.  The virtual views take the frame's own
+        campos, as the reference's do (Camera.update never refreshes camera_center).
+        One camera launch, four x (_maintain_render, dqo_prune_touch), dqo_prune_rows and one activation pass, everything in place:
+        deleted rows become spare rows, P stays, captured graphs stay valid.  The FIRST call for a (P, H, W) sizes the render's context
+        from one header read exactly as maintain() does (they share it); every later call reads nothing back and does not synchronise.
+        A view that outgrows that context touches nothing valid: then the call deletes nothing and reports skipped = 1
+        (prune_overflowed() tells, where a synchronisation is affordable).  The spare-row count is read again by the next grow().  Returns
+        the int32 [8] device tensor of counts (dqo_mapgrowth.PRUNE_STATS)."""
+        import dqo_mapgrowth as mg
+        self._require_lifecycle("prune_floaters")
+        if self.attach_count_reducer is not None:
+            raise NotImplementedError("FusedMapper.prune_floaters: a sharded mapper would need the touch counts of the whole map's render (DESIGN.md §6)")
+        if centre not in ("reference", "principal"):
+            raise ValueError("FusedMapper.prune_floaters: centre is 'reference' or 'principal'")
+        dev = self.device
+        st = self.settings if settings is None else _normalised_settings(settings, dev)
+        H, W = int(self.settings.image_height), int(self.settings.image_width)
+        if (int(st.image_height), int(st.image_width)) != (H, W):
+            raise RuntimeError("FusedMapper.prune_floaters: every frame of a mapper has the mapper's image size")
+        N.require_gpu_op((depth_map, projection))
+        if depth_map.dtype != torch.float32 or depth_map.numel() != H * W:
+            raise RuntimeError(f"FusedMapper.prune_floaters: depth_map is a float32 tensor of {H} x {W} elements, the mapper's image size")
+        lo, hi = int(window[0]), int(window[1])
+        if lo > hi:
+            raise ValueError(f"FusedMapper.prune_floaters: bad window ({lo}, {hi}]")
+        row, col = (int(st.cx), int(st.cy)) if centre == "reference" else (int(st.cy), int(st.cx))
+        if not (0 <= row < H and 0 <= col < W):
+            raise ValueError(f"FusedMapper.prune_floaters: the centre pixel (row {row}, column {col}) lies outside the {H} x {W} image")
+        tm = None if tile_mask is None else _checked_tile_mask(tile_mask, dev, H, W)
+        if self.alive is None:
+            self.alive = torch.ones((self.P,), dtype=torch.uint8, device=dev)
+        p = self._prune_ctx
+        if p is None or p["key"] != self.P:
+            f32 = dict(dtype=torch.float32, device=dev)
+            p = self._prune_ctx = dict(key=self.P, cameras=(torch.empty((4, 4, 4), **f32), torch.empty((4, 4, 4), **f32), torch.empty((3,), **f32)),
+                                       ws=mg.prune_workspace(self.P, dev), stats=torch.zeros((8,), dtype=torch.int32, device=dev))
+        with torch.cuda.device(dev):
+            self.activate()
+            view, proj, _ = mg.prune_cameras(st.viewmatrix, projection.to(dev).contiguous(), depth_map.contiguous().reshape(H, W), row * W + col,
+                                             theta_deg, out=p["cameras"])
+            try:
+                for k in range(4):
+                    c = self._maintain_render(st._replace(viewmatrix=view[k], projmatrix=proj[k]), tile_mask=tm)
+                    mg.prune_touch(c["out"][7], p["ws"], render_header=c["geom"])
+                # (the buffers as they are bound NOW)
+                stats = mg.prune_step({b.name: a for b, a in self._rows("param", "meta")}, p["ws"], (lo, hi), self._park_position(), stats=p["stats"])
+            except Exception:
+                self._prune_ctx = None  # (a call that failed between its touches and its row pass leaves marks in the workspace)
+                raise
+        self._n_spare_stale = True  # (_refresh_spare_count)
+        self._act_valid = False  # deleted rows' raw parameters changed
+        self.activate()  # (a captured iteration starts from the activations of the current parameters)
+        return stats
+
+    def prune_overflowed(self):
+        """Whether the most recent prune_floaters() skipped its deletion because one of its four renders outgrew the context (one small
+        device-to-host read, like maintain_overflowed()).  If so the next call sizes a new context."""
+        p = self._prune_ctx
+        if p is None:
+            return False
+        over = int(p["stats"][4].item()) != 0
+        if over:
+            self._maintain_ctx = None
+        return over
 
     @torch.no_grad()
     def evaluate(self, frames, min_depth=0.3, max_depth=5.0, out=None):
@@ -920,7 +1006,7 @@ class FusedMapper:
         make_mesh.py) into THIS mapper, in place: the rows of `path` become the unstable cloud in rows [0, U), the rows of `stable_path`
         the stable cloud in rows [U, U + S) (either may be None: an empty cloud has no file).  Values are the files' raw parameters, bit
         for bit (the constructor's clamp and log are not applied); confidence is the file's column, or zeros without one.  add_tick =
-        tick, both strike counters and every Adam moment zero; every other row becomes a spare row exactly as _free_rows leaves one.
+        frame_id = tick (the files do not hold the column), both strike counters and every Adam moment zero; every other row becomes a spare row exactly as _free_rows leaves one.
         P never changes: more rows than P is a RuntimeError that names the reserve() needed.  A stable file on a mapper that does not
         track lifecycles starts tracking.  One host-to-device copy and one launch (dqo_map_unpack_rows) per file.  Row flags: every live
         row is trained and rendered (set_training_rows() names the next call's clouds).  Ends with
@@ -956,6 +1042,7 @@ class FusedMapper:
             self.stable[:U] = 0
             self.stable[U:n] = 1
             self.add_tick[:n] = int(tick)
+            self.frame_id[:n] = int(tick)
             self.depth_error_counter.zero_(), self.color_error_counter.zero_()
         if n < P:
             self._free_rows(torch.arange(n, P, device=dev))
@@ -1043,7 +1130,7 @@ class FusedMapper:
 
     @torch.no_grad()
     def grow(self, new, delete_mask=None, min_radius=0.001, max_radius=0.05, xyz_factor=(1.0, 1.0, 0.1), scale_factor=1.0,
-             new_mapping_call=False, stable_mask=None, unstable_opacity_low=0.1, attach_async=True, tick=None):
+             new_mapping_call=False, stable_mask=None, unstable_opacity_low=0.1, attach_async=True, tick=None, frame_id=None):
         """The map-growth step between two mapping calls — Mapping.gaussians_add (SLAM/multiprocess/mapper.py:249-254) and the
         deletion half of error_gaussians_remove (:1086-1096) — on this mapper's map.  `new`: dict(xyz [Q,3], scales [Q,3],
         rotations [Q,4], opacity [Q,1], shs [Q,M,3]; with an object gate also obj_id [Q]) of numpy arrays or GPU tensors.
@@ -1069,8 +1156,8 @@ class FusedMapper:
         place when the map has reserve()d spare rows, new_mapping_call is set and the spare and deleted rows hold the new Gaussians;
         into re-allocated buffers otherwise.  new_mapping_call=True also starts the next mapping call (begin_mapping_call: fresh Adam,
         fresh init_stat, as the reference does after every growth step, mapper.py:533-548).  tick (a mapper that track_lifecycle()s): the
-        new rows' add_tick — they join the unstable cloud with zero strike counters (temp_to_optimize, mapper.py:1438-1466).  Returns the
-        counts of each stage."""
+        new rows' add_tick — they join the unstable cloud with zero strike counters (temp_to_optimize, mapper.py:1438-1466); frame_id:
+        their frame_id (temp_to_optimize(frame_id), :1451-1460; None = tick if given, else 0).  Returns the counts of each stage."""
         self._refresh_spare_count()
         c = self._grow_candidates(new)
         Q = c["xyz"].shape[0]
@@ -1095,6 +1182,9 @@ class FusedMapper:
         stats["added"] = n_add = int(rows["xyz"].shape[0])
         if tick is not None and self.add_tick is not None:
             rows["add_tick"] = torch.full((n_add,), int(tick), dtype=torch.int32, device=self.device)
+        if self.frame_id is not None:
+            fid = frame_id if frame_id is not None else (tick if tick is not None else 0)
+            rows["frame_id"] = torch.full((n_add,), int(fid), dtype=torch.int32, device=self.device)
         if self.alive is not None:
             # (the deleted rows as indices, found once: four boolean-mask writes were four passes over the map + four host round trips)
             if delete_mask is None:

@@ -479,6 +479,91 @@ def lifecycle_step(state, tick, gt_color, gt_depth, render_color, render_depth, 
     return stats
 
 
+# ---- floater pruning: virtual cameras, touch counts, delete (csrc/map_prune.hip) -----------------------------------------------------------
+PRUNE_STATE = LIFECYCLE_STATE + (("frame_id", torch.int32, 1),)
+PRUNE_STATS = ("window_rows", "deleted_unstable", "deleted_stable", "valid_renders", "skipped", "alive_left", "reserved0", "reserved1")
+
+
+def prune_cameras(viewmatrix, projection, depth_map, pixel, theta_deg=3.0, out=None):
+    """The four virtual cameras of Mapping.to_purne (SLAM/multiprocess/mapper.py:424-481, 497): the keyframe's camera turned by
+    +-theta_deg about two axes around the point it looks at (include/dqo_raster.h, dqo_prune_cameras, lists the statements and the
+    reference's quirks they keep).  viewmatrix: the frame's float32 [4,4] as in the raster settings; projection: float32 [4,4], transposed
+    as the reference keeps it; depth_map: the frame's depth, float32 [H,W]; pixel: the index row * W + column
+    that the centre depth is read from.  cos / sin of the angle are formed here, in double, and travel as
+    arguments.  Returns (viewmatrix [4,4,4], projmatrix [4,4,4], focal [3]) float32 device tensors (`out`: the same three, reused).
+    One launch, nothing read back."""
+    import math
+    N.require_gpu_op((viewmatrix, projection, depth_map))
+    dev = depth_map.device
+    if depth_map.dim() != 2:
+        raise RuntimeError("prune_cameras: depth_map is [H, W]")
+    H, W = int(depth_map.shape[0]), int(depth_map.shape[1])
+    for a, what in ((viewmatrix, "viewmatrix"), (projection, "projection")):
+        if a.dtype != torch.float32 or a.numel() != 16 or not a.is_contiguous():
+            raise RuntimeError(f"prune_cameras: {what} is a contiguous float32 [4,4]")
+    if depth_map.dtype != torch.float32 or not depth_map.is_contiguous():
+        raise RuntimeError("prune_cameras: depth_map is contiguous float32")
+    if out is None:
+        out = (torch.empty((4, 4, 4), dtype=torch.float32, device=dev), torch.empty((4, 4, 4), dtype=torch.float32, device=dev),
+               torch.empty((3,), dtype=torch.float32, device=dev))
+    view, proj, focal = out
+    for a, n in ((view, 64), (proj, 64), (focal, 3)):
+        N.require_gpu(a)
+        if a.dtype != torch.float32 or a.numel() != n or not a.is_contiguous():
+            raise RuntimeError("prune_cameras: out is (float32 [4,4,4], float32 [4,4,4], float32 [3]), contiguous")
+    theta = math.radians(float(theta_deg))
+    with torch.cuda.device(dev):
+        N.check(N.lib().dqo_prune_cameras(H, W, N.ptr(viewmatrix), N.ptr(projection), N.ptr(depth_map), int(pixel), math.cos(theta),
+                                          math.sin(theta), N.ptr(view), N.ptr(proj), N.ptr(focal), N.current_stream()))
+    return view, proj, focal
+
+
+def prune_workspace(P, device):
+    """The zeroed workspace prune_touch / prune_step share for a map of P rows (they hand it back zero)."""
+    return torch.zeros((N.lib().dqo_prune_workspace_bytes(int(P)),), dtype=torch.uint8, device=device)
+
+
+def prune_touch(n_touched, touched_ws, render_header=None):
+    """Behind one virtual camera's render: rows with n_touched != 0 are marked in the workspace (dqo_prune_touch).  render_header: the
+    geometry buffer of that render — one that overflowed its capacity marks nothing and counts as invalid."""
+    N.require_gpu_op((n_touched, touched_ws))
+    if n_touched.dtype != torch.int32 or not n_touched.is_contiguous():
+        raise RuntimeError("prune_touch: n_touched is a contiguous int32 [P]")
+    with torch.cuda.device(n_touched.device):
+        N.check(N.lib().dqo_prune_touch(int(n_touched.numel()), N.ptr(n_touched), N.ptr(render_header), N.ptr(touched_ws), touched_ws.numel(),
+                                        N.current_stream()))
+
+
+def prune_step(state, touched_ws, window, park, stats=None):
+    """The deletion of Mapping.to_purne (SLAM/multiprocess/mapper.py:509-527) on ONE map, in the style of lifecycle_step: state is the
+    dict of GPU tensors rewritten IN PLACE (PRUNE_STATE: LIFECYCLE_STATE and frame_id int32 [P]); touched_ws: the workspace the
+    prune_touch calls of the four renders marked (prune_workspace); window = (lo, hi): rows with lo < frame_id <= hi; park: [3] GPU
+    tensor, where deleted rows go.  A window row that is alive and untouched becomes a spare row — unless one of the renders was invalid,
+    then nothing is deleted.  Returns the int32 [8] device tensor of counts (PRUNE_STATS; `stats` if given).  One launch, no host
+    synchronisation; the workspace is zero again afterwards."""
+    dev = state["xyz"].device
+    P = int(state["xyz"].shape[0])
+    for name, dtype, width in PRUNE_STATE:
+        a = state[name]
+        N.require_gpu(a)
+        if a.dtype != dtype or a.numel() != P * width or not a.is_contiguous() or a.device != dev:
+            raise RuntimeError(f"prune_step: state['{name}'] must be a contiguous {dtype} tensor of {P} x {width} on {dev} (it is rewritten in place)")
+    park = park.contiguous() if torch.is_tensor(park) else const_tensor(list(park), dev)
+    N.require_gpu(park, touched_ws)
+    if park.dtype != torch.float32 or park.numel() != 3:
+        raise RuntimeError("prune_step: park is a float32 tensor of 3")
+    lo, hi = int(window[0]), int(window[1])
+    if stats is None:
+        stats = torch.empty((8,), dtype=torch.int32, device=dev)
+    N.require_gpu(stats)
+    if stats.dtype != torch.int32 or stats.numel() != 8 or not stats.is_contiguous():
+        raise RuntimeError("prune_step: stats is a contiguous int32 tensor of 8")
+    with torch.cuda.device(dev):
+        N.check(N.lib().dqo_prune_rows(P, *[N.ptr(state[name]) for name, _, _ in PRUNE_STATE], N.ptr(park), lo, hi, N.ptr(touched_ws),
+                                       touched_ws.numel(), N.ptr(stats), N.current_stream()))
+    return stats
+
+
 # ---- map growth, the first statement: a frame's new Gaussians (csrc/map_sample.hip) --------------------------------------------------------
 SAMPLE_HEADER = ("mask_a", "mask_a_stripped", "mask_b", "mask_b_stripped", "k_a", "k_b", "rows", "overflow")
 _SAMPLE_ROWS = (("xyz", torch.float32, (3,)), ("scales", torch.float32, (3,)), ("rotations", torch.float32, (4,)), ("opacity", torch.float32, (1,)),

@@ -1005,6 +1005,49 @@ size_t dqo_eval_ate_workspace_bytes(int32_t N);
 int dqo_eval_ate(int32_t N, const double* model, int64_t model_stride, int64_t model_cstride, const double* data, int64_t data_stride,
                  int64_t data_cstride, double* ate, double* fit, void* workspace, size_t workspace_bytes, void* hipStream);
 
+/* dqo_prune_cameras / dqo_prune_touch / dqo_prune_rows (ABI 5, symbols-only addition) — floater pruning: Mapping.to_purne with
+ * create_virtual_cameras (SLAM/multiprocess/mapper.py:424-529) on one map whose rows carry `stable` and `frame_id`
+ * (GaussianPointCloud._frame_ids, SLAM/gaussian_pointcloud.py:52, 230-231, 277-279, 435), nothing read back, every row rewritten in place.
+ * csrc/map_prune.hip lists every statement in order; tests/prune_oracle.py restates them.
+ *
+ * dqo_prune_cameras — replaces :471-481 and create_virtual_cameras (:424-466) with frame.update (scene/cameras.py:169-183) of :497.  One
+ *   launch, one lane, double, one rounding per statement, none contracted.  viewmatrix: the keyframe's float32 [4,4] as in the raster
+ *   settings (the transposed w2c); projection: float32 [4,4], transposed as the reference keeps it (dqo_traj_append's argument); depth:
+ *   the frame's depth map, float32 [H*W]; pixel: the index read from it; cos_t, sin_t: cos / sin of the angle, formed by the HOST in double.
+ *     W2V[a][b] = viewmatrix[b][a]; Rw = W2V[:3,:3]; T = W2V[:3,3]; d0 = depth[pixel]; d = d0 == 0 ? -1 : -d0;
+ *     focal = T + d * Rw[:,2]; offset = T - focal; for A_k = Ry(+t), Ry(-t), Rx(+t), Rx(-t) (rotation_matrix's signs, :431-443):
+ *     R_k = A_k @ Rw, T_k = A_k @ offset + focal, every entry (a0 b0 + a1 b1) + a2 b2.
+ *   out_viewmatrix [4,4,4]: [k][:3,:3] = float(R_k) as it stands, [k][3,:3] = float(T_k), last column (0,0,0,1) — update() takes R_k for
+ *   the camera's R.  out_projmatrix [4,4,4]: float(viewmatrix_k in double @ double(projection)), entry ((a0 b0 + a1 b1) + a2 b2) + a3 b3
+ *   rounded once (the departure dqo_traj_append documents).  out_focal [3]: float(focal), for inspection.  campos is not formed:
+ *   Camera.update never refreshes camera_center, the reference renders the virtual views with the real camera's centre.
+ *   The reference's quirks are kept: `cx, cy = int(frame.cy), int(frame.cx)` then depth_map[cy, cx] reads row int(frame.cx), column
+ *   int(frame.cy) (the caller forms `pixel`); camera_T is the w2c translation used as a position; update() is handed a w2c rotation
+ *   where it expects the transposed one.  The frame is not mutated, so the restore of :529 has no counterpart.
+ *   DQO_ERR_INVALID_ARG before the launch: H * W < 1 or too large, a NULL pointer, pixel outside [0, H * W).
+ * dqo_prune_touch — replaces `n_touched += render_output["n_touched"]` (:506-508); one launch per virtual camera directly behind its
+ *   render, one thread per row: touched[i] = 1 where n_touched[i] != 0.  render_header: the device header of that render (the start of
+ *   its geometry buffer), or NULL.  A render that overflowed its capacity (overflow != 0) left n_touched at zero for every row: the launch
+ *   then marks nothing and counts an invalid render.  DQO_ERR_INVALID_ARG: P < 0, NULL n_touched; DQO_ERR_WORKSPACE.
+ * dqo_prune_rows — replaces :509-527 (the mask, its .item(), GaussianPointCloud.delete of both clouds); one launch, one thread per row.
+ *   A row with alive != 0 && lo < frame_id <= hi is in the window ((keyframe_list[-2].uid, keyframe_list[-1].uid], or (uid - 1, uid]
+ *   with one keyframe, :510-515).  If no render since the last call was invalid, a window row with touched == 0 is deleted: xyz = park,
+ *   opacity_raw = scaling_raw = -10, alive = 0, row_flags = DQO_ROW_HIDDEN | DQO_ROW_FROZEN, confidence = 0, and 0 into stable / add_tick
+ *   / both counters / frame_id (what dqo_map_lifecycle_rows writes into a freed row, plus frame_id).  Every touched word and both render
+ *   counts are cleared as they are read.  stats[8] (overwritten): rows in the window, deleted unstable, deleted stable, valid renders,
+ *   skipped (1: some render was invalid, nothing was deleted), rows alive afterwards, 0, 0.  With P == 0 stats is all zero.
+ *   A row dqo_map_lifecycle_rows frees keeps a stale frame_id; nothing reads it while alive == 0.
+ *   DQO_ERR_INVALID_ARG before the launch: P < 0, lo > hi, NULL stats, a NULL per-Gaussian buffer or park; DQO_ERR_WORKSPACE.
+ * workspace: dqo_prune_workspace_bytes(P) bytes, ZERO when first used and then left to these calls (dqo_prune_rows hands it back zero). */
+size_t dqo_prune_workspace_bytes(int32_t P);
+int dqo_prune_cameras(int32_t H, int32_t W, const float* viewmatrix, const float* projection, const float* depth, int64_t pixel, double cos_t,
+                      double sin_t, float* out_viewmatrix, float* out_projmatrix, float* out_focal, void* hipStream);
+int dqo_prune_touch(int32_t P, const int32_t* n_touched, const DqoRastHeader* render_header, void* workspace, size_t workspace_bytes,
+                    void* hipStream);
+int dqo_prune_rows(int32_t P, float* xyz, float* opacity_raw, float* scaling_raw, float* confidence, uint8_t* alive, uint8_t* row_flags,
+                   uint8_t* stable, int32_t* add_tick, int32_t* depth_error_counter, int32_t* color_error_counter, int32_t* frame_id,
+                   const float* park, int32_t lo, int32_t hi, void* workspace, size_t workspace_bytes, int32_t* stats, void* hipStream);
+
 #define DQO_TICKET_WORDS (16 + 16 * 64) /* int32 words behind DqoAdamStep.block_ticket */
 typedef struct DqoAdamStep {
     int32_t P, M;      /* Gaussians, SH coefficients per Gaussian (f_dc = coefficient 0, f_rest = the others) */
