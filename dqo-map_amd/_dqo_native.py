@@ -121,6 +121,7 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_growth_sample_workspace_bytes", "dqo_growth_sample", "dqo_eval_picture_workspace_bytes", "dqo_eval_picture",
            "dqo_eval_ms_ssim_workspace_bytes", "dqo_eval_ms_ssim",
            "dqo_nn1_workspace_bytes", "dqo_nn1", "dqo_eval_pcd_workspace_bytes", "dqo_eval_pcd", "dqo_window_masks_workspace_bytes",
+           "dqo_nn1_grouped_workspace_bytes", "dqo_nn1_grouped", "dqo_eval_pcd_grouped_workspace_bytes", "dqo_eval_pcd_grouped", "dqo_map_pack_rows_by_object",
            "dqo_window_masks", "dqo_surfel_densify_workspace_bytes", "dqo_surfel_densify", "dqo_map_pack_workspace_bytes",
            "dqo_map_pack_rows", "dqo_map_unpack_rows", "dqo_mesh_sample_workspace_bytes", "dqo_mesh_sample",
            "dqo_objmap_frame", "dqo_objmap_optimize", "dqo_objmap_mean_iou", "dqo_traj_append", "dqo_track_world_maps",
@@ -181,6 +182,8 @@ def lib():
         L.dqo_knn3.argtypes = [c_i32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]
         L.dqo_nn1_workspace_bytes.argtypes = [c_i32, c_i32]
         L.dqo_nn1.argtypes = [c_i32, c_vp, c_vp, c_i32] + [c_vp] * 7 + [c_sz, c_vp]
+        L.dqo_nn1_grouped_workspace_bytes.argtypes = [c_i32, c_i32]
+        L.dqo_nn1_grouped.argtypes = [c_i32, c_vp, c_vp, c_i32] + [c_vp] * 7 + [c_sz, c_vp]
         # quadric.hip
         L.dqo_quadric_iou_fwd_bwd.argtypes = [c_i32] + [c_vp] * 12
         L.dqo_quadric_adam.argtypes = [c_i32, c_i32] + [c_vp] * 9
@@ -229,11 +232,14 @@ def lib():
         L.dqo_eval_picture.argtypes = [c_i32, c_i32] + [c_vp] * 5 + [c_f, c_f, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]
         L.dqo_eval_pcd_workspace_bytes.argtypes = [c_i32, c_i32]
         L.dqo_eval_pcd.argtypes = [c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, P(c_f), c_vp, c_i32, c_vp, c_sz, c_vp]
+        L.dqo_eval_pcd_grouped_workspace_bytes.argtypes = [c_i32, c_i32]
+        L.dqo_eval_pcd_grouped.argtypes = [c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, P(c_f), c_vp, c_i64, c_i64, c_vp, c_sz, c_vp]
         L.dqo_eval_ms_ssim_workspace_bytes.argtypes = [c_i32, c_i32]
         L.dqo_eval_ms_ssim.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]
         # map_checkpoint.hip
         L.dqo_map_pack_workspace_bytes.argtypes = [c_i32]
         L.dqo_map_pack_rows.argtypes = [c_i32] * 3 + [c_vp] * 9 + [c_i64, c_vp, c_vp, c_sz, c_vp]
+        L.dqo_map_pack_rows_by_object.argtypes = [c_i32] * 3 + [c_vp] * 10 + [c_i64, c_vp, c_vp, c_sz, c_vp]
         L.dqo_map_unpack_rows.argtypes = [c_i32] * 5 + [c_vp] * 8
         # map_objects.hip
         L.dqo_objmap_frame.argtypes = [c_i32] * 3 + [c_vp] * 9 + [c_i32] + [c_vp] * 7 + [c_i32] * 3 + [c_u64] + [c_vp] * 6

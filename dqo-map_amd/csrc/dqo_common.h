@@ -551,3 +551,5 @@ bool dqo_nn1_size_ok(int32_t n);
 size_t dqo_nn1_ws_bytes(int Q, int R);
 int dqo_launch_nn1(int Q, const float* q_xyz, const uint8_t* q_keep, int R, const float* r_xyz, const uint8_t* r_keep, const float* q_xform,
                    const float* r_xform, float* dist2, int32_t* idx, void* ws, hipStream_t s);
+int dqo_launch_nn1_grouped(int Q, const float* q_xyz, const int32_t* q_group, int R, const float* r_xyz, const int32_t* r_group,
+                           const float* q_xform, const float* r_xform, float* dist2, int32_t* idx, float2* by_rank, void* ws, hipStream_t s);

@@ -185,9 +185,18 @@ __global__ void morton_fine_kernel(int P, int P2, const float* __restrict__ xyz,
 }
 
 // ---- stable LSD radix sort, one 8-bit pass = three kernels ----
+// The digit of a key: eight bits of it, or (BY_GROUP: the pass that sorts dqo_nn1_grouped's queries by object) the group id of the row
+// the key's index bits name — [0, 64), 64 for a row without a group, so those sort behind every object.
+template <bool BY_GROUP>
+__device__ __forceinline__ uint32_t radix_digit(uint64_t key, int shift, const int32_t* __restrict__ group) {
+    if (!BY_GROUP) return (uint32_t)(key >> shift) & 255u;
+    const int gid = group[(uint32_t)key & ((1u << 25) - 1u)];  // (FINE_IDX_BITS index bits)
+    return gid >= 0 && gid < 64 ? (uint32_t)gid : 64u;
+}
 // (1) digit histogram of every block of RDX_BLK keys, stored digit-major: hist[digit][block]
+template <bool BY_GROUP>
 __global__ __launch_bounds__(RDX_T) void radix_hist_kernel(int n, const uint64_t* __restrict__ keys, int shift, uint32_t* __restrict__ hist,
-                                                            int nblk) {
+                                                            int nblk, const int32_t* __restrict__ group) {
     __shared__ uint32_t s[256];
     s[threadIdx.x] = 0;
     __syncthreads();
@@ -195,7 +204,7 @@ __global__ __launch_bounds__(RDX_T) void radix_hist_kernel(int n, const uint64_t
 #pragma unroll
     for (int r = 0; r < RDX_KPT; r++) {
         const int i = base + r * RDX_T + threadIdx.x;
-        if (i < n) atomicAdd(&s[(uint32_t)(keys[i] >> shift) & 255u], 1u);
+        if (i < n) atomicAdd(&s[radix_digit<BY_GROUP>(keys[i], shift, group)], 1u);
     }
     __syncthreads();
     hist[(size_t)threadIdx.x * nblk + blockIdx.x] = s[threadIdx.x];
@@ -226,9 +235,10 @@ __global__ __launch_bounds__(256) void radix_scan_kernel(uint32_t* __restrict__ 
     if (tid == 255) tot[blockIdx.x] = pre;  // (the last thread's running sum is the row total)
 }
 // (3) scatter: key -> offs[digit][block] + its rank among the block's keys of the same digit, in block order (stable)
+template <bool BY_GROUP>
 __global__ __launch_bounds__(RDX_T) void radix_scatter_kernel(int n, const uint64_t* __restrict__ in, uint64_t* __restrict__ out, int shift,
                                                                const uint32_t* __restrict__ offs, int nblk,
-                                                               const uint32_t* __restrict__ tot) {
+                                                               const uint32_t* __restrict__ tot, const int32_t* __restrict__ group) {
     __shared__ uint32_t s_run[256];              // next free position of every digit (earlier rounds of this block included)
     __shared__ uint32_t s_wc[RDX_T / 64][256];   // this round's keys per (wave, digit)
     __shared__ uint32_t s_t[RDX_T / 64];
@@ -255,7 +265,7 @@ __global__ __launch_bounds__(RDX_T) void radix_scatter_kernel(int n, const uint6
         const int i = base + r * RDX_T + tid;
         const bool valid = i < n;
         const uint64_t key = valid ? in[i] : 0ull;
-        const uint32_t d = (uint32_t)(key >> shift) & 255u;
+        const uint32_t d = valid ? radix_digit<BY_GROUP>(key, shift, group) : 0u;
         // the lanes of this wave that hold the same digit: eight ballots
         unsigned long long peers = __builtin_amdgcn_ballot_w64(valid);
 #pragma unroll
@@ -765,6 +775,118 @@ __global__ void nn1_fill_kernel(int Q, float* __restrict__ dist2, int32_t* __res
     if (idx != nullptr) idx[i] = -1;
 }
 
+// ---- dqo_nn1_grouped: dqo_nn1 for up to 64 objects in ONE search ------------------------------------------------------------------------
+// (metric_obj.py:169-236: eval_pcd of every object's cloud against that object's own mesh.)  A reference only counts for a query of the same
+// group.  The reference set is built once with its group ids (knn_build's group path: the id + 1 in bits 25..31 of a point's index word,
+// the set of groups under it in every record), the queries are sorted once — by group, and within a group by their Morton code on the
+// reference's grid (the sort's last pass takes the group id as its digit), so a wave holds one object where it can — and one scan serves
+// every object.  The scan is nn1_scan_kernel's with two more rules: a record is opened only if one of the lanes that cannot exclude it
+// belongs to a group the record holds (a ballot over `need && (record's set & my bit)`: the record's set is wave-uniform), and a lane takes
+// a candidate only if the candidate's group word is its own.  The four references around a query's rank are candidates like any other:
+// they count only if they are of the query's group, so a lane may start the scan without a bound — it then opens every record that
+// holds its group until it has met a reference of its own.  Every candidate a lane takes is a reference of its group, every record it
+// skips holds none of its group or has dist_box_point > its best: the result is the minimum of kbest's float expression over ALL
+// references of the query's group, bit for bit — what dqo_nn1 returns with the two keep masks of that group.
+__global__ void nn1g_query_keys_kernel(int Q, const float* __restrict__ xyz, const int32_t* __restrict__ group, const float* __restrict__ xform,
+                                       const float* __restrict__ ref_bbox, uint64_t* __restrict__ keys) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Q) return;
+    uint64_t code = (1ull << (3 * FINE_BITS)) - 1ull;
+    if (knn_in_group(group, i)) {
+        const float4 p = nn1_point(xyz, xform, i);
+        code = morton_fine_code(p.x, p.y, p.z, ref_bbox);
+    }
+    keys[i] = (code << FINE_IDX_BITS) | (uint64_t)i;
+}
+
+// the sorted query: xyz under the transform, the row index and the group id + 1 above it (0: no group, the point is not searched for)
+__global__ void nn1g_gather_query_kernel(int Q, const float* __restrict__ xyz, const int32_t* __restrict__ group, const float* __restrict__ xform,
+                                         const uint64_t* __restrict__ keys, float4* __restrict__ sorted_q) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Q) return;
+    const uint32_t src = (uint32_t)keys[i] & NN1_IDX_MASK;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    uint32_t w = src;
+    if (knn_in_group(group, (int)src)) p = nn1_point(xyz, xform, (int)src), w |= (uint32_t)(group[src] + 1) << KNN_GROUP_SHIFT;
+    p.w = __uint_as_float(w);
+    sorted_q[i] = p;
+}
+
+__device__ __forceinline__ void nn1g_take(const float4 me, const float4 cand, uint32_t my_group, float& best, int& bidx) {
+#pragma clang fp contract(off)
+    const float dx = cand.x - me.x, dy = cand.y - me.y, dz = cand.z - me.z;
+    const float dist = dx * dx + dy * dy + dz * dz;
+    const uint32_t w = __float_as_uint(cand.w);
+    if ((w >> KNN_GROUP_SHIFT) == my_group && dist < best) best = dist, bidx = (int)(w & NN1_IDX_MASK);
+}
+
+// by_rank (dqo_eval_pcd_grouped; may be NULL): the result in the queries' SORTED order too, {dist2, group id (64: none)} of sorted query q —
+// an object's rows are contiguous there, which is what the reduction's fixed summation order is laid over.  dist2 may be NULL then.
+__global__ __launch_bounds__(256) void nn1_grouped_scan_kernel(int Q, const float4* __restrict__ sorted_q, const uint64_t* __restrict__ keys_q,
+                                                               int R, const float4* __restrict__ sorted_r, const uint64_t* __restrict__ keys_r,
+                                                               const float* __restrict__ boxes, const float* __restrict__ sub,
+                                                               const float* __restrict__ groups, float* __restrict__ dist2,
+                                                               int32_t* __restrict__ idx, float2* __restrict__ by_rank) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    const float4 me = q < Q ? sorted_q[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint32_t my_w = __float_as_uint(me.w);
+    const uint32_t my_group = q < Q ? my_w >> KNN_GROUP_SHIFT : 0u;  // id + 1
+    const bool live = my_group != 0u;
+    const unsigned long long my_bit = live ? 1ull << (my_group - 1u) : 0ull;
+    float best = FLT_MAX;
+    int bidx = -1, rank = 0;
+    if (live) {  // the first reference key not below the query's code; the two references either side of it count if they are of its group
+        const uint64_t key = (keys_q[q] >> FINE_IDX_BITS) << FINE_IDX_BITS;
+        int lo = 0, hi = R;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (keys_r[mid] < key) lo = mid + 1;
+            else hi = mid;
+        }
+        rank = lo;
+        for (int i = max(0, rank - 2); i <= min(R - 1, rank + 1); i++) nn1g_take(me, sorted_r[i], my_group, best, bidx);
+    }
+    const int nb = (R + KNN_BOX - 1) / KNN_BOX, ng = (nb + 63) / 64;
+    // a record (wave-uniform address) is opened if a lane that cannot exclude it is of a group the record holds
+    auto wanted = [&](const float* rec) {
+        const unsigned long long held = knn_record_groups(rec);
+        if (held == 0ull) return false;
+        const float d = dist_box_point(rec, me);
+        return __ballot(live && (held & my_bit) != 0ull && !(d > best)) != 0;
+    };
+    auto scan_box = [&](int b) {
+        if (!wanted(boxes + 8 * (size_t)b)) return;
+        const int lo = b * KNN_BOX, hi = min(R, lo + KNN_BOX);
+        for (int r0 = lo; r0 < hi; r0 += KNN_SUB) {
+            if (!wanted(sub + 8 * (size_t)(r0 / KNN_SUB))) continue;
+            if (r0 + KNN_SUB <= hi) {
+#pragma unroll 8
+                for (int i = 0; i < KNN_SUB; i++) nn1g_take(me, sorted_r[r0 + i], my_group, best, bidx);
+            } else {
+                for (int i = r0; i < hi; i++) nn1g_take(me, sorted_r[i], my_group, best, bidx);
+            }
+        }
+    };
+    if (__ballot(live) != 0) {
+        // queries without a group sort last, so lane 0 of a wave with a live lane is live: the box its rank falls into first
+        const int home = min(nb - 1, __builtin_amdgcn_readfirstlane(rank) / KNN_BOX);
+        scan_box(home);
+        for (int g = 0; g < ng; g++) {
+            if (!wanted(groups + 8 * (size_t)g)) continue;
+            const int b1 = min(nb, (g + 1) * 64);
+            for (int b = g * 64; b < b1; b++)
+                if (b != home) scan_box(b);
+        }
+    }
+    if (q < Q) {
+        const uint32_t dst = my_w & NN1_IDX_MASK;
+        const float d = live && bidx >= 0 ? best : FLT_MAX;
+        if (dist2 != nullptr) dist2[dst] = d;
+        if (idx != nullptr) idx[dst] = live ? bidx : -1;
+        if (by_rank != nullptr) by_rank[q] = make_float2(d, __uint_as_float(live ? my_group - 1u : 64u));
+    }
+}
+
 struct Nn1Ws {
     KnnWs r, q;
     float* txyz;    // [R][3] the reference rows under ref_xform
@@ -790,17 +912,25 @@ static size_t dqo_knn3_ws_bytes(int P) { return knn_ws(nullptr, P).total; }
 // is `sorted` (16 B per point, written by the gather only after the sort); an even number of passes leaves the result in w.keys.
 // (fine codes: 39 bits above the 25-bit index — five passes; an even pass count leaves the result in w.keys, so a sixth pass
 // sorts by the top byte once more: a stable sort of sorted keys by a prefix of the key moves nothing but the buffer)
-static int knn_radix_sort(int P, const KnnWs& w, bool fine, hipStream_t s) {
+// by_group (dqo_nn1_grouped's queries, fine codes only): that sixth pass sorts by the rows' group ids instead — by object, and within an
+// object by code, since every pass is stable.
+static int knn_radix_sort(int P, const KnnWs& w, bool fine, hipStream_t s, const int32_t* by_group = nullptr) {
     const int nblk = (P + RDX_BLK - 1) / RDX_BLK;
     uint64_t* a = w.keys;
     uint64_t* b = reinterpret_cast<uint64_t*>(w.sorted);
     const int n_pass = fine ? 6 : 4, shift0 = fine ? FINE_IDX_BITS : 32;
     for (int pass = 0; pass < n_pass; pass++) {
         const int shift = pass < 5 ? shift0 + 8 * pass : 56;
-        DQO_LAUNCH("radix_hist_kernel", radix_hist_kernel, dim3(nblk), dim3(RDX_T), s, P, a, shift, w.hist, nblk);
+        const bool grp = by_group != nullptr && pass == 5;
+        if (grp) DQO_LAUNCH("radix_hist_kernel", radix_hist_kernel<true>, dim3(nblk), dim3(RDX_T), s, P, a, shift, w.hist, nblk, by_group);
+        else DQO_LAUNCH("radix_hist_kernel", radix_hist_kernel<false>, dim3(nblk), dim3(RDX_T), s, P, a, shift, w.hist, nblk, by_group);
         DQO_LAUNCH("radix_scan_kernel", radix_scan_kernel, dim3(256), dim3(256), s, w.hist, nblk, w.hist + (size_t)256 * nblk);
-        DQO_LAUNCH("radix_scatter_kernel", radix_scatter_kernel, dim3(nblk), dim3(RDX_T), s, P, a, b, shift, w.hist, nblk,
-                   w.hist + (size_t)256 * nblk);
+        if (grp)
+            DQO_LAUNCH("radix_scatter_kernel", radix_scatter_kernel<true>, dim3(nblk), dim3(RDX_T), s, P, a, b, shift, w.hist, nblk,
+                       w.hist + (size_t)256 * nblk, by_group);
+        else
+            DQO_LAUNCH("radix_scatter_kernel", radix_scatter_kernel<false>, dim3(nblk), dim3(RDX_T), s, P, a, b, shift, w.hist, nblk,
+                       w.hist + (size_t)256 * nblk, by_group);
         std::swap(a, b);
     }
     return DQO_OK;
@@ -899,6 +1029,37 @@ int dqo_launch_nn1(int Q, const float* q_xyz, const uint8_t* q_keep, int R, cons
     return DQO_OK;
 }
 
+// dqo_nn1's workspace serves (its group column goes unused: the caller's ids are read in place).  Q, R >= 1 when by_rank is asked for.
+int dqo_launch_nn1_grouped(int Q, const float* q_xyz, const int32_t* q_group, int R, const float* r_xyz, const int32_t* r_group,
+                           const float* q_xform, const float* r_xform, float* dist2, int32_t* idx, float2* by_rank, void* ws, hipStream_t s) {
+    if (Q == 0) return DQO_OK;
+    if (R == 0) {
+        DQO_LAUNCH("nn1_fill_kernel", nn1_fill_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, dist2, idx);
+        return DQO_OK;
+    }
+    const Nn1Ws w = nn1_ws(ws, Q, R);
+    const float* ref = r_xyz;
+    if (r_xform != nullptr) {
+        DQO_LAUNCH("nn1_prepare_ref_kernel", nn1_prepare_ref_kernel, dim3((R + 255) / 256), dim3(256), s, R, r_xyz, (const uint8_t*)nullptr,
+                   r_xform, w.txyz, (int32_t*)nullptr);
+        ref = w.txyz;
+    }
+    int rc = knn_build(R, ref, w.r, true, s, true, r_group);
+    if (rc) return rc;
+    const int ns = (R + KNN_SUB - 1) / KNN_SUB, nb = (R + KNN_BOX - 1) / KNN_BOX, ng = (nb + 63) / 64;
+    DQO_LAUNCH("sub_minmax_kernel", sub_minmax_kernel, dim3((ns * 64 + 255) / 256), dim3(256), s, R, w.r.sorted, w.r.sub);
+    DQO_LAUNCH("group_minmax_kernel", group_minmax_kernel, dim3((ng * 64 + 255) / 256), dim3(256), s, nb, w.r.boxes, w.r.groups);
+    DQO_LAUNCH("nn1g_query_keys_kernel", nn1g_query_keys_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, q_xyz, q_group, q_xform, w.r.bbox,
+               w.q.keys);
+    rc = knn_radix_sort(Q, w.q, true, s, q_group);
+    if (rc) return rc;
+    DQO_LAUNCH("nn1g_gather_query_kernel", nn1g_gather_query_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, q_xyz, q_group, q_xform, w.q.keys,
+               w.q.sorted);
+    DQO_LAUNCH("nn1_grouped_scan_kernel", nn1_grouped_scan_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, w.q.sorted, w.q.keys, R, w.r.sorted,
+               w.r.keys, w.r.boxes, w.r.sub, w.r.groups, dist2, idx, by_rank);
+    return DQO_OK;
+}
+
 // ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
 extern "C" {
 
@@ -954,6 +1115,19 @@ DQO_API int dqo_nn1(int32_t Q, const float* q_xyz, const uint8_t* q_keep, int32_
     DQO_CHECK_ARG(R == 0 || r_xyz, "null reference set");
     DQO_CHECK_WS("nn1", ws, ws_bytes, dqo_nn1_ws_bytes(Q, R));
     return dqo_launch_nn1(Q, q_xyz, q_keep, R, r_xyz, r_keep, q_xform, r_xform, dist2, idx, ws, (hipStream_t)stream);
+}
+
+DQO_API size_t dqo_nn1_grouped_workspace_bytes(int32_t Q, int32_t R) { return dqo_nn1_workspace_bytes(Q, R); }
+
+DQO_API int dqo_nn1_grouped(int32_t Q, const float* q_xyz, const int32_t* q_group, int32_t R, const float* r_xyz, const int32_t* r_group,
+                            const float* q_xform, const float* r_xform, float* dist2, int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(dqo_nn1_size_ok(Q) && dqo_nn1_size_ok(R), "bad size: at most 2^25 - 1 rows per set");
+    if (Q == 0) return DQO_OK;
+    DQO_CHECK_ARG(q_xyz && dist2, "null query / output");
+    DQO_CHECK_ARG(R == 0 || r_xyz, "null reference set");
+    DQO_CHECK_ARG(q_group && (R == 0 || r_group), "null group ids");
+    DQO_CHECK_WS("nn1 grouped", ws, ws_bytes, dqo_nn1_ws_bytes(Q, R));
+    return dqo_launch_nn1_grouped(Q, q_xyz, q_group, R, r_xyz, r_group, q_xform, r_xform, dist2, idx, nullptr, ws, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -205,6 +205,108 @@ __global__ __launch_bounds__(256) void map_unpack_rows_kernel(UnpkArgs a) {
     }
 }
 
+// ---- pack by object: every file of save_model_ply_obj (SLAM/gaussian_pointcloud.py:589-637) in one table ---------------------------------
+// The alive rows that have an object, ordered by (stable != 0, object id, row index): 128 classes (cloud, object), class q = 64 cloud +
+// object.  header[q] is the class's row count, so the rows of (cloud c, object g) are the slice that starts at the sum of the counts before
+// class 64 c + g.  Three launches, no atomics at all, nothing but the table and the header written:
+//   count  one block per class walks the map's flag and id columns and stores its class's count (a plain store: nothing to zero);
+//   order  one block per class, its start = the counts before it; each of its 16 waves takes a sixteenth of the rows, counts its hits,
+//          and then walks them again with ballots — the hits' row indices go, in ascending row order, into WORD 0 OF THE TABLE ROWS THE
+//          CLASS WILL FILL: the order list needs no memory of its own, and rows behind the total are not touched;
+//   pack   one block per 64 table rows reads their source indices, then a wave gathers a row's C words column by column (the stores are
+//          contiguous, the SH loads stay inside the row's 12 M bytes) — word-for-word copies, as map_pack_rows_kernel's.
+// 128 blocks each read all P flags and ids (6 bytes a row, from L2 after the first): 2 x 1.5 GB at 2 M rows, a fraction of the copy of
+// the table to the host that follows.
+enum {
+    PKO_CLASSES = 128,
+    PKO_WAVES = 16,  // waves of a count / order block
+};
+
+__device__ __forceinline__ int pko_class(const PkArgs& a, const int32_t* __restrict__ object, int64_t i) {
+    const int cls = pk_class(a, i);
+    if (cls == 0) return -1;
+    const int g = object[i];
+    return g >= 0 && g < 64 ? (cls - 1) * 64 + g : -1;
+}
+
+__global__ __launch_bounds__(64 * PKO_WAVES) void map_pack_object_count_kernel(PkArgs a, const int32_t* __restrict__ object) {
+    __shared__ int s_n[PKO_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, mine = (int)blockIdx.x;
+    int n = 0;
+    for (int64_t i = tid; i < (int64_t)a.P; i += 64 * PKO_WAVES) n += pko_class(a, object, i) == mine ? 1 : 0;
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
+    if (lane == 0) s_n[wave] = n;
+    __syncthreads();
+    if (tid == 0) {
+        int t = 0;
+        for (int w = 0; w < PKO_WAVES; w++) t += s_n[w];
+        a.header[mine] = t;
+    }
+}
+
+__global__ __launch_bounds__(64 * PKO_WAVES) void map_pack_object_order_kernel(PkArgs a, const int32_t* __restrict__ object) {
+    __shared__ int s_n[PKO_WAVES];
+    __shared__ int s_base;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, mine = (int)blockIdx.x;
+    if (a.header[mine] == 0) return;  // (the whole block)
+    if (wave == 0) {  // the rows of the classes before this one
+        int v = (lane < mine ? a.header[lane] : 0) + (lane + 64 < mine ? a.header[lane + 64] : 0);
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if (lane == 0) s_base = v;
+    }
+    const int64_t seg = (((int64_t)a.P + PKO_WAVES - 1) / PKO_WAVES + 63) / 64 * 64;  // rows of a wave: a multiple of 64
+    const int64_t lo = seg * wave, hi = min((int64_t)a.P, lo + seg);
+    int n = 0;
+    for (int64_t i = lo + lane; i < hi; i += 64) n += pko_class(a, object, i) == mine ? 1 : 0;
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
+    if (lane == 0) s_n[wave] = n;
+    __syncthreads();
+    int64_t run = s_base;
+    for (int w = 0; w < wave; w++) run += s_n[w];
+    for (int64_t i0 = lo; i0 < hi; i0 += 64) {
+        const int64_t i = i0 + lane;
+        const bool hit = i < hi && pko_class(a, object, i) == mine;
+        const u64 m = __ballot(hit);
+        if (hit) a.table[(size_t)(run + __popcll(m & ((1ull << lane) - 1ull))) * a.C] = (uint32_t)i;
+        run += __popcll(m);
+    }
+}
+
+__global__ __launch_bounds__(256) void map_pack_object_rows_kernel(PkArgs a) {
+    __shared__ int s_part[4];
+    __shared__ uint32_t s_src[PK_ROWS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    {
+        int v = tid < PKO_CLASSES ? a.header[tid] : 0;
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if (lane == 0) s_part[wave] = v;
+    }
+    __syncthreads();
+    const int64_t total = (int64_t)s_part[0] + s_part[1], k0 = (int64_t)blockIdx.x * PK_ROWS;
+    if (k0 >= total) return;
+    const int n = (int)min((int64_t)PK_ROWS, total - k0), C = a.C, K = a.M - 1, M3 = 3 * a.M;
+    if (tid < n) s_src[tid] = a.table[(size_t)(k0 + tid) * C];
+    __syncthreads();
+    for (int r = wave; r < n; r += 4) {
+        const size_t src = s_src[r];
+        uint32_t* out = a.table + (size_t)(k0 + r) * C;
+        for (int c = lane; c < C; c += 64) {
+            uint32_t v;
+            if (c < 3) v = a.xyz[src * 3 + c];
+            else if (c < 6) v = 0u;  // the normals
+            else if (c < 9) v = a.shs[src * M3 + (c - 6)];
+            else if (c < 9 + 3 * K) {
+                const int q = c - 9, ch = q / K, k = q - ch * K + 1;
+                v = a.shs[src * M3 + 3 * k + ch];
+            } else if (c == 9 + 3 * K) v = a.opacity[src];
+            else if (c < 13 + 3 * K) v = a.scaling[src * 3 + (c - 10 - 3 * K)];
+            else if (c < 17 + 3 * K) v = a.rotation[src * 4 + (c - 13 - 3 * K)];
+            else v = a.confidence != nullptr ? a.confidence[src] : 0u;
+            out[c] = v;
+        }
+    }
+}
+
 inline const uint32_t* pk_u32(const float* p) { return reinterpret_cast<const uint32_t*>(p); }
 inline uint32_t* pk_u32(float* p) { return reinterpret_cast<uint32_t*>(p); }
 
@@ -226,6 +328,21 @@ static int dqo_launch_map_pack(int P, int M, int with_conf, const float* xyz, co
     const unsigned tiles = (unsigned)(((int64_t)P + PK_ROWS - 1) / PK_ROWS);
     // (a count block's four quarters: blocks 4 cb .. 4 cb + 3; the last count block may have fewer)
     DQO_LAUNCH_SMEM("map_pack_rows_kernel", map_pack_rows_kernel, dim3(tiles), dim3(256), (size_t)PK_ROWS * a.Cp * 4, s, a);
+    return DQO_OK;
+}
+
+static int dqo_launch_map_pack_by_object(int P, int M, int with_conf, const float* xyz, const float* shs, const float* opacity_raw,
+                                         const float* scaling_raw, const float* rotation_raw, const float* confidence, const uint8_t* alive,
+                                         const uint8_t* stable, const int32_t* object, float* table, int32_t* header, hipStream_t s) {
+    PkArgs a;
+    a.P = P, a.M = M, a.C = 6 + 3 * M + 8 + (with_conf ? 1 : 0), a.Cp = a.C | 1, a.with_conf = with_conf ? 1 : 0;
+    a.xyz = pk_u32(xyz), a.shs = pk_u32(shs), a.opacity = pk_u32(opacity_raw), a.scaling = pk_u32(scaling_raw);
+    a.rotation = pk_u32(rotation_raw), a.confidence = pk_u32(confidence);
+    a.alive = alive, a.stable = stable, a.table = pk_u32(table);
+    a.pairs = nullptr, a.header = header;
+    DQO_LAUNCH("map_pack_object_count_kernel", map_pack_object_count_kernel, dim3(PKO_CLASSES), dim3(64 * PKO_WAVES), s, a, object);
+    DQO_LAUNCH("map_pack_object_order_kernel", map_pack_object_order_kernel, dim3(PKO_CLASSES), dim3(64 * PKO_WAVES), s, a, object);
+    DQO_LAUNCH("map_pack_object_rows_kernel", map_pack_object_rows_kernel, dim3((unsigned)(((int64_t)P + PK_ROWS - 1) / PK_ROWS)), dim3(256), s, a);
     return DQO_OK;
 }
 
@@ -263,6 +380,22 @@ DQO_API int dqo_map_pack_rows(int32_t P, int32_t M, int32_t include_confidence, 
     DQO_CHECK_WS("map pack", ws, ws_bytes, dqo_map_pack_ws_bytes(P));
     return dqo_launch_map_pack(P, M, include_confidence != 0, xyz, shs, opacity_raw, scaling_raw, rotation_raw, confidence, alive, stable, table,
                                header, ws, (hipStream_t)stream);
+}
+
+// save_model_ply_obj (SLAM/gaussian_pointcloud.py:589-637; mapper.py:1586-1588): the vertex tables of every per-object file
+DQO_API int dqo_map_pack_rows_by_object(int32_t P, int32_t M, int32_t include_confidence, const float* xyz, const float* shs,
+                                        const float* opacity_raw, const float* scaling_raw, const float* rotation_raw, const float* confidence,
+                                        const uint8_t* alive, const uint8_t* stable, const int32_t* gaussian_object, float* table,
+                                        int64_t table_rows, int32_t* header, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(P >= 1, "bad row count %d", P);
+    DQO_CHECK_ARG(M >= 1 && M <= 64, "bad SH size M = %d: 1 to 64 coefficients", M);
+    DQO_CHECK_ARG(map_table_size_ok(P, M, include_confidence), "bad size: a table of %d rows exceeds 2^31 - 1 floats", P);
+    DQO_CHECK_ARG(xyz && shs && opacity_raw && scaling_raw && rotation_raw && table && header, "null pointer");
+    DQO_CHECK_ARG(gaussian_object, "null object ids");
+    DQO_CHECK_ARG(table_rows >= (int64_t)P, "table capacity %lld rows is below the map's %d rows", (long long)table_rows, P);
+    DQO_CHECK_WS("map pack", ws, ws_bytes, dqo_map_pack_ws_bytes(P));
+    return dqo_launch_map_pack_by_object(P, M, include_confidence != 0, xyz, shs, opacity_raw, scaling_raw, rotation_raw, confidence, alive, stable,
+                                         gaussian_object, table, header, (hipStream_t)stream);
 }
 
 DQO_API int dqo_map_unpack_rows(int32_t P, int32_t M, int32_t n, int32_t first_row, int32_t has_confidence, const float* table, float* xyz,

@@ -185,6 +185,136 @@ inline PcWorkspace pc_ws(void* base, int n_gt, int n_rec) {
     return w;
 }
 
+// ---- per-object geometry evaluation: eval_pcd's row for each of up to 64 objects (metric_obj.py:169-236) ------------------------------
+// Two dqo_nn1_grouped searches leave, per side, {dist2, object id} of every row in the search's SORTED order (by object, then by Morton
+// code; rows without an object last, id 64): an object's rows are one contiguous run.  Block b of a side takes the sorted rows
+// [1024 b, 1024 b + 1024) and stores one partial per object g it meets, at line b + g of the side's partials — the runs ascend with b, so
+// no two (block, object) pairs share a line, and an object's lines are the contiguous range [first block + g, last block + g].
+// THE ORDER OF EVERY SUM, fixed by the search's sorted order alone: a thread adds its rows (4 b + k) * 256 + tid, k ascending; a wave
+// its lanes by the xor butterfly; a block its four waves in order; the last block (integer ticket, dqo_reduce.h) an object's lines in
+// ascending block order.  No float or double atomic; the arithmetic per row and per table row is eval_pcd_kernel's.
+enum {
+    PCG_OBJECTS = 64,
+};
+
+__global__ __launch_bounds__(256) void eval_pcd_grouped_kernel(int n_rec, const float2* __restrict__ rk_rec, int n_gt,
+                                                               const float2* __restrict__ rk_gt, int n_thres, PcThres thres, int blocks_rec,
+                                                               EvWorkspace w, float* __restrict__ out) {
+    __shared__ double s_stage[PC_STAGE * PC_STRIDE];
+    __shared__ double s_tot[2][PCG_OBJECTS][PC_SUMS];
+    __shared__ int s_first[2][PCG_OBJECTS + 1];  // where object g's run starts in a side's sorted order; [64]: where the rows without one start
+    __shared__ int s_last;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool rec_side = (int)blockIdx.x < blocks_rec;
+    const int n = rec_side ? n_rec : n_gt, block = rec_side ? (int)blockIdx.x : (int)blockIdx.x - blocks_rec;
+    const float2* __restrict__ rk = rec_side ? rk_rec : rk_gt;
+    const int gt_base = blocks_rec + PCG_OBJECTS;  // the first line of the ground truth's partials
+    if ((int64_t)block * (256 * PC_ROWS) < n) {
+        double th2[PC_THRES];
+#pragma unroll
+        for (int t = 0; t < PC_THRES; t++) th2[t] = (double)thres.th[t] * (double)thres.th[t];
+        double v[PC_ROWS];
+        int obj[PC_ROWS];
+#pragma unroll
+        for (int k = 0; k < PC_ROWS; k++) {
+            const int64_t i = ((int64_t)block * PC_ROWS + k) * 256 + tid;
+            const float2 e = i < n ? rk[i] : make_float2(0.f, __int_as_float(PCG_OBJECTS));
+            v[k] = (double)e.x, obj[k] = __float_as_int(e.y);
+        }
+        const int row0 = block * (256 * PC_ROWS), row1 = min(n, row0 + 256 * PC_ROWS) - 1;
+        const int g0 = __float_as_int(rk[row0].y), g1 = min(PCG_OBJECTS - 1, __float_as_int(rk[row1].y));  // (block-uniform)
+        for (int g = g0; g <= g1; g++) {
+            double a[PC_SUMS];
+#pragma unroll
+            for (int q = 0; q < PC_SUMS; q++) a[q] = 0.0;
+#pragma unroll
+            for (int k = 0; k < PC_ROWS; k++)
+                if (obj[k] == g) {
+                    a[0] += sqrt(v[k]);
+                    a[1] += 1.0;
+#pragma unroll
+                    for (int t = 0; t < PC_THRES; t++)
+                        if (t < n_thres && v[k] < th2[t]) a[2 + t] += 1.0;
+                }
+#pragma unroll
+            for (int q = 0; q < PC_SUMS; q++) a[q] = dqo_wave_sum_f64(a[q], lane);
+            if (lane == 0) {
+#pragma unroll
+                for (int q = 0; q < PC_SUMS; q++) s_stage[wave * PC_STRIDE + q] = a[q];
+            }
+            __syncthreads();
+            if (tid < PC_SUMS) {
+                double t = 0.0;
+                for (int u = 0; u < 4; u++) t += s_stage[u * PC_STRIDE + tid];
+                __hip_atomic_store(&w.partial[(size_t)((rec_side ? 0 : gt_base) + block + g) * PC_STRIDE + tid], t, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+            }
+            __syncthreads();
+        }
+    }
+    if (!dqo_last_block(w.ticket, &s_last)) return;
+    if (tid < 2 * (PCG_OBJECTS + 1)) {  // the first sorted row whose object id is not below g
+        const int side = tid / (PCG_OBJECTS + 1), g = tid % (PCG_OBJECTS + 1);
+        const float2* __restrict__ r = side == 0 ? rk_rec : rk_gt;
+        int lo = 0, hi = side == 0 ? n_rec : n_gt;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (__float_as_int(r[mid].y) < g) lo = mid + 1;
+            else hi = mid;
+        }
+        s_first[side][g] = lo;
+    }
+    __syncthreads();
+    for (int side = 0; side < 2; side++)
+        for (int g = 0; g < PCG_OBJECTS; g++) {
+            const int a = s_first[side][g], b = s_first[side][g + 1];  // (block-uniform)
+            double tot = 0.0;
+            if (b > a) {
+                const int base = (side == 0 ? 0 : gt_base) + g;
+                tot = dqo_fold_partials<PC_SUMS, PC_STRIDE, PC_STAGE>(w.partial, base + a / (256 * PC_ROWS), base + (b - 1) / (256 * PC_ROWS) + 1,
+                                                                      s_stage);
+            }
+            if (tid < PC_SUMS) s_tot[side][g][tid] = tot;
+        }
+    __syncthreads();
+    if (tid >= PCG_OBJECTS) return;
+    const float nan = __int_as_float(0x7fc00000);
+    const double* rec = s_tot[0][tid];
+    const double* gt = s_tot[1][tid];
+    float* row = out + (size_t)PC_SLOTS * tid;
+    for (int q = 0; q < PC_SLOTS; q++) row[q] = nan;
+    if (rec[1] == 0.0 || gt[1] == 0.0) return;  // the object has no row on one side: nothing to report
+    const double acc = rec[0] / rec[1], comp = gt[0] / gt[1];
+    row[0] = (float)(100.0 * acc);
+    row[1] = (float)(100.0 * comp);
+    row[2] = (float)(acc + comp);
+    row[3] = (float)n_thres;
+    for (int t = 0; t < n_thres; t++) {
+        const double P = 100.0 * (rec[2 + t] / rec[1]), R = 100.0 * (gt[2 + t] / gt[1]);
+        row[4 + 3 * t] = (float)P;
+        row[5 + 3 * t] = (float)R;
+        row[6 + 3 * t] = (float)(2.0 * P * R / (P + R));
+    }
+}
+
+struct PcgWorkspace {
+    EvWorkspace ev;
+    float2 *rk_rec, *rk_gt;  // {dist2, object id} in the searches' sorted order
+    void* nn1;
+    size_t total;
+};
+inline PcgWorkspace pcg_ws(void* base, int n_gt, int n_rec) {
+    PcgWorkspace w;
+    char* p = (char*)base;
+    w.ev.ticket = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
+    w.ev.partial = (double*)p, p += dqo_align_up((pc_blocks(n_rec) + pc_blocks(n_gt) + 2 * PCG_OBJECTS) * PC_STRIDE * sizeof(double), 256);
+    w.rk_rec = (float2*)p, p += dqo_align_up(8 * (size_t)n_rec, 256);
+    w.rk_gt = (float2*)p, p += dqo_align_up(8 * (size_t)n_gt, 256);
+    w.nn1 = p, p += std::max(dqo_nn1_ws_bytes(n_rec, n_gt), dqo_nn1_ws_bytes(n_gt, n_rec));
+    w.total = (size_t)(p - (char*)base);
+    return w;
+}
+
 }  // namespace
 
 static size_t dqo_eval_ws_bytes(int64_t HW) { return DQO_REDUCE_HEAD_WORDS * 4 + dqo_align_up(ev_blocks(HW) * EV_STRIDE * sizeof(double), 256); }
@@ -216,6 +346,25 @@ static int dqo_launch_eval_pcd(int n_gt, const float* gt_xyz, const uint8_t* gt_
     const int blocks_rec = (int)pc_blocks(n_rec), blocks = std::max(1, blocks_rec + (int)pc_blocks(n_gt));  // (two empty sets: one block writes the NaN row)
     DQO_LAUNCH("eval_pcd_kernel", eval_pcd_kernel, dim3((unsigned)blocks), dim3(256), s, n_rec, w.d2_rec, rec_keep, n_gt, w.d2_gt, gt_keep, n_thres,
                th, blocks_rec, w.ev, out_row);
+    return DQO_OK;
+}
+
+static int dqo_launch_eval_pcd_grouped(int n_gt, const float* gt_xyz, const int32_t* gt_group, int n_rec, const float* rec_xyz,
+                                       const int32_t* rec_group, const float* rec_xform, int n_thres, const float* thres, float* out_rows, void* ws,
+                                       hipStream_t s) {
+    const PcgWorkspace w = pcg_ws(ws, n_gt, n_rec);
+    if (n_gt == 0 || n_rec == 0) n_gt = n_rec = 0;  // an empty set: no object has rows on both sides — one block writes the 64 NaN rows
+    if (n_rec > 0) {
+        int rc = dqo_launch_nn1_grouped(n_rec, rec_xyz, rec_group, n_gt, gt_xyz, gt_group, rec_xform, nullptr, nullptr, nullptr, w.rk_rec, w.nn1, s);
+        if (rc) return rc;
+        rc = dqo_launch_nn1_grouped(n_gt, gt_xyz, gt_group, n_rec, rec_xyz, rec_group, nullptr, rec_xform, nullptr, nullptr, w.rk_gt, w.nn1, s);
+        if (rc) return rc;
+    }
+    PcThres th;
+    for (int t = 0; t < PC_THRES; t++) th.th[t] = t < n_thres ? thres[t] : 0.f;
+    const int blocks_rec = (int)pc_blocks(n_rec), blocks = std::max(1, blocks_rec + (int)pc_blocks(n_gt));
+    DQO_LAUNCH("eval_pcd_grouped_kernel", eval_pcd_grouped_kernel, dim3((unsigned)blocks), dim3(256), s, n_rec, w.rk_rec, n_gt, w.rk_gt, n_thres, th,
+               blocks_rec, w.ev, out_rows);
     return DQO_OK;
 }
 
@@ -253,6 +402,25 @@ DQO_API int dqo_eval_pcd(int32_t n_gt, const float* gt_xyz, const uint8_t* gt_ke
     DQO_CHECK_WS("eval_pcd", ws, ws_bytes, dqo_eval_pcd_ws_bytes(n_gt, n_rec));
     return dqo_launch_eval_pcd(n_gt, gt_xyz, gt_keep, n_rec, rec_xyz, rec_keep, rec_xform, n_thres, thres_host, out_table + (size_t)32 * row, ws,
                                (hipStream_t)stream);
+}
+
+// metric_obj.py:169-236: eval_pcd of every object's cloud against its own ground truth — one row per object id
+DQO_API size_t dqo_eval_pcd_grouped_workspace_bytes(int32_t n_gt, int32_t n_rec) {
+    return dqo_nn1_size_ok(n_gt) && dqo_nn1_size_ok(n_rec) ? pcg_ws(nullptr, n_gt, n_rec).total : 0;
+}
+
+DQO_API int dqo_eval_pcd_grouped(int32_t n_gt, const float* gt_xyz, const int32_t* gt_group, int32_t n_rec, const float* rec_xyz,
+                                 const int32_t* rec_group, const float* rec_xform, int32_t n_thres, const float* thres_host, float* out_table,
+                                 int64_t table_rows, int64_t first_row, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(dqo_nn1_size_ok(n_gt) && dqo_nn1_size_ok(n_rec), "bad size: at most 2^25 - 1 rows per set");
+    DQO_CHECK_ARG((n_gt == 0 || gt_xyz) && (n_rec == 0 || rec_xyz) && out_table, "null pointer");
+    DQO_CHECK_ARG((n_gt == 0 || gt_group) && (n_rec == 0 || rec_group), "null group ids");
+    DQO_CHECK_ARG(n_thres >= 0 && n_thres <= 8 && (n_thres == 0 || thres_host), "at most 8 thresholds (got %d)", n_thres);
+    DQO_CHECK_ARG(first_row >= 0 && first_row <= table_rows - 64, "bad rows: [%lld, %lld + 64) of a table of %lld", (long long)first_row,
+                  (long long)first_row, (long long)table_rows);
+    DQO_CHECK_WS("eval_pcd grouped", ws, ws_bytes, pcg_ws(nullptr, n_gt, n_rec).total);
+    return dqo_launch_eval_pcd_grouped(n_gt, gt_xyz, gt_group, n_rec, rec_xyz, rec_group, rec_xform, n_thres, thres_host,
+                                       out_table + (size_t)32 * first_row, ws, (hipStream_t)stream);
 }
 
 }  // extern "C"

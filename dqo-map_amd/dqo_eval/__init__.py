@@ -54,6 +54,19 @@ their cumulative sum, one draw located in it, two draws folded back into the tri
 arguments: the draws are the key rule of csrc/dqo_sample_hash.h instead of numpy's stream (the same distribution), and the cumulative
 table counts integer quanta of area instead of float sums (no summation order can reach it).
 
+The geometry number the reference reports PER OBJECT — metric_obj.py:169-236: eval_pcd of each object's stable cloud against that
+object's own mesh, dist_threshs=[0.01] — is one call for up to 64 objects, an integer object id per row on both sides:
+
+    nearest_grouped(query, query_group, ref, ref_group)     ->  (dist2, idx): the nearest reference OF THE QUERY'S OWN GROUP
+    eval_pcd_objects(gt_points, gt_object, rec_points, rec_object, dist_thres)  ->  float32 [64,32] on the device, a PCD_ROW per object
+    eval_pcd_objects_dict(table, dist_thres)                ->  {object id: eval_pcd_dict's dict} (the ONE host read)
+    sample_surface_objects(meshes, count, seed)             ->  (points, object): sample_surface of every object's mesh
+
+One build of the reference set, one sort of the queries (by object, then along the Morton grid) and one scan per direction
+(dqo_nn1_grouped, csrc/knn.hip), one reduction launch (dqo_eval_pcd_grouped, csrc/map_eval.hip) — instead of one masked eval_pcd per
+object, each of which sorts and scans every row of both sets.  Not built: metric_obj.py's hard-coded mesh paths and id -> name table,
+its CSV, and the per-frame picture half of its loop (FusedMapper.evaluate serves that).
+
 What is NOT here: writing `pcd_densify.ply` (open3d's layout) is not built; the unused bounding box of eval.py:237-239 is not formed.
 
 Tracking evaluation — Tracker.eval_total_ate, SLAM/multiprocess/tracker.py:341-346, 426-430: the absolute trajectory error after Horn's
@@ -286,6 +299,45 @@ def nearest(query, ref, query_keep=None, ref_keep=None, query_transform=None, re
     return dist2, idx
 
 
+OBJECTS = 64  # object ids of a grouped call: [0, OBJECTS); any other id = the row has no object
+
+
+def _group(t, n, dev, name):
+    """One object id per row as a contiguous int32 [n] tensor on the device (an int32 tensor goes in as it is)."""
+    if not torch.is_tensor(t) or t.numel() != n or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise RuntimeError(f"dqo_eval: {name} must be an integer tensor with one object id for each of the {n} rows")
+    if t.numel() > 0 and t.device != dev:
+        raise RuntimeError(f"dqo_eval: {name} must be on {dev}")
+    return t.reshape(-1).to(torch.int32).contiguous()
+
+
+def nearest_grouped(query, query_group, ref, ref_group, query_transform=None, ref_transform=None, want_idx=True, workspace_buffer=None):
+    """nearest() for up to 64 objects in one search (dqo_nn1_grouped): query [Q,3] with query_group [Q], ref [R,3] with ref_group [R] ->
+    (dist2 float32 [Q], idx int32 [Q] or None).  A group id in [0, 64) is the row's object, any other value (-1, 64, ...) means the row
+    has none and takes no part on either side.  dist2 is the smallest float32 dx*dx + dy*dy + dz*dz over the references of the query's
+    own group, idx one of them attaining it; FLT_MAX / -1 for a query without a group or whose group has no reference.  Bit for bit
+    nearest() with query_keep = (query_group == g) and ref_keep = (ref_group == g), for every g — from one build of the reference set,
+    one sort of the queries and one scan.  Transforms, workspace (dqo_nn1_grouped_workspace_bytes(Q, R)) and contract as nearest():
+    no host read, no synchronisation."""
+    N.require_gpu_op((query, ref), query_group, ref_group)
+    lib, dev = N.lib(), query.device
+    query, ref = _points(query, "query"), _points(ref, "ref")
+    Q, R = int(query.shape[0]), int(ref.shape[0])
+    qg, rg = _group(query_group, Q, dev, "query_group"), _group(ref_group, R, dev, "ref_group")
+    qx, rx = _xform(query_transform, dev, "query_transform"), _xform(ref_transform, dev, "ref_transform")
+    n = lib.dqo_nn1_grouped_workspace_bytes(Q, R)
+    if n == 0:
+        raise RuntimeError(f"dqo_eval.nearest_grouped: bad sizes {Q}, {R} (at most 2^25 - 1 rows per set)")
+    ws = workspace_buffer if workspace_buffer is not None else _workspace(("nn1", _dev_index(dev), Q, R), n, dev)
+    dist2 = torch.empty((Q,), dtype=torch.float32, device=dev)
+    idx = torch.empty((Q,), dtype=torch.int32, device=dev) if want_idx else None
+    if Q > 0:  # (the C entry wants the ids even when R = 0; an empty tensor has no pointer)
+        with torch.cuda.device(dev):
+            N.check(lib.dqo_nn1_grouped(Q, N.ptr(query), N.ptr(qg), R, N.ptr(ref), N.ptr(rg), N.ptr(qx), N.ptr(rx), N.ptr(dist2), N.ptr(idx),
+                                        ws.data_ptr(), ws.numel(), N.current_stream()))
+    return dist2, idx
+
+
 DENSIFY_HEADER = ("kept_rows", "N_lo", "N_hi", "n", "M", "threshold_key", "frame", "zero")
 DENSIFY_FRAMES = {"reference": 0, "surfel": 1}
 
@@ -472,6 +524,89 @@ def eval_pcd_dict(row_tensor, dist_thres=(0.03,)):
             results["{} (< {})".format(name, th)] = v[off + 3 * t]
     results["chamfer"] = v[2]
     return results
+
+
+def pcd_objects_workspace(n_gt, n_rec, device):
+    """dqo_eval_pcd_grouped's workspace for these sizes as a uint8 tensor (zero when first used, handed back ready by every call)."""
+    n = N.lib().dqo_eval_pcd_grouped_workspace_bytes(int(n_gt), int(n_rec))
+    if n == 0:
+        raise RuntimeError(f"dqo_eval: bad point counts {n_gt}, {n_rec} (at most 2^25 - 1 rows per set)")
+    return torch.zeros((n,), dtype=torch.uint8, device=device)
+
+
+def eval_pcd_objects(gt_points, gt_object, rec_points, rec_object, dist_thres=(0.01,), transform=None, out=None, row=0, workspace_buffer=None):
+    """The per-object geometry numbers of the reference (metric_obj.py:169-236: eval_pcd of every object's stable cloud against that
+    object's own ground-truth mesh, dist_threshs=[0.01]) for up to 64 objects in one call (dqo_eval_pcd_grouped): two grouped searches
+    and one reduction launch, instead of one eval_pcd with keep masks per object.
+
+    gt_points [G,3] with gt_object [G], rec_points [P,3] with rec_object [P]: an integer id per row, [0, 64) = the row's object, any
+    other value (-1, 64, ...) = none, the row takes no part; transform: applied to rec_points; dist_thres: up to 8 distances in metres.
+    Returns a float32 [64,32] device table — row g is eval_pcd's row (PCD_ROW) of object g's rows on both sides, 32 NaN for an object
+    without a row on either side — a new tensor, or rows [row, row + 64) of a caller-owned contiguous float32 [K,32] table, whose other
+    rows are not touched.  Nothing is read back, the call does not synchronise and can be captured in a graph; a table is bitwise
+    reproducible.  eval_pcd_objects_dict does the single host read.
+
+    workspace_buffer: a tensor of pcd_objects_workspace(G, P, device) the caller keeps (default: one per device and sizes, kept by this
+    module — calls that share it must be on one stream).  GPU tensors only: a CPU tensor raises RuntimeError."""
+    N.require_gpu_op((gt_points, rec_points), gt_object, rec_object, out)
+    lib, dev = N.lib(), rec_points.device
+    gt, rec = _points(gt_points, "gt_points"), _points(rec_points, "rec_points")
+    G, P = int(gt.shape[0]), int(rec.shape[0])
+    gg, rg = _group(gt_object, G, dev, "gt_object"), _group(rec_object, P, dev, "rec_object")
+    xf = _xform(transform, dev, "transform")
+    thres = [float(t) for t in dist_thres]
+    if len(thres) > PCD_THRES_MAX:
+        raise RuntimeError(f"dqo_eval.eval_pcd_objects: at most {PCD_THRES_MAX} thresholds, got {len(thres)}")
+    if out is None:
+        out, row = torch.empty((OBJECTS, 32), dtype=torch.float32, device=dev), 0
+    if (out.dim() != 2 or out.shape[1] != 32 or out.dtype != torch.float32 or not out.is_contiguous()
+            or not 0 <= int(row) <= out.shape[0] - OBJECTS):
+        raise RuntimeError(f"dqo_eval.eval_pcd_objects: out must be a contiguous float32 [K,32] table and [row, row + {OBJECTS}) rows of it")
+    if workspace_buffer is not None:
+        ws = workspace_buffer
+    else:
+        n = lib.dqo_eval_pcd_grouped_workspace_bytes(G, P)
+        if n == 0:
+            raise RuntimeError(f"dqo_eval: bad point counts {G}, {P} (at most 2^25 - 1 rows per set)")
+        ws = _workspace(("pcd_objects", _dev_index(dev), G, P), n, dev)
+    with torch.cuda.device(dev):
+        N.check(lib.dqo_eval_pcd_grouped(G, N.ptr(gt), N.ptr(gg), P, N.ptr(rec), N.ptr(rg), N.ptr(xf), len(thres),
+                                         (ctypes.c_float * len(thres))(*thres), out.data_ptr(), int(out.shape[0]), int(row), ws.data_ptr(),
+                                         ws.numel(), N.current_stream()))
+    return out[int(row):int(row) + OBJECTS]
+
+
+def eval_pcd_objects_dict(table, dist_thres=(0.01,)):
+    """{object id: eval_pcd_dict's dict} from eval_pcd_objects' [64,32] table, for the rows that are not all NaN (the objects with rows on
+    both sides), ids ascending — ONE host read."""
+    if tuple(table.shape) != (OBJECTS, 32):
+        raise RuntimeError(f"dqo_eval.eval_pcd_objects_dict: a [{OBJECTS},32] table, got {tuple(table.shape)}")
+    host = table.detach().to("cpu", torch.float32)
+    return {g: eval_pcd_dict(host[g], dist_thres) for g in range(OBJECTS) if not bool(torch.isnan(host[g]).all())}
+
+
+def object_seed(seed, obj):
+    """The seed of object `obj`'s draw in sample_surface_objects: (seed + 0x9E3779B97F4A7C15 * (obj + 1)) mod 2^64 — a different stream
+    per object, a pure function of the two."""
+    return (int(seed) + 0x9E3779B97F4A7C15 * (int(obj) + 1)) & (2 ** 64 - 1)
+
+
+def sample_surface_objects(meshes, count, seed=0):
+    """The ground truth of the per-object evaluation: `count` points on the surface of every object's mesh (metric_obj.py evaluates each
+    object against its own mesh with sample_nums points).  meshes = {object id in [0, 64): (vertices [V,3] float32, faces [F,3] int32)},
+    device tensors.  Returns (points float32 [n,3], object int32 [n]), n = count * len(meshes), ids ascending: each object's part is
+    exactly sample_surface(vertices, faces, count, seed=object_seed(seed, id))["points"], and the rows its `keep` drops (a mesh without
+    area) get object -1 — eval_pcd_objects' gt_points / gt_object.  Nothing is read back."""
+    ids = sorted(int(g) for g in meshes)
+    if not ids or ids[0] < 0 or ids[-1] >= OBJECTS:
+        raise RuntimeError(f"dqo_eval.sample_surface_objects: object ids must be in [0, {OBJECTS}), got {ids}")
+    points, objects = [], []
+    for g in ids:
+        v, f = meshes[g]
+        s = sample_surface(v, f, count, seed=object_seed(seed, g))
+        points.append(s["points"])
+        objects.append(torch.where(s["keep"] != 0, g, -1).to(torch.int32))
+    return torch.cat(points), torch.cat(objects)
 
 
 def _positions(t, name):

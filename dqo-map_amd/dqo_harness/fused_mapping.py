@@ -251,6 +251,7 @@ class FusedMapper:
         self._prune_ctx = None  # prune_floaters(): its camera tables, workspace and stats, made anew when P changes
         self._eval_tables, self._eval_ws = {}, None  # evaluate(): its [K,8] table per K, and dqo_eval's workspace
         self._eval_ms_ws = None  # evaluate_ms_ssim(): dqo_eval.ms_ssim's workspace
+        self._eval_object_rows = None  # evaluate_geometry_objects(): its int32 [P] group column (gaussian_object, -1 = the row is left out)
         self._checkpoint = {}  # pack_rows() / save_model(): workspace, header, table and pinned staging buffer, made anew when P changes
         # refresh_window(): its [K] ratio table per K, dqo_window_masks' workspace, the uint8 [P] row flags of its render (per P)
         self._window_ratios, self._window_ws, self._window_flags = {}, None, None
@@ -917,6 +918,60 @@ class FusedMapper:
             rec, rec_keep = d["points"], d["keep"]
         return dqo_eval.eval_pcd(gt["points"], rec, dist_thres, transform, gt_keep=gt["keep"], rec_keep=rec_keep, out=out, row=row)
 
+    def _object_rows(self, rows, who):
+        """int32 [P], a buffer of this mapper's own: gaussian_object where the row is alive and in `rows`, -1 elsewhere — the group
+        column of the per-object evaluation.  Nothing is gathered: the map's buffers go in as stored."""
+        if self.attach_count_reducer is not None:
+            raise NotImplementedError(f"FusedMapper.{who}: a sharded mapper holds its own objects only; merging shards is not built (DESIGN.md §6)")
+        if self.gaussian_object is None:
+            raise RuntimeError(f"FusedMapper.{who}: this mapper has no object ids; call set_object_gate() first")
+        if isinstance(rows, str):
+            if rows == "stable":
+                self._require_lifecycle(who)
+                take = self.stable_rows()
+            elif rows == "all":
+                take = None if self.alive is None else self.alive != 0
+            else:
+                raise RuntimeError(f"FusedMapper.{who}: rows must be 'stable', 'all' or a mask of {self.P} rows, got {rows!r}")
+        else:
+            if not torch.is_tensor(rows) or rows.numel() != self.P or rows.dtype not in (torch.bool, torch.uint8) or rows.device != self.xyz.device:
+                raise RuntimeError(f"FusedMapper.{who}: rows must be 'stable', 'all' or a uint8 / bool device mask of {self.P} rows")
+            take = rows.reshape(-1) != 0
+            if self.alive is not None:
+                take = take & (self.alive != 0)
+        col = self._eval_object_rows
+        if col is None or col.numel() != self.P:
+            col = self._eval_object_rows = torch.empty((self.P,), dtype=torch.int32, device=self.device)
+        col.copy_(self.gaussian_object)
+        if take is not None:
+            col.masked_fill_(~take, -1)
+        return col
+
+    @torch.no_grad()
+    def evaluate_geometry_objects(self, gt_points, gt_object, dist_thres=(0.01,), transform=None, rows="stable", out=None, row=0):
+        """The map's geometry PER OBJECT: what metric_obj.py:169-236 reports from the `*_stable_obj{id}.ply` files, without the files —
+        dqo_eval.eval_pcd_objects of this mapper's own `xyz` with its `gaussian_object` column against gt_points [G,3] / gt_object [G]
+        (from meshes: evaluate_geometry_objects_mesh).  rows "stable": the alive rows of the stable cloud (what metric_obj.py loads;
+        needs track_lifecycle()); "all": every alive row; or a uint8 / bool [P] mask (alive rows of it).  The restriction is written as -1
+        into a group column this mapper keeps: no row is gathered, nothing is read back.  Returns the float32 [64,32] device table (rows
+        [row, row + 64) of `out` if given); dqo_eval.eval_pcd_objects_dict reads it.  RuntimeError without an object gate
+        (set_object_gate), and without track_lifecycle() for rows="stable"; NotImplementedError on a sharded mapper."""
+        import dqo_eval
+        col = self._object_rows(rows, "evaluate_geometry_objects")
+        return dqo_eval.eval_pcd_objects(gt_points, gt_object, self.xyz.detach(), col, dist_thres, transform, out=out, row=row)
+
+    @torch.no_grad()
+    def evaluate_geometry_objects_mesh(self, meshes, sample_nums=1000000, seed=0, dist_thres=(0.01,), transform=None, rows="stable", out=None,
+                                       row=0):
+        """evaluate_geometry_objects from the objects' ground-truth MESHES, meshes = {object id: (vertices [V,3] float32, faces [F,3]
+        int32)} as device tensors: sample_nums points are drawn on every mesh (dqo_eval.sample_surface_objects, metric_obj.py's
+        sample_nums=1000000 per object) and the map is evaluated against them — one chain on the current stream from the mesh tensors
+        to the [64,32] table, no host read."""
+        import dqo_eval
+        col = self._object_rows(rows, "evaluate_geometry_objects_mesh")  # (the checks first: no sample is drawn for a refused call)
+        gt, gt_object = dqo_eval.sample_surface_objects(meshes, sample_nums, seed=seed)
+        return dqo_eval.eval_pcd_objects(gt, gt_object, self.xyz.detach(), col, dist_thres, transform, out=out, row=row)
+
     # ------------------------------------------------------------------ checkpoints (csrc/map_checkpoint.hip) -----------
     @torch.no_grad()
     def pack_rows(self, include_confidence=True, out=None):
@@ -949,8 +1004,8 @@ class FusedMapper:
         into a pinned staging buffer this mapper keeps, and every file is written from a slice of that buffer (the merged file is the
         table itself: nothing is re-read).  It runs on the current stream, behind whatever replays are enqueued, and synchronises once
         per column set; the first set's copy takes all P rows (the counts are not known yet), the second the U + S live rows.
-        Returns {file: rows} of the files written.  Not built: save_model_ply_obj (SAVE_obj_ply is False in the reference); a sharded
-        mapper saves its shard."""
+        Returns {file: rows} of the files written.  The per-object files of save_model_ply_obj (SAVE_obj_ply, mapper.py:1586-1588) are
+        save_model_objects(); a sharded mapper saves its shard."""
         import dqo_ply
         P, M = self.P, self.M
         written, counts = {}, None
@@ -976,6 +1031,44 @@ class FusedMapper:
             for name, part in files:
                 if dqo_ply.write_vertex_table(name, part, 3 * (M - 1), with_conf) > 0:
                     written[name] = int(part.shape[0])
+        return written
+
+    @torch.no_grad()
+    def save_model_objects(self, path):
+        """The per-object files gaussian_map.save_model writes with SAVE_obj_ply (mapper.py:1586-1588: save_model_ply_obj,
+        SLAM/gaussian_pointcloud.py:589-637, of both clouds) — path_obj{id}.ply for the unstable cloud, path_stable_obj{id}.ply for the
+        stable one (what metric_obj.py loads), WITHOUT the confidence column, one file per object a cloud has rows of (ids in [0, 64),
+        set_object_gate's; a row with another id is in no file).  ONE pack (dqo_ply.pack_rows_by_object), one device-to-host copy into
+        save_model's pinned staging buffer, every file a slice of it; one synchronisation.  Returns {file: rows} of the files written.
+        A method of its own so that save_model's files, signature and return value stay what they are; a sharded mapper saves its shard."""
+        import dqo_ply
+        if self.gaussian_object is None:
+            raise RuntimeError("FusedMapper.save_model_objects: the files need the Gaussians' object ids; call set_object_gate() first")
+        P, M = self.P, self.M
+        C = 6 + 3 * M + 8
+        k = self._checkpoint
+        if k.get("P") != P:
+            k = self._checkpoint = dict(P=P, ws=dqo_ply.pack_workspace(P, self.device),
+                                        header=torch.empty((2,), dtype=torch.int32, device=self.device))
+        if "buf" not in k:
+            k["buf"] = torch.empty((P * (6 + 3 * M + 9),), dtype=torch.float32, device=self.device)
+        if "host" not in k:
+            k["host"] = torch.empty((P * (6 + 3 * M + 9),), dtype=torch.float32, pin_memory=True)
+            k["host_header"] = torch.empty((2,), dtype=torch.int32, pin_memory=True)
+        if "obj_header" not in k:
+            k["obj_header"] = torch.empty((2, 64), dtype=torch.int32, device=self.device)
+            k["host_obj_header"] = torch.empty((2, 64), dtype=torch.int32, pin_memory=True)
+        table, header = dqo_ply.pack_rows_by_object(self.xyz, self.shs, self.opacity_raw, self.scaling_raw, self.rotation_raw,
+                                                    self.gaussian_object, None, self.alive, self.stable, False,
+                                                    out=k["buf"][:P * C].view(P, C), header=k["obj_header"], workspace_buffer=k["ws"])
+        k["host"][:P * C].copy_(table.view(-1), non_blocking=True)  # (all P rows: the counts are not known yet)
+        k["host_obj_header"].copy_(header, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        written = {}
+        for name, first, rows in dqo_ply.object_file_slices(path, k["host_obj_header"].numpy()):
+            part = k["host"][first * C:(first + rows) * C].view(rows, C)
+            if dqo_ply.write_vertex_table(name, part, 3 * (M - 1), False) > 0:
+                written[name] = rows
         return written
 
     @staticmethod

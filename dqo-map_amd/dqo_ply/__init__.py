@@ -110,6 +110,60 @@ def pack_rows(xyz, shs, opacity_raw, scaling_raw, rotation_raw, confidence=None,
     return out, header
 
 
+def pack_rows_by_object(xyz, shs, opacity_raw, scaling_raw, rotation_raw, gaussian_object, confidence=None, alive=None, stable=None,
+                        include_confidence=False, out=None, header=None, workspace_buffer=None):
+    """(table, header): the vertex data of every per-object file of save_model_ply_obj in one table, on the device
+    (dqo_map_pack_rows_by_object, include/dqo_raster.h).  Buffers as pack_rows'; gaussian_object int32 [P], an id in [0, 64) = the row's
+    object.  table float32 [P, C] (`out`, or new): the alive rows that have an object, ordered by (stable != 0, object id, row index);
+    rows at and behind the total keep their bytes.  header int32 [2,64]: header[c, g] = the rows of cloud c (0 unstable, 1 stable),
+    object g — object_file_slices turns its host copy into file names and slices.  include_confidence defaults to False, as
+    mapper.py:1587-1588 passes.  Nothing is read back."""
+    import torch
+    import _dqo_native as N
+    N.require_gpu(xyz, shs, opacity_raw, scaling_raw, rotation_raw, gaussian_object, confidence, alive, stable, out, header, workspace_buffer)
+    P, M = int(xyz.shape[0]), int(shs.shape[1])
+    C = 6 + 3 * M + 8 + (1 if include_confidence else 0)
+    for t, n, dt in ((xyz, 3 * P, torch.float32), (shs, 3 * M * P, torch.float32), (opacity_raw, P, torch.float32),
+                     (scaling_raw, 3 * P, torch.float32), (rotation_raw, 4 * P, torch.float32), (confidence, P, torch.float32),
+                     (alive, P, torch.uint8), (stable, P, torch.uint8), (gaussian_object, P, torch.int32)):
+        if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous()):
+            raise RuntimeError(f"pack_rows_by_object: every buffer is contiguous, of the map's {P} rows and of its own type (got {t.dtype} "
+                               f"{tuple(t.shape)})")
+    dev = xyz.device
+    if out is None:
+        out = torch.empty((P, C), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[1] != C or not out.is_contiguous():
+        raise RuntimeError(f"pack_rows_by_object: out must be a contiguous float32 [rows, {C}] table")
+    if header is None:
+        header = torch.empty((2, 64), dtype=torch.int32, device=dev)
+    elif header.dtype != torch.int32 or header.numel() != 128 or not header.is_contiguous():
+        raise RuntimeError("pack_rows_by_object: header must be a contiguous int32 [2,64] tensor")
+    if workspace_buffer is None:
+        workspace_buffer = pack_workspace(P, dev)
+    with torch.cuda.device(dev):
+        N.check(N.lib().dqo_map_pack_rows_by_object(P, M, 1 if include_confidence else 0, N.ptr(xyz), N.ptr(shs), N.ptr(opacity_raw),
+                                                    N.ptr(scaling_raw), N.ptr(rotation_raw), N.ptr(confidence), N.ptr(alive), N.ptr(stable),
+                                                    N.ptr(gaussian_object), N.ptr(out), int(out.shape[0]), N.ptr(header),
+                                                    N.ptr(workspace_buffer), workspace_buffer.numel(), N.current_stream()))
+    return out, header
+
+
+def object_file_slices(path, header):
+    """[(file name, first table row, rows)] of the per-object files of a map saved under the prefix `path`, from the HOST copy of
+    pack_rows_by_object's header ([2][64] counts, any nesting numpy can flatten): the reference's names — path + "_obj" +
+    "{}.ply".format(id) for the unstable cloud, path + "_stable_obj" + ... for the stable one (mapper.py:1587-1588,
+    gaussian_pointcloud.py:637) — in table order, only for the objects a cloud has rows of (np.unique, :593)."""
+    counts = np.asarray(header, np.int64).reshape(2, 64)
+    files, first = [], 0
+    for c, tag in ((0, "_obj"), (1, "_stable_obj")):
+        for g in range(64):
+            n = int(counts[c, g])
+            if n > 0:
+                files.append((path + tag + "{}.ply".format(g), first, n))
+            first += n
+    return files
+
+
 def unpack_rows(table, first_row, xyz, shs, opacity_raw, scaling_raw, rotation_raw, confidence=None):
     """The inverse (dqo_map_unpack_rows): the rows of `table` (float32 [n, C] on the device, with or without the confidence column) into
     rows [first_row, first_row + n) of the buffers; a table without the column writes zeros into `confidence`."""

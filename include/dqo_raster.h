@@ -580,6 +580,23 @@ int dqo_nn1(int32_t Q, const float* query_xyz, const uint8_t* query_keep, int32_
             const float* query_xform, const float* ref_xform, float* dist2, int32_t* idx, void* workspace, size_t workspace_bytes,
             void* hipStream);
 
+/* dqo_nn1_grouped (ABI 5, symbols-only addition) — dqo_nn1 for every object at once: the searches behind metric_obj.py:169-236, which
+ * loads each object's cloud and evaluates it against that object's own mesh (one KDTree build and query per object, direction and
+ * statement).  A group id is an int32 per row: an id in [0, 64) is the row's object, any other value (-1, 64, ...) means "no object" and
+ * the row takes no part on either side — the limit of the object gate's 64 ids and of the 64-bit group sets of the pruning records.
+ * dist2[i] = the minimum of dqo_nn1's float expression over the references whose group equals query i's, idx[i] (may be NULL) a reference
+ * of that group attaining it; FLT_MAX / -1 for a query without a group or whose group has no reference (or R = 0).  A pure function of
+ * the inputs: bit for bit what dqo_nn1 returns with query_keep = (query_group == g) and ref_keep = (ref_group == g), for every g.
+ * One build of the reference set (points and records carry their groups), one sort of the queries (by group, then by Morton code on the
+ * reference's grid) and one scan launch serve every object; a record is opened only for lanes of a group it holds.
+ * query_xform / ref_xform, the row limit (dqo_nn1_grouped_workspace_bytes: 0 beyond 2^25 - 1 rows; the bytes are dqo_nn1_workspace_bytes')
+ * and the contract — no allocation, no synchronisation, nothing read back, capturable, the workspace needs no initialisation — are
+ * dqo_nn1's. */
+size_t dqo_nn1_grouped_workspace_bytes(int32_t Q, int32_t R);
+int dqo_nn1_grouped(int32_t Q, const float* query_xyz, const int32_t* query_group, int32_t R, const float* ref_xyz, const int32_t* ref_group,
+                    const float* query_xform, const float* ref_xform, float* dist2, int32_t* idx, void* workspace, size_t workspace_bytes,
+                    void* hipStream);
+
 /* Geometry evaluation: the metrics eval_pcd reports for a reconstruction against a ground-truth point set (SLAM/eval.py:190-282), nothing
  * read back.  Two dqo_nn1 searches (rec -> gt under rec_xform, gt -> rec) and one reduction launch replace the 4 + 2 T KDTree builds and
  * queries of the reference:
@@ -599,6 +616,20 @@ size_t dqo_eval_pcd_workspace_bytes(int32_t n_gt, int32_t n_rec);
 int dqo_eval_pcd(int32_t n_gt, const float* gt_xyz, const uint8_t* gt_keep, int32_t n_rec, const float* rec_xyz, const uint8_t* rec_keep,
                  const float* rec_xform, int32_t n_thres, const float* thres_host, float* out_table, int32_t row, void* workspace,
                  size_t workspace_bytes, void* hipStream);
+
+/* dqo_eval_pcd_grouped (ABI 5, symbols-only addition) — the per-object geometry numbers of metric_obj.py:169-236: for every object id its
+ * stable cloud is evaluated against that object's own ground truth with eval_pcd(..., dist_threshs=[0.01], sample_nums=1000000).  Two
+ * dqo_nn1_grouped searches (rec -> gt under rec_xform, gt -> rec) and one reduction launch write a [64,32] table: row first_row + g of
+ * out_table is dqo_eval_pcd's row for object g — the same arithmetic per row (sqrt((double)dist2), (double)dist2 < (double)th * (double)th,
+ * means and shares in double over the object's rows, rounded once; slot 3 = n_thres, unused slots NaN, P + R = 0 gives NaN).  An object
+ * without a row on either side gets 32 NaN.  All 64 rows are written by every call, no row outside [first_row, first_row + 64) is
+ * touched (table_rows: the rows out_table holds).  gt_group / rec_group: dqo_nn1_grouped's ids, any value outside [0, 64) = no object.
+ * Bitwise reproducible: no float or double atomic; every double sum is added in an order fixed by the search's sorted order of the rows
+ * (csrc/map_eval.hip states it).  thres_host and the workspace contract are dqo_eval_pcd's: ZERO when first used, handed back ready. */
+size_t dqo_eval_pcd_grouped_workspace_bytes(int32_t n_gt, int32_t n_rec);
+int dqo_eval_pcd_grouped(int32_t n_gt, const float* gt_xyz, const int32_t* gt_group, int32_t n_rec, const float* rec_xyz,
+                         const int32_t* rec_group, const float* rec_xform, int32_t n_thres, const float* thres_host, float* out_table,
+                         int64_t table_rows, int64_t first_row, void* workspace, size_t workspace_bytes, void* hipStream);
 
 /* dqo_surfel_densify (ABI 5, symbols-only addition) — the point set the reference evaluates its geometry on where a config sets
  * pcd_densify: GaussianPointCloud.densify(sigma, circle_num, levels) (SLAM/gaussian_pointcloud.py:67-130; slam.py:202-206 calls
@@ -887,6 +918,24 @@ int dqo_map_pack_rows(int32_t P, int32_t M, int32_t include_confidence, const fl
                       void* hipStream);
 int dqo_map_unpack_rows(int32_t P, int32_t M, int32_t n, int32_t first_row, int32_t has_confidence, const float* table, float* xyz,
                         float* shs, float* opacity_raw, float* scaling_raw, float* rotation_raw, float* confidence, void* hipStream);
+
+/* dqo_map_pack_rows_by_object (ABI 5, symbols-only addition) — the vertex data of every file GaussianPointCloud.save_model_ply_obj writes
+ * (SLAM/gaussian_pointcloud.py:589-637, called for both clouds from mapper.py:1586-1588; metric_obj.py loads the `_stable_obj{id}.ply`
+ * ones), in ONE table.  It replaces, per cloud and per object, the boolean indexing of every buffer, seven device-to-host copies, the SH
+ * transpose and np.concatenate of :606-634, and the np.unique of :592-593.
+ * The map arguments, the row layout and the word-for-word copies are dqo_map_pack_rows'.  gaussian_object int32 [P]: an id in [0, 64) is
+ *   the row's object, any other value means none.  The table's rows are the alive rows that have an object, ordered by (stable != 0,
+ *   object id, row index), all ascending; header (int32 [2][64], device, overwritten): header[c][g] = the rows of cloud c (0 unstable, 1
+ *   stable), object g.  The slice of (cloud 0, object g) is the vertex data of path + "_obj{g}.ply", that of (cloud 1, object g) of
+ *   path + "_stable_obj{g}.ply"; an object without rows in a cloud has no file (:590-593).  table_rows >= P; rows at and behind the
+ *   total are NOT written.  Three launches, nothing read back, no atomics: the table is a pure function of the inputs.
+ *   workspace: dqo_map_pack_workspace_bytes(P) bytes, the same query — those bytes suffice: this call's order list lives in word 0 of the
+ *   table rows it is about to fill, and the workspace is handed back as it came (the contract of dqo_map_pack_rows holds trivially).
+ * DQO_ERR_INVALID_ARG / DQO_ERR_WORKSPACE as dqo_map_pack_rows, and for a NULL gaussian_object. */
+int dqo_map_pack_rows_by_object(int32_t P, int32_t M, int32_t include_confidence, const float* xyz, const float* shs,
+                                const float* opacity_raw, const float* scaling_raw, const float* rotation_raw, const float* confidence,
+                                const uint8_t* alive, const uint8_t* stable, const int32_t* gaussian_object, float* table, int64_t table_rows,
+                                int32_t* header, void* workspace, size_t workspace_bytes, void* hipStream);
 
 /* Row f4 — normal equations of one Gauss-Newton iteration of the point-to-plane ICP tracker (SLAM/icp.py:51-123:
  * compute_residuals_jacobian + compute_jtj + compute_jtr).  vertex / normal maps are [H, W, 3] fp32, pose10 a row-major 4x4
