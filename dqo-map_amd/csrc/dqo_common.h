@@ -546,10 +546,14 @@ int dqo_check_adam_step(const DqoAdamStep* st, bool need_grads);
 int dqo_launch_backward_adam(const DqoRastParams* p, const DqoRastInputs* in, const DqoRastCtx* ctx, const float* dL_dcolor,
                              const float* dL_ddepth, const DqoAdamStep* st, void* ws, hipStream_t s);
 int dqo_launch_adam_advance(int32_t* step_dev, const DqoRastHeader* frame_header, hipStream_t s);
-// the exact 1-NN search (knn.hip), which dqo_eval_pcd (map_eval.hip) runs in both directions; its row limit per set
+// the exact 1-NN search (knn.hip), which dqo_eval_pcd and dqo_eval_pcd_grouped (map_eval.hip) run in both directions; its row limit per set.
+// Which rows of a set take part, and as which object: a keep byte column (0 = dropped, the others are object 0), an int32 id column
+// ([0, 64), any other value = no object), or neither (every row, one object).  At most one of the two.
+struct DqoNn1Rows {
+    const uint8_t* keep;
+    const int32_t* ids;
+};
 bool dqo_nn1_size_ok(int32_t n);
 size_t dqo_nn1_ws_bytes(int Q, int R);
-int dqo_launch_nn1(int Q, const float* q_xyz, const uint8_t* q_keep, int R, const float* r_xyz, const uint8_t* r_keep, const float* q_xform,
-                   const float* r_xform, float* dist2, int32_t* idx, void* ws, hipStream_t s);
-int dqo_launch_nn1_grouped(int Q, const float* q_xyz, const int32_t* q_group, int R, const float* r_xyz, const int32_t* r_group,
-                           const float* q_xform, const float* r_xform, float* dist2, int32_t* idx, float2* by_rank, void* ws, hipStream_t s);
+int dqo_launch_nn1(int Q, const float* q_xyz, DqoNn1Rows q_rows, int R, const float* r_xyz, DqoNn1Rows r_rows, const float* q_xform,
+                   const float* r_xform, float* dist2, int32_t* idx, float2* by_rank, void* ws, hipStream_t s);

@@ -634,18 +634,33 @@ __global__ __launch_bounds__(256) void knn_query_wave_kernel(int Q, const float*
 }
 
 
-// ---- dqo_nn1: the exact nearest REFERENCE of every QUERY when both sets are large and lie among each other ----------------------------
-// (eval_pcd, SLAM/eval.py:190-226: scipy's KDTree(a).query(b), one million points against one million.)  knn_query_wave_kernel puts a
-// wave on every query: right for few scattered queries, but a million queries among a million references repeat the same walk over the
-// level-1 boxes a million times.  Here the QUERIES are sorted too — by their Morton code on the REFERENCE's grid, so that a wave's 64
-// lanes hold 64 neighbouring queries — and the search is knn_scan_kernel's: one lane per query, a record (group of 64 boxes, box, run of
-// 64 points) is opened by the whole wave when any lane cannot exclude it, its candidates arrive by wave-uniform loads.  K = 1, so a lane
-// keeps one distance; it starts from the references either side of its own rank among the reference keys, and the box that rank falls
-// into is scanned first.  Every candidate a lane sees is a kept reference, every record it skips has dist_box_point > its best: the
-// result is the minimum of kbest's float expression over ALL kept references, bit for bit, whatever the order.
-// A dropped row (keep byte 0) of the reference set takes knn_build's group path (no group: outside the bounding box, sorted last, a far
-// sentinel, its records' group words 0), a kept one is group 0: bit 25 of its index word.  The same bit marks a kept query.
+// ---- dqo_nn1 / dqo_nn1_grouped: the exact nearest REFERENCE of every QUERY when both sets are large and lie among each other ----------
+// (eval_pcd, SLAM/eval.py:190-226: scipy's KDTree(a).query(b), one million points against one million; metric_obj.py:169-236: the same
+// for every object's cloud against that object's own mesh.)  knn_query_wave_kernel puts a wave on every query: right for few scattered
+// queries, but a million queries among a million references repeat the same walk over the level-1 boxes a million times.  Here the
+// QUERIES are sorted too — by their Morton code on the REFERENCE's grid, so that a wave's 64 lanes hold 64 neighbouring queries — and the
+// search is knn_scan_kernel's: one lane per query, a record (group of 64 boxes, box, run of 64 points) is opened by the whole wave when
+// any lane cannot exclude it, its candidates arrive by wave-uniform loads.  K = 1, so a lane keeps one distance; the references either
+// side of its own rank among the reference keys come first, then the box that rank falls into.
+// ONE SEARCH, THREE ROW SOURCES.  Every row of either set has a group word, id + 1, 0 = the row takes no part (DqoNn1Rows): 1 for every
+// row (the plain search), keep[i] != 0 (a keep byte column: the kept rows are object 0) or an int32 id column (up to 64 objects).  A
+// query's word rides in bits 25..31 of its index word.  A reference set WITH a source is built on knn_build's group path (a row without
+// a group: outside the bounding box, sorted last, a far sentinel; the word in a point's index word, the set of groups under it in every
+// record) and scanned with FILTER: a record is opened only if one of the lanes that cannot exclude it belongs to a group the record
+// holds (a ballot over `need && (record's set & my bit)`: the record's set is wave-uniform), and a lane takes a candidate only if the
+// candidate's word is its own — so a lane may start without a bound, and then opens every record that holds its group until it has met
+// a reference of its own.  A reference set WITHOUT one is built without groups (its words are 0) and scanned with those tests compiled
+// out.  Queries given by ids are sorted by object first (the sort's last pass takes the id as its digit), so a wave holds one object
+// where it can; dropped queries sort last by their all-ones code either way.  Every candidate a lane takes is a reference of its group,
+// every record it skips holds none of its group or has dist_box_point > its best: the result is the minimum of kbest's float
+// expression over ALL references of the query's group, bit for bit, whatever the order and whichever source named the group.
 constexpr uint32_t NN1_IDX_MASK = (1u << FINE_IDX_BITS) - 1u;
+static_assert(FINE_IDX_BITS == KNN_GROUP_SHIFT, "a query's group word sits where knn_build puts a reference's");
+
+__device__ __forceinline__ uint32_t nn1_row_group(const DqoNn1Rows rows, int i) {
+    if (rows.ids != nullptr) return knn_in_group(rows.ids, i) ? (uint32_t)(rows.ids[i] + 1) : 0u;
+    return rows.keep == nullptr || rows.keep[i] != 0 ? 1u : 0u;
+}
 
 // the point as it is searched: row i under the row-major 3x4 transform m (NULL: as stored) — open3d's rec_pc.transform(transform)
 __device__ __forceinline__ float4 nn1_point(const float* __restrict__ xyz, const float* __restrict__ m, int i) {
@@ -668,165 +683,53 @@ __global__ void nn1_prepare_ref_kernel(int R, const float* __restrict__ xyz, con
     if (grp != nullptr) grp[i] = keep[i] != 0 ? 0 : -1;
 }
 
-// query keys on the reference's grid; a dropped query sorts behind every kept one
-__global__ void nn1_query_keys_kernel(int Q, const float* __restrict__ xyz, const uint8_t* __restrict__ keep, const float* __restrict__ xform,
+// query keys on the reference's grid; a query that takes no part sorts behind every one that does
+__global__ void nn1_query_keys_kernel(int Q, const float* __restrict__ xyz, DqoNn1Rows rows, const float* __restrict__ xform,
                                       const float* __restrict__ ref_bbox, uint64_t* __restrict__ keys) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Q) return;
     uint64_t code = (1ull << (3 * FINE_BITS)) - 1ull;
-    if (keep == nullptr || keep[i] != 0) {
+    if (nn1_row_group(rows, i) != 0u) {
         const float4 p = nn1_point(xyz, xform, i);
         code = morton_fine_code(p.x, p.y, p.z, ref_bbox);
     }
     keys[i] = (code << FINE_IDX_BITS) | (uint64_t)i;
 }
 
-__global__ void nn1_gather_query_kernel(int Q, const float* __restrict__ xyz, const uint8_t* __restrict__ keep, const float* __restrict__ xform,
+// the sorted query: xyz under the transform, the row index and the group word above it (0: the point is not searched for)
+__global__ void nn1_gather_query_kernel(int Q, const float* __restrict__ xyz, DqoNn1Rows rows, const float* __restrict__ xform,
                                         const uint64_t* __restrict__ keys, float4* __restrict__ sorted_q) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Q) return;
     const uint32_t src = (uint32_t)keys[i] & NN1_IDX_MASK;
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
     uint32_t w = src;
-    if (keep == nullptr || keep[src] != 0) p = nn1_point(xyz, xform, (int)src), w |= 1u << FINE_IDX_BITS;
+    const uint32_t g1 = nn1_row_group(rows, (int)src);
+    if (g1 != 0u) p = nn1_point(xyz, xform, (int)src), w |= g1 << KNN_GROUP_SHIFT;
     p.w = __uint_as_float(w);
     sorted_q[i] = p;
 }
 
-// kbest with K = 1; with a mask only a reference that carries a group counts (the sentinel rows do not)
-__device__ __forceinline__ void nn1_take(const float4 me, const float4 cand, bool masked, float& best, int& bidx) {
+// kbest with K = 1; FILTER: only a reference of the lane's own group counts (the sentinel rows carry none)
+template <bool FILTER>
+__device__ __forceinline__ void nn1_take(const float4 me, const float4 cand, uint32_t my_group, float& best, int& bidx) {
 #pragma clang fp contract(off)
     const float dx = cand.x - me.x, dy = cand.y - me.y, dz = cand.z - me.z;
     const float dist = dx * dx + dy * dy + dz * dz;
     const uint32_t w = __float_as_uint(cand.w);
-    if ((!masked || (w >> FINE_IDX_BITS) != 0u) && dist < best) best = dist, bidx = (int)(w & NN1_IDX_MASK);
-}
-
-__global__ __launch_bounds__(256) void nn1_scan_kernel(int Q, const float4* __restrict__ sorted_q, const uint64_t* __restrict__ keys_q, int R,
-                                                       const float4* __restrict__ sorted_r, const uint64_t* __restrict__ keys_r,
-                                                       const float* __restrict__ boxes, const float* __restrict__ sub,
-                                                       const float* __restrict__ groups, int masked_i, float* __restrict__ dist2,
-                                                       int32_t* __restrict__ idx) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool masked = masked_i != 0;
-    const float4 me = q < Q ? sorted_q[q] : make_float4(0.f, 0.f, 0.f, 0.f);
-    const uint32_t my_w = __float_as_uint(me.w);
-    const bool live = q < Q && (my_w >> FINE_IDX_BITS) != 0u;
-    float best = FLT_MAX;
-    int bidx = -1, rank = 0;
-    if (live) {  // the first reference key not below the query's code, and the two references either side of it
-        const uint64_t key = (keys_q[q] >> FINE_IDX_BITS) << FINE_IDX_BITS;
-        int lo = 0, hi = R;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (keys_r[mid] < key) lo = mid + 1;
-            else hi = mid;
-        }
-        rank = lo;
-        for (int i = max(0, rank - 2); i <= min(R - 1, rank + 1); i++) nn1_take(me, sorted_r[i], masked, best, bidx);
-    }
-    const int nb = (R + KNN_BOX - 1) / KNN_BOX, ng = (nb + 63) / 64;
-    auto scan_box = [&](int b) {  // (b wave-uniform: the records and the candidates come by wave-uniform loads)
-        const float* bx = boxes + 8 * (size_t)b;
-        if (masked && knn_record_groups(bx) == 0ull) return;  // nothing kept in it
-        const float d = dist_box_point(bx, me);
-        if (__ballot(live && !(d > best)) == 0) return;
-        const int lo = b * KNN_BOX, hi = min(R, lo + KNN_BOX);
-        for (int r0 = lo; r0 < hi; r0 += KNN_SUB) {
-            const float* sx = sub + 8 * (size_t)(r0 / KNN_SUB);
-            if (masked && knn_record_groups(sx) == 0ull) continue;
-            const float ds = dist_box_point(sx, me);
-            if (__ballot(live && !(ds > best)) == 0) continue;
-            // every lane takes every candidate, asked for the run or not (a candidate like any other; a lane without a query is not
-            // written).  A full run has a constant trip count: its wave-uniform loads are issued several at a time
-            if (r0 + KNN_SUB <= hi) {
-#pragma unroll 8
-                for (int i = 0; i < KNN_SUB; i++) nn1_take(me, sorted_r[r0 + i], masked, best, bidx);
-            } else {
-                for (int i = r0; i < hi; i++) nn1_take(me, sorted_r[i], masked, best, bidx);
-            }
-        }
-    };
-    if (__ballot(live) != 0) {
-        // dropped queries sort last, so lane 0 of a wave with a live lane is live: the box its rank falls into first
-        const int home = min(nb - 1, __builtin_amdgcn_readfirstlane(rank) / KNN_BOX);
-        scan_box(home);
-        for (int g = 0; g < ng; g++) {
-            const float* gx = groups + 8 * (size_t)g;
-            if (masked && knn_record_groups(gx) == 0ull) continue;
-            const float dg = dist_box_point(gx, me);
-            if (__ballot(live && !(dg > best)) == 0) continue;
-            const int b1 = min(nb, (g + 1) * 64);
-            for (int b = g * 64; b < b1; b++)
-                if (b != home) scan_box(b);
-        }
-    }
-    if (q < Q) {
-        const uint32_t dst = my_w & NN1_IDX_MASK;
-        dist2[dst] = live && bidx >= 0 ? best : FLT_MAX;
-        if (idx != nullptr) idx[dst] = live ? bidx : -1;
-    }
-}
-
-__global__ void nn1_fill_kernel(int Q, float* __restrict__ dist2, int32_t* __restrict__ idx) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= Q) return;
-    dist2[i] = FLT_MAX;
-    if (idx != nullptr) idx[i] = -1;
-}
-
-// ---- dqo_nn1_grouped: dqo_nn1 for up to 64 objects in ONE search ------------------------------------------------------------------------
-// (metric_obj.py:169-236: eval_pcd of every object's cloud against that object's own mesh.)  A reference only counts for a query of the same
-// group.  The reference set is built once with its group ids (knn_build's group path: the id + 1 in bits 25..31 of a point's index word,
-// the set of groups under it in every record), the queries are sorted once — by group, and within a group by their Morton code on the
-// reference's grid (the sort's last pass takes the group id as its digit), so a wave holds one object where it can — and one scan serves
-// every object.  The scan is nn1_scan_kernel's with two more rules: a record is opened only if one of the lanes that cannot exclude it
-// belongs to a group the record holds (a ballot over `need && (record's set & my bit)`: the record's set is wave-uniform), and a lane takes
-// a candidate only if the candidate's group word is its own.  The four references around a query's rank are candidates like any other:
-// they count only if they are of the query's group, so a lane may start the scan without a bound — it then opens every record that
-// holds its group until it has met a reference of its own.  Every candidate a lane takes is a reference of its group, every record it
-// skips holds none of its group or has dist_box_point > its best: the result is the minimum of kbest's float expression over ALL
-// references of the query's group, bit for bit — what dqo_nn1 returns with the two keep masks of that group.
-__global__ void nn1g_query_keys_kernel(int Q, const float* __restrict__ xyz, const int32_t* __restrict__ group, const float* __restrict__ xform,
-                                       const float* __restrict__ ref_bbox, uint64_t* __restrict__ keys) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= Q) return;
-    uint64_t code = (1ull << (3 * FINE_BITS)) - 1ull;
-    if (knn_in_group(group, i)) {
-        const float4 p = nn1_point(xyz, xform, i);
-        code = morton_fine_code(p.x, p.y, p.z, ref_bbox);
-    }
-    keys[i] = (code << FINE_IDX_BITS) | (uint64_t)i;
-}
-
-// the sorted query: xyz under the transform, the row index and the group id + 1 above it (0: no group, the point is not searched for)
-__global__ void nn1g_gather_query_kernel(int Q, const float* __restrict__ xyz, const int32_t* __restrict__ group, const float* __restrict__ xform,
-                                         const uint64_t* __restrict__ keys, float4* __restrict__ sorted_q) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= Q) return;
-    const uint32_t src = (uint32_t)keys[i] & NN1_IDX_MASK;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-    uint32_t w = src;
-    if (knn_in_group(group, (int)src)) p = nn1_point(xyz, xform, (int)src), w |= (uint32_t)(group[src] + 1) << KNN_GROUP_SHIFT;
-    p.w = __uint_as_float(w);
-    sorted_q[i] = p;
-}
-
-__device__ __forceinline__ void nn1g_take(const float4 me, const float4 cand, uint32_t my_group, float& best, int& bidx) {
-#pragma clang fp contract(off)
-    const float dx = cand.x - me.x, dy = cand.y - me.y, dz = cand.z - me.z;
-    const float dist = dx * dx + dy * dy + dz * dz;
-    const uint32_t w = __float_as_uint(cand.w);
-    if ((w >> KNN_GROUP_SHIFT) == my_group && dist < best) best = dist, bidx = (int)(w & NN1_IDX_MASK);
+    // (two selects, not a branch: a run's candidates stay in one block, so their wave-uniform loads are merged and issued ahead)
+    const bool take = (!FILTER || (w >> KNN_GROUP_SHIFT) == my_group) && dist < best;
+    best = take ? dist : best, bidx = take ? (int)(w & NN1_IDX_MASK) : bidx;
 }
 
 // by_rank (dqo_eval_pcd_grouped; may be NULL): the result in the queries' SORTED order too, {dist2, group id (64: none)} of sorted query q —
 // an object's rows are contiguous there, which is what the reduction's fixed summation order is laid over.  dist2 may be NULL then.
-__global__ __launch_bounds__(256) void nn1_grouped_scan_kernel(int Q, const float4* __restrict__ sorted_q, const uint64_t* __restrict__ keys_q,
-                                                               int R, const float4* __restrict__ sorted_r, const uint64_t* __restrict__ keys_r,
-                                                               const float* __restrict__ boxes, const float* __restrict__ sub,
-                                                               const float* __restrict__ groups, float* __restrict__ dist2,
-                                                               int32_t* __restrict__ idx, float2* __restrict__ by_rank) {
+template <bool FILTER>
+__global__ __launch_bounds__(256) void nn1_scan_kernel(int Q, const float4* __restrict__ sorted_q, const uint64_t* __restrict__ keys_q, int R,
+                                                       const float4* __restrict__ sorted_r, const uint64_t* __restrict__ keys_r,
+                                                       const float* __restrict__ boxes, const float* __restrict__ sub,
+                                                       const float* __restrict__ groups, float* __restrict__ dist2, int32_t* __restrict__ idx,
+                                                       float2* __restrict__ by_rank) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     const float4 me = q < Q ? sorted_q[q] : make_float4(0.f, 0.f, 0.f, 0.f);
     const uint32_t my_w = __float_as_uint(me.w);
@@ -835,7 +738,7 @@ __global__ __launch_bounds__(256) void nn1_grouped_scan_kernel(int Q, const floa
     const unsigned long long my_bit = live ? 1ull << (my_group - 1u) : 0ull;
     float best = FLT_MAX;
     int bidx = -1, rank = 0;
-    if (live) {  // the first reference key not below the query's code; the two references either side of it count if they are of its group
+    if (live) {  // the first reference key not below the query's code, and the two references either side of it: candidates like any other
         const uint64_t key = (keys_q[q] >> FINE_IDX_BITS) << FINE_IDX_BITS;
         int lo = 0, hi = R;
         while (lo < hi) {
@@ -844,31 +747,37 @@ __global__ __launch_bounds__(256) void nn1_grouped_scan_kernel(int Q, const floa
             else hi = mid;
         }
         rank = lo;
-        for (int i = max(0, rank - 2); i <= min(R - 1, rank + 1); i++) nn1g_take(me, sorted_r[i], my_group, best, bidx);
+        for (int i = max(0, rank - 2); i <= min(R - 1, rank + 1); i++) nn1_take<FILTER>(me, sorted_r[i], my_group, best, bidx);
     }
     const int nb = (R + KNN_BOX - 1) / KNN_BOX, ng = (nb + 63) / 64;
-    // a record (wave-uniform address) is opened if a lane that cannot exclude it is of a group the record holds
+    // a record (wave-uniform address) is opened if a lane cannot exclude it — FILTER: a lane of a group the record holds
     auto wanted = [&](const float* rec) {
-        const unsigned long long held = knn_record_groups(rec);
-        if (held == 0ull) return false;
+        bool mine = true;
+        if (FILTER) {
+            const unsigned long long held = knn_record_groups(rec);
+            if (held == 0ull) return false;
+            mine = (held & my_bit) != 0ull;
+        }
         const float d = dist_box_point(rec, me);
-        return __ballot(live && (held & my_bit) != 0ull && !(d > best)) != 0;
+        return __ballot(live && mine && !(d > best)) != 0;
     };
-    auto scan_box = [&](int b) {
+    auto scan_box = [&](int b) {  // (b wave-uniform: the records and the candidates come by wave-uniform loads)
         if (!wanted(boxes + 8 * (size_t)b)) return;
         const int lo = b * KNN_BOX, hi = min(R, lo + KNN_BOX);
         for (int r0 = lo; r0 < hi; r0 += KNN_SUB) {
             if (!wanted(sub + 8 * (size_t)(r0 / KNN_SUB))) continue;
+            // every lane takes every candidate, asked for the run or not (a candidate like any other; a lane without a query is not
+            // written).  A full run has a constant trip count: its wave-uniform loads are issued several at a time
             if (r0 + KNN_SUB <= hi) {
 #pragma unroll 8
-                for (int i = 0; i < KNN_SUB; i++) nn1g_take(me, sorted_r[r0 + i], my_group, best, bidx);
+                for (int i = 0; i < KNN_SUB; i++) nn1_take<FILTER>(me, sorted_r[r0 + i], my_group, best, bidx);
             } else {
-                for (int i = r0; i < hi; i++) nn1g_take(me, sorted_r[i], my_group, best, bidx);
+                for (int i = r0; i < hi; i++) nn1_take<FILTER>(me, sorted_r[i], my_group, best, bidx);
             }
         }
     };
     if (__ballot(live) != 0) {
-        // queries without a group sort last, so lane 0 of a wave with a live lane is live: the box its rank falls into first
+        // queries that take no part sort last, so lane 0 of a wave with a live lane is live: the box its rank falls into first
         const int home = min(nb - 1, __builtin_amdgcn_readfirstlane(rank) / KNN_BOX);
         scan_box(home);
         for (int g = 0; g < ng; g++) {
@@ -885,6 +794,13 @@ __global__ __launch_bounds__(256) void nn1_grouped_scan_kernel(int Q, const floa
         if (idx != nullptr) idx[dst] = live ? bidx : -1;
         if (by_rank != nullptr) by_rank[q] = make_float2(d, __uint_as_float(live ? my_group - 1u : 64u));
     }
+}
+
+__global__ void nn1_fill_kernel(int Q, float* __restrict__ dist2, int32_t* __restrict__ idx) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Q) return;
+    dist2[i] = FLT_MAX;
+    if (idx != nullptr) idx[i] = -1;
 }
 
 struct Nn1Ws {
@@ -922,15 +838,12 @@ static int knn_radix_sort(int P, const KnnWs& w, bool fine, hipStream_t s, const
     for (int pass = 0; pass < n_pass; pass++) {
         const int shift = pass < 5 ? shift0 + 8 * pass : 56;
         const bool grp = by_group != nullptr && pass == 5;
-        if (grp) DQO_LAUNCH("radix_hist_kernel", radix_hist_kernel<true>, dim3(nblk), dim3(RDX_T), s, P, a, shift, w.hist, nblk, by_group);
-        else DQO_LAUNCH("radix_hist_kernel", radix_hist_kernel<false>, dim3(nblk), dim3(RDX_T), s, P, a, shift, w.hist, nblk, by_group);
+        const auto hist = grp ? radix_hist_kernel<true> : radix_hist_kernel<false>;
+        const auto scatter = grp ? radix_scatter_kernel<true> : radix_scatter_kernel<false>;
+        DQO_LAUNCH("radix_hist_kernel", hist, dim3(nblk), dim3(RDX_T), s, P, a, shift, w.hist, nblk, by_group);
         DQO_LAUNCH("radix_scan_kernel", radix_scan_kernel, dim3(256), dim3(256), s, w.hist, nblk, w.hist + (size_t)256 * nblk);
-        if (grp)
-            DQO_LAUNCH("radix_scatter_kernel", radix_scatter_kernel<true>, dim3(nblk), dim3(RDX_T), s, P, a, b, shift, w.hist, nblk,
-                       w.hist + (size_t)256 * nblk, by_group);
-        else
-            DQO_LAUNCH("radix_scatter_kernel", radix_scatter_kernel<false>, dim3(nblk), dim3(RDX_T), s, P, a, b, shift, w.hist, nblk,
-                       w.hist + (size_t)256 * nblk, by_group);
+        DQO_LAUNCH("radix_scatter_kernel", scatter, dim3(nblk), dim3(RDX_T), s, P, a, b, shift, w.hist, nblk, w.hist + (size_t)256 * nblk,
+                   by_group);
         std::swap(a, b);
     }
     return DQO_OK;
@@ -971,24 +884,27 @@ static int dqo_launch_knn3(int P, const float* xyz, float* mean_d2, int32_t* idx
     return DQO_OK;
 }
 
+// the reference set of a query search: knn_build on the fine grid, then the two further pruning levels (runs of 64 points, runs of 64 boxes)
+static int knn_build_ref(int R, const float* xyz, const KnnWs& w, hipStream_t s, const int32_t* group) {
+    const int rc = knn_build(R, xyz, w, true, s, true, group);
+    if (rc) return rc;
+    const int ns = (R + KNN_SUB - 1) / KNN_SUB, nb = (R + KNN_BOX - 1) / KNN_BOX, ng = (nb + 63) / 64;
+    DQO_LAUNCH("sub_minmax_kernel", sub_minmax_kernel, dim3((ns * 64 + 255) / 256), dim3(256), s, R, w.sorted, w.sub);
+    DQO_LAUNCH("group_minmax_kernel", group_minmax_kernel, dim3((ng * 64 + 255) / 256), dim3(256), s, nb, w.boxes, w.groups);
+    return DQO_OK;
+}
+
 static size_t dqo_knn3_query_ws_bytes(int Q, int R) { return knn_ws(nullptr, Q).total + knn_ws(nullptr, R).total; }
 
 static int dqo_launch_knn3_query(int Q, const float* q_xyz, int R, const float* r_xyz, float* dist2, int32_t* idx3, void* ws, size_t ws_bytes,
                                  hipStream_t s, float bound2, const int32_t* q_group, const int32_t* r_group, const float* group_box) {
     (void)ws_bytes;
     KnnWs wr = knn_ws(ws, R);
-    int rc = knn_build(R, r_xyz, wr, true, s, true, r_group);
+    const int rc = knn_build_ref(R, r_xyz, wr, s, r_group);
     if (rc) return rc;
-    const int ns = (R + KNN_SUB - 1) / KNN_SUB;
-    DQO_LAUNCH("sub_minmax_kernel", sub_minmax_kernel, dim3((ns * 64 + 255) / 256), dim3(256), s, R, wr.sorted, wr.sub);
-    const int nb = (R + KNN_BOX - 1) / KNN_BOX, ng = (nb + 63) / 64;
-    DQO_LAUNCH("group_minmax_kernel", group_minmax_kernel, dim3((ng * 64 + 255) / 256), dim3(256), s, nb, wr.boxes, wr.groups);
-    if (q_group != nullptr)
-        DQO_LAUNCH("knn_query_wave_kernel", knn_query_wave_kernel<true>, dim3(((size_t)Q * 64 + 255) / 256), dim3(256), s, Q, q_xyz, R, wr.sorted,
-                   wr.boxes, wr.sub, wr.groups, dist2, idx3, bound2, q_group, group_box);
-    else
-        DQO_LAUNCH("knn_query_wave_kernel", knn_query_wave_kernel<false>, dim3(((size_t)Q * 64 + 255) / 256), dim3(256), s, Q, q_xyz, R, wr.sorted,
-                   wr.boxes, wr.sub, wr.groups, dist2, idx3, bound2, q_group, group_box);
+    const auto scan = q_group != nullptr ? knn_query_wave_kernel<true> : knn_query_wave_kernel<false>;
+    DQO_LAUNCH("knn_query_wave_kernel", scan, dim3(((size_t)Q * 64 + 255) / 256), dim3(256), s, Q, q_xyz, R, wr.sorted, wr.boxes, wr.sub,
+               wr.groups, dist2, idx3, bound2, q_group, group_box);
     return DQO_OK;
 }
 
@@ -997,8 +913,10 @@ bool dqo_nn1_size_ok(int32_t n) { return n >= 0 && n < (1 << FINE_IDX_BITS); }
 
 size_t dqo_nn1_ws_bytes(int Q, int R) { return nn1_ws(nullptr, Q < 1 ? 1 : Q, R < 1 ? 1 : R).total; }
 
-int dqo_launch_nn1(int Q, const float* q_xyz, const uint8_t* q_keep, int R, const float* r_xyz, const uint8_t* r_keep, const float* q_xform,
-                   const float* r_xform, float* dist2, int32_t* idx, void* ws, hipStream_t s) {
+// The workspace's group column holds a reference keep mask as ids; the caller's own ids are read in place.  Q, R >= 1 when by_rank is
+// asked for.
+int dqo_launch_nn1(int Q, const float* q_xyz, DqoNn1Rows q_rows, int R, const float* r_xyz, DqoNn1Rows r_rows, const float* q_xform,
+                   const float* r_xform, float* dist2, int32_t* idx, float2* by_rank, void* ws, hipStream_t s) {
     if (Q == 0) return DQO_OK;
     if (R == 0) {
         DQO_LAUNCH("nn1_fill_kernel", nn1_fill_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, dist2, idx);
@@ -1006,57 +924,24 @@ int dqo_launch_nn1(int Q, const float* q_xyz, const uint8_t* q_keep, int R, cons
     }
     const Nn1Ws w = nn1_ws(ws, Q, R);
     const float* ref = r_xyz;
-    const int32_t* grp = nullptr;
-    if (r_keep != nullptr || r_xform != nullptr) {
-        DQO_LAUNCH("nn1_prepare_ref_kernel", nn1_prepare_ref_kernel, dim3((R + 255) / 256), dim3(256), s, R, r_xyz, r_keep, r_xform,
-                   r_xform != nullptr ? w.txyz : nullptr, r_keep != nullptr ? w.grp : nullptr);
+    const int32_t* grp = r_rows.ids;
+    if (r_rows.keep != nullptr || r_xform != nullptr) {
+        DQO_LAUNCH("nn1_prepare_ref_kernel", nn1_prepare_ref_kernel, dim3((R + 255) / 256), dim3(256), s, R, r_xyz, r_rows.keep, r_xform,
+                   r_xform != nullptr ? w.txyz : nullptr, r_rows.keep != nullptr ? w.grp : nullptr);
         if (r_xform != nullptr) ref = w.txyz;
-        if (r_keep != nullptr) grp = w.grp;
+        if (r_rows.keep != nullptr) grp = w.grp;
     }
-    int rc = knn_build(R, ref, w.r, true, s, true, grp);
+    int rc = knn_build_ref(R, ref, w.r, s, grp);
     if (rc) return rc;
-    const int ns = (R + KNN_SUB - 1) / KNN_SUB, nb = (R + KNN_BOX - 1) / KNN_BOX, ng = (nb + 63) / 64;
-    DQO_LAUNCH("sub_minmax_kernel", sub_minmax_kernel, dim3((ns * 64 + 255) / 256), dim3(256), s, R, w.r.sorted, w.r.sub);
-    DQO_LAUNCH("group_minmax_kernel", group_minmax_kernel, dim3((ng * 64 + 255) / 256), dim3(256), s, nb, w.r.boxes, w.r.groups);
-    DQO_LAUNCH("nn1_query_keys_kernel", nn1_query_keys_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, q_xyz, q_keep, q_xform, w.r.bbox,
+    DQO_LAUNCH("nn1_query_keys_kernel", nn1_query_keys_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, q_xyz, q_rows, q_xform, w.r.bbox,
                w.q.keys);
-    rc = knn_radix_sort(Q, w.q, true, s);
+    rc = knn_radix_sort(Q, w.q, true, s, q_rows.ids);  // (by object only when there are objects: a keep mask's dropped rows sort last by their code)
     if (rc) return rc;
-    DQO_LAUNCH("nn1_gather_query_kernel", nn1_gather_query_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, q_xyz, q_keep, q_xform, w.q.keys,
+    DQO_LAUNCH("nn1_gather_query_kernel", nn1_gather_query_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, q_xyz, q_rows, q_xform, w.q.keys,
                w.q.sorted);
-    DQO_LAUNCH("nn1_scan_kernel", nn1_scan_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, w.q.sorted, w.q.keys, R, w.r.sorted, w.r.keys,
-               w.r.boxes, w.r.sub, w.r.groups, grp != nullptr ? 1 : 0, dist2, idx);
-    return DQO_OK;
-}
-
-// dqo_nn1's workspace serves (its group column goes unused: the caller's ids are read in place).  Q, R >= 1 when by_rank is asked for.
-int dqo_launch_nn1_grouped(int Q, const float* q_xyz, const int32_t* q_group, int R, const float* r_xyz, const int32_t* r_group,
-                           const float* q_xform, const float* r_xform, float* dist2, int32_t* idx, float2* by_rank, void* ws, hipStream_t s) {
-    if (Q == 0) return DQO_OK;
-    if (R == 0) {
-        DQO_LAUNCH("nn1_fill_kernel", nn1_fill_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, dist2, idx);
-        return DQO_OK;
-    }
-    const Nn1Ws w = nn1_ws(ws, Q, R);
-    const float* ref = r_xyz;
-    if (r_xform != nullptr) {
-        DQO_LAUNCH("nn1_prepare_ref_kernel", nn1_prepare_ref_kernel, dim3((R + 255) / 256), dim3(256), s, R, r_xyz, (const uint8_t*)nullptr,
-                   r_xform, w.txyz, (int32_t*)nullptr);
-        ref = w.txyz;
-    }
-    int rc = knn_build(R, ref, w.r, true, s, true, r_group);
-    if (rc) return rc;
-    const int ns = (R + KNN_SUB - 1) / KNN_SUB, nb = (R + KNN_BOX - 1) / KNN_BOX, ng = (nb + 63) / 64;
-    DQO_LAUNCH("sub_minmax_kernel", sub_minmax_kernel, dim3((ns * 64 + 255) / 256), dim3(256), s, R, w.r.sorted, w.r.sub);
-    DQO_LAUNCH("group_minmax_kernel", group_minmax_kernel, dim3((ng * 64 + 255) / 256), dim3(256), s, nb, w.r.boxes, w.r.groups);
-    DQO_LAUNCH("nn1g_query_keys_kernel", nn1g_query_keys_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, q_xyz, q_group, q_xform, w.r.bbox,
-               w.q.keys);
-    rc = knn_radix_sort(Q, w.q, true, s, q_group);
-    if (rc) return rc;
-    DQO_LAUNCH("nn1g_gather_query_kernel", nn1g_gather_query_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, q_xyz, q_group, q_xform, w.q.keys,
-               w.q.sorted);
-    DQO_LAUNCH("nn1_grouped_scan_kernel", nn1_grouped_scan_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, w.q.sorted, w.q.keys, R, w.r.sorted,
-               w.r.keys, w.r.boxes, w.r.sub, w.r.groups, dist2, idx, by_rank);
+    const auto scan = grp != nullptr ? nn1_scan_kernel<true> : nn1_scan_kernel<false>;
+    DQO_LAUNCH("nn1_scan_kernel", scan, dim3((Q + 255) / 256), dim3(256), s, Q, w.q.sorted, w.q.keys, R, w.r.sorted, w.r.keys, w.r.boxes, w.r.sub,
+               w.r.groups, dist2, idx, by_rank);
     return DQO_OK;
 }
 
@@ -1107,27 +992,29 @@ DQO_API int dqo_knn3(int32_t P, const float* xyz, float* mean_d2, int32_t* idx3,
 
 DQO_API size_t dqo_nn1_workspace_bytes(int32_t Q, int32_t R) { return dqo_nn1_size_ok(Q) && dqo_nn1_size_ok(R) ? dqo_nn1_ws_bytes(Q, R) : 0; }
 
-DQO_API int dqo_nn1(int32_t Q, const float* q_xyz, const uint8_t* q_keep, int32_t R, const float* r_xyz, const uint8_t* r_keep,
-                    const float* q_xform, const float* r_xform, float* dist2, int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
+// dqo_nn1 and dqo_nn1_grouped: one set of checks, one search; by_ids: the rows are given by group ids, which then must be there
+static int nn1(bool by_ids, int32_t Q, const float* q_xyz, DqoNn1Rows q_rows, int32_t R, const float* r_xyz, DqoNn1Rows r_rows,
+               const float* q_xform, const float* r_xform, float* dist2, int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
     DQO_CHECK_ARG(dqo_nn1_size_ok(Q) && dqo_nn1_size_ok(R), "bad size: at most 2^25 - 1 rows per set");
     if (Q == 0) return DQO_OK;
     DQO_CHECK_ARG(q_xyz && dist2, "null query / output");
     DQO_CHECK_ARG(R == 0 || r_xyz, "null reference set");
-    DQO_CHECK_WS("nn1", ws, ws_bytes, dqo_nn1_ws_bytes(Q, R));
-    return dqo_launch_nn1(Q, q_xyz, q_keep, R, r_xyz, r_keep, q_xform, r_xform, dist2, idx, ws, (hipStream_t)stream);
+    DQO_CHECK_ARG(!by_ids || (q_rows.ids && (R == 0 || r_rows.ids)), "null group ids");
+    if (by_ids) DQO_CHECK_WS("nn1 grouped", ws, ws_bytes, dqo_nn1_ws_bytes(Q, R));
+    else DQO_CHECK_WS("nn1", ws, ws_bytes, dqo_nn1_ws_bytes(Q, R));
+    return dqo_launch_nn1(Q, q_xyz, q_rows, R, r_xyz, r_rows, q_xform, r_xform, dist2, idx, nullptr, ws, (hipStream_t)stream);
+}
+
+DQO_API int dqo_nn1(int32_t Q, const float* q_xyz, const uint8_t* q_keep, int32_t R, const float* r_xyz, const uint8_t* r_keep,
+                    const float* q_xform, const float* r_xform, float* dist2, int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
+    return nn1(false, Q, q_xyz, {q_keep, nullptr}, R, r_xyz, {r_keep, nullptr}, q_xform, r_xform, dist2, idx, ws, ws_bytes, stream);
 }
 
 DQO_API size_t dqo_nn1_grouped_workspace_bytes(int32_t Q, int32_t R) { return dqo_nn1_workspace_bytes(Q, R); }
 
 DQO_API int dqo_nn1_grouped(int32_t Q, const float* q_xyz, const int32_t* q_group, int32_t R, const float* r_xyz, const int32_t* r_group,
                             const float* q_xform, const float* r_xform, float* dist2, int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
-    DQO_CHECK_ARG(dqo_nn1_size_ok(Q) && dqo_nn1_size_ok(R), "bad size: at most 2^25 - 1 rows per set");
-    if (Q == 0) return DQO_OK;
-    DQO_CHECK_ARG(q_xyz && dist2, "null query / output");
-    DQO_CHECK_ARG(R == 0 || r_xyz, "null reference set");
-    DQO_CHECK_ARG(q_group && (R == 0 || r_group), "null group ids");
-    DQO_CHECK_WS("nn1 grouped", ws, ws_bytes, dqo_nn1_ws_bytes(Q, R));
-    return dqo_launch_nn1_grouped(Q, q_xyz, q_group, R, r_xyz, r_group, q_xform, r_xform, dist2, idx, nullptr, ws, (hipStream_t)stream);
+    return nn1(true, Q, q_xyz, {nullptr, q_group}, R, r_xyz, {nullptr, r_group}, q_xform, r_xform, dist2, idx, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -112,6 +112,24 @@ struct PcThres {
 
 inline size_t pc_blocks(int n) { return ((size_t)n + 256 * PC_ROWS - 1) / (256 * PC_ROWS); }
 
+// one table row from the PC_SUMS sums of each side (an object's, or the whole sets'); a side without a kept row: a row of NaN
+__device__ __forceinline__ void pc_table_row(const double* rec, const double* gt, int n_thres, float* __restrict__ out) {
+    const float nan = __int_as_float(0x7fc00000);
+    for (int q = 0; q < PC_SLOTS; q++) out[q] = nan;
+    if (rec[1] == 0.0 || gt[1] == 0.0) return;
+    const double acc = rec[0] / rec[1], comp = gt[0] / gt[1];
+    out[0] = (float)(100.0 * acc);   // :273 (cm)
+    out[1] = (float)(100.0 * comp);  // :274
+    out[2] = (float)(acc + comp);    // :225 (metres)
+    out[3] = (float)n_thres;
+    for (int t = 0; t < n_thres; t++) {
+        const double P = 100.0 * (rec[2 + t] / rec[1]), R = 100.0 * (gt[2 + t] / gt[1]);  // :264-268
+        out[4 + 3 * t] = (float)P;
+        out[5 + 3 * t] = (float)R;
+        out[6 + 3 * t] = (float)(2.0 * P * R / (P + R));  // :269 (P + R = 0: 0 / 0 = NaN, numpy's value)
+    }
+}
+
 // blocks [0, blocks_rec) reduce d2_rec, the rest d2_gt
 __global__ __launch_bounds__(256) void eval_pcd_kernel(int n_rec, const float* __restrict__ d2_rec, const uint8_t* __restrict__ rec_keep, int n_gt,
                                                        const float* __restrict__ d2_gt, const uint8_t* __restrict__ gt_keep, int n_thres,
@@ -147,24 +165,7 @@ __global__ __launch_bounds__(256) void eval_pcd_kernel(int n_rec, const float* _
     const double tot_gt = dqo_fold_partials<PC_SUMS, PC_STRIDE, PC_STAGE>(w.partial, blocks_rec, (int)gridDim.x, s_stage);
     if (tid < PC_SUMS) s_stage[tid] = tot_rec, s_stage[PC_STRIDE + tid] = tot_gt;
     __syncthreads();
-    if (tid != 0) return;
-    const float nan = __int_as_float(0x7fc00000);
-    const double* rec = s_stage;
-    const double* gt = s_stage + PC_STRIDE;
-#pragma unroll
-    for (int q = 0; q < PC_SLOTS; q++) out[q] = nan;
-    if (rec[1] == 0.0 || gt[1] == 0.0) return;  // an empty set on either side: nothing to report
-    const double acc = rec[0] / rec[1], comp = gt[0] / gt[1];
-    out[0] = (float)(100.0 * acc);   // :273 (cm)
-    out[1] = (float)(100.0 * comp);  // :274
-    out[2] = (float)(acc + comp);    // :225 (metres)
-    out[3] = (float)n_thres;
-    for (int t = 0; t < n_thres; t++) {
-        const double P = 100.0 * (rec[2 + t] / rec[1]), R = 100.0 * (gt[2 + t] / gt[1]);  // :264-268
-        out[4 + 3 * t] = (float)P;
-        out[5 + 3 * t] = (float)R;
-        out[6 + 3 * t] = (float)(2.0 * P * R / (P + R));  // :269 (P + R = 0: 0 / 0 = NaN, numpy's value)
-    }
+    if (tid == 0) pc_table_row(s_stage, s_stage + PC_STRIDE, n_thres, out);
 }
 
 struct PcWorkspace {
@@ -186,7 +187,7 @@ inline PcWorkspace pc_ws(void* base, int n_gt, int n_rec) {
 }
 
 // ---- per-object geometry evaluation: eval_pcd's row for each of up to 64 objects (metric_obj.py:169-236) ------------------------------
-// Two dqo_nn1_grouped searches leave, per side, {dist2, object id} of every row in the search's SORTED order (by object, then by Morton
+// Two dqo_nn1 searches by object id leave, per side, {dist2, object id} of every row in the search's SORTED order (by object, then by Morton
 // code; rows without an object last, id 64): an object's rows are one contiguous run.  Block b of a side takes the sorted rows
 // [1024 b, 1024 b + 1024) and stores one partial per object g it meets, at line b + g of the side's partials — the runs ascend with b, so
 // no two (block, object) pairs share a line, and an object's lines are the contiguous range [first block + g, last block + g].
@@ -277,24 +278,7 @@ __global__ __launch_bounds__(256) void eval_pcd_grouped_kernel(int n_rec, const 
             if (tid < PC_SUMS) s_tot[side][g][tid] = tot;
         }
     __syncthreads();
-    if (tid >= PCG_OBJECTS) return;
-    const float nan = __int_as_float(0x7fc00000);
-    const double* rec = s_tot[0][tid];
-    const double* gt = s_tot[1][tid];
-    float* row = out + (size_t)PC_SLOTS * tid;
-    for (int q = 0; q < PC_SLOTS; q++) row[q] = nan;
-    if (rec[1] == 0.0 || gt[1] == 0.0) return;  // the object has no row on one side: nothing to report
-    const double acc = rec[0] / rec[1], comp = gt[0] / gt[1];
-    row[0] = (float)(100.0 * acc);
-    row[1] = (float)(100.0 * comp);
-    row[2] = (float)(acc + comp);
-    row[3] = (float)n_thres;
-    for (int t = 0; t < n_thres; t++) {
-        const double P = 100.0 * (rec[2 + t] / rec[1]), R = 100.0 * (gt[2 + t] / gt[1]);
-        row[4 + 3 * t] = (float)P;
-        row[5 + 3 * t] = (float)R;
-        row[6 + 3 * t] = (float)(2.0 * P * R / (P + R));
-    }
+    if (tid < PCG_OBJECTS) pc_table_row(s_tot[0][tid], s_tot[1][tid], n_thres, out + (size_t)PC_SLOTS * tid);
 }
 
 struct PcgWorkspace {
@@ -336,10 +320,11 @@ static size_t dqo_eval_pcd_ws_bytes(int n_gt, int n_rec) { return pc_ws(nullptr,
 static int dqo_launch_eval_pcd(int n_gt, const float* gt_xyz, const uint8_t* gt_keep, int n_rec, const float* rec_xyz, const uint8_t* rec_keep,
                                const float* rec_xform, int n_thres, const float* thres, float* out_row, void* ws, hipStream_t s) {
     const PcWorkspace w = pc_ws(ws, n_gt, n_rec);
+    const DqoNn1Rows gt_rows = {gt_keep, nullptr}, rec_rows = {rec_keep, nullptr};
     // accuracy: every reconstructed point to the ground truth (:204-208); completion: the other way round (:211-215)
-    int rc = dqo_launch_nn1(n_rec, rec_xyz, rec_keep, n_gt, gt_xyz, gt_keep, rec_xform, nullptr, w.d2_rec, nullptr, w.nn1, s);
+    int rc = dqo_launch_nn1(n_rec, rec_xyz, rec_rows, n_gt, gt_xyz, gt_rows, rec_xform, nullptr, w.d2_rec, nullptr, nullptr, w.nn1, s);
     if (rc) return rc;
-    rc = dqo_launch_nn1(n_gt, gt_xyz, gt_keep, n_rec, rec_xyz, rec_keep, nullptr, rec_xform, w.d2_gt, nullptr, w.nn1, s);
+    rc = dqo_launch_nn1(n_gt, gt_xyz, gt_rows, n_rec, rec_xyz, rec_rows, nullptr, rec_xform, w.d2_gt, nullptr, nullptr, w.nn1, s);
     if (rc) return rc;
     PcThres th;
     for (int t = 0; t < PC_THRES; t++) th.th[t] = t < n_thres ? thres[t] : 0.f;
@@ -353,11 +338,12 @@ static int dqo_launch_eval_pcd_grouped(int n_gt, const float* gt_xyz, const int3
                                        const int32_t* rec_group, const float* rec_xform, int n_thres, const float* thres, float* out_rows, void* ws,
                                        hipStream_t s) {
     const PcgWorkspace w = pcg_ws(ws, n_gt, n_rec);
+    const DqoNn1Rows gt_rows = {nullptr, gt_group}, rec_rows = {nullptr, rec_group};
     if (n_gt == 0 || n_rec == 0) n_gt = n_rec = 0;  // an empty set: no object has rows on both sides — one block writes the 64 NaN rows
     if (n_rec > 0) {
-        int rc = dqo_launch_nn1_grouped(n_rec, rec_xyz, rec_group, n_gt, gt_xyz, gt_group, rec_xform, nullptr, nullptr, nullptr, w.rk_rec, w.nn1, s);
+        int rc = dqo_launch_nn1(n_rec, rec_xyz, rec_rows, n_gt, gt_xyz, gt_rows, rec_xform, nullptr, nullptr, nullptr, w.rk_rec, w.nn1, s);
         if (rc) return rc;
-        rc = dqo_launch_nn1_grouped(n_gt, gt_xyz, gt_group, n_rec, rec_xyz, rec_group, nullptr, rec_xform, nullptr, nullptr, w.rk_gt, w.nn1, s);
+        rc = dqo_launch_nn1(n_gt, gt_xyz, gt_rows, n_rec, rec_xyz, rec_rows, nullptr, rec_xform, nullptr, nullptr, w.rk_gt, w.nn1, s);
         if (rc) return rc;
     }
     PcThres th;

@@ -587,8 +587,10 @@ int dqo_nn1(int32_t Q, const float* query_xyz, const uint8_t* query_keep, int32_
  * dist2[i] = the minimum of dqo_nn1's float expression over the references whose group equals query i's, idx[i] (may be NULL) a reference
  * of that group attaining it; FLT_MAX / -1 for a query without a group or whose group has no reference (or R = 0).  A pure function of
  * the inputs: bit for bit what dqo_nn1 returns with query_keep = (query_group == g) and ref_keep = (ref_group == g), for every g.
- * One build of the reference set (points and records carry their groups), one sort of the queries (by group, then by Morton code on the
- * reference's grid) and one scan launch serve every object; a record is opened only for lanes of a group it holds.
+ * It is dqo_nn1's search with another source for a row's group: there a keep byte makes the kept rows one object (and without a mask the
+ * group tests are compiled out), here an id column names up to 64.  One build of the reference set (points and records carry their
+ * groups), one sort of the queries (by group, then by Morton code on the reference's grid) and one scan launch serve every object; a
+ * record is opened only for lanes of a group it holds.
  * query_xform / ref_xform, the row limit (dqo_nn1_grouped_workspace_bytes: 0 beyond 2^25 - 1 rows; the bytes are dqo_nn1_workspace_bytes')
  * and the contract — no allocation, no synchronisation, nothing read back, capturable, the workspace needs no initialisation — are
  * dqo_nn1's. */

@@ -124,6 +124,45 @@ def test_masks_equal_the_search_on_the_gathered_subsets():
     assert (d == po.FLT_MAX).all() and (i == -1).all()
 
 
+def _half_dropped(seed, Q=200, R=1025):
+    """Q queries against R references (one full box of 1024 and one row: a ragged last run), and a keep mask for each side that drops
+    half its rows; `parked` puts a side's dropped rows where spare rows of a map lie."""
+    rng = np.random.default_rng(seed)
+    q, r = _cloud(rng, Q), _cloud(rng, R)
+    qk, rk = np.arange(Q) % 2 == 0, rng.permutation(R) % 2 == 0
+
+    def parked(x, keep):
+        x = x.copy()
+        x[~keep] = np.float32([0, 0, -1000.0])
+        return x
+    return q, r, qk, rk, parked
+
+
+@pytest.mark.parametrize("side", ["query", "reference"])
+def test_a_keep_mask_on_one_side_only(side):
+    """A masked query set against a reference set built without groups, and every query against a masked reference set."""
+    q, r, qk, rk, parked = _half_dropped(13)
+    if side == "query":
+        d, i = _check(parked(q, qk), r, (qk, None), what="query mask only")
+        assert (d[~qk] == po.FLT_MAX).all() and (i[~qk] == -1).all() and (d[qk] < po.FLT_MAX).all()
+    else:
+        d, i = _check(q, parked(r, rk), (None, rk), what="reference mask only")
+        assert (d < po.FLT_MAX).all() and rk[i].all()
+
+
+def test_ids_0_and_minus_1_are_the_two_keep_masks():
+    """nearest_grouped with one object is nearest with that object's two keep masks: dist2 and idx, bit for bit."""
+    import torch
+    import dqo_eval
+    q, r, qk, rk, parked = _half_dropped(14)
+    tq, tr = _t(parked(q, qk)), _t(parked(r, rk))
+    gd, gi = dqo_eval.nearest_grouped(tq, _t(np.where(qk, 0, -1), np.int32), tr, _t(np.where(rk, 0, -1), np.int32))
+    md, mi = dqo_eval.nearest(tq, tr, _t(qk, np.uint8), _t(rk, np.uint8))
+    torch.cuda.synchronize()
+    assert _bits(gd).tobytes() == _bits(md).tobytes() and gi.cpu().numpy().tobytes() == mi.cpu().numpy().tobytes()
+    assert (mi.cpu().numpy()[qk] >= 0).all() and (mi.cpu().numpy()[~qk] == -1).all()
+
+
 def test_transforms_match_the_oracles_restatement():
     gt, rec, _, _ = room()
     _check(rec, gt, xforms=(XFORM, None), what="query transform")
