@@ -406,6 +406,20 @@ static inline int dqo_spread_blocks(int P) {
     return (rows * 16 * 16 + 255) / 256;
 }
 
+// A deleted map row becomes a spare row: FusedMapper._free_rows' `freed` values of _ROW_BUFFERS, and nothing else.  A: an argument
+// struct with the per-Gaussian columns under DqoLifecycle's names (map_lifecycle.hip's DqoLifecycle, map_prune.hip's PruneRows).
+template <class A>
+__device__ __forceinline__ void dqo_map_free_row(const A& a, size_t i) {
+    a.xyz[3 * i] = a.park[0], a.xyz[3 * i + 1] = a.park[1], a.xyz[3 * i + 2] = a.park[2];
+    a.opacity_raw[i] = -10.f;
+    a.scaling_raw[3 * i] = -10.f, a.scaling_raw[3 * i + 1] = -10.f, a.scaling_raw[3 * i + 2] = -10.f;
+    a.alive[i] = 0;
+    a.row_flags[i] = DQO_ROW_HIDDEN | DQO_ROW_FROZEN;
+    a.confidence[i] = 0.f;
+    a.stable[i] = 0;
+    a.add_tick[i] = 0, a.depth_error_counter[i] = 0, a.color_error_counter[i] = 0;
+}
+
 // Per-view constants.  Scalars travel by value (kernarg -> SGPRs); the matrices stay device pointers because the
 // reference API hands them over as device tensors (no host read, no sync) — kernels fetch them with scalar loads.
 struct DqoView {

@@ -2,13 +2,21 @@
 // that takes the launch's LAST ticket folds the partials in block-index order and writes the result.  One launch, no float atomics, the
 // same bits on every run whatever order the blocks ran in, and the ticket words handed back at zero — no zero fill per call, so the entry
 // can be captured in a hipGraph.  Users: map_eval.hip (eval_picture_kernel, eval_pcd_kernel, eval_pcd_grouped_kernel: its own partial lines), map_msssim.hip (msssim_level_kernel), map_lifecycle.hip (the two cloud limits and
-// the frame's counts), map_tilemask.hip (window_masks_kernel: ticket only, its last block selects tiles), map_checkpoint.hip (map_pack_count_kernel: its last block scans
+// the frame's counts), map_prune.hip (prune_rows_kernel: ticket and counts), map_tilemask.hip (window_masks_kernel: ticket only, its last block selects tiles), map_checkpoint.hip (map_pack_count_kernel: its last block scans
 // the blocks' row counts), map_meshsample.hip (mesh_area_kernel: max and counts; mesh_quantise_kernel: its last block scans the blocks'
 // quanta), dqo_adam.h (ticket only, unfenced).
 //
-// Deliberately NOT users, and not to be "finished" into this header:
-//   - map_sample.hip's sp_last_block: one uint32 word per kernel, zeroed by the call's first launch, a few hundred blocks — a different
-//     and simpler contract;
+// Below the double reductions, the integer ends the map operators share (behind whichever last-block ticket their kernel takes):
+//   - dqo_block_exclusive, the block-wide exclusive scan: map_densify.hip (the count and emit passes, the first histogram pass's N),
+//     map_meshsample.hip (mesh_scan_kernel), and dqo_scan_block_counts;
+//   - dqo_scan_block_counts, the last block's turn of the blocks' counts into exclusive offsets in index order: map_sample.hip
+//     (sample_rank_kernel, sample_rows_kernel: two interleaved columns), map_densify.hip (densify_count_kernel: eight per thread),
+//     map_checkpoint.hip (map_pack_count_kernel), map_meshsample.hip (mesh_quantise_kernel);
+//   - dqo_line_count / dqo_line_totals, a row pass's counts on 64 lines: map_lifecycle.hip, map_prune.hip.
+//
+// Deliberately NOT users of the ticket, and not to be "finished" into this header:
+//   - dqo_select.h's dqo_single_ticket_last_block (map_sample.hip, map_densify.hip): one uint32 word per kernel, zeroed by the call's
+//     first launch, a few hundred to two thousand blocks — a different and simpler contract;
 //   - the reductions that finish in a second launch (ICP, the tracker's p2p, SSIM, the loss, the attach loss): folding them into one launch
 //     changes the launch count and the summation order, which is a performance change;
 //   - everything under rast_*.
@@ -66,6 +74,78 @@ __device__ __forceinline__ bool dqo_last_block(int32_t* ticket, int* s_last) {
     if (!*s_last) return false;
     __threadfence();  // 3
     return true;
+}
+
+// Exclusive prefix of x over the block's threads in thread order, and the block's total (for every thread): __shfl_up over the wave, the
+// four wave totals through LDS.  T: uint32_t or a 64-bit unsigned.  s_wave: 4 words of LDS; the call starts with a barrier, so the
+// previous call's reads of them are done.
+template <class T>
+__device__ __forceinline__ T dqo_block_exclusive(T x, T& total, T* s_wave) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T incl = x;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const T y = __shfl_up(incl, off);
+        if (lane >= off) incl += y;
+    }
+    __syncthreads();  // (s_wave may still be read by the previous call)
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    T before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        if (w < wave) before += s_wave[w];
+        all += s_wave[w];
+    }
+    total = all;
+    return before + incl - x;
+}
+
+// In the last block, by every thread: the blocks' counts a[0], a[stride], ... (n entries) become their exclusive prefix in index order,
+// in place, and every thread gets the total.  A thread takes PER consecutive entries of a round of 256 * PER; the total so far is
+// carried from round to round in a register.  Relaxed agent-scope loads and stores: dqo_last_block's fences (or the single-word ticket's,
+// dqo_select.h) order the loads behind the other blocks' stores, the kernel boundary orders the next launch's reads behind the stores.
+template <class T, int PER>
+__device__ __forceinline__ T dqo_scan_block_counts(T* a, size_t n, int stride, T* s_wave) {
+    T carry = 0;
+    for (size_t base = 0; base < n; base += 256 * PER) {
+        const size_t i0 = base + (size_t)threadIdx.x * PER;
+        T h[PER], sum = 0, total;
+#pragma unroll
+        for (int j = 0; j < PER; j++) {
+            h[j] = i0 + j < n ? __hip_atomic_load(&a[(i0 + j) * stride], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (T)0;
+            sum += h[j];
+        }
+        T run = carry + dqo_block_exclusive(sum, total, s_wave);
+#pragma unroll
+        for (int j = 0; j < PER; j++) {
+            if (i0 + j < n) __hip_atomic_store(&a[(i0 + j) * stride], run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            run += h[j];
+        }
+        carry += total;
+    }
+    return carry;
+}
+
+// The counts of a row pass (map_lifecycle.hip, map_prune.hip): acc[DQO_COUNT_LINES][64] int32 behind the workspace's head, word k of a
+// line is count k while the launch runs.  Same-address atomics are served one at a time memory-side (above), so a block counts on line
+// blockIdx % DQO_COUNT_LINES: one integer atomic per wave and count, ballot + popcount.
+enum { DQO_COUNT_LINES = 64 };
+__device__ __forceinline__ void dqo_line_count(int32_t* acc, int k, bool pred, int lane) {
+    const int n = __popcll(__ballot(pred));
+    if (lane == 0 && n > 0) atomicAdd(&acc[(blockIdx.x % DQO_COUNT_LINES) * 64 + k], n);
+}
+
+// In the last block, by every thread: wave w adds up counts 2w and 2w + 1 over the lines (lane = line) into stats[k], for the k of
+// `which` (a bit mask of the eight counts), and leaves their lines at zero.
+__device__ __forceinline__ void dqo_line_totals(int32_t* acc, uint32_t which, int32_t* stats) {
+    static_assert(DQO_COUNT_LINES == 64, "one lane per line");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int k = 2 * wave; k < 2 * wave + 2; k++) {
+        if (!((which >> k) & 1u)) continue;
+        const uint32_t n = dqo_wave_sum_u32((uint32_t)atomicExch(&acc[lane * 64 + k], 0), lane);
+        if (lane == 0) stats[k] = (int32_t)n;
+    }
 }
 
 // The block's sums of every thread's a[0 .. NSUM): lanes by the xor butterfly, then the four waves in order; sum q goes to

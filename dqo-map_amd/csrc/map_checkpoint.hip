@@ -83,25 +83,7 @@ __global__ __launch_bounds__(256) void map_pack_count_kernel(PkArgs a, int32_t* 
     if (!dqo_last_block(ticket, &s_last)) return;
     // the last block: pairs -> exclusive offsets, in block-index order.  Both halves of a pair stay below 2^31 (P does), so one 64-bit add
     // adds the two counts without a carry between them.
-    const int nb = (int)gridDim.x;
-    u64 carry = 0;
-    for (int base = 0; base < nb; base += 256) {
-        const int b = base + tid;
-        const u64 v = b < nb ? __hip_atomic_load(&a.pairs[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-        u64 incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const u64 up = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += up;
-        }
-        __syncthreads();  // (s_wave is free: the round before has read it)
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        u64 before = carry;
-        for (int w = 0; w < wave; w++) before += s_wave[w];
-        if (b < nb) a.pairs[b] = before + (incl - v);
-        carry += ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-    }
+    const u64 carry = dqo_scan_block_counts<u64, 1>(a.pairs, gridDim.x, 1, s_wave);
     if (tid == 0) a.header[0] = (int32_t)(uint32_t)carry, a.header[1] = (int32_t)(carry >> 32);
 }
 

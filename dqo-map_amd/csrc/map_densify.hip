@@ -6,7 +6,8 @@
 // min(N, sample_nums) of the N points of the kept rows by np.random.choice; here a virtual point gets the 32-bit key of dqo_sample_hash.h
 // (draw 3) and the n = min(N, cap) smallest keys are chosen: the same distribution, a pure function of the arguments.  fmix32 is a
 // bijection and v < 2^32, so two keys never tie: "key <= t" with t the n-th smallest key names exactly n points, and no rank pass is needed.
-// t is found by a radix select over three digits (11 + 11 + 10 bits), never by a sort:
+// t is found by a radix select over three digits (11 + 11 + 10 bits), never by a sort (dqo_select.h: the digit, the flush, the last
+// block's pick and its single-word ticket, shared with map_sample.hip; the scans over a block's threads and over the chunks: dqo_reduce.h):
 //
 //     zero            the workspace's head (histograms, tickets, state): the workspace needs no initialisation
 //     histogram x 3   keys of the kept rows' virtual points, one digit per launch, inside the bucket picked so far; a block's histogram is
@@ -36,7 +37,9 @@
 // with c = (b * levels + l) * circle_num + k.  A thread keeps the frame of the row it last formed: the consecutive chosen columns of a
 // row it emits share it.
 #include "dqo_common.h"
+#include "dqo_reduce.h"
 #include "dqo_sample_hash.h"
+#include "dqo_select.h"
 
 namespace {
 
@@ -44,11 +47,10 @@ enum {
     DN_THREADS = 256,
     DN_VPT = 8,                      // virtual points per thread: v = chunk * DN_CHUNK + thread * 8 + j
     DN_CHUNK = DN_THREADS * DN_VPT,
-    DN_BINS = 2048,
     DN_MAX_BLOCKS = 2048,
     // words of the workspace's head (zeroed by the first launch of every call)
-    DN_HIST = 0,                     // [3 levels][DN_BINS]
-    DN_TICKET = 3 * DN_BINS,         // [4] one per kernel that ends in a last block
+    DN_HIST = 0,                     // [3 levels][DQO_SELECT_BINS]
+    DN_TICKET = 3 * DQO_SELECT_BINS,  // [4] one per kernel that ends in a last block
     DN_STATE = DN_TICKET + 8,        // 0 key prefix / threshold t, 1 rank left in the bucket, 2 N, 4 n, 5 nothing is rejected (n == N)
     DN_HEAD_WORDS = DN_STATE + 56,
 };
@@ -70,45 +72,6 @@ struct DnArgs {
     uint32_t* head;
     uint32_t* chunk_count;  // [nchunks] chosen points of a chunk, then their exclusive prefix
 };
-
-__device__ __forceinline__ uint32_t dn_ld(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void dn_st(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// true (for every thread) in the block that took the launch's last ticket: it sees what every other block wrote before its own
-__device__ __forceinline__ bool dn_last_block(uint32_t* ticket) {
-    __shared__ int s_last;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        s_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!s_last) return false;
-    __threadfence();
-    return true;
-}
-
-// Exclusive prefix of `cnt` over the block's threads in thread order, and the block's total.  s_wave: 4 words of LDS.
-__device__ __forceinline__ uint32_t dn_block_exclusive(uint32_t cnt, uint32_t& total, uint32_t* s_wave) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t x = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)x, off);
-        if (lane >= off) x += y;
-    }
-    __syncthreads();  // (s_wave may still be read by the previous call)
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    uint32_t before = 0u, all = 0u;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        if (w < wave) before += s_wave[w];
-        all += s_wave[w];
-    }
-    total = all;
-    return before + x - cnt;
-}
 
 // f(j, key) for each of this thread's eight virtual points of `chunk` that lie in a kept row: v = chunk * DN_CHUNK + thread * 8 + j
 template <class F>
@@ -137,117 +100,62 @@ __device__ __forceinline__ uint32_t dn_chosen(const DnArgs& a, uint32_t chunk, u
     return mask;
 }
 
-// The last block picks the bucket of the k-th smallest key on this level: state[0] gets the digit appended, state[1] the rank inside the
-// bucket.  All 256 threads call it; k >= 1 and the bins hold k or more keys in all.
-__device__ __forceinline__ void dn_select(uint32_t* head, int level) {
-    __shared__ uint32_t s_part[DN_THREADS];
-    const int tid = threadIdx.x;
-    uint32_t* const state = head + DN_STATE;
-    const uint32_t k = dn_ld(&state[1]), prefix = dn_ld(&state[0]);
-    const uint32_t* const hist = head + DN_HIST + level * DN_BINS;
-    uint32_t h[8], sum = 0u;
-#pragma unroll
-    for (int j = 0; j < 8; j++) h[j] = dn_ld(&hist[tid * 8 + j]), sum += h[j];
-    s_part[tid] = sum;
-    __syncthreads();
-    uint32_t before = 0u;
-    for (int t = 0; t < tid; t++) before += s_part[t];
-    if (k >= 1u && before < k && k <= before + sum) {  // exactly one thread
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            if (k <= before + h[j]) {
-                dn_st(&state[0], (prefix << (level == 2 ? 10 : 11)) | (uint32_t)(tid * 8 + j));
-                dn_st(&state[1], k - before);
-                break;
-            }
-            before += h[j];
-        }
-    }
-    __syncthreads();
-}
-
 // ---- the histogram passes: one digit of the keys of the kept rows' virtual points, inside the bucket picked so far ----------------------
 template <int LEVEL>
 __global__ __launch_bounds__(DN_THREADS) void densify_hist_kernel(DnArgs a) {
-    __shared__ uint32_t s_hist[DN_BINS];
+    __shared__ uint32_t s_hist[DQO_SELECT_BINS];
     __shared__ uint32_t s_wave[4];
     const int tid = threadIdx.x;
+    uint32_t* const hist = a.head + DN_HIST + LEVEL * DQO_SELECT_BINS;
     if (LEVEL > 0 && a.head[DN_STATE + 5] != 0u) return;  // (every block: nothing is rejected, the first pass left t = 0xffffffff)
     const uint32_t prefix = LEVEL > 0 ? a.head[DN_STATE + 0] : 0u;
-    for (int i = tid; i < DN_BINS; i += DN_THREADS) s_hist[i] = 0u;
+    for (int i = tid; i < DQO_SELECT_BINS; i += DN_THREADS) s_hist[i] = 0u;
     __syncthreads();
     for (uint32_t chunk = blockIdx.x; chunk < a.nchunks; chunk += gridDim.x)
         dn_kept_points(a, chunk, [&](int, uint32_t key) {
-            if (LEVEL == 0) atomicAdd(&s_hist[key >> 21], 1u);
-            else if (LEVEL == 1) { if ((key >> 21) == prefix) atomicAdd(&s_hist[(key >> 10) & 2047u], 1u); }
-            else { if ((key >> 10) == prefix) atomicAdd(&s_hist[key & 1023u], 1u); }
+            if (dqo_select_in_bucket(key, prefix, LEVEL)) dqo_select_count(s_hist, key, LEVEL);
         });
     __syncthreads();
-    for (int i = tid; i < DN_BINS; i += DN_THREADS) {
-        const uint32_t v = s_hist[i];
-        if (v != 0u) atomicAdd(&a.head[DN_HIST + LEVEL * DN_BINS + i], v);
-    }
-    if (!dn_last_block(&a.head[DN_TICKET + LEVEL])) return;
+    dqo_select_flush(s_hist, hist);
+    if (!dqo_single_ticket_last_block(&a.head[DN_TICKET + LEVEL])) return;
     uint32_t* const state = a.head + DN_STATE;
     if (LEVEL == 0) {
         // N = the keys counted (P * M < 2^32: a word holds it), n = min(N, cap)
         uint32_t sum = 0u, N;
 #pragma unroll
-        for (int j = 0; j < 8; j++) sum += dn_ld(&a.head[DN_HIST + tid * 8 + j]);
-        dn_block_exclusive(sum, N, s_wave);
+        for (int j = 0; j < 8; j++) sum += dqo_ld_u32(&hist[tid * 8 + j]);
+        dqo_block_exclusive(sum, N, s_wave);
         if (tid == 0) {
             const uint32_t n = (uint64_t)N <= a.cap ? N : (uint32_t)a.cap;
-            dn_st(&state[1], n), dn_st(&state[2], N);
-            dn_st(&state[5], n == N ? 1u : 0u);
-            if (n == N) dn_st(&state[0], 0xffffffffu);
+            dqo_st_u32(&state[1], n), dqo_st_u32(&state[2], N);
+            dqo_st_u32(&state[5], n == N ? 1u : 0u);
+            if (n == N) dqo_st_u32(&state[0], 0xffffffffu);
             __threadfence();
         }
         __syncthreads();
-        if (dn_ld(&state[5]) != 0u) return;
+        if (dqo_ld_u32(&state[5]) != 0u) return;
     }
-    dn_select(a.head, LEVEL);
+    dqo_select_pick(hist, state, LEVEL);
 }
 
 // ---- the count pass: chosen points per chunk, and how many come before each chunk ----------------------------------------------------------
 __global__ __launch_bounds__(DN_THREADS) void densify_count_kernel(DnArgs a) {
     __shared__ uint32_t s_wave[4];
-    __shared__ uint32_t s_carry;
     const int tid = threadIdx.x;
     const uint32_t t = a.skip_select ? 0xffffffffu : a.head[DN_STATE + 0];
     for (uint32_t chunk = blockIdx.x; chunk < a.nchunks; chunk += gridDim.x) {
         uint32_t total;
-        dn_block_exclusive((uint32_t)__popc(dn_chosen(a, chunk, t)), total, s_wave);
-        if (tid == 0) dn_st(&a.chunk_count[chunk], total);
+        dqo_block_exclusive((uint32_t)__popc(dn_chosen(a, chunk, t)), total, s_wave);
+        if (tid == 0) dqo_st_u32(&a.chunk_count[chunk], total);
     }
-    if (!dn_last_block(&a.head[DN_TICKET + 3])) return;
-    // exclusive prefix of the chunks' counts in index order, in place: a thread takes eight consecutive chunks
-    if (tid == 0) s_carry = 0u;
-    __syncthreads();
-    for (uint32_t base = 0; base < a.nchunks; base += DN_CHUNK) {
-        uint32_t h[8], sum = 0u, total;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint64_t i = (uint64_t)base + (uint64_t)tid * 8 + j;
-            h[j] = i < a.nchunks ? dn_ld(&a.chunk_count[i]) : 0u;
-            sum += h[j];
-        }
-        uint32_t run = s_carry + dn_block_exclusive(sum, total, s_wave);
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint64_t i = (uint64_t)base + (uint64_t)tid * 8 + j;
-            if (i < a.nchunks) dn_st(&a.chunk_count[i], run);
-            run += h[j];
-        }
-        __syncthreads();
-        if (tid == 0) s_carry += total;
-        __syncthreads();
-    }
+    if (!dqo_single_ticket_last_block(&a.head[DN_TICKET + 3])) return;
+    // exclusive prefix of the chunks' counts in index order, in place: a thread takes eight consecutive chunks of a round
+    const uint32_t n = dqo_scan_block_counts<uint32_t, 8>(a.chunk_count, a.nchunks, 1, s_wave);
     if (tid == 0) {
         uint32_t* const state = a.head + DN_STATE;
-        const uint32_t n = s_carry;
-        const uint32_t N = a.skip_select ? n : dn_ld(&state[2]);
-        if (a.skip_select) dn_st(&state[0], t);
-        dn_st(&state[4], n);
+        const uint32_t N = a.skip_select ? n : dqo_ld_u32(&state[2]);
+        if (a.skip_select) dqo_st_u32(&state[0], t);
+        dqo_st_u32(&state[4], n);
         a.header[0] = (int32_t)(N / a.M), a.header[1] = (int32_t)N, a.header[2] = 0;  // (N < 2^32: the high word)
         a.header[3] = (int32_t)n, a.header[4] = (int32_t)a.M, a.header[5] = (int32_t)t, a.header[6] = a.frame, a.header[7] = 0;
     }
@@ -300,7 +208,7 @@ __global__ __launch_bounds__(DN_THREADS) void densify_emit_kernel(DnArgs a) {
         // two, and forming them where they are found runs the whole statement sequence below once per such lane and slot
         const uint32_t mask = dn_chosen(a, chunk, t);
         uint32_t total;
-        uint32_t pos = dn_block_exclusive((uint32_t)__popc(mask), total, s_wave);
+        uint32_t pos = dqo_block_exclusive((uint32_t)__popc(mask), total, s_wave);
         const uint32_t v0 = chunk * (uint32_t)DN_CHUNK + (uint32_t)tid * DN_VPT;  // (mask != 0: v0 < P * M < 2^32)
 #pragma unroll
         for (int j = 0; j < DN_VPT; j++)

@@ -25,14 +25,13 @@ namespace {
 // ticket words of dqo_reduce.h — the row kernels run one after the other and share them —, the results in free words of word 0's line,
 // and the frame's counts.  Same-address atomics are served one at a time memory-side (dqo_reduce.h): with ONE word per count the last row
 // kernel — whose two what-is-left counts take an atomic from every wave of the map — ran 272 us on a 550 k map
-// (profiles/lifecycle_single_counter_kernel_stats.csv), so the counts are spread over LC_LINES lines of 256 bytes that the last block of
+// (profiles/lifecycle_single_counter_kernel_stats.csv), so the counts are spread over DQO_COUNT_LINES lines of 256 bytes that the last block of
 // the last row kernel adds up.
 enum {
-    LC_LINES = 64,
     LC_COUNT = 4,          // [2] rows of the stable / unstable cloud the limits below were formed over
     LC_LIMIT = 6,          // [2] float bits: 10 x mean radius of the stable / unstable cloud
-    LC_ACC = DQO_REDUCE_HEAD_WORDS,  // [LC_LINES][64] word k of a line: count k of the frame while the row kernels run (DqoLifecycle.stats gets the sums)
-    LC_HEAD_WORDS = LC_ACC + LC_LINES * 64,
+    LC_ACC = DQO_REDUCE_HEAD_WORDS,  // [DQO_COUNT_LINES][64] word k of a line: count k of the frame while the row kernels run (DqoLifecycle.stats gets the sums)
+    LC_HEAD_WORDS = LC_ACC + DQO_COUNT_LINES * 64,
     LC_SUMS = 2,           // doubles per block partial: radius sum | member rows
     LC_STAGE = 128,        // partials staged through LDS at a time by the last block
 };
@@ -56,24 +55,6 @@ inline LcWorkspace lc_workspace(void* base) {
 __device__ __forceinline__ float lc_radius(const float* __restrict__ scaling_raw, size_t i) {
     const float a = expf(scaling_raw[3 * i]), b = expf(scaling_raw[3 * i + 1]), c = expf(scaling_raw[3 * i + 2]);
     return (((a + b) + c) - fminf(fminf(a, b), c)) / 2.f;
-}
-
-// FusedMapper._free_rows: the `freed` values of _ROW_BUFFERS, and nothing else
-__device__ __forceinline__ void lc_free_row(const DqoLifecycle& a, size_t i) {
-    a.xyz[3 * i] = a.park[0], a.xyz[3 * i + 1] = a.park[1], a.xyz[3 * i + 2] = a.park[2];
-    a.opacity_raw[i] = -10.f;
-    a.scaling_raw[3 * i] = -10.f, a.scaling_raw[3 * i + 1] = -10.f, a.scaling_raw[3 * i + 2] = -10.f;
-    a.alive[i] = 0;
-    a.row_flags[i] = DQO_ROW_HIDDEN | DQO_ROW_FROZEN;
-    a.confidence[i] = 0.f;
-    a.stable[i] = 0;
-    a.add_tick[i] = 0, a.depth_error_counter[i] = 0, a.color_error_counter[i] = 0;
-}
-
-// one integer atomic per wave and count: ballot + popcount, onto the block's line
-__device__ __forceinline__ void lc_count(int32_t* head, int k, bool pred, int lane) {
-    const int n = __popcll(__ballot(pred));
-    if (lane == 0 && n > 0) atomicAdd(&head[LC_ACC + (blockIdx.x % LC_LINES) * 64 + k], n);
 }
 
 // 10 x the mean radius of the rows with `member` set, over the whole launch: head[LC_LIMIT + which] (float bits) and the row count in
@@ -133,7 +114,7 @@ __global__ __launch_bounds__(256) void lifecycle_fix_kernel(DqoLifecycle a, LcWo
     const float radius = alive ? lc_radius(a.scaling_raw, i) : 0.f;
     // 0. gaussians_delete(unstable=False): oversized rows of the stable cloud (a cloud with a member has a limit)
     const bool big_stable = a.stable_oversized != 0 && stable && radius > __int_as_float(w.head[LC_LIMIT + 0]);
-    if (big_stable) lc_free_row(a, i), alive = stable = false;
+    if (big_stable) dqo_map_free_row(a, i), alive = stable = false;
     // 1. gaussians_fix
     const bool promoted = alive && !stable && a.confidence[i] > a.stable_confidence_thres;
     if (promoted) {
@@ -150,7 +131,7 @@ __global__ __launch_bounds__(256) void lifecycle_fix_kernel(DqoLifecycle a, LcWo
             by_depth = dc >= a.delete_thresh;
             released = !by_depth && cc >= a.delete_thresh;
             if (by_depth) {
-                lc_free_row(a, i), alive = stable = false;
+                dqo_map_free_row(a, i), alive = stable = false;
             } else {
                 if (v & 1u) a.depth_error_counter[i] = dc;
                 if (v & 2u) a.color_error_counter[i] = cc;
@@ -162,10 +143,10 @@ __global__ __launch_bounds__(256) void lifecycle_fix_kernel(DqoLifecycle a, LcWo
             }
         }
     }
-    lc_count(w.head, 0, promoted, lane);
-    lc_count(w.head, 1, released, lane);
-    lc_count(w.head, 2, by_depth, lane);
-    lc_count(w.head, 5, big_stable, lane);
+    dqo_line_count(w.head + LC_ACC, 0, promoted, lane);
+    dqo_line_count(w.head + LC_ACC, 1, released, lane);
+    dqo_line_count(w.head + LC_ACC, 2, by_depth, lane);
+    dqo_line_count(w.head + LC_ACC, 5, big_stable, lane);
     lc_cloud_limit(w, 1, radius, alive && !stable);
 }
 
@@ -178,19 +159,13 @@ __global__ __launch_bounds__(256) void lifecycle_delete_kernel(DqoLifecycle a, L
     const bool stable = alive && a.stable[i] != 0, unstable = alive && !stable;
     const bool big = unstable && lc_radius(a.scaling_raw, i) > __int_as_float(w.head[LC_LIMIT + 1]);
     const bool old = unstable && !big && a.tick - a.add_tick[i] > a.unstable_time_window;  // (a row that is both counts as oversized)
-    if (big || old) lc_free_row(a, i);
-    lc_count(w.head, 3, big, lane);
-    lc_count(w.head, 4, old, lane);
-    lc_count(w.head, 6, unstable && !big && !old, lane);
-    lc_count(w.head, 7, stable, lane);
+    if (big || old) dqo_map_free_row(a, i);
+    dqo_line_count(w.head + LC_ACC, 3, big, lane);
+    dqo_line_count(w.head + LC_ACC, 4, old, lane);
+    dqo_line_count(w.head + LC_ACC, 6, unstable && !big && !old, lane);
+    dqo_line_count(w.head + LC_ACC, 7, stable, lane);
     if (!dqo_last_block(w.head, &s_last)) return;
-    // the eight counts: wave w adds up counts 2w and 2w + 1 over the lines (lane = line) and leaves the lines at zero
-    const int wave = threadIdx.x >> 6;
-    static_assert(LC_LINES == 64, "one lane per line");
-    for (int k = 2 * wave; k < 2 * wave + 2; k++) {
-        const uint32_t n = dqo_wave_sum_u32((uint32_t)atomicExch(&w.head[LC_ACC + lane * 64 + k], 0), lane);
-        if (lane == 0) a.stats[k] = (int32_t)n;
-    }
+    dqo_line_totals(w.head + LC_ACC, 0xffu, a.stats);  // the eight counts
 }
 
 }  // namespace

@@ -151,7 +151,7 @@ __device__ __forceinline__ void ms_load4(const MsArgs& a, int64_t f0, u64 x[MS_F
 __global__ __launch_bounds__(MS_THREADS) void mesh_quantise_kernel(MsArgs a) {
     __shared__ u64 s_wave[4];
     __shared__ int s_last;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int e = a.state->e;
     const int64_t f0 = (int64_t)blockIdx.x * MS_BLOCK + (int64_t)tid * MS_FPT;
     u64 x[MS_FPT], sum = 0ull;
@@ -166,24 +166,7 @@ __global__ __launch_bounds__(MS_THREADS) void mesh_quantise_kernel(MsArgs a) {
     if (tid == 0) ms_st(&a.bsum[blockIdx.x], sum);
     if (!dqo_last_block(a.ticket, &s_last)) return;
     // the last block: the blocks' sums -> exclusive offsets, in block-index order
-    u64 carry = 0ull;
-    for (uint32_t base = 0; base < a.nblocks; base += MS_THREADS) {
-        const uint32_t b = base + (uint32_t)tid;
-        const u64 v = b < a.nblocks ? ms_ld(&a.bsum[b]) : 0ull;
-        u64 incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const u64 up = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += up;
-        }
-        __syncthreads();  // (s_wave is free: the round before has read it)
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        u64 before = carry;
-        for (int w = 0; w < wave; w++) before += s_wave[w];
-        if (b < a.nblocks) a.bsum[b] = before + (incl - v);
-        carry += ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-    }
+    const u64 carry = dqo_scan_block_counts<u64, 1>(a.bsum, a.nblocks, 1, s_wave);
     if (tid == 0) {
         a.state->total = carry;
         a.header[0] = carry != 0ull ? a.count : 0;
@@ -194,21 +177,11 @@ __global__ __launch_bounds__(MS_THREADS) void mesh_quantise_kernel(MsArgs a) {
 // ---- scan -------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MS_THREADS) void mesh_scan_kernel(MsArgs a) {
     __shared__ u64 s_wave[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t f0 = (int64_t)blockIdx.x * MS_BLOCK + (int64_t)tid * MS_FPT;
-    u64 x[MS_FPT];
+    u64 x[MS_FPT], total;
     ms_load4(a, f0, x);
-    const u64 own = ((x[0] + x[1]) + x[2]) + x[3];
-    u64 incl = own;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 up = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    u64 run = a.bsum[blockIdx.x] + (incl - own);
-    for (int w = 0; w < wave; w++) run += s_wave[w];
+    u64 run = a.bsum[blockIdx.x] + dqo_block_exclusive(((x[0] + x[1]) + x[2]) + x[3], total, s_wave);
 #pragma unroll
     for (int j = 0; j < MS_FPT; j++) {
         if (f0 + j >= (int64_t)a.F) break;

@@ -35,7 +35,7 @@
 //
 // prune_rows_kernel (dqo_prune_rows) — one launch, one thread per row: a row with alive != 0 && lo < frame_id <= hi is in the window
 // (:510-515); if every render was valid, a window row with touched == 0 is deleted (:519-527): what map_lifecycle.hip writes into a freed
-// row, and frame_id = 0.  Every touched word is cleared as it is read and the last block clears the render counts: the workspace goes back
+// row (dqo_map_free_row, dqo_common.h), and frame_id = 0.  Every touched word is cleared as it is read and the last block clears the render counts: the workspace goes back
 // ready for the next call.  The counts are integer atomics per wave on 64 lines that the block with the last ticket adds up (dqo_reduce.h).
 //
 // A row that map_lifecycle.hip frees keeps a stale frame_id (DqoLifecycle does not know the column): no kernel reads frame_id while
@@ -98,14 +98,13 @@ __global__ void prune_cameras_kernel(const float* __restrict__ viewmatrix, const
 // ---- dqo_prune_touch / dqo_prune_rows ---------------------------------------------------------------------------------------------
 
 // words of the workspace's head (int32; zero when the workspace is made, handed back at zero by dqo_prune_rows): the ticket words of
-// dqo_reduce.h, the two render counts in free words of word 0's line, and the call's counts spread over PR_LINES lines of 256 bytes
+// dqo_reduce.h, the two render counts in free words of word 0's line, and the call's counts spread over DQO_COUNT_LINES lines of 256 bytes
 // (same-address atomics are served one at a time memory-side: map_lifecycle.hip measured it)
 enum {
-    PR_LINES = 64,
     PR_INVALID = 2,  // renders that overflowed their capacity since the last dqo_prune_rows
     PR_VALID = 3,    // renders that marked rows
-    PR_ACC = DQO_REDUCE_HEAD_WORDS,  // [PR_LINES][64] word k of a line: count k of the call (stats gets the sums)
-    PR_HEAD_WORDS = PR_ACC + PR_LINES * 64,
+    PR_ACC = DQO_REDUCE_HEAD_WORDS,  // [DQO_COUNT_LINES][64] word k of a line: count k of the call (stats gets the sums)
+    PR_HEAD_WORDS = PR_ACC + DQO_COUNT_LINES * 64,
 };
 static_assert(PR_VALID < 16 && PR_HEAD_WORDS * 4 % 256 == 0, "workspace head layout");
 
@@ -130,26 +129,6 @@ struct PruneRows {
 };
 
 __host__ __device__ inline size_t pr_blocks(int64_t P) { return (size_t)((P + 255) / 256); }
-
-// the `freed` values of FusedMapper's _ROW_BUFFERS — map_lifecycle.hip's lc_free_row, kept as a local copy so that file's code stays as
-// it is — and the row's frame_id
-__device__ __forceinline__ void pr_free_row(const PruneRows& a, size_t i) {
-    a.xyz[3 * i] = a.park[0], a.xyz[3 * i + 1] = a.park[1], a.xyz[3 * i + 2] = a.park[2];
-    a.opacity_raw[i] = -10.f;
-    a.scaling_raw[3 * i] = -10.f, a.scaling_raw[3 * i + 1] = -10.f, a.scaling_raw[3 * i + 2] = -10.f;
-    a.alive[i] = 0;
-    a.row_flags[i] = DQO_ROW_HIDDEN | DQO_ROW_FROZEN;
-    a.confidence[i] = 0.f;
-    a.stable[i] = 0;
-    a.add_tick[i] = 0, a.depth_error_counter[i] = 0, a.color_error_counter[i] = 0;
-    a.frame_id[i] = 0;
-}
-
-// one integer atomic per wave and count: ballot + popcount, onto the block's line
-__device__ __forceinline__ void pr_count(int32_t* head, int k, bool pred, int lane) {
-    const int n = __popcll(__ballot(pred));
-    if (lane == 0 && n > 0) atomicAdd(&head[PR_ACC + (blockIdx.x % PR_LINES) * 64 + k], n);
-}
 
 __global__ __launch_bounds__(256) void prune_touch_kernel(int P, const int32_t* __restrict__ n_touched, const DqoRastHeader* __restrict__ header,
                                                           int32_t* __restrict__ head, uint32_t* __restrict__ touched) {
@@ -180,20 +159,13 @@ __global__ __launch_bounds__(256) void prune_rows_kernel(PruneRows a) {
     const bool window = alive && fid > a.lo && fid <= a.hi;
     const bool del = window && !touched && invalid == 0;
     const bool stable = del && a.stable[i] != 0;
-    if (del) pr_free_row(a, i);
-    pr_count(a.head, 0, window, lane);
-    pr_count(a.head, 1, del && !stable, lane);
-    pr_count(a.head, 2, del && stable, lane);
-    pr_count(a.head, 5, alive && !del, lane);
+    if (del) dqo_map_free_row(a, i), a.frame_id[i] = 0;
+    dqo_line_count(a.head + PR_ACC, 0, window, lane);
+    dqo_line_count(a.head + PR_ACC, 1, del && !stable, lane);
+    dqo_line_count(a.head + PR_ACC, 2, del && stable, lane);
+    dqo_line_count(a.head + PR_ACC, 5, alive && !del, lane);
     if (!dqo_last_block(a.head, &s_last)) return;
-    // the counts: wave w adds up counts 2w and 2w + 1 over the lines (lane = line) and leaves the lines at zero
-    const int wave = threadIdx.x >> 6;
-    static_assert(PR_LINES == 64, "one lane per line");
-    for (int k = 2 * wave; k < 2 * wave + 2; k++) {
-        if (k == 3 || k == 4 || k >= 6) continue;
-        const uint32_t n = dqo_wave_sum_u32((uint32_t)atomicExch(&a.head[PR_ACC + lane * 64 + k], 0), lane);
-        if (lane == 0) a.stats[k] = (int32_t)n;
-    }
+    dqo_line_totals(a.head + PR_ACC, 1u << 0 | 1u << 1 | 1u << 2 | 1u << 5, a.stats);  // the counts this kernel took
     if (threadIdx.x == 0) {  // (every block read the two words before it took its ticket)
         a.stats[3] = valid, a.stats[4] = invalid != 0 ? 1 : 0, a.stats[6] = 0, a.stats[7] = 0;
         atomicExch(&a.head[PR_INVALID], 0), atomicExch(&a.head[PR_VALID], 0);

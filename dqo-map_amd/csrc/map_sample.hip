@@ -3,14 +3,16 @@
 //
 // The reference draws k of a mask's n pixels with the first k of a CPU torch.randperm (SLAM/utils.py:185).  Here every pixel of the mask
 // gets a 32-bit key (dqo_sample_hash.h) and the k smallest (key, pixel) pairs are chosen: the same distribution, a pure function of the
-// arguments.  The k-th smallest key is found by a radix select over three digits (11 + 11 + 10 bits), never by a sort:
+// arguments.  The k-th smallest key is found by a radix select over three digits (11 + 11 + 10 bits), never by a sort (dqo_select.h: the
+// digit, the flush, the last block's pick and its single-word ticket, shared with map_densify.hip; this file keeps its two-draw histogram):
 //
 //     zero            the workspace's head (histograms, counts, tickets)
 //     pixel pass      both masks in registers, their counts before and after sample_pixels' in-place strip, one flag byte per pixel,
 //                     histogram of the keys' top digit; the last block forms both k and picks each draw's bucket
 //     refine x 2      histogram of the next digit over the pixels inside the bucket; the last block picks the next bucket.  After the
 //                     second one a draw has its threshold key t and the number r of pixels with key == t it takes (lowest pixels first)
-//     rank pass       per block: pixels with key == t; the last block scans them over the blocks in index order
+//     rank pass       per block: pixels with key == t; the last block scans them over the blocks in index order (dqo_reduce.h's
+//                     dqo_scan_block_counts, as in the rows pass: [blocks][2], one column per draw)
 //     rows pass       per block: chosen pixels (key < t, or key == t among the first r) whose normalised normal does not sum to 0
 //                     (gaussian_pointcloud.py:457); the last block scans them in index order and writes the header
 //     emit pass       ordered compaction by ballot and prefix: rows in ascending pixel index, draw A's before draw B's
@@ -20,7 +22,9 @@
 // reduced per block first (one atomic per block and count, a few hundred to a word per frame — no need to spread them over lines).
 // This file is compiled with -ffp-contract=off: every float statement below is the reference's, rounded where torch rounds it.
 #include "dqo_common.h"
+#include "dqo_reduce.h"
 #include "dqo_sample_hash.h"
+#include "dqo_select.h"
 
 namespace {
 
@@ -28,11 +32,10 @@ enum {
     SP_THREADS = 256,
     SP_PPT = 2,                      // pixels per thread: pixel = block * SP_PIX + j * 256 + thread
     SP_PIX = SP_THREADS * SP_PPT,
-    SP_BINS = 2048,
     // words of the workspace's head (zeroed by the first launch of every call)
-    SP_HIST = 0,                     // [2 draws][3 levels][SP_BINS]
-    SP_CNT = 2 * 3 * SP_BINS,        // [5] A before / after the strip, B before / after, B's pixels that leave if trans is not stripped
-    SP_TICKET = SP_CNT + 8,          // [4] one per kernel that ends in a last block
+    SP_HIST = 0,                     // [2 draws][3 levels][DQO_SELECT_BINS]
+    SP_CNT = 2 * 3 * DQO_SELECT_BINS,  // [5] A before / after the strip, B before / after, B's pixels that leave if trans is not stripped
+    SP_TICKET = SP_CNT + 8,          // [8] one per kernel that ends in a last block: five kernels, words 0..4
     SP_STATE = SP_TICKET + 8,        // [2 draws][8]: 0 key prefix / threshold t, 1 k left / r, 2 clamped k, 3 rows of the draw
     SP_HEAD_WORDS = SP_STATE + 16 + 32,
     // flag byte of a pixel
@@ -64,106 +67,26 @@ struct SpKeys {
     uint32_t seed_word, draw_word[2], key_mask;
 };
 
-__device__ __forceinline__ uint32_t sp_ld(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void sp_st(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// true (for every thread) in the block that took the launch's last ticket: it sees what every other block wrote before its own
-__device__ __forceinline__ bool sp_last_block(uint32_t* ticket) {
-    __shared__ int s_last;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        s_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!s_last) return false;
-    __threadfence();
-    return true;
-}
-
-__device__ __forceinline__ uint32_t sp_digit(uint32_t key, int level) {
-    return level == 0 ? key >> 21 : level == 1 ? (key >> 10) & 2047u : key & 1023u;
-}
-// whether `key` lies in the bucket the levels above `level` picked (prefix: the digits picked so far)
-__device__ __forceinline__ bool sp_in_bucket(uint32_t key, uint32_t prefix, int level) {
-    return level == 0 ? true : level == 1 ? (key >> 21) == prefix : (key >> 10) == prefix;
-}
+// draw d's histogram of a level in the workspace's head
+__device__ __forceinline__ uint32_t* sp_hist(uint32_t* head, int level, int d) { return head + SP_HIST + (d * 3 + level) * DQO_SELECT_BINS; }
 
 // The block's histogram of one digit, both draws: LDS first, its non-zero bins to memory.  in[d][j]: pixel j of this thread counts for draw d.
 __device__ __forceinline__ void sp_histogram(uint32_t* head, int level, const uint32_t key[2][SP_PPT], const bool in[2][SP_PPT]) {
-    __shared__ uint32_t s_hist[2 * SP_BINS];
-    const int tid = threadIdx.x;
-    for (int i = tid; i < 2 * SP_BINS; i += SP_THREADS) s_hist[i] = 0u;
+    __shared__ uint32_t s_hist[2 * DQO_SELECT_BINS];
+    for (int i = threadIdx.x; i < 2 * DQO_SELECT_BINS; i += SP_THREADS) s_hist[i] = 0u;
     __syncthreads();
 #pragma unroll
     for (int d = 0; d < 2; d++)
 #pragma unroll
         for (int j = 0; j < SP_PPT; j++)
-            if (in[d][j]) atomicAdd(&s_hist[d * SP_BINS + sp_digit(key[d][j], level)], 1u);
+            if (in[d][j]) dqo_select_count(s_hist + d * DQO_SELECT_BINS, key[d][j], level);
     __syncthreads();
-    for (int i = tid; i < 2 * SP_BINS; i += SP_THREADS) {
-        const uint32_t v = s_hist[i];
-        if (v != 0u) atomicAdd(&head[SP_HIST + ((i / SP_BINS) * 3 + level) * SP_BINS + (i % SP_BINS)], v);
-    }
+    for (int d = 0; d < 2; d++) dqo_select_flush(s_hist + d * DQO_SELECT_BINS, sp_hist(head, level, d));
 }
 
-// The last block picks the bucket of draw d's k-th smallest key on this level: state[0] gets the digit appended, state[1] the rank
-// inside the bucket.  k == 0 leaves (0, 0): threshold 0 with nothing taken at it.  All 256 threads call it.
-__device__ __forceinline__ void sp_select(uint32_t* head, int level, int d) {
-    __shared__ uint32_t s_part[SP_THREADS];
-    const int tid = threadIdx.x;
-    uint32_t* const state = head + SP_STATE + 8 * d;
-    const uint32_t k = sp_ld(&state[1]), prefix = sp_ld(&state[0]);
-    const uint32_t* const hist = head + SP_HIST + (d * 3 + level) * SP_BINS;
-    uint32_t h[8], sum = 0u;
-#pragma unroll
-    for (int j = 0; j < 8; j++) h[j] = sp_ld(&hist[tid * 8 + j]), sum += h[j];
-    __syncthreads();  // (s_part may still be read by the previous call)
-    s_part[tid] = sum;
-    __syncthreads();
-    uint32_t before = 0u;
-    for (int t = 0; t < tid; t++) before += s_part[t];
-    if (k >= 1u && before < k && k <= before + sum) {  // exactly one thread: the bins are counts of k or more pixels in all
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            if (k <= before + h[j]) {
-                sp_st(&state[0], (prefix << (level == 2 ? 10 : 11)) | (uint32_t)(tid * 8 + j));
-                sp_st(&state[1], k - before);
-                break;
-            }
-            before += h[j];
-        }
-    }
-    __syncthreads();
-}
-
-// Exclusive prefix of a[0], a[stride], ... (n entries) in index order, in place, by the 256 threads of one block; returns the total.
-__device__ __forceinline__ uint32_t sp_scan_blocks(uint32_t* a, int stride, size_t n) {
-    __shared__ uint32_t s_scan[SP_THREADS];
-    __shared__ uint32_t s_carry;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_carry = 0u;
-    __syncthreads();
-    for (size_t base = 0; base < n; base += SP_THREADS) {
-        const size_t i = base + tid;
-        const uint32_t v = i < n ? sp_ld(&a[i * stride]) : 0u;
-        s_scan[tid] = v;
-        __syncthreads();
-        for (int off = 1; off < SP_THREADS; off <<= 1) {  // (integers: any order gives the same sums)
-            const uint32_t t = tid >= off ? s_scan[tid - off] : 0u;
-            __syncthreads();
-            s_scan[tid] += t;
-            __syncthreads();
-        }
-        const uint32_t carry = s_carry;
-        if (i < n) sp_st(&a[i * stride], carry + s_scan[tid] - v);
-        __syncthreads();
-        if (tid == SP_THREADS - 1) s_carry = carry + s_scan[tid];
-        __syncthreads();
-    }
-    const uint32_t total = s_carry;
-    __syncthreads();  // (the next call starts by clearing s_carry)
-    return total;
+// The last block picks the level's bucket of both draws (dqo_select.h: state[0] the key prefix, state[1] the rank left)
+__device__ __forceinline__ void sp_select(uint32_t* head, int level) {
+    for (int d = 0; d < 2; d++) dqo_select_pick(sp_hist(head, level, d), head + SP_STATE + 8 * d, level);
 }
 
 // Rank of this thread's pixel j among the block's pixels with pred set, in pixel order (j, wave, lane), and the block's count.
@@ -250,30 +173,29 @@ __global__ __launch_bounds__(SP_THREADS) void sample_pixel_kernel(DqoGrowthSampl
     __syncthreads();
     if (tid < 5 && s_cnt[tid] != 0u) atomicAdd(&w.head[SP_CNT + tid], s_cnt[tid]);
     sp_histogram(w.head, 0, key, in);
-    if (!sp_last_block(&w.head[SP_TICKET + 0])) return;
+    if (!dqo_single_ticket_last_block(&w.head[SP_TICKET + 0])) return;
     if (tid == 0) {
-        const uint32_t a_pre = sp_ld(&w.head[SP_CNT + 0]), a_post = sp_ld(&w.head[SP_CNT + 1]), b_post = sp_ld(&w.head[SP_CNT + 3]);
-        uint32_t b_pre = sp_ld(&w.head[SP_CNT + 2]);
+        const uint32_t a_pre = dqo_ld_u32(&w.head[SP_CNT + 0]), a_post = dqo_ld_u32(&w.head[SP_CNT + 1]), b_post = dqo_ld_u32(&w.head[SP_CNT + 3]);
+        uint32_t b_pre = dqo_ld_u32(&w.head[SP_CNT + 2]);
         int64_t k_a, k_b = 0;
         if (a.first_frame) {
             k_a = a.uniform_sample_num;  // mapper.py:1242
         } else {
             const float ratio = (float)a_pre / (float)HW;                                            // :1254-1256
             k_a = (int64_t)((a.transmission_sample_ratio * ratio) * (float)a.uniform_sample_num);  // :1258-1262, devI truncates
-            if (k_a == 0) b_pre -= sp_ld(&w.head[SP_CNT + 4]);
+            if (k_a == 0) b_pre -= dqo_ld_u32(&w.head[SP_CNT + 4]);
             k_b = (int64_t)((float)b_pre * a.error_sample_ratio);  // :1327
         }
         k_a = k_a < 0 ? 0 : k_a > (int64_t)a_post ? (int64_t)a_post : k_a;  // utils.py:176-177
         k_b = k_b < 0 ? 0 : k_b > (int64_t)b_post ? (int64_t)b_post : k_b;
-        sp_st(&w.head[SP_STATE + 1], (uint32_t)k_a), sp_st(&w.head[SP_STATE + 2], (uint32_t)k_a);
-        sp_st(&w.head[SP_STATE + 8 + 1], (uint32_t)k_b), sp_st(&w.head[SP_STATE + 8 + 2], (uint32_t)k_b);
+        dqo_st_u32(&w.head[SP_STATE + 1], (uint32_t)k_a), dqo_st_u32(&w.head[SP_STATE + 2], (uint32_t)k_a);
+        dqo_st_u32(&w.head[SP_STATE + 8 + 1], (uint32_t)k_b), dqo_st_u32(&w.head[SP_STATE + 8 + 2], (uint32_t)k_b);
         a.header[0] = (int32_t)a_pre, a.header[1] = (int32_t)a_post, a.header[2] = (int32_t)b_pre, a.header[3] = (int32_t)b_post;
         a.header[4] = (int32_t)k_a, a.header[5] = (int32_t)k_b;
         __threadfence();
     }
     __syncthreads();
-    sp_select(w.head, 0, 0);
-    sp_select(w.head, 0, 1);
+    sp_select(w.head, 0);
 }
 
 // a pixel's flags and keys as the later passes need them
@@ -298,18 +220,17 @@ __global__ __launch_bounds__(SP_THREADS) void sample_refine_kernel(SpWorkspace w
     const uint32_t prefix[2] = {w.head[SP_STATE + 0], w.head[SP_STATE + 8]};
 #pragma unroll
     for (int j = 0; j < SP_PPT; j++) {
-        in[0][j] = (flag[j] & SP_IN_A) && sp_in_bucket(key[0][j], prefix[0], LEVEL);
-        in[1][j] = (flag[j] & SP_IN_B) && sp_in_bucket(key[1][j], prefix[1], LEVEL);
+        in[0][j] = (flag[j] & SP_IN_A) && dqo_select_in_bucket(key[0][j], prefix[0], LEVEL);
+        in[1][j] = (flag[j] & SP_IN_B) && dqo_select_in_bucket(key[1][j], prefix[1], LEVEL);
     }
     sp_histogram(w.head, LEVEL, key, in);
-    if (!sp_last_block(&w.head[SP_TICKET + LEVEL])) return;
-    sp_select(w.head, LEVEL, 0);
-    sp_select(w.head, LEVEL, 1);
+    if (!dqo_single_ticket_last_block(&w.head[SP_TICKET + LEVEL])) return;
+    sp_select(w.head, LEVEL);
 }
 
 // ---- the rank pass: ties at the threshold key go to the lowest pixels, so a block needs the ties in the blocks before it ----------------
 __global__ __launch_bounds__(SP_THREADS) void sample_rank_kernel(SpWorkspace w, SpKeys keys, int64_t HW) {
-    __shared__ uint32_t s_seg[SP_PPT * 4];
+    __shared__ uint32_t s_seg[SP_PPT * 4], s_wave[4];
     uint8_t flag[SP_PPT];
     uint32_t key[2][SP_PPT], rank[SP_PPT], total;
     bool eq[SP_PPT];
@@ -320,16 +241,15 @@ __global__ __launch_bounds__(SP_THREADS) void sample_rank_kernel(SpWorkspace w, 
 #pragma unroll
         for (int j = 0; j < SP_PPT; j++) eq[j] = (flag[j] & (d == 0 ? SP_IN_A : SP_IN_B)) && key[d][j] == t;
         sp_block_rank(eq, rank, total, s_seg);
-        if (threadIdx.x == 0) sp_st(&w.blk_eq[2 * (size_t)blockIdx.x + d], total);
+        if (threadIdx.x == 0) dqo_st_u32(&w.blk_eq[2 * (size_t)blockIdx.x + d], total);
     }
-    if (!sp_last_block(&w.head[SP_TICKET + 3])) return;
-    sp_scan_blocks(w.blk_eq, 2, gridDim.x);
-    sp_scan_blocks(w.blk_eq + 1, 2, gridDim.x);
+    if (!dqo_single_ticket_last_block(&w.head[SP_TICKET + 3])) return;
+    for (int d = 0; d < 2; d++) dqo_scan_block_counts<uint32_t, 1>(w.blk_eq + d, gridDim.x, 2, s_wave);
 }
 
 // ---- the rows pass: which chosen pixels become rows (gaussian_pointcloud.py:455-460), and how many come before each block ---------------
 __global__ __launch_bounds__(SP_THREADS) void sample_rows_kernel(DqoGrowthSample a, SpWorkspace w, SpKeys keys, int64_t HW) {
-    __shared__ uint32_t s_seg[SP_PPT * 4];
+    __shared__ uint32_t s_seg[SP_PPT * 4], s_wave[4];
     uint8_t flag[SP_PPT];
     uint32_t key[2][SP_PPT], rank[SP_PPT], total;
     bool eq[SP_PPT], row[SP_PPT];
@@ -356,19 +276,19 @@ __global__ __launch_bounds__(SP_THREADS) void sample_rows_kernel(DqoGrowthSample
             if (row[j]) flag[j] |= (uint8_t)row_bit;
         }
         sp_block_rank(row, rank, total, s_seg);
-        if (threadIdx.x == 0) sp_st(&w.blk_rows[2 * (size_t)blockIdx.x + d], total);
+        if (threadIdx.x == 0) dqo_st_u32(&w.blk_rows[2 * (size_t)blockIdx.x + d], total);
     }
 #pragma unroll
     for (int j = 0; j < SP_PPT; j++) {
         const int64_t p = (int64_t)blockIdx.x * SP_PIX + j * SP_THREADS + threadIdx.x;
         if (p < HW && (flag[j] & (SP_ROW_A | SP_ROW_B))) w.flags[p] = flag[j];
     }
-    if (!sp_last_block(&w.head[SP_TICKET + 4])) return;
-    const uint32_t rows_a = sp_scan_blocks(w.blk_rows, 2, gridDim.x);
-    const uint32_t rows_b = sp_scan_blocks(w.blk_rows + 1, 2, gridDim.x);
+    if (!dqo_single_ticket_last_block(&w.head[SP_TICKET + 4])) return;
+    const uint32_t rows_a = dqo_scan_block_counts<uint32_t, 1>(w.blk_rows, gridDim.x, 2, s_wave);
+    const uint32_t rows_b = dqo_scan_block_counts<uint32_t, 1>(w.blk_rows + 1, gridDim.x, 2, s_wave);
     if (threadIdx.x == 0) {
         const uint64_t rows = (uint64_t)rows_a + rows_b;
-        sp_st(&w.head[SP_STATE + 3], rows_a);
+        dqo_st_u32(&w.head[SP_STATE + 3], rows_a);
         a.header[6] = (int32_t)(rows > (uint64_t)a.capacity ? (uint64_t)a.capacity : rows);
         a.header[7] = rows > (uint64_t)a.capacity ? 1 : 0;
     }

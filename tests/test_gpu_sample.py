@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import sample_cases as sc
-from sample_oracle import rotations, sample_oracle
+from sample_oracle import rotations, sample_keys, sample_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -101,6 +101,26 @@ def test_ties_go_to_the_lower_pixel(first, key_bits):
     kw = dict(sc.SMALL, seed=21, key_bits=key_bits)
     want = sample_oracle(frame, None if first else model, **kw)
     got, header = _run(frame, None if first else model, **kw)
+    _assert_rows(got, header, want, False)
+
+
+def test_ties_in_the_second_round_of_the_block_scan_carry_the_first_rounds_total():
+    """512 x 258, every pixel in the mask: 258 blocks, so the last block turns the blocks' tie counts into offsets in two rounds of 256.
+    Three key bits put about 64 ties at the threshold key into every block, and k cuts them inside block 256: the ties of blocks 256 and
+    257 are chosen or left out by the total the first round carries into the second."""
+    H, W, seed, t, cut = 258, 512, 21, 4, 256 * 512 + 300
+    pixels = np.arange(H * W)
+    frame, _ = sc.blank_frame(H, W, pixels)
+    keys = sample_keys(seed, 0, pixels, 3)
+    k = int((keys < t).sum() + ((keys == t) & (pixels < cut)).sum())
+    kw = dict(sc.DEFAULTS, uniform_sample_num=k, seed=seed, key_bits=3)
+    want = sample_oracle(frame, None, **kw)
+    assert want["header"]["k_a"] == k == want["header"]["rows"]
+    chosen = np.zeros(H * W, bool)
+    chosen[want["pixel"]] = True
+    assert np.any(chosen[256 * 512:] & (keys[256 * 512:] == t)), "a tie behind the first round's 256 blocks is chosen"
+    assert np.any(~chosen[cut:] & (keys[cut:] == t)), "a tie behind the cut is left out"
+    got, header = _run(frame, None, **kw)
     _assert_rows(got, header, want, False)
 
 
