@@ -218,6 +218,22 @@ DQO_API int dqo_rast_forward(const DqoRastParams* p, const DqoRastInputs* in, Dq
     return dqo_launch_forward_render(p, in, out, ctx, (hipStream_t)stream);
 }
 
+// The training form: the caller's struct is checked like every forward's, then the launches get a copy without the auxiliary members.
+// NULL there is what selects the lean blend kernel (dqo_launch_blend_forward) and keeps K1 from zeroing n_touched; no other entry point
+// lets a NULL output through.
+DQO_API int dqo_rast_forward_train(const DqoRastParams* p, const DqoRastInputs* in, DqoRastOutputs* out, DqoRastCtx* ctx, void* stream) {
+    int rc = check_render(p, in, out, ctx);
+    if (rc) return rc;
+    DQO_CHECK_ARG(ctx->loss_tap != nullptr, "dqo_rast_forward_train: without a loss tap the loss reads out_hit_depth");
+    DQO_CHECK_ARG(dqo_list_split(ctx) == 0, "dqo_rast_forward_train: the list-split blend kernels have no training form");
+    DqoRastOutputs lean = *out;
+    lean.out_hit_color = nullptr, lean.out_hit_depth = nullptr, lean.out_hit_color_weight = nullptr, lean.out_hit_depth_weight = nullptr;
+    lean.out_T = nullptr, lean.n_touched = nullptr;
+    rc = dqo_launch_forward_prepare(p, in, &lean, ctx, (hipStream_t)stream);
+    if (rc) return rc;
+    return dqo_launch_forward_render(p, in, &lean, ctx, (hipStream_t)stream);
+}
+
 DQO_API int dqo_rast_forward_async(const DqoRastParams* p, const DqoRastInputs* in, DqoRastOutputs* out, DqoRastCtx* ctx,
                                    DqoRastHeader* header_host, void* header_event, void* stream) {
     int rc = check_render(p, in, out, ctx);  // (covers the checks of the first stage)

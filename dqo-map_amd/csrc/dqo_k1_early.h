@@ -19,7 +19,7 @@ struct K1Early {
     float4 co, xy;                   // what went into g.conic_opacity / g.xy_depth (only written when radius > 0)
 };
 
-// Writes the Gaussian's rows of conic_opacity / xy_depth (visible ones), rect16, radii and n_touched (all of them), and — LATE — the
+// Writes the Gaussian's rows of conic_opacity / xy_depth (visible ones), rect16, radii and n_touched (all of them; n_touched may be NULL), and — LATE — the
 // late part's tables.  view / proj: the matrices in registers (wave-uniform loads of the caller).
 template <bool LATE, bool PF = false>
 __device__ __forceinline__ K1Early k1_early(const DqoView& v, const float (&view)[16], const float (&proj)[16], const float cam0,
@@ -120,7 +120,7 @@ __device__ __forceinline__ K1Early k1_early(const DqoView& v, const float (&view
         g.xy_depth[idx] = e.xy;
     } while (false);
     radii_out[idx] = radius;
-    n_touched_out[idx] = 0;
+    if (n_touched_out != nullptr) n_touched_out[idx] = 0;  // (NULL: the training form of the forward, which counts no touches)
     g.rect16[idx] = make_uint2((uint32_t)rminx | ((uint32_t)rmaxx << 16), (uint32_t)rminy | ((uint32_t)rmaxy << 16));
     e.radius = radius, e.rminx = rminx, e.rminy = rminy, e.rmaxx = rmaxx, e.rmaxy = rmaxy;
     return e;

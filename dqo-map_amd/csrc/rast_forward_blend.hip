@@ -232,7 +232,11 @@ constexpr int PART_STRIDE = FWD_BLK * 4;                    // floats per wave b
 constexpr int PART_WORDS = 14;                              // merge record of one (run, pixel): 14 x 64 floats <= PART_STRIDE (word 9 unused)
 static_assert(PART_WORDS * FWD_THREADS <= PART_STRIDE, "the merge record lives in the wave's own LDS block");
 
-template <bool GATE, int SEGS, bool PF>
+// AUX: the auxiliary outputs are wanted — out_hit_color / _weight (the running maximum of the blend weights), out_hit_depth /
+// _weight, out_T and n_touched (the T' > 0.5 count, its atomics).  !AUX is the training form of an iteration whose render nobody
+// reads (the inner iterations of an unrolled graph, dqo_rast_forward_train): everything the backward, the loss tap and the tail read
+// is kept — colour, depth, the hit id for the tap, hit_pos, n_contrib, final_T, walk4, live bytes and row codes — bit for bit.
+template <bool GATE, int SEGS, bool PF, bool AUX>
 __device__ __forceinline__ void blend_quadrant(const DqoView& v, const DqoGeomLayout& g, const DqoImageLayout& img, const DqoBinLayout& bin,
                                                const DqoRastOutputs& out, const DqoTapDev& tap, const DqoGateDev& gate, const int tile,
                                                const int quad, const int wave, const int lane, float4* const lds, const int skip_over,
@@ -283,11 +287,13 @@ __device__ __forceinline__ void blend_quadrant(const DqoView& v, const DqoGeomLa
             out.out_color[HW + pix_id] = rendered ? v.bg[1] : 0.f;
             out.out_color[2 * HW + pix_id] = rendered ? v.bg[2] : 0.f;
             out.out_depth[pix_id] = 0.f;
-            out.out_hit_depth[pix_id] = rendered ? -1 : 0;
-            out.out_hit_color[pix_id] = rendered ? -1 : 0;
-            out.out_hit_color_weight[pix_id] = 0.f;
-            out.out_hit_depth_weight[pix_id] = 0.f;
-            out.out_T[pix_id] = 1.f;
+            if (AUX) {
+                out.out_hit_depth[pix_id] = rendered ? -1 : 0;
+                out.out_hit_color[pix_id] = rendered ? -1 : 0;
+                out.out_hit_color_weight[pix_id] = 0.f;
+                out.out_hit_depth_weight[pix_id] = 0.f;
+                out.out_T[pix_id] = 1.f;
+            }
             img.final_T[pix_id] = 1.f;
             img.n_contrib[pix_id] = 0;
             img.hit_pos[pix_id] = 0;
@@ -353,7 +359,7 @@ __device__ __forceinline__ void blend_quadrant(const DqoView& v, const DqoGeomLa
                     // and its two gathers runs ONCE per pixel behind the walk (finish_hit) — inside the loop it ran once per distinct
                     // hit entry of the quadrant, each time behind a vmcnt(0) wait that also drained the next chunk's prefetch
                     hit_id = (int)sel_u(hit_m, (uint32_t)gid, (uint32_t)hit_id);
-                    hit_depth_weight = sel_f(hit_m, alpha * T, hit_depth_weight);
+                    if (AUX) hit_depth_weight = sel_f(hit_m, alpha * T, hit_depth_weight);
                     hit_pos = sel_u(hit_m, contributor, hit_pos);
                     fixed_m |= hit_m;
                 }
@@ -365,10 +371,12 @@ __device__ __forceinline__ void blend_quadrant(const DqoView& v, const DqoGeomLa
                 C0 += cs.x * w;
                 C1 += cs.y * w;
                 C2 += cs.z * w;
-                const lanemask newmax_m = blend_m & m_gt(w, color_weight_max);
-                color_weight_max = sel_f(newmax_m, w, color_weight_max);
-                hit_color_id = (int)sel_u(newmax_m, (uint32_t)gid, (uint32_t)hit_color_id);
-                if (SEGS > 1) wmax_pos = sel_u(newmax_m, contributor, wmax_pos);  // (the waves' maxima are merged by list position)
+                if (AUX) {
+                    const lanemask newmax_m = blend_m & m_gt(w, color_weight_max);
+                    color_weight_max = sel_f(newmax_m, w, color_weight_max);
+                    hit_color_id = (int)sel_u(newmax_m, (uint32_t)gid, (uint32_t)hit_color_id);
+                    if (SEGS > 1) wmax_pos = sel_u(newmax_m, contributor, wmax_pos);  // (the waves' maxima are merged by list position)
+                }
                 last_contributor = sel_u(blend_m, contributor, last_contributor);
                 end_T = sel_f(blend_m, test_T, end_T);
                 T = sel_f(finish_m, T, test_T);  // keeps decaying below T_thr until an opaque hit appears (forward.cu:841)
@@ -378,8 +386,13 @@ __device__ __forceinline__ void blend_quadrant(const DqoView& v, const DqoGeomLa
                 // below T_threshold), so the backward never misses a pair it has work for.  The per-entry results are
                 // wave-uniform: n_touched count | WHICH 16-lane rows (4x4 pixel blocks, dqo_lane_x / _y) saw the entry (the backward's
                 // rows walk their own sub-lists), one word of the entry's record.
-                const lanemask half_m = blend_m & m_lt_half(test_T);
-                lds_st1i(ea + 56, (int)__popcll(half_m) | (int)(dqo_row_code(valid_m) << 8));
+                // (!AUX: the row code alone)
+                if (AUX) {
+                    const lanemask half_m = blend_m & m_lt_half(test_T);
+                    lds_st1i(ea + 56, (int)__popcll(half_m) | (int)(dqo_row_code(valid_m) << 8));
+                } else {
+                    lds_st1i(ea + 56, (int)(dqo_row_code(valid_m) << 8));
+                }
             }
         }
     };
@@ -399,7 +412,7 @@ __device__ __forceinline__ void blend_quadrant(const DqoView& v, const DqoGeomLa
             e[2] = cs_me;
             // (the reference's running counter `contributor` = list position + 1; the result word starts at "not live")
             *reinterpret_cast<int4*>(e + 3) = make_int4(id, pos + 1, 0, 0);
-            s_idt[myk] = id;
+            if (AUX) s_idt[myk] = id;
         }
         return myk;
     };
@@ -407,8 +420,10 @@ __device__ __forceinline__ void blend_quadrant(const DqoView& v, const DqoGeomLa
     // (coalesced 64-byte store)
     auto chunk_results = [&](int pos, bool reach, int myk) {
         const int* const res = reinterpret_cast<const int*>(s_ent) + 14;  // entry k: res[16 k]
-        const int half_k = lane < cnt ? (res[16 * lane] & 0xff) : 0;
-        if (half_k > 0) atomicAdd(&out.n_touched[s_idt[lane]], half_k);
+        if (AUX) {
+            const int half_k = lane < cnt ? (res[16 * lane] & 0xff) : 0;
+            if (half_k > 0) atomicAdd(&out.n_touched[s_idt[lane]], half_k);
+        }
         // live byte = the entry's row code (0: no pixel of the quadrant has work for it)
         if (pos < n) live[pos] = reach ? (uint8_t)((res[16 * myk] >> 8) & 0xf) : (uint8_t)0;
     };
@@ -570,11 +585,13 @@ __device__ __forceinline__ void blend_quadrant(const DqoView& v, const DqoGeomLa
         out.out_color[HW + pix_id] = oc1;
         out.out_color[2 * HW + pix_id] = oc2;
         out.out_depth[pix_id] = depth_;
-        out.out_hit_depth[pix_id] = hit_id;
-        out.out_hit_color[pix_id] = hit_color_id;
-        out.out_hit_color_weight[pix_id] = fmaxf(color_weight_max, 0.f);  // the running maximum IS the recorded weight (0 if none)
-        out.out_hit_depth_weight[pix_id] = hit_depth_weight;
-        out.out_T[pix_id] = end_T;
+        if (AUX) {
+            out.out_hit_depth[pix_id] = hit_id;
+            out.out_hit_color[pix_id] = hit_color_id;
+            out.out_hit_color_weight[pix_id] = fmaxf(color_weight_max, 0.f);  // the running maximum IS the recorded weight (0 if none)
+            out.out_hit_depth_weight[pix_id] = hit_depth_weight;
+            out.out_T[pix_id] = end_T;
+        }
     }
     // list positions the backward has to walk for this quadrant
     int w = inside ? (int)max(last_contributor, hit_pos & 0x7fffffffu) : 0;
@@ -598,7 +615,7 @@ __device__ __forceinline__ void blend_quadrant(const DqoView& v, const DqoGeomLa
                     // one (the drop-in operator's) fits 64 without a spill and runs at 8; maps beyond 768 Ki Gaussians run the gated
                     // kernel at 6 (dqo_launch_blend_forward)
 #endif
-template <bool GATE, int MINW>
+template <bool GATE, int MINW, bool AUX>
 __global__ __launch_bounds__(FWD_THREADS * FWD_WPB, MINW) void blend_forward_kernel(const DqoView v, DqoGeomLayout g, DqoImageLayout img,
                                                                                             DqoBinLayout bin, DqoRastOutputs out,
                                                                                             const DqoTapDev tap, const DqoGateDev gate,
@@ -616,8 +633,8 @@ __global__ __launch_bounds__(FWD_THREADS * FWD_WPB, MINW) void blend_forward_ker
     const uint4 si = img.slot_info[xg * T8 + (jg >> 2)];  // (tile, list start, list end) of the slot: one round
     const uint32_t tile_u = si.x;
     if (tile_u == 0xffffffffu) return;  // unused slot
-    blend_quadrant<GATE, 1, FWD_PF>(v, g, img, bin, out, tap, gate, (int)tile_u, jg & 3, wave, (int)(threadIdx.x & 63), lds, 0x7fffffff,
-                                    make_uint2(si.y, si.z));
+    blend_quadrant<GATE, 1, FWD_PF, AUX>(v, g, img, bin, out, tap, gate, (int)tile_u, jg & 3, wave, (int)(threadIdx.x & 63), lds, 0x7fffffff,
+                                         make_uint2(si.y, si.z));
 }
 
 // DqoRastCtx.list_split: blocks of SPLIT_RUNS waves.  The first SPLIT_GRID blocks take the long lists (longer than list_split entries: the
@@ -651,8 +668,8 @@ __global__ __launch_bounds__(FWD_THREADS * SPLIT_RUNS, 4) void blend_forward_spl
             const uint32_t it = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_item);
             if (it >= items) return;
             const int tile_s = (int)img.split_tiles[it >> 2];
-            blend_quadrant<GATE, SPLIT_RUNS, SPLIT_PF>(v, g, img, bin, out, tap, gate, tile_s, (int)(it & 3u), wave, lane, lds, 0x7fffffff,
-                                                       img.ranges[tile_s]);
+            blend_quadrant<GATE, SPLIT_RUNS, SPLIT_PF, true>(v, g, img, bin, out, tap, gate, tile_s, (int)(it & 3u), wave, lane, lds, 0x7fffffff,
+                                                             img.ranges[tile_s]);
             __syncthreads();  // wave 0 has read the other waves' merge records (and everyone this trip's ticket)
         }
     }
@@ -661,7 +678,7 @@ __global__ __launch_bounds__(FWD_THREADS * SPLIT_RUNS, 4) void blend_forward_spl
     if (slot >= T8) return;
     const uint32_t tile_u = img.tile_order[(b & 7) * T8 + slot];
     if (tile_u == 0xffffffffu) return;
-    blend_quadrant<GATE, 1, SPLIT_PF>(v, g, img, bin, out, tap, gate, (int)tile_u, wave & 3, wave, lane, lds, list_split, img.ranges[tile_u]);
+    blend_quadrant<GATE, 1, SPLIT_PF, true>(v, g, img, bin, out, tap, gate, (int)tile_u, wave & 3, wave, lane, lds, list_split, img.ranges[tile_u]);
 }
 
 }  // namespace
@@ -670,6 +687,9 @@ int dqo_launch_blend_forward(const DqoView& v, const DqoGeomLayout& g, const Dqo
                              const DqoRastOutputs& out, int T, const DqoTapDev& tap, const DqoGateDev& gate, int list_split, hipStream_t s,
                              int64_t header_capacity) {
     const bool gt = gate.gobj != nullptr;
+    // the training form (blend_quadrant): a caller without the auxiliary outputs — only dqo_rast_forward_train hands such a struct in.
+    // (The list-split kernels stay in the full form: that entry point refuses a split forward.)
+    const bool aux = out.out_T != nullptr;
     if (list_split > 0) {
         const dim3 grid(2 * SPLIT_GRID + 8 * (((T + 7) / 8 + 1) / 2)), block(FWD_THREADS * SPLIT_RUNS);
         if (gt) DQO_LAUNCH("blend_forward_kernel", blend_forward_split_kernel<true>, grid, block, s, v, g, img, bin, out, tap, gate, list_split);
@@ -680,9 +700,15 @@ int dqo_launch_blend_forward(const DqoView& v, const DqoGeomLayout& g, const Dqo
     // waves per SIMD the register allocation leaves room for: what the walk gains from a seventh wave on a 500 k map (-3 us) it loses on
     // a 1 M one (+5 us: more waves gathering from a bigger set of records) — same-box A/B, profiles/r06_ab_fwd_seven_waves.txt
     const bool small_map = v.P <= 786432;
-    if (gt && small_map) DQO_LAUNCH("blend_forward_kernel", (blend_forward_kernel<true, FWD_MINW>), grid, block, s, v, g, img, bin, out, tap, gate, header_capacity);
-    else if (gt) DQO_LAUNCH("blend_forward_kernel", (blend_forward_kernel<true, 6>), grid, block, s, v, g, img, bin, out, tap, gate, header_capacity);
-    else if (small_map) DQO_LAUNCH("blend_forward_kernel", (blend_forward_kernel<false, 8>), grid, block, s, v, g, img, bin, out, tap, gate, header_capacity);
-    else DQO_LAUNCH("blend_forward_kernel", (blend_forward_kernel<false, 6>), grid, block, s, v, g, img, bin, out, tap, gate, header_capacity);
+#define DQO_BLEND(GATE, MINW)                                                                                                          \
+    do {                                                                                                                              \
+        if (aux) DQO_LAUNCH("blend_forward_kernel", (blend_forward_kernel<GATE, MINW, true>), grid, block, s, v, g, img, bin, out, tap, gate, header_capacity); \
+        else DQO_LAUNCH("blend_forward_kernel", (blend_forward_kernel<GATE, MINW, false>), grid, block, s, v, g, img, bin, out, tap, gate, header_capacity);    \
+    } while (0)
+    if (gt && small_map) DQO_BLEND(true, FWD_MINW);
+    else if (gt) DQO_BLEND(true, 6);
+    else if (small_map) DQO_BLEND(false, 8);
+    else DQO_BLEND(false, 6);
+#undef DQO_BLEND
     return DQO_OK;
 }

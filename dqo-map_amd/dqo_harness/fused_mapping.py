@@ -1714,8 +1714,9 @@ class FusedMapper:
         # thread_local: other threads of the process (e.g. a collective library's watchdog) may keep issuing runtime calls
         g.unroll = max(1, int(g.options["unroll"]))
         with torch.cuda.graph(g.graph, capture_error_mode="thread_local"):
-            for _ in range(g.unroll):
-                self._static_iteration()
+            # (everything a caller can see after a launch is what the LAST iteration left: the ones before it run lean)
+            for i in range(g.unroll):
+                self._static_iteration(lean=i + 1 < g.unroll)
         # run_unroll (capture_window): a SECOND graph over the same context buffers with that many iterations, for the stretches of a
         # schedule that stay on one frame — the second half of local_optimize renders the newest frame only (mapper.py:574-576) —
         # where one launch per iteration leaves the GPU idle for ~9 us between graphs (replay_run)
@@ -1723,8 +1724,8 @@ class FusedMapper:
         if g.run_unroll > 1:
             g.run_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g.run_graph, capture_error_mode="thread_local"):
-                for _ in range(g.run_unroll):
-                    self._static_iteration()
+                for i in range(g.run_unroll):
+                    self._static_iteration(lean=i + 1 < g.run_unroll)
         self._expected_step = self.step_count + 1
         return True
 
@@ -2068,14 +2069,17 @@ class FusedMapper:
         N.check(lib.dqo_rast_read_header(ctypes.byref(cctx), ctypes.byref(hdr), stream))
         return cand, int(hdr.max_tile_count)
 
-    def _static_iteration(self):
-        """The five C-ABI calls of one iteration over the persistent buffers (no allocation, no host-side per-step state)."""
+    def _static_iteration(self, lean=False):
+        """The five C-ABI calls of one iteration over the persistent buffers (no allocation, no host-side per-step state).  lean: the
+        forward in its training form (dqo_rast_forward_train) — for an iteration whose outputs the next one overwrites unread; honoured
+        where nothing behind the forward reads an auxiliary output (loss tap on, no split forward)."""
         lib, g = N.lib(), self._g
+        forward = lib.dqo_rast_forward_train if (lean and g.tap is not None and g.ls_fwd <= 0) else lib.dqo_rast_forward
         st = self.settings
         H, W = int(st.image_height), int(st.image_width)
         stream = N.current_stream()
         g.cctx.list_split = g.ls_fwd
-        N.check(lib.dqo_rast_forward(ctypes.byref(g.params), ctypes.byref(g.inputs), ctypes.byref(g.outputs), ctypes.byref(g.cctx), stream))
+        N.check(forward(ctypes.byref(g.params), ctypes.byref(g.inputs), ctypes.byref(g.outputs), ctypes.byref(g.cctx), stream))
         g.cctx.list_split = g.ls_bwd  # (0 with a split forward: the single-wave backward walks every list, the queue is ignored)
         o = g.out
         if g.tap is None:

@@ -275,6 +275,12 @@ int dqo_rast_read_header(const DqoRastCtx*, DqoRastHeader* host_out, void* hipSt
 int dqo_rast_forward_render(const DqoRastParams*, const DqoRastInputs*, DqoRastOutputs*, DqoRastCtx*, void* hipStream);
 /* Both stages back to back, no host synchronisation (caller guarantees / later checks capacity). */
 int dqo_rast_forward(const DqoRastParams*, const DqoRastInputs*, DqoRastOutputs*, DqoRastCtx*, void* hipStream);
+/* As dqo_rast_forward, in the training form: for an iteration whose render nobody reads — its backward, loss tap and per-Gaussian tail
+ * are its only consumers (the inner iterations of a graph that holds several: FusedMapper.capture(unroll=k)).  Writes out_color,
+ * out_depth and radii and the whole forward->backward context; leaves out_hit_color, out_hit_depth, out_hit_color_weight,
+ * out_hit_depth_weight, out_T and n_touched UNTOUCHED (not even zeroed), and skips the work that only they need.  The struct is checked
+ * like dqo_rast_forward's (no NULL member).  Needs ctx.loss_tap (without it the loss kernels read out_hit_depth) and list_split == 0. */
+int dqo_rast_forward_train(const DqoRastParams*, const DqoRastInputs*, DqoRastOutputs*, DqoRastCtx*, void* hipStream);
 
 /* Both stages in ONE call for a caller that carries its instance capacity over from earlier frames and checks it afterwards (ABI 4; the
  * drop-in op's 'lazy' / 'deferred' modes): as dqo_rast_forward, plus — where the frame's header is final, behind the sort kernels and
