@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 
 import _dqo_native as N
+from _dqo_context import RastContext, bucket_for, capacity_for, forward_call, header_dict, header_words, read_header
 
 # Operator state.  It lives at module level on purpose: the reference's caller builds a NEW GaussianRasterizer for every render call
 # (SLAM/render.py:163), so state hung off the module instance would not survive from one call to the next — and the lazy mode's capacity
@@ -61,11 +62,18 @@ _POOL_SETS = 3         # contexts per key; a forward that finds all of them leas
 _POOL_KEYS = 4         # shapes with pooled contexts, most recently used last: a map that grows changes P with every keyframe, and the
                        # contexts of the sizes it has left behind are dropped (one still leased lives on with its graph)
 _shape_hint = {}       # (device index, P, W, H) -> [candidate pairs, longest tile list] of earlier frames (max over them)
+_HINT_KEYS = 64        # shapes with a capacity / shape hint, most recently written last (_raise_hint): an entry is three integers and
+                       # a SLAM process has a handful of shapes in use at once — a cap chosen for those reasons, not a measurement
 
 
-class _CtxSet:
-    __slots__ = ("geom", "img", "binning", "cap", "bucket", "order_valid", "clean", "leased",
+class _CtxSet(RastContext):
+    """A pooled context: the buffers and what the pool knows about them."""
+    __slots__ = ("order_valid", "clean", "leased",
                  "captured")  # captured: (keep_tile_order, frame_prezeroed) of the captured forward that pinned it ('graph' mode)
+
+    def __init__(self, P, W, H, device):
+        super().__init__(P, W, H, device)
+        self.order_valid = self.clean = self.leased = False
 
 
 class _Lease:
@@ -117,18 +125,20 @@ def set_context_pool(on):
             _pool.clear()
 
 
-def _bucket_for(longest):
-    """Per-tile bucket for lists up to `longest` entries in earlier frames: a power of two, at least twice that (FusedMapper.capture's
-    rule, and its exception: 1024 — what the per-tile sort reaches, so the long-list sort launch disappears — if 1.3 x longest fits)."""
-    b = 256
-    while b < 2 * longest:
-        b *= 2
-    if b == 2048 and 1.3 * longest <= 1024:
-        b = 1024
-    return b
+def _raise_hint(hints, key, value):
+    """hints[key] = max(what it held, value) — element by element for _shape_hint's [candidates, longest] — as the key written last;
+    beyond _HINT_KEYS keys the one written longest ago goes (a map that grows changes P with every keyframe).  An evicted shape costs
+    one measured forward in 'lazy' / 'deferred' mode; 'graph' mode raises its "no instance capacity known".  Under the module lock."""
+    old = hints.pop(key, None)
+    if old is not None:
+        value = max(old, value) if isinstance(value, int) else [max(o, v) for o, v in zip(old, value)]
+    hints[key] = value
+    while len(hints) > _HINT_KEYS:
+        del hints[next(iter(hints))]
+    return value
 
 
-def _pooled_set(lib, key, stream, dev, W, H, pin=False):
+def _pooled_set(key, stream, dev, pin=False):
     """A free pooled context for this shape with room for the shape's hints, or None (pool off, statistics not known yet, every
     context leased).  Called under the module lock.
     pin ('graph' mode, a forward that is being captured): the context leaves the pool for good (_Pinned); a free one of ANY stream will
@@ -139,7 +149,7 @@ def _pooled_set(lib, key, stream, dev, W, H, pin=False):
     hint = _shape_hint.get(key)
     if hint is None or hint[1] <= 0:
         return None
-    cap, bucket = int(hint[0] * 1.25) + 4096, _bucket_for(hint[1])
+    cap, bucket = capacity_for(hint[0], 1.25), bucket_for(hint[1])
     if pin:
         for pkey, sets in _pool.items():
             if (pkey[0],) + pkey[2:] != key:
@@ -159,13 +169,7 @@ def _pooled_set(lib, key, stream, dev, W, H, pin=False):
     sets[:] = [cs for cs in sets if cs.leased or (cs.cap >= cap and cs.bucket >= bucket)]  # (outgrown free contexts go)
     if len(sets) >= _POOL_SETS:
         return None
-    u8 = dict(dtype=torch.uint8, device=dev)
-    cs = _CtxSet()
-    cs.cap, cs.bucket = int(cap * 1.2), bucket  # (headroom: a context is replaced when the hints outgrow it)
-    cs.geom = torch.empty((lib.dqo_rast_geom_bytes(key[1], W, H),), **u8)
-    cs.img = torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8)
-    cs.binning = torch.empty((lib.dqo_rast_binning_bytes_bucketed(cs.cap, W, H, cs.bucket),), **u8)
-    cs.order_valid = cs.clean = cs.leased = False
+    cs = _CtxSet(*key[1:], dev).size(int(cap * 1.2), bucket)  # (headroom: a context is replaced when the hints outgrow it)
     if not pin:
         sets.append(cs)
     return cs
@@ -197,12 +201,10 @@ def last_header():
     if hd is None:
         return None
     if torch.is_tensor(hd):  # exact mode: read on demand from the forward's geometry buffer
-        h = hd[:32].view(torch.int32).cpu().tolist()
-        return dict(num_rendered=h[0], num_tiles=h[1], overflow=h[2], max_tile_count=h[3], num_visible=h[4], num_candidates=h[5])
+        return read_header(hd)
     ev, host = hd
     ev.synchronize()
-    h = host.tolist()
-    return dict(num_rendered=h[0], num_tiles=h[1], overflow=h[2], max_tile_count=h[3], num_visible=h[4], num_candidates=h[5])
+    return header_dict(host)
 
 
 def last_num_rendered():
@@ -251,7 +253,7 @@ def set_capacity(P, W, H, instances, device_index=None):
     dev_index = torch.cuda.current_device() if device_index is None else int(device_index)
     key = (dev_index, int(P), int(W), int(H))
     with _lock:
-        _cap_hint[key] = max(_cap_hint.get(key, 0), int(instances))
+        _raise_hint(_cap_hint, key, int(instances))
 
 
 def verify_pending():
@@ -271,15 +273,15 @@ def _verify_pending(block):
                 keep.append((ev, host, key, cap, pooled))
                 continue
             ev.synchronize()
-            n, overflow = int(host[0]), int(host[2])
+            h = header_dict(host)
+            n, overflow, candidates = h["num_rendered"], h["overflow"], h["num_candidates"]
             # the hint only grows: one key serves calls with different tile masks / camera poses, whose N differ
-            _cap_hint[key] = max(_cap_hint.get(key, 0), int(n * 1.25) + 4096)
-            sh = _shape_hint.setdefault(key, [0, 0])  # (the context pool's sizing: candidate pairs and the longest list)
-            sh[0], sh[1] = max(sh[0], int(host[5])), max(sh[1], int(host[3]))
+            _raise_hint(_cap_hint, key, capacity_for(n, 1.25))
             if overflow and pooled:
                 # a region of the map may have outgrown its share of the instance slots although the bucket and the total fitted
-                # (include/dqo_raster.h, tile_bucket_capacity) -> more instance slots next time (cap = 1.25 x this + 4096)
-                sh[0] = max(sh[0], int(cap * 1.2))
+                # (include/dqo_raster.h, tile_bucket_capacity) -> more instance slots next time (_pooled_set: capacity_for(this, 1.25))
+                candidates = max(candidates, int(cap * 1.2))
+            _raise_hint(_shape_hint, key, [candidates, h["max_tile_count"]])  # (the context pool's sizing)
             if overflow:
                 keep.extend(_pending[i + 1:])  # (the later forwards stay pending: they are checked by the next call)
                 err = (n, cap, pooled)
@@ -380,13 +382,137 @@ def _new_outputs(P, H, W, device):
     return out, N.DqoRastOutputs(*(N.ptr(t) for t in out))
 
 
-def _forward_call(lib, stage, params, inputs, pinputs, outputs, cctx, *rest):
-    """dqo_rast_forward_<stage> of the activated form, or its _params counterpart when the parameter form's inputs are given."""
-    if pinputs is None:
-        return getattr(lib, "dqo_rast_forward_" + stage)(ctypes.byref(params), ctypes.byref(inputs), ctypes.byref(outputs),
-                                                         ctypes.byref(cctx), *rest)
-    return getattr(lib, "dqo_rast_forward_" + stage + "_params")(ctypes.byref(params), ctypes.byref(inputs), ctypes.byref(pinputs),
-                                                                 ctypes.byref(outputs), ctypes.byref(cctx), *rest)
+def _checked_gate(P, H, W, gaussian_object, pixel_object, tile_objects):
+    """(DqoObjectGate, (gaussian_object, pixel_object, tile_objects) as the struct points at them) of a gated call, or (None, None)."""
+    if (gaussian_object is None) != (pixel_object is None):
+        raise RuntimeError("object gate: gaussian_object and pixel_object go together")
+    if gaussian_object is None:
+        if tile_objects is not None:
+            raise RuntimeError("object gate: tile_objects without gaussian_object / pixel_object")
+        return None, None
+    N.require_gpu(gaussian_object, pixel_object)
+    if gaussian_object.dtype != torch.int32 or pixel_object.dtype != torch.int32:
+        raise RuntimeError("expected scalar type Int (object gate)")
+    if gaussian_object.numel() != P or pixel_object.numel() != H * W:
+        raise RuntimeError("object gate: gaussian_object must have num_points elements, pixel_object H x W")
+    gaussian_object, pixel_object = gaussian_object.contiguous(), pixel_object.contiguous()
+    _check_gate_ids(gaussian_object, pixel_object)
+    gate = N.DqoObjectGate(gaussian_object=N.ptr(gaussian_object), pixel_object=N.ptr(pixel_object))
+    if tile_objects is not None:
+        N.require_gpu(tile_objects)
+        if tile_objects.dtype != torch.int64 or tile_objects.numel() != ((H + 15) // 16) * ((W + 15) // 16):
+            raise RuntimeError("object gate: tile_objects must be int64 with ceil(H/16) x ceil(W/16) elements")
+        tile_objects = tile_objects.contiguous()
+        gate.tile_objects = N.ptr(tile_objects)
+    return gate, (gaussian_object, pixel_object, tile_objects)
+
+
+def _checked_tensors(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask, rs, row_flags):
+    """The forward's tensors as the library reads them (fp32 / int32, contiguous, on the GPU), the settings with such tensors."""
+    if means3D.ndimension() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:67-70
+    N.require_gpu_op(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask, rs.bg, rs.viewmatrix,
+                     rs.projmatrix, rs.campos)
+    means3D, opacities = _f32(means3D, "means3D"), _f32(opacities, "opacities")
+    sh, colors_precomp = _f32(sh, "sh"), _f32(colors_precomp, "colors_precomp")
+    scales, rotations, cov3Ds_precomp = _f32(scales, "scales"), _f32(rotations, "rotations"), _f32(cov3Ds_precomp, "cov3D_precomp")
+    rs = rs._replace(bg=_f32(rs.bg, "bg"), viewmatrix=_f32(rs.viewmatrix, "viewmatrix"), projmatrix=_f32(rs.projmatrix, "projmatrix"),
+                     campos=_f32(rs.campos, "campos"))
+    if tile_mask is not None:
+        if tile_mask.dtype != torch.int32:
+            raise RuntimeError(f"expected scalar type Int but found {tile_mask.dtype} (tile_mask)")
+        tile_mask = tile_mask.contiguous()
+    if row_flags is not None:
+        N.require_gpu(row_flags)
+        if row_flags.dtype != torch.uint8 or row_flags.numel() != means3D.size(0) or not row_flags.is_contiguous():
+            raise RuntimeError("row_flags must be a contiguous uint8 tensor with num_points elements")  # (read in place: no copy)
+    return (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask), rs
+
+
+def _adopt(pooled, prezeroed, fields):
+    """The DqoRastCtx of a forward on a pooled context (see _pool): lists in its per-tile buckets, the tile order of the previous frame
+    on it, and — prezeroed: that frame's backward cleared the counters — no zero fill and no preprocess launch.  Under the module lock."""
+    cctx = pooled.cctx(keep_tile_order=1 if pooled.order_valid else 0, frame_prezeroed=1 if prezeroed else 0, **fields)
+    pooled.clean = False  # (whatever happens next: this frame's counters are in use)
+    return cctx
+
+
+def _run_measured(key, dev, stream, structs, pinputs, fields):
+    """'exact', or the first call of a shape in 'lazy' / 'deferred' (measure once): stage 1, the one D2H read, stage 2, on a context of
+    the call's own.  -> (context, the reference's num_rendered; -1 outside 'exact')"""
+    exact = _sync_mode == "exact"
+    rc = RastContext(*key[1:], dev)
+    hdr = rc.measure(*structs, stream, pinputs, **fields)
+    # (Gaussian, tile) pairs in the tile rects: the reference's num_rendered, and an upper bound of the instances the binning keeps
+    # after its footprint test — a capacity that always fits
+    num_rendered = int(hdr.num_candidates)
+    if exact:
+        _last["num_rendered"], _last["num_visible"] = num_rendered, int(hdr.num_visible)
+        rc.size(max(num_rendered, 1))
+    else:
+        with _lock:
+            cap = _raise_hint(_cap_hint, key, capacity_for(num_rendered, 1.0))  # later calls keep max(this, 1.25 N)
+        rc.size(cap)
+    rc.render(*structs, stream, pinputs, **fields)
+    if exact:
+        # exact mode has read what it needs already: nothing per call; last_header() reads the rest on demand from the geometry
+        # buffer, which therefore stays referenced until the next forward (~160 B per Gaussian, one call longer)
+        _last["header"] = rc.geom
+        return rc, num_rendered
+    with _lock:
+        host, ev, _, _ = _ring_slot(dev.index)
+        host.copy_(header_words(rc.geom), non_blocking=True)
+        ev.record()
+        _pending.append((ev, host, key, rc.cap, False))
+        _last["header"] = (ev, host)
+    return rc, -1
+
+
+def _run_carried(key, dev, stream, cap, structs, pinputs, fields):
+    """'lazy' / 'deferred' with a carried-over capacity: ONE call — both stages, and between the sort and the blend kernel (where the
+    frame's header is final) its asynchronous copy into a pinned ring slot + the slot's event: the deferred capacity check, available
+    a blend kernel before the forward's end.  On a pooled context if the shape has a free one.  -> (context, its lease or None)"""
+    with _lock:
+        pooled = _pooled_set(key, stream, dev) if key[1] > 0 else None
+        if pooled is not None:
+            rc, lease, cctx = pooled, _Lease(pooled), _adopt(pooled, pooled.clean and _list_split == 0, fields)
+        else:
+            rc, lease = RastContext(*key[1:], dev).size(cap), None
+            cctx = rc.cctx(**fields)
+        host, ev, host_ptr, ev_handle = _ring_slot(dev.index)
+        forward_call("_async", *structs, cctx, host_ptr, ev_handle, stream, pinputs=pinputs)
+        if pooled is not None:
+            pooled.order_valid = True
+        _pending.append((ev, host, key, rc.cap, pooled is not None))
+        _last["header"] = (ev, host)
+    return rc, lease
+
+
+def _run_captured(ctx, key, dev, stream, structs, pinputs, fields):
+    """'graph' mode: nothing touches the host — the launches of both stages, no header copy, no event.  A forward that IS being
+    captured pins a pooled context (an eager call in this mode keeps contexts of its own).  -> (context, _Pinned or None)"""
+    with _lock:
+        cap = _cap_hint.get(key)
+        if cap is None:
+            raise RuntimeError("diff_gaussian_rasterization_depth ('graph' mode): no instance capacity known for "
+                               f"P={key[1]}, {key[2]}x{key[3]}: run one forward in 'lazy' mode first (the warm-up before the capture) or "
+                               "call set_capacity(P, W, H, instances)")
+        capturing = key[1] > 0 and torch.cuda.is_current_stream_capturing()
+        pooled = _pooled_set(key, stream, dev, pin=True) if capturing else None
+        if pooled is not None:
+            # the context belongs to the graph from here on (_Pinned).  The counters' promise holds at every replay only if the
+            # captured iteration also holds this frame's backward, which clears them: a forward that needs no gradient is captured
+            # with its own zero fill
+            rc, lease = pooled, _Pinned(pooled)
+            _captured.append(pooled)
+            cctx = _adopt(pooled, pooled.clean and _list_split == 0 and any(ctx.needs_input_grad), fields)
+            pooled.captured = (int(cctx.keep_tile_order), int(cctx.frame_prezeroed))
+        else:
+            rc, lease = RastContext(*key[1:], dev).size(cap), None
+            cctx = rc.cctx(**fields)
+    forward_call("_async", *structs, cctx, None, None, stream, pinputs=pinputs)
+    _last["header"] = rc.geom  # (a captured forward: the graph's own buffer, valid after every replay)
+    return rc, lease
 
 
 def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask, raster_settings,
@@ -396,24 +522,12 @@ def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov
     rotations given as empty tensors; everything else (sync modes, pooled contexts, leases, capacity hints) is the same code.
     ctx.row_flags (optional, set by a caller that drives forward / backward by hand — FusedMapper.step): DqoRastInputs.row_flags, uint8 [P]
     in device memory; hidden rows are not rendered, in this forward and in its backward.  Absent or None (the drop-in operator): every row."""
-    rs = raster_settings
-    lib = N.lib()
-    if means3D.ndimension() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:67-70
-    N.require_gpu_op(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask, rs.bg, rs.viewmatrix,
-                     rs.projmatrix, rs.campos)
-    dev = means3D.device
-    means3D, opacities = _f32(means3D, "means3D"), _f32(opacities, "opacities")
-    sh, colors_precomp = _f32(sh, "sh"), _f32(colors_precomp, "colors_precomp")
-    scales, rotations, cov3Ds_precomp = _f32(scales, "scales"), _f32(rotations, "rotations"), _f32(cov3Ds_precomp, "cov3D_precomp")
-    bg, view, proj, campos = (_f32(rs.bg, "bg"), _f32(rs.viewmatrix, "viewmatrix"), _f32(rs.projmatrix, "projmatrix"),
-                              _f32(rs.campos, "campos"))
-    rs = rs._replace(bg=bg, viewmatrix=view, projmatrix=proj, campos=campos)
-    if tile_mask is not None:
-        if tile_mask.dtype != torch.int32:
-            raise RuntimeError(f"expected scalar type Int but found {tile_mask.dtype} (tile_mask)")
-        tile_mask = tile_mask.contiguous()
-    P = means3D.size(0)
+    N.lib()
+    row_flags = getattr(ctx, "row_flags", None)
+    tensors, rs = _checked_tensors(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask, raster_settings,
+                                   row_flags)
+    means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask = tensors
+    dev, P = means3D.device, means3D.size(0)
     H, W = int(rs.image_height), int(rs.image_width)
     M = sh.size(1) if sh.numel() != 0 else 0  # rasterize_points.cu:105-109
     pinputs = None
@@ -422,143 +536,27 @@ def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov
         M = 1 + f_rest.size(1)
         pinputs = N.DqoRastParamInputs(features_dc=N.ptr(f_dc), features_rest=N.ptr(f_rest), rest=M - 1, opacity_raw=N.ptr(o_raw),
                                        scaling_raw=N.ptr(s_raw), rotation_raw=N.ptr(r_raw))
-    gate = None
-    if (gaussian_object is None) != (pixel_object is None):
-        raise RuntimeError("object gate: gaussian_object and pixel_object go together")
-    if gaussian_object is not None:
-        N.require_gpu(gaussian_object, pixel_object)
-        if gaussian_object.dtype != torch.int32 or pixel_object.dtype != torch.int32:
-            raise RuntimeError("expected scalar type Int (object gate)")
-        if gaussian_object.numel() != P or pixel_object.numel() != H * W:
-            raise RuntimeError("object gate: gaussian_object must have num_points elements, pixel_object H x W")
-        gaussian_object, pixel_object = gaussian_object.contiguous(), pixel_object.contiguous()
-        _check_gate_ids(gaussian_object, pixel_object)
-        gate = N.DqoObjectGate(gaussian_object=N.ptr(gaussian_object), pixel_object=N.ptr(pixel_object))
-        if tile_objects is not None:
-            N.require_gpu(tile_objects)
-            if tile_objects.dtype != torch.int64 or tile_objects.numel() != ((H + 15) // 16) * ((W + 15) // 16):
-                raise RuntimeError("object gate: tile_objects must be int64 with ceil(H/16) x ceil(W/16) elements")
-            tile_objects = tile_objects.contiguous()
-            gate.tile_objects = N.ptr(tile_objects)
-    elif tile_objects is not None:
-        raise RuntimeError("object gate: tile_objects without gaussian_object / pixel_object")
-    row_flags = getattr(ctx, "row_flags", None)
-    if row_flags is not None:
-        N.require_gpu(row_flags)
-        if row_flags.dtype != torch.uint8 or row_flags.numel() != P or not row_flags.is_contiguous():
-            raise RuntimeError("row_flags must be a contiguous uint8 tensor with num_points elements")  # (read in place: no copy)
-    u8 = dict(dtype=torch.uint8, device=dev)
+    gate, gate_ids = _checked_gate(P, H, W, gaussian_object, pixel_object, tile_objects)
     with torch.cuda.device(dev):
         stream = N.current_stream()
         out, outputs = _new_outputs(P, H, W, dev)
-        _, _, hit_color, hit_depth, _, _, _, n_touched, radii = out
-        geomBuffer = torch.empty((lib.dqo_rast_geom_bytes(P, W, H),), **u8)
-        imgBuffer = torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8)
-        params = _params(rs, P, M)
-        inputs = _inputs(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask, row_flags=row_flags)
-        cctx = N.DqoRastCtx(geom=geomBuffer.data_ptr(), geom_bytes=geomBuffer.numel(), binning=None, binning_bytes=0,
-                            image=imgBuffer.data_ptr(), image_bytes=imgBuffer.numel(), inst_capacity=0, list_split=_list_split)
-        if gate is not None:
-            cctx.object_gate = ctypes.addressof(gate)
+        structs = (_params(rs, P, M), _inputs(rs, *tensors, row_flags=row_flags), outputs)
+        # the DqoRastCtx members of every forward of this call, whatever context it runs on
+        fields = dict(list_split=_list_split, object_gate=None if gate is None else ctypes.addressof(gate))
         key = (dev.index, P, W, H)
-        cap = None
-        lease = None
+        num_rendered, lease, cap = -1, None, None
         if _sync_mode == "graph":
-            with _lock:
-                cap = _cap_hint.get(key)
-            if cap is None:
-                raise RuntimeError("diff_gaussian_rasterization_depth ('graph' mode): no instance capacity known for "
-                                   f"P={P}, {W}x{H}: run one forward in 'lazy' mode first (the warm-up before the capture) or call "
-                                   "set_capacity(P, W, H, instances)")
-            # nothing below touches the host: the launches of both stages, no header copy, no event
-            num_rendered = -1
-            with _lock:
-                # (only a forward that IS being captured pins a context: an eager call in this mode keeps contexts of its own)
-                capturing = P > 0 and torch.cuda.is_current_stream_capturing()
-                pooled = _pooled_set(lib, key, stream, dev, W, H, pin=True) if capturing else None
-                if pooled is not None:
-                    # the context belongs to the graph from here on (_Pinned).  The counters' promise holds at every replay only if
-                    # the captured iteration also holds this frame's backward, which clears them: a forward that needs no gradient
-                    # is captured with its own zero fill
-                    lease = _Pinned(pooled)
-                    _captured.append(pooled)
-                    geomBuffer, imgBuffer, binningBuffer, cap = pooled.geom, pooled.img, pooled.binning, pooled.cap
-                    cctx.geom, cctx.geom_bytes = geomBuffer.data_ptr(), geomBuffer.numel()
-                    cctx.image, cctx.image_bytes = imgBuffer.data_ptr(), imgBuffer.numel()
-                    cctx.tile_bucket_capacity = pooled.bucket
-                    cctx.keep_tile_order = 1 if pooled.order_valid else 0
-                    cctx.frame_prezeroed = 1 if (pooled.clean and _list_split == 0 and any(ctx.needs_input_grad)) else 0
-                    pooled.clean = False
-                    pooled.captured = (int(cctx.keep_tile_order), int(cctx.frame_prezeroed))
-                else:
-                    binningBuffer = torch.empty((lib.dqo_rast_binning_bytes(cap),), **u8)
-            cctx.binning, cctx.binning_bytes, cctx.inst_capacity = binningBuffer.data_ptr(), binningBuffer.numel(), cap
-            N.check(_forward_call(lib, "async", params, inputs, pinputs, outputs, cctx, None, None, stream))
-            _last["header"] = geomBuffer  # (a captured forward: the graph's own buffer, valid after every replay)
-        elif _sync_mode != "exact":
-            _verify_pending(block=False)
-            with _lock:
-                cap = _cap_hint.get(key)
-        if _sync_mode == "graph":
-            pass
-        elif cap is None:
-            # 'exact', or the first call for this shape in 'lazy' / 'deferred' (measure once): stage 1, the one D2H read, stage 2
-            N.check(_forward_call(lib, "prepare", params, inputs, pinputs, outputs, cctx, stream))
-            hdr = N.DqoRastHeader()
-            N.check(lib.dqo_rast_read_header(ctypes.byref(cctx), ctypes.byref(hdr), stream))
-            # (Gaussian, tile) pairs in the tile rects: the reference's num_rendered, and an upper bound of the instances
-            # the binning keeps after its footprint test — a capacity that always fits
-            num_rendered = int(hdr.num_candidates)
-            cap = max(num_rendered, 1)
-            if _sync_mode == "exact":
-                _last["num_rendered"], _last["num_visible"] = num_rendered, int(hdr.num_visible)
-            else:
-                cap = num_rendered + 4096  # later calls keep max(this, 1.25 N)
-                with _lock:
-                    cap = _cap_hint[key] = max(_cap_hint.get(key, 0), cap)
-                num_rendered = -1
-            binningBuffer = torch.empty((lib.dqo_rast_binning_bytes(cap),), **u8)
-            cctx.binning, cctx.binning_bytes, cctx.inst_capacity = binningBuffer.data_ptr(), binningBuffer.numel(), cap
-            N.check(_forward_call(lib, "render", params, inputs, pinputs, outputs, cctx, stream))
-            if _sync_mode == "exact":
-                # exact mode has read what it needs already: nothing per call; last_header() reads the rest on demand from the
-                # geometry buffer, which therefore stays referenced until the next forward (~160 B per Gaussian, one call longer)
-                _last["header"] = geomBuffer
-            else:
-                with _lock:
-                    host, ev, _, _ = _ring_slot(dev.index)
-                    host.copy_(geomBuffer[:32].view(torch.int32), non_blocking=True)
-                    ev.record()
-                    _pending.append((ev, host, key, cap, False))
-                    _last["header"] = (ev, host)
+            rc, lease = _run_captured(ctx, key, dev, stream, structs, pinputs, fields)
         else:
-            # 'lazy' / 'deferred' with a carried-over capacity: ONE call — both stages, and between the sort and the blend kernel
-            # (where the frame's header is final) its asynchronous copy into a pinned ring slot + the slot's event: the deferred
-            # capacity check, available a blend kernel before the forward's end
-            num_rendered = -1
-            with _lock:
-                pooled = _pooled_set(lib, key, stream, dev, W, H) if P > 0 else None
-                if pooled is not None:
-                    # a pooled context (see _pool): its buffers instead of the fresh ones, lists in per-tile buckets, the tile
-                    # order of the previous frame on it, and — if that frame's backward cleared the counters — no zero fill and
-                    # no preprocess launch
-                    lease = _Lease(pooled)
-                    geomBuffer, imgBuffer, binningBuffer, cap = pooled.geom, pooled.img, pooled.binning, pooled.cap
-                    cctx.geom, cctx.geom_bytes = geomBuffer.data_ptr(), geomBuffer.numel()
-                    cctx.image, cctx.image_bytes = imgBuffer.data_ptr(), imgBuffer.numel()
-                    cctx.tile_bucket_capacity = pooled.bucket
-                    cctx.keep_tile_order = 1 if pooled.order_valid else 0
-                    cctx.frame_prezeroed = 1 if (pooled.clean and _list_split == 0) else 0
-                    pooled.clean = False  # (whatever happens below: this frame's counters are in use)
-                else:
-                    binningBuffer = torch.empty((lib.dqo_rast_binning_bytes(cap),), **u8)
-                cctx.binning, cctx.binning_bytes, cctx.inst_capacity = binningBuffer.data_ptr(), binningBuffer.numel(), cap
-                host, ev, host_ptr, ev_handle = _ring_slot(dev.index)
-                N.check(_forward_call(lib, "async", params, inputs, pinputs, outputs, cctx, host_ptr, ev_handle, stream))
-                if pooled is not None:
-                    pooled.order_valid = True
-                _pending.append((ev, host, key, cap, pooled is not None))
-                _last["header"] = (ev, host)
+            if _sync_mode != "exact":
+                _verify_pending(block=False)
+                with _lock:
+                    cap = _cap_hint.get(key)
+            if cap is None:
+                rc, num_rendered = _run_measured(key, dev, stream, structs, pinputs, fields)
+            else:
+                rc, lease = _run_carried(key, dev, stream, cap, structs, pinputs, fields)
+    _, _, hit_color, hit_depth, _, _, _, n_touched, radii = out
     # Only grad_out_color and grad_out_depth are consumed by the backward (like the reference's, __init__.py:176-238): the engine need not
     # fill zero images for the three float outputs nobody differentiated through (hit_color_weight, hit_depth_weight, T_map) — three
     # fill launches per backward; an undefined colour / depth gradient arrives as None and is replaced by zeros there
@@ -567,13 +565,12 @@ def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov
     ctx.pooled = lease  # (None: a context of this call's own)
     ctx.raster_settings = rs
     ctx.num_rendered = num_rendered
-    ctx.inst_capacity = cap
+    ctx.inst_capacity = rc.cap
     ctx.list_split = _list_split  # (the backward shares the same lists between eight waves: the queue is the forward's)
     ctx.M = M
-    ctx.object_gate = None if gate is None else (gaussian_object, pixel_object)
-    ctx.save_for_backward(colors_precomp, hit_depth, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                          binningBuffer, imgBuffer, opacities, tile_mask if tile_mask is not None else torch.empty(0),
-                          *(pf if pf is not None else ()))
+    ctx.object_gate = None if gate is None else gate_ids[:2]
+    ctx.save_for_backward(colors_precomp, hit_depth, means3D, scales, rotations, cov3Ds_precomp, radii, sh, rc.geom, rc.binning, rc.img,
+                          opacities, tile_mask if tile_mask is not None else torch.empty(0), *(pf if pf is not None else ()))
     ctx.mark_non_differentiable(hit_color, hit_depth, n_touched, radii)
     return out
 
@@ -628,14 +625,12 @@ def _backward(ctx, grad_out_color, grad_out_depth):
             # (the forward's row flags: the per-Gaussian chain sees the rows the forward culled as culled)
             inputs = _inputs(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tile_mask,
                              row_flags=getattr(ctx, "row_flags", None))
-            cctx = N.DqoRastCtx(geom=geomBuffer.data_ptr(), geom_bytes=geomBuffer.numel(), binning=binningBuffer.data_ptr(),
-                                binning_bytes=binningBuffer.numel(), image=imgBuffer.data_ptr(), image_bytes=imgBuffer.numel(),
-                                inst_capacity=cap, list_split=getattr(ctx, "list_split", 0))
             lease = getattr(ctx, "pooled", None)
+            cctx = RastContext.over(P, W, H, geomBuffer, imgBuffer, binningBuffer, cap, 0 if lease is None else lease.set.bucket).cctx(
+                list_split=getattr(ctx, "list_split", 0))
             if lease is not None:
                 # a pooled context: its lists live in buckets, and this call — the last consumer of the frame's counters — clears
                 # them for the next forward on the context (DqoRastCtx.frame_prezeroed as dqo_rast_backward reads it)
-                cctx.tile_bucket_capacity = lease.set.bucket
                 cctx.frame_prezeroed = 1 if cctx.list_split == 0 else 0
             if getattr(ctx, "object_gate", None) is not None:
                 gate = N.DqoObjectGate(gaussian_object=N.ptr(ctx.object_gate[0]), pixel_object=N.ptr(ctx.object_gate[1]))

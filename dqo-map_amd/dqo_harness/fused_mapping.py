@@ -35,6 +35,7 @@ import torch
 
 import _dqo_native as N
 import diff_gaussian_rasterization_depth as dgr
+from _dqo_context import RastContext, bucket_for, capacity_for, overflowed, read_header
 from dqo_harness import mapping
 
 
@@ -90,6 +91,15 @@ class _Ctx:
 
     def mark_non_differentiable(self, *a):
         pass
+
+
+class _RenderContext(RastContext):
+    """A rasteriser context plus the op's nine outputs (dgr._new_outputs) of the frames rendered on it."""
+    __slots__ = ("out", "outputs")
+
+    def __init__(self, P, W, H, device):
+        self.out, self.outputs = dgr._new_outputs(P, H, W, device)
+        super().__init__(P, W, H, device)
 
 
 class _SideJob:
@@ -171,7 +181,7 @@ class _FrameGraph:
         self.cap = 0  # instance capacity
         self.bucket = 0  # DqoRastCtx.tile_bucket_capacity (0: packed lists)
         self.out = None  # the op's 9 outputs (dgr._new_outputs) of the last iteration
-        self.geom = self.img = self.binning = self.ws = None  # context buffers and the backward's workspace
+        self.ctx = self.geom = self.img = self.binning = self.ws = None  # the context (its buffers by name) and the backward's workspace
         self.grads = None  # gradient rows of the unfused tail (dict: means3D, sh, opacity, scales, rot)
         self.grad_scale = None  # DqoLossTap.grad_scale
         # the step state is the mapper's, shared by all its graphs (DqoAdamStep.step_dev: the Adam launch advances it itself through
@@ -613,41 +623,27 @@ class FusedMapper:
 
     def _maintain_render(self, st, row_flags=None, tile_mask=None):
         """The whole map (both clouds: no row flags, no object gate; spare rows are parked and transparent) rendered at camera `st` through
-        the C ABI into persistent buffers: the op's nine outputs c["out"] (0 colour, 1 depth, 2 colour hit index, 3 depth hit index).
+        the C ABI into persistent buffers: the op's nine outputs c.out (0 colour, 1 depth, 2 colour hit index, 3 depth hit index).
         row_flags (refresh_window): DqoRastInputs.row_flags, uint8 [P] — its DQO_ROW_HIDDEN rows are not rendered; None: every row.
         tile_mask (prune_floaters): int32 [gy,gx], checked by the caller; None: every tile.
-        The first call measures the frame (prepare, one header read, render) and sizes the instance capacity at 1.5 x its candidate
-        pairs + 4096; later calls are ONE dqo_rast_forward call on those buffers — no header copy, no event, no allocation."""
-        lib, dev, P, M = N.lib(), self.device, self.P, self.M
+        The first call measures the frame (prepare, one header read, render) and sizes the instance capacity at
+        capacity_for(its candidate pairs, 1.5); later calls are ONE dqo_rast_forward call on those buffers — no header copy, no event, no allocation."""
+        dev, P, M = self.device, self.P, self.M
         H, W = int(st.image_height), int(st.image_width)
         if (H, W) != (int(self.settings.image_height), int(self.settings.image_width)):
             raise RuntimeError("FusedMapper.maintain: every frame of a mapper has the mapper's image size")
         stream = N.current_stream()
-        b = ctypes.byref
         c = self._maintain_ctx
-        first = c is None or c["key"] != (P, H, W)
+        first = c is None or (c.P, c.H, c.W) != (P, H, W)
         if first:
-            u8 = dict(dtype=torch.uint8, device=dev)
-            out, outputs = dgr._new_outputs(P, H, W, dev)
-            c = dict(key=(P, H, W), out=out, outputs=outputs, geom=torch.empty((lib.dqo_rast_geom_bytes(P, W, H),), **u8),
-                     img=torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8))
+            c = _RenderContext(P, W, H, dev)
         params = dgr._params(st, P, M)
         inputs = dgr._inputs(st, self.xyz, self.shs, self._empty, self.opacity, self.scales, self.rotations, self._empty,
                              self.tile_mask if tile_mask is None else tile_mask, row_flags=row_flags)
-        cctx = N.DqoRastCtx(geom=c["geom"].data_ptr(), geom_bytes=c["geom"].numel(), binning=None, binning_bytes=0,
-                            image=c["img"].data_ptr(), image_bytes=c["img"].numel(), inst_capacity=0)
         if first:
-            hdr = N.DqoRastHeader()
-            N.check(lib.dqo_rast_forward_prepare(b(params), b(inputs), b(c["outputs"]), b(cctx), stream))
-            N.check(lib.dqo_rast_read_header(b(cctx), b(hdr), stream))
-            c["cap"] = int(1.5 * int(hdr.num_candidates)) + 4096
-            c["binning"] = torch.empty((lib.dqo_rast_binning_bytes(c["cap"]),), dtype=torch.uint8, device=dev)
-        cctx.binning, cctx.binning_bytes, cctx.inst_capacity = c["binning"].data_ptr(), c["binning"].numel(), c["cap"]
-        if first:
-            N.check(lib.dqo_rast_forward_render(b(params), b(inputs), b(c["outputs"]), b(cctx), stream))
-            self._maintain_ctx = c
-        else:
-            N.check(lib.dqo_rast_forward(b(params), b(inputs), b(c["outputs"]), b(cctx), stream))
+            c.size(capacity_for(int(c.measure(params, inputs, c.outputs, stream).num_candidates), 1.5))
+        c.render(params, inputs, c.outputs, stream, prepare=not first)
+        self._maintain_ctx = c
         return c
 
     def maintain_overflowed(self):
@@ -657,7 +653,7 @@ class FusedMapper:
         c = self._maintain_ctx
         if c is None:
             return False
-        over = int(c["geom"][:32].view(torch.int32)[2].item()) != 0
+        over = overflowed(c.geom)
         if over:
             self._maintain_ctx = None
         return over
@@ -699,8 +695,8 @@ class FusedMapper:
             c = self._maintain_render(st)
             # (the buffers as they are bound NOW; only the vote words and the workspace are kept from call to call)
             state = dict({b.name: a for b, a in self._rows("param", "meta")}, **self._lifecycle)
-            stats = mg.lifecycle_step(state, tick, gt_color, gt_depth, c["out"][0], c["out"][1], c["out"][3], c["out"][2],
-                                      stable_oversized=stable_oversized, park=self._park_position(), render_header=c["geom"], **th)
+            stats = mg.lifecycle_step(state, tick, gt_color, gt_depth, c.out[0], c.out[1], c.out[3], c.out[2],
+                                      stable_oversized=stable_oversized, park=self._park_position(), render_header=c.geom, **th)
             self._lifecycle = {"_lifecycle": state["_lifecycle"]}
         self._n_spare_stale = True  # (_refresh_spare_count)
         self._act_valid = False  # deleted rows' raw parameters changed
@@ -763,7 +759,7 @@ class FusedMapper:
             try:
                 for k in range(4):
                     c = self._maintain_render(st._replace(viewmatrix=view[k], projmatrix=proj[k]), tile_mask=tm)
-                    mg.prune_touch(c["out"][7], p["ws"], render_header=c["geom"])
+                    mg.prune_touch(c.out[7], p["ws"], render_header=c.geom)
                 # (the buffers as they are bound NOW)
                 stats = mg.prune_step({b.name: a for b, a in self._rows("param", "meta")}, p["ws"], (lo, hi), self._park_position(), stats=p["stats"])
             except Exception:
@@ -839,11 +835,11 @@ class FusedMapper:
             self.activate()
             for k, (settings, gt_color, gt_depth) in enumerate(frames):
                 c = self._maintain_render(self.settings if settings is None else _normalised_settings(settings, dev))
-                o = c["out"]
+                o = c.out
                 dqo_eval.eval_picture(dict(render=o[0], depth=o[1], depth_index_map=o[3]), gt_color, gt_depth, min_depth, max_depth, out=table,
-                                      row=k, workspace_buffer=self._eval_ws, render_header=c["geom"])
+                                      row=k, workspace_buffer=self._eval_ws, render_header=c.geom)
                 if ms_ssim is not None:
-                    dqo_eval.ms_ssim(o[0], gt_color, out=ms_ssim, row=k, workspace_buffer=self._eval_ms_ws, render_header=c["geom"])
+                    dqo_eval.ms_ssim(o[0], gt_color, out=ms_ssim, row=k, workspace_buffer=self._eval_ms_ws, render_header=c.geom)
         return table
 
     @torch.no_grad()
@@ -1203,7 +1199,7 @@ class FusedMapper:
                 c = self._maintain_render(st)
                 if self.maintain_overflowed():  # (the frame outgrew the context an earlier frame sized: size a new one)
                     c = self._maintain_render(st)
-                out = c["out"]
+                out = c.out
                 model_map = dict(render_color=out[0].permute(1, 2, 0), render_depth=out[1].permute(1, 2, 0),
                                  render_depth_index=out[3].permute(1, 2, 0), render_transmission=out[6].permute(1, 2, 0))
             s = self._sample_ctx
@@ -1619,31 +1615,21 @@ class FusedMapper:
             reuse_probe = False
             cand, longest = self._probe(g.tile_mask, g.settings, g.pixel_object, g.tile_objects)
         self._last_probe = (cand, longest, P)
-        g.cap = int(cand * capacity_margin) + 4096
-        # fixed per-tile list buckets (DqoRastCtx.tile_bucket_capacity): at least twice the longest list of the current state,
-        # a power of two; a tile that outgrows it raises the same overflow flag as running out of instance capacity
+        g.cap = capacity_for(cand, capacity_margin)
+        # fixed per-tile list buckets (bucket_for; short_bucket_margin: how much margin over the longest list is worth keeping the
+        # long-list sort launch away, 6 us on a map whose lists are all short).  A tile that outgrows its bucket flags the frame
+        # (graph_overflowed(); run() / run_window() re-capture; the replays in between train nothing).
         if g.options["tile_buckets"]:
-            g.bucket = 256
-            while g.bucket < 2 * longest:
-                g.bucket *= 2
-            # 1024 entries are what the per-tile sort launch reaches: while no list can be longer, the long-list sort launch is
-            # dropped (6 us of launch on a map whose lists are all short) — worth a smaller margin (short_bucket_margin, default
-            # 1.3 x the longest list; pass 2.0 to never trade margin for that launch) to stay there.  A tile that outgrows its
-            # bucket flags the frame (graph_overflowed(); run() / run_window() re-capture; the replays in between train nothing).
-            if g.bucket == 2048 and float(g.options["short_bucket_margin"]) * longest <= 1024:
-                g.bucket = 1024
+            g.bucket = bucket_for(longest, float(g.options["short_bucket_margin"]))
         return reuse_probe, longest
 
     def _allocate_graph(self, g):
         """The persistent buffers of a new graph: outputs, context buffers, the backward's workspace and gradient rows."""
         lib, dev, P, M = N.lib(), self.device, self.P, self.M
-        H, W = int(g.settings.image_height), int(g.settings.image_width)
-        f, u8 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.uint8, device=dev)
-        g.out, g.outputs = dgr._new_outputs(P, H, W, dev)
-        g.geom = torch.empty((lib.dqo_rast_geom_bytes(P, W, H),), **u8)
-        g.img = torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8)
-        g.binning = torch.empty((lib.dqo_rast_binning_bytes_bucketed(g.cap, W, H, g.bucket),), **u8)
-        g.ws = torch.empty((lib.dqo_rast_backward_workspace_bytes(g.cap),), **u8)
+        f = dict(dtype=torch.float32, device=dev)
+        g.ctx = c = _RenderContext(P, int(g.settings.image_width), int(g.settings.image_height), dev).size(g.cap, g.bucket)
+        g.out, g.outputs, g.geom, g.img, g.binning = c.out, c.outputs, c.geom, c.img, c.binning
+        g.ws = torch.empty((lib.dqo_rast_backward_workspace_bytes(g.cap),), dtype=torch.uint8, device=dev)
         # dL_dcolors / dL_dcov3D / dL_dmeans2D have no consumer in the mapping step: NULL = the backward does not store them
         g.grads = dict(means3D=torch.empty((P, 3), **f), sh=torch.empty((P, M, 3), **f),
                        opacity=torch.empty((P, 1), **f), scales=torch.empty((P, 3), **f), rot=torch.empty((P, 4), **f))
@@ -1656,12 +1642,9 @@ class FusedMapper:
         g.params = dgr._params(st, self.P, self.M)
         g.inputs = dgr._inputs(st, self.xyz, self.shs, self._empty, self.opacity, self.scales, self.rotations, self._empty, g.tile_mask,
                                row_flags=self.row_flags)
-        g.cctx = N.DqoRastCtx(geom=g.geom.data_ptr(), geom_bytes=g.geom.numel(), binning=g.binning.data_ptr(),
-                              binning_bytes=g.binning.numel(), image=g.img.data_ptr(), image_bytes=g.img.numel(), inst_capacity=g.cap,
-                              tile_bucket_capacity=g.bucket)
         # (DqoRastCtx.list_split is read by the forward and by the backward call: _static_iteration sets it before each)
         g.ls_fwd, g.ls_bwd = self.pick_list_split_pair(opt["list_split"], g.tile_mask, st, longest)
-        g.cctx.list_split = g.ls_fwd
+        g.cctx = g.ctx.cctx(list_split=g.ls_fwd)
         # DqoLossTap: the masked loss is summed by the forward's blend kernel and its gradient images are formed inside the
         # backward's (bit for bit what dqo_map_loss_fwd_bwd computes): no loss kernels, no passes over the full image.
         # The SSIM term's gradient (no render mask) is an image (an 11 x 11 window around every pixel): the tap, which forms
@@ -1972,10 +1955,10 @@ class FusedMapper:
             for i, k in enumerate(slots):
                 g = self._frames[k]
                 c = self._maintain_render(g.settings, row_flags=self._window_flags)
-                o = c["out"]
+                o = c.out
                 dqo_tilemask.window_masks(o[6], o[0], g.gt_color, global_opt=global_opt, sample_ratio=sample_ratio,
                                           render_mask=g.mask.view(H, W), tile_mask=g.tile_mask.view(gy, gx), ratio_out=table[i:i + 1],
-                                          render_header=c["geom"], workspace=self._window_ws)
+                                          render_header=c.geom, workspace=self._window_ws)
                 done.update((g.mask.data_ptr(), g.tile_mask.data_ptr()))
             for k in slots:
                 g = self._frames[k]
@@ -2039,35 +2022,25 @@ class FusedMapper:
 
     def _probe(self, tile_mask, st=None, pixel_object=None, tile_objects=None):
         """(num_candidates, longest tile list) of the current state: one forward on scratch buffers with packed lists."""
-        lib, dev, P, M = N.lib(), self.device, self.P, self.M
+        P, M = self.P, self.M
         st = self.settings if st is None else st
         if pixel_object is None:
             pixel_object, tile_objects = self.pixel_object, self.tile_objects
-        H, W = int(st.image_height), int(st.image_width)
-        u8 = dict(dtype=torch.uint8, device=dev)
-        out, outputs = dgr._new_outputs(P, H, W, dev)
-        geom = torch.empty((lib.dqo_rast_geom_bytes(P, W, H),), **u8)
-        img = torch.empty((lib.dqo_rast_image_bytes(W, H),), **u8)
+        c = _RenderContext(P, int(st.image_width), int(st.image_height), self.device)
         params = dgr._params(st, P, M)
         inputs = dgr._inputs(st, self.xyz, self.shs, self._empty, self.opacity, self.scales, self.rotations, self._empty, tile_mask,
                              row_flags=self.row_flags)
-        cctx = N.DqoRastCtx(geom=geom.data_ptr(), geom_bytes=geom.numel(), binning=None, binning_bytes=0, image=img.data_ptr(),
-                            image_bytes=img.numel(), inst_capacity=0)
+        fields = {}
         if self.gaussian_object is not None:
             # the lists of the gated job (the binning drops a pair whose object owns no pixel of the tile): its longest list, not the
             # ungated frame's, sizes the buckets
             gate = N.DqoObjectGate(gaussian_object=N.ptr(self.gaussian_object), pixel_object=N.ptr(pixel_object), tile_objects=N.ptr(tile_objects))
-            cctx.object_gate = ctypes.addressof(gate)
+            fields["object_gate"] = ctypes.addressof(gate)
         stream = N.current_stream()
-        hdr = N.DqoRastHeader()
-        N.check(lib.dqo_rast_forward_prepare(ctypes.byref(params), ctypes.byref(inputs), ctypes.byref(outputs), ctypes.byref(cctx), stream))
-        N.check(lib.dqo_rast_read_header(ctypes.byref(cctx), ctypes.byref(hdr), stream))
-        cand = int(hdr.num_candidates)
-        binning = torch.empty((lib.dqo_rast_binning_bytes(max(cand, 1)),), **u8)
-        cctx.binning, cctx.binning_bytes, cctx.inst_capacity = binning.data_ptr(), binning.numel(), max(cand, 1)
-        N.check(lib.dqo_rast_forward_render(ctypes.byref(params), ctypes.byref(inputs), ctypes.byref(outputs), ctypes.byref(cctx), stream))
-        N.check(lib.dqo_rast_read_header(ctypes.byref(cctx), ctypes.byref(hdr), stream))
-        return cand, int(hdr.max_tile_count)
+        cand = int(c.measure(params, inputs, c.outputs, stream, **fields).num_candidates)
+        c.size(max(cand, 1))
+        c.render(params, inputs, c.outputs, stream, **fields)
+        return cand, int(c.header(stream).max_tile_count)
 
     def _static_iteration(self, lean=False):
         """The five C-ABI calls of one iteration over the persistent buffers (no allocation, no host-side per-step state).  lean: the
@@ -2210,13 +2183,12 @@ class FusedMapper:
 
     def header(self, g=None):
         """Device header of the captured iteration's last forward (one small D2H read, synchronises)."""
-        h = (self._g if g is None else g).geom[:32].view(torch.int32).cpu().tolist()
-        return dict(num_rendered=h[0], num_tiles=h[1], overflow=h[2], max_tile_count=h[3], num_visible=h[4], num_candidates=h[5])
+        return read_header((self._g if g is None else g).geom)
 
     def graph_overflowed(self, g=None):
         """True if the last replayed iteration (of graph g: a frame of the window; default the current one) produced more instances than
         the captured capacity (one small D2H read)."""
-        return bool((self._g if g is None else g).geom[:12].view(torch.int32)[2].item())
+        return overflowed((self._g if g is None else g).geom)
 
     def _params(self):
         return dict(xyz=self.xyz, shs=self.shs, opacity=self.opacity_raw, scaling=self.scaling_raw, rotation=self.rotation_raw)

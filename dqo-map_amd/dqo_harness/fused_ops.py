@@ -18,6 +18,7 @@ import ctypes
 import torch
 
 import _dqo_native as N
+from _dqo_context import read_header
 from dqo_harness import mapping
 
 
@@ -277,8 +278,7 @@ class CapturedIteration:
         self.replays += 1
 
     def header(self):
-        h = self._header[:32].view(torch.int32).cpu().tolist()
-        return dict(num_rendered=h[0], num_tiles=h[1], overflow=h[2], max_tile_count=h[3], num_visible=h[4], num_candidates=h[5])
+        return read_header(self._header)
 
     def check(self):
         """Raises if the last replayed frame outgrew the captured capacity (its outputs were background, its gradients zeros)."""

@@ -153,7 +153,9 @@ def test_a_pooled_context_that_is_outgrown_is_flagged_and_replaced(torch_cuda):
 def test_the_pool_forgets_the_shapes_a_growing_map_has_left_behind(torch_cuda):
     import diff_gaussian_rasterization_depth as dgr
     torch = torch_cuda
+    hint_keys = dgr._HINT_KEYS
     try:
+        dgr._HINT_KEYS = 4  # (the capacity and shape hints beside the pool are bounded the same way)
         dgr.set_sync_mode("deferred")
         for P in range(3000, 3000 + 100 * 7, 100):  # seven map sizes, two frames each
             cam, sc = scenes.make_config(1, P=P)
@@ -162,8 +164,15 @@ def test_the_pool_forgets_the_shapes_a_growing_map_has_left_behind(torch_cuda):
                 dgr.verify_pending()
         keys = list(dgr._pool)
         assert len(keys) == dgr._POOL_KEYS and [k[2] for k in keys] == [3300, 3400, 3500, 3600]
+        dev = torch.cuda.current_device()
+        for hints in (dgr._cap_hint, dgr._shape_hint):
+            mine = [k for k in hints if k[0] == dev]
+            assert len(mine) <= 4 and [k[1] for k in mine] == [3300, 3400, 3500, 3600], (mine, hints is dgr._cap_hint)
+        U.run_hip(cam, sc, dL=_dL(cam, 7))  # one more frame at the newest P: its hints are there, the frame is valid
+        dgr.verify_pending()
     finally:
         dgr.set_sync_mode("exact")
+        dgr._HINT_KEYS = hint_keys
     assert len(dgr._pool) == 0
 
 

@@ -168,7 +168,7 @@ def test_maintain_end_to_end_keeps_the_captured_graph():
     assert fm._n_spare_stale
     torch.cuda.synchronize()
     assert not fm.maintain_overflowed()
-    out = dict(zip(("render", "depth", "color_index_map", "depth_index_map"), fm._maintain_ctx["out"][:4]))
+    out = dict(zip(("render", "depth", "color_index_map", "depth_index_map"), fm._maintain_ctx.out[:4]))
     for k in out:  # maintain's own render is the op's render of the same parameters
         assert torch.equal(out[k], ref[k]), k
     want = lifecycle_oracle({k: v.cpu() for k, v in before.items()}, 7, gt_c.cpu(), gt_d.cpu(), out["render"].cpu(), out["depth"].cpu(),
@@ -198,7 +198,7 @@ def test_maintain_end_to_end_keeps_the_captured_graph():
     finally:
         torch.cuda.set_sync_debug_mode("default")
     torch.cuda.synchronize()
-    out = [t.cpu() for t in fm._maintain_ctx["out"][:4]]
+    out = [t.cpu() for t in fm._maintain_ctx.out[:4]]
     want2 = lifecycle_oracle({k: v.cpu() for k, v in before.items()}, 8, gt_c.cpu(), gt_d.cpu(), out[0], out[1], out[3], out[2],
                              park=park.cpu(), **th)
     assert want2["margin"] >= 1e-5 and stats.tolist() == want2["stats"] and not fm.maintain_overflowed()

@@ -236,7 +236,7 @@ def test_prune_floaters_end_to_end_keeps_the_captured_graph():
     for got, name in ((view, "viewmatrix"), (proj, "projmatrix"), (focal, "focal")):
         assert torch.equal(got.cpu(), torch.from_numpy(want_cams[name])), name
     touched, last = _op_touch_counts(fm, params, view, proj, tile_mask)
-    out = fm._maintain_ctx["out"]
+    out = fm._maintain_ctx.out
     for k, i in dict(render=0, depth=1, color_index_map=2, depth_index_map=3, n_touched=7).items():
         assert torch.equal(out[i], last[k]), k  # the mapper's own fourth render is the op's
     want = po.prune_oracle({k: v.cpu() for k, v in before.items()}, touched, window, park)

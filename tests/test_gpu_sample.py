@@ -210,7 +210,7 @@ def test_sample_new_equals_the_oracle_on_its_own_render_and_feeds_grow():
     fm = FusedMapper(scene, settings, dev).reserve(6000).track_lifecycle()
     new = fm.sample_new(frame, seed=9, tick=4, **SAMPLE_KW)
     torch.cuda.synchronize()
-    out = fm._maintain_ctx["out"]
+    out = fm._maintain_ctx.out
     model = dict(render_color=out[0].permute(1, 2, 0), render_depth=out[1].permute(1, 2, 0), render_depth_index=out[3].permute(1, 2, 0),
                  render_transmission=out[6].permute(1, 2, 0))
     want = sample_oracle({k: v.cpu().numpy() for k, v in frame.items()}, {k: v.cpu().numpy() for k, v in model.items()}, seed=9,
@@ -232,7 +232,7 @@ def test_a_shard_keeps_the_unsharded_rows_of_its_objects_in_order():
     po = np.broadcast_to((np.arange(W) * 8 // W).astype(np.int32)[None, :], (H, W)).copy()
     whole = FusedMapper(scene, settings, dev).set_object_gate(go, po)
     rows = whole.sample_new(frame, seed=9, tick=4, **SAMPLE_KW)
-    out = whole._maintain_ctx["out"]
+    out = whole._maintain_ctx.out
     model = dict(render_color=out[0].permute(1, 2, 0), render_depth=out[1].permute(1, 2, 0), render_depth_index=out[3].permute(1, 2, 0),
                  render_transmission=out[6].permute(1, 2, 0))
     assert set(np.unique(go)) == set(range(8)) and rows["xyz"].shape[0] == whole.sample_header["rows"]

@@ -102,7 +102,7 @@ def main():
                  normal_map_w=up(rng.normal(size=(H, W, 3))), instance_img=None)
     fm = FusedMapper(scene, settings, dev)
     fm.sample_new(frame, seed=0, tick=0, **CFG)  # (sizes the render context and the sampler's buffers)
-    out = fm._maintain_ctx["out"]
+    out = fm._maintain_ctx.out
     model = dict(render_color=out[0].permute(1, 2, 0), render_depth=out[1].permute(1, 2, 0), render_depth_index=out[3].permute(1, 2, 0),
                  render_transmission=out[6].permute(1, 2, 0))
     print("header:", fm.sample_header)
