@@ -126,7 +126,7 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_map_pack_rows", "dqo_map_unpack_rows", "dqo_mesh_sample_workspace_bytes", "dqo_mesh_sample",
            "dqo_objmap_frame", "dqo_objmap_optimize", "dqo_objmap_mean_iou", "dqo_traj_append", "dqo_track_world_maps",
            "dqo_eval_ate_workspace_bytes", "dqo_eval_ate", "dqo_prune_workspace_bytes", "dqo_prune_cameras", "dqo_prune_touch",
-           "dqo_prune_rows")
+           "dqo_prune_rows", "dqo_tsdf_workspace_bytes", "dqo_tsdf_clear", "dqo_tsdf_integrate", "dqo_tsdf_extract")
 
 _lib = None
 
@@ -256,6 +256,11 @@ def lib():
         L.dqo_prune_cameras.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_d, c_d, c_vp, c_vp, c_vp, c_vp]
         L.dqo_prune_touch.argtypes = [c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]
         L.dqo_prune_rows.argtypes = [c_i32] + [c_vp] * 12 + [c_i32, c_i32, c_vp, c_sz, c_vp, c_vp]
+        # map_tsdf.hip
+        L.dqo_tsdf_workspace_bytes.argtypes = [c_i32] * 3
+        L.dqo_tsdf_clear.argtypes = [c_i32] * 3 + [c_vp] * 5
+        L.dqo_tsdf_integrate.argtypes = [c_i32] * 3 + [c_f] * 5 + [c_vp] * 4 + [c_i32, c_i32, c_vp, c_vp] + [c_f] * 4 + [c_vp, c_f, c_vp, c_vp]
+        L.dqo_tsdf_extract.argtypes = [c_i32] * 3 + [c_f] * 4 + [c_vp] * 6 + [c_i32, c_i32, c_vp, c_vp, c_sz, c_vp]
         # icp.hip, track.hip
         L.dqo_icp_normal_equations.argtypes = [c_i32, c_i32] + [c_vp] * 5 + [c_f] * 6 + [c_vp] * 4 + [c_sz, c_vp]
         L.dqo_icp_gauss_newton.argtypes = [c_i32, c_i32] + [c_vp] * 6 + [c_f] * 4 + [c_vp] * 2 + [c_sz, c_vp]

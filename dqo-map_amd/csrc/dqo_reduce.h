@@ -4,14 +4,16 @@
 // can be captured in a hipGraph.  Users: map_eval.hip (eval_picture_kernel, eval_pcd_kernel, eval_pcd_grouped_kernel: its own partial lines), map_msssim.hip (msssim_level_kernel), map_lifecycle.hip (the two cloud limits and
 // the frame's counts), map_prune.hip (prune_rows_kernel: ticket and counts), map_tilemask.hip (window_masks_kernel: ticket only, its last block selects tiles), map_checkpoint.hip (map_pack_count_kernel: its last block scans
 // the blocks' row counts), map_meshsample.hip (mesh_area_kernel: max and counts; mesh_quantise_kernel: its last block scans the blocks'
-// quanta), dqo_adam.h (ticket only, unfenced).
+// quanta), map_tsdf.hip (tsdf_edges_kernel, tsdf_vertices_kernel: their last blocks scan the spans' vertex and face counts), dqo_adam.h
+// (ticket only, unfenced).
 //
 // Below the double reductions, the integer ends the map operators share (behind whichever last-block ticket their kernel takes):
 //   - dqo_block_exclusive, the block-wide exclusive scan: map_densify.hip (the count and emit passes, the first histogram pass's N),
 //     map_meshsample.hip (mesh_scan_kernel), and dqo_scan_block_counts;
 //   - dqo_scan_block_counts, the last block's turn of the blocks' counts into exclusive offsets in index order: map_sample.hip
 //     (sample_rank_kernel, sample_rows_kernel: two interleaved columns), map_densify.hip (densify_count_kernel: eight per thread),
-//     map_checkpoint.hip (map_pack_count_kernel), map_meshsample.hip (mesh_quantise_kernel);
+//     map_checkpoint.hip (map_pack_count_kernel), map_meshsample.hip (mesh_quantise_kernel), map_tsdf.hip (tsdf_edges_kernel,
+//     tsdf_vertices_kernel);
 //   - dqo_line_count / dqo_line_totals, a row pass's counts on 64 lines: map_lifecycle.hip, map_prune.hip.
 //
 // Deliberately NOT users of the ticket, and not to be "finished" into this header:

@@ -79,6 +79,16 @@ prefix and a Python loop over its points:
 One launch (dqo_eval_ate, csrc/map_traj.hip), one block per prefix, sums added in a fixed order.  dqo_icp.Trajectory keeps the two pose
 stacks on the device and calls it (`Trajectory.ate()`).  The ATE figure (matplotlib) and scripts/eval_ate.py are not built.
 
+The map as a triangle mesh — make_mesh.py and eval_frame(..., volume=..., scale=...), SLAM/eval.py:299, 316-343, which integrate every
+frame's render into an open3d TSDF volume; open3d does not exist on this platform, so the volume and the extraction are the library's
+own (csrc/map_tsdf.hip: a dense grid, the integration rule restated in include/dqo_raster.h, marching tetrahedra):
+
+    TsdfVolume(origin, voxel_length, dims, sdf_trunc, device)   tsdf, weight, color: public device tensors
+        .clear()  .integrate(depth, color, K, w2c, depth_trunc, render_header)  .extract(cap_vertices, cap_faces)  .counts()
+
+FusedMapper.make_mesh(frames, volume) renders and integrates a camera list; dqo_ply.write_mesh_ply writes the mesh.  Laplacian smoothing
+(the reference's mesh_smooth_* keys are read by nothing in its tree), sparse volumes and mesh simplification are not built.
+
 GPU only: there is no CPU path.
 """
 import ctypes
@@ -661,3 +671,119 @@ def eval_ate(pose_es, pose_gt, out=None, fit=None, workspace_buffer=None):
 def eval_ate_dict(curve):
     """{"ate": the full trajectory's ATE in cm} — what save_traj prints (tracker.py:406-407) — from a device curve: ONE host read."""
     return {"ate": float(curve.detach().reshape(-1)[-1].cpu())}
+
+
+# ---- the map as a triangle mesh (csrc/map_tsdf.hip) ---------------------------------------------------------------------------------------
+TSDF_HEADER = ("vertices", "faces", "vertices_dropped", "faces_dropped", "frames", "frames_skipped", "unused6", "unused7")
+TSDF_MAX_VOXELS = 1 << 28
+
+
+def _intrinsics(K):
+    """(fx, fy, cx, cy) from a sequence of the four, or from a host 3 x 3 pinhole matrix."""
+    if torch.is_tensor(K):
+        if K.is_cuda:
+            raise RuntimeError("dqo_eval.TsdfVolume.integrate: K is host data (fx, fy, cx, cy or a 3 x 3 matrix); a device tensor would be a host read")
+        K = K.tolist()
+    K = list(K)
+    if len(K) == 4 and not hasattr(K[0], "__len__"):
+        return tuple(float(v) for v in K)
+    if len(K) == 3 and all(len(r) == 3 for r in K):
+        return float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
+    raise RuntimeError("dqo_eval.TsdfVolume.integrate: K is (fx, fy, cx, cy) or a 3 x 3 matrix")
+
+
+class TsdfVolume:
+    """A dense uniform TSDF volume on the device and its mesh — what make_mesh.py and eval_frame(..., volume=..., scale=...)
+    (SLAM/eval.py:299, 316-343) use open3d for, which does not exist on this platform.  include/dqo_raster.h (dqo_tsdf_integrate,
+    dqo_tsdf_extract) states both rules; tests/tsdf_oracle.py restates them in numpy.  A dense grid over the caller's box, not open3d's
+    hashed blocks; marching tetrahedra, not open3d's marching cubes.
+
+    origin: the box's lowest corner (three floats); voxel_length; dims = (nx, ny, nz), every side >= 2, fewer than 2^28 voxels;
+    sdf_trunc: the truncation distance in metres.  Lattice point (x, y, z) sits at origin + (index + 0.5) * voxel_length.
+    Public tensors (float32, x fastest): tsdf [nz,ny,nx], weight [nz,ny,nx], color [3,nz,ny,nx]; header int32 [8] (TSDF_HEADER).
+    The constructor allocates the volume and the extraction workspace and clears the volume (one launch); after the first call of a
+    shape no method allocates.  Nothing is read back except by counts().  GPU only: there is no CPU path."""
+
+    def __init__(self, origin, voxel_length, dims, sdf_trunc, device):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("libdqoraster operators need GPU (ROCm) tensors; there is no CPU path.")
+        nx, ny, nz = (int(d) for d in dims)
+        if min(nx, ny, nz) < 2:
+            raise RuntimeError(f"dqo_eval.TsdfVolume: bad dims {nx} x {ny} x {nz}: every side is at least 2")
+        if nx * ny * nz >= TSDF_MAX_VOXELS:
+            raise RuntimeError(f"dqo_eval.TsdfVolume: too many voxels: {nx} x {ny} x {nz} is not below 2^28")
+        if not (float(voxel_length) > 0.0 and float(sdf_trunc) > 0.0):
+            raise RuntimeError("dqo_eval.TsdfVolume: voxel_length and sdf_trunc are above 0")
+        self.device, self.dims = dev, (nx, ny, nz)
+        self.origin = tuple(float(v) for v in origin)
+        self.voxel_length, self.sdf_trunc = float(voxel_length), float(sdf_trunc)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.tsdf, self.weight = torch.empty((nz, ny, nx), **f32), torch.empty((nz, ny, nx), **f32)
+        self.color = torch.empty((3, nz, ny, nx), **f32)
+        self.header = torch.empty((8,), dtype=torch.int32, device=dev)
+        self._ws = torch.zeros((N.lib().dqo_tsdf_workspace_bytes(nx, ny, nz),), dtype=torch.uint8, device=dev)
+        self._meshes = {}
+        self.clear()
+
+    def clear(self):
+        """tsdf = 1, weight = 0, color = 0, header = 0: one launch."""
+        with torch.cuda.device(self.device):
+            N.check(N.lib().dqo_tsdf_clear(*self.dims, self.tsdf.data_ptr(), self.weight.data_ptr(), self.color.data_ptr(),
+                                           self.header.data_ptr(), N.current_stream()))
+        return self
+
+    def integrate(self, depth, color, K, w2c, depth_trunc=30.0, render_header=None):
+        """One RGB-D frame into the volume, one launch.  depth: float32 [H,W] or [1,H,W] device tensor in metres; color: float32 [3,H,W];
+        K: (fx, fy, cx, cy) or a 3 x 3 matrix, HOST numbers; w2c: float32 device tensor of 16 elements, the world-to-camera matrix row
+        major; depth_trunc: pixels deeper than this are ignored, as are pixels with depth <= 0.  render_header: the geometry buffer of
+        the forward that rendered the frame; a render that outgrew its context integrates nothing and counts in header[5]."""
+        N.require_gpu_op((depth, color, w2c), render_header)
+        H, W = int(depth.shape[-2]), int(depth.shape[-1])
+        if depth.numel() != H * W or tuple(color.shape) != (3, H, W):
+            raise RuntimeError(f"dqo_eval.TsdfVolume.integrate: depth is [{H},{W}] and color [3,{H},{W}], got {tuple(depth.shape)} and {tuple(color.shape)}")
+        for t, name in ((depth, "depth"), (color, "color"), (w2c, "w2c")):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.tsdf.device:
+                raise RuntimeError(f"dqo_eval.TsdfVolume.integrate: {name} must be a contiguous float32 tensor on the volume's device")
+        if w2c.numel() != 16:
+            raise RuntimeError("dqo_eval.TsdfVolume.integrate: w2c holds 16 floats, row major")
+        fx, fy, cx, cy = _intrinsics(K)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().dqo_tsdf_integrate(*self.dims, *self.origin, self.voxel_length, self.sdf_trunc, self.tsdf.data_ptr(),
+                                               self.weight.data_ptr(), self.color.data_ptr(), self.header.data_ptr(), W, H, depth.data_ptr(),
+                                               color.data_ptr(), fx, fy, cx, cy, w2c.data_ptr(), float(depth_trunc), N.ptr(render_header),
+                                               N.current_stream()))
+        return self
+
+    def extract(self, cap_vertices, cap_faces, out=None):
+        """The volume's mesh: dict(vertices float32 [cap_vertices,3], colors float32 [cap_vertices,3], faces int32 [cap_faces,3], header),
+        all on the device; header[0..3] = vertices written, faces written, vertices dropped, faces dropped (rows behind the written
+        counts are not touched).  out: such a dict to write into (default: this volume's own buffers for the two capacities, made on the
+        first call and overwritten by the next).  Four launches, no host read; the same bits on every run."""
+        cv, cf = int(cap_vertices), int(cap_faces)
+        if cv < 0 or cf < 0:
+            raise RuntimeError(f"dqo_eval.TsdfVolume.extract: bad capacity: {cv} vertices, {cf} faces")
+        dev = self.tsdf.device
+        if out is None:
+            out = self._meshes.get((cv, cf))
+            if out is None:
+                out = self._meshes[(cv, cf)] = dict(vertices=torch.empty((cv, 3), dtype=torch.float32, device=dev),
+                                                    colors=torch.empty((cv, 3), dtype=torch.float32, device=dev),
+                                                    faces=torch.empty((cf, 3), dtype=torch.int32, device=dev))
+        v, c, f = out["vertices"], out["colors"], out["faces"]
+        N.require_gpu_op((self.tsdf,), v, c, f)
+        for t, shape, dtype, name in ((v, (cv, 3), torch.float32, "vertices"), (c, (cv, 3), torch.float32, "colors"), (f, (cf, 3), torch.int32, "faces")):
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or (t.numel() and t.device != dev):
+                raise RuntimeError(f"dqo_eval.TsdfVolume.extract: out[{name!r}] must be a contiguous {dtype} {list(shape)} tensor on the volume's device")
+        with torch.cuda.device(self.device):
+            N.check(N.lib().dqo_tsdf_extract(*self.dims, *self.origin, self.voxel_length, self.tsdf.data_ptr(), self.weight.data_ptr(),
+                                             self.color.data_ptr(), N.ptr(v), N.ptr(c), N.ptr(f), cv, cf, self.header.data_ptr(),
+                                             self._ws.data_ptr(), self._ws.numel(), N.current_stream()))
+        out["header"] = self.header
+        return out
+
+    def counts(self):
+        """{name: int} of the header (TSDF_HEADER): the last extract's written and dropped counts, the frames integrated and skipped
+        since clear() — the ONE host read."""
+        h = self.header.cpu().tolist()
+        return {n: int(x) for n, x in zip(TSDF_HEADER, h) if not n.startswith("unused")}

@@ -261,6 +261,7 @@ class FusedMapper:
         self._prune_ctx = None  # prune_floaters(): its camera tables, workspace and stats, made anew when P changes
         self._eval_tables, self._eval_ws = {}, None  # evaluate(): its [K,8] table per K, and dqo_eval's workspace
         self._eval_ms_ws = None  # evaluate_ms_ssim(): dqo_eval.ms_ssim's workspace
+        self._mesh_w2c = None  # make_mesh(): the frame's world-to-camera matrix, row major, float32 [4,4] on the device
         self._eval_object_rows = None  # evaluate_geometry_objects(): its int32 [P] group column (gaussian_object, -1 = the row is left out)
         self._checkpoint = {}  # pack_rows() / save_model(): workspace, header, table and pinned staging buffer, made anew when P changes
         # refresh_window(): its [K] ratio table per K, dqo_window_masks' workspace, the uint8 [P] row flags of its render (per P)
@@ -841,6 +842,39 @@ class FusedMapper:
                 if ms_ssim is not None:
                     dqo_eval.ms_ssim(o[0], gt_color, out=ms_ssim, row=k, workspace_buffer=self._eval_ms_ws, render_header=c.geom)
         return table
+
+    @torch.no_grad()
+    def make_mesh(self, frames, volume, depth_trunc=30.0):
+        """The map as a triangle mesh: what make_mesh.py and eval_frame(..., volume=..., scale=...) (SLAM/eval.py:299, 316-343) do with
+        an open3d TSDF volume — every frame's render of the whole map becomes an RGB-D image and is integrated — into `volume`, a
+        dqo_eval.TsdfVolume the caller made over the box it wants (and clears when it wants a fresh one).  frames: a list of raster
+        settings, None = the mapper's camera.  Per frame: the whole map rendered on maintain()'s persistent context (_maintain_render, as
+        evaluate() does: no row flags, no gate — what eval_frame renders), then volume.integrate(depth, colour) with
+        fx = W / (2 tanfovx), fy = H / (2 tanfovy), the settings' cx, cy, w2c = the transpose of the settings' viewmatrix (formed on the
+        device) and render_header = the context's header: a frame that outgrew the context integrates nothing and counts in
+        volume.header[5] (maintain_overflowed() tells, where a read is affordable).  depth_trunc: deeper pixels are ignored.
+        The reference swaps its eval opaque threshold into the renderer for this walk (make_mesh.py:156); here the caller chooses it:
+        pass settings whose opaque_threshold is the one it wants.  The FIRST call for a (P, H, W) sizes the render's context from one
+        32-byte header read, exactly as maintain() does; after that a call reads nothing back, allocates nothing and does not
+        synchronise.  Returns `volume`; volume.extract(cap_vertices, cap_faces) is the mesh, dqo_ply.write_mesh_ply its file.
+        Not built: Laplacian smoothing (the mesh_smooth_* keys of the reference's configs are read by nothing in its tree), mesh
+        simplification; NotImplementedError on a sharded mapper (a shard's render shows its objects only, volumes are not merged)."""
+        if self.attach_count_reducer is not None:
+            raise NotImplementedError("FusedMapper.make_mesh: a sharded mapper would need the whole map's render, a shard's shows its "
+                                      "objects only (DESIGN.md §6)")
+        dev = self.device
+        H, W = int(self.settings.image_height), int(self.settings.image_width)
+        if self._mesh_w2c is None:
+            self._mesh_w2c = torch.empty((4, 4), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            self.activate()
+            for settings in frames:
+                st = self.settings if settings is None else _normalised_settings(settings, dev)
+                c = self._maintain_render(st)
+                self._mesh_w2c.copy_(st.viewmatrix.reshape(4, 4).t())  # (the settings keep the transposed w2c)
+                K = (W / (2.0 * float(st.tanfovx)), H / (2.0 * float(st.tanfovy)), float(st.cx), float(st.cy))
+                volume.integrate(c.out[1], c.out[0], K, self._mesh_w2c, depth_trunc=depth_trunc, render_header=c.geom)
+        return volume
 
     @torch.no_grad()
     def densify(self, rows="stable", **kw):

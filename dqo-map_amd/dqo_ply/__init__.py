@@ -13,7 +13,8 @@ The reference goes through the third-party `plyfile` package (not vendored, not 
 the reference stores.
 
 read_mesh_ply reads the other PLY of an evaluation: the ground-truth triangle mesh eval_pcd loads with trimesh (SLAM/eval.py:236), as
-the two arrays dqo_eval.sample_surface takes.
+the two arrays dqo_eval.sample_surface takes.  write_mesh_ply writes such a file — the mesh of dqo_eval.TsdfVolume.extract, with vertex
+colours — in the layout read_mesh_ply reads.
 """
 import numpy as np
 
@@ -371,3 +372,37 @@ def read_mesh_ply(path):
     if n == 4:
         idx = idx[:, [0, 1, 2, 0, 2, 3]].reshape(-1, 3)
     return vertices, np.ascontiguousarray(idx, dtype=np.int32)
+
+
+def write_mesh_ply(path, vertices, faces, colors=None):
+    """A triangle mesh file that read_mesh_ply reads back: `format binary_little_endian 1.0`, a `vertex` element of float x y z and, with
+    colors, uchar red green blue = round(255 * clamp(c, 0, 1)), then a `face` element `property list uchar int vertex_indices`.
+    vertices [V,3], faces [F,3] (indices, written as int32), colors [V,3] in [0, 1] or None; arrays or tensors (a device tensor is copied
+    to the host: cut the buffers of dqo_eval.TsdfVolume.extract at its written counts first).  Returns (V, F)."""
+    a = lambda t, dt: np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=dt)
+    v, f = a(vertices, np.float32), a(faces, np.int32)
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError(f"write_mesh_ply: vertices must be [V,3] and faces [F,3], got {v.shape} and {f.shape}")
+    V, F = v.shape[0], f.shape[0]
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = "ply\nformat binary_little_endian 1.0\n" + f"element vertex {V}\n" + "property float x\nproperty float y\nproperty float z\n"
+    if colors is not None:
+        c = a(colors, np.float32)
+        if c.shape != (V, 3):
+            raise ValueError(f"write_mesh_ply: colors must be [{V},3], got {c.shape}")
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    header += f"element face {F}\nproperty list uchar int vertex_indices\nend_header\n"
+    vt = np.zeros((V,), dtype=np.dtype(fields))
+    vt["x"], vt["y"], vt["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if colors is not None:
+        with np.errstate(invalid="ignore"):
+            c8 = np.rint(255.0 * np.clip(np.nan_to_num(c.astype(np.float64), nan=0.0), 0.0, 1.0)).astype(np.uint8)
+        vt["red"], vt["green"], vt["blue"] = c8[:, 0], c8[:, 1], c8[:, 2]
+    ft = np.zeros((F,), dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    ft["n"], ft["v"] = 3, f
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(vt.tobytes())
+        fh.write(ft.tobytes())
+    return V, F

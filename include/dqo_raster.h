@@ -1105,6 +1105,70 @@ int dqo_prune_rows(int32_t P, float* xyz, float* opacity_raw, float* scaling_raw
                    uint8_t* stable, int32_t* add_tick, int32_t* depth_error_counter, int32_t* color_error_counter, int32_t* frame_id,
                    const float* park, int32_t lo, int32_t hi, void* workspace, size_t workspace_bytes, int32_t* stats, void* hipStream);
 
+/* dqo_tsdf_clear / dqo_tsdf_integrate / dqo_tsdf_extract (ABI 5, symbols-only addition) — the map as a triangle mesh: what make_mesh.py
+ * and eval_frame(..., volume=..., scale=...) (SLAM/eval.py:299, 316-343: every frame's render becomes an RGB-D image, then
+ * volume.integrate(rgbd, intrinsics, w2c) on an open3d TSDF volume) are there to produce.  The shipped make_mesh.py breaks off inside its
+ * loop and open3d does not exist on this platform, so THIS text defines the rule (it follows open3d's UniformTSDFVolume integrate as
+ * published) and tests/tsdf_oracle.py restates it in numpy; nothing is pinned against the library.  csrc/map_tsdf.hip lists every
+ * statement in order.  Plain arguments, no struct.
+ *
+ * The volume: a DENSE uniform grid over the caller's box (not open3d's hashed blocks) of nx x ny x nz voxels, x fastest, lattice point
+ *   (x, y, z) at origin + (index + 0.5) * voxel_length.  The caller owns the device tensors, a structure of arrays: tsdf float32
+ *   [nz,ny,nx], weight float32 [nz,ny,nx], color float32 [3,nz,ny,nx], header int32 [8].  Every entry refuses, before any launch
+ *   (DQO_ERR_INVALID_ARG), a side below 2 and nx * ny * nz >= 2^28.
+ * dqo_tsdf_clear — one launch (no memset): tsdf = 1, weight = 0, color = 0, header = 0.
+ * dqo_tsdf_integrate — one frame, one launch, one thread per voxel, float32, one rounding per operation, left to right, none contracted,
+ *   division and square root correctly rounded.  depth float32 [H,W] in metres, image float32 [3,H,W], fx fy cx cy the pinhole
+ *   intrinsics, w2c 16 floats in DEVICE memory, row major (world to camera), m below:
+ *       pw_a = origin_a + ((float)i_a + 0.5f) * L                                  a = x, y, z
+ *       pc_r = ((m[r][0] * pw_x + m[r][1] * pw_y) + m[r][2] * pw_z) + m[r][3]
+ *       skip unless pc_z > 0
+ *       u_f = ((pc_x * fx) / pc_z + cx) + 0.5f;  v_f likewise with fy, cy
+ *       skip unless u_f >= 0.0001f && u_f < (float)W - 0.0001f                     (the same for v_f and H)
+ *       u = (int)u_f;  v = (int)v_f;  d = depth[v][u]
+ *       skip unless d > 0 && d <= depth_trunc
+ *       mult = sqrtf((1.0f + ((u - cx) / fx) * ((u - cx) / fx)) + ((v - cy) / fy) * ((v - cy) / fy))
+ *       sdf = (d - pc_z) * mult;  skip unless sdf > -sdf_trunc
+ *       t = fminf(1.0f, sdf / sdf_trunc);  w = weight
+ *       tsdf = (tsdf * w + t) / (w + 1.0f);  color_c = (color_c * w + image[c][v][u]) / (w + 1.0f);  weight = w + 1.0f
+ *   Every skip comes before the thread's first access to the volume; a touched voxel reads 20 bytes and writes 20, plus one gathered
+ *   pixel.  render_header (may be NULL): the device header of the forward that rendered the frame; a render that outgrew its context
+ *   (overflow != 0, as dqo_eval_picture tests it) integrates nothing and adds 1 to header[5]; every other frame adds 1 to header[4].
+ *   DQO_ERR_INVALID_ARG before the launch: bad dims, voxel_length or sdf_trunc not above 0, a bad image size, a NULL pointer.
+ * dqo_tsdf_extract — the volume as a welded, indexed, coloured triangle mesh in caller-owned device buffers: vertices float32
+ *   [cap_vertices,3], vertex_color float32 [cap_vertices,3], faces int32 [cap_faces,3].  Marching tetrahedra on the Kuhn decomposition
+ *   (no marching-cubes table; watertight by construction); four launches, no host read, no float atomics, the same bits on every run.
+ *     - a cube is the lattice points o + {0,1}^3, named by o, valid iff all eight weights are > 0; the corner o + (dx,dy,dz) has code
+ *       dx + 2 dy + 4 dz.  Tetrahedron k belongs to the k-th permutation p of (0,1,2) in lexicographic order, path corners c0 = o,
+ *       c1 = c0 + e[p0], c2 = c1 + e[p1], c3 = o + (1,1,1).
+ *     - the edges are of seven translation-invariant types, offsets (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1) = types 0..6;
+ *       an edge is owned by its lower lattice point.  A corner is negative iff tsdf < 0.  An edge carries a vertex iff its ends differ in
+ *       sign and at least one valid cube contains it: no vertex is unreferenced.
+ *     - with a the negative end, s = f_a / (f_a - f_b); position and colour are p_a + s * (p_b - p_a) per component (float32, one
+ *       rounding each).  Vertices are numbered in ascending (lattice linear index, edge type).
+ *     - triangles per tetrahedron case (bit i: path corner i is negative): one negative corner a — the edges (a,b) for the positive b
+ *       ascending; three — the edges (a,b) for the negative a ascending; two, a0 < a1 and b0 < b1 — the quad (a0b0, a0b1, a1b1, a1b0) cut
+ *       into (q0,q1,q2), (q0,q2,q3).  The last two indices are swapped iff FLIP[case] XOR parity(p), FLIP = cases 0010 0101 1000 1010
+ *       1011 1110 (bit 3 first): the right-hand normal points to the positive side, free space.  Faces are numbered in ascending (cube
+ *       linear index, tetrahedron, triangle).
+ *     - capacities: the vertex list is cut at cap_vertices; the faces that name a cut vertex leave the list; what is left is cut at
+ *       cap_faces.  Nothing is written behind either.  header[0..3] = vertices written, faces written, vertices dropped, faces dropped.
+ *   DQO_ERR_INVALID_ARG before any launch: bad dims, a NULL volume buffer or header, a capacity below 0, a NULL mesh buffer with a
+ *   capacity above 0; DQO_ERR_WORKSPACE.
+ * workspace: dqo_tsdf_workspace_bytes(nx, ny, nz) bytes (0 for bad dims; 5 bytes per voxel and 12 per 2048 voxels behind the ticket words),
+ *   ZERO when first used and then left to dqo_tsdf_extract, which hands it back ready for the next call.
+ * Not built: Laplacian smoothing (the mesh_smooth_iter / mesh_smooth_lambda keys of configs/Cube_Diorama_base.yaml:45-46 are read by nothing
+ *   in the reference tree), hashed or sparse volumes, mesh simplification, merging the volumes of shards. */
+size_t dqo_tsdf_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int dqo_tsdf_clear(int32_t nx, int32_t ny, int32_t nz, float* tsdf, float* weight, float* color, int32_t* header, void* hipStream);
+int dqo_tsdf_integrate(int32_t nx, int32_t ny, int32_t nz, float origin_x, float origin_y, float origin_z, float voxel_length,
+                       float sdf_trunc, float* tsdf, float* weight, float* color, int32_t* header, int32_t W, int32_t H, const float* depth,
+                       const float* image, float fx, float fy, float cx, float cy, const float* w2c, float depth_trunc,
+                       const DqoRastHeader* render_header, void* hipStream);
+int dqo_tsdf_extract(int32_t nx, int32_t ny, int32_t nz, float origin_x, float origin_y, float origin_z, float voxel_length,
+                     const float* tsdf, const float* weight, const float* color, float* vertices, float* vertex_color, int32_t* faces,
+                     int32_t cap_vertices, int32_t cap_faces, int32_t* header, void* workspace, size_t workspace_bytes, void* hipStream);
+
 #define DQO_TICKET_WORDS (16 + 16 * 64) /* int32 words behind DqoAdamStep.block_ticket */
 typedef struct DqoAdamStep {
     int32_t P, M;      /* Gaussians, SH coefficients per Gaussian (f_dc = coefficient 0, f_rest = the others) */
