@@ -4,7 +4,8 @@
 // can be captured in a hipGraph.  Users: map_eval.hip (eval_picture_kernel, eval_pcd_kernel, eval_pcd_grouped_kernel: its own partial lines), map_msssim.hip (msssim_level_kernel), map_lifecycle.hip (the two cloud limits and
 // the frame's counts), map_prune.hip (prune_rows_kernel: ticket and counts), map_tilemask.hip (window_masks_kernel: ticket only, its last block selects tiles), map_checkpoint.hip (map_pack_count_kernel: its last block scans
 // the blocks' row counts), map_meshsample.hip (mesh_area_kernel: max and counts; mesh_quantise_kernel: its last block scans the blocks'
-// quanta), map_tsdf.hip (tsdf_edges_kernel, tsdf_vertices_kernel: their last blocks scan the spans' vertex and face counts), dqo_adam.h
+// quanta), map_tsdf.hip (tsdf_edges_kernel, tsdf_vertices_kernel: their last blocks scan the spans' vertex and face counts),
+// map_meshops.hip (mesh_comp_stats / _fcount / _vcount_kernel, mesh_csr_scan_kernel: span partials folded or scanned), dqo_adam.h
 // (ticket only, unfenced).
 //
 // Below the double reductions, the integer ends the map operators share (behind whichever last-block ticket their kernel takes):

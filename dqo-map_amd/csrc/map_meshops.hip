@@ -1,0 +1,760 @@
+// Mesh clean-up for gfx950 on the indexed mesh dqo_tsdf_extract leaves (map_tsdf.hip): connected components and the filtered mesh, Laplacian /
+// Taubin smoothing, area-weighted vertex normals — what a SLAM mesh pipeline does with open3d's cluster_connected_triangles +
+// remove_triangles_by_mask + remove_unreferenced_vertices, filter_smooth_laplacian / filter_smooth_taubin (the reference's
+// configs/Cube_Diorama_base.yaml:45-46 names mesh_smooth_iter: 10, mesh_smooth_lambda: 0.5) and compute_vertex_normals.  open3d does not
+// exist on this platform, so the rules of include/dqo_raster.h are the definition (they follow open3d's published algorithms; the
+// departures are listed there) and tests/mesh_ops_oracle.py restates them in numpy; nothing is pinned against the library.
+//
+// The operand: vertices float32 [cap_v,3], colors float32 [cap_v,3] (may be NULL), faces int32 [cap_f,3], counts = a device pointer to
+// two int32 (vertices, faces; NULL: the capacities are the counts; a count is clamped to [0, capacity]).  Rows behind the counts are never
+// read and never written; grids are sized from the capacities, so the launch count is a fixed function of the arguments: no host read, no
+// synchronise, no memset (what must be zero is cleared by a launch), no float atomics.  Blocks are 256 threads.  A face is VALID iff its
+// three indices lie in [0, V).
+//
+// dqo_mesh_components — eleven launches:
+//   init      parent[v] = v, size[v] = 0, mark[v] = 0, header = 0;
+//   prelink   parent[x] = min(parent[x], the smallest index of a valid face that names x) by atomicMin, nothing returned, then a first
+//   flatten   — a forest of the right sets already, whose trees end in local minima.  Without the two the hook took 1.14 ms on the mesh
+//             of a 256^3 room scan (514 k faces in lattice order: long chains of dependent reads), with them 0.29 ms (profiles/mesh_ops.txt);
+//   hook      a lock-free union-find over `parent`: a valid face unites (a, b) and (a, c); a union finds both roots with path halving and
+//             links the LARGER root under the smaller by a returning CAS that expects the root to still be one.  parent[x] <= x always, so
+//             the final root of a set is its smallest vertex id whatever order the hardware ran in.  Bad faces are counted, one integer
+//             atomic per wave that has any;
+//   flatten   parent[v] = root(v), by a walk that stores nothing: v's own thread is the only writer of parent[v], so it is final;
+//   label     label[f] = parent[a] (-1: a bad face), size[root] += 1 — aggregated first: a lane carries (root, count) over the eight
+//             faces it visits and hands it on only when the root changes, and a wave issues ONE atomic per distinct root among its lanes
+//             (a mesh that is one big component costs one same-address atomic per 512 faces, not one per face);
+//   stats     components (roots with size > 0) and the largest size: block partials, folded by the launch's last block (dqo_reduce.h);
+//   fcount    threshold = max(min_faces, largest_only ? largest : 0); keep[f] = label >= 0 && size[label] >= threshold; the vertices of a
+//             kept face are marked; the spans' kept counts, scanned by the last block (dqo_scan_block_counts) -> header[1], [7];
+//   vcount    the spans' marked-vertex counts and kept-component counts, scanned -> header[0], [6], [3];
+//   vscatter  marked vertices, in order, to their dense new ids (positions and colours copied bit for bit); mark[v] becomes the new id;
+//   fscatter  kept faces, in order, renumbered.
+// dqo_mesh_smooth / dqo_mesh_normals share one CSR build (five launches), templated on what a corner contributes: its two other
+// vertices (neighbours) or its face:
+//   zero      deg[v] = 0;
+//   count     deg[vertex of a corner of a valid face] += entries (integer atomics on scattered addresses);
+//   scan      a vertex's exclusive count within its span of 2048 and the spans' totals, scanned by the last block;
+//   fill      every corner takes its slots through the vertex's own count as a cursor (atomicSub; the order inside a segment is racy here);
+//   tidy      every segment is sorted ascending; neighbours also lose their duplicates and the vertex itself.  After it nothing depends on
+//             the race.  Up to 32 raw entries (a marching-tetrahedra vertex has at most 20): an insertion sort by the vertex's thread.
+//             More: the vertex's block sorts it with a bitonic network (the same-direction form, which takes any length) — in LDS up to
+//             2048 entries, in place in global memory beyond — and compacts it with block scans.
+// Then smoothing runs one thread per vertex per step (a gather over the segment, double arithmetic, ping-pong between the mesh and the
+// workspace, a copy back after an odd number of steps), normals one thread per vertex.  Every double statement is the one written,
+// rounded once, none contracted (the Makefile states -ffp-contract=off); sqrt and `/` on doubles are the correctly rounded ones.
+#include "dqo_common.h"
+#include "dqo_reduce.h"
+
+namespace {
+
+typedef unsigned long long u64;
+
+enum {
+    MO_CHUNKS = 8,        // runs of 256 items that a block of a span launch walks
+    MO_SPAN_SHIFT = 11,   // a span: 2048 consecutive vertices / faces
+    MO_SPAN = 1 << MO_SPAN_SHIFT,
+    MO_THREAD_MAX = 32,   // tidy: raw entries a single thread sorts
+    MO_LDS_MAX = 2048,    // tidy: raw entries a block sorts in LDS
+    MO_MAX = 1 << 28,     // capacities lie below it: 6 cap_f adjacency entries stay below 2^32
+};
+static_assert(MO_SPAN == 256 * MO_CHUNKS, "a span is MO_CHUNKS runs of a block");
+
+__host__ __device__ inline size_t mo_blocks(size_t n) { return (n + 255) / 256; }
+__host__ __device__ inline size_t mo_spans(size_t n) { return (n + MO_SPAN - 1) / MO_SPAN; }
+
+__device__ __forceinline__ uint32_t mo_count(const int32_t* counts, int k, uint32_t cap) {
+    if (counts == nullptr) return cap;
+    const int32_t n = counts[k];
+    return n <= 0 ? 0u : ((uint32_t)n < cap ? (uint32_t)n : cap);
+}
+
+__device__ __forceinline__ int32_t mo_ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void mo_st(int32_t* p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ bool mo_face(const int32_t* __restrict__ faces, uint32_t f, uint32_t V, int32_t& a, int32_t& b, int32_t& c) {
+    a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
+    return (uint32_t)a < V && (uint32_t)b < V && (uint32_t)c < V;
+}
+
+// ---- components -------------------------------------------------------------------------------------------------------------------------
+struct MoComp {
+    int32_t* head;
+    int32_t* parent;   // [cap_v]
+    int32_t* size;     // [cap_v] faces of the component whose root this vertex is
+    int32_t* mark;     // [cap_v] 1: a kept face names the vertex; after vscatter: its new id
+    int32_t* label;    // [cap_f] (the caller's, or the workspace's)
+    uint8_t* keep;     // [cap_f]
+    u64* spair;        // [spans of cap_v] stats: components | largest << 32 of the span
+    u64* vpair;        // [spans of cap_v] marked vertices | kept components << 32
+    uint32_t* fblock;  // [spans of cap_f] kept faces
+};
+
+// the root of x, with path halving.  parent[y] <= y, and a vertex that is no root never becomes one again: the store below only ever
+// replaces an ancestor of a non-root by another ancestor, and no CAS of mo_unite succeeds on a non-root.  That keeps the SETS right under
+// any interleaving; it does not keep parent[x] moving towards the root — a store formed from older loads can land behind a newer one
+// and put a farther ancestor back.  So whoever needs THE root walks for it (mo_unite, the final flatten's mo_root)
+__device__ __forceinline__ int32_t mo_find(int32_t* parent, int32_t x) {
+    for (;;) {
+        const int32_t p = mo_ld(parent + x);
+        if (p == x) return x;
+        const int32_t gp = mo_ld(parent + p);
+        if (gp != p) mo_st(parent + x, gp);
+        x = gp;
+    }
+}
+
+__device__ __forceinline__ void mo_unite(int32_t* parent, int32_t a, int32_t b) {
+    int32_t ra = mo_find(parent, a), rb = mo_find(parent, b);
+    while (ra != rb) {
+        if (ra < rb) {
+            const int32_t t = ra;
+            ra = rb, rb = t;
+        }
+        const int32_t old = atomicCAS(parent + ra, ra, rb);  // the larger root under the smaller, if it still is a root
+        if (old == ra) return;
+        ra = mo_find(parent, old), rb = mo_find(parent, rb);
+    }
+}
+
+__global__ __launch_bounds__(256) void mesh_comp_init_kernel(const int32_t* __restrict__ counts, uint32_t cap_v, MoComp w,
+                                                             int32_t* __restrict__ header) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < 8u) header[i] = 0;
+    if (i >= mo_count(counts, 0, cap_v)) return;
+    w.parent[i] = (int32_t)i, w.size[i] = 0, w.mark[i] = 0;
+}
+
+// before the hook: every vertex of a valid face is linked to the face's smallest index if that is below its parent (atomicMin on
+// scattered addresses, nothing returned).  parent[x] <= x still holds and a parent lies in its child's component, so this is a forest of
+// the right sets already; flattened once, it leaves the hook little more than the unions between the local minima's trees.
+__global__ __launch_bounds__(256) void mesh_comp_prelink_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ counts,
+                                                                uint32_t cap_v, uint32_t cap_f, MoComp w) {
+    const uint32_t f = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t V = mo_count(counts, 0, cap_v), F = mo_count(counts, 1, cap_f);
+    if (f >= F) return;
+    int32_t a, b, c;
+    if (!mo_face(faces, f, V, a, b, c)) return;
+    const int32_t m = min(a, min(b, c));
+    if (a != m) atomicMin(w.parent + a, m);
+    if (b != m) atomicMin(w.parent + b, m);
+    if (c != m) atomicMin(w.parent + c, m);
+}
+
+__global__ __launch_bounds__(256) void mesh_comp_hook_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ counts,
+                                                             uint32_t cap_v, uint32_t cap_f, MoComp w, int32_t* __restrict__ header) {
+    const uint32_t f = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t V = mo_count(counts, 0, cap_v), F = mo_count(counts, 1, cap_f);
+    bool bad = false;
+    if (f < F) {
+        int32_t a, b, c;
+        if (mo_face(faces, f, V, a, b, c)) {
+            if (a != b) mo_unite(w.parent, a, b);
+            if (a != c) mo_unite(w.parent, a, c);
+        } else bad = true;
+    }
+    const int n = __popcll(__ballot(bad));
+    if ((threadIdx.x & 63) == 0 && n > 0) atomicAdd(&header[4], n);
+}
+
+// the root of x by a walk that stores nothing
+__device__ __forceinline__ int32_t mo_root(const int32_t* parent, int32_t x) {
+    for (;;) {
+        const int32_t p = mo_ld(parent + x);
+        if (p == x) return x;
+        x = p;
+    }
+}
+
+// parent[i] = root(i).  FINAL (behind the hook; the label launch takes parent[a] as the root without a find): the walk stores nothing, so
+// parent[i] has ONE writer in the launch, thread i, and what it writes is the root — no union runs beside it, a root stays one, and
+// whatever a walk reads on its way (an older ancestor, or a root another thread has just written) lies on the path to the same root.
+// A halving walk here could leave parent[i] short of the root: thread j, passing through i, reads parent[i] and parent[parent[i]],
+// thread i writes the root in between, and j's late store puts the nearer ancestor back.  The first flatten (behind prelink) only
+// shortens paths for the hook, which finds for itself, and keeps the halving.
+template <bool FINAL>
+__global__ __launch_bounds__(256) void mesh_comp_flatten_kernel(const int32_t* __restrict__ counts, uint32_t cap_v, MoComp w) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= mo_count(counts, 0, cap_v)) return;
+    mo_st(w.parent + i, FINAL ? mo_root(w.parent, (int32_t)i) : mo_find(w.parent, (int32_t)i));
+}
+
+// size[root] += cnt for the lanes with `active`, one atomic per distinct root of the wave.  Called by every lane of the wave.
+__device__ __forceinline__ void mo_wave_add(int32_t* size, int32_t root, uint32_t cnt, bool active, int lane) {
+    u64 todo = __ballot(active);
+    while (todo != 0ull) {  // (wave-uniform)
+        const int leader = __ffsll((long long)todo) - 1;
+        const int32_t r = __shfl(root, leader);
+        const bool same = active && root == r;
+        const uint32_t total = dqo_wave_sum_u32(same ? cnt : 0u, lane);
+        if (lane == leader) atomicAdd(&size[r], (int32_t)total);
+        todo &= ~__ballot(same);
+    }
+}
+
+__global__ __launch_bounds__(256) void mesh_comp_label_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ counts,
+                                                              uint32_t cap_v, uint32_t cap_f, MoComp w) {
+    const uint32_t V = mo_count(counts, 0, cap_v), F = mo_count(counts, 1, cap_f);
+    const int lane = threadIdx.x & 63;
+    int32_t held = -1;  // the root this lane is counting for, and how many faces so far
+    uint32_t held_n = 0u;
+    for (uint32_t chunk = 0; chunk < (uint32_t)MO_CHUNKS; chunk++) {
+        const uint32_t f = (blockIdx.x * (uint32_t)MO_CHUNKS + chunk) * 256u + threadIdx.x;
+        int32_t r = -1;
+        if (f < F) {
+            int32_t a, b, c;
+            if (mo_face(faces, f, V, a, b, c)) r = w.parent[a];
+            w.label[f] = r;
+        }
+        const bool flush = held_n != 0u && r >= 0 && r != held;
+        mo_wave_add(w.size, held, held_n, flush, lane);
+        if (flush) held_n = 0u;
+        if (r >= 0) held = r, held_n++;
+    }
+    mo_wave_add(w.size, held, held_n, held_n != 0u, lane);
+}
+
+// the block's sum of n and maximum of mx, for every thread.  s8: 8 words of LDS.
+__device__ __forceinline__ void mo_block_sum_max(uint32_t& n, uint32_t& mx, uint32_t* s8) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    n = dqo_wave_sum_u32(n, lane), mx = dqo_wave_max_u32(mx, lane);
+    __syncthreads();  // (s8 may still be read by the previous call)
+    if (lane == 0) s8[wave] = n, s8[4 + wave] = mx;
+    __syncthreads();
+    n = (s8[0] + s8[1]) + (s8[2] + s8[3]);
+    mx = max(max(s8[4], s8[5]), max(s8[6], s8[7]));
+}
+
+__global__ __launch_bounds__(256) void mesh_comp_stats_kernel(const int32_t* __restrict__ counts, uint32_t cap_v, MoComp w,
+                                                              int32_t* __restrict__ header) {
+    __shared__ uint32_t s8[8];
+    __shared__ int s_last;
+    const uint32_t V = mo_count(counts, 0, cap_v);
+    uint32_t n = 0u, mx = 0u;
+    for (uint32_t chunk = 0; chunk < (uint32_t)MO_CHUNKS; chunk++) {
+        const uint32_t i = (blockIdx.x * (uint32_t)MO_CHUNKS + chunk) * 256u + threadIdx.x;
+        if (i < V && w.parent[i] == (int32_t)i) {
+            const uint32_t s = (uint32_t)w.size[i];
+            if (s != 0u) n++, mx = max(mx, s);
+        }
+    }
+    mo_block_sum_max(n, mx, s8);
+    if (threadIdx.x == 0) __hip_atomic_store(&w.spair[blockIdx.x], (u64)n | ((u64)mx << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!dqo_last_block(w.head, &s_last)) return;
+    n = 0u, mx = 0u;
+    for (uint32_t b = threadIdx.x; b < gridDim.x; b += 256u) {
+        const u64 p = __hip_atomic_load(&w.spair[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        n += (uint32_t)p, mx = max(mx, (uint32_t)(p >> 32));
+    }
+    mo_block_sum_max(n, mx, s8);
+    if (threadIdx.x == 0) header[2] = (int32_t)n, header[5] = (int32_t)mx;
+}
+
+__device__ __forceinline__ int32_t mo_threshold(const int32_t* header, int32_t min_faces, int32_t largest_only) {
+    const int32_t largest = largest_only ? header[5] : 0;
+    return min_faces > largest ? min_faces : largest;
+}
+
+__global__ __launch_bounds__(256) void mesh_comp_fcount_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ counts,
+                                                               uint32_t cap_f, MoComp w, int32_t min_faces, int32_t largest_only,
+                                                               int32_t* __restrict__ header) {
+    __shared__ uint32_t s_wave[4];
+    __shared__ int s_last;
+    const uint32_t F = mo_count(counts, 1, cap_f);
+    const int32_t thr = mo_threshold(header, min_faces, largest_only);
+    uint32_t run = 0u;
+    for (uint32_t chunk = 0; chunk < (uint32_t)MO_CHUNKS; chunk++) {
+        const uint32_t f = (blockIdx.x * (uint32_t)MO_CHUNKS + chunk) * 256u + threadIdx.x;
+        uint32_t keep = 0u;
+        if (f < F) {
+            const int32_t l = w.label[f];
+            keep = (l >= 0 && w.size[l] >= thr) ? 1u : 0u;
+            w.keep[f] = (uint8_t)keep;
+            if (keep) {  // (a labelled face: its indices are in range)
+                w.mark[faces[3 * (size_t)f]] = 1, w.mark[faces[3 * (size_t)f + 1]] = 1, w.mark[faces[3 * (size_t)f + 2]] = 1;
+            }
+        }
+        uint32_t total;
+        dqo_block_exclusive<uint32_t>(keep, total, s_wave);
+        run += total;
+    }
+    if (threadIdx.x == 0) __hip_atomic_store(&w.fblock[blockIdx.x], run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!dqo_last_block(w.head, &s_last)) return;
+    const uint32_t kept = dqo_scan_block_counts<uint32_t, 4>(w.fblock, gridDim.x, 1, s_wave);
+    if (threadIdx.x == 0) header[1] = (int32_t)kept, header[7] = (int32_t)(F - (uint32_t)header[4] - kept);
+}
+
+__global__ __launch_bounds__(256) void mesh_comp_vcount_kernel(const int32_t* __restrict__ counts, uint32_t cap_v, MoComp w, int32_t min_faces,
+                                                               int32_t largest_only, int32_t* __restrict__ header) {
+    __shared__ u64 s_wave[4];
+    __shared__ int s_last;
+    const uint32_t V = mo_count(counts, 0, cap_v);
+    const int32_t thr = mo_threshold(header, min_faces, largest_only);
+    u64 pair = 0ull;
+    for (uint32_t chunk = 0; chunk < (uint32_t)MO_CHUNKS; chunk++) {
+        const uint32_t i = (blockIdx.x * (uint32_t)MO_CHUNKS + chunk) * 256u + threadIdx.x;
+        if (i >= V) break;
+        pair += (u64)(uint32_t)w.mark[i];
+        if (w.parent[i] == (int32_t)i) {
+            const int32_t s = w.size[i];
+            if (s > 0 && s >= thr) pair += 1ull << 32;
+        }
+    }
+    u64 total;
+    dqo_block_exclusive<u64>(pair, total, s_wave);
+    if (threadIdx.x == 0) __hip_atomic_store(&w.vpair[blockIdx.x], total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!dqo_last_block(w.head, &s_last)) return;
+    const u64 sums = dqo_scan_block_counts<u64, 2>(w.vpair, gridDim.x, 1, s_wave);
+    if (threadIdx.x == 0) header[0] = (int32_t)(uint32_t)sums, header[6] = (int32_t)(V - (uint32_t)sums), header[3] = (int32_t)(sums >> 32);
+}
+
+__global__ __launch_bounds__(256) void mesh_comp_vscatter_kernel(const float* __restrict__ vertices, const float* __restrict__ colors,
+                                                                 const int32_t* __restrict__ counts, uint32_t cap_v, MoComp w,
+                                                                 float* __restrict__ out_vertices, float* __restrict__ out_colors) {
+    __shared__ uint32_t s_wave[4];
+    const uint32_t V = mo_count(counts, 0, cap_v);
+    uint32_t run = (uint32_t)w.vpair[blockIdx.x];  // marked vertices of the spans before this one, then of the span so far
+    for (uint32_t chunk = 0; chunk < (uint32_t)MO_CHUNKS; chunk++) {
+        const uint32_t i = (blockIdx.x * (uint32_t)MO_CHUNKS + chunk) * 256u + threadIdx.x;
+        const uint32_t m = i < V ? (uint32_t)w.mark[i] : 0u;
+        uint32_t total;
+        const uint32_t before = dqo_block_exclusive<uint32_t>(m, total, s_wave);
+        if (m != 0u) {
+            const size_t id = (size_t)run + before;  // (<= i: inside the out buffers, whose capacities are not below the input's)
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                out_vertices[3 * id + c] = vertices[3 * (size_t)i + c];
+                if (colors != nullptr) out_colors[3 * id + c] = colors[3 * (size_t)i + c];
+            }
+            w.mark[i] = (int32_t)id;
+        }
+        run += total;
+    }
+}
+
+__global__ __launch_bounds__(256) void mesh_comp_fscatter_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ counts,
+                                                                 uint32_t cap_f, MoComp w, int32_t* __restrict__ out_faces) {
+    __shared__ uint32_t s_wave[4];
+    const uint32_t F = mo_count(counts, 1, cap_f);
+    uint32_t run = w.fblock[blockIdx.x];
+    for (uint32_t chunk = 0; chunk < (uint32_t)MO_CHUNKS; chunk++) {
+        const uint32_t f = (blockIdx.x * (uint32_t)MO_CHUNKS + chunk) * 256u + threadIdx.x;
+        const uint32_t k = f < F ? (uint32_t)w.keep[f] : 0u;
+        uint32_t total;
+        const uint32_t before = dqo_block_exclusive<uint32_t>(k, total, s_wave);
+        if (k != 0u) {
+            const size_t o = (size_t)run + before;  // (<= f)
+#pragma unroll
+            for (int c = 0; c < 3; c++) out_faces[3 * o + c] = w.mark[faces[3 * (size_t)f + c]];
+        }
+        run += total;
+    }
+}
+
+// ---- the CSR of a vertex's neighbours (NBR) or of its corners' faces ----------------------------------------------------------------------
+struct MoCsr {
+    int32_t* head;
+    uint32_t* deg;   // [cap_v + 1] raw entries (count), the fill's cursor (fill), the tidied entries (tidy)
+    uint32_t* off;   // [cap_v + 1] raw entries of the span's vertices before this one
+    uint32_t* span;  // [spans of cap_v + 1] raw entries of the span, then of the spans before it
+    int32_t* adj;    // [6 cap_f] (NBR) or [3 cap_f]
+};
+
+__device__ __forceinline__ size_t mo_start(const MoCsr& c, uint32_t v) { return (size_t)c.span[v >> MO_SPAN_SHIFT] + (size_t)c.off[v]; }
+
+__global__ __launch_bounds__(256) void mesh_csr_zero_kernel(uint32_t cap_v, MoCsr c) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i <= cap_v) c.deg[i] = 0u;
+}
+
+template <bool NBR>
+__global__ __launch_bounds__(256) void mesh_csr_count_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ counts,
+                                                             uint32_t cap_v, uint32_t cap_f, MoCsr c) {
+    const uint32_t f = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t V = mo_count(counts, 0, cap_v), F = mo_count(counts, 1, cap_f);
+    if (f >= F) return;
+    int32_t a, b, d;
+    if (!mo_face(faces, f, V, a, b, d)) return;
+    const uint32_t e = NBR ? 2u : 1u;
+    atomicAdd(&c.deg[a], e), atomicAdd(&c.deg[b], e), atomicAdd(&c.deg[d], e);
+}
+
+__global__ __launch_bounds__(256) void mesh_csr_scan_kernel(const int32_t* __restrict__ counts, uint32_t cap_v, MoCsr c) {
+    __shared__ uint32_t s_wave[4];
+    __shared__ int s_last;
+    const uint32_t V = mo_count(counts, 0, cap_v);
+    uint32_t run = 0u;
+    for (uint32_t chunk = 0; chunk < (uint32_t)MO_CHUNKS; chunk++) {
+        const uint32_t i = (blockIdx.x * (uint32_t)MO_CHUNKS + chunk) * 256u + threadIdx.x;
+        const uint32_t n = i < V ? c.deg[i] : 0u;
+        uint32_t total;
+        const uint32_t before = dqo_block_exclusive<uint32_t>(n, total, s_wave);
+        if (i <= V) c.off[i] = run + before;  // (V itself: the end of the last segment)
+        run += total;
+    }
+    if (threadIdx.x == 0) __hip_atomic_store(&c.span[blockIdx.x], run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!dqo_last_block(c.head, &s_last)) return;
+    dqo_scan_block_counts<uint32_t, 4>(c.span, gridDim.x, 1, s_wave);  // (<= 6 cap_f < 2^32)
+}
+
+template <bool NBR>
+__global__ __launch_bounds__(256) void mesh_csr_fill_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ counts,
+                                                            uint32_t cap_v, uint32_t cap_f, MoCsr c) {
+    const uint32_t f = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t V = mo_count(counts, 0, cap_v), F = mo_count(counts, 1, cap_f);
+    if (f >= F) return;
+    int32_t idx[3];
+    if (!mo_face(faces, f, V, idx[0], idx[1], idx[2])) return;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const uint32_t v = (uint32_t)idx[k], e = NBR ? 2u : 1u;
+        const size_t at = mo_start(c, v) + (size_t)(atomicSub(&c.deg[v], e) - e);  // (the count launch added e for this corner)
+        if (NBR) c.adj[at] = idx[(k + 1) % 3], c.adj[at + 1] = idx[(k + 2) % 3];
+        else c.adj[at] = (int32_t)f;
+    }
+}
+
+// a[0 .. n) ascending, by the block: the bitonic network whose merges compare i with its mirror image first, so that every comparator
+// puts the smaller value at the lower index — entries behind n then act as +infinity without being there, and any n sorts
+__device__ __forceinline__ void mo_block_sort(int32_t* a, uint32_t n) {
+    u64 npow = 1ull;
+    while (npow < (u64)n) npow <<= 1;
+    for (u64 k = 2ull; k <= npow; k <<= 1) {
+        const u64 half = k >> 1;
+        for (u64 t = threadIdx.x; t < (npow >> 1); t += 256ull) {
+            const u64 lo = ((t & ~(half - 1ull)) << 1) + (t & (half - 1ull)), hi = ((t & ~(half - 1ull)) << 1) + (k - 1ull) - (t & (half - 1ull));
+            if (hi < (u64)n) {
+                const int32_t x = a[lo], y = a[hi];
+                if (x > y) a[lo] = y, a[hi] = x;
+            }
+        }
+        __syncthreads();
+        for (u64 s = k >> 2; s >= 1ull; s >>= 1) {
+            for (u64 t = threadIdx.x; t < (npow >> 1); t += 256ull) {
+                const u64 lo = ((t & ~(s - 1ull)) << 1) + (t & (s - 1ull)), hi = lo + s;
+                if (hi < (u64)n) {
+                    const int32_t x = a[lo], y = a[hi];
+                    if (x > y) a[lo] = y, a[hi] = x;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+template <bool NBR>
+__global__ __launch_bounds__(256) void mesh_csr_tidy_kernel(const int32_t* __restrict__ counts, uint32_t cap_v, MoCsr c) {
+    __shared__ int32_t s_sort[MO_LDS_MAX];
+    __shared__ uint32_t s_queue[256];
+    __shared__ uint32_t s_nq;
+    __shared__ uint32_t s_wave[4];
+    const uint32_t V = mo_count(counts, 0, cap_v);
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (threadIdx.x == 0) s_nq = 0u;
+    __syncthreads();
+    if (v < V) {
+        const size_t start = mo_start(c, v);
+        const uint32_t n = (uint32_t)(mo_start(c, v + 1u) - start);
+        if (n <= (uint32_t)MO_THREAD_MAX) {
+            int32_t* a = c.adj + start;
+            for (uint32_t i = 1; i < n; i++) {
+                const int32_t x = a[i];
+                uint32_t j = i;
+                for (; j > 0u && a[j - 1u] > x; j--) a[j] = a[j - 1u];
+                a[j] = x;
+            }
+            uint32_t m = n;
+            if (NBR) {
+                m = 0u;
+                for (uint32_t i = 0; i < n; i++) {
+                    const int32_t x = a[i];
+                    if (x != (int32_t)v && (m == 0u || a[m - 1u] != x)) a[m++] = x;
+                }
+            }
+            c.deg[v] = m;
+        } else s_queue[atomicAdd(&s_nq, 1u)] = v;
+    }
+    __syncthreads();
+    const uint32_t nq = s_nq;
+    for (uint32_t q = 0; q < nq; q++) {  // the block's long segments, one after the other, by the whole block
+        const uint32_t u = s_queue[q];
+        const size_t start = mo_start(c, u);
+        const uint32_t n = (uint32_t)(mo_start(c, u + 1u) - start);
+        int32_t* a = c.adj + start;
+        if (n <= (uint32_t)MO_LDS_MAX) {
+            for (uint32_t j = threadIdx.x; j < n; j += 256u) s_sort[j] = a[j];
+            __syncthreads();
+            mo_block_sort(s_sort, n);
+            for (uint32_t j = threadIdx.x; j < n; j += 256u) a[j] = s_sort[j];
+        } else mo_block_sort(a, n);
+        __syncthreads();
+        uint32_t m = n;
+        if (NBR) {
+            // in place: an entry moves to an index that is not above its own, a run of 256 is read before it is written, and the one entry
+            // a run reads from the run before it (its last) can only have been overwritten by itself
+            m = 0u;
+            for (uint32_t base = 0; base < n; base += 256u) {
+                const uint32_t j = base + threadIdx.x;
+                int32_t x = 0;
+                uint32_t keep = 0u;
+                if (j < n) {
+                    x = a[j];
+                    keep = (x != (int32_t)u && (j == 0u || a[j - 1u] != x)) ? 1u : 0u;
+                }
+                uint32_t total;
+                const uint32_t before = dqo_block_exclusive<uint32_t>(keep, total, s_wave);  // (its barriers: the reads are done)
+                if (keep) a[m + before] = x;
+                m += total;
+                __syncthreads();
+            }
+        }
+        if (threadIdx.x == 0) c.deg[u] = m;
+        __syncthreads();  // (s_sort is free again)
+    }
+}
+
+// ---- smoothing --------------------------------------------------------------------------------------------------------------------------
+// One step with factor lam for every vertex (include/dqo_raster.h states the rule): in double from the float32 values of `src`, sums
+// left to right over the ascending neighbours.  POS / COL: which of the two arrays the step moves; the weights always come from p_src.
+template <bool POS, bool COL>
+__global__ __launch_bounds__(256) void mesh_smooth_step_kernel(const int32_t* __restrict__ counts, uint32_t cap_v, MoCsr c,
+                                                               const float* __restrict__ p_src, float* __restrict__ p_dst,
+                                                               const float* __restrict__ c_src, float* __restrict__ c_dst, double lam) {
+#pragma clang fp contract(off)
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= mo_count(counts, 0, cap_v)) return;
+    const uint32_t n = c.deg[i];
+    const float pf[3] = {p_src[3 * (size_t)i], p_src[3 * (size_t)i + 1], p_src[3 * (size_t)i + 2]};
+    float cf[3] = {0.f, 0.f, 0.f};
+    if (COL) cf[0] = c_src[3 * (size_t)i], cf[1] = c_src[3 * (size_t)i + 1], cf[2] = c_src[3 * (size_t)i + 2];
+    if (n == 0u) {  // no neighbours: copied unchanged
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            if (POS) p_dst[3 * (size_t)i + k] = pf[k];
+            if (COL) c_dst[3 * (size_t)i + k] = cf[k];
+        }
+        return;
+    }
+    const double px = (double)pf[0], py = (double)pf[1], pz = (double)pf[2];
+    const int32_t* a = c.adj + mo_start(c, i);
+    double Sx = 0.0, Sy = 0.0, Sz = 0.0, Cx = 0.0, Cy = 0.0, Cz = 0.0, T = 0.0;
+    for (uint32_t k = 0; k < n; k++) {
+        const size_t nb = (size_t)a[k];
+        const double qx = (double)p_src[3 * nb], qy = (double)p_src[3 * nb + 1], qz = (double)p_src[3 * nb + 2];
+        const double dx = px - qx, dy = py - qy, dz = pz - qz;
+        const double dist = sqrt((dx * dx + dy * dy) + dz * dz);
+        const double w = 1.0 / (dist + 1e-12);
+        if (POS) Sx = Sx + w * qx, Sy = Sy + w * qy, Sz = Sz + w * qz;
+        if (COL) Cx = Cx + w * (double)c_src[3 * nb], Cy = Cy + w * (double)c_src[3 * nb + 1], Cz = Cz + w * (double)c_src[3 * nb + 2];
+        T = T + w;
+    }
+    if (POS) {
+        p_dst[3 * (size_t)i] = (float)(px + lam * (Sx / T - px));
+        p_dst[3 * (size_t)i + 1] = (float)(py + lam * (Sy / T - py));
+        p_dst[3 * (size_t)i + 2] = (float)(pz + lam * (Sz / T - pz));
+    }
+    if (COL) {
+        const double cx = (double)cf[0], cy = (double)cf[1], cz = (double)cf[2];
+        c_dst[3 * (size_t)i] = (float)(cx + lam * (Cx / T - cx));
+        c_dst[3 * (size_t)i + 1] = (float)(cy + lam * (Cy / T - cy));
+        c_dst[3 * (size_t)i + 2] = (float)(cz + lam * (Cz / T - cz));
+    }
+}
+
+// after an odd number of steps: the workspace's half back into the mesh (a or b may be NULL)
+__global__ __launch_bounds__(256) void mesh_smooth_copy_kernel(const int32_t* __restrict__ counts, uint32_t cap_v, const float* __restrict__ a_src,
+                                                               float* __restrict__ a_dst, const float* __restrict__ b_src,
+                                                               float* __restrict__ b_dst) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= mo_count(counts, 0, cap_v)) return;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        if (a_src != nullptr) a_dst[3 * (size_t)i + k] = a_src[3 * (size_t)i + k];
+        if (b_src != nullptr) b_dst[3 * (size_t)i + k] = b_src[3 * (size_t)i + k];
+    }
+}
+
+// ---- normals ----------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void mesh_normals_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ faces,
+                                                           const int32_t* __restrict__ counts, uint32_t cap_v, MoCsr c,
+                                                           float* __restrict__ normals) {
+#pragma clang fp contract(off)
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= mo_count(counts, 0, cap_v)) return;
+    const uint32_t n = c.deg[i];
+    const int32_t* a = c.adj + mo_start(c, i);
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (uint32_t k = 0; k < n; k++) {  // ascending face index; a face that names the vertex twice is there twice
+        const size_t f = (size_t)a[k];
+        const size_t i0 = (size_t)faces[3 * f], i1 = (size_t)faces[3 * f + 1], i2 = (size_t)faces[3 * f + 2];
+        const double p0x = (double)vertices[3 * i0], p0y = (double)vertices[3 * i0 + 1], p0z = (double)vertices[3 * i0 + 2];
+        const double ux = (double)vertices[3 * i1] - p0x, uy = (double)vertices[3 * i1 + 1] - p0y, uz = (double)vertices[3 * i1 + 2] - p0z;
+        const double vx = (double)vertices[3 * i2] - p0x, vy = (double)vertices[3 * i2 + 1] - p0y, vz = (double)vertices[3 * i2 + 2] - p0z;
+        sx = sx + (uy * vz - uz * vy), sy = sy + (uz * vx - ux * vz), sz = sz + (ux * vy - uy * vx);
+    }
+    const double len = sqrt((sx * sx + sy * sy) + sz * sz);
+    float nx = 0.f, ny = 0.f, nz = 1.f;
+    if (len > 0.0 && len <= 1.7976931348623157e308) nx = (float)(sx / len), ny = (float)(sy / len), nz = (float)(sz / len);
+    normals[3 * (size_t)i] = nx, normals[3 * (size_t)i + 1] = ny, normals[3 * (size_t)i + 2] = nz;
+}
+
+inline bool mo_caps_ok(int64_t cap_v, int64_t cap_f) { return cap_v >= 1 && cap_f >= 1 && cap_v < MO_MAX && cap_f < MO_MAX; }
+
+inline size_t mo_comp_ws_bytes(size_t cv, size_t cf) {
+    return DQO_REDUCE_HEAD_WORDS * 4 + 3 * dqo_align_up(cv * 4, 256) + dqo_align_up(cf * 4, 256) + dqo_align_up(cf, 256) +
+           2 * dqo_align_up(mo_spans(cv) * sizeof(u64), 256) + dqo_align_up(mo_spans(cf) * 4, 256);
+}
+
+inline size_t mo_csr_bytes(size_t cv, size_t cf, size_t per_face) {
+    return DQO_REDUCE_HEAD_WORDS * 4 + 2 * dqo_align_up((cv + 1) * 4, 256) + dqo_align_up(mo_spans(cv + 1) * 4, 256) +
+           dqo_align_up(per_face * cf * 4, 256);
+}
+
+inline char* mo_csr_layout(MoCsr& c, void* ws, size_t cv, size_t cf, size_t per_face) {
+    char* p = (char*)ws;
+    c.head = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
+    c.deg = (uint32_t*)p, p += dqo_align_up((cv + 1) * 4, 256);
+    c.off = (uint32_t*)p, p += dqo_align_up((cv + 1) * 4, 256);
+    c.span = (uint32_t*)p, p += dqo_align_up(mo_spans(cv + 1) * 4, 256);
+    c.adj = (int32_t*)p, p += dqo_align_up(per_face * cf * 4, 256);
+    return p;
+}
+
+// the five launches of the CSR build
+template <bool NBR>
+int mo_build_csr(const int32_t* faces, const int32_t* counts, uint32_t cv, uint32_t cf, const MoCsr& c, hipStream_t s) {
+    const dim3 block(256), gv((unsigned)mo_blocks((size_t)cv + 1)), gf((unsigned)mo_blocks(cf));
+    DQO_LAUNCH("mesh_csr_zero_kernel", mesh_csr_zero_kernel, gv, block, s, cv, c);
+    DQO_LAUNCH("mesh_csr_count_kernel", mesh_csr_count_kernel<NBR>, gf, block, s, faces, counts, cv, cf, c);
+    DQO_LAUNCH("mesh_csr_scan_kernel", mesh_csr_scan_kernel, dim3((unsigned)mo_spans((size_t)cv + 1)), block, s, counts, cv, c);
+    DQO_LAUNCH("mesh_csr_fill_kernel", mesh_csr_fill_kernel<NBR>, gf, block, s, faces, counts, cv, cf, c);
+    DQO_LAUNCH("mesh_csr_tidy_kernel", mesh_csr_tidy_kernel<NBR>, dim3((unsigned)mo_blocks(cv)), block, s, counts, cv, c);
+    return DQO_OK;
+}
+
+}  // namespace
+
+#define DQO_MESH_CHECK_CAPS(cv, cf) \
+    DQO_CHECK_ARG(mo_caps_ok(cv, cf), "bad capacity: %d vertices, %d faces: both are at least 1 and below 2^28", cv, cf)
+
+// ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
+extern "C" {
+
+DQO_API size_t dqo_mesh_components_workspace_bytes(int32_t cap_vertices, int32_t cap_faces) {
+    return mo_caps_ok(cap_vertices, cap_faces) ? mo_comp_ws_bytes((size_t)cap_vertices, (size_t)cap_faces) : 0;
+}
+
+DQO_API size_t dqo_mesh_smooth_workspace_bytes(int32_t cap_vertices, int32_t cap_faces) {
+    return mo_caps_ok(cap_vertices, cap_faces)
+               ? mo_csr_bytes((size_t)cap_vertices, (size_t)cap_faces, 6) + 2 * dqo_align_up((size_t)cap_vertices * 12, 256) : 0;
+}
+
+DQO_API size_t dqo_mesh_normals_workspace_bytes(int32_t cap_vertices, int32_t cap_faces) {
+    return mo_caps_ok(cap_vertices, cap_faces) ? mo_csr_bytes((size_t)cap_vertices, (size_t)cap_faces, 3) : 0;
+}
+
+DQO_API int dqo_mesh_components(const float* vertices, const float* colors, const int32_t* faces, const int32_t* counts, int32_t cap_vertices,
+                                int32_t cap_faces, int32_t min_faces, int32_t largest_only, float* out_vertices, float* out_colors,
+                                int32_t* out_faces, int32_t out_cap_vertices, int32_t out_cap_faces, int32_t* labels, int32_t* header,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    DQO_MESH_CHECK_CAPS(cap_vertices, cap_faces);
+    DQO_CHECK_ARG(vertices && faces && header, "null mesh buffer / header");
+    DQO_CHECK_ARG(min_faces >= 0, "bad min_faces %d: it is at least 0", min_faces);
+    DQO_CHECK_ARG(out_cap_vertices >= cap_vertices && out_cap_faces >= cap_faces,
+                  "out capacity (%d vertices, %d faces) below the input's (%d, %d)", out_cap_vertices, out_cap_faces, cap_vertices, cap_faces);
+    DQO_CHECK_ARG(out_vertices && out_faces && (colors == nullptr || out_colors), "null out mesh buffer");
+    DQO_CHECK_ARG(out_vertices != vertices && out_faces != faces && (colors == nullptr || out_colors != colors),
+                  "the out mesh must not be the input mesh");
+    DQO_CHECK_ARG(header != counts, "header must not be the input's counts: the first launch clears it before the counts are read");
+    const size_t cv = (size_t)cap_vertices, cf = (size_t)cap_faces;
+    DQO_CHECK_WS("mesh components", workspace, workspace_bytes, mo_comp_ws_bytes(cv, cf));
+    MoComp w;
+    char* p = (char*)workspace;
+    w.head = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
+    w.parent = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
+    w.size = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
+    w.mark = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
+    w.label = labels != nullptr ? labels : (int32_t*)p, p += dqo_align_up(cf * 4, 256);
+    w.keep = (uint8_t*)p, p += dqo_align_up(cf, 256);
+    w.spair = (u64*)p, p += dqo_align_up(mo_spans(cv) * sizeof(u64), 256);
+    w.vpair = (u64*)p, p += dqo_align_up(mo_spans(cv) * sizeof(u64), 256);
+    w.fblock = (uint32_t*)p;
+    const uint32_t ucv = (uint32_t)cap_vertices, ucf = (uint32_t)cap_faces;
+    const dim3 block(256), gv((unsigned)mo_blocks(cv)), gf((unsigned)mo_blocks(cf)), sv((unsigned)mo_spans(cv)), sf((unsigned)mo_spans(cf));
+    hipStream_t s = (hipStream_t)stream;
+    DQO_LAUNCH("mesh_comp_init_kernel", mesh_comp_init_kernel, gv, block, s, counts, ucv, w, header);
+    DQO_LAUNCH("mesh_comp_prelink_kernel", mesh_comp_prelink_kernel, gf, block, s, faces, counts, ucv, ucf, w);
+    DQO_LAUNCH("mesh_comp_flatten_kernel", mesh_comp_flatten_kernel<false>, gv, block, s, counts, ucv, w);
+    DQO_LAUNCH("mesh_comp_hook_kernel", mesh_comp_hook_kernel, gf, block, s, faces, counts, ucv, ucf, w, header);
+    DQO_LAUNCH("mesh_comp_flatten_kernel", mesh_comp_flatten_kernel<true>, gv, block, s, counts, ucv, w);
+    DQO_LAUNCH("mesh_comp_label_kernel", mesh_comp_label_kernel, sf, block, s, faces, counts, ucv, ucf, w);
+    DQO_LAUNCH("mesh_comp_stats_kernel", mesh_comp_stats_kernel, sv, block, s, counts, ucv, w, header);
+    DQO_LAUNCH("mesh_comp_fcount_kernel", mesh_comp_fcount_kernel, sf, block, s, faces, counts, ucf, w, min_faces, largest_only, header);
+    DQO_LAUNCH("mesh_comp_vcount_kernel", mesh_comp_vcount_kernel, sv, block, s, counts, ucv, w, min_faces, largest_only, header);
+    DQO_LAUNCH("mesh_comp_vscatter_kernel", mesh_comp_vscatter_kernel, sv, block, s, vertices, colors, counts, ucv, w, out_vertices, out_colors);
+    DQO_LAUNCH("mesh_comp_fscatter_kernel", mesh_comp_fscatter_kernel, sf, block, s, faces, counts, ucf, w, out_faces);
+    return DQO_OK;
+}
+
+DQO_API int dqo_mesh_smooth(float* vertices, float* colors, const int32_t* faces, const int32_t* counts, int32_t cap_vertices, int32_t cap_faces,
+                            int32_t iterations, double lambda, double mu, int32_t scope, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+    DQO_MESH_CHECK_CAPS(cap_vertices, cap_faces);
+    DQO_CHECK_ARG(vertices && faces, "null mesh buffer");
+    DQO_CHECK_ARG(iterations >= 0, "bad iterations %d: at least 0", iterations);
+    DQO_CHECK_ARG(lambda == lambda && mu == mu && lambda - lambda == 0.0 && mu - mu == 0.0, "bad lambda / mu: both are finite");
+    DQO_CHECK_ARG(scope >= DQO_MESH_SMOOTH_POSITIONS && scope <= DQO_MESH_SMOOTH_BOTH, "bad scope %d: 0 positions, 1 colours, 2 both", scope);
+    DQO_CHECK_ARG(scope == DQO_MESH_SMOOTH_POSITIONS || colors, "null colors with a scope that smooths them");
+    const size_t cv = (size_t)cap_vertices, cf = (size_t)cap_faces;
+    DQO_CHECK_WS("mesh smooth", workspace, workspace_bytes, mo_csr_bytes(cv, cf, 6) + 2 * dqo_align_up(cv * 12, 256));
+    if (iterations == 0) return DQO_OK;
+    MoCsr c;
+    char* p = mo_csr_layout(c, workspace, cv, cf, 6);
+    float* const other_p = (float*)p;
+    float* const other_c = (float*)(p + dqo_align_up(cv * 12, 256));
+    const uint32_t ucv = (uint32_t)cap_vertices, ucf = (uint32_t)cap_faces;
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = mo_build_csr<true>(faces, counts, ucv, ucf, c, s);
+    if (rc != DQO_OK) return rc;
+    const bool pos = scope != DQO_MESH_SMOOTH_COLOURS, col = scope != DQO_MESH_SMOOTH_POSITIONS;
+    const dim3 block(256), gv((unsigned)mo_blocks(cv));
+    const int steps = mu != 0.0 ? 2 * iterations : iterations;
+    float *p_cur = vertices, *p_nxt = other_p, *c_cur = colors, *c_nxt = other_c;
+    const auto step = pos && col ? mesh_smooth_step_kernel<true, true> : pos ? mesh_smooth_step_kernel<true, false> : mesh_smooth_step_kernel<false, true>;
+    for (int k = 0; k < steps; k++) {
+        const double lam = (mu != 0.0 && (k & 1)) ? mu : lambda;
+        // (a scope's other array is read at most: positions give the weights of a colour step)
+        DQO_LAUNCH("mesh_smooth_step_kernel", step, gv, block, s, counts, ucv, c, (const float*)p_cur, p_nxt, (const float*)c_cur, c_nxt, lam);
+        if (pos) {
+            float* t = p_cur;
+            p_cur = p_nxt, p_nxt = t;
+        }
+        if (col) {
+            float* t = c_cur;
+            c_cur = c_nxt, c_nxt = t;
+        }
+    }
+    if (steps & 1) {
+        DQO_LAUNCH("mesh_smooth_copy_kernel", mesh_smooth_copy_kernel, gv, block, s, counts, ucv, pos ? other_p : nullptr, vertices,
+                   col ? other_c : nullptr, colors);
+    }
+    return DQO_OK;
+}
+
+DQO_API int dqo_mesh_normals(const float* vertices, const int32_t* faces, const int32_t* counts, int32_t cap_vertices, int32_t cap_faces,
+                             float* normals, void* workspace, size_t workspace_bytes, void* stream) {
+    DQO_MESH_CHECK_CAPS(cap_vertices, cap_faces);
+    DQO_CHECK_ARG(vertices && faces && normals, "null mesh buffer / normals");
+    const size_t cv = (size_t)cap_vertices, cf = (size_t)cap_faces;
+    DQO_CHECK_WS("mesh normals", workspace, workspace_bytes, mo_csr_bytes(cv, cf, 3));
+    MoCsr c;
+    mo_csr_layout(c, workspace, cv, cf, 3);
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = mo_build_csr<false>(faces, counts, (uint32_t)cap_vertices, (uint32_t)cap_faces, c, s);
+    if (rc != DQO_OK) return rc;
+    DQO_LAUNCH("mesh_normals_kernel", mesh_normals_kernel, dim3((unsigned)mo_blocks(cv)), dim3(256), s, vertices, faces, counts,
+               (uint32_t)cap_vertices, c, normals);
+    return DQO_OK;
+}
+
+}  // extern "C"

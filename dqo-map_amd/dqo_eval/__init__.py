@@ -86,8 +86,18 @@ own (csrc/map_tsdf.hip: a dense grid, the integration rule restated in include/d
     TsdfVolume(origin, voxel_length, dims, sdf_trunc, device)   tsdf, weight, color: public device tensors
         .clear()  .integrate(depth, color, K, w2c, depth_trunc, render_header)  .extract(cap_vertices, cap_faces)  .counts()
 
-FusedMapper.make_mesh(frames, volume) renders and integrates a camera list; dqo_ply.write_mesh_ply writes the mesh.  Laplacian smoothing
-(the reference's mesh_smooth_* keys are read by nothing in its tree), sparse volumes and mesh simplification are not built.
+FusedMapper.make_mesh(frames, volume) renders and integrates a camera list; dqo_ply.write_mesh_ply writes the mesh.  Sparse volumes and
+mesh simplification are not built.
+
+The mesh's clean-up (csrc/map_meshops.hip; the rules in include/dqo_raster.h follow open3d's published algorithms, tests/mesh_ops_oracle.py
+restates them), on the mesh dict extract() returns, nothing read back:
+
+    mesh_components(mesh, min_faces, largest_only, ...)   cluster_connected_triangles + remove_triangles_by_mask + remove_unreferenced_vertices
+    mesh_smooth(mesh, iterations, lam, mu, scope)         filter_smooth_laplacian / filter_smooth_taubin (configs' mesh_smooth_iter, mesh_smooth_lambda)
+    mesh_normals(mesh)                                    compute_vertex_normals
+    mesh_counts(mesh)                                     the one host read
+
+FusedMapper.make_clean_mesh chains them behind make_mesh; dqo_ply.write_mesh_ply_normals writes the result.
 
 GPU only: there is no CPU path.
 """
@@ -787,3 +797,136 @@ class TsdfVolume:
         since clear() — the ONE host read."""
         h = self.header.cpu().tolist()
         return {n: int(x) for n, x in zip(TSDF_HEADER, h) if not n.startswith("unused")}
+
+
+# ---- the mesh's clean-up (csrc/map_meshops.hip) ------------------------------------------------------------------------------------------
+MESHOPS_HEADER = ("vertices", "faces", "components", "components_kept", "faces_bad_index", "largest_component_faces", "vertices_removed",
+                  "faces_removed")
+_MESH_SCOPES = {"positions": 0, "colors": 1, "colours": 1, "all": 2, "both": 2}
+_mesh_outs = {}  # the module's own out meshes and normals, one per (device, capacities)
+
+
+def _mesh(mesh, who):
+    """(vertices, colors or None, faces, counts or None, cap_v, cap_f) of a mesh dict, checked."""
+    v, f, c, h = mesh["vertices"], mesh["faces"], mesh.get("colors"), mesh.get("header")
+    N.require_gpu_op((v, f), c, h)
+    cv, cf = int(v.shape[0]), int(f.shape[0])
+    if tuple(v.shape) != (cv, 3) or v.dtype != torch.float32 or not v.is_contiguous():
+        raise RuntimeError(f"dqo_eval.{who}: mesh['vertices'] must be a contiguous float32 [V,3] tensor")
+    if tuple(f.shape) != (cf, 3) or f.dtype != torch.int32 or not f.is_contiguous() or f.device != v.device:
+        raise RuntimeError(f"dqo_eval.{who}: mesh['faces'] must be a contiguous int32 [F,3] tensor on the vertices' device")
+    if c is not None and (tuple(c.shape) != (cv, 3) or c.dtype != torch.float32 or not c.is_contiguous() or c.device != v.device):
+        raise RuntimeError(f"dqo_eval.{who}: mesh['colors'] must be a contiguous float32 [{cv},3] tensor on the vertices' device")
+    if h is not None and (h.dtype != torch.int32 or h.numel() < 2 or not h.is_contiguous() or h.device != v.device):
+        raise RuntimeError(f"dqo_eval.{who}: mesh['header'] must be a contiguous int32 tensor of at least two words (vertices, faces) on the vertices' device")
+    if not (1 <= cv < (1 << 28) and 1 <= cf < (1 << 28)):
+        raise RuntimeError(f"dqo_eval.{who}: bad capacity: {cv} vertices, {cf} faces: both are at least 1 and below 2^28")
+    return v, c, f, h, cv, cf
+
+
+def _mesh_ws(kind, workspace_buffer, dev, cv, cf):
+    need = getattr(N.lib(), f"dqo_mesh_{kind}_workspace_bytes")(cv, cf)
+    if workspace_buffer is None:
+        return _workspace(("mesh_" + kind, _dev_index(dev), cv, cf), need, dev)
+    N.require_gpu_op(workspace_buffer)
+    return workspace_buffer
+
+
+def mesh_components(mesh, min_faces=0, largest_only=False, out=None, want_labels=False, workspace_buffer=None):
+    """Connected components of a mesh and the mesh without its small ones — open3d's cluster_connected_triangles +
+    remove_triangles_by_mask + remove_unreferenced_vertices (include/dqo_raster.h, dqo_mesh_components, states the rule: faces are
+    connected through shared vertex indices, a component's label is its smallest vertex id, a face is kept iff its component has at
+    least max(min_faces, largest_only ? the largest component's size : 0) faces).  mesh: the dict TsdfVolume.extract returns (vertices,
+    faces, optionally colors, and header, whose words 0 and 1 are the counts; without a header the capacities are the counts).
+    Returns a mesh dict of the same shape in OTHER buffers (`out`, whose capacities must not be below the input's; default: this module's
+    own for the capacities, overwritten by the next call) whose header is the int32 [8] MESHOPS_HEADER; with want_labels also
+    "labels", int32 [cap_faces] (-1: a face with a bad index).  The returned dict also carries "header_names" = MESHOPS_HEADER, a tuple,
+    not a tensor: the mesh-dict contract's one host-side key, by which mesh_counts names the header's words; a dict without it has
+    TsdfVolume.extract's header (so do not hand a dict this function filled to extract(out=...) without dropping that key).  out's
+    header must not be the input mesh's: the first launch clears it.  Eleven launches, nothing read back; mesh_counts reads a header."""
+    v, c, f, h, cv, cf = _mesh(mesh, "mesh_components")
+    dev = v.device
+    if out is None:
+        key = (_dev_index(dev), cv, cf, c is not None)
+        out = _mesh_outs.get(key)
+        if out is None:
+            out = _mesh_outs[key] = dict(vertices=torch.empty((cv, 3), dtype=torch.float32, device=dev),
+                                         faces=torch.empty((cf, 3), dtype=torch.int32, device=dev),
+                                         header=torch.empty((8,), dtype=torch.int32, device=dev))
+            if c is not None:
+                out["colors"] = torch.empty((cv, 3), dtype=torch.float32, device=dev)
+        if not want_labels:
+            out.pop("labels", None)  # (an earlier call's)
+    if "header" not in out:
+        out["header"] = torch.empty((8,), dtype=torch.int32, device=dev)
+    if want_labels and "labels" not in out:
+        out["labels"] = torch.empty((cf,), dtype=torch.int32, device=dev)
+    if c is not None and "colors" not in out:
+        raise RuntimeError("dqo_eval.mesh_components: the mesh has colors, out has none")
+    ov, oc, of, oh, ocv, ocf = _mesh(out, "mesh_components")
+    labels = out["labels"] if want_labels else None
+    if oh.numel() != 8 or (labels is not None and (labels.dtype != torch.int32 or labels.numel() < cf or not labels.is_contiguous() or not labels.is_cuda)):
+        raise RuntimeError("dqo_eval.mesh_components: out['header'] is int32 [8], out['labels'] a contiguous int32 [cap_faces] device tensor")
+    ws = _mesh_ws("components", workspace_buffer, dev, cv, cf)
+    with torch.cuda.device(dev):
+        N.check(N.lib().dqo_mesh_components(v.data_ptr(), N.ptr(c), f.data_ptr(), N.ptr(h), cv, cf, int(min_faces), 1 if largest_only else 0,
+                                            ov.data_ptr(), N.ptr(oc) if c is not None else None, of.data_ptr(), ocv, ocf, N.ptr(labels),
+                                            oh.data_ptr(), ws.data_ptr(), ws.numel(), N.current_stream()))
+    out["header_names"] = MESHOPS_HEADER  # (what mesh_counts calls the words)
+    return out
+
+
+def mesh_smooth(mesh, iterations, lam=0.5, mu=None, scope="all", workspace_buffer=None):
+    """Laplacian smoothing in place — open3d's filter_smooth_laplacian(iterations, lam), the reference configs' mesh_smooth_iter and
+    mesh_smooth_lambda (configs/Cube_Diorama_base.yaml:45-46) — and, with mu (open3d's default -0.53 beside lam 0.5),
+    filter_smooth_taubin: every iteration a step with lam, then one with mu.  include/dqo_raster.h (dqo_mesh_smooth) states the step:
+    inverse-distance weights over the vertices that share a face, in double, rounded to float32 between steps.  scope: "positions",
+    "colors" (the positions give the weights and stay) or "all" (both; positions only when the mesh has no colors).  Returns `mesh`.
+    Five launches for the adjacency, one per step, nothing read back."""
+    v, c, f, h, cv, cf = _mesh(mesh, "mesh_smooth")
+    if scope not in _MESH_SCOPES:
+        raise RuntimeError(f"dqo_eval.mesh_smooth: scope is 'positions', 'colors' or 'all', got {scope!r}")
+    sc = _MESH_SCOPES[scope]
+    if sc == 2 and c is None:
+        sc = 0
+    if sc == 1 and c is None:
+        raise RuntimeError("dqo_eval.mesh_smooth: scope 'colors' on a mesh without colors")
+    ws = _mesh_ws("smooth", workspace_buffer, v.device, cv, cf)
+    with torch.cuda.device(v.device):
+        N.check(N.lib().dqo_mesh_smooth(v.data_ptr(), N.ptr(c), f.data_ptr(), N.ptr(h), cv, cf, int(iterations), float(lam),
+                                        0.0 if mu is None else float(mu), sc, ws.data_ptr(), ws.numel(), N.current_stream()))
+    return mesh
+
+
+def mesh_normals(mesh, out=None, workspace_buffer=None):
+    """Area-weighted vertex normals — open3d's compute_vertex_normals (include/dqo_raster.h, dqo_mesh_normals): the sum of the incident
+    faces' un-normalised normals in ascending face index, in double, normalised, (0, 0, 1) where the sum has no direction.  Adds
+    mesh["normals"], float32 [cap_vertices,3] (`out`, or this module's own for the capacities, overwritten by the next call), and
+    returns `mesh`.  Six launches, nothing read back."""
+    v, c, f, h, cv, cf = _mesh(mesh, "mesh_normals")
+    dev = v.device
+    if out is None:
+        key = ("normals", _dev_index(dev), cv, cf)
+        out = _mesh_outs.get(key)
+        if out is None:
+            out = _mesh_outs[key] = torch.empty((cv, 3), dtype=torch.float32, device=dev)
+    N.require_gpu_op(out)
+    if tuple(out.shape) != (cv, 3) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError(f"dqo_eval.mesh_normals: out must be a contiguous float32 [{cv},3] tensor on the mesh's device")
+    ws = _mesh_ws("normals", workspace_buffer, dev, cv, cf)
+    with torch.cuda.device(dev):
+        N.check(N.lib().dqo_mesh_normals(v.data_ptr(), f.data_ptr(), N.ptr(h), cv, cf, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                         N.current_stream()))
+    mesh["normals"] = out
+    return mesh
+
+
+def mesh_counts(mesh):
+    """{name: int} of a mesh dict's header, or the capacities of a mesh without one: the ONE host read.  The words are named by the
+    dict's "header_names" (mesh_components puts MESHOPS_HEADER there); a dict without that key has TsdfVolume.extract's header, whose
+    first four words are TSDF_HEADER's."""
+    h = mesh.get("header")
+    if h is None:
+        return dict(vertices=int(mesh["vertices"].shape[0]), faces=int(mesh["faces"].shape[0]))
+    names = mesh.get("header_names", TSDF_HEADER[:4])
+    return {n: int(x) for n, x in zip(names, h.cpu().tolist())}

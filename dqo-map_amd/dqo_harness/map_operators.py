@@ -329,9 +329,10 @@ class MapOperators:
         The reference swaps its eval opaque threshold into the renderer for this walk (make_mesh.py:156); here the caller chooses it:
         pass settings whose opaque_threshold is the one it wants.  The FIRST call for a (P, H, W) sizes the render's context from one
         32-byte header read, exactly as maintain() does; after that a call reads nothing back, allocates nothing and does not
-        synchronise.  Returns `volume`; volume.extract(cap_vertices, cap_faces) is the mesh, dqo_ply.write_mesh_ply its file.
-        Not built: Laplacian smoothing (the mesh_smooth_* keys of the reference's configs are read by nothing in its tree), mesh
-        simplification; NotImplementedError on a sharded mapper (a shard's render shows its objects only, volumes are not merged)."""
+        synchronise.  Returns `volume`; volume.extract(cap_vertices, cap_faces) is the mesh, dqo_ply.write_mesh_ply its file;
+        make_clean_mesh goes on to the cleaned, smoothed mesh with normals.
+        Not built: mesh simplification; NotImplementedError on a sharded mapper (a shard's render shows its objects only, volumes are
+        not merged)."""
         self._refuse_sharded("make_mesh")
         H, W = int(self.settings.image_height), int(self.settings.image_width)
         if self._mesh_w2c is None:
@@ -345,6 +346,29 @@ class MapOperators:
                 K = (W / (2.0 * float(st.tanfovx)), H / (2.0 * float(st.tanfovy)), float(st.cx), float(st.cy))
                 volume.integrate(c.out[1], c.out[0], K, self._mesh_w2c, depth_trunc=depth_trunc, render_header=c.geom)
         return volume
+
+    @torch.no_grad()
+    def make_clean_mesh(self, frames, volume, cap_vertices, cap_faces, depth_trunc=30.0, min_component_faces=0, largest_only=False,
+                        smooth_iter=0, smooth_lambda=0.5, smooth_mu=None, normals=True):
+        """The map as the mesh a SLAM pipeline reports: make_mesh(frames, volume, depth_trunc), volume.extract(cap_vertices, cap_faces),
+        then on the device dqo_eval.mesh_components(min_faces=min_component_faces, largest_only) — the floaters that the renders of a
+        Gaussian map leave in the volume go —, dqo_eval.mesh_smooth(smooth_iter, smooth_lambda, smooth_mu) on positions and colours —
+        smooth_iter and smooth_lambda are the reference configs' mesh_smooth_iter and mesh_smooth_lambda
+        (configs/Cube_Diorama_base.yaml:45-46: 10 and 0.5), smooth_mu makes it Taubin's — and, with `normals`, dqo_eval.mesh_normals.
+        Returns the cleaned mesh dict (vertices, colors, faces, header = dqo_eval.MESHOPS_HEADER, normals), in dqo_eval's own buffers
+        for the capacities, overwritten by the next call; dqo_eval.mesh_counts(mesh) reads its counts,
+        dqo_ply.write_mesh_ply_normals writes it (cut at the counts).  No host read after the first call of a shape (make_mesh's one
+        header read); NotImplementedError on a sharded mapper, exactly as make_mesh."""
+        self._refuse_sharded("make_clean_mesh")
+        self.make_mesh(frames, volume, depth_trunc=depth_trunc)
+        with torch.cuda.device(self.device):
+            mesh = dqo_eval.mesh_components(volume.extract(cap_vertices, cap_faces), min_faces=min_component_faces, largest_only=largest_only)
+            dqo_eval.mesh_smooth(mesh, smooth_iter, lam=smooth_lambda, mu=smooth_mu, scope="all")
+            if normals:
+                dqo_eval.mesh_normals(mesh)
+            else:
+                mesh.pop("normals", None)
+        return mesh
 
     # ------------------------------------------------------------------ geometry evaluation (csrc/knn.hip, map_densify.hip) --
     @torch.no_grad()

@@ -14,7 +14,7 @@ the reference stores.
 
 read_mesh_ply reads the other PLY of an evaluation: the ground-truth triangle mesh eval_pcd loads with trimesh (SLAM/eval.py:236), as
 the two arrays dqo_eval.sample_surface takes.  write_mesh_ply writes such a file — the mesh of dqo_eval.TsdfVolume.extract, with vertex
-colours — in the layout read_mesh_ply reads.
+colours — in the layout read_mesh_ply reads; write_mesh_ply_normals adds the vertex normals of dqo_eval.mesh_normals.
 """
 import numpy as np
 
@@ -374,27 +374,30 @@ def read_mesh_ply(path):
     return vertices, np.ascontiguousarray(idx, dtype=np.int32)
 
 
-def write_mesh_ply(path, vertices, faces, colors=None):
-    """A triangle mesh file that read_mesh_ply reads back: `format binary_little_endian 1.0`, a `vertex` element of float x y z and, with
-    colors, uchar red green blue = round(255 * clamp(c, 0, 1)), then a `face` element `property list uchar int vertex_indices`.
-    vertices [V,3], faces [F,3] (indices, written as int32), colors [V,3] in [0, 1] or None; arrays or tensors (a device tensor is copied
-    to the host: cut the buffers of dqo_eval.TsdfVolume.extract at its written counts first).  Returns (V, F)."""
+def _write_mesh(who, path, vertices, faces, normals, colors):
     a = lambda t, dt: np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=dt)
     v, f = a(vertices, np.float32), a(faces, np.int32)
     if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
-        raise ValueError(f"write_mesh_ply: vertices must be [V,3] and faces [F,3], got {v.shape} and {f.shape}")
+        raise ValueError(f"{who}: vertices must be [V,3] and faces [F,3], got {v.shape} and {f.shape}")
     V, F = v.shape[0], f.shape[0]
-    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
-    header = "ply\nformat binary_little_endian 1.0\n" + f"element vertex {V}\n" + "property float x\nproperty float y\nproperty float z\n"
+    columns = [("x", v[:, 0]), ("y", v[:, 1]), ("z", v[:, 2])]
+    if normals is not None:
+        n = a(normals, np.float32)
+        if n.shape != (V, 3):
+            raise ValueError(f"{who}: normals must be [{V},3], got {n.shape}")
+        columns += [("nx", n[:, 0]), ("ny", n[:, 1]), ("nz", n[:, 2])]
+    fields = [(k, "<f4") for k, _ in columns]
+    header = "ply\nformat binary_little_endian 1.0\n" + f"element vertex {V}\n" + "".join(f"property float {k}\n" for k, _ in columns)
     if colors is not None:
         c = a(colors, np.float32)
         if c.shape != (V, 3):
-            raise ValueError(f"write_mesh_ply: colors must be [{V},3], got {c.shape}")
+            raise ValueError(f"{who}: colors must be [{V},3], got {c.shape}")
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
         header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
     header += f"element face {F}\nproperty list uchar int vertex_indices\nend_header\n"
     vt = np.zeros((V,), dtype=np.dtype(fields))
-    vt["x"], vt["y"], vt["z"] = v[:, 0], v[:, 1], v[:, 2]
+    for k, col in columns:
+        vt[k] = col
     if colors is not None:
         with np.errstate(invalid="ignore"):
             c8 = np.rint(255.0 * np.clip(np.nan_to_num(c.astype(np.float64), nan=0.0), 0.0, 1.0)).astype(np.uint8)
@@ -406,3 +409,18 @@ def write_mesh_ply(path, vertices, faces, colors=None):
         fh.write(vt.tobytes())
         fh.write(ft.tobytes())
     return V, F
+
+
+def write_mesh_ply(path, vertices, faces, colors=None):
+    """A triangle mesh file that read_mesh_ply reads back: `format binary_little_endian 1.0`, a `vertex` element of float x y z and, with
+    colors, uchar red green blue = round(255 * clamp(c, 0, 1)), then a `face` element `property list uchar int vertex_indices`.
+    vertices [V,3], faces [F,3] (indices, written as int32), colors [V,3] in [0, 1] or None; arrays or tensors (a device tensor is copied
+    to the host: cut the buffers of dqo_eval.TsdfVolume.extract at its written counts first).  Returns (V, F)."""
+    return _write_mesh("write_mesh_ply", path, vertices, faces, None, colors)
+
+
+def write_mesh_ply_normals(path, vertices, faces, normals, colors=None):
+    """write_mesh_ply with vertex normals — the mesh of dqo_eval.mesh_normals: the `vertex` element is float x y z nx ny nz and, with
+    colors, uchar red green blue (open3d's property order; the colour bytes as write_mesh_ply writes them).  normals [V,3] float32.
+    read_mesh_ply skips the extra scalars, so the file reads back.  Returns (V, F)."""
+    return _write_mesh("write_mesh_ply_normals", path, vertices, faces, normals, colors)

@@ -1157,8 +1157,8 @@ int dqo_prune_rows(int32_t P, float* xyz, float* opacity_raw, float* scaling_raw
  *   capacity above 0; DQO_ERR_WORKSPACE.
  * workspace: dqo_tsdf_workspace_bytes(nx, ny, nz) bytes (0 for bad dims; 5 bytes per voxel and 12 per 2048 voxels behind the ticket words),
  *   ZERO when first used and then left to dqo_tsdf_extract, which hands it back ready for the next call.
- * Not built: Laplacian smoothing (the mesh_smooth_iter / mesh_smooth_lambda keys of configs/Cube_Diorama_base.yaml:45-46 are read by nothing
- *   in the reference tree), hashed or sparse volumes, mesh simplification, merging the volumes of shards. */
+ * Laplacian smoothing (the mesh_smooth_iter / mesh_smooth_lambda keys of configs/Cube_Diorama_base.yaml:45-46, read by nothing in the
+ *   reference tree) is dqo_mesh_smooth below.  Not built: hashed or sparse volumes, mesh simplification, merging the volumes of shards. */
 size_t dqo_tsdf_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
 int dqo_tsdf_clear(int32_t nx, int32_t ny, int32_t nz, float* tsdf, float* weight, float* color, int32_t* header, void* hipStream);
 int dqo_tsdf_integrate(int32_t nx, int32_t ny, int32_t nz, float origin_x, float origin_y, float origin_z, float voxel_length,
@@ -1168,6 +1168,83 @@ int dqo_tsdf_integrate(int32_t nx, int32_t ny, int32_t nz, float origin_x, float
 int dqo_tsdf_extract(int32_t nx, int32_t ny, int32_t nz, float origin_x, float origin_y, float origin_z, float voxel_length,
                      const float* tsdf, const float* weight, const float* color, float* vertices, float* vertex_color, int32_t* faces,
                      int32_t cap_vertices, int32_t cap_faces, int32_t* header, void* workspace, size_t workspace_bytes, void* hipStream);
+
+/* dqo_mesh_components / dqo_mesh_smooth / dqo_mesh_normals (ABI 5, symbols-only addition) — the clean-up of the mesh dqo_tsdf_extract
+ * leaves, on the device: what a SLAM mesh pipeline does with open3d before it reports or shows a mesh.  open3d does not exist on this
+ * platform, so THIS text defines the rules (they follow open3d's published algorithms; every departure is marked) and
+ * tests/mesh_ops_oracle.py restates them in numpy; nothing is pinned against the library.  csrc/map_meshops.hip lists the launches.
+ *
+ * The operand: an indexed mesh in caller-owned device buffers, laid out as dqo_tsdf_extract's output — vertices float32 [cap_vertices,3],
+ *   colors float32 [cap_vertices,3] (may be NULL), faces int32 [cap_faces,3] — and counts, a device pointer to two int32 (vertices, faces;
+ *   words 0 and 1 of a TSDF header or of dqo_mesh_components' header fit directly; NULL: the capacities are the counts; a count is clamped
+ *   to [0, capacity]).  V and F below are the counts.  Rows behind the counts are never read and never written.  Grids are sized from the
+ *   capacities: the launch count is a fixed function of the arguments, never of the data; no host read, no synchronise, no memset, no float
+ *   atomics — every entry can be captured in a hipGraph.  A face is VALID iff its three indices lie in [0, V).
+ *   Every entry refuses, before any launch (DQO_ERR_INVALID_ARG), a capacity outside 1 <= cap_vertices, cap_faces < 2^28 and a NULL
+ *   vertices / faces pointer; then a short workspace (DQO_ERR_WORKSPACE).
+ *
+ * dqo_mesh_components — open3d's cluster_connected_triangles + remove_triangles_by_mask + remove_unreferenced_vertices.  Eleven launches.
+ *     - two faces are connected iff they share a vertex INDEX.  (Departure: open3d clusters by shared edges; the two differ only at
+ *       non-manifold pinch vertices, where two sheets touch in one vertex.)
+ *     - a face that is not valid belongs to no component: it is dropped and counted.  A face with a repeated index is a face like any other.
+ *     - a component's label is the smallest vertex id in it, its size its number of faces.
+ *     - threshold = max(min_faces, largest_only ? the size of the largest component : 0); a face is kept iff its component's size >=
+ *       threshold (components tied for largest are all kept).
+ *     - kept faces keep their order; the vertices they reference keep their order and are renumbered densely; positions and colours are
+ *       copied bit for bit.
+ *   Outputs: the out mesh in separate buffers (out_vertices, out_colors — ignored when colors is NULL — and out_faces must not be the
+ *   input's; their capacities must not be below the input's, so nothing can be cut); labels (may be NULL) int32 [cap_faces]: a face's
+ *   label, -1 for a dropped bad face; header int32 [8]: [0] vertices written, [1] faces written (so the header is the next operator's
+ *   counts), [2] components, [3] components kept, [4] faces with a bad index, [5] the largest component's faces, [6] vertices removed,
+ *   [7] faces removed by the threshold.
+ *   A lock-free union-find over the vertices (the larger root goes under the smaller by a returning compare-and-swap, with path halving:
+ *   the final root is the component's minimum whatever order the hardware ran in), sizes by integer atomics aggregated per wave and root,
+ *   compaction by block counts and a last-block scan.  The same bits on every run.
+ *   DQO_ERR_INVALID_ARG also for min_faces < 0, a NULL header or out buffer, an out buffer that is the input's, a header that is the
+ *   input's counts (the first launch clears the header before any launch reads the counts), an out capacity below the
+ *   input's.
+ *
+ * dqo_mesh_smooth — open3d's filter_smooth_laplacian (configs/Cube_Diorama_base.yaml:45-46: mesh_smooth_iter = iterations,
+ *   mesh_smooth_lambda = lambda) and, with mu != 0, filter_smooth_taubin (open3d's defaults: lambda 0.5, mu -0.53), in place.
+ *   Adjacency, the same for every iteration of a call: N(i) = the vertices that share a valid face with i, i itself excluded, each once,
+ *   in ascending id order.  One step with factor L, for every vertex with N(i) non-empty, in DOUBLE from the float32 values of the step
+ *   before, every operation rounded once, none contracted, sums left to right from 0 over ascending neighbour id, sqrt and division
+ *   correctly rounded:
+ *       d_n = p_i - p_n;  dist = sqrt((d_x * d_x + d_y * d_y) + d_z * d_z);  w_n = 1 / (dist + 1e-12)
+ *       S = sum w_n * p_n;  T = sum w_n;  p_i' = (float)(p_i + L * (S / T - p_i))
+ *   Colours, when the scope includes them, use the same w_n — taken from the positions BEFORE the step — in place of p in the last line.
+ *   A vertex without neighbours is copied unchanged (departure: open3d divides by zero there); rounding to float32 between steps is a
+ *   departure too (open3d keeps doubles).  mu == 0: an iteration is one step with lambda; otherwise a step with lambda, then one with mu.
+ *   scope: DQO_MESH_SMOOTH_POSITIONS, _COLOURS (positions give the weights and stay), _BOTH.  iterations == 0: nothing is launched.
+ *   Five launches build the adjacency as a CSR (count by integer atomics, scan, fill through an atomic cursor, then every vertex's segment
+ *   is sorted and made unique — by its thread up to 32 raw entries, by its block beyond: nothing depends on the fill's order), then one
+ *   launch per step, one thread per vertex, and a copy after an odd number of steps (the workspace holds the other half of the ping-pong).
+ *   DQO_ERR_INVALID_ARG also for iterations < 0, a lambda or mu that is not finite, a bad scope, NULL colors with a scope that needs them.
+ *
+ * dqo_mesh_normals — open3d's compute_vertex_normals: normals float32 [cap_vertices,3].  Face normal n_f = cross(p1 - p0, p2 - p0) in
+ *   double, un-normalised (the sum is area-weighted), each component a * b - c * d with one rounding per operation.  A vertex's normal is
+ *   the sum, from 0, of the normals of its incident valid faces in ascending face index — a face that names the vertex twice counts once
+ *   per corner, as open3d's loop does — divided by its length sqrt((x * x + y * y) + z * z) and rounded once to float32.  A zero or
+ *   non-finite length gives (0, 0, 1): an unreferenced vertex, a vertex with only degenerate faces.  The CSR build of dqo_mesh_smooth with
+ *   a corner's face in place of its two neighbours (five launches), then one thread per vertex.
+ *
+ * workspaces: dqo_mesh_components_workspace_bytes / dqo_mesh_smooth_workspace_bytes / dqo_mesh_normals_workspace_bytes (cap_vertices,
+ *   cap_faces): 0 for bad capacities; ZERO when first used and then left to the entry, which hands it back ready for the next call.
+ * Not built: edge-based clustering, mesh simplification, hole filling, smoothing of normals. */
+#define DQO_MESH_SMOOTH_POSITIONS 0
+#define DQO_MESH_SMOOTH_COLOURS 1
+#define DQO_MESH_SMOOTH_BOTH 2
+size_t dqo_mesh_components_workspace_bytes(int32_t cap_vertices, int32_t cap_faces);
+size_t dqo_mesh_smooth_workspace_bytes(int32_t cap_vertices, int32_t cap_faces);
+size_t dqo_mesh_normals_workspace_bytes(int32_t cap_vertices, int32_t cap_faces);
+int dqo_mesh_components(const float* vertices, const float* colors, const int32_t* faces, const int32_t* counts, int32_t cap_vertices,
+                        int32_t cap_faces, int32_t min_faces, int32_t largest_only, float* out_vertices, float* out_colors,
+                        int32_t* out_faces, int32_t out_cap_vertices, int32_t out_cap_faces, int32_t* labels, int32_t* header,
+                        void* workspace, size_t workspace_bytes, void* hipStream);
+int dqo_mesh_smooth(float* vertices, float* colors, const int32_t* faces, const int32_t* counts, int32_t cap_vertices, int32_t cap_faces,
+                    int32_t iterations, double lambda, double mu, int32_t scope, void* workspace, size_t workspace_bytes, void* hipStream);
+int dqo_mesh_normals(const float* vertices, const int32_t* faces, const int32_t* counts, int32_t cap_vertices, int32_t cap_faces,
+                     float* normals, void* workspace, size_t workspace_bytes, void* hipStream);
 
 #define DQO_TICKET_WORDS (16 + 16 * 64) /* int32 words behind DqoAdamStep.block_ticket */
 typedef struct DqoAdamStep {
