@@ -128,7 +128,7 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_eval_ate_workspace_bytes", "dqo_eval_ate", "dqo_prune_workspace_bytes", "dqo_prune_cameras", "dqo_prune_touch",
            "dqo_prune_rows", "dqo_tsdf_workspace_bytes", "dqo_tsdf_clear", "dqo_tsdf_integrate", "dqo_tsdf_extract",
            "dqo_mesh_components_workspace_bytes", "dqo_mesh_smooth_workspace_bytes", "dqo_mesh_normals_workspace_bytes",
-           "dqo_mesh_components", "dqo_mesh_smooth", "dqo_mesh_normals")
+           "dqo_mesh_components", "dqo_mesh_smooth", "dqo_mesh_normals", "dqo_mesh_simplify_workspace_bytes", "dqo_mesh_simplify")
 
 _lib = None
 
@@ -264,11 +264,12 @@ def lib():
         L.dqo_tsdf_integrate.argtypes = [c_i32] * 3 + [c_f] * 5 + [c_vp] * 4 + [c_i32, c_i32, c_vp, c_vp] + [c_f] * 4 + [c_vp, c_f, c_vp, c_vp]
         L.dqo_tsdf_extract.argtypes = [c_i32] * 3 + [c_f] * 4 + [c_vp] * 6 + [c_i32, c_i32, c_vp, c_vp, c_sz, c_vp]
         # map_meshops.hip
-        for n in ("components", "smooth", "normals"):
+        for n in ("components", "smooth", "normals", "simplify"):
             getattr(L, f"dqo_mesh_{n}_workspace_bytes").argtypes = [c_i32, c_i32]
         L.dqo_mesh_components.argtypes = [c_vp] * 4 + [c_i32] * 4 + [c_vp] * 3 + [c_i32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]
         L.dqo_mesh_smooth.argtypes = [c_vp] * 4 + [c_i32] * 3 + [c_d, c_d, c_i32, c_vp, c_sz, c_vp]
         L.dqo_mesh_normals.argtypes = [c_vp] * 3 + [c_i32, c_i32, c_vp, c_vp, c_sz, c_vp]
+        L.dqo_mesh_simplify.argtypes = [c_vp] * 4 + [c_i32, c_i32] + [c_d] * 4 + [c_vp] * 3 + [c_i32, c_i32, c_vp, c_vp, c_sz, c_vp]
         # icp.hip, track.hip
         L.dqo_icp_normal_equations.argtypes = [c_i32, c_i32] + [c_vp] * 5 + [c_f] * 6 + [c_vp] * 4 + [c_sz, c_vp]
         L.dqo_icp_gauss_newton.argtypes = [c_i32, c_i32] + [c_vp] * 6 + [c_f] * 4 + [c_vp] * 2 + [c_sz, c_vp]

@@ -5,7 +5,8 @@
 // the frame's counts), map_prune.hip (prune_rows_kernel: ticket and counts), map_tilemask.hip (window_masks_kernel: ticket only, its last block selects tiles), map_checkpoint.hip (map_pack_count_kernel: its last block scans
 // the blocks' row counts), map_meshsample.hip (mesh_area_kernel: max and counts; mesh_quantise_kernel: its last block scans the blocks'
 // quanta), map_tsdf.hip (tsdf_edges_kernel, tsdf_vertices_kernel: their last blocks scan the spans' vertex and face counts),
-// map_meshops.hip (mesh_comp_stats / _fcount / _vcount_kernel, mesh_csr_scan_kernel: span partials folded or scanned), dqo_adam.h
+// map_meshops.hip (mesh_comp_stats / _fcount / _vcount_kernel, mesh_csr_scan_kernel, mesh_simp_number / _keep_kernel: span partials folded
+// or scanned), dqo_adam.h
 // (ticket only, unfenced).
 //
 // Below the double reductions, the integer ends the map operators share (behind whichever last-block ticket their kernel takes):

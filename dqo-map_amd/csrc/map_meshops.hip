@@ -1,9 +1,9 @@
-// Mesh clean-up for gfx950 on the indexed mesh dqo_tsdf_extract leaves (map_tsdf.hip): connected components and the filtered mesh, Laplacian /
-// Taubin smoothing, area-weighted vertex normals — what a SLAM mesh pipeline does with open3d's cluster_connected_triangles +
-// remove_triangles_by_mask + remove_unreferenced_vertices, filter_smooth_laplacian / filter_smooth_taubin (the reference's
+// Mesh clean-up for gfx950 on the indexed mesh dqo_tsdf_extract leaves (map_tsdf.hip): connected components and the filtered mesh,
+// simplification by vertex clustering, Laplacian / Taubin smoothing, area-weighted vertex normals — what a SLAM mesh pipeline does with open3d's cluster_connected_triangles +
+// remove_triangles_by_mask + remove_unreferenced_vertices, simplify_vertex_clustering, filter_smooth_laplacian / filter_smooth_taubin (the reference's
 // configs/Cube_Diorama_base.yaml:45-46 names mesh_smooth_iter: 10, mesh_smooth_lambda: 0.5) and compute_vertex_normals.  open3d does not
 // exist on this platform, so the rules of include/dqo_raster.h are the definition (they follow open3d's published algorithms; the
-// departures are listed there) and tests/mesh_ops_oracle.py restates them in numpy; nothing is pinned against the library.
+// departures are listed there) and tests/mesh_ops_oracle.py and tests/mesh_simplify_oracle.py restate them in numpy; nothing is pinned against the library.
 //
 // The operand: vertices float32 [cap_v,3], colors float32 [cap_v,3] (may be NULL), faces int32 [cap_f,3], counts = a device pointer to
 // two int32 (vertices, faces; NULL: the capacities are the counts; a count is clamped to [0, capacity]).  Rows behind the counts are never
@@ -40,6 +40,29 @@
 //             the race.  Up to 32 raw entries (a marching-tetrahedra vertex has at most 20): an insertion sort by the vertex's thread.
 //             More: the vertex's block sorts it with a bitonic network (the same-direction form, which takes any length) — in LDS up to
 //             2048 entries, in place in global memory beyond — and compacts it with block scans.
+// dqo_mesh_simplify — open3d's simplify_vertex_clustering with the Average contraction — twelve launches, no device-wide sort:
+//   clear     the two tables to -1 (their slots: the power of two that is at least twice the COUNT, so a small mesh in large buffers
+//             clears and probes a small table), the member counts, the marks and the header to 0, by a bounded grid that strides;
+//   cells     a vertex's cell from its position in double; an open-addressed table of vertex ids with linear probing:
+//             atomicCAS(slot, -1, v) claims an empty slot; an occupant of the same cell — recomputed from the immutable positions —
+//             makes it atomicMin(slot, v); another cell's sends it on.  A slot's cell never changes, so the slot ends at the cluster's
+//             smallest vertex id whatever order the hardware ran in.  The vertex keeps its slot.  Vertices outside the grid are counted;
+//   faces     a face is bad, outside, collapsed (counted, one integer atomic per span of 2048 faces that has any) or live; a live
+//             face's representatives, rotated so that the smallest comes first, go to the workspace and are marked (plain stores of 1);
+//   ftable    the same table over the live faces, keyed by the rotated triple; an occupant's triple is read from what `faces` wrote,
+//             which is why the two are two launches;
+//   number    a marked representative's rank within its span; the spans' totals scanned by the last block -> header[0], [2];
+//   members   every in-grid vertex of a written cluster takes the cluster's id and adds one to its member count;
+//   scan      mesh_csr_scan_kernel with the written clusters as the segment owners (its counts: the header);
+//   fill      members into their cluster's segment through the count as a cursor;
+//   order     every member list ascending: up to 2048 members, each member counts the ids below its own and takes that place (one
+//             thread per member: a clustering at a few voxels has thousands of lists of a hundred, which the CSR's tidy would sort
+//             one after the other on a few blocks — it took 1.31 ms of a 1.95 ms call at four voxels, profiles/mesh_ops.txt); longer
+//             lists by their cluster's block with the tidy's bitonic network in global memory;
+//   average   one thread per written cluster: the sum in double over the ascending members, divided, rounded once;
+//   keep      a live face is kept iff its slot holds its own index; the spans' kept counts scanned -> header[1], [7];
+//   scatter   kept faces, in order, renumbered.
+//   Every probe loop ends after as many steps as the table has slots; a table of twice the entries always has an empty one.
 // Then smoothing runs one thread per vertex per step (a gather over the segment, double arithmetic, ping-pong between the mesh and the
 // workspace, a copy back after an odd number of steps), normals one thread per vertex.  Every double statement is the one written,
 // rounded once, none contracted (the Makefile states -ffp-contract=off); sqrt and `/` on doubles are the correctly rounded ones.
@@ -57,6 +80,7 @@ enum {
     MO_THREAD_MAX = 32,   // tidy: raw entries a single thread sorts
     MO_LDS_MAX = 2048,    // tidy: raw entries a block sorts in LDS
     MO_MAX = 1 << 28,     // capacities lie below it: 6 cap_f adjacency entries stay below 2^32
+    MO_CLEAR_BLOCKS = 2048,  // simplify: the most blocks of its clearing launch
 };
 static_assert(MO_SPAN == 256 * MO_CHUNKS, "a span is MO_CHUNKS runs of a block");
 
@@ -598,7 +622,363 @@ __global__ __launch_bounds__(256) void mesh_normals_kernel(const float* __restri
     normals[3 * (size_t)i] = nx, normals[3 * (size_t)i + 1] = ny, normals[3 * (size_t)i + 2] = nz;
 }
 
+// ---- simplification by vertex clustering ------------------------------------------------------------------------------------------------
+struct MoSimp {
+    int32_t* head;
+    int32_t* vtab;     // [slots of cap_v] the vertex table: -1, or the smallest vertex id so far of the slot's cell
+    int32_t* vslot;    // [cap_v] a vertex's slot of vtab (-1: outside the grid)
+    int32_t* mark;     // [cap_v] 1: a live face names the cluster whose representative this vertex is
+    int32_t* cnum;     // [cap_v] a written representative's rank among those of its span (-1: none)
+    int32_t* vcid;     // [cap_v] the written cluster a vertex is a member of (-1: none)
+    int32_t* sorted;   // [cap_v] the member lists of up to MO_LDS_MAX entries, ascending (the longer ones: sorted in the CSR's adj)
+    int32_t* ftab;     // [slots of cap_f] the face table: -1, or the lowest face index so far of the slot's rotated triple
+    int32_t* fslot;    // [cap_f] a live face's slot of ftab (-1: not live)
+    int32_t* ftri;     // [cap_f,3] a live face's representatives, the smallest first
+    u64* vspan;        // [spans of cap_v] written clusters | clusters formed << 32 of the span, then of the spans before it
+    uint32_t* fspan;   // [spans of cap_f] kept faces, likewise
+    double voxel, org[3];
+};
+
+// the slots of a table for n entries: the power of two that is at least 2 n (n < 2^28), so an empty slot always ends a probe
+__host__ __device__ inline uint32_t mo_slots(uint32_t n) {
+    uint32_t s = 2u;
+    while (s < 2u * n) s <<= 1;
+    return s;
+}
+
+__device__ __forceinline__ u64 mo_mix(u64 x) {  // (splitmix64's finaliser)
+    x ^= x >> 30, x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27, x *= 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+
+// the cell of vertex v as 21 bits an axis; false: outside the grid
+__device__ __forceinline__ bool mo_cell(const float* __restrict__ vertices, uint32_t v, const MoSimp& w, u64& key) {
+#pragma clang fp contract(off)
+    key = 0ull;
+    bool in = true;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const double t = ((double)vertices[3 * (size_t)v + a] - w.org[a]) / w.voxel;
+        const double i = floor(t);  // (NaN fails both comparisons; an infinite t is its own floor and fails one)
+        in = in && i >= 0.0 && i < 2097152.0;
+        key = (key << 21) | (u64)(in ? (uint32_t)i : 0u);
+    }
+    return in;
+}
+
+// (a grid of at most MO_CLEAR_BLOCKS blocks strides over what the COUNTS need: the capacities' tables may be a hundred times that)
+__global__ __launch_bounds__(256) void mesh_simp_clear_kernel(const int32_t* __restrict__ counts, uint32_t cap_v, uint32_t cap_f, MoSimp w,
+                                                              uint32_t* __restrict__ deg, int32_t* __restrict__ header) {
+    const uint32_t V = mo_count(counts, 0, cap_v), F = mo_count(counts, 1, cap_f);
+    const uint32_t sv = mo_slots(V), sf = mo_slots(F), n = max(max(sv, sf), 8u);  // (above V, and the header's eight words even when V = F = 0)
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        if (i < sv) w.vtab[i] = -1;
+        if (i < sf) w.ftab[i] = -1;
+        if (i < V) w.mark[i] = 0;
+        if (i <= V) deg[i] = 0u;
+        if (i < 8u) header[i] = 0;
+    }
+}
+
+// A vertex enters the table at the first slot of its cell's probe sequence that is empty or holds a vertex of its cell.  A slot's cell
+// never changes (a replacement has the same cell) and a slot never empties, so every vertex of a cell ends in the same slot, and the
+// slot's final value is the cell's smallest vertex id whatever order the hardware ran in.  Relaxed agent-scope atomics: the argument
+// needs the order of the accesses to ONE word only; the positions an occupant's cell is recomputed from are never written.
+__global__ __launch_bounds__(256) void mesh_simp_cells_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ counts,
+                                                              uint32_t cap_v, MoSimp w, int32_t* __restrict__ header) {
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t V = mo_count(counts, 0, cap_v);
+    bool outside = false;
+    if (v < V) {
+        int32_t slot = -1;
+        u64 key;
+        if (mo_cell(vertices, v, w, key)) {
+            const uint32_t mask = mo_slots(V) - 1u;
+            uint32_t s = (uint32_t)mo_mix(key) & mask;
+            for (uint32_t probe = 0; probe <= mask; probe++, s = (s + 1u) & mask) {  // (bounded: a bug cannot spin)
+                const int32_t occ = atomicCAS(w.vtab + s, -1, (int32_t)v);
+                if (occ == -1) {
+                    slot = (int32_t)s;
+                    break;
+                }
+                u64 other;
+                if ((uint32_t)occ < V && mo_cell(vertices, (uint32_t)occ, w, other) && other == key) {
+                    if (occ > (int32_t)v) atomicMin(w.vtab + s, (int32_t)v);
+                    slot = (int32_t)s;
+                    break;
+                }
+            }
+        }
+        w.vslot[v] = slot;
+        outside = slot < 0;
+    }
+    const int n = __popcll(__ballot(outside));
+    if ((threadIdx.x & 63) == 0 && n > 0) atomicAdd(&header[3], n);
+}
+
+__device__ __forceinline__ void mo_wave_count(int32_t* word, bool pred) {  // (every lane of the wave calls it)
+    const int n = __popcll(__ballot(pred));
+    if ((threadIdx.x & 63) == 0 && n > 0) atomicAdd(word, n);
+}
+
+// the representative of the cluster of v (-1: v is outside the grid)
+__device__ __forceinline__ int32_t mo_rep(const MoSimp& w, int32_t v) {
+    const int32_t s = w.vslot[v];
+    return s < 0 ? -1 : w.vtab[s];
+}
+
+__global__ __launch_bounds__(256) void mesh_simp_faces_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ counts,
+                                                              uint32_t cap_v, uint32_t cap_f, MoSimp w, int32_t* __restrict__ header) {
+    __shared__ uint32_t s_n[3];
+    const uint32_t V = mo_count(counts, 0, cap_v), F = mo_count(counts, 1, cap_f);
+    if (threadIdx.x < 3u) s_n[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t n[3] = {0u, 0u, 0u};  // bad, outside, collapsed
+    for (uint32_t chunk = 0; chunk < (uint32_t)MO_CHUNKS; chunk++) {
+        const uint32_t f = (blockIdx.x * (uint32_t)MO_CHUNKS + chunk) * 256u + threadIdx.x;
+        if (f >= F) break;
+        int32_t a, b, c;
+        bool live = false;
+        if (!mo_face(faces, f, V, a, b, c)) n[0]++;
+        else {
+            const int32_t ra = mo_rep(w, a), rb = mo_rep(w, b), rc = mo_rep(w, c);
+            if (ra < 0 || rb < 0 || rc < 0) n[1]++;
+            else if (ra == rb || rb == rc || ra == rc) n[2]++;
+            else {
+                live = true;
+                int32_t t0 = ra, t1 = rb, t2 = rc;  // rotated, the smallest first: the orientation stays
+                if (rb < ra && rb < rc) t0 = rb, t1 = rc, t2 = ra;
+                else if (rc < ra && rc < rb) t0 = rc, t1 = ra, t2 = rb;
+                w.ftri[3 * (size_t)f] = t0, w.ftri[3 * (size_t)f + 1] = t1, w.ftri[3 * (size_t)f + 2] = t2;
+                w.mark[t0] = 1, w.mark[t1] = 1, w.mark[t2] = 1;
+            }
+        }
+        w.fslot[f] = live ? 0 : -1;  // (a live face's slot: by the next launch)
+    }
+    // a span's counts: the waves' sums into LDS, then one integer atomic per word that is not zero — a mesh whose faces nearly all
+    // collapse would otherwise send one same-address atomic per wave
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const uint32_t t = dqo_wave_sum_u32(n[k], lane);
+        if (lane == 0 && t != 0u) atomicAdd(&s_n[k], t);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3u && s_n[threadIdx.x] != 0u) atomicAdd(&header[4 + threadIdx.x], (int32_t)s_n[threadIdx.x]);
+}
+
+// The vertex table's protocol over the live faces, keyed by the rotated triple.  An occupant's triple is read from ftri, which the
+// launch before this one wrote: nothing is ordered inside this launch but the accesses to one slot.
+__global__ __launch_bounds__(256) void mesh_simp_ftable_kernel(const int32_t* __restrict__ counts, uint32_t cap_f, MoSimp w,
+                                                               int32_t* __restrict__ header) {
+    const uint32_t f = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t F = mo_count(counts, 1, cap_f);
+    bool lost = false;
+    if (f < F && w.fslot[f] >= 0) {  // live: mesh_simp_faces_kernel wrote its triple
+        const int32_t t0 = w.ftri[3 * (size_t)f], t1 = w.ftri[3 * (size_t)f + 1], t2 = w.ftri[3 * (size_t)f + 2];
+        const uint32_t mask = mo_slots(F) - 1u;
+        uint32_t s = (uint32_t)mo_mix(mo_mix(((u64)(uint32_t)t0 << 32) | (u64)(uint32_t)t1) ^ (u64)(uint32_t)t2) & mask;
+        int32_t slot = -1;
+        for (uint32_t probe = 0; probe <= mask; probe++, s = (s + 1u) & mask) {
+            const int32_t occ = atomicCAS(w.ftab + s, -1, (int32_t)f);
+            if (occ == -1) {
+                slot = (int32_t)s;
+                break;
+            }
+            if ((uint32_t)occ < F && w.ftri[3 * (size_t)occ] == t0 && w.ftri[3 * (size_t)occ + 1] == t1 && w.ftri[3 * (size_t)occ + 2] == t2) {
+                if (occ > (int32_t)f) atomicMin(w.ftab + s, (int32_t)f);
+                slot = (int32_t)s;
+                break;
+            }
+        }
+        w.fslot[f] = slot;
+        lost = slot < 0;  // (a full table: never, with twice the slots; the face then counts as bad)
+    }
+    mo_wave_count(&header[4], lost);
+}
+
+// cnum[v] = the rank of v among its span's written representatives; the spans' totals, scanned by the last block -> header[0], [2]
+__global__ __launch_bounds__(256) void mesh_simp_number_kernel(const int32_t* __restrict__ counts, uint32_t cap_v, MoSimp w,
+                                                               int32_t* __restrict__ header) {
+    __shared__ u64 s_wave[4];
+    __shared__ int s_last;
+    const uint32_t V = mo_count(counts, 0, cap_v);
+    u64 run = 0ull;
+    for (uint32_t chunk = 0; chunk < (uint32_t)MO_CHUNKS; chunk++) {
+        const uint32_t i = (blockIdx.x * (uint32_t)MO_CHUNKS + chunk) * 256u + threadIdx.x;
+        u64 pair = 0ull;
+        if (i < V && mo_rep(w, (int32_t)i) == (int32_t)i) pair = (1ull << 32) | (u64)(uint32_t)w.mark[i];
+        u64 total;
+        const u64 before = dqo_block_exclusive<u64>(pair, total, s_wave);
+        if (i < V) w.cnum[i] = (uint32_t)pair != 0u ? (int32_t)(uint32_t)(run + before) : -1;
+        run += total;
+    }
+    if (threadIdx.x == 0) __hip_atomic_store(&w.vspan[blockIdx.x], run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!dqo_last_block(w.head, &s_last)) return;
+    const u64 sums = dqo_scan_block_counts<u64, 2>(w.vspan, gridDim.x, 1, s_wave);
+    if (threadIdx.x == 0) header[0] = (int32_t)(uint32_t)sums, header[2] = (int32_t)(sums >> 32);
+}
+
+// vcid[v] = the written cluster v is a member of, whose member count goes up by one
+__global__ __launch_bounds__(256) void mesh_simp_members_kernel(const int32_t* __restrict__ counts, uint32_t cap_v, MoSimp w,
+                                                                uint32_t* __restrict__ deg) {
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= mo_count(counts, 0, cap_v)) return;
+    const int32_t r = mo_rep(w, (int32_t)v);
+    int32_t cid = -1;
+    if (r >= 0 && w.cnum[r] >= 0) {
+        cid = (int32_t)((uint32_t)w.vspan[(uint32_t)r >> MO_SPAN_SHIFT] + (uint32_t)w.cnum[r]);  // (<= r < cap_v)
+        atomicAdd(&deg[cid], 1u);
+    }
+    w.vcid[v] = cid;
+}
+
+// the CSR's fill with the cluster as the segment's owner (the order inside a segment is racy here; mesh_simp_order_kernel ends that)
+__global__ __launch_bounds__(256) void mesh_simp_fill_kernel(const int32_t* __restrict__ counts, uint32_t cap_v, MoSimp w, MoCsr c) {
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= mo_count(counts, 0, cap_v)) return;
+    const int32_t cid = w.vcid[v];
+    if (cid < 0) return;
+    c.adj[mo_start(c, (uint32_t)cid) + (size_t)(atomicSub(&c.deg[cid], 1u) - 1u)] = (int32_t)v;
+}
+
+// The member lists in ascending order.  Clustering at a few voxels leaves thousands of lists of tens to hundreds of members: the CSR's
+// tidy, which hands every list above 32 entries to its vertex's whole block, one after the other, would run them on a handful of
+// blocks.  Here thread i is first VERTEX i: the member of a list of up to MO_LDS_MAX entries counts the entries below its own id —
+// its place — and writes itself there in `sorted` (ids are distinct; one thread per member, the reads of a list shared by its
+// members).  Then it is CLUSTER i: a longer list is queued, and the block sorts its queue in place in the raw list with the bitonic
+// network of the CSR's tidy.  The two touch different lists.  mo_members() below picks the array by the length.
+__global__ __launch_bounds__(256) void mesh_simp_order_kernel(const int32_t* __restrict__ counts, const int32_t* __restrict__ header,
+                                                              uint32_t cap_v, MoSimp w, MoCsr c) {
+    __shared__ uint32_t s_queue[256];
+    __shared__ uint32_t s_nq;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (threadIdx.x == 0) s_nq = 0u;
+    __syncthreads();
+    if (i < mo_count(counts, 0, cap_v)) {
+        const int32_t cid = w.vcid[i];
+        if (cid >= 0) {
+            const size_t start = mo_start(c, (uint32_t)cid);
+            const uint32_t n = (uint32_t)(mo_start(c, (uint32_t)cid + 1u) - start);
+            if (n <= (uint32_t)MO_LDS_MAX) {
+                const int32_t* a = c.adj + start;
+                uint32_t below = 0u;
+                for (uint32_t j = 0; j < n; j++) below += a[j] < (int32_t)i ? 1u : 0u;
+                w.sorted[start + below] = (int32_t)i;
+            }
+        }
+    }
+    if (i < mo_count(header, 0, cap_v) && (uint32_t)(mo_start(c, i + 1u) - mo_start(c, i)) > (uint32_t)MO_LDS_MAX) s_queue[atomicAdd(&s_nq, 1u)] = i;
+    __syncthreads();
+    const uint32_t nq = s_nq;
+    for (uint32_t q = 0; q < nq; q++) {
+        const size_t start = mo_start(c, s_queue[q]);
+        mo_block_sort(c.adj + start, (uint32_t)(mo_start(c, s_queue[q] + 1u) - start));  // (every stage ends in a barrier)
+    }
+}
+
+// cluster k's members, ascending, and their number
+__device__ __forceinline__ const int32_t* mo_members(const MoSimp& w, const MoCsr& c, uint32_t k, uint32_t& n) {
+    const size_t start = mo_start(c, k);
+    n = (uint32_t)(mo_start(c, k + 1u) - start);
+    return (n <= (uint32_t)MO_LDS_MAX ? w.sorted : c.adj) + start;
+}
+
+// one thread per written cluster: S = 0, S = S + (double)x over the members in ascending id, (float)(S / n); one member: copied
+__global__ __launch_bounds__(256) void mesh_simp_average_kernel(const float* __restrict__ vertices, const float* __restrict__ colors,
+                                                                const int32_t* __restrict__ header, uint32_t cap_v, MoSimp w, MoCsr c,
+                                                                float* __restrict__ out_vertices, float* __restrict__ out_colors) {
+#pragma clang fp contract(off)
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= mo_count(header, 0, cap_v)) return;
+    uint32_t n;
+    const int32_t* a = mo_members(w, c, k, n);
+    if (n == 1u) {
+        const size_t m = (size_t)a[0];
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            out_vertices[3 * (size_t)k + j] = vertices[3 * m + j];
+            if (colors != nullptr) out_colors[3 * (size_t)k + j] = colors[3 * m + j];
+        }
+        return;
+    }
+    double S[3] = {0.0, 0.0, 0.0}, C[3] = {0.0, 0.0, 0.0};
+    for (uint32_t i = 0; i < n; i++) {
+        const size_t m = (size_t)a[i];
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            S[j] = S[j] + (double)vertices[3 * m + j];
+            if (colors != nullptr) C[j] = C[j] + (double)colors[3 * m + j];
+        }
+    }
+    const double dn = (double)n;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        out_vertices[3 * (size_t)k + j] = (float)(S[j] / dn);
+        if (colors != nullptr) out_colors[3 * (size_t)k + j] = (float)(C[j] / dn);
+    }
+}
+
+// a live face is kept iff its slot holds its own index; the spans' kept counts, scanned by the last block -> header[1], [7]
+__global__ __launch_bounds__(256) void mesh_simp_keep_kernel(const int32_t* __restrict__ counts, uint32_t cap_f, MoSimp w,
+                                                             int32_t* __restrict__ header) {
+    __shared__ uint32_t s_wave[4];
+    __shared__ int s_last;
+    const uint32_t F = mo_count(counts, 1, cap_f);
+    uint32_t run = 0u;
+    for (uint32_t chunk = 0; chunk < (uint32_t)MO_CHUNKS; chunk++) {
+        const uint32_t f = (blockIdx.x * (uint32_t)MO_CHUNKS + chunk) * 256u + threadIdx.x;
+        uint32_t keep = 0u;
+        if (f < F) {
+            const int32_t s = w.fslot[f];
+            keep = (s >= 0 && w.ftab[s] == (int32_t)f) ? 1u : 0u;
+        }
+        uint32_t total;
+        dqo_block_exclusive<uint32_t>(keep, total, s_wave);
+        run += total;
+    }
+    if (threadIdx.x == 0) __hip_atomic_store(&w.fspan[blockIdx.x], run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!dqo_last_block(w.head, &s_last)) return;
+    const uint32_t kept = dqo_scan_block_counts<uint32_t, 4>(w.fspan, gridDim.x, 1, s_wave);
+    if (threadIdx.x == 0) {
+        header[1] = (int32_t)kept;
+        header[7] = (int32_t)(F - (uint32_t)header[4] - (uint32_t)header[5] - (uint32_t)header[6] - kept);  // live faces that are not kept
+    }
+}
+
+__global__ __launch_bounds__(256) void mesh_simp_scatter_kernel(const int32_t* __restrict__ counts, uint32_t cap_f, MoSimp w,
+                                                                int32_t* __restrict__ out_faces) {
+    __shared__ uint32_t s_wave[4];
+    const uint32_t F = mo_count(counts, 1, cap_f);
+    uint32_t run = w.fspan[blockIdx.x];
+    for (uint32_t chunk = 0; chunk < (uint32_t)MO_CHUNKS; chunk++) {
+        const uint32_t f = (blockIdx.x * (uint32_t)MO_CHUNKS + chunk) * 256u + threadIdx.x;
+        uint32_t keep = 0u;
+        if (f < F) {
+            const int32_t s = w.fslot[f];
+            keep = (s >= 0 && w.ftab[s] == (int32_t)f) ? 1u : 0u;
+        }
+        uint32_t total;
+        const uint32_t before = dqo_block_exclusive<uint32_t>(keep, total, s_wave);
+        if (keep != 0u) {
+            const size_t o = (size_t)run + before;  // (<= f)
+#pragma unroll
+            for (int j = 0; j < 3; j++) out_faces[3 * o + j] = w.vcid[w.ftri[3 * (size_t)f + j]];  // (a representative is a member of its cluster)
+        }
+        run += total;
+    }
+}
+
 inline bool mo_caps_ok(int64_t cap_v, int64_t cap_f) { return cap_v >= 1 && cap_f >= 1 && cap_v < MO_MAX && cap_f < MO_MAX; }
+
+// the simplification's workspace: the ticket words, MoSimp's arrays in the order of the struct, then the members' CSR (deg, off, span, adj)
+inline size_t mo_simp_ws_bytes(size_t cv, size_t cf) {
+    return DQO_REDUCE_HEAD_WORDS * 4 + dqo_align_up((size_t)mo_slots((uint32_t)cv) * 4, 256) + 5 * dqo_align_up(cv * 4, 256) +
+           dqo_align_up((size_t)mo_slots((uint32_t)cf) * 4, 256) + dqo_align_up(cf * 4, 256) + dqo_align_up(cf * 12, 256) +
+           dqo_align_up(mo_spans(cv) * sizeof(u64), 256) + dqo_align_up(mo_spans(cf) * 4, 256) + 2 * dqo_align_up((cv + 1) * 4, 256) +
+           dqo_align_up(mo_spans(cv + 1) * 4, 256) + dqo_align_up(cv * 4, 256);
+}
 
 inline size_t mo_comp_ws_bytes(size_t cv, size_t cf) {
     return DQO_REDUCE_HEAD_WORDS * 4 + 3 * dqo_align_up(cv * 4, 256) + dqo_align_up(cf * 4, 256) + dqo_align_up(cf, 256) +
@@ -651,6 +1031,68 @@ DQO_API size_t dqo_mesh_smooth_workspace_bytes(int32_t cap_vertices, int32_t cap
 
 DQO_API size_t dqo_mesh_normals_workspace_bytes(int32_t cap_vertices, int32_t cap_faces) {
     return mo_caps_ok(cap_vertices, cap_faces) ? mo_csr_bytes((size_t)cap_vertices, (size_t)cap_faces, 3) : 0;
+}
+
+DQO_API size_t dqo_mesh_simplify_workspace_bytes(int32_t cap_vertices, int32_t cap_faces) {
+    return mo_caps_ok(cap_vertices, cap_faces) ? mo_simp_ws_bytes((size_t)cap_vertices, (size_t)cap_faces) : 0;
+}
+
+DQO_API int dqo_mesh_simplify(const float* vertices, const float* colors, const int32_t* faces, const int32_t* counts, int32_t cap_vertices,
+                              int32_t cap_faces, double voxel_size, double origin_x, double origin_y, double origin_z, float* out_vertices,
+                              float* out_colors, int32_t* out_faces, int32_t out_cap_vertices, int32_t out_cap_faces, int32_t* header,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    DQO_MESH_CHECK_CAPS(cap_vertices, cap_faces);
+    DQO_CHECK_ARG(vertices && faces && header, "null mesh buffer / header");
+    DQO_CHECK_ARG(voxel_size - voxel_size == 0.0 && voxel_size > 0.0, "bad voxel_size: it is finite and above 0");
+    DQO_CHECK_ARG(origin_x - origin_x == 0.0 && origin_y - origin_y == 0.0 && origin_z - origin_z == 0.0, "bad origin: it is finite");
+    DQO_CHECK_ARG(out_cap_vertices >= cap_vertices && out_cap_faces >= cap_faces,
+                  "out capacity (%d vertices, %d faces) below the input's (%d, %d)", out_cap_vertices, out_cap_faces, cap_vertices, cap_faces);
+    DQO_CHECK_ARG(out_vertices && out_faces && (colors == nullptr || out_colors), "null out mesh buffer");
+    DQO_CHECK_ARG(out_vertices != vertices && out_faces != faces && (colors == nullptr || out_colors != colors),
+                  "the out mesh must not be the input mesh");
+    DQO_CHECK_ARG(header != counts, "header must not be the input's counts: the first launch clears it before the counts are read");
+    const size_t cv = (size_t)cap_vertices, cf = (size_t)cap_faces;
+    DQO_CHECK_WS("mesh simplify", workspace, workspace_bytes, mo_simp_ws_bytes(cv, cf));
+    const uint32_t ucv = (uint32_t)cap_vertices, ucf = (uint32_t)cap_faces;
+    MoSimp w;
+    MoCsr c;
+    char* p = (char*)workspace;
+    w.head = c.head = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
+    w.vtab = (int32_t*)p, p += dqo_align_up((size_t)mo_slots(ucv) * 4, 256);
+    w.vslot = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
+    w.mark = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
+    w.cnum = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
+    w.vcid = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
+    w.sorted = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
+    w.ftab = (int32_t*)p, p += dqo_align_up((size_t)mo_slots(ucf) * 4, 256);
+    w.fslot = (int32_t*)p, p += dqo_align_up(cf * 4, 256);
+    w.ftri = (int32_t*)p, p += dqo_align_up(cf * 12, 256);
+    w.vspan = (u64*)p, p += dqo_align_up(mo_spans(cv) * sizeof(u64), 256);
+    w.fspan = (uint32_t*)p, p += dqo_align_up(mo_spans(cf) * 4, 256);
+    c.deg = (uint32_t*)p, p += dqo_align_up((cv + 1) * 4, 256);
+    c.off = (uint32_t*)p, p += dqo_align_up((cv + 1) * 4, 256);
+    c.span = (uint32_t*)p, p += dqo_align_up(mo_spans(cv + 1) * 4, 256);
+    c.adj = (int32_t*)p;
+    w.voxel = voxel_size, w.org[0] = origin_x, w.org[1] = origin_y, w.org[2] = origin_z;
+    const size_t slots = mo_slots(ucv) > mo_slots(ucf) ? mo_slots(ucv) : mo_slots(ucf);
+    const size_t clear_blocks = mo_blocks(slots) < (size_t)MO_CLEAR_BLOCKS ? mo_blocks(slots) : (size_t)MO_CLEAR_BLOCKS;
+    const dim3 block(256), gv((unsigned)mo_blocks(cv)), gf((unsigned)mo_blocks(cf)), sv((unsigned)mo_spans(cv)), sf((unsigned)mo_spans(cf));
+    hipStream_t s = (hipStream_t)stream;
+    // the segment owners of the CSR are the written clusters: the header's word 0 is its launches' vertex count
+    DQO_LAUNCH("mesh_simp_clear_kernel", mesh_simp_clear_kernel, dim3((unsigned)clear_blocks), block, s, counts, ucv, ucf, w, c.deg, header);
+    DQO_LAUNCH("mesh_simp_cells_kernel", mesh_simp_cells_kernel, gv, block, s, vertices, counts, ucv, w, header);
+    DQO_LAUNCH("mesh_simp_faces_kernel", mesh_simp_faces_kernel, sf, block, s, faces, counts, ucv, ucf, w, header);
+    DQO_LAUNCH("mesh_simp_ftable_kernel", mesh_simp_ftable_kernel, gf, block, s, counts, ucf, w, header);
+    DQO_LAUNCH("mesh_simp_number_kernel", mesh_simp_number_kernel, sv, block, s, counts, ucv, w, header);
+    DQO_LAUNCH("mesh_simp_members_kernel", mesh_simp_members_kernel, gv, block, s, counts, ucv, w, c.deg);
+    DQO_LAUNCH("mesh_csr_scan_kernel", mesh_csr_scan_kernel, dim3((unsigned)mo_spans(cv + 1)), block, s, (const int32_t*)header, ucv, c);
+    DQO_LAUNCH("mesh_simp_fill_kernel", mesh_simp_fill_kernel, gv, block, s, counts, ucv, w, c);
+    DQO_LAUNCH("mesh_simp_order_kernel", mesh_simp_order_kernel, gv, block, s, counts, (const int32_t*)header, ucv, w, c);
+    DQO_LAUNCH("mesh_simp_average_kernel", mesh_simp_average_kernel, gv, block, s, vertices, colors, (const int32_t*)header, ucv, w, c,
+               out_vertices, out_colors);
+    DQO_LAUNCH("mesh_simp_keep_kernel", mesh_simp_keep_kernel, sf, block, s, counts, ucf, w, header);
+    DQO_LAUNCH("mesh_simp_scatter_kernel", mesh_simp_scatter_kernel, sf, block, s, counts, ucf, w, out_faces);
+    return DQO_OK;
 }
 
 DQO_API int dqo_mesh_components(const float* vertices, const float* colors, const int32_t* faces, const int32_t* counts, int32_t cap_vertices,

@@ -86,18 +86,19 @@ own (csrc/map_tsdf.hip: a dense grid, the integration rule restated in include/d
     TsdfVolume(origin, voxel_length, dims, sdf_trunc, device)   tsdf, weight, color: public device tensors
         .clear()  .integrate(depth, color, K, w2c, depth_trunc, render_header)  .extract(cap_vertices, cap_faces)  .counts()
 
-FusedMapper.make_mesh(frames, volume) renders and integrates a camera list; dqo_ply.write_mesh_ply writes the mesh.  Sparse volumes and
-mesh simplification are not built.
+FusedMapper.make_mesh(frames, volume) renders and integrates a camera list; dqo_ply.write_mesh_ply writes the mesh.  Sparse volumes are
+not built.
 
 The mesh's clean-up (csrc/map_meshops.hip; the rules in include/dqo_raster.h follow open3d's published algorithms, tests/mesh_ops_oracle.py
 restates them), on the mesh dict extract() returns, nothing read back:
 
     mesh_components(mesh, min_faces, largest_only, ...)   cluster_connected_triangles + remove_triangles_by_mask + remove_unreferenced_vertices
+    mesh_simplify(mesh, voxel_size, origin)               simplify_vertex_clustering, the Average contraction, on a grid the caller places
     mesh_smooth(mesh, iterations, lam, mu, scope)         filter_smooth_laplacian / filter_smooth_taubin (configs' mesh_smooth_iter, mesh_smooth_lambda)
     mesh_normals(mesh)                                    compute_vertex_normals
     mesh_counts(mesh)                                     the one host read
 
-FusedMapper.make_clean_mesh chains them behind make_mesh; dqo_ply.write_mesh_ply_normals writes the result.
+FusedMapper.make_clean_mesh chains them behind make_mesh (make_simplified_mesh: with mesh_simplify); dqo_ply.write_mesh_ply_normals writes the result.
 
 GPU only: there is no CPU path.
 """
@@ -873,6 +874,48 @@ def mesh_components(mesh, min_faces=0, largest_only=False, out=None, want_labels
                                             ov.data_ptr(), N.ptr(oc) if c is not None else None, of.data_ptr(), ocv, ocf, N.ptr(labels),
                                             oh.data_ptr(), ws.data_ptr(), ws.numel(), N.current_stream()))
     out["header_names"] = MESHOPS_HEADER  # (what mesh_counts calls the words)
+    return out
+
+
+MESH_SIMPLIFY_HEADER = ("vertices", "faces", "clusters", "vertices_outside", "faces_bad_index", "faces_outside", "faces_collapsed",
+                        "faces_duplicate")
+
+
+def mesh_simplify(mesh, voxel_size, origin=(0.0, 0.0, 0.0), out=None, workspace_buffer=None):
+    """The mesh with fewer triangles, by vertex clustering — open3d's simplify_vertex_clustering(voxel_size, Average)
+    (include/dqo_raster.h, dqo_mesh_simplify, states the rule: the vertices of a cell of the grid of `voxel_size` at `origin` become
+    one vertex at their average position and colour, summed in double in ascending vertex id; a face two of whose corners share a
+    cell collapses; of the faces that name the same three clusters in the same orientation the first stays; a cluster that no face
+    names any more goes).  The caller places the grid: for a TsdfVolume's mesh, the volume's origin.  mesh: a mesh dict, as for
+    mesh_components — often mesh_components' own output.  Returns a mesh dict in OTHER buffers (`out`, whose capacities must not be
+    below the input's; default: this module's own for the capacities — not mesh_components' —, overwritten by the next call) whose
+    header is the int32 [8] MESH_SIMPLIFY_HEADER, words 0 and 1 the counts, and whose "header_names" names it for mesh_counts.
+    Twelve launches, nothing read back."""
+    v, c, f, h, cv, cf = _mesh(mesh, "mesh_simplify")
+    dev = v.device
+    if out is None:
+        key = ("simplify", _dev_index(dev), cv, cf, c is not None)
+        out = _mesh_outs.get(key)
+        if out is None:
+            out = _mesh_outs[key] = dict(vertices=torch.empty((cv, 3), dtype=torch.float32, device=dev),
+                                         faces=torch.empty((cf, 3), dtype=torch.int32, device=dev),
+                                         header=torch.empty((8,), dtype=torch.int32, device=dev))
+            if c is not None:
+                out["colors"] = torch.empty((cv, 3), dtype=torch.float32, device=dev)
+    if "header" not in out:
+        out["header"] = torch.empty((8,), dtype=torch.int32, device=dev)
+    if c is not None and "colors" not in out:
+        raise RuntimeError("dqo_eval.mesh_simplify: the mesh has colors, out has none")
+    ov, oc, of, oh, ocv, ocf = _mesh(out, "mesh_simplify")
+    if oh.numel() != 8:
+        raise RuntimeError("dqo_eval.mesh_simplify: out['header'] is int32 [8]")
+    ox, oy, oz = (float(x) for x in origin)
+    ws = _mesh_ws("simplify", workspace_buffer, dev, cv, cf)
+    with torch.cuda.device(dev):
+        N.check(N.lib().dqo_mesh_simplify(v.data_ptr(), N.ptr(c), f.data_ptr(), N.ptr(h), cv, cf, float(voxel_size), ox, oy, oz, ov.data_ptr(),
+                                          N.ptr(oc) if c is not None else None, of.data_ptr(), ocv, ocf, oh.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), N.current_stream()))
+    out["header_names"] = MESH_SIMPLIFY_HEADER  # (what mesh_counts calls the words)
     return out
 
 

@@ -330,8 +330,8 @@ class MapOperators:
         pass settings whose opaque_threshold is the one it wants.  The FIRST call for a (P, H, W) sizes the render's context from one
         32-byte header read, exactly as maintain() does; after that a call reads nothing back, allocates nothing and does not
         synchronise.  Returns `volume`; volume.extract(cap_vertices, cap_faces) is the mesh, dqo_ply.write_mesh_ply its file;
-        make_clean_mesh goes on to the cleaned, smoothed mesh with normals.
-        Not built: mesh simplification; NotImplementedError on a sharded mapper (a shard's render shows its objects only, volumes are
+        make_clean_mesh goes on to the cleaned, smoothed mesh with normals, make_simplified_mesh to the same with fewer triangles.
+        NotImplementedError on a sharded mapper (a shard's render shows its objects only, volumes are
         not merged)."""
         self._refuse_sharded("make_mesh")
         H, W = int(self.settings.image_height), int(self.settings.image_width)
@@ -358,11 +358,34 @@ class MapOperators:
         Returns the cleaned mesh dict (vertices, colors, faces, header = dqo_eval.MESHOPS_HEADER, normals), in dqo_eval's own buffers
         for the capacities, overwritten by the next call; dqo_eval.mesh_counts(mesh) reads its counts,
         dqo_ply.write_mesh_ply_normals writes it (cut at the counts).  No host read after the first call of a shape (make_mesh's one
-        header read); NotImplementedError on a sharded mapper, exactly as make_mesh."""
-        self._refuse_sharded("make_clean_mesh")
+        header read); NotImplementedError on a sharded mapper, exactly as make_mesh.  make_simplified_mesh is the same with fewer
+        triangles."""
+        return self._clean_mesh("make_clean_mesh", frames, volume, cap_vertices, cap_faces, depth_trunc, min_component_faces, largest_only,
+                                None, None, smooth_iter, smooth_lambda, smooth_mu, normals)
+
+    @torch.no_grad()
+    def make_simplified_mesh(self, frames, volume, cap_vertices, cap_faces, simplify_voxel, simplify_origin=None, depth_trunc=30.0,
+                             min_component_faces=0, largest_only=False, smooth_iter=0, smooth_lambda=0.5, smooth_mu=None, normals=True):
+        """make_clean_mesh with fewer triangles: extract -> mesh_components -> dqo_eval.mesh_simplify(voxel_size=simplify_voxel,
+        origin=simplify_origin, or the volume's origin) -> mesh_smooth -> mesh_normals, the other arguments make_clean_mesh's.
+        Components come first, because clustering would weld a floater to a surface that passes through its cell; smoothing comes
+        after, because clustering leaves the jaggedness that smoothing removes.  simplify_voxel is typically two to four times
+        volume.voxel_length.  Returns the mesh dict of dqo_eval.mesh_simplify (header = dqo_eval.MESH_SIMPLIFY_HEADER) with normals, in
+        dqo_eval's own buffers for the capacities — not make_clean_mesh's.  Nothing is read back; NotImplementedError on a sharded
+        mapper.  A method of its own, not two more keywords of make_clean_mesh, whose parameter list is held as it is."""
+        if simplify_voxel is None:
+            raise ValueError("make_simplified_mesh: simplify_voxel is a cell size in metres (make_clean_mesh is the call without simplification)")
+        return self._clean_mesh("make_simplified_mesh", frames, volume, cap_vertices, cap_faces, depth_trunc, min_component_faces, largest_only,
+                                simplify_voxel, simplify_origin, smooth_iter, smooth_lambda, smooth_mu, normals)
+
+    def _clean_mesh(self, who, frames, volume, cap_vertices, cap_faces, depth_trunc, min_component_faces, largest_only, simplify_voxel,
+                    simplify_origin, smooth_iter, smooth_lambda, smooth_mu, normals):
+        self._refuse_sharded(who)
         self.make_mesh(frames, volume, depth_trunc=depth_trunc)
         with torch.cuda.device(self.device):
             mesh = dqo_eval.mesh_components(volume.extract(cap_vertices, cap_faces), min_faces=min_component_faces, largest_only=largest_only)
+            if simplify_voxel is not None:
+                mesh = dqo_eval.mesh_simplify(mesh, simplify_voxel, origin=volume.origin if simplify_origin is None else simplify_origin)
             dqo_eval.mesh_smooth(mesh, smooth_iter, lam=smooth_lambda, mu=smooth_mu, scope="all")
             if normals:
                 dqo_eval.mesh_normals(mesh)

@@ -1158,7 +1158,7 @@ int dqo_prune_rows(int32_t P, float* xyz, float* opacity_raw, float* scaling_raw
  * workspace: dqo_tsdf_workspace_bytes(nx, ny, nz) bytes (0 for bad dims; 5 bytes per voxel and 12 per 2048 voxels behind the ticket words),
  *   ZERO when first used and then left to dqo_tsdf_extract, which hands it back ready for the next call.
  * Laplacian smoothing (the mesh_smooth_iter / mesh_smooth_lambda keys of configs/Cube_Diorama_base.yaml:45-46, read by nothing in the
- *   reference tree) is dqo_mesh_smooth below.  Not built: hashed or sparse volumes, mesh simplification, merging the volumes of shards. */
+ *   reference tree) is dqo_mesh_smooth below.  Simplification is dqo_mesh_simplify below.  Not built: hashed or sparse volumes, merging the volumes of shards. */
 size_t dqo_tsdf_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
 int dqo_tsdf_clear(int32_t nx, int32_t ny, int32_t nz, float* tsdf, float* weight, float* color, int32_t* header, void* hipStream);
 int dqo_tsdf_integrate(int32_t nx, int32_t ny, int32_t nz, float origin_x, float origin_y, float origin_z, float voxel_length,
@@ -1230,7 +1230,7 @@ int dqo_tsdf_extract(int32_t nx, int32_t ny, int32_t nz, float origin_x, float o
  *
  * workspaces: dqo_mesh_components_workspace_bytes / dqo_mesh_smooth_workspace_bytes / dqo_mesh_normals_workspace_bytes (cap_vertices,
  *   cap_faces): 0 for bad capacities; ZERO when first used and then left to the entry, which hands it back ready for the next call.
- * Not built: edge-based clustering, mesh simplification, hole filling, smoothing of normals. */
+ * Not built: edge-based clustering, hole filling, smoothing of normals; simplification is dqo_mesh_simplify below. */
 #define DQO_MESH_SMOOTH_POSITIONS 0
 #define DQO_MESH_SMOOTH_COLOURS 1
 #define DQO_MESH_SMOOTH_BOTH 2
@@ -1245,6 +1245,52 @@ int dqo_mesh_smooth(float* vertices, float* colors, const int32_t* faces, const 
                     int32_t iterations, double lambda, double mu, int32_t scope, void* workspace, size_t workspace_bytes, void* hipStream);
 int dqo_mesh_normals(const float* vertices, const int32_t* faces, const int32_t* counts, int32_t cap_vertices, int32_t cap_faces,
                      float* normals, void* workspace, size_t workspace_bytes, void* hipStream);
+
+/* dqo_mesh_simplify (ABI 5, symbols-only addition) — the mesh with fewer triangles, by vertex clustering on the device: open3d's
+ * simplify_vertex_clustering(voxel_size, SimplificationContraction::Average).  Marching tetrahedra leave about twice the triangles of
+ * marching cubes, at lattice resolution on flat walls too; a pipeline that reports or shows a mesh decimates it first.  open3d does not
+ * exist on this platform, so THIS text defines the rule (every departure is marked) and tests/mesh_simplify_oracle.py restates it in
+ * numpy; nothing is pinned against the library.  The operand, the counts and the common refusals are those of the three operators above;
+ * csrc/map_meshops.hip lists the launches.  Twelve launches, whatever the data.
+ *     - cells: for vertex v < V and axis a, t_a = ((double)p_a - origin_a) / voxel_size in double, one rounding per operation, none
+ *       contracted; i_a = floor(t_a).  The vertex is IN THE GRID iff the three t_a are finite and 0 <= i_a < 2^21; its cell is
+ *       (i_x, i_y, i_z).  (Departure: open3d puts the grid at the bounding box's minimum minus half a voxel; here the caller gives the
+ *       origin, which costs no reduction and no host read — the caller of a TSDF mesh has the volume's origin.)
+ *     - clusters: a cluster is the set of in-grid vertices of one cell; its representative is its smallest vertex id.
+ *     - faces, classified in this order: not valid — dropped, counted in [4]; names a vertex outside the grid — dropped, [5]; two corners
+ *       share a cluster — collapsed, [6]; otherwise LIVE.  A live face's triple of clusters is rotated so that the smallest comes first
+ *       (the orientation stays, as in open3d).  Among the live faces with the same rotated triple the one with the lowest face index is
+ *       kept, the others are duplicates, [7].  Kept faces keep their input order.
+ *     - output vertices: a cluster is written iff a live face names it; written clusters are numbered densely in ascending representative
+ *       id.  (Departure: open3d keeps a cluster none of whose triangles survive as an unreferenced vertex; here it goes, which is what
+ *       remove_unreferenced_vertices would do next.)
+ *     - position and colour of a written cluster of n members, in double: S = 0; S = S + (double)p_m over the members m in ASCENDING
+ *       vertex id; the result is (float)(S / (double)n) per component; colours the same way.  A cluster of one member is copied bit for
+ *       bit (for every value but -0 and a NaN's payload that is what the formula gives).
+ *   voxel_size, origin_x, origin_y, origin_z: doubles.  Outputs: the out mesh in separate buffers, under dqo_mesh_components' conditions
+ *   (not the input's buffers, capacities not below the input's: nothing can be cut; out_colors is ignored when colors is NULL); header
+ *   int32 [8]: [0] vertices written, [1] faces written (so the header is the next operator's counts), [2] clusters formed, before the
+ *   unreferenced ones go, [3] vertices outside the grid, [4] faces with a bad index, [5] faces with a vertex outside the grid, [6] faces
+ *   collapsed, [7] duplicate faces removed.  valid faces = [1] + [5] + [6] + [7]; [0] <= [2] <= V - [3].
+ *   No device-wide sort: two open-addressed tables (vertex ids keyed by the cell, face indices keyed by the rotated triple; a power of two
+ *   of slots, at least twice the entries; linear probing, every probe loop bounded by the slot count; a compare-and-swap claims an empty
+ *   slot, an occupant with the same key makes it an integer atomic minimum, and a slot's key never changes — so a slot ends at the
+ *   smallest id of its key whatever order the hardware ran in), member lists by the count, scan and fill of dqo_mesh_smooth's CSR build
+ *   with the cluster as the segment's owner, put in ascending order by counting (a member's place is the number of ids below its own;
+ *   lists above 2048 members: a bitonic network), compaction by span counts and a last-block scan.  Integer atomics only: the same bits
+ *   on every run.
+ *   DQO_ERR_INVALID_ARG before any launch also for a NULL header or out buffer, an out buffer that is the input's, a header that is the
+ *   input's counts, an out capacity below the input's, a voxel_size that is not finite or not above 0, an origin that is not finite;
+ *   then DQO_ERR_WORKSPACE.
+ * workspace: dqo_mesh_simplify_workspace_bytes(cap_vertices, cap_faces): 0 for bad capacities; ZERO when first used and then left to the
+ *   entry, which hands it back ready for the next call.
+ * Not built: quadric-error placement of a cluster's vertex, normals carried through (dqo_mesh_normals recomputes them), edge-collapse
+ *   decimation. */
+size_t dqo_mesh_simplify_workspace_bytes(int32_t cap_vertices, int32_t cap_faces);
+int dqo_mesh_simplify(const float* vertices, const float* colors, const int32_t* faces, const int32_t* counts, int32_t cap_vertices,
+                      int32_t cap_faces, double voxel_size, double origin_x, double origin_y, double origin_z, float* out_vertices,
+                      float* out_colors, int32_t* out_faces, int32_t out_cap_vertices, int32_t out_cap_faces, int32_t* header,
+                      void* workspace, size_t workspace_bytes, void* hipStream);
 
 #define DQO_TICKET_WORDS (16 + 16 * 64) /* int32 words behind DqoAdamStep.block_ticket */
 typedef struct DqoAdamStep {

@@ -1,10 +1,14 @@
-"""Times the mesh clean-up (dqo_eval.mesh_components, mesh_smooth, mesh_normals; csrc/map_meshops.hip) on the mesh of
+"""Times the mesh clean-up (dqo_eval.mesh_components, mesh_simplify, mesh_smooth, mesh_normals; csrc/map_meshops.hip) on the mesh of
 tools/profile_tsdf.py's volume — a 256^3 grid of 2 cm voxels, a wall with a sphere in front integrated from `--frames` poses — and the
 extraction of that mesh for scale.  Device events around the calls, warmed up; the library's own per-launch timers give the split of
 each operator's launches.  Next to each measurement stands the least time its compulsory memory traffic allows at the HBM peak
 (8.0 TB/s), from the counts the run itself reports:
     components  faces read five times (prelink, hook, label, fcount, fscatter: 12 bytes each) and written once, vertices read and written once
                 (24 bytes with colours each way), about 40 bytes of workspace a vertex and 15 a face
+    simplify    vertices read by the cell pass (12 bytes, and 12 per probed occupant), again with colours by the average (24), faces read once
+                (12), their rotated triples written and read by the table, keep and scatter passes (12 each time), the two tables
+                cleared and probed (8 bytes a slot, two slots an entry), about 36 bytes of workspace a vertex and 12 a face; at
+                voxel_size = 2 x and 4 x the voxel length, with the counts in and out
     smooth      per step and vertex: 24 bytes read and written, its neighbour list (4 bytes an entry) and a gathered 24 bytes a neighbour
                 (from cache where neighbours share lines); the adjacency build: 12 bytes a face read twice, 24 written, read and rewritten
     normals     the adjacency build (12 bytes a face twice, 12 written, read and rewritten), then 12 bytes a vertex written and, per
@@ -79,6 +83,11 @@ def main():
     cc = dqo_eval.mesh_counts(clean)
     print("components: " + "  ".join(f"{k}={v}" for k, v in cc.items()))
     V2, F2 = cc["vertices"], cc["faces"]
+    for k in (2, 4):  # (before the smoothing, which moves `clean` in place)
+        run = lambda k=k: dqo_eval.mesh_simplify(clean, k * L, origin=vol.origin)
+        report(f"mesh_simplify(voxel_size = {k} x the voxel length)", run, V2 * (12 + 12 + 24 + 16 + 36) + F2 * (12 + 4 * 12 + 16 + 12), 12)
+        sc = dqo_eval.mesh_counts(run())
+        print(f"simplify {k} x: in vertices={V2} faces={F2}  out " + "  ".join(f"{n}={v}" for n, v in sc.items()))
     build = F2 * (24 + 24 * 3)
     step = V2 * (48 + 6 * 4 + 6 * 24 + 48)  # (about six neighbours a vertex)
     report("mesh_smooth(1 step, positions and colours)", lambda: dqo_eval.mesh_smooth(clean, 1, lam=0.5), build + step, 7)
