@@ -120,6 +120,7 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_track_p2p_loss", "dqo_map_lifecycle_workspace_bytes", "dqo_map_lifecycle_vote", "dqo_map_lifecycle_rows",
            "dqo_growth_sample_workspace_bytes", "dqo_growth_sample", "dqo_eval_picture_workspace_bytes", "dqo_eval_picture",
            "dqo_eval_ms_ssim_workspace_bytes", "dqo_eval_ms_ssim",
+           "dqo_eval_lpips_weight_floats", "dqo_eval_lpips_workspace_bytes", "dqo_eval_lpips",
            "dqo_nn1_workspace_bytes", "dqo_nn1", "dqo_eval_pcd_workspace_bytes", "dqo_eval_pcd", "dqo_window_masks_workspace_bytes",
            "dqo_nn1_grouped_workspace_bytes", "dqo_nn1_grouped", "dqo_eval_pcd_grouped_workspace_bytes", "dqo_eval_pcd_grouped", "dqo_map_pack_rows_by_object",
            "dqo_window_masks", "dqo_surfel_densify_workspace_bytes", "dqo_surfel_densify", "dqo_map_pack_workspace_bytes",
@@ -239,6 +240,11 @@ def lib():
         L.dqo_eval_pcd_grouped.argtypes = [c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, P(c_f), c_vp, c_i64, c_i64, c_vp, c_sz, c_vp]
         L.dqo_eval_ms_ssim_workspace_bytes.argtypes = [c_i32, c_i32]
         L.dqo_eval_ms_ssim.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]
+        # map_lpips.hip
+        L.dqo_eval_lpips_weight_floats.restype = c_sz
+        L.dqo_eval_lpips_weight_floats.argtypes = [c_i32]
+        L.dqo_eval_lpips_workspace_bytes.argtypes = [c_i32, c_i32]
+        L.dqo_eval_lpips.argtypes = [c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]
         # map_checkpoint.hip
         L.dqo_map_pack_workspace_bytes.argtypes = [c_i32]
         L.dqo_map_pack_rows.argtypes = [c_i32] * 3 + [c_vp] * 9 + [c_i64, c_vp, c_vp, c_sz, c_vp]

@@ -1,7 +1,7 @@
 // A launch that ends with its own fixed-order reduction: every block stores a partial, every block takes an integer ticket, and the block
 // that takes the launch's LAST ticket folds the partials in block-index order and writes the result.  One launch, no float atomics, the
 // same bits on every run whatever order the blocks ran in, and the ticket words handed back at zero — no zero fill per call, so the entry
-// can be captured in a hipGraph.  Users: map_eval.hip (eval_picture_kernel, eval_pcd_kernel, eval_pcd_grouped_kernel: its own partial lines), map_msssim.hip (msssim_level_kernel), map_lifecycle.hip (the two cloud limits and
+// can be captured in a hipGraph.  Users: map_eval.hip (eval_picture_kernel, eval_pcd_kernel, eval_pcd_grouped_kernel: its own partial lines), map_msssim.hip (msssim_level_kernel), map_lpips.hip (lpips_head_kernel), map_lifecycle.hip (the two cloud limits and
 // the frame's counts), map_prune.hip (prune_rows_kernel: ticket and counts), map_tilemask.hip (window_masks_kernel: ticket only, its last block selects tiles), map_checkpoint.hip (map_pack_count_kernel: its last block scans
 // the blocks' row counts), map_meshsample.hip (mesh_area_kernel: max and counts; mesh_quantise_kernel: its last block scans the blocks'
 // quanta), map_tsdf.hip (tsdf_edges_kernel, tsdf_vertices_kernel: their last blocks scan the spans' vertex and face counts),

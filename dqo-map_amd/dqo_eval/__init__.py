@@ -3,7 +3,8 @@ frame from slam.py:155,184 and from metric.py — without a host round trip per 
 
     eval_picture(render_output, gt_color, gt_depth, min_depth, max_depth)  ->  float32 [8] on the device (ROW)
     ms_ssim(image, gt)                                                     ->  float32 [20] on the device (MS_ROW)
-    eval_picture_dict(row, ms_row=None)                                    ->  the reference's dict (the ONE host read)
+    lpips(image, gt, weights)                                              ->  float32 [8] on the device (LPIPS_ROW)
+    eval_picture_dict(row, ms_row=None, lpips_row=None)                    ->  the reference's dict (the ONE host read)
 
 One HIP launch (libdqoraster.so: dqo_eval_picture, csrc/map_eval.hip) forms psnr (eval.py:63), the colour L1 (:70) and the depth
 statements (:115-126) from double sums added in a fixed order: a row is bitwise reproducible.  The SSIM slot is filled by
@@ -16,10 +17,15 @@ into a row of its own, and eval_picture_dict(row, ms_row) reports it under "ssim
 kernels follow the algorithm as its published source states it (tests/msssim_oracle.py restates it), and are held to that restatement,
 not to a value recorded from the library.
 
-What is NOT here: the reference also reports LPIPS (`lpips` AlexNet, :65-68).  Its weights do not exist on this platform, so the value
-cannot be pinned against its source and is not built: there is no "lpips" key.  Slot 4 of ROW stays the SINGLE-SCALE SSIM of
-utils/loss_utils.py:60-100 (the one the mapping loss uses).  The picture dumps (`save_picture`) and the semantic / instance branches are
-not part of this either.
+The reference's third number, "lpips" (`lpips` AlexNet through torchmetrics, :28-30, :65-68), is `lpips` (libdqoraster.so: dqo_eval_lpips,
+csrc/map_lpips.hip — five convolutions on the f32 matrix cores, two pools, five heads, nothing read back) on weights the CALLER brings
+as a LpipsWeights: none are shipped and nothing is fetched, so the number is the reference's only on the reference's weights.  Its row
+holds the five layer terms beside the value, and eval_picture_dict(row, ms_row, lpips_row) reports it under "lpips".  Neither `lpips`
+nor `torchmetrics` exists on this platform: the kernels follow the algorithm as the published sources state it (tests/lpips_oracle.py
+restates it) and are held to that restatement on seeded random weights of the real shapes, not to a value recorded from the libraries.
+
+What is NOT here: slot 4 of ROW stays the SINGLE-SCALE SSIM of utils/loss_utils.py:60-100 (the one the mapping loss uses).  The picture
+dumps (`save_picture`) and the semantic / instance branches are not built.
 
 Geometry evaluation — eval_pcd, SLAM/eval.py:190-282: accuracy, completion, chamfer distance and precision / recall / F1 per distance
 threshold of a reconstruction against a ground-truth point set — stays on the device as well:
@@ -167,8 +173,8 @@ def eval_picture(render_output, gt_color, gt_depth, min_depth, max_depth, out=No
     valid depth pixel depth_loss = NaN: the reference's values.  ssim=False leaves slot 4 alone (NaN in a new row).
 
     Slot 4 is the single-scale SSIM of utils/loss_utils.py:60-100 (dqo_map_ssim_fwd_bwd, value only).  The reference's `ssim` key is
-    MS-SSIM (pytorch_msssim's `ms_ssim`): that is ms_ssim()'s row, which eval_picture_dict takes as `ms_row`.  LPIPS is not built (no
-    AlexNet weights here).
+    MS-SSIM (pytorch_msssim's `ms_ssim`): that is ms_ssim()'s row, which eval_picture_dict takes as `ms_row`.  LPIPS is lpips()'s row
+    (`lpips_row`), on weights the caller brings.
 
     workspace_buffer: a tensor of workspace(W, H, device) the caller keeps (default: one per device and image size, kept by this
     module — calls that share it must be on one stream).  render_header: the geometry buffer of the forward that rendered the frame
@@ -247,26 +253,156 @@ def ms_ssim(image, gt, out=None, row=0, *, workspace_buffer=None, render_header=
     return out[int(row)]
 
 
-def eval_picture_dict(row_tensor, ms_row=None):
+LPIPS_ROW = ("lpips", "d0", "d1", "d2", "d3", "d4", "unused6", "unused7")
+LPIPS_MIN_SIDE = 31  # every AlexNet map needs a pixel
+LPIPS_NET = ((3, 64, 11, 4, 2), (64, 192, 5, 1, 2), (192, 384, 3, 1, 1), (384, 256, 3, 1, 1), (256, 256, 3, 1, 1))  # Cin, Cout, kernel, stride, pad
+LPIPS_NORMS = {"torchmetrics": 0, "lpips": 1}  # DQO_LPIPS_NORM_*
+_LPIPS_FEATURES_OFFSET = 4608  # DQO_LPIPS_FEATURES_OFFSET
+
+
+def lpips_sizes(W, H):
+    """The sides ((h0, w0), .., (h4, w4)) of the five feature maps of an H x W image: h0 = (H - 7) // 4 + 1 (11-tap, stride 4, pad 2),
+    h1 = (h0 - 3) // 2 + 1, h2 = h3 = h4 = (h1 - 3) // 2 + 1 (the two 3 / 2 max-pools, floor mode; the other convolutions keep the side)."""
+    def side(n):
+        a = (int(n) - 7) // 4 + 1
+        b = (a - 3) // 2 + 1
+        c = (b - 3) // 2 + 1
+        return a, b, c, c, c
+    return tuple(zip(side(H), side(W)))
+
+
+class LpipsWeights:
+    """The weights of LPIPS' AlexNet, which the CALLER brings (nothing is shipped or fetched), packed once into the one buffer
+    dqo_eval_lpips reads (include/dqo_raster.h states the layout): per layer W[k][co] with k = (kh * KW + kw) * Cin + ci — the k order is
+    the accumulation order of a convolution output — then bias[Cout], then lin[Cout].
+
+    conv_w: five [Cout,Cin,k,k] tensors (LPIPS_NET: 3 -> 64 k 11, 64 -> 192 k 5, 192 -> 384 k 3, 384 -> 256 k 3, 256 -> 256 k 3), conv_b: five
+    [Cout] biases, lin: five [Cout] (or [1,Cout,1,1]) vectors of the linear heads.  Any other shape raises RuntimeError.  The packing is
+    torch ops on the tensors' own device and not hot; `packed` is the float32 [2 470 848] result on `device`."""
+
+    def __init__(self, conv_w, conv_b, lin, device):
+        if len(conv_w) != 5 or len(conv_b) != 5 or len(lin) != 5:
+            raise RuntimeError("dqo_eval.LpipsWeights: five convolution weights, five biases and five lin vectors")
+        parts = []
+        for l, (cin, cout, k, _, _) in enumerate(LPIPS_NET):
+            w, b, v = conv_w[l], conv_b[l], lin[l]
+            if tuple(w.shape) != (cout, cin, k, k):
+                raise RuntimeError(f"dqo_eval.LpipsWeights: conv_w[{l}] must be [{cout},{cin},{k},{k}], got {tuple(w.shape)}")
+            if tuple(b.shape) != (cout,):
+                raise RuntimeError(f"dqo_eval.LpipsWeights: conv_b[{l}] must be [{cout}], got {tuple(b.shape)}")
+            if tuple(v.shape) not in ((cout,), (1, cout, 1, 1)):
+                raise RuntimeError(f"dqo_eval.LpipsWeights: lin[{l}] must be [{cout}] or [1,{cout},1,1], got {tuple(v.shape)}")
+            parts += [w.detach().to(torch.float32).permute(2, 3, 1, 0).reshape(-1), b.detach().to(torch.float32).reshape(-1),
+                      v.detach().to(torch.float32).reshape(-1)]
+        self.packed = torch.cat([t.to(device) for t in parts]).contiguous()
+        self.device = self.packed.device
+
+    @classmethod
+    def from_state_dicts(cls, alexnet_state, lin_state, device=None):
+        """From torchvision's AlexNet state dict (`features.{0,3,6,8,10}.{weight,bias}`) and the `lpips` package's linear heads
+        (`lin{0..4}.model.1.weight`, [1,Cout,1,1]): the key names of the published sources.  The tensor constructor is the contract.
+        device None: where the first convolution's weight is."""
+        idx = (0, 3, 6, 8, 10)
+        device = alexnet_state["features.0.weight"].device if device is None else device
+        return cls([alexnet_state[f"features.{i}.weight"] for i in idx], [alexnet_state[f"features.{i}.bias"] for i in idx],
+                   [lin_state[f"lin{l}.model.1.weight"] for l in range(5)], device)
+
+
+def _lpips_bytes(W, H):
+    n = N.lib().dqo_eval_lpips_workspace_bytes(int(W), int(H))
+    if n == 0:
+        raise RuntimeError(f"dqo_eval.lpips: bad image size {W} x {H}: both sides must be at least {LPIPS_MIN_SIDE} (every AlexNet map "
+                           "needs a pixel)")
+    return n
+
+
+def lpips_workspace(W, H, device):
+    """dqo_eval_lpips' workspace at W x H as a uint8 tensor (its ticket words zero when first used, handed back at zero by every call): the
+    five feature maps of both images, the two pooled maps and the reduction's partials."""
+    return torch.zeros((_lpips_bytes(W, H),), dtype=torch.uint8, device=device)
+
+
+def lpips(image, gt, weights, out=None, row=0, *, norm="torchmetrics", workspace_buffer=None, render_header=None):
+    """LPIPS of a rendered image against its target, on the device: the reference's `lpips` (SLAM/eval.py:28-30, :65-68) —
+    LearnedPerceptualImagePatchSimilarity(net_type="alex", normalize=True) of clamp(gt, 0, 1) and clamp(image, 0, 1), a batch of one — on
+    `weights`, a LpipsWeights the caller made from ITS AlexNet and linear heads.  The number is the reference's only on the reference's
+    weights.
+
+    image, gt: [3,H,W] (clamped to [0, 1] in the kernel); both sides at least 31, else RuntimeError before any launch.
+    Returns the float32 [8] device row (names: LPIPS_ROW)
+        0 lpips   1..5 the layer terms d_0 .. d_4 (lpips is their sum)   6, 7 unused (NaN)
+    — a new tensor initialised to NaN, or out[row] of a caller-owned contiguous float32 [K,8] table, whose other rows are not touched.
+    The layer terms are in the row on purpose: an error at one layer shows at that layer.  norm: "torchmetrics" (a / sqrt(1e-8 + sum a^2),
+    what the reference calls) or "lpips" (a / (sqrt(sum a^2) + 1e-10), the `lpips` package's form).  Nothing is read back and the call does
+    not synchronise; a row is bitwise reproducible, symmetric in (image, gt), and the call can be captured in a graph.  The five
+    convolutions run on the f32 matrix cores, an output element one fmaf chain in the packed k order (include/dqo_raster.h states every
+    step).  The algorithm is the one the published sources of `lpips` and `torchmetrics` state; neither package exists on this platform,
+    so no value here was recorded from them (tests/lpips_oracle.py restates the steps).
+
+    workspace_buffer: a tensor of lpips_workspace(W, H, device) the caller keeps (default: one per device and image size, kept by this
+    module — calls that share it must be on one stream); lpips_feature_view reads the maps the call left in it.  render_header: as
+    eval_picture's — a frame that overflowed its context gets a row of NaN.  GPU tensors only: a CPU tensor raises RuntimeError."""
+    if not isinstance(weights, LpipsWeights):
+        raise RuntimeError("dqo_eval.lpips: weights must be a LpipsWeights")
+    N.require_gpu_op((image, weights.packed), gt, out)
+    lib, dev = N.lib(), image.device
+    if weights.packed.device != dev:
+        raise RuntimeError(f"dqo_eval.lpips: the weights are on {weights.packed.device}, the image on {dev}")
+    if norm not in LPIPS_NORMS:
+        raise RuntimeError(f"dqo_eval.lpips: norm must be one of {sorted(LPIPS_NORMS)}, got {norm!r}")
+    H, W = int(image.shape[-2]), int(image.shape[-1])
+    f32 = torch.float32
+    image, gt = _image(image, 3, H, W, f32, "image"), _image(gt, 3, H, W, f32, "gt")
+    if min(H, W) < LPIPS_MIN_SIDE:
+        raise RuntimeError(f"dqo_eval.lpips: image size {W} x {H}: both sides must be at least {LPIPS_MIN_SIDE} (every AlexNet map needs a "
+                           "pixel)")
+    if out is None:
+        out, row = torch.full((1, 8), float("nan"), dtype=f32, device=dev), 0
+    if out.dim() != 2 or out.shape[1] != 8 or out.dtype != f32 or not out.is_contiguous() or not 0 <= int(row) < out.shape[0]:
+        raise RuntimeError("dqo_eval.lpips: out must be a contiguous float32 [K,8] table and row one of its rows")
+    ws = workspace_buffer if workspace_buffer is not None else _workspace(("lpips", _dev_index(dev), W, H), _lpips_bytes(W, H), dev)
+    with torch.cuda.device(dev):
+        N.check(lib.dqo_eval_lpips(W, H, N.ptr(image), N.ptr(gt), N.ptr(weights.packed), LPIPS_NORMS[norm], N.ptr(render_header), out.data_ptr(),
+                                   int(row), ws.data_ptr(), ws.numel(), N.current_stream()))
+    return out[int(row)]
+
+
+def lpips_feature_view(workspace_buffer, W, H, layer):
+    """Feature map `layer` (0..4) the last lpips call left in its workspace: float32 [2,h,w,C], pixel-major, 0 = image, 1 = gt
+    (lpips_sizes; C = LPIPS_NET[layer][1]).  A view, for tests and inspection: the next call overwrites it."""
+    sizes, off = lpips_sizes(W, H), _LPIPS_FEATURES_OFFSET
+    for l in range(int(layer)):
+        off += (4 * 2 * sizes[l][0] * sizes[l][1] * LPIPS_NET[l][1] + 255) // 256 * 256
+    (h, w), C = sizes[int(layer)], LPIPS_NET[int(layer)][1]
+    return workspace_buffer[off:off + 4 * 2 * h * w * C].view(torch.float32).view(2, h, w, C)
+
+
+def eval_picture_dict(row_tensor, ms_row=None, lpips_row=None):
     """The reference's `losses` dict (eval.py:178-185) from a device row — ONE host read.  Keys: valid_pixel_ratio, depth_loss,
-    normal_loss (0, as eval.py:167), psnr, ssim, plus color_loss.  No `lpips` key: not built.
+    normal_loss (0, as eval.py:167), psnr, ssim, plus color_loss.
     ms_row=None: `ssim` is slot 4, the single-scale SSIM (see eval_picture).  With ms_ssim()'s row of the same frame, `ssim` is that
-    row's slot 0 — the reference's quantity — and the single-scale value moves to `ssim_single_scale`.  Two rows that are views of one
-    tensor (one storage, at most 4 096 floats apart) are read in one transfer of the span that holds both; otherwise there are two reads."""
-    if ms_row is None:
+    row's slot 0 — the reference's quantity — and the single-scale value moves to `ssim_single_scale`.  With lpips()'s row of the same
+    frame (lpips_row) the dict gains `lpips`, that row's slot 0; without it there is no such key.  Rows that are views of one tensor
+    (one storage, at most 4 096 floats apart) are read in one transfer of the span that holds them all; otherwise there is one read per row."""
+    if ms_row is None and lpips_row is None:
         v = row_tensor.detach().reshape(-1)[:8].cpu().tolist()
         return {"valid_pixel_ratio": v[3], "depth_loss": v[2], "normal_loss": 0, "psnr": v[0], "ssim": v[4], "color_loss": v[1]}
-    r, m = row_tensor.detach(), ms_row.detach()
-    a, b = r.storage_offset(), m.storage_offset()
-    lo, hi = min(a, b), max(a + 8, b + 1)
-    if (r.dtype == m.dtype == torch.float32 and r.is_contiguous() and m.is_contiguous() and r.numel() >= 8 and hi - lo <= 4096
-            and r.untyped_storage().data_ptr() == m.untyped_storage().data_ptr()):
+    want = [(row_tensor.detach(), 8)] + [(t.detach(), 1) for t in (ms_row, lpips_row) if t is not None]
+    r = want[0][0]
+    lo, hi = min(t.storage_offset() for t, _ in want), max(t.storage_offset() + n for t, n in want)
+    if (all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n
+            and t.untyped_storage().data_ptr() == r.untyped_storage().data_ptr() for t, n in want) and hi - lo <= 4096):
         span = torch.as_strided(r, (hi - lo,), (1,), lo).cpu().tolist()
-        v, ms = span[a - lo:a - lo + 8], span[b - lo]
+        got = [span[t.storage_offset() - lo:t.storage_offset() - lo + n] for t, n in want]
     else:
-        v, ms = r.reshape(-1)[:8].cpu().tolist(), m.reshape(-1)[:1].cpu().tolist()[0]
-    return {"valid_pixel_ratio": v[3], "depth_loss": v[2], "normal_loss": 0, "psnr": v[0], "ssim": ms, "color_loss": v[1],
-            "ssim_single_scale": v[4]}
+        got = [t.reshape(-1)[:n].cpu().tolist() for t, n in want]
+    v = got[0]
+    d = {"valid_pixel_ratio": v[3], "depth_loss": v[2], "normal_loss": 0, "psnr": v[0], "ssim": v[4], "color_loss": v[1]}
+    if ms_row is not None:
+        d["ssim"], d["ssim_single_scale"] = got[1][0], v[4]
+    if lpips_row is not None:
+        d["lpips"] = got[-1][0]
+    return d
 
 
 def _points(t, name):

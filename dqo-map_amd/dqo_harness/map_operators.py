@@ -74,6 +74,7 @@ class MapOperators:
         by a K of the caller's survives a change of P; the rest is _drop_row_sized_operator_state's."""
         self._eval_tables, self._eval_ws = {}, None  # evaluate(): its [K,8] table per K, and dqo_eval's workspace
         self._eval_ms_ws = None  # evaluate_ms_ssim(): dqo_eval.ms_ssim's workspace
+        self._eval_lpips_ws = None  # evaluate_lpips(): dqo_eval.lpips' workspace
         self._mesh_w2c = None  # make_mesh(): the frame's world-to-camera matrix, row major, float32 [4,4] on the device
         self._window_ratios, self._window_ws = {}, None  # refresh_window(): its [K] ratio table per K, dqo_window_masks' workspace
         self._sample_ctx, self.sample_header = None, None  # sample_new(): the sampler's row buffers and workspace; its last header
@@ -276,11 +277,11 @@ class MapOperators:
         call reads nothing back, allocates nothing and does not synchronise.  A frame that outgrows that context leaves a row of NaN; the
         caller checks maintain_overflowed() where it can afford a read (it tells about the LAST frame rendered, and makes the next call
         size a new context).  Slot 4, "ssim", is the single-scale SSIM of utils/loss_utils.py:60-100; the reference's own "ssim", MS-SSIM,
-        comes from evaluate_ms_ssim (the same renders, a second table); its LPIPS is not built (dqo_eval)."""
+        comes from evaluate_ms_ssim (the same renders, a second table), its LPIPS from evaluate_lpips (a third, on weights the caller brings)."""
         return self._evaluate(frames, min_depth, max_depth, out, None)
 
     @torch.no_grad()
-    def evaluate_ms_ssim(self, frames, ms_ssim, min_depth=0.3, max_depth=5.0, out=None):
+    def evaluate_ms_ssim(self, frames, ms_ssim, min_depth=0.3, max_depth=5.0, out=None, _lpips=None):
         """evaluate(frames, min_depth, max_depth, out) that ALSO fills `ms_ssim`, a float32 [K,20] device table (dqo_eval.MS_ROW): row k
         receives the reference's OWN "ssim", MS-SSIM (dqo_eval.ms_ssim, SLAM/eval.py:19-25, :64), of frame k's render — the render
         eval_picture used, no second one, with the same render header; nine launches more per frame.  Returns the [K,8] table, byte for
@@ -294,12 +295,37 @@ class MapOperators:
         if (not torch.is_tensor(ms_ssim) or tuple(ms_ssim.shape) != (K, 20) or ms_ssim.dtype != torch.float32 or not ms_ssim.is_contiguous()
                 or not ms_ssim.is_cuda):
             raise RuntimeError(f"FusedMapper.evaluate_ms_ssim: ms_ssim must be a contiguous float32 [{K},20] device table")
-        return self._evaluate(frames, min_depth, max_depth, out, ms_ssim)
+        return self._evaluate(frames, min_depth, max_depth, out, ms_ssim, _lpips)
 
-    def _evaluate(self, frames, min_depth, max_depth, out, ms_ssim):
+    @torch.no_grad()
+    def evaluate_lpips(self, frames, lpips, weights, ms_ssim=None, min_depth=0.3, max_depth=5.0, out=None):
+        """evaluate(frames, min_depth, max_depth, out) that ALSO fills `lpips`, a float32 [K,8] device table (dqo_eval.LPIPS_ROW): row k
+        receives the reference's "lpips" (dqo_eval.lpips, SLAM/eval.py:28-30, :65-68) of frame k's render — the render eval_picture used,
+        no second one, with the same render header; twelve launches more per frame — on `weights`, a dqo_eval.LpipsWeights the caller made
+        from ITS AlexNet and linear heads (none are shipped: the number is the reference's only on the reference's weights).  ms_ssim: a
+        [K,20] table as evaluate_ms_ssim's, filled as well, or None.  Returns the [K,8] picture table, byte for byte evaluate()'s;
+        dqo_eval.eval_picture_dict(table[k], ms_row=ms_ssim[k], lpips_row=lpips[k]) reports "lpips".  Both image sides must be at least
+        31: RuntimeError before anything is rendered, as for a table of another shape.  The workspace is kept on the mapper; after the
+        first call nothing is allocated or read."""
+        H, W = int(self.settings.image_height), int(self.settings.image_width)
+        if min(H, W) < dqo_eval.LPIPS_MIN_SIDE:
+            raise RuntimeError(f"FusedMapper.evaluate_lpips: both image sides must be at least 31, the mapper's image is {W} x {H}")
+        K = len(frames)
+        if (not torch.is_tensor(lpips) or tuple(lpips.shape) != (K, 8) or lpips.dtype != torch.float32 or not lpips.is_contiguous()
+                or not lpips.is_cuda):
+            raise RuntimeError(f"FusedMapper.evaluate_lpips: lpips must be a contiguous float32 [{K},8] device table")
+        if not isinstance(weights, dqo_eval.LpipsWeights):
+            raise RuntimeError("FusedMapper.evaluate_lpips: weights must be a dqo_eval.LpipsWeights")
+        if ms_ssim is not None:
+            return self.evaluate_ms_ssim(frames, ms_ssim, min_depth, max_depth, out, _lpips=(lpips, weights))
+        return self._evaluate(frames, min_depth, max_depth, out, None, (lpips, weights))
+
+    def _evaluate(self, frames, min_depth, max_depth, out, ms_ssim, lpips=None):
         self._refuse_sharded("evaluate")
         dev = self.device
         H, W = int(self.settings.image_height), int(self.settings.image_width)
+        if lpips is not None and self._eval_lpips_ws is None:
+            self._eval_lpips_ws = dqo_eval.lpips_workspace(W, H, dev)
         if ms_ssim is not None and self._eval_ms_ws is None:
             self._eval_ms_ws = dqo_eval.ms_ssim_workspace(W, H, dev)
         if self._eval_ws is None:
@@ -314,6 +340,8 @@ class MapOperators:
                                       row=k, workspace_buffer=self._eval_ws, render_header=c.geom)
                 if ms_ssim is not None:
                     dqo_eval.ms_ssim(o[0], gt_color, out=ms_ssim, row=k, workspace_buffer=self._eval_ms_ws, render_header=c.geom)
+                if lpips is not None:
+                    dqo_eval.lpips(o[0], gt_color, lpips[1], out=lpips[0], row=k, workspace_buffer=self._eval_lpips_ws, render_header=c.geom)
         return table
 
     @torch.no_grad()

@@ -568,6 +568,46 @@ size_t dqo_eval_ms_ssim_workspace_bytes(int32_t W, int32_t H);
 int dqo_eval_ms_ssim(int32_t W, int32_t H, const float* render, const float* gt_color, const DqoRastHeader* render_header, float* out,
                      int32_t row, void* workspace, size_t workspace_bytes, void* hipStream);
 
+/* dqo_eval_lpips (ABI 5, symbols-only addition) — the "lpips" number of eval_picture (SLAM/eval.py:28-30, :65-68):
+ * LearnedPerceptualImagePatchSimilarity(net_type="alex", normalize=True) of clamp(gt, 0, 1) and clamp(image, 0, 1), a batch of one, on
+ * weights the CALLER brings; nothing read back.  Written from the published sources of `lpips` and `torchmetrics` (neither exists on this
+ * platform: no value was recorded from them; tests/lpips_oracle.py restates the steps).  image, gt: [3, H*W] planes.
+ *   1. per element, float, one rounding per statement: x = clamp(x, 0, 1) (a NaN stays NaN), x = 2 x - 1, s = (x - shift_c) / scale_c,
+ *      shift = (-0.030, -0.088, -0.188), scale = (0.458, 0.448, 0.450).  Padding is zero in s-space.
+ *   2. five maps f_l = relu(conv2d(in_l) + bias_l): (Cin -> Cout, kernel, stride, pad) = (3 -> 64, 11, 4, 2) on s, (64 -> 192, 5, 1, 2) on
+ *      maxpool3/2(f_0), (192 -> 384, 3, 1, 1) on maxpool3/2(f_1), (384 -> 256, 3, 1, 1) on f_2, (256 -> 256, 3, 1, 1) on f_3; the pools
+ *      floor mode, unpadded.  Sides: h0 = (H - 7) / 4 + 1, h1 = (h0 - 3) / 2 + 1, h2 = h3 = h4 = (h1 - 3) / 2 + 1 (integer division), so
+ *      H, W >= 31.  An output element is ONE float accumulator: 0, then fmaf(x_k, w_k, acc) for k = 0 .. K - 1 in the packed order below
+ *      (the f32 MFMA is that chain bit for bit), then + bias, then the ReLU (a NaN stays NaN).
+ *   3. per layer and pixel, double, channels in ascending order: na = a / sqrt(1e-8 + sum a^2) (DQO_LPIPS_NORM_TORCHMETRICS, what the
+ *      reference calls) or na = a / (sqrt(sum a^2) + 1e-10) (DQO_LPIPS_NORM_LPIPS, the `lpips` package); v = sum_c lin_l[c] (na_c - nb_c)^2.
+ *   4. d_l = the mean of v over the layer's pixels: a double sum added in a fixed order (see dqo_eval_picture); lpips = d_0 + .. + d_4 in
+ *      double; each slot rounded once to float.
+ * out + 8 * row receives eight floats: 0 lpips, 1..5 d_0..d_4, 6 and 7 NaN.  Bitwise reproducible, and symmetric in (image, gt).
+ * weights: ONE packed device buffer of dqo_eval_lpips_weight_floats(-1) = 2 470 848 floats (2 468 544 convolution weights, 1 152 biases,
+ *   1 152 lin weights), 16-byte aligned.  Per layer, in order: W[k][co] with k = (kh * KW + kw) * Cin + ci (K = Cin * KH * KW rows of Cout
+ *   floats), then bias[Cout], then lin[Cout].  Float offsets of (W, bias, lin):
+ *     layer 0 (K  363, Cout  64):       0,   23232,   23296        layer 3 (K 3456, Cout 256):  995264, 1880000, 1880256
+ *     layer 1 (K 1600, Cout 192):   23360,  330560,  330752        layer 4 (K 2304, Cout 256): 1880512, 2470336, 2470592
+ *     layer 2 (K 1728, Cout 384):  330944,  994496,  994880
+ *   The k order IS the accumulation order of step 2.
+ * render_header (may be NULL): as dqo_eval_picture's — a frame that overflowed its capacity gets NaN in all eight slots.
+ * dqo_eval_lpips_workspace_bytes returns 0 for a side below 31 or W * H beyond dqo_eval_picture's limit; the call then returns
+ *   DQO_ERR_INVALID_ARG — as for a NULL image, gt, weights or out, weights that are not 16-byte aligned, a negative row or an unknown
+ *   norm_mode — and DQO_ERR_WORKSPACE for a workspace that is too small, all before anything is launched.
+ * workspace: the ticket words ZERO when first used and handed back at zero; nothing else needs initialising.  No allocation, no
+ *   synchronisation, no float atomics; twelve launches (five convolutions, two pools, five heads) on the one stream, capturable in a
+ *   hipGraph.  From byte DQO_LPIPS_FEATURES_OFFSET on it holds f_0 .. f_4 of the last call, pixel-major float [2][h_l][w_l][Cout_l]
+ *   (0: image, 1: gt), each map's bytes rounded up to a multiple of 256; behind them the pooled maps and the reduction's partials.
+ *   Calls that share a workspace must be ordered (one stream). */
+#define DQO_LPIPS_NORM_TORCHMETRICS 0
+#define DQO_LPIPS_NORM_LPIPS 1
+#define DQO_LPIPS_FEATURES_OFFSET 4608
+size_t dqo_eval_lpips_weight_floats(int32_t layer); /* layer 0..4: the floats of that layer's W, bias and lin; any other value: all */
+size_t dqo_eval_lpips_workspace_bytes(int32_t W, int32_t H);
+int dqo_eval_lpips(int32_t W, int32_t H, const float* image, const float* gt, const float* weights, int32_t norm_mode,
+                   const DqoRastHeader* render_header, float* out, int32_t row, void* workspace, size_t workspace_bytes, void* hipStream);
+
 /* Dense exact 1-NN between two large sets (scipy's KDTree(ref).query(query) of SLAM/eval.py:190-226, one million points against one
  * million): dist2[i] = the smallest squared distance from query i to any kept reference, idx[i] (may be NULL) a reference attaining it,
  * in the caller's numbering; which one of several equally distant references is arbitrary.  A pair's distance is dx*dx + dy*dy + dz*dz in
