@@ -6,7 +6,7 @@
 // the blocks' row counts), map_meshsample.hip (mesh_area_kernel: max and counts; mesh_quantise_kernel: its last block scans the blocks'
 // quanta), map_tsdf.hip (tsdf_edges_kernel, tsdf_vertices_kernel: their last blocks scan the spans' vertex and face counts),
 // map_meshops.hip (mesh_comp_stats / _fcount / _vcount_kernel, mesh_csr_scan_kernel, mesh_simp_number / _keep_kernel: span partials folded
-// or scanned), dqo_adam.h
+// or scanned), map_meshcull.hip (mesh_cull_fcount / _vcount_kernel: span pairs scanned, tickets over the spans that have items), dqo_adam.h
 // (ticket only, unfenced).
 //
 // Below the double reductions, the integer ends the map operators share (behind whichever last-block ticket their kernel takes):
@@ -42,9 +42,10 @@ static_assert(DQO_REDUCE_HEAD_WORDS * 4 == DQO_WINDOW_MASKS_SUMS_OFFSET, "the ti
 
 // Takes the block's ticket (ONE thread of the block calls it); true in the block that took the launch's last one.  The words it used are
 // zero again.  No barrier and, by default, no fence: it orders nothing but the tickets themselves.  ORDERED is dqo_last_block's (there).
+// `grid`: the blocks that take a ticket — blocks 0 .. grid - 1 of the launch, every one of them exactly once (the launch's own gridDim.x in
+// the forms without it; fewer where the blocks behind a device-side count leave at once: map_meshsample.hip's counted form, map_meshcull.hip).
 template <bool ORDERED = false>
-__device__ __forceinline__ bool dqo_ticket_take(int32_t* ticket) {
-    const int grid = (int)gridDim.x;
+__device__ __forceinline__ bool dqo_ticket_take(int32_t* ticket, int grid) {
     const int lines = min((int)DQO_REDUCE_LINES, max(1, grid / 16));
     const int l = (int)blockIdx.x % lines;
     const int on_line = (grid - l + lines - 1) / lines;  // blocks b < grid with b % lines == l
@@ -55,6 +56,10 @@ __device__ __forceinline__ bool dqo_ticket_take(int32_t* ticket) {
     if (atomicAdd(ticket, 1) != lines - 1) return false;
     *ticket = 0;
     return true;
+}
+template <bool ORDERED = false>
+__device__ __forceinline__ bool dqo_ticket_take(int32_t* ticket) {
+    return dqo_ticket_take<ORDERED>(ticket, (int)gridDim.x);
 }
 
 // Every thread of every block calls it after the block's last store that the last block is to read; true (for every thread of the block)
@@ -68,17 +73,18 @@ __device__ __forceinline__ bool dqo_ticket_take(int32_t* ticket) {
 //   3. in the last block only thread 0 has read a ticket.  The second barrier hands its answer to the block, and then EVERY thread fences
 //      before it reads: a fence orders the accesses of the thread that executes it and of no other, so thread 0's alone would leave the
 //      other threads' loads of the partials free to be served from before the last ticket was taken.
-__device__ __forceinline__ bool dqo_last_block(int32_t* ticket, int* s_last) {
+__device__ __forceinline__ bool dqo_last_block(int32_t* ticket, int* s_last, int grid) {
     __syncthreads();
     if (threadIdx.x == 0) {
         __threadfence();  // 1
-        *s_last = dqo_ticket_take<true>(ticket);
+        *s_last = dqo_ticket_take<true>(ticket, grid);
     }
     __syncthreads();
     if (!*s_last) return false;
     __threadfence();  // 3
     return true;
 }
+__device__ __forceinline__ bool dqo_last_block(int32_t* ticket, int* s_last) { return dqo_last_block(ticket, s_last, (int)gridDim.x); }
 
 // Exclusive prefix of x over the block's threads in thread order, and the block's total (for every thread): __shfl_up over the wave, the
 // four wave totals through LDS.  T: uint32_t or a 64-bit unsigned.  s_wave: 4 words of LDS; the call starts with a barrier, so the

@@ -67,6 +67,7 @@
 // workspace, a copy back after an odd number of steps), normals one thread per vertex.  Every double statement is the one written,
 // rounded once, none contracted (the Makefile states -ffp-contract=off); sqrt and `/` on doubles are the correctly rounded ones.
 #include "dqo_common.h"
+#include "dqo_mesh_operand.h"
 #include "dqo_reduce.h"
 
 namespace {
@@ -74,32 +75,13 @@ namespace {
 typedef unsigned long long u64;
 
 enum {
-    MO_CHUNKS = 8,        // runs of 256 items that a block of a span launch walks
-    MO_SPAN_SHIFT = 11,   // a span: 2048 consecutive vertices / faces
-    MO_SPAN = 1 << MO_SPAN_SHIFT,
     MO_THREAD_MAX = 32,   // tidy: raw entries a single thread sorts
     MO_LDS_MAX = 2048,    // tidy: raw entries a block sorts in LDS
-    MO_MAX = 1 << 28,     // capacities lie below it: 6 cap_f adjacency entries stay below 2^32
     MO_CLEAR_BLOCKS = 2048,  // simplify: the most blocks of its clearing launch
 };
-static_assert(MO_SPAN == 256 * MO_CHUNKS, "a span is MO_CHUNKS runs of a block");
-
-__host__ __device__ inline size_t mo_blocks(size_t n) { return (n + 255) / 256; }
-__host__ __device__ inline size_t mo_spans(size_t n) { return (n + MO_SPAN - 1) / MO_SPAN; }
-
-__device__ __forceinline__ uint32_t mo_count(const int32_t* counts, int k, uint32_t cap) {
-    if (counts == nullptr) return cap;
-    const int32_t n = counts[k];
-    return n <= 0 ? 0u : ((uint32_t)n < cap ? (uint32_t)n : cap);
-}
 
 __device__ __forceinline__ int32_t mo_ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void mo_st(int32_t* p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ bool mo_face(const int32_t* __restrict__ faces, uint32_t f, uint32_t V, int32_t& a, int32_t& b, int32_t& c) {
-    a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-    return (uint32_t)a < V && (uint32_t)b < V && (uint32_t)c < V;
-}
 
 // ---- components -------------------------------------------------------------------------------------------------------------------------
 struct MoComp {
@@ -335,44 +317,13 @@ __global__ __launch_bounds__(256) void mesh_comp_vcount_kernel(const int32_t* __
 __global__ __launch_bounds__(256) void mesh_comp_vscatter_kernel(const float* __restrict__ vertices, const float* __restrict__ colors,
                                                                  const int32_t* __restrict__ counts, uint32_t cap_v, MoComp w,
                                                                  float* __restrict__ out_vertices, float* __restrict__ out_colors) {
-    __shared__ uint32_t s_wave[4];
-    const uint32_t V = mo_count(counts, 0, cap_v);
-    uint32_t run = (uint32_t)w.vpair[blockIdx.x];  // marked vertices of the spans before this one, then of the span so far
-    for (uint32_t chunk = 0; chunk < (uint32_t)MO_CHUNKS; chunk++) {
-        const uint32_t i = (blockIdx.x * (uint32_t)MO_CHUNKS + chunk) * 256u + threadIdx.x;
-        const uint32_t m = i < V ? (uint32_t)w.mark[i] : 0u;
-        uint32_t total;
-        const uint32_t before = dqo_block_exclusive<uint32_t>(m, total, s_wave);
-        if (m != 0u) {
-            const size_t id = (size_t)run + before;  // (<= i: inside the out buffers, whose capacities are not below the input's)
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                out_vertices[3 * id + c] = vertices[3 * (size_t)i + c];
-                if (colors != nullptr) out_colors[3 * id + c] = colors[3 * (size_t)i + c];
-            }
-            w.mark[i] = (int32_t)id;
-        }
-        run += total;
-    }
+    // (vpair's low word: the marked vertices of the spans before this one)
+    mo_scatter_vertices(vertices, colors, mo_count(counts, 0, cap_v), w.mark, (uint32_t)w.vpair[blockIdx.x], out_vertices, out_colors);
 }
 
 __global__ __launch_bounds__(256) void mesh_comp_fscatter_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ counts,
                                                                  uint32_t cap_f, MoComp w, int32_t* __restrict__ out_faces) {
-    __shared__ uint32_t s_wave[4];
-    const uint32_t F = mo_count(counts, 1, cap_f);
-    uint32_t run = w.fblock[blockIdx.x];
-    for (uint32_t chunk = 0; chunk < (uint32_t)MO_CHUNKS; chunk++) {
-        const uint32_t f = (blockIdx.x * (uint32_t)MO_CHUNKS + chunk) * 256u + threadIdx.x;
-        const uint32_t k = f < F ? (uint32_t)w.keep[f] : 0u;
-        uint32_t total;
-        const uint32_t before = dqo_block_exclusive<uint32_t>(k, total, s_wave);
-        if (k != 0u) {
-            const size_t o = (size_t)run + before;  // (<= f)
-#pragma unroll
-            for (int c = 0; c < 3; c++) out_faces[3 * o + c] = w.mark[faces[3 * (size_t)f + c]];
-        }
-        run += total;
-    }
+    mo_scatter_faces(faces, mo_count(counts, 1, cap_f), w.keep, w.mark, w.fblock[blockIdx.x], out_faces);
 }
 
 // ---- the CSR of a vertex's neighbours (NBR) or of its corners' faces ----------------------------------------------------------------------
@@ -970,8 +921,6 @@ __global__ __launch_bounds__(256) void mesh_simp_scatter_kernel(const int32_t* _
     }
 }
 
-inline bool mo_caps_ok(int64_t cap_v, int64_t cap_f) { return cap_v >= 1 && cap_f >= 1 && cap_v < MO_MAX && cap_f < MO_MAX; }
-
 // the simplification's workspace: the ticket words, MoSimp's arrays in the order of the struct, then the members' CSR (deg, off, span, adj)
 inline size_t mo_simp_ws_bytes(size_t cv, size_t cf) {
     return DQO_REDUCE_HEAD_WORDS * 4 + dqo_align_up((size_t)mo_slots((uint32_t)cv) * 4, 256) + 5 * dqo_align_up(cv * 4, 256) +
@@ -1013,9 +962,6 @@ int mo_build_csr(const int32_t* faces, const int32_t* counts, uint32_t cv, uint3
 }
 
 }  // namespace
-
-#define DQO_MESH_CHECK_CAPS(cv, cf) \
-    DQO_CHECK_ARG(mo_caps_ok(cv, cf), "bad capacity: %d vertices, %d faces: both are at least 1 and below 2^28", cv, cf)
 
 // ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
 extern "C" {

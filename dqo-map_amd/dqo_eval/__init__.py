@@ -1109,3 +1109,131 @@ def mesh_counts(mesh):
         return dict(vertices=int(mesh["vertices"].shape[0]), faces=int(mesh["faces"].shape[0]))
     names = mesh.get("header_names", TSDF_HEADER[:4])
     return {n: int(x) for n, x in zip(names, h.cpu().tolist())}
+
+
+# ---- mesh evaluation: cull to the views, sample by count, compare (csrc/map_meshcull.hip, map_meshsample.hip) ------------------------------
+MESH_CULL_HEADER = ("vertices", "faces", "vertices_seen", "views_used", "faces_bad_index", "faces_removed", "vertices_removed", "zero")
+
+
+def _own_mesh_out(tag, dev, cv, cf, colors):
+    """This module's own out mesh of one operator (`tag`) for a device and capacities, made on first use."""
+    key = (tag, _dev_index(dev), cv, cf, colors)
+    out = _mesh_outs.get(key)
+    if out is None:
+        out = _mesh_outs[key] = dict(vertices=torch.empty((cv, 3), dtype=torch.float32, device=dev),
+                                     faces=torch.empty((cf, 3), dtype=torch.int32, device=dev),
+                                     header=torch.empty((8,), dtype=torch.int32, device=dev))
+        if colors:
+            out["colors"] = torch.empty((cv, 3), dtype=torch.float32, device=dev)
+    return out
+
+
+def mesh_cull(mesh, w2c, K, W, H, depth=None, view_keep=None, eps=0.03, near=0.0, depth_trunc=float("inf"), min_corners=3, out=None,
+              want_views=False, workspace_buffer=None):
+    """The mesh restricted to what the views see — the culling every mesh-evaluation protocol of dense SLAM applies to both meshes
+    before it samples them: frustum, then occlusion against the frames' depth (include/dqo_raster.h, dqo_mesh_cull, states the rule: a
+    vertex is seen by a view iff it lies in front of it beyond `near`, projects into the image by TsdfVolume.integrate's own float32
+    statements and, with `depth`, is not more than `eps` behind the depth of its pixel, which is above 0 and at most depth_trunc; a face
+    is kept iff at least min_corners of its corners are seen by some used view; vertices no kept face names go).
+    mesh: a mesh dict, as for mesh_components.  w2c: float32 device tensor [n,16] or [n,4,4], the views' world-to-camera matrices, row
+    major; K: (fx, fy, cx, cy) or a 3 x 3 matrix, HOST numbers, and W, H: the camera all views share; depth: float32 [n,H,W] device
+    tensor in metres (None: frustum only); view_keep: uint8 / bool [n] device tensor, 0 = the view is not used (None: all are).
+    Returns a mesh dict in OTHER buffers (`out`, whose capacities must not be below the input's; default: this module's own for the
+    capacities, overwritten by the next call) with header = the int32 [8] MESH_CULL_HEADER, words 0 and 1 the counts, "header_names"
+    naming it for mesh_counts, and "vertex_views": with want_views int32 [cap_vertices], how many used views see each vertex (rows
+    behind the count untouched), else None.  dqo_ply.write_mesh_ply writes it once cut at its counts.  Six launches, nothing read
+    back, no synchronise; capturable in a graph."""
+    v, c, f, h, cv, cf = _mesh(mesh, "mesh_cull")
+    dev = v.device
+    N.require_gpu_op((v, w2c), depth, view_keep)
+    if w2c.dtype != torch.float32 or not w2c.is_contiguous() or w2c.numel() % 16 != 0 or w2c.numel() == 0 or w2c.device != dev:
+        raise RuntimeError("dqo_eval.mesh_cull: w2c must be a contiguous float32 [n,16] or [n,4,4] tensor on the mesh's device")
+    n, W, H = w2c.numel() // 16, int(W), int(H)
+    if depth is not None and (tuple(depth.shape) != (n, H, W) or depth.dtype != torch.float32 or not depth.is_contiguous() or depth.device != dev):
+        raise RuntimeError(f"dqo_eval.mesh_cull: depth must be a contiguous float32 [{n},{H},{W}] tensor on the mesh's device")
+    if view_keep is not None:
+        if view_keep.dtype == torch.bool:
+            view_keep = view_keep.view(torch.uint8)
+        if view_keep.dtype != torch.uint8 or view_keep.numel() != n or not view_keep.is_contiguous() or view_keep.device != dev:
+            raise RuntimeError(f"dqo_eval.mesh_cull: view_keep must be a contiguous uint8 / bool [{n}] tensor on the mesh's device")
+    fx, fy, cx, cy = _intrinsics(K)
+    if out is None:
+        out = _own_mesh_out("cull", dev, cv, cf, c is not None)
+    if "header" not in out:
+        out["header"] = torch.empty((8,), dtype=torch.int32, device=dev)
+    if c is not None and "colors" not in out:
+        raise RuntimeError("dqo_eval.mesh_cull: the mesh has colors, out has none")
+    ov, oc, of, oh, ocv, ocf = _mesh(out, "mesh_cull")
+    if oh.numel() != 8:
+        raise RuntimeError("dqo_eval.mesh_cull: out['header'] is int32 [8]")
+    vv = None
+    if want_views:
+        vv = out.get("vertex_views")
+        if vv is None:
+            vv = out.get("_views_buffer")  # (an earlier call's, kept while a call without want_views set the public key to None)
+        if vv is None:
+            vv = out["_views_buffer"] = torch.empty((cv,), dtype=torch.int32, device=dev)
+        if vv.dtype != torch.int32 or vv.numel() < cv or not vv.is_contiguous() or vv.device != dev:
+            raise RuntimeError("dqo_eval.mesh_cull: out['vertex_views'] is a contiguous int32 [cap_vertices] tensor on the mesh's device")
+    ws = _mesh_ws("cull", workspace_buffer, dev, cv, cf)
+    with torch.cuda.device(dev):
+        N.check(N.lib().dqo_mesh_cull(v.data_ptr(), N.ptr(c), f.data_ptr(), N.ptr(h), cv, cf, n, w2c.data_ptr(), N.ptr(view_keep), W, H, fx, fy,
+                                      cx, cy, N.ptr(depth), float(near), float(eps), float(depth_trunc), int(min_corners), ov.data_ptr(),
+                                      N.ptr(oc) if c is not None else None, of.data_ptr(), ocv, ocf, N.ptr(vv), oh.data_ptr(), ws.data_ptr(),
+                                      ws.numel(), N.current_stream()))
+    out["header_names"] = MESH_CULL_HEADER  # (what mesh_counts calls the words)
+    out["vertex_views"] = vv
+    return out
+
+
+def sample_surface_counted(mesh, count, seed=0, want_face_index=False, workspace_buffer=None):
+    """sample_surface on a mesh dict (as for mesh_components: vertices, faces and, when it has one, a header whose words 0 and 1 are
+    the counts — TsdfVolume.extract's, mesh_components', mesh_simplify's, mesh_cull's): the counts stay on the device
+    (dqo_mesh_sample_counted, include/dqo_raster.h).  Every byte of the returned dict — sample_surface's: points, face_index | None,
+    keep, header (MESH_HEADER) — is what sample_surface(vertices[:V], faces[:F], count, seed) gives; a mesh without faces or without
+    area gives keep all 0 (eval_pcd's mask) and no point.  Without a header the capacities are the counts.  The face capacity and count
+    lie in [1, 2^25 - 1].  workspace_buffer: a tensor of mesh_sample_workspace(cap_faces, count, device) the caller keeps (default: one
+    per device and sizes, kept by this module).  Four launches, nothing read back, no synchronise; capturable in a graph."""
+    v, c, f, h, cv, cf = _mesh(mesh, "sample_surface_counted")
+    dev, count = v.device, int(count)
+    nbytes = N.lib().dqo_mesh_sample_counted_workspace_bytes(cf, count)
+    if nbytes == 0:
+        raise RuntimeError(f"dqo_eval.sample_surface_counted: bad sizes: {cf} faces of capacity, count = {count}: each in [1, 2^25 - 1]")
+    if workspace_buffer is not None:
+        N.require_gpu_op(workspace_buffer)
+    ws = workspace_buffer if workspace_buffer is not None else _workspace(("mesh_counted", _dev_index(dev), cf, count), nbytes, dev)
+    points = torch.empty((count, 3), dtype=torch.float32, device=dev)
+    face_index = torch.empty((count,), dtype=torch.int32, device=dev) if want_face_index else None
+    keep = torch.empty((count,), dtype=torch.uint8, device=dev)
+    header = torch.empty((8,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        N.check(N.lib().dqo_mesh_sample_counted(v.data_ptr(), f.data_ptr(), N.ptr(h), cv, cf, count, int(seed) & (2 ** 64 - 1), N.ptr(points),
+                                                N.ptr(face_index), N.ptr(keep), N.ptr(header), ws.data_ptr(), ws.numel(), N.current_stream()))
+    return dict(points=points, face_index=face_index, keep=keep, header=header)
+
+
+def eval_mesh(rec_mesh, gt_mesh, sample_nums=1000000, seed=0, rec_seed=None, dist_thres=(0.03,), transform=None, views=None, out=None, row=0):
+    """How good a reconstructed MESH is against the ground-truth mesh, in one call on the device: both meshes culled to what the
+    cameras saw, both sampled, the two point sets compared — mesh_cull -> sample_surface_counted -> eval_pcd.
+    rec_mesh, gt_mesh: mesh dicts (as for mesh_components; the ground truth of dqo_ply.read_mesh_ply as device tensors, without a
+    header, is one).  views: None (no culling) or a dict of mesh_cull's keywords — w2c, K, W, H and optionally depth, view_keep, eps,
+    near, depth_trunc, min_corners — applied to BOTH meshes, each in its own coordinates, before anything is sampled (so with `views`
+    the two meshes share the cameras' frame); the culled meshes live in buffers of this module's own, one pair per device and
+    capacities.  sample_nums points are drawn on each: gt_mesh with `seed`, rec_mesh with rec_seed (None: seed + 1).  transform:
+    eval_pcd's, applied to the reconstruction's points; dist_thres, out, row: eval_pcd's.
+    Returns the float32 [32] device row (PCD_ROW); nothing is read back and the call does not synchronise.  A side that is empty — no
+    faces, no area, a cull that keeps nothing — gives a row of NaN, eval_pcd's rule.  Without `views`, a gt_mesh without a header yields
+    the very points sample_surface(gt vertices, gt faces, sample_nums, seed) yields."""
+    if views is not None:
+        kw = dict(views)
+        for k in ("out", "want_views", "workspace_buffer"):
+            if k in kw:
+                raise RuntimeError(f"dqo_eval.eval_mesh: views is a dict of mesh_cull's view keywords; {k!r} is eval_mesh's own")
+        meshes = []
+        for tag, m in (("cull_rec", rec_mesh), ("cull_gt", gt_mesh)):
+            v, c, f, h, cv, cf = _mesh(m, "eval_mesh")
+            meshes.append(mesh_cull(m, out=_own_mesh_out(tag, v.device, cv, cf, c is not None), **kw))
+        rec_mesh, gt_mesh = meshes
+    gt = sample_surface_counted(gt_mesh, sample_nums, seed=seed)
+    rec = sample_surface_counted(rec_mesh, sample_nums, seed=int(seed) + 1 if rec_seed is None else rec_seed)
+    return eval_pcd(gt["points"], rec["points"], dist_thres, transform, gt_keep=gt["keep"], rec_keep=rec["keep"], out=out, row=row)

@@ -76,6 +76,7 @@ class MapOperators:
         self._eval_ms_ws = None  # evaluate_ms_ssim(): dqo_eval.ms_ssim's workspace
         self._eval_lpips_ws = None  # evaluate_lpips(): dqo_eval.lpips' workspace
         self._mesh_w2c = None  # make_mesh(): the frame's world-to-camera matrix, row major, float32 [4,4] on the device
+        self._mesh_eval_views = {}  # evaluate_mesh(): per K, the views' w2c [K,16] and, once depths="render" asked for it, depth [K,H,W]
         self._window_ratios, self._window_ws = {}, None  # refresh_window(): its [K] ratio table per K, dqo_window_masks' workspace
         self._sample_ctx, self.sample_header = None, None  # sample_new(): the sampler's row buffers and workspace; its last header
         self._drop_row_sized_operator_state()
@@ -488,6 +489,61 @@ class MapOperators:
         else:
             rec, rec_keep = self._densified_cloud("evaluate_geometry_mesh", None if densify is True else densify)
         return dqo_eval.eval_pcd(gt["points"], rec, dist_thres, transform, gt_keep=gt["keep"], rec_keep=rec_keep, out=out, row=row)
+
+    @torch.no_grad()
+    def evaluate_mesh(self, mesh, gt_vertices, gt_faces, frames=None, depths=None, sample_nums=1000000, seed=0, dist_thres=(0.03,),
+                      transform=None, eps=0.03, min_corners=3, depth_trunc=float("inf"), out=None, row=0):
+        """How good the MESH this mapper produced is against the ground-truth mesh, in one call: dqo_eval.eval_mesh — both meshes
+        culled to what the frames' cameras saw (dqo_eval.mesh_cull), both sampled by their device counts
+        (dqo_eval.sample_surface_counted: gt with `seed`, the reconstruction with seed + 1), the point sets compared (eval_pcd).
+        mesh: a mesh dict — make_mesh's volume.extract(...), make_clean_mesh's or make_simplified_mesh's; gt_vertices [V,3] float32,
+        gt_faces [F,3] int32: device tensors (dqo_ply.read_mesh_ply reads gt_mesh.ply on the host).
+        frames: make_mesh's list of raster settings (None in the list = the mapper's camera), or None = no culling.  From the frames
+        the method forms, on the device, w2c [K,16] — each settings' viewmatrix transposed, as make_mesh does — and takes
+        fx = W / (2 tanfovx), fy = H / (2 tanfovy), cx, cy; the frames must share one image size and one set of intrinsics: ValueError
+        otherwise, before anything is launched.
+        depths: None — frustum test only; "render" — the whole map rendered per frame on maintain()'s context (_maintain_render, as
+        make_mesh does) and its depth copied into a [K,H,W] buffer this mapper keeps: the cull's occlusion test runs against the very
+        pixels that made the mesh (NotImplementedError on a sharded mapper, whose render shows its objects only); a float32 [K,H,W]
+        device tensor — the caller's own depth, for example the sensor's.  eps, min_corners, depth_trunc: mesh_cull's.
+        sample_nums, seed, dist_thres, transform, out, row: eval_mesh's.  Returns the float32 [32] device row (dqo_eval.PCD_ROW;
+        dqo_eval.eval_pcd_dict reads it).  Nothing is read back after the first render of a shape (make_mesh's one header read)."""
+        gt = dict(vertices=gt_vertices, faces=gt_faces)
+        if frames is None:
+            if depths is not None:
+                raise ValueError("FusedMapper.evaluate_mesh: depths belong to frames; frames=None is the evaluation without culling")
+            return dqo_eval.eval_mesh(mesh, gt, sample_nums, seed, dist_thres=dist_thres, transform=transform, out=out, row=row)
+        render = isinstance(depths, str)
+        if render and depths != "render":
+            raise ValueError(f"FusedMapper.evaluate_mesh: depths is None, 'render' or a [K,H,W] device tensor, got {depths!r}")
+        if render:
+            self._refuse_sharded("evaluate_mesh")
+        raw = [self.settings if st is None else st for st in frames]
+        if not raw:
+            raise ValueError("FusedMapper.evaluate_mesh: frames is empty (None is the evaluation without culling)")
+        camera = lambda st: (int(st.image_width), int(st.image_height), float(st.tanfovx), float(st.tanfovy), float(st.cx), float(st.cy))
+        W, H, tfx, tfy, cx, cy = camera(raw[0])
+        for k, st in enumerate(raw):
+            if camera(st) != (W, H, tfx, tfy, cx, cy):
+                raise ValueError(f"FusedMapper.evaluate_mesh: frame {k} has another image size or other intrinsics than frame 0 "
+                                 f"({camera(st)} against {(W, H, tfx, tfy, cx, cy)}): mesh_cull's views share one camera")
+        K = len(raw)
+        with torch.cuda.device(self.device):
+            bufs = self._mesh_eval_views.setdefault((K, H, W), {})
+            if "w2c" not in bufs:
+                bufs["w2c"] = torch.empty((K, 16), dtype=torch.float32, device=self.device)
+            if render and "depth" not in bufs:
+                bufs["depth"] = torch.empty((K, H, W), dtype=torch.float32, device=self.device)
+            if render:
+                self.activate()
+            for k, st in enumerate(raw):
+                st = _normalised_settings(st, self.device)
+                bufs["w2c"][k].view(4, 4).copy_(st.viewmatrix.reshape(4, 4).t())  # (the settings keep the transposed w2c)
+                if render:
+                    bufs["depth"][k].copy_(self._maintain_render(st).out[1].reshape(H, W))
+            views = dict(w2c=bufs["w2c"], K=(W / (2.0 * tfx), H / (2.0 * tfy), cx, cy), W=W, H=H, depth=bufs["depth"] if render else depths,
+                         eps=eps, depth_trunc=depth_trunc, min_corners=min_corners)
+            return dqo_eval.eval_mesh(mesh, gt, sample_nums, seed, dist_thres=dist_thres, transform=transform, views=views, out=out, row=row)
 
     def _object_rows(self, rows, who):
         """int32 [P], a buffer of this mapper's own: gaussian_object where the row is alive and in `rows`, -1 elsewhere — the group

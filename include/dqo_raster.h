@@ -747,6 +747,21 @@ size_t dqo_mesh_sample_workspace_bytes(int32_t F, int32_t count);
 int dqo_mesh_sample(int32_t V, const float* vertices, int32_t F, const int32_t* faces, int32_t count, uint64_t seed, float* points,
                     int32_t* face_index, uint8_t* keep, int32_t* header, void* workspace, size_t workspace_bytes, void* hipStream);
 
+/* dqo_mesh_sample_counted (ABI 5, symbols-only addition) — dqo_mesh_sample on a mesh operand (dqo_mesh_components', below): vertices
+ * float32 [cap_vertices,3], faces int32 [cap_faces,3] and counts, a device pointer to two int32 (V, F; each clamped to [0, capacity];
+ * NULL: the capacities are the counts) — the header of dqo_tsdf_extract, dqo_mesh_components, dqo_mesh_simplify or dqo_mesh_cull fits
+ * directly, so the mesh this library makes is sampled without its counts leaving the device.  The same statements (area, quanta, table,
+ * draw) in the same four launches; bit_length(F) and the exponent e are formed on the device from the count; the workspace,
+ * dqo_mesh_sample_counted_workspace_bytes(cap_faces, count), and the grids are sized from cap_faces and count.
+ * For every counts, every output byte — points, face_index, keep, header words 0-6 — equals dqo_mesh_sample of the sliced mesh
+ * (vertices[:V], faces[:F]).  F == 0, or no area: keep all 0, no point written, header[0] = 0 (the table is never searched).  Rows behind
+ * the counts are never read.  DQO_ERR_INVALID_ARG before anything is launched: a NULL required pointer, cap_vertices outside [1, 2^28),
+ * cap_faces or count outside [1, 2^25 - 1], a header that is the counts; then DQO_ERR_WORKSPACE. */
+size_t dqo_mesh_sample_counted_workspace_bytes(int32_t cap_faces, int32_t count);
+int dqo_mesh_sample_counted(const float* vertices, const int32_t* faces, const int32_t* counts, int32_t cap_vertices, int32_t cap_faces,
+                            int32_t count, uint64_t seed, float* points, int32_t* face_index, uint8_t* keep, int32_t* header, void* workspace,
+                            size_t workspace_bytes, void* hipStream);
+
 /* Batched dual-quadric residual over B independent (object, view) pairs: loss = 1 - IoU(obs, bbox(ellipsoid, P34)),
  * with gradients.  valid[b] = 0 when loss == 1 (the reference skips that Adam step). */
 int dqo_quadric_iou_fwd_bwd(int32_t B, const float* axes, const float* R, const float* center, const float* P34,
@@ -1331,6 +1346,55 @@ int dqo_mesh_simplify(const float* vertices, const float* colors, const int32_t*
                       int32_t cap_faces, double voxel_size, double origin_x, double origin_y, double origin_z, float* out_vertices,
                       float* out_colors, int32_t* out_faces, int32_t out_cap_vertices, int32_t out_cap_faces, int32_t* header,
                       void* workspace, size_t workspace_bytes, void* hipStream);
+
+/* dqo_mesh_cull (ABI 5, symbols-only addition) — a mesh restricted to what K views see: the frustum test and the occlusion test against
+ * the frames' depth that the mesh-evaluation protocols of dense SLAM (the NICE-SLAM lineage) apply to the reconstructed AND the
+ * ground-truth mesh before they sample them, so that neither is charged for surface no camera looked at.  Neither a reference
+ * implementation nor open3d exists on this platform, so THIS text defines the rule and tests/mesh_cull_oracle.py restates it in numpy;
+ * nothing is pinned against a library.  The operand, the counts and the common refusals are those of dqo_mesh_components;
+ * csrc/map_meshcull.hip lists the launches.  Six launches, whatever the data.  Plain arguments, no struct.
+ *   Views: n_views in [1, 65535]; w2c float32 [n_views,16] in DEVICE memory, row major, world to camera (dqo_tsdf_integrate's
+ *   convention), m below; view_keep uint8 [n_views] (may be NULL: every view is USED; otherwise the views with a byte != 0 are); W, H,
+ *   fx, fy, cx, cy: the pinhole camera all views share; depth float32 [n_views,H,W] in metres, device (may be NULL: frustum test
+ *   only); near (finite, >= 0), eps (finite, >= 0), depth_trunc (> 0, may be +inf): host floats.
+ *   Per vertex v < V at (x, y, z) and used view k — float32, one rounding per operation, left to right, none contracted, division
+ *   correctly rounded; the projection is dqo_tsdf_integrate's own statements, so a mesh is culled by exactly the pixels that made it:
+ *       pc_r = ((m[r][0] * x + m[r][1] * y) + m[r][2] * z) + m[r][3]                r = 0, 1, 2
+ *       not seen unless pc_z > near
+ *       u_f = ((pc_x * fx) / pc_z + cx) + 0.5f;  v_f likewise with fy, cy
+ *       not seen unless u_f >= 0.0001f && u_f < (float)W - 0.0001f                  (the same for v_f and H)
+ *       depth == NULL: seen
+ *       else u = (int)u_f;  v = (int)v_f;  d = depth[k][v][u];
+ *            seen iff d > 0 && d <= depth_trunc && pc_z <= d + eps                   (d + eps: one float32 add)
+ *   views(v) = the number of used views that see v.
+ *     - a face is KEPT iff it is valid and at least min_corners (1, 2 or 3) of its corners have views > 0; a repeated index counts once
+ *       per corner.
+ *     - kept faces keep their order; the vertices they reference keep their order and are renumbered densely; positions and colours are
+ *       copied bit for bit (dqo_mesh_components' compaction rules).  A seen vertex that no kept face names is dropped.
+ *   Outputs: the out mesh in separate buffers, under dqo_mesh_components' conditions (not the input's buffers, capacities not below the
+ *   input's: nothing can be cut; out_colors is ignored when colors is NULL); vertex_views (may be NULL) int32 [cap_vertices]: views(v)
+ *   for v < V, rows behind V untouched; header int32 [8]: [0] vertices written, [1] faces written (so the header is the next operator's
+ *   counts), [2] vertices with views > 0, [3] views used, [4] faces with a bad index, [5] faces removed by the rule, [6] vertices
+ *   removed, [7] 0.  F = [1] + [4] + [5] and V = [0] + [6].
+ *   The hot path is V x n_views: a grid over (256 vertices, 32 views); a view's matrix and its used bit are wave-uniform scalar loads,
+ *   the vertex stays in registers, the one per-pair memory access is the gathered depth pixel, and a vertex's count is merged by one
+ *   integer atomic add per chunk of views that saw it (without vertex_views a wave leaves its chunk once all its lanes are seen: no
+ *   output can tell).  Compaction by span counts and a last-block scan.  Integer atomics only: the same bits on every run and under
+ *   any schedule; no memset, no host read, no synchronise — the entry can be captured in a hipGraph.
+ *   DQO_ERR_INVALID_ARG before any launch also for n_views outside [1, 65535], a NULL w2c, W or H below 1 or n_views * H * W not below
+ *   2^40 (the kernel indexes the depth with size_t), a near or eps that is not finite or below 0, a depth_trunc that is not above 0,
+ *   min_corners outside 1..3, a NULL header or out buffer, an out buffer that is the input's, a header that is the input's counts, an
+ *   out capacity below the input's; then DQO_ERR_WORKSPACE.
+ * workspace: dqo_mesh_cull_workspace_bytes(cap_vertices, cap_faces): 0 for bad capacities; ZERO when first used and then left to the
+ *   entry, which hands it back ready for the next call.
+ * Not built: rendering the mesh for a depth-L1 metric, per-view intrinsics or image sizes, triangle-frustum intersection (a large face
+ *   whose corners all fall outside the image is dropped), exact point-to-triangle distances. */
+size_t dqo_mesh_cull_workspace_bytes(int32_t cap_vertices, int32_t cap_faces);
+int dqo_mesh_cull(const float* vertices, const float* colors, const int32_t* faces, const int32_t* counts, int32_t cap_vertices,
+                  int32_t cap_faces, int32_t n_views, const float* w2c, const uint8_t* view_keep, int32_t W, int32_t H, float fx, float fy,
+                  float cx, float cy, const float* depth, float near, float eps, float depth_trunc, int32_t min_corners, float* out_vertices,
+                  float* out_colors, int32_t* out_faces, int32_t out_cap_vertices, int32_t out_cap_faces, int32_t* vertex_views,
+                  int32_t* header, void* workspace, size_t workspace_bytes, void* hipStream);
 
 #define DQO_TICKET_WORDS (16 + 16 * 64) /* int32 words behind DqoAdamStep.block_ticket */
 typedef struct DqoAdamStep {
