@@ -50,6 +50,32 @@ void dqo_set_error(const char* fmt, ...);
 
 static inline size_t dqo_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// A workspace's parts, taken in order from `base` (host only).  Every multi-part buffer has ONE layout function built on this:
+// layout(nullptr, ...).total is the size its *_bytes query reports, layout(ws, ...) gives the pointers, so the two cannot disagree.
+// A null base counts offsets only: every part is nullptr then, and no pointer is formed from it.
+struct DqoCarver {
+    char* base;
+    size_t off = 0;
+    explicit DqoCarver(void* b) : base((char*)b) {}
+    // the next `bytes` exactly (the DQO_REDUCE_HEAD_WORDS * 4 head of a last-block reduction, a fixed state block)
+    template <class T = char>
+    T* take_raw(size_t bytes) {
+        char* r = base != nullptr ? base + off : nullptr;
+        off += bytes;
+        return (T*)r;
+    }
+    // the next part: `bytes` rounded up to 256, so that every part behind an aligned one is aligned
+    template <class T = char>
+    T* take(size_t bytes) { return take_raw<T>(dqo_align_up(bytes, 256)); }
+    size_t total() const { return off; }
+};
+// what a layout function returns where the work struct W travels to the kernels by value and so cannot carry the size itself
+template <class W>
+struct DqoLayout {
+    W w;
+    size_t total;
+};
+
 // The 11-tap Gaussian window of utils/loss_utils.py:41-58 (sigma 1.5), bit for bit the reference's floats; by value into the SSIM kernels
 // (map_ssim.hip, which defines it, and map_msssim.hip)
 struct DqoSsimWindow {
@@ -118,28 +144,23 @@ struct DqoGeomLayout {
 
 static inline DqoGeomLayout dqo_geom_layout(void* base, int64_t P) {
     DqoGeomLayout L;
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) {
-        char* r = p;
-        p += dqo_align_up(bytes, 256);
-        return r;
-    };
-    L.header = (DqoRastHeader*)take(256);
-    L.counters = (uint32_t*)take(256);
-    L.spread = (uint32_t*)take(256 * DQO_SPREAD);
-    L.obj_tap = (unsigned long long*)take(sizeof(unsigned long long) * 4 * DQO_GATE_OBJECTS * DQO_OBJ_SPREAD);  // (directly after spread)
-    L.conic_opacity = (float4*)take(sizeof(float4) * P);
-    L.xy_depth = (float4*)take(sizeof(float4) * P);
-    L.rgb_smax = (float4*)take(sizeof(float4) * P);
-    L.normal_c = (float4*)take(sizeof(float4) * P);
-    L.point_c = (float4*)take(sizeof(float4) * P);
-    L.drgb_dir = (float4*)take(sizeof(float4) * 3 * P);
-    L.rect16 = (uint2*)take(sizeof(uint2) * P);
-    L.tiles_touched = (uint32_t*)take(sizeof(uint32_t) * P);
-    L.slot_base = (uint32_t*)take(sizeof(uint32_t) * P);
-    L.clamped = (uint8_t*)take(P);
-    L.grad_sum = (float4*)take(sizeof(float4) * 4 * P);
-    L.total = (size_t)(p - (char*)base);
+    DqoCarver k(base);
+    L.header = k.take<DqoRastHeader>(256);
+    L.counters = k.take<uint32_t>(256);
+    L.spread = k.take<uint32_t>(256 * DQO_SPREAD);
+    L.obj_tap = k.take<unsigned long long>(sizeof(unsigned long long) * 4 * DQO_GATE_OBJECTS * DQO_OBJ_SPREAD);  // (directly after spread)
+    L.conic_opacity = k.take<float4>(sizeof(float4) * P);
+    L.xy_depth = k.take<float4>(sizeof(float4) * P);
+    L.rgb_smax = k.take<float4>(sizeof(float4) * P);
+    L.normal_c = k.take<float4>(sizeof(float4) * P);
+    L.point_c = k.take<float4>(sizeof(float4) * P);
+    L.drgb_dir = k.take<float4>(sizeof(float4) * 3 * P);
+    L.rect16 = k.take<uint2>(sizeof(uint2) * P);
+    L.tiles_touched = k.take<uint32_t>(sizeof(uint32_t) * P);
+    L.slot_base = k.take<uint32_t>(sizeof(uint32_t) * P);
+    L.clamped = k.take<uint8_t>(P);
+    L.grad_sum = k.take<float4>(sizeof(float4) * 4 * P);
+    L.total = k.total();
     return L;
 }
 
@@ -297,25 +318,20 @@ static inline DqoImageLayout dqo_image_layout(void* base, int W, int H) {
     DqoImageLayout L;
     const size_t gx = (W + DQO_TILE - 1) / DQO_TILE, gy = (H + DQO_TILE - 1) / DQO_TILE;
     const size_t T = gx * gy, HW = (size_t)W * H;
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) {
-        char* r = p;
-        p += dqo_align_up(bytes, 256);
-        return r;
-    };
-    L.tile_count = (uint32_t*)take(4 * T * DQO_TSTRIDE);
-    L.tile_flag = (uint32_t*)take(4 * T);  // directly after tile_count: both are zeroed by one fill
-    L.tile_cursor = (uint32_t*)take(4 * T * DQO_TSTRIDE);
-    L.ranges = (uint2*)take(8 * T);
-    L.walk4 = (uint32_t*)take(16 * T);
-    L.tile_order = (uint32_t*)take(4 * 8 * ((T + 7) / 8));
-    L.slot_info = (uint4*)take(16 * 8 * ((T + 7) / 8));
-    L.final_T = (float*)take(4 * HW);
-    L.n_contrib = (uint32_t*)take(4 * HW);
-    L.hit_pos = (uint32_t*)take(4 * HW);
-    L.long_tiles = (uint32_t*)take(4 * T);
-    L.split_tiles = (uint32_t*)take(4 * T);
-    L.total = (size_t)(p - (char*)base);
+    DqoCarver k(base);
+    L.tile_count = k.take<uint32_t>(4 * T * DQO_TSTRIDE);
+    L.tile_flag = k.take<uint32_t>(4 * T);  // directly after tile_count: both are zeroed by one fill
+    L.tile_cursor = k.take<uint32_t>(4 * T * DQO_TSTRIDE);
+    L.ranges = k.take<uint2>(8 * T);
+    L.walk4 = k.take<uint32_t>(16 * T);
+    L.tile_order = k.take<uint32_t>(4 * 8 * ((T + 7) / 8));
+    L.slot_info = k.take<uint4>(16 * 8 * ((T + 7) / 8));
+    L.final_T = k.take<float>(4 * HW);
+    L.n_contrib = k.take<uint32_t>(4 * HW);
+    L.hit_pos = k.take<uint32_t>(4 * HW);
+    L.long_tiles = k.take<uint32_t>(4 * T);
+    L.split_tiles = k.take<uint32_t>(4 * T);
+    L.total = k.total();
     return L;
 }
 
@@ -344,20 +360,15 @@ static inline int64_t dqo_list_cap(int64_t cap, int W, int H, int bucket) {
 static inline DqoBinLayout dqo_bin_layout(void* base, int64_t cap, int64_t list_cap, int bucket) {
     DqoBinLayout L;
     L.list_cap = list_cap, L.bucket = bucket;
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) {
-        char* r = p;
-        p += dqo_align_up(bytes, 256);
-        return r;
-    };
-    L.recs = (uint4*)take(16 * (size_t)list_cap);
-    L.point_list = (uint32_t*)take(4 * (size_t)list_cap);
-    L.slot_list = (uint32_t*)take(4 * (size_t)list_cap);
-    L.live_q = (uint8_t*)take(4 * (size_t)list_cap);
-    L.slot_info = (uint2*)take(8 * (size_t)cap);
-    L.slot_gid = (uint32_t*)take(4 * (size_t)cap);
-    L.rec_valid = (uint32_t*)take(4 * (size_t)cap);
-    L.total = (size_t)(p - (char*)base);
+    DqoCarver k(base);
+    L.recs = k.take<uint4>(16 * (size_t)list_cap);
+    L.point_list = k.take<uint32_t>(4 * (size_t)list_cap);
+    L.slot_list = k.take<uint32_t>(4 * (size_t)list_cap);
+    L.live_q = k.take<uint8_t>(4 * (size_t)list_cap);
+    L.slot_info = k.take<uint2>(8 * (size_t)cap);
+    L.slot_gid = k.take<uint32_t>(4 * (size_t)cap);
+    L.rec_valid = k.take<uint32_t>(4 * (size_t)cap);
+    L.total = k.total();
     return L;
 }
 

@@ -23,6 +23,15 @@ inline bool mo_caps_ok(int64_t cap_v, int64_t cap_f) { return cap_v >= 1 && cap_
 #define DQO_MESH_CHECK_CAPS(cv, cf) \
     DQO_CHECK_ARG(mo_caps_ok(cv, cf), "bad capacity: %d vertices, %d faces: both are at least 1 and below 2^28", cv, cf)
 
+// the out mesh and the header of dqo_mesh_components, dqo_mesh_simplify and dqo_mesh_cull, under the entries' own argument names
+#define DQO_MESH_CHECK_OUT()                                                                                                                  \
+    DQO_CHECK_ARG(out_cap_vertices >= cap_vertices && out_cap_faces >= cap_faces,                                                             \
+                  "out capacity (%d vertices, %d faces) below the input's (%d, %d)", out_cap_vertices, out_cap_faces, cap_vertices, cap_faces); \
+    DQO_CHECK_ARG(out_vertices && out_faces && (colors == nullptr || out_colors), "null out mesh buffer");                                    \
+    DQO_CHECK_ARG(out_vertices != vertices && out_faces != faces && (colors == nullptr || out_colors != colors),                              \
+                  "the out mesh must not be the input mesh");                                                                                 \
+    DQO_CHECK_ARG(header != counts, "header must not be the input's counts: the first launch clears it before the counts are read")
+
 __device__ __forceinline__ uint32_t mo_count(const int32_t* counts, int k, uint32_t cap) {
     if (counts == nullptr) return cap;
     const int32_t n = counts[k];

@@ -46,21 +46,16 @@ inline int next_pow2(int n) {
 
 inline KnnWs knn_ws(void* base, int P) {
     KnnWs w;
-    char* p = (char*)base;
-    auto take = [&](size_t b) {
-        char* r = p;
-        p += dqo_align_up(b, 256);
-        return r;
-    };
+    DqoCarver k(base);
     const int P2 = next_pow2(P < SORT_RUN ? SORT_RUN : P);
-    w.bbox = (float*)take(32);
-    w.keys = (uint64_t*)take(8 * (size_t)P2);
-    w.sorted = (float4*)take(16 * (size_t)P);
-    w.boxes = (float*)take(32 * (size_t)((P + KNN_BOX - 1) / KNN_BOX));
-    w.sub = (float*)take(32 * (size_t)((P + KNN_SUB - 1) / KNN_SUB));
-    w.hist = (uint32_t*)take(4 * 256 * ((size_t)((P + RDX_BLK - 1) / RDX_BLK) + 1));  // + the 256 row totals behind the table
-    w.groups = (float*)take(32 * (size_t)(((P + KNN_BOX - 1) / KNN_BOX + 63) / 64));
-    w.total = (size_t)(p - (char*)base);
+    w.bbox = k.take<float>(32);
+    w.keys = k.take<uint64_t>(8 * (size_t)P2);
+    w.sorted = k.take<float4>(16 * (size_t)P);
+    w.boxes = k.take<float>(32 * (size_t)((P + KNN_BOX - 1) / KNN_BOX));
+    w.sub = k.take<float>(32 * (size_t)((P + KNN_SUB - 1) / KNN_SUB));
+    w.hist = k.take<uint32_t>(4 * 256 * ((size_t)((P + RDX_BLK - 1) / RDX_BLK) + 1));  // + the 256 row totals behind the table
+    w.groups = k.take<float>(32 * (size_t)(((P + KNN_BOX - 1) / KNN_BOX + 63) / 64));
+    w.total = k.total();
     return w;
 }
 
@@ -811,12 +806,12 @@ struct Nn1Ws {
 };
 inline Nn1Ws nn1_ws(void* base, int Q, int R) {
     Nn1Ws w;
-    char* p = (char*)base;
-    w.r = knn_ws(p, R), p += w.r.total;
-    w.q = knn_ws(p, Q), p += w.q.total;
-    w.txyz = (float*)p, p += dqo_align_up(12 * (size_t)R, 256);
-    w.grp = (int32_t*)p, p += dqo_align_up(4 * (size_t)R, 256);
-    w.total = (size_t)(p - (char*)base);
+    DqoCarver k(base);
+    w.r = knn_ws(k.take_raw(knn_ws(nullptr, R).total), R);  // (a set's layout is one part of its own size)
+    w.q = knn_ws(k.take_raw(knn_ws(nullptr, Q).total), Q);
+    w.txyz = k.take<float>(12 * (size_t)R);
+    w.grp = k.take<int32_t>(4 * (size_t)R);
+    w.total = k.total();
     return w;
 }
 

@@ -36,6 +36,20 @@ struct EvWorkspace {
 
 inline size_t ev_blocks(int64_t HW) { return (size_t)((HW + 256 * EV_PIX - 1) / (256 * EV_PIX)); }
 
+// the head of every workspace of this file: the ticket words | `lines` partial lines of `stride` doubles
+inline EvWorkspace ev_take(DqoCarver& k, size_t lines, size_t stride) {
+    EvWorkspace w;
+    w.ticket = k.take_raw<int32_t>(DQO_REDUCE_HEAD_WORDS * 4);
+    w.partial = k.take<double>(lines * stride * sizeof(double));
+    return w;
+}
+// dqo_eval_picture's workspace: that head alone
+inline DqoLayout<EvWorkspace> ev_ws(void* base, int64_t HW) {
+    DqoCarver k(base);
+    const EvWorkspace w = ev_take(k, ev_blocks(HW), EV_STRIDE);
+    return {w, k.total()};
+}
+
 __global__ __launch_bounds__(256) void eval_picture_kernel(int64_t HW, const float* __restrict__ render, const float* __restrict__ gt_color,
                                                            const float* __restrict__ depth, const float* __restrict__ gt_depth,
                                                            const int32_t* __restrict__ depth_index, float min_depth, float max_depth,
@@ -176,13 +190,12 @@ struct PcWorkspace {
 };
 inline PcWorkspace pc_ws(void* base, int n_gt, int n_rec) {
     PcWorkspace w;
-    char* p = (char*)base;
-    w.ev.ticket = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
-    w.ev.partial = (double*)p, p += dqo_align_up((pc_blocks(n_rec) + pc_blocks(n_gt) + 1) * PC_STRIDE * sizeof(double), 256);
-    w.d2_rec = (float*)p, p += dqo_align_up(4 * (size_t)n_rec, 256);
-    w.d2_gt = (float*)p, p += dqo_align_up(4 * (size_t)n_gt, 256);
-    w.nn1 = p, p += std::max(dqo_nn1_ws_bytes(n_rec, n_gt), dqo_nn1_ws_bytes(n_gt, n_rec));  // the two searches run one after the other
-    w.total = (size_t)(p - (char*)base);
+    DqoCarver k(base);
+    w.ev = ev_take(k, pc_blocks(n_rec) + pc_blocks(n_gt) + 1, PC_STRIDE);
+    w.d2_rec = k.take<float>(4 * (size_t)n_rec);
+    w.d2_gt = k.take<float>(4 * (size_t)n_gt);
+    w.nn1 = k.take_raw(std::max(dqo_nn1_ws_bytes(n_rec, n_gt), dqo_nn1_ws_bytes(n_gt, n_rec)));  // the two searches run one after the other
+    w.total = k.total();
     return w;
 }
 
@@ -289,27 +302,24 @@ struct PcgWorkspace {
 };
 inline PcgWorkspace pcg_ws(void* base, int n_gt, int n_rec) {
     PcgWorkspace w;
-    char* p = (char*)base;
-    w.ev.ticket = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
-    w.ev.partial = (double*)p, p += dqo_align_up((pc_blocks(n_rec) + pc_blocks(n_gt) + 2 * PCG_OBJECTS) * PC_STRIDE * sizeof(double), 256);
-    w.rk_rec = (float2*)p, p += dqo_align_up(8 * (size_t)n_rec, 256);
-    w.rk_gt = (float2*)p, p += dqo_align_up(8 * (size_t)n_gt, 256);
-    w.nn1 = p, p += std::max(dqo_nn1_ws_bytes(n_rec, n_gt), dqo_nn1_ws_bytes(n_gt, n_rec));
-    w.total = (size_t)(p - (char*)base);
+    DqoCarver k(base);
+    w.ev = ev_take(k, pc_blocks(n_rec) + pc_blocks(n_gt) + 2 * PCG_OBJECTS, PC_STRIDE);
+    w.rk_rec = k.take<float2>(8 * (size_t)n_rec);
+    w.rk_gt = k.take<float2>(8 * (size_t)n_gt);
+    w.nn1 = k.take_raw(std::max(dqo_nn1_ws_bytes(n_rec, n_gt), dqo_nn1_ws_bytes(n_gt, n_rec)));
+    w.total = k.total();
     return w;
 }
 
 }  // namespace
 
-static size_t dqo_eval_ws_bytes(int64_t HW) { return DQO_REDUCE_HEAD_WORDS * 4 + dqo_align_up(ev_blocks(HW) * EV_STRIDE * sizeof(double), 256); }
+static size_t dqo_eval_ws_bytes(int64_t HW) { return ev_ws(nullptr, HW).total; }
 
 static int dqo_launch_eval_picture(int W, int H, const float* render, const float* gt_color, const float* depth, const float* gt_depth,
                                    const int32_t* depth_index, float min_depth, float max_depth, const DqoRastHeader* header, float* out_row,
                                    void* ws, hipStream_t s) {
     const int64_t HW = (int64_t)W * H;
-    EvWorkspace w;
-    w.ticket = (int32_t*)ws;
-    w.partial = (double*)((char*)ws + DQO_REDUCE_HEAD_WORDS * 4);
+    const EvWorkspace w = ev_ws(ws, HW).w;
     DQO_LAUNCH("eval_picture_kernel", eval_picture_kernel, dim3((unsigned)ev_blocks(HW)), dim3(256), s, HW, render, gt_color, depth, gt_depth,
                depth_index, min_depth, max_depth, header, w, out_row);
     return DQO_OK;

@@ -85,16 +85,16 @@ struct LpWorkspace {
 
 inline LpWorkspace lp_ws(void* base, int W, int H) {
     LpWorkspace k;
-    char* p = (char*)base;
-    k.ticket = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
-    k.means = (double*)p, p += 256;  // = DQO_LPIPS_FEATURES_OFFSET
+    DqoCarver c(base);
+    k.ticket = c.take_raw<int32_t>(DQO_REDUCE_HEAD_WORDS * 4);
+    k.means = c.take<double>(256);  // = DQO_LPIPS_FEATURES_OFFSET
     k.h[0] = (H - 7) / 4 + 1, k.w[0] = (W - 7) / 4 + 1;
     k.h[1] = (k.h[0] - 3) / 2 + 1, k.w[1] = (k.w[0] - 3) / 2 + 1;
     k.h[2] = k.h[3] = k.h[4] = (k.h[1] - 3) / 2 + 1, k.w[2] = k.w[3] = k.w[4] = (k.w[1] - 3) / 2 + 1;
-    for (int l = 0; l < LP_LAYERS; l++) k.feat[l] = (float*)p, p += dqo_align_up(sizeof(float) * 2 * (size_t)k.h[l] * k.w[l] * LP_NET[l].cout, 256);
-    for (int l = 0; l < 2; l++) k.pooled[l] = (float*)p, p += dqo_align_up(sizeof(float) * 2 * (size_t)k.h[l + 1] * k.w[l + 1] * LP_NET[l].cout, 256);
-    k.partial = (double*)p, p += dqo_align_up((size_t)LP_HEAD_BLOCKS * LP_STRIDE * sizeof(double), 256);
-    k.total = (size_t)(p - (char*)base);
+    for (int l = 0; l < LP_LAYERS; l++) k.feat[l] = c.take<float>(sizeof(float) * 2 * (size_t)k.h[l] * k.w[l] * LP_NET[l].cout);
+    for (int l = 0; l < 2; l++) k.pooled[l] = c.take<float>(sizeof(float) * 2 * (size_t)k.h[l + 1] * k.w[l + 1] * LP_NET[l].cout);
+    k.partial = c.take<double>((size_t)LP_HEAD_BLOCKS * LP_STRIDE * sizeof(double));
+    k.total = c.total();
     return k;
 }
 static_assert(DQO_REDUCE_HEAD_WORDS * 4 + 256 == DQO_LPIPS_FEATURES_OFFSET, "the feature maps' place in the workspace is part of the public header");

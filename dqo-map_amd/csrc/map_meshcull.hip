@@ -209,9 +209,17 @@ __global__ __launch_bounds__(256) void mesh_cull_fscatter_kernel(const int32_t* 
 }
 
 // the ticket words | views | mark | keep | vpair | fpair | the used views' bits
-inline size_t mc_ws_bytes(size_t cv, size_t cf) {
-    return DQO_REDUCE_HEAD_WORDS * 4 + 2 * dqo_align_up(cv * 4, 256) + dqo_align_up(cf, 256) + dqo_align_up(mo_spans(cv) * sizeof(u64), 256) +
-           dqo_align_up(mo_spans(cf) * sizeof(u64), 256) + MC_BITS_BYTES;
+inline DqoLayout<McWork> mc_ws(void* base, size_t cv, size_t cf) {
+    McWork w;
+    DqoCarver k(base);
+    w.head = k.take_raw<int32_t>(DQO_REDUCE_HEAD_WORDS * 4);
+    w.views = k.take<int32_t>(cv * 4);
+    w.mark = k.take<int32_t>(cv * 4);
+    w.keep = k.take<uint8_t>(cf);
+    w.vpair = k.take<u64>(mo_spans(cv) * sizeof(u64));
+    w.fpair = k.take<u64>(mo_spans(cf) * sizeof(u64));
+    w.viewbits = k.take<uint32_t>(MC_BITS_BYTES);
+    return {w, k.total()};
 }
 
 }  // namespace
@@ -220,7 +228,7 @@ inline size_t mc_ws_bytes(size_t cv, size_t cf) {
 extern "C" {
 
 DQO_API size_t dqo_mesh_cull_workspace_bytes(int32_t cap_vertices, int32_t cap_faces) {
-    return mo_caps_ok(cap_vertices, cap_faces) ? mc_ws_bytes((size_t)cap_vertices, (size_t)cap_faces) : 0;
+    return mo_caps_ok(cap_vertices, cap_faces) ? mc_ws(nullptr, (size_t)cap_vertices, (size_t)cap_faces).total : 0;
 }
 
 DQO_API int dqo_mesh_cull(const float* vertices, const float* colors, const int32_t* faces, const int32_t* counts, int32_t cap_vertices,
@@ -238,23 +246,11 @@ DQO_API int dqo_mesh_cull(const float* vertices, const float* colors, const int3
     DQO_CHECK_ARG(eps - eps == 0.0f && eps >= 0.0f, "bad eps: it is finite and at least 0");
     DQO_CHECK_ARG(depth_trunc > 0.0f, "bad depth_trunc: it is above 0 (it may be +inf)");
     DQO_CHECK_ARG(min_corners >= 1 && min_corners <= 3, "bad min_corners %d: 1, 2 or 3", min_corners);
-    DQO_CHECK_ARG(out_cap_vertices >= cap_vertices && out_cap_faces >= cap_faces,
-                  "out capacity (%d vertices, %d faces) below the input's (%d, %d)", out_cap_vertices, out_cap_faces, cap_vertices, cap_faces);
-    DQO_CHECK_ARG(out_vertices && out_faces && (colors == nullptr || out_colors), "null out mesh buffer");
-    DQO_CHECK_ARG(out_vertices != vertices && out_faces != faces && (colors == nullptr || out_colors != colors),
-                  "the out mesh must not be the input mesh");
-    DQO_CHECK_ARG(header != counts, "header must not be the input's counts: the first launch clears it before the counts are read");
+    DQO_MESH_CHECK_OUT();
     const size_t cv = (size_t)cap_vertices, cf = (size_t)cap_faces;
-    DQO_CHECK_WS("mesh cull", workspace, workspace_bytes, mc_ws_bytes(cv, cf));
-    McWork w;
-    char* p = (char*)workspace;
-    w.head = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
-    w.views = vertex_views != nullptr ? vertex_views : (int32_t*)p, p += dqo_align_up(cv * 4, 256);
-    w.mark = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
-    w.keep = (uint8_t*)p, p += dqo_align_up(cf, 256);
-    w.vpair = (u64*)p, p += dqo_align_up(mo_spans(cv) * sizeof(u64), 256);
-    w.fpair = (u64*)p, p += dqo_align_up(mo_spans(cf) * sizeof(u64), 256);
-    w.viewbits = (uint32_t*)p;
+    DQO_CHECK_WS("mesh cull", workspace, workspace_bytes, mc_ws(nullptr, cv, cf).total);
+    McWork w = mc_ws(workspace, cv, cf).w;
+    if (vertex_views != nullptr) w.views = vertex_views;  // (the part is taken all the same: the size does not depend on the option)
     McCamera cam;
     cam.W = W, cam.H = H, cam.fx = fx, cam.fy = fy, cam.cx = cx, cam.cy = cy, cam.near = near, cam.eps = eps, cam.depth_trunc = depth_trunc;
     const uint32_t ucv = (uint32_t)cap_vertices, ucf = (uint32_t)cap_faces, nv = (uint32_t)n_views;

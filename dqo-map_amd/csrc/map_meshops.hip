@@ -921,32 +921,70 @@ __global__ __launch_bounds__(256) void mesh_simp_scatter_kernel(const int32_t* _
     }
 }
 
-// the simplification's workspace: the ticket words, MoSimp's arrays in the order of the struct, then the members' CSR (deg, off, span, adj)
-inline size_t mo_simp_ws_bytes(size_t cv, size_t cf) {
-    return DQO_REDUCE_HEAD_WORDS * 4 + dqo_align_up((size_t)mo_slots((uint32_t)cv) * 4, 256) + 5 * dqo_align_up(cv * 4, 256) +
-           dqo_align_up((size_t)mo_slots((uint32_t)cf) * 4, 256) + dqo_align_up(cf * 4, 256) + dqo_align_up(cf * 12, 256) +
-           dqo_align_up(mo_spans(cv) * sizeof(u64), 256) + dqo_align_up(mo_spans(cf) * 4, 256) + 2 * dqo_align_up((cv + 1) * 4, 256) +
-           dqo_align_up(mo_spans(cv + 1) * 4, 256) + dqo_align_up(cv * 4, 256);
+// the ticket words | parent | size | mark | label | keep | spair | vpair | fblock
+inline DqoLayout<MoComp> mo_comp_ws(void* base, size_t cv, size_t cf) {
+    MoComp w;
+    DqoCarver k(base);
+    w.head = k.take_raw<int32_t>(DQO_REDUCE_HEAD_WORDS * 4);
+    w.parent = k.take<int32_t>(cv * 4);
+    w.size = k.take<int32_t>(cv * 4);
+    w.mark = k.take<int32_t>(cv * 4);
+    w.label = k.take<int32_t>(cf * 4);
+    w.keep = k.take<uint8_t>(cf);
+    w.spair = k.take<u64>(mo_spans(cv) * sizeof(u64));
+    w.vpair = k.take<u64>(mo_spans(cv) * sizeof(u64));
+    w.fblock = k.take<uint32_t>(mo_spans(cf) * 4);
+    return {w, k.total()};
 }
 
-inline size_t mo_comp_ws_bytes(size_t cv, size_t cf) {
-    return DQO_REDUCE_HEAD_WORDS * 4 + 3 * dqo_align_up(cv * 4, 256) + dqo_align_up(cf * 4, 256) + dqo_align_up(cf, 256) +
-           2 * dqo_align_up(mo_spans(cv) * sizeof(u64), 256) + dqo_align_up(mo_spans(cf) * 4, 256);
+// deg | off | span | adj (`entries` of it), from wherever the carver stands; the ticket words are the caller's
+inline MoCsr mo_csr_take(DqoCarver& k, int32_t* head, size_t cv, size_t entries) {
+    MoCsr c;
+    c.head = head;
+    c.deg = k.take<uint32_t>((cv + 1) * 4);
+    c.off = k.take<uint32_t>((cv + 1) * 4);
+    c.span = k.take<uint32_t>(mo_spans(cv + 1) * 4);
+    c.adj = k.take<int32_t>(entries * 4);
+    return c;
 }
 
-inline size_t mo_csr_bytes(size_t cv, size_t cf, size_t per_face) {
-    return DQO_REDUCE_HEAD_WORDS * 4 + 2 * dqo_align_up((cv + 1) * 4, 256) + dqo_align_up(mo_spans(cv + 1) * 4, 256) +
-           dqo_align_up(per_face * cf * 4, 256);
+// smoothing (6 entries a face) and normals (3): the ticket words | the CSR | with `pingpong`, the positions' and the colours' other half
+struct MoCsrWs {
+    MoCsr c;
+    float *other_p, *other_c;
+    size_t total;
+};
+inline MoCsrWs mo_csr_ws(void* base, size_t cv, size_t cf, size_t per_face, bool pingpong) {
+    DqoCarver k(base);
+    int32_t* const head = k.take_raw<int32_t>(DQO_REDUCE_HEAD_WORDS * 4);
+    const MoCsr c = mo_csr_take(k, head, cv, per_face * cf);
+    float* const other_p = pingpong ? k.take<float>(cv * 12) : nullptr;
+    float* const other_c = pingpong ? k.take<float>(cv * 12) : nullptr;
+    return {c, other_p, other_c, k.total()};
 }
 
-inline char* mo_csr_layout(MoCsr& c, void* ws, size_t cv, size_t cf, size_t per_face) {
-    char* p = (char*)ws;
-    c.head = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
-    c.deg = (uint32_t*)p, p += dqo_align_up((cv + 1) * 4, 256);
-    c.off = (uint32_t*)p, p += dqo_align_up((cv + 1) * 4, 256);
-    c.span = (uint32_t*)p, p += dqo_align_up(mo_spans(cv + 1) * 4, 256);
-    c.adj = (int32_t*)p, p += dqo_align_up(per_face * cf * 4, 256);
-    return p;
+// the ticket words | MoSimp's arrays in the order of the struct | the members' CSR, which shares the ticket words (adj: one entry a vertex)
+struct MoSimpWs {
+    MoSimp w;
+    MoCsr c;
+    size_t total;
+};
+inline MoSimpWs mo_simp_ws(void* base, size_t cv, size_t cf) {
+    MoSimp w = {};
+    DqoCarver k(base);
+    w.head = k.take_raw<int32_t>(DQO_REDUCE_HEAD_WORDS * 4);
+    w.vtab = k.take<int32_t>((size_t)mo_slots((uint32_t)cv) * 4);
+    w.vslot = k.take<int32_t>(cv * 4);
+    w.mark = k.take<int32_t>(cv * 4);
+    w.cnum = k.take<int32_t>(cv * 4);
+    w.vcid = k.take<int32_t>(cv * 4);
+    w.sorted = k.take<int32_t>(cv * 4);
+    w.ftab = k.take<int32_t>((size_t)mo_slots((uint32_t)cf) * 4);
+    w.fslot = k.take<int32_t>(cf * 4);
+    w.ftri = k.take<int32_t>(cf * 12);
+    w.vspan = k.take<u64>(mo_spans(cv) * sizeof(u64));
+    w.fspan = k.take<uint32_t>(mo_spans(cf) * 4);
+    return {w, mo_csr_take(k, w.head, cv, cv), k.total()};
 }
 
 // the five launches of the CSR build
@@ -967,20 +1005,19 @@ int mo_build_csr(const int32_t* faces, const int32_t* counts, uint32_t cv, uint3
 extern "C" {
 
 DQO_API size_t dqo_mesh_components_workspace_bytes(int32_t cap_vertices, int32_t cap_faces) {
-    return mo_caps_ok(cap_vertices, cap_faces) ? mo_comp_ws_bytes((size_t)cap_vertices, (size_t)cap_faces) : 0;
+    return mo_caps_ok(cap_vertices, cap_faces) ? mo_comp_ws(nullptr, (size_t)cap_vertices, (size_t)cap_faces).total : 0;
 }
 
 DQO_API size_t dqo_mesh_smooth_workspace_bytes(int32_t cap_vertices, int32_t cap_faces) {
-    return mo_caps_ok(cap_vertices, cap_faces)
-               ? mo_csr_bytes((size_t)cap_vertices, (size_t)cap_faces, 6) + 2 * dqo_align_up((size_t)cap_vertices * 12, 256) : 0;
+    return mo_caps_ok(cap_vertices, cap_faces) ? mo_csr_ws(nullptr, (size_t)cap_vertices, (size_t)cap_faces, 6, true).total : 0;
 }
 
 DQO_API size_t dqo_mesh_normals_workspace_bytes(int32_t cap_vertices, int32_t cap_faces) {
-    return mo_caps_ok(cap_vertices, cap_faces) ? mo_csr_bytes((size_t)cap_vertices, (size_t)cap_faces, 3) : 0;
+    return mo_caps_ok(cap_vertices, cap_faces) ? mo_csr_ws(nullptr, (size_t)cap_vertices, (size_t)cap_faces, 3, false).total : 0;
 }
 
 DQO_API size_t dqo_mesh_simplify_workspace_bytes(int32_t cap_vertices, int32_t cap_faces) {
-    return mo_caps_ok(cap_vertices, cap_faces) ? mo_simp_ws_bytes((size_t)cap_vertices, (size_t)cap_faces) : 0;
+    return mo_caps_ok(cap_vertices, cap_faces) ? mo_simp_ws(nullptr, (size_t)cap_vertices, (size_t)cap_faces).total : 0;
 }
 
 DQO_API int dqo_mesh_simplify(const float* vertices, const float* colors, const int32_t* faces, const int32_t* counts, int32_t cap_vertices,
@@ -991,34 +1028,13 @@ DQO_API int dqo_mesh_simplify(const float* vertices, const float* colors, const 
     DQO_CHECK_ARG(vertices && faces && header, "null mesh buffer / header");
     DQO_CHECK_ARG(voxel_size - voxel_size == 0.0 && voxel_size > 0.0, "bad voxel_size: it is finite and above 0");
     DQO_CHECK_ARG(origin_x - origin_x == 0.0 && origin_y - origin_y == 0.0 && origin_z - origin_z == 0.0, "bad origin: it is finite");
-    DQO_CHECK_ARG(out_cap_vertices >= cap_vertices && out_cap_faces >= cap_faces,
-                  "out capacity (%d vertices, %d faces) below the input's (%d, %d)", out_cap_vertices, out_cap_faces, cap_vertices, cap_faces);
-    DQO_CHECK_ARG(out_vertices && out_faces && (colors == nullptr || out_colors), "null out mesh buffer");
-    DQO_CHECK_ARG(out_vertices != vertices && out_faces != faces && (colors == nullptr || out_colors != colors),
-                  "the out mesh must not be the input mesh");
-    DQO_CHECK_ARG(header != counts, "header must not be the input's counts: the first launch clears it before the counts are read");
+    DQO_MESH_CHECK_OUT();
     const size_t cv = (size_t)cap_vertices, cf = (size_t)cap_faces;
-    DQO_CHECK_WS("mesh simplify", workspace, workspace_bytes, mo_simp_ws_bytes(cv, cf));
+    DQO_CHECK_WS("mesh simplify", workspace, workspace_bytes, mo_simp_ws(nullptr, cv, cf).total);
     const uint32_t ucv = (uint32_t)cap_vertices, ucf = (uint32_t)cap_faces;
-    MoSimp w;
-    MoCsr c;
-    char* p = (char*)workspace;
-    w.head = c.head = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
-    w.vtab = (int32_t*)p, p += dqo_align_up((size_t)mo_slots(ucv) * 4, 256);
-    w.vslot = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
-    w.mark = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
-    w.cnum = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
-    w.vcid = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
-    w.sorted = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
-    w.ftab = (int32_t*)p, p += dqo_align_up((size_t)mo_slots(ucf) * 4, 256);
-    w.fslot = (int32_t*)p, p += dqo_align_up(cf * 4, 256);
-    w.ftri = (int32_t*)p, p += dqo_align_up(cf * 12, 256);
-    w.vspan = (u64*)p, p += dqo_align_up(mo_spans(cv) * sizeof(u64), 256);
-    w.fspan = (uint32_t*)p, p += dqo_align_up(mo_spans(cf) * 4, 256);
-    c.deg = (uint32_t*)p, p += dqo_align_up((cv + 1) * 4, 256);
-    c.off = (uint32_t*)p, p += dqo_align_up((cv + 1) * 4, 256);
-    c.span = (uint32_t*)p, p += dqo_align_up(mo_spans(cv + 1) * 4, 256);
-    c.adj = (int32_t*)p;
+    const MoSimpWs l = mo_simp_ws(workspace, cv, cf);
+    MoSimp w = l.w;
+    const MoCsr& c = l.c;
     w.voxel = voxel_size, w.org[0] = origin_x, w.org[1] = origin_y, w.org[2] = origin_z;
     const size_t slots = mo_slots(ucv) > mo_slots(ucf) ? mo_slots(ucv) : mo_slots(ucf);
     const size_t clear_blocks = mo_blocks(slots) < (size_t)MO_CLEAR_BLOCKS ? mo_blocks(slots) : (size_t)MO_CLEAR_BLOCKS;
@@ -1048,25 +1064,11 @@ DQO_API int dqo_mesh_components(const float* vertices, const float* colors, cons
     DQO_MESH_CHECK_CAPS(cap_vertices, cap_faces);
     DQO_CHECK_ARG(vertices && faces && header, "null mesh buffer / header");
     DQO_CHECK_ARG(min_faces >= 0, "bad min_faces %d: it is at least 0", min_faces);
-    DQO_CHECK_ARG(out_cap_vertices >= cap_vertices && out_cap_faces >= cap_faces,
-                  "out capacity (%d vertices, %d faces) below the input's (%d, %d)", out_cap_vertices, out_cap_faces, cap_vertices, cap_faces);
-    DQO_CHECK_ARG(out_vertices && out_faces && (colors == nullptr || out_colors), "null out mesh buffer");
-    DQO_CHECK_ARG(out_vertices != vertices && out_faces != faces && (colors == nullptr || out_colors != colors),
-                  "the out mesh must not be the input mesh");
-    DQO_CHECK_ARG(header != counts, "header must not be the input's counts: the first launch clears it before the counts are read");
+    DQO_MESH_CHECK_OUT();
     const size_t cv = (size_t)cap_vertices, cf = (size_t)cap_faces;
-    DQO_CHECK_WS("mesh components", workspace, workspace_bytes, mo_comp_ws_bytes(cv, cf));
-    MoComp w;
-    char* p = (char*)workspace;
-    w.head = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
-    w.parent = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
-    w.size = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
-    w.mark = (int32_t*)p, p += dqo_align_up(cv * 4, 256);
-    w.label = labels != nullptr ? labels : (int32_t*)p, p += dqo_align_up(cf * 4, 256);
-    w.keep = (uint8_t*)p, p += dqo_align_up(cf, 256);
-    w.spair = (u64*)p, p += dqo_align_up(mo_spans(cv) * sizeof(u64), 256);
-    w.vpair = (u64*)p, p += dqo_align_up(mo_spans(cv) * sizeof(u64), 256);
-    w.fblock = (uint32_t*)p;
+    DQO_CHECK_WS("mesh components", workspace, workspace_bytes, mo_comp_ws(nullptr, cv, cf).total);
+    MoComp w = mo_comp_ws(workspace, cv, cf).w;
+    if (labels != nullptr) w.label = labels;  // (the part is taken all the same: the size does not depend on the option)
     const uint32_t ucv = (uint32_t)cap_vertices, ucf = (uint32_t)cap_faces;
     const dim3 block(256), gv((unsigned)mo_blocks(cv)), gf((unsigned)mo_blocks(cf)), sv((unsigned)mo_spans(cv)), sf((unsigned)mo_spans(cf));
     hipStream_t s = (hipStream_t)stream;
@@ -1094,12 +1096,11 @@ DQO_API int dqo_mesh_smooth(float* vertices, float* colors, const int32_t* faces
     DQO_CHECK_ARG(scope >= DQO_MESH_SMOOTH_POSITIONS && scope <= DQO_MESH_SMOOTH_BOTH, "bad scope %d: 0 positions, 1 colours, 2 both", scope);
     DQO_CHECK_ARG(scope == DQO_MESH_SMOOTH_POSITIONS || colors, "null colors with a scope that smooths them");
     const size_t cv = (size_t)cap_vertices, cf = (size_t)cap_faces;
-    DQO_CHECK_WS("mesh smooth", workspace, workspace_bytes, mo_csr_bytes(cv, cf, 6) + 2 * dqo_align_up(cv * 12, 256));
+    DQO_CHECK_WS("mesh smooth", workspace, workspace_bytes, mo_csr_ws(nullptr, cv, cf, 6, true).total);
     if (iterations == 0) return DQO_OK;
-    MoCsr c;
-    char* p = mo_csr_layout(c, workspace, cv, cf, 6);
-    float* const other_p = (float*)p;
-    float* const other_c = (float*)(p + dqo_align_up(cv * 12, 256));
+    const MoCsrWs l = mo_csr_ws(workspace, cv, cf, 6, true);
+    const MoCsr& c = l.c;
+    float *const other_p = l.other_p, *const other_c = l.other_c;
     const uint32_t ucv = (uint32_t)cap_vertices, ucf = (uint32_t)cap_faces;
     hipStream_t s = (hipStream_t)stream;
     const int rc = mo_build_csr<true>(faces, counts, ucv, ucf, c, s);
@@ -1134,9 +1135,8 @@ DQO_API int dqo_mesh_normals(const float* vertices, const int32_t* faces, const 
     DQO_MESH_CHECK_CAPS(cap_vertices, cap_faces);
     DQO_CHECK_ARG(vertices && faces && normals, "null mesh buffer / normals");
     const size_t cv = (size_t)cap_vertices, cf = (size_t)cap_faces;
-    DQO_CHECK_WS("mesh normals", workspace, workspace_bytes, mo_csr_bytes(cv, cf, 3));
-    MoCsr c;
-    mo_csr_layout(c, workspace, cv, cf, 3);
+    DQO_CHECK_WS("mesh normals", workspace, workspace_bytes, mo_csr_ws(nullptr, cv, cf, 3, false).total);
+    const MoCsr c = mo_csr_ws(workspace, cv, cf, 3, false).c;
     hipStream_t s = (hipStream_t)stream;
     const int rc = mo_build_csr<false>(faces, counts, (uint32_t)cap_vertices, (uint32_t)cap_faces, c, s);
     if (rc != DQO_OK) return rc;

@@ -264,31 +264,33 @@ __global__ __launch_bounds__(MS_THREADS) void mesh_sample_kernel(MsArgs a) {
 }
 
 inline size_t ms_blocks(int64_t F) { return (size_t)((F + MS_BLOCK - 1) / MS_BLOCK); }
-inline size_t ms_partial_bytes(int64_t F) { return dqo_align_up(ms_blocks(F) * sizeof(u64), 256); }
+// the ticket words | MsState | bmax | bcount | bsum | cum (the last align_up(8 F, 256) bytes: dqo_eval.mesh_cum_view reads them for the tests).
+// Of MsArgs it sets the workspace's pointers and nothing else.  F: the face capacity of the counted form
+inline DqoLayout<MsArgs> ms_ws(void* base, int64_t F) {
+    MsArgs w = {};
+    DqoCarver k(base);
+    w.ticket = k.take_raw<int32_t>(DQO_REDUCE_HEAD_WORDS * 4);
+    w.state = k.take_raw<MsState>(MS_STATE_BYTES);
+    w.bmax = k.take<u64>(ms_blocks(F) * sizeof(u64));
+    w.bcount = k.take<u64>(ms_blocks(F) * sizeof(u64));
+    w.bsum = k.take<u64>(ms_blocks(F) * sizeof(u64));
+    w.cum = k.take<u64>((size_t)F * sizeof(u64));
+    return {w, k.total()};
+}
 
 }  // namespace
 
-// the ticket words | MsState | bmax | bcount | bsum | cum (the last align_up(8 F, 256) bytes: dqo_eval.mesh_cum_view reads them for the tests)
-static size_t dqo_mesh_sample_ws_bytes(int64_t F) {
-    return DQO_REDUCE_HEAD_WORDS * 4 + MS_STATE_BYTES + 3 * ms_partial_bytes(F) + dqo_align_up((size_t)F * sizeof(u64), 256);
-}
+static size_t dqo_mesh_sample_ws_bytes(int64_t F) { return ms_ws(nullptr, F).total; }
 
 // COUNTED: V and F are the capacities — they size the workspace's parts and the grids — and `counts` holds the counts
 template <bool COUNTED>
 static int dqo_launch_mesh_sample(int V, const float* vertices, int F, const int32_t* faces, const int32_t* counts, int count, uint64_t seed,
                                   float* points, int32_t* face_index, uint8_t* keep, int32_t* header, void* ws, hipStream_t s) {
-    MsArgs a;
+    MsArgs a = ms_ws(ws, F).w;
     a.V = V, a.F = F, a.count = count, a.nblocks = (uint32_t)ms_blocks(F), a.counts = counts;
     a.seed_word = dqo_sample_seed_word(seed);
     for (uint32_t d = 0; d < 4; d++) a.draw_word[d] = dqo_sample_draw_word(a.seed_word, 4u + d);
     a.vertices = vertices, a.faces = faces, a.points = points, a.face_index = face_index, a.keep = keep, a.header = header;
-    char* p = (char*)ws;
-    a.ticket = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
-    a.state = (MsState*)p, p += MS_STATE_BYTES;
-    a.bmax = (u64*)p, p += ms_partial_bytes(F);
-    a.bcount = (u64*)p, p += ms_partial_bytes(F);
-    a.bsum = (u64*)p, p += ms_partial_bytes(F);
-    a.cum = (u64*)p;
     const dim3 grid(a.nblocks), block(MS_THREADS);
     DQO_LAUNCH("mesh_area_kernel", mesh_area_kernel<COUNTED>, grid, block, s, a);
     DQO_LAUNCH("mesh_quantise_kernel", mesh_quantise_kernel<COUNTED>, grid, block, s, a);

@@ -77,19 +77,19 @@ inline MsLevel ms_level(int w, int h) {
 
 inline MsWorkspace ms_ws(void* base, int W, int H) {
     MsWorkspace w;
-    char* p = (char*)base;
-    w.ticket = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
-    w.means = (double*)p, p += dqo_align_up(MS_LEVELS * MS_MEANS * sizeof(double), 256);
+    DqoCarver k(base);
+    w.ticket = k.take_raw<int32_t>(DQO_REDUCE_HEAD_WORDS * 4);
+    w.means = k.take<double>(MS_LEVELS * MS_MEANS * sizeof(double));
     int blocks = 0, lw = W, lh = H;
     for (int l = 0; l < MS_LEVELS; l++, lw = ms_next(lw), lh = ms_next(lh)) blocks = std::max(blocks, ms_level(lw, lh).blocks);
-    w.partial = (double*)p, p += dqo_align_up((size_t)blocks * MS_STRIDE * sizeof(double), 256);
+    w.partial = k.take<double>((size_t)blocks * MS_STRIDE * sizeof(double));
     w.pooled[0] = nullptr;
     lw = W, lh = H;
     for (int l = 1; l < MS_LEVELS; l++) {
         lw = ms_next(lw), lh = ms_next(lh);
-        w.pooled[l] = (float*)p, p += dqo_align_up(sizeof(float) * 6 * (size_t)lw * lh, 256);
+        w.pooled[l] = k.take<float>(sizeof(float) * 6 * (size_t)lw * lh);
     }
-    w.total = (size_t)(p - (char*)base);
+    w.total = k.total();
     return w;
 }
 

@@ -52,15 +52,15 @@ struct SpWorkspace {
 
 __host__ __device__ inline size_t sp_blocks(int64_t HW) { return (size_t)((HW + SP_PIX - 1) / SP_PIX); }
 
-inline SpWorkspace sp_workspace(void* base, int64_t HW) {
+// the head words | blk_eq | blk_rows | flags
+inline DqoLayout<SpWorkspace> sp_workspace(void* base, int64_t HW) {
     SpWorkspace w;
-    char* p = (char*)base;
-    const size_t per_block = dqo_align_up(sp_blocks(HW) * 2 * sizeof(uint32_t), 256);
-    w.head = (uint32_t*)p;
-    w.blk_eq = (uint32_t*)(p + SP_HEAD_WORDS * 4);
-    w.blk_rows = (uint32_t*)(p + SP_HEAD_WORDS * 4 + per_block);
-    w.flags = (uint8_t*)(p + SP_HEAD_WORDS * 4 + 2 * per_block);
-    return w;
+    DqoCarver k(base);
+    w.head = k.take_raw<uint32_t>(SP_HEAD_WORDS * 4);
+    w.blk_eq = k.take<uint32_t>(sp_blocks(HW) * 2 * sizeof(uint32_t));
+    w.blk_rows = k.take<uint32_t>(sp_blocks(HW) * 2 * sizeof(uint32_t));
+    w.flags = k.take<uint8_t>((size_t)HW);
+    return {w, k.total()};
 }
 
 struct SpKeys {
@@ -352,13 +352,11 @@ __global__ __launch_bounds__(SP_THREADS) void sample_emit_kernel(DqoGrowthSample
 
 }  // namespace
 
-static size_t dqo_sample_ws_bytes(int64_t HW) {
-    return SP_HEAD_WORDS * 4 + 2 * dqo_align_up(sp_blocks(HW) * 2 * sizeof(uint32_t), 256) + dqo_align_up((size_t)HW, 256);
-}
+static size_t dqo_sample_ws_bytes(int64_t HW) { return sp_workspace(nullptr, HW).total; }
 
 static int dqo_launch_growth_sample(const DqoGrowthSample* a, hipStream_t s) {
     const int64_t HW = (int64_t)a->W * a->H;
-    const SpWorkspace w = sp_workspace(a->workspace, HW);
+    const SpWorkspace w = sp_workspace(a->workspace, HW).w;
     SpKeys keys;
     keys.seed_word = dqo_sample_seed_word(a->seed);
     keys.draw_word[0] = dqo_sample_draw_word(keys.seed_word, a->first_frame ? 0u : 1u);

@@ -172,17 +172,23 @@ DqoSsimWindow dqo_ssim_window() {
     return w;
 }
 
-static size_t dqo_map_ssim_ws_bytes(int W, int H) {
-    const size_t HW = (size_t)W * H;
-    const size_t blocks = (size_t)((W + SS_T - 1) / SS_T) * ((H + SS_T - 1) / SS_T) * 3;
-    return dqo_align_up(sizeof(float) * 9 * HW, 256) + dqo_align_up(sizeof(float) * blocks, 256);
+struct SsimWs {
+    float *maps, *partial;  // the nine maps of a pixel | a partial per block
+    size_t total;
+};
+static SsimWs ssim_ws(void* base, int W, int H) {
+    DqoCarver k(base);
+    const size_t HW = (size_t)W * H, blocks = (size_t)((W + SS_T - 1) / SS_T) * ((H + SS_T - 1) / SS_T) * 3;
+    float* const maps = k.take<float>(sizeof(float) * 9 * HW);
+    return {maps, k.take<float>(sizeof(float) * blocks), k.total()};
 }
+static size_t dqo_map_ssim_ws_bytes(int W, int H) { return ssim_ws(nullptr, W, H).total; }
 
 static int dqo_launch_map_ssim(int W, int H, const float* img, const float* gt, float weight, float* ssim_out, float* dL_dimg, int accumulate,
                                float* loss8, void* ws, hipStream_t s) {
     const size_t HW = (size_t)W * H;
-    float* maps = reinterpret_cast<float*>(ws);
-    float* partial = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + dqo_align_up(sizeof(float) * 9 * HW, 256));
+    const SsimWs l = ssim_ws(ws, W, H);
+    float *const maps = l.maps, *const partial = l.partial;
     const SsimWin w = dqo_ssim_window();
     const dim3 grid((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, 3), block(SS_T * SS_T);
     const int nblocks = (int)(grid.x * grid.y * grid.z);

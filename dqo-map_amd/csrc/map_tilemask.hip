@@ -89,14 +89,13 @@ struct WmWorkspace {
     float* sums;      // [T] mode 1
     int32_t* counts;  // [T] modes 0, 2
 };
-inline WmWorkspace wm_ws(void* base, size_t T, size_t* total) {
+inline DqoLayout<WmWorkspace> wm_ws(void* base, size_t T) {
     WmWorkspace w;
-    char* p = (char*)base;
-    w.ticket = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;  // = DQO_WINDOW_MASKS_SUMS_OFFSET
-    w.sums = (float*)p, p += dqo_align_up(4 * T, 256);
-    w.counts = (int32_t*)p, p += dqo_align_up(4 * T, 256);
-    if (total) *total = (size_t)(p - (char*)base);
-    return w;
+    DqoCarver k(base);
+    w.ticket = k.take_raw<int32_t>(DQO_REDUCE_HEAD_WORDS * 4);  // = DQO_WINDOW_MASKS_SUMS_OFFSET
+    w.sums = k.take<float>(4 * T);
+    w.counts = k.take<int32_t>(4 * T);
+    return {w, k.total()};
 }
 
 // the block's sum of one word per thread (every thread gets it); s_wave is free again after the call
@@ -250,15 +249,13 @@ static int dqo_launch_tile_color_error(int W, int H, const float* render, const 
 }
 
 static size_t dqo_window_masks_ws_bytes(int W, int H) {
-    size_t total = 0;
-    wm_ws(nullptr, (size_t)((W + DQO_TILE - 1) / DQO_TILE) * ((H + DQO_TILE - 1) / DQO_TILE), &total);
-    return total;
+    return wm_ws(nullptr, (size_t)((W + DQO_TILE - 1) / DQO_TILE) * ((H + DQO_TILE - 1) / DQO_TILE)).total;
 }
 
 static int dqo_launch_window_masks(int W, int H, int mode, const float* T_map, const float* render, const float* gt, float tile_mask_ratio, int k,
                                    uint8_t* render_mask, int32_t* tile_mask, float* ratio_out, const DqoRastHeader* header, void* ws, hipStream_t s) {
     const int gx = (W + DQO_TILE - 1) / DQO_TILE, gy = (H + DQO_TILE - 1) / DQO_TILE, T = gx * gy;
-    const WmWorkspace w = wm_ws(ws, (size_t)T, nullptr);
+    const WmWorkspace w = wm_ws(ws, (size_t)T).w;
     DQO_LAUNCH("window_masks_kernel", window_masks_kernel, dim3(T), dim3(256), s, W, H, gx, T, mode, T_map, render, gt, tile_mask_ratio, k,
                render_mask, tile_mask, ratio_out, header, w);
     if (mode == 1) {

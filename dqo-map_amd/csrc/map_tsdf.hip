@@ -381,13 +381,21 @@ inline TsdfGrid ts_grid(int nx, int ny, int nz, float ox, float oy, float oz, fl
 inline bool ts_dims_ok(int64_t nx, int64_t ny, int64_t nz) { return nx >= 2 && ny >= 2 && nz >= 2 && nx < (1 << 28) && ny < (1 << 28) && nz < (1 << 28); }
 inline bool ts_count_ok(int64_t nx, int64_t ny, int64_t nz) { return nx * ny < (1ll << 28) && nx * ny * nz < (1ll << 28); }
 
-}  // namespace
-
-static size_t dqo_tsdf_ws_bytes(size_t N) {
-    const size_t nb = ts_spans(N);
-    return DQO_REDUCE_HEAD_WORDS * 4 + dqo_align_up(nb * sizeof(uint32_t), 256) + dqo_align_up(nb * sizeof(u64), 256) + 3 * dqo_align_up(N, 256) +
-           dqo_align_up(N * sizeof(uint16_t), 256);
+// dqo_tsdf_extract's workspace: the ticket words | vblock | fpairs | flags | mask | fcount | base
+inline DqoLayout<TsdfWs> ts_ws(void* base, size_t N) {
+    TsdfWs w;
+    DqoCarver k(base);
+    w.head = k.take_raw<int32_t>(DQO_REDUCE_HEAD_WORDS * 4);
+    w.vblock = k.take<uint32_t>(ts_spans(N) * sizeof(uint32_t));
+    w.fpairs = k.take<u64>(ts_spans(N) * sizeof(u64));
+    w.flags = k.take<uint8_t>(N);
+    w.mask = k.take<uint8_t>(N);
+    w.fcount = k.take<uint8_t>(N);
+    w.base = k.take<uint16_t>(N * sizeof(uint16_t));
+    return {w, k.total()};
 }
+
+}  // namespace
 
 #define DQO_TSDF_CHECK_DIMS(nx, ny, nz)                                                                                    \
     do {                                                                                                                   \
@@ -399,7 +407,7 @@ static size_t dqo_tsdf_ws_bytes(size_t N) {
 extern "C" {
 
 DQO_API size_t dqo_tsdf_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
-    return ts_dims_ok(nx, ny, nz) && ts_count_ok(nx, ny, nz) ? dqo_tsdf_ws_bytes((size_t)nx * ny * nz) : 0;
+    return ts_dims_ok(nx, ny, nz) && ts_count_ok(nx, ny, nz) ? ts_ws(nullptr, (size_t)nx * ny * nz).total : 0;
 }
 
 DQO_API int dqo_tsdf_clear(int32_t nx, int32_t ny, int32_t nz, float* tsdf, float* weight, float* color, int32_t* header, void* stream) {
@@ -435,18 +443,9 @@ DQO_API int dqo_tsdf_extract(int32_t nx, int32_t ny, int32_t nz, float origin_x,
     DQO_CHECK_ARG(cap_vertices >= 0 && cap_faces >= 0, "bad capacity: %d vertices, %d faces", cap_vertices, cap_faces);
     DQO_CHECK_ARG((cap_vertices == 0 || (vertices && vertex_color)) && (cap_faces == 0 || faces), "null mesh buffer");
     const TsdfGrid g = ts_grid(nx, ny, nz, origin_x, origin_y, origin_z, voxel_length);
-    DQO_CHECK_WS("tsdf", workspace, workspace_bytes, dqo_tsdf_ws_bytes(g.N));
-    const size_t nb = ts_spans(g.N);
-    TsdfWs w;
-    char* p = (char*)workspace;
-    w.head = (int32_t*)p, p += DQO_REDUCE_HEAD_WORDS * 4;
-    w.vblock = (uint32_t*)p, p += dqo_align_up(nb * sizeof(uint32_t), 256);
-    w.fpairs = (u64*)p, p += dqo_align_up(nb * sizeof(u64), 256);
-    w.flags = (uint8_t*)p, p += dqo_align_up(g.N, 256);
-    w.mask = (uint8_t*)p, p += dqo_align_up(g.N, 256);
-    w.fcount = (uint8_t*)p, p += dqo_align_up(g.N, 256);
-    w.base = (uint16_t*)p;
-    const dim3 grid((unsigned)nb), block(256);
+    DQO_CHECK_WS("tsdf", workspace, workspace_bytes, ts_ws(nullptr, g.N).total);
+    const TsdfWs w = ts_ws(workspace, g.N).w;
+    const dim3 grid((unsigned)ts_spans(g.N)), block(256);
     hipStream_t s = (hipStream_t)stream;
     DQO_LAUNCH("tsdf_flags_kernel", tsdf_flags_kernel, dim3((unsigned)ts_blocks(g.N)), block, s, g, tsdf, weight, w.flags);
     DQO_LAUNCH("tsdf_edges_kernel", tsdf_edges_kernel, grid, block, s, g, w);

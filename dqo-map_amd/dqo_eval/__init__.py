@@ -109,6 +109,7 @@ FusedMapper.make_clean_mesh chains them behind make_mesh (make_simplified_mesh: 
 GPU only: there is no CPU path.
 """
 import ctypes
+import functools
 
 import torch
 
@@ -135,6 +136,29 @@ def _workspace(key, nbytes, dev):
 
 def _dev_index(dev):
     return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
+def _ws(workspace_buffer, dev, nbytes, tag, *sizes):
+    """The caller's workspace, or the module's own for (tag, device, sizes).  nbytes: its size, or a function that gives it and raises
+    for bad sizes — asked only when the workspace is the module's."""
+    if workspace_buffer is not None:
+        return workspace_buffer
+    return _workspace((tag, _dev_index(dev)) + sizes, nbytes() if callable(nbytes) else nbytes, dev)
+
+
+_nan_table = functools.partial(torch.full, fill_value=float("nan"))  # (a launch)
+
+
+def _table_row(out, row, width, who, dev, rows=1, fresh=_nan_table):
+    """(out, row) of a result table: the caller's contiguous float32 [K, width] table and the first of the `rows` rows the call writes,
+    checked, or a new [rows, width] table made by `fresh` and row 0."""
+    if out is None:
+        out, row = fresh((rows, width), dtype=torch.float32, device=dev), 0
+    if (out.dim() != 2 or out.shape[1] != width or out.dtype != torch.float32 or not out.is_contiguous()
+            or not 0 <= int(row) <= out.shape[0] - rows):
+        which = "row one of its rows" if rows == 1 else f"[row, row + {rows}) rows of it"
+        raise RuntimeError(f"dqo_eval.{who}: out must be a contiguous float32 [K,{width}] table and {which}")
+    return out, int(row)
 
 
 def _picture_bytes(W, H):
@@ -187,22 +211,19 @@ def eval_picture(render_output, gt_color, gt_depth, min_depth, max_depth, out=No
     render, gt_color = _image(render, 3, H, W, f32, "render"), _image(gt_color, 3, H, W, f32, "gt_color")
     depth, gt_depth = _image(depth, 1, H, W, f32, "depth"), _image(gt_depth, 1, H, W, f32, "gt_depth")
     index = _image(index, 1, H, W, torch.int32, "depth_index_map")
-    if out is None:
-        out, row = torch.full((1, 8), float("nan"), dtype=f32, device=dev), 0
-    if out.dim() != 2 or out.shape[1] != 8 or out.dtype != f32 or not out.is_contiguous() or not 0 <= int(row) < out.shape[0]:
-        raise RuntimeError("dqo_eval.eval_picture: out must be a contiguous float32 [K,8] table and row one of its rows")
-    ws = workspace_buffer if workspace_buffer is not None else _workspace((_dev_index(dev), W, H), _picture_bytes(W, H), dev)
+    out, row = _table_row(out, row, 8, "eval_picture", dev)
+    ws = _ws(workspace_buffer, dev, lambda: _picture_bytes(W, H), "picture", W, H)
     n_eval = lib.dqo_eval_picture_workspace_bytes(W, H)
     with torch.cuda.device(dev):
         stream = N.current_stream()
         if ssim:
             # dqo_map_ssim_fwd_bwd writes TWO floats (the value, weight * (1 - value)): into slots 4 and 5, BEFORE dqo_eval_picture writes
             # mse_r over slot 5 on the same stream — no staging buffer, no copy launch
-            N.check(lib.dqo_map_ssim_fwd_bwd(W, H, N.ptr(render), N.ptr(gt_color), 0.0, out.data_ptr() + 4 * (8 * int(row) + 4), None, 0, None,
+            N.check(lib.dqo_map_ssim_fwd_bwd(W, H, N.ptr(render), N.ptr(gt_color), 0.0, out.data_ptr() + 4 * (8 * row + 4), None, 0, None,
                                              ws.data_ptr() + n_eval, ws.numel() - n_eval, stream))
         N.check(lib.dqo_eval_picture(W, H, N.ptr(render), N.ptr(gt_color), N.ptr(depth), N.ptr(gt_depth), N.ptr(index), float(min_depth),
-                                     float(max_depth), N.ptr(render_header), out.data_ptr(), int(row), ws.data_ptr(), n_eval, stream))
-    return out[int(row)]
+                                     float(max_depth), N.ptr(render_header), out.data_ptr(), row, ws.data_ptr(), n_eval, stream))
+    return out[row]
 
 
 def _ms_ssim_bytes(W, H):
@@ -242,15 +263,12 @@ def ms_ssim(image, gt, out=None, row=0, *, workspace_buffer=None, render_header=
     if min(H, W) < MS_MIN_SIDE:
         raise RuntimeError(f"dqo_eval.ms_ssim: image size {W} x {H}: both sides must be at least {MS_MIN_SIDE} (the reference's library "
                            "asserts smaller_side > 160)")
-    if out is None:
-        out, row = torch.full((1, 20), float("nan"), dtype=f32, device=dev), 0
-    if out.dim() != 2 or out.shape[1] != 20 or out.dtype != f32 or not out.is_contiguous() or not 0 <= int(row) < out.shape[0]:
-        raise RuntimeError("dqo_eval.ms_ssim: out must be a contiguous float32 [K,20] table and row one of its rows")
-    ws = workspace_buffer if workspace_buffer is not None else _workspace(("ms", _dev_index(dev), W, H), _ms_ssim_bytes(W, H), dev)
+    out, row = _table_row(out, row, 20, "ms_ssim", dev)
+    ws = _ws(workspace_buffer, dev, lambda: _ms_ssim_bytes(W, H), "ms", W, H)
     with torch.cuda.device(dev):
-        N.check(lib.dqo_eval_ms_ssim(W, H, N.ptr(image), N.ptr(gt), N.ptr(render_header), out.data_ptr(), int(row), ws.data_ptr(), ws.numel(),
+        N.check(lib.dqo_eval_ms_ssim(W, H, N.ptr(image), N.ptr(gt), N.ptr(render_header), out.data_ptr(), row, ws.data_ptr(), ws.numel(),
                                      N.current_stream()))
-    return out[int(row)]
+    return out[row]
 
 
 LPIPS_ROW = ("lpips", "d0", "d1", "d2", "d3", "d4", "unused6", "unused7")
@@ -356,15 +374,12 @@ def lpips(image, gt, weights, out=None, row=0, *, norm="torchmetrics", workspace
     if min(H, W) < LPIPS_MIN_SIDE:
         raise RuntimeError(f"dqo_eval.lpips: image size {W} x {H}: both sides must be at least {LPIPS_MIN_SIDE} (every AlexNet map needs a "
                            "pixel)")
-    if out is None:
-        out, row = torch.full((1, 8), float("nan"), dtype=f32, device=dev), 0
-    if out.dim() != 2 or out.shape[1] != 8 or out.dtype != f32 or not out.is_contiguous() or not 0 <= int(row) < out.shape[0]:
-        raise RuntimeError("dqo_eval.lpips: out must be a contiguous float32 [K,8] table and row one of its rows")
-    ws = workspace_buffer if workspace_buffer is not None else _workspace(("lpips", _dev_index(dev), W, H), _lpips_bytes(W, H), dev)
+    out, row = _table_row(out, row, 8, "lpips", dev)
+    ws = _ws(workspace_buffer, dev, lambda: _lpips_bytes(W, H), "lpips", W, H)
     with torch.cuda.device(dev):
         N.check(lib.dqo_eval_lpips(W, H, N.ptr(image), N.ptr(gt), N.ptr(weights.packed), LPIPS_NORMS[norm], N.ptr(render_header), out.data_ptr(),
-                                   int(row), ws.data_ptr(), ws.numel(), N.current_stream()))
-    return out[int(row)]
+                                   row, ws.data_ptr(), ws.numel(), N.current_stream()))
+    return out[row]
 
 
 def lpips_feature_view(workspace_buffer, W, H, layer):
@@ -438,22 +453,7 @@ def nearest(query, ref, query_keep=None, ref_keep=None, query_transform=None, re
     reference: FLT_MAX / -1 everywhere.  *_transform: [3,4] / [4,4], applied to the rows as they are loaded.  No host read, no
     synchronisation; workspace_buffer: a uint8 tensor of dqo_nn1_workspace_bytes(Q, R) the caller keeps (default: one per device and
     size, kept by this module — calls that share it must be on one stream)."""
-    N.require_gpu_op((query, ref), query_keep, ref_keep)
-    lib, dev = N.lib(), query.device
-    query, ref = _points(query, "query"), _points(ref, "ref")
-    Q, R = int(query.shape[0]), int(ref.shape[0])
-    qk, rk = _keep(query_keep, Q, "query_keep"), _keep(ref_keep, R, "ref_keep")
-    qx, rx = _xform(query_transform, dev, "query_transform"), _xform(ref_transform, dev, "ref_transform")
-    n = lib.dqo_nn1_workspace_bytes(Q, R)
-    if n == 0:
-        raise RuntimeError(f"dqo_eval.nearest: bad sizes {Q}, {R} (at most 2^25 - 1 rows per set)")
-    ws = workspace_buffer if workspace_buffer is not None else _workspace(("nn1", _dev_index(dev), Q, R), n, dev)
-    dist2 = torch.empty((Q,), dtype=torch.float32, device=dev)
-    idx = torch.empty((Q,), dtype=torch.int32, device=dev) if want_idx else None
-    with torch.cuda.device(dev):
-        N.check(lib.dqo_nn1(Q, N.ptr(query), N.ptr(qk), R, N.ptr(ref), N.ptr(rk), N.ptr(qx), N.ptr(rx), N.ptr(dist2), N.ptr(idx), ws.data_ptr(),
-                            ws.numel(), N.current_stream()))
-    return dist2, idx
+    return _nearest(False, query, query_keep, ref, ref_keep, query_transform, ref_transform, want_idx, workspace_buffer)
 
 
 OBJECTS = 64  # object ids of a grouped call: [0, OBJECTS); any other id = the row has no object
@@ -476,22 +476,30 @@ def nearest_grouped(query, query_group, ref, ref_group, query_transform=None, re
     nearest() with query_keep = (query_group == g) and ref_keep = (ref_group == g), for every g — from one build of the reference set,
     one sort of the queries and one scan.  Transforms, workspace (dqo_nn1_grouped_workspace_bytes(Q, R)) and contract as nearest():
     no host read, no synchronisation."""
-    N.require_gpu_op((query, ref), query_group, ref_group)
+    return _nearest(True, query, query_group, ref, ref_group, query_transform, ref_transform, want_idx, workspace_buffer)
+
+
+def _nearest(grouped, query, q_rows, ref, r_rows, query_transform, ref_transform, want_idx, workspace_buffer):
+    """nearest (q_rows, r_rows: the keep masks) and nearest_grouped (the group ids): one search, one workspace key."""
+    N.require_gpu_op((query, ref), q_rows, r_rows)
     lib, dev = N.lib(), query.device
     query, ref = _points(query, "query"), _points(ref, "ref")
     Q, R = int(query.shape[0]), int(ref.shape[0])
-    qg, rg = _group(query_group, Q, dev, "query_group"), _group(ref_group, R, dev, "ref_group")
+    if grouped:
+        qr, rr = _group(q_rows, Q, dev, "query_group"), _group(r_rows, R, dev, "ref_group")
+    else:
+        qr, rr = _keep(q_rows, Q, "query_keep"), _keep(r_rows, R, "ref_keep")
     qx, rx = _xform(query_transform, dev, "query_transform"), _xform(ref_transform, dev, "ref_transform")
-    n = lib.dqo_nn1_grouped_workspace_bytes(Q, R)
+    n = (lib.dqo_nn1_grouped_workspace_bytes if grouped else lib.dqo_nn1_workspace_bytes)(Q, R)
     if n == 0:
-        raise RuntimeError(f"dqo_eval.nearest_grouped: bad sizes {Q}, {R} (at most 2^25 - 1 rows per set)")
-    ws = workspace_buffer if workspace_buffer is not None else _workspace(("nn1", _dev_index(dev), Q, R), n, dev)
+        raise RuntimeError(f"dqo_eval.nearest{'_grouped' if grouped else ''}: bad sizes {Q}, {R} (at most 2^25 - 1 rows per set)")
+    ws = _ws(workspace_buffer, dev, n, "nn1", Q, R)
     dist2 = torch.empty((Q,), dtype=torch.float32, device=dev)
     idx = torch.empty((Q,), dtype=torch.int32, device=dev) if want_idx else None
-    if Q > 0:  # (the C entry wants the ids even when R = 0; an empty tensor has no pointer)
+    if Q > 0 or not grouped:  # (the grouped C entry wants the ids even when R = 0; an empty tensor has no pointer)
         with torch.cuda.device(dev):
-            N.check(lib.dqo_nn1_grouped(Q, N.ptr(query), N.ptr(qg), R, N.ptr(ref), N.ptr(rg), N.ptr(qx), N.ptr(rx), N.ptr(dist2), N.ptr(idx),
-                                        ws.data_ptr(), ws.numel(), N.current_stream()))
+            N.check((lib.dqo_nn1_grouped if grouped else lib.dqo_nn1)(Q, N.ptr(query), N.ptr(qr), R, N.ptr(ref), N.ptr(rr), N.ptr(qx), N.ptr(rx),
+                                                                      N.ptr(dist2), N.ptr(idx), ws.data_ptr(), ws.numel(), N.current_stream()))
     return dist2, idx
 
 
@@ -553,7 +561,7 @@ def densify(xyz, scaling_raw, rotation_raw, sigma=1, circle_num=30, levels=5, th
     if theta.numel() != circle_num:
         raise RuntimeError(f"dqo_eval.densify: theta must have circle_num = {circle_num} entries, got {theta.numel()}")
     circle_cs = torch.cat([torch.cos(theta), torch.sin(theta)]).contiguous().to(dev)  # (gaussian_pointcloud.py:104-105, on the CPU)
-    ws = workspace_buffer if workspace_buffer is not None else _workspace(("densify", _dev_index(dev), P, M), nbytes, dev)
+    ws = _ws(workspace_buffer, dev, nbytes, "densify", P, M)
     points = torch.empty((cap, 3), dtype=torch.float32, device=dev)
     normals = torch.empty((cap, 3), dtype=torch.float32, device=dev) if want_normals else None
     index = torch.empty((cap,), dtype=torch.int64, device=dev) if want_index else None
@@ -586,6 +594,14 @@ def mesh_cum_view(workspace_buffer, F):
     return workspace_buffer[workspace_buffer.numel() - n:].view(torch.int64)[:int(F)]
 
 
+def _sample_outs(count, want_face_index, dev):
+    """The sampler's outputs, new: (dict(points, face_index | None, keep, header), their pointers in the entries' order)."""
+    o = dict(points=torch.empty((count, 3), dtype=torch.float32, device=dev),
+             face_index=torch.empty((count,), dtype=torch.int32, device=dev) if want_face_index else None,
+             keep=torch.empty((count,), dtype=torch.uint8, device=dev), header=torch.empty((8,), dtype=torch.int32, device=dev))
+    return o, [N.ptr(t) for t in o.values()]
+
+
 def sample_surface(vertices, faces, count, seed=0, want_face_index=False, workspace_buffer=None):
     """trimesh.sample.sample_surface(mesh, count) (SLAM/eval.py:247) on the device: `count` points on the surface of a triangle mesh, a
     face picked in proportion to its area, a uniform point inside it (dqo_mesh_sample, include/dqo_raster.h, states every statement).
@@ -609,19 +625,16 @@ def sample_surface(vertices, faces, count, seed=0, want_face_index=False, worksp
     if nbytes == 0:
         raise RuntimeError(f"dqo_eval.sample_surface: bad sizes V = {V}, F = {F}, count = {count}: at least one vertex, F and count in "
                            "[1, 2^25 - 1]")
-    ws = workspace_buffer if workspace_buffer is not None else _workspace(("mesh", _dev_index(dev), F, count), nbytes, dev)
-    points = torch.empty((count, 3), dtype=torch.float32, device=dev)
-    face_index = torch.empty((count,), dtype=torch.int32, device=dev) if want_face_index else None
-    keep = torch.empty((count,), dtype=torch.uint8, device=dev)
-    header = torch.empty((8,), dtype=torch.int32, device=dev)
+    ws = _ws(workspace_buffer, dev, nbytes, "mesh", F, count)
+    o, ptrs = _sample_outs(count, want_face_index, dev)
     with torch.cuda.device(dev):
-        N.check(lib.dqo_mesh_sample(V, N.ptr(vertices), F, N.ptr(faces), count, int(seed) & (2 ** 64 - 1), N.ptr(points), N.ptr(face_index),
-                                    N.ptr(keep), N.ptr(header), ws.data_ptr(), ws.numel(), N.current_stream()))
-    return dict(points=points, face_index=face_index, keep=keep, header=header)
+        N.check(lib.dqo_mesh_sample(V, N.ptr(vertices), F, N.ptr(faces), count, int(seed) & (2 ** 64 - 1), *ptrs, ws.data_ptr(), ws.numel(),
+                                    N.current_stream()))
+    return o
 
 
-def _pcd_bytes(n_gt, n_rec):
-    n = N.lib().dqo_eval_pcd_workspace_bytes(int(n_gt), int(n_rec))
+def _pcd_bytes(n_gt, n_rec, query="dqo_eval_pcd_workspace_bytes"):
+    n = getattr(N.lib(), query)(int(n_gt), int(n_rec))
     if n == 0:
         raise RuntimeError(f"dqo_eval: bad point counts {n_gt}, {n_rec} (at most 2^25 - 1 rows per set)")
     return n
@@ -656,15 +669,12 @@ def eval_pcd(gt_points, rec_points, dist_thres=(0.03,), transform=None, gt_keep=
     thres = [float(t) for t in dist_thres]
     if len(thres) > PCD_THRES_MAX:
         raise RuntimeError(f"dqo_eval.eval_pcd: at most {PCD_THRES_MAX} thresholds, got {len(thres)}")
-    if out is None:
-        out, row = torch.empty((1, 32), dtype=torch.float32, device=dev), 0
-    if out.dim() != 2 or out.shape[1] != 32 or out.dtype != torch.float32 or not out.is_contiguous() or not 0 <= int(row) < out.shape[0]:
-        raise RuntimeError("dqo_eval.eval_pcd: out must be a contiguous float32 [K,32] table and row one of its rows")
-    ws = workspace_buffer if workspace_buffer is not None else _workspace(("pcd", _dev_index(dev), G, P), _pcd_bytes(G, P), dev)
+    out, row = _table_row(out, row, 32, "eval_pcd", dev, fresh=torch.empty)
+    ws = _ws(workspace_buffer, dev, lambda: _pcd_bytes(G, P), "pcd", G, P)
     with torch.cuda.device(dev):
         N.check(lib.dqo_eval_pcd(G, N.ptr(gt), N.ptr(gk), P, N.ptr(rec), N.ptr(rk), N.ptr(xf), len(thres), (ctypes.c_float * len(thres))(*thres),
-                                 out.data_ptr(), int(row), ws.data_ptr(), ws.numel(), N.current_stream()))
-    return out[int(row)]
+                                 out.data_ptr(), row, ws.data_ptr(), ws.numel(), N.current_stream()))
+    return out[row]
 
 
 def eval_pcd_dict(row_tensor, dist_thres=(0.03,)):
@@ -683,12 +693,13 @@ def eval_pcd_dict(row_tensor, dist_thres=(0.03,)):
     return results
 
 
+def _pcd_objects_bytes(n_gt, n_rec):
+    return _pcd_bytes(n_gt, n_rec, "dqo_eval_pcd_grouped_workspace_bytes")
+
+
 def pcd_objects_workspace(n_gt, n_rec, device):
     """dqo_eval_pcd_grouped's workspace for these sizes as a uint8 tensor (zero when first used, handed back ready by every call)."""
-    n = N.lib().dqo_eval_pcd_grouped_workspace_bytes(int(n_gt), int(n_rec))
-    if n == 0:
-        raise RuntimeError(f"dqo_eval: bad point counts {n_gt}, {n_rec} (at most 2^25 - 1 rows per set)")
-    return torch.zeros((n,), dtype=torch.uint8, device=device)
+    return torch.zeros((_pcd_objects_bytes(n_gt, n_rec),), dtype=torch.uint8, device=device)
 
 
 def eval_pcd_objects(gt_points, gt_object, rec_points, rec_object, dist_thres=(0.01,), transform=None, out=None, row=0, workspace_buffer=None):
@@ -714,23 +725,13 @@ def eval_pcd_objects(gt_points, gt_object, rec_points, rec_object, dist_thres=(0
     thres = [float(t) for t in dist_thres]
     if len(thres) > PCD_THRES_MAX:
         raise RuntimeError(f"dqo_eval.eval_pcd_objects: at most {PCD_THRES_MAX} thresholds, got {len(thres)}")
-    if out is None:
-        out, row = torch.empty((OBJECTS, 32), dtype=torch.float32, device=dev), 0
-    if (out.dim() != 2 or out.shape[1] != 32 or out.dtype != torch.float32 or not out.is_contiguous()
-            or not 0 <= int(row) <= out.shape[0] - OBJECTS):
-        raise RuntimeError(f"dqo_eval.eval_pcd_objects: out must be a contiguous float32 [K,32] table and [row, row + {OBJECTS}) rows of it")
-    if workspace_buffer is not None:
-        ws = workspace_buffer
-    else:
-        n = lib.dqo_eval_pcd_grouped_workspace_bytes(G, P)
-        if n == 0:
-            raise RuntimeError(f"dqo_eval: bad point counts {G}, {P} (at most 2^25 - 1 rows per set)")
-        ws = _workspace(("pcd_objects", _dev_index(dev), G, P), n, dev)
+    out, row = _table_row(out, row, 32, "eval_pcd_objects", dev, rows=OBJECTS, fresh=torch.empty)
+    ws = _ws(workspace_buffer, dev, lambda: _pcd_objects_bytes(G, P), "pcd_objects", G, P)
     with torch.cuda.device(dev):
         N.check(lib.dqo_eval_pcd_grouped(G, N.ptr(gt), N.ptr(gg), P, N.ptr(rec), N.ptr(rg), N.ptr(xf), len(thres),
-                                         (ctypes.c_float * len(thres))(*thres), out.data_ptr(), int(out.shape[0]), int(row), ws.data_ptr(),
+                                         (ctypes.c_float * len(thres))(*thres), out.data_ptr(), int(out.shape[0]), row, ws.data_ptr(),
                                          ws.numel(), N.current_stream()))
-    return out[int(row):int(row) + OBJECTS]
+    return out[row:row + OBJECTS]
 
 
 def eval_pcd_objects_dict(table, dist_thres=(0.01,)):
@@ -808,7 +809,7 @@ def eval_ate(pose_es, pose_gt, out=None, fit=None, workspace_buffer=None):
     need = lib.dqo_eval_ate_workspace_bytes(n)
     if need == 0:
         raise RuntimeError(f"dqo_eval.eval_ate: bad point count {n}")
-    ws = workspace_buffer if workspace_buffer is not None else _workspace(("ate", _dev_index(dev), n), need, dev)
+    ws = _ws(workspace_buffer, dev, need, "ate", n)
     with torch.cuda.device(dev):
         # model = ground truth, data = estimate: Tracker.eval_ate calls eval_ate(pose_gt, pose_es) (:429)
         N.check(lib.dqo_eval_ate(n, gt_p, gt_s, gt_c, es_p, es_s, es_c, out.data_ptr(), N.ptr(fit), ws.data_ptr(), ws.numel(), N.current_stream()))
@@ -962,11 +963,37 @@ def _mesh(mesh, who):
 
 
 def _mesh_ws(kind, workspace_buffer, dev, cv, cf):
-    need = getattr(N.lib(), f"dqo_mesh_{kind}_workspace_bytes")(cv, cf)
-    if workspace_buffer is None:
-        return _workspace(("mesh_" + kind, _dev_index(dev), cv, cf), need, dev)
-    N.require_gpu_op(workspace_buffer)
-    return workspace_buffer
+    if workspace_buffer is not None:
+        N.require_gpu_op(workspace_buffer)
+    return _ws(workspace_buffer, dev, lambda: getattr(N.lib(), f"dqo_mesh_{kind}_workspace_bytes")(cv, cf), "mesh_" + kind, cv, cf)
+
+
+def _own_mesh_out(tag, dev, cv, cf, colors):
+    """This module's own out mesh of one operator (`tag`) for a device and capacities, made on first use."""
+    key = (tag, _dev_index(dev), cv, cf, colors)
+    out = _mesh_outs.get(key)
+    if out is None:
+        out = _mesh_outs[key] = dict(vertices=torch.empty((cv, 3), dtype=torch.float32, device=dev),
+                                     faces=torch.empty((cf, 3), dtype=torch.int32, device=dev),
+                                     header=torch.empty((8,), dtype=torch.int32, device=dev))
+        if colors:
+            out["colors"] = torch.empty((cv, 3), dtype=torch.float32, device=dev)
+    return out
+
+
+def _out_mesh(who, out, dev, cv, cf, colors, header_is="out['header'] is int32 [8]"):
+    """The out mesh of mesh_components, mesh_simplify and mesh_cull: the caller's, or (None) the module's own for the operator — its
+    cache is the operator's alone — with a header; checked as a mesh whose header has 8 words.  Returns (out, _mesh(out)'s tuple)."""
+    if out is None:
+        out = _own_mesh_out(who, dev, cv, cf, colors)
+    if "header" not in out:
+        out["header"] = torch.empty((8,), dtype=torch.int32, device=dev)
+    if colors and "colors" not in out:
+        raise RuntimeError(f"dqo_eval.{who}: the mesh has colors, out has none")
+    parts = _mesh(out, who)
+    if parts[3].numel() != 8:
+        raise RuntimeError(f"dqo_eval.{who}: {header_is}")
+    return out, parts
 
 
 def mesh_components(mesh, min_faces=0, largest_only=False, out=None, want_labels=False, workspace_buffer=None):
@@ -983,27 +1010,15 @@ def mesh_components(mesh, min_faces=0, largest_only=False, out=None, want_labels
     header must not be the input mesh's: the first launch clears it.  Eleven launches, nothing read back; mesh_counts reads a header."""
     v, c, f, h, cv, cf = _mesh(mesh, "mesh_components")
     dev = v.device
-    if out is None:
-        key = (_dev_index(dev), cv, cf, c is not None)
-        out = _mesh_outs.get(key)
-        if out is None:
-            out = _mesh_outs[key] = dict(vertices=torch.empty((cv, 3), dtype=torch.float32, device=dev),
-                                         faces=torch.empty((cf, 3), dtype=torch.int32, device=dev),
-                                         header=torch.empty((8,), dtype=torch.int32, device=dev))
-            if c is not None:
-                out["colors"] = torch.empty((cv, 3), dtype=torch.float32, device=dev)
-        if not want_labels:
-            out.pop("labels", None)  # (an earlier call's)
-    if "header" not in out:
-        out["header"] = torch.empty((8,), dtype=torch.int32, device=dev)
+    own, shapes = out is None, "out['header'] is int32 [8], out['labels'] a contiguous int32 [cap_faces] device tensor"
+    out, (ov, oc, of, oh, ocv, ocf) = _out_mesh("mesh_components", out, dev, cv, cf, c is not None, shapes)
+    if own and not want_labels:
+        out.pop("labels", None)  # (an earlier call's)
     if want_labels and "labels" not in out:
         out["labels"] = torch.empty((cf,), dtype=torch.int32, device=dev)
-    if c is not None and "colors" not in out:
-        raise RuntimeError("dqo_eval.mesh_components: the mesh has colors, out has none")
-    ov, oc, of, oh, ocv, ocf = _mesh(out, "mesh_components")
     labels = out["labels"] if want_labels else None
-    if oh.numel() != 8 or (labels is not None and (labels.dtype != torch.int32 or labels.numel() < cf or not labels.is_contiguous() or not labels.is_cuda)):
-        raise RuntimeError("dqo_eval.mesh_components: out['header'] is int32 [8], out['labels'] a contiguous int32 [cap_faces] device tensor")
+    if labels is not None and (labels.dtype != torch.int32 or labels.numel() < cf or not labels.is_contiguous() or not labels.is_cuda):
+        raise RuntimeError(f"dqo_eval.mesh_components: {shapes}")
     ws = _mesh_ws("components", workspace_buffer, dev, cv, cf)
     with torch.cuda.device(dev):
         N.check(N.lib().dqo_mesh_components(v.data_ptr(), N.ptr(c), f.data_ptr(), N.ptr(h), cv, cf, int(min_faces), 1 if largest_only else 0,
@@ -1029,22 +1044,7 @@ def mesh_simplify(mesh, voxel_size, origin=(0.0, 0.0, 0.0), out=None, workspace_
     Twelve launches, nothing read back."""
     v, c, f, h, cv, cf = _mesh(mesh, "mesh_simplify")
     dev = v.device
-    if out is None:
-        key = ("simplify", _dev_index(dev), cv, cf, c is not None)
-        out = _mesh_outs.get(key)
-        if out is None:
-            out = _mesh_outs[key] = dict(vertices=torch.empty((cv, 3), dtype=torch.float32, device=dev),
-                                         faces=torch.empty((cf, 3), dtype=torch.int32, device=dev),
-                                         header=torch.empty((8,), dtype=torch.int32, device=dev))
-            if c is not None:
-                out["colors"] = torch.empty((cv, 3), dtype=torch.float32, device=dev)
-    if "header" not in out:
-        out["header"] = torch.empty((8,), dtype=torch.int32, device=dev)
-    if c is not None and "colors" not in out:
-        raise RuntimeError("dqo_eval.mesh_simplify: the mesh has colors, out has none")
-    ov, oc, of, oh, ocv, ocf = _mesh(out, "mesh_simplify")
-    if oh.numel() != 8:
-        raise RuntimeError("dqo_eval.mesh_simplify: out['header'] is int32 [8]")
+    out, (ov, oc, of, oh, ocv, ocf) = _out_mesh("mesh_simplify", out, dev, cv, cf, c is not None)
     ox, oy, oz = (float(x) for x in origin)
     ws = _mesh_ws("simplify", workspace_buffer, dev, cv, cf)
     with torch.cuda.device(dev):
@@ -1115,19 +1115,6 @@ def mesh_counts(mesh):
 MESH_CULL_HEADER = ("vertices", "faces", "vertices_seen", "views_used", "faces_bad_index", "faces_removed", "vertices_removed", "zero")
 
 
-def _own_mesh_out(tag, dev, cv, cf, colors):
-    """This module's own out mesh of one operator (`tag`) for a device and capacities, made on first use."""
-    key = (tag, _dev_index(dev), cv, cf, colors)
-    out = _mesh_outs.get(key)
-    if out is None:
-        out = _mesh_outs[key] = dict(vertices=torch.empty((cv, 3), dtype=torch.float32, device=dev),
-                                     faces=torch.empty((cf, 3), dtype=torch.int32, device=dev),
-                                     header=torch.empty((8,), dtype=torch.int32, device=dev))
-        if colors:
-            out["colors"] = torch.empty((cv, 3), dtype=torch.float32, device=dev)
-    return out
-
-
 def mesh_cull(mesh, w2c, K, W, H, depth=None, view_keep=None, eps=0.03, near=0.0, depth_trunc=float("inf"), min_corners=3, out=None,
               want_views=False, workspace_buffer=None):
     """The mesh restricted to what the views see — the culling every mesh-evaluation protocol of dense SLAM applies to both meshes
@@ -1157,15 +1144,7 @@ def mesh_cull(mesh, w2c, K, W, H, depth=None, view_keep=None, eps=0.03, near=0.0
         if view_keep.dtype != torch.uint8 or view_keep.numel() != n or not view_keep.is_contiguous() or view_keep.device != dev:
             raise RuntimeError(f"dqo_eval.mesh_cull: view_keep must be a contiguous uint8 / bool [{n}] tensor on the mesh's device")
     fx, fy, cx, cy = _intrinsics(K)
-    if out is None:
-        out = _own_mesh_out("cull", dev, cv, cf, c is not None)
-    if "header" not in out:
-        out["header"] = torch.empty((8,), dtype=torch.int32, device=dev)
-    if c is not None and "colors" not in out:
-        raise RuntimeError("dqo_eval.mesh_cull: the mesh has colors, out has none")
-    ov, oc, of, oh, ocv, ocf = _mesh(out, "mesh_cull")
-    if oh.numel() != 8:
-        raise RuntimeError("dqo_eval.mesh_cull: out['header'] is int32 [8]")
+    out, (ov, oc, of, oh, ocv, ocf) = _out_mesh("mesh_cull", out, dev, cv, cf, c is not None)
     vv = None
     if want_views:
         vv = out.get("vertex_views")
@@ -1201,15 +1180,12 @@ def sample_surface_counted(mesh, count, seed=0, want_face_index=False, workspace
         raise RuntimeError(f"dqo_eval.sample_surface_counted: bad sizes: {cf} faces of capacity, count = {count}: each in [1, 2^25 - 1]")
     if workspace_buffer is not None:
         N.require_gpu_op(workspace_buffer)
-    ws = workspace_buffer if workspace_buffer is not None else _workspace(("mesh_counted", _dev_index(dev), cf, count), nbytes, dev)
-    points = torch.empty((count, 3), dtype=torch.float32, device=dev)
-    face_index = torch.empty((count,), dtype=torch.int32, device=dev) if want_face_index else None
-    keep = torch.empty((count,), dtype=torch.uint8, device=dev)
-    header = torch.empty((8,), dtype=torch.int32, device=dev)
+    ws = _ws(workspace_buffer, dev, nbytes, "mesh_counted", cf, count)
+    o, ptrs = _sample_outs(count, want_face_index, dev)
     with torch.cuda.device(dev):
-        N.check(N.lib().dqo_mesh_sample_counted(v.data_ptr(), f.data_ptr(), N.ptr(h), cv, cf, count, int(seed) & (2 ** 64 - 1), N.ptr(points),
-                                                N.ptr(face_index), N.ptr(keep), N.ptr(header), ws.data_ptr(), ws.numel(), N.current_stream()))
-    return dict(points=points, face_index=face_index, keep=keep, header=header)
+        N.check(N.lib().dqo_mesh_sample_counted(v.data_ptr(), f.data_ptr(), N.ptr(h), cv, cf, count, int(seed) & (2 ** 64 - 1), *ptrs,
+                                                ws.data_ptr(), ws.numel(), N.current_stream()))
+    return o
 
 
 def eval_mesh(rec_mesh, gt_mesh, sample_nums=1000000, seed=0, rec_seed=None, dist_thres=(0.03,), transform=None, views=None, out=None, row=0):

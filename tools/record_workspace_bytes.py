@@ -1,0 +1,102 @@
+"""The size of every caller-owned buffer of libdqoraster.so over a fixed argument grid: every *_workspace_bytes export and the
+rasteriser context's size queries.  A workspace's size is its layout function at a null base, so a part that moves, grows
+or is taken in another order shows here as a changed number.  tests/workspace_bytes_parent.json holds the table of the commit before
+the layouts were unified; tests/test_workspace_layouts.py rebuilds it from the library of the tree and compares entry by entry.
+
+The grid sits on the steps where a part crosses a 256-byte alignment or a span of 2048: mesh capacities, the sampler's face counts,
+TSDF dims, image sizes (MS-SSIM's and LPIPS' smallest sides among them), point counts — and arguments every query must answer with 0.
+
+    python tools/record_workspace_bytes.py [--lib path/to/libdqoraster.so] [--out tests/workspace_bytes_parent.json]
+"""
+import argparse
+import ctypes
+import itertools
+import json
+import os
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEFAULT_LIB = os.path.join(ROOT, "dqo-map_amd", "lib", "libdqoraster.so")
+DEFAULT_OUT = os.path.join(ROOT, "tests", "workspace_bytes_parent.json")
+
+MESH_CAPS = [1, 2, 255, 256, 257, 2047, 2048, 2049, 6498, 100000, 1 << 22, (1 << 28) - 1]
+MESH_BAD = [(0, 1), (1, 0), (-1, 5), (1 << 28, 1), (1, 1 << 28)]
+SAMPLE_F = [1, 1023, 1024, 1025, 100000, (1 << 25) - 1]
+SAMPLE_COUNT = [1, 257, (1 << 25) - 1]
+SAMPLE_BAD = [(0, 1), (1, 0), (1 << 25, 1), (1, 1 << 25)]
+TSDF_DIMS = [(2, 2, 2), (3, 5, 7), (65, 4, 3), (64, 64, 64), (645, 645, 645)]
+TSDF_BAD = [(1, 2, 2), (2, 2, 0), (646, 646, 646), (1 << 28, 2, 2)]
+IMAGES = [(1, 1), (15, 17), (16, 16), (33, 17), (64, 48), (1200, 680)]
+IMAGES_LPIPS = [(31, 31), (31, 47), (64, 48)]      # both sides at least 31
+IMAGES_MSSSIM = [(161, 161), (161, 203), (203, 177)]  # both sides above 160
+IMAGES_BAD = [(0, 1), (1, 0), (-3, 5), (46341, 46341)]
+POINTS = [1, 255, 256, 4097, (1 << 25) - 1]
+POINTS_BAD = [-1, 1 << 25]
+
+I32, I64 = ctypes.c_int32, ctypes.c_int64
+
+
+def _queries():
+    """(export, argument types, argument tuples)"""
+    mesh = list(itertools.product(MESH_CAPS, MESH_CAPS)) + MESH_BAD
+    for name in ("components", "smooth", "normals", "simplify", "cull"):
+        yield f"dqo_mesh_{name}_workspace_bytes", (I32, I32), mesh
+    sample = list(itertools.product(SAMPLE_F, SAMPLE_COUNT)) + SAMPLE_BAD
+    yield "dqo_mesh_sample_workspace_bytes", (I32, I32), sample
+    yield "dqo_mesh_sample_counted_workspace_bytes", (I32, I32), sample
+    yield "dqo_tsdf_workspace_bytes", (I32, I32, I32), TSDF_DIMS + TSDF_BAD
+    images = IMAGES + IMAGES_LPIPS + IMAGES_MSSSIM + IMAGES_BAD
+    for name in ("dqo_map_ssim_workspace_bytes", "dqo_growth_sample_workspace_bytes", "dqo_eval_picture_workspace_bytes",
+                 "dqo_window_masks_workspace_bytes", "dqo_eval_ms_ssim_workspace_bytes", "dqo_eval_lpips_workspace_bytes",
+                 "dqo_track_preprocess_workspace_bytes"):
+        yield name, (I32, I32), images
+    yield "dqo_rast_image_bytes", (I32, I32), IMAGES + IMAGES_LPIPS + IMAGES_MSSSIM  # (no argument check of its own)
+    points = POINTS + POINTS_BAD
+    for name in ("dqo_knn3_workspace_bytes", "dqo_prune_workspace_bytes", "dqo_map_lifecycle_workspace_bytes", "dqo_map_pack_workspace_bytes",
+                 "dqo_map_attach_workspace_bytes", "dqo_eval_ate_workspace_bytes"):
+        yield name, (I32,), [(n,) for n in [0] + points]
+    pairs = list(itertools.product([0] + POINTS, [0] + POINTS)) + [(-1, 1), (1, 1 << 25)]
+    for name in ("dqo_knn3_query_workspace_bytes", "dqo_nn1_workspace_bytes", "dqo_nn1_grouped_workspace_bytes", "dqo_eval_pcd_workspace_bytes",
+                 "dqo_eval_pcd_grouped_workspace_bytes"):
+        yield name, (I32, I32), pairs
+    yield "dqo_rast_geom_bytes", (I32, I32, I32), [(n, 1200, 680) for n in [0] + points]
+    caps = [0, 1, 255, 256, 4097, 1 << 22, -1]
+    yield "dqo_rast_binning_bytes", (I64,), [(c,) for c in caps]
+    yield "dqo_rast_backward_workspace_bytes", (I64,), [(c,) for c in caps]
+    yield "dqo_rast_binning_bytes_bucketed", (I64, I32, I32, I32), [(c, w, h, b) for c in (0, 4097) for w, h in IMAGES for b in (0, 64, 1000)]
+    yield "dqo_surfel_densify_workspace_bytes", (I32, I32, I32, I32), [(n, c, l, s) for n in [0] + points for c, l, s in ((8, 1, 1), (12, 3, 2), (0, 1, 1))]
+    for name in ("dqo_icp_workspace_bytes", "dqo_map_loss_workspace_bytes", "dqo_track_pyramid_workspace_bytes", "dqo_track_p2p_workspace_bytes"):
+        yield name, (), [()]
+
+
+def key(name, args):
+    return f"{name}({', '.join(str(a) for a in args)})"
+
+
+def table(lib_path=DEFAULT_LIB):
+    """{"export(arguments)": bytes} over the grid, from the library at lib_path"""
+    lib = ctypes.CDLL(lib_path)
+    out = {}
+    for name, types, rows in _queries():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = list(types), ctypes.c_size_t
+        for args in rows:
+            out[key(name, args)] = int(fn(*args))
+    return out
+
+
+def exports(header_path=os.path.join(ROOT, "include", "dqo_raster.h")):
+    """the size queries the public header declares: the grid must name every one of them"""
+    import re
+    return sorted(set(re.findall(r"^size_t (dqo_\w+_bytes\w*)\(", open(header_path).read(), re.M)))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--lib", default=DEFAULT_LIB)
+    ap.add_argument("--out", default=DEFAULT_OUT)
+    a = ap.parse_args()
+    t = table(a.lib)
+    with open(a.out, "w") as f:
+        json.dump(t, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print(f"{len(t)} entries -> {a.out}")
