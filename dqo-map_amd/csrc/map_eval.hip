@@ -311,6 +311,130 @@ inline PcgWorkspace pcg_ws(void* base, int n_gt, int n_rec) {
     return w;
 }
 
+// ---- Depth L1: two depth stacks compared pixel by pixel (the NICE-SLAM lineage's number; include/dqo_raster.h, dqo_eval_depth_l1) ------
+// a = the truth, b = the other, float32 [n,H,W], 0 = no hit.  Per pixel of a used view: ha = a > 0 && a <= depth_trunc, hb = b > 0; the
+// differences in double from the floats (exact), a side without a hit taken as 0.  Launch 1: a block takes DL_PIX * 256 pixels of ONE
+// view and stores seven double sums and the float maximum as one 64-byte line (eval_picture_kernel's order: a thread its pixels in order,
+// dqo_block_partial).  Launch 2: block k adds view k's lines IN BLOCK-INDEX ORDER and writes row k; the block that takes the last ticket
+// reads the n rows back and writes row n.  No float or double atomic: a table is bitwise reproducible (tests/depth_l1_oracle.py).
+enum {
+    DL_PIX = 4,      // pixels per thread
+    DL_SUMS = 7,     // |a - b| valid | (a - b)^2 valid | |a' - b'| every pixel | both | only a | only b | neither
+    DL_STRIDE = 8,   // doubles per line: the sums and, in word 7, the largest |a - b| of the valid pixels (a float, widened)
+    DL_STAGE = 256,
+    DL_MAX_HW = 1 << 24,  // a view's counts are exact float32
+};
+
+struct DlArgs {
+    int32_t HW, bpv, n_views;  // bpv: blocks (lines) per view
+    const float *a, *b;
+    const uint8_t* view_keep;
+    float depth_trunc;
+};
+
+inline int64_t dl_bpv(int64_t HW) { return (HW + 256 * DL_PIX - 1) / (256 * DL_PIX); }
+inline bool dl_size_ok(int64_t n, int64_t W, int64_t H) {
+    return n >= 1 && n <= 65535 && W >= 1 && H >= 1 && W * H < DL_MAX_HW && n * dl_bpv(W * H) < (1ll << 30);
+}
+inline DqoLayout<EvWorkspace> dl_ws(void* base, int64_t n, int64_t HW) {
+    DqoCarver k(base);
+    const EvWorkspace w = ev_take(k, (size_t)(n * dl_bpv(HW)), DL_STRIDE);
+    return {w, k.total()};
+}
+
+// the block's maximum of non-negative floats (compared as their bits), for every thread.  s_max: 4 words, free again after a barrier
+__device__ __forceinline__ float dl_block_max(float m, uint32_t* s_max) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t wm = dqo_wave_max_u32(__float_as_uint(m), lane);
+    if (lane == 0) s_max[wave] = wm;
+    __syncthreads();
+    return __uint_as_float(max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3])));
+}
+
+__global__ __launch_bounds__(256) void depth_l1_partial_kernel(DlArgs g, EvWorkspace w) {
+    __shared__ double s_stage[4 * DL_STRIDE];
+    __shared__ uint32_t s_max[4];
+    const int tid = threadIdx.x;
+    const int k = (int)(blockIdx.x / (uint32_t)g.bpv), j = (int)(blockIdx.x % (uint32_t)g.bpv);
+    if (g.view_keep != nullptr && g.view_keep[k] == 0) return;  // (block-uniform: an unused view has no lines)
+    const float* __restrict__ a = g.a + (size_t)k * (size_t)g.HW;
+    const float* __restrict__ b = g.b + (size_t)k * (size_t)g.HW;
+    double s[DL_SUMS];
+#pragma unroll
+    for (int q = 0; q < DL_SUMS; q++) s[q] = 0.0;
+    float mx = 0.0f;
+#pragma unroll
+    for (int p = 0; p < DL_PIX; p++) {
+        const int64_t i = ((int64_t)j * DL_PIX + p) * 256 + tid;
+        if (i < g.HW) {
+            const float av = a[i], bv = b[i];
+            const bool ha = av > 0.0f && av <= g.depth_trunc, hb = bv > 0.0f;
+            const double diff = (ha ? (double)av : 0.0) - (hb ? (double)bv : 0.0), ad = fabs(diff);
+            s[2] += ad;
+            if (ha && hb) {
+                s[0] += ad, s[1] += diff * diff, s[3] += 1.0;
+                mx = fmaxf(mx, (float)ad);
+            } else if (ha) s[4] += 1.0;
+            else if (hb) s[5] += 1.0;
+            else s[6] += 1.0;
+        }
+    }
+    const float bm = dl_block_max(mx, s_max);
+    dqo_block_partial<DL_SUMS, DL_STRIDE>(s, s_stage, w.partial);
+    if (tid == DL_SUMS) __hip_atomic_store(&w.partial[(size_t)blockIdx.x * DL_STRIDE + DL_SUMS], (double)bm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// grid: n_views blocks.  table: float32 [n_views + 1][8]
+__global__ __launch_bounds__(256) void depth_l1_rows_kernel(DlArgs g, EvWorkspace w, float* __restrict__ table) {
+    __shared__ double s_stage[DL_STAGE * DL_STRIDE];
+    __shared__ double s_tot[DL_STRIDE];
+    __shared__ uint32_t s_max[4];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, k = (int)blockIdx.x;
+    const float nan = __int_as_float(0x7fc00000);
+    float* const row = table + (size_t)8 * k;
+    if (g.view_keep != nullptr && g.view_keep[k] == 0) {
+        if (tid < 8) __hip_atomic_store(&row[tid], nan, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+        const int first = k * g.bpv, last = first + g.bpv;
+        const double total = dqo_fold_partials<DL_SUMS, DL_STRIDE, DL_STAGE>(w.partial, first, last, s_stage);
+        float mx = 0.0f;
+        for (int j = first + tid; j < last; j += 256)
+            mx = fmaxf(mx, (float)__hip_atomic_load(&w.partial[(size_t)j * DL_STRIDE + DL_SUMS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        mx = dl_block_max(mx, s_max);
+        if (tid < DL_SUMS) s_tot[tid] = total;
+        __syncthreads();
+        if (tid == 0) {
+            const double both = s_tot[3];
+            float r[8];
+            r[0] = (float)(s_tot[0] / both);  // (both == 0: 0 / 0 = NaN)
+            r[1] = both > 0.0 ? (float)(s_tot[2] / (double)g.HW) : nan;
+            r[2] = (float)sqrt(s_tot[1] / both);
+            r[3] = (float)both, r[4] = (float)s_tot[4], r[5] = (float)s_tot[5], r[6] = (float)s_tot[6];
+            r[7] = mx;
+#pragma unroll
+            for (int q = 0; q < 8; q++) __hip_atomic_store(&row[q], r[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if (!dqo_last_block(w.ticket, &s_last)) return;
+    // row n, column q by thread q over the rows in view order: 0-2 the mean of the rows where the value is defined, 3-6 the sum, 7 the maximum
+    float* const stage = reinterpret_cast<float*>(s_stage);  // DL_STAGE rows of 8 floats
+    double sum = 0.0, cnt = 0.0;
+    float mx = 0.0f;
+    for (int base = 0; base < g.n_views; base += DL_STAGE) {
+        const int m = min((int)DL_STAGE, g.n_views - base);
+        for (int j = tid; j < m * 8; j += 256) stage[j] = __hip_atomic_load(&table[(size_t)base * 8 + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (tid < 8)
+            for (int v = 0; v < m; v++) {
+                const float x = stage[v * 8 + tid];
+                if (x == x) sum += (double)x, cnt += 1.0, mx = fmaxf(mx, x);
+            }
+        __syncthreads();
+    }
+    if (tid < 8) table[(size_t)8 * g.n_views + tid] = tid < 3 ? (float)(sum / cnt) : (tid < 7 ? (cnt > 0.0 ? (float)sum : nan) : (cnt > 0.0 ? mx : nan));
+}
+
 }  // namespace
 
 static size_t dqo_eval_ws_bytes(int64_t HW) { return ev_ws(nullptr, HW).total; }
@@ -417,6 +541,28 @@ DQO_API int dqo_eval_pcd_grouped(int32_t n_gt, const float* gt_xyz, const int32_
     DQO_CHECK_WS("eval_pcd grouped", ws, ws_bytes, pcg_ws(nullptr, n_gt, n_rec).total);
     return dqo_launch_eval_pcd_grouped(n_gt, gt_xyz, gt_group, n_rec, rec_xyz, rec_group, rec_xform, n_thres, thres_host,
                                        out_table + (size_t)32 * first_row, ws, (hipStream_t)stream);
+}
+
+// Depth L1 of two depth stacks: a row per view and the row of the whole set
+DQO_API size_t dqo_eval_depth_l1_workspace_bytes(int32_t n_views, int32_t W, int32_t H) {
+    return dl_size_ok(n_views, W, H) ? dl_ws(nullptr, n_views, (int64_t)W * H).total : 0;
+}
+
+DQO_API int dqo_eval_depth_l1(int32_t n_views, int32_t W, int32_t H, const float* a, const float* b, const uint8_t* view_keep, float depth_trunc,
+                              float* out_table, void* ws, size_t ws_bytes, void* stream) {
+    DQO_CHECK_ARG(n_views >= 1 && n_views <= 65535, "bad n_views %d: 1 to 65535 views", n_views);
+    DQO_CHECK_ARG(dl_size_ok(n_views, W, H), "bad image size %d x %d for %d views: both sides are at least 1, W * H is below 2^24", W, H, n_views);
+    DQO_CHECK_ARG(a && b && out_table, "null pointer");
+    DQO_CHECK_ARG(depth_trunc > 0.0f, "bad depth_trunc: it is above 0 (it may be +inf)");
+    const int64_t HW = (int64_t)W * H;
+    DQO_CHECK_WS("depth L1", ws, ws_bytes, dl_ws(nullptr, n_views, HW).total);
+    DlArgs g;
+    g.HW = (int32_t)HW, g.bpv = (int32_t)dl_bpv(HW), g.n_views = n_views, g.a = a, g.b = b, g.view_keep = view_keep, g.depth_trunc = depth_trunc;
+    const EvWorkspace w = dl_ws(ws, n_views, HW).w;
+    hipStream_t s = (hipStream_t)stream;
+    DQO_LAUNCH("depth_l1_partial_kernel", depth_l1_partial_kernel, dim3((unsigned)(n_views * g.bpv)), dim3(256), s, g, w);
+    DQO_LAUNCH("depth_l1_rows_kernel", depth_l1_rows_kernel, dim3((unsigned)n_views), dim3(256), s, g, w, out_table);
+    return DQO_OK;
 }
 
 }  // extern "C"

@@ -106,6 +106,18 @@ restates them), on the mesh dict extract() returns, nothing read back:
 
 FusedMapper.make_clean_mesh chains them behind make_mesh (make_simplified_mesh: with mesh_simplify); dqo_ply.write_mesh_ply_normals writes the result.
 
+Depth L1 — the one number of the dense-SLAM evaluation protocols (the NICE-SLAM lineage) that needs a mesh as an IMAGE: both meshes
+rendered to depth from the frames' cameras and compared pixel by pixel (csrc/map_meshrender.hip, a triangle depth rasteriser whose rule
+include/dqo_raster.h states and tests/mesh_render_oracle.py restates; csrc/map_eval.hip, dqo_eval_depth_l1):
+
+    mesh_render_depth(mesh, w2c, K, W, H, ...)              ->  dict(depth [n,H,W], face_index | None, header, header_names)
+    depth_l1(depth_gt, depth_rec, view_keep, depth_trunc)   ->  float32 [n + 1, 8] on the device (DEPTH_L1_ROW), a row per view and the set's
+    depth_l1_dict(table)                                    ->  the rows as dicts (the ONE host read)
+    eval_mesh_depth(rec_mesh, gt_mesh, views)               ->  both meshes rendered, the table
+
+FusedMapper.evaluate_mesh_depth forms the views from frames, and with mesh=None compares the map's own render.  Not built: near-plane
+clipping, back-face culling, per-view intrinsics, colour or normal shading of the mesh.
+
 GPU only: there is no CPU path.
 """
 import ctypes
@@ -1115,6 +1127,19 @@ def mesh_counts(mesh):
 MESH_CULL_HEADER = ("vertices", "faces", "vertices_seen", "views_used", "faces_bad_index", "faces_removed", "vertices_removed", "zero")
 
 
+def _views(who, w2c, view_keep, dev):
+    """(n, view_keep as uint8 or None) of an operator's views, checked: w2c float32 [n,16] or [n,4,4], view_keep uint8 / bool [n]."""
+    if w2c.dtype != torch.float32 or not w2c.is_contiguous() or w2c.numel() % 16 != 0 or w2c.numel() == 0 or w2c.device != dev:
+        raise RuntimeError(f"dqo_eval.{who}: w2c must be a contiguous float32 [n,16] or [n,4,4] tensor on the mesh's device")
+    n = w2c.numel() // 16
+    if view_keep is not None:
+        if view_keep.dtype == torch.bool:
+            view_keep = view_keep.view(torch.uint8)
+        if view_keep.dtype != torch.uint8 or view_keep.numel() != n or not view_keep.is_contiguous() or view_keep.device != dev:
+            raise RuntimeError(f"dqo_eval.{who}: view_keep must be a contiguous uint8 / bool [{n}] tensor on the mesh's device")
+    return n, view_keep
+
+
 def mesh_cull(mesh, w2c, K, W, H, depth=None, view_keep=None, eps=0.03, near=0.0, depth_trunc=float("inf"), min_corners=3, out=None,
               want_views=False, workspace_buffer=None):
     """The mesh restricted to what the views see — the culling every mesh-evaluation protocol of dense SLAM applies to both meshes
@@ -1124,7 +1149,8 @@ def mesh_cull(mesh, w2c, K, W, H, depth=None, view_keep=None, eps=0.03, near=0.0
     is kept iff at least min_corners of its corners are seen by some used view; vertices no kept face names go).
     mesh: a mesh dict, as for mesh_components.  w2c: float32 device tensor [n,16] or [n,4,4], the views' world-to-camera matrices, row
     major; K: (fx, fy, cx, cy) or a 3 x 3 matrix, HOST numbers, and W, H: the camera all views share; depth: float32 [n,H,W] device
-    tensor in metres (None: frustum only); view_keep: uint8 / bool [n] device tensor, 0 = the view is not used (None: all are).
+    tensor in metres (None: frustum only) — the frames' depth, or, where no sensor depth exists, mesh_render_depth's stack of the
+    ground-truth mesh; view_keep: uint8 / bool [n] device tensor, 0 = the view is not used (None: all are).
     Returns a mesh dict in OTHER buffers (`out`, whose capacities must not be below the input's; default: this module's own for the
     capacities, overwritten by the next call) with header = the int32 [8] MESH_CULL_HEADER, words 0 and 1 the counts, "header_names"
     naming it for mesh_counts, and "vertex_views": with want_views int32 [cap_vertices], how many used views see each vertex (rows
@@ -1133,16 +1159,10 @@ def mesh_cull(mesh, w2c, K, W, H, depth=None, view_keep=None, eps=0.03, near=0.0
     v, c, f, h, cv, cf = _mesh(mesh, "mesh_cull")
     dev = v.device
     N.require_gpu_op((v, w2c), depth, view_keep)
-    if w2c.dtype != torch.float32 or not w2c.is_contiguous() or w2c.numel() % 16 != 0 or w2c.numel() == 0 or w2c.device != dev:
-        raise RuntimeError("dqo_eval.mesh_cull: w2c must be a contiguous float32 [n,16] or [n,4,4] tensor on the mesh's device")
-    n, W, H = w2c.numel() // 16, int(W), int(H)
+    n, view_keep = _views("mesh_cull", w2c, view_keep, dev)
+    W, H = int(W), int(H)
     if depth is not None and (tuple(depth.shape) != (n, H, W) or depth.dtype != torch.float32 or not depth.is_contiguous() or depth.device != dev):
         raise RuntimeError(f"dqo_eval.mesh_cull: depth must be a contiguous float32 [{n},{H},{W}] tensor on the mesh's device")
-    if view_keep is not None:
-        if view_keep.dtype == torch.bool:
-            view_keep = view_keep.view(torch.uint8)
-        if view_keep.dtype != torch.uint8 or view_keep.numel() != n or not view_keep.is_contiguous() or view_keep.device != dev:
-            raise RuntimeError(f"dqo_eval.mesh_cull: view_keep must be a contiguous uint8 / bool [{n}] tensor on the mesh's device")
     fx, fy, cx, cy = _intrinsics(K)
     out, (ov, oc, of, oh, ocv, ocf) = _out_mesh("mesh_cull", out, dev, cv, cf, c is not None)
     vv = None
@@ -1213,3 +1233,143 @@ def eval_mesh(rec_mesh, gt_mesh, sample_nums=1000000, seed=0, rec_seed=None, dis
     gt = sample_surface_counted(gt_mesh, sample_nums, seed=seed)
     rec = sample_surface_counted(rec_mesh, sample_nums, seed=int(seed) + 1 if rec_seed is None else rec_seed)
     return eval_pcd(gt["points"], rec["points"], dist_thres, transform, gt_keep=gt["keep"], rec_keep=rec["keep"], out=out, row=row)
+
+
+# ---- mesh depth and Depth L1 (csrc/map_meshrender.hip, map_eval.hip) ------------------------------------------------------------------------
+MESH_RENDER_HEADER = ("views_used", "faces_bad_index", "pairs_rasterised", "pairs_near_dropped", "pairs_degenerate", "pairs_cooperative",
+                      "pixels_hit", "zero")
+DEPTH_L1_ROW = ("l1_valid", "l1_image", "rmse_valid", "both", "only_a", "only_b", "neither", "max_abs")
+_render_outs = {}  # the module's own depth stacks, one per (tag, device, n, H, W)
+
+
+def _own_render_out(tag, dev, n, H, W):
+    key = (tag, _dev_index(dev), n, H, W)
+    out = _render_outs.get(key)
+    if out is None:
+        out = _render_outs[key] = dict(depth=torch.empty((n, H, W), dtype=torch.float32, device=dev),
+                                       header=torch.empty((8,), dtype=torch.int32, device=dev))
+    return out
+
+
+def mesh_render_depth(mesh, w2c, K, W, H, view_keep=None, near=0.0, depth_trunc=float("inf"), want_face_index=False, out=None,
+                      workspace_buffer=None):
+    """The mesh rasterised to depth in n views — the render whose depths the Depth L1 number compares (include/dqo_raster.h,
+    dqo_mesh_render_depth, states the rule: corners projected by mesh_cull's own float32 statements without its + 0.5, so pixel centres
+    sit at integer coordinates; edge functions in double, ordered by vertex id, so two faces that share an edge leave no pixel between
+    them; coverage inclusive, both sides of a face; depth by ray-plane intersection in double; a pixel keeps the nearest face, the
+    lower face id at equal depth, whatever order the faces arrive in).  A face that crosses the near plane of a view is dropped there
+    and counted, not clipped.
+    mesh: a mesh dict, as for mesh_components.  w2c, K, W, H, view_keep, near, depth_trunc: mesh_cull's.  Returns dict(depth float32
+    [n,H,W], 0 = no hit; face_index int32 [n,H,W], -1 = no hit, or None without want_face_index; header int32 [8]; header_names =
+    MESH_RENDER_HEADER, by which mesh_counts reads the header) in `out` (a dict with such tensors; default: this module's own for the
+    device and sizes, overwritten by the next call); the images of unused views are written as no hit.  The depth stack is a `depth`
+    for mesh_cull: the ground-truth mesh's own render serves its occlusion test where no sensor depth exists.
+    workspace_buffer: a uint8 tensor of dqo_mesh_render_depth_workspace_bytes(n, W, H) bytes the caller keeps, zero when first used
+    (default: one per device and sizes, kept by this module).  Three launches, nothing read back, no synchronise; capturable in a graph."""
+    v, c, f, h, cv, cf = _mesh(mesh, "mesh_render_depth")
+    dev = v.device
+    N.require_gpu_op((v, w2c), view_keep, workspace_buffer)
+    n, view_keep = _views("mesh_render_depth", w2c, view_keep, dev)
+    W, H = int(W), int(H)
+    fx, fy, cx, cy = _intrinsics(K)
+    nbytes = N.lib().dqo_mesh_render_depth_workspace_bytes(n, W, H)
+    if nbytes == 0:
+        raise RuntimeError(f"dqo_eval.mesh_render_depth: bad image size {W} x {H} for {n} views")
+    if out is None:
+        out = _own_render_out("render", dev, n, H, W)
+    if "depth" not in out:
+        out["depth"] = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+    if "header" not in out:
+        out["header"] = torch.empty((8,), dtype=torch.int32, device=dev)
+    fi = None
+    if want_face_index:
+        fi = out.get("face_index")
+        if fi is None:
+            fi = out.get("_face_index_buffer")  # (an earlier call's, kept while a call without want_face_index set the public key to None)
+        if fi is None:
+            fi = out["_face_index_buffer"] = torch.empty((n, H, W), dtype=torch.int32, device=dev)
+    d, oh = out["depth"], out["header"]
+    N.require_gpu_op((v, d, oh), fi)
+    for t, dt, name in ((d, torch.float32, "depth"), (fi, torch.int32, "face_index")):
+        if t is not None and (tuple(t.shape) != (n, H, W) or t.dtype != dt or not t.is_contiguous() or t.device != dev):
+            raise RuntimeError(f"dqo_eval.mesh_render_depth: out['{name}'] is a contiguous {dt} [{n},{H},{W}] tensor on the mesh's device")
+    if oh.dtype != torch.int32 or oh.numel() != 8 or not oh.is_contiguous() or oh.device != dev:
+        raise RuntimeError("dqo_eval.mesh_render_depth: out['header'] is int32 [8] on the mesh's device")
+    ws = _ws(workspace_buffer, dev, nbytes, "mesh_render", n, W, H)
+    with torch.cuda.device(dev):
+        N.check(N.lib().dqo_mesh_render_depth(v.data_ptr(), f.data_ptr(), N.ptr(h), cv, cf, n, w2c.data_ptr(), N.ptr(view_keep), W, H, fx, fy, cx, cy,
+                                              float(near), float(depth_trunc), d.data_ptr(), N.ptr(fi), oh.data_ptr(), ws.data_ptr(), ws.numel(),
+                                              N.current_stream()))
+    out["face_index"] = fi
+    out["header_names"] = MESH_RENDER_HEADER  # (what mesh_counts calls the words)
+    return out
+
+
+def depth_l1(depth_gt, depth_rec, view_keep=None, depth_trunc=float("inf"), out=None):
+    """Depth L1 of two depth stacks, on the device (include/dqo_raster.h, dqo_eval_depth_l1): depth_gt (the truth) and depth_rec,
+    float32 [n,H,W] device tensors, 0 = no hit — mesh_render_depth's, a stack of the map's renders, the sensor's.  A pixel is valid iff
+    0 < depth_gt <= depth_trunc and depth_rec > 0.  Returns the float32 [n + 1, 8] table (DEPTH_L1_ROW; `out`, or a new tensor): row k
+    of a used view = l1_valid (the mean of |gt - rec| over the valid pixels), l1_image (the mean over all pixels, a side without a hit
+    taken as 0: the NICE-SLAM form), rmse_valid, the counts both / only_a / only_b / neither, max_abs; NaN in the three means of a view
+    without a valid pixel, a row of NaN for an unused view (view_keep: uint8 / bool [n], 0 = unused); row n = the means of the used
+    views' three values where defined, the counts summed, the largest maximum.  Double sums added in a fixed order: the table is
+    bitwise reproducible.  Two launches, nothing read back; depth_l1_dict reads the table."""
+    N.require_gpu_op((depth_gt, depth_rec), view_keep, out)
+    dev = depth_gt.device
+    if depth_gt.dim() != 3 or depth_gt.dtype != torch.float32 or not depth_gt.is_contiguous():
+        raise RuntimeError("dqo_eval.depth_l1: depth_gt must be a contiguous float32 [n,H,W] device tensor")
+    n, H, W = (int(x) for x in depth_gt.shape)
+    if tuple(depth_rec.shape) != (n, H, W) or depth_rec.dtype != torch.float32 or not depth_rec.is_contiguous() or depth_rec.device != dev:
+        raise RuntimeError(f"dqo_eval.depth_l1: depth_rec must be a contiguous float32 [{n},{H},{W}] tensor on depth_gt's device")
+    if view_keep is not None:
+        if view_keep.dtype == torch.bool:
+            view_keep = view_keep.view(torch.uint8)
+        if view_keep.dtype != torch.uint8 or view_keep.numel() != n or not view_keep.is_contiguous() or view_keep.device != dev:
+            raise RuntimeError(f"dqo_eval.depth_l1: view_keep must be a contiguous uint8 / bool [{n}] tensor on depth_gt's device")
+    nbytes = N.lib().dqo_eval_depth_l1_workspace_bytes(n, W, H)
+    if nbytes == 0:
+        raise RuntimeError(f"dqo_eval.depth_l1: bad sizes: {n} views of {W} x {H}: 1 to 65535 views, W * H below 2^24")
+    if out is None:
+        out = torch.empty((n + 1, 8), dtype=torch.float32, device=dev)
+    if tuple(out.shape) != (n + 1, 8) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError(f"dqo_eval.depth_l1: out must be a contiguous float32 [{n + 1},8] tensor on depth_gt's device")
+    ws = _ws(None, dev, nbytes, "depth_l1", n, W, H)
+    with torch.cuda.device(dev):
+        N.check(N.lib().dqo_eval_depth_l1(n, W, H, depth_gt.data_ptr(), depth_rec.data_ptr(), N.ptr(view_keep), float(depth_trunc), out.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), N.current_stream()))
+    return out
+
+
+def depth_l1_dict(table):
+    """depth_l1's table as {"views": [a dict per view, None for an unused one], "mean": the last row's dict}, names DEPTH_L1_ROW, the
+    counts as ints: the ONE host read."""
+    rows = table.cpu().tolist()
+
+    def named(r):
+        if all(x != x for x in r):
+            return None
+        return {k: (x if i < 3 or i == 7 else int(x)) for i, (k, x) in enumerate(zip(DEPTH_L1_ROW, r))}
+
+    return dict(views=[named(r) for r in rows[:-1]], mean=named(rows[-1]))
+
+
+def eval_mesh_depth(rec_mesh, gt_mesh, views, out=None):
+    """Depth L1 of a reconstructed mesh against the ground-truth mesh, in one call on the device: both meshes rendered to depth from the
+    same views (mesh_render_depth), the two stacks compared (depth_l1, the ground truth as the truth).  rec_mesh, gt_mesh: mesh dicts,
+    as for eval_mesh.  views: eval_mesh's dict — w2c, K, W, H and optionally view_keep, near, depth_trunc; its other keys (depth, eps,
+    min_corners) belong to the cull and are ignored here.  depth_trunc applies to both renders and to the comparison.  The two depth
+    stacks live in buffers of this module's own, one pair per device and sizes.  Returns depth_l1's float32 [n + 1, 8] table (`out`,
+    or a new tensor); nothing is read back."""
+    if views is None:
+        raise RuntimeError("dqo_eval.eval_mesh_depth: views is a dict with w2c, K, W and H: a depth needs cameras")
+    kw = {k: x for k, x in dict(views).items() if k not in ("depth", "eps", "min_corners")}
+    for k in ("out", "want_face_index", "workspace_buffer"):
+        if k in kw:
+            raise RuntimeError(f"dqo_eval.eval_mesh_depth: views is a dict of the views' keywords; {k!r} is mesh_render_depth's own")
+    stacks = []
+    for tag, m in (("depth_gt", gt_mesh), ("depth_rec", rec_mesh)):
+        v = m["vertices"]
+        N.require_gpu_op((v, kw["w2c"]))
+        n, H, W = kw["w2c"].numel() // 16, int(kw["H"]), int(kw["W"])
+        stacks.append(mesh_render_depth(m, out=_own_render_out(tag, v.device, n, H, W), **kw)["depth"])
+    return depth_l1(stacks[0], stacks[1], view_keep=kw.get("view_keep"), depth_trunc=kw.get("depth_trunc", float("inf")), out=out)

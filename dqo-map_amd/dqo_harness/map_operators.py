@@ -76,7 +76,8 @@ class MapOperators:
         self._eval_ms_ws = None  # evaluate_ms_ssim(): dqo_eval.ms_ssim's workspace
         self._eval_lpips_ws = None  # evaluate_lpips(): dqo_eval.lpips' workspace
         self._mesh_w2c = None  # make_mesh(): the frame's world-to-camera matrix, row major, float32 [4,4] on the device
-        self._mesh_eval_views = {}  # evaluate_mesh(): per K, the views' w2c [K,16] and, once depths="render" asked for it, depth [K,H,W]
+        self._mesh_eval_views = {}  # evaluate_mesh(), evaluate_mesh_depth(): per (K, H, W), the views' w2c [K,16], once a render was asked for
+        # depth [K,H,W], and evaluate_mesh_depth's two mesh renders
         self._window_ratios, self._window_ws = {}, None  # refresh_window(): its [K] ratio table per K, dqo_window_masks' workspace
         self._sample_ctx, self.sample_header = None, None  # sample_new(): the sampler's row buffers and workspace; its last header
         self._drop_row_sized_operator_state()
@@ -505,7 +506,8 @@ class MapOperators:
         depths: None — frustum test only; "render" — the whole map rendered per frame on maintain()'s context (_maintain_render, as
         make_mesh does) and its depth copied into a [K,H,W] buffer this mapper keeps: the cull's occlusion test runs against the very
         pixels that made the mesh (NotImplementedError on a sharded mapper, whose render shows its objects only); a float32 [K,H,W]
-        device tensor — the caller's own depth, for example the sensor's.  eps, min_corners, depth_trunc: mesh_cull's.
+        device tensor — the caller's own depth, for example the sensor's, or the ground-truth mesh's own render
+        (dqo_eval.mesh_render_depth(gt, ...)["depth"]) where no sensor depth exists.  eps, min_corners, depth_trunc: mesh_cull's.
         sample_nums, seed, dist_thres, transform, out, row: eval_mesh's.  Returns the float32 [32] device row (dqo_eval.PCD_ROW;
         dqo_eval.eval_pcd_dict reads it).  Nothing is read back after the first render of a shape (make_mesh's one header read)."""
         gt = dict(vertices=gt_vertices, faces=gt_faces)
@@ -518,32 +520,67 @@ class MapOperators:
             raise ValueError(f"FusedMapper.evaluate_mesh: depths is None, 'render' or a [K,H,W] device tensor, got {depths!r}")
         if render:
             self._refuse_sharded("evaluate_mesh")
+        with torch.cuda.device(self.device):
+            bufs, K, W, H = self._frame_views("evaluate_mesh", frames, render)
+            views = dict(w2c=bufs["w2c"], K=K, W=W, H=H, depth=bufs["depth"] if render else depths, eps=eps, depth_trunc=depth_trunc,
+                         min_corners=min_corners)
+            return dqo_eval.eval_mesh(mesh, gt, sample_nums, seed, dist_thres=dist_thres, transform=transform, views=views, out=out, row=row)
+
+    def _frame_views(self, who, frames, render):
+        """What evaluate_mesh and evaluate_mesh_depth form from a list of raster settings (None in the list = the mapper's camera), on
+        the device: (bufs, K, W, H) — bufs: this mapper's buffers for (len(frames), H, W), with "w2c" float32 [K,16], each settings'
+        viewmatrix transposed as make_mesh does, and, with `render`, "depth" float32 [K,H,W]: the whole map rendered per frame on
+        maintain()'s context (_maintain_render); K = (fx, fy, cx, cy) with fx = W / (2 tanfovx), fy = H / (2 tanfovy).  The frames must
+        share one image size and one set of intrinsics: ValueError otherwise, before anything is made or launched."""
         raw = [self.settings if st is None else st for st in frames]
         if not raw:
-            raise ValueError("FusedMapper.evaluate_mesh: frames is empty (None is the evaluation without culling)")
+            raise ValueError(f"FusedMapper.{who}: frames is empty" + (" (None is the evaluation without culling)" if who == "evaluate_mesh" else ""))
         camera = lambda st: (int(st.image_width), int(st.image_height), float(st.tanfovx), float(st.tanfovy), float(st.cx), float(st.cy))
         W, H, tfx, tfy, cx, cy = camera(raw[0])
         for k, st in enumerate(raw):
             if camera(st) != (W, H, tfx, tfy, cx, cy):
-                raise ValueError(f"FusedMapper.evaluate_mesh: frame {k} has another image size or other intrinsics than frame 0 "
-                                 f"({camera(st)} against {(W, H, tfx, tfy, cx, cy)}): mesh_cull's views share one camera")
+                raise ValueError(f"FusedMapper.{who}: frame {k} has another image size or other intrinsics than frame 0 "
+                                 f"({camera(st)} against {(W, H, tfx, tfy, cx, cy)}): the views share one camera")
         K = len(raw)
-        with torch.cuda.device(self.device):
-            bufs = self._mesh_eval_views.setdefault((K, H, W), {})
-            if "w2c" not in bufs:
-                bufs["w2c"] = torch.empty((K, 16), dtype=torch.float32, device=self.device)
-            if render and "depth" not in bufs:
-                bufs["depth"] = torch.empty((K, H, W), dtype=torch.float32, device=self.device)
+        bufs = self._mesh_eval_views.setdefault((K, H, W), {})
+        if "w2c" not in bufs:
+            bufs["w2c"] = torch.empty((K, 16), dtype=torch.float32, device=self.device)
+        if render and "depth" not in bufs:
+            bufs["depth"] = torch.empty((K, H, W), dtype=torch.float32, device=self.device)
+        if render:
+            self.activate()
+        for k, st in enumerate(raw):
+            st = _normalised_settings(st, self.device)
+            bufs["w2c"][k].view(4, 4).copy_(st.viewmatrix.reshape(4, 4).t())  # (the settings keep the transposed w2c)
             if render:
-                self.activate()
-            for k, st in enumerate(raw):
-                st = _normalised_settings(st, self.device)
-                bufs["w2c"][k].view(4, 4).copy_(st.viewmatrix.reshape(4, 4).t())  # (the settings keep the transposed w2c)
-                if render:
-                    bufs["depth"][k].copy_(self._maintain_render(st).out[1].reshape(H, W))
-            views = dict(w2c=bufs["w2c"], K=(W / (2.0 * tfx), H / (2.0 * tfy), cx, cy), W=W, H=H, depth=bufs["depth"] if render else depths,
-                         eps=eps, depth_trunc=depth_trunc, min_corners=min_corners)
-            return dqo_eval.eval_mesh(mesh, gt, sample_nums, seed, dist_thres=dist_thres, transform=transform, views=views, out=out, row=row)
+                bufs["depth"][k].copy_(self._maintain_render(st).out[1].reshape(H, W))
+        return bufs, (W / (2.0 * tfx), H / (2.0 * tfy), cx, cy), W, H
+
+    @torch.no_grad()
+    def evaluate_mesh_depth(self, mesh, gt_vertices, gt_faces, frames, depth_trunc=float("inf"), out=None):
+        """Depth L1 of this mapper's reconstruction against the ground-truth mesh at the frames' cameras — the number the dense-SLAM
+        evaluation protocols report beside evaluate_mesh's: the ground-truth mesh rendered to depth per frame
+        (dqo_eval.mesh_render_depth) and compared pixel by pixel (dqo_eval.depth_l1, the ground truth as the truth) with
+        mesh given — that mesh (make_mesh's, make_clean_mesh's, ...) rendered the same way;
+        mesh=None  — the map's own render per frame (_maintain_render, as evaluate_mesh's depths="render"): NotImplementedError on a
+                     sharded mapper, whose render shows its objects only.
+        gt_vertices, gt_faces: as evaluate_mesh's.  frames: evaluate_mesh's list of raster settings; w2c and the intrinsics are formed
+        from them exactly as there (one image size, one set of intrinsics: ValueError otherwise).  depth_trunc: deeper ground truth is
+        not rendered and not compared.  The depth stacks live in buffers this mapper keeps per (K, H, W).  Returns depth_l1's float32
+        [K + 1, 8] device table (dqo_eval.DEPTH_L1_ROW; `out` if given); dqo_eval.depth_l1_dict reads it.  Nothing is read back after
+        the first render of a shape (make_mesh's one header read)."""
+        render = mesh is None
+        if render:
+            self._refuse_sharded("evaluate_mesh_depth")
+        if frames is None:
+            raise ValueError("FusedMapper.evaluate_mesh_depth: frames is a list of raster settings: a depth needs cameras")
+        gt = dict(vertices=gt_vertices, faces=gt_faces)
+        with torch.cuda.device(self.device):
+            bufs, K, W, H = self._frame_views("evaluate_mesh_depth", frames, render)
+            kw = dict(depth_trunc=depth_trunc)
+            truth = dqo_eval.mesh_render_depth(gt, bufs["w2c"], K, W, H, out=bufs.setdefault("render_gt", {}), **kw)["depth"]
+            rec = bufs["depth"] if render else dqo_eval.mesh_render_depth(mesh, bufs["w2c"], K, W, H, out=bufs.setdefault("render_rec", {}), **kw)["depth"]
+            return dqo_eval.depth_l1(truth, rec, depth_trunc=depth_trunc, out=out)
 
     def _object_rows(self, rows, who):
         """int32 [P], a buffer of this mapper's own: gaussian_object where the row is alive and in `rows`, -1 elsewhere — the group

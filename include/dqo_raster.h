@@ -1387,14 +1387,86 @@ int dqo_mesh_simplify(const float* vertices, const float* colors, const int32_t*
  *   out capacity below the input's; then DQO_ERR_WORKSPACE.
  * workspace: dqo_mesh_cull_workspace_bytes(cap_vertices, cap_faces): 0 for bad capacities; ZERO when first used and then left to the
  *   entry, which hands it back ready for the next call.
- * Not built: rendering the mesh for a depth-L1 metric, per-view intrinsics or image sizes, triangle-frustum intersection (a large face
- *   whose corners all fall outside the image is dropped), exact point-to-triangle distances. */
+ * Rendering the mesh to depth — for the Depth L1 number, or as this entry's `depth` where no sensor depth exists — is
+ *   dqo_mesh_render_depth below.  Not built: per-view intrinsics or image sizes, triangle-frustum intersection (a large face whose
+ *   corners all fall outside the image is dropped), exact point-to-triangle distances. */
 size_t dqo_mesh_cull_workspace_bytes(int32_t cap_vertices, int32_t cap_faces);
 int dqo_mesh_cull(const float* vertices, const float* colors, const int32_t* faces, const int32_t* counts, int32_t cap_vertices,
                   int32_t cap_faces, int32_t n_views, const float* w2c, const uint8_t* view_keep, int32_t W, int32_t H, float fx, float fy,
                   float cx, float cy, const float* depth, float near, float eps, float depth_trunc, int32_t min_corners, float* out_vertices,
                   float* out_colors, int32_t* out_faces, int32_t out_cap_vertices, int32_t out_cap_faces, int32_t* vertex_views,
                   int32_t* header, void* workspace, size_t workspace_bytes, void* hipStream);
+
+/* dqo_mesh_render_depth (ABI 5, symbols-only addition) — a triangle mesh rasterised to depth in K views: what the Depth L1 number of the
+ * dense-SLAM evaluation protocols (the NICE-SLAM lineage) compares pixel by pixel for the reconstructed and the ground-truth mesh, and a
+ * depth for dqo_mesh_cull's occlusion test where no sensor depth exists.  No rasterising library exists on this platform, so THIS text
+ * defines the rule and tests/mesh_render_oracle.py restates it in numpy; nothing is pinned against a library.  The operand (vertices,
+ * faces, counts, the capacities), the views (n_views, w2c, view_keep) and the camera (W, H, fx, fy, cx, cy, near, depth_trunc) are
+ * dqo_mesh_cull's; csrc/map_meshrender.hip lists the launches.  Three launches, whatever the data.  Plain arguments, no struct.
+ *   Per valid face f < F with corners i = 0, 1, 2 at vertex ids v_i, and used view k.
+ *   float32, one rounding per operation, left to right, none contracted, division correctly rounded — dqo_mesh_cull's statements:
+ *       pc_i,r = ((m[r][0] * x + m[r][1] * y) + m[r][2] * z) + m[r][3]              r = 0, 1, 2; m = w2c[k]
+ *       a corner is in front iff pc_i,z > near.  No corner in front: the pair is skipped silently.  Some but not all: the pair CROSSES
+ *       THE NEAR PLANE and is dropped and counted — there is no clipping (a documented departure from a clipping rasteriser).
+ *       x_i = (pc_i,x * fx) / pc_i,z + cx;  y_i likewise with fy, cy — dqo_mesh_cull's u_f without the + 0.5f: pixel centres sit at
+ *       integer coordinates, and a mesh is rendered by the very projection that integrated and culled it.
+ *       box: [ceil(min x_i), floor(max x_i)] x [ceil(min y_i), floor(max y_i)], a lower end below 0 set to 0 and an upper end above
+ *       W - 1 (H - 1) set to that, in float32, before the conversion to int; unless lo <= hi on both axes the pair is skipped.
+ *   double, from the widened floats, one rounding per operation, none contracted:
+ *       for the edge between corners i and j let (p, q) be the two ordered by VERTEX ID, lower first;
+ *       E = (x_q - x_p) * (Y - y_p) - (y_q - y_p) * (X - x_p);  e_ij = E if p is i, else -E.  Two faces that share an edge compute
+ *       bitwise opposite values there: no pixel centre falls between them and none is lost on the edge.
+ *       A = e_01 at (x_2, y_2).  A repeated vertex id or A == 0: the pair is DEGENERATE, counted and skipped.
+ *       pixel (X, Y) of the box is covered iff A > 0 and e_01, e_12, e_20 are all >= 0, or A < 0 and they are all <= 0: inclusive,
+ *       and both sides of a face are rendered (no back-face culling).
+ *       depth by ray-plane intersection in camera space: n = (P_1 - P_0) x (P_2 - P_0) with P_i = pc_i;  r_x = (X - cx) / fx,
+ *       r_y = (Y - cy) / fy;  nr = (n_x * r_x + n_y * r_y) + n_z;  nr == 0: no hit;
+ *       z = ((n_x * P_0,x + n_y * P_0,y) + n_z * P_0,z) / nr, set to min pc_i,z where below it and to max pc_i,z where above it;
+ *       d = (float)z;  a hit iff d > near && d <= depth_trunc.
+ *   The pixel's key is the uint64 (float bits of d) << 32 | f, and a pixel keeps the MINIMUM key of its hits: the nearest face wins,
+ *   equal depth goes to the lower face id, and the result does not depend on the order the faces arrive in — the same bits on every
+ *   run and under any schedule.
+ *   Outputs: depth float32 [n_views,H,W], 0 = no hit; face_index int32 [n_views,H,W] (may be NULL), -1 = no hit; the images of unused
+ *   views are written as no hit.  header int32 [8]: [0] views used, [1] faces with a bad index, [2] pairs rasterised (in front, a box,
+ *   not degenerate), [3] pairs dropped at the near plane, [4] degenerate pairs, [5] the pairs of [2] whose clipped box holds more than
+ *   SMALL_MAX = 64 pixels (or is wider or taller than 64) — the pairs a whole wave walks, below —, [6] pixels hit, summed over the
+ *   views (its low 32 bits), [7] 0.
+ *   The hot path is F x n_views: a grid over (256 faces, 32 views); a view's matrix and its used bit are wave-uniform scalar loads,
+ *   the face's nine corner floats stay in registers across the chunk.  A pair with a box of at most SMALL_MAX pixels is walked by its
+ *   own lane; a larger one by the whole wave — a ballot finds the flagged lanes, the face's floats are broadcast, the 64 lanes stride
+ *   the box in 8 x 8 pixel tiles — so no lane walks a wall-sized triangle alone.  Per hit one 64-bit no-return integer min atomic
+ *   (a load of the pixel's key in front of it, to skip an atomic that cannot win, was measured slower and is not there:
+ *   profiles/mesh_render.txt).  Integer atomics only; no memset, no host read, no synchronise — the entry can be captured in a hipGraph.
+ *   DQO_ERR_INVALID_ARG before any launch for dqo_mesh_cull's refusals of the operand, the views and the camera, and also for W or H
+ *   above 2^24 (W - 1 must be an exact float32), cap_faces * n_views not below 2^31 (the pair counts are int32: a caller with more
+ *   views renders them in chunks), a NULL depth, a header that is the mesh's counts; then DQO_ERR_WORKSPACE.
+ * workspace: dqo_mesh_render_depth_workspace_bytes(n_views, W, H): 0 for a bad size; it holds the 8-byte keys, which the first launch
+ *   clears; its head is ZERO when first used and then left to the entry, which hands it back ready for the next call.
+ * Not built: near-plane clipping, back-face culling, per-view intrinsics or image sizes, colour or normal shading of the mesh. */
+size_t dqo_mesh_render_depth_workspace_bytes(int32_t n_views, int32_t W, int32_t H);
+int dqo_mesh_render_depth(const float* vertices, const int32_t* faces, const int32_t* counts, int32_t cap_vertices, int32_t cap_faces,
+                          int32_t n_views, const float* w2c, const uint8_t* view_keep, int32_t W, int32_t H, float fx, float fy, float cx,
+                          float cy, float near, float depth_trunc, float* depth, int32_t* face_index, int32_t* header, void* workspace,
+                          size_t workspace_bytes, void* hipStream);
+
+/* dqo_eval_depth_l1 (ABI 5, symbols-only addition) — Depth L1: two depth stacks compared pixel by pixel.  a (the truth) and b, float32
+ * [n_views,H,W] in DEVICE memory, 0 = no hit (dqo_mesh_render_depth's, a Gaussian render's, a sensor's); view_keep as dqo_mesh_cull's;
+ * depth_trunc > 0 (may be +inf).  A pixel is hit in a iff a > 0 && a <= depth_trunc, in b iff b > 0; VALID iff hit in both.
+ * out_table float32 [n_views + 1][8]; row k of a used view:
+ *     [0] l1_valid    the mean of |a - b| over the valid pixels
+ *     [1] l1_image    the mean over all H * W pixels of |a' - b'|, a side without a hit taken as 0 (the NICE-SLAM form)
+ *     [2] rmse_valid  the root of the mean of (a - b)^2 over the valid pixels
+ *     [3] both  [4] only_a  [5] only_b  [6] neither     the pixels hit in both, in a alone, in b alone, in neither
+ *     [7] max_abs     the largest |a - b| of the valid pixels (0 without one)
+ * A view with both == 0 has NaN in the three means; an unused view is a row of NaN.  Row n_views: [0..2] the means of the used views'
+ * values where they are defined (NaN without one), [3..6] the counts summed in double and rounded once, [7] the largest maximum.
+ * Differences and sums are doubles added in a fixed order (see dqo_eval_picture; tests/depth_l1_oracle.py restates it): a table is
+ * bitwise reproducible.  Two launches, no float atomic, no host read, no synchronise.  DQO_ERR_INVALID_ARG for n_views outside
+ * [1, 65535], W * H not below 2^24 (a view's counts are exact float32), a NULL pointer, a depth_trunc that is not above 0; then
+ * DQO_ERR_WORKSPACE.  workspace: dqo_eval_depth_l1_workspace_bytes(n_views, W, H), 0 for a bad size; ZERO when first used. */
+size_t dqo_eval_depth_l1_workspace_bytes(int32_t n_views, int32_t W, int32_t H);
+int dqo_eval_depth_l1(int32_t n_views, int32_t W, int32_t H, const float* a, const float* b, const uint8_t* view_keep, float depth_trunc,
+                      float* out_table, void* workspace, size_t workspace_bytes, void* hipStream);
 
 #define DQO_TICKET_WORDS (16 + 16 * 64) /* int32 words behind DqoAdamStep.block_ticket */
 typedef struct DqoAdamStep {

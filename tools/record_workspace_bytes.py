@@ -6,7 +6,13 @@ the layouts were unified; tests/test_workspace_layouts.py rebuilds it from the l
 The grid sits on the steps where a part crosses a 256-byte alignment or a span of 2048: mesh capacities, the sampler's face counts,
 TSDF dims, image sizes (MS-SSIM's and LPIPS' smallest sides among them), point counts — and arguments every query must answer with 0.
 
+A size query added after that commit has no parent to be held to.  It goes on a second grid (_queries_since) with a table of its own,
+tests/workspace_bytes_since.json, recorded from the commit that adds it and held by that commit's own test
+(tests/test_mesh_render_abi.py); exports() names the declared queries that are NOT on the second grid, exports_since() those that are —
+so a declared query that is on neither grid still fails the first test.
+
     python tools/record_workspace_bytes.py [--lib path/to/libdqoraster.so] [--out tests/workspace_bytes_parent.json]
+    python tools/record_workspace_bytes.py --since [--out tests/workspace_bytes_since.json]
 """
 import argparse
 import ctypes
@@ -68,15 +74,25 @@ def _queries():
         yield name, (), [()]
 
 
+STACKS = [(n, w, h) for n in (1, 2, 33, 100) for w, h in IMAGES]  # (n_views, W, H)
+STACKS_BAD = [(0, 8, 8), (65536, 8, 8), (1, 0, 8), (1, 8, -1), (1, 1 << 24, 1 << 24)]
+
+
+def _queries_since():
+    """the size queries added since the parent table was recorded: (export, argument types, argument tuples)"""
+    yield "dqo_mesh_render_depth_workspace_bytes", (I32, I32, I32), STACKS + STACKS_BAD
+    yield "dqo_eval_depth_l1_workspace_bytes", (I32, I32, I32), STACKS + STACKS_BAD
+
+
 def key(name, args):
     return f"{name}({', '.join(str(a) for a in args)})"
 
 
-def table(lib_path=DEFAULT_LIB):
+def table(lib_path=DEFAULT_LIB, queries=_queries):
     """{"export(arguments)": bytes} over the grid, from the library at lib_path"""
     lib = ctypes.CDLL(lib_path)
     out = {}
-    for name, types, rows in _queries():
+    for name, types, rows in queries():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = list(types), ctypes.c_size_t
         for args in rows:
@@ -84,18 +100,34 @@ def table(lib_path=DEFAULT_LIB):
     return out
 
 
-def exports(header_path=os.path.join(ROOT, "include", "dqo_raster.h")):
-    """the size queries the public header declares: the grid must name every one of them"""
+def table_since(lib_path=DEFAULT_LIB):
+    """the second grid's table (tests/workspace_bytes_since.json)"""
+    return table(lib_path, _queries_since)
+
+
+def _declared(header_path):
     import re
-    return sorted(set(re.findall(r"^size_t (dqo_\w+_bytes\w*)\(", open(header_path).read(), re.M)))
+    return set(re.findall(r"^size_t (dqo_\w+_bytes\w*)\(", open(header_path).read(), re.M))
+
+
+def exports(header_path=os.path.join(ROOT, "include", "dqo_raster.h")):
+    """the size queries the public header declares, less those of the second grid: the first grid must name every one of them"""
+    return sorted(_declared(header_path) - {name for name, _, _ in _queries_since()})
+
+
+def exports_since(header_path=os.path.join(ROOT, "include", "dqo_raster.h")):
+    """the size queries of the second grid that the public header declares"""
+    return sorted(_declared(header_path) & {name for name, _, _ in _queries_since()})
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--lib", default=DEFAULT_LIB)
-    ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--since", action="store_true", help="the second grid: the queries added since the parent table was recorded")
     a = ap.parse_args()
-    t = table(a.lib)
+    t = table_since(a.lib) if a.since else table(a.lib)
+    a.out = a.out or (os.path.join(ROOT, "tests", "workspace_bytes_since.json") if a.since else DEFAULT_OUT)
     with open(a.out, "w") as f:
         json.dump(t, f, indent=0, sort_keys=True)
         f.write("\n")
