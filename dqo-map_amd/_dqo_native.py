@@ -131,7 +131,8 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_mesh_components_workspace_bytes", "dqo_mesh_smooth_workspace_bytes", "dqo_mesh_normals_workspace_bytes",
            "dqo_mesh_components", "dqo_mesh_smooth", "dqo_mesh_normals", "dqo_mesh_simplify_workspace_bytes", "dqo_mesh_simplify",
            "dqo_mesh_cull_workspace_bytes", "dqo_mesh_cull", "dqo_mesh_sample_counted_workspace_bytes", "dqo_mesh_sample_counted",
-           "dqo_mesh_render_depth_workspace_bytes", "dqo_mesh_render_depth", "dqo_eval_depth_l1_workspace_bytes", "dqo_eval_depth_l1")
+           "dqo_mesh_render_depth_workspace_bytes", "dqo_mesh_render_depth", "dqo_eval_depth_l1_workspace_bytes", "dqo_eval_depth_l1",
+           "dqo_mesh_render_depth_clip", "dqo_mesh_cull_faces")
 
 _lib = None
 
@@ -284,9 +285,12 @@ def lib():
         L.dqo_mesh_cull_workspace_bytes.argtypes = [c_i32, c_i32]
         L.dqo_mesh_cull.argtypes = ([c_vp] * 4 + [c_i32] * 3 + [c_vp] * 2 + [c_i32] * 2 + [c_f] * 4 + [c_vp] + [c_f] * 3 + [c_i32] + [c_vp] * 3 +
                                     [c_i32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp])
+        L.dqo_mesh_cull_faces.argtypes = ([c_vp] * 4 + [c_i32] * 3 + [c_vp] + [c_i32] * 2 + [c_vp] * 3 + [c_f] * 2 + [c_i32] + [c_vp] * 3 +
+                                          [c_i32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp])
         # map_meshrender.hip; map_eval.hip's depth L1
         L.dqo_mesh_render_depth_workspace_bytes.argtypes = [c_i32, c_i32, c_i32]
         L.dqo_mesh_render_depth.argtypes = ([c_vp] * 3 + [c_i32] * 3 + [c_vp] * 2 + [c_i32] * 2 + [c_f] * 6 + [c_vp] * 4 + [c_sz, c_vp])
+        L.dqo_mesh_render_depth_clip.argtypes = L.dqo_mesh_render_depth.argtypes
         L.dqo_eval_depth_l1_workspace_bytes.argtypes = [c_i32, c_i32, c_i32]
         L.dqo_eval_depth_l1.argtypes = [c_i32] * 3 + [c_vp] * 3 + [c_f] + [c_vp] * 2 + [c_sz, c_vp]
         # icp.hip, track.hip

@@ -31,6 +31,14 @@
 //   fscatter  kept faces, in order, renumbered.
 // Integer atomics only (the adds of `views`, whose sum does not depend on their order, and the tickets, which come back at zero);
 // nothing is allocated, set by a memset, read back or synchronised: the entry can be captured in a hipGraph.
+//
+// dqo_mesh_cull_faces — visibility per FACE, by the pixels a face wins in a render of the mesh (face_index, rdepth: map_meshrender.hip's
+// outputs); six launches too, in the same workspace (the per-face counts are the caller's face_pixels):
+//   finit     mark[v] = 0, face_pixels[f] = 0, header = 0, the used views' bits;
+//   pixels    the hot path, n_views x H x W: a pixel counts for f = face_index iff 0 <= f < F and, with the frames' depth,
+//             s > 0 && s <= depth_trunc && rdepth <= s + eps — the occlusion statement above.  One integer add per RUN of one id;
+//   fpix      fcount with the rule pixels(f) >= min_pixels; the faces with a pixel and the pixels -> header[2], [7];
+//   vcount (without the seen vertices), vscatter, fscatter: the launches above.
 #include "dqo_common.h"
 #include "dqo_mesh_operand.h"
 #include "dqo_reduce.h"
@@ -164,6 +172,8 @@ __global__ __launch_bounds__(256) void mesh_cull_fcount_kernel(const int32_t* __
     }
 }
 
+// SEEN: header[2] = the vertices with views > 0 (dqo_mesh_cull); dqo_mesh_cull_faces, which has no views, leaves the word to its fpix launch
+template <bool SEEN>
 __global__ __launch_bounds__(256) void mesh_cull_vcount_kernel(const int32_t* __restrict__ counts, uint32_t cap_v, uint32_t n_views, McWork w,
                                                                int32_t* __restrict__ header) {
     __shared__ u64 s_wave[4];
@@ -176,7 +186,7 @@ __global__ __launch_bounds__(256) void mesh_cull_vcount_kernel(const int32_t* __
         const uint32_t i = (blockIdx.x * (uint32_t)MO_CHUNKS + chunk) * 256u + threadIdx.x;
         if (i >= V) break;
         pair += (u64)(uint32_t)w.mark[i];
-        if (w.views[i] > 0) pair += 1ull << 32;
+        if (SEEN && w.views[i] > 0) pair += 1ull << 32;
     }
     u64 total;
     dqo_block_exclusive<u64>(pair, total, s_wave);
@@ -187,7 +197,8 @@ __global__ __launch_bounds__(256) void mesh_cull_vcount_kernel(const int32_t* __
     for (uint32_t c = threadIdx.x; c < (n_views + (uint32_t)MC_CHUNK - 1u) / (uint32_t)MC_CHUNK; c += 256u) used += (u64)__popc(w.viewbits[c]);
     dqo_block_exclusive<u64>(used, all, s_wave);
     if (threadIdx.x == 0) {
-        header[0] = (int32_t)(uint32_t)sums, header[6] = (int32_t)(V - (uint32_t)sums), header[2] = (int32_t)(sums >> 32);
+        header[0] = (int32_t)(uint32_t)sums, header[6] = (int32_t)(V - (uint32_t)sums);
+        if (SEEN) header[2] = (int32_t)(sums >> 32);
         header[3] = (int32_t)all;
     }
 }
@@ -206,6 +217,147 @@ __global__ __launch_bounds__(256) void mesh_cull_fscatter_kernel(const int32_t* 
     const uint32_t F = mo_count(counts, 1, cap_f);
     if (blockIdx.x >= mc_active_spans(F)) return;
     mo_scatter_faces(faces, F, w.keep, w.mark, (uint32_t)w.fpair[blockIdx.x], out_faces);
+}
+
+// ---- dqo_mesh_cull_faces: a face is kept by the pixels it wins in a render of the mesh ----
+enum {
+    MC_PIX_BATCH = 16,                  // rounds of 64 consecutive pixels whose loads a wave of the pixels launch issues together
+    MC_PIX_ROUNDS = 4 * MC_PIX_BATCH,   // rounds that a wave walks
+    MC_PIX_WAVE = 64 * MC_PIX_ROUNDS,   // a wave's pixels: consecutive, so a run of one face id goes on from round to round
+    MC_PIX_BLOCK = 4 * MC_PIX_WAVE,
+};
+
+__global__ __launch_bounds__(256) void mesh_cull_finit_kernel(const int32_t* __restrict__ counts, uint32_t cap_v, uint32_t cap_f, uint32_t n_views,
+                                                              const uint8_t* __restrict__ view_keep, McWork w, int32_t* __restrict__ face_pixels,
+                                                              int32_t* __restrict__ header) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < 8u) header[i] = 0;
+    if (i < (n_views + (uint32_t)MC_CHUNK - 1u) / (uint32_t)MC_CHUNK) {
+        uint32_t bits = 0u;
+        for (uint32_t j = 0; j < (uint32_t)MC_CHUNK; j++) {
+            const uint32_t k = i * (uint32_t)MC_CHUNK + j;
+            if (k < n_views && (view_keep == nullptr || view_keep[k] != 0)) bits |= 1u << j;
+        }
+        w.viewbits[i] = bits;
+    }
+    if (i < mo_count(counts, 0, cap_v)) w.mark[i] = 0;
+    if (i < mo_count(counts, 1, cap_f)) face_pixels[i] = 0;
+}
+
+// The hot path, n_views x H x W pixels: blockIdx.y is the view (its used bit a scalar load), a wave walks MC_PIX_WAVE consecutive
+// pixels.  A wall wins most of a view, so an add per pixel would queue on one address: a lane shift and a ballot find the heads of
+// the runs of one face id across the wave, and a run is ONE integer add; a round whose 64 pixels all continue the run of the round
+// before adds nothing — the run's length rides in a scalar until the run ends.  A pixel that does not count has id -1, which ends a
+// run and starts none.  DEPTH: the occlusion statement against the frames' depth.
+template <bool DEPTH>
+__global__ __launch_bounds__(256) void mesh_cull_pixels_kernel(const int32_t* __restrict__ counts, uint32_t cap_f,
+                                                               const uint32_t* __restrict__ viewbits, size_t plane,
+                                                               const int32_t* __restrict__ face_index, const float* __restrict__ rdepth,
+                                                               const float* __restrict__ depth, float eps, float depth_trunc,
+                                                               int32_t* __restrict__ face_pixels) {
+#pragma clang fp contract(off)
+    const uint32_t k = blockIdx.y;
+    if ((viewbits[k >> 5] >> (k & 31u) & 1u) == 0u) return;  // (block-uniform: a scalar load)
+    const uint32_t F = mo_count(counts, 1, cap_f);
+    const int lane = threadIdx.x & 63;
+    const size_t view = (size_t)k * plane;
+    const size_t first = (size_t)blockIdx.x * MC_PIX_BLOCK + (size_t)(threadIdx.x >> 6) * MC_PIX_WAVE;
+    int32_t run_id = -1, run_len = 0;  // (wave-uniform) the run that the rounds so far left open
+    for (int batch = 0; batch < MC_PIX_ROUNDS / MC_PIX_BATCH; batch++) {
+        const size_t start = first + (size_t)batch * (64 * MC_PIX_BATCH);
+        if (start >= plane) break;  // (wave-uniform)
+        // the batch's loads first, none waiting for another: a round's ballot and adds would otherwise stand between two loads
+        int32_t ids[MC_PIX_BATCH];
+#pragma unroll
+        for (int r = 0; r < MC_PIX_BATCH; r++) {
+            const size_t i = start + (size_t)r * 64 + (size_t)lane;
+            int32_t id = -1;
+            if (i < plane) {
+                const int32_t f = face_index[view + i];
+                bool on = (uint32_t)f < F;  // (anything else, -1 included, is never an index)
+                if (DEPTH && on) {
+                    const float s = depth[view + i];
+                    on = s > 0.0f && s <= depth_trunc && rdepth[view + i] <= s + eps;
+                }
+                if (on) id = f;
+            }
+            ids[r] = id;
+        }
+#pragma unroll
+        for (int r = 0; r < MC_PIX_BATCH; r++) {
+            if (start + (size_t)r * 64 >= plane) break;  // (wave-uniform)
+            const int32_t id = ids[r];
+            const int32_t prev = __shfl_up(id, 1);
+            const bool head = lane == 0 || prev != id;
+            const u64 heads = __ballot(head);
+            if (heads == 1ull) {  // (wave-uniform) one id in all 64 lanes
+                const int32_t id0 = __builtin_amdgcn_readfirstlane(id);
+                if (id0 != run_id) {
+                    if (run_id >= 0 && lane == 0) atomicAdd(&face_pixels[run_id], run_len);
+                    run_id = id0, run_len = 0;
+                }
+                run_len += 64;
+                continue;
+            }
+            if (run_id >= 0 && lane == 0) atomicAdd(&face_pixels[run_id], run_len);
+            run_id = -1, run_len = 0;
+            if (head && id >= 0) {
+                const u64 above = lane < 63 ? heads >> (lane + 1) : 0ull;  // the next head ends the run
+                atomicAdd(&face_pixels[id], above != 0ull ? (int32_t)__ffsll((long long)above) : 64 - lane);
+            }
+        }
+    }
+    if (run_id >= 0 && lane == 0) atomicAdd(&face_pixels[run_id], run_len);
+}
+
+// dqo_mesh_cull's fcount with the pixel rule: keep[f], the kept faces' vertices marked, a span's (kept, bad) counts scanned by the last
+// block -> header[1], [4], [5]; the faces with a pixel and the pixels -> header[2], [7], one integer add per wave and word (the finit
+// launch cleared them).  A bad face's count is put back to 0: a pixel counts for a valid face only.
+__global__ __launch_bounds__(256) void mesh_cull_fpix_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ counts, uint32_t cap_v,
+                                                             uint32_t cap_f, McWork w, int32_t min_pixels, int32_t* __restrict__ face_pixels,
+                                                             int32_t* __restrict__ header) {
+    __shared__ u64 s_wave[4];
+    __shared__ int s_last;
+    const uint32_t V = mo_count(counts, 0, cap_v), F = mo_count(counts, 1, cap_f);
+    const uint32_t nact = mc_active_spans(F);
+    if (blockIdx.x >= nact) return;
+    const int lane = threadIdx.x & 63;
+    u64 run = 0ull;
+    uint32_t n_with = 0u, n_pixels = 0u;
+    for (uint32_t chunk = 0; chunk < (uint32_t)MO_CHUNKS; chunk++) {
+        const uint32_t f = (blockIdx.x * (uint32_t)MO_CHUNKS + chunk) * 256u + threadIdx.x;
+        u64 pair = 0ull;
+        if (f < F) {
+            const int32_t px = face_pixels[f];
+            int32_t a, b, c;
+            if (mo_face(faces, f, V, a, b, c)) {
+                n_with += px != 0 ? 1u : 0u, n_pixels += (uint32_t)px;
+                if (px >= min_pixels) {
+                    pair = 1ull;
+                    w.mark[a] = 1, w.mark[b] = 1, w.mark[c] = 1;
+                }
+            } else {
+                pair = 1ull << 32;
+                if (px != 0) face_pixels[f] = 0;
+            }
+            w.keep[f] = (uint8_t)(pair & 1ull);
+        }
+        u64 total;
+        dqo_block_exclusive<u64>(pair, total, s_wave);
+        run += total;
+    }
+    n_with = dqo_wave_sum_u32(n_with, lane), n_pixels = dqo_wave_sum_u32(n_pixels, lane);
+    if (lane == 0) {
+        if (n_with > 0u) atomicAdd(&header[2], (int32_t)n_with);
+        if (n_pixels > 0u) atomicAdd(&header[7], (int32_t)n_pixels);
+    }
+    if (threadIdx.x == 0) __hip_atomic_store(&w.fpair[blockIdx.x], run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!dqo_last_block(w.head, &s_last, (int)nact)) return;
+    const u64 sums = dqo_scan_block_counts<u64, 2>(w.fpair, nact, 1, s_wave);
+    if (threadIdx.x == 0) {
+        const uint32_t kept = (uint32_t)sums, bad = (uint32_t)(sums >> 32);
+        header[1] = (int32_t)kept, header[4] = (int32_t)bad, header[5] = (int32_t)(F - bad - kept);
+    }
 }
 
 // the ticket words | views | mark | keep | vpair | fpair | the used views' bits
@@ -265,7 +417,45 @@ DQO_API int dqo_mesh_cull(const float* vertices, const float* colors, const int3
     DQO_LAUNCH("mesh_cull_views_kernel", views_kernel, gvk, block, s, vertices, counts, ucv, w2c, (const uint32_t*)w.viewbits, depth, cam,
                w.views);
     DQO_LAUNCH("mesh_cull_fcount_kernel", mesh_cull_fcount_kernel, sf, block, s, faces, counts, ucv, ucf, w, min_corners, header);
-    DQO_LAUNCH("mesh_cull_vcount_kernel", mesh_cull_vcount_kernel, sv, block, s, counts, ucv, nv, w, header);
+    DQO_LAUNCH("mesh_cull_vcount_kernel", mesh_cull_vcount_kernel<true>, sv, block, s, counts, ucv, nv, w, header);
+    DQO_LAUNCH("mesh_cull_vscatter_kernel", mesh_cull_vscatter_kernel, sv, block, s, vertices, colors, counts, ucv, w, out_vertices, out_colors);
+    DQO_LAUNCH("mesh_cull_fscatter_kernel", mesh_cull_fscatter_kernel, sf, block, s, faces, counts, ucf, w, out_faces);
+    return DQO_OK;
+}
+
+DQO_API int dqo_mesh_cull_faces(const float* vertices, const float* colors, const int32_t* faces, const int32_t* counts, int32_t cap_vertices,
+                                int32_t cap_faces, int32_t n_views, const uint8_t* view_keep, int32_t W, int32_t H, const int32_t* face_index,
+                                const float* rdepth, const float* depth, float eps, float depth_trunc, int32_t min_pixels, float* out_vertices,
+                                float* out_colors, int32_t* out_faces, int32_t out_cap_vertices, int32_t out_cap_faces, int32_t* face_pixels,
+                                int32_t* header, void* workspace, size_t workspace_bytes, void* stream) {
+    DQO_MESH_CHECK_CAPS(cap_vertices, cap_faces);
+    DQO_CHECK_ARG(vertices && faces && header, "null mesh buffer / header");
+    DQO_CHECK_ARG(n_views >= 1 && n_views <= MC_MAX_VIEWS, "bad n_views %d: 1 to 65535 views", n_views);
+    DQO_CHECK_ARG(W >= 1 && H >= 1 && (uint64_t)W * (uint64_t)H <= ((1ull << 40) - 1ull) / (uint64_t)n_views,
+                  "bad image size %d x %d for %d views: both sides are at least 1, n_views * H * W is below 2^40", W, H, n_views);
+    DQO_CHECK_ARG(face_index && rdepth, "null face_index / rdepth: the entry culls by a render of this mesh");
+    DQO_CHECK_ARG(face_pixels, "null face_pixels");
+    DQO_CHECK_ARG(eps - eps == 0.0f && eps >= 0.0f, "bad eps: it is finite and at least 0");
+    DQO_CHECK_ARG(depth_trunc > 0.0f, "bad depth_trunc: it is above 0 (it may be +inf)");
+    DQO_CHECK_ARG(min_pixels >= 1, "bad min_pixels %d: at least 1", min_pixels);
+    DQO_MESH_CHECK_OUT();
+    DQO_CHECK_ARG(face_pixels != faces && face_pixels != out_faces && face_pixels != header && face_pixels != counts,
+                  "face_pixels must be a buffer of its own");
+    const size_t cv = (size_t)cap_vertices, cf = (size_t)cap_faces;
+    DQO_CHECK_WS("mesh cull", workspace, workspace_bytes, mc_ws(nullptr, cv, cf).total);
+    const McWork w = mc_ws(workspace, cv, cf).w;
+    const uint32_t ucv = (uint32_t)cap_vertices, ucf = (uint32_t)cap_faces, nv = (uint32_t)n_views;
+    const size_t chunks = ((size_t)n_views + MC_CHUNK - 1) / MC_CHUNK, plane = (size_t)W * (size_t)H;
+    const size_t most = cv > cf ? (cv > chunks ? cv : chunks) : (cf > chunks ? cf : chunks);
+    const dim3 block(256), gi((unsigned)mo_blocks(most)), gp((unsigned)((plane + MC_PIX_BLOCK - 1) / MC_PIX_BLOCK), (unsigned)n_views);
+    const dim3 sv((unsigned)mo_spans(cv)), sf((unsigned)mo_spans(cf));
+    auto pixels_kernel = depth != nullptr ? mesh_cull_pixels_kernel<true> : mesh_cull_pixels_kernel<false>;
+    hipStream_t s = (hipStream_t)stream;
+    DQO_LAUNCH("mesh_cull_finit_kernel", mesh_cull_finit_kernel, gi, block, s, counts, ucv, ucf, nv, view_keep, w, face_pixels, header);
+    DQO_LAUNCH("mesh_cull_pixels_kernel", pixels_kernel, gp, block, s, counts, ucf, (const uint32_t*)w.viewbits, plane, face_index, rdepth, depth,
+               eps, depth_trunc, face_pixels);
+    DQO_LAUNCH("mesh_cull_fpix_kernel", mesh_cull_fpix_kernel, sf, block, s, faces, counts, ucv, ucf, w, min_pixels, face_pixels, header);
+    DQO_LAUNCH("mesh_cull_vcount_kernel", mesh_cull_vcount_kernel<false>, sv, block, s, counts, ucv, nv, w, header);
     DQO_LAUNCH("mesh_cull_vscatter_kernel", mesh_cull_vscatter_kernel, sv, block, s, vertices, colors, counts, ucv, w, out_vertices, out_colors);
     DQO_LAUNCH("mesh_cull_fscatter_kernel", mesh_cull_fscatter_kernel, sf, block, s, faces, counts, ucf, w, out_faces);
     return DQO_OK;

@@ -40,6 +40,15 @@
 //              used views' bits -> header[0].
 // Integer atomics only (min, whose result does not depend on the order; adds; the tickets, which come back at zero); nothing is
 // allocated, set by a memset, read back or synchronised: the entry can be captured in a hipGraph.
+//
+// dqo_mesh_render_depth_clip — the same three launches with the rasterise kernel's CLIP instantiation (the plain entry launches the
+// other one, whose code the flag leaves as it was: 118 VGPRs, no scratch; CLIP: 186 VGPRs, no scratch).  A pair with 1 or 2 corners in
+// front is not dropped: homogeneous rasterisation, no clip polygon (include/dqo_raster.h states it; tests/mesh_clip_oracle.py restates it)
+//     an edge with both endpoints in front keeps the 2-D form above; any other edge: c = P_p x P_q, E = (c_x * r_x + c_y * r_y) + c_z
+//     A = P_0 . (P_1 x P_2);  covered and the depth as above — the test d > near IS the clip
+//     box (mr_cross_box): the projected corners in front and the edges' crossings of z = near, in double, a pixel of margin; with
+//     near == 0 a crossing is a point at infinity and opens its side to the image border
+//   and takes the same two paths by its box: its own lane, or — the wall-sized ones — the whole wave.
 #include <algorithm>
 
 #include "dqo_common.h"
@@ -102,6 +111,13 @@ __device__ __forceinline__ double mr_edge_at(const MrEdge& e, double X, double Y
     return e.fwd ? E : -E;
 }
 
+// the 3-D form of an edge that has an endpoint not in front: c = P_p x P_q in (xp, yp, dx);  E = (c_x * r_x + c_y * r_y) + c_z, r the pixel's ray
+__device__ __forceinline__ double mr_edge3_at(const MrEdge& e, double rx, double ry) {
+#pragma clang fp contract(off)
+    const double E = (e.xp * rx + e.yp * ry) + e.dx;
+    return e.fwd ? E : -E;
+}
+
 // x, y: the projected corners; P: pc of the corners (P[3 i + r]); order: bit 0: v_0 < v_1, bit 1: v_1 < v_2, bit 2: v_2 < v_0
 __device__ __forceinline__ MrSetup mr_setup(const float (&x)[3], const float (&y)[3], const float (&P)[9], uint32_t order, const MrCamera& cam) {
 #pragma clang fp contract(off)
@@ -124,14 +140,47 @@ __device__ __forceinline__ MrSetup mr_setup(const float (&x)[3], const float (&y
     return s;
 }
 
+// The set-up of a pair that CROSSES the near plane (dqo_mesh_render_depth_clip): front = bit i: corner i is in front.  An edge with both
+// endpoints in front keeps the 2-D form on its projected corners (x, y of a corner that is not in front are never read); any other edge
+// takes the 3-D form on (p, q), the endpoints ordered by vertex id as in mr_setup; A = the triple product P_0 . (P_1 x P_2).  The
+// plane, np0 and the z range are mr_setup's.
+__device__ __forceinline__ MrSetup mr_setup_cross(const float (&x)[3], const float (&y)[3], const float (&P)[9], uint32_t order, uint32_t front,
+                                                  const MrCamera& cam) {
+#pragma clang fp contract(off)
+    MrSetup s = mr_setup(x, y, P, order, cam);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const int j = (i + 1) % 3;
+        if ((front >> i & 1u) != 0u && (front >> j & 1u) != 0u) continue;
+        const bool i_first = (order >> i & 1u) != 0u;
+        const int p = i_first ? i : j, q = i_first ? j : i;
+        const double px = (double)P[3 * p], py = (double)P[3 * p + 1], pz = (double)P[3 * p + 2];
+        const double qx = (double)P[3 * q], qy = (double)P[3 * q + 1], qz = (double)P[3 * q + 2];
+        s.e[i].xp = py * qz - pz * qy, s.e[i].yp = pz * qx - px * qz, s.e[i].dx = px * qy - py * qx, s.e[i].dy = 0.0;
+    }
+    const double tx = (double)P[4] * (double)P[8] - (double)P[5] * (double)P[7];
+    const double ty = (double)P[5] * (double)P[6] - (double)P[3] * (double)P[8];
+    const double tz = (double)P[3] * (double)P[7] - (double)P[4] * (double)P[6];
+    s.A = ((double)P[0] * tx + (double)P[1] * ty) + (double)P[2] * tz;
+    return s;
+}
+
 // THE pixel function of both paths: pixel (X, Y) of view plane `keys` against face f.  (X, Y) lies inside the image: the box is clipped.
-__device__ __forceinline__ void mr_pixel(const MrSetup& s, int X, int Y, uint32_t f, const MrCamera& cam, u64* __restrict__ keys) {
+// CROSS: the pair crosses the near plane (s is mr_setup_cross's, front its corners in front); the depth test below is what clips it.
+template <bool CROSS>
+__device__ __forceinline__ void mr_pixel(const MrSetup& s, uint32_t front, int X, int Y, uint32_t f, const MrCamera& cam, u64* __restrict__ keys) {
 #pragma clang fp contract(off)
     const double Xd = (double)X, Yd = (double)Y;
-    const double e0 = mr_edge_at(s.e[0], Xd, Yd), e1 = mr_edge_at(s.e[1], Xd, Yd), e2 = mr_edge_at(s.e[2], Xd, Yd);
+    double e0, e1, e2, rx, ry;
+    if (CROSS) {
+        rx = (Xd - s.cx) / s.fx, ry = (Yd - s.cy) / s.fy;
+        e0 = (front & 3u) == 3u ? mr_edge_at(s.e[0], Xd, Yd) : mr_edge3_at(s.e[0], rx, ry);
+        e1 = (front & 6u) == 6u ? mr_edge_at(s.e[1], Xd, Yd) : mr_edge3_at(s.e[1], rx, ry);
+        e2 = (front & 5u) == 5u ? mr_edge_at(s.e[2], Xd, Yd) : mr_edge3_at(s.e[2], rx, ry);
+    } else e0 = mr_edge_at(s.e[0], Xd, Yd), e1 = mr_edge_at(s.e[1], Xd, Yd), e2 = mr_edge_at(s.e[2], Xd, Yd);
     const bool covered = (s.A > 0.0 && e0 >= 0.0 && e1 >= 0.0 && e2 >= 0.0) || (s.A < 0.0 && e0 <= 0.0 && e1 <= 0.0 && e2 <= 0.0);
     if (!covered) return;
-    const double rx = (Xd - s.cx) / s.fx, ry = (Yd - s.cy) / s.fy;
+    if (!CROSS) rx = (Xd - s.cx) / s.fx, ry = (Yd - s.cy) / s.fy;
     const double nr = (s.nx * rx + s.ny * ry) + s.nz;
     if (nr == 0.0) return;
     double z = s.np0 / nr;
@@ -165,6 +214,65 @@ __global__ __launch_bounds__(256) void mesh_render_clear_kernel(uint32_t n_views
 
 __device__ __forceinline__ float mr_lane_f(float v, int src) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src)); }
 
+// The box of a pair that crosses the near plane, in double: the hull of what can be covered is spanned by the projected corners in
+// front (x, y: the float32 ones, widened) and by the two points where an edge from a corner in front (a) to one that is not (b) meets
+// z = near,
+//     t = (near - z_a) / (z_b - z_a);  q = P_a + t * (P_b - P_a) in x and y;  u = (q_x * fx) / near + cx;  v likewise with fy, cy
+// — with near == 0 a crossing is a point at infinity: u is +inf or -inf by the sign of q_x (the side opens to the image border) or a
+// NaN (q_x == 0), which the comparisons leave out.  lo = ceil(min) - 1, below 0 -> 0; hi = floor(max) + 1, above W - 1 -> W - 1: a
+// pixel of margin, since the float32 corners and the 3-D edges do not meet in exactly one point.  False unless lo <= hi on both axes.
+__device__ __forceinline__ bool mr_cross_box(const float (&x)[3], const float (&y)[3], const float (&P)[9], uint32_t front, const MrCamera& cam,
+                                             int& bx0, int& bx1, int& by0, int& by1) {
+#pragma clang fp contract(off)
+    const double inf = __builtin_huge_val(), near = (double)cam.near;
+    double xmin = inf, xmax = -inf, ymin = inf, ymax = -inf;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        if ((front >> i & 1u) == 0u) continue;
+        const double u = (double)x[i], v = (double)y[i];
+        if (u < xmin) xmin = u;
+        if (u > xmax) xmax = u;
+        if (v < ymin) ymin = v;
+        if (v > ymax) ymax = v;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const int j = (i + 1) % 3;
+        if ((front >> i & 1u) == (front >> j & 1u)) continue;
+        const int a = (front >> i & 1u) != 0u ? i : j, b = a == i ? j : i;
+        const double za = (double)P[3 * a + 2], t = (near - za) / ((double)P[3 * b + 2] - za);
+        const double qx = (double)P[3 * a] + t * ((double)P[3 * b] - (double)P[3 * a]);
+        const double qy = (double)P[3 * a + 1] + t * ((double)P[3 * b + 1] - (double)P[3 * a + 1]);
+        const double u = (qx * (double)cam.fx) / near + (double)cam.cx, v = (qy * (double)cam.fy) / near + (double)cam.cy;
+        if (u < xmin) xmin = u;
+        if (u > xmax) xmax = u;
+        if (v < ymin) ymin = v;
+        if (v > ymax) ymax = v;
+    }
+    double x0 = ceil(xmin) - 1.0, x1 = floor(xmax) + 1.0, y0 = ceil(ymin) - 1.0, y1 = floor(ymax) + 1.0;
+    if (x0 < 0.0) x0 = 0.0;
+    if (y0 < 0.0) y0 = 0.0;
+    if (x1 > (double)(cam.W - 1)) x1 = (double)(cam.W - 1);
+    if (y1 > (double)(cam.H - 1)) y1 = (double)(cam.H - 1);
+    if (!(x0 <= x1 && y0 <= y1)) return false;  // (false for a NaN; all four lie inside [0, W - 1] x [0, H - 1] here)
+    bx0 = (int)x0, bx1 = (int)x1, by0 = (int)y0, by1 = (int)y1;
+    return true;
+}
+
+// a flagged pair's box by the whole wave, in 8 x 8 pixel tiles, a lane a pixel
+template <bool CROSS>
+__device__ __forceinline__ void mr_wave_walk(const MrSetup& s, uint32_t front, int x0, int x1, int y0, int y1, int lane, uint32_t f,
+                                             const MrCamera& cam, u64* __restrict__ keys) {
+    const int lx = lane & 7, ly = lane >> 3;
+    for (int ty = y0; ty <= y1; ty += 8)
+        for (int tx = x0; tx <= x1; tx += 8) {
+            const int X = tx + lx, Y = ty + ly;
+            if (X <= x1 && Y <= y1) mr_pixel<CROSS>(s, front, X, Y, f, cam, keys);
+        }
+}
+
+// CLIP: dqo_mesh_render_depth_clip's rule — a pair that crosses the near plane is rasterised (mr_setup_cross, mr_cross_box), not dropped
+template <bool CLIP>
 __global__ __launch_bounds__(256) void mesh_render_raster_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ faces,
                                                                  const int32_t* __restrict__ counts, uint32_t cap_v, uint32_t cap_f,
                                                                  const float* __restrict__ w2c, MrCamera cam, MrWork w) {
@@ -215,9 +323,34 @@ __global__ __launch_bounds__(256) void mesh_render_raster_kernel(const float* __
         }
         bool large = false;
         int bx0 = 0, bx1 = 0, by0 = 0, by1 = 0;
+        uint32_t cross = 7u;  // (CLIP) the corners in front of a flagged pair that crosses the near plane; 7: it does not
         if (ok && front > 0) {
-            if (front < 3) n_near++;
-            else {
+            if (front < 3) {
+                n_near++;
+                if (CLIP) {
+                    uint32_t fm = 0u;
+#pragma unroll
+                    for (int i = 0; i < 3; i++)
+                        if (P[3 * i + 2] > cam.near) {
+                            fm |= 1u << i;
+                            x[i] = (P[3 * i] * cam.fx) / P[3 * i + 2] + cam.cx;
+                            y[i] = (P[3 * i + 1] * cam.fy) / P[3 * i + 2] + cam.cy;
+                        }
+                    if (mr_cross_box(x, y, P, fm, cam, bx0, bx1, by0, by1)) {
+                        const MrSetup s = mr_setup_cross(x, y, P, order, fm, cam);
+                        if (repeated || s.A == 0.0) n_degen++;
+                        else {
+                            n_rast++;
+                            const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
+                            large = bw > MR_SMALL_MAX || bh > MR_SMALL_MAX || bw * bh > MR_SMALL_MAX;
+                            if (!large) {
+                                for (int Y = by0; Y <= by1; Y++)
+                                    for (int X = bx0; X <= bx1; X++) mr_pixel<true>(s, fm, X, Y, f, cam, keys);
+                            } else n_coop++, cross = fm;
+                        }
+                    }
+                }
+            } else {
 #pragma unroll
                 for (int i = 0; i < 3; i++) {
                     x[i] = (P[3 * i] * cam.fx) / P[3 * i + 2] + cam.cx;
@@ -247,7 +380,7 @@ __global__ __launch_bounds__(256) void mesh_render_raster_kernel(const float* __
                         large = bw > MR_SMALL_MAX || bh > MR_SMALL_MAX || bw * bh > MR_SMALL_MAX;
                         if (!large) {
                             for (int Y = by0; Y <= by1; Y++)
-                                for (int X = bx0; X <= bx1; X++) mr_pixel(s, X, Y, f, cam, keys);
+                                for (int X = bx0; X <= bx1; X++) mr_pixel<false>(s, 7u, X, Y, f, cam, keys);
                         } else n_coop++;
                     }
                 }
@@ -267,13 +400,14 @@ __global__ __launch_bounds__(256) void mesh_render_raster_kernel(const float* __
             const int qx0 = __builtin_amdgcn_readlane(bx0, src), qx1 = __builtin_amdgcn_readlane(bx1, src);
             const int qy0 = __builtin_amdgcn_readlane(by0, src), qy1 = __builtin_amdgcn_readlane(by1, src);
             const uint32_t qf = f - (uint32_t)lane + (uint32_t)src;
-            const MrSetup s = mr_setup(qx, qy, qP, qorder, cam);
-            const int lx = lane & 7, ly = lane >> 3;
-            for (int ty = qy0; ty <= qy1; ty += 8)
-                for (int tx = qx0; tx <= qx1; tx += 8) {
-                    const int X = tx + lx, Y = ty + ly;
-                    if (X <= qx1 && Y <= qy1) mr_pixel(s, X, Y, qf, cam, keys);
-                }
+            const uint32_t qcross = CLIP ? (uint32_t)__builtin_amdgcn_readlane((int)cross, src) : 7u;
+            if (CLIP && qcross != 7u) {  // (wave-uniform)
+                const MrSetup s = mr_setup_cross(qx, qy, qP, qorder, qcross, cam);
+                mr_wave_walk<true>(s, qcross, qx0, qx1, qy0, qy1, lane, qf, cam, keys);
+            } else {
+                const MrSetup s = mr_setup(qx, qy, qP, qorder, cam);
+                mr_wave_walk<false>(s, 7u, qx0, qx1, qy0, qy1, lane, qf, cam, keys);
+            }
         }
     }
     n_rast = dqo_wave_sum_u32(n_rast, lane), n_near = dqo_wave_sum_u32(n_near, lane);
@@ -331,19 +465,18 @@ inline bool mr_image_ok(int64_t n_views, int64_t W, int64_t H) {
            (uint64_t)W * (uint64_t)H <= ((1ull << 40) - 1ull) / (uint64_t)n_views;
 }
 
-}  // namespace
+// what both entries check and size before their three launches
+struct MrCall {
+    MrWork w;
+    MrCamera cam;
+    uint32_t ucv, ucf, nv;
+    size_t pixels, key_pairs;
+    dim3 block, gc, gr, gs;
+};
 
-// ---- entry points (include/dqo_raster.h): size query, argument validation, the call ----
-extern "C" {
-
-DQO_API size_t dqo_mesh_render_depth_workspace_bytes(int32_t n_views, int32_t W, int32_t H) {
-    return mr_image_ok(n_views, W, H) ? mr_ws(nullptr, (size_t)n_views * (size_t)W * (size_t)H).total : 0;
-}
-
-DQO_API int dqo_mesh_render_depth(const float* vertices, const int32_t* faces, const int32_t* counts, int32_t cap_vertices, int32_t cap_faces,
-                                  int32_t n_views, const float* w2c, const uint8_t* view_keep, int32_t W, int32_t H, float fx, float fy, float cx,
-                                  float cy, float near, float depth_trunc, float* depth, int32_t* face_index, int32_t* header, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
+inline int mr_prepare(const float* vertices, const int32_t* faces, const int32_t* counts, int32_t cap_vertices, int32_t cap_faces, int32_t n_views,
+                      const float* w2c, int32_t W, int32_t H, float fx, float fy, float cx, float cy, float near, float depth_trunc,
+                      const float* depth, const int32_t* header, void* workspace, size_t workspace_bytes, MrCall& c) {
     DQO_MESH_CHECK_CAPS(cap_vertices, cap_faces);
     DQO_CHECK_ARG(vertices && faces && header, "null mesh buffer / header");
     DQO_CHECK_ARG(n_views >= 1 && n_views <= MR_MAX_VIEWS, "bad n_views %d: 1 to 65535 views", n_views);
@@ -357,20 +490,58 @@ DQO_API int dqo_mesh_render_depth(const float* vertices, const int32_t* faces, c
     DQO_CHECK_ARG(depth_trunc > 0.0f, "bad depth_trunc: it is above 0 (it may be +inf)");
     DQO_CHECK_ARG(depth, "null depth");
     DQO_CHECK_ARG(header != counts, "header must not be the mesh's counts: the first launch clears it before the counts are read");
-    const size_t pixels = (size_t)n_views * (size_t)W * (size_t)H;
-    DQO_CHECK_WS("mesh render", workspace, workspace_bytes, mr_ws(nullptr, pixels).total);
-    const MrWork w = mr_ws(workspace, pixels).w;
-    MrCamera cam;
-    cam.W = W, cam.H = H, cam.fx = fx, cam.fy = fy, cam.cx = cx, cam.cy = cy, cam.near = near, cam.depth_trunc = depth_trunc;
-    const uint32_t ucv = (uint32_t)cap_vertices, ucf = (uint32_t)cap_faces, nv = (uint32_t)n_views;
-    const size_t chunks = ((size_t)n_views + MR_CHUNK - 1) / MR_CHUNK, key_pairs = (pixels + 1) / 2;
-    const size_t clear_blocks = (key_pairs + 256 * MR_CLEAR_PAIRS - 1) / (256 * MR_CLEAR_PAIRS);
-    const dim3 block(256), gc((unsigned)(clear_blocks > mo_blocks(chunks) ? clear_blocks : mo_blocks(chunks)));
-    const dim3 gr((unsigned)mo_blocks((size_t)cap_faces), (unsigned)chunks), gs((unsigned)std::min<size_t>((pixels + 256 * MR_RES_PIX - 1) / (256 * MR_RES_PIX), MR_RES_BLOCKS));
+    c.pixels = (size_t)n_views * (size_t)W * (size_t)H;
+    DQO_CHECK_WS("mesh render", workspace, workspace_bytes, mr_ws(nullptr, c.pixels).total);
+    c.w = mr_ws(workspace, c.pixels).w;
+    c.cam.W = W, c.cam.H = H, c.cam.fx = fx, c.cam.fy = fy, c.cam.cx = cx, c.cam.cy = cy, c.cam.near = near, c.cam.depth_trunc = depth_trunc;
+    c.ucv = (uint32_t)cap_vertices, c.ucf = (uint32_t)cap_faces, c.nv = (uint32_t)n_views;
+    const size_t chunks = ((size_t)n_views + MR_CHUNK - 1) / MR_CHUNK;
+    c.key_pairs = (c.pixels + 1) / 2;
+    const size_t clear_blocks = (c.key_pairs + 256 * MR_CLEAR_PAIRS - 1) / (256 * MR_CLEAR_PAIRS);
+    c.block = dim3(256), c.gc = dim3((unsigned)(clear_blocks > mo_blocks(chunks) ? clear_blocks : mo_blocks(chunks)));
+    c.gr = dim3((unsigned)mo_blocks((size_t)cap_faces), (unsigned)chunks);
+    c.gs = dim3((unsigned)std::min<size_t>((c.pixels + 256 * MR_RES_PIX - 1) / (256 * MR_RES_PIX), MR_RES_BLOCKS));
+    return DQO_OK;
+}
+
+}  // namespace
+
+// ---- entry points (include/dqo_raster.h): size query, argument validation, the call ----
+extern "C" {
+
+DQO_API size_t dqo_mesh_render_depth_workspace_bytes(int32_t n_views, int32_t W, int32_t H) {
+    return mr_image_ok(n_views, W, H) ? mr_ws(nullptr, (size_t)n_views * (size_t)W * (size_t)H).total : 0;
+}
+
+DQO_API int dqo_mesh_render_depth(const float* vertices, const int32_t* faces, const int32_t* counts, int32_t cap_vertices, int32_t cap_faces,
+                                  int32_t n_views, const float* w2c, const uint8_t* view_keep, int32_t W, int32_t H, float fx, float fy, float cx,
+                                  float cy, float near, float depth_trunc, float* depth, int32_t* face_index, int32_t* header, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    MrCall c;
+    const int rc = mr_prepare(vertices, faces, counts, cap_vertices, cap_faces, n_views, w2c, W, H, fx, fy, cx, cy, near, depth_trunc, depth, header,
+                              workspace, workspace_bytes, c);
+    if (rc != DQO_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    DQO_LAUNCH("mesh_render_clear_kernel", mesh_render_clear_kernel, gc, block, s, nv, view_keep, key_pairs, w, header);
-    DQO_LAUNCH("mesh_render_raster_kernel", mesh_render_raster_kernel, gr, block, s, vertices, faces, counts, ucv, ucf, w2c, cam, w);
-    DQO_LAUNCH("mesh_render_resolve_kernel", mesh_render_resolve_kernel, gs, block, s, pixels, nv, w, depth, face_index, header);
+    DQO_LAUNCH("mesh_render_clear_kernel", mesh_render_clear_kernel, c.gc, c.block, s, c.nv, view_keep, c.key_pairs, c.w, header);
+    DQO_LAUNCH("mesh_render_raster_kernel", mesh_render_raster_kernel<false>, c.gr, c.block, s, vertices, faces, counts, c.ucv, c.ucf, w2c, c.cam, c.w);
+    DQO_LAUNCH("mesh_render_resolve_kernel", mesh_render_resolve_kernel, c.gs, c.block, s, c.pixels, c.nv, c.w, depth, face_index, header);
+    return DQO_OK;
+}
+
+// the same call with the rasterise launch's CLIP instantiation: a pair that crosses the near plane is rasterised, header[3] counts it
+DQO_API int dqo_mesh_render_depth_clip(const float* vertices, const int32_t* faces, const int32_t* counts, int32_t cap_vertices, int32_t cap_faces,
+                                       int32_t n_views, const float* w2c, const uint8_t* view_keep, int32_t W, int32_t H, float fx, float fy,
+                                       float cx, float cy, float near, float depth_trunc, float* depth, int32_t* face_index, int32_t* header,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    MrCall c;
+    const int rc = mr_prepare(vertices, faces, counts, cap_vertices, cap_faces, n_views, w2c, W, H, fx, fy, cx, cy, near, depth_trunc, depth, header,
+                              workspace, workspace_bytes, c);
+    if (rc != DQO_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DQO_LAUNCH("mesh_render_clear_kernel", mesh_render_clear_kernel, c.gc, c.block, s, c.nv, view_keep, c.key_pairs, c.w, header);
+    DQO_LAUNCH("mesh_render_raster_clip_kernel", mesh_render_raster_kernel<true>, c.gr, c.block, s, vertices, faces, counts, c.ucv, c.ucf, w2c, c.cam,
+               c.w);
+    DQO_LAUNCH("mesh_render_resolve_kernel", mesh_render_resolve_kernel, c.gs, c.block, s, c.pixels, c.nv, c.w, depth, face_index, header);
     return DQO_OK;
 }
 

@@ -111,12 +111,14 @@ rendered to depth from the frames' cameras and compared pixel by pixel (csrc/map
 include/dqo_raster.h states and tests/mesh_render_oracle.py restates; csrc/map_eval.hip, dqo_eval_depth_l1):
 
     mesh_render_depth(mesh, w2c, K, W, H, ...)              ->  dict(depth [n,H,W], face_index | None, header, header_names)
+    mesh_render_depth_clip(mesh, w2c, K, W, H, ...)         ->  the same, a face that crosses a view's near plane clipped, not dropped
+    mesh_cull_visible(mesh, w2c, K, W, H, depth, ...)       ->  the mesh's faces that win pixels in that render (eval_mesh's visibility="faces")
     depth_l1(depth_gt, depth_rec, view_keep, depth_trunc)   ->  float32 [n + 1, 8] on the device (DEPTH_L1_ROW), a row per view and the set's
     depth_l1_dict(table)                                    ->  the rows as dicts (the ONE host read)
     eval_mesh_depth(rec_mesh, gt_mesh, views)               ->  both meshes rendered, the table
 
-FusedMapper.evaluate_mesh_depth forms the views from frames, and with mesh=None compares the map's own render.  Not built: near-plane
-clipping, back-face culling, per-view intrinsics, colour or normal shading of the mesh.
+FusedMapper.evaluate_mesh_depth forms the views from frames, and with mesh=None compares the map's own render.  Not built: back-face
+culling, per-view intrinsics, colour or normal shading of the mesh.
 
 GPU only: there is no CPU path.
 """
@@ -1214,21 +1216,29 @@ def eval_mesh(rec_mesh, gt_mesh, sample_nums=1000000, seed=0, rec_seed=None, dis
     rec_mesh, gt_mesh: mesh dicts (as for mesh_components; the ground truth of dqo_ply.read_mesh_ply as device tensors, without a
     header, is one).  views: None (no culling) or a dict of mesh_cull's keywords — w2c, K, W, H and optionally depth, view_keep, eps,
     near, depth_trunc, min_corners — applied to BOTH meshes, each in its own coordinates, before anything is sampled (so with `views`
-    the two meshes share the cameras' frame); the culled meshes live in buffers of this module's own, one pair per device and
-    capacities.  sample_nums points are drawn on each: gt_mesh with `seed`, rec_mesh with rec_seed (None: seed + 1).  transform:
+    the two meshes share the cameras' frame); visibility="faces" (default "vertices") culls by mesh_cull_visible in its place — a face
+    is kept by the pixels it wins in a clipped render of its mesh, min_pixels (default 1) of them, so a wall whose corners all lie
+    outside the image stays — and a key of the rule not chosen, or eval_mesh_depth's clip_near, is ignored; the culled meshes live
+    in buffers of this module's own, one pair per device and capacities.  sample_nums points are drawn on each: gt_mesh with `seed`, rec_mesh with rec_seed (None: seed + 1).  transform:
     eval_pcd's, applied to the reconstruction's points; dist_thres, out, row: eval_pcd's.
     Returns the float32 [32] device row (PCD_ROW); nothing is read back and the call does not synchronise.  A side that is empty — no
     faces, no area, a cull that keeps nothing — gives a row of NaN, eval_pcd's rule.  Without `views`, a gt_mesh without a header yields
     the very points sample_surface(gt vertices, gt faces, sample_nums, seed) yields."""
     if views is not None:
         kw = dict(views)
-        for k in ("out", "want_views", "workspace_buffer"):
+        for k in ("out", "want_views", "want_pixels", "workspace_buffer"):
             if k in kw:
                 raise RuntimeError(f"dqo_eval.eval_mesh: views is a dict of mesh_cull's view keywords; {k!r} is eval_mesh's own")
+        kw.pop("clip_near", None)  # (eval_mesh_depth's)
+        visibility = kw.pop("visibility", "vertices")
+        if visibility not in ("vertices", "faces"):
+            raise RuntimeError(f"dqo_eval.eval_mesh: views['visibility'] is 'vertices' or 'faces', got {visibility!r}")
+        kw.pop("min_pixels" if visibility == "vertices" else "min_corners", None)  # (the other rule's)
+        cull = mesh_cull if visibility == "vertices" else mesh_cull_visible
         meshes = []
         for tag, m in (("cull_rec", rec_mesh), ("cull_gt", gt_mesh)):
             v, c, f, h, cv, cf = _mesh(m, "eval_mesh")
-            meshes.append(mesh_cull(m, out=_own_mesh_out(tag, v.device, cv, cf, c is not None), **kw))
+            meshes.append(cull(m, out=_own_mesh_out(tag, v.device, cv, cf, c is not None), **kw))
         rec_mesh, gt_mesh = meshes
     gt = sample_surface_counted(gt_mesh, sample_nums, seed=seed)
     rec = sample_surface_counted(rec_mesh, sample_nums, seed=int(seed) + 1 if rec_seed is None else rec_seed)
@@ -1251,30 +1261,18 @@ def _own_render_out(tag, dev, n, H, W):
     return out
 
 
-def mesh_render_depth(mesh, w2c, K, W, H, view_keep=None, near=0.0, depth_trunc=float("inf"), want_face_index=False, out=None,
-                      workspace_buffer=None):
-    """The mesh rasterised to depth in n views — the render whose depths the Depth L1 number compares (include/dqo_raster.h,
-    dqo_mesh_render_depth, states the rule: corners projected by mesh_cull's own float32 statements without its + 0.5, so pixel centres
-    sit at integer coordinates; edge functions in double, ordered by vertex id, so two faces that share an edge leave no pixel between
-    them; coverage inclusive, both sides of a face; depth by ray-plane intersection in double; a pixel keeps the nearest face, the
-    lower face id at equal depth, whatever order the faces arrive in).  A face that crosses the near plane of a view is dropped there
-    and counted, not clipped.
-    mesh: a mesh dict, as for mesh_components.  w2c, K, W, H, view_keep, near, depth_trunc: mesh_cull's.  Returns dict(depth float32
-    [n,H,W], 0 = no hit; face_index int32 [n,H,W], -1 = no hit, or None without want_face_index; header int32 [8]; header_names =
-    MESH_RENDER_HEADER, by which mesh_counts reads the header) in `out` (a dict with such tensors; default: this module's own for the
-    device and sizes, overwritten by the next call); the images of unused views are written as no hit.  The depth stack is a `depth`
-    for mesh_cull: the ground-truth mesh's own render serves its occlusion test where no sensor depth exists.
-    workspace_buffer: a uint8 tensor of dqo_mesh_render_depth_workspace_bytes(n, W, H) bytes the caller keeps, zero when first used
-    (default: one per device and sizes, kept by this module).  Three launches, nothing read back, no synchronise; capturable in a graph."""
-    v, c, f, h, cv, cf = _mesh(mesh, "mesh_render_depth")
+def _mesh_render(who, entry, names, mesh, w2c, K, W, H, view_keep, near, depth_trunc, want_face_index, out, workspace_buffer):
+    """mesh_render_depth's and mesh_render_depth_clip's body: the same checks, buffers and workspace, the entry and the header's names
+    apart."""
+    v, c, f, h, cv, cf = _mesh(mesh, who)
     dev = v.device
     N.require_gpu_op((v, w2c), view_keep, workspace_buffer)
-    n, view_keep = _views("mesh_render_depth", w2c, view_keep, dev)
+    n, view_keep = _views(who, w2c, view_keep, dev)
     W, H = int(W), int(H)
     fx, fy, cx, cy = _intrinsics(K)
     nbytes = N.lib().dqo_mesh_render_depth_workspace_bytes(n, W, H)
     if nbytes == 0:
-        raise RuntimeError(f"dqo_eval.mesh_render_depth: bad image size {W} x {H} for {n} views")
+        raise RuntimeError(f"dqo_eval.{who}: bad image size {W} x {H} for {n} views")
     if out is None:
         out = _own_render_out("render", dev, n, H, W)
     if "depth" not in out:
@@ -1292,16 +1290,98 @@ def mesh_render_depth(mesh, w2c, K, W, H, view_keep=None, near=0.0, depth_trunc=
     N.require_gpu_op((v, d, oh), fi)
     for t, dt, name in ((d, torch.float32, "depth"), (fi, torch.int32, "face_index")):
         if t is not None and (tuple(t.shape) != (n, H, W) or t.dtype != dt or not t.is_contiguous() or t.device != dev):
-            raise RuntimeError(f"dqo_eval.mesh_render_depth: out['{name}'] is a contiguous {dt} [{n},{H},{W}] tensor on the mesh's device")
+            raise RuntimeError(f"dqo_eval.{who}: out['{name}'] is a contiguous {dt} [{n},{H},{W}] tensor on the mesh's device")
     if oh.dtype != torch.int32 or oh.numel() != 8 or not oh.is_contiguous() or oh.device != dev:
-        raise RuntimeError("dqo_eval.mesh_render_depth: out['header'] is int32 [8] on the mesh's device")
+        raise RuntimeError(f"dqo_eval.{who}: out['header'] is int32 [8] on the mesh's device")
     ws = _ws(workspace_buffer, dev, nbytes, "mesh_render", n, W, H)
     with torch.cuda.device(dev):
-        N.check(N.lib().dqo_mesh_render_depth(v.data_ptr(), f.data_ptr(), N.ptr(h), cv, cf, n, w2c.data_ptr(), N.ptr(view_keep), W, H, fx, fy, cx, cy,
-                                              float(near), float(depth_trunc), d.data_ptr(), N.ptr(fi), oh.data_ptr(), ws.data_ptr(), ws.numel(),
-                                              N.current_stream()))
+        N.check(getattr(N.lib(), entry)(v.data_ptr(), f.data_ptr(), N.ptr(h), cv, cf, n, w2c.data_ptr(), N.ptr(view_keep), W, H, fx, fy, cx, cy,
+                                        float(near), float(depth_trunc), d.data_ptr(), N.ptr(fi), oh.data_ptr(), ws.data_ptr(), ws.numel(),
+                                        N.current_stream()))
     out["face_index"] = fi
-    out["header_names"] = MESH_RENDER_HEADER  # (what mesh_counts calls the words)
+    out["header_names"] = names  # (what mesh_counts calls the words)
+    return out
+
+
+def mesh_render_depth(mesh, w2c, K, W, H, view_keep=None, near=0.0, depth_trunc=float("inf"), want_face_index=False, out=None,
+                      workspace_buffer=None):
+    """The mesh rasterised to depth in n views — the render whose depths the Depth L1 number compares (include/dqo_raster.h,
+    dqo_mesh_render_depth, states the rule: corners projected by mesh_cull's own float32 statements without its + 0.5, so pixel centres
+    sit at integer coordinates; edge functions in double, ordered by vertex id, so two faces that share an edge leave no pixel between
+    them; coverage inclusive, both sides of a face; depth by ray-plane intersection in double; a pixel keeps the nearest face, the
+    lower face id at equal depth, whatever order the faces arrive in).  A face that crosses the near plane of a view is dropped there
+    and counted, not clipped.
+    mesh: a mesh dict, as for mesh_components.  w2c, K, W, H, view_keep, near, depth_trunc: mesh_cull's.  Returns dict(depth float32
+    [n,H,W], 0 = no hit; face_index int32 [n,H,W], -1 = no hit, or None without want_face_index; header int32 [8]; header_names =
+    MESH_RENDER_HEADER, by which mesh_counts reads the header) in `out` (a dict with such tensors; default: this module's own for the
+    device and sizes, overwritten by the next call); the images of unused views are written as no hit.  The depth stack is a `depth`
+    for mesh_cull: the ground-truth mesh's own render serves its occlusion test where no sensor depth exists.
+    workspace_buffer: a uint8 tensor of dqo_mesh_render_depth_workspace_bytes(n, W, H) bytes the caller keeps, zero when first used
+    (default: one per device and sizes, kept by this module).  Three launches, nothing read back, no synchronise; capturable in a graph."""
+    return _mesh_render("mesh_render_depth", "dqo_mesh_render_depth", MESH_RENDER_HEADER, mesh, w2c, K, W, H, view_keep, near, depth_trunc,
+                        want_face_index, out, workspace_buffer)
+
+
+MESH_RENDER_CLIP_HEADER = MESH_RENDER_HEADER[:3] + ("pairs_near_clipped",) + MESH_RENDER_HEADER[4:]
+
+
+def mesh_render_depth_clip(mesh, w2c, K, W, H, view_keep=None, near=0.0, depth_trunc=float("inf"), want_face_index=False, out=None,
+                           workspace_buffer=None):
+    """mesh_render_depth with the near plane CLIPPED (include/dqo_raster.h, dqo_mesh_render_depth_clip): a face that crosses the near
+    plane of a view is rasterised there — homogeneous edge functions for its edges that leave the front, the depth test d > near as the
+    clip — where mesh_render_depth drops it, so a wall of two triangles seen from inside the room is an image, not a hole.  A mesh that
+    no view crosses gives mesh_render_depth's bytes.  Arguments, buffers, workspace and the returned dict are mesh_render_depth's
+    (without `out` the two share this module's buffers for a device and sizes); header_names = MESH_RENDER_CLIP_HEADER, whose word 3 is
+    pairs_near_clipped.  Its face_index is what mesh_cull_visible culls by.  mesh_render_depth's signature is pinned, so the switch
+    is this twin; eval_mesh_depth's views take clip_near=True.  Three launches, nothing read back; capturable in a graph."""
+    return _mesh_render("mesh_render_depth_clip", "dqo_mesh_render_depth_clip", MESH_RENDER_CLIP_HEADER, mesh, w2c, K, W, H, view_keep, near,
+                        depth_trunc, want_face_index, out, workspace_buffer)
+
+
+MESH_CULL_FACES_HEADER = ("vertices", "faces", "faces_with_pixels", "views_used", "faces_bad_index", "faces_removed", "vertices_removed",
+                          "pixels_counted")
+
+
+def mesh_cull_visible(mesh, w2c, K, W, H, depth=None, view_keep=None, eps=0.03, near=0.0, depth_trunc=float("inf"), min_pixels=1, out=None,
+                      want_pixels=False):
+    """The mesh restricted to the faces the views SEE, decided per face by the pixels it wins: the mesh is rendered from the views with
+    the near plane clipped (mesh_render_depth_clip, with face_index; near is the render's, whose own depth_trunc is +inf), and a face
+    is kept iff it wins at least min_pixels pixels of the used views (include/dqo_raster.h, dqo_mesh_cull_faces) — with `depth`, the
+    frames' depth, only pixels where that depth is above 0, at most depth_trunc and not more than eps in front of the render's count:
+    mesh_cull's occlusion statement per pixel.  Where mesh_cull tests vertices, and so drops a wall of two triangles that fills every
+    frame because its corners lie outside them, this keeps it; a face hidden behind another wins no pixel and goes.
+    mesh, w2c, K, W, H, depth, view_keep, eps, depth_trunc, out: mesh_cull's.  Returns a mesh dict like mesh_cull's: header = the int32
+    [8] MESH_CULL_FACES_HEADER (words 0 and 1 the counts), "header_names", "face_pixels": with want_pixels int32 [cap_faces], the
+    pixels each face won (rows behind the count untouched), else None, and "render": mesh_render_depth_clip's dict of this call (depth,
+    face_index, header), in buffers of this module's own per device and sizes.  Nine launches, nothing read back, no synchronise;
+    capturable in a graph."""
+    v, c, f, h, cv, cf = _mesh(mesh, "mesh_cull_visible")
+    dev = v.device
+    N.require_gpu_op((v, w2c), depth, view_keep)
+    n, view_keep = _views("mesh_cull_visible", w2c, view_keep, dev)
+    W, H = int(W), int(H)
+    if depth is not None and (tuple(depth.shape) != (n, H, W) or depth.dtype != torch.float32 or not depth.is_contiguous() or depth.device != dev):
+        raise RuntimeError(f"dqo_eval.mesh_cull_visible: depth must be a contiguous float32 [{n},{H},{W}] tensor on the mesh's device")
+    out, (ov, oc, of, oh, ocv, ocf) = _out_mesh("mesh_cull_visible", out, dev, cv, cf, c is not None)
+    px = out.get("face_pixels")
+    if px is None:
+        px = out.get("_pixels_buffer")  # (an earlier call's, kept while a call without want_pixels set the public key to None)
+    if px is None:
+        px = out["_pixels_buffer"] = torch.empty((cf,), dtype=torch.int32, device=dev)
+    if px.dtype != torch.int32 or px.numel() < cf or not px.is_contiguous() or px.device != dev:
+        raise RuntimeError("dqo_eval.mesh_cull_visible: out['face_pixels'] is a contiguous int32 [cap_faces] tensor on the mesh's device")
+    out["_pixels_buffer"] = px
+    r = mesh_render_depth_clip(mesh, w2c, K, W, H, view_keep=view_keep, near=near, want_face_index=True,
+                               out=_own_render_out("cull_visible", dev, n, H, W))
+    ws = _mesh_ws("cull", None, dev, cv, cf)
+    with torch.cuda.device(dev):
+        N.check(N.lib().dqo_mesh_cull_faces(v.data_ptr(), N.ptr(c), f.data_ptr(), N.ptr(h), cv, cf, n, N.ptr(view_keep), W, H,
+                                            r["face_index"].data_ptr(), r["depth"].data_ptr(), N.ptr(depth), float(eps), float(depth_trunc),
+                                            int(min_pixels), ov.data_ptr(), N.ptr(oc) if c is not None else None, of.data_ptr(), ocv, ocf,
+                                            px.data_ptr(), oh.data_ptr(), ws.data_ptr(), ws.numel(), N.current_stream()))
+    out["header_names"] = MESH_CULL_FACES_HEADER  # (what mesh_counts calls the words)
+    out["face_pixels"] = px if want_pixels else None
+    out["render"] = r
     return out
 
 
@@ -1356,13 +1436,15 @@ def depth_l1_dict(table):
 def eval_mesh_depth(rec_mesh, gt_mesh, views, out=None):
     """Depth L1 of a reconstructed mesh against the ground-truth mesh, in one call on the device: both meshes rendered to depth from the
     same views (mesh_render_depth), the two stacks compared (depth_l1, the ground truth as the truth).  rec_mesh, gt_mesh: mesh dicts,
-    as for eval_mesh.  views: eval_mesh's dict — w2c, K, W, H and optionally view_keep, near, depth_trunc; its other keys (depth, eps,
-    min_corners) belong to the cull and are ignored here.  depth_trunc applies to both renders and to the comparison.  The two depth
+    as for eval_mesh.  views: eval_mesh's dict — w2c, K, W, H and optionally view_keep, near, depth_trunc and clip_near (True: both
+    meshes by mesh_render_depth_clip, so a wall that crosses a camera's near plane is depth and not a hole; default False); its other
+    keys (depth, eps, min_corners, min_pixels, visibility) belong to the cull and are ignored here.  depth_trunc applies to both renders and to the comparison.  The two depth
     stacks live in buffers of this module's own, one pair per device and sizes.  Returns depth_l1's float32 [n + 1, 8] table (`out`,
     or a new tensor); nothing is read back."""
     if views is None:
         raise RuntimeError("dqo_eval.eval_mesh_depth: views is a dict with w2c, K, W and H: a depth needs cameras")
-    kw = {k: x for k, x in dict(views).items() if k not in ("depth", "eps", "min_corners")}
+    kw = {k: x for k, x in dict(views).items() if k not in ("depth", "eps", "min_corners", "min_pixels", "visibility")}
+    render = mesh_render_depth_clip if kw.pop("clip_near", False) else mesh_render_depth
     for k in ("out", "want_face_index", "workspace_buffer"):
         if k in kw:
             raise RuntimeError(f"dqo_eval.eval_mesh_depth: views is a dict of the views' keywords; {k!r} is mesh_render_depth's own")
@@ -1371,5 +1453,5 @@ def eval_mesh_depth(rec_mesh, gt_mesh, views, out=None):
         v = m["vertices"]
         N.require_gpu_op((v, kw["w2c"]))
         n, H, W = kw["w2c"].numel() // 16, int(kw["H"]), int(kw["W"])
-        stacks.append(mesh_render_depth(m, out=_own_render_out(tag, v.device, n, H, W), **kw)["depth"])
+        stacks.append(render(m, out=_own_render_out(tag, v.device, n, H, W), **kw)["depth"])
     return depth_l1(stacks[0], stacks[1], view_keep=kw.get("view_keep"), depth_trunc=kw.get("depth_trunc", float("inf")), out=out)

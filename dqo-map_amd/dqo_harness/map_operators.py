@@ -510,20 +510,38 @@ class MapOperators:
         (dqo_eval.mesh_render_depth(gt, ...)["depth"]) where no sensor depth exists.  eps, min_corners, depth_trunc: mesh_cull's.
         sample_nums, seed, dist_thres, transform, out, row: eval_mesh's.  Returns the float32 [32] device row (dqo_eval.PCD_ROW;
         dqo_eval.eval_pcd_dict reads it).  Nothing is read back after the first render of a shape (make_mesh's one header read)."""
+        return self._evaluate_mesh("evaluate_mesh", mesh, gt_vertices, gt_faces, frames, depths, sample_nums, seed, dist_thres, transform,
+                                   dict(eps=eps, depth_trunc=depth_trunc, min_corners=min_corners), out, row)
+
+    @torch.no_grad()
+    def evaluate_mesh_visible(self, mesh, gt_vertices, gt_faces, frames, depths=None, sample_nums=1000000, seed=0, dist_thres=(0.03,),
+                              transform=None, eps=0.03, min_pixels=1, depth_trunc=float("inf"), out=None, row=0):
+        """evaluate_mesh with visibility decided per FACE (dqo_eval.eval_mesh's views["visibility"] = "faces", dqo_eval.mesh_cull_visible):
+        each mesh is rendered from the frames' cameras with the near plane clipped and keeps the faces that win at least min_pixels
+        pixels, so a wall of two triangles that fills every frame stays in the ground truth although no corner of it lies inside an
+        image — evaluate_mesh's per-vertex rule drops it, and reports completion and recall against a ground truth without walls.
+        frames, depths (None, "render" or a [K,H,W] tensor: the occlusion test per pixel), eps, depth_trunc and every other argument:
+        evaluate_mesh's, whose signature is pinned, so the rule is this method.  Returns the float32 [32] device row."""
+        if frames is None:
+            raise ValueError("FusedMapper.evaluate_mesh_visible: frames is a list of raster settings: visibility needs cameras")
+        return self._evaluate_mesh("evaluate_mesh_visible", mesh, gt_vertices, gt_faces, frames, depths, sample_nums, seed, dist_thres, transform,
+                                   dict(eps=eps, depth_trunc=depth_trunc, min_pixels=min_pixels, visibility="faces"), out, row)
+
+    def _evaluate_mesh(self, who, mesh, gt_vertices, gt_faces, frames, depths, sample_nums, seed, dist_thres, transform, rule, out, row):
+        """evaluate_mesh's and evaluate_mesh_visible's body; rule: the cull's keywords of dqo_eval.eval_mesh's views."""
         gt = dict(vertices=gt_vertices, faces=gt_faces)
         if frames is None:
             if depths is not None:
-                raise ValueError("FusedMapper.evaluate_mesh: depths belong to frames; frames=None is the evaluation without culling")
+                raise ValueError(f"FusedMapper.{who}: depths belong to frames; frames=None is the evaluation without culling")
             return dqo_eval.eval_mesh(mesh, gt, sample_nums, seed, dist_thres=dist_thres, transform=transform, out=out, row=row)
         render = isinstance(depths, str)
         if render and depths != "render":
-            raise ValueError(f"FusedMapper.evaluate_mesh: depths is None, 'render' or a [K,H,W] device tensor, got {depths!r}")
+            raise ValueError(f"FusedMapper.{who}: depths is None, 'render' or a [K,H,W] device tensor, got {depths!r}")
         if render:
-            self._refuse_sharded("evaluate_mesh")
+            self._refuse_sharded(who)
         with torch.cuda.device(self.device):
-            bufs, K, W, H = self._frame_views("evaluate_mesh", frames, render)
-            views = dict(w2c=bufs["w2c"], K=K, W=W, H=H, depth=bufs["depth"] if render else depths, eps=eps, depth_trunc=depth_trunc,
-                         min_corners=min_corners)
+            bufs, K, W, H = self._frame_views(who, frames, render)
+            views = dict(w2c=bufs["w2c"], K=K, W=W, H=H, depth=bufs["depth"] if render else depths, **rule)
             return dqo_eval.eval_mesh(mesh, gt, sample_nums, seed, dist_thres=dist_thres, transform=transform, views=views, out=out, row=row)
 
     def _frame_views(self, who, frames, render):
@@ -569,17 +587,30 @@ class MapOperators:
         not rendered and not compared.  The depth stacks live in buffers this mapper keeps per (K, H, W).  Returns depth_l1's float32
         [K + 1, 8] device table (dqo_eval.DEPTH_L1_ROW; `out` if given); dqo_eval.depth_l1_dict reads it.  Nothing is read back after
         the first render of a shape (make_mesh's one header read)."""
+        return self._evaluate_mesh_depth("evaluate_mesh_depth", dqo_eval.mesh_render_depth, mesh, gt_vertices, gt_faces, frames, depth_trunc, out)
+
+    @torch.no_grad()
+    def evaluate_mesh_depth_clipped(self, mesh, gt_vertices, gt_faces, frames, depth_trunc=float("inf"), out=None):
+        """evaluate_mesh_depth with the near plane clipped (dqo_eval.mesh_render_depth_clip; dqo_eval.eval_mesh_depth's views["clip_near"]):
+        a face that crosses a frame's near plane — the floor or a wall of the room the camera stands in — is rendered, where
+        evaluate_mesh_depth drops it and the table shows its hole as only_b, neither and l1_image.  Arguments and the returned table:
+        evaluate_mesh_depth's, whose signature is pinned, so the rule is this method."""
+        return self._evaluate_mesh_depth("evaluate_mesh_depth_clipped", dqo_eval.mesh_render_depth_clip, mesh, gt_vertices, gt_faces, frames,
+                                         depth_trunc, out)
+
+    def _evaluate_mesh_depth(self, who, render_mesh, mesh, gt_vertices, gt_faces, frames, depth_trunc, out):
+        """evaluate_mesh_depth's and evaluate_mesh_depth_clipped's body; render_mesh: dqo_eval's mesh render of the two."""
         render = mesh is None
         if render:
-            self._refuse_sharded("evaluate_mesh_depth")
+            self._refuse_sharded(who)
         if frames is None:
-            raise ValueError("FusedMapper.evaluate_mesh_depth: frames is a list of raster settings: a depth needs cameras")
+            raise ValueError(f"FusedMapper.{who}: frames is a list of raster settings: a depth needs cameras")
         gt = dict(vertices=gt_vertices, faces=gt_faces)
         with torch.cuda.device(self.device):
-            bufs, K, W, H = self._frame_views("evaluate_mesh_depth", frames, render)
+            bufs, K, W, H = self._frame_views(who, frames, render)
             kw = dict(depth_trunc=depth_trunc)
-            truth = dqo_eval.mesh_render_depth(gt, bufs["w2c"], K, W, H, out=bufs.setdefault("render_gt", {}), **kw)["depth"]
-            rec = bufs["depth"] if render else dqo_eval.mesh_render_depth(mesh, bufs["w2c"], K, W, H, out=bufs.setdefault("render_rec", {}), **kw)["depth"]
+            truth = render_mesh(gt, bufs["w2c"], K, W, H, out=bufs.setdefault("render_gt", {}), **kw)["depth"]
+            rec = bufs["depth"] if render else render_mesh(mesh, bufs["w2c"], K, W, H, out=bufs.setdefault("render_rec", {}), **kw)["depth"]
             return dqo_eval.depth_l1(truth, rec, depth_trunc=depth_trunc, out=out)
 
     def _object_rows(self, rows, who):

@@ -1389,13 +1389,46 @@ int dqo_mesh_simplify(const float* vertices, const float* colors, const int32_t*
  *   entry, which hands it back ready for the next call.
  * Rendering the mesh to depth — for the Depth L1 number, or as this entry's `depth` where no sensor depth exists — is
  *   dqo_mesh_render_depth below.  Not built: per-view intrinsics or image sizes, triangle-frustum intersection (a large face whose
- *   corners all fall outside the image is dropped), exact point-to-triangle distances. */
+ *   corners all fall outside the image is dropped), exact point-to-triangle distances.  (That is this entry's rule and stays it;
+ *   dqo_mesh_cull_faces below decides per FACE, by the pixels a face wins in a render, and keeps such a face.) */
 size_t dqo_mesh_cull_workspace_bytes(int32_t cap_vertices, int32_t cap_faces);
 int dqo_mesh_cull(const float* vertices, const float* colors, const int32_t* faces, const int32_t* counts, int32_t cap_vertices,
                   int32_t cap_faces, int32_t n_views, const float* w2c, const uint8_t* view_keep, int32_t W, int32_t H, float fx, float fy,
                   float cx, float cy, const float* depth, float near, float eps, float depth_trunc, int32_t min_corners, float* out_vertices,
                   float* out_colors, int32_t* out_faces, int32_t out_cap_vertices, int32_t out_cap_faces, int32_t* vertex_views,
                   int32_t* header, void* workspace, size_t workspace_bytes, void* hipStream);
+
+/* dqo_mesh_cull_faces (ABI 5, symbols-only addition) — a mesh restricted to the faces that WIN PIXELS in a render of it: visibility per
+ * face, where dqo_mesh_cull's is per vertex and drops a wall of two triangles whose corners all lie outside the image although it fills
+ * it.  The operand, the counts, n_views, view_keep, W, H, the out mesh and the common refusals are dqo_mesh_cull's; tests/mesh_clip_oracle.py
+ * restates the rule in numpy.  Six launches, whatever the data.  Plain arguments, no struct.
+ *   face_index int32 [n_views,H,W] and rdepth float32 [n_views,H,W], device: a render of THIS mesh from the views —
+ *   dqo_mesh_render_depth_clip's (or dqo_mesh_render_depth's) face_index and depth; depth float32 [n_views,H,W] (may be NULL): the
+ *   frames' depth; eps (finite, >= 0), depth_trunc (> 0, may be +inf), min_pixels (>= 1).
+ *   Pixel (k, Y, X) of a used view k, with f = face_index[k][Y][X], COUNTS for f iff
+ *       0 <= f < F — anything else, -1 included, is ignored and never used as an index —, f is a valid face, and
+ *       depth == NULL, or s = depth[k][Y][X] has s > 0 && s <= depth_trunc && rdepth[k][Y][X] <= s + eps       (one float32 add)
+ *   — dqo_mesh_cull's occlusion statement with the render's depth in the place of the vertex's.  pixels(f) = the pixels that count
+ *   for f.  A face is KEPT iff it is valid and pixels(f) >= min_pixels.  Compaction, renumbering and the bit-for-bit copies are
+ *   dqo_mesh_cull's.
+ *   Outputs: the out mesh; face_pixels int32 [cap_faces] (required, a buffer of its own): pixels(f) for f < F (0 for a face with a bad
+ *   index), rows behind F untouched; header int32 [8]: [0] vertices written, [1] faces written, [2] faces with a pixel, [3] views
+ *   used, [4] faces with a bad index, [5] faces removed by the rule, [6] vertices removed, [7] pixels counted, summed over the faces (its
+ *   low 32 bits).  F = [1] + [4] + [5] and V = [0] + [6].
+ *   The hot path is n_views x H x W pixels.  A wall wins most of a view, so one add per pixel would queue on one address: a wave walks
+ *   consecutive pixels, a lane shift and a ballot find the heads of the runs of one face id across its 64 lanes, a run is ONE integer
+ *   add, and a run that goes on through whole rounds of 64 rides in a scalar until it ends.  Integer adds only: the same bits on every
+ *   run and under any schedule; no memset, no host read, no synchronise — the entry can be captured in a hipGraph.
+ *   DQO_ERR_INVALID_ARG before any launch for dqo_mesh_cull's refusals of the operand, n_views, the image size, eps, depth_trunc and
+ *   the out mesh, and also for a NULL face_index, rdepth or face_pixels, min_pixels below 1, a face_pixels that is the faces, the out
+ *   faces, the header or the counts; then DQO_ERR_WORKSPACE.
+ * workspace: dqo_mesh_cull_workspace_bytes(cap_vertices, cap_faces) is this entry's query too (mark, keep, the span pairs, the view
+ *   bits; the per-face counts are the caller's face_pixels): ZERO when first used and then left to the entry. */
+int dqo_mesh_cull_faces(const float* vertices, const float* colors, const int32_t* faces, const int32_t* counts, int32_t cap_vertices,
+                        int32_t cap_faces, int32_t n_views, const uint8_t* view_keep, int32_t W, int32_t H, const int32_t* face_index,
+                        const float* rdepth, const float* depth, float eps, float depth_trunc, int32_t min_pixels, float* out_vertices,
+                        float* out_colors, int32_t* out_faces, int32_t out_cap_vertices, int32_t out_cap_faces, int32_t* face_pixels,
+                        int32_t* header, void* workspace, size_t workspace_bytes, void* hipStream);
 
 /* dqo_mesh_render_depth (ABI 5, symbols-only addition) — a triangle mesh rasterised to depth in K views: what the Depth L1 number of the
  * dense-SLAM evaluation protocols (the NICE-SLAM lineage) compares pixel by pixel for the reconstructed and the ground-truth mesh, and a
@@ -1442,12 +1475,49 @@ int dqo_mesh_cull(const float* vertices, const float* colors, const int32_t* fac
  *   views renders them in chunks), a NULL depth, a header that is the mesh's counts; then DQO_ERR_WORKSPACE.
  * workspace: dqo_mesh_render_depth_workspace_bytes(n_views, W, H): 0 for a bad size; it holds the 8-byte keys, which the first launch
  *   clears; its head is ZERO when first used and then left to the entry, which hands it back ready for the next call.
- * Not built: near-plane clipping, back-face culling, per-view intrinsics or image sizes, colour or normal shading of the mesh. */
+ * Not built: near-plane clipping, back-face culling, per-view intrinsics or image sizes, colour or normal shading of the mesh.
+ * (That is this entry's rule and stays it; dqo_mesh_render_depth_clip below is the entry that clips at the near plane.) */
 size_t dqo_mesh_render_depth_workspace_bytes(int32_t n_views, int32_t W, int32_t H);
 int dqo_mesh_render_depth(const float* vertices, const int32_t* faces, const int32_t* counts, int32_t cap_vertices, int32_t cap_faces,
                           int32_t n_views, const float* w2c, const uint8_t* view_keep, int32_t W, int32_t H, float fx, float fy, float cx,
                           float cy, float near, float depth_trunc, float* depth, int32_t* face_index, int32_t* header, void* workspace,
                           size_t workspace_bytes, void* hipStream);
+
+/* dqo_mesh_render_depth_clip (ABI 5, symbols-only addition) — dqo_mesh_render_depth with the near plane CLIPPED: a camera that stands in a
+ * room is within one triangle of its floor or of a wall, and a wall of two triangles that crosses the near plane is most of the image.
+ * Arguments, refusals, workspace (dqo_mesh_render_depth_workspace_bytes), the three launches, the key and the outputs are
+ * dqo_mesh_render_depth's; header[3] counts the pairs that cross the near plane, which are now rasterised, and nothing is dropped.
+ * tests/mesh_clip_oracle.py restates the rule in numpy.  The rule is homogeneous rasterisation: no clip polygon is formed.
+ *   pc_i and "in front" (pc_i,z > near) as above.  No corner in front: skipped.  All three in front: the pair goes through
+ *   dqo_mesh_render_depth's statements UNCHANGED — a mesh that no used view crosses gives that entry's bytes.
+ *   1 or 2 corners in front — the pair CROSSES (counted in [3], whatever follows):
+ *       x_i, y_i of the corners in front as above (float32).
+ *       box, in double from the widened floats, one rounding per operation: the points are (x_i, y_i) of the corners in front and, for
+ *       each edge from a corner a in front to a corner b that is not, the edge's crossing of z = near,
+ *           t = (near - z_a) / (z_b - z_a);  q_x = x_a + t * (x_b - x_a), q_y likewise (camera space);
+ *           u = (q_x * fx) / near + cx;  v = (q_y * fy) / near + cy
+ *       — with near == 0 a crossing lies at infinity: u is +inf or -inf by the sign of q_x, so the box opens to the image border on
+ *       that side, or a NaN (q_x == 0), which is left out.  [ceil(min u) - 1, floor(max u) + 1] x [ceil(min v) - 1, floor(max v) + 1],
+ *       comparisons that a NaN fails, the ends set to 0 and W - 1 (H - 1) where beyond; unless lo <= hi on both axes the pair is
+ *       skipped.  (One pixel of margin: the float32 corners of a 2-D edge and the exact lines of the 3-D edges do not meet in one
+ *       point.  The visible part of the face is the hull of these points, so the box holds every covered pixel.)
+ *       orientation: A = (P_0,x * t_x + P_0,y * t_y) + P_0,z * t_z with t = P_1 x P_2, t_x = P_1,y * P_2,z - P_1,z * P_2,y and so on:
+ *       the triple product P_0 . (P_1 x P_2), in double.  A repeated vertex id or A == 0: DEGENERATE, counted and skipped.
+ *       edge between corners i and j, (p, q) the two ordered by vertex id: both in front — the 2-D edge function above, on the
+ *       projected float32 corners; otherwise c = P_p x P_q (c_x = P_p,y * P_q,z - P_p,z * P_q,y, c_y = P_p,z * P_q,x - P_p,x * P_q,z,
+ *       c_z = P_p,x * P_q,y - P_p,y * P_q,x), E = (c_x * r_x + c_y * r_y) + c_z with r the pixel's ray of the depth step; e_ij = E if p
+ *       is i, else -E.  E is the 2-D form times z_p * z_q / (fx * fy): the two agree in sign on an edge in front (fx, fy > 0).  Both
+ *       faces that share an edge see the same endpoints, pick the same form and compute bitwise opposite values.
+ *       covered iff A > 0 and all three >= 0, or A < 0 and all three <= 0; depth, clamp and the test d > near && d <= depth_trunc as
+ *       above — that test IS the clip: the part of the face's cone behind the near plane fails it.
+ *   header: [2] counts the crossing pairs that have a box and are not degenerate too, [3] pairs that cross the near plane (clipped, not
+ *   dropped), [5] by the box above for a crossing pair; the other words as above.
+ *   The rasterise launch is the CLIP instantiation of dqo_mesh_render_depth's kernel; a crossing pair takes the same two paths (its own
+ *   lane up to SMALL_MAX pixels of box, the whole wave above), and both paths call the one pixel function. */
+int dqo_mesh_render_depth_clip(const float* vertices, const int32_t* faces, const int32_t* counts, int32_t cap_vertices, int32_t cap_faces,
+                               int32_t n_views, const float* w2c, const uint8_t* view_keep, int32_t W, int32_t H, float fx, float fy, float cx,
+                               float cy, float near, float depth_trunc, float* depth, int32_t* face_index, int32_t* header, void* workspace,
+                               size_t workspace_bytes, void* hipStream);
 
 /* dqo_eval_depth_l1 (ABI 5, symbols-only addition) — Depth L1: two depth stacks compared pixel by pixel.  a (the truth) and b, float32
  * [n_views,H,W] in DEVICE memory, 0 = no hit (dqo_mesh_render_depth's, a Gaussian render's, a sensor's); view_keep as dqo_mesh_cull's;

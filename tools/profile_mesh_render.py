@@ -7,6 +7,13 @@ the comparison.  Yardsticks, in the same run on the same GPU:
     rasterise        no floor is claimed: the pairs, the pixels hit and the pairs the whole wave walked are printed beside the time.
     a second mesh    two wall-sized triangles in front of the scene (the ground-truth kind of face), alone and added to the mesh: the
                      whole-wave path's time, and a near surface that hides the rest.
+    the clip         dqo_eval.mesh_render_depth_clip on the volume's mesh, run in turns with the plain entry in the same process: the
+                     plain entry is the yardstick, and a mesh that hardly crosses the near planes runs the same statements per pair;
+                     then a floor of two triangles that every camera stands on (each pair crosses its near plane), which the plain
+                     entry drops and the clip rasterises by the whole wave.
+    the face cull    dqo_eval.mesh_cull_visible (the clipped render with face_index, then dqo_mesh_cull_faces) on the volume's mesh and
+                     on the mesh behind the two triangles, where two faces win most pixels; the pixels launch against the bytes it
+                     must read at the HBM peak: 4 per pixel, 12 with the frames' depth.
 
 `--lib` loads another build of the library — that is how the variants of profiles/mesh_render.txt were measured: map_meshrender.hip
 compiled with MR_SMALL_MAX set to 16 and to 256, and once with the atomic filter (a plain load of the pixel's key in front of the min
@@ -95,6 +102,45 @@ def main():
         print("  " + "  ".join(f"{k}: {v:.3f} ms" for k, v in per.items()) + "  (per launch, serialised by the timers)")
         wr = 12 if fi else 8
         print(f"  at {HBM_PEAK / 1e12:.1f} TB/s: clear {pixels * 8 / HBM_PEAK * 1e3:.3f} ms, resolve {pixels * (8 + wr - 4) / HBM_PEAK * 1e3:.3f} ms")
+    # the clip beside the plain entry: in turns, so that both see the same clocks
+    cnames = ("mesh_render_clear_kernel", "mesh_render_raster_clip_kernel", "mesh_render_resolve_kernel")
+    plain_out, clip_out = {}, {}
+    run_plain = lambda: dqo_eval.mesh_render_depth(mesh, w2c, K, W, H, out=plain_out)
+    run_clip = lambda: dqo_eval.mesh_render_depth_clip(mesh, w2c, K, W, H, out=clip_out)
+    for _ in range(WARMUP):
+        run_plain(), run_clip()
+    for turn in range(3):
+        for name, run, nm in (("mesh_render_depth", run_plain, names), ("mesh_render_depth_clip", run_clip, cnames)):
+            med, lo, hi = spread(run, a.reps)
+            per = launches(N, run, nm)
+            print(f"turn {turn}: {name}, the volume's mesh: median {med:.3f} ms, least {lo:.3f}, most {hi:.3f} of {a.reps};  rasterise launch {per[nm[1]]:.3f} ms")
+    print("  header, clipped: " + "  ".join(f"{k}={v}" for k, v in dqo_eval.mesh_counts(run_clip()).items()))
+    print("  same depth bytes as the plain entry: " + str(bool(torch.equal(plain_out["depth"], clip_out["depth"]))))
+    floor = dict(vertices=torch.tensor([[-6.0, 0.8, -6.0], [6.0, 0.8, -6.0], [6.0, 0.8, 6.0], [-6.0, 0.8, 6.0]], device=dev),
+                 faces=torch.tensor([[0, 1, 2], [0, 2, 3]], dtype=torch.int32, device=dev))
+    for name, fn, nm in (("mesh_render_depth", dqo_eval.mesh_render_depth, names), ("mesh_render_depth_clip", dqo_eval.mesh_render_depth_clip, cnames)):
+        out = {}
+        run = lambda fn=fn, out=out: fn(floor, w2c, K, W, H, out=out)
+        for _ in range(WARMUP):
+            run()
+        med, lo, hi = spread(run, a.reps)
+        per = launches(N, run, nm)
+        print(f"{name}, a floor of two triangles under every camera: median {med:.3f} ms, least {lo:.3f}, most {hi:.3f} of {a.reps};  rasterise launch {per[nm[1]]:.3f} ms")
+        print("  header: " + "  ".join(f"{k}={v}" for k, v in dqo_eval.mesh_counts(run()).items()))
+    # the face cull
+    fnames = ("mesh_cull_finit_kernel", "mesh_cull_pixels_kernel", "mesh_cull_fpix_kernel", "mesh_cull_vcount_kernel", "mesh_cull_vscatter_kernel",
+              "mesh_cull_fscatter_kernel")
+    for name, m, dep in (("the volume's mesh", mesh, None), ("the volume's mesh, against the ray-cast depth", mesh, sensor),
+                         ("the mesh behind the two triangles", both, None)):
+        run = lambda m=m, dep=dep: dqo_eval.mesh_cull_visible(m, w2c, K, W, H, depth=dep, eps=0.05)
+        for _ in range(WARMUP):
+            run()
+        med, lo, hi = spread(run, a.reps)
+        print(f"mesh_cull_visible, {name} (the clipped render, then six launches): median {med:.3f} ms, least {lo:.3f}, most {hi:.3f} of {a.reps}")
+        print("  header: " + "  ".join(f"{k}={v}" for k, v in dqo_eval.mesh_counts(run()).items()))
+        per = launches(N, run, fnames)
+        print("  " + "  ".join(f"{k}: {v:.3f} ms" for k, v in per.items()))
+        print(f"  pixels launch at {HBM_PEAK / 1e12:.1f} TB/s: {pixels * (4 if dep is None else 12) / HBM_PEAK * 1e3:.3f} ms")
     rendered = outs["the volume's mesh"]["depth"]
     run = lambda: dqo_eval.depth_l1(sensor, rendered, depth_trunc=30.0)
     for _ in range(WARMUP):
