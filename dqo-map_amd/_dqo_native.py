@@ -105,6 +105,20 @@ class DqoGrowthSample(ctypes.Structure):
                 [("workspace_bytes", ctypes.c_size_t)])
 
 
+class DqoWindowBank(ctypes.Structure):
+    """dqo_window_bank_select (ABI 5 symbols-only addition): the bank's parts, the destination a captured graph reads, the schedule, the
+    state words, the lost-frame log and the render's header."""
+    _fields_ = ([(n, c_i32) for n in ("W", "H", "K_cap", "n")] +
+                [(n, c_vp) for n in ("camera", "gt_color", "gt_depth", "render_mask", "tile_mask", "pixel_object", "tile_objects", "dst_bg",
+                                     "dst_viewmatrix", "dst_projmatrix", "dst_campos", "dst_gt_color", "dst_gt_depth", "dst_render_mask",
+                                     "dst_tile_mask", "dst_pixel_object", "dst_tile_objects", "schedule", "state", "lost", "render_header")])
+
+
+TICKET_WORDS = 16 + 16 * 64  # DQO_TICKET_WORDS
+# the state words of the keyframe bank behind its ticket (DQO_WINDOW_BANK_* of include/dqo_raster.h), in order, and the state's size
+WINDOW_BANK_WORDS = ("cursor", "n", "prev_k", "prev_m", "force", "overrun", "lost_count")
+WINDOW_BANK_STATE_WORDS = TICKET_WORDS + 48  # DQO_WINDOW_BANK_STATE_WORDS
+
 EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_enable", "dqo_profile_collect", "dqo_map_activate",
            "dqo_map_loss_workspace_bytes", "dqo_map_loss_fwd_bwd", "dqo_map_ssim_workspace_bytes", "dqo_map_ssim_fwd_bwd", "dqo_map_adam_step", "dqo_adam_multi_dev", "dqo_map_attach_workspace_bytes",
            "dqo_map_attach_loss_fwd_bwd", "dqo_adam_multi", "dqo_accumulate_gaussian_error", "dqo_accumulate_gaussian_confidence", "dqo_rast_geom_bytes", "dqo_rast_image_bytes",
@@ -132,7 +146,7 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_mesh_components", "dqo_mesh_smooth", "dqo_mesh_normals", "dqo_mesh_simplify_workspace_bytes", "dqo_mesh_simplify",
            "dqo_mesh_cull_workspace_bytes", "dqo_mesh_cull", "dqo_mesh_sample_counted_workspace_bytes", "dqo_mesh_sample_counted",
            "dqo_mesh_render_depth_workspace_bytes", "dqo_mesh_render_depth", "dqo_eval_depth_l1_workspace_bytes", "dqo_eval_depth_l1",
-           "dqo_mesh_render_depth_clip", "dqo_mesh_cull_faces")
+           "dqo_mesh_render_depth_clip", "dqo_mesh_cull_faces", "dqo_window_bank_arm", "dqo_window_bank_select")
 
 _lib = None
 
@@ -293,6 +307,9 @@ def lib():
         L.dqo_mesh_render_depth_clip.argtypes = L.dqo_mesh_render_depth.argtypes
         L.dqo_eval_depth_l1_workspace_bytes.argtypes = [c_i32, c_i32, c_i32]
         L.dqo_eval_depth_l1.argtypes = [c_i32] * 3 + [c_vp] * 3 + [c_f] + [c_vp] * 2 + [c_sz, c_vp]
+        # map_window_bank.hip
+        L.dqo_window_bank_arm.argtypes = [c_vp, c_i32, c_vp]
+        L.dqo_window_bank_select.argtypes = [P(DqoWindowBank), c_vp]
         # icp.hip, track.hip
         L.dqo_icp_normal_equations.argtypes = [c_i32, c_i32] + [c_vp] * 5 + [c_f] * 6 + [c_vp] * 4 + [c_sz, c_vp]
         L.dqo_icp_gauss_newton.argtypes = [c_i32, c_i32] + [c_vp] * 6 + [c_f] * 4 + [c_vp] * 2 + [c_sz, c_vp]
@@ -306,7 +323,7 @@ def lib():
             raise RuntimeError("libdqoraster.so ABI version mismatch")
         for k, st in enumerate((DqoRastParams, DqoRastInputs, DqoRastOutputs, DqoRastCtx, DqoRastGrads, DqoRastHeader, DqoProfileEntry,
                                 DqoAdamStep, DqoLossTap, DqoObjectGate, DqoAdamTensor, DqoRastParamInputs, DqoRastParamGrads, None,
-                                DqoLifecycle, DqoGrowthSample)):  # (None: index 13 is unused)
+                                DqoLifecycle, DqoGrowthSample, None, DqoWindowBank)):  # (None: indices 13 and 16 are unused)
             if st is not None and L.dqo_abi_sizeof(k) != ctypes.sizeof(st):
                 raise RuntimeError(f"libdqoraster.so: struct {st.__name__} is {L.dqo_abi_sizeof(k)} bytes in the library, "
                                    f"{ctypes.sizeof(st)} in the binding")

@@ -40,7 +40,7 @@ import torch
 import _dqo_native as N
 import diff_gaussian_rasterization_depth as dgr
 import dqo_mapgrowth as mg
-from _dqo_context import bucket_for, capacity_for, overflowed, read_header
+from _dqo_context import bucket_for, capacity_for, header_words, overflowed, read_header
 from dqo_harness import mapping
 from dqo_harness.map_operators import MapOperators, _RenderContext, _checked_tile_mask, _normalised_settings
 
@@ -137,7 +137,7 @@ class _FrameGraph:
     capacities, buffers and C structs the capture fixed (the graph holds their addresses)."""
 
     def __init__(self, frame, settings, pixel_object, tile_objects, gt_color, gt_depth, mask, tile_mask, options):
-        self.frame = frame  # slot of the window (None: the single-frame mapper's graph; (k, m): a mixed graph of _graph_of)
+        self.frame = frame  # slot of the window (None: the single-frame mapper's graph; (k, m): a mixed graph of _graph_of; "bank": capture_bank's)
         # the frame's inputs, read in place at every replay and rewritten in place by set_frame: the graph's own copies of the camera
         # tensors, the gate's owner map and its tile sets (None: no gate), the target images, the uint8 render mask (None: unmasked)
         self.settings, self.pixel_object, self.tile_objects = settings, pixel_object, tile_objects
@@ -145,6 +145,9 @@ class _FrameGraph:
         # capture()'s options as passed (tile_buckets, keep_tile_order, loss_tap, fused_tail, list_split, unroll, run_unroll,
         # short_bucket_margin): _recapture passes them again
         self.options = options
+        # capture_bank's graph: the keyframe bank, whose select launch every iteration of this graph issues first (None: the frame's inputs
+        # change by set_frame alone), and that launch's DqoWindowBank over this graph's buffers
+        self.head, self.head_args = options.get("head"), None
         self.stale = False  # the attach set / object gate changed since the capture: its kernel arguments point at freed buffers
         self.cap = 0  # instance capacity
         self.bucket = 0  # DqoRastCtx.tile_bucket_capacity (0: packed lists)
@@ -161,6 +164,99 @@ class _FrameGraph:
         self.fused_tail = False  # the per-Gaussian backward and Adam as one kernel (dqo_rast_backward_adam)
         self.unroll, self.graph = 1, None  # iterations per replay(), the graph
         self.run_unroll, self.run_graph = 1, None  # iterations per launch of replay_run's graph (None: run_unroll is 1)
+
+
+_CAMERA_ROW = (("bg", 0, 3), ("viewmatrix", 3, 19), ("projmatrix", 19, 35), ("campos", 35, 38))  # floats of a bank's camera row (DqoWindowBank)
+_CAPTURED_SCALARS = ("image_height", "image_width", "tanfovx", "tanfovy", "cx", "cy", "sh_degree", "scale_modifier", "opaque_threshold",
+                     "depth_threshold", "normal_threshold", "color_sigma", "T_threshold")  # kernel arguments of a captured iteration
+
+
+class _KeyframeBank:
+    """The keyframe bank of a FusedMapper (capture_bank): K_cap slots of everything a captured iteration reads per frame, in device
+    memory (DqoWindowBank's layout), the staging buffers ONE captured graph reads, the schedule, the select launch's state words and its
+    lost-frame log.  dqo_window_bank_select, issued at the head of every iteration of that graph, moves the scheduled slot into the
+    staging buffers (csrc/map_window_bank.hip)."""
+
+    def __init__(self, K_cap, st, gate, schedule_capacity, device):
+        H, W = int(st.image_height), int(st.image_width)
+        gy, gx = (H + 15) // 16, (W + 15) // 16
+        f, i32 = dict(dtype=torch.float32, device=device), dict(dtype=torch.int32, device=device)
+        self.K_cap, self.H, self.W, self.gate, self.device = int(K_cap), H, W, bool(gate), device
+        self.scalars = st  # the intrinsics every slot shares: captured kernel arguments
+        self.filled = [False] * self.K_cap
+        self.camera = torch.zeros((K_cap, 40), **f)
+        self.gt_color, self.gt_depth = torch.empty((K_cap, 3, H, W), **f), torch.empty((K_cap, 1, H, W), **f)
+        self.render_mask = torch.zeros((K_cap, H, W), dtype=torch.uint8, device=device)
+        self.tile_mask = torch.ones((K_cap, gy, gx), **i32)
+        self.pixel_object = torch.full((K_cap, H, W), -1, **i32) if gate else None
+        self.tile_objects = torch.zeros((K_cap, gy * gx), dtype=torch.int64, device=device) if gate else None
+        # what the graph reads (capture() makes its own copies of the camera tensors and of the gate's tile sets: DqoWindowBank's
+        # destination is taken from the graph, select())
+        self.stage = dict(gt_color=torch.empty((3, H, W), **f), gt_depth=torch.empty((1, H, W), **f),
+                          render_mask=torch.zeros((H, W), dtype=torch.uint8, device=device), tile_mask=torch.ones((gy, gx), **i32),
+                          pixel_object=torch.full((H, W), -1, **i32) if gate else None)
+        # a camera in tensors of its own for the renders that read a slot in place (probe(), refresh_bank): a camera row's parts start
+        # on 4-byte boundaries, the allocator's tensors on 256-byte ones
+        self.camera_scratch = st._replace(bg=torch.zeros((3,), **f), viewmatrix=torch.zeros((16,), **f), projmatrix=torch.zeros((16,), **f),
+                                          campos=torch.zeros((3,), **f))
+        self.schedule = torch.zeros((max(1, int(schedule_capacity)), 2), **i32)
+        self.lost = torch.zeros((self.schedule.shape[0],), **i32)
+        self.state = torch.zeros((N.WINDOW_BANK_STATE_WORDS,), **i32)
+        self.graph = None  # the _FrameGraph (frame "bank"); None: run_bank captures it
+        self.capture_kw, self.capacity_margin, self.unroll = {}, 1.15, 1
+
+    def slots(self):
+        return [k for k, on in enumerate(self.filled) if on]
+
+    def word(self, name):
+        """The state word `name` (N.WINDOW_BANK_WORDS) as a one-element view."""
+        at = N.TICKET_WORDS + N.WINDOW_BANK_WORDS.index(name)
+        return self.state[at:at + 1]
+
+    def camera_of(self, slot):
+        """Slot's camera as settings over camera_scratch (four small device copies; the next call overwrites them)."""
+        for name, a, b in _CAMERA_ROW:
+            getattr(self.camera_scratch, name).copy_(self.camera[slot, a:b])
+        return self.camera_scratch
+
+    def stage_slot(self, slot, g=None):
+        """Slot's parts into the staging buffers by host-issued copies (graph g given: into the buffers it reads)."""
+        dst = self.stage if g is None else dict(gt_color=g.gt_color, gt_depth=g.gt_depth, render_mask=g.mask, tile_mask=g.tile_mask,
+                                                pixel_object=g.pixel_object)
+        for name in ("gt_color", "gt_depth", "render_mask", "tile_mask") + (("pixel_object",) if self.gate else ()):
+            dst[name].copy_(getattr(self, name)[slot].view(dst[name].shape))
+        if g is not None:
+            for name, a, b in _CAMERA_ROW:
+                getattr(g.settings, name).copy_(self.camera[slot, a:b].view(getattr(g.settings, name).shape))
+            if self.gate:
+                g.tile_objects.copy_(self.tile_objects[slot].view(g.tile_objects.shape))
+
+    def probe(self, mapper):
+        """(candidates, longest tile list) a graph that serves every filled slot must hold: the maximum of FusedMapper._probe under
+        each slot's own camera, tile mask and owner map."""
+        cand = longest = 0
+        for k in self.slots():
+            c, l = mapper._probe(self.tile_mask[k], self.camera_of(k), self.pixel_object[k] if self.gate else None,
+                                 self.tile_objects[k] if self.gate else None)
+            cand, longest = max(cand, c), max(longest, l)
+        return cand, longest
+
+    def select(self, g, stream):
+        """dqo_window_bank_select into graph g's input buffers (the launch a captured iteration starts with)."""
+        if g.head_args is None:
+            st, gate = g.settings, self.gate
+            g.head_args = N.DqoWindowBank(
+                W=self.W, H=self.H, K_cap=self.K_cap, n=self.schedule.shape[0], camera=N.ptr(self.camera), gt_color=N.ptr(self.gt_color),
+                gt_depth=N.ptr(self.gt_depth), render_mask=N.ptr(self.render_mask), tile_mask=N.ptr(self.tile_mask),
+                pixel_object=N.ptr(self.pixel_object) if gate else None, tile_objects=N.ptr(self.tile_objects) if gate else None,
+                dst_bg=N.ptr(st.bg), dst_viewmatrix=N.ptr(st.viewmatrix), dst_projmatrix=N.ptr(st.projmatrix), dst_campos=N.ptr(st.campos),
+                dst_gt_color=N.ptr(g.gt_color), dst_gt_depth=N.ptr(g.gt_depth), dst_render_mask=N.ptr(g.mask), dst_tile_mask=N.ptr(g.tile_mask),
+                dst_pixel_object=N.ptr(g.pixel_object) if gate else None, dst_tile_objects=N.ptr(g.tile_objects) if gate else None,
+                schedule=N.ptr(self.schedule), state=N.ptr(self.state), lost=N.ptr(self.lost), render_header=g.geom.data_ptr())
+        N.check(N.lib().dqo_window_bank_select(ctypes.byref(g.head_args), stream))
+
+    def arm(self, n, stream):
+        N.check(N.lib().dqo_window_bank_arm(N.ptr(self.state), int(n), stream))
 
 
 class FusedMapper(MapOperators):
@@ -196,6 +292,7 @@ class FusedMapper(MapOperators):
         # _mixed: (k, m) -> graph of frame k's camera and target under frame m's masks (global_optimization's quirk)
         self._drop_graphs()
         self._window_kw, self._window_frames = {}, []  # capture_window's arguments: _graph_of captures mixed graphs from them
+        self._bank = None  # capture_bank's keyframe bank (_KeyframeBank); its graph is one of _graphs()
         self._last_probe = None  # (candidates, longest list, P) the last capture was sized on: capture(reuse_probe=True)
         self._side_stream = None  # grow()'s stream for the attach step (made once: creating a stream costs a growth step ~1 ms)
         # The reference keeps TWO clouds and trains one of them per mapping call while it renders one or both (mapper.py:533, 578,
@@ -271,6 +368,8 @@ class FusedMapper(MapOperators):
     # ------------------------------------------------------------------ the two clouds, per-call learning rates ---------
     def _graphs(self):
         gs = [g for g in self._frames if g is not None] + list(self._mixed.values())
+        if self._bank is not None and self._bank.graph is not None:
+            gs.append(self._bank.graph)
         if self._g is not None and all(self._g is not f for f in gs):
             gs.append(self._g)
         return gs
@@ -507,6 +606,8 @@ class FusedMapper(MapOperators):
         self._attach_n, self._act_valid = 0, False
         self._drop_row_sized_operator_state()
         self._drop_graphs()
+        if self._bank is not None:  # (the bank's keyframes do not depend on P: run_bank captures its graph again)
+            self._bank.graph = None
 
     @torch.no_grad()
     def reserve(self, spare_rows):
@@ -876,7 +977,7 @@ class FusedMapper(MapOperators):
     def capture(self, gt_color, gt_depth, render_mask, tile_mask=None, capacity_margin=1.15, tile_buckets=True, keep_tile_order=True,
                 loss_tap=True, reuse_probe=False, fused_tail=True, list_split=0, unroll=1, settings=None, pixel_object=None, frame=None,
                 run_unroll=1,
-                short_bucket_margin=1.3):
+                short_bucket_margin=1.3, head=None):
         """Allocate persistent buffers for every intermediate of an iteration, run it once eagerly, then capture it into a
         hipGraph.  The inputs (gt images, masks) are read from the tensors passed here at every replay().
 
@@ -902,7 +1003,10 @@ class FusedMapper(MapOperators):
         the previous capture's counts (scaled by the map's growth) instead of a probing forward — for a re-capture right after a small
         change of the map; falls back to probing if the eager iteration overflows.  unroll: iterations per graph — replay() then runs
         `unroll` iterations with one launch call (back-to-back graph launches leave the GPU idle for ~9 us each on MI355X; the
-        iterations inside one graph follow each other without a gap); self._g.out / self.loss then show the last of them."""
+        iterations inside one graph follow each other without a gap); self._g.out / self.loss then show the last of them.
+        head (capture_bank drives it, with frame="bank"): the keyframe bank whose select launch every iteration issues first — it moves
+        the scheduled keyframe into this graph's input buffers — and whose probe() sizes the capacities over all its keyframes; None,
+        the default: no such launch."""
         dev = self.device
         st = self._settings_or_own(settings)
         # (the graph's own copies: set_frame rewrites them in place)
@@ -924,7 +1028,8 @@ class FusedMapper(MapOperators):
         mask = None if render_mask is None else render_mask.to(torch.uint8).contiguous()
         g = _FrameGraph(frame, st, pix_obj, tile_obj, gt_color, gt_depth, mask, tile_mask,
                         dict(tile_buckets=tile_buckets, keep_tile_order=keep_tile_order, loss_tap=loss_tap, fused_tail=fused_tail,
-                             list_split=list_split, unroll=unroll, run_unroll=run_unroll, short_bucket_margin=short_bucket_margin))
+                             list_split=list_split, unroll=unroll, run_unroll=run_unroll, short_bucket_margin=short_bucket_margin,
+                             head=head))
         with torch.cuda.device(dev):
             # re-capture (e.g. after an overflow): replays of invalid frames did not advance the device-side step count
             # (DqoAdamStep.frame_header), the host count assumed they did — _settle_replays takes exactly those back; eager step()
@@ -937,6 +1042,8 @@ class FusedMapper(MapOperators):
             self._g = g
             if isinstance(frame, tuple):  # (camera / target of frame k, masks of frame m): global_optimization's second half
                 self._mixed[frame] = g
+            elif frame == "bank":
+                self._bank.graph = g
             elif frame is not None:
                 while len(self._frames) <= frame:
                     self._frames.append(None)
@@ -970,7 +1077,10 @@ class FusedMapper(MapOperators):
             cand, longest = int(last[0] * grown) + 1, int(last[1] * grown) + 1
         else:
             reuse_probe = False
-            cand, longest = self._probe(g.tile_mask, g.settings, g.pixel_object, g.tile_objects)
+            if g.head is not None:  # (the one graph of a keyframe bank serves every keyframe: the largest of their counts)
+                cand, longest = g.head.probe(self)
+            else:
+                cand, longest = self._probe(g.tile_mask, g.settings, g.pixel_object, g.tile_objects)
         self._last_probe = (cand, longest, P)
         g.cap = capacity_for(cand, capacity_margin)
         # fixed per-tile list buckets (bucket_for; short_bucket_margin: how much margin over the longest list is worth keeping the
@@ -1198,6 +1308,177 @@ class FusedMapper(MapOperators):
             i += len(batch)
         return recaptures
 
+    # ------------------------------------------------------------------ the keyframe bank (csrc/map_window_bank.hip) -----
+    def _require_bank(self, who):
+        if self._bank is None:
+            raise RuntimeError(f"FusedMapper.{who}: this mapper has no keyframe bank; call capture_bank() first")
+        return self._bank
+
+    @torch.no_grad()
+    def capture_bank(self, frames, slots=None, schedule_capacity=16384, capacity_margin=1.15, unroll=1, **capture_kw):
+        """ONE captured graph that trains over a whole keyframe set — the call that ends every run of the reference,
+        global_optimization(is_end=True) (SLAM/slam.py:183, mapper.py:1143-1148, 1196-1199: all keyframes, a random one per iteration),
+        where one graph, one probe and one set of context buffers per keyframe (capture_window) cost more than the iterations they
+        prepare.  frames: capture_window's dicts, every one with a render mask; they fill slots 0 .. len(frames) - 1 of a bank of
+        `slots` (default len(frames)) keyframes in device memory — spare slots take keyframes that arrive later (bank_set) without a new
+        capture.  The graph reads staging buffers of its own; every iteration of it starts with dqo_window_bank_select, which moves the
+        keyframe the device-side schedule names into them (run_bank), so the frame choice costs no host work and iterations on
+        DIFFERENT frames share a launch: unroll = iterations per launch of run_bank (a single-iteration graph serves the tail).
+        The capacities are the maximum over the filled slots of what a probe under each slot's own camera and tile mask reports, with
+        capacity_margin; schedule_capacity: entries of the device schedule (run_bank uploads a longer one in pieces).  capture_kw:
+        capture()'s other options (list_split="auto" is refused: it is a per-frame choice; keep_tile_order defaults to False here: one frame's
+        tile order would serve every keyframe).  The capture's eager iteration is undone as
+        capture_window undoes it; the select state is left unarmed.  Parameters, moments and every result are bit for bit those of
+        capture_window + run_window on the same schedule."""
+        self._refuse_sharded("capture_bank", "would need a bank per shard and one schedule over them")
+        if capture_kw.get("list_split", 0) == "auto":
+            raise RuntimeError("FusedMapper.capture_bank: list_split='auto' is a per-frame choice; give a threshold")
+        for name in ("run_unroll", "frame", "head", "settings", "pixel_object", "tile_mask", "reuse_probe"):
+            if name in capture_kw:
+                raise RuntimeError(f"FusedMapper.capture_bank: {name} is not an option of a bank's graph")
+        frames = list(frames)
+        K_cap = len(frames) if slots is None else int(slots)
+        if not frames or K_cap < len(frames):
+            raise RuntimeError("FusedMapper.capture_bank: slots must hold the frames given (at least one)")
+        if any(fr.get("render_mask") is None for fr in frames):
+            raise RuntimeError("FusedMapper.capture_bank: every keyframe needs a render mask")
+        bank = _KeyframeBank(K_cap, self.settings, self.gaussian_object is not None, schedule_capacity, self.device)
+        # keep_tile_order would keep the tile launch order of the ONE frame the capture's eager iteration ran on for every keyframe: a
+        # stale order costs the blend kernels more (30 us on bench.py's window of five, profiles/window_bank.txt) than the scan that
+        # recomputes it (20 us), and the keyframes of a bank lie further apart than a window's frames.  Off unless asked for; the order
+        # is a scheduling hint, the results are the same bits either way
+        capture_kw.setdefault("keep_tile_order", False)
+        bank.capture_kw, bank.capacity_margin, bank.unroll = dict(capture_kw), float(capacity_margin), max(1, int(unroll))
+        self._bank = bank
+        for k, fr in enumerate(frames):
+            self.bank_set(k, gt_color=fr["gt_color"], gt_depth=fr["gt_depth"], render_mask=fr["render_mask"], tile_mask=fr.get("tile_mask"),
+                          settings=fr.get("settings", self.settings),
+                          pixel_object=(self.pixel_object if fr.get("pixel_object") is None else fr["pixel_object"]) if bank.gate else None)
+        self._capture_bank_graph(bank.capacity_margin)
+        return self
+
+    def _capture_bank_graph(self, capacity_margin):
+        """The bank's graph, captured (again) on the current state: staging buffers filled from the first keyframe for the eager
+        iteration, whose select launch finds an empty schedule and copies nothing; the iteration is undone."""
+        bank = self._bank
+        self._settle_replays()  # (the snapshot's step count is the settled one)
+        snap = self._snapshot_state()
+        cur = self._g
+        with torch.cuda.device(self.device):
+            bank.stage_slot(bank.slots()[0])
+            bank.arm(0, N.current_stream())
+        self.capture(bank.stage["gt_color"], bank.stage["gt_depth"], bank.stage["render_mask"], tile_mask=bank.stage["tile_mask"],
+                     settings=bank.camera_of(bank.slots()[0]), pixel_object=bank.stage["pixel_object"], frame="bank",
+                     capacity_margin=capacity_margin, unroll=1, run_unroll=bank.unroll, head=bank, **bank.capture_kw)
+        torch.cuda.synchronize()
+        self._restore_state(snap)
+        self._g = cur if cur is not None else bank.graph
+
+    @torch.no_grad()
+    def bank_set(self, slot, gt_color=None, gt_depth=None, render_mask=None, tile_mask=None, settings=None, pixel_object=None):
+        """New inputs for slot `slot` of the keyframe bank, written in place, with set_frame's rules: same shapes, and the scalar
+        intrinsics are captured kernel arguments that must not change.  A slot that was never filled needs gt_color, gt_depth,
+        render_mask and settings; a new keyframe in a spare slot keeps the captured graph (if it outgrows the capacities, run_bank
+        captures again as for any overflow).  The next select copies both groups whatever it copied last (force)."""
+        bank = self._require_bank("bank_set")
+        slot = int(slot)
+        if not 0 <= slot < bank.K_cap:
+            raise RuntimeError(f"FusedMapper.bank_set: slot {slot} outside the bank's {bank.K_cap}")
+        H, W, dev = bank.H, bank.W, self.device
+        if not bank.filled[slot] and any(x is None for x in (gt_color, gt_depth, render_mask, settings)):
+            raise RuntimeError("FusedMapper.bank_set: a new keyframe needs gt_color, gt_depth, render_mask and settings")
+        if pixel_object is not None and not bank.gate:
+            raise RuntimeError("FusedMapper.bank_set: the bank was captured without an object gate")
+        if settings is not None:
+            new = _normalised_settings(settings, dev)
+            for name in _CAPTURED_SCALARS:
+                if getattr(new, name) != getattr(bank.scalars, name):
+                    raise RuntimeError(f"FusedMapper.bank_set: {name} is a captured kernel argument; every keyframe of a bank shares it")
+            for name, a, b in _CAMERA_ROW:
+                bank.camera[slot, a:b].copy_(getattr(new, name).reshape(-1))
+        for name, src, shape in (("gt_color", gt_color, (3, H, W)), ("gt_depth", gt_depth, (1, H, W))):
+            if src is not None:
+                if tuple(src.shape) != shape or src.dtype != torch.float32:
+                    raise RuntimeError(f"FusedMapper.bank_set: {name} must be a float32 tensor of shape {shape}")
+                getattr(bank, name)[slot].copy_(src)
+        if render_mask is not None:
+            bank.render_mask[slot].copy_(render_mask.to(torch.uint8).reshape(H, W))
+        if tile_mask is not None:
+            bank.tile_mask[slot].copy_(_checked_tile_mask(tile_mask, dev, H, W).view(bank.tile_mask.shape[1:]))
+        if pixel_object is not None:
+            bank.pixel_object[slot].copy_(torch.as_tensor(pixel_object).to(dev, torch.int32).reshape(H, W))
+            bank.tile_objects[slot].copy_(tile_object_sets(bank.pixel_object[slot]))
+        bank.filled[slot] = True
+        bank.word("force").fill_(1)
+        return self
+
+    def _bank_launch(self, n):
+        """n iterations of the bank's graph: launches of `unroll` iterations while that many remain, single ones for the rest."""
+        g = self._bank.graph
+        self._g, k = g, g.run_unroll
+        while n >= k and k > 1:
+            self._launch(g, g.run_graph, k)
+            n -= k
+        for _ in range(n):
+            self._launch(g, g.graph, 1)
+
+    def run_bank(self, schedule, check_every=64, capacity_margin=1.5):
+        """The iterations of `schedule` — window_schedule's list: slot indices, or pairs (k, m) = slot k's camera, targets and gate
+        under slot m's render mask and tile mask — on the bank's ONE graph: one upload of the schedule, one arm launch, then graph
+        launches with no host work per iteration.  One small read per `check_every` iterations: the device step count, the select
+        state's overrun and lost_count words and the overflow flag of the batch's last frame.  A frame that outgrew the captured
+        capacities was a no-op for the optimiser; the select launch behind it logged its schedule position, so the lost positions are
+        known exactly: the graph is captured again on the current state with `capacity_margin`, the rest of the schedule goes on, and
+        the lost entries are replayed as a new armed schedule after it — the call trains the schedule less the retried positions, then
+        the retried positions.  Returns the retried schedule positions (a position retried twice is listed twice)."""
+        bank = self._require_bank("run_bank")
+        entries = [tuple(int(x) for x in e) if isinstance(e, (tuple, list)) else (int(e), int(e)) for e in schedule]
+        for k, m in entries:
+            if not (0 <= k < bank.K_cap and 0 <= m < bank.K_cap and bank.filled[k] and bank.filled[m]):
+                raise RuntimeError(f"FusedMapper.run_bank: schedule entry ({k}, {m}) names a slot that holds no keyframe")
+        if bank.graph is None:
+            self._capture_bank_graph(bank.capacity_margin)
+        retried, pending, recaptures = [], list(range(len(entries))), [0]
+        while pending:
+            lost = self._run_bank_pass([entries[p] for p in pending], check_every, capacity_margin, recaptures)
+            pending = [pending[i] for i in lost]
+            retried += pending
+        return retried
+
+    def _run_bank_pass(self, entries, check_every, capacity_margin, recaptures):
+        """One armed pass over `entries`; returns the positions (indices into entries) whose frames were lost.  recaptures: [count]."""
+        bank, dev = self._bank, self.device
+        room, lost_all = bank.schedule.shape[0], []
+        i, first, end, logged = 0, 0, 0, 0  # the armed piece is entries[first:end]; `logged` entries of its log have been read
+        with torch.cuda.device(dev):
+            while i < len(entries):
+                if i >= end:
+                    first, end, logged = i, min(len(entries), i + room), 0
+                    bank.schedule[:end - first].copy_(torch.from_numpy(np.asarray(entries[first:end], np.int32).reshape(-1, 2)))
+                    bank.arm(end - first, N.current_stream())
+                b = min(int(check_every), end - i)
+                self._bank_launch(b)
+                i += b
+                words = torch.cat([self._step_dev, bank.state[N.TICKET_WORDS:N.TICKET_WORDS + len(N.WINDOW_BANK_WORDS)],
+                                   header_words(bank.graph.geom)[2:3]]).tolist()
+                dev_step, state, last_lost = words[0], dict(zip(N.WINDOW_BANK_WORDS, words[1:])), words[-1] != 0
+                if state["overrun"]:
+                    raise RuntimeError(f"FusedMapper.run_bank: the select launch ran off its schedule (overrun {state['overrun']})")
+                lost = bank.lost[logged:state["lost_count"]].tolist() if state["lost_count"] > logged else []
+                if last_lost:  # (the next select would log it; the schedule is armed anew before that)
+                    lost.append(i - 1 - first)
+                if (self.step_count + 1) - dev_step != len(lost):
+                    raise RuntimeError("FusedMapper.run_bank: the device step count and the lost-frame log disagree")
+                if lost:
+                    lost_all += [first + p for p in lost]
+                    self._settle_replays()
+                    recaptures[0] += 1
+                    if recaptures[0] > 8 * max(1, len(bank.slots())):
+                        raise RuntimeError("FusedMapper.run_bank: the map keeps outgrowing the captured capacities")
+                    self._capture_bank_graph(capacity_margin)
+                    end = i  # (the capture's eager select used the state: the rest of the schedule is armed anew)
+        return lost_all
+
     @torch.no_grad()
     def set_frame(self, frame, gt_color=None, gt_depth=None, render_mask=None, tile_mask=None, settings=None, pixel_object=None):
         """New inputs for a captured frame WITHOUT a new capture: the next mapping call's window keeps four of its five frames and every
@@ -1232,8 +1513,7 @@ class FusedMapper(MapOperators):
         if settings is not None:
             new = _normalised_settings(settings, self.device)
             for g in cams:
-                for name in ("image_height", "image_width", "tanfovx", "tanfovy", "cx", "cy", "sh_degree", "scale_modifier", "opaque_threshold",
-                             "depth_threshold", "normal_threshold", "color_sigma", "T_threshold"):
+                for name in _CAPTURED_SCALARS:
                     if getattr(new, name) != getattr(g.settings, name):
                         raise RuntimeError(f"FusedMapper.set_frame: {name} is a captured kernel argument; capture the frame again")
                 for name in ("bg", "viewmatrix", "projmatrix", "campos"):
@@ -1327,6 +1607,8 @@ class FusedMapper(MapOperators):
         st = self.settings
         H, W = int(st.image_height), int(st.image_width)
         stream = N.current_stream()
+        if g.head is not None:  # (a bank graph: the scheduled keyframe moves into the buffers the calls below read)
+            g.head.select(g, stream)
         g.cctx.list_split = g.ls_fwd
         N.check(forward(ctypes.byref(g.params), ctypes.byref(g.inputs), ctypes.byref(g.outputs), ctypes.byref(g.cctx), stream))
         g.cctx.list_split = g.ls_bwd  # (0 with a split forward: the single-wave backward walks every list, the queue is ignored)

@@ -22,7 +22,7 @@ from _dqo_context import RastContext, capacity_for, overflowed
 #   the camera      settings (normalised), tile_mask (the shared all-ones one), add_depth_thres
 #   spare rows      _park_position(), _free_rows(rows), _ensure_alive(), _n_spare / _n_spare_stale, reserve()
 #   the two clouds  trained_rows(), stable_rows(), _require_lifecycle(who), track_lifecycle(), attach_count_reducer (a shard's mark)
-#   refresh_window  _frames / _mixed, the captured graphs whose masks it writes
+#   refresh_window  _frames / _mixed, the captured graphs whose masks it writes; refresh_bank: _bank / _require_bank(who), the keyframe bank
 #   load_model      _graphs(), _last_probe, begin_mapping_call(), set_training_rows(); from_model_ply also the constructor
 # and what it owns: the operators' scratch, declared in _init_operator_state() and dropped per P by _drop_row_sized_operator_state().
 
@@ -944,15 +944,39 @@ class MapOperators:
                                    "mapper's shared all-ones tile mask, which every default-mask render reads too)")
             if g.mask.numel() != H * W or g.tile_mask.numel() != gy * gx:
                 raise RuntimeError("FusedMapper.refresh_window: every frame of a mapper has the mapper's image size")
+        targets = [(lambda g=self._frames[k]: g.settings, self._frames[k].gt_color, self._frames[k].mask.view(H, W),
+                    self._frames[k].tile_mask.view(gy, gx)) for k in slots]
+        table = self._window_mask_pass("refresh_window", targets, global_opt, sample_ratio, rows, out)
+        done = set()
+        for k in slots:
+            done.update((self._frames[k].mask.data_ptr(), self._frames[k].tile_mask.data_ptr()))
+        with torch.cuda.device(dev):
+            for k in slots:
+                g = self._frames[k]
+                for (_, m), g2 in self._mixed.items():
+                    if m != k:
+                        continue
+                    for src, dst in ((g.mask, g2.mask), (g.tile_mask, g2.tile_mask)):
+                        if dst is not None and dst.data_ptr() not in done and dst.data_ptr() != self.tile_mask.data_ptr():
+                            done.add(dst.data_ptr())
+                            dst.copy_(src.view(dst.shape))
+        return table
+
+    def _window_mask_pass(self, who, targets, global_opt, sample_ratio, rows, out):
+        """The loop refresh_window and refresh_bank share.  targets: per frame (camera: a call that returns the settings to render at,
+        made when the frame's turn comes; gt_color; render mask uint8 [H,W]; tile mask int32 [gy,gx]) — the masks are written in place.
+        Returns the ratio table (refresh_window says what `rows` and `out` are and what the first call reads back)."""
+        dev = self.device
+        H, W = int(self.settings.image_height), int(self.settings.image_width)
         if rows is None:
             rows = self.trained_rows()
         elif not torch.is_tensor(rows) or rows.dtype != torch.bool or rows.numel() != self.P or rows.device != self.row_flags.device:
-            raise RuntimeError("FusedMapper.refresh_window: rows must be a bool GPU tensor with one entry per row")
-        K = len(slots)
+            raise RuntimeError(f"FusedMapper.{who}: rows must be a bool GPU tensor with one entry per row")
+        K = len(targets)
         if out is None:
             table = self._own_table(self._window_ratios, K)
         elif out.dtype != torch.float32 or tuple(out.shape) != (K,) or not out.is_contiguous() or out.device != self.row_flags.device:
-            raise RuntimeError(f"FusedMapper.refresh_window: out must be a contiguous float32 [{K}] tensor on the mapper's device")
+            raise RuntimeError(f"FusedMapper.{who}: out must be a contiguous float32 [{K}] tensor on the mapper's device")
         else:
             table = out
         with torch.cuda.device(dev):
@@ -965,22 +989,26 @@ class MapOperators:
                 hidden |= self.alive == 0
             self._window_flags.copy_(hidden).mul_(N.ROW_HIDDEN)
             self.activate()
-            done = set()
-            for i, k in enumerate(slots):
-                g = self._frames[k]
-                c = self._maintain_render(g.settings, row_flags=self._window_flags)
+            for i, (camera, gt_color, render_mask, tile_mask) in enumerate(targets):
+                c = self._maintain_render(camera(), row_flags=self._window_flags)
                 o = c.out
-                dqo_tilemask.window_masks(o[6], o[0], g.gt_color, global_opt=global_opt, sample_ratio=sample_ratio,
-                                          render_mask=g.mask.view(H, W), tile_mask=g.tile_mask.view(gy, gx), ratio_out=table[i:i + 1],
-                                          render_header=c.geom, workspace=self._window_ws)
-                done.update((g.mask.data_ptr(), g.tile_mask.data_ptr()))
-            for k in slots:
-                g = self._frames[k]
-                for (_, m), g2 in self._mixed.items():
-                    if m != k:
-                        continue
-                    for src, dst in ((g.mask, g2.mask), (g.tile_mask, g2.tile_mask)):
-                        if dst is not None and dst.data_ptr() not in done and dst.data_ptr() != self.tile_mask.data_ptr():
-                            done.add(dst.data_ptr())
-                            dst.copy_(src.view(dst.shape))
+                dqo_tilemask.window_masks(o[6], o[0], gt_color, global_opt=global_opt, sample_ratio=sample_ratio, render_mask=render_mask,
+                                          tile_mask=tile_mask, ratio_out=table[i:i + 1], render_header=c.geom, workspace=self._window_ws)
+        return table
+
+    @torch.no_grad()
+    def refresh_bank(self, slots=None, *, global_opt=False, sample_ratio=-1, rows=None, out=None):
+        """refresh_window's loop for the keyframes of the bank (capture_bank; `slots`: default every filled one): the cloud `rows` rendered
+        at the slot's camera, dqo_tilemask.window_masks straight into the slot's render mask and tile mask in the bank — the next select
+        launch that names the slot copies them (force is set: also when the slot is the one the graph holds).  Returns the ratio table
+        as refresh_window does; like it, a call after the first for a (P, H, W) reads nothing back and does not synchronise."""
+        self._refuse_sharded("refresh_bank")
+        bank = self._require_bank("refresh_bank")
+        slots = bank.slots() if slots is None else [int(k) for k in slots]
+        for k in slots:
+            if not 0 <= k < bank.K_cap or not bank.filled[k]:
+                raise RuntimeError(f"FusedMapper.refresh_bank: slot {k} of the bank holds no keyframe")
+        targets = [(lambda k=k: bank.camera_of(k), bank.gt_color[k], bank.render_mask[k], bank.tile_mask[k]) for k in slots]
+        table = self._window_mask_pass("refresh_bank", targets, global_opt, sample_ratio, rows, out)
+        bank.word("force").fill_(1)
         return table

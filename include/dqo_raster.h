@@ -1659,6 +1659,75 @@ int dqo_rast_backward_adam(const DqoRastParams*, const DqoRastInputs*, const Dqo
                            const float* dL_dout_depth, const DqoAdamStep* step, void* workspace, size_t workspace_bytes,
                            void* hipStream);
 
+/* dqo_window_bank_arm / dqo_window_bank_select (ABI 5, symbols-only addition) — the keyframe bank.  The final pass of the reference,
+ * global_optimization(is_end=True) (SLAM/slam.py:183, SLAM/multiprocess/mapper.py:1143-1148, 1196-1199), trains over ALL keyframes with a
+ * random keyframe per iteration.  A captured iteration reads everything per frame from device buffers (the DESTINATION below); a bank of
+ * keyframes and a schedule in device memory plus ONE launch at the head of the iteration, which moves the scheduled keyframe into those
+ * buffers, let one captured graph train over any number of keyframes with no host work per iteration.  csrc/map_window_bank.hip lists
+ * the statements in order; tests/window_bank_oracle.py restates them.
+ *   The bank: K_cap slots, a structure of arrays in caller-owned device memory, every part contiguous per slot.  gy = ceil(H/16),
+ *     gx = ceil(W/16).
+ *       camera        float32 [K_cap, 40]        bg[3], viewmatrix[16], projmatrix[16], campos[3], two pad floats
+ *       gt_color      float32 [K_cap, 3, H, W]     gt_depth     float32 [K_cap, 1, H, W]
+ *       render_mask   uint8   [K_cap, H, W]        tile_mask    int32   [K_cap, gy, gx]
+ *       pixel_object  int32   [K_cap, H, W]        tile_objects int64   [K_cap, gy * gx]     (both NULL without an object gate)
+ *   The destination: dst_bg [3], dst_viewmatrix [16], dst_projmatrix [16], dst_campos [3] (four pointers of their own), dst_gt_color,
+ *     dst_gt_depth, dst_render_mask, dst_tile_mask, dst_pixel_object, dst_tile_objects: one slot's worth each.  The gate parts are given
+ *     on both sides or on neither.
+ *   The schedule: int32 [n][2] in device memory; entry (k, m) = camera, targets and gate of slot k under the render mask and tile mask
+ *     of slot m (the pair of global_optimization's second half, mapper.py:1188-1195); a plain keyframe k is (k, k).  `lost`: int32 [n].
+ *     `n` of the struct is the ENTRIES both lists hold; the length of the armed schedule is the state's word.
+ *   The state: DQO_WINDOW_BANK_STATE_WORDS int32 of device memory: the ticket's DQO_TICKET_WORDS, then the words of the enum below, padded
+ *     to a multiple of 256 bytes as every last-block head is.  dqo_window_bank_arm writes ALL of it (no zero fill needed before).
+ *   dqo_window_bank_arm(state, n, stream): one small launch: cursor = 0, n, prev_k = prev_m = -1, force = 1, overrun = lost_count = 0, the
+ *     ticket words zero.
+ *   dqo_window_bank_select(args, stream): ONE launch, the same grid on every call, capturable.  Every block reads c = cursor, n, the
+ *     previous pair and force.  Then
+ *       c >= n, or c >= args.n             nothing is copied; overrun = 1; the cursor, the previous pair, force and the log stay
+ *       (k, m) = schedule[c] with k or m outside [0, K_cap): nothing is copied; overrun = 2; the rest stays likewise
+ *       otherwise   camera, gt_color, gt_depth, pixel_object, tile_objects from slot k  iff  force != 0 or k != prev_k;
+ *                   render_mask, tile_mask from slot m                                  iff  force != 0 or m != prev_m;
+ *                   if c > 0 and render_header (may be NULL; the device header of the context the graph renders on) has its overflow
+ *                   word set (!= 0, as dqo_eval_picture and dqo_tsdf_integrate test it), the frame trained at position c - 1 was a no-op
+ *                   for the optimiser (DqoAdamStep.frame_header): lost[lost_count] = c - 1, lost_count += 1;
+ *                   then prev_k = k, prev_m = m, force = 0, cursor = c + 1.
+ *     Copies are exact bytes and nothing outside the destinations' extents is written: 16-byte accesses where source and destination
+ *     are both 16-byte aligned, 4-byte ones where both are 4-byte aligned, single bytes otherwise, and single bytes for what is left
+ *     of a part whose length is no multiple of the access.  The state changes in the block that takes the launch's last ticket, after
+ *     every block has read it.  Integer atomics on the ticket words only; no float arithmetic.
+ *   DQO_ERR_INVALID_ARG before the launch: K_cap < 1, a bad image size, a NULL required pointer (everything but render_header and the
+ *     gate parts), gate parts on one side only, n < 0; dqo_window_bank_arm: a NULL state, n < 0.  Calls that share a state must be
+ *     ordered (one stream). */
+enum {
+    DQO_WINDOW_BANK_CURSOR = DQO_TICKET_WORDS + 0,     /* schedule position of the NEXT select */
+    DQO_WINDOW_BANK_N = DQO_TICKET_WORDS + 1,          /* length of the armed schedule */
+    DQO_WINDOW_BANK_PREV_K = DQO_TICKET_WORDS + 2,     /* the slots the destination holds: camera group / mask group (-1: none) */
+    DQO_WINDOW_BANK_PREV_M = DQO_TICKET_WORDS + 3,
+    DQO_WINDOW_BANK_FORCE = DQO_TICKET_WORDS + 4,      /* non-zero: copy even if unchanged; cleared by the launch that honours it */
+    DQO_WINDOW_BANK_OVERRUN = DQO_TICKET_WORDS + 5,    /* 1: a select ran past the schedule; 2: a schedule entry names no slot */
+    DQO_WINDOW_BANK_LOST_COUNT = DQO_TICKET_WORDS + 6, /* entries of `lost` */
+    DQO_WINDOW_BANK_STATE_WORDS = DQO_TICKET_WORDS + 48
+};
+typedef struct DqoWindowBank {
+    int32_t W, H, K_cap, n;
+    const float *camera, *gt_color, *gt_depth;
+    const uint8_t* render_mask;
+    const int32_t* tile_mask;
+    const int32_t* pixel_object;
+    const int64_t* tile_objects;
+    float *dst_bg, *dst_viewmatrix, *dst_projmatrix, *dst_campos, *dst_gt_color, *dst_gt_depth;
+    uint8_t* dst_render_mask;
+    int32_t* dst_tile_mask;
+    int32_t* dst_pixel_object;
+    int64_t* dst_tile_objects;
+    const int32_t* schedule;
+    int32_t* state;
+    int32_t* lost;
+    const DqoRastHeader* render_header;
+} DqoWindowBank;
+int dqo_window_bank_arm(int32_t* state, int32_t n, void* hipStream);
+int dqo_window_bank_select(const DqoWindowBank*, void* hipStream);
+
 #ifdef __cplusplus
 }
 #endif
