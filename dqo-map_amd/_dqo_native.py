@@ -114,6 +114,21 @@ class DqoWindowBank(ctypes.Structure):
                                      "dst_tile_mask", "dst_pixel_object", "dst_tile_objects", "schedule", "state", "lost", "render_header")])
 
 
+class DqoTrajRepose(ctypes.Structure):
+    """dqo_traj_repose (ABI 5 symbols-only addition): the trajectory's store and header, the corrected poses, the target table
+    (REPOSE_TARGET_FIELDS per entry), the projection, a keyframe bank's state words and the counts."""
+    _fields_ = ([(n, c_i32) for n in ("cap", "n_new", "T", "flags")] +
+                [(n, c_vp) for n in ("pose", "header", "new_pose", "targets", "projection", "bank_state", "stats")])
+
+
+class DqoReposeTarget(ctypes.Structure):
+    _fields_ = [("row", ctypes.c_int64)] + [(n, c_vp) for n in ("c2w", "w2c", "viewmatrix", "projmatrix", "campos")]
+
+
+# a DqoReposeTarget as the columns of an int64 [T,6] device table, and DQO_REPOSE_HAS_PROJMATRIX
+REPOSE_TARGET_FIELDS = ("row", "c2w", "w2c", "viewmatrix", "projmatrix", "campos")
+REPOSE_HAS_PROJMATRIX = 1
+
 TICKET_WORDS = 16 + 16 * 64  # DQO_TICKET_WORDS
 # the state words of the keyframe bank behind its ticket (DQO_WINDOW_BANK_* of include/dqo_raster.h), in order, and the state's size
 WINDOW_BANK_WORDS = ("cursor", "n", "prev_k", "prev_m", "force", "overrun", "lost_count")
@@ -146,7 +161,7 @@ EXPORTS = ("dqo_abi_version", "dqo_abi_sizeof", "dqo_last_error", "dqo_profile_e
            "dqo_mesh_components", "dqo_mesh_smooth", "dqo_mesh_normals", "dqo_mesh_simplify_workspace_bytes", "dqo_mesh_simplify",
            "dqo_mesh_cull_workspace_bytes", "dqo_mesh_cull", "dqo_mesh_sample_counted_workspace_bytes", "dqo_mesh_sample_counted",
            "dqo_mesh_render_depth_workspace_bytes", "dqo_mesh_render_depth", "dqo_eval_depth_l1_workspace_bytes", "dqo_eval_depth_l1",
-           "dqo_mesh_render_depth_clip", "dqo_mesh_cull_faces", "dqo_window_bank_arm", "dqo_window_bank_select")
+           "dqo_mesh_render_depth_clip", "dqo_mesh_cull_faces", "dqo_window_bank_arm", "dqo_window_bank_select", "dqo_traj_repose")
 
 _lib = None
 
@@ -310,6 +325,8 @@ def lib():
         # map_window_bank.hip
         L.dqo_window_bank_arm.argtypes = [c_vp, c_i32, c_vp]
         L.dqo_window_bank_select.argtypes = [P(DqoWindowBank), c_vp]
+        # map_repose.hip
+        L.dqo_traj_repose.argtypes = [P(DqoTrajRepose), c_vp]
         # icp.hip, track.hip
         L.dqo_icp_normal_equations.argtypes = [c_i32, c_i32] + [c_vp] * 5 + [c_f] * 6 + [c_vp] * 4 + [c_sz, c_vp]
         L.dqo_icp_gauss_newton.argtypes = [c_i32, c_i32] + [c_vp] * 6 + [c_f] * 4 + [c_vp] * 2 + [c_sz, c_vp]
@@ -323,7 +340,7 @@ def lib():
             raise RuntimeError("libdqoraster.so ABI version mismatch")
         for k, st in enumerate((DqoRastParams, DqoRastInputs, DqoRastOutputs, DqoRastCtx, DqoRastGrads, DqoRastHeader, DqoProfileEntry,
                                 DqoAdamStep, DqoLossTap, DqoObjectGate, DqoAdamTensor, DqoRastParamInputs, DqoRastParamGrads, None,
-                                DqoLifecycle, DqoGrowthSample, None, DqoWindowBank)):  # (None: indices 13 and 16 are unused)
+                                DqoLifecycle, DqoGrowthSample, None, DqoWindowBank, DqoTrajRepose, DqoReposeTarget)):  # (None: indices 13 and 16 are unused)
             if st is not None and L.dqo_abi_sizeof(k) != ctypes.sizeof(st):
                 raise RuntimeError(f"libdqoraster.so: struct {st.__name__} is {L.dqo_abi_sizeof(k)} bytes in the library, "
                                    f"{ctypes.sizeof(st)} in the binding")

@@ -97,7 +97,8 @@ DQO_API size_t dqo_abi_sizeof(int32_t which) {
     static const size_t sz[] = {sizeof(DqoRastParams), sizeof(DqoRastInputs), sizeof(DqoRastOutputs), sizeof(DqoRastCtx), sizeof(DqoRastGrads),
                                 sizeof(DqoRastHeader), sizeof(DqoProfileEntry), sizeof(DqoAdamStep), sizeof(DqoLossTap), sizeof(DqoObjectGate),
                                 sizeof(DqoAdamTensor), sizeof(DqoRastParamInputs), sizeof(DqoRastParamGrads), 0 /* 13: unused */,
-                                sizeof(DqoLifecycle), sizeof(DqoGrowthSample), 0 /* 16: unused */, sizeof(DqoWindowBank)};
+                                sizeof(DqoLifecycle), sizeof(DqoGrowthSample), 0 /* 16: unused */, sizeof(DqoWindowBank), sizeof(DqoTrajRepose),
+                                sizeof(DqoReposeTarget)};
     return (which >= 0 && which < (int32_t)(sizeof(sz) / sizeof(sz[0]))) ? sz[which] : 0;
 }
 DQO_API const char* dqo_last_error(void) { return g_err; }

@@ -7,16 +7,8 @@
 //     pose[i]      relative mode, i > 0: pose[i-1] @ double(rel), entry (r, c) = ((a_r0 b_0c + a_r1 b_1c) + a_r2 b_2c) + a_r3 b_3c
 //                  (tracker.py:324, numpy's float64 @ of a float32 matrix); i == 0: the initial pose (identity without one; :318);
 //                  absolute mode: the given world pose (:313, :322)
-//     w2c          the inverse of the AFFINE pose by the cofactors of its 3x3 block R (cameras.py:166 calls np.linalg.inv, and R is
-//                  orthonormal only to float32, so not the transpose):
-//                      c00 = r11 r22 - r12 r21   c01 = r12 r20 - r10 r22   c02 = r10 r21 - r11 r20
-//                      c10 = r02 r21 - r01 r22   c11 = r00 r22 - r02 r20   c12 = r01 r20 - r00 r21
-//                      c20 = r01 r12 - r02 r11   c21 = r02 r10 - r00 r12   c22 = r00 r11 - r01 r10
-//                      det = (r00 c00 + r01 c01) + r02 c02;   W[a][b] = c[b][a] / det;   T[a] = -((W[a][0] t0 + W[a][1] t1) + W[a][2] t2)
-//     camera       c2w = float(pose[i]); viewmatrix = float(w2c transposed) (cameras.py:174-178); projmatrix = float(w2c transposed @
-//                  double(projection)), entry = ((a0 b0 + a1 b1) + a2 b2) + a3 b3 in double, rounded once (:179-183 form the product
-//                  in float32 from the rounded viewmatrix, which lands up to 1.25 ulp from the double product; this is within half an
-//                  ulp of it); campos = float(pose[i]'s translation)
+//     w2c, camera  dqo_traj_camera.h's statements (shared with traj_repose_kernel of map_repose.hip): the cofactor inverse of the affine
+//                  pose; c2w, viewmatrix, projmatrix, campos rounded once each from the doubles
 //     keyframe     on the rows i == 0 || (i + 1) % gaussian_update_frame == 0, with Wk, Tk / Wc, Tc the w2c of the last keyframe row / of
 //                  this row (mapper.py:749-757, SLAM/utils.py:42-54): d_j = (Wk[0][j] Wc[0][j] + Wk[1][j] Wc[1][j]) + Wk[2][j] Wc[2][j],
 //                  cos = (((d_0 + d_1) + d_2) - 1) / 2 NOT clamped, theta = acos(cos) * (180 / pi), e = Tk - Tc,
@@ -28,27 +20,13 @@
 // eval_ate_kernel (dqo_eval_ate) — the whole ATE curve in one launch: one block per prefix, three passes over its points in double,
 // Horn's quaternion for the rotation.  Lanes by butterfly, the four waves in order, no atomics: a curve is the same bytes on every run.
 #include "dqo_common.h"
+#include "dqo_traj_camera.h"
 
 namespace {
 
 constexpr int TRAJ_THREADS = 256;
 
 // ---- dqo_traj_append ------------------------------------------------------------------------------------------------------------
-
-// w2c (W 3x3 row-major, T 3) of the affine pose P (4x4 row-major) by the cofactors of its 3x3 block (the head comment's statements)
-__device__ __forceinline__ void traj_invert_affine(const double* P, double* W, double* T) {
-#pragma clang fp contract(off)
-    const double r00 = P[0], r01 = P[1], r02 = P[2], r10 = P[4], r11 = P[5], r12 = P[6], r20 = P[8], r21 = P[9], r22 = P[10];
-    const double c00 = r11 * r22 - r12 * r21, c01 = r12 * r20 - r10 * r22, c02 = r10 * r21 - r11 * r20;
-    const double c10 = r02 * r21 - r01 * r22, c11 = r00 * r22 - r02 * r20, c12 = r01 * r20 - r00 * r21;
-    const double c20 = r01 * r12 - r02 * r11, c21 = r02 * r10 - r00 * r12, c22 = r00 * r11 - r01 * r10;
-    const double det = (r00 * c00 + r01 * c01) + r02 * c02;
-    W[0] = c00 / det, W[1] = c10 / det, W[2] = c20 / det;
-    W[3] = c01 / det, W[4] = c11 / det, W[5] = c21 / det;
-    W[6] = c02 / det, W[7] = c12 / det, W[8] = c22 / det;
-    const double t0 = P[3], t1 = P[7], t2 = P[11];
-    for (int a = 0; a < 3; a++) T[a] = -((W[3 * a] * t0 + W[3 * a + 1] * t1) + W[3 * a + 2] * t2);
-}
 
 __global__ void traj_append_kernel(int cap, double* __restrict__ pose, double* __restrict__ pose_gt, int32_t* __restrict__ flags,
                                    double* __restrict__ kf_metric, int32_t* __restrict__ header, const float* __restrict__ rel,
@@ -82,28 +60,7 @@ __global__ void traj_append_kernel(int cap, double* __restrict__ pose, double* _
 
     double W[9], T[3];
     traj_invert_affine(P, W, T);
-    if (c2w)
-        for (int k = 0; k < 16; k++) c2w[k] = (float)P[k];
-    if (campos) campos[0] = (float)P[3], campos[1] = (float)P[7], campos[2] = (float)P[11];
-    if (viewmatrix || projmatrix) {
-        double V[16];  // w2c transposed: the reference's world_view_transform, still in double
-        for (int a = 0; a < 3; a++) {
-            for (int b = 0; b < 3; b++) V[4 * b + a] = W[3 * a + b];
-            V[12 + a] = T[a];
-            V[4 * a + 3] = 0.0;
-        }
-        V[15] = 1.0;
-        if (viewmatrix)
-            for (int k = 0; k < 16; k++) viewmatrix[k] = (float)V[k];
-        if (projmatrix) {
-            double Q[16];
-            for (int k = 0; k < 16; k++) Q[k] = (double)projection[k];
-            for (int r = 0; r < 4; r++)
-                for (int c = 0; c < 4; c++)
-                    projmatrix[4 * r + c] =
-                        (float)(((V[4 * r] * Q[c] + V[4 * r + 1] * Q[4 + c]) + V[4 * r + 2] * Q[8 + c]) + V[4 * r + 3] * Q[12 + c]);
-        }
-    }
+    traj_store_camera(P, W, T, projection, c2w, nullptr, viewmatrix, projmatrix, campos);
 
     // check_keyframe on the rows where the mapper calls it
     int flag = 0;

@@ -184,6 +184,7 @@ class _KeyframeBank:
         self.K_cap, self.H, self.W, self.gate, self.device = int(K_cap), H, W, bool(gate), device
         self.scalars = st  # the intrinsics every slot shares: captured kernel arguments
         self.filled = [False] * self.K_cap
+        self.rows = [None] * self.K_cap  # the trajectory row a slot's camera follows (bank_set(row=...)); None: not bound
         self.camera = torch.zeros((K_cap, 40), **f)
         self.gt_color, self.gt_depth = torch.empty((K_cap, 3, H, W), **f), torch.empty((K_cap, 1, H, W), **f)
         self.render_mask = torch.zeros((K_cap, H, W), dtype=torch.uint8, device=device)
@@ -593,6 +594,9 @@ class FusedMapper(MapOperators):
 
     def _drop_graphs(self):
         self._g, self._frames, self._mixed = None, [], {}
+        # update_poses: window frame -> the trajectory row its camera follows (set_frame(row=...)), and the target table built from the
+        # bound rows (None: build it; every capture and every binding drops it, since the addresses can change)
+        self._frame_rows, self._repose_table = {}, None
 
     def _row_count_changed(self):
         """After P changed: what is sized by P is made anew (the one place the activations and attach_partial are allocated), what holds
@@ -1008,6 +1012,7 @@ class FusedMapper(MapOperators):
         the scheduled keyframe into this graph's input buffers — and whose probe() sizes the capacities over all its keyframes; None,
         the default: no such launch."""
         dev = self.device
+        self._repose_table = None  # (update_poses' targets are the graphs' camera tensors: this capture makes new ones)
         st = self._settings_or_own(settings)
         # (the graph's own copies: set_frame rewrites them in place)
         st = st._replace(bg=st.bg.clone(), viewmatrix=st.viewmatrix.clone(), projmatrix=st.projmatrix.clone(), campos=st.campos.clone())
@@ -1221,7 +1226,8 @@ class FusedMapper(MapOperators):
     def capture_window(self, frames, **kw):
         """One captured graph per frame of a mapping call's frame set — the five `processed_frames` of local_optimize (mapper.py:549-555)
         or the selected keyframes of global_optimization (:1159-1180).  frames: list of dict(gt_color, gt_depth, render_mask=None,
-        tile_mask=None, settings=None, pixel_object=None); kw: capture()'s other arguments.  Each graph owns its context buffers and
+        tile_mask=None, settings=None, pixel_object=None, row=None); row: the trajectory row the frame's camera follows under
+        update_poses (set_frame's argument); kw: capture()'s other arguments.  Each graph owns its context buffers and
         capacities (a frame's tail clears ITS counters for ITS next replay: DqoRastCtx.frame_prezeroed holds per frame); they share the
         map, the optimiser state and the device step count, so replay(k) in any order is the reference's loop with its per-iteration
         frame choice = one graph launch.  The eager iterations the captures run are undone (parameters, moments, confidence, step
@@ -1237,7 +1243,76 @@ class FusedMapper(MapOperators):
                          pixel_object=fr.get("pixel_object"), frame=k, **kw)
             torch.cuda.synchronize()
         self._restore_state(snap)
+        for k, fr in enumerate(frames):
+            if fr.get("row") is not None:
+                self._bind_row(self._frame_rows, k, fr["row"])
         return self
+
+    def _bind_row(self, table, key, row):
+        """update_poses' binding of a window frame / bank slot to a trajectory row (row < 0: unbound)."""
+        row = int(row)
+        if row < 0:
+            if isinstance(table, dict):
+                table.pop(key, None)
+            else:
+                table[key] = None
+        else:
+            table[key] = row
+        self._repose_table = None
+
+    def _repose_targets(self):
+        """update_poses' target table from the bound rows: int64 [T,6] on the device (DqoReposeTarget: row, c2w,
+        w2c, viewmatrix, projmatrix, campos), one entry per graph that renders a bound window frame's camera (its own settings tensors)
+        and one per bound bank slot (its camera row: viewmatrix at float 3, projmatrix at 19, campos at 35 of the 40).  Built once and
+        kept until a binding changes or a graph is captured again."""
+        if self._repose_table is None:
+            entries, held = [], []
+            for k, row in sorted(self._frame_rows.items()):
+                graphs = ([self._frames[k]] if k < len(self._frames) and self._frames[k] is not None else []) + \
+                         [g for (a, b), g in self._mixed.items() if a == k]
+                for g in graphs:
+                    st = g.settings
+                    for name in ("viewmatrix", "projmatrix", "campos"):
+                        if getattr(st, name).data_ptr() == getattr(self.settings, name).data_ptr():
+                            raise ValueError(f"FusedMapper.update_poses: frame {k}'s {name} is the mapper's default camera tensor; "
+                                             "a correction would move every default-camera render with it")
+                    entries.append((row, 0, 0, st.viewmatrix.data_ptr(), st.projmatrix.data_ptr(), st.campos.data_ptr()))
+                    held.append(st)
+            if self._bank is not None:
+                base = self._bank.camera.data_ptr()
+                at = {name: a for name, a, b in _CAMERA_ROW}
+                for slot, row in enumerate(self._bank.rows):
+                    if row is not None:
+                        p = base + 160 * slot
+                        entries.append((row, 0, 0, p + 4 * at["viewmatrix"], p + 4 * at["projmatrix"], p + 4 * at["campos"]))
+            seen = {}
+            for e in entries:
+                for addr in e[3:]:
+                    if seen.setdefault(addr, e[0]) != e[0]:
+                        raise ValueError(f"FusedMapper.update_poses: one camera tensor is bound to trajectory rows {seen[addr]} and {e[0]}")
+            table = torch.tensor(np.asarray(entries, np.int64).reshape(-1, 6), device=self.device)
+            self._repose_table = (table, held)
+        return self._repose_table[0]
+
+    def update_poses(self, traj, new_poses=None):
+        """Mapping.update_poses (SLAM/multiprocess/mapper.py:256-263; slam.py:126-127 before every mapping(), :181-182 before the final
+        global_optimization) for the trajectory, the window and the bank in ONE launch (dqo_traj_repose, csrc/map_repose.hip): traj (a
+        dqo_icp.Trajectory made with a projection) takes new_poses as Trajectory.update_poses does, and every window frame and bank
+        slot bound to a trajectory row — set_frame(k, row=...), bank_set(slot, row=...), the "row" key of capture_window's and
+        capture_bank's frame dicts — gets the viewmatrix / projmatrix / campos of its row's corrected pose, written where the captured
+        graphs read them: a window graph's own settings tensors in place, a bank slot's camera row, whose next select copies it again
+        (the launch sets the bank's force word).  new_poses None: the cameras are formed again from the stored poses (a new binding).
+        Nothing is read back and the host does no work per keyframe; returns the device counts (int32 [4]: pose rows rewritten,
+        targets written — the trajectory's own camera among them — targets skipped for a row outside the trajectory, 0) unread.
+        ValueError before the launch: a bound frame whose camera tensors are the mapper's default camera's, or one camera tensor bound
+        to two different rows.  Works on a sharded mapper: a camera needs nothing of the map.  bg, the images, the masks and the
+        capacities stay: a frame that outgrows its capacities under the new view is run_window's / run_bank's overflow as ever.  A mixed
+        graph (k, m) that run_window captures on first use AFTER a correction starts from the camera capture_window was given, as it
+        does after set_frame: call update_poses(traj) once more when such a graph has been added."""
+        if traj.projection is None:
+            raise ValueError("FusedMapper.update_poses: the trajectory was made without a projection, so there is no projmatrix")
+        table = self._repose_targets()
+        return traj.update_poses(new_poses, targets=table, bank_state=None if self._bank is None else self._bank.state)
 
     @staticmethod
     def window_schedule(n_iters, n_frames, rng, final=False, random_keyframes=False, global_opt=False):
@@ -1353,7 +1428,8 @@ class FusedMapper(MapOperators):
         for k, fr in enumerate(frames):
             self.bank_set(k, gt_color=fr["gt_color"], gt_depth=fr["gt_depth"], render_mask=fr["render_mask"], tile_mask=fr.get("tile_mask"),
                           settings=fr.get("settings", self.settings),
-                          pixel_object=(self.pixel_object if fr.get("pixel_object") is None else fr["pixel_object"]) if bank.gate else None)
+                          pixel_object=(self.pixel_object if fr.get("pixel_object") is None else fr["pixel_object"]) if bank.gate else None,
+                          row=fr.get("row"))
         self._capture_bank_graph(bank.capacity_margin)
         return self
 
@@ -1375,11 +1451,12 @@ class FusedMapper(MapOperators):
         self._g = cur if cur is not None else bank.graph
 
     @torch.no_grad()
-    def bank_set(self, slot, gt_color=None, gt_depth=None, render_mask=None, tile_mask=None, settings=None, pixel_object=None):
+    def bank_set(self, slot, gt_color=None, gt_depth=None, render_mask=None, tile_mask=None, settings=None, pixel_object=None, row=None):
         """New inputs for slot `slot` of the keyframe bank, written in place, with set_frame's rules: same shapes, and the scalar
         intrinsics are captured kernel arguments that must not change.  A slot that was never filled needs gt_color, gt_depth,
         render_mask and settings; a new keyframe in a spare slot keeps the captured graph (if it outgrows the capacities, run_bank
-        captures again as for any overflow).  The next select copies both groups whatever it copied last (force)."""
+        captures again as for any overflow).  The next select copies both groups whatever it copied last (force).  row: the trajectory
+        row the slot's camera follows under update_poses (negative: none any more; None: as it was)."""
         bank = self._require_bank("bank_set")
         slot = int(slot)
         if not 0 <= slot < bank.K_cap:
@@ -1409,6 +1486,8 @@ class FusedMapper(MapOperators):
             bank.pixel_object[slot].copy_(torch.as_tensor(pixel_object).to(dev, torch.int32).reshape(H, W))
             bank.tile_objects[slot].copy_(tile_object_sets(bank.pixel_object[slot]))
         bank.filled[slot] = True
+        if row is not None:
+            self._bind_row(bank.rows, slot, row)
         bank.word("force").fill_(1)
         return self
 
@@ -1480,13 +1559,16 @@ class FusedMapper(MapOperators):
         return lost_all
 
     @torch.no_grad()
-    def set_frame(self, frame, gt_color=None, gt_depth=None, render_mask=None, tile_mask=None, settings=None, pixel_object=None):
+    def set_frame(self, frame, gt_color=None, gt_depth=None, render_mask=None, tile_mask=None, settings=None, pixel_object=None, row=None):
         """New inputs for a captured frame WITHOUT a new capture: the next mapping call's window keeps four of its five frames and every
         call re-evaluates the masks (mapper.py:549-555).  Everything a graph reads per frame lives in device buffers the capture fixed:
         the camera's matrices / position / background, the ground-truth images, the render mask, the tile mask, the owner map — they
         are overwritten in place (same shapes; a frame captured without a render mask cannot get one later, and the scalar intrinsics
         — image size, tan(fov), principal point, thresholds — are kernel arguments: they must not change).  The captured capacities
-        were sized on the old view: check graph_overflowed(frame) / use run_window, which re-captures a frame that outgrew them."""
+        were sized on the old view: check graph_overflowed(frame) / use run_window, which re-captures a frame that outgrew them.
+        row: the trajectory row the frame's camera follows under update_poses (negative: none any more; None: as it was)."""
+        if row is not None:
+            self._bind_row(self._frame_rows, frame, row)
         cams = [self._frames[frame]] + [g for (k, m), g in self._mixed.items() if k == frame]    # graphs that render frame's camera / target
         masks = [self._frames[frame]] + [g for (k, m), g in self._mixed.items() if m == frame]   # graphs that use frame's masks
         done = set()

@@ -13,7 +13,9 @@ host synchronisation is predict_pose's read of the result.
 
 `Trajectory` takes the pose from there (csrc/map_traj.hip): the world pose, the frame's camera tensors, the world-frame vertex / normal
 maps, the keyframe test and the ATE curve (Tracker.tracking, SLAM/multiprocess/tracker.py:307-339; check_keyframe, mapper.py:734-773;
-eval_total_ate, tracker.py:341-346) from predict_pose_async's device tensors, with no host read per frame.
+eval_total_ate, tracker.py:341-346) from predict_pose_async's device tensors, with no host read per frame.  Poses that come back
+corrected (Mapping.update_poses, SLAM/multiprocess/mapper.py:256-263; pose_es.npy) go through `Trajectory.update_poses` and
+`cameras_from_poses` (csrc/map_repose.hip): the store and every camera that follows it in one launch.
 """
 import ctypes
 import math
@@ -356,6 +358,76 @@ def world_maps(vertex_c, normal_c, c2w, out=None):
     return vw, nw
 
 
+REPOSE_OUTPUTS = (("c2w", (4, 4)), ("w2c", (4, 4)), ("viewmatrix", (4, 4)), ("projmatrix", (4, 4)), ("campos", (3,)))
+
+
+def repose_targets(rows, device, c2w=None, w2c=None, viewmatrix=None, projmatrix=None, campos=None):
+    """A target table of dqo_traj_repose (DqoReposeTarget, include/dqo_raster.h): int64 [T,6] on the device, entry t = (rows[t], the
+    address of entry t of each destination; 0 for a destination that is None).  rows: T trajectory rows, a sequence or an integer GPU
+    tensor (then nothing is copied from the host); a destination: a contiguous float32 GPU tensor [T,4,4] ([T,3] for campos; without the
+    leading T when T == 1).  The destinations must outlive every launch that reads the table."""
+    if torch.is_tensor(rows):
+        r = rows.detach().to(device=device, dtype=torch.int64).reshape(-1)
+    else:
+        r = torch.tensor([int(x) for x in rows], dtype=torch.int64, device=device)
+    T = r.numel()
+    cols = [r]
+    step = None
+    for (name, shape), t in zip(REPOSE_OUTPUTS, (c2w, w2c, viewmatrix, projmatrix, campos)):
+        if t is None:
+            cols.append(torch.zeros_like(r))
+            continue
+        n = int(np.prod(shape))
+        N.require_gpu_op(t)
+        if not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == T * n):
+            raise RuntimeError(f"repose_targets: {name} must be a contiguous float32 tensor of {T} x {shape}")
+        if step is None:
+            step = torch.arange(T, dtype=torch.int64, device=device)
+        cols.append(step * (4 * n) + t.data_ptr())
+    return torch.stack(cols, 1).contiguous()
+
+
+def _repose(pose, cap, header, new_pose, table, projection, has_projmatrix, bank_state, stats):
+    """The dqo_traj_repose launch on the current stream (the caller holds the operands alive)."""
+    args = N.DqoTrajRepose(cap=int(cap), n_new=0 if new_pose is None else int(new_pose.shape[0]), T=0 if table is None else int(table.shape[0]),
+                           flags=N.REPOSE_HAS_PROJMATRIX if has_projmatrix else 0, pose=pose.data_ptr(), header=header.data_ptr(),
+                           new_pose=N.ptr(new_pose), targets=N.ptr(table), projection=N.ptr(projection), bank_state=N.ptr(bank_state),
+                           stats=N.ptr(stats))
+    N.check(N.lib().dqo_traj_repose(ctypes.byref(args), N.current_stream()))
+
+
+def cameras_from_poses(poses, projection=None, rows=None, out=None):
+    """Camera.updatePose for a whole pose stack in ONE launch (dqo_traj_repose over the stack itself, no trajectory involved): what
+    metric.py:181, make_mesh.py:199 and metric_obj.py:212 run per dataset frame (test_frame.updatePose(pose_es[cam_id])).
+    poses: [N,4,4] GPU tensor of world poses (c2w; float64 contiguous is read in place, anything else is converted on the device);
+    projection: the camera's projection_matrix (float32 [4,4], transposed as the reference keeps it) — without one no projmatrix is
+    formed; rows: the T stack rows to form cameras for (a sequence or an integer GPU tensor; default all N, in order); out: a dict of
+    contiguous float32 GPU tensors to write into (default: new ones).  Returns dict(c2w [T,4,4], w2c [T,4,4], viewmatrix [T,4,4],
+    projmatrix [T,4,4] (only with a projection), campos [T,3], stats int32 [4]): Trajectory.append's camera bits for the same pose; `w2c`
+    (row-major) is directly the view dqo_eval.mesh_cull and mesh_render_depth take, `viewmatrix` its transpose (world_view_transform).
+    A row outside [0, N) leaves its entry as it was (new tensors: zero) and is counted in stats[2]."""
+    N.require_gpu_op(poses, projection)
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4) or poses.shape[0] < 1:
+        raise RuntimeError("cameras_from_poses: an [N,4,4] stack of at least one pose expected")
+    dev, n = poses.device, int(poses.shape[0])
+    p = poses.detach().to(torch.float64).contiguous()
+    proj = None if projection is None else projection.detach().to(device=dev, dtype=torch.float32).reshape(4, 4).contiguous()
+    with torch.cuda.device(dev):
+        r = torch.arange(n, dtype=torch.int64, device=dev) if rows is None else rows
+        T = int(r.numel()) if torch.is_tensor(r) else len(r)
+        res = {} if out is None else dict(out)
+        for name, shape in REPOSE_OUTPUTS:
+            if name == "projmatrix" and proj is None:
+                res.pop(name, None)
+            elif name not in res:
+                res[name] = torch.zeros((T,) + shape, dtype=torch.float32, device=dev)
+        res["stats"] = torch.zeros((4,), dtype=torch.int32, device=dev)
+        table = repose_targets(r, dev, **{name: res.get(name) for name, _ in REPOSE_OUTPUTS})
+        header = torch.full((4,), n, dtype=torch.int32, device=dev)  # (only the count word is read)
+        _repose(p, n, header, None, table, proj, proj is not None, None, res["stats"])
+    return res
+
+
 class Trajectory:
     """The trajectory on the device: what Tracker.tracking does between the tracker's answer and the mapper's input
     (SLAM/multiprocess/tracker.py:307-339), the mapper's keyframe test (SLAM/multiprocess/mapper.py:734-773) and the ATE curve
@@ -404,6 +476,13 @@ class Trajectory:
         self._n = 0
         self._ate_ws = None
         self._held = ()  # the last append's converted operands, alive while its launch (or a graph that captured it) may read them
+        # update_poses: the device counts of the last call, the table entry of the trajectory's own camera tensors (made here: its
+        # destinations never move, and a captured call must not copy from the host), that entry joined with the caller's table (cached
+        # per table object), and what the last launch reads
+        self.repose_stats = torch.zeros((4,), dtype=torch.int32, device=device)
+        self._own_targets = repose_targets([-1], device, c2w=self.c2w, viewmatrix=self.viewmatrix, campos=self.campos,
+                                           projmatrix=None if self.projection is None else self.projmatrix)
+        self._joined_targets, self._held_repose = (None, None), ()
 
     def __len__(self):
         """The host's mirror of the row count (the device's is header[0]): every append() counts one, up to the capacity.  Replays of a
@@ -435,6 +514,44 @@ class Trajectory:
                                             self.keyframe_trans_thes, N.current_stream()))
         self.advance()
         return self
+
+    def update_poses(self, new_poses, targets=None, bank_state=None):
+        """Mapping.update_poses / Tracker.save_traj's pose_es replacement (SLAM/multiprocess/mapper.py:256-263, tracker.py:399-401) in ONE
+        launch (dqo_traj_repose, csrc/map_repose.hip), nothing read back: row r of the store takes new_poses[r] for every
+        r < min(len, N) as exact bytes — rows at or beyond N keep their pose, where the reference would raise IndexError — and the
+        trajectory's own current-frame tensors (c2w, viewmatrix, projmatrix, campos) are formed again from row len - 1, so settings() and
+        world_maps() follow.  The next tested append compares against the MOVED pose of the last keyframe, as check_keyframe reads
+        keyframe_list[-1] after update_poses; pose_gt, flags, kf_metric and the header stay (the reference never re-tests a keyframe).
+        new_poses: [N,4,4] GPU tensor, used in place when float64 and contiguous, otherwise converted on the device first and kept alive
+        like append's operands; None: poses unchanged, only the cameras are formed again.  targets: further cameras to form in the same
+        launch, an int64 [T,6] GPU table of (row, c2w, w2c, viewmatrix, projmatrix, campos) — a trajectory row and five float32
+        destination addresses, 0 = skip (repose_targets() builds one; the table is read at the call: pass a NEW tensor when its
+        contents change; a trajectory made without a projection forms no projmatrix, its own or a target's); bank_state: a keyframe bank's state words, whose force word the launch sets (FusedMapper.update_poses passes
+        both).  Returns the device counts, int32 [4], unread: pose rows rewritten, targets written, targets skipped for their row
+        (outside [0, len)), 0.  Capturable: a replay reads new_poses and the tables where they were; the own camera's row is the host
+        mirror's len - 1 at the call, as for append.  The world-frame maps of stored frames are not re-transformed (nor are the
+        reference's)."""
+        N.require_gpu_op(self._pose, new_poses, targets, bank_state)
+        p = None
+        if new_poses is not None:
+            if new_poses.dim() != 3 or tuple(new_poses.shape[1:]) != (4, 4):
+                raise RuntimeError("Trajectory.update_poses: new_poses must be an [N,4,4] stack")
+            p = new_poses.detach().to(torch.float64).contiguous()
+        if targets is not None and not (targets.dtype == torch.int64 and targets.dim() == 2 and targets.shape[1] == 6 and targets.is_contiguous()):
+            raise RuntimeError("Trajectory.update_poses: targets must be a contiguous int64 [T,6] table")
+        own = self._own_targets
+        if targets is None or targets.shape[0] == 0:
+            table = own
+        else:
+            if self._joined_targets[0] is not targets:
+                self._joined_targets = (targets, torch.cat([own, targets]))
+            table = self._joined_targets[1]
+        table[0, 0:1].fill_(self._n - 1)  # (a fill launch: no host copy, capturable)
+        self._held_repose = (p, table)
+        with torch.cuda.device(self.device):
+            _repose(self._pose, self.capacity, self.header, p, table, self.projection, self.projection is not None, bank_state,
+                    self.repose_stats)
+        return self.repose_stats
 
     def poses(self):
         """[len, 4, 4] float64 view of the world poses (pose_es)."""

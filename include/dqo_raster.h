@@ -1728,6 +1728,54 @@ typedef struct DqoWindowBank {
 int dqo_window_bank_arm(int32_t* state, int32_t n, void* hipStream);
 int dqo_window_bank_select(const DqoWindowBank*, void* hipStream);
 
+/* dqo_traj_repose (ABI 5, symbols-only addition) — pose corrections.  Mapping.update_poses (SLAM/multiprocess/mapper.py:256-263; called
+ * by slam.py:126-127 before every mapping() and by :181-182 before the final global_optimization) hands Camera.updatePose
+ * (scene/cameras.py:165-183) the corrected world pose of every processed frame and keyframe; Tracker.save_traj (tracker.py:399-401)
+ * replaces pose_es by the same set; metric.py:181, make_mesh.py:199 and metric_obj.py:212 run updatePose per dataset frame.  ONE launch,
+ * capturable: nothing is read back, no memset, no atomics; the same bytes on every run.  csrc/map_repose.hip lists the statements in
+ * order; tests/repose_oracle.py restates them.
+ *   The store: pose [cap,16] double and header of dqo_traj_append's trajectory.  count = header[DQO_TRAJ_HEADER_COUNT], read on the
+ *     device (clipped to [0, cap]).
+ *   Pose part: new_pose, double [n_new,16] in device memory, indexed by trajectory row (new_poses[frame.uid] of the reference, the
+ *     [N,4,4] stack of pose_es.npy).  pose[r] = new_pose[r] for every r < min(count, n_new, cap), as exact bytes.  Rows at or beyond n_new
+ *     keep their pose (the reference would raise IndexError there).  pose_gt, flags, kf_metric and the header are not touched: the
+ *     reference never re-tests a keyframe.  new_pose == NULL: poses unchanged, only the cameras are re-formed.
+ *   Camera part: `targets`, T entries of DqoReposeTarget in device memory (48 bytes each, 8-byte aligned: an int64 [T,6] table): a
+ *     trajectory row and up to five float32 destinations — c2w [16], w2c [16] (row-major: what dqo_mesh_cull / dqo_mesh_render_depth*
+ *     take as a view), viewmatrix [16], projmatrix [16], campos [3]; a NULL destination skips that one.  Destinations are only
+ *     guaranteed 4-byte aligned (a bank slot's viewmatrix starts at float 3 of a 160-byte camera row): every store is a 4-byte store and
+ *     nothing outside the named extents is written.  A target's source pose is new_pose[row] when new_pose is given and row < n_new,
+ *     otherwise pose[row]: the camera lanes never read a store row that the same launch is writing.  A target with row < 0 or
+ *     row >= count writes nothing and is counted.  One lane per target in blocks of 256, doubles throughout, dqo_traj_append's camera
+ *     statements and bits: c2w = the pose rounded once; w2c = the double inverse of the affine pose (by the cofactors of its 3x3 block)
+ *     rounded once, viewmatrix its transpose; projmatrix = the double w2c transposed @ double(projection), rounded once (projection:
+ *     device float32 [4,4], transposed as the reference keeps it); campos = the pose's translation (it follows the pose, where
+ *     Camera.update keeps the constructor's centre).  Two targets may name one row; two targets must not share a destination.
+ *   Bank state: bank_state non-NULL (a DqoWindowBank's state words): its DQO_WINDOW_BANK_FORCE word is set to 1 by one thread, so the
+ *     next dqo_window_bank_select copies the camera group even when k == prev_k.  Graphs that read their camera tensors in place need
+ *     no flag.  Calls that share a state must be ordered (one stream).
+ *   stats: int32 [4], overwritten (may be NULL): pose rows rewritten, targets written, targets skipped for their row, 0.
+ *   flags: DQO_REPOSE_HAS_PROJMATRIX when any target of the table has a projmatrix destination (the host cannot see a device table).
+ * DQO_ERR_INVALID_ARG before the launch: NULL arguments, cap < 1, a NULL store or header, n_new < 0, T < 0, T > 0 with a NULL table,
+ *   DQO_REPOSE_HAS_PROJMATRIX without a projection (without the flag and without a projection a projmatrix destination is skipped).
+ * Not done: the world-frame maps of stored frames are not re-transformed (the reference's keymap_list keeps its normal_map too). */
+enum { DQO_REPOSE_HAS_PROJMATRIX = 1 };
+typedef struct DqoReposeTarget {
+    int64_t row;
+    float *c2w, *w2c, *viewmatrix, *projmatrix, *campos;
+} DqoReposeTarget;
+typedef struct DqoTrajRepose {
+    int32_t cap, n_new, T, flags;
+    double* pose;
+    const int32_t* header;
+    const double* new_pose;
+    const DqoReposeTarget* targets;
+    const float* projection;
+    int32_t* bank_state;
+    int32_t* stats;
+} DqoTrajRepose;
+int dqo_traj_repose(const DqoTrajRepose*, void* hipStream);
+
 #ifdef __cplusplus
 }
 #endif
