@@ -288,8 +288,8 @@ def ms_ssim(image, gt, out=None, row=0, *, workspace_buffer=None, render_header=
 LPIPS_ROW = ("lpips", "d0", "d1", "d2", "d3", "d4", "unused6", "unused7")
 LPIPS_MIN_SIDE = 31  # every AlexNet map needs a pixel
 LPIPS_NET = ((3, 64, 11, 4, 2), (64, 192, 5, 1, 2), (192, 384, 3, 1, 1), (384, 256, 3, 1, 1), (256, 256, 3, 1, 1))  # Cin, Cout, kernel, stride, pad
-LPIPS_NORMS = {"torchmetrics": 0, "lpips": 1}  # DQO_LPIPS_NORM_*
-_LPIPS_FEATURES_OFFSET = 4608  # DQO_LPIPS_FEATURES_OFFSET
+LPIPS_NORMS = {"torchmetrics": N.CONSTANTS["DQO_LPIPS_NORM_TORCHMETRICS"], "lpips": N.CONSTANTS["DQO_LPIPS_NORM_LPIPS"]}
+_LPIPS_FEATURES_OFFSET = N.CONSTANTS["DQO_LPIPS_FEATURES_OFFSET"]
 
 
 def lpips_sizes(W, H):
@@ -518,7 +518,7 @@ def _nearest(grouped, query, q_rows, ref, r_rows, query_transform, ref_transform
 
 
 DENSIFY_HEADER = ("kept_rows", "N_lo", "N_hi", "n", "M", "threshold_key", "frame", "zero")
-DENSIFY_FRAMES = {"reference": 0, "surfel": 1}
+DENSIFY_FRAMES = {"reference": N.CONSTANTS["DQO_DENSIFY_FRAME_REFERENCE"], "surfel": N.CONSTANTS["DQO_DENSIFY_FRAME_SURFEL"]}
 
 
 def densify_theta(circle_num, seed=0):
@@ -589,7 +589,7 @@ def densify(xyz, scaling_raw, rotation_raw, sigma=1, circle_num=30, levels=5, th
 
 
 MESH_HEADER = ("n", "F", "bad_index_faces", "zero_area_faces", "quantum_exponent", "total_lo", "total_hi", "zero")
-MESH_SCAN_BLOCK = 1024  # faces per block of the table's scan (include/dqo_raster.h: DQO_MESH_SCAN_BLOCK)
+MESH_SCAN_BLOCK = N.CONSTANTS["DQO_MESH_SCAN_BLOCK"]  # faces per block of the table's scan
 
 
 def mesh_sample_workspace(F, count, device):
@@ -954,7 +954,9 @@ class TsdfVolume:
 # ---- the mesh's clean-up (csrc/map_meshops.hip) ------------------------------------------------------------------------------------------
 MESHOPS_HEADER = ("vertices", "faces", "components", "components_kept", "faces_bad_index", "largest_component_faces", "vertices_removed",
                   "faces_removed")
-_MESH_SCOPES = {"positions": 0, "colors": 1, "colours": 1, "all": 2, "both": 2}
+_MESH_SCOPES = {"positions": N.CONSTANTS["DQO_MESH_SMOOTH_POSITIONS"], "colors": N.CONSTANTS["DQO_MESH_SMOOTH_COLOURS"],
+                "colours": N.CONSTANTS["DQO_MESH_SMOOTH_COLOURS"], "all": N.CONSTANTS["DQO_MESH_SMOOTH_BOTH"],
+                "both": N.CONSTANTS["DQO_MESH_SMOOTH_BOTH"]}
 _mesh_outs = {}  # the module's own out meshes and normals, one per (device, capacities)
 
 
@@ -1080,9 +1082,9 @@ def mesh_smooth(mesh, iterations, lam=0.5, mu=None, scope="all", workspace_buffe
     if scope not in _MESH_SCOPES:
         raise RuntimeError(f"dqo_eval.mesh_smooth: scope is 'positions', 'colors' or 'all', got {scope!r}")
     sc = _MESH_SCOPES[scope]
-    if sc == 2 and c is None:
-        sc = 0
-    if sc == 1 and c is None:
+    if sc == _MESH_SCOPES["all"] and c is None:
+        sc = _MESH_SCOPES["positions"]
+    if sc == _MESH_SCOPES["colors"] and c is None:
         raise RuntimeError("dqo_eval.mesh_smooth: scope 'colors' on a mesh without colors")
     ws = _mesh_ws("smooth", workspace_buffer, v.device, cv, cf)
     with torch.cuda.device(v.device):

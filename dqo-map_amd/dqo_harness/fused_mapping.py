@@ -284,7 +284,7 @@ class FusedMapper(MapOperators):
         # DqoAdamStep.step_dev / block_ticket / bias_table.  _expected_step = what step_dev holds while host and device counts agree.
         i32 = dict(dtype=torch.int32, device=device)
         self._step_dev = torch.full((1,), 1, **i32)
-        self._ticket = torch.zeros((16 + 16 * 64,), **i32)  # DQO_TICKET_WORDS
+        self._ticket = torch.zeros((N.TICKET_WORDS,), **i32)
         self._bias = torch.zeros((8,), dtype=torch.float32, device=device)
         self._expected_step, self._unsettled = 1, False
         # DqoAdamStep.block_ticket: the Adam launch advances the device step count itself (False: a one-thread launch behind it does)

@@ -205,14 +205,15 @@ class DqoAdam(torch.optim.Optimizer):
                 by_step.setdefault(key, []).append(
                     N.DqoAdamTensor(p=p.data_ptr(), g=g.data_ptr(), m=st["exp_avg"].data_ptr(), v=st["exp_avg_sq"].data_ptr(), n=p.numel(),
                                     lr=float(group["lr"])))
+        most = N.CONSTANTS["DQO_ADAM_MULTI_MAX"]  # tensors per launch
         for step, ts in by_step.items():
             with torch.cuda.device(dev):
-                for i in range(0, len(ts), 16):
-                    chunk = ts[i:i + 16]
+                for i in range(0, len(ts), most):
+                    chunk = ts[i:i + most]
                     arr = (N.DqoAdamTensor * len(chunk))(*chunk)
                     if self.capturable:
                         N.check(lib.dqo_adam_multi_dev(ctypes.cast(arr, ctypes.c_void_p), len(chunk), N.ptr(self._step_dev),
-                                                       1 if i + 16 >= len(ts) else 0, betas[0], betas[1], eps, N.current_stream()))
+                                                       1 if i + most >= len(ts) else 0, betas[0], betas[1], eps, N.current_stream()))
                     else:
                         N.check(lib.dqo_adam_multi(ctypes.cast(arr, ctypes.c_void_p), len(chunk), step, betas[0], betas[1], eps,
                                                    N.current_stream()))

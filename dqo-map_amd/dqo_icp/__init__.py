@@ -468,7 +468,9 @@ class Trajectory:
         self._pose, self._pose_gt = torch.zeros((capacity, 4, 4), **f64), torch.zeros((capacity, 4, 4), **f64)
         self.flags = torch.zeros((capacity,), dtype=torch.int32, device=device)
         self.kf_metric = torch.zeros((capacity, 2), **f64)
-        self.header = torch.tensor([0, -1, 0, 0], dtype=torch.int32, device=device)  # count, last keyframe row, overflow, unused
+        header = [0] * N.CONSTANTS["DQO_TRAJ_HEADER_WORDS"]  # count, last keyframe row, overflow, unused
+        header[N.CONSTANTS["DQO_TRAJ_HEADER_LAST_KEYFRAME"]] = -1
+        self.header = torch.tensor(header, dtype=torch.int32, device=device)
         self.projection = None if projection is None else projection.detach().to(**f32).reshape(4, 4).contiguous()
         self.init_pose = None if init_pose is None else torch.as_tensor(init_pose).detach().to(**f64).reshape(4, 4).contiguous()
         self.c2w, self.viewmatrix, self.projmatrix = torch.eye(4, **f32), torch.eye(4, **f32), torch.zeros((4, 4), **f32)
@@ -580,7 +582,7 @@ class Trajectory:
 
     def is_keyframe(self):
         """check_keyframe's return value for the last row: the one 4-byte read, where the caller has to branch."""
-        return bool(int(self.keyframe().cpu()) & 2)
+        return bool(int(self.keyframe().cpu()) & N.CONSTANTS["DQO_TRAJ_KEYFRAME"])
 
     def ate(self, out=None):
         """The ATE curve so far, float64 [len] on the device (dqo_eval.eval_ate of the stored poses against the stored ground truth)."""
@@ -591,7 +593,7 @@ class Trajectory:
 
     def overflowed(self):
         """True when an append found the store full (a host read)."""
-        return bool(int(self.header[2].cpu()))
+        return bool(int(self.header[N.CONSTANTS["DQO_TRAJ_HEADER_OVERFLOW"]].cpu()))
 
     def save(self, save_path):
         """pose_es.npy / pose_gt.npy under save_path/save_traj as Tracker.save_traj writes them (tracker.py:397, 403-409): the only host

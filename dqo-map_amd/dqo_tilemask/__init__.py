@@ -114,7 +114,7 @@ def evaluate_render_range(T_map, render=None, gt=None, global_opt=False, sample_
 
 
 MODE_LOCAL, MODE_ERROR, MODE_FINAL = 0, 1, 2  # dqo_window_masks: the three branches of mapper.py:945-985
-_SUMS_OFFSET = 4352  # DQO_WINDOW_MASKS_SUMS_OFFSET
+_SUMS_OFFSET = N.CONSTANTS["DQO_WINDOW_MASKS_SUMS_OFFSET"]
 
 
 def window_masks_workspace(h, w, device):

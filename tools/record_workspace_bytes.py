@@ -19,8 +19,12 @@ import ctypes
 import itertools
 import json
 import os
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "dqo-map_amd"))
+from _dqo_native import PROTOTYPES  # noqa: E402
+
 DEFAULT_LIB = os.path.join(ROOT, "dqo-map_amd", "lib", "libdqoraster.so")
 DEFAULT_OUT = os.path.join(ROOT, "tests", "workspace_bytes_parent.json")
 
@@ -38,40 +42,37 @@ IMAGES_BAD = [(0, 1), (1, 0), (-3, 5), (46341, 46341)]
 POINTS = [1, 255, 256, 4097, (1 << 25) - 1]
 POINTS_BAD = [-1, 1 << 25]
 
-I32, I64 = ctypes.c_int32, ctypes.c_int64
-
-
 def _queries():
-    """(export, argument types, argument tuples)"""
+    """(export, argument tuples)"""
     mesh = list(itertools.product(MESH_CAPS, MESH_CAPS)) + MESH_BAD
     for name in ("components", "smooth", "normals", "simplify", "cull"):
-        yield f"dqo_mesh_{name}_workspace_bytes", (I32, I32), mesh
+        yield f"dqo_mesh_{name}_workspace_bytes", mesh
     sample = list(itertools.product(SAMPLE_F, SAMPLE_COUNT)) + SAMPLE_BAD
-    yield "dqo_mesh_sample_workspace_bytes", (I32, I32), sample
-    yield "dqo_mesh_sample_counted_workspace_bytes", (I32, I32), sample
-    yield "dqo_tsdf_workspace_bytes", (I32, I32, I32), TSDF_DIMS + TSDF_BAD
+    yield "dqo_mesh_sample_workspace_bytes", sample
+    yield "dqo_mesh_sample_counted_workspace_bytes", sample
+    yield "dqo_tsdf_workspace_bytes", TSDF_DIMS + TSDF_BAD
     images = IMAGES + IMAGES_LPIPS + IMAGES_MSSSIM + IMAGES_BAD
     for name in ("dqo_map_ssim_workspace_bytes", "dqo_growth_sample_workspace_bytes", "dqo_eval_picture_workspace_bytes",
                  "dqo_window_masks_workspace_bytes", "dqo_eval_ms_ssim_workspace_bytes", "dqo_eval_lpips_workspace_bytes",
                  "dqo_track_preprocess_workspace_bytes"):
-        yield name, (I32, I32), images
-    yield "dqo_rast_image_bytes", (I32, I32), IMAGES + IMAGES_LPIPS + IMAGES_MSSSIM  # (no argument check of its own)
+        yield name, images
+    yield "dqo_rast_image_bytes", IMAGES + IMAGES_LPIPS + IMAGES_MSSSIM  # (no argument check of its own)
     points = POINTS + POINTS_BAD
     for name in ("dqo_knn3_workspace_bytes", "dqo_prune_workspace_bytes", "dqo_map_lifecycle_workspace_bytes", "dqo_map_pack_workspace_bytes",
                  "dqo_map_attach_workspace_bytes", "dqo_eval_ate_workspace_bytes"):
-        yield name, (I32,), [(n,) for n in [0] + points]
+        yield name, [(n,) for n in [0] + points]
     pairs = list(itertools.product([0] + POINTS, [0] + POINTS)) + [(-1, 1), (1, 1 << 25)]
     for name in ("dqo_knn3_query_workspace_bytes", "dqo_nn1_workspace_bytes", "dqo_nn1_grouped_workspace_bytes", "dqo_eval_pcd_workspace_bytes",
                  "dqo_eval_pcd_grouped_workspace_bytes"):
-        yield name, (I32, I32), pairs
-    yield "dqo_rast_geom_bytes", (I32, I32, I32), [(n, 1200, 680) for n in [0] + points]
+        yield name, pairs
+    yield "dqo_rast_geom_bytes", [(n, 1200, 680) for n in [0] + points]
     caps = [0, 1, 255, 256, 4097, 1 << 22, -1]
-    yield "dqo_rast_binning_bytes", (I64,), [(c,) for c in caps]
-    yield "dqo_rast_backward_workspace_bytes", (I64,), [(c,) for c in caps]
-    yield "dqo_rast_binning_bytes_bucketed", (I64, I32, I32, I32), [(c, w, h, b) for c in (0, 4097) for w, h in IMAGES for b in (0, 64, 1000)]
-    yield "dqo_surfel_densify_workspace_bytes", (I32, I32, I32, I32), [(n, c, l, s) for n in [0] + points for c, l, s in ((8, 1, 1), (12, 3, 2), (0, 1, 1))]
+    yield "dqo_rast_binning_bytes", [(c,) for c in caps]
+    yield "dqo_rast_backward_workspace_bytes", [(c,) for c in caps]
+    yield "dqo_rast_binning_bytes_bucketed", [(c, w, h, b) for c in (0, 4097) for w, h in IMAGES for b in (0, 64, 1000)]
+    yield "dqo_surfel_densify_workspace_bytes", [(n, c, l, s) for n in [0] + points for c, l, s in ((8, 1, 1), (12, 3, 2), (0, 1, 1))]
     for name in ("dqo_icp_workspace_bytes", "dqo_map_loss_workspace_bytes", "dqo_track_pyramid_workspace_bytes", "dqo_track_p2p_workspace_bytes"):
-        yield name, (), [()]
+        yield name, [()]
 
 
 STACKS = [(n, w, h) for n in (1, 2, 33, 100) for w, h in IMAGES]  # (n_views, W, H)
@@ -79,9 +80,9 @@ STACKS_BAD = [(0, 8, 8), (65536, 8, 8), (1, 0, 8), (1, 8, -1), (1, 1 << 24, 1 <<
 
 
 def _queries_since():
-    """the size queries added since the parent table was recorded: (export, argument types, argument tuples)"""
-    yield "dqo_mesh_render_depth_workspace_bytes", (I32, I32, I32), STACKS + STACKS_BAD
-    yield "dqo_eval_depth_l1_workspace_bytes", (I32, I32, I32), STACKS + STACKS_BAD
+    """the size queries added since the parent table was recorded: (export, argument tuples)"""
+    yield "dqo_mesh_render_depth_workspace_bytes", STACKS + STACKS_BAD
+    yield "dqo_eval_depth_l1_workspace_bytes", STACKS + STACKS_BAD
 
 
 def key(name, args):
@@ -92,9 +93,9 @@ def table(lib_path=DEFAULT_LIB, queries=_queries):
     """{"export(arguments)": bytes} over the grid, from the library at lib_path"""
     lib = ctypes.CDLL(lib_path)
     out = {}
-    for name, types, rows in queries():
+    for name, rows in queries():
         fn = getattr(lib, name)
-        fn.argtypes, fn.restype = list(types), ctypes.c_size_t
+        fn.restype, fn.argtypes = PROTOTYPES[name]  # (the binding's, read from the header)
         for args in rows:
             out[key(name, args)] = int(fn(*args))
     return out
@@ -112,12 +113,12 @@ def _declared(header_path):
 
 def exports(header_path=os.path.join(ROOT, "include", "dqo_raster.h")):
     """the size queries the public header declares, less those of the second grid: the first grid must name every one of them"""
-    return sorted(_declared(header_path) - {name for name, _, _ in _queries_since()})
+    return sorted(_declared(header_path) - {name for name, _ in _queries_since()})
 
 
 def exports_since(header_path=os.path.join(ROOT, "include", "dqo_raster.h")):
     """the size queries of the second grid that the public header declares"""
-    return sorted(_declared(header_path) & {name for name, _, _ in _queries_since()})
+    return sorted(_declared(header_path) & {name for name, _ in _queries_since()})
 
 
 if __name__ == "__main__":
