@@ -582,3 +582,10 @@ bool dqo_nn1_size_ok(int32_t n);
 size_t dqo_nn1_ws_bytes(int Q, int R);
 int dqo_launch_nn1(int Q, const float* q_xyz, DqoNn1Rows q_rows, int R, const float* r_xyz, DqoNn1Rows r_rows, const float* q_xform,
                    const float* r_xform, float* dist2, int32_t* idx, float2* by_rank, void* ws, hipStream_t s);
+// the nearest face of a mesh operand for every query (knn.hip: dqo_mesh_nearest), which dqo_eval_pcd_surface (map_eval.hip) runs for a side
+// that has a mesh; header: int32 [8], cleared by the first launch
+bool dqo_mesh_nearest_size_ok(int32_t Q, int32_t cap_v, int32_t cap_f);
+size_t dqo_mesh_nearest_ws_bytes(int Q, int cap_v, int cap_f);
+int dqo_launch_mesh_nearest(int Q, const float* q_xyz, const uint8_t* q_keep, const float* q_xform, const float* vertices, const int32_t* faces,
+                            const int32_t* counts, int cap_v, int cap_f, const float* mesh_xform, float* dist2, int32_t* face, float* closest,
+                            int32_t* header, void* ws, hipStream_t s);

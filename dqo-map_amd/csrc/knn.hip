@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "dqo_common.h"
+#include "dqo_mesh_operand.h"
 
 namespace {
 
@@ -846,7 +847,9 @@ static int knn_radix_sort(int P, const KnnWs& w, bool fine, hipStream_t s, const
 
 // bounding box -> Morton keys -> sort -> gather into Morton order (-> boxes)
 // fine: morton_fine_kernel's 39-bit codes (the query search's reference set) instead of the reference's 30-bit ones
-static int knn_build(int P, const float* xyz, const KnnWs& w, bool with_boxes, hipStream_t s, bool fine = false, const int32_t* group = nullptr) {
+// gather = false (dqo_mesh_nearest, whose sorted rows are its own three float4 per face): the sorted keys only, w.sorted left as the sort's scratch
+static int knn_build(int P, const float* xyz, const KnnWs& w, bool with_boxes, hipStream_t s, bool fine = false, const int32_t* group = nullptr,
+                     bool gather = true) {
     fine = fine && P < (1 << FINE_IDX_BITS);
     const int P2 = next_pow2(P < SORT_RUN ? SORT_RUN : P);
     {   // (the partial boxes live at the start of the key array: P2 >= 4096 keys = 32 KB, and the keys are written after the fold)
@@ -859,6 +862,7 @@ static int knn_build(int P, const float* xyz, const KnnWs& w, bool with_boxes, h
     else DQO_LAUNCH("morton_kernel", morton_kernel, dim3((P2 + 255) / 256), dim3(256), s, P, P2, xyz, w.bbox, w.keys);
     const int rc = knn_radix_sort(P, w, fine, s);
     if (rc) return rc;
+    if (!gather) return DQO_OK;
     DQO_LAUNCH("gather_sorted_kernel", gather_sorted_kernel, dim3((P + 255) / 256), dim3(256), s, P, xyz, w.keys, w.sorted,
                fine ? ((1ull << FINE_IDX_BITS) - 1ull) : 0xffffffffull, group);
     if (with_boxes) {
@@ -940,8 +944,347 @@ int dqo_launch_nn1(int Q, const float* q_xyz, DqoNn1Rows q_rows, int R, const fl
     return DQO_OK;
 }
 
+// ---- dqo_mesh_nearest: the nearest FACE of a mesh for every query, the exact point-to-triangle distance ----------------------------------
+// dqo_nn1's walk with three changes: the references are triangles (sorted along the fine Morton grid of their centroids, gathered as three
+// float4: corner a with the face index in .w — -1 for a face that is not valid —, corner b, corner c), the pruning records (runs of 64
+// faces, boxes of 1024, groups of 64 boxes; the same 8-float format) are taken over the faces' CORNERS, and the candidate step is the
+// point-triangle distance of include/dqo_raster.h: E(p, f), Ericson's seven-region walk one float rounding at a time, clamped from below
+// by the face's own bounding box: D(p, f) = fmaxf(E(p, f), B(p, aabb(f))), B = dist_box_point.
+// WHY THE CLAMP MAKES PRUNING EXACT.  nn1_scan_kernel skips a record when B(record) > best.  B is monotone under box enclosure IN FLOAT:
+// per axis, a point outside the outer box lies outside the inner one on the same side, the two differences are rounded monotonically and
+// the smaller of them is taken, squares and sums round monotonically.  A record's box encloses the boxes of its faces (min / max are
+// exact), so B(record) <= B(aabb(f)) <= D(p, f) for every face under it: a skipped record holds no face with D < best, and the result is
+// the minimum of D over ALL valid faces, bit for bit, whatever the order.  E alone does not have this property: its rounding error
+// relative to d^2 grows without bound as d -> 0 (x is a rounded point of the triangle, p - x cancels), so a face in a skipped record could
+// have E below B(record).  The clamp only ever raises E by E's own rounding error: in real arithmetic B(aabb(f)) <= d^2.
+// Faces that are not valid (row behind the count, an index outside the vertices, n.n not finite or not above 0) go through knn_build's
+// sentinel path (group -1: outside the grid's bounding box, sorted last), are gathered with face word -1, left out of every record and
+// never taken.  No float atomic; the header's counts are integer atomics on words the first launch cleared.
+#pragma clang fp contract(off)
+namespace {
+
+struct Tri {
+    float ax, ay, az, bx, by, bz, cx, cy, cz;
+};
+
+__device__ __forceinline__ float mn_dot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+
+// the validity rule's third statement: n = ab x ac, n.n finite and above 0
+__device__ __forceinline__ bool mn_has_area(const Tri t) {
+    const float abx = t.bx - t.ax, aby = t.by - t.ay, abz = t.bz - t.az, acx = t.cx - t.ax, acy = t.cy - t.ay, acz = t.cz - t.az;
+    const float nx = aby * acz - abz * acy, ny = abz * acx - abx * acz, nz = abx * acy - aby * acx;
+    const float nn = mn_dot(nx, ny, nz, nx, ny, nz);
+    return nn > 0.0f && nn < __int_as_float(0x7f800000);
+}
+
+// E(p, f) and its closest point x (include/dqo_raster.h states the walk; Ericson, Real-Time Collision Detection, 5.1.5)
+__device__ __forceinline__ float mn_closest(float px, float py, float pz, const Tri t, float& xx, float& xy, float& xz) {
+    const float abx = t.bx - t.ax, aby = t.by - t.ay, abz = t.bz - t.az, acx = t.cx - t.ax, acy = t.cy - t.ay, acz = t.cz - t.az;
+    const float apx = px - t.ax, apy = py - t.ay, apz = pz - t.az;
+    const float d1 = mn_dot(abx, aby, abz, apx, apy, apz), d2 = mn_dot(acx, acy, acz, apx, apy, apz);
+    const float bpx = px - t.bx, bpy = py - t.by, bpz = pz - t.bz;
+    const float d3 = mn_dot(abx, aby, abz, bpx, bpy, bpz), d4 = mn_dot(acx, acy, acz, bpx, bpy, bpz);
+    const float cpx = px - t.cx, cpy = py - t.cy, cpz = pz - t.cz;
+    const float d5 = mn_dot(abx, aby, abz, cpx, cpy, cpz), d6 = mn_dot(acx, acy, acz, cpx, cpy, cpz);
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    const float e = d4 - d3, g = d5 - d6;
+    if (d1 <= 0.0f && d2 <= 0.0f) {
+        xx = t.ax, xy = t.ay, xz = t.az;
+    } else if (d3 >= 0.0f && d4 <= d3) {
+        xx = t.bx, xy = t.by, xz = t.bz;
+    } else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {
+        const float v = d1 / (d1 - d3);
+        xx = t.ax + v * abx, xy = t.ay + v * aby, xz = t.az + v * abz;
+    } else if (d6 >= 0.0f && d5 <= d6) {
+        xx = t.cx, xy = t.cy, xz = t.cz;
+    } else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {
+        const float w = d2 / (d2 - d6);
+        xx = t.ax + w * acx, xy = t.ay + w * acy, xz = t.az + w * acz;
+    } else if (va <= 0.0f && e >= 0.0f && g >= 0.0f) {
+        const float w = e / (e + g);
+        xx = t.bx + w * (t.cx - t.bx), xy = t.by + w * (t.cy - t.by), xz = t.bz + w * (t.cz - t.bz);
+    } else {
+        const float den = 1.0f / ((va + vb) + vc);
+        const float v = vb * den, w = vc * den;
+        xx = (t.ax + abx * v) + acx * w, xy = (t.ay + aby * v) + acy * w, xz = (t.az + abz * v) + acz * w;
+    }
+    const float rx = px - xx, ry = py - xy, rz = pz - xz;
+    float E = mn_dot(rx, ry, rz, rx, ry, rz);
+    if (!(E - E == 0.0f)) {  // not finite (0 / 0 in a sliver's edge branch): the face stands for its corner a
+        E = mn_dot(apx, apy, apz, apx, apy, apz);
+        xx = t.ax, xy = t.ay, xz = t.az;
+    }
+    return E;
+}
+
+// D(p, f) = fmaxf(E(p, f), B(p, aabb(f)))
+__device__ __forceinline__ float mn_dist(const float4 me, const Tri t, float& xx, float& xy, float& xz) {
+    const float E = mn_closest(me.x, me.y, me.z, t, xx, xy, xz);
+    float bx[6];
+    bx[0] = fminf(fminf(t.ax, t.bx), t.cx), bx[1] = fminf(fminf(t.ay, t.by), t.cy), bx[2] = fminf(fminf(t.az, t.bz), t.cz);
+    bx[3] = fmaxf(fmaxf(t.ax, t.bx), t.cx), bx[4] = fmaxf(fmaxf(t.ay, t.by), t.cy), bx[5] = fmaxf(fmaxf(t.az, t.bz), t.cz);
+    return fmaxf(E, dist_box_point(bx, me));
+}
+
+// face f's corners under the mesh transform, as every kernel here loads them; false: a row behind the count or a bad index
+__device__ __forceinline__ bool mn_load(const float* __restrict__ vertices, const int32_t* __restrict__ faces, const float* __restrict__ xform,
+                                        uint32_t f, uint32_t V, Tri& t) {
+    int32_t a, b, c;
+    if (!mo_face(faces, f, V, a, b, c)) return false;
+    const float4 pa = nn1_point(vertices, xform, a), pb = nn1_point(vertices, xform, b), pc = nn1_point(vertices, xform, c);
+    t.ax = pa.x, t.ay = pa.y, t.az = pa.z, t.bx = pb.x, t.by = pb.y, t.bz = pb.z, t.cx = pc.x, t.cy = pc.y, t.cz = pc.z;
+    return true;
+}
+
+enum { MN_FACES = 0, MN_VALID = 1, MN_BAD_INDEX = 2, MN_DEGENERATE = 3, MN_QUERIES = 4 };
+
+__global__ void mn_clear_kernel(int32_t* __restrict__ header) {
+    if (threadIdx.x < 8) header[threadIdx.x] = 0;
+}
+
+// per face of the capacity: its centroid (the point knn_build sorts it by) and its group id, 0 = valid, -1 = not; the header's counts
+__global__ __launch_bounds__(256) void mn_face_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ faces,
+                                                      const int32_t* __restrict__ counts, uint32_t cap_v, uint32_t cap_f,
+                                                      const float* __restrict__ xform, float* __restrict__ centroid, int32_t* __restrict__ grp,
+                                                      int32_t* __restrict__ header) {
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t V = mo_count(counts, 0, cap_v), F = mo_count(counts, 1, cap_f);
+    int kind = -1;  // -1: behind the count, else one of the header's words
+    float cx = 0.f, cy = 0.f, cz = 0.f;
+    if (f < F) {
+        Tri t;
+        if (!mn_load(vertices, faces, xform, f, V, t)) kind = MN_BAD_INDEX;
+        else if (!mn_has_area(t)) kind = MN_DEGENERATE;
+        else {
+            kind = MN_VALID;
+            cx = ((t.ax + t.bx) + t.cx) / 3.0f, cy = ((t.ay + t.by) + t.cy) / 3.0f, cz = ((t.az + t.bz) + t.cz) / 3.0f;
+        }
+    }
+    if (f < cap_f) {
+        centroid[3 * (size_t)f] = cx, centroid[3 * (size_t)f + 1] = cy, centroid[3 * (size_t)f + 2] = cz;
+        grp[f] = kind == MN_VALID ? 0 : -1;
+    }
+    const int lane = threadIdx.x & 63;
+    const unsigned long long below = __ballot(kind >= 0), valid = __ballot(kind == MN_VALID), bad = __ballot(kind == MN_BAD_INDEX),
+                             deg = __ballot(kind == MN_DEGENERATE);
+    if (lane == 0 && below != 0ull) {
+        atomicAdd(&header[MN_FACES], __popcll(below));
+        if (valid != 0ull) atomicAdd(&header[MN_VALID], __popcll(valid));
+        if (bad != 0ull) atomicAdd(&header[MN_BAD_INDEX], __popcll(bad));
+        if (deg != 0ull) atomicAdd(&header[MN_DEGENERATE], __popcll(deg));
+    }
+}
+
+// the faces in Morton order: three float4 per face; a face that is not valid (grp -1) becomes a far sentinel with face word -1
+__global__ void mn_gather_kernel(uint32_t cap_f, const float* __restrict__ vertices, const int32_t* __restrict__ faces,
+                                 const int32_t* __restrict__ counts, uint32_t cap_v, const float* __restrict__ xform,
+                                 const int32_t* __restrict__ grp, const uint64_t* __restrict__ keys, float4* __restrict__ tris) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap_f) return;
+    const uint32_t src = (uint32_t)keys[i] & NN1_IDX_MASK;
+    Tri t;
+    const bool ok = grp[src] == 0 && mn_load(vertices, faces, xform, src, mo_count(counts, 0, cap_v), t);
+    if (!ok) t.ax = t.ay = t.az = t.bx = t.by = t.bz = t.cx = t.cy = t.cz = 1e18f;
+    tris[3 * (size_t)i] = make_float4(t.ax, t.ay, t.az, __int_as_float(ok ? (int)src : -1));
+    tris[3 * (size_t)i + 1] = make_float4(t.bx, t.by, t.bz, 0.f);
+    tris[3 * (size_t)i + 2] = make_float4(t.cx, t.cy, t.cz, 0.f);
+}
+
+// the run (64 faces, one wave) and box (1024 faces, the block) records over the CORNERS of the valid faces; a record without one keeps
+// {FLT_MAX, -FLT_MAX}: its box distance is +inf and nothing opens it.  Group words 0 (the scan is the unfiltered one).
+__global__ __launch_bounds__(KNN_BOX) void mn_records_kernel(int F, const float4* __restrict__ tris, float* __restrict__ boxes,
+                                                              float* __restrict__ sub) {
+    __shared__ float s[6][KNN_BOX / KNN_SUB];
+    const int i = blockIdx.x * KNN_BOX + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+    if (i < F) {
+        const float4 a = tris[3 * (size_t)i], b = tris[3 * (size_t)i + 1], c = tris[3 * (size_t)i + 2];
+        if (__float_as_int(a.w) >= 0) {
+            mn[0] = fminf(fminf(a.x, b.x), c.x), mn[1] = fminf(fminf(a.y, b.y), c.y), mn[2] = fminf(fminf(a.z, b.z), c.z);
+            mx[0] = fmaxf(fmaxf(a.x, b.x), c.x), mx[1] = fmaxf(fmaxf(a.y, b.y), c.y), mx[2] = fmaxf(fmaxf(a.z, b.z), c.z);
+        }
+    }
+    for (int a = 0; a < 3; a++)
+        for (int off = 32; off > 0; off >>= 1) {
+            mn[a] = fminf(mn[a], __shfl_xor(mn[a], off));
+            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off));
+        }
+    const int run = blockIdx.x * (KNN_BOX / KNN_SUB) + wave;
+    if (run * KNN_SUB < F && lane < 8)
+        sub[8 * (size_t)run + lane] = lane == 0 ? mn[0] : lane == 1 ? mn[1] : lane == 2 ? mn[2] : lane == 3 ? mx[0] : lane == 4 ? mx[1]
+                                                                                                                  : lane == 5 ? mx[2] : 0.f;
+    if (lane == 0)
+        for (int a = 0; a < 3; a++) s[a][wave] = mn[a], s[3 + a][wave] = mx[a];
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        float r = 0.f;
+        if (threadIdx.x < 6) {
+            r = s[threadIdx.x][0];
+            for (int w = 1; w < KNN_BOX / KNN_SUB; w++) r = threadIdx.x < 3 ? fminf(r, s[threadIdx.x][w]) : fmaxf(r, s[threadIdx.x][w]);
+        }
+        boxes[8 * (size_t)blockIdx.x + threadIdx.x] = r;
+    }
+}
+
+__device__ __forceinline__ Tri mn_tri(const float4* __restrict__ tris, int i, int& face) {
+    const float4 a = tris[3 * (size_t)i], b = tris[3 * (size_t)i + 1], c = tris[3 * (size_t)i + 2];  // (wave-uniform address)
+    face = __float_as_int(a.w);
+    return Tri{a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z};
+}
+
+// D and a two-select take; a sentinel (face word -1) is never taken
+__device__ __forceinline__ void mn_take(const float4 me, const float4* __restrict__ tris, int i, float& best, int& bface) {
+    int face;
+    const Tri t = mn_tri(tris, i, face);
+    float xx, xy, xz;
+    const float D = mn_dist(me, t, xx, xy, xz);
+    const bool take = face >= 0 && D < best;
+    best = take ? D : best, bface = take ? face : bface;
+}
+
+// nn1_scan_kernel<false>'s walk over the faces: one lane per sorted query, a record opened by the wave's ballot, a run's faces by
+// wave-uniform loads, the faces around the query's rank first (a start bound), then the home box, then every group that cannot be excluded.
+__global__ __launch_bounds__(256) void mn_scan_kernel(int Q, const float4* __restrict__ sorted_q, const uint64_t* __restrict__ keys_q, int F,
+                                                      const float4* __restrict__ tris, const uint64_t* __restrict__ keys_f,
+                                                      const float* __restrict__ boxes, const float* __restrict__ sub,
+                                                      const float* __restrict__ groups, const float* __restrict__ vertices,
+                                                      const int32_t* __restrict__ faces, const int32_t* __restrict__ counts, uint32_t cap_v,
+                                                      const float* __restrict__ xform, float* __restrict__ dist2, int32_t* __restrict__ face_out,
+                                                      float* __restrict__ closest, int32_t* __restrict__ header) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    const float4 me = q < Q ? sorted_q[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint32_t my_w = __float_as_uint(me.w);
+    const bool live = q < Q && (my_w >> KNN_GROUP_SHIFT) != 0u;
+    float best = FLT_MAX;
+    int bface = -1, rank = 0;
+    if (live) {
+        const uint64_t key = (keys_q[q] >> FINE_IDX_BITS) << FINE_IDX_BITS;
+        int lo = 0, hi = F;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (keys_f[mid] < key) lo = mid + 1;
+            else hi = mid;
+        }
+        rank = lo;
+        for (int i = max(0, rank - 2); i <= min(F - 1, rank + 1); i++) mn_take(me, tris, i, best, bface);
+    }
+    const int nb = (F + KNN_BOX - 1) / KNN_BOX, ng = (nb + 63) / 64;
+    auto wanted = [&](const float* rec) { return __ballot(live && !(dist_box_point(rec, me) > best)) != 0; };
+    auto scan_box = [&](int b) {
+        if (!wanted(boxes + 8 * (size_t)b)) return;
+        const int lo = b * KNN_BOX, hi = min(F, lo + KNN_BOX);
+        for (int r0 = lo; r0 < hi; r0 += KNN_SUB) {
+            if (!wanted(sub + 8 * (size_t)(r0 / KNN_SUB))) continue;
+            const int r1 = min(hi, r0 + KNN_SUB);
+            for (int i = r0; i < r1; i++) mn_take(me, tris, i, best, bface);
+        }
+    };
+    const unsigned long long lives = __ballot(live);
+    if (lives != 0ull) {
+        if ((threadIdx.x & 63) == 0) atomicAdd(&header[MN_QUERIES], __popcll(lives));
+        // queries that take no part sort last, so lane 0 of a wave with a live lane is live: the box its rank falls into first
+        const int home = min(nb - 1, __builtin_amdgcn_readfirstlane(rank) / KNN_BOX);
+        scan_box(home);
+        for (int g = 0; g < ng; g++) {
+            if (!wanted(groups + 8 * (size_t)g)) continue;
+            const int b1 = min(nb, (g + 1) * 64);
+            for (int b = g * 64; b < b1; b++)
+                if (b != home) scan_box(b);
+        }
+    }
+    if (q < Q) {
+        const uint32_t dst = my_w & NN1_IDX_MASK;
+        const bool found = live && bface >= 0;
+        dist2[dst] = found ? best : FLT_MAX;
+        if (face_out != nullptr) face_out[dst] = found ? bface : -1;
+        if (closest != nullptr && found) {  // E's x for the returned face, once
+            Tri t;
+            mn_load(vertices, faces, xform, (uint32_t)bface, mo_count(counts, 0, cap_v), t);
+            float xx, xy, xz;
+            mn_closest(me.x, me.y, me.z, t, xx, xy, xz);
+            closest[3 * (size_t)dst] = xx, closest[3 * (size_t)dst + 1] = xy, closest[3 * (size_t)dst + 2] = xz;
+        }
+    }
+}
+
+struct MnWs {
+    KnnWs f, q;
+    float* centroid;  // [cap_f][3]
+    int32_t* grp;     // [cap_f] 0 = a valid face, -1 = not
+    float4* tris;     // [cap_f][3] the faces in Morton order
+    size_t total;
+};
+inline MnWs mn_ws(void* base, int Q, int cap_f) {
+    MnWs w;
+    DqoCarver k(base);
+    w.f = knn_ws(k.take_raw(knn_ws(nullptr, cap_f).total), cap_f);
+    w.q = knn_ws(k.take_raw(knn_ws(nullptr, Q).total), Q);
+    w.centroid = k.take<float>(12 * (size_t)cap_f);
+    w.grp = k.take<int32_t>(4 * (size_t)cap_f);
+    w.tris = k.take<float4>(48 * (size_t)cap_f);
+    w.total = k.total();
+    return w;
+}
+
+}  // namespace
+
+// Q and cap_faces carry dqo_nn1's index bits; cap_vertices is the mesh operand's
+bool dqo_mesh_nearest_size_ok(int32_t Q, int32_t cap_v, int32_t cap_f) {
+    return Q >= 1 && cap_f >= 1 && dqo_nn1_size_ok(Q) && dqo_nn1_size_ok(cap_f) && cap_v >= 1 && cap_v < MO_MAX;
+}
+
+size_t dqo_mesh_nearest_ws_bytes(int Q, int cap_v, int cap_f) {
+    (void)cap_v;
+    return mn_ws(nullptr, Q, cap_f).total;
+}
+
+int dqo_launch_mesh_nearest(int Q, const float* q_xyz, const uint8_t* q_keep, const float* q_xform, const float* vertices, const int32_t* faces,
+                            const int32_t* counts, int cap_v, int cap_f, const float* mesh_xform, float* dist2, int32_t* face, float* closest,
+                            int32_t* header, void* ws, hipStream_t s) {
+    const MnWs w = mn_ws(ws, Q, cap_f);
+    DQO_LAUNCH("mn_clear_kernel", mn_clear_kernel, dim3(1), dim3(64), s, header);
+    DQO_LAUNCH("mn_face_kernel", mn_face_kernel, dim3((cap_f + 255) / 256), dim3(256), s, vertices, faces, counts, (uint32_t)cap_v,
+               (uint32_t)cap_f, mesh_xform, w.centroid, w.grp, header);
+    int rc = knn_build(cap_f, w.centroid, w.f, false, s, true, w.grp, false);  // (the keys only: mn_gather_kernel makes the sorted rows)
+    if (rc) return rc;
+    DQO_LAUNCH("mn_gather_kernel", mn_gather_kernel, dim3((cap_f + 255) / 256), dim3(256), s, (uint32_t)cap_f, vertices, faces, counts,
+               (uint32_t)cap_v, mesh_xform, w.grp, w.f.keys, w.tris);
+    const int nb = (cap_f + KNN_BOX - 1) / KNN_BOX, ng = (nb + 63) / 64;
+    DQO_LAUNCH("mn_records_kernel", mn_records_kernel, dim3(nb), dim3(KNN_BOX), s, cap_f, w.tris, w.f.boxes, w.f.sub);
+    DQO_LAUNCH("group_minmax_kernel", group_minmax_kernel, dim3((ng * 64 + 255) / 256), dim3(256), s, nb, w.f.boxes, w.f.groups);
+    const DqoNn1Rows q_rows = {q_keep, nullptr};
+    DQO_LAUNCH("nn1_query_keys_kernel", nn1_query_keys_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, q_xyz, q_rows, q_xform, w.f.bbox, w.q.keys);
+    rc = knn_radix_sort(Q, w.q, true, s);
+    if (rc) return rc;
+    DQO_LAUNCH("nn1_gather_query_kernel", nn1_gather_query_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, q_xyz, q_rows, q_xform, w.q.keys,
+               w.q.sorted);
+    DQO_LAUNCH("mn_scan_kernel", mn_scan_kernel, dim3((Q + 255) / 256), dim3(256), s, Q, w.q.sorted, w.q.keys, cap_f, w.tris, w.f.keys, w.f.boxes,
+               w.f.sub, w.f.groups, vertices, faces, counts, (uint32_t)cap_v, mesh_xform, dist2, face, closest, header);
+    return DQO_OK;
+}
+
 // ---- entry points (include/dqo_raster.h): size queries, argument validation, the call ----
 extern "C" {
+
+DQO_API size_t dqo_mesh_nearest_workspace_bytes(int32_t Q, int32_t cap_vertices, int32_t cap_faces) {
+    return dqo_mesh_nearest_size_ok(Q, cap_vertices, cap_faces) ? dqo_mesh_nearest_ws_bytes(Q, cap_vertices, cap_faces) : 0;
+}
+
+DQO_API int dqo_mesh_nearest(int32_t Q, const float* query_xyz, const uint8_t* query_keep, const float* query_xform, const float* vertices,
+                             const int32_t* faces, const int32_t* counts, int32_t cap_vertices, int32_t cap_faces, const float* mesh_xform,
+                             float* dist2, int32_t* face, float* closest, int32_t* header, void* workspace, size_t workspace_bytes,
+                             void* hipStream) {
+    DQO_CHECK_ARG(dqo_mesh_nearest_size_ok(Q, cap_vertices, cap_faces),
+                  "bad size: %d queries, %d vertices, %d faces of capacity: queries and faces in [1, 2^25 - 1], vertices in [1, 2^28)", Q,
+                  cap_vertices, cap_faces);
+    DQO_CHECK_ARG(query_xyz && dist2, "null query / output");
+    DQO_CHECK_ARG(vertices && faces && header, "null mesh buffer / header");
+    DQO_CHECK_ARG(header != counts, "header must not be the mesh's counts: the first launch clears it before the counts are read");
+    DQO_CHECK_WS("mesh nearest", workspace, workspace_bytes, dqo_mesh_nearest_ws_bytes(Q, cap_vertices, cap_faces));
+    return dqo_launch_mesh_nearest(Q, query_xyz, query_keep, query_xform, vertices, faces, counts, cap_vertices, cap_faces, mesh_xform, dist2,
+                                   face, closest, header, workspace, (hipStream_t)hipStream);
+}
+
 
 DQO_API size_t dqo_knn3_query_workspace_bytes(int32_t Q, int32_t R) { return dqo_knn3_query_ws_bytes(Q < 1 ? 1 : Q, R < 1 ? 1 : R); }
 

@@ -468,6 +468,68 @@ static int dqo_launch_eval_pcd(int n_gt, const float* gt_xyz, const uint8_t* gt_
     return DQO_OK;
 }
 
+// ---- dqo_eval_pcd_surface: eval_pcd's row with a side's distances taken to the other side's SURFACE where that side has a mesh ----------
+// The two dist2 columns come from dqo_mesh_nearest (knn.hip) for a side with a mesh and from dqo_nn1 for a side without; eval_pcd_kernel
+// reduces them unchanged.  The searches run one after the other in one workspace part; each mesh search has its own int32 [8] header.
+struct PcMesh {
+    const float* vertices;
+    const int32_t* faces;
+    const int32_t* counts;
+    int cap_v, cap_f;  // 0, 0: the side has no mesh
+    bool has() const { return cap_f > 0; }
+};
+struct PcsWorkspace {
+    EvWorkspace ev;
+    float *d2_rec, *d2_gt;
+    int32_t *header_gt, *header_rec;  // dqo_mesh_nearest's headers: rec points against the gt mesh, gt points against the rec mesh
+    void* search;
+    size_t total;
+};
+inline size_t pcs_search_bytes(int Q, int R, const PcMesh& m) {  // Q queries against the other side: its mesh, or its R points
+    if (!m.has()) return dqo_nn1_ws_bytes(Q, R);
+    return Q > 0 ? dqo_mesh_nearest_ws_bytes(Q, m.cap_v, m.cap_f) : 0;
+}
+inline PcsWorkspace pcs_ws(void* base, int n_gt, int n_rec, const PcMesh& gt_mesh, const PcMesh& rec_mesh) {
+    PcsWorkspace w;
+    DqoCarver k(base);
+    w.ev = ev_take(k, pc_blocks(n_rec) + pc_blocks(n_gt) + 1, PC_STRIDE);
+    w.d2_rec = k.take<float>(4 * (size_t)n_rec);
+    w.d2_gt = k.take<float>(4 * (size_t)n_gt);
+    w.header_gt = k.take<int32_t>(32);
+    w.header_rec = k.take<int32_t>(32);
+    w.search = k.take_raw(std::max(pcs_search_bytes(n_rec, n_gt, gt_mesh), pcs_search_bytes(n_gt, n_rec, rec_mesh)));
+    w.total = k.total();
+    return w;
+}
+
+static int dqo_launch_eval_pcd_surface(int n_gt, const float* gt_xyz, const uint8_t* gt_keep, const PcMesh& gt_mesh, int n_rec,
+                                       const float* rec_xyz, const uint8_t* rec_keep, const PcMesh& rec_mesh, const float* rec_xform, int n_thres,
+                                       const float* thres, float* out_row, void* ws, hipStream_t s) {
+    const PcsWorkspace w = pcs_ws(ws, n_gt, n_rec, gt_mesh, rec_mesh);
+    const DqoNn1Rows gt_rows = {gt_keep, nullptr}, rec_rows = {rec_keep, nullptr};
+    int rc = DQO_OK;
+    // accuracy: every reconstructed point (under rec_xform) to the ground truth — its surface, or its points
+    if (!gt_mesh.has())
+        rc = dqo_launch_nn1(n_rec, rec_xyz, rec_rows, n_gt, gt_xyz, gt_rows, rec_xform, nullptr, w.d2_rec, nullptr, nullptr, w.search, s);
+    else if (n_rec > 0)
+        rc = dqo_launch_mesh_nearest(n_rec, rec_xyz, rec_keep, rec_xform, gt_mesh.vertices, gt_mesh.faces, gt_mesh.counts, gt_mesh.cap_v,
+                                     gt_mesh.cap_f, nullptr, w.d2_rec, nullptr, nullptr, w.header_gt, w.search, s);
+    if (rc) return rc;
+    // completion: every ground-truth point to the reconstruction — its surface with the vertices under rec_xform, or its points
+    if (!rec_mesh.has())
+        rc = dqo_launch_nn1(n_gt, gt_xyz, gt_rows, n_rec, rec_xyz, rec_rows, nullptr, rec_xform, w.d2_gt, nullptr, nullptr, w.search, s);
+    else if (n_gt > 0)
+        rc = dqo_launch_mesh_nearest(n_gt, gt_xyz, gt_keep, nullptr, rec_mesh.vertices, rec_mesh.faces, rec_mesh.counts, rec_mesh.cap_v,
+                                     rec_mesh.cap_f, rec_xform, w.d2_gt, nullptr, nullptr, w.header_rec, w.search, s);
+    if (rc) return rc;
+    PcThres th;
+    for (int t = 0; t < PC_THRES; t++) th.th[t] = t < n_thres ? thres[t] : 0.f;
+    const int blocks_rec = (int)pc_blocks(n_rec), blocks = std::max(1, blocks_rec + (int)pc_blocks(n_gt));
+    DQO_LAUNCH("eval_pcd_kernel", eval_pcd_kernel, dim3((unsigned)blocks), dim3(256), s, n_rec, w.d2_rec, rec_keep, n_gt, w.d2_gt, gt_keep, n_thres,
+               th, blocks_rec, w.ev, out_row);
+    return DQO_OK;
+}
+
 static int dqo_launch_eval_pcd_grouped(int n_gt, const float* gt_xyz, const int32_t* gt_group, int n_rec, const float* rec_xyz,
                                        const int32_t* rec_group, const float* rec_xform, int n_thres, const float* thres, float* out_rows, void* ws,
                                        hipStream_t s) {
@@ -522,6 +584,38 @@ DQO_API int dqo_eval_pcd(int32_t n_gt, const float* gt_xyz, const uint8_t* gt_ke
     DQO_CHECK_WS("eval_pcd", ws, ws_bytes, dqo_eval_pcd_ws_bytes(n_gt, n_rec));
     return dqo_launch_eval_pcd(n_gt, gt_xyz, gt_keep, n_rec, rec_xyz, rec_keep, rec_xform, n_thres, thres_host, out_table + (size_t)32 * row, ws,
                                (hipStream_t)stream);
+}
+
+// eval_pcd's row with exact point-to-triangle distances on every side that has a mesh (a side without one: capacities 0, 0 and no buffers)
+static bool pcs_mesh_ok(const PcMesh& m) {
+    if (m.cap_v == 0 && m.cap_f == 0) return m.vertices == nullptr && m.faces == nullptr && m.counts == nullptr;
+    return dqo_mesh_nearest_size_ok(1, m.cap_v, m.cap_f);
+}
+
+DQO_API size_t dqo_eval_pcd_surface_workspace_bytes(int32_t n_gt, int32_t gt_cap_vertices, int32_t gt_cap_faces, int32_t n_rec,
+                                                    int32_t rec_cap_vertices, int32_t rec_cap_faces) {
+    const PcMesh gt_mesh = {nullptr, nullptr, nullptr, gt_cap_vertices, gt_cap_faces}, rec_mesh = {nullptr, nullptr, nullptr, rec_cap_vertices, rec_cap_faces};
+    if (!dqo_nn1_size_ok(n_gt) || !dqo_nn1_size_ok(n_rec) || !pcs_mesh_ok(gt_mesh) || !pcs_mesh_ok(rec_mesh)) return 0;
+    return pcs_ws(nullptr, n_gt, n_rec, gt_mesh, rec_mesh).total;
+}
+
+DQO_API int dqo_eval_pcd_surface(int32_t n_gt, const float* gt_xyz, const uint8_t* gt_keep, const float* gt_vertices, const int32_t* gt_faces,
+                                 const int32_t* gt_counts, int32_t gt_cap_vertices, int32_t gt_cap_faces, int32_t n_rec, const float* rec_xyz,
+                                 const uint8_t* rec_keep, const float* rec_vertices, const int32_t* rec_faces, const int32_t* rec_counts,
+                                 int32_t rec_cap_vertices, int32_t rec_cap_faces, const float* rec_xform, int32_t n_thres, const float* thres_host,
+                                 float* out_table, int32_t row, void* ws, size_t ws_bytes, void* stream) {
+    const PcMesh gt_mesh = {gt_vertices, gt_faces, gt_counts, gt_cap_vertices, gt_cap_faces};
+    const PcMesh rec_mesh = {rec_vertices, rec_faces, rec_counts, rec_cap_vertices, rec_cap_faces};
+    DQO_CHECK_ARG(dqo_nn1_size_ok(n_gt) && dqo_nn1_size_ok(n_rec), "bad size: at most 2^25 - 1 rows per set");
+    DQO_CHECK_ARG(pcs_mesh_ok(gt_mesh) && pcs_mesh_ok(rec_mesh),
+                  "bad mesh: a side without one has capacities 0, 0 and null buffers, else faces in [1, 2^25 - 1] and vertices in [1, 2^28)");
+    DQO_CHECK_ARG((!gt_mesh.has() || (gt_vertices && gt_faces)) && (!rec_mesh.has() || (rec_vertices && rec_faces)), "null mesh buffer");
+    DQO_CHECK_ARG((n_gt == 0 || gt_xyz) && (n_rec == 0 || rec_xyz) && out_table, "null pointer");
+    DQO_CHECK_ARG(n_thres >= 0 && n_thres <= 8 && (n_thres == 0 || thres_host), "at most 8 thresholds (got %d)", n_thres);
+    DQO_CHECK_ARG(row >= 0, "bad row %d", row);
+    DQO_CHECK_WS("eval_pcd surface", ws, ws_bytes, pcs_ws(nullptr, n_gt, n_rec, gt_mesh, rec_mesh).total);
+    return dqo_launch_eval_pcd_surface(n_gt, gt_xyz, gt_keep, gt_mesh, n_rec, rec_xyz, rec_keep, rec_mesh, rec_xform, n_thres, thres_host,
+                                       out_table + (size_t)32 * row, ws, (hipStream_t)stream);
 }
 
 // metric_obj.py:169-236: eval_pcd of every object's cloud against its own ground truth — one row per object id

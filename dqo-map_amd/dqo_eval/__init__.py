@@ -120,6 +120,14 @@ include/dqo_raster.h states and tests/mesh_render_oracle.py restates; csrc/map_e
 FusedMapper.evaluate_mesh_depth forms the views from frames, and with mesh=None compares the map's own render.  Not built: back-face
 culling, per-view intrinsics, colour or normal shading of the mesh.
 
+Exact point-to-triangle distance — the nearest FACE of a mesh per point (csrc/knn.hip, dqo_mesh_nearest: dqo_nn1's walk over the faces;
+include/dqo_raster.h states the float32 rule and tests/mesh_dist_oracle.py restates it), and eval_pcd's row on those distances, free of
+the nearest-sample floor of about 0.5 / sqrt(samples per square metre) that the sampled form adds to accuracy and completion:
+
+    nearest_on_mesh(points, mesh, ...)                      ->  (dist2 [Q], face [Q] | None, closest [Q,3] | None, header: MESH_NEAREST_HEADER)
+    eval_pcd_surface(gt_points, rec_points, gt_mesh, rec_mesh, ...)  ->  float32 [32] (PCD_ROW); a side without a mesh keeps eval_pcd's search
+    eval_mesh_surface(rec_mesh, gt_mesh, ...)               ->  eval_mesh's culls and samples, the distances to the culled surfaces
+
 GPU only: there is no CPU path.
 """
 import ctypes
@@ -1212,6 +1220,92 @@ def sample_surface_counted(mesh, count, seed=0, want_face_index=False, workspace
     return o
 
 
+# ---- exact point-to-triangle distance: the nearest face of a mesh per point (csrc/knn.hip: dqo_mesh_nearest) ------------------------------
+MESH_NEAREST_HEADER = ("faces", "faces_valid", "faces_bad_index", "faces_degenerate", "queries", "zero5", "zero6", "zero7")
+
+
+def nearest_on_mesh(points, mesh, query_keep=None, query_transform=None, mesh_transform=None, want_face=True, want_closest=False,
+                    workspace_buffer=None):
+    """The nearest face of a mesh for every point and the exact squared point-to-triangle distance to it (dqo_mesh_nearest;
+    include/dqo_raster.h states the float32 rule): points [Q,3], mesh a mesh dict (as for mesh_components: vertices, faces and, when it
+    has one, a header whose words 0 and 1 are the counts) -> (dist2 float32 [Q], face int32 [Q] or None, closest float32 [Q,3] or None,
+    header int32 [8]: MESH_NEAREST_HEADER).  dist2 is the minimum over the VALID faces (indices inside the vertices, an area above 0) of
+    the rule's D — bit for bit, whatever the search order —, face one of the faces attaining it, closest the point of that face nearest
+    to the query.  query_keep: uint8 / bool mask, 0 = the point is not searched for (FLT_MAX / -1, its closest row left as
+    torch.empty made it); a mesh without a valid face gives FLT_MAX / -1 everywhere.  *_transform: [3,4] / [4,4], applied to the points /
+    the vertices as they are loaded.  Q and the face capacity lie in [1, 2^25 - 1].  No host read, no synchronisation, capturable;
+    workspace_buffer: a uint8 tensor of dqo_mesh_nearest_workspace_bytes(Q, cap_vertices, cap_faces) the caller keeps (default: one per
+    device and sizes, kept by this module — calls that share it must be on one stream)."""
+    v, c, f, h, cv, cf = _mesh(mesh, "nearest_on_mesh")
+    N.require_gpu_op((points, v), query_keep, workspace_buffer)
+    lib, dev = N.lib(), v.device
+    points = _points(points, "points")
+    Q = int(points.shape[0])
+    qk = _keep(query_keep, Q, "query_keep")
+    qx, mx = _xform(query_transform, dev, "query_transform"), _xform(mesh_transform, dev, "mesh_transform")
+    n = lib.dqo_mesh_nearest_workspace_bytes(Q, cv, cf)
+    if n == 0:
+        raise RuntimeError(f"dqo_eval.nearest_on_mesh: bad sizes: {Q} points, {cf} faces of capacity: each in [1, 2^25 - 1]")
+    ws = _ws(workspace_buffer, dev, n, "mesh_nearest", Q, cv, cf)
+    dist2 = torch.empty((Q,), dtype=torch.float32, device=dev)
+    face = torch.empty((Q,), dtype=torch.int32, device=dev) if want_face else None
+    closest = torch.empty((Q, 3), dtype=torch.float32, device=dev) if want_closest else None
+    header = torch.empty((8,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        N.check(lib.dqo_mesh_nearest(Q, N.ptr(points), N.ptr(qk), N.ptr(qx), v.data_ptr(), f.data_ptr(), N.ptr(h), cv, cf, N.ptr(mx),
+                                     N.ptr(dist2), N.ptr(face), N.ptr(closest), header.data_ptr(), ws.data_ptr(), ws.numel(),
+                                     N.current_stream()))
+    return dist2, face, closest, header
+
+
+def _surface_mesh(mesh, who, dev):
+    """(vertices ptr, faces ptr, counts ptr, cap_v, cap_f) of an optional mesh dict of eval_pcd_surface; None: no mesh on that side."""
+    if mesh is None:
+        return None, None, None, 0, 0
+    v, c, f, h, cv, cf = _mesh(mesh, who)
+    if v.device != dev:
+        raise RuntimeError(f"dqo_eval.{who}: the mesh must be on {dev}")
+    return v.data_ptr(), f.data_ptr(), N.ptr(h), cv, cf
+
+
+def eval_pcd_surface(gt_points, rec_points, gt_mesh=None, rec_mesh=None, dist_thres=(0.03,), transform=None, gt_keep=None, rec_keep=None,
+                     out=None, row=0, workspace_buffer=None):
+    """eval_pcd with exact point-to-SURFACE distances wherever a side has a mesh (dqo_eval_pcd_surface): the same float32 [32] row
+    (PCD_ROW), arguments and contract as eval_pcd, and two optional mesh dicts (as for mesh_components).
+    gt_mesh: every reconstructed point (under `transform`) is measured to the nearest FACE of gt_mesh instead of the nearest gt point —
+    accuracy and precision; rec_mesh: every ground-truth point is measured to the nearest face of rec_mesh, whose vertices go under
+    `transform` — completion and recall.  A side without a mesh keeps eval_pcd's nearest-point search; with neither mesh the row is
+    eval_pcd's.  The points of both sides are still given: they are the queries, and their keep masks decide which rows count.
+    A mesh without a valid face makes every distance to it FLT_MAX: that accuracy / completion is then 100 * sqrt(FLT_MAX) (about
+    1.8447e21), its P / R 0 and F1 with it; a side without a kept point gives a row of NaN, as in eval_pcd.
+    workspace_buffer: a zeroed uint8 tensor of dqo_eval_pcd_surface_workspace_bytes(...) the caller keeps (default: one per device and
+    sizes, kept by this module).  Nothing is read back, no synchronisation."""
+    N.require_gpu_op((gt_points, rec_points), gt_keep, rec_keep, out, workspace_buffer)
+    lib, dev = N.lib(), rec_points.device
+    gt, rec = _points(gt_points, "gt_points"), _points(rec_points, "rec_points")
+    G, P = int(gt.shape[0]), int(rec.shape[0])
+    gk, rk = _keep(gt_keep, G, "gt_keep"), _keep(rec_keep, P, "rec_keep")
+    xf = _xform(transform, dev, "transform")
+    gm, rm = _surface_mesh(gt_mesh, "eval_pcd_surface", dev), _surface_mesh(rec_mesh, "eval_pcd_surface", dev)
+    thres = [float(t) for t in dist_thres]
+    if len(thres) > PCD_THRES_MAX:
+        raise RuntimeError(f"dqo_eval.eval_pcd_surface: at most {PCD_THRES_MAX} thresholds, got {len(thres)}")
+    out, row = _table_row(out, row, 32, "eval_pcd_surface", dev, fresh=torch.empty)
+
+    def nbytes():
+        n = lib.dqo_eval_pcd_surface_workspace_bytes(G, gm[3], gm[4], P, rm[3], rm[4])
+        if n == 0:
+            raise RuntimeError(f"dqo_eval.eval_pcd_surface: bad sizes: {G}, {P} points (at most 2^25 - 1 rows per set), face capacities "
+                               f"{gm[4]}, {rm[4]} (at most 2^25 - 1)")
+        return n
+    ws = _ws(workspace_buffer, dev, nbytes, "pcd_surface", G, P, gm[3], gm[4], rm[3], rm[4])
+    with torch.cuda.device(dev):
+        N.check(lib.dqo_eval_pcd_surface(G, N.ptr(gt), N.ptr(gk), *gm, P, N.ptr(rec), N.ptr(rk), *rm, N.ptr(xf), len(thres),
+                                         (ctypes.c_float * len(thres))(*thres), out.data_ptr(), row, ws.data_ptr(), ws.numel(),
+                                         N.current_stream()))
+    return out[row]
+
+
 def eval_mesh(rec_mesh, gt_mesh, sample_nums=1000000, seed=0, rec_seed=None, dist_thres=(0.03,), transform=None, views=None, out=None, row=0):
     """How good a reconstructed MESH is against the ground-truth mesh, in one call on the device: both meshes culled to what the
     cameras saw, both sampled, the two point sets compared — mesh_cull -> sample_surface_counted -> eval_pcd.
@@ -1225,25 +1319,48 @@ def eval_mesh(rec_mesh, gt_mesh, sample_nums=1000000, seed=0, rec_seed=None, dis
     eval_pcd's, applied to the reconstruction's points; dist_thres, out, row: eval_pcd's.
     Returns the float32 [32] device row (PCD_ROW); nothing is read back and the call does not synchronise.  A side that is empty — no
     faces, no area, a cull that keeps nothing — gives a row of NaN, eval_pcd's rule.  Without `views`, a gt_mesh without a header yields
-    the very points sample_surface(gt vertices, gt faces, sample_nums, seed) yields."""
+    the very points sample_surface(gt vertices, gt faces, sample_nums, seed) yields.
+    The distances are point to nearest sampled POINT, as the reference's; eval_mesh_surface measures to the surface itself (this
+    function's signature is pinned, so that rule is a function of its own)."""
+    return _eval_mesh("eval_mesh", "samples", rec_mesh, gt_mesh, sample_nums, seed, rec_seed, dist_thres, transform, views, out, row)
+
+
+def eval_mesh_surface(rec_mesh, gt_mesh, sample_nums=1000000, seed=0, rec_seed=None, dist_thres=(0.03,), transform=None, views=None, out=None,
+                      row=0):
+    """eval_mesh with the distances taken to the SURFACE: the same culling and the same sampling — byte for byte the meshes and points
+    eval_mesh compares — but the chain ends in eval_pcd_surface on the culled meshes: a reconstructed sample is measured to the nearest
+    FACE of the (culled) ground-truth mesh, a ground-truth sample to the nearest face of the (culled) reconstruction under `transform`
+    (nearest_on_mesh's exact point-to-triangle distance).  eval_mesh's sampled form adds the mean nearest-sample distance of the other
+    side, about 0.5 / sqrt(samples per square metre), to accuracy and completion, and its result depends on `seed` through BOTH sides'
+    samples; here a side's samples are only the places where the other surface's distance is read.  Arguments, the returned float32
+    [32] device row and the contract (nothing read back, no synchronisation) are eval_mesh's; a side whose culled mesh keeps no valid
+    face has no kept sample either, so the row is NaN, as eval_mesh's."""
+    return _eval_mesh("eval_mesh_surface", "surface", rec_mesh, gt_mesh, sample_nums, seed, rec_seed, dist_thres, transform, views, out, row)
+
+
+def _eval_mesh(who, distance, rec_mesh, gt_mesh, sample_nums, seed, rec_seed, dist_thres, transform, views, out, row):
+    """eval_mesh's and eval_mesh_surface's chain; distance: "samples" (eval_pcd) or "surface" (eval_pcd_surface on the culled meshes)."""
     if views is not None:
         kw = dict(views)
         for k in ("out", "want_views", "want_pixels", "workspace_buffer"):
             if k in kw:
-                raise RuntimeError(f"dqo_eval.eval_mesh: views is a dict of mesh_cull's view keywords; {k!r} is eval_mesh's own")
+                raise RuntimeError(f"dqo_eval.{who}: views is a dict of mesh_cull's view keywords; {k!r} is {who}'s own")
         kw.pop("clip_near", None)  # (eval_mesh_depth's)
         visibility = kw.pop("visibility", "vertices")
         if visibility not in ("vertices", "faces"):
-            raise RuntimeError(f"dqo_eval.eval_mesh: views['visibility'] is 'vertices' or 'faces', got {visibility!r}")
+            raise RuntimeError(f"dqo_eval.{who}: views['visibility'] is 'vertices' or 'faces', got {visibility!r}")
         kw.pop("min_pixels" if visibility == "vertices" else "min_corners", None)  # (the other rule's)
         cull = mesh_cull if visibility == "vertices" else mesh_cull_visible
         meshes = []
         for tag, m in (("cull_rec", rec_mesh), ("cull_gt", gt_mesh)):
-            v, c, f, h, cv, cf = _mesh(m, "eval_mesh")
+            v, c, f, h, cv, cf = _mesh(m, who)
             meshes.append(cull(m, out=_own_mesh_out(tag, v.device, cv, cf, c is not None), **kw))
         rec_mesh, gt_mesh = meshes
     gt = sample_surface_counted(gt_mesh, sample_nums, seed=seed)
     rec = sample_surface_counted(rec_mesh, sample_nums, seed=int(seed) + 1 if rec_seed is None else rec_seed)
+    if distance == "surface":
+        return eval_pcd_surface(gt["points"], rec["points"], gt_mesh, rec_mesh, dist_thres, transform, gt_keep=gt["keep"], rec_keep=rec["keep"],
+                                out=out, row=row)
     return eval_pcd(gt["points"], rec["points"], dist_thres, transform, gt_keep=gt["keep"], rec_keep=rec["keep"], out=out, row=row)
 
 

@@ -484,11 +484,31 @@ class MapOperators:
         densify()'s keywords: the densified cloud, as evaluate_geometry_densified's (True: the reference's densify(1, 30, 5) of the
         stable cloud).  The sampled points and their `keep` go in as gt_points / gt_keep: one chain on the current stream from the mesh
         tensors to the [32] row, no host read.  A mesh without area gives a row of NaN.  Everything else as evaluate_geometry."""
+        return self._evaluate_geometry_mesh("evaluate_geometry_mesh", False, vertices, faces, sample_nums, seed, dist_thres, transform, out, row,
+                                            densify)
+
+    @torch.no_grad()
+    def evaluate_geometry_mesh_surface(self, vertices, faces, sample_nums=1000000, seed=0, dist_thres=(0.03,), transform=None, out=None, row=0,
+                                       densify=None):
+        """evaluate_geometry_mesh with the map's points measured to the ground-truth SURFACE (dqo_eval.eval_pcd_surface with gt_mesh):
+        accuracy and precision are the exact point-to-triangle distances from every point of the reconstruction to the mesh
+        (dqo_eval.nearest_on_mesh), free of the sampling's noise floor and of `seed`.  The map is a point cloud and has no surface, so
+        completion and recall stay evaluate_geometry_mesh's: the sampled ground-truth points to their nearest map point.  Every
+        argument and the returned float32 [32] device row are evaluate_geometry_mesh's, whose signature is pinned, so the rule is this
+        method.  The face count lies in [1, 2^25 - 1]."""
+        return self._evaluate_geometry_mesh("evaluate_geometry_mesh_surface", True, vertices, faces, sample_nums, seed, dist_thres, transform, out,
+                                            row, densify)
+
+    def _evaluate_geometry_mesh(self, who, surface, vertices, faces, sample_nums, seed, dist_thres, transform, out, row, densify):
+        """evaluate_geometry_mesh's and evaluate_geometry_mesh_surface's body."""
         gt = dqo_eval.sample_surface(vertices, faces, sample_nums, seed=seed)
         if densify is None or densify is False:
             rec, rec_keep = self.xyz.detach(), self.alive
         else:
-            rec, rec_keep = self._densified_cloud("evaluate_geometry_mesh", None if densify is True else densify)
+            rec, rec_keep = self._densified_cloud(who, None if densify is True else densify)
+        if surface:
+            return dqo_eval.eval_pcd_surface(gt["points"], rec, dict(vertices=vertices, faces=faces), None, dist_thres, transform,
+                                             gt_keep=gt["keep"], rec_keep=rec_keep, out=out, row=row)
         return dqo_eval.eval_pcd(gt["points"], rec, dist_thres, transform, gt_keep=gt["keep"], rec_keep=rec_keep, out=out, row=row)
 
     @torch.no_grad()
@@ -527,13 +547,34 @@ class MapOperators:
         return self._evaluate_mesh("evaluate_mesh_visible", mesh, gt_vertices, gt_faces, frames, depths, sample_nums, seed, dist_thres, transform,
                                    dict(eps=eps, depth_trunc=depth_trunc, min_pixels=min_pixels, visibility="faces"), out, row)
 
-    def _evaluate_mesh(self, who, mesh, gt_vertices, gt_faces, frames, depths, sample_nums, seed, dist_thres, transform, rule, out, row):
-        """evaluate_mesh's and evaluate_mesh_visible's body; rule: the cull's keywords of dqo_eval.eval_mesh's views."""
+    @torch.no_grad()
+    def evaluate_mesh_surface(self, mesh, gt_vertices, gt_faces, frames=None, depths=None, sample_nums=1000000, seed=0, dist_thres=(0.03,),
+                              transform=None, eps=0.03, min_corners=3, depth_trunc=float("inf"), out=None, row=0, visibility="vertices",
+                              min_pixels=1):
+        """evaluate_mesh / evaluate_mesh_visible with the distances taken to the SURFACE (dqo_eval.eval_mesh_surface): the same culling,
+        the same samples, but a sample is measured to the nearest FACE of the other culled mesh — the exact point-to-triangle distance of
+        dqo_eval.nearest_on_mesh — instead of the nearest sample of it, which adds about 0.5 / sqrt(samples per square metre) to accuracy
+        and completion.  visibility: "vertices" — evaluate_mesh's rule with min_corners (frames may be None: no culling) — or "faces" —
+        evaluate_mesh_visible's with min_pixels (frames required).  Every other argument and the returned float32 [32] device row are
+        evaluate_mesh's; that method's and evaluate_mesh_visible's signatures are pinned, so the rule is this method."""
+        if visibility not in ("vertices", "faces"):
+            raise ValueError(f"FusedMapper.evaluate_mesh_surface: visibility is 'vertices' or 'faces', got {visibility!r}")
+        if visibility == "faces" and frames is None:
+            raise ValueError("FusedMapper.evaluate_mesh_surface: frames is a list of raster settings: visibility='faces' needs cameras")
+        rule = dict(eps=eps, depth_trunc=depth_trunc, min_corners=min_corners) if visibility == "vertices" else \
+            dict(eps=eps, depth_trunc=depth_trunc, min_pixels=min_pixels, visibility="faces")
+        return self._evaluate_mesh("evaluate_mesh_surface", mesh, gt_vertices, gt_faces, frames, depths, sample_nums, seed, dist_thres, transform,
+                                   rule, out, row, chain=dqo_eval.eval_mesh_surface)
+
+    def _evaluate_mesh(self, who, mesh, gt_vertices, gt_faces, frames, depths, sample_nums, seed, dist_thres, transform, rule, out, row,
+                       chain=dqo_eval.eval_mesh):
+        """evaluate_mesh's, evaluate_mesh_visible's and evaluate_mesh_surface's body; rule: the cull's keywords of dqo_eval.eval_mesh's
+        views; chain: dqo_eval.eval_mesh or eval_mesh_surface."""
         gt = dict(vertices=gt_vertices, faces=gt_faces)
         if frames is None:
             if depths is not None:
                 raise ValueError(f"FusedMapper.{who}: depths belong to frames; frames=None is the evaluation without culling")
-            return dqo_eval.eval_mesh(mesh, gt, sample_nums, seed, dist_thres=dist_thres, transform=transform, out=out, row=row)
+            return chain(mesh, gt, sample_nums, seed, dist_thres=dist_thres, transform=transform, out=out, row=row)
         render = isinstance(depths, str)
         if render and depths != "render":
             raise ValueError(f"FusedMapper.{who}: depths is None, 'render' or a [K,H,W] device tensor, got {depths!r}")
@@ -542,7 +583,7 @@ class MapOperators:
         with torch.cuda.device(self.device):
             bufs, K, W, H = self._frame_views(who, frames, render)
             views = dict(w2c=bufs["w2c"], K=K, W=W, H=H, depth=bufs["depth"] if render else depths, **rule)
-            return dqo_eval.eval_mesh(mesh, gt, sample_nums, seed, dist_thres=dist_thres, transform=transform, views=views, out=out, row=row)
+            return chain(mesh, gt, sample_nums, seed, dist_thres=dist_thres, transform=transform, views=views, out=out, row=row)
 
     def _frame_views(self, who, frames, render):
         """What evaluate_mesh and evaluate_mesh_depth form from a list of raster settings (None in the list = the mapper's camera), on

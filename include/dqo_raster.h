@@ -679,6 +679,71 @@ int dqo_eval_pcd_grouped(int32_t n_gt, const float* gt_xyz, const int32_t* gt_gr
                          const int32_t* rec_group, const float* rec_xform, int32_t n_thres, const float* thres_host, float* out_table,
                          int64_t table_rows, int64_t first_row, void* workspace, size_t workspace_bytes, void* hipStream);
 
+/* dqo_mesh_nearest (ABI 5, symbols-only addition) — the nearest FACE of a mesh for every query point and the exact point-to-triangle
+ * distance to it: what dqo_nn1 is for two point sets, for a point set against a surface.  This text is the specification;
+ * tests/mesh_dist_oracle.py restates it one rounding at a time.
+ * ARITHMETIC.  All of the rule is in float32.  Every operation is rounded once, evaluated left to right and never contracted; division
+ *   is correctly rounded.  A dot product u.v is (ux*vx + uy*vy) + uz*vz.  A cross product has one rounding per product and per
+ *   difference: (u x v).x = uy*vz - uz*vy, .y = uz*vx - ux*vz, .z = ux*vy - uy*vx.
+ * VALID FACE.  A face is valid when (1) its row lies below the face count — counts[1] clamped to [0, cap_faces]; counts == NULL: the
+ *   capacity is the count —, (2) its three indices lie in [0, vertex count) (counts[0], clamped alike) and (3) with ab = b - a,
+ *   ac = c - a and n = ab x ac, the dot product n.n is finite and > 0.  A face below the count that fails (2) is counted in
+ *   faces_bad_index, any other invalid face below the count in faces_degenerate (a zero-area face holds no surface; dqo_mesh_sample
+ *   never draws from one either; a NaN or infinite corner fails (3)).  Invalid faces are never found.
+ * E(p, f): the squared distance from p to the closest point x of triangle (a, b, c), by the seven-region walk of Ericson, Real-Time
+ *   Collision Detection, 5.1.5, in this order and with these expressions:
+ *     ap = p - a, d1 = ab.ap, d2 = ac.ap;  if d1 <= 0 && d2 <= 0:  x = a                                        (region 0)
+ *     bp = p - b, d3 = ab.bp, d4 = ac.bp;  if d3 >= 0 && d4 <= d3: x = b                                        (region 1)
+ *     vc = d1*d4 - d3*d2;  if vc <= 0 && d1 >= 0 && d3 <= 0:  v = d1 / (d1 - d3), x = a + v*ab                  (region 2)
+ *     cp = p - c, d5 = ab.cp, d6 = ac.cp;  if d6 >= 0 && d5 <= d6: x = c                                        (region 3)
+ *     vb = d5*d2 - d1*d6;  if vb <= 0 && d2 >= 0 && d6 <= 0:  w = d2 / (d2 - d6), x = a + w*ac                  (region 4)
+ *     va = d3*d6 - d5*d4, e = d4 - d3, g = d5 - d6;  if va <= 0 && e >= 0 && g >= 0:  w = e / (e + g), x = b + w*(c - b)   (region 5)
+ *     otherwise  den = 1 / ((va + vb) + vc), v = vb*den, w = vc*den, x = (a + ab*v) + ac*w                      (region 6)
+ *     E = (p - x).(p - x);  if E is not finite (a 0 / 0 in a sliver's edge branch): E = ap.ap and x = a — the face stands for its corner a.
+ * D(p, f) = fmaxf(E(p, f), B(p, aabb(f))): aabb(f) is the min / max of the three corners per axis, and B the squared box distance:
+ *     per axis t: dt = 0 if lo_t <= p_t <= hi_t, else fminf(fabsf(p_t - lo_t), fabsf(p_t - hi_t));  B = (dx*dx + dy*dy) + dz*dz.
+ *   In real arithmetic B <= the squared distance, so the clamp only ever raises E by E's own rounding error (whose size relative to d^2
+ *   is unbounded as d -> 0); it is what makes the search's box pruning exact in float (csrc/knn.hip gives the argument).
+ * RESULT.  dist2[i] = the minimum of D(p_i, f) over the valid faces f, bit for bit: a pure function of the inputs, whatever the order
+ *   the search visits the faces in.  face[i] (may be NULL) is a valid face attaining it — which one of several is arbitrary, a point
+ *   over a shared edge has two.  closest (may be NULL; float [Q,3]) receives E's x for that face, recomputed once after the search.
+ *   A query whose keep byte is 0, and every query when the mesh has no valid face, gets FLT_MAX / -1 and its closest row is NOT written.
+ * query_xyz [Q,3], query_keep (NULL: every row) and query_xform / mesh_xform (NULL: identity) are dqo_nn1's: 12 floats, a row-major 3x4
+ *   transform, per output row ((m0 * x + m1 * y) + m2 * z) + m3; mesh_xform is applied to each vertex as it is loaded.
+ * The mesh is the mesh operand of dqo_mesh_components: vertices [cap_vertices,3], faces int32 [cap_faces,3], counts a DEVICE pointer to
+ *   two int32 (vertices, faces) or NULL; rows behind the counts are never read, so the header of dqo_tsdf_extract, dqo_mesh_components,
+ *   dqo_mesh_simplify or dqo_mesh_cull goes in as counts.
+ * header: int32 [8] on the device, cleared by the first launch (it must not be `counts`): 0 faces below the count, 1 valid faces,
+ *   2 faces_bad_index, 3 faces_degenerate, 4 live queries (keep byte not 0), 5..7 zero.
+ * Sizes: Q and cap_faces in [1, 2^25 - 1] (the index bits of a sorted row), cap_vertices in [1, 2^28); the size query returns 0 outside.
+ * DQO_ERR_INVALID_ARG / DQO_ERR_WORKSPACE come back before anything is launched.  No allocation, no synchronisation, nothing read
+ * back, no float atomic; the workspace needs no initialisation; capturable in a hipGraph. */
+size_t dqo_mesh_nearest_workspace_bytes(int32_t Q, int32_t cap_vertices, int32_t cap_faces);
+int dqo_mesh_nearest(int32_t Q, const float* query_xyz, const uint8_t* query_keep, const float* query_xform, const float* vertices,
+                     const int32_t* faces, const int32_t* counts, int32_t cap_vertices, int32_t cap_faces, const float* mesh_xform,
+                     float* dist2, int32_t* face, float* closest, int32_t* header, void* workspace, size_t workspace_bytes,
+                     void* hipStream);
+
+/* dqo_eval_pcd_surface (ABI 5, symbols-only addition) — dqo_eval_pcd's [32] row (the same slots, the same reduction launch, the same
+ * arithmetic per row) with the distances taken to the other side's SURFACE wherever that side has a mesh:
+ *   with a ground-truth mesh, a reconstructed point's dist2 is dqo_mesh_nearest's from that point (under rec_xform) to the gt mesh
+ *     (accuracy, precision); with a rec mesh, a ground-truth point's dist2 is dqo_mesh_nearest's to the rec mesh with its vertices under
+ *     rec_xform (completion, recall).  A side without a mesh — capacities 0, 0 and NULL buffers — keeps its dqo_nn1 search against the
+ *     other side's points, so a point-cloud reconstruction against a ground-truth mesh is exact in the one direction a surface exists.
+ *   The points of both sides are always given (a mesh's own samples: dqo_mesh_sample_counted); a mesh operand is dqo_mesh_nearest's.
+ *   A side whose mesh has no valid face makes the other side's column FLT_MAX: the row then holds 100 * sqrt(FLT_MAX) (about 1.8447e21)
+ *     as that accuracy / completion, sqrt(FLT_MAX) in the chamfer sum, 0 as that P / R and with it 0 as F1 (NaN when the other share
+ *     is 0 too) — not a row of NaN, which stays the mark of a side without a kept POINT.
+ * Row limits, thres_host, out_table / row and the workspace contract are dqo_eval_pcd's: dqo_eval_pcd_surface_workspace_bytes (0 for a
+ * bad size or capacity) bytes, ZERO when first used and then left to this call, which hands it back ready (capturable in a hipGraph). */
+size_t dqo_eval_pcd_surface_workspace_bytes(int32_t n_gt, int32_t gt_cap_vertices, int32_t gt_cap_faces, int32_t n_rec,
+                                            int32_t rec_cap_vertices, int32_t rec_cap_faces);
+int dqo_eval_pcd_surface(int32_t n_gt, const float* gt_xyz, const uint8_t* gt_keep, const float* gt_vertices, const int32_t* gt_faces,
+                         const int32_t* gt_counts, int32_t gt_cap_vertices, int32_t gt_cap_faces, int32_t n_rec, const float* rec_xyz,
+                         const uint8_t* rec_keep, const float* rec_vertices, const int32_t* rec_faces, const int32_t* rec_counts,
+                         int32_t rec_cap_vertices, int32_t rec_cap_faces, const float* rec_xform, int32_t n_thres, const float* thres_host,
+                         float* out_table, int32_t row, void* workspace, size_t workspace_bytes, void* hipStream);
+
 /* dqo_surfel_densify (ABI 5, symbols-only addition) — the point set the reference evaluates its geometry on where a config sets
  * pcd_densify: GaussianPointCloud.densify(sigma, circle_num, levels) (SLAM/gaussian_pointcloud.py:67-130; slam.py:202-206 calls
  * densify(1, 30, 5)) followed by eval_pcd's subsample (SLAM/eval.py:244), in one step that never holds the densified cloud.

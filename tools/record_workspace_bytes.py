@@ -9,10 +9,12 @@ TSDF dims, image sizes (MS-SSIM's and LPIPS' smallest sides among them), point c
 A size query added after that commit has no parent to be held to.  It goes on a second grid (_queries_since) with a table of its own,
 tests/workspace_bytes_since.json, recorded from the commit that adds it and held by that commit's own test
 (tests/test_mesh_render_abi.py); exports() names the declared queries that are NOT on the second grid, exports_since() those that are —
-so a declared query that is on neither grid still fails the first test.
+so a declared query that is on no grid still fails the first test.  The exact point-to-triangle distance's two queries are a third grid
+of the same kind (_queries_surface, tests/workspace_bytes_surface.json, held by tests/test_mesh_dist_abi.py).
 
     python tools/record_workspace_bytes.py [--lib path/to/libdqoraster.so] [--out tests/workspace_bytes_parent.json]
     python tools/record_workspace_bytes.py --since [--out tests/workspace_bytes_since.json]
+    python tools/record_workspace_bytes.py --surface [--out tests/workspace_bytes_surface.json]
 """
 import argparse
 import ctypes
@@ -85,6 +87,19 @@ def _queries_since():
     yield "dqo_eval_depth_l1_workspace_bytes", STACKS + STACKS_BAD
 
 
+SURFACE_SIZES = [1, 63, 64, 65, 1023, 1025, 4097, 70001, (1 << 25) - 1]
+SURFACE_BAD = [(0, 8, 8), (8, 0, 8), (8, 8, 0), (-1, 8, 8), (1 << 25, 8, 8), (8, 1 << 28, 8), (8, 8, 1 << 25)]
+SURFACE_SIDES = [(0, 0, 0), (1, 0, 0), (4097, 0, 0), (4097, 300, 1025), (70001, 40000, 70001), ((1 << 25) - 1, (1 << 28) - 1, (1 << 25) - 1)]
+SURFACE_SIDES_BAD = [(-1, 0, 0), (1 << 25, 0, 0), (8, 0, 5), (8, 5, 0), (8, 5, 1 << 25), (8, 1 << 28, 5)]  # (points, cap_vertices, cap_faces)
+
+
+def _queries_surface():
+    """the third grid: dqo_mesh_nearest's and dqo_eval_pcd_surface's size queries: (export, argument tuples)"""
+    yield "dqo_mesh_nearest_workspace_bytes", [(q, 1000, f) for q in SURFACE_SIZES for f in SURFACE_SIZES] + SURFACE_BAD
+    sides = [g + r for g in SURFACE_SIDES for r in SURFACE_SIDES]
+    yield "dqo_eval_pcd_surface_workspace_bytes", sides + [b + SURFACE_SIDES[1] for b in SURFACE_SIDES_BAD] + [SURFACE_SIDES[1] + b for b in SURFACE_SIDES_BAD]
+
+
 def key(name, args):
     return f"{name}({', '.join(str(a) for a in args)})"
 
@@ -106,14 +121,19 @@ def table_since(lib_path=DEFAULT_LIB):
     return table(lib_path, _queries_since)
 
 
+def table_surface(lib_path=DEFAULT_LIB):
+    """the third grid's table (tests/workspace_bytes_surface.json)"""
+    return table(lib_path, _queries_surface)
+
+
 def _declared(header_path):
     import re
     return set(re.findall(r"^size_t (dqo_\w+_bytes\w*)\(", open(header_path).read(), re.M))
 
 
 def exports(header_path=os.path.join(ROOT, "include", "dqo_raster.h")):
-    """the size queries the public header declares, less those of the second grid: the first grid must name every one of them"""
-    return sorted(_declared(header_path) - {name for name, _ in _queries_since()})
+    """the size queries the public header declares, less those of the later grids: the first grid must name every one of them"""
+    return sorted(_declared(header_path) - {name for name, _ in _queries_since()} - {name for name, _ in _queries_surface()})
 
 
 def exports_since(header_path=os.path.join(ROOT, "include", "dqo_raster.h")):
@@ -126,9 +146,11 @@ if __name__ == "__main__":
     ap.add_argument("--lib", default=DEFAULT_LIB)
     ap.add_argument("--out", default=None)
     ap.add_argument("--since", action="store_true", help="the second grid: the queries added since the parent table was recorded")
+    ap.add_argument("--surface", action="store_true", help="the third grid: the exact point-to-triangle distance's size queries")
     a = ap.parse_args()
-    t = table_since(a.lib) if a.since else table(a.lib)
-    a.out = a.out or (os.path.join(ROOT, "tests", "workspace_bytes_since.json") if a.since else DEFAULT_OUT)
+    t = table_surface(a.lib) if a.surface else table_since(a.lib) if a.since else table(a.lib)
+    a.out = a.out or (os.path.join(ROOT, "tests", "workspace_bytes_surface.json" if a.surface else "workspace_bytes_since.json")
+                      if a.surface or a.since else DEFAULT_OUT)
     with open(a.out, "w") as f:
         json.dump(t, f, indent=0, sort_keys=True)
         f.write("\n")
